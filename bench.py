@@ -33,6 +33,9 @@ utterance, passed by value at prefill).
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant decode kernel, measured live with HIP
 events on the launch stream; `cpu_baseline` times the CPU oracle (a port of the reference's
 PyTorch-CPU arithmetic) on this box's host cores: the whole configs[1] utterance, 1 warm-up + median of 3.
+
+`--dump-outputs DIR` writes what the last timed step returned (waveforms, token ids) as DIR/<name>.npy; the
+inputs depend only on the arguments, so two builds run with the same arguments can be compared file by file.
 """
 from __future__ import annotations
 
@@ -79,7 +82,43 @@ def parse():
                     help="voice-clone path (BASELINE configs[4]): every utterance first encodes a prompt wav on the GPU "
                          "(wav2vec2 + BiCodec encoder + speaker encoder), its tokens join the LLM prompt; use with --batch 8")
     ap.add_argument("--prompt-seconds", type=float, default=6.0, help="--clone: length of each synthetic prompt wav")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (waveforms, token ids) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BUDGET = 64 << 20   # bytes of .npy payload per --dump-outputs call, all ranks together
+
+
+def dump_outputs(out_dir, wav, toks, rank, world):
+    """The last timed step's results as float arrays: `wav` (B, 1, hop*Nmax) float32 as the vocoder returned it (a ragged
+    row is zero past its own length) and `tokens` (B, max row length) float64, each row's generated ids padded with -1.
+    Over this rank's share of DUMP_BUDGET the waveform is replaced by a fixed sample: `wav_sample` (values, float32) at the
+    flat indices `wav_sample_index` (float64, ascending; PCG64 seed 0).  Ranks > 0 add a `_rank<r>` suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank > 0 else ""
+    w = wav.detach().cpu().numpy().astype(np.float32)
+    t = np.full((len(toks), max(len(r) for r in toks)), -1.0, dtype=np.float64)
+    for b, r in enumerate(toks):
+        t[b, : len(r)] = r
+    arrays = {"tokens": t}
+    room = DUMP_BUDGET // world - t.nbytes
+    if w.nbytes <= room:
+        arrays["wav"] = w
+    else:
+        k = max(0, room // (4 + 8))
+        idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(w.size, size=k, replace=False))
+        arrays["wav_sample"] = w.reshape(-1)[idx]
+        arrays["wav_sample_index"] = idx.astype(np.float64)
+    files = {}
+    for name, arr in arrays.items():
+        path = os.path.join(out_dir, f"{name}{sfx}.npy")
+        np.save(path, arr)
+        files[os.path.basename(path)] = {"shape": list(arr.shape), "dtype": str(arr.dtype)}
+    return {"dir": os.path.abspath(out_dir), "files": files}
 
 
 def host_cores() -> int:
@@ -429,6 +468,7 @@ def main():
         t = torch.tensor([el], device="cpu" if one_gpu else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    dumped = dump_outputs(a.dump_outputs, wav, toks, rank, world) if a.dump_outputs else None
 
     samples_per_step = sum(want) * voc_cfg.hop
     value = world * a.steps * samples_per_step / el
@@ -461,6 +501,8 @@ def main():
                      **({"prompt_encode_all": float(np.median(enc_ms))} if enc_ms else {})},
         "first_tokens": toks[0][:8], "wav_std": float(wav.std()),
     }
+    if dumped is not None:
+        res["dump_outputs"] = dumped
 
     # ---- BASELINE configs[3]: the 256-utterance set, sharded over the ranks, batches of <= 32 per GPU (strong scaling)
     if do_cfg4:
