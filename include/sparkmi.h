@@ -168,6 +168,35 @@ int smi_llm_get_tokens(smi_llm* h, int64_t* out_host, int32_t* lens_host, int ca
  * the neighbouring bf16 value and flip a near-tie arg-max between two batch compositions. */
 int smi_llm_session_begin(smi_llm* h, const int64_t* eos_ids_host, int n_eos, void* stream);
 int smi_llm_admit(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max, int32_t* slots_out, void* stream);
+/* Per-request token selection (TensorRT-LLM's per-request temperature / runtime_top_k / runtime_top_p / random_seed inputs,
+ * runtime/triton_trtllm/model_repo/tensorrt_llm/config.pbtxt:160-251).  smi_llm_admit_sampled takes one record per prompt; the
+ * library keeps it per KV slot in device memory next to the sequence's admission number, so records of any mix ride the same
+ * captured decode step (nothing of them is a kernel argument; the step graph only knows whether SOME live row may sample).
+ *   SMI_SAMPLING_INHERIT: smi_llm_set_sampling's settings and stream, bit for bit what smi_llm_admit gives.
+ *   SMI_SAMPLING_GREEDY:  arg-max, lowest id on ties -- the greedy path's bits, even while the handle samples.
+ *   SMI_SAMPLING_SAMPLE:  this record's temperature (> 0), top_k (1..256) and top_p (0, 1].  has_seed = 1: the draws come from a
+ *                         Philox stream keyed by (seed; the sequence's own token index) alone, so its tokens do not depend on its
+ *                         slot, on what else is live or was admitted with it, on the admission order or on the handle -- the
+ *                         random_seed contract (the stream's counter carries a marker no admission number takes, so it never
+ *                         meets an inheriting row's stream).  has_seed = 0: the handle's seed and smi_llm_set_sampling's key
+ *                         (seed; admission number, token index).
+ * Other fields are ignored outside SMI_SAMPLING_SAMPLE.  params = NULL: every prompt inherits (= smi_llm_admit).  Every record
+ * is checked before anything of the handle is touched: a bad one fails the call with SMI_EINVAL and takes no slot, KV page
+ * or admission number. */
+#define SMI_SAMPLING_INHERIT 0
+#define SMI_SAMPLING_GREEDY 1
+#define SMI_SAMPLING_SAMPLE 2
+typedef struct smi_sample_params {
+  int32_t mode;          /* SMI_SAMPLING_* */
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  uint64_t seed;
+  int32_t has_seed;      /* 0 or 1 */
+  int32_t reserved;      /* 0 */
+} smi_sample_params;
+int smi_llm_admit_sampled(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
+                          const smi_sample_params* params, int32_t* slots_out, void* stream);
 int smi_llm_retire(smi_llm* h, int slot, void* stream);
 int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished, void* stream);
 /* Several sequences leave at once with no host round trip (the device row list is compacted in place), and the tokens of

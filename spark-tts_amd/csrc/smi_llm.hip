@@ -27,6 +27,7 @@
 #include "smi_common.h"
 #include <stdio.h>
 #include <string.h>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -40,6 +41,15 @@ struct RowDesc {  // 16 bytes, lives in device memory
   int32_t slot, pos, token, flags;
 };
 
+// One sequence's token selection (smi_sample_params as admitted, 32 bytes); all zero = SMI_SAMPLING_INHERIT.
+struct SampRec {
+  int32_t mode;                   // SMI_SAMPLING_*
+  int32_t top_k;                  // SAMPLE: 1..min(256, vocab)
+  float inv_temp, top_p;
+  unsigned long long seed;
+  int32_t has_seed, pad;          // has_seed: the stream is keyed by (seed; token index) alone
+};
+
 // Generation controls in device memory (written at prefill / session_begin / admit; read by k_finalize and the sampler),
 // so that nothing of them is baked into the captured decode graph: the graph survives from one utterance to the next.
 struct Ctl {
@@ -47,6 +57,7 @@ struct Ctl {
   int32_t n_eos, pad;
   unsigned long long seed;        // sampler stream key
   int32_t seqid[SMI_MAX_ROWS];    // per KV slot: admission number of the sequence living there (sampler stream key)
+  SampRec samp[SMI_MAX_ROWS];     // per KV slot: the sequence's sampling record (smi_llm_admit_sampled)
 };
 
 struct KvMap {
@@ -2781,12 +2792,14 @@ __global__ __launch_bounds__(256) void k_load_hidden(const float* src, int KT, i
 // nucleus (drop the low tail whose cumulative probability <= 1 - top_p, keep >= 1) -> softmax ->
 // one multinomial draw.  The draw uses a counter-based Philox4x32-10 stream keyed by
 // (seed; the sequence's own token index, its admission number), so a run is reproducible but not
-// bit-identical to torch.multinomial.
+// bit-identical to torch.multinomial.  What a row does comes from its slot's record (Ctl::samp): the handle's settings
+// (inherit), arg-max (greedy: the sampler kernels leave the row to k_finalize) or its own T / k / p and stream.
 // ------------------------------------------------------------------------------------------
 struct SampleP {
   const float* logits;  // [M][V]
-  int V, top_k;
+  int V, top_k;         // top_k, inv_temp, top_p: the handle's settings (rows whose record inherits)
   float inv_temp, top_p;
+  int hs;               // the handle samples (smi_llm_set_sampling(do_sample = 1))
   const Ctl* ctl;        // seed and the per-slot admission numbers
   const RowDesc* rows;   // the live rows: (slot, ..., flags = tokens this sequence has emitted so far)
   int* tok;             // [kMaxRows] sampled token per row
@@ -2816,6 +2829,34 @@ __device__ inline uint32_t philox_u32(unsigned long long seed, uint32_t c0, uint
 }
 
 constexpr int kSampleCap = 256;  // top_k upper bound
+constexpr uint32_t kSeededStream = 0xFFFFFFFFu;   // admission-number word of a seeded record's stream (admission numbers are < 2^31)
+
+__device__ __forceinline__ bool rec_samples(const SampRec& r, int hs) {
+  return r.mode == SMI_SAMPLING_SAMPLE || (r.mode == SMI_SAMPLING_INHERIT && hs);
+}
+
+// Row m's selection: on = it draws a token; its top_k / 1/T / top_p; the Philox key and the counter word beside the token index
+struct RowSel {
+  bool on;
+  int top_k;
+  float inv_temp, top_p;
+  unsigned long long seed;
+  uint32_t c1;
+};
+__device__ __forceinline__ RowSel row_sel(const SampleP& p, int m) {
+  const int sl = p.rows[m].slot;
+  const SampRec& r = p.ctl->samp[sl];
+  RowSel s;
+  s.on = rec_samples(r, p.hs);
+  const bool own = r.mode == SMI_SAMPLING_SAMPLE;
+  s.top_k = own ? r.top_k : p.top_k;
+  s.inv_temp = own ? r.inv_temp : p.inv_temp;
+  s.top_p = own ? r.top_p : p.top_p;
+  const bool seeded = own && r.has_seed;
+  s.seed = seeded ? r.seed : p.ctl->seed;
+  s.c1 = seeded ? kSeededStream : (uint32_t)p.ctl->seqid[sl];
+  return s;
+}
 constexpr int kCandCap = 1024;   // candidates at or above the threshold taken from the lm_head blocks' maxima
 
 // Exact key of the k-th largest logit by 4 passes of 8-bit radix selection (fallback path: one block walks
@@ -2860,7 +2901,8 @@ constexpr int kScanBlocks = 16;  // blocks per row in k_sample_scan
 __global__ __launch_bounds__(256) void k_sample_scan(SampleP p) {
   __shared__ float s_thr;
   const int m = blockIdx.y, tid = threadIdx.x;
-  if (!(p.pval && p.nblk <= kCandCap && p.nblk >= p.top_k)) return;   // no usable bound: k_sample selects by radix
+  const RowSel rs = row_sel(p, m);   // per row: greedy rows leave at once, and the bound path is chosen by the row's own top_k
+  if (!rs.on || !(p.pval && p.nblk <= kCandCap && p.nblk >= rs.top_k)) return;   // no usable bound: k_sample selects by radix
   // the bound, by ONE wave: each lane holds up to 16 of the (<= 1024) maxima as order-preserving keys and the answer is
   // built bit by bit from ballots (K = max{x : #{keys >= x} >= top_k}) -- no LDS, no barrier
   if (tid < 64) {
@@ -2877,7 +2919,7 @@ __global__ __launch_bounds__(256) void k_sample_scan(SampleP p) {
 #pragma unroll
       for (int i = 0; i < kCandCap / 64; ++i)
         if (i * 64 < p.nblk) c += __popcll(__ballot(key[i] >= t));   // uniform: slots beyond nblk hold no key
-      if (c >= p.top_k) K = t;   // wave-uniform
+      if (c >= rs.top_k) K = t;   // wave-uniform
     }
     if (tid == 0) s_thr = __uint_as_float((K & 0x80000000u) ? (K ^ 0x80000000u) : ~K);
   }
@@ -2926,10 +2968,12 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
   __shared__ float cv[kCandCap], sv[kSampleCap];
   __shared__ int ci[kCandCap], si[kSampleCap];
   const int m = blockIdx.x, tid = threadIdx.x;
+  const RowSel rs = row_sel(p, m);
+  if (!rs.on) return;   // greedy row: k_finalize takes its arg-max
   const float* lg = p.logits + (size_t)m * p.V;
   if (tid == 0) { s_cnt = 0; s_thr = -INFINITY; s_k = 0; }
   __syncthreads();
-  const bool bound_ok = p.pval && p.nblk <= kCandCap && p.nblk >= p.top_k;   // the condition k_sample_scan ran under
+  const bool bound_ok = p.pval && p.nblk <= kCandCap && p.nblk >= rs.top_k;   // the condition k_sample_scan ran under
   if (bound_ok) {
     if (tid == 0) { s_cnt = p.cand_n[m]; p.cand_n[m] = 0; s_thr = 0.f; }   // the counter is left at zero for the next step
     __syncthreads();
@@ -2944,7 +2988,7 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
   if (thr0 == -INFINITY || s_cnt > (unsigned)kCandCap) {
     // no usable bound (or a pathological row with > 1024 logits above it): exact radix selection of the k-th key
     __syncthreads();
-    const uint32_t thr = radix_kth_key(lg, p.V, p.top_k, hist, &s_prefix, &s_need);
+    const uint32_t thr = radix_kth_key(lg, p.V, rs.top_k, hist, &s_prefix, &s_need);
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     for (int i = tid; i < p.V; i += 1024) {
@@ -2970,7 +3014,7 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
   // every logit that ties with the k-th stays: the kept set is the sorted prefix of ranks < top_k plus the ranks behind it
   // that hold the same value (up to the kSampleCap ranks this kernel sorts)
   {
-    const int nn = n < kSampleCap ? n : kSampleCap, kb = n < p.top_k ? n : p.top_k;
+    const int nn = n < kSampleCap ? n : kSampleCap, kb = n < rs.top_k ? n : rs.top_k;
     if (tid < nn && (tid < kb || sv[tid] == sv[kb - 1])) atomicAdd(&s_k, 1);
   }
   __syncthreads();
@@ -2978,7 +3022,7 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
   {   // softmax numerators of the top-k of logits / T (fp32, like the warpers), one per thread
     const int k = ktop;
     float e = 0.f;
-    if (tid < k) e = expf(sv[tid] * p.inv_temp - sv[0] * p.inv_temp);
+    if (tid < k) e = expf(sv[tid] * rs.inv_temp - sv[0] * rs.inv_temp);
     __syncthreads();   // cv (the candidates) has been read by the rank sort
     if (tid < k) cv[tid] = e;
     __syncthreads();
@@ -3010,7 +3054,7 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
     int best = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (i0 + e >= 1 && i0 + e < k && sfx[e] + above > 1.0f - p.top_p) best = i0 + e;
+      if (i0 + e >= 1 && i0 + e < k && sfx[e] + above > 1.0f - rs.top_p) best = i0 + e;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_xor(best, d, 64); best = v > best ? v : best; }
     const int keep = best + 1;   // rank 0 always stays
@@ -3030,9 +3074,10 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
     float before = __shfl_up(q, 1, 64);
     if (tid == 0) before = 0.f;
     // one stream per SEQUENCE: (its admission number, its own token index) -- a request's draws do not depend on which
-    // row it occupies, on what else is live or on when its neighbours were admitted
+    // row it occupies, on what else is live or on when its neighbours were admitted; a seeded record: (its seed; its own
+    // token index) -- nor on the admission order or the handle
     const RowDesc rd = p.rows[m];
-    const uint32_t r = philox_u32(p.ctl->seed, (uint32_t)rd.flags, (uint32_t)p.ctl->seqid[rd.slot]);
+    const uint32_t r = philox_u32(rs.seed, (uint32_t)rd.flags, rs.c1);
     const float u = (float)(r >> 8) * (1.0f / 16777216.0f) * ksum;
     int pick = keep - 1;
 #pragma unroll
@@ -3045,7 +3090,8 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
 }
 
 struct FinP {
-  const int* tok;       // non-null: tokens already chosen by k_sample
+  const int* tok;       // non-null: tokens already chosen by k_sample for the rows that sample (rec_samples)
+  int hs;               // the handle samples
   const float* pval;
   const int* pidx;
   int nblk, M, KT, V;
@@ -3075,7 +3121,8 @@ __global__ __launch_bounds__(256) void k_finalize(FinP p) {
   const int m = blockIdx.x;
   float bv = -INFINITY;
   int bi = 0x7fffffff;
-  if (!p.tok) {
+  const bool sampled = p.tok && rec_samples(p.ctl->samp[p.rows[m].slot], p.hs);
+  if (!sampled) {   // greedy: the arg-max of the lm_head blocks' maxima, the same bits with or without the sampler in the step
     constexpr int NP = 16;   // all partial loads in flight together (one memory round trip)
     float pv[NP];
     int pi[NP];
@@ -3106,7 +3153,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinP p) {
   if (tid == 0) {
     for (int w = 1; w < 4; ++w)
       if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-    if (p.tok) bi = p.tok[m];
+    if (sampled) bi = p.tok[m];
     if ((unsigned)bi >= (unsigned)p.V) bi = 0;   // no finite logit (NaN weights / inputs): a defined token instead of an out-of-range embedding row
     tok_s = bi;
     RowDesc rd = p.rows[m];
@@ -3250,6 +3297,7 @@ struct smi_llm {
   int max_len, steps_launched;  // host-side bound on cache positions in use
   // sampling state (smi_llm_set_sampling)
   int do_sample, top_k; float temperature, top_p; unsigned long long seed;
+  int slot_samp[kMaxRows];      // host: the record of the sequence in this slot (live or being admitted) is SMI_SAMPLING_SAMPLE
   float* logits; int* tok;
   float* cand_v; int* cand_i; unsigned int* cand_n;   // sampler candidate lists
   unsigned long long* stamps; int stamps_on;
@@ -3266,14 +3314,16 @@ struct smi_llm {
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
   int gu1_lo;           // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (SPARKMI_GU1_LO; default 4)
   int gu1_rows;         // rows up to which gate_up runs its one-batch, three-tile shape (SPARKMI_GU1_ROWS; default 32)
-  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident;   // the step graph in use (owned by graph_cache)
+  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp;   // the step graph in use (owned by graph_cache)
   // every exec remembers the stream it last ran on: a caller may alternate streams, and an exec is destroyed only after THAT
   // stream has drained (graphs_flush)
   std::map<hipGraphExec_t, hipStream_t> graph_last;
-  // One captured decode step per (row count, context segments, slots-are-rows): in-flight batching changes the row count at
-  // every admission / retirement, and re-capturing the ~100-node step each time cost more than the steps saved.  Everything
-  // else a step reads is device data (row descriptors, stop ids, seed) or fixed at create; the sampler's parameters and the
-  // attention-partials buffer are kernel arguments, so a change of either empties the cache (graphs_flush).
+  // One captured decode step per (row count, context segments, slots-are-rows, some row may sample): in-flight batching changes
+  // the row count at every admission / retirement, and re-capturing the ~100-node step each time cost more than the steps saved.
+  // Everything else a step reads is device data (row descriptors, stop ids, seed, the per-slot sampling records) or fixed at
+  // create; the handle's sampler settings and the attention-partials buffer are kernel arguments, so a change of either empties
+  // the cache (graphs_flush).  The sample bit decides only whether lm_head writes the logits rows and the sampler kernels run:
+  // a step in which no row samples is the greedy step exactly.
   std::map<uint32_t, hipGraphExec_t> graph_cache;
   hipEvent_t ev0, ev1;
   // host staging
@@ -3317,6 +3367,14 @@ int pages_ensure(smi_llm* L, const int* slots, const int* tokens, int n, hipStre
   return SMI_OK;
 }
 KvMap kv_map(const smi_llm* L) { return KvMap{L->paged ? L->ptab : nullptr, L->pshift, L->ppslot}; }
+// Some row of the step may sample: the handle does, or a live / just-admitted sequence's record says SMI_SAMPLING_SAMPLE.  (An
+// over-estimate is harmless: the rows that do not sample leave the sampler kernels at once and k_finalize takes their arg-max.)
+bool samp_any(const smi_llm* L) {
+  if (L->do_sample) return true;
+  for (int sl = 0; sl < kMaxRows; ++sl)
+    if (L->slot_samp[sl]) return true;
+  return false;
+}
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
   // (one synchronise per distinct stream)
@@ -3567,7 +3625,8 @@ int eng_create(smi_llm* L) {
   return SMI_OK;
 }
 
-// the one-row step the engine stands for: one live sequence in slot 0, contiguous bf16 cache, one context segment
+// the one-row step the engine stands for: one live sequence in slot 0, contiguous bf16 cache, one context segment (its layers
+// only: lm_head, the sampler and k_finalize stay launches, so a sampling record applies to the engine's row as to any other)
 bool eng_usable(const smi_llm* L, const RowDesc* rows, int M) {
   return L->eng.enabled && L->eng_on && M == 1 && rows == L->rows && L->identity_slots && !L->paged && L->attn_seg <= 1 && !L->stamps_on;
 }
@@ -3774,7 +3833,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
       case KLM:
         p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh; p.XS = L->xs_h;
-        p.Y = logits ? logits : (L->do_sample ? L->logits : nullptr);
+        p.Y = logits ? logits : (samp_any(L) ? L->logits : nullptr);
         p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
         SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
         return launch_gemm_x<PRO_NORM, EPI_LM>(L, p, st);
@@ -3878,7 +3937,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KLM:
       p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh;
       p.XS = L->xs_h;
-      p.Y = logits ? logits : (L->do_sample ? L->logits : nullptr);
+      p.Y = logits ? logits : (samp_any(L) ? L->logits : nullptr);
       p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
       p.stamps = L->stamps_on ? L->stamps : nullptr;
       if (L->KTh <= 32) {   // persistent path: 16 rows' operand resident in the registers of a 4-wave group
@@ -3906,10 +3965,11 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KFIN: {
       FinP f;
       f.tok = nullptr;
-      if (L->do_sample) {
+      f.hs = L->do_sample;
+      if (samp_any(L)) {   // rows that do not sample leave both sampler kernels at once
         SampleP sp;
         sp.logits = L->logits; sp.V = c.vocab_size; sp.top_k = L->top_k; sp.inv_temp = 1.0f / L->temperature;
-        sp.top_p = L->top_p; sp.ctl = L->ctl; sp.rows = L->rows; sp.tok = L->tok;
+        sp.top_p = L->top_p; sp.hs = L->do_sample; sp.ctl = L->ctl; sp.rows = L->rows; sp.tok = L->tok;
         sp.pval = L->pval; sp.nblk = lm_blocks_for(L, M);
         sp.cand_v = L->cand_v; sp.cand_i = L->cand_i; sp.cand_n = L->cand_n;
         hipLaunchKernelGGL(k_sample_scan, dim3(kScanBlocks, M), dim3(256), 0, st, sp);
@@ -4238,7 +4298,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
-  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
+  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
   const size_t esz = cfg->kv_dtype ? 4 : 2;
   L->paged = cfg->kv_page_tokens > 0; L->pshift = 0; L->ppslot = 0; L->ptab = nullptr;
@@ -4514,6 +4574,8 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   }
   for (int b = 0; b < B; ++b) L->plen[b] = lens[b];
   for (int b = 0; b < kMaxRows; ++b) L->hctl.seqid[b] = b;
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));   // every sequence inherits the handle's settings
+  memset(L->slot_samp, 0, sizeof(L->slot_samp));
   L->admit_seq = B;
   { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
   SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
@@ -4542,6 +4604,8 @@ int smi_llm_session_begin(smi_llm* L, const int64_t* eos_ids, int n_eos, void* s
   SMI_REQUIRE(L, "smi_llm_session_begin: null handle");
   hipStream_t st = (hipStream_t)stream;
   memset(L->hctl.seqid, 0, sizeof(L->hctl.seqid));
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->slot_samp, 0, sizeof(L->slot_samp));
   L->admit_seq = 0;
   if (L->paged)
     for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
@@ -4581,11 +4645,47 @@ static int session_live_rows(smi_llm* L, std::vector<RowDesc>& live, hipStream_t
   return SMI_OK;
 }
 
+// Checks of the sampling records of an admission (before anything of the handle is touched, like validate_prompts).
+static int validate_sampling(const smi_sample_params* sp, int n) {
+  if (!sp) return SMI_OK;
+  for (int b = 0; b < n; ++b) {
+    const smi_sample_params& r = sp[b];
+    SMI_REQUIRE(r.mode == SMI_SAMPLING_INHERIT || r.mode == SMI_SAMPLING_GREEDY || r.mode == SMI_SAMPLING_SAMPLE,
+                "smi_llm_admit_sampled: params[%d].mode=%d is not an SMI_SAMPLING_* value", b, r.mode);
+    if (r.mode != SMI_SAMPLING_SAMPLE) continue;
+    SMI_REQUIRE(r.temperature > 0.f && std::isfinite(r.temperature), "smi_llm_admit_sampled: params[%d].temperature must be finite and > 0", b);
+    SMI_REQUIRE(r.top_k >= 1 && r.top_k <= kSampleCap, "smi_llm_admit_sampled: params[%d].top_k=%d outside 1..%d", b, r.top_k, kSampleCap);
+    SMI_REQUIRE(r.top_p > 0.f && r.top_p <= 1.f, "smi_llm_admit_sampled: params[%d].top_p must be in (0, 1]", b);
+    SMI_REQUIRE(r.has_seed == 0 || r.has_seed == 1, "smi_llm_admit_sampled: params[%d].has_seed must be 0 or 1", b);
+  }
+  return SMI_OK;
+}
+
+static SampRec samp_record(const smi_sample_params* sp, int V) {
+  SampRec r;
+  memset(&r, 0, sizeof(r));
+  if (!sp || sp->mode == SMI_SAMPLING_INHERIT) return r;
+  r.mode = sp->mode;
+  if (sp->mode != SMI_SAMPLING_SAMPLE) return r;
+  r.top_k = sp->top_k < V ? sp->top_k : V;
+  r.inv_temp = 1.0f / sp->temperature;   // the handle's settings are applied the same way (1 / T in the launch)
+  r.top_p = sp->top_p;
+  r.seed = sp->seed;
+  r.has_seed = sp->has_seed;
+  return r;
+}
+
 int smi_llm_admit(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, int32_t* slots_out, void* stream) {
+  return smi_llm_admit_sampled(L, ids, lens, n, P_max, nullptr, slots_out, stream);
+}
+
+int smi_llm_admit_sampled(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
+                          int32_t* slots_out, void* stream) {
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
   SMI_REQUIRE(n >= 1 && L->B + n <= L->cfg.max_slots && L->B + n <= kMaxRows, "smi_llm_admit: %d new + %d live sequences exceed %d slots", n,
               L->B, L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows);
+  { const int rcs = validate_sampling(params, n); if (rcs) return rcs; }   // nothing touched yet
   hipStream_t st = (hipStream_t)stream;
   int rc;
   std::vector<RowDesc> live;
@@ -4599,9 +4699,16 @@ int smi_llm_admit(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, in
   if (L->paged && (rc = pages_ensure(L, slots, lens, n, st))) return rc;   // all or nothing: a short pool admits nobody
   const int seq0 = L->admit_seq;
   int32_t old_seqid[kMaxRows];
+  SampRec old_rec[kMaxRows];
   for (int b = 0; b < n; ++b) { old_seqid[b] = L->hctl.seqid[slots[b]]; L->hctl.seqid[slots[b]] = L->admit_seq++; }
-  auto undo = [&]() {   // nothing was admitted: sequence numbers and pages as before (the device copy is rewritten by the next admission)
-    for (int b = 0; b < n; ++b) L->hctl.seqid[slots[b]] = old_seqid[b];
+  // the records go up with the sequence numbers, before the admission's own step: its finalize emits the first token
+  for (int b = 0; b < n; ++b) {
+    old_rec[b] = L->hctl.samp[slots[b]];
+    L->hctl.samp[slots[b]] = samp_record(params ? &params[b] : nullptr, L->cfg.vocab_size);
+    L->slot_samp[slots[b]] = L->hctl.samp[slots[b]].mode == SMI_SAMPLING_SAMPLE;
+  }
+  auto undo = [&]() {   // nothing was admitted: sequence numbers, records and pages as before (the device copy is rewritten by the next admission)
+    for (int b = 0; b < n; ++b) { L->hctl.seqid[slots[b]] = old_seqid[b]; L->hctl.samp[slots[b]] = old_rec[b]; L->slot_samp[slots[b]] = 0; }
     L->admit_seq = seq0;
     if (L->paged)
       for (int b = 0; b < n; ++b) pages_release(L, slots[b]);
@@ -4649,6 +4756,7 @@ int smi_llm_retire(smi_llm* L, int slot, void* stream) {
     if (live[i].slot == slot) { live.erase(live.begin() + (long)i); break; }
   L->slot_busy[slot] = 0;
   L->slot_len[slot] = 0;
+  L->slot_samp[slot] = 0;
   if (L->paged) pages_release(L, slot);   // its pages go back to the pool (stale table entries are never read: no live row names the slot)
   return session_set_rows(L, live, st);
 }
@@ -4673,6 +4781,7 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
   for (int i = 0; i < n; ++i) {
     L->slot_busy[slots[i]] = 0;
     L->slot_len[slots[i]] = 0;
+    L->slot_samp[slots[i]] = 0;
     if (L->paged) pages_release(L, slots[i]);
   }
   L->live_order = keep;
@@ -4759,14 +4868,16 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     L->attn_seg = segs_for(bound);
     if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
   }
-  if (L->cfg.use_graph && n_steps > 0 && (!L->graph || L->graph_B != L->B || L->graph_seg != L->attn_seg || L->graph_ident != L->identity_slots)) {
-    const uint32_t key = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24);
+  const int samp = samp_any(L) ? 1 : 0;
+  if (L->cfg.use_graph && n_steps > 0 && (!L->graph || L->graph_B != L->B || L->graph_seg != L->attn_seg || L->graph_ident != L->identity_slots ||
+                                          L->graph_samp != samp)) {
+    const uint32_t key = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24) | ((uint32_t)samp << 25);
     auto hit = L->graph_cache.find(key);
     L->graph = hit != L->graph_cache.end() ? hit->second : nullptr;
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp;
   }
   if (L->cfg.use_graph && n_steps > 0 && !L->graph) {
-    const uint32_t key = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24);
+    const uint32_t key = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24) | ((uint32_t)samp << 25);
     if (L->graph_cache.size() >= 192) graphs_flush(L);
     hipStream_t cs;
     SMI_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
@@ -4782,7 +4893,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     }
     (void)hipStreamDestroy(cs);
     (void)hipGetLastError();
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp;
     if (!L->graph) { smi_set_error("hipGraph capture of the decode step failed"); return SMI_EHIP; }
     L->graph_cache[key] = L->graph;
   }
@@ -4794,7 +4905,8 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
   int s0 = 0;
   if (L->cfg.use_graph && L->graph_steps > 1 && n_steps >= L->graph_steps) {
     const int K = L->graph_steps;
-    const uint32_t keyk = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24) | ((uint32_t)K << 26);
+    const uint32_t keyk = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24) | ((uint32_t)samp << 25) |
+                          ((uint32_t)K << 26);
     hipGraphExec_t gk = nullptr;
     auto hit = L->graph_cache.find(keyk);
     if (hit != L->graph_cache.end()) gk = hit->second;
@@ -5282,13 +5394,14 @@ int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint6
   }
   std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
   for (int m = 0; m < kMaxRows; ++m) { rows[m].slot = m; L->hctl.seqid[m] = m; }
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));   // every row inherits the handle's settings
   L->hctl.seed = seed;
   SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
   SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
   SampleP sp;
   sp.logits = L->logits; sp.V = V; sp.top_k = L->top_k; sp.inv_temp = 1.0f / L->temperature;
-  sp.top_p = L->top_p; sp.ctl = L->ctl; sp.rows = L->rows; sp.tok = L->tok;
+  sp.top_p = L->top_p; sp.hs = 1; sp.ctl = L->ctl; sp.rows = L->rows; sp.tok = L->tok;
   sp.pval = use_bound ? L->pval : nullptr; sp.nblk = nblk;
   sp.cand_v = L->cand_v; sp.cand_i = L->cand_i; sp.cand_n = L->cand_n;
   hipLaunchKernelGGL(k_sample_scan, dim3(kScanBlocks, n_rows), dim3(256), 0, 0, sp);

@@ -73,6 +73,15 @@ class LLMArenaTag(C.Structure):
         "max_positions", "weights_exact")] + [("reserved", C.c_int32 * 52)]
 
 # every symbol include/sparkmi.h declares: (name, restype, argtypes)
+SAMPLING_INHERIT, SAMPLING_GREEDY, SAMPLING_SAMPLE = 0, 1, 2
+
+
+class SampleParams(C.Structure):
+    """smi_sample_params: one admitted sequence's token selection (smi_llm_admit_sampled)"""
+    _fields_ = [("mode", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("seed", C.c_uint64), ("has_seed", C.c_int32), ("reserved", C.c_int32)]
+
+
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
 _P = C.POINTER
 SYMBOLS = {
@@ -90,6 +99,7 @@ SYMBOLS = {
     "smi_llm_get_tokens": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _VP]),
     "smi_llm_session_begin": (_I, [_VP, _P(C.c_int64), _I, _VP]),
     "smi_llm_admit": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _VP]),
+    "smi_llm_admit_sampled": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(SampleParams), _P(C.c_int32), _VP]),
     "smi_llm_retire": (_I, [_VP, _I, _VP]),
     "smi_llm_slot_tokens": (_I, [_VP, _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_retire_many": (_I, [_VP, _P(C.c_int32), _I, _VP]),

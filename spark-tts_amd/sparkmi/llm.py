@@ -24,6 +24,40 @@ from .config import LLMConfig
 
 
 EosLike = Union[None, int, Iterable[int]]
+# keys of a per-request sampling dict (SparkLLM.admit, generate_ragged, serve; SparkTTS.inference_batch / serve requests)
+SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p", "seed")
+
+
+def sampling_records(sampling: Optional[Sequence[Optional[Mapping]]], n: int, defaults: Mapping):
+    """One ``smi_sample_params`` per prompt, or None when every prompt inherits the handle's settings (``smi_llm_admit``).
+    ``sampling[i]`` None: inherit.  A dict: ``do_sample`` False -> greedy, else this record's own temperature / top_k / top_p
+    (keys it leaves out take ``defaults``, the handle's ``set_sampling`` values, ``do_sample`` included) and, with ``seed``
+    given, its own stream keyed by that seed and the sequence's token index alone.  Ranges are checked by the library."""
+    if sampling is None:
+        return None
+    sampling = list(sampling)
+    if len(sampling) != n:
+        raise ValueError(f"sampling: {len(sampling)} entries for {n} prompts")
+    if all(d is None for d in sampling):
+        return None
+    recs = (_lib.SampleParams * n)()
+    for i, d in enumerate(sampling):
+        if d is None:
+            continue
+        bad = set(d) - set(SAMPLING_KEYS)
+        if bad:
+            raise ValueError(f"sampling[{i}]: unknown keys {sorted(bad)} (known: {', '.join(SAMPLING_KEYS)})")
+        r = recs[i]
+        if not bool(d.get("do_sample", defaults["do_sample"])):
+            r.mode = _lib.SAMPLING_GREEDY
+            continue
+        r.mode = _lib.SAMPLING_SAMPLE
+        r.temperature = float(d.get("temperature", defaults["temperature"]))
+        r.top_k = int(d.get("top_k", defaults["top_k"]))
+        r.top_p = float(d.get("top_p", defaults["top_p"]))
+        if d.get("seed") is not None:
+            r.seed, r.has_seed = int(d["seed"]) & (2 ** 64 - 1), 1
+    return recs
 
 
 def eos_ids_from_generation_config(model_dir: Union[str, Path], cfg: Optional[LLMConfig] = None) -> List[int]:
@@ -84,6 +118,7 @@ class SparkLLM:
                 if tag.magic == b"SMIARENA":
                     self._cs.wd_plain = tag.wd_plain
         self.arena = arena  # uint8 device tensor; must outlive the handle
+        self._sampling = dict(do_sample=False, temperature=0.8, top_k=50, top_p=0.95)   # the handle's (smi_llm_create's)
         self._h = C.c_void_p()
         self._lib.check(self._lib.smi_llm_create(C.byref(self._cs), C.c_void_p(arena.data_ptr()),
                                             arena.numel(), C.byref(self._h)), "smi_llm_create")
@@ -163,6 +198,7 @@ class SparkLLM:
             seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0]) if do_sample else 0
         self._lib.check(self._lib.smi_llm_set_sampling(self._h, int(bool(do_sample)), float(temperature), int(top_k),
                                                   float(top_p), int(seed) & (2 ** 64 - 1)), "smi_llm_set_sampling")
+        self._sampling = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p))
 
     def generate_ids(self, prompts: Sequence[Sequence[int]], max_new_tokens: int,
                      eos_token_id: EosLike = None, check_every: int = 32, do_sample: bool = False,
@@ -227,8 +263,10 @@ class SparkLLM:
         eos_arr, n_eos = self._eos_args(eos_token_id)
         self._lib.check(self._lib.smi_llm_session_begin(self._h, eos_arr, n_eos, self._stream()), "smi_llm_session_begin")
 
-    def admit(self, prompts: Sequence[Sequence[int]]) -> List[int]:
-        """Prefill new prompts into free KV slots (first token emitted); returns their slot ids."""
+    def admit(self, prompts: Sequence[Sequence[int]], sampling: Optional[Sequence[Optional[Mapping]]] = None) -> List[int]:
+        """Prefill new prompts into free KV slots (first token emitted); returns their slot ids.  ``sampling``: one dict
+        (``SAMPLING_KEYS``) or None per prompt -- that sequence's own token selection (``sampling_records``); None everywhere
+        (the default): every sequence follows ``set_sampling``."""
         n = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int32)
         pmax = int(lens.max())
@@ -236,8 +274,14 @@ class SparkLLM:
         for b, p in enumerate(prompts):
             ids[b, : len(p)] = np.asarray(p, dtype=np.int64)
         slots = np.zeros(n, dtype=np.int32)
-        self._lib.check(self._lib.smi_llm_admit(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                                           n, pmax, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_admit")
+        recs = sampling_records(sampling, n, self._sampling)
+        if recs is None:
+            self._lib.check(self._lib.smi_llm_admit(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), lens.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               n, pmax, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_admit")
+        else:
+            self._lib.check(self._lib.smi_llm_admit_sampled(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs,
+                                                       slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_admit_sampled")
         return slots.tolist()
 
     def retire(self, slot: int) -> None:
@@ -284,8 +328,9 @@ class SparkLLM:
 
     def serve(self, requests, max_live: Optional[int] = None, decode_stride: int = 8):
         """In-flight batching driver: ``requests`` yields (key, prompt ids, max_new_tokens, eos id or None -- one eos for
-        the session: the first request's); yields (key, new ids) as each sequence finishes.  New requests are admitted
-        whenever a slot is free, so short utterances never wait for long ones."""
+        the session: the first request's[, sampling dict or None]); yields (key, new ids) as each sequence finishes.  New
+        requests are admitted whenever a slot is free, so short utterances never wait for long ones.  The optional fifth
+        element is that request's own token selection (``admit``); without it the request follows ``set_sampling``."""
         it = iter(requests)
         max_live = min(max_live or self.max_slots, self.max_slots)
         live = {}                      # slot -> (key, max_new)
@@ -300,7 +345,7 @@ class SparkLLM:
                 if not started:
                     self.session_begin(batch[0][3])
                     started = True
-                slots = self.admit([list(b[1]) for b in batch])
+                slots = self.admit([list(b[1]) for b in batch], [b[4] if len(b) > 4 else None for b in batch])
                 for slot, b in zip(slots, batch):
                     live[slot] = (b[0], int(b[2]))
             self.decode(decode_stride)
@@ -314,13 +359,15 @@ class SparkLLM:
                     yield key, toks[:max_new]
 
     def generate_ragged(self, prompts: Sequence[Sequence[int]], max_new_tokens: Sequence[int], eos_token_id: EosLike = None,
-                        check_every: int = 16, on_prefilled=None) -> List[List[int]]:
+                        check_every: int = 16, on_prefilled=None,
+                        sampling: Optional[Sequence[Optional[Mapping]]] = None) -> List[List[int]]:
         """One batch of prompts with PER-ROW token budgets, rows retired as they finish (their budget, or eos): the decode
         step then runs on the rows still alive instead of padding finished ones to the longest (HF ``generate`` pads; the
         reference's TensorRT-LLM deployment batches in flight, run.sh:50-65).  Rows are independent in every kernel, so
         row i's tokens are exactly those of ``generate_ids`` truncated to its budget.  The captured step of every row
         count is cached in the library, so retiring costs a row-table upload, not a graph capture.  Greedy or the
-        sampler set by ``set_sampling``; ``on_prefilled()`` is called after the prompts' prefill was enqueued."""
+        sampler set by ``set_sampling``, or per prompt by ``sampling`` (as ``admit``); ``on_prefilled()`` is called after the
+        prompts' prefill was enqueued."""
         n = len(prompts)
         want = [int(w) for w in max_new_tokens]
         if n != len(want) or n > self.max_slots or min(want) < 1:
@@ -329,7 +376,7 @@ class SparkLLM:
             raise ValueError("generate_ragged: prompt + budget exceeds max_positions")
         eos = self._eos_list(eos_token_id)
         self.session_begin(eos or None)
-        slots = self.admit([list(p) for p in prompts])
+        slots = self.admit([list(p) for p in prompts], sampling)
         if on_prefilled is not None:
             on_prefilled()
         live = {slot: i for i, slot in enumerate(slots)}

@@ -19,11 +19,17 @@ import torch
 from . import _lib
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
-from .llm import SparkLLM, eos_ids_from_generation_config
+from .llm import SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
 from .streaming import ChunkScheduler
 from .weights import load_llm_state
+
+
+def _request_sampling(r: dict) -> Optional[dict]:
+    """The sampling keys (``SAMPLING_KEYS``) a request dict carries, or None: the call-level arguments apply unchanged."""
+    d = {k: r[k] for k in SAMPLING_KEYS if k in r}
+    return d or None
 
 
 class _TokenMap:
@@ -140,7 +146,10 @@ class SparkTTS:
                         seed: Optional[int] = None) -> List[np.ndarray]:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
-        arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin)."""
+        arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
+        A request may carry its own ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` (the call's arguments
+        are the defaults of the keys it leaves out; TensorRT-LLM's per-request inputs): such a batch, even of one request,
+        runs through the admission path, so a request with its own ``seed`` gets the same tokens alone and in any batch."""
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         prompts, globals_ = [], []
@@ -169,7 +178,11 @@ class SparkTTS:
         if room < 1:
             raise ValueError(f"a prompt of {max(len(i) for i in ids)} tokens does not fit max_positions={self._max_positions}")
         max_new_tokens = min(int(max_new_tokens), room)
-        if len(ids) > 1 and self._eos and len(ids) <= self.model.max_slots:
+        sampling = [_request_sampling(r) for r in requests]
+        if any(sampling):   # (max_batch = the LLM's slots)
+            self.model.set_sampling(bool(do_sample), temperature, int(top_k), float(top_p), seed)
+            new = self.model.generate_ragged(ids, [max_new_tokens] * len(ids), self._eos, sampling=sampling)
+        elif len(ids) > 1 and self._eos and len(ids) <= self.model.max_slots:
             # a batch: rows are retired at their own eos (SparkLLM.generate_ragged), so the step runs on the rows still
             # speaking instead of padding the finished ones to the longest utterance; same tokens per row
             self.model.set_sampling(bool(do_sample), temperature, int(top_k), float(top_p), seed)
@@ -267,7 +280,8 @@ class SparkTTS:
         runtime/triton_trtllm/run.sh:50-65): ``requests`` is an iterable of the dicts ``inference_batch`` takes;
         yields ``(index, waveform)`` as each utterance finishes.  Up to ``max_batch`` utterances are live; a new
         request is admitted into the LLM's free KV slot as soon as one retires, so short utterances do not wait for
-        long ones.  Greedy results equal ``inference()`` of the same request."""
+        long ones.  Greedy results equal ``inference()`` of the same request.  Per-request ``do_sample`` / ``temperature`` /
+        ``top_k`` / ``top_p`` / ``seed`` keys as in ``inference_batch``."""
         voc = self.audio_tokenizer.model
         ntok, hop = voc.cfg.spk_token_num, voc.hop
         globals_: Dict[int, Optional[torch.Tensor]] = {}
@@ -281,7 +295,7 @@ class SparkTTS:
                     prompt, g = self.process_prompt(r["text"], r.get("prompt_speech_path"), r.get("prompt_text"), r.get("prompt_tokens"))
                 globals_[i] = g
                 ids = self.tokenizer([prompt], return_tensors="pt").input_ids[0].tolist()
-                yield i, ids, min(max_new_tokens, self._max_positions - len(ids) - decode_stride), self._eos
+                yield i, ids, min(max_new_tokens, self._max_positions - len(ids) - decode_stride), self._eos, _request_sampling(r)
 
         for i, toks in self.model.serve(llm_requests(), max_live=self._max_batch, decode_stride=decode_stride):
             stops = [toks.index(e) for e in self._eos if e in toks]
