@@ -141,3 +141,70 @@ class Qwen2Ref:
                 break
             logits = self.forward([tok], last_only=True)
         return out
+
+
+# ---------------------------------------------------------------------------- one decoder layer, stage by stage, in float64
+def rope_angles(cfg, positions) -> np.ndarray:
+    """(S, head_dim / 2) RoPE angles as MQ:81-102 forms them: inv_freq and position * inv_freq in fp32 (that rounding is part
+    of the model's definition -- the arena's table and transformers share it); cos / sin of them are taken in float64."""
+    d = cfg.head_dim
+    inv_freq = 1.0 / (cfg.rope_theta ** (torch.arange(0, d, 2, dtype=torch.float32) / d))
+    pos = torch.as_tensor(np.asarray(positions), dtype=torch.float32)
+    return (pos[:, None] * inv_freq[None, :]).numpy().astype(np.float64)
+
+
+def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.ndarray], vcache: Dict[int, np.ndarray],
+                     own_kv: bool = True) -> Dict[str, np.ndarray]:
+    """One Qwen2 decoder layer (MQ Qwen2DecoderLayer) on M caller rows, every product and sum in float64.
+
+    ``weights``: ``name -> array`` under HF names; ``rows``: (M, 2) (KV slot, position) pairs; ``x``: (M, hidden) residual rows
+    entering the layer; ``kcache`` / ``vcache``: slot -> (n, kv heads, head_dim) cached keys (already rotated) / values of
+    positions 0 .. n-1.  Row (s, p) attends to positions 0 .. p of slot s: position t is the K/V of the call's own row (s, t)
+    when there is one and ``own_kv`` is set, else ``kcache[s][t]`` (``own_kv=False``: the caches already hold the rows' K/V,
+    e.g. as a bf16 cache stored them).  Returns what ``SparkLLM.debug_layer`` returns for stages 0-4, in its layouts:
+    q (M, heads, hd), k / v (M, kv heads, hd) after bias and RoPE, attn (M, heads * hd), h_mid (M, hidden) after o_proj +
+    residual, act (M, intermediate) = silu(gate) * up, h_out (M, hidden) after down_proj + residual."""
+    p = f"model.layers.{layer}."
+    w = lambda n: np.asarray(weights[p + n], dtype=np.float64)  # noqa: E731
+    nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+    x = np.asarray(x, dtype=np.float64)
+    M = rows.shape[0]
+
+    def rms(h, g):                                                   # MQ:247-252
+        return g * (h / np.sqrt((h * h).mean(-1, keepdims=True) + cfg.rms_norm_eps))
+
+    def rope(t, ang):                                                # MQ:105-133 (rotate_half on the full head_dim)
+        c = np.cos(np.concatenate([ang, ang], -1))[:, None, :]
+        s = np.sin(np.concatenate([ang, ang], -1))[:, None, :]
+        return t * c + np.concatenate([-t[..., hd // 2:], t[..., : hd // 2]], -1) * s
+
+    xn = rms(x, w("input_layernorm.weight"))
+    q = (xn @ w("self_attn.q_proj.weight").T + w("self_attn.q_proj.bias")).reshape(M, nh, hd)
+    k = (xn @ w("self_attn.k_proj.weight").T + w("self_attn.k_proj.bias")).reshape(M, nkv, hd)
+    v = (xn @ w("self_attn.v_proj.weight").T + w("self_attn.v_proj.bias")).reshape(M, nkv, hd)
+    ang = rope_angles(cfg, rows[:, 1])
+    q, k = rope(q, ang), rope(k, ang)
+    attn = np.zeros((M, nh * hd))
+    rep = nh // nkv
+    for i, (s, pos) in enumerate(rows):                              # MQ:150-173 eager attention, GQA by repeat_kv
+        K = np.array(kcache[int(s)][: pos + 1], dtype=np.float64) if int(s) in kcache else np.zeros((0, nkv, hd))
+        V = np.array(vcache[int(s)][: pos + 1], dtype=np.float64) if int(s) in vcache else np.zeros((0, nkv, hd))
+        if own_kv:
+            K = np.concatenate([K, np.zeros((pos + 1 - len(K), nkv, hd))])
+            V = np.concatenate([V, np.zeros((pos + 1 - len(V), nkv, hd))])
+            for j, (s2, p2) in enumerate(rows):
+                if s2 == s and p2 <= pos:
+                    K[p2], V[p2] = k[j], v[j]
+        assert K.shape[0] == V.shape[0] == pos + 1, f"row {i} (slot {s}, pos {pos}): keys for {K.shape[0]} positions"
+        Kr, Vr = np.repeat(K, rep, axis=1), np.repeat(V, rep, axis=1)          # (T, nh, hd)
+        sc = np.einsum("hd,thd->ht", q[i], Kr) * hd ** -0.5
+        pr = np.exp(sc - sc.max(-1, keepdims=True))
+        pr /= pr.sum(-1, keepdims=True)
+        attn[i] = np.einsum("ht,thd->hd", pr, Vr).reshape(-1)
+    h_mid = x + attn @ w("self_attn.o_proj.weight").T
+    xn2 = rms(h_mid, w("post_attention_layernorm.weight"))
+    g = xn2 @ w("mlp.gate_proj.weight").T
+    act = g / (1.0 + np.exp(-g)) * (xn2 @ w("mlp.up_proj.weight").T)  # MQ:46-48 silu(gate) * up
+    h_out = h_mid + act @ w("mlp.down_proj.weight").T
+    return {"q": q, "k": k, "v": v, "attn": attn, "h_mid": h_mid, "act": act, "h_out": h_out}

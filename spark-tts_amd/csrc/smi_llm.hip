@@ -3336,6 +3336,25 @@ struct smi_llm {
 
 namespace {
 
+// Kernels a launch site may start with more dynamic LDS than the default 64 KiB window.  Such a site names its kernel in
+// LdsBig<kernel>::reg; the initialiser of that static member runs when the library is loaded and enters the kernel here, and
+// smi_llm_create opts every entry in to the large window on its device.  So the opt-in never happens inside a stream capture
+// (a step's first launch of k_downC<10, 4> -- 33+ rows -- may be the one in the captured decode step), and a launch does not
+// depend on what ran before it in the process.
+std::vector<const void*>& lds_big_kernels() {
+  static std::vector<const void*> v;
+  return v;
+}
+bool lds_big_register(const void* f) {
+  lds_big_kernels().push_back(f);
+  return true;
+}
+template <auto F>
+struct LdsBig {
+  static inline const bool reg = lds_big_register((const void*)F);
+};
+constexpr int kLdsBigBytes = 160 * 1024;   // the window every LdsBig kernel is opted in to
+
 // ---- paged KV cache: host-side page allocator.  A slot's row of the table lists the pages of its positions in order.
 void pages_release(smi_llm* L, int slot) {
   for (int i = 0; i < L->slot_pages[slot]; ++i) L->free_pages.push_back(L->hptab[(size_t)slot * L->ppslot + i]);
@@ -3437,19 +3456,10 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
       lds += per_wave * NW;
     }
   }
-  if (lds > 64 * 1024) {   // more than the default dynamic LDS window: opt in once per instantiation AND device
-    // (the attribute belongs to the function on one device; several handles / host threads may get here together)
-    static std::mutex mu;
-    static bool done[64] = {};
-    int dev = 0;
-    SMI_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev >= 0 && dev < 64 && !done[dev]) {
-      SMI_HIP(hipFuncSetAttribute((const void*)k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      SMI_HIP(hipFuncSetAttribute((const void*)k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      done[dev] = true;
-    }
-  }
+  // more than the default dynamic LDS window: both cache types' instantiations were opted in by smi_llm_create (LdsBig)
+  static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>>::reg);
+  static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>>::reg);
+  SMI_REQUIRE(lds <= (size_t)kLdsBigBytes, "k_gemm: %zu bytes of LDS", lds);
   const int groups = (p.M + MT * 16 - 1) / (MT * 16);   // one block row per MT*16 rows (more than one: prefill, or 17..32 rows as 2 x 16)
   SMI_REQUIRE(groups == 1 || EPI != EPI_LM, "lm_head takes at most 32 rows per launch");
   constexpr int kLean = (MT == 1 && EPI != EPI_LM) ? 1 : 0;
@@ -3764,18 +3774,9 @@ int launch_oproj(const smi_llm* L, const GemmP& p, int M, hipStream_t st) {
 // down_proj with the chains split over blocks (k_downC) and the in-order combine + RESID epilogue (k_resid_comb)
 template <int TPC, int MTN>
 int launch_down_chains_t(const smi_llm* L, const DownCP& d, hipStream_t st) {
-  const size_t lds = (size_t)TPC * 12 * (d.M < MTN * 16 ? d.M : MTN * 16) * 16;
-  if (lds > 64 * 1024) {   // opt in once per instantiation and device (as in launch_gemm_kv)
-    static std::mutex mu;
-    static bool done[64] = {};
-    int dev = 0;
-    SMI_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev >= 0 && dev < 64 && !done[dev]) {
-      SMI_HIP(hipFuncSetAttribute((const void*)k_downC<TPC, MTN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      done[dev] = true;
-    }
-  }
+  const size_t lds = (size_t)TPC * 12 * (d.M < MTN * 16 ? d.M : MTN * 16) * 16;   // > 64 KiB from 35 rows at TPC = 10
+  static_cast<void>(LdsBig<k_downC<TPC, MTN>>::reg);                               // (opted in by smi_llm_create)
+  SMI_REQUIRE(lds <= (size_t)kLdsBigBytes, "k_downC: %zu bytes of LDS", lds);
   hipLaunchKernelGGL((k_downC<TPC, MTN>), dim3(d.NT / 4 * 16), dim3(256), lds, st, d);
   SMI_LAUNCH_CHECK();
   hipLaunchKernelGGL((k_resid_comb<0, 0>), dim3(d.NT * MTN), dim3(64), 0, st, d, 16, MTN);
@@ -3895,7 +3896,6 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       if (fused) {
         p.part_o = L->part_o; p.n_oheads = c.num_heads; p.hres = L->h; p.h2out = L->h2;
         if (const char* e = smi_env("SPARKMI_FAKE_OHEADS")) p.n_oheads = atoi(e);   // TIMING ONLY (diagnostics build): gate_up reads that many partials -- wrong sums (profiles/r04_gate_up_two_tiles_and_fewer_partials.txt)
-        if (const char* e = smi_env("SPARKMI_FAKE_OHEADS")) p.n_oheads = atoi(e);   // TIMING ONLY (diagnostics build): gate_up reads that many partials -- wrong sums
         if (L->pf_inline && layer + 1 < c.num_layers && L->NTqkv % 8 == 0) {   // SPARKMI_PF_INLINE=0: off (A/B)
           p.pf2_base = sec(L, SMI_LLM_WQKV, layer + 1); p.pf2_slice = L->KTh * 1024; p.pf2_nslices = L->NTqkv;
         }
@@ -4001,18 +4001,11 @@ int launch_pgemm(const smi_llm* L, GemmP p, hipStream_t st, int nsplit = 1) {
   constexpr int rows = MTB * 16;
   const dim3 grid2((p.NT + cols - 1) / cols, (p.M + rows - 1) / rows);
   dim3 grid = XMAP ? dim3(grid2.x * grid2.y) : grid2;
-  const size_t lds = (RING ? (size_t)RING * (12 * rows + cols * 64) : (size_t)2 * 12 * rows) * 16 + (TWO ? 0 : rows * 4);
-  if (lds > 64 * 1024) {   // opt in once per instantiation and device (as in launch_gemm_kv)
-    static std::mutex mu;
-    static bool done[64] = {};
-    int dev = 0;
-    SMI_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev >= 0 && dev < 64 && !done[dev]) {
-      SMI_HIP(hipFuncSetAttribute((const void*)k_pgemm<PRO, EPI, 1, NTW, WR, RING, XMAP, TWO, MTB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      SMI_HIP(hipFuncSetAttribute((const void*)k_pgemm<PRO, EPI, 0, NTW, WR, RING, XMAP, TWO, MTB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      done[dev] = true;
-    }
+  constexpr size_t lds = (RING ? (size_t)RING * (12 * rows + cols * 64) : (size_t)2 * 12 * rows) * 16 + (TWO ? 0 : rows * 4);
+  if constexpr (lds > 64 * 1024) {   // both cache types' instantiations were opted in by smi_llm_create (LdsBig)
+    static_cast<void>(LdsBig<k_pgemm<PRO, EPI, 1, NTW, WR, RING, XMAP, TWO, MTB>>::reg);
+    static_cast<void>(LdsBig<k_pgemm<PRO, EPI, 0, NTW, WR, RING, XMAP, TWO, MTB>>::reg);
+    static_assert(lds <= (size_t)kLdsBigBytes, "k_pgemm: LDS beyond the opted-in window");
   }
   const int mtiles = (p.M + 15) / 16;
   if (nsplit > 1) {
@@ -4370,6 +4363,24 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   // handle (= per device), outside any stream capture
   if (hipFuncSetAttribute((const void*)k_lm32<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
   if (hipFuncSetAttribute((const void*)k_lm32<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+  {   // and so do the k_gemm / k_pgemm / k_downC instantiations whose launches may pass 64 KiB (LdsBig), once per device
+    static std::mutex mu;
+    static bool done[64] = {};
+    int dev = 0;
+    std::lock_guard<std::mutex> lk(mu);
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+      smi_set_error("smi_llm_create: no current device");
+      smi_llm_destroy(L);
+      return SMI_EHIP;
+    }
+    for (size_t i = 0; i < lds_big_kernels().size() && !done[dev]; ++i)
+      if (hipFuncSetAttribute(lds_big_kernels()[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBigBytes) != hipSuccess) {
+        smi_set_error("smi_llm_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(hipGetLastError()));
+        smi_llm_destroy(L);
+        return SMI_EHIP;
+      }
+    done[dev] = true;
+  }
   if (hipEventCreate(&L->ev0) != hipSuccess || hipEventCreate(&L->ev1) != hipSuccess) {
     smi_set_error("hipEventCreate failed");
     smi_llm_destroy(L);

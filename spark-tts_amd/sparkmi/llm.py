@@ -510,11 +510,11 @@ class SparkLLM:
             return {"attn": np.ascontiguousarray(t.transpose(0, 2, 1, 3)).reshape(M, Q)}
         if stage == 3:
             return {"act": self._from_triples(self.debug_read(2), c.intermediate_size, M)}
-        fused_one = stage == 2 and M == 1 and self.debug_fused_o()
+        fused_one = stage == 2 and M == 1 and int(rows[0, 0]) == 0 and self.debug_fused_o()   # (fuse_o_now: the row sits in slot 0)
         return {"h": self.debug_read(8 if fused_one else 4).view(np.float32).reshape(M, c.hidden_size)[:M].copy()}
 
     def debug_fused_o(self) -> bool:
-        """One live row takes the fused attention + o_proj kernel (smi_llm.hip: fuse_o_now) unless SPARKMI_NO_FUSE_O=1 was set
+        """One live row in slot 0 takes the fused attention + o_proj kernel (smi_llm.hip: fuse_o_now) unless SPARKMI_NO_FUSE_O=1 was set
         when the engine was built or the head count has no fused instantiation."""
         import os
         return os.environ.get("SPARKMI_NO_FUSE_O") is None and self.cfg.num_attention_heads in (4, 14)

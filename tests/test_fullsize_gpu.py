@@ -266,3 +266,127 @@ def test_config3_vocoder_batch_of_32_ragged_rows(full_voc, exact):
         o = ref.detokenize(torch.from_numpy(sem[b:b + 1, :n]), torch.from_numpy(glob[b:b + 1])).numpy()
         d = float(np.abs(wav[b, 0, : n * hop] - o[0, 0]).max())
         assert d < 3e-4, f"row {b} vs oracle: {d}"
+
+
+def test_teacher_forced_logits_at_every_position_against_the_oracle(full_llm, full_llm_oracle, golden_dir):
+    """forward_logits over a 160-token sequence (the golden prompt + 32 of its greedy tokens: 64-row chunks, 64 / 64 / 32 rows)
+    against the fp32 oracle at EVERY position, f32 KV: all four m-tiles of the step's 64-row kernels and both 32-row k_lm32 passes
+    over the 166 000-entry vocabulary are compared, not just the last row.  Per position: the oracle's top-64 logits within
+    LOGIT_ATOL and the row's |logit| sum within 1e-4 of the oracle's (as the golden test does for the last position)."""
+    from test_llm_gpu import LOGIT_ATOL
+    cfg, syn, arena = full_llm
+    g = np.load(os.path.join(golden_dir, "llm_full.npz"))
+    seq = np.concatenate([g["prompt"], g["greedy"][:32]])
+    got = _llm(cfg, arena, kv_dtype="f32").forward_logits(seq).cpu().numpy()
+    ref = full_llm_oracle
+    ref.kv_dtype = "f32"
+    ref.reset()
+    want = ref.forward(seq).numpy()
+    ref.reset()
+    assert got.shape == want.shape == (160, cfg.vocab_size)
+    top = np.argpartition(-want, 64, axis=1)[:, :64]
+    err = np.abs(np.take_along_axis(got, top, 1) - np.take_along_axis(want, top, 1)).max(axis=1)
+    bad = np.nonzero(err >= LOGIT_ATOL)[0]
+    assert bad.size == 0, f"positions {bad.tolist()[:16]}: top-64 logits off by up to {err.max():.3e}"
+    sg, sw = np.abs(got.astype(np.float64)).sum(1), np.abs(want.astype(np.float64)).sum(1)
+    rel = np.abs(sg - sw) / sw
+    assert rel.max() < 1e-4, f"position {int(rel.argmax())}: |logit| sum off by {rel.max():.2e}"
+
+
+_SESSION_CHILD = r"""
+import json, sys
+import numpy as np
+from sparkmi import config as C, weights as W
+from sparkmi.llm import SparkLLM
+# the 0.5B layer widths (hidden 896, intermediate 4864: k_downC<10, .>; 14 / 2 heads), two layers and a small vocabulary
+cfg = C.LLMConfig(vocab_size=4096, num_hidden_layers=2)
+llm = SparkLLM(cfg, W.SyntheticLLM(cfg), "cuda:0", max_slots=64, max_positions=128, kv_dtype="bf16", use_graph=True)
+rng = np.random.Generator(np.random.PCG64(3535))
+llm.session_begin()
+prompts, tokens, live, most = [], {}, {}, 0         # live: slot -> sequence index
+for group in range(12):
+    n = int(rng.integers(4, 8))                      # at most 7 prompts of at most 5 tokens: under 35 prompt rows per admission
+    new = [rng.integers(0, cfg.vocab_size, size=int(rng.integers(2, 6))).tolist() for _ in range(n)]
+    if len(live) + n > 56:
+        break
+    for slot, p in zip(llm.admit(new), new):
+        live[slot] = len(prompts)
+        prompts.append(p)
+    llm.decode(3)                                    # a step graph per live-row count: captured as the rows grow past 35
+    most = max(most, len(live))
+    if group % 3 == 2:                               # a few sequences leave: their tokens first, then their rows
+        leave = list(live)[:2]
+        for slot, (t, _) in zip(leave, llm.slots_tokens(leave, 128)):
+            tokens[live.pop(slot)] = t
+        llm.retire_many(leave)
+llm.decode(6)
+most = max(most, len(live))
+for slot, (t, _) in zip(list(live), llm.slots_tokens(list(live), 128)):
+    tokens[live[slot]] = t
+llm.close()
+one = SparkLLM(cfg, None, "cuda:0", max_slots=1, max_positions=128, kv_dtype="bf16", use_graph=True, arena=llm.arena)
+differ = [i for i in range(len(prompts)) if one.generate_ids([prompts[i]], len(tokens[i]))[0] != tokens[i]]
+print(json.dumps({"sequences": len(prompts), "most_live": most, "differ": differ}))
+"""
+
+
+def test_captured_decode_steps_past_35_live_rows_in_a_fresh_process():
+    """A decode step of 35+ live rows at the 0.5B layer widths launches k_downC<10, 4> with more than 64 KiB of LDS; the kernel
+    must be opted in to that window before ITS FIRST LAUNCH in the process, which in a session whose admissions are all small is
+    a captured decode step.  A fresh child process (nothing ran before in it; one attempt, no retry) admits groups of under 35
+    prompt rows, decodes between them and retires a few rows, until more than 40 rows are live; then every sequence, run
+    alone, must give its session tokens."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, os.path.join(root, "spark-tts_amd")]))
+    r = subprocess.run([sys.executable, "-c", _SESSION_CHILD], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, f"child exited with {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert 40 <= out["most_live"] <= 64 and out["sequences"] >= 45, out
+    assert out["differ"] == [], f"sequences whose session tokens differ from their solo run: {out['differ']}"
+
+
+def _group_case(cfg, arena, prompts, kv, n=4):
+    """Every sequence of one call against its solo run: tokens, and the K and V rows of layer 0 and of the last layer (prompt and
+    generated positions), bit for bit."""
+    from sparkmi.llm import SparkLLM
+    mk = lambda slots: SparkLLM(cfg, None, "cuda:0", max_slots=slots, max_positions=FULL_MAX_POS, arena=arena, kv_dtype=kv, diag=True)  # noqa: E731
+    layers = (0, cfg.num_hidden_layers - 1)
+    big = mk(len(prompts))
+    batched = big.generate_ids(prompts, n)
+    kv_big = {b: [big.debug_get_kv(layer, b, 0, len(p) + n - 1) for layer in layers] for b, p in enumerate(prompts)}
+    big.close()
+    one = mk(1)
+    for b, p in enumerate(prompts):
+        assert one.generate_ids([p], n)[0] == batched[b], f"sequence {b} ({len(p)} tokens, {kv} KV): tokens in the call vs alone"
+        for i, layer in enumerate(layers):
+            k, v = one.debug_get_kv(layer, 0, 0, len(p) + n - 1)
+            assert np.array_equal(k, kv_big[b][i][0]), f"sequence {b} ({kv} KV), layer {layer}: K rows differ from its solo run"
+            assert np.array_equal(v, kv_big[b][i][1]), f"sequence {b} ({kv} KV), layer {layer}: V rows differ from its solo run"
+
+
+@pytest.mark.parametrize("kv", ["f32", "bf16"])
+@pytest.mark.parametrize("count", [6, 7])
+def test_prefill_pass_beyond_one_4096_row_group(full_llm, kv, count):
+    """Prompts of 690 tokens (689 rows each, the prefill GEMM family) whose pass exceeds one 4096-row group: 6 prompts (4134 rows:
+    the 6th straddles row 4096 at its own position 651, no multiple of 16, and its 38-row tail is a group of its own) and 7 (4823
+    rows: the tail group holds 727 rows).  Each sequence's tokens and K / V rows equal its solo run's (include/sparkmi.h: a
+    sequence's K/V rows and tokens do not depend on the rest of the call)."""
+    cfg, syn, arena = full_llm
+    rng = np.random.Generator(np.random.PCG64(690 + count))
+    prompts = [rng.integers(0, cfg.vocab_size, size=690).tolist() for _ in range(count)]
+    assert sum(len(p) - 1 for p in prompts) > 4096
+    _group_case(cfg, arena, prompts, kv)
+
+
+@pytest.mark.parametrize("kv", ["f32", "bf16"])
+@pytest.mark.parametrize("lens", [(257, 257), (257, 258)], ids=["512rows", "513rows"])
+def test_prefill_pass_at_the_few_row_boundary(full_llm, kv, lens):
+    """Two prompts of the prefill GEMM family whose pass holds 512 rows (kPgSplitRows: the few-row shapes and split-K o_proj /
+    down_proj) or 513 (the many-row shapes); alone each takes the few-row shapes.  Tokens and K / V rows equal the solo runs'."""
+    cfg, syn, arena = full_llm
+    rng = np.random.Generator(np.random.PCG64(sum(lens)))
+    prompts = [rng.integers(0, cfg.vocab_size, size=L).tolist() for L in lens]
+    _group_case(cfg, arena, prompts, kv)

@@ -91,3 +91,39 @@ def test_full_size_golden_is_present(golden_dir):
     g = np.load(os.path.join(golden_dir, "llm_full.npz"))
     assert g["prompt"].shape == (128,) and g["greedy"].shape == (150,)
     assert g["last_top_ids"].shape == (64,)
+
+
+def test_float64_layer_stages_match_transformers_classes(golden_dir):
+    """oracle.llm_ref.layer_stages_f64 -- the reference of tests/test_llm_ops_full_gpu.py -- against tests/golden/llm_ops.npz, which
+    transformers' own Qwen2RMSNorm / Qwen2Attention / apply_rotary_pos_emb / eager_attention_forward / Qwen2MLP produced (fp32):
+    every stage of the fixture's five rows (three slots, two consecutive rows of one slot) within 2e-6 of that stage's scale."""
+    from oracle.llm_ref import layer_stages_f64
+    g = np.load(os.path.join(golden_dir, "llm_ops.npz"))
+    cfg = C.LLMConfig(vocab_size=64, hidden_size=256, num_hidden_layers=1, num_attention_heads=4, num_key_value_heads=2,
+                      intermediate_size=608, rope_theta=1000000.0, rms_norm_eps=1e-6)
+    w = {"model.layers.0.input_layernorm.weight": g["ln1"], "model.layers.0.post_attention_layernorm.weight": g["ln2"]}
+    for k in g.files:
+        if k.startswith("attn/"):
+            w["model.layers.0.self_attn." + k[5:]] = g[k]
+        elif k.startswith("mlp/"):
+            w["model.layers.0.mlp." + k[4:]] = g[k]
+    kc = {s: g[f"kcache{s}"].transpose(1, 0, 2) for s in range(3)}
+    vc = {s: g[f"vcache{s}"].transpose(1, 0, 2) for s in range(3)}
+    got = layer_stages_f64(cfg, w, 0, g["rows"], g["x"], kc, vc)
+    for mine, theirs in (("q", "q_rot"), ("k", "k_rot"), ("v", "v"), ("attn", "attn_out"), ("h_mid", "h_mid"), ("act", "act"),
+                         ("h_out", "h_out")):
+        want = g[theirs].astype(np.float64)
+        assert got[mine].shape == want.shape, mine
+        err, scale = float(np.abs(got[mine] - want).max()), float(np.abs(want).max())
+        assert err <= 2e-6 * scale, f"{mine}: max |diff| {err:.3e} against scale {scale:.3f}"
+    # own_kv=False reads the rows' K/V from the caches: with the caches extended by the reference's own rows, the same numbers
+    ext_k, ext_v = {}, {}
+    for s in range(3):
+        n = max(p for s2, p in g["rows"] if s2 == s) + 1
+        ext_k[s] = np.concatenate([kc[s], np.zeros((n - kc[s].shape[0], 2, 64))])
+        ext_v[s] = np.concatenate([vc[s], np.zeros((n - vc[s].shape[0], 2, 64))])
+    for j, (s, p) in enumerate(g["rows"]):
+        ext_k[s][p], ext_v[s][p] = got["k"][j], got["v"][j]
+    again = layer_stages_f64(cfg, w, 0, g["rows"], g["x"], ext_k, ext_v, own_kv=False)
+    for key in ("attn", "h_mid", "act", "h_out"):
+        assert np.array_equal(again[key], got[key]), key
