@@ -197,6 +197,33 @@ typedef struct smi_sample_params {
 } smi_sample_params;
 int smi_llm_admit_sampled(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
                           const smi_sample_params* params, int32_t* slots_out, void* stream);
+/* Per-request logits penalties (TensorRT-LLM's per-request repetition_penalty / presence_penalty / frequency_penalty /
+ * min_length inputs).  smi_llm_admit_penalized = smi_llm_admit_sampled plus one penalty record per prompt (pens = NULL: exactly
+ * smi_llm_admit_sampled), kept per KV slot in device memory like the sampling record.  Before token selection, a penalised
+ * row's fp32 logits x go through, in this order:
+ *   1. repetition_penalty r > 0 (transformers' RepetitionPenaltyLogitsProcessor): every id of the row's history becomes
+ *      x < 0 ? x * r : x / r (IEEE fp32 product / quotient, once per distinct id).  History = prompt + generated tokens with
+ *      penalize_prompt = 1 (transformers' default), the generated tokens alone with 0 (its prompt_ignore_length = len(prompt);
+ *      what voice cloning wants: the prompt holds the reference clip's semantic tokens).
+ *   2. presence_penalty p and frequency_penalty f in [-2, 2] (the OpenAI / vLLM additive form): with c = occurrences of the id
+ *      among the GENERATED tokens, x - (f * c + p * (c > 0 ? 1 : 0)), each operation fp32, in this order.
+ *   3. min_new_tokens n (transformers' MinNewTokensLengthLogitsProcessor): every id of the session's eos list is -inf while the
+ *      sequence has emitted fewer than n tokens (the first token, emitted by the admission, is token 0).
+ *   4. selection as without penalties, on the processed logits: arg-max (lowest id on ties), or temperature -> top-k -> top-p
+ *      -> draw (transformers' processors-before-warpers order).
+ * A record with r = 1, p = f = 0 and n = 0 is neutral: that row is not penalised and its tokens are the bits it gets without
+ * the record.  Checked before anything of the handle is touched (SMI_EINVAL, no slot, page or admission number taken):
+ * r finite and > 0, p and f finite in [-2, 2], 0 <= n <= max_positions, penalize_prompt 0 or 1, reserved 0. */
+typedef struct smi_penalty_params {
+  float repetition_penalty;    /* r; 1 = off */
+  float presence_penalty;      /* p; 0 = off */
+  float frequency_penalty;     /* f; 0 = off */
+  int32_t min_new_tokens;      /* n; 0 = off */
+  int32_t penalize_prompt;     /* 0 or 1 */
+  int32_t reserved[3];         /* 0 */
+} smi_penalty_params;
+int smi_llm_admit_penalized(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
+                            const smi_sample_params* params, const smi_penalty_params* pens, int32_t* slots_out, void* stream);
 int smi_llm_retire(smi_llm* h, int slot, void* stream);
 int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished, void* stream);
 /* Several sequences leave at once with no host round trip (the device row list is compacted in place), and the tokens of

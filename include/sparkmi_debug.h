@@ -83,6 +83,14 @@ int smi_llm_debug_raw_stamps(smi_llm* h, unsigned long long* out, int n);
  * (block j = the j-th contiguous share of the row, as many blocks as the lm_head launch of n_rows rows leaves); 0: the exact
  * radix selection.  Parameters come from smi_llm_set_sampling.  Synchronises; ends the current generation. */
 int smi_llm_debug_sample(smi_llm* h, const float* logits_host, int n_rows, uint64_t seed, int use_bound, int32_t* tokens_out);
+/* Tests: the penalty kernel alone (k_penalize, as a step launches it for n_rows rows, n_rows <= max_slots) on caller rows:
+ * logits_host [n_rows][vocab_size], hist_host [n_rows][vocab_size] history entries (bit 15: the id is in the prompt, bits 0..14:
+ * its count among the generated tokens), pens [n_rows] records (smi_llm_admit_penalized's checks), emitted_host [n_rows]
+ * tokens each row has emitted; eos ids: the last smi_llm_session_begin's.  logits_out [n_rows][vocab_size]: the processed rows;
+ * argmax_out [n_rows]: the arg-max over the per-set maxima the kernel leaves for k_finalize.  Synchronises; ends the current
+ * generation. */
+int smi_llm_debug_penalize(smi_llm* h, const float* logits_host, int n_rows, const uint16_t* hist_host, const smi_penalty_params* pens,
+                           const int32_t* emitted_host, float* logits_out, int32_t* argmax_out);
 
 #ifdef __cplusplus
 }

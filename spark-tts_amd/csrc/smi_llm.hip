@@ -50,6 +50,14 @@ struct SampRec {
   int32_t has_seed, pad;          // has_seed: the stream is keyed by (seed; token index) alone
 };
 
+// One sequence's logits penalties (smi_penalty_params as admitted, 24 bytes); on = 0 (all zero): not penalised.
+struct PenRec {
+  float rep, pres, freq;          // repetition / presence / frequency penalty
+  int32_t min_new;                // eos ids are -inf while fewer tokens than this have been emitted
+  int32_t prompt;                 // the prompt ids count for the repetition penalty
+  int32_t on;                     // the record is not neutral: k_penalize processes the row, k_finalize counts its tokens
+};
+
 // Generation controls in device memory (written at prefill / session_begin / admit; read by k_finalize and the sampler),
 // so that nothing of them is baked into the captured decode graph: the graph survives from one utterance to the next.
 struct Ctl {
@@ -58,6 +66,7 @@ struct Ctl {
   unsigned long long seed;        // sampler stream key
   int32_t seqid[SMI_MAX_ROWS];    // per KV slot: admission number of the sequence living there (sampler stream key)
   SampRec samp[SMI_MAX_ROWS];     // per KV slot: the sequence's sampling record (smi_llm_admit_sampled)
+  PenRec pen[SMI_MAX_ROWS];       // per KV slot: the sequence's penalty record (smi_llm_admit_penalized)
 };
 
 struct KvMap {
@@ -3089,9 +3098,101 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Logits penalties (smi_llm_admit_penalized; include/sparkmi.h states the semantics).  Per KV slot a history row
+// uint16 [vocab]: bit 15 = the id is in the prompt, bits 0..14 = its count among the generated tokens (k_finalize adds one per
+// token; 32 767 > max_positions, so it cannot saturate).  k_penalize runs between the lm_head and the sampler / k_finalize,
+// on the logits rows the lm_head wrote: a penalised row's logits are processed (written back only when the row samples) and its
+// nblk (value, id) maxima are rebuilt over the kernel's own partition of the vocabulary (set j = ids [j * per, (j + 1) * per)).
+// k_finalize's arg-max and k_sample_scan's top-k bound hold for ANY partition into nblk disjoint sets; unpenalised rows leave
+// at once and keep the lm_head's own maxima, so their bits do not change.
+// ------------------------------------------------------------------------------------------
+constexpr int kPenWaves = 4;   // sets per block: one wave per set
+
+struct PenP {
+  float* logits;          // [M][V] the lm_head's logits rows
+  const uint16_t* hist;   // [max_slots][V]
+  const Ctl* ctl;         // per-slot records, eos ids
+  const RowDesc* rows;
+  float* pval;            // [M][nblk]
+  int* pidx;
+  int V, nblk, per;       // per: ids per set, a multiple of 4 (per * nblk >= V)
+  int hs;                 // the handle samples
+};
+
+// stages 1..3 on one logit (fp32, each operation rounded on its own: the build compiles with -ffp-contract=off)
+__device__ __forceinline__ float pen_logit(float x, uint32_t h, const PenRec& r, bool mask, int id, const int* eos) {
+  const uint32_t c = h & 0x7fffu;
+  if (c || (r.prompt && (h & 0x8000u))) x = x < 0.f ? x * r.rep : x / r.rep;
+  x = x - (r.freq * (float)c + r.pres * (c ? 1.f : 0.f));
+  if (mask) {
+#pragma unroll
+    for (int e = 0; e < SMI_MAX_EOS; ++e)
+      if (id == eos[e]) x = -INFINITY;
+  }
+  return x;
+}
+
+__device__ __forceinline__ void pen_best(float v, int i, float& bv, int& bi) {
+  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+}
+
+// grid (ceil(nblk / kPenWaves), M) x 256: wave w of block x owns set x * kPenWaves + w of row blockIdx.y.  No barrier: a wave
+// reads its set's logits and history entries once (float4 + 4 x uint16 when V % 4 == 0: sets start at multiples of 4), writes
+// them back processed if the row samples, and leaves one (maximum, lowest id) pair.
+__global__ __launch_bounds__(256) void k_penalize(PenP p) {
+  const int m = blockIdx.y;
+  const RowDesc rd = p.rows[m];
+  const PenRec r = p.ctl->pen[rd.slot];
+  if (!r.on) return;   // not penalised: the lm_head's maxima stand
+  const int lane = threadIdx.x & 63, set = blockIdx.x * kPenWaves + (threadIdx.x >> 6);
+  if (set >= p.nblk) return;
+  const bool wb = rec_samples(p.ctl->samp[rd.slot], p.hs);   // the sampler reads the logits; k_finalize only the maxima
+  const bool mask = rd.flags < r.min_new;
+  int eos[SMI_MAX_EOS];
+#pragma unroll
+  for (int e = 0; e < SMI_MAX_EOS; ++e) eos[e] = e < p.ctl->n_eos ? (int)p.ctl->eos[e] : -1;
+  float* lg = p.logits + (size_t)m * p.V;
+  const uint16_t* hs = p.hist + (size_t)rd.slot * p.V;
+  const int i0 = set * p.per, i1 = min(i0 + p.per, p.V);
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  if ((p.V & 3) == 0) {   // i1 - i0 is a multiple of 4: every float4 / uint2 lies inside the set and is aligned
+    for (int i = i0 + 4 * lane; i < i1; i += 256) {
+      float4 x = *(const float4*)(lg + i);
+      const uint2 hh = *(const uint2*)(hs + i);
+      x.x = pen_logit(x.x, hh.x & 0xffffu, r, mask, i, eos);
+      x.y = pen_logit(x.y, hh.x >> 16, r, mask, i + 1, eos);
+      x.z = pen_logit(x.z, hh.y & 0xffffu, r, mask, i + 2, eos);
+      x.w = pen_logit(x.w, hh.y >> 16, r, mask, i + 3, eos);
+      if (wb) *(float4*)(lg + i) = x;
+      pen_best(x.x, i, bv, bi); pen_best(x.y, i + 1, bv, bi); pen_best(x.z, i + 2, bv, bi); pen_best(x.w, i + 3, bv, bi);
+    }
+  } else {
+    for (int i = i0 + lane; i < i1; i += 64) {
+      const float x = pen_logit(lg[i], hs[i], r, mask, i, eos);
+      if (wb) lg[i] = x;
+      pen_best(x, i, bv, bi);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) pen_best(__shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64), bv, bi);
+  if (lane == 0) {
+    p.pval[(size_t)m * p.nblk + set] = bv;   // an empty set (per * nblk > V): (-inf, no id), below every real entry
+    p.pidx[(size_t)m * p.nblk + set] = bi;
+  }
+}
+
+// admission of penalised prompts: idx[i] = slot * V + id for every prompt token of a record that penalises its prompt
+__global__ __launch_bounds__(256) void k_pen_prompt(uint16_t* hist, const int32_t* idx, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) hist[idx[i]] = 0x8000;   // (plain stores: duplicate ids write the same value; the row was zeroed before)
+}
+
 struct FinP {
   const int* tok;       // non-null: tokens already chosen by k_sample for the rows that sample (rec_samples)
   int hs;               // the handle samples
+  uint16_t* phist;      // non-null (some row is penalised): penalised rows count their token in their slot's history row
   const float* pval;
   const int* pidx;
   int nblk, M, KT, V;
@@ -3160,6 +3261,10 @@ __global__ __launch_bounds__(256) void k_finalize(FinP p) {
     const int step = rd.flags;                 // tokens this row has emitted so far
     const int sl = rd.slot;                    // history / counters live per KV slot (== m outside sessions)
     if (step < p.max_steps) p.hist[(size_t)step * kMaxRows + sl] = bi;
+    if (p.phist && p.ctl->pen[sl].on) {   // one writer per slot: no atomics
+      uint16_t& e = p.phist[(size_t)sl * p.V + bi];
+      if ((e & 0x7fffu) != 0x7fffu) e = (uint16_t)(e + 1);
+    }
     if (!p.finished[sl]) {
       p.count[sl] = step + 1;
       bool stop = false;   // HF generate(): any id of generation_config.eos_token_id ends the sequence
@@ -3298,6 +3403,10 @@ struct smi_llm {
   // sampling state (smi_llm_set_sampling)
   int do_sample, top_k; float temperature, top_p; unsigned long long seed;
   int slot_samp[kMaxRows];      // host: the record of the sequence in this slot (live or being admitted) is SMI_SAMPLING_SAMPLE
+  int slot_pen[kMaxRows];       // host: the sequence in this slot (live or being admitted) has a penalty record (PenRec::on)
+  uint16_t* phist;              // penalty histories [max_slots][vocab] (k_penalize, k_finalize)
+  int32_t* pen_idx; size_t pen_idx_cap;   // admission: slot * vocab + id of the prompt tokens whose bit k_pen_prompt sets
+  std::vector<int32_t> host_pen_idx;
   float* logits; int* tok;
   float* cand_v; int* cand_i; unsigned int* cand_n;   // sampler candidate lists
   unsigned long long* stamps; int stamps_on;
@@ -3314,17 +3423,19 @@ struct smi_llm {
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
   int gu1_lo;           // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (SPARKMI_GU1_LO; default 4)
   int gu1_rows;         // rows up to which gate_up runs its one-batch, three-tile shape (SPARKMI_GU1_ROWS; default 32)
-  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp;   // the step graph in use (owned by graph_cache)
+  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen;   // the step graph in use (owned by graph_cache)
   // every exec remembers the stream it last ran on: a caller may alternate streams, and an exec is destroyed only after THAT
   // stream has drained (graphs_flush)
   std::map<hipGraphExec_t, hipStream_t> graph_last;
-  // One captured decode step per (row count, context segments, slots-are-rows, some row may sample): in-flight batching changes
+  // One captured decode step per (row count, context segments, slots-are-rows, some row may sample, some row is penalised,
+  // steps per replay): in-flight batching changes
   // the row count at every admission / retirement, and re-capturing the ~100-node step each time cost more than the steps saved.
   // Everything else a step reads is device data (row descriptors, stop ids, seed, the per-slot sampling records) or fixed at
   // create; the handle's sampler settings and the attention-partials buffer are kernel arguments, so a change of either empties
   // the cache (graphs_flush).  The sample bit decides only whether lm_head writes the logits rows and the sampler kernels run:
-  // a step in which no row samples is the greedy step exactly.
-  std::map<uint32_t, hipGraphExec_t> graph_cache;
+  // a step in which no row samples is the greedy step exactly.  Likewise the penalty bit only adds the logits rows and
+  // k_penalize: a step in which no row is penalised is the step without penalties exactly.
+  std::map<uint64_t, hipGraphExec_t> graph_cache;
   hipEvent_t ev0, ev1;
   // host staging
   std::vector<RowDesc> host_rows;
@@ -3393,6 +3504,17 @@ bool samp_any(const smi_llm* L) {
   for (int sl = 0; sl < kMaxRows; ++sl)
     if (L->slot_samp[sl]) return true;
   return false;
+}
+// Some live / just-admitted row has a penalty record: lm_head writes the logits rows and k_penalize runs.
+bool pen_any(const smi_llm* L) {
+  for (int sl = 0; sl < kMaxRows; ++sl)
+    if (L->slot_pen[sl]) return true;
+  return false;
+}
+// the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | sample << 25 | penalty << 26 | steps per replay << 32
+uint64_t graph_key(const smi_llm* L, int samp, int pen, int K) {
+  return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)samp << 25) |
+         ((uint64_t)pen << 26) | ((uint64_t)K << 32);
 }
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
@@ -3702,6 +3824,9 @@ int lm_blocks_for(const smi_llm* L, int M) {
   return M <= 16 ? L->lm_blocks : (L->lm_blocks < 256 ? L->lm_blocks : 256);
 }
 
+// ids per set of k_penalize's partition of a row into nblk sets: a multiple of 4 (aligned float4 sets)
+int pen_set_ids(int V, int nblk) { return ((V + nblk - 1) / nblk + 3) & ~3; }
+
 int segs_for(int ctx_bound) { return ctx_bound <= kAttnSeg ? 1 : (ctx_bound + kAttnSeg - 1) / kAttnSeg; }
 
 // attention (+ the segment merge when the context bound of the current call exceeds one segment)
@@ -3834,7 +3959,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
       case KLM:
         p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh; p.XS = L->xs_h;
-        p.Y = logits ? logits : (samp_any(L) ? L->logits : nullptr);
+        p.Y = logits ? logits : (samp_any(L) || pen_any(L) ? L->logits : nullptr);
         p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
         SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
         return launch_gemm_x<PRO_NORM, EPI_LM>(L, p, st);
@@ -3937,7 +4062,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KLM:
       p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh;
       p.XS = L->xs_h;
-      p.Y = logits ? logits : (samp_any(L) ? L->logits : nullptr);
+      p.Y = logits ? logits : (samp_any(L) || pen_any(L) ? L->logits : nullptr);
       p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
       p.stamps = L->stamps_on ? L->stamps : nullptr;
       if (L->KTh <= 32) {   // persistent path: 16 rows' operand resident in the registers of a 4-wave group
@@ -3966,6 +4091,15 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       FinP f;
       f.tok = nullptr;
       f.hs = L->do_sample;
+      f.phist = nullptr;
+      if (pen_any(L)) {   // unpenalised rows leave k_penalize at once
+        PenP pp;
+        pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
+        pp.V = c.vocab_size; pp.nblk = lm_blocks_for(L, M); pp.per = pen_set_ids(pp.V, pp.nblk); pp.hs = L->do_sample;
+        hipLaunchKernelGGL(k_penalize, dim3((pp.nblk + kPenWaves - 1) / kPenWaves, M), dim3(256), 0, st, pp);
+        SMI_LAUNCH_CHECK();
+        f.phist = L->phist;
+      }
       if (samp_any(L)) {   // rows that do not sample leave both sampler kernels at once
         SampleP sp;
         sp.logits = L->logits; sp.V = c.vocab_size; sp.top_k = L->top_k; sp.inv_temp = 1.0f / L->temperature;
@@ -4291,7 +4425,8 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
-  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
+  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
+  L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
   const size_t esz = cfg->kv_dtype ? 4 : 2;
   L->paged = cfg->kv_page_tokens > 0; L->pshift = 0; L->ppslot = 0; L->ptab = nullptr;
@@ -4336,6 +4471,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
     SMI_HIP(hipMemset(L->ptab, 0, L->hptab.size() * 4));
   }
   SMI_ALLOC(L->logits, (size_t)kMaxRows * cfg->vocab_size * 4);
+  SMI_ALLOC(L->phist, (size_t)cfg->max_slots * cfg->vocab_size * 2);   // (a penalised admission zeroes its slot's row)
   SMI_ALLOC(L->tok, kMaxRows * 4);
   SMI_ALLOC(L->cand_v, (size_t)kMaxRows * kCandCap * 4);
   SMI_ALLOC(L->cand_i, (size_t)kMaxRows * kCandCap * 4);
@@ -4410,7 +4546,8 @@ int smi_llm_destroy(smi_llm* L) {
   graphs_flush(L);
   eng_destroy(L);
   void* ptrs[] = {L->h, L->qbuf, L->xs_h, L->xs_attn, L->xs_act, L->sspart, L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
-                  L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab, L->apart};
+                  L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab, L->apart,
+                  L->phist, L->pen_idx};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (L->ev0) (void)hipEventDestroy(L->ev0);
@@ -4587,6 +4724,8 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   for (int b = 0; b < kMaxRows; ++b) L->hctl.seqid[b] = b;
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));   // every sequence inherits the handle's settings
   memset(L->slot_samp, 0, sizeof(L->slot_samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));     // and has no penalties
+  memset(L->slot_pen, 0, sizeof(L->slot_pen));
   L->admit_seq = B;
   { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
   SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
@@ -4617,6 +4756,8 @@ int smi_llm_session_begin(smi_llm* L, const int64_t* eos_ids, int n_eos, void* s
   memset(L->hctl.seqid, 0, sizeof(L->hctl.seqid));
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
   memset(L->slot_samp, 0, sizeof(L->slot_samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  memset(L->slot_pen, 0, sizeof(L->slot_pen));
   L->admit_seq = 0;
   if (L->paged)
     for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
@@ -4686,17 +4827,77 @@ static SampRec samp_record(const smi_sample_params* sp, int V) {
   return r;
 }
 
+// The history rows of an admission's penalised sequences, before their first step: zeroed, then the prompt bits (records that
+// penalise their prompt).  Rows without a record are never touched.
+static int pen_histories(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* slots, hipStream_t st) {
+  const size_t V = (size_t)L->cfg.vocab_size;
+  std::vector<int32_t>& idx = L->host_pen_idx;
+  idx.clear();
+  for (int b = 0; b < n; ++b) {
+    const PenRec& r = L->hctl.pen[slots[b]];
+    if (!r.on) continue;
+    SMI_HIP(hipMemsetAsync(L->phist + (size_t)slots[b] * V, 0, V * 2, st));
+    if (r.prompt)
+      for (int t = 0; t < lens[b]; ++t) idx.push_back((int32_t)((size_t)slots[b] * V + (size_t)ids[(size_t)b * P_max + t]));
+  }
+  if (idx.empty()) return SMI_OK;
+  if (idx.size() > L->pen_idx_cap) {
+    if (L->pen_idx) (void)hipFree(L->pen_idx);
+    L->pen_idx = nullptr; L->pen_idx_cap = 0;
+    const size_t cap = idx.size() + 4096;
+    if (hipMalloc((void**)&L->pen_idx, cap * 4) != hipSuccess) { smi_set_error("hipMalloc(penalty prompt ids) failed"); return SMI_ENOMEM; }
+    L->pen_idx_cap = cap;
+  }
+  // (pageable source: staged before the call returns; host_pen_idx is rebuilt only by the next admission)
+  SMI_HIP(hipMemcpyAsync(L->pen_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_pen_prompt, dim3((unsigned)((idx.size() + 255) / 256)), dim3(256), 0, st, L->phist, L->pen_idx, (int)idx.size());
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
 int smi_llm_admit(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, int32_t* slots_out, void* stream) {
   return smi_llm_admit_sampled(L, ids, lens, n, P_max, nullptr, slots_out, stream);
 }
 
+// Checks of one penalty record (smi_llm_admit_penalized, smi_llm_debug_penalize).
+static int validate_penalty(const smi_llm* L, const smi_penalty_params& r, int b) {
+  SMI_REQUIRE(std::isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f,
+              "smi_llm_admit_penalized: pens[%d].repetition_penalty must be finite and > 0", b);
+  SMI_REQUIRE(std::isfinite(r.presence_penalty) && r.presence_penalty >= -2.f && r.presence_penalty <= 2.f,
+              "smi_llm_admit_penalized: pens[%d].presence_penalty must be in [-2, 2]", b);
+  SMI_REQUIRE(std::isfinite(r.frequency_penalty) && r.frequency_penalty >= -2.f && r.frequency_penalty <= 2.f,
+              "smi_llm_admit_penalized: pens[%d].frequency_penalty must be in [-2, 2]", b);
+  SMI_REQUIRE(r.min_new_tokens >= 0 && r.min_new_tokens <= L->cfg.max_positions,
+              "smi_llm_admit_penalized: pens[%d].min_new_tokens=%d outside 0..%d", b, r.min_new_tokens, L->cfg.max_positions);
+  SMI_REQUIRE(r.penalize_prompt == 0 || r.penalize_prompt == 1, "smi_llm_admit_penalized: pens[%d].penalize_prompt must be 0 or 1", b);
+  SMI_REQUIRE(r.reserved[0] == 0 && r.reserved[1] == 0 && r.reserved[2] == 0, "smi_llm_admit_penalized: pens[%d].reserved must be 0", b);
+  return SMI_OK;
+}
+
+static PenRec pen_record(const smi_penalty_params* pp) {
+  PenRec r;
+  memset(&r, 0, sizeof(r));
+  if (!pp || (pp->repetition_penalty == 1.f && pp->presence_penalty == 0.f && pp->frequency_penalty == 0.f && pp->min_new_tokens == 0))
+    return r;   // neutral: not penalised
+  r.rep = pp->repetition_penalty; r.pres = pp->presence_penalty; r.freq = pp->frequency_penalty;
+  r.min_new = pp->min_new_tokens; r.prompt = pp->penalize_prompt; r.on = 1;
+  return r;
+}
+
 int smi_llm_admit_sampled(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
                           int32_t* slots_out, void* stream) {
+  return smi_llm_admit_penalized(L, ids, lens, n, P_max, params, nullptr, slots_out, stream);
+}
+
+int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
+                            const smi_penalty_params* pens, int32_t* slots_out, void* stream) {
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
   SMI_REQUIRE(n >= 1 && L->B + n <= L->cfg.max_slots && L->B + n <= kMaxRows, "smi_llm_admit: %d new + %d live sequences exceed %d slots", n,
               L->B, L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows);
   { const int rcs = validate_sampling(params, n); if (rcs) return rcs; }   // nothing touched yet
+  if (pens)
+    for (int b = 0; b < n; ++b) { const int rcp = validate_penalty(L, pens[b], b); if (rcp) return rcp; }
   hipStream_t st = (hipStream_t)stream;
   int rc;
   std::vector<RowDesc> live;
@@ -4711,15 +4912,22 @@ int smi_llm_admit_sampled(smi_llm* L, const int64_t* ids, const int32_t* lens, i
   const int seq0 = L->admit_seq;
   int32_t old_seqid[kMaxRows];
   SampRec old_rec[kMaxRows];
+  PenRec old_pen[kMaxRows];
   for (int b = 0; b < n; ++b) { old_seqid[b] = L->hctl.seqid[slots[b]]; L->hctl.seqid[slots[b]] = L->admit_seq++; }
   // the records go up with the sequence numbers, before the admission's own step: its finalize emits the first token
   for (int b = 0; b < n; ++b) {
     old_rec[b] = L->hctl.samp[slots[b]];
     L->hctl.samp[slots[b]] = samp_record(params ? &params[b] : nullptr, L->cfg.vocab_size);
     L->slot_samp[slots[b]] = L->hctl.samp[slots[b]].mode == SMI_SAMPLING_SAMPLE;
+    old_pen[b] = L->hctl.pen[slots[b]];
+    L->hctl.pen[slots[b]] = pen_record(pens ? &pens[b] : nullptr);
+    L->slot_pen[slots[b]] = L->hctl.pen[slots[b]].on;
   }
   auto undo = [&]() {   // nothing was admitted: sequence numbers, records and pages as before (the device copy is rewritten by the next admission)
-    for (int b = 0; b < n; ++b) { L->hctl.seqid[slots[b]] = old_seqid[b]; L->hctl.samp[slots[b]] = old_rec[b]; L->slot_samp[slots[b]] = 0; }
+    for (int b = 0; b < n; ++b) {
+      L->hctl.seqid[slots[b]] = old_seqid[b]; L->hctl.samp[slots[b]] = old_rec[b]; L->slot_samp[slots[b]] = 0;
+      L->hctl.pen[slots[b]] = old_pen[b]; L->slot_pen[slots[b]] = 0;
+    }
     L->admit_seq = seq0;
     if (L->paged)
       for (int b = 0; b < n; ++b) pages_release(L, slots[b]);
@@ -4738,6 +4946,7 @@ int smi_llm_admit_sampled(smi_llm* L, const int64_t* ids, const int32_t* lens, i
     SMI_HIP(hipMemcpyAsync(L->finished + slots[b], zeros, 4, hipMemcpyHostToDevice, st));
   }
   SMI_HIP(hipMemcpyAsync(L->rows, L->plan + tail, kMaxRows * sizeof(RowDesc), hipMemcpyDeviceToDevice, st));
+  if ((rc = pen_histories(L, ids, lens, n, P_max, slots, st))) return rc;
   L->graph = nullptr;
   const int oldB = L->B;
   L->B = n;
@@ -4768,6 +4977,7 @@ int smi_llm_retire(smi_llm* L, int slot, void* stream) {
   L->slot_busy[slot] = 0;
   L->slot_len[slot] = 0;
   L->slot_samp[slot] = 0;
+  L->slot_pen[slot] = 0;
   if (L->paged) pages_release(L, slot);   // its pages go back to the pool (stale table entries are never read: no live row names the slot)
   return session_set_rows(L, live, st);
 }
@@ -4793,6 +5003,7 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
     L->slot_busy[slots[i]] = 0;
     L->slot_len[slots[i]] = 0;
     L->slot_samp[slots[i]] = 0;
+    L->slot_pen[slots[i]] = 0;
     if (L->paged) pages_release(L, slots[i]);
   }
   L->live_order = keep;
@@ -4879,16 +5090,16 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     L->attn_seg = segs_for(bound);
     if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
   }
-  const int samp = samp_any(L) ? 1 : 0;
+  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0;
   if (L->cfg.use_graph && n_steps > 0 && (!L->graph || L->graph_B != L->B || L->graph_seg != L->attn_seg || L->graph_ident != L->identity_slots ||
-                                          L->graph_samp != samp)) {
-    const uint32_t key = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24) | ((uint32_t)samp << 25);
+                                          L->graph_samp != samp || L->graph_pen != pen)) {
+    const uint64_t key = graph_key(L, samp, pen, 0);
     auto hit = L->graph_cache.find(key);
     L->graph = hit != L->graph_cache.end() ? hit->second : nullptr;
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen;
   }
   if (L->cfg.use_graph && n_steps > 0 && !L->graph) {
-    const uint32_t key = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24) | ((uint32_t)samp << 25);
+    const uint64_t key = graph_key(L, samp, pen, 0);
     if (L->graph_cache.size() >= 192) graphs_flush(L);
     hipStream_t cs;
     SMI_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
@@ -4904,7 +5115,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     }
     (void)hipStreamDestroy(cs);
     (void)hipGetLastError();
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen;
     if (!L->graph) { smi_set_error("hipGraph capture of the decode step failed"); return SMI_EHIP; }
     L->graph_cache[key] = L->graph;
   }
@@ -4916,8 +5127,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
   int s0 = 0;
   if (L->cfg.use_graph && L->graph_steps > 1 && n_steps >= L->graph_steps) {
     const int K = L->graph_steps;
-    const uint32_t keyk = (uint32_t)L->B | ((uint32_t)L->attn_seg << 8) | ((uint32_t)(L->identity_slots ? 1 : 0) << 24) | ((uint32_t)samp << 25) |
-                          ((uint32_t)K << 26);
+    const uint64_t keyk = graph_key(L, samp, pen, K);
     hipGraphExec_t gk = nullptr;
     auto hit = L->graph_cache.find(keyk);
     if (hit != L->graph_cache.end()) gk = hit->second;
@@ -5406,6 +5616,7 @@ int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint6
   std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
   for (int m = 0; m < kMaxRows; ++m) { rows[m].slot = m; L->hctl.seqid[m] = m; }
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));   // every row inherits the handle's settings
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
   L->hctl.seed = seed;
   SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
@@ -5421,6 +5632,59 @@ int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint6
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());
   SMI_HIP(hipMemcpy(tokens_out, L->tok, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+  L->started = 0;   // rows, controls and the lm_head partials no longer belong to a generation
+  return SMI_OK;
+}
+
+// Tests: the penalty kernel alone on caller rows (see sparkmi_debug.h).
+int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, const uint16_t* hist_host, const smi_penalty_params* pens,
+                           const int32_t* emitted_host, float* logits_out, int32_t* argmax_out) {
+  SMI_REQUIRE(L && logits_host && hist_host && pens && emitted_host && logits_out && argmax_out, "smi_llm_debug_penalize: null argument");
+  SMI_REQUIRE(n_rows >= 1 && n_rows <= L->cfg.max_slots && n_rows <= kMaxRows, "smi_llm_debug_penalize: n_rows=%d outside 1..max_slots", n_rows);
+  for (int m = 0; m < n_rows; ++m) {
+    const int rcp = validate_penalty(L, pens[m], m);
+    if (rcp) return rcp;
+  }
+  const size_t V = (size_t)L->cfg.vocab_size;
+  const int nblk = lm_blocks_for(L, n_rows);
+  SMI_HIP(hipDeviceSynchronize());
+  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->phist, hist_host, (size_t)n_rows * V * 2, hipMemcpyHostToDevice));
+  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  for (int m = 0; m < n_rows; ++m) {
+    rows[m] = RowDesc{m, 0, 0, emitted_host[m]};
+    L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: the kernel writes its processed logits back)
+    PenRec& r = L->hctl.pen[m];
+    r.rep = pens[m].repetition_penalty; r.pres = pens[m].presence_penalty; r.freq = pens[m].frequency_penalty;
+    r.min_new = pens[m].min_new_tokens; r.prompt = pens[m].penalize_prompt; r.on = 1;   // a neutral record too: the identity
+  }
+  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
+  PenP pp;
+  pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
+  pp.V = (int)V; pp.nblk = nblk; pp.per = pen_set_ids((int)V, nblk); pp.hs = 0;
+  hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
+  SMI_LAUNCH_CHECK();
+  SMI_HIP(hipDeviceSynchronize());
+  SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n_rows * V * 4, hipMemcpyDeviceToHost));
+  std::vector<float> pv((size_t)n_rows * nblk);
+  std::vector<int32_t> pi((size_t)n_rows * nblk);
+  SMI_HIP(hipMemcpy(pv.data(), L->pval, pv.size() * 4, hipMemcpyDeviceToHost));
+  SMI_HIP(hipMemcpy(pi.data(), L->pidx, pi.size() * 4, hipMemcpyDeviceToHost));
+  for (int m = 0; m < n_rows; ++m) {   // k_finalize's reduction of the maxima
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int j = 0; j < nblk; ++j) {
+      const float v = pv[(size_t)m * nblk + j];
+      const int ix = pi[(size_t)m * nblk + j];
+      if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
+    }
+    argmax_out[m] = bi;
+  }
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
   L->started = 0;   // rows, controls and the lm_head partials no longer belong to a generation
   return SMI_OK;
 }

@@ -82,6 +82,12 @@ class SampleParams(C.Structure):
                 ("seed", C.c_uint64), ("has_seed", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PenaltyParams(C.Structure):
+    """smi_penalty_params: one admitted sequence's logits penalties (smi_llm_admit_penalized)"""
+    _fields_ = [("repetition_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
+                ("min_new_tokens", C.c_int32), ("penalize_prompt", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
 _P = C.POINTER
 SYMBOLS = {
@@ -100,6 +106,8 @@ SYMBOLS = {
     "smi_llm_session_begin": (_I, [_VP, _P(C.c_int64), _I, _VP]),
     "smi_llm_admit": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _VP]),
     "smi_llm_admit_sampled": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(SampleParams), _P(C.c_int32), _VP]),
+    "smi_llm_admit_penalized": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(SampleParams), _P(PenaltyParams),
+                                     _P(C.c_int32), _VP]),
     "smi_llm_retire": (_I, [_VP, _I, _VP]),
     "smi_llm_slot_tokens": (_I, [_VP, _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_retire_many": (_I, [_VP, _P(C.c_int32), _I, _VP]),
@@ -144,6 +152,8 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_read": (_I, [_VP, _I, _VP, _SZ, _P(_SZ)]),
     "smi_llm_debug_raw_stamps": (_I, [_VP, _P(C.c_uint64), _I]),
     "smi_llm_debug_sample": (_I, [_VP, _P(C.c_float), _I, C.c_uint64, _I, _P(C.c_int32)]),
+    "smi_llm_debug_penalize": (_I, [_VP, _P(C.c_float), _I, _P(C.c_uint16), _P(PenaltyParams), _P(C.c_int32), _P(C.c_float),
+                                    _P(C.c_int32)]),
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),

@@ -26,11 +26,46 @@ from .config import LLMConfig
 EosLike = Union[None, int, Iterable[int]]
 # keys of a per-request sampling dict (SparkLLM.admit, generate_ragged, serve; SparkTTS.inference_batch / serve requests)
 SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p", "seed")
+# keys of its logits penalties, in the same dicts (smi_llm_admit_penalized; include/sparkmi.h states the semantics), and the
+# values that leave a request unpenalised
+PENALTY_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "min_new_tokens", "penalize_prompt")
+PENALTY_NEUTRAL = dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0)
+
+
+def penalty_neutral(d: Optional[Mapping]) -> bool:
+    """True when a request dict asks for no penalty (every penalty key it carries has its neutral value)."""
+    return d is None or all(float(d.get(k, v)) == v for k, v in PENALTY_NEUTRAL.items())
+
+
+def penalty_records(requests: Optional[Sequence[Optional[Mapping]]], n: int):
+    """One ``smi_penalty_params`` per prompt from the penalty keys of the request dicts, or None when no request is penalised
+    (neutral values and missing keys alike: the admission is then exactly the unpenalised one).  ``penalize_prompt``
+    defaults to True (transformers' default; False: only the generated tokens count for ``repetition_penalty``).  Ranges are
+    checked by the library."""
+    if requests is None:
+        return None
+    requests = list(requests)
+    if len(requests) != n:
+        raise ValueError(f"sampling: {len(requests)} entries for {n} prompts")
+    if all(penalty_neutral(d) for d in requests):
+        return None
+    recs = (_lib.PenaltyParams * n)()
+    for i, d in enumerate(requests):
+        r = recs[i]
+        r.repetition_penalty, r.penalize_prompt = 1.0, 1
+        if penalty_neutral(d):
+            continue
+        r.repetition_penalty = float(d.get("repetition_penalty", 1.0))
+        r.presence_penalty = float(d.get("presence_penalty", 0.0))
+        r.frequency_penalty = float(d.get("frequency_penalty", 0.0))
+        r.min_new_tokens = int(d.get("min_new_tokens", 0))
+        r.penalize_prompt = int(bool(d.get("penalize_prompt", True)))
+    return recs
 
 
 def sampling_records(sampling: Optional[Sequence[Optional[Mapping]]], n: int, defaults: Mapping):
     """One ``smi_sample_params`` per prompt, or None when every prompt inherits the handle's settings (``smi_llm_admit``).
-    ``sampling[i]`` None: inherit.  A dict: ``do_sample`` False -> greedy, else this record's own temperature / top_k / top_p
+    ``sampling[i]`` None, or a dict of penalty keys (``PENALTY_KEYS``) alone: inherit.  A dict: ``do_sample`` False -> greedy, else this record's own temperature / top_k / top_p
     (keys it leaves out take ``defaults``, the handle's ``set_sampling`` values, ``do_sample`` included) and, with ``seed``
     given, its own stream keyed by that seed and the sequence's token index alone.  Ranges are checked by the library."""
     if sampling is None:
@@ -40,13 +75,19 @@ def sampling_records(sampling: Optional[Sequence[Optional[Mapping]]], n: int, de
         raise ValueError(f"sampling: {len(sampling)} entries for {n} prompts")
     if all(d is None for d in sampling):
         return None
+    known = SAMPLING_KEYS + PENALTY_KEYS
+    for i, d in enumerate(sampling):
+        bad = set(d or ()) - set(known)
+        if bad:
+            raise ValueError(f"sampling[{i}]: unknown keys {sorted(bad)} (known: {', '.join(known)})")
+    # a dict that carries penalty keys alone leaves the token selection to the handle (inherit)
+    sampling = [None if d is not None and d and not set(d) & set(SAMPLING_KEYS) else d for d in sampling]
+    if all(d is None for d in sampling):
+        return None
     recs = (_lib.SampleParams * n)()
     for i, d in enumerate(sampling):
         if d is None:
             continue
-        bad = set(d) - set(SAMPLING_KEYS)
-        if bad:
-            raise ValueError(f"sampling[{i}]: unknown keys {sorted(bad)} (known: {', '.join(SAMPLING_KEYS)})")
         r = recs[i]
         if not bool(d.get("do_sample", defaults["do_sample"])):
             r.mode = _lib.SAMPLING_GREEDY
@@ -265,8 +306,9 @@ class SparkLLM:
 
     def admit(self, prompts: Sequence[Sequence[int]], sampling: Optional[Sequence[Optional[Mapping]]] = None) -> List[int]:
         """Prefill new prompts into free KV slots (first token emitted); returns their slot ids.  ``sampling``: one dict
-        (``SAMPLING_KEYS``) or None per prompt -- that sequence's own token selection (``sampling_records``); None everywhere
-        (the default): every sequence follows ``set_sampling``."""
+        (``SAMPLING_KEYS``, ``PENALTY_KEYS``) or None per prompt -- that sequence's own token selection (``sampling_records``)
+        and logits penalties (``penalty_records``); None everywhere (the default): every sequence follows ``set_sampling``,
+        unpenalised.  A request with any non-neutral penalty goes through ``smi_llm_admit_penalized``."""
         n = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int32)
         pmax = int(lens.max())
@@ -275,7 +317,13 @@ class SparkLLM:
             ids[b, : len(p)] = np.asarray(p, dtype=np.int64)
         slots = np.zeros(n, dtype=np.int32)
         recs = sampling_records(sampling, n, self._sampling)
-        if recs is None:
+        pens = penalty_records(sampling, n)
+        if pens is not None:
+            self._lib.check(self._lib.smi_llm_admit_penalized(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                         lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs, pens,
+                                                         slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                            "smi_llm_admit_penalized")
+        elif recs is None:
             self._lib.check(self._lib.smi_llm_admit(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), lens.ctypes.data_as(C.POINTER(C.c_int32)),
                                                n, pmax, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_admit")
         else:
@@ -330,7 +378,8 @@ class SparkLLM:
         """In-flight batching driver: ``requests`` yields (key, prompt ids, max_new_tokens, eos id or None -- one eos for
         the session: the first request's[, sampling dict or None]); yields (key, new ids) as each sequence finishes.  New
         requests are admitted whenever a slot is free, so short utterances never wait for long ones.  The optional fifth
-        element is that request's own token selection (``admit``); without it the request follows ``set_sampling``."""
+        element is that request's own token selection and penalties (``admit``); without it the request follows
+        ``set_sampling``, unpenalised."""
         it = iter(requests)
         max_live = min(max_live or self.max_slots, self.max_slots)
         live = {}                      # slot -> (key, max_new)
@@ -366,7 +415,7 @@ class SparkLLM:
         reference's TensorRT-LLM deployment batches in flight, run.sh:50-65).  Rows are independent in every kernel, so
         row i's tokens are exactly those of ``generate_ids`` truncated to its budget.  The captured step of every row
         count is cached in the library, so retiring costs a row-table upload, not a graph capture.  Greedy or the
-        sampler set by ``set_sampling``, or per prompt by ``sampling`` (as ``admit``); ``on_prefilled()`` is called after the
+        sampler set by ``set_sampling``, or per prompt by ``sampling`` (as ``admit``: sampling and penalty keys); ``on_prefilled()`` is called after the
         prompts' prefill was enqueued."""
         n = len(prompts)
         want = [int(w) for w in max_new_tokens]
@@ -532,6 +581,33 @@ class SparkLLM:
         self._lib.check(self._lib.smi_llm_debug_sample(self._h, ptr, int(n_rows), C.c_uint64(int(seed)), 1 if use_bound else 0,
                                                        out.ctypes.data_as(C.POINTER(C.c_int32))), "smi_llm_debug_sample")
         return out
+
+    def debug_penalize(self, logits: np.ndarray, hist: np.ndarray, pens: Sequence[Mapping], emitted: Sequence[int]):
+        """The penalty kernel alone (``smi_llm_debug_penalize``) on caller rows: ``logits`` [n][vocab] f32, ``hist`` [n][vocab]
+        uint16 history entries (bit 15: in the prompt; bits 0..14: generated count), one penalty dict (``PENALTY_KEYS``) and
+        the tokens emitted so far per row; eos ids from the last ``session_begin``.  Returns (processed logits [n][vocab],
+        arg-max [n] over the per-set maxima the kernel leaves for k_finalize)."""
+        self._need_diag("debug_penalize")
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        hs = np.ascontiguousarray(hist, dtype=np.uint16)
+        n = lg.shape[0]
+        assert lg.shape == hs.shape == (n, self.cfg.vocab_size)
+        recs = (_lib.PenaltyParams * n)()
+        for i, d in enumerate(pens):
+            recs[i].repetition_penalty = float(d.get("repetition_penalty", 1.0))
+            recs[i].presence_penalty = float(d.get("presence_penalty", 0.0))
+            recs[i].frequency_penalty = float(d.get("frequency_penalty", 0.0))
+            recs[i].min_new_tokens = int(d.get("min_new_tokens", 0))
+            recs[i].penalize_prompt = int(bool(d.get("penalize_prompt", True)))
+        em = np.ascontiguousarray(emitted, dtype=np.int32)
+        out = np.empty_like(lg)
+        am = np.zeros(n, dtype=np.int32)
+        self._lib.check(self._lib.smi_llm_debug_penalize(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), n,
+                                                         hs.ctypes.data_as(C.POINTER(C.c_uint16)), recs,
+                                                         em.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         out.ctypes.data_as(C.POINTER(C.c_float)),
+                                                         am.ctypes.data_as(C.POINTER(C.c_int32))), "smi_llm_debug_penalize")
+        return out, am
 
     KERNELS = ("qkv", "attn", "o_proj", "gate_up", "down", "lm_head", "finalize", "step", "layers")
 

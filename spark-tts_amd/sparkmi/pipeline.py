@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
-from .llm import SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config
+from .llm import PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config, penalty_neutral
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
 from .streaming import ChunkScheduler
@@ -27,8 +27,13 @@ from .weights import load_llm_state
 
 
 def _request_sampling(r: dict) -> Optional[dict]:
-    """The sampling keys (``SAMPLING_KEYS``) a request dict carries, or None: the call-level arguments apply unchanged."""
+    """The sampling keys (``SAMPLING_KEYS``) and penalty keys (``PENALTY_KEYS``) a request dict carries, or None: the
+    call-level arguments apply unchanged.  Penalty keys that ask for no penalty are dropped, so such a request keeps the
+    route (and the bits) of the same request without them."""
     d = {k: r[k] for k in SAMPLING_KEYS if k in r}
+    pen = {k: r[k] for k in PENALTY_KEYS if k in r}
+    if not penalty_neutral(pen):
+        d.update(pen)
     return d or None
 
 
@@ -133,10 +138,17 @@ class SparkTTS:
                   gender: str = None, pitch: str = None, speed: str = None,
                   temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *,
                   do_sample: bool = True, max_new_tokens: int = 3000, seed: Optional[int] = None,
-                  prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> np.ndarray:
-        """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate``."""
+                  prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                  min_new_tokens: int = 0, penalize_prompt: bool = True) -> np.ndarray:
+        """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate``.  The penalties
+        (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
+        For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
+        penalty."""
+        pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                   frequency_penalty=frequency_penalty, min_new_tokens=min_new_tokens, penalize_prompt=penalize_prompt)
         return self.inference_batch([dict(text=text, prompt_speech_path=prompt_speech_path, prompt_text=prompt_text,
-                                          gender=gender, pitch=pitch, speed=speed, prompt_tokens=prompt_tokens)],
+                                          gender=gender, pitch=pitch, speed=speed, prompt_tokens=prompt_tokens, **pen)],
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                                     max_new_tokens=max_new_tokens, seed=seed)[0]
 
@@ -149,7 +161,9 @@ class SparkTTS:
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
         A request may carry its own ``do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` (the call's arguments
         are the defaults of the keys it leaves out; TensorRT-LLM's per-request inputs): such a batch, even of one request,
-        runs through the admission path, so a request with its own ``seed`` gets the same tokens alone and in any batch."""
+        runs through the admission path, so a request with its own ``seed`` gets the same tokens alone and in any batch.
+        Likewise ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_new_tokens`` /
+        ``penalize_prompt`` (TensorRT-LLM's per-request penalty inputs); neutral values leave the request's route unchanged."""
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         prompts, globals_ = [], []
@@ -281,7 +295,7 @@ class SparkTTS:
         yields ``(index, waveform)`` as each utterance finishes.  Up to ``max_batch`` utterances are live; a new
         request is admitted into the LLM's free KV slot as soon as one retires, so short utterances do not wait for
         long ones.  Greedy results equal ``inference()`` of the same request.  Per-request ``do_sample`` / ``temperature`` /
-        ``top_k`` / ``top_p`` / ``seed`` keys as in ``inference_batch``."""
+        ``top_k`` / ``top_p`` / ``seed`` and penalty keys as in ``inference_batch``."""
         voc = self.audio_tokenizer.model
         ntok, hop = voc.cfg.spk_token_num, voc.hop
         globals_: Dict[int, Optional[torch.Tensor]] = {}
