@@ -224,6 +224,25 @@ typedef struct smi_penalty_params {
 } smi_penalty_params;
 int smi_llm_admit_penalized(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
                             const smi_sample_params* params, const smi_penalty_params* pens, int32_t* slots_out, void* stream);
+/* Per-token log-probabilities (TensorRT-LLM's return_log_probs -> output_log_probs / cum_log_probs).
+ * smi_llm_admit_logprobs = smi_llm_admit_penalized plus one 0/1 flag per prompt (return_log_probs = NULL: exactly
+ * smi_llm_admit_penalized).  For every token a flagged sequence emits -- the admission's first token and an eos included --
+ * the library keeps one fp32 value
+ *     lp = z[tok] - logsumexp(z), over the full vocabulary,
+ * where z is the logits token selection saw: the lm_head's fp32 logits after the row's penalties (stages 1-3 above, the -inf
+ * of min_new_tokens included), multiplied by the row's 1/temperature when the row samples (its record's, or the handle's for
+ * an inheriting row of a sampling handle).  In transformers' terms: log_softmax of the scores after the logits processors
+ * and TemperatureLogitsWarper, before TopK / TopP.  A greedy, unpenalised row gets the model's own log_softmax(logits)[tok].
+ * The value is NOT renormalised over the top-k / top-p survivors (that variant is not provided); a sampled token's value is
+ * always finite, since top-k / top-p only remove ids and do not change z.  A flag other than 0 / 1 is SMI_EINVAL, checked
+ * with the other records before anything of the handle is touched (no slot, page or admission number taken).
+ * smi_llm_slots_logprobs mirrors smi_llm_slots_tokens: out_host [n][cap] (the first n_out[i] values of row i, one per token
+ * of smi_llm_slots_tokens), one round trip; a retired slot stays readable until a later admission reuses it; a slot whose
+ * sequence was admitted without the flag is SMI_ESTATE.  Static generation (smi_llm_prefill) keeps no log-probabilities. */
+int smi_llm_admit_logprobs(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
+                           const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* return_log_probs,
+                           int32_t* slots_out, void* stream);
+int smi_llm_slots_logprobs(smi_llm* h, const int32_t* slots, int n, float* out_host, int cap, int32_t* n_out, void* stream);
 int smi_llm_retire(smi_llm* h, int slot, void* stream);
 int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished, void* stream);
 /* Several sequences leave at once with no host round trip (the device row list is compacted in place), and the tokens of

@@ -91,6 +91,13 @@ int smi_llm_debug_sample(smi_llm* h, const float* logits_host, int n_rows, uint6
  * generation. */
 int smi_llm_debug_penalize(smi_llm* h, const float* logits_host, int n_rows, const uint16_t* hist_host, const smi_penalty_params* pens,
                            const int32_t* emitted_host, float* logits_out, int32_t* argmax_out);
+/* Tests: the log-probability kernels alone (k_logprob and k_finalize's combine, as a step launches them for n_rows rows,
+ * n_rows <= max_slots) on caller rows: logits_host [n_rows][vocab_size] (the processed logits z before temperature),
+ * temperature_host [n_rows] (finite, > 0; each row is a sampling row with 1/T, T = 1: unscaled), tokens_host [n_rows] the
+ * emitted ids.  The row maxima the kernel reads are left as the lm_head leaves them (per-set maxima over a contiguous
+ * partition).  lp_out [n_rows]: z[tok] / T - logsumexp(z / T).  Synchronises; ends the current generation. */
+int smi_llm_debug_logprob(smi_llm* h, const float* logits_host, int n_rows, const float* temperature_host, const int32_t* tokens_host,
+                          float* lp_out);
 
 #ifdef __cplusplus
 }

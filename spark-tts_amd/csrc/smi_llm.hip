@@ -67,6 +67,7 @@ struct Ctl {
   int32_t seqid[SMI_MAX_ROWS];    // per KV slot: admission number of the sequence living there (sampler stream key)
   SampRec samp[SMI_MAX_ROWS];     // per KV slot: the sequence's sampling record (smi_llm_admit_sampled)
   PenRec pen[SMI_MAX_ROWS];       // per KV slot: the sequence's penalty record (smi_llm_admit_penalized)
+  int32_t lp[SMI_MAX_ROWS];       // per KV slot: 1 = the sequence returns per-token log-probabilities (smi_llm_admit_logprobs)
 };
 
 struct KvMap {
@@ -3147,7 +3148,8 @@ __global__ __launch_bounds__(256) void k_penalize(PenP p) {
   if (!r.on) return;   // not penalised: the lm_head's maxima stand
   const int lane = threadIdx.x & 63, set = blockIdx.x * kPenWaves + (threadIdx.x >> 6);
   if (set >= p.nblk) return;
-  const bool wb = rec_samples(p.ctl->samp[rd.slot], p.hs);   // the sampler reads the logits; k_finalize only the maxima
+  // the sampler and k_logprob read the logits; k_finalize of a row that does neither only the maxima
+  const bool wb = rec_samples(p.ctl->samp[rd.slot], p.hs) || p.ctl->lp[rd.slot];
   const bool mask = rd.flags < r.min_new;
   int eos[SMI_MAX_EOS];
 #pragma unroll
@@ -3189,10 +3191,79 @@ __global__ __launch_bounds__(256) void k_pen_prompt(uint16_t* hist, const int32_
   if (i < n) hist[idx[i]] = 0x8000;   // (plain stores: duplicate ids write the same value; the row was zeroed before)
 }
 
+// ------------------------------------------------------------------------------------------
+// Per-token log-probabilities (smi_llm_admit_logprobs; include/sparkmi.h states the semantics).  k_logprob runs after
+// k_penalize and the sampler, before k_finalize, on the logits rows the lm_head wrote (a penalised flagged row's are the
+// processed ones: k_penalize writes them back for flagged rows too).  Grid (kLpBlocks, M) x 256: block b of row m sums
+// exp((x - max) * 1/T) over its fixed slice of the row and leaves one partial; k_finalize adds the kLpBlocks partials in block
+// order and writes lp = (x[tok] - max) * 1/T - log(sum) beside the token.  max is the row maximum, taken from the nblk (value,
+// id) maxima the lm_head (or k_penalize) left: exact, whatever partition produced them.  Fixed slices and a fixed reduction
+// order (shuffles, then the waves in order; no atomics): a row's value depends on its own logits alone, not on the row count
+// or its neighbours.  Unflagged rows leave at once.
+// ------------------------------------------------------------------------------------------
+constexpr int kLpBlocks = 64;   // blocks (partials) per row
+
+struct LpP {
+  const float* logits;    // [M][V]
+  const Ctl* ctl;         // per-slot flags and sampling records
+  const RowDesc* rows;
+  const float* pval;      // [M][nblk] row maxima by sets
+  int nblk, V, per;       // per: ids per block, a multiple of 4 (per * kLpBlocks >= V)
+  float inv_temp;         // the handle's 1/T (inheriting rows of a sampling handle)
+  int hs;                 // the handle samples
+  float* part;            // [kMaxRows][kLpBlocks] partial sums
+  float2* rowc;           // [kMaxRows] (max, 1/T) of each flagged row (block 0 writes it)
+};
+
+// 1/T of row m exactly as k_sample scales it (row_sel): its record's, the handle's for an inheriting row of a sampling
+// handle; 1 for a row that does not sample
+__device__ __forceinline__ float lp_inv_temp(const SampRec& r, int hs, float handle_inv_temp) {
+  if (!rec_samples(r, hs)) return 1.f;
+  return r.mode == SMI_SAMPLING_SAMPLE ? r.inv_temp : handle_inv_temp;
+}
+
+__global__ __launch_bounds__(256) void k_logprob(LpP p) {
+  __shared__ float s_red[4];
+  const int m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const RowDesc rd = p.rows[m];
+  if (!p.ctl->lp[rd.slot]) return;   // not flagged
+  const float it = lp_inv_temp(p.ctl->samp[rd.slot], p.hs, p.inv_temp);
+  float mx = -INFINITY;
+  for (int j = tid; j < p.nblk; j += 256) mx = fmaxf(mx, p.pval[(size_t)m * p.nblk + j]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) s_red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+  __syncthreads();   // (s_red is reused below)
+  const float* lg = p.logits + (size_t)m * p.V;
+  const int i0 = (int)blockIdx.x * p.per, i1 = min(i0 + p.per, p.V);
+  float s = 0.f;
+  if ((p.V & 3) == 0) {   // i0 and i1 are multiples of 4: every float4 lies inside the slice and is aligned
+    for (int i = i0 + 4 * tid; i < i1; i += 1024) {
+      const float4 x = *(const float4*)(lg + i);
+      s += (expf((x.x - mx) * it) + expf((x.y - mx) * it)) + (expf((x.z - mx) * it) + expf((x.w - mx) * it));
+    }
+  } else {
+    for (int i = i0 + tid; i < i1; i += 256) s += expf((lg[i] - mx) * it);
+  }
+  s = smi_wave_sum(s);
+  if (lane == 0) s_red[wave] = s;
+  __syncthreads();
+  if (tid == 0) {
+    p.part[(size_t)m * kLpBlocks + blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    if (blockIdx.x == 0) p.rowc[m] = make_float2(mx, it);
+  }
+}
+
 struct FinP {
   const int* tok;       // non-null: tokens already chosen by k_sample for the rows that sample (rec_samples)
   int hs;               // the handle samples
   uint16_t* phist;      // non-null (some row is penalised): penalised rows count their token in their slot's history row
+  float* lp;            // non-null (some row is flagged): [max_steps][kMaxRows] log-probabilities beside hist
+  const float* lp_part; // [kMaxRows][kLpBlocks] k_logprob's partial sums
+  const float2* lp_rowc;// [kMaxRows] (max, 1/T)
+  const float* logits;  // [M][V]
   const float* pval;
   const int* pidx;
   int nblk, M, KT, V;
@@ -3218,11 +3289,22 @@ __global__ __launch_bounds__(256) void k_finalize(FinP p) {
   __shared__ float sv[4];
   __shared__ int si[4];
   __shared__ int tok_s;
+  __shared__ float lp_sum;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = blockIdx.x;
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   const bool sampled = p.tok && rec_samples(p.ctl->samp[p.rows[m].slot], p.hs);
+  const bool want_lp = p.lp && p.ctl->lp[p.rows[m].slot];
+  if (want_lp && tid == 64) {   // wave 1 adds k_logprob's partials in block order while wave 0 reduces the maxima
+    float part[kLpBlocks];
+#pragma unroll
+    for (int b = 0; b < kLpBlocks; ++b) part[b] = p.lp_part[(size_t)m * kLpBlocks + b];
+    float s = 0.f;
+#pragma unroll
+    for (int b = 0; b < kLpBlocks; ++b) s += part[b];
+    lp_sum = s;
+  }
   if (!sampled) {   // greedy: the arg-max of the lm_head blocks' maxima, the same bits with or without the sampler in the step
     constexpr int NP = 16;   // all partial loads in flight together (one memory round trip)
     float pv[NP];
@@ -3261,6 +3343,10 @@ __global__ __launch_bounds__(256) void k_finalize(FinP p) {
     const int step = rd.flags;                 // tokens this row has emitted so far
     const int sl = rd.slot;                    // history / counters live per KV slot (== m outside sessions)
     if (step < p.max_steps) p.hist[(size_t)step * kMaxRows + sl] = bi;
+    if (want_lp && step < p.max_steps) {
+      const float2 rc = p.lp_rowc[m];
+      p.lp[(size_t)step * kMaxRows + sl] = (p.logits[(size_t)m * p.V + bi] - rc.x) * rc.y - logf(lp_sum);
+    }
     if (p.phist && p.ctl->pen[sl].on) {   // one writer per slot: no atomics
       uint16_t& e = p.phist[(size_t)sl * p.V + bi];
       if ((e & 0x7fffu) != 0x7fffu) e = (uint16_t)(e + 1);
@@ -3404,6 +3490,9 @@ struct smi_llm {
   int do_sample, top_k; float temperature, top_p; unsigned long long seed;
   int slot_samp[kMaxRows];      // host: the record of the sequence in this slot (live or being admitted) is SMI_SAMPLING_SAMPLE
   int slot_pen[kMaxRows];       // host: the sequence in this slot (live or being admitted) has a penalty record (PenRec::on)
+  int slot_lp[kMaxRows];        // host: the sequence in this slot (live or being admitted) returns log-probabilities (Ctl::lp)
+  float* lp;                    // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
+  float* lp_part; float2* lp_rowc;   // k_logprob -> k_finalize: [kMaxRows][kLpBlocks] partial sums, [kMaxRows] (max, 1/T)
   uint16_t* phist;              // penalty histories [max_slots][vocab] (k_penalize, k_finalize)
   int32_t* pen_idx; size_t pen_idx_cap;   // admission: slot * vocab + id of the prompt tokens whose bit k_pen_prompt sets
   std::vector<int32_t> host_pen_idx;
@@ -3423,7 +3512,7 @@ struct smi_llm {
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
   int gu1_lo;           // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (SPARKMI_GU1_LO; default 4)
   int gu1_rows;         // rows up to which gate_up runs its one-batch, three-tile shape (SPARKMI_GU1_ROWS; default 32)
-  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen;   // the step graph in use (owned by graph_cache)
+  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen, graph_lp;   // the step graph in use (owned by graph_cache)
   // every exec remembers the stream it last ran on: a caller may alternate streams, and an exec is destroyed only after THAT
   // stream has drained (graphs_flush)
   std::map<hipGraphExec_t, hipStream_t> graph_last;
@@ -3434,7 +3523,8 @@ struct smi_llm {
   // create; the handle's sampler settings and the attention-partials buffer are kernel arguments, so a change of either empties
   // the cache (graphs_flush).  The sample bit decides only whether lm_head writes the logits rows and the sampler kernels run:
   // a step in which no row samples is the greedy step exactly.  Likewise the penalty bit only adds the logits rows and
-  // k_penalize: a step in which no row is penalised is the step without penalties exactly.
+  // k_penalize: a step in which no row is penalised is the step without penalties exactly; and the log-probability bit only
+  // adds the logits rows and k_logprob.
   std::map<uint64_t, hipGraphExec_t> graph_cache;
   hipEvent_t ev0, ev1;
   // host staging
@@ -3511,10 +3601,17 @@ bool pen_any(const smi_llm* L) {
     if (L->slot_pen[sl]) return true;
   return false;
 }
-// the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | sample << 25 | penalty << 26 | steps per replay << 32
-uint64_t graph_key(const smi_llm* L, int samp, int pen, int K) {
+// Some live / just-admitted row returns log-probabilities: lm_head writes the logits rows and k_logprob runs.
+bool lp_any(const smi_llm* L) {
+  for (int sl = 0; sl < kMaxRows; ++sl)
+    if (L->slot_lp[sl]) return true;
+  return false;
+}
+// the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | sample << 25 | penalty << 26 | log-probs << 27 |
+// steps per replay << 32
+uint64_t graph_key(const smi_llm* L, int samp, int pen, int lp, int K) {
   return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)samp << 25) |
-         ((uint64_t)pen << 26) | ((uint64_t)K << 32);
+         ((uint64_t)pen << 26) | ((uint64_t)lp << 27) | ((uint64_t)K << 32);
 }
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
@@ -3760,7 +3857,8 @@ int eng_create(smi_llm* L) {
 // the one-row step the engine stands for: one live sequence in slot 0, contiguous bf16 cache, one context segment (its layers
 // only: lm_head, the sampler and k_finalize stay launches, so a sampling record applies to the engine's row as to any other)
 bool eng_usable(const smi_llm* L, const RowDesc* rows, int M) {
-  return L->eng.enabled && L->eng_on && M == 1 && rows == L->rows && L->identity_slots && !L->paged && L->attn_seg <= 1 && !L->stamps_on;
+  return L->eng.enabled && L->eng_on && M == 1 && rows == L->rows && L->identity_slots && !L->paged && L->attn_seg <= 1 && !L->stamps_on &&
+         !lp_any(L);   // (a step with a log-probability row keeps to the launch path)
 }
 
 int eng_launch(smi_llm* L, hipStream_t st) {
@@ -3826,6 +3924,15 @@ int lm_blocks_for(const smi_llm* L, int M) {
 
 // ids per set of k_penalize's partition of a row into nblk sets: a multiple of 4 (aligned float4 sets)
 int pen_set_ids(int V, int nblk) { return ((V + nblk - 1) / nblk + 3) & ~3; }
+
+// k_logprob's arguments for a step of M rows (the lm_head's maxima, the handle's sampler settings)
+LpP lp_params(const smi_llm* L, int M) {
+  LpP lp;
+  lp.logits = L->logits; lp.ctl = L->ctl; lp.rows = L->rows; lp.pval = L->pval; lp.nblk = lm_blocks_for(L, M);
+  lp.V = L->cfg.vocab_size; lp.per = pen_set_ids(lp.V, kLpBlocks); lp.inv_temp = 1.0f / L->temperature; lp.hs = L->do_sample;
+  lp.part = L->lp_part; lp.rowc = L->lp_rowc;
+  return lp;
+}
 
 int segs_for(int ctx_bound) { return ctx_bound <= kAttnSeg ? 1 : (ctx_bound + kAttnSeg - 1) / kAttnSeg; }
 
@@ -3959,7 +4066,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
       case KLM:
         p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh; p.XS = L->xs_h;
-        p.Y = logits ? logits : (samp_any(L) || pen_any(L) ? L->logits : nullptr);
+        p.Y = logits ? logits : (samp_any(L) || pen_any(L) || lp_any(L) ? L->logits : nullptr);
         p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
         SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
         return launch_gemm_x<PRO_NORM, EPI_LM>(L, p, st);
@@ -4062,7 +4169,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KLM:
       p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh;
       p.XS = L->xs_h;
-      p.Y = logits ? logits : (samp_any(L) || pen_any(L) ? L->logits : nullptr);
+      p.Y = logits ? logits : (samp_any(L) || pen_any(L) || lp_any(L) ? L->logits : nullptr);
       p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
       p.stamps = L->stamps_on ? L->stamps : nullptr;
       if (L->KTh <= 32) {   // persistent path: 16 rows' operand resident in the registers of a 4-wave group
@@ -4111,6 +4218,13 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         hipLaunchKernelGGL(k_sample, dim3(M), dim3(1024), 0, st, sp);
         SMI_LAUNCH_CHECK();
         f.tok = L->tok;
+      }
+      f.lp = nullptr; f.lp_part = nullptr; f.lp_rowc = nullptr; f.logits = L->logits;
+      if (lp_any(L)) {   // unflagged rows leave k_logprob at once
+        LpP lp = lp_params(L, M);
+        hipLaunchKernelGGL(k_logprob, dim3(kLpBlocks, M), dim3(256), 0, st, lp);
+        SMI_LAUNCH_CHECK();
+        f.lp = L->lp; f.lp_part = L->lp_part; f.lp_rowc = L->lp_rowc;
       }
       f.pval = L->pval; f.pidx = L->pidx; f.M = M; f.KT = L->KTh; f.V = c.vocab_size;
       f.nblk = lm_blocks_for(L, M);
@@ -4425,7 +4539,8 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
-  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
+  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; L->graph_lp = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
+  memset(L->slot_lp, 0, sizeof(L->slot_lp)); L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
   L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
   const size_t esz = cfg->kv_dtype ? 4 : 2;
@@ -4480,6 +4595,10 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   SMI_ALLOC(L->stamps, (size_t)4096 * 8 * 8);
   SMI_ALLOC(L->kcache, kvbytes);
   SMI_ALLOC(L->vcache, kvbytes);
+  // log-probabilities (smi_llm_admit_logprobs), after everything else: the other buffers keep the placement they had without them
+  SMI_ALLOC(L->lp, (size_t)L->max_steps * kMaxRows * 4);
+  SMI_ALLOC(L->lp_part, (size_t)kMaxRows * kLpBlocks * 4);
+  SMI_ALLOC(L->lp_rowc, (size_t)kMaxRows * sizeof(float2));
 #undef SMI_ALLOC
   if (hipMemset(L->kcache, 0, kvbytes) != hipSuccess || hipMemset(L->vcache, 0, kvbytes) != hipSuccess ||
       hipMemset(L->h, 0, (size_t)kMaxRows * L->H * 4) != hipSuccess ||
@@ -4547,7 +4666,7 @@ int smi_llm_destroy(smi_llm* L) {
   eng_destroy(L);
   void* ptrs[] = {L->h, L->qbuf, L->xs_h, L->xs_attn, L->xs_act, L->sspart, L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
                   L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab, L->apart,
-                  L->phist, L->pen_idx};
+                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (L->ev0) (void)hipEventDestroy(L->ev0);
@@ -4726,6 +4845,8 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   memset(L->slot_samp, 0, sizeof(L->slot_samp));
   memset(L->hctl.pen, 0, sizeof(L->hctl.pen));     // and has no penalties
   memset(L->slot_pen, 0, sizeof(L->slot_pen));
+  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));       // and keeps no log-probabilities
+  memset(L->slot_lp, 0, sizeof(L->slot_lp));
   L->admit_seq = B;
   { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
   SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
@@ -4758,6 +4879,8 @@ int smi_llm_session_begin(smi_llm* L, const int64_t* eos_ids, int n_eos, void* s
   memset(L->slot_samp, 0, sizeof(L->slot_samp));
   memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
   memset(L->slot_pen, 0, sizeof(L->slot_pen));
+  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
+  memset(L->slot_lp, 0, sizeof(L->slot_lp));
   L->admit_seq = 0;
   if (L->paged)
     for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
@@ -4891,6 +5014,11 @@ int smi_llm_admit_sampled(smi_llm* L, const int64_t* ids, const int32_t* lens, i
 
 int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
                             const smi_penalty_params* pens, int32_t* slots_out, void* stream) {
+  return smi_llm_admit_logprobs(L, ids, lens, n, P_max, params, pens, nullptr, slots_out, stream);
+}
+
+int smi_llm_admit_logprobs(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
+                           const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out, void* stream) {
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
   SMI_REQUIRE(n >= 1 && L->B + n <= L->cfg.max_slots && L->B + n <= kMaxRows, "smi_llm_admit: %d new + %d live sequences exceed %d slots", n,
@@ -4898,6 +5026,9 @@ int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens,
   { const int rcs = validate_sampling(params, n); if (rcs) return rcs; }   // nothing touched yet
   if (pens)
     for (int b = 0; b < n; ++b) { const int rcp = validate_penalty(L, pens[b], b); if (rcp) return rcp; }
+  if (want_lp)
+    for (int b = 0; b < n; ++b)
+      SMI_REQUIRE(want_lp[b] == 0 || want_lp[b] == 1, "smi_llm_admit_logprobs: return_log_probs[%d]=%d must be 0 or 1", b, want_lp[b]);
   hipStream_t st = (hipStream_t)stream;
   int rc;
   std::vector<RowDesc> live;
@@ -4913,6 +5044,7 @@ int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens,
   int32_t old_seqid[kMaxRows];
   SampRec old_rec[kMaxRows];
   PenRec old_pen[kMaxRows];
+  int32_t old_lp[kMaxRows];
   for (int b = 0; b < n; ++b) { old_seqid[b] = L->hctl.seqid[slots[b]]; L->hctl.seqid[slots[b]] = L->admit_seq++; }
   // the records go up with the sequence numbers, before the admission's own step: its finalize emits the first token
   for (int b = 0; b < n; ++b) {
@@ -4922,11 +5054,15 @@ int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens,
     old_pen[b] = L->hctl.pen[slots[b]];
     L->hctl.pen[slots[b]] = pen_record(pens ? &pens[b] : nullptr);
     L->slot_pen[slots[b]] = L->hctl.pen[slots[b]].on;
+    old_lp[b] = L->hctl.lp[slots[b]];
+    L->hctl.lp[slots[b]] = want_lp ? want_lp[b] : 0;
+    L->slot_lp[slots[b]] = L->hctl.lp[slots[b]];
   }
   auto undo = [&]() {   // nothing was admitted: sequence numbers, records and pages as before (the device copy is rewritten by the next admission)
     for (int b = 0; b < n; ++b) {
       L->hctl.seqid[slots[b]] = old_seqid[b]; L->hctl.samp[slots[b]] = old_rec[b]; L->slot_samp[slots[b]] = 0;
       L->hctl.pen[slots[b]] = old_pen[b]; L->slot_pen[slots[b]] = 0;
+      L->hctl.lp[slots[b]] = old_lp[b]; L->slot_lp[slots[b]] = 0;
     }
     L->admit_seq = seq0;
     if (L->paged)
@@ -4978,6 +5114,7 @@ int smi_llm_retire(smi_llm* L, int slot, void* stream) {
   L->slot_len[slot] = 0;
   L->slot_samp[slot] = 0;
   L->slot_pen[slot] = 0;
+  L->slot_lp[slot] = 0;   // (Ctl::lp stays: the slot's log-probabilities stay readable until it is reused)
   if (L->paged) pages_release(L, slot);   // its pages go back to the pool (stale table entries are never read: no live row names the slot)
   return session_set_rows(L, live, st);
 }
@@ -5004,6 +5141,7 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
     L->slot_len[slots[i]] = 0;
     L->slot_samp[slots[i]] = 0;
     L->slot_pen[slots[i]] = 0;
+    L->slot_lp[slots[i]] = 0;
     if (L->paged) pages_release(L, slots[i]);
   }
   L->live_order = keep;
@@ -5032,6 +5170,30 @@ int smi_llm_slots_tokens(smi_llm* L, const int32_t* slots, int n, int64_t* out_h
     for (int t = 0; t < k; ++t) out_host[(size_t)i * cap + t] = hist[(size_t)t * kMaxRows + slots[i]];
     n_out[i] = k;
     finished[i] = fin[slots[i]];
+  }
+  return SMI_OK;
+}
+
+// Log-probabilities of several slots in one device round trip: out_host [n][cap], n_out[n] (as smi_llm_slots_tokens).
+int smi_llm_slots_logprobs(smi_llm* L, const int32_t* slots, int n, float* out_host, int cap, int32_t* n_out, void* stream) {
+  SMI_REQUIRE(L && slots && out_host && n_out && n >= 1 && n <= kMaxRows && cap >= 1, "smi_llm_slots_logprobs: bad argument");
+  for (int i = 0; i < n; ++i) SMI_REQUIRE(slots[i] >= 0 && slots[i] < kMaxRows, "smi_llm_slots_logprobs: slot %d out of range", slots[i]);
+  for (int i = 0; i < n; ++i)
+    if (!L->hctl.lp[slots[i]]) {
+      smi_set_error("smi_llm_slots_logprobs: the sequence in slot %d was admitted without return_log_probs", slots[i]);
+      return SMI_ESTATE;
+    }
+  hipStream_t st = (hipStream_t)stream;
+  int32_t cnt[kMaxRows];
+  SMI_HIP(hipMemcpyAsync(cnt, L->count, kMaxRows * 4, hipMemcpyDeviceToHost, st));
+  int steps = cap < L->max_steps ? cap : L->max_steps;
+  std::vector<float> lp((size_t)steps * kMaxRows);
+  SMI_HIP(hipMemcpyAsync(lp.data(), L->lp, lp.size() * 4, hipMemcpyDeviceToHost, st));
+  SMI_HIP(hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i) {
+    int k = cnt[slots[i]] < steps ? cnt[slots[i]] : steps;
+    for (int t = 0; t < k; ++t) out_host[(size_t)i * cap + t] = lp[(size_t)t * kMaxRows + slots[i]];
+    n_out[i] = k;
   }
   return SMI_OK;
 }
@@ -5090,16 +5252,16 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     L->attn_seg = segs_for(bound);
     if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
   }
-  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0;
+  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0, lpb = lp_any(L) ? 1 : 0;
   if (L->cfg.use_graph && n_steps > 0 && (!L->graph || L->graph_B != L->B || L->graph_seg != L->attn_seg || L->graph_ident != L->identity_slots ||
-                                          L->graph_samp != samp || L->graph_pen != pen)) {
-    const uint64_t key = graph_key(L, samp, pen, 0);
+                                          L->graph_samp != samp || L->graph_pen != pen || L->graph_lp != lpb)) {
+    const uint64_t key = graph_key(L, samp, pen, lpb, 0);
     auto hit = L->graph_cache.find(key);
     L->graph = hit != L->graph_cache.end() ? hit->second : nullptr;
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb;
   }
   if (L->cfg.use_graph && n_steps > 0 && !L->graph) {
-    const uint64_t key = graph_key(L, samp, pen, 0);
+    const uint64_t key = graph_key(L, samp, pen, lpb, 0);
     if (L->graph_cache.size() >= 192) graphs_flush(L);
     hipStream_t cs;
     SMI_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
@@ -5115,7 +5277,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     }
     (void)hipStreamDestroy(cs);
     (void)hipGetLastError();
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb;
     if (!L->graph) { smi_set_error("hipGraph capture of the decode step failed"); return SMI_EHIP; }
     L->graph_cache[key] = L->graph;
   }
@@ -5127,7 +5289,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
   int s0 = 0;
   if (L->cfg.use_graph && L->graph_steps > 1 && n_steps >= L->graph_steps) {
     const int K = L->graph_steps;
-    const uint64_t keyk = graph_key(L, samp, pen, K);
+    const uint64_t keyk = graph_key(L, samp, pen, lpb, K);
     hipGraphExec_t gk = nullptr;
     auto hit = L->graph_cache.find(keyk);
     if (hit != L->graph_cache.end()) gk = hit->second;
@@ -5686,6 +5848,68 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
   memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
   L->started = 0;   // rows, controls and the lm_head partials no longer belong to a generation
+  return SMI_OK;
+}
+
+// Tests: the log-probability kernels alone on caller rows (see sparkmi_debug.h).
+int smi_llm_debug_logprob(smi_llm* L, const float* logits_host, int n_rows, const float* temperature_host, const int32_t* tokens_host,
+                          float* lp_out) {
+  SMI_REQUIRE(L && logits_host && temperature_host && tokens_host && lp_out, "smi_llm_debug_logprob: null argument");
+  SMI_REQUIRE(n_rows >= 1 && n_rows <= L->cfg.max_slots && n_rows <= kMaxRows, "smi_llm_debug_logprob: n_rows=%d outside 1..max_slots", n_rows);
+  const int V = L->cfg.vocab_size;
+  for (int m = 0; m < n_rows; ++m) {
+    SMI_REQUIRE(std::isfinite(temperature_host[m]) && temperature_host[m] > 0.f, "smi_llm_debug_logprob: temperature[%d] must be finite and > 0", m);
+    SMI_REQUIRE(tokens_host[m] >= 0 && tokens_host[m] < V, "smi_llm_debug_logprob: tokens[%d]=%d outside the vocabulary", m, tokens_host[m]);
+  }
+  SMI_REQUIRE(L->max_steps >= 1, "smi_llm_debug_logprob: no history");
+  const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
+  // the row maxima as the lm_head leaves them: (maximum, lowest id) of each contiguous set
+  std::vector<float> pv((size_t)n_rows * nblk, -INFINITY);
+  std::vector<int32_t> pi((size_t)n_rows * nblk, 0x7fffffff);
+  for (int m = 0; m < n_rows; ++m)
+    for (int j = 0; j < nblk; ++j)
+      for (int i = j * per; i < V && i < (j + 1) * per; ++i) {
+        const float x = logits_host[(size_t)m * V + i];
+        if (x > pv[(size_t)m * nblk + j]) { pv[(size_t)m * nblk + j] = x; pi[(size_t)m * nblk + j] = i; }
+      }
+  SMI_HIP(hipDeviceSynchronize());
+  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->tok, tokens_host, (size_t)n_rows * 4, hipMemcpyHostToDevice));
+  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
+  for (int m = 0; m < n_rows; ++m) {
+    rows[m] = RowDesc{m, 0, 0, 0};   // token index 0: k_finalize writes lp[0][m]
+    SampRec& r = L->hctl.samp[m];
+    r.mode = SMI_SAMPLING_SAMPLE;    // a sampling row: its token is the caller's (L->tok) and its z is scaled by 1/T
+    r.inv_temp = 1.0f / temperature_host[m];
+    r.top_k = 1; r.top_p = 1.f;
+    L->hctl.lp[m] = 1;
+  }
+  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
+  LpP lp = lp_params(L, n_rows);
+  lp.hs = 0;
+  hipLaunchKernelGGL(k_logprob, dim3(kLpBlocks, n_rows), dim3(256), 0, 0, lp);
+  SMI_LAUNCH_CHECK();
+  FinP f;
+  f.tok = L->tok; f.hs = 0; f.phist = nullptr;
+  f.lp = L->lp; f.lp_part = L->lp_part; f.lp_rowc = L->lp_rowc; f.logits = L->logits;
+  f.pval = L->pval; f.pidx = L->pidx; f.M = n_rows; f.KT = L->KTh; f.V = V; f.nblk = nblk;
+  f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
+  f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
+  f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
+  hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
+  SMI_LAUNCH_CHECK();
+  SMI_HIP(hipDeviceSynchronize());
+  SMI_HIP(hipMemcpy(lp_out, L->lp, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
+  L->started = 0;   // rows, controls, the lm_head partials and the histories no longer belong to a generation
   return SMI_OK;
 }
 

@@ -112,6 +112,9 @@ SYMBOLS = {
     "smi_llm_slot_tokens": (_I, [_VP, _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_retire_many": (_I, [_VP, _P(C.c_int32), _I, _VP]),
     "smi_llm_slots_tokens": (_I, [_VP, _P(C.c_int32), _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _VP]),
+    "smi_llm_admit_logprobs": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(SampleParams), _P(PenaltyParams),
+                                    _P(C.c_int32), _P(C.c_int32), _VP]),
+    "smi_llm_slots_logprobs": (_I, [_VP, _P(C.c_int32), _I, _P(C.c_float), _I, _P(C.c_int32), _VP]),
     "smi_llm_status": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_forward_logits": (_I, [_VP, _P(C.c_int64), _I, _VP, _VP]),
     "smi_llm_steps": (_I, [_VP]),
@@ -152,6 +155,7 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_read": (_I, [_VP, _I, _VP, _SZ, _P(_SZ)]),
     "smi_llm_debug_raw_stamps": (_I, [_VP, _P(C.c_uint64), _I]),
     "smi_llm_debug_sample": (_I, [_VP, _P(C.c_float), _I, C.c_uint64, _I, _P(C.c_int32)]),
+    "smi_llm_debug_logprob": (_I, [_VP, _P(C.c_float), _I, _P(C.c_float), _P(C.c_int32), _P(C.c_float)]),
     "smi_llm_debug_penalize": (_I, [_VP, _P(C.c_float), _I, _P(C.c_uint16), _P(PenaltyParams), _P(C.c_int32), _P(C.c_float),
                                     _P(C.c_int32)]),
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),

@@ -30,6 +30,33 @@ SAMPLING_KEYS = ("do_sample", "temperature", "top_k", "top_p", "seed")
 # values that leave a request unpenalised
 PENALTY_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "min_new_tokens", "penalize_prompt")
 PENALTY_NEUTRAL = dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0)
+# key of the per-token log-probabilities, in the same dicts (smi_llm_admit_logprobs; include/sparkmi.h states the semantics)
+LOGPROB_KEYS = ("return_log_probs",)
+
+
+def logprob_flags(requests: Optional[Sequence[Optional[Mapping]]], n: int):
+    """One int32 0/1 flag per prompt from the ``return_log_probs`` keys of the request dicts, or None when no request carries
+    the key (the admission then keeps the route and bits it has without it).  The value must be a bool: anything else is
+    refused here, before any device call."""
+    if requests is None:
+        return None
+    requests = list(requests)
+    if len(requests) != n:
+        raise ValueError(f"sampling: {len(requests)} entries for {n} prompts")
+    if not any(d is not None and "return_log_probs" in d for d in requests):
+        return None
+    flags = np.zeros(n, dtype=np.int32)
+    for i, d in enumerate(requests):
+        v = (d or {}).get("return_log_probs", False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"sampling[{i}]: return_log_probs must be a bool, not {v!r}")
+        flags[i] = int(bool(v))
+    return flags
+
+
+def logprob_requested(d: Optional[Mapping]) -> bool:
+    """The request dict asks for per-token log-probabilities."""
+    return d is not None and bool(d.get("return_log_probs", False))
 
 
 def penalty_neutral(d: Optional[Mapping]) -> bool:
@@ -75,12 +102,12 @@ def sampling_records(sampling: Optional[Sequence[Optional[Mapping]]], n: int, de
         raise ValueError(f"sampling: {len(sampling)} entries for {n} prompts")
     if all(d is None for d in sampling):
         return None
-    known = SAMPLING_KEYS + PENALTY_KEYS
+    known = SAMPLING_KEYS + PENALTY_KEYS + LOGPROB_KEYS
     for i, d in enumerate(sampling):
         bad = set(d or ()) - set(known)
         if bad:
             raise ValueError(f"sampling[{i}]: unknown keys {sorted(bad)} (known: {', '.join(known)})")
-    # a dict that carries penalty keys alone leaves the token selection to the handle (inherit)
+    # a dict that carries penalty / log-probability keys alone leaves the token selection to the handle (inherit)
     sampling = [None if d is not None and d and not set(d) & set(SAMPLING_KEYS) else d for d in sampling]
     if all(d is None for d in sampling):
         return None
@@ -308,7 +335,9 @@ class SparkLLM:
         """Prefill new prompts into free KV slots (first token emitted); returns their slot ids.  ``sampling``: one dict
         (``SAMPLING_KEYS``, ``PENALTY_KEYS``) or None per prompt -- that sequence's own token selection (``sampling_records``)
         and logits penalties (``penalty_records``); None everywhere (the default): every sequence follows ``set_sampling``,
-        unpenalised.  A request with any non-neutral penalty goes through ``smi_llm_admit_penalized``."""
+        unpenalised.  A request with any non-neutral penalty goes through ``smi_llm_admit_penalized``; an admission in which
+        some request carries ``return_log_probs`` (``LOGPROB_KEYS``, a bool) through ``smi_llm_admit_logprobs``, and the
+        flagged sequences' log-probabilities are read with ``slots_logprobs``."""
         n = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int32)
         pmax = int(lens.max())
@@ -318,7 +347,14 @@ class SparkLLM:
         slots = np.zeros(n, dtype=np.int32)
         recs = sampling_records(sampling, n, self._sampling)
         pens = penalty_records(sampling, n)
-        if pens is not None:
+        flags = logprob_flags(sampling, n)
+        if flags is not None:
+            self._lib.check(self._lib.smi_llm_admit_logprobs(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                        lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs, pens,
+                                                        flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                            "smi_llm_admit_logprobs")
+        elif pens is not None:
             self._lib.check(self._lib.smi_llm_admit_penalized(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
                                                          lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs, pens,
                                                          slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
@@ -352,6 +388,18 @@ class SparkLLM:
                                                   fin.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_slots_tokens")
         return [(out[i, : n[i]].tolist(), bool(fin[i])) for i in range(len(arr))]
 
+    def slots_logprobs(self, slots: Sequence[int], cap: int) -> List[np.ndarray]:
+        """Per-token log-probabilities (float32, one per token of ``slots_tokens``) of several slots whose sequences were
+        admitted with ``return_log_probs``, live or retired and not yet reused, in one device round trip."""
+        arr = np.asarray(list(slots), dtype=np.int32)
+        out = np.zeros((len(arr), max(cap, 1)), dtype=np.float32)
+        n = np.zeros(len(arr), dtype=np.int32)
+        self._lib.check(self._lib.smi_llm_slots_logprobs(self._h, arr.ctypes.data_as(C.POINTER(C.c_int32)), len(arr),
+                                                    out.ctypes.data_as(C.POINTER(C.c_float)), max(cap, 1),
+                                                    n.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                        "smi_llm_slots_logprobs")
+        return [out[i, : n[i]].copy() for i in range(len(arr))]
+
     def slot_tokens(self, slot: int, cap: int):
         """(tokens emitted so far by the sequence in ``slot``, finished flag)."""
         out = np.zeros(max(cap, 1), dtype=np.int64)
@@ -374,13 +422,16 @@ class SparkLLM:
                                             self._stream()), "smi_llm_status")
         return cnt, fin
 
-    def serve(self, requests, max_live: Optional[int] = None, decode_stride: int = 8):
+    def serve(self, requests, max_live: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False):
         """In-flight batching driver: ``requests`` yields (key, prompt ids, max_new_tokens, eos id or None -- one eos for
         the session: the first request's[, sampling dict or None]); yields (key, new ids) as each sequence finishes.  New
         requests are admitted whenever a slot is free, so short utterances never wait for long ones.  The optional fifth
         element is that request's own token selection and penalties (``admit``); without it the request follows
-        ``set_sampling``, unpenalised."""
+        ``set_sampling``, unpenalised.  ``return_log_probs=True`` flags every request, a ``return_log_probs`` key one
+        request: a flagged request yields (key, (new ids, float32 log-probabilities, one per id))."""
         it = iter(requests)
+        if return_log_probs:
+            it = (tuple(r[:4]) + (dict(r[4] if len(r) > 4 and r[4] is not None else {}, return_log_probs=True),) for r in it)
         max_live = min(max_live or self.max_slots, self.max_slots)
         live = {}                      # slot -> (key, max_new)
         pending = next(it, None)
@@ -396,28 +447,35 @@ class SparkLLM:
                     started = True
                 slots = self.admit([list(b[1]) for b in batch], [b[4] if len(b) > 4 else None for b in batch])
                 for slot, b in zip(slots, batch):
-                    live[slot] = (b[0], int(b[2]))
+                    live[slot] = (b[0], int(b[2]), logprob_requested(b[4] if len(b) > 4 else None))
             self.decode(decode_stride)
             cnt, fin = self.status()
             leave = [slot for slot in live if fin[slot] or cnt[slot] >= live[slot][1]]
             if leave:                      # their tokens in one round trip, their rows dropped on the device
-                got = self.slots_tokens(leave, max(live[slot][1] for slot in leave))
+                cap = max(live[slot][1] for slot in leave)
+                got = self.slots_tokens(leave, cap)
+                flagged = [slot for slot in leave if live[slot][2]]
+                lps = dict(zip(flagged, self.slots_logprobs(flagged, cap))) if flagged else {}
                 self.retire_many(leave)
                 for slot, (toks, _) in zip(leave, got):
-                    key, max_new = live.pop(slot)
-                    yield key, toks[:max_new]
+                    key, max_new, want_lp = live.pop(slot)
+                    yield key, ((toks[:max_new], lps[slot][:max_new]) if want_lp else toks[:max_new])
 
     def generate_ragged(self, prompts: Sequence[Sequence[int]], max_new_tokens: Sequence[int], eos_token_id: EosLike = None,
                         check_every: int = 16, on_prefilled=None,
-                        sampling: Optional[Sequence[Optional[Mapping]]] = None) -> List[List[int]]:
+                        sampling: Optional[Sequence[Optional[Mapping]]] = None, return_log_probs: bool = False) -> List:
         """One batch of prompts with PER-ROW token budgets, rows retired as they finish (their budget, or eos): the decode
         step then runs on the rows still alive instead of padding finished ones to the longest (HF ``generate`` pads; the
         reference's TensorRT-LLM deployment batches in flight, run.sh:50-65).  Rows are independent in every kernel, so
         row i's tokens are exactly those of ``generate_ids`` truncated to its budget.  The captured step of every row
         count is cached in the library, so retiring costs a row-table upload, not a graph capture.  Greedy or the
         sampler set by ``set_sampling``, or per prompt by ``sampling`` (as ``admit``: sampling and penalty keys); ``on_prefilled()`` is called after the
-        prompts' prefill was enqueued."""
+        prompts' prefill was enqueued.  ``return_log_probs=True`` flags every row, a ``return_log_probs`` key in ``sampling``
+        one row: a flagged row's result is (tokens, float32 log-probabilities, one per token; include/sparkmi.h,
+        smi_llm_admit_logprobs)."""
         n = len(prompts)
+        if return_log_probs:
+            sampling = [dict(d or {}, return_log_probs=True) for d in (sampling if sampling is not None else [None] * n)]
         want = [int(w) for w in max_new_tokens]
         if n != len(want) or n > self.max_slots or min(want) < 1:
             raise ValueError("generate_ragged: one budget >= 1 per prompt, at most max_slots prompts")
@@ -448,7 +506,12 @@ class SparkLLM:
             done += steps
         # histories are per KV slot and stay until a slot is reused: all rows in one round trip
         got = self.slots_tokens(slots, max(want))
-        return [t[: want[i]] for i, (t, _) in enumerate(got)]
+        res = [t[: want[i]] for i, (t, _) in enumerate(got)]
+        flagged = [i for i in range(n) if logprob_requested(sampling[i] if sampling is not None else None)]
+        if flagged:
+            for i, lp in zip(flagged, self.slots_logprobs([slots[i] for i in flagged], max(want))):
+                res[i] = (res[i], lp[: want[i]])
+        return res
 
     # ------------------------------------------------------------------ test / bench entries
     def forward_logits(self, ids: Sequence[int]) -> torch.Tensor:
@@ -608,6 +671,24 @@ class SparkLLM:
                                                          out.ctypes.data_as(C.POINTER(C.c_float)),
                                                          am.ctypes.data_as(C.POINTER(C.c_int32))), "smi_llm_debug_penalize")
         return out, am
+
+    def debug_logprob(self, logits: np.ndarray, temperature: Sequence[float], tokens: Sequence[int]) -> np.ndarray:
+        """The log-probability kernels alone (``smi_llm_debug_logprob``: k_logprob and k_finalize's combine) on caller rows:
+        ``logits`` [n][vocab] f32 (the processed logits), one temperature (> 0; 1: unscaled) and one emitted id per row.
+        Returns [n] float32: z[tok] - logsumexp(z), z = logits / T."""
+        self._need_diag("debug_logprob")
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        n = lg.shape[0]
+        assert lg.shape == (n, self.cfg.vocab_size)
+        t = np.ascontiguousarray(temperature, dtype=np.float32)
+        tk = np.ascontiguousarray(tokens, dtype=np.int32)
+        assert t.shape == tk.shape == (n,)
+        out = np.zeros(n, dtype=np.float32)
+        self._lib.check(self._lib.smi_llm_debug_logprob(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), n,
+                                                        t.ctypes.data_as(C.POINTER(C.c_float)),
+                                                        tk.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        out.ctypes.data_as(C.POINTER(C.c_float))), "smi_llm_debug_logprob")
+        return out
 
     KERNELS = ("qkv", "attn", "o_proj", "gate_up", "down", "lm_head", "finalize", "step", "layers")
 

@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
-from .llm import PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config, penalty_neutral
+from .llm import LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config, penalty_neutral
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
 from .streaming import ChunkScheduler
@@ -29,12 +29,23 @@ from .weights import load_llm_state
 def _request_sampling(r: dict) -> Optional[dict]:
     """The sampling keys (``SAMPLING_KEYS``) and penalty keys (``PENALTY_KEYS``) a request dict carries, or None: the
     call-level arguments apply unchanged.  Penalty keys that ask for no penalty are dropped, so such a request keeps the
-    route (and the bits) of the same request without them."""
+    route (and the bits) of the same request without them.  ``return_log_probs`` (``LOGPROB_KEYS``) is kept when True."""
     d = {k: r[k] for k in SAMPLING_KEYS if k in r}
     pen = {k: r[k] for k in PENALTY_KEYS if k in r}
     if not penalty_neutral(pen):
         d.update(pen)
+    for k in LOGPROB_KEYS:
+        if k in r and not isinstance(r[k], (bool, np.bool_)):
+            raise ValueError(f"{k} must be a bool, not {r[k]!r}")
+        if r.get(k):
+            d[k] = True
     return d or None
+
+
+def _lp_info(toks: Sequence[int], lps: np.ndarray) -> dict:
+    """The info dict that comes with a waveform when log-probabilities are asked for."""
+    lps = np.asarray(lps, dtype=np.float32)
+    return {"token_ids": list(toks), "output_log_probs": lps, "cum_log_prob": float(np.sum(lps, dtype=np.float64))}
 
 
 class _TokenMap:
@@ -140,22 +151,24 @@ class SparkTTS:
                   do_sample: bool = True, max_new_tokens: int = 3000, seed: Optional[int] = None,
                   prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                  min_new_tokens: int = 0, penalize_prompt: bool = True) -> np.ndarray:
+                  min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate``.  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
-        penalty."""
+        penalty.  ``return_log_probs=True``: (waveform, info) with info = {``token_ids``: the generated ids,
+        ``output_log_probs``: float32, one per id (include/sparkmi.h, smi_llm_admit_logprobs), ``cum_log_prob``: their
+        float64 sum}; the waveform is the one the call gives without it."""
         pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, min_new_tokens=min_new_tokens, penalize_prompt=penalize_prompt)
         return self.inference_batch([dict(text=text, prompt_speech_path=prompt_speech_path, prompt_text=prompt_text,
                                           gender=gender, pitch=pitch, speed=speed, prompt_tokens=prompt_tokens, **pen)],
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
-                                    max_new_tokens=max_new_tokens, seed=seed)[0]
+                                    max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs)[0]
 
     @torch.no_grad()
     def inference_batch(self, requests: Sequence[dict], temperature: float = 0.8, top_k: float = 50,
                         top_p: float = 0.95, *, do_sample: bool = True, max_new_tokens: int = 3000,
-                        seed: Optional[int] = None) -> List[np.ndarray]:
+                        seed: Optional[int] = None, return_log_probs: bool = False) -> List:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
@@ -163,7 +176,9 @@ class SparkTTS:
         are the defaults of the keys it leaves out; TensorRT-LLM's per-request inputs): such a batch, even of one request,
         runs through the admission path, so a request with its own ``seed`` gets the same tokens alone and in any batch.
         Likewise ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_new_tokens`` /
-        ``penalize_prompt`` (TensorRT-LLM's per-request penalty inputs); neutral values leave the request's route unchanged."""
+        ``penalize_prompt`` (TensorRT-LLM's per-request penalty inputs); neutral values leave the request's route unchanged.
+        ``return_log_probs=True`` (every request) or a request's ``return_log_probs`` key: that request's waveform comes as
+        (waveform, info), info as in ``inference``; such a batch runs through the admission path."""
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         prompts, globals_ = [], []
@@ -193,6 +208,8 @@ class SparkTTS:
             raise ValueError(f"a prompt of {max(len(i) for i in ids)} tokens does not fit max_positions={self._max_positions}")
         max_new_tokens = min(int(max_new_tokens), room)
         sampling = [_request_sampling(r) for r in requests]
+        if return_log_probs:
+            sampling = [dict(d or {}, return_log_probs=True) for d in sampling]
         if any(sampling):   # (max_batch = the LLM's slots)
             self.model.set_sampling(bool(do_sample), temperature, int(top_k), float(top_p), seed)
             new = self.model.generate_ragged(ids, [max_new_tokens] * len(ids), self._eos, sampling=sampling)
@@ -206,6 +223,11 @@ class SparkTTS:
                                           top_k=int(top_k), top_p=float(top_p), seed=seed)
         else:
             new = self.model.generate_ids(ids, max_new_tokens, self._eos)
+        infos: List[Optional[dict]] = [None] * len(new)
+        for b, r in enumerate(new):
+            if isinstance(r, tuple):   # a flagged row: (tokens, log-probabilities)
+                new[b] = r[0]
+                infos[b] = _lp_info(*r)
         sems, globs, lens = [], [], []
         ntok = self.audio_tokenizer.model.cfg.spk_token_num
         for b, toks in enumerate(new):
@@ -228,7 +250,8 @@ class SparkTTS:
         wav = self.audio_tokenizer.model.detokenize(sem_t, torch.stack(globs).unsqueeze(1), lengths=lens)
         wav = wav.squeeze(1).cpu().numpy()
         hop = self.audio_tokenizer.model.hop
-        return [wav[b, : lens[b] * hop].copy() for b in range(len(sems))]
+        out = [wav[b, : lens[b] * hop].copy() for b in range(len(sems))]
+        return [(w, infos[b]) if infos[b] is not None else w for b, w in enumerate(out)]
 
     @torch.no_grad()
     def inference_stream(self, text: str, prompt_speech_path: Path = None, prompt_text: str = None,
@@ -289,13 +312,15 @@ class SparkTTS:
 
     @torch.no_grad()
     def serve(self, requests, temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *, do_sample: bool = True,
-              max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8):
+              max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False):
         """In-flight batching front end (the functional analogue of the reference's Triton deployment,
         runtime/triton_trtllm/run.sh:50-65): ``requests`` is an iterable of the dicts ``inference_batch`` takes;
         yields ``(index, waveform)`` as each utterance finishes.  Up to ``max_batch`` utterances are live; a new
         request is admitted into the LLM's free KV slot as soon as one retires, so short utterances do not wait for
         long ones.  Greedy results equal ``inference()`` of the same request.  Per-request ``do_sample`` / ``temperature`` /
-        ``top_k`` / ``top_p`` / ``seed`` and penalty keys as in ``inference_batch``."""
+        ``top_k`` / ``top_p`` / ``seed`` and penalty keys as in ``inference_batch``.  ``return_log_probs=True`` (every
+        request) or a request's ``return_log_probs`` key: that request yields ``(index, waveform, info)``, info as in
+        ``inference`` (up to and including the first eos id, like the waveform's tokens)."""
         voc = self.audio_tokenizer.model
         ntok, hop = voc.cfg.spk_token_num, voc.hop
         globals_: Dict[int, Optional[torch.Tensor]] = {}
@@ -311,7 +336,11 @@ class SparkTTS:
                 ids = self.tokenizer([prompt], return_tensors="pt").input_ids[0].tolist()
                 yield i, ids, min(max_new_tokens, self._max_positions - len(ids) - decode_stride), self._eos, _request_sampling(r)
 
-        for i, toks in self.model.serve(llm_requests(), max_live=self._max_batch, decode_stride=decode_stride):
+        for i, toks in self.model.serve(llm_requests(), max_live=self._max_batch, decode_stride=decode_stride,
+                                        return_log_probs=return_log_probs):
+            lps = None
+            if isinstance(toks, tuple):   # a flagged request: (tokens, log-probabilities)
+                toks, lps = toks
             stops = [toks.index(e) for e in self._eos if e in toks]
             if stops:
                 toks = toks[: min(stops) + 1]
@@ -322,4 +351,8 @@ class SparkTTS:
             if not sem:
                 raise ValueError(f"request {i}: the model generated no semantic tokens")
             wav = voc.detokenize(torch.tensor([sem], dtype=torch.long), g.reshape(1, 1, -1), lengths=[len(sem)])
-            yield i, wav.reshape(-1)[: len(sem) * hop].cpu().numpy().copy()
+            w = wav.reshape(-1)[: len(sem) * hop].cpu().numpy().copy()
+            if lps is None:
+                yield i, w
+            else:
+                yield i, w, _lp_info(toks, lps[: len(toks)])
