@@ -243,6 +243,30 @@ int smi_llm_admit_logprobs(smi_llm* h, const int64_t* ids_host, const int32_t* l
                            const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* return_log_probs,
                            int32_t* slots_out, void* stream);
 int smi_llm_slots_logprobs(smi_llm* h, const int32_t* slots, int n, float* out_host, int cap, int32_t* n_out, void* stream);
+/* Several takes of one prompt (TensorRT-LLM's num_return_sequences): n_return[b] >= 1 takes of prompt b.  Output sequences are
+ * prompt-major: prompt 0's takes, then prompt 1's, ...  N = sum(n_return).  params / pens / return_log_probs hold one entry per
+ * OUTPUT sequence ([N]; NULL as in smi_llm_admit_logprobs).  slots_out [N].
+ *   Equivalence: the call equals smi_llm_admit_logprobs of the expanded prompt list, in which prompt b appears n_return[b]
+ *     times in a row, with the same records -- bit for bit in the slots returned (lowest free slots, in order), the admission
+ *     numbers given out, every token and log-probability, and every K/V element at every position, with either cache dtype,
+ *     contiguous or paged.  n_return = NULL or all ones: exactly smi_llm_admit_logprobs.
+ *   Prefill work: each distinct prompt's prompt rows (all its tokens but the last) run once, in the slot of its first take
+ *     (its leader), through the kernels its own length selects; the leader's K/V rows 0 .. L-2 then reach the other takes
+ *     (k_kv_fork), and one step over all N rows emits every take's first token with its own record.
+ *   Paged cache (page size P, prompt length L): the followers share the leader's first S = floor((L-1)/P) pages read-only
+ *     (they hold positions < S P <= L-1, which no later step writes); every take owns its pages from page S on, and positions
+ *     S P .. L-2 (possibly none) are copied into each follower's page S.  A page goes back to the pool when its last holder
+ *     retires (smi_llm_retire, smi_llm_retire_many, smi_llm_session_begin, smi_llm_prefill); smi_llm_kv_pages counts as free
+ *     only the pages no slot holds.  One prompt's n takes use ceil(L/P) + (n-1) (ceil(L/P) - S) pages, against n ceil(L/P)
+ *     for the expanded admission.
+ *   Contiguous cache: positions 0 .. L-2 of every layer, K and V, every kv head, are copied into each follower.
+ *   All or nothing: every n_return[b] >= 1, N within the free slots, the records (as smi_llm_admit_logprobs) and the pool's
+ *     pages for the formula above are checked before anything of the handle is touched; a failing call returns SMI_EINVAL
+ *     or SMI_ENOMEM and takes no slot, page, page reference or admission number.
+ * Static generation (smi_llm_prefill) has no forks. */
+int smi_llm_admit_forked(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
+                         const int32_t* n_return, const smi_sample_params* params, const smi_penalty_params* pens,
+                         const int32_t* return_log_probs, int32_t* slots_out, void* stream);
 int smi_llm_retire(smi_llm* h, int slot, void* stream);
 int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished, void* stream);
 /* Several sequences leave at once with no host round trip (the device row list is compacted in place), and the tokens of

@@ -2756,6 +2756,32 @@ __global__ __launch_bounds__(64) void k_rows_drop(RowDesc* rows, int B, unsigned
   else if (i < 64) { /* nothing: the tail beyond the new count is never read */ }
 }
 
+// Forked admission (smi_llm_admit_forked): copies cache positions [p0, p1) of a source slot into a destination slot, every
+// layer, K and V, every kv head, for a flat work list of (src slot, dst slot, p0, p1) entries -- one per follower take.  A byte
+// copy in 16-byte pieces addressed through KvMap on both sides, so bf16 / f32 and contiguous / paged caches run the same code.
+// grid: x = (position, piece) of the longest entry, y = work entry, z = (layer, K / V, kv head).
+struct ForkP {
+  const int4* work;           // [gridDim.y] (src slot, dst slot, p0, p1)
+  unsigned char* kcache;      // layer 0's K cache (layer l at + l * layer_bytes)
+  unsigned char* vcache;
+  size_t layer_bytes;
+  int n_kv, max_pos;
+  int piece_shift;            // log2(16-byte pieces per 64-element row): 3 (bf16) or 4 (f32)
+  KvMap km;
+};
+__global__ __launch_bounds__(256) void k_kv_fork(ForkP p) {
+  const int4 w = p.work[blockIdx.y];
+  const int u = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int pos = w.z + (u >> p.piece_shift), piece = u & ((1 << p.piece_shift) - 1);
+  if (pos >= w.w) return;
+  const int kvh = (int)blockIdx.z % p.n_kv, isv = ((int)blockIdx.z / p.n_kv) & 1, layer = (int)blockIdx.z / (2 * p.n_kv);
+  unsigned char* base = (isv ? p.vcache : p.kcache) + (size_t)layer * p.layer_bytes;
+  const size_t rb = (size_t)16 << p.piece_shift;   // bytes of one row
+  const uint4* s = (const uint4*)(base + kv_row(p.km, w.x, kvh, p.n_kv, p.max_pos, pos) * rb) + piece;
+  uint4* d = (uint4*)(base + kv_row(p.km, w.y, kvh, p.n_kv, p.max_pos, pos) * rb) + piece;
+  *d = *s;
+}
+
 __global__ __launch_bounds__(256) void k_embed(const uint16_t* Wlm, int KT, const RowDesc* rows, int M, const float* gamma,
                                                float* h, unsigned char* xs, float* sspart, int npart, int exact) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3475,6 +3501,7 @@ struct smi_llm {
   int32_t* ptab;
   std::vector<int32_t> hptab;
   std::vector<int32_t> free_pages;
+  std::vector<int32_t> page_ref;   // [kv_pages] slots whose table rows hold the page (> 1: shared by forked takes)
   int slot_pages[kMaxRows];     // pages a slot holds
   int plen[kMaxRows];           // plain (non-session) generation: prompt length per slot
   Ctl hctl; Ctl* ctl;   // host copy / device block of the generation controls
@@ -3556,10 +3583,25 @@ struct LdsBig {
 };
 constexpr int kLdsBigBytes = 160 * 1024;   // the window every LdsBig kernel is opted in to
 
-// ---- paged KV cache: host-side page allocator.  A slot's row of the table lists the pages of its positions in order.
+// ---- paged KV cache: host-side page allocator.  A slot's row of the table lists the pages of its positions in order.  A page
+// may sit in several rows (the leading pages of a forked admission's takes, pages_share); page_ref counts them, and a page goes
+// back to the pool when its last holder lets go of it.
 void pages_release(smi_llm* L, int slot) {
-  for (int i = 0; i < L->slot_pages[slot]; ++i) L->free_pages.push_back(L->hptab[(size_t)slot * L->ppslot + i]);
+  for (int i = 0; i < L->slot_pages[slot]; ++i) {
+    const int32_t pg = L->hptab[(size_t)slot * L->ppslot + i];
+    if (--L->page_ref[pg] == 0) L->free_pages.push_back(pg);
+  }
   L->slot_pages[slot] = 0;
+}
+// The empty slot `dst` takes the first `n` pages of slot `src` as its own first n pages, shared (read-only by contract: they
+// hold positions no later step writes).  Host table only; the next pages_ensure uploads it.
+void pages_share(smi_llm* L, int src, int dst, int n) {
+  for (int i = 0; i < n; ++i) {
+    const int32_t pg = L->hptab[(size_t)src * L->ppslot + i];
+    L->hptab[(size_t)dst * L->ppslot + i] = pg;
+    ++L->page_ref[pg];
+  }
+  L->slot_pages[dst] = n;
 }
 // Makes every listed slot hold pages for `tokens[i]` positions; all or nothing (SMI_ENOMEM when the pool is short).
 int pages_ensure(smi_llm* L, const int* slots, const int* tokens, int n, hipStream_t st) {
@@ -3580,6 +3622,7 @@ int pages_ensure(smi_llm* L, const int* slots, const int* tokens, int n, hipStre
     const int sl = slots[i], need = (tokens[i] + (1 << L->pshift) - 1) >> L->pshift;
     while (L->slot_pages[sl] < need) {
       L->hptab[(size_t)sl * L->ppslot + L->slot_pages[sl]++] = L->free_pages.back();
+      L->page_ref[L->free_pages.back()] = 1;
       L->free_pages.pop_back();
     }
   }
@@ -4553,6 +4596,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
     L->kv_layer_elems = (size_t)cfg->kv_pages * cfg->num_kv_heads * cfg->kv_page_tokens * kHeadDim;
     L->hptab.assign((size_t)cfg->max_slots * L->ppslot, 0);
     for (int pg = cfg->kv_pages - 1; pg >= 0; --pg) L->free_pages.push_back(pg);
+    L->page_ref.assign((size_t)cfg->kv_pages, 0);
   }
   const size_t kvbytes = L->kv_layer_elems * esz * cfg->num_layers;
 #define SMI_ALLOC(ptr, bytes)                                                      \
@@ -4710,8 +4754,11 @@ static int validate_prompts(const smi_llm* L, const int64_t* ids, const int32_t*
   return SMI_OK;
 }
 
+// Forked admission: n_ret[b] takes of prompt b (null: one each) -- the prompt rows run once, in slots[b], and the tail holds one
+// row per take, in tail_slots (prompt-major).  `extra` rows (the fork copy's work list) go up with the plan, at *tail_off + kMaxRows.
 static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, int P_max, const int32_t* slots,
-                           size_t* tail_off, hipStream_t st) {
+                           size_t* tail_off, hipStream_t st, const int32_t* n_ret = nullptr, const int32_t* tail_slots = nullptr,
+                           const std::vector<RowDesc>* extra = nullptr) {
   size_t total = 0;
   { const int rcv = validate_prompts(L, ids, lens, B, P_max); if (rcv) return rcv; }
   for (int b = 0; b < B; ++b) total += lens[b] - 1;
@@ -4742,8 +4789,9 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
   // plan: [class 2 rows][class 1 rows][class 3 rows][class 0 rows, padded to whole chunks][the B last-token rows]
   const size_t off2 = 0, off1 = ncls[2], off3 = off1 + ncls[1], off0 = off3 + ncls[3], tail = off0 + nchunks * kMaxRows;
   int rc;
-  if ((rc = ensure_plan(L, tail + kMaxRows))) return rc;
-  L->host_rows.assign(tail + kMaxRows, RowDesc{0, 0, 0, 0});
+  const size_t nextra = extra ? extra->size() : 0;
+  if ((rc = ensure_plan(L, tail + kMaxRows + nextra))) return rc;
+  L->host_rows.assign(tail + kMaxRows + nextra, RowDesc{0, 0, 0, 0});
   {
     size_t w[4] = {off0, off1, off2, off3};
     for (int b = 0; b < B; ++b) {
@@ -4751,8 +4799,10 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
       for (int t = 0; t + 1 < lens[b]; ++t) L->host_rows[r++] = RowDesc{slots[b], t, (int32_t)ids[(size_t)b * P_max + t], 0};
     }
   }
-  for (int b = 0; b < B; ++b)
-    L->host_rows[tail + b] = RowDesc{slots[b], lens[b] - 1, (int32_t)ids[(size_t)b * P_max + lens[b] - 1], 0};   // flags = tokens emitted
+  for (int b = 0, j = 0; b < B; ++b)
+    for (int r = 0; r < (n_ret ? n_ret[b] : 1); ++r, ++j)   // flags = tokens emitted
+      L->host_rows[tail + j] = RowDesc{tail_slots ? tail_slots[j] : slots[b], lens[b] - 1, (int32_t)ids[(size_t)b * P_max + lens[b] - 1], 0};
+  for (size_t e = 0; e < nextra; ++e) L->host_rows[tail + kMaxRows + e] = (*extra)[e];
   SMI_HIP(hipMemcpyAsync(L->plan, L->host_rows.data(), L->host_rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice, st));
   // measured (tools/prefill_time.py, profiles/README.md): 32-row chunks ~1.4 ms each; row-grouped decode GEMMs
   // ~1.5 ms + 9 us/row; the prefill GEMM ~15 ms + 5 us/row (crossover near 3000 rows)
@@ -5019,83 +5069,165 @@ int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens,
 
 int smi_llm_admit_logprobs(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
                            const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out, void* stream) {
+  return smi_llm_admit_forked(L, ids, lens, n, P_max, nullptr, params, pens, want_lp, slots_out, stream);
+}
+
+// n_ret[b] takes of prompt b; the records are per take (N = sum of n_ret).  n_ret = null or all ones: the plain admission.
+int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
+                         const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out,
+                         void* stream) {
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
-  SMI_REQUIRE(n >= 1 && L->B + n <= L->cfg.max_slots && L->B + n <= kMaxRows, "smi_llm_admit: %d new + %d live sequences exceed %d slots", n,
-              L->B, L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows);
-  { const int rcs = validate_sampling(params, n); if (rcs) return rcs; }   // nothing touched yet
+  const int slot_cap = L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows;
+  int N = n;   // output sequences (takes)
+  bool forked = false;
+  if (n_ret && n >= 1) {
+    N = 0;
+    for (int b = 0; b < n; ++b) {
+      SMI_REQUIRE(n_ret[b] >= 1 && n_ret[b] <= kMaxRows, "smi_llm_admit_forked: n_return[%d]=%d outside 1..%d", b, n_ret[b], kMaxRows);
+      N += n_ret[b];
+      forked |= n_ret[b] > 1;
+    }
+  }
+  SMI_REQUIRE(n >= 1 && L->B + N <= slot_cap, "smi_llm_admit: %d new + %d live sequences exceed %d slots", N, L->B, slot_cap);
+  { const int rcs = validate_sampling(params, N); if (rcs) return rcs; }   // nothing touched yet
   if (pens)
-    for (int b = 0; b < n; ++b) { const int rcp = validate_penalty(L, pens[b], b); if (rcp) return rcp; }
+    for (int j = 0; j < N; ++j) { const int rcp = validate_penalty(L, pens[j], j); if (rcp) return rcp; }
   if (want_lp)
-    for (int b = 0; b < n; ++b)
-      SMI_REQUIRE(want_lp[b] == 0 || want_lp[b] == 1, "smi_llm_admit_logprobs: return_log_probs[%d]=%d must be 0 or 1", b, want_lp[b]);
+    for (int j = 0; j < N; ++j)
+      SMI_REQUIRE(want_lp[j] == 0 || want_lp[j] == 1, "smi_llm_admit_logprobs: return_log_probs[%d]=%d must be 0 or 1", j, want_lp[j]);
   hipStream_t st = (hipStream_t)stream;
   int rc;
   std::vector<RowDesc> live;
   if ((rc = session_live_rows(L, live, st))) return rc;
-  int32_t slots[kMaxRows];
+  int32_t slots[kMaxRows];   // one per take, lowest free first
   int k = 0;
-  for (int sl = 0; sl < L->cfg.max_slots && k < n; ++sl)
+  for (int sl = 0; sl < L->cfg.max_slots && k < N; ++sl)
     if (!L->slot_busy[sl]) slots[k++] = sl;
-  SMI_REQUIRE(k == n, "smi_llm_admit: no free KV slot");
+  SMI_REQUIRE(k == N, "smi_llm_admit: no free KV slot");
   if ((rc = validate_prompts(L, ids, lens, n, P_max))) return rc;   // nothing touched yet
-  if (L->paged && (rc = pages_ensure(L, slots, lens, n, st))) return rc;   // all or nothing: a short pool admits nobody
+  // take j belongs to prompt src[j]; the first take of a prompt is its leader, the slot its prompt rows are prefilled in
+  int32_t src[kMaxRows], lead[kMaxRows], lens_j[kMaxRows];
+  for (int b = 0, j = 0; b < n; ++b) {
+    lead[b] = slots[j];
+    for (int r = 0; r < (n_ret ? n_ret[b] : 1); ++r, ++j) { src[j] = b; lens_j[j] = lens[b]; }
+  }
+  const int P = L->paged ? 1 << L->pshift : 0;
+  auto shared_pages = [&](int b) { return (lens[b] - 1) >> L->pshift; };   // S = floor((L - 1) / P): positions < S P <= L - 1
+  if (L->paged && forked) {   // the whole demand first: a short pool takes nothing (pages_ensure below cannot fail after this)
+    long need = 0;
+    for (int b = 0; b < n; ++b) {
+      const int own = (lens[b] + P - 1) >> L->pshift;
+      need += own + (long)(n_ret[b] - 1) * (own - shared_pages(b));
+    }
+    if (need > (long)L->free_pages.size()) {
+      smi_set_error("KV page pool exhausted: %ld more pages of %d tokens needed, %zu of %d free (retire a sequence or enlarge kv_pages)",
+                    need, P, L->free_pages.size(), L->cfg.kv_pages);
+      return SMI_ENOMEM;
+    }
+  }
+  if (L->paged && (rc = pages_ensure(L, lead, lens, n, st))) return rc;   // all or nothing: a short pool admits nobody
+  if (L->paged && forked) {   // followers: the leader's first S pages shared, their own pages from page S on
+    int32_t fsl[kMaxRows], flen[kMaxRows];
+    int nf = 0;
+    for (int j = 0; j < N; ++j)
+      if (slots[j] != lead[src[j]]) {
+        pages_share(L, lead[src[j]], slots[j], shared_pages(src[j]));
+        fsl[nf] = slots[j]; flen[nf++] = lens_j[j];
+      }
+    if ((rc = pages_ensure(L, fsl, flen, nf, st))) {
+      for (int j = 0; j < N; ++j) pages_release(L, slots[j]);
+      return rc;
+    }
+  }
   const int seq0 = L->admit_seq;
   int32_t old_seqid[kMaxRows];
   SampRec old_rec[kMaxRows];
   PenRec old_pen[kMaxRows];
   int32_t old_lp[kMaxRows];
-  for (int b = 0; b < n; ++b) { old_seqid[b] = L->hctl.seqid[slots[b]]; L->hctl.seqid[slots[b]] = L->admit_seq++; }
+  for (int j = 0; j < N; ++j) { old_seqid[j] = L->hctl.seqid[slots[j]]; L->hctl.seqid[slots[j]] = L->admit_seq++; }
   // the records go up with the sequence numbers, before the admission's own step: its finalize emits the first token
-  for (int b = 0; b < n; ++b) {
-    old_rec[b] = L->hctl.samp[slots[b]];
-    L->hctl.samp[slots[b]] = samp_record(params ? &params[b] : nullptr, L->cfg.vocab_size);
-    L->slot_samp[slots[b]] = L->hctl.samp[slots[b]].mode == SMI_SAMPLING_SAMPLE;
-    old_pen[b] = L->hctl.pen[slots[b]];
-    L->hctl.pen[slots[b]] = pen_record(pens ? &pens[b] : nullptr);
-    L->slot_pen[slots[b]] = L->hctl.pen[slots[b]].on;
-    old_lp[b] = L->hctl.lp[slots[b]];
-    L->hctl.lp[slots[b]] = want_lp ? want_lp[b] : 0;
-    L->slot_lp[slots[b]] = L->hctl.lp[slots[b]];
+  for (int j = 0; j < N; ++j) {
+    old_rec[j] = L->hctl.samp[slots[j]];
+    L->hctl.samp[slots[j]] = samp_record(params ? &params[j] : nullptr, L->cfg.vocab_size);
+    L->slot_samp[slots[j]] = L->hctl.samp[slots[j]].mode == SMI_SAMPLING_SAMPLE;
+    old_pen[j] = L->hctl.pen[slots[j]];
+    L->hctl.pen[slots[j]] = pen_record(pens ? &pens[j] : nullptr);
+    L->slot_pen[slots[j]] = L->hctl.pen[slots[j]].on;
+    old_lp[j] = L->hctl.lp[slots[j]];
+    L->hctl.lp[slots[j]] = want_lp ? want_lp[j] : 0;
+    L->slot_lp[slots[j]] = L->hctl.lp[slots[j]];
   }
-  auto undo = [&]() {   // nothing was admitted: sequence numbers, records and pages as before (the device copy is rewritten by the next admission)
-    for (int b = 0; b < n; ++b) {
-      L->hctl.seqid[slots[b]] = old_seqid[b]; L->hctl.samp[slots[b]] = old_rec[b]; L->slot_samp[slots[b]] = 0;
-      L->hctl.pen[slots[b]] = old_pen[b]; L->slot_pen[slots[b]] = 0;
-      L->hctl.lp[slots[b]] = old_lp[b]; L->slot_lp[slots[b]] = 0;
+  // undo: nothing was admitted -- sequence numbers, records and pages (and page references) as before (the device copy is
+  // rewritten by the next admission)
+  auto undo = [&]() {
+    for (int j = 0; j < N; ++j) {
+      L->hctl.seqid[slots[j]] = old_seqid[j]; L->hctl.samp[slots[j]] = old_rec[j]; L->slot_samp[slots[j]] = 0;
+      L->hctl.pen[slots[j]] = old_pen[j]; L->slot_pen[slots[j]] = 0;
+      L->hctl.lp[slots[j]] = old_lp[j]; L->slot_lp[slots[j]] = 0;
     }
     L->admit_seq = seq0;
     if (L->paged)
-      for (int b = 0; b < n; ++b) pages_release(L, slots[b]);
+      for (int j = 0; j < N; ++j) pages_release(L, slots[j]);
   };
   if (hipMemcpyAsync(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice, st) != hipSuccess) {
     undo();
     smi_set_error("smi_llm_admit: uploading the generation controls failed");
     return SMI_EHIP;
   }
+  // the fork copy's work list: each follower gets the leader's positions it does not share -- 0 .. L-2 (contiguous), S P .. L-2
+  // (paged); position L-1 and on are written by the follower's own steps
+  std::vector<RowDesc> fork;
+  int fork_span = 0;
+  if (forked)
+    for (int j = 0; j < N; ++j) {
+      const int b = src[j], p0 = L->paged ? shared_pages(b) << L->pshift : 0, p1 = lens[b] - 1;
+      if (slots[j] == lead[b] || p1 <= p0) continue;
+      fork.push_back(RowDesc{lead[b], slots[j], p0, p1});
+      fork_span = p1 - p0 > fork_span ? p1 - p0 : fork_span;
+    }
   size_t tail = 0;
-  if ((rc = prefill_prompts(L, ids, lens, n, P_max, slots, &tail, st))) { undo(); return rc; }
+  if ((rc = prefill_prompts(L, ids, lens, n, P_max, lead, &tail, st, n_ret, slots, fork.empty() ? nullptr : &fork))) { undo(); return rc; }
+  if (!fork.empty()) {   // after the leaders' prompt rows, before the takes' first step
+    ForkP fp;
+    fp.work = (const int4*)(L->plan + tail + kMaxRows);
+    fp.kcache = (unsigned char*)L->kcache; fp.vcache = (unsigned char*)L->vcache;
+    fp.piece_shift = L->cfg.kv_dtype ? 4 : 3;
+    fp.layer_bytes = L->kv_layer_elems * (L->cfg.kv_dtype ? 4 : 2);
+    fp.n_kv = L->cfg.num_kv_heads; fp.max_pos = L->cfg.max_positions;
+    fp.km = kv_map(L);
+    const dim3 grid((unsigned)(((size_t)fork_span << fp.piece_shift) + 255) / 256, (unsigned)fork.size(),
+                    (unsigned)(L->cfg.num_layers * 2 * L->cfg.num_kv_heads));
+    hipLaunchKernelGGL(k_kv_fork, grid, dim3(256), 0, st, fp);
+    SMI_LAUNCH_CHECK();
+  }
   // first token of the new sequences: one step over the new rows alone
   int32_t zeros[kMaxRows] = {0};
-  for (int b = 0; b < n; ++b) {
-    SMI_HIP(hipMemcpyAsync(L->count + slots[b], zeros, 4, hipMemcpyHostToDevice, st));
-    SMI_HIP(hipMemcpyAsync(L->finished + slots[b], zeros, 4, hipMemcpyHostToDevice, st));
+  for (int j = 0; j < N; ++j) {
+    SMI_HIP(hipMemcpyAsync(L->count + slots[j], zeros, 4, hipMemcpyHostToDevice, st));
+    SMI_HIP(hipMemcpyAsync(L->finished + slots[j], zeros, 4, hipMemcpyHostToDevice, st));
   }
   SMI_HIP(hipMemcpyAsync(L->rows, L->plan + tail, kMaxRows * sizeof(RowDesc), hipMemcpyDeviceToDevice, st));
-  if ((rc = pen_histories(L, ids, lens, n, P_max, slots, st))) return rc;
+  if (forked) {   // every take's history row gets its own prompt's ids
+    std::vector<int64_t> eids((size_t)N * P_max);
+    for (int j = 0; j < N; ++j) memcpy(&eids[(size_t)j * P_max], ids + (size_t)src[j] * P_max, (size_t)P_max * 8);
+    if ((rc = pen_histories(L, eids.data(), lens_j, N, P_max, slots, st))) return rc;
+  } else if ((rc = pen_histories(L, ids, lens, n, P_max, slots, st))) {
+    return rc;
+  }
   L->graph = nullptr;
   const int oldB = L->B;
-  L->B = n;
+  L->B = N;
   L->identity_slots = 1;
-  for (int b = 0; b < n; ++b) L->identity_slots &= slots[b] == b;
-  if ((rc = launch_embed(L, L->rows, n, st)) || (rc = launch_step(L, n, st))) { L->B = oldB; return rc; }
+  for (int j = 0; j < N; ++j) L->identity_slots &= slots[j] == j;
+  if ((rc = launch_embed(L, L->rows, N, st)) || (rc = launch_step(L, N, st))) { L->B = oldB; return rc; }
   std::vector<RowDesc> fresh;
   if ((rc = session_live_rows(L, fresh, st))) return rc;
-  for (int b = 0; b < n; ++b) {
-    live.push_back(fresh[b]);
-    L->slot_busy[slots[b]] = 1;
-    L->slot_len[slots[b]] = lens[b] + 1;
-    slots_out[b] = slots[b];
+  for (int j = 0; j < N; ++j) {
+    live.push_back(fresh[j]);
+    L->slot_busy[slots[j]] = 1;
+    L->slot_len[slots[j]] = lens_j[j] + 1;
+    slots_out[j] = slots[j];
   }
   return session_set_rows(L, live, st);
 }

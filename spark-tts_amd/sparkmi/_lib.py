@@ -115,6 +115,8 @@ SYMBOLS = {
     "smi_llm_admit_logprobs": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(SampleParams), _P(PenaltyParams),
                                     _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_slots_logprobs": (_I, [_VP, _P(C.c_int32), _I, _P(C.c_float), _I, _P(C.c_int32), _VP]),
+    "smi_llm_admit_forked": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams), _P(PenaltyParams),
+                                  _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_status": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_forward_logits": (_I, [_VP, _P(C.c_int64), _I, _VP, _VP]),
     "smi_llm_steps": (_I, [_VP]),

@@ -10,6 +10,7 @@ top-p → multinomial chain on the device (``k_sample``).
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import json
 import warnings
 from pathlib import Path
@@ -32,6 +33,39 @@ PENALTY_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "
 PENALTY_NEUTRAL = dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0)
 # key of the per-token log-probabilities, in the same dicts (smi_llm_admit_logprobs; include/sparkmi.h states the semantics)
 LOGPROB_KEYS = ("return_log_probs",)
+
+
+# key of a request's number of takes (TensorRT-LLM's num_return_sequences; smi_llm_admit_forked): SparkLLM.serve and SparkTTS
+# requests take it out of the dict before its records are built
+FORK_KEY = "num_return_sequences"
+
+
+def num_returns(v, what: str = FORK_KEY) -> int:
+    """A number of takes: an int >= 1 (a bool is refused); ValueError otherwise, before any device call."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+        raise ValueError(f"{what} must be an int >= 1, not {v!r}")
+    return int(v)
+
+
+def expand_takes(sampling: Optional[Sequence[Optional[Mapping]]], n_return: Sequence[int]):
+    """The per-take request dicts of a forked admission, prompt-major (prompt 0's takes, then prompt 1's, ...), or None when
+    ``sampling`` is None.  A dict with its own ``seed`` gives take j the seed ``seed + j`` (mod 2^64) -- otherwise every take
+    would draw the same tokens; every other key is copied as is."""
+    if sampling is None:
+        return None
+    sampling = list(sampling)
+    if len(sampling) != len(n_return):
+        raise ValueError(f"sampling: {len(sampling)} entries for {len(n_return)} prompts")
+    out: List[Optional[dict]] = []
+    for d, k in zip(sampling, n_return):
+        for j in range(k):
+            if d is None:
+                out.append(None)
+            elif d.get("seed") is not None:
+                out.append(dict(d, seed=(int(d["seed"]) + j) % 2 ** 64))
+            else:
+                out.append(dict(d))
+    return out
 
 
 def logprob_flags(requests: Optional[Sequence[Optional[Mapping]]], n: int):
@@ -331,13 +365,19 @@ class SparkLLM:
         eos_arr, n_eos = self._eos_args(eos_token_id)
         self._lib.check(self._lib.smi_llm_session_begin(self._h, eos_arr, n_eos, self._stream()), "smi_llm_session_begin")
 
-    def admit(self, prompts: Sequence[Sequence[int]], sampling: Optional[Sequence[Optional[Mapping]]] = None) -> List[int]:
+    def admit(self, prompts: Sequence[Sequence[int]], sampling: Optional[Sequence[Optional[Mapping]]] = None,
+              n_return: Optional[Sequence[int]] = None) -> List[int]:
         """Prefill new prompts into free KV slots (first token emitted); returns their slot ids.  ``sampling``: one dict
         (``SAMPLING_KEYS``, ``PENALTY_KEYS``) or None per prompt -- that sequence's own token selection (``sampling_records``)
         and logits penalties (``penalty_records``); None everywhere (the default): every sequence follows ``set_sampling``,
         unpenalised.  A request with any non-neutral penalty goes through ``smi_llm_admit_penalized``; an admission in which
         some request carries ``return_log_probs`` (``LOGPROB_KEYS``, a bool) through ``smi_llm_admit_logprobs``, and the
-        flagged sequences' log-probabilities are read with ``slots_logprobs``."""
+        flagged sequences' log-probabilities are read with ``slots_logprobs``.
+        ``n_return``: one int >= 1 per prompt -- that many takes of the prompt, its prompt prefilled once
+        (``smi_llm_admit_forked``); ``sampling`` stays one dict per prompt and is expanded per take (``expand_takes``).  The
+        result is then the flat, prompt-major slot list; None (the default) keeps today's route and bits."""
+        if n_return is not None:
+            return self._admit_forked(prompts, sampling, n_return)
         n = len(prompts)
         lens = np.array([len(p) for p in prompts], dtype=np.int32)
         pmax = int(lens.max())
@@ -366,6 +406,33 @@ class SparkLLM:
             self._lib.check(self._lib.smi_llm_admit_sampled(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
                                                        lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs,
                                                        slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_admit_sampled")
+        return slots.tolist()
+
+    def _admit_forked(self, prompts, sampling, n_return) -> List[int]:
+        n_return = [num_returns(k, f"n_return[{b}]") for b, k in enumerate(n_return)]
+        n = len(prompts)
+        if len(n_return) != n or n == 0:
+            raise ValueError(f"n_return: {len(n_return)} entries for {n} prompts")
+        N = sum(n_return)
+        if N > self.max_slots:
+            raise ValueError(f"{N} takes > max_slots={self.max_slots}")
+        takes = expand_takes(sampling, n_return)
+        recs = sampling_records(takes, N, self._sampling)
+        pens = penalty_records(takes, N)
+        flags = logprob_flags(takes, N)
+        lens = np.array([len(p) for p in prompts], dtype=np.int32)
+        pmax = int(lens.max())
+        ids = np.zeros((n, pmax), dtype=np.int64)
+        for b, p in enumerate(prompts):
+            ids[b, : len(p)] = np.asarray(p, dtype=np.int64)
+        nret = np.asarray(n_return, dtype=np.int32)
+        slots = np.zeros(N, dtype=np.int32)
+        self._lib.check(self._lib.smi_llm_admit_forked(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
+                                                      nret.ctypes.data_as(C.POINTER(C.c_int32)), recs, pens,
+                                                      None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                        "smi_llm_admit_forked")
         return slots.tolist()
 
     def retire(self, slot: int) -> None:
@@ -428,26 +495,61 @@ class SparkLLM:
         requests are admitted whenever a slot is free, so short utterances never wait for long ones.  The optional fifth
         element is that request's own token selection and penalties (``admit``); without it the request follows
         ``set_sampling``, unpenalised.  ``return_log_probs=True`` flags every request, a ``return_log_probs`` key one
-        request: a flagged request yields (key, (new ids, float32 log-probabilities, one per id))."""
+        request: a flagged request yields (key, (new ids, float32 log-probabilities, one per id)).  A ``num_return_sequences``
+        key (``FORK_KEY``, an int >= 1, at most ``max_live``) asks for that many takes of the prompt, prefilled once
+        (``admit(n_return=...)``): the request is admitted whole once that many slots are free and yields (key, [one result
+        per take]) when all of its takes have finished."""
         it = iter(requests)
         if return_log_probs:
             it = (tuple(r[:4]) + (dict(r[4] if len(r) > 4 and r[4] is not None else {}, return_log_probs=True),) for r in it)
         max_live = min(max_live or self.max_slots, self.max_slots)
-        live = {}                      # slot -> (key, max_new)
+
+        def split(r):   # (request without the takes key, takes or None)
+            d = r[4] if len(r) > 4 else None
+            if d is None or FORK_KEY not in d:
+                return r, None
+            k = num_returns(d[FORK_KEY])
+            if k > max_live:
+                raise ValueError(f"{FORK_KEY}={k} > max_live={max_live}")
+            d = {key: v for key, v in d.items() if key != FORK_KEY}
+            return tuple(r[:4]) + (d or None,), k
+
+        live = {}                      # slot -> (key, max_new, log-probabilities wanted, (group, take) or None)
+        groups = {}                    # group -> [key, take results]
+        group_ids = itertools.count()
         pending = next(it, None)
+        pending = split(pending) if pending is not None else None
         started = False
         while pending is not None or live:
             batch = []
-            while pending is not None and len(live) + len(batch) < max_live:
+            while pending is not None and len(live) + sum(b[1] or 1 for b in batch) + (pending[1] or 1) <= max_live:
                 batch.append(pending)
                 pending = next(it, None)
+                pending = split(pending) if pending is not None else None
             if batch:                      # all free slots are filled by ONE admission (one prefill launch sequence)
                 if not started:
-                    self.session_begin(batch[0][3])
+                    self.session_begin(batch[0][0][3])
                     started = True
-                slots = self.admit([list(b[1]) for b in batch], [b[4] if len(b) > 4 else None for b in batch])
-                for slot, b in zip(slots, batch):
-                    live[slot] = (b[0], int(b[2]), logprob_requested(b[4] if len(b) > 4 else None))
+                reqs = [b[0] for b in batch]
+                samp = [r[4] if len(r) > 4 else None for r in reqs]
+                if any(b[1] is not None for b in batch):
+                    nret = [b[1] or 1 for b in batch]
+                    slots = self.admit([list(r[1]) for r in reqs], samp, n_return=nret)
+                    takes = expand_takes(samp, nret)
+                    j = 0
+                    for (r, k) in batch:
+                        g = None
+                        if k is not None:
+                            g = next(group_ids)
+                            groups[g] = [r[0], [None] * k]
+                        for t in range(k or 1):
+                            live[slots[j]] = (r[0], int(r[2]), logprob_requested(takes[j] if takes is not None else None),
+                                              None if g is None else (g, t))
+                            j += 1
+                else:
+                    slots = self.admit([list(r[1]) for r in reqs], samp)
+                    for slot, r, d in zip(slots, reqs, samp):
+                        live[slot] = (r[0], int(r[2]), logprob_requested(d), None)
             self.decode(decode_stride)
             cnt, fin = self.status()
             leave = [slot for slot in live if fin[slot] or cnt[slot] >= live[slot][1]]
@@ -458,12 +560,21 @@ class SparkLLM:
                 lps = dict(zip(flagged, self.slots_logprobs(flagged, cap))) if flagged else {}
                 self.retire_many(leave)
                 for slot, (toks, _) in zip(leave, got):
-                    key, max_new, want_lp = live.pop(slot)
-                    yield key, ((toks[:max_new], lps[slot][:max_new]) if want_lp else toks[:max_new])
+                    key, max_new, want_lp, take = live.pop(slot)
+                    res = (toks[:max_new], lps[slot][:max_new]) if want_lp else toks[:max_new]
+                    if take is None:
+                        yield key, res
+                        continue
+                    g, t = take
+                    groups[g][1][t] = res
+                    if all(x is not None for x in groups[g][1]):
+                        key, results = groups.pop(g)
+                        yield key, results
 
     def generate_ragged(self, prompts: Sequence[Sequence[int]], max_new_tokens: Sequence[int], eos_token_id: EosLike = None,
                         check_every: int = 16, on_prefilled=None,
-                        sampling: Optional[Sequence[Optional[Mapping]]] = None, return_log_probs: bool = False) -> List:
+                        sampling: Optional[Sequence[Optional[Mapping]]] = None, return_log_probs: bool = False,
+                        n_return: Optional[Sequence[int]] = None) -> List:
         """One batch of prompts with PER-ROW token budgets, rows retired as they finish (their budget, or eos): the decode
         step then runs on the rows still alive instead of padding finished ones to the longest (HF ``generate`` pads; the
         reference's TensorRT-LLM deployment batches in flight, run.sh:50-65).  Rows are independent in every kernel, so
@@ -472,18 +583,31 @@ class SparkLLM:
         sampler set by ``set_sampling``, or per prompt by ``sampling`` (as ``admit``: sampling and penalty keys); ``on_prefilled()`` is called after the
         prompts' prefill was enqueued.  ``return_log_probs=True`` flags every row, a ``return_log_probs`` key in ``sampling``
         one row: a flagged row's result is (tokens, float32 log-probabilities, one per token; include/sparkmi.h,
-        smi_llm_admit_logprobs)."""
+        smi_llm_admit_logprobs).  ``n_return``: one int >= 1 per prompt -- that many takes of it (``admit``), each with the
+        prompt's budget; ``result[b]`` is then a list of ``n_return[b]`` results, each in the shape above."""
         n = len(prompts)
         if return_log_probs:
             sampling = [dict(d or {}, return_log_probs=True) for d in (sampling if sampling is not None else [None] * n)]
         want = [int(w) for w in max_new_tokens]
-        if n != len(want) or n > self.max_slots or min(want) < 1:
-            raise ValueError("generate_ragged: one budget >= 1 per prompt, at most max_slots prompts")
+        if n_return is not None:
+            n_return = [num_returns(k, f"n_return[{b}]") for b, k in enumerate(n_return)]
+            if len(n_return) != n:
+                raise ValueError(f"n_return: {len(n_return)} entries for {n} prompts")
+        rows = sum(n_return) if n_return is not None else n
+        if n != len(want) or rows > self.max_slots or min(want) < 1:
+            raise ValueError("generate_ragged: one budget >= 1 per prompt, at most max_slots sequences")
         if max(len(p) + w for p, w in zip(prompts, want)) > self.max_positions:
             raise ValueError("generate_ragged: prompt + budget exceeds max_positions")
         eos = self._eos_list(eos_token_id)
         self.session_begin(eos or None)
-        slots = self.admit([list(p) for p in prompts], sampling)
+        if n_return is not None:
+            slots = self.admit([list(p) for p in prompts], sampling, n_return=n_return)
+            owner = [b for b, k in enumerate(n_return) for _ in range(k)]
+            row_samp = expand_takes(sampling, n_return)
+        else:
+            slots = self.admit([list(p) for p in prompts], sampling)
+            owner, row_samp = list(range(n)), sampling
+        row_want = [want[b] for b in owner]
         if on_prefilled is not None:
             on_prefilled()
         live = {slot: i for i, slot in enumerate(slots)}
@@ -492,26 +616,31 @@ class SparkLLM:
             fin = None
             if eos:
                 _, fin = self.status()             # one device round trip
-            leave = [slot for slot, i in live.items() if done >= want[i] or (fin is not None and fin[slot])]
+            leave = [slot for slot, i in live.items() if done >= row_want[i] or (fin is not None and fin[slot])]
             if leave:
                 self.retire_many(leave)            # enqueued behind the steps so far: no host round trip
                 for slot in leave:
                     del live[slot]
             if not live:
                 break
-            steps = min(want[i] for i in live.values()) - done
+            steps = min(row_want[i] for i in live.values()) - done
             if eos:
                 steps = min(steps, check_every)
             self.decode(steps)
             done += steps
         # histories are per KV slot and stay until a slot is reused: all rows in one round trip
         got = self.slots_tokens(slots, max(want))
-        res = [t[: want[i]] for i, (t, _) in enumerate(got)]
-        flagged = [i for i in range(n) if logprob_requested(sampling[i] if sampling is not None else None)]
+        res = [t[: row_want[i]] for i, (t, _) in enumerate(got)]
+        flagged = [i for i in range(len(slots)) if logprob_requested(row_samp[i] if row_samp is not None else None)]
         if flagged:
             for i, lp in zip(flagged, self.slots_logprobs([slots[i] for i in flagged], max(want))):
-                res[i] = (res[i], lp[: want[i]])
-        return res
+                res[i] = (res[i], lp[: row_want[i]])
+        if n_return is None:
+            return res
+        out: List[List] = [[] for _ in range(n)]
+        for i, b in enumerate(owner):
+            out[b].append(res[i])
+        return out
 
     # ------------------------------------------------------------------ test / bench entries
     def forward_logits(self, ids: Sequence[int]) -> torch.Tensor:

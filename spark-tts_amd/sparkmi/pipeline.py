@@ -19,7 +19,8 @@ import torch
 from . import _lib
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
-from .llm import LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config, penalty_neutral
+from .llm import (FORK_KEY, LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config, num_returns,
+                  penalty_neutral)
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
 from .streaming import ChunkScheduler
@@ -40,6 +41,18 @@ def _request_sampling(r: dict) -> Optional[dict]:
         if r.get(k):
             d[k] = True
     return d or None
+
+
+def _take_counts(requests: Sequence[dict], max_batch: int) -> Optional[List[int]]:
+    """The ``num_return_sequences`` of every request (1 where a request leaves the key out), or None when no request carries
+    it (today's route).  Checked before any device call: each an int >= 1 (a bool is refused), all takes together at most
+    ``max_batch``."""
+    if not any(FORK_KEY in r for r in requests):
+        return None
+    n = [num_returns(r[FORK_KEY], f"request {i}: {FORK_KEY}") if FORK_KEY in r else 1 for i, r in enumerate(requests)]
+    if sum(n) > max_batch:
+        raise ValueError(f"{sum(n)} takes (num_return_sequences) > max_batch={max_batch}")
+    return n
 
 
 def _lp_info(toks: Sequence[int], lps: np.ndarray) -> dict:
@@ -151,17 +164,25 @@ class SparkTTS:
                   do_sample: bool = True, max_new_tokens: int = 3000, seed: Optional[int] = None,
                   prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                  min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False):
+                  min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False,
+                  num_return_sequences: int = 1):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate``.  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
         penalty.  ``return_log_probs=True``: (waveform, info) with info = {``token_ids``: the generated ids,
         ``output_log_probs``: float32, one per id (include/sparkmi.h, smi_llm_admit_logprobs), ``cum_log_prob``: their
-        float64 sum}; the waveform is the one the call gives without it."""
+        float64 sum}; the waveform is the one the call gives without it.  ``num_return_sequences=n > 1``: a list of n takes
+        (waveforms, or (waveform, info) pairs), the prompt prefilled once (include/sparkmi.h, smi_llm_admit_forked) and the
+        takes vocoded together -- the same as ``inference_batch`` of the request n times; with its own ``seed``, take j is
+        the call alone with ``seed + j``."""
+        n_takes = num_returns(num_return_sequences)
+        if n_takes > self._max_batch:
+            raise ValueError(f"num_return_sequences={n_takes} > max_batch={self._max_batch}")
         pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, min_new_tokens=min_new_tokens, penalize_prompt=penalize_prompt)
         return self.inference_batch([dict(text=text, prompt_speech_path=prompt_speech_path, prompt_text=prompt_text,
-                                          gender=gender, pitch=pitch, speed=speed, prompt_tokens=prompt_tokens, **pen)],
+                                          gender=gender, pitch=pitch, speed=speed, prompt_tokens=prompt_tokens, **pen,
+                                          **({FORK_KEY: n_takes} if n_takes > 1 else {}))],
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                                     max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs)[0]
 
@@ -178,9 +199,12 @@ class SparkTTS:
         Likewise ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``min_new_tokens`` /
         ``penalize_prompt`` (TensorRT-LLM's per-request penalty inputs); neutral values leave the request's route unchanged.
         ``return_log_probs=True`` (every request) or a request's ``return_log_probs`` key: that request's waveform comes as
-        (waveform, info), info as in ``inference``; such a batch runs through the admission path."""
+        (waveform, info), info as in ``inference``; such a batch runs through the admission path.
+        A request's ``num_return_sequences`` key (an int >= 1): that many takes of it, its prompt prefilled once; its result
+        is a list of one result per take.  All takes together are at most ``max_batch``."""
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
+        n_takes = _take_counts(requests, self._max_batch)
         prompts, globals_ = [], []
         # voice-clone requests that come with prompt FILES: all their prompt encodes run side by side (parallel HIP streams)
         need = [i for i, r in enumerate(requests)
@@ -210,7 +234,14 @@ class SparkTTS:
         sampling = [_request_sampling(r) for r in requests]
         if return_log_probs:
             sampling = [dict(d or {}, return_log_probs=True) for d in sampling]
-        if any(sampling):   # (max_batch = the LLM's slots)
+        owner = list(range(len(ids)))   # request of every generated row
+        if n_takes is not None:          # takes of one prompt: one forked admission (SparkLLM.admit(n_return=...))
+            self.model.set_sampling(bool(do_sample), temperature, int(top_k), float(top_p), seed)
+            grouped = self.model.generate_ragged(ids, [max_new_tokens] * len(ids), self._eos, sampling=sampling, n_return=n_takes)
+            owner = [b for b, k in enumerate(n_takes) for _ in range(k)]
+            new = [r for takes in grouped for r in takes]
+            globals_ = [globals_[b] for b in owner]
+        elif any(sampling):   # (max_batch = the LLM's slots)
             self.model.set_sampling(bool(do_sample), temperature, int(top_k), float(top_p), seed)
             new = self.model.generate_ragged(ids, [max_new_tokens] * len(ids), self._eos, sampling=sampling)
         elif len(ids) > 1 and self._eos and len(ids) <= self.model.max_slots:
@@ -251,7 +282,13 @@ class SparkTTS:
         wav = wav.squeeze(1).cpu().numpy()
         hop = self.audio_tokenizer.model.hop
         out = [wav[b, : lens[b] * hop].copy() for b in range(len(sems))]
-        return [(w, infos[b]) if infos[b] is not None else w for b, w in enumerate(out)]
+        out = [(w, infos[b]) if infos[b] is not None else w for b, w in enumerate(out)]
+        if n_takes is None:
+            return out
+        res: List = [[] for _ in requests]
+        for i, b in enumerate(owner):
+            res[b].append(out[i])
+        return [res[b] if FORK_KEY in r else res[b][0] for b, r in enumerate(requests)]
 
     @torch.no_grad()
     def inference_stream(self, text: str, prompt_speech_path: Path = None, prompt_text: str = None,
@@ -320,24 +357,69 @@ class SparkTTS:
         long ones.  Greedy results equal ``inference()`` of the same request.  Per-request ``do_sample`` / ``temperature`` /
         ``top_k`` / ``top_p`` / ``seed`` and penalty keys as in ``inference_batch``.  ``return_log_probs=True`` (every
         request) or a request's ``return_log_probs`` key: that request yields ``(index, waveform, info)``, info as in
-        ``inference`` (up to and including the first eos id, like the waveform's tokens)."""
+        ``inference`` (up to and including the first eos id, like the waveform's tokens).  A request's
+        ``num_return_sequences`` key (an int >= 1, at most ``max_batch``): that many takes of it, admitted together once
+        that many slots are free, its prompt prefilled once; it yields ``(index, [one result per take])`` when all of its
+        takes have finished, each take a waveform or a (waveform, info) pair, vocoded together."""
+        forks: Dict[int, int] = {}   # request index -> takes, for the requests that carry num_return_sequences
+
+        def checked(reqs):   # each request's takes, checked before the request reaches the device
+            for i, r in enumerate(reqs):
+                if FORK_KEY in r:
+                    forks[i] = _take_counts([r], self._max_batch)[0]
+                yield r
+
+        if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
+            for _ in checked(requests):
+                pass
         voc = self.audio_tokenizer.model
         ntok, hop = voc.cfg.spk_token_num, voc.hop
         globals_: Dict[int, Optional[torch.Tensor]] = {}
         self.model.set_sampling(do_sample, temperature, int(top_k), float(top_p), seed)
 
         def llm_requests():
-            for i, r in enumerate(requests):
+            for i, r in enumerate(checked(requests)):
                 if r.get("gender") is not None:
                     prompt, g = self.process_prompt_control(r["gender"], r.get("pitch"), r.get("speed"), r["text"]), None
                 else:
                     prompt, g = self.process_prompt(r["text"], r.get("prompt_speech_path"), r.get("prompt_text"), r.get("prompt_tokens"))
                 globals_[i] = g
                 ids = self.tokenizer([prompt], return_tensors="pt").input_ids[0].tolist()
-                yield i, ids, min(max_new_tokens, self._max_positions - len(ids) - decode_stride), self._eos, _request_sampling(r)
+                d = _request_sampling(r)
+                if FORK_KEY in r:
+                    d = dict(d or {}, **{FORK_KEY: forks[i]})
+                yield i, ids, min(max_new_tokens, self._max_positions - len(ids) - decode_stride), self._eos, d
+
+        def vocode_takes(i, takes):   # one ragged vocoder call for all takes of request i
+            rows, infos = [], []
+            for toks in takes:
+                lps = None
+                if isinstance(toks, tuple):
+                    toks, lps = toks
+                stops = [toks.index(e) for e in self._eos if e in toks]
+                if stops:
+                    toks = toks[: min(stops) + 1]
+                sem, glob = self._parse(toks)
+                g = torch.tensor(glob, dtype=torch.long) if globals_[i] is None else torch.as_tensor(globals_[i]).reshape(-1).long()
+                if g.numel() != ntok:
+                    raise ValueError(f"request {i}: {g.numel()} global tokens, the speaker encoder needs {ntok}")
+                if not sem:
+                    raise ValueError(f"request {i}: the model generated no semantic tokens")
+                rows.append((sem, g))
+                infos.append(None if lps is None else _lp_info(toks, lps[: len(toks)]))
+            lens = [len(sem) for sem, _ in rows]
+            sem_t = torch.zeros((len(rows), max(lens)), dtype=torch.long)
+            for b, (sem, _) in enumerate(rows):
+                sem_t[b, : len(sem)] = torch.tensor(sem)
+            wav = voc.detokenize(sem_t, torch.stack([g for _, g in rows]).unsqueeze(1), lengths=lens).squeeze(1).cpu().numpy()
+            return [(wav[b, : lens[b] * hop].copy(), infos[b]) if infos[b] is not None else wav[b, : lens[b] * hop].copy()
+                    for b in range(len(rows))]
 
         for i, toks in self.model.serve(llm_requests(), max_live=self._max_batch, decode_stride=decode_stride,
                                         return_log_probs=return_log_probs):
+            if i in forks:
+                yield i, vocode_takes(i, toks)
+                continue
             lps = None
             if isinstance(toks, tuple):   # a flagged request: (tokens, log-probabilities)
                 toks, lps = toks
