@@ -22,7 +22,7 @@ weights) -> BiCodec vocoder.  Workloads:
   --clone --batch 8 (configs[4])  each utterance first encodes a 6 s prompt wav on the GPU.
   --gpus N   one rank per GPU: `value` = the same per-rank loop on every rank (weak scaling, N x the work).
              Started without WORLD_SIZE it spawns the N ranks itself (torch.distributed.run, before any
-             GPU call) and exits with their code.  Every line also carries `config4` (configs[3]): the
+             GPU call) and exits with their code.  With --full the line also carries `config4` (configs[3]): the
              256-utterance set (cfg-3-style inputs, seeds 3000+i) dealt over the ranks by
              sparkmi.dist.shard_indices, batches of <= 32 per GPU, one pass = strong scaling.
 
@@ -30,9 +30,17 @@ Weights are synthetic (no checkpoint exists offline), generated on rank 0 and br
 inputs are already in HBM when the timed region starts (prompt ids are ~1 KiB of host data per
 utterance, passed by value at prefill).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant decode kernel, measured live with HIP
-events on the launch stream; `cpu_baseline` times the CPU oracle (a port of the reference's
-PyTorch-CPU arithmetic) on this box's host cores: the whole configs[1] utterance, 1 warm-up + median of 3.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, dumps (--dump-outputs) and prints: its
+`roofline_step` (and `roofline`, a copy of it) comes from HIP events inside the timed region.  `--full` adds everything that
+takes runs of its own:
+  `config4`       the 256-utterance set (above; --no-config4 skips it)
+  `roofline`      for the dominant decode kernel, measured live with HIP events on the launch stream, with the per-kernel
+                  `kernels`, `engine`, sampling / greedy step times, `streaming` (batch 1) and `vocoder_mfma` (--no-probes
+                  skips them and config4)
+  `cpu_baseline`  the CPU oracle (a port of the reference's PyTorch-CPU arithmetic) on the host cores: the whole configs[1]
+                  utterance, 1 warm-up + median of 3, and transformers' own generate() beside it (one rank only;
+                  --no-cpu-baseline skips it)
+The engines are sized for the config4 set whenever --full could run it, so a plain run times the same layouts as --full.
 
 `--dump-outputs DIR` writes what the last timed step returned (waveforms, token ids) as DIR/<name>.npy; the
 inputs depend only on the arguments, so two builds run with the same arguments can be compared file by file.
@@ -70,13 +78,16 @@ def parse():
     ap.add_argument("--kv", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--engine", action="store_true", help="one-row steps through the persistent-layer engine (csrc/smi_eng.h; opt-in A/B: slower than the launch path on MI355X, DESIGN.md 3.7)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probes", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run config4, the per-kernel probes and the CPU baseline (each can be "
+                         "skipped with its --no-* option); a plain run reports the timed steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle and transformers' generate()")
+    ap.add_argument("--no-probes", action="store_true", help="--full: skip the per-kernel probes (and config4)")
     ap.add_argument("--cpu-tokens", type=int, default=150, help="tokens of the CPU-oracle utterance (SURVEY 8d: the whole configs[1] utterance)")
     ap.add_argument("--cpu-runs", type=int, default=3, help="timed CPU-oracle runs (median reported) after one warm-up run")
     ap.add_argument("--uniform", action="store_true", help="--batch > 1 with identical lengths (--prompt-len -> --new-tokens) instead of the ragged configs[2] inputs")
     ap.add_argument("--static-batch", action="store_true", help="ragged batches decode max(N_i) steps on all rows (no retirement of finished rows)")
-    ap.add_argument("--no-config4", action="store_true", help="skip the 256-utterance sharded set (BASELINE configs[3])")
+    ap.add_argument("--no-config4", action="store_true", help="--full: skip the 256-utterance sharded set (BASELINE configs[3])")
     ap.add_argument("--set-size", type=int, default=256, help="utterances of the configs[3] set")
     ap.add_argument("--clone", action="store_true",
                     help="voice-clone path (BASELINE configs[4]): every utterance first encodes a prompt wav on the GPU "
@@ -343,14 +354,17 @@ def main():
     want = [u["n"] for u in utts]
     globs = [u["glob"] for u in utts]
     Nmax, Pmax = max(want), max(len(p) for p in prompts)
-    do_cfg4 = not a.no_config4 and not a.clone and not a.no_probes
-    max_pos = max(Pmax + Nmax, (160 + 180) if do_cfg4 else 0) + 32
+    # sized for the config4 set whenever --full would run it: a plain run times the very layouts a --full run times
+    size_cfg4 = not a.no_config4 and not a.clone and not a.no_probes
+    do_cfg4 = a.full and size_cfg4
+    probes = a.full and not a.no_probes
+    max_pos = max(Pmax + Nmax, (160 + 180) if size_cfg4 else 0) + 32
     if a.clone:
         from sparkmi import config_tok as T
         from sparkmi.encoder import BiCodecEncoder, get_ref_clip
         wcfg, tcfg = T.xlsr53(), T.spark_0p5b_tok()
         max_pos += wcfg.frames(int(16000 * a.prompt_seconds)) + tcfg.spk_token_num
-    max_frames = max(Nmax, 180 if do_cfg4 else 0) + 10
+    max_frames = max(Nmax, 180 if size_cfg4 else 0) + 10
     cs_llm = A.llm_cfg_struct(llm_cfg, B, max_pos, a.kv, not a.no_graph)
     cs_voc = BC.voc_cfg_struct(voc_cfg, B, max_frames)
 
@@ -552,7 +566,7 @@ def main():
             llm32.close()
 
     if rank == 0:
-        log(f"timed: {el:.3f}s for {a.steps} steps -> {value:.0f} samples/s; probing kernels")
+        log(f"timed: {el:.3f}s for {a.steps} steps -> {value:.0f} samples/s" + ("; probing kernels" if probes else ""))
         # ---- roofline: decode step is HBM-bound; algorithmic bytes = weights once + KV read + KV write.  Every row steps
         # through all Nmax - 1 decode steps (rows past their own length are the padding of a static batch).
         wb = llm.step_weight_bytes()
@@ -581,7 +595,7 @@ def main():
                 res["roofline_step"]["traffic"] = (llm_cfg.num_hidden_layers * sum(tk[k]["hbm_bytes_per_launch"] for k in need)
                                                    + tk["lm_head"]["hbm_bytes_per_launch"])
                 res["roofline_step"]["traffic_source"] = tr_src
-        if not a.no_probes:
+        if probes:
             # per-kernel probes, stamps and the sampling-step timing are diagnostics (include/sparkmi_debug.h): they run on a
             # second engine on libsparkmi_diag.so -- the same sources and kernels, same arena -- never on the product library
             # that the timed region above ran on
@@ -692,7 +706,7 @@ def main():
                                            for n, m, f in sorted(vl, key=lambda x: -x[1])[:6]]}
         else:
             res["roofline"] = dict(res["roofline_step"])
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             log("gpu side done; timing the CPU oracle")
             cprompt = np.random.Generator(np.random.PCG64(1234)).integers(0, llm_cfg.vocab_size, size=128).tolist()
             cglob = np.random.Generator(np.random.PCG64(1235)).integers(0, 4096, size=ntok_glob)
