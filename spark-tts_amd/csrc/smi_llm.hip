@@ -220,12 +220,20 @@ __device__ __forceinline__ float smi_ss_lane_sum(const float* sp, int npart, int
   return v;
 }
 
+// One-row decode kernels: every 64-byte line of the kernel arguments is requested at entry, together.  Left to itself the
+// compiler asks for them as they are needed -- the helper test (work_blocks), then the work path's pointers -- and every
+// first touch of a line is a scalar-cache miss: two or three round trips in a row in front of the first weight load.
+__device__ __forceinline__ void smi_kernarg_lines(const GemmP& p) {
+  asm volatile("" ::"s"(p.W), "s"(p.bias), "s"(p.work_blocks), "s"(p.pf.base), "s"(p.Yin), "s"(gridDim.x));
+}
+
 template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int KVF32, int H = 1, int OCC = 1, int LEAN = 0, int NOH = kMaxOHeads>
 __global__ __launch_bounds__(NW * 64, OCC) void k_gemm(GemmP p) {
   static_assert(H == 1 || ((H == 2 || H == 4) && NTB == 1 && EPI == EPI_RESID), "row-split tiles: RESID, one tile per block");
   static_assert(PRO != PRO_FUSEDO || (LEAN == 2 && MT == 1 && EPI == EPI_SWIGLU), "PRO_FUSEDO: the one-row gate_up kernel");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (LEAN == 2) smi_kernarg_lines(p);
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, NW * 64);
     return;
@@ -749,6 +757,7 @@ template <int TPC>
 __global__ __launch_bounds__(256) void k_down1(GemmP p) {
   __shared__ __attribute__((aligned(16))) float red[16 * 4];   // read and written as float4
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  smi_kernarg_lines(p);
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, 256);
     return;
@@ -2103,6 +2112,42 @@ constexpr int kFuseQB = 4;       // fused o_proj: blocks per head -- each repeat
 constexpr int kFuse2Max = 8;     // rows up to which several live rows take the fused attention + o_proj (FUSE = 2: last-arriver head sum)
 constexpr int kFuseOT = 2;       // W_o n tiles per wave (8 waves x 2 x 4 blocks x 16 = hidden sizes up to 1024)
 
+// k_attn's merge step 2, across the waves, for head dim d: each wave's sums rescaled to the block maximum and added in wave
+// order.  Every form of the kernel runs this one piece of code (the fused one-row kernel in each of its o_proj waves), so the
+// sums are the same everywhere.  (pw is requested behind the maximum; its round trip hides under the eight exp2f.)
+__device__ __forceinline__ void attn_merge(const float* wmax, const float (*pw)[kHeadDim], const float* pl, int d,
+                                           float& bm, float& O, float& Ls) {
+  constexpr float LOG2E = 1.4426950408889634f;
+  float wm[kAttnWaves], po[kAttnWaves], pls[kAttnWaves];
+#pragma unroll
+  for (int w = 0; w < kAttnWaves; ++w) { wm[w] = wmax[w]; po[w] = pw[w][d]; pls[w] = pl[w]; }
+  bm = wm[0];
+#pragma unroll
+  for (int w = 1; w < kAttnWaves; ++w) bm = fmaxf(bm, wm[w]);
+  O = 0.f; Ls = 0.f;
+#pragma unroll
+  for (int w = 0; w < kAttnWaves; ++w) {
+    const float sc = exp2f((wm[w] - bm) * LOG2E);   // 0 for a wave that saw no valid token (m_run = NEG)
+    O += po[w] * sc; Ls += pls[w] * sc;
+  }
+}
+
+// ... and the head's output O / Ls of dim d as exact bf16 triples
+__device__ __forceinline__ void attn_merge_split(const float* wmax, const float (*pw)[kHeadDim], const float* pl, int d,
+                                                 uint32_t& hi, uint32_t& mi, uint32_t& lo) {
+  float bm, O, Ls;
+  attn_merge(wmax, pw, pl, d, bm, O, Ls);
+  split3(O / Ls, hi, mi, lo);
+}
+
+// fused o_proj: dim d's triple into the B-operand pieces of the head's 64 values, [half][split][k8][8 bf16]
+__device__ __forceinline__ void attn_put_pieces(unsigned char* xs, int d, uint32_t hi, uint32_t mi, uint32_t lo) {
+  unsigned char* q = xs + (size_t)((d >> 5) * 12 + ((d >> 3) & 3)) * 16 + (d & 7) * 2;
+  *(uint16_t*)q = (uint16_t)hi;
+  *(uint16_t*)(q + 64) = (uint16_t)mi;
+  *(uint16_t*)(q + 128) = (uint16_t)lo;
+}
+
 // 8 waves; a group of LPT lanes owns one token per pass (16-byte K and V pieces per lane, dot product
 // reduced on the DPP path), UNR passes of loads in flight together (256 tokens per chunk with bf16
 // KV).  Softmax runs per chunk against a block-wide running max (one LDS word per wave, one barrier),
@@ -2116,8 +2161,9 @@ constexpr int kFuseOT = 2;       // W_o n tiles per wave (8 waves x 2 x 4 blocks
 // kernel entry, in flight under the whole attention) and leaves a per-head partial of the o_proj; the consumer
 // (k_gemm<PRO_FUSEDO>: gate_up) adds the heads in order, which is the order k_gemm<RESID> with NW = n_heads sums its waves in:
 // one kernel boundary and one cold weight stream less per layer, same bits.
-// The W_o tiles are held by eight EXTRA waves (8..15) that do nothing else: they request their tiles at entry, sit at the
-// block's two barriers while waves 0..7 run the attention exactly as in the plain kernel, then multiply and store.  (Issued
+// The W_o tiles are held by eight EXTRA waves (8..15): they request their tiles at entry, sit at the block's merge barrier
+// while waves 0..7 run the attention exactly as in the plain kernel, then each runs the cross-wave merge (step 2) for itself
+// into a slice of LDS of its own -- no second barrier, the attention waves end at the first -- and multiplies and stores.  (Issued
 // by the attention waves themselves, the cold weight loads either hold q / K / V back -- loads return in issue order -- or,
 // issued behind them, are caught by the compiler's counted waits for K / V.)
 // PG (with ONE != 0): the KV cache is paged -- a token's row comes through the slot's page-table row (one more dependent,
@@ -2146,9 +2192,17 @@ __global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP
   __shared__ __attribute__((aligned(16))) float so[kAttnWaves][TPW][kHeadDim];   // wave-private merge slices
   __shared__ float sl[kAttnWaves][TPW];
   __shared__ float pw[kAttnWaves][kHeadDim], pl[kAttnWaves];
-  __shared__ __attribute__((aligned(16))) unsigned char xsl[FUSE ? 2 * 3 * 4 * 16 : 16];   // FUSE: this head's output as B-operand pieces
+  // FUSE: this head's output as B-operand pieces (FUSE == 1: one copy per o_proj wave, each wave merges for itself)
+  __shared__ __attribute__((aligned(16))) unsigned char xsl[FUSE == 1 ? kAttnWaves * 2 * 3 * 4 * 16 : FUSE ? 2 * 3 * 4 * 16 : 16];
   __shared__ unsigned int s_last;   // FUSE == 2: this block was the last of its (row, quarter) to arrive
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (ONE == 1) {
+    // one row: every 64-byte line of kernel arguments the block reads is requested at entry, together (the compiler asked
+    // for them one after the other -- the helper test, then q / K / V's addresses -- three scalar round trips in a row in
+    // front of the first global load)
+    if constexpr (FUSE) asm volatile("" ::"s"(p.q), "s"(p.work_blocks), "s"(p.Wo), "s"(gridDim.x));
+    else asm volatile("" ::"s"(p.q), "s"(p.work_blocks), "s"(gridDim.x));
+  }
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, (FUSE ? 2 : 1) * kAttnWaves * 64);
     return;
@@ -2175,11 +2229,20 @@ __global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP
         for (int j = 0; j < 2; ++j) wo[i][j] = smi_ldw(&p.Wo[((size_t)(fq * fper + nl) * KTo + j * p.n_heads + fh) * 64 + lane]);
       }
       __syncthreads();   // the attention waves' merge barrier
-      __syncthreads();   // the head's output is in xsl
+      unsigned char* xo = xsl;
+      if constexpr (FUSE == 1) {   // this wave runs the cross-wave merge itself (lane = dim) into its own slice: no second barrier
+        xo = xsl + ow * (2 * 3 * 4 * 16);
+        uint32_t hi, mi, lo;
+        attn_merge_split(wmax, pw, pl, lane, hi, mi, lo);
+        attn_put_pieces(xo, lane, hi, mi, lo);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own LDS writes have landed
+      } else {
+        __syncthreads();   // the head's output is in xsl
+      }
       // MFMA columns 0 / 1 / 2 are the row's hi / mid / lo split terms (one MFMA per k tile instead of three; k_gemm LEAN == 2)
       bf16x8 bo[2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) bo[j] = *(const bf16x8*)(xsl + (size_t)((j * 3 + ((lane & 15) < 3 ? (lane & 15) : 0)) * 4 + (lane >> 4)) * 16);
+      for (int j = 0; j < 2; ++j) bo[j] = *(const bf16x8*)(xo + (size_t)((j * 3 + ((lane & 15) < 3 ? (lane & 15) : 0)) * 4 + (lane >> 4)) * 16);
 #pragma unroll
       for (int i = 0; i < kFuseOT; ++i) {
         const int nl = ow + kAttnWaves * i, nt = fq * fper + nl;
@@ -2336,29 +2399,20 @@ __global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP
     if (lane == 0) { pl[wave] = Ls; wmax[wave] = m_run; }
   }
   __syncthreads();
+  if constexpr (FUSE == 1) return;   // step 2 runs in each o_proj wave (attn_merge_split), the attention waves are done
   if (tid < kHeadDim) {   // step 2, across the waves
-    float bm = wmax[0];
-#pragma unroll
-    for (int w = 1; w < kAttnWaves; ++w) bm = fmaxf(bm, wmax[w]);
-    float O = 0.f, Ls = 0.f;
-#pragma unroll
-    for (int w = 0; w < kAttnWaves; ++w) {
-      const float sc = exp2f((wmax[w] - bm) * LOG2E);   // 0 for a wave that saw no valid token (m_run = NEG)
-      O += pw[w][tid] * sc; Ls += pl[w] * sc;
-    }
     if (!ONE && p.nseg > 1) {   // segment partial at scale exp(-bm); k_attn_merge finishes the row
+      float bm, O, Ls;
+      attn_merge(wmax, pw, pl, tid, bm, O, Ls);
       float* pp = p.part + (((size_t)m * p.n_heads + head) * p.nseg + seg) * 66;
       pp[2 + tid] = O;
       if (tid == 0) { pp[0] = bm; pp[1] = Ls; }
       return;
     }
     uint32_t hi, mi, lo;
-    split3(O / Ls, hi, mi, lo);
-    if constexpr (FUSE) {   // B-operand pieces of this head's 64 values: [half][split][k8][8 bf16]
-      unsigned char* q = xsl + (size_t)((tid >> 5) * 12 + ((tid >> 3) & 3)) * 16 + (tid & 7) * 2;
-      *(uint16_t*)q = (uint16_t)hi;
-      *(uint16_t*)(q + 64) = (uint16_t)mi;
-      *(uint16_t*)(q + 128) = (uint16_t)lo;
+    attn_merge_split(wmax, pw, pl, tid, hi, mi, lo);
+    if constexpr (FUSE) {
+      attn_put_pieces(xsl, tid, hi, mi, lo);
     } else {
       const int Mx = ONE == 1 ? 1 : p.M;
       const size_t ob = xs_off(o_ktile(head, tid, p.n_heads), 0, (tid >> 3) & 3, m, Mx) + (tid & 7) * 2;
@@ -2368,7 +2422,7 @@ __global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP
       *(uint16_t*)(p.xs_out + ob + 2 * pl2) = (uint16_t)lo;
     }
   }
-  if constexpr (FUSE) __syncthreads();   // the o_proj waves take over: xsl holds this head's output
+  if constexpr (FUSE == 2) __syncthreads();   // the o_proj waves take over: xsl holds this head's output
   }   // attention waves
   if constexpr (FUSE == 2) {
     __syncthreads();                          // every o_proj wave of this block has drained its partial stores (vmcnt(0) above)
