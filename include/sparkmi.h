@@ -229,8 +229,9 @@ int smi_llm_admit_penalized(smi_llm* h, const int64_t* ids_host, const int32_t* 
  * smi_llm_admit_penalized).  For every token a flagged sequence emits -- the admission's first token and an eos included --
  * the library keeps one fp32 value
  *     lp = z[tok] - logsumexp(z), over the full vocabulary,
- * where z is the logits token selection saw: the lm_head's fp32 logits after the row's penalties (stages 1-3 above, the -inf
- * of min_new_tokens included), multiplied by the row's 1/temperature when the row samples (its record's, or the handle's for
+ * where z is the logits token selection saw: the lm_head's fp32 logits after the row's allowed-token stage 0
+ * (smi_llm_admit_constrained: -inf outside the set, so the values are normalised over the allowed ids) and penalties
+ * (stages 1-3 above, the -inf of min_new_tokens included), multiplied by the row's 1/temperature when the row samples (its record's, or the handle's for
  * an inheriting row of a sampling handle).  In transformers' terms: log_softmax of the scores after the logits processors
  * and TemperatureLogitsWarper, before TopK / TopP.  A greedy, unpenalised row gets the model's own log_softmax(logits)[tok].
  * The value is NOT renormalised over the top-k / top-p survivors (that variant is not provided); a sampled token's value is
@@ -267,6 +268,32 @@ int smi_llm_slots_logprobs(smi_llm* h, const int32_t* slots, int n, float* out_h
 int smi_llm_admit_forked(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
                          const int32_t* n_return, const smi_sample_params* params, const smi_penalty_params* pens,
                          const int32_t* return_log_probs, int32_t* slots_out, void* stream);
+/* Allowed-token constraints (vLLM's allowed_token_ids; transformers' SuppressTokensLogitsProcessor of the complement).
+ * smi_llm_admit_constrained = smi_llm_admit_forked plus one allow record per OUTPUT sequence ([N], like the other records;
+ * allow = NULL: exactly smi_llm_admit_forked).  The allowed set of a record is the union of the half-open ranges
+ * [lo[i], hi[i]), i < n_ranges.  Stage 0, before the penalty stages 1-3 of smi_llm_admit_penalized: every id outside the
+ * row's set gets logit -inf; selection (arg-max, or temperature -> top-k -> top-p -> draw) then sees only allowed ids, the
+ * admission's first token included.  Log-probabilities (smi_llm_admit_logprobs) are taken over the logits after stage 0, so
+ * they are normalised over the allowed set (SuppressTokensLogitsProcessor placed first among the processors).
+ *   Eos ids are NOT added implicitly: a set without an eos id runs until the token budget runs out.
+ *   Neutral: n_ranges = 0, or ranges that cover [0, vocab_size); that row takes the route and the bits it gets without a record.
+ *   Checked before anything of the handle is touched (SMI_EINVAL, no slot, page, page reference or admission number taken):
+ *   0 <= n_ranges <= SMI_MAX_ALLOW_RANGES, reserved = 0, 0 <= lo[i] < hi[i] <= vocab_size, ranges sorted and disjoint
+ *   (hi[i] <= lo[i + 1]), and with min_new_tokens > 0 the set holds at least one id that is not an eos id.
+ *   Independence: a constrained row's tokens and log-probabilities do not depend on what else is live, bit for bit, with
+ *   either KV dtype, paged or contiguous -- nor on whether its step read only the lm_head rows the constrained rows can emit
+ *   (every row of the step constrained) or the whole table.
+ * Static generation (smi_llm_prefill) has no constraints. */
+#define SMI_MAX_ALLOW_RANGES 16
+typedef struct smi_allow_params {
+  int32_t n_ranges;                     /* 0 .. SMI_MAX_ALLOW_RANGES; 0 = no constraint */
+  int32_t reserved;                     /* 0 */
+  int32_t lo[SMI_MAX_ALLOW_RANGES];     /* first id of range i */
+  int32_t hi[SMI_MAX_ALLOW_RANGES];     /* one past its last id */
+} smi_allow_params;
+int smi_llm_admit_constrained(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
+                              const int32_t* n_return, const smi_sample_params* params, const smi_penalty_params* pens,
+                              const int32_t* return_log_probs, const smi_allow_params* allow, int32_t* slots_out, void* stream);
 int smi_llm_retire(smi_llm* h, int slot, void* stream);
 int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished, void* stream);
 /* Several sequences leave at once with no host round trip (the device row list is compacted in place), and the tokens of

@@ -58,6 +58,13 @@ struct PenRec {
   int32_t on;                     // the record is not neutral: k_penalize processes the row, k_finalize counts its tokens
 };
 
+// One sequence's allowed-token set (smi_allow_params as admitted, 136 bytes): the union of [lo[i], hi[i]), i < n, sorted and
+// disjoint; n = 0: not constrained (a neutral record is stored as n = 0).
+struct AllowRec {
+  int32_t n, pad;
+  int32_t lo[SMI_MAX_ALLOW_RANGES], hi[SMI_MAX_ALLOW_RANGES];
+};
+
 // Generation controls in device memory (written at prefill / session_begin / admit; read by k_finalize and the sampler),
 // so that nothing of them is baked into the captured decode graph: the graph survives from one utterance to the next.
 struct Ctl {
@@ -68,7 +75,16 @@ struct Ctl {
   SampRec samp[SMI_MAX_ROWS];     // per KV slot: the sequence's sampling record (smi_llm_admit_sampled)
   PenRec pen[SMI_MAX_ROWS];       // per KV slot: the sequence's penalty record (smi_llm_admit_penalized)
   int32_t lp[SMI_MAX_ROWS];       // per KV slot: 1 = the sequence returns per-token log-probabilities (smi_llm_admit_logprobs)
+  AllowRec allow[SMI_MAX_ROWS];   // per KV slot: the sequence's allowed-token ranges (smi_llm_admit_constrained; n = 0: none)
 };
+
+// stage 0: the id lies in one of the record's ranges
+__device__ __forceinline__ bool allow_has(const AllowRec* a, int id) {
+  const int n = a->n;
+  bool in = false;
+  for (int r = 0; r < n; ++r) in |= id >= a->lo[r] && id < a->hi[r];
+  return in;
+}
 
 struct KvMap {
   const int32_t* ptab;   // [slots][ppslot] page ids, or null
@@ -141,6 +157,10 @@ struct GemmP {
   int kseg;
   float4* slab;
   int slab_mt;           // m-tiles of the whole launch (slab indexing)
+  // restricted lm_head (k_lm / k_lm32 with RT = 1): the vocabulary tiles come through tlist = {count, tile indices ascending}, and
+  // the epilogue masks the ids outside each row's own ranges (ctl->allow of the row's slot)
+  const int* tlist;
+  const Ctl* ctl;
 };
 // piece index of `lane` inside a 1 KiB weight tile (see GemmP::wperm)
 __device__ __forceinline__ int smi_wlane(int lane, int wperm) {
@@ -1721,8 +1741,26 @@ __global__ __launch_bounds__(256, TWO ? 2 : 1) void k_pgemm(GemmP p) {
 // ------------------------------------------------------------------------------------------
 // HV = 2: two groups of four waves share a block and the weight stream (the second group's tile loads hit L2); group h
 // owns rows m0 + 16 h .. and does exactly what the HV = 1 kernel does for 16 rows, so the logits are the same bits.
-template <int HV>
-__global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups, int m0_launch) {
+// RT = 1 (restricted lm_head, every row of the step constrained): group g's two vocabulary tiles are entries 2g, 2g + 1 of the
+// device tile list p.tlist (the union of the rows' allowed tiles) instead of tiles 2g, 2g + 1; the group count is read from the
+// list.  A tile's chains, wave map and reduction are those of the full kernel, so every logit computed is the same bits; the
+// epilogue then sets the ids outside the row's own ranges to -inf before the logits store and the running arg-max.
+// Clamped list entries: lm_tile.
+__device__ __forceinline__ int lm_tile(const int* tlist, int idx) {
+  const int c = tlist[0];
+  idx = idx < c ? idx : c - 1;
+  return tlist[1 + (idx > 0 ? idx : 0)];
+}
+// RT epilogue: the four logits of ids n .. n + 3 of the row in `slot`, outside its ranges -> -inf
+__device__ __forceinline__ void lm_mask4(const Ctl* ctl, int slot, int n, float4& s) {
+  const AllowRec* a = &ctl->allow[slot];
+  if (!allow_has(a, n + 0)) s.x = -INFINITY;
+  if (!allow_has(a, n + 1)) s.y = -INFINITY;
+  if (!allow_has(a, n + 2)) s.z = -INFINITY;
+  if (!allow_has(a, n + 3)) s.w = -INFINITY;
+}
+template <int HV, int RT = 0>
+__global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups_arg, int m0_launch) {
   constexpr int NTB = 2, NW = 4, U = 8, MT = 1;
   constexpr size_t kHalfBytes = (size_t)NW * NTB * MT * 1024 + 32 * 4 + NTB * 32 * 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
@@ -1732,6 +1770,8 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups, int m0_la
   const int KT = p.KT, NT = p.NT;
   const int m0 = m0_launch + 16 * half;
   const int M = p.M - m0 < 16 ? (p.M - m0 > 0 ? p.M - m0 : 0) : 16;   // this wave group: rows m0 .. m0 + M - 1 (none: it only keeps the barriers)
+  const int ntl = RT ? p.tlist[0] : 0;                                // RT: vocabulary tiles in the list
+  const int ngroups = RT ? (ntl + NTB - 1) / NTB : ngroups_arg;
   float4* red = (float4*)smem;                                   // [NW][NTB][64]
   float* rarr = (float*)(smem + (size_t)NW * NTB * MT * 1024);
   float* bestv = rarr + 32;                                      // [NTB][32] running best of this block
@@ -1756,7 +1796,7 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups, int m0_la
 #pragma unroll
       for (int nb = 0; nb < NTB; ++nb) {
         int nt = g * NTB + nb;
-        nt = nt < NT ? nt : NT - 1;
+        nt = RT ? lm_tile(p.tlist, nt) : (nt < NT ? nt : NT - 1);
         w[u][nb] = smi_ldw(&p.W[((size_t)nt * KT + j) * 64 + lane]);
       }
     }
@@ -1798,7 +1838,7 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups, int m0_la
     }
     __syncthreads();
     if (wave < NTB) {
-      const int nb = wave, nt = g * NTB + nb;
+      const int nb = wave, nt = RT ? (g * NTB + nb < ntl ? p.tlist[1 + g * NTB + nb] : NT) : g * NTB + nb;
       if (nt < NT) {
         float4 s = red[(0 * NTB + nb) * 64 + lane];
 #pragma unroll
@@ -1809,6 +1849,7 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups, int m0_la
         s.x *= rn; s.y *= rn; s.z *= rn; s.w *= rn;
         const int n = nt * 16 + 4 * (lane >> 4);
         const bool valid = em < M;
+        if (RT && valid) lm_mask4(p.ctl, p.rows[m0 + em].slot, n, s);
         if (valid && p.Y) {
           float* y = p.Y + (size_t)(m0 + em) * p.V + n;
           if (n + 0 < p.V) y[0] = s.x;
@@ -1862,12 +1903,15 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups, int m0_la
 // MFMAs, the reduction and the epilogue (3.2 us per group against 2.3 us for the 56 KB at the CU's share of the HBM rate); now
 // the tiles of group g + 2 are requested as soon as group g's MFMAs are issued and the tiles of g + 1 are already in flight.
 // UW = k tiles per wave (ceil(KT / 4)): no clamped duplicate loads (U = 8 at KT = 28 re-requested tile 27 once per wave and n tile).
-template <int UW>
-__global__ __launch_bounds__(256) void k_lm32(GemmP p, int ngroups, int m0) {
+// RT = 1: the restricted form, as k_lm's (groups through the tile list, the rows' own ranges masked in the epilogue).
+template <int UW, int RT = 0>
+__global__ __launch_bounds__(256) void k_lm32(GemmP p, int ngroups_arg, int m0) {
   constexpr int NTB = 2, NW = 4, U = UW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int KT = p.KT, NT = p.NT;
+  const int ntl = RT ? p.tlist[0] : 0;
+  const int ngroups = RT ? (ntl + NTB - 1) / NTB : ngroups_arg;
   const int M = p.M - m0 < 32 ? p.M - m0 : 32;                    // rows of this pass (>= 1)
   float4* red = (float4*)smem;                                     // [NW][NTB][2][64]
   float* rarr = (float*)(smem + (size_t)NW * NTB * 2 * 1024);      // [32]
@@ -1931,7 +1975,7 @@ __global__ __launch_bounds__(256) void k_lm32(GemmP p, int ngroups, int m0) {
 #pragma unroll
       for (int nb = 0; nb < NTB; ++nb) {
         int nt = g * NTB + nb;
-        nt = nt < NT ? nt : NT - 1;
+        nt = RT ? lm_tile(p.tlist, nt) : (nt < NT ? nt : NT - 1);
         w[u][nb] = smi_ldw(&p.W[((size_t)nt * KT + j) * 64 + lane]);
       }
     }
@@ -2015,7 +2059,7 @@ __global__ __launch_bounds__(256) void k_lm32(GemmP p, int ngroups, int m0) {
     __syncthreads();
     SMI_LMSTAMP(2);
     {
-      const int nt = gcur * NTB + nb_e;
+      const int nt = RT ? (gcur * NTB + nb_e < ntl ? p.tlist[1 + gcur * NTB + nb_e] : NT) : gcur * NTB + nb_e;
       if (nt < NT) {
         float4 s = red[((0 * NTB + nb_e) * 2 + mt_e) * 64 + lane];
 #pragma unroll
@@ -2026,6 +2070,7 @@ __global__ __launch_bounds__(256) void k_lm32(GemmP p, int ngroups, int m0) {
         s.x *= rn; s.y *= rn; s.z *= rn; s.w *= rn;
         const int n = nt * 16 + 4 * (lane >> 4);
         const bool valid = ml < M;
+        if (RT && valid) lm_mask4(p.ctl, p.rows[m0 + ml].slot, n, s);
         if (valid && p.Y) {
           float* y = p.Y + (size_t)(m0 + ml) * p.V + n;
           if (n + 0 < p.V) y[0] = s.x;
@@ -3016,8 +3061,10 @@ __global__ __launch_bounds__(256) void k_sample_scan(SampleP p) {
   __syncthreads();
   const float thr = s_thr;
   const float* lg = p.logits + (size_t)m * p.V;
+  // (a -inf logit has probability 0 and is never a candidate: a row with fewer than top_k finite logits -- a constrained row,
+  // smi_llm_admit_constrained -- has the bound -inf, and its -inf ids would otherwise crowd the finite ones out of the list)
   auto take = [&](float v, int idx) {
-    if (v >= thr) {
+    if (v >= thr && v != -INFINITY) {
       const unsigned pos = atomicAdd(&p.cand_n[m], 1u);
       if (pos < (unsigned)kCandCap) { p.cand_v[(size_t)m * kCandCap + pos] = v; p.cand_i[(size_t)m * kCandCap + pos] = idx; }
     }
@@ -3083,7 +3130,7 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
     __syncthreads();
     for (int i = tid; i < p.V; i += 1024) {
       const float v = lg[i];
-      if (sortable(v) >= thr) {
+      if (sortable(v) >= thr && v != -INFINITY) {   // (-inf: probability 0, as in k_sample_scan)
         const unsigned pos = atomicAdd(&s_cnt, 1u);
         if (pos < kCandCap) { cv[pos] = v; ci[pos] = i; }
       }
@@ -3221,11 +3268,17 @@ __device__ __forceinline__ void pen_best(float v, int i, float& bv, int& bi) {
 // grid (ceil(nblk / kPenWaves), M) x 256: wave w of block x owns set x * kPenWaves + w of row blockIdx.y.  No barrier: a wave
 // reads its set's logits and history entries once (float4 + 4 x uint16 when V % 4 == 0: sets start at multiples of 4), writes
 // them back processed if the row samples, and leaves one (maximum, lowest id) pair.
+// Stage 0 (smi_llm_admit_constrained) runs here too, first: a constrained row's ids outside its ranges become -inf (what the
+// restricted lm_head leaves unwritten outside the union of the rows' tiles included), and the row's maxima are rebuilt over
+// this kernel's partition -- so the sampler, k_logprob and k_finalize see the same dense row and the same maxima whichever
+// lm_head form ran.  A constrained, unpenalised row takes stage 0 alone.
 __global__ __launch_bounds__(256) void k_penalize(PenP p) {
   const int m = blockIdx.y;
   const RowDesc rd = p.rows[m];
   const PenRec r = p.ctl->pen[rd.slot];
-  if (!r.on) return;   // not penalised: the lm_head's maxima stand
+  const AllowRec* al = &p.ctl->allow[rd.slot];
+  const bool con = al->n > 0;
+  if (!r.on && !con) return;   // neither penalised nor constrained: the lm_head's maxima stand
   const int lane = threadIdx.x & 63, set = blockIdx.x * kPenWaves + (threadIdx.x >> 6);
   if (set >= p.nblk) return;
   // the sampler and k_logprob read the logits; k_finalize of a row that does neither only the maxima
@@ -3242,17 +3295,27 @@ __global__ __launch_bounds__(256) void k_penalize(PenP p) {
   if ((p.V & 3) == 0) {   // i1 - i0 is a multiple of 4: every float4 / uint2 lies inside the set and is aligned
     for (int i = i0 + 4 * lane; i < i1; i += 256) {
       float4 x = *(const float4*)(lg + i);
-      const uint2 hh = *(const uint2*)(hs + i);
-      x.x = pen_logit(x.x, hh.x & 0xffffu, r, mask, i, eos);
-      x.y = pen_logit(x.y, hh.x >> 16, r, mask, i + 1, eos);
-      x.z = pen_logit(x.z, hh.y & 0xffffu, r, mask, i + 2, eos);
-      x.w = pen_logit(x.w, hh.y >> 16, r, mask, i + 3, eos);
+      if (con) {
+        if (!allow_has(al, i)) x.x = -INFINITY;
+        if (!allow_has(al, i + 1)) x.y = -INFINITY;
+        if (!allow_has(al, i + 2)) x.z = -INFINITY;
+        if (!allow_has(al, i + 3)) x.w = -INFINITY;
+      }
+      if (r.on) {
+        const uint2 hh = *(const uint2*)(hs + i);
+        x.x = pen_logit(x.x, hh.x & 0xffffu, r, mask, i, eos);
+        x.y = pen_logit(x.y, hh.x >> 16, r, mask, i + 1, eos);
+        x.z = pen_logit(x.z, hh.y & 0xffffu, r, mask, i + 2, eos);
+        x.w = pen_logit(x.w, hh.y >> 16, r, mask, i + 3, eos);
+      }
       if (wb) *(float4*)(lg + i) = x;
       pen_best(x.x, i, bv, bi); pen_best(x.y, i + 1, bv, bi); pen_best(x.z, i + 2, bv, bi); pen_best(x.w, i + 3, bv, bi);
     }
   } else {
     for (int i = i0 + lane; i < i1; i += 64) {
-      const float x = pen_logit(lg[i], hs[i], r, mask, i, eos);
+      float x = lg[i];
+      if (con && !allow_has(al, i)) x = -INFINITY;
+      if (r.on) x = pen_logit(x, hs[i], r, mask, i, eos);
       if (wb) lg[i] = x;
       pen_best(x, i, bv, bi);
     }
@@ -3572,6 +3635,10 @@ struct smi_llm {
   int slot_samp[kMaxRows];      // host: the record of the sequence in this slot (live or being admitted) is SMI_SAMPLING_SAMPLE
   int slot_pen[kMaxRows];       // host: the sequence in this slot (live or being admitted) has a penalty record (PenRec::on)
   int slot_lp[kMaxRows];        // host: the sequence in this slot (live or being admitted) returns log-probabilities (Ctl::lp)
+  int slot_allow[kMaxRows];     // host: the sequence in this slot (live or being admitted) is constrained (Ctl::allow, n > 0)
+  int lm_restrict;              // host: every row of the steps being issued is constrained (the restricted lm_head may run)
+  int* tlist;                   // device: {count, vocabulary tiles ascending} -- the union of the constrained slots' tiles
+  std::vector<int32_t> host_tlist;
   float* lp;                    // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
   float* lp_part; float2* lp_rowc;   // k_logprob -> k_finalize: [kMaxRows][kLpBlocks] partial sums, [kMaxRows] (max, 1/T)
   uint16_t* phist;              // penalty histories [max_slots][vocab] (k_penalize, k_finalize)
@@ -3593,7 +3660,7 @@ struct smi_llm {
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
   int gu1_lo;           // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (SPARKMI_GU1_LO; default 4)
   int gu1_rows;         // rows up to which gate_up runs its one-batch, three-tile shape (SPARKMI_GU1_ROWS; default 32)
-  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen, graph_lp;   // the step graph in use (owned by graph_cache)
+  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen, graph_lp, graph_allow;   // the step graph in use (owned by graph_cache)
   // every exec remembers the stream it last ran on: a caller may alternate streams, and an exec is destroyed only after THAT
   // stream has drained (graphs_flush)
   std::map<hipGraphExec_t, hipStream_t> graph_last;
@@ -3605,7 +3672,8 @@ struct smi_llm {
   // the cache (graphs_flush).  The sample bit decides only whether lm_head writes the logits rows and the sampler kernels run:
   // a step in which no row samples is the greedy step exactly.  Likewise the penalty bit only adds the logits rows and
   // k_penalize: a step in which no row is penalised is the step without penalties exactly; and the log-probability bit only
-  // adds the logits rows and k_logprob.
+  // adds the logits rows and k_logprob.  The constraint bits: some row constrained (the full lm_head writes the logits rows and
+  // k_penalize applies stage 0), and every row constrained (the restricted lm_head, whose tile list is device data).
   std::map<uint64_t, hipGraphExec_t> graph_cache;
   hipEvent_t ev0, ev1;
   // host staging
@@ -3704,11 +3772,30 @@ bool lp_any(const smi_llm* L) {
     if (L->slot_lp[sl]) return true;
   return false;
 }
+// Some live / just-admitted row is constrained (smi_llm_admit_constrained).
+bool allow_any(const smi_llm* L) {
+  for (int sl = 0; sl < kMaxRows; ++sl)
+    if (L->slot_allow[sl]) return true;
+  return false;
+}
+// The step's lm_head reads only the tiles of the union (k_lm / k_lm32 with RT = 1): every row of the step is constrained, and the
+// persistent kernels run (K <= 32 tiles, bf16 weights; the generic EPI_LM GEMM and the exact-weights mode take the full path).
+bool lm_restricted(const smi_llm* L) {
+  return L->lm_restrict && L->KTh <= 32 && !L->exact && allow_any(L);
+}
+// Some row of the step reads the logits rows: a sampling, penalised or log-probability row, or a constrained row whose stage 0
+// runs in k_penalize (every constrained row of a full-lm_head step; on the restricted path k_penalize then also runs, so the
+// rows it hands on are dense).
+bool logits_needed(const smi_llm* L) {
+  return samp_any(L) || pen_any(L) || lp_any(L) || (allow_any(L) && !lm_restricted(L));
+}
+// the constraint bits of a step: 1 = some row constrained, 2 = every row (restricted lm_head)
+int allow_bits(const smi_llm* L) { return allow_any(L) ? (lm_restricted(L) ? 3 : 1) : 0; }
 // the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | sample << 25 | penalty << 26 | log-probs << 27 |
-// steps per replay << 32
+// constraints << 28 (2 bits) | steps per replay << 32
 uint64_t graph_key(const smi_llm* L, int samp, int pen, int lp, int K) {
   return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)samp << 25) |
-         ((uint64_t)pen << 26) | ((uint64_t)lp << 27) | ((uint64_t)K << 32);
+         ((uint64_t)pen << 26) | ((uint64_t)lp << 27) | ((uint64_t)allow_bits(L) << 28) | ((uint64_t)K << 32);
 }
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
@@ -4163,7 +4250,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
       case KLM:
         p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh; p.XS = L->xs_h;
-        p.Y = logits ? logits : (samp_any(L) || pen_any(L) || lp_any(L) ? L->logits : nullptr);
+        p.Y = logits ? logits : (logits_needed(L) ? L->logits : nullptr);
         p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
         SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
         return launch_gemm_x<PRO_NORM, EPI_LM>(L, p, st);
@@ -4266,9 +4353,28 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KLM:
       p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh;
       p.XS = L->xs_h;
-      p.Y = logits ? logits : (samp_any(L) || pen_any(L) || lp_any(L) ? L->logits : nullptr);
+      p.Y = logits ? logits : (logits_needed(L) ? L->logits : nullptr);
       p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
       p.stamps = L->stamps_on ? L->stamps : nullptr;
+      if (L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L)) {   // every row constrained: only the union's tiles
+        p.tlist = L->tlist; p.ctl = L->ctl;
+        const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
+        const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
+        if (M <= 16) {
+          hipLaunchKernelGGL((k_lm<1, 1>), dim3(L->lm_blocks), dim3(256), lds, st, p, 0, 0);
+          SMI_LAUNCH_CHECK();
+          return SMI_OK;
+        }
+        for (int m0 = 0; m0 < M; m0 += 32) {   // the kernel the full path picks for this row count, in its restricted form
+          if (!(L->tune2 & 8192) && lds32 <= 150 * 1024) {
+            if (L->KTh <= 28) hipLaunchKernelGGL((k_lm32<7, 1>), dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, 0, m0);
+            else hipLaunchKernelGGL((k_lm32<8, 1>), dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, 0, m0);
+          } else
+            hipLaunchKernelGGL((k_lm<2, 1>), dim3(lm_blocks_for(L, M)), dim3(512), 2 * lds, st, p, 0, m0);
+          SMI_LAUNCH_CHECK();
+        }
+        return SMI_OK;
+      }
       if (L->KTh <= 32) {   // persistent path: 16 rows' operand resident in the registers of a 4-wave group
         const int ngroups = (L->NTlm + 1) / 2;
         const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
@@ -4296,7 +4402,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       f.tok = nullptr;
       f.hs = L->do_sample;
       f.phist = nullptr;
-      if (pen_any(L)) {   // unpenalised rows leave k_penalize at once
+      if (pen_any(L) || (allow_any(L) && logits_needed(L))) {   // rows neither penalised nor constrained leave k_penalize at once
         PenP pp;
         pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
         pp.V = c.vocab_size; pp.nblk = lm_blocks_for(L, M); pp.per = pen_set_ids(pp.V, pp.nblk); pp.hs = L->do_sample;
@@ -4636,8 +4742,9 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
-  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; L->graph_lp = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
+  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; L->graph_lp = 0; L->graph_allow = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
   memset(L->slot_lp, 0, sizeof(L->slot_lp)); L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
+  memset(L->slot_allow, 0, sizeof(L->slot_allow)); L->lm_restrict = 0; L->tlist = nullptr;
   L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
   const size_t esz = cfg->kv_dtype ? 4 : 2;
@@ -4697,6 +4804,9 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   SMI_ALLOC(L->lp, (size_t)L->max_steps * kMaxRows * 4);
   SMI_ALLOC(L->lp_part, (size_t)kMaxRows * kLpBlocks * 4);
   SMI_ALLOC(L->lp_rowc, (size_t)kMaxRows * sizeof(float2));
+  // the restricted lm_head's tile list (smi_llm_admit_constrained): {count, tiles}; zeros = no tile, entry 0 a valid tile index
+  SMI_ALLOC(L->tlist, ((size_t)L->NTlm + 1) * 4);
+  SMI_HIP(hipMemset(L->tlist, 0, ((size_t)L->NTlm + 1) * 4));
 #undef SMI_ALLOC
   if (hipMemset(L->kcache, 0, kvbytes) != hipSuccess || hipMemset(L->vcache, 0, kvbytes) != hipSuccess ||
       hipMemset(L->h, 0, (size_t)kMaxRows * L->H * 4) != hipSuccess ||
@@ -4716,6 +4826,8 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   // handle (= per device), outside any stream capture
   if (hipFuncSetAttribute((const void*)k_lm32<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
   if (hipFuncSetAttribute((const void*)k_lm32<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+  if (hipFuncSetAttribute((const void*)k_lm32<7, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
+  if (hipFuncSetAttribute((const void*)k_lm32<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
   {   // and so do the k_gemm / k_pgemm / k_downC instantiations whose launches may pass 64 KiB (LdsBig), once per device
     static std::mutex mu;
     static bool done[64] = {};
@@ -4764,7 +4876,7 @@ int smi_llm_destroy(smi_llm* L) {
   eng_destroy(L);
   void* ptrs[] = {L->h, L->qbuf, L->xs_h, L->xs_attn, L->xs_act, L->sspart, L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
                   L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab, L->apart,
-                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc};
+                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (L->ev0) (void)hipEventDestroy(L->ev0);
@@ -4951,6 +5063,9 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   memset(L->slot_pen, 0, sizeof(L->slot_pen));
   memset(L->hctl.lp, 0, sizeof(L->hctl.lp));       // and keeps no log-probabilities
   memset(L->slot_lp, 0, sizeof(L->slot_lp));
+  memset(L->hctl.allow, 0, sizeof(L->hctl.allow)); // and is not constrained
+  memset(L->slot_allow, 0, sizeof(L->slot_allow));
+  L->lm_restrict = 0;
   L->admit_seq = B;
   { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
   SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
@@ -4985,6 +5100,9 @@ int smi_llm_session_begin(smi_llm* L, const int64_t* eos_ids, int n_eos, void* s
   memset(L->slot_pen, 0, sizeof(L->slot_pen));
   memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
   memset(L->slot_lp, 0, sizeof(L->slot_lp));
+  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
+  memset(L->slot_allow, 0, sizeof(L->slot_allow));
+  L->lm_restrict = 0;
   L->admit_seq = 0;
   if (L->paged)
     for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
@@ -5006,6 +5124,8 @@ static int session_set_rows(smi_llm* L, const std::vector<RowDesc>& live, hipStr
   L->B = (int)live.size();
   L->identity_slots = 1;
   for (int b = 0; b < L->B; ++b) L->identity_slots &= live[b].slot == b;
+  L->lm_restrict = L->B > 0;
+  for (int b = 0; b < L->B; ++b) L->lm_restrict &= L->slot_allow[live[b].slot];
   L->live_order.clear();
   for (int b = 0; b < L->B; ++b) L->live_order.push_back(live[b].slot);
   L->graph = nullptr;   // (the next decode picks the cached step of the new row count)
@@ -5126,10 +5246,79 @@ int smi_llm_admit_logprobs(smi_llm* L, const int64_t* ids, const int32_t* lens, 
   return smi_llm_admit_forked(L, ids, lens, n, P_max, nullptr, params, pens, want_lp, slots_out, stream);
 }
 
+// Checks of one allow record (smi_llm_admit_constrained; before anything of the handle is touched).  pen: the take's penalty
+// record or null.
+static int validate_allow(const smi_llm* L, const smi_allow_params& a, const smi_penalty_params* pen, int j) {
+  const int V = L->cfg.vocab_size;
+  SMI_REQUIRE(a.n_ranges >= 0 && a.n_ranges <= SMI_MAX_ALLOW_RANGES, "smi_llm_admit_constrained: allow[%d].n_ranges=%d outside 0..%d", j,
+              a.n_ranges, SMI_MAX_ALLOW_RANGES);
+  SMI_REQUIRE(a.reserved == 0, "smi_llm_admit_constrained: allow[%d].reserved must be 0", j);
+  long covered = 0;
+  for (int i = 0; i < a.n_ranges; ++i) {
+    SMI_REQUIRE(a.lo[i] >= 0 && a.lo[i] < a.hi[i] && a.hi[i] <= V, "smi_llm_admit_constrained: allow[%d] range %d = [%d, %d) is not inside [0, %d) or empty",
+                j, i, a.lo[i], a.hi[i], V);
+    SMI_REQUIRE(i == 0 || a.hi[i - 1] <= a.lo[i], "smi_llm_admit_constrained: allow[%d] ranges %d and %d are not sorted and disjoint", j, i - 1, i);
+    covered += a.hi[i] - a.lo[i];
+  }
+  if (pen && pen->min_new_tokens > 0 && a.n_ranges > 0) {   // some id of the set must stay selectable while eos is banned
+    long eos_in = 0;
+    for (int e = 0; e < L->hctl.n_eos; ++e) {
+      const long long id = L->hctl.eos[e];
+      bool dup = false;
+      for (int f = 0; f < e; ++f) dup |= L->hctl.eos[f] == id;
+      if (dup) continue;
+      for (int i = 0; i < a.n_ranges; ++i) eos_in += id >= a.lo[i] && id < a.hi[i];
+    }
+    SMI_REQUIRE(covered > eos_in, "smi_llm_admit_constrained: allow[%d] holds only eos ids but min_new_tokens=%d bans them", j, pen->min_new_tokens);
+  }
+  return SMI_OK;
+}
+
+// The device record of an allow record: n = 0 for none and for a neutral one (no ranges, or ranges that cover [0, V)).
+static AllowRec allow_record(const smi_allow_params* a, int V) {
+  AllowRec r;
+  memset(&r, 0, sizeof(r));
+  if (!a || a->n_ranges == 0) return r;
+  long covered = 0;
+  for (int i = 0; i < a->n_ranges; ++i) covered += a->hi[i] - a->lo[i];
+  if (covered == V) return r;
+  r.n = a->n_ranges;
+  for (int i = 0; i < a->n_ranges; ++i) { r.lo[i] = a->lo[i]; r.hi[i] = a->hi[i]; }
+  return r;
+}
+
+// The restricted lm_head's tile list -> device, in stream order: the 16-id vocabulary tiles that hold an id of some constrained
+// slot's set (live or being admitted), ascending.  Nothing to do while no slot is constrained (the list is not read).
+static int allow_tiles_upload(smi_llm* L, hipStream_t st) {
+  if (!allow_any(L)) return SMI_OK;
+  std::vector<char> mark((size_t)L->NTlm, 0);
+  for (int sl = 0; sl < kMaxRows; ++sl) {
+    if (!L->slot_allow[sl]) continue;
+    const AllowRec& a = L->hctl.allow[sl];
+    for (int i = 0; i < a.n; ++i)
+      for (int t = a.lo[i] >> 4; t <= (a.hi[i] - 1) >> 4; ++t) mark[(size_t)t] = 1;
+  }
+  std::vector<int32_t>& T = L->host_tlist;
+  T.assign(1, 0);
+  for (int t = 0; t < L->NTlm; ++t)
+    if (mark[(size_t)t]) T.push_back(t);
+  T[0] = (int32_t)T.size() - 1;
+  // (pageable source: staged before the call returns; host_tlist is rebuilt only by the next admission or retirement)
+  SMI_HIP(hipMemcpyAsync(L->tlist, T.data(), T.size() * 4, hipMemcpyHostToDevice, st));
+  return SMI_OK;
+}
+
 // n_ret[b] takes of prompt b; the records are per take (N = sum of n_ret).  n_ret = null or all ones: the plain admission.
 int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
                          const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out,
                          void* stream) {
+  return smi_llm_admit_constrained(L, ids, lens, n, P_max, n_ret, params, pens, want_lp, nullptr, slots_out, stream);
+}
+
+// smi_llm_admit_forked plus one allow record per take (allow = null: exactly smi_llm_admit_forked).
+int smi_llm_admit_constrained(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
+                              const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
+                              const smi_allow_params* allow, int32_t* slots_out, void* stream) {
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
   const int slot_cap = L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows;
@@ -5150,6 +5339,8 @@ int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, in
   if (want_lp)
     for (int j = 0; j < N; ++j)
       SMI_REQUIRE(want_lp[j] == 0 || want_lp[j] == 1, "smi_llm_admit_logprobs: return_log_probs[%d]=%d must be 0 or 1", j, want_lp[j]);
+  if (allow)
+    for (int j = 0; j < N; ++j) { const int rca = validate_allow(L, allow[j], pens ? &pens[j] : nullptr, j); if (rca) return rca; }
   hipStream_t st = (hipStream_t)stream;
   int rc;
   std::vector<RowDesc> live;
@@ -5199,6 +5390,7 @@ int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, in
   SampRec old_rec[kMaxRows];
   PenRec old_pen[kMaxRows];
   int32_t old_lp[kMaxRows];
+  AllowRec old_allow[kMaxRows];
   for (int j = 0; j < N; ++j) { old_seqid[j] = L->hctl.seqid[slots[j]]; L->hctl.seqid[slots[j]] = L->admit_seq++; }
   // the records go up with the sequence numbers, before the admission's own step: its finalize emits the first token
   for (int j = 0; j < N; ++j) {
@@ -5211,6 +5403,9 @@ int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, in
     old_lp[j] = L->hctl.lp[slots[j]];
     L->hctl.lp[slots[j]] = want_lp ? want_lp[j] : 0;
     L->slot_lp[slots[j]] = L->hctl.lp[slots[j]];
+    old_allow[j] = L->hctl.allow[slots[j]];
+    L->hctl.allow[slots[j]] = allow_record(allow ? &allow[j] : nullptr, L->cfg.vocab_size);
+    L->slot_allow[slots[j]] = L->hctl.allow[slots[j]].n > 0;
   }
   // undo: nothing was admitted -- sequence numbers, records and pages (and page references) as before (the device copy is
   // rewritten by the next admission)
@@ -5219,6 +5414,7 @@ int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, in
       L->hctl.seqid[slots[j]] = old_seqid[j]; L->hctl.samp[slots[j]] = old_rec[j]; L->slot_samp[slots[j]] = 0;
       L->hctl.pen[slots[j]] = old_pen[j]; L->slot_pen[slots[j]] = 0;
       L->hctl.lp[slots[j]] = old_lp[j]; L->slot_lp[slots[j]] = 0;
+      L->hctl.allow[slots[j]] = old_allow[j]; L->slot_allow[slots[j]] = 0;
     }
     L->admit_seq = seq0;
     if (L->paged)
@@ -5229,6 +5425,7 @@ int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, in
     smi_set_error("smi_llm_admit: uploading the generation controls failed");
     return SMI_EHIP;
   }
+  if ((rc = allow_tiles_upload(L, st))) { undo(); return rc; }   // the union now holds the new takes' tiles
   // the fork copy's work list: each follower gets the leader's positions it does not share -- 0 .. L-2 (contiguous), S P .. L-2
   // (paged); position L-1 and on are written by the follower's own steps
   std::vector<RowDesc> fork;
@@ -5274,7 +5471,9 @@ int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, in
   L->B = N;
   L->identity_slots = 1;
   for (int j = 0; j < N; ++j) L->identity_slots &= slots[j] == j;
-  if ((rc = launch_embed(L, L->rows, N, st)) || (rc = launch_step(L, N, st))) { L->B = oldB; return rc; }
+  L->lm_restrict = 1;   // the admission's step runs over the new rows alone
+  for (int j = 0; j < N; ++j) L->lm_restrict &= L->slot_allow[slots[j]];
+  if ((rc = launch_embed(L, L->rows, N, st)) || (rc = launch_step(L, N, st))) { L->B = oldB; L->lm_restrict = 0; return rc; }
   std::vector<RowDesc> fresh;
   if ((rc = session_live_rows(L, fresh, st))) return rc;
   for (int j = 0; j < N; ++j) {
@@ -5301,7 +5500,9 @@ int smi_llm_retire(smi_llm* L, int slot, void* stream) {
   L->slot_samp[slot] = 0;
   L->slot_pen[slot] = 0;
   L->slot_lp[slot] = 0;   // (Ctl::lp stays: the slot's log-probabilities stay readable until it is reused)
+  L->slot_allow[slot] = 0;
   if (L->paged) pages_release(L, slot);   // its pages go back to the pool (stale table entries are never read: no live row names the slot)
+  if ((rc = allow_tiles_upload(L, st))) return rc;
   return session_set_rows(L, live, st);
 }
 
@@ -5328,12 +5529,16 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
     L->slot_samp[slots[i]] = 0;
     L->slot_pen[slots[i]] = 0;
     L->slot_lp[slots[i]] = 0;
+    L->slot_allow[slots[i]] = 0;
     if (L->paged) pages_release(L, slots[i]);
   }
   L->live_order = keep;
   L->B = (int)keep.size();
   L->identity_slots = 1;
   for (int b = 0; b < L->B; ++b) L->identity_slots &= keep[b] == b;
+  L->lm_restrict = L->B > 0;
+  for (int b = 0; b < L->B; ++b) L->lm_restrict &= L->slot_allow[keep[b]];
+  { const int rct = allow_tiles_upload(L, st); if (rct) return rct; }
   L->graph = nullptr;
   if (L->B == 0) return SMI_OK;
   return launch_embed(L, L->rows, L->B, st);
@@ -5438,13 +5643,13 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     L->attn_seg = segs_for(bound);
     if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
   }
-  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0, lpb = lp_any(L) ? 1 : 0;
+  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0, lpb = lp_any(L) ? 1 : 0, alw = allow_bits(L);
   if (L->cfg.use_graph && n_steps > 0 && (!L->graph || L->graph_B != L->B || L->graph_seg != L->attn_seg || L->graph_ident != L->identity_slots ||
-                                          L->graph_samp != samp || L->graph_pen != pen || L->graph_lp != lpb)) {
+                                          L->graph_samp != samp || L->graph_pen != pen || L->graph_lp != lpb || L->graph_allow != alw)) {
     const uint64_t key = graph_key(L, samp, pen, lpb, 0);
     auto hit = L->graph_cache.find(key);
     L->graph = hit != L->graph_cache.end() ? hit->second : nullptr;
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw;
   }
   if (L->cfg.use_graph && n_steps > 0 && !L->graph) {
     const uint64_t key = graph_key(L, samp, pen, lpb, 0);
@@ -5463,7 +5668,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     }
     (void)hipStreamDestroy(cs);
     (void)hipGetLastError();
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw;
     if (!L->graph) { smi_set_error("hipGraph capture of the decode step failed"); return SMI_EHIP; }
     L->graph_cache[key] = L->graph;
   }
@@ -6001,6 +6206,7 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
   std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
   memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
   for (int m = 0; m < n_rows; ++m) {
     rows[m] = RowDesc{m, 0, 0, emitted_host[m]};
     L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: the kernel writes its processed logits back)
@@ -6033,6 +6239,7 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
   }
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
   memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
   L->started = 0;   // rows, controls and the lm_head partials no longer belong to a generation
   return SMI_OK;
 }
@@ -6066,6 +6273,7 @@ int smi_llm_debug_logprob(smi_llm* L, const float* logits_host, int n_rows, cons
   std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
   memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
   memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
   for (int m = 0; m < n_rows; ++m) {
     rows[m] = RowDesc{m, 0, 0, 0};   // token index 0: k_finalize writes lp[0][m]

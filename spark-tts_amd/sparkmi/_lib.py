@@ -88,6 +88,15 @@ class PenaltyParams(C.Structure):
                 ("min_new_tokens", C.c_int32), ("penalize_prompt", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+SMI_MAX_ALLOW_RANGES = 16
+
+
+class AllowParams(C.Structure):
+    """smi_allow_params: one admitted sequence's allowed-token ranges [lo[i], hi[i]) (smi_llm_admit_constrained)"""
+    _fields_ = [("n_ranges", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_int32 * SMI_MAX_ALLOW_RANGES),
+                ("hi", C.c_int32 * SMI_MAX_ALLOW_RANGES)]
+
+
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
 _P = C.POINTER
 SYMBOLS = {
@@ -117,6 +126,8 @@ SYMBOLS = {
     "smi_llm_slots_logprobs": (_I, [_VP, _P(C.c_int32), _I, _P(C.c_float), _I, _P(C.c_int32), _VP]),
     "smi_llm_admit_forked": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams), _P(PenaltyParams),
                                   _P(C.c_int32), _P(C.c_int32), _VP]),
+    "smi_llm_admit_constrained": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams),
+                                       _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(C.c_int32), _VP]),
     "smi_llm_status": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_forward_logits": (_I, [_VP, _P(C.c_int64), _I, _VP, _VP]),
     "smi_llm_steps": (_I, [_VP]),

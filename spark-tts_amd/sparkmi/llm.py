@@ -33,6 +33,57 @@ PENALTY_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "
 PENALTY_NEUTRAL = dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_new_tokens=0)
 # key of the per-token log-probabilities, in the same dicts (smi_llm_admit_logprobs; include/sparkmi.h states the semantics)
 LOGPROB_KEYS = ("return_log_probs",)
+# key of the allowed-token set, in the same dicts (smi_llm_admit_constrained; include/sparkmi.h states the semantics): an
+# iterable of token ids, merged into sorted runs of consecutive ids (at most SMI_MAX_ALLOW_RANGES of them)
+ALLOW_KEY = "allowed_token_ids"
+
+
+def allow_ranges(ids, vocab_size: int, what: str = ALLOW_KEY) -> List[tuple]:
+    """The sorted, disjoint half-open runs [lo, hi) of consecutive ids that make up the set ``ids``.  ValueError, before any
+    device call, when the set is empty, holds a non-integer or an id outside [0, vocab_size), or needs more than
+    ``SMI_MAX_ALLOW_RANGES`` runs."""
+    if isinstance(ids, (str, bytes)) or not isinstance(ids, Iterable):
+        raise ValueError(f"{what} must be an iterable of token ids, not {ids!r}")
+    vals = []
+    for v in ids:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: {v!r} is not an integer token id")
+        if not 0 <= int(v) < vocab_size:
+            raise ValueError(f"{what}: id {int(v)} outside [0, {vocab_size})")
+        vals.append(int(v))
+    if not vals:
+        raise ValueError(f"{what} is empty: nothing could be generated")
+    runs: List[list] = []
+    for v in sorted(set(vals)):
+        if runs and runs[-1][1] == v:
+            runs[-1][1] = v + 1
+        else:
+            runs.append([v, v + 1])
+    if len(runs) > _lib.SMI_MAX_ALLOW_RANGES:
+        raise ValueError(f"{what}: {len(runs)} runs of consecutive ids, at most {_lib.SMI_MAX_ALLOW_RANGES} are supported")
+    return [tuple(r) for r in runs]
+
+
+def allow_records(requests: Optional[Sequence[Optional[Mapping]]], n: int, vocab_size: int):
+    """One ``smi_allow_params`` per prompt from the ``allowed_token_ids`` keys of the request dicts, or None when no request
+    carries the key (the admission then keeps the route and bits it has without it).  A request without the key gets a record
+    with no ranges (not constrained)."""
+    if requests is None:
+        return None
+    requests = list(requests)
+    if len(requests) != n:
+        raise ValueError(f"sampling: {len(requests)} entries for {n} prompts")
+    if not any(d is not None and d.get(ALLOW_KEY) is not None for d in requests):
+        return None
+    recs = (_lib.AllowParams * n)()
+    for i, d in enumerate(requests):
+        if d is None or d.get(ALLOW_KEY) is None:
+            continue
+        runs = allow_ranges(d[ALLOW_KEY], vocab_size, f"sampling[{i}].{ALLOW_KEY}")
+        recs[i].n_ranges = len(runs)
+        for r, (lo, hi) in enumerate(runs):
+            recs[i].lo[r], recs[i].hi[r] = lo, hi
+    return recs
 
 
 # key of a request's number of takes (TensorRT-LLM's num_return_sequences; smi_llm_admit_forked): SparkLLM.serve and SparkTTS
@@ -58,6 +109,8 @@ def expand_takes(sampling: Optional[Sequence[Optional[Mapping]]], n_return: Sequ
         raise ValueError(f"sampling: {len(sampling)} entries for {len(n_return)} prompts")
     out: List[Optional[dict]] = []
     for d, k in zip(sampling, n_return):
+        if d is not None and d.get(ALLOW_KEY) is not None and not isinstance(d[ALLOW_KEY], (list, tuple)):
+            d = dict(d, **{ALLOW_KEY: tuple(d[ALLOW_KEY])})   # a one-shot iterable serves every take
         for j in range(k):
             if d is None:
                 out.append(None)
@@ -136,7 +189,7 @@ def sampling_records(sampling: Optional[Sequence[Optional[Mapping]]], n: int, de
         raise ValueError(f"sampling: {len(sampling)} entries for {n} prompts")
     if all(d is None for d in sampling):
         return None
-    known = SAMPLING_KEYS + PENALTY_KEYS + LOGPROB_KEYS
+    known = SAMPLING_KEYS + PENALTY_KEYS + LOGPROB_KEYS + (ALLOW_KEY,)
     for i, d in enumerate(sampling):
         bad = set(d or ()) - set(known)
         if bad:
@@ -372,7 +425,9 @@ class SparkLLM:
         and logits penalties (``penalty_records``); None everywhere (the default): every sequence follows ``set_sampling``,
         unpenalised.  A request with any non-neutral penalty goes through ``smi_llm_admit_penalized``; an admission in which
         some request carries ``return_log_probs`` (``LOGPROB_KEYS``, a bool) through ``smi_llm_admit_logprobs``, and the
-        flagged sequences' log-probabilities are read with ``slots_logprobs``.
+        flagged sequences' log-probabilities are read with ``slots_logprobs``.  An admission in which some request carries
+        ``allowed_token_ids`` (``ALLOW_KEY``: an iterable of ids; ``allow_records``) goes through ``smi_llm_admit_constrained``:
+        that sequence emits only ids of its set (eos ids are not added to it).
         ``n_return``: one int >= 1 per prompt -- that many takes of the prompt, its prompt prefilled once
         (``smi_llm_admit_forked``); ``sampling`` stays one dict per prompt and is expanded per take (``expand_takes``).  The
         result is then the flat, prompt-major slot list; None (the default) keeps today's route and bits."""
@@ -388,7 +443,14 @@ class SparkLLM:
         recs = sampling_records(sampling, n, self._sampling)
         pens = penalty_records(sampling, n)
         flags = logprob_flags(sampling, n)
-        if flags is not None:
+        allow = allow_records(sampling, n, self.cfg.vocab_size)
+        if allow is not None:
+            self._lib.check(self._lib.smi_llm_admit_constrained(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, None, recs, pens,
+                                                           None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           allow, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                            "smi_llm_admit_constrained")
+        elif flags is not None:
             self._lib.check(self._lib.smi_llm_admit_logprobs(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
                                                         lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs, pens,
                                                         flags.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -420,6 +482,7 @@ class SparkLLM:
         recs = sampling_records(takes, N, self._sampling)
         pens = penalty_records(takes, N)
         flags = logprob_flags(takes, N)
+        allow = allow_records(takes, N, self.cfg.vocab_size)
         lens = np.array([len(p) for p in prompts], dtype=np.int32)
         pmax = int(lens.max())
         ids = np.zeros((n, pmax), dtype=np.int64)
@@ -427,6 +490,14 @@ class SparkLLM:
             ids[b, : len(p)] = np.asarray(p, dtype=np.int64)
         nret = np.asarray(n_return, dtype=np.int32)
         slots = np.zeros(N, dtype=np.int32)
+        if allow is not None:
+            self._lib.check(self._lib.smi_llm_admit_constrained(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
+                                                           nret.ctypes.data_as(C.POINTER(C.c_int32)), recs, pens,
+                                                           None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           allow, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                            "smi_llm_admit_constrained")
+            return slots.tolist()
         self._lib.check(self._lib.smi_llm_admit_forked(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
                                                       lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
                                                       nret.ctypes.data_as(C.POINTER(C.c_int32)), recs, pens,

@@ -19,19 +19,35 @@ import torch
 from . import _lib
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
-from .llm import (FORK_KEY, LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config, num_returns,
-                  penalty_neutral)
+from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config,
+                  num_returns, penalty_neutral)
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
 from .streaming import ChunkScheduler
 from .weights import load_llm_state
 
 
-def _request_sampling(r: dict) -> Optional[dict]:
+# request key: generate only the ids of the tokenizer's added vocabulary (the <|bicodec_*|> and control tokens) and eos
+SPEECH_ONLY_KEY = "speech_tokens_only"
+
+
+def _request_sampling(r: dict, speech_ids=None) -> Optional[dict]:
     """The sampling keys (``SAMPLING_KEYS``) and penalty keys (``PENALTY_KEYS``) a request dict carries, or None: the
     call-level arguments apply unchanged.  Penalty keys that ask for no penalty are dropped, so such a request keeps the
-    route (and the bits) of the same request without them.  ``return_log_probs`` (``LOGPROB_KEYS``) is kept when True."""
+    route (and the bits) of the same request without them.  ``return_log_probs`` (``LOGPROB_KEYS``) is kept when True.
+    ``allowed_token_ids`` (``ALLOW_KEY``) and ``speech_tokens_only`` (``SPEECH_ONLY_KEY``: True -> ``speech_ids()``) become
+    the request's allowed-token set (both given: their intersection); include/sparkmi.h, smi_llm_admit_constrained."""
     d = {k: r[k] for k in SAMPLING_KEYS if k in r}
+    speech = r.get(SPEECH_ONLY_KEY, False)
+    if not isinstance(speech, (bool, np.bool_)):
+        raise ValueError(f"{SPEECH_ONLY_KEY} must be a bool, not {speech!r}")
+    allowed = r.get(ALLOW_KEY)
+    if allowed is not None or speech:
+        s = None if allowed is None else tuple(allowed)
+        if speech:
+            sp = speech_ids()
+            s = tuple(sp) if s is None else tuple(sorted(set(s) & set(sp)))
+        d[ALLOW_KEY] = s
     pen = {k: r[k] for k in PENALTY_KEYS if k in r}
     if not penalty_neutral(pen):
         d.update(pen)
@@ -157,6 +173,13 @@ class SparkTTS:
         predicts = self.tokenizer.batch_decode([list(new_ids)], skip_special_tokens=True)[0]
         return parse_semantic(predicts), parse_global(predicts)
 
+    def speech_token_ids(self) -> List[int]:
+        """The ids a ``speech_tokens_only`` request may generate: the tokenizer's added vocabulary (the ``<|bicodec_*|>``
+        and control tokens) and every eos id of the session; the ordinary BPE text ids are left out."""
+        if getattr(self, "_speech_ids", None) is None:
+            self._speech_ids = sorted(set(int(i) for i in self.tokenizer.get_added_vocab().values()) | set(self._eos))
+        return self._speech_ids
+
     @torch.no_grad()
     def inference(self, text: str, prompt_speech_path: Path = None, prompt_text: str = None,
                   gender: str = None, pitch: str = None, speed: str = None,
@@ -165,7 +188,8 @@ class SparkTTS:
                   prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                   min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False,
-                  num_return_sequences: int = 1):
+                  num_return_sequences: int = 1, allowed_token_ids: Optional[Sequence[int]] = None,
+                  speech_tokens_only: bool = False):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate``.  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
@@ -174,7 +198,9 @@ class SparkTTS:
         float64 sum}; the waveform is the one the call gives without it.  ``num_return_sequences=n > 1``: a list of n takes
         (waveforms, or (waveform, info) pairs), the prompt prefilled once (include/sparkmi.h, smi_llm_admit_forked) and the
         takes vocoded together -- the same as ``inference_batch`` of the request n times; with its own ``seed``, take j is
-        the call alone with ``seed + j``."""
+        the call alone with ``seed + j``.  ``allowed_token_ids`` (an iterable of ids) / ``speech_tokens_only=True`` (the
+        tokenizer's added vocabulary and the eos ids: every ordinary BPE text id is banned): every generated id lies in that
+        set (include/sparkmi.h, smi_llm_admit_constrained; eos ids are not added to an ``allowed_token_ids`` set)."""
         n_takes = num_returns(num_return_sequences)
         if n_takes > self._max_batch:
             raise ValueError(f"num_return_sequences={n_takes} > max_batch={self._max_batch}")
@@ -182,7 +208,9 @@ class SparkTTS:
                    frequency_penalty=frequency_penalty, min_new_tokens=min_new_tokens, penalize_prompt=penalize_prompt)
         return self.inference_batch([dict(text=text, prompt_speech_path=prompt_speech_path, prompt_text=prompt_text,
                                           gender=gender, pitch=pitch, speed=speed, prompt_tokens=prompt_tokens, **pen,
-                                          **({FORK_KEY: n_takes} if n_takes > 1 else {}))],
+                                          **({FORK_KEY: n_takes} if n_takes > 1 else {}),
+                                          **({ALLOW_KEY: allowed_token_ids} if allowed_token_ids is not None else {}),
+                                          **({SPEECH_ONLY_KEY: speech_tokens_only} if speech_tokens_only else {}))],
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                                     max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs)[0]
 
@@ -201,7 +229,9 @@ class SparkTTS:
         ``return_log_probs=True`` (every request) or a request's ``return_log_probs`` key: that request's waveform comes as
         (waveform, info), info as in ``inference``; such a batch runs through the admission path.
         A request's ``num_return_sequences`` key (an int >= 1): that many takes of it, its prompt prefilled once; its result
-        is a list of one result per take.  All takes together are at most ``max_batch``."""
+        is a list of one result per take.  All takes together are at most ``max_batch``.  A request's ``allowed_token_ids``
+        / ``speech_tokens_only`` keys (as in ``inference``) restrict its generated ids; such a batch runs through the
+        admission path."""
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         n_takes = _take_counts(requests, self._max_batch)
@@ -231,7 +261,7 @@ class SparkTTS:
         if room < 1:
             raise ValueError(f"a prompt of {max(len(i) for i in ids)} tokens does not fit max_positions={self._max_positions}")
         max_new_tokens = min(int(max_new_tokens), room)
-        sampling = [_request_sampling(r) for r in requests]
+        sampling = [_request_sampling(r, self.speech_token_ids) for r in requests]
         if return_log_probs:
             sampling = [dict(d or {}, return_log_probs=True) for d in sampling]
         owner = list(range(len(ids)))   # request of every generated row
@@ -385,7 +415,7 @@ class SparkTTS:
                     prompt, g = self.process_prompt(r["text"], r.get("prompt_speech_path"), r.get("prompt_text"), r.get("prompt_tokens"))
                 globals_[i] = g
                 ids = self.tokenizer([prompt], return_tensors="pt").input_ids[0].tolist()
-                d = _request_sampling(r)
+                d = _request_sampling(r, self.speech_token_ids)
                 if FORK_KEY in r:
                     d = dict(d or {}, **{FORK_KEY: forks[i]})
                 yield i, ids, min(max_new_tokens, self._max_positions - len(ids) - decode_stride), self._eos, d
