@@ -302,6 +302,18 @@ int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_
 int smi_llm_retire_many(smi_llm* h, const int32_t* slots, int n, void* stream);
 int smi_llm_slots_tokens(smi_llm* h, const int32_t* slots, int n, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished,
                          void* stream);
+/* The tokens the listed slots have emitted since their own offsets, in one small round trip -- what a streaming loop needs
+ * every few decode steps.  Per listed slot i: count[i] = tokens emitted so far, finished[i] = its eos flag,
+ * n_out[i] = max(0, min(count[i], from[i] + cap) - from[i]) and out_host[i][0 .. n_out[i]) = its history entries from[i] ..
+ * (out_host is [n][cap]).  By definition this is smi_llm_slots_tokens of the same slots, sliced; like it, it reads live slots
+ * and retired ones until a later admission reuses them, and synchronises the stream.  A gather kernel (one block per listed
+ * slot) packs {count, finished, ids[cap]} per slot into a staging buffer of the handle, and ONE copy of n * (8 + 8 * cap) bytes
+ * brings them to a pinned host buffer of the handle (cap counts up to max_positions, the history's length) -- against the whole
+ * [max_positions][SMI_MAX_ROWS] history that smi_llm_slots_tokens copies.  The kernel runs on the caller's stream between decode
+ * calls, never inside the captured decode step.  n outside 1..SMI_MAX_ROWS, a slot out of range, from[i] < 0 or cap < 1:
+ * SMI_EINVAL, nothing written. */
+int smi_llm_poll(smi_llm* h, const int32_t* slots, const int32_t* from, int n, int64_t* out_host, int cap, int32_t* n_out,
+                 int32_t* count, int32_t* finished, void* stream);
 /* count_host / finished_host [SMI_MAX_ROWS]: tokens emitted and eos flag per KV slot, one round trip. */
 int smi_llm_status(smi_llm* h, int32_t* count_host, int32_t* finished_host, void* stream);
 /* Test/teacher-forcing entry: feeds ids_host[0..S) at positions 0..S-1 of slot 0 (cache reset) and
@@ -353,6 +365,16 @@ int smi_voc_destroy(smi_voc* h);
  * Each row's result equals an un-padded B=1 run of that row. */
 int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host, const int32_t* glob_dev,
                     int B, int T_max, float* wav_dev, void* stream);
+/* smi_voc_forward's arguments; row b of the result equals, bit for bit, smi_voc_forward of that row alone (B = 1,
+ * T_max = lens_host[b]) on a handle of the same config -- whatever else is in the call and wherever the row sits; samples beyond
+ * hop*lens[b] are zero.  (smi_voc_forward chooses each layer's tiling, channel split and kernel form from its call shape
+ * (B, longest row), so one of its rows equals its solo run only up to fp32 re-association.)  Here every such choice is taken as
+ * if the call were the row's own (1, lens[b]); consecutive rows whose choices agree in every layer run as ONE launch sequence
+ * whose grids cover their count and their longest row (a shorter row's spare blocks exit), so the call costs one launch sequence
+ * per run of equal plans: sort the rows by length (BiCodecVocoder.detokenize_rows does) and a scheduler's few chunk lengths give
+ * a handful of runs.  The kernels are smi_voc_forward's. */
+int smi_voc_forward_rows(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host, const int32_t* glob_dev,
+                         int B, int T_max, float* wav_dev, void* stream);
 /* Test entry: copies an internal activation (after `stage`) of the last forward to out_dev. */
 int smi_voc_debug_stage(smi_voc* h, int stage, float* out_dev, size_t max_floats, size_t* n_floats, void* stream);
 /* Per-kernel timing probe (see smi_llm_time_kernel): stage index into the launch list of the last

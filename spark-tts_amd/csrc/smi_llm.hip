@@ -3642,6 +3642,7 @@ struct smi_llm {
   float* lp;                    // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
   float* lp_part; float2* lp_rowc;   // k_logprob -> k_finalize: [kMaxRows][kLpBlocks] partial sums, [kMaxRows] (max, 1/T)
   uint16_t* phist;              // penalty histories [max_slots][vocab] (k_penalize, k_finalize)
+  int64_t* poll_dev; int64_t* poll_host;   // smi_llm_poll: device staging / pinned host copy, [kMaxRows][1 + max_steps] words
   int32_t* pen_idx; size_t pen_idx_cap;   // admission: slot * vocab + id of the prompt tokens whose bit k_pen_prompt sets
   std::vector<int32_t> host_pen_idx;
   float* logits; int* tok;
@@ -4637,6 +4638,27 @@ int ensure_plan(smi_llm* L, size_t rows) {
   return SMI_OK;
 }
 
+// smi_llm_poll's gather: one block per listed slot.  Word 0 of the slot's staging record holds {count, finished}, words 1 .. cap the
+// history entries from[i] .. (the lanes run over t; the history is [t][kMaxRows], so a slot's ids are kMaxRows words apart).
+// Entries past the sequence's count are left as they are: the host reads none of them.
+struct PollArgs {
+  int32_t slot[kMaxRows];
+  int32_t from[kMaxRows];
+};
+__global__ __launch_bounds__(64) void k_poll(const int64_t* hist, const int32_t* count, const int32_t* finished, int max_steps,
+                                             PollArgs a, int cap, int64_t* stage) {
+  const int i = blockIdx.x, sl = a.slot[i], from = a.from[i];
+  int64_t* rec = stage + (size_t)i * (1 + cap);
+  const int cnt = count[sl];
+  if (threadIdx.x == 0) {
+    int2 head; head.x = cnt; head.y = finished[sl];
+    *(int2*)rec = head;
+  }
+  int end = cnt < max_steps ? cnt : max_steps;           // (the history holds max_steps entries per slot)
+  if (end - from > cap) end = from + cap;                 // (from <= max_steps here or the loop is empty: no overflow)
+  for (int t = from + (int)threadIdx.x; t < end; t += 64) rec[1 + (t - from)] = hist[(size_t)t * kMaxRows + sl];
+}
+
 }  // namespace
 
 extern "C" {
@@ -4745,6 +4767,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; L->graph_lp = 0; L->graph_allow = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
   memset(L->slot_lp, 0, sizeof(L->slot_lp)); L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
   memset(L->slot_allow, 0, sizeof(L->slot_allow)); L->lm_restrict = 0; L->tlist = nullptr;
+  L->poll_dev = nullptr; L->poll_host = nullptr;
   L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
   const size_t esz = cfg->kv_dtype ? 4 : 2;
@@ -4807,7 +4830,15 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   // the restricted lm_head's tile list (smi_llm_admit_constrained): {count, tiles}; zeros = no tile, entry 0 a valid tile index
   SMI_ALLOC(L->tlist, ((size_t)L->NTlm + 1) * 4);
   SMI_HIP(hipMemset(L->tlist, 0, ((size_t)L->NTlm + 1) * 4));
+  // smi_llm_poll's staging: {count, finished, ids[cap]} per listed slot, cap <= max_steps, and its pinned host copy
+  SMI_ALLOC(L->poll_dev, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8);
 #undef SMI_ALLOC
+  if (hipHostMalloc((void**)&L->poll_host, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8, hipHostMallocDefault) != hipSuccess) {
+    L->poll_host = nullptr;
+    smi_set_error("hipHostMalloc(poll_host, %zu bytes) failed", (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8);
+    smi_llm_destroy(L);
+    return SMI_ENOMEM;
+  }
   if (hipMemset(L->kcache, 0, kvbytes) != hipSuccess || hipMemset(L->vcache, 0, kvbytes) != hipSuccess ||
       hipMemset(L->h, 0, (size_t)kMaxRows * L->H * 4) != hipSuccess ||
       hipMemset(L->xs_h, 0, (size_t)kMaxRows * L->H * 6) != hipSuccess ||
@@ -4876,9 +4907,10 @@ int smi_llm_destroy(smi_llm* L) {
   eng_destroy(L);
   void* ptrs[] = {L->h, L->qbuf, L->xs_h, L->xs_attn, L->xs_act, L->sspart, L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
                   L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab, L->apart,
-                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist};
+                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist, L->poll_dev};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
+  if (L->poll_host) (void)hipHostFree(L->poll_host);
   if (L->ev0) (void)hipEventDestroy(L->ev0);
   if (L->ev1) (void)hipEventDestroy(L->ev1);
   delete L;
@@ -5561,6 +5593,40 @@ int smi_llm_slots_tokens(smi_llm* L, const int32_t* slots, int n, int64_t* out_h
     for (int t = 0; t < k; ++t) out_host[(size_t)i * cap + t] = hist[(size_t)t * kMaxRows + slots[i]];
     n_out[i] = k;
     finished[i] = fin[slots[i]];
+  }
+  return SMI_OK;
+}
+
+// The tokens the listed slots have emitted since from[i], at most cap each, in one small round trip (include/sparkmi.h): k_poll
+// packs them, one copy of n * (8 + 8 * cap) bytes brings them to the pinned buffer.  Launched on the caller's stream between
+// decode calls -- never inside the captured step.
+int smi_llm_poll(smi_llm* L, const int32_t* slots, const int32_t* from, int n, int64_t* out_host, int cap, int32_t* n_out,
+                 int32_t* count, int32_t* finished, void* stream) {
+  SMI_REQUIRE(L && slots && from && out_host && n_out && count && finished && n >= 1 && n <= kMaxRows && cap >= 1, "smi_llm_poll: bad argument");
+  for (int i = 0; i < n; ++i) {
+    SMI_REQUIRE(slots[i] >= 0 && slots[i] < kMaxRows, "smi_llm_poll: slot %d out of range", slots[i]);
+    SMI_REQUIRE(from[i] >= 0, "smi_llm_poll: from[%d]=%d < 0", i, from[i]);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int capd = cap < L->max_steps ? cap : L->max_steps;   // no sequence has more history than that
+  PollArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n; ++i) { a.slot[i] = slots[i]; a.from[i] = from[i] < L->max_steps ? from[i] : L->max_steps; }
+  hipLaunchKernelGGL(k_poll, dim3(n), dim3(64), 0, st, L->hist, L->count, L->finished, L->max_steps, a, capd, L->poll_dev);
+  SMI_LAUNCH_CHECK();
+  SMI_HIP(hipMemcpyAsync(L->poll_host, L->poll_dev, (size_t)n * (8 + 8 * (size_t)capd), hipMemcpyDeviceToHost, st));
+  SMI_HIP(hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i) {
+    const int64_t* rec = L->poll_host + (size_t)i * (1 + capd);
+    int32_t head[2];
+    memcpy(head, rec, 8);
+    int end = head[0] < L->max_steps ? head[0] : L->max_steps;
+    if (end - a.from[i] > capd) end = a.from[i] + capd;
+    const int k = end > a.from[i] ? end - a.from[i] : 0;
+    if (k) memcpy(out_host + (size_t)i * cap, rec + 1, (size_t)k * 8);
+    n_out[i] = k;
+    count[i] = head[0];
+    finished[i] = head[1];
   }
   return SMI_OK;
 }

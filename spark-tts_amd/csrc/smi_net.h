@@ -1288,6 +1288,7 @@ struct Launch {
   double flops;
   ConvP cp; int qb; bool ks; int chg; int nwv = 4; bool gemv; bool bf = false; bool c1 = false; int c1_len = 0; dim3 grid; size_t lds;
   int tph = 0;       // k_convbT: output phases per block of a transposed conv (0: k_convb, one phase per block)
+  long long plan_blocks = 0;   // blocks of the grid the plan was chosen for, where that is not the launch's own (PlanShape); 0: the launch's
   ResP rp; int res_nwv = 0;   // kind 5: a fused ResidualUnit (k_resunit) with res_nwv waves per block
   LnP lp; int cpt;
   // small kernels keep their args here
@@ -1296,6 +1297,9 @@ struct Launch {
   float* wav; int wstride, hop, tmaxhop;
   const int* lens;
 };
+
+// blocks of the grid a launch's plan was made for: the small-grid kernel forms (WPF, WALL) are part of the plan
+inline long long plan_grid_blocks(const Launch& L) { return L.plan_blocks ? L.plan_blocks : (long long)L.grid.x * L.grid.y * L.grid.z; }
 
 int run_launch(const Launch& L, hipStream_t st) {
   switch (L.kind) {
@@ -1312,7 +1316,7 @@ int run_launch(const Launch& L, hipStream_t st) {
         const bool wide = L.cp.xw > 64;
         if (L.chg == 4) {
           // one tap, channels split over the waves, at most two blocks per CU: the chunk's weights are requested one chunk ahead (WPF)
-          const bool wpf = L.ks && L.cp.S == 1 && L.cp.ntaps[0] == 1 && (long long)L.grid.x * L.grid.y * L.grid.z <= 512 && !smi_env("SPARKMI_CB_NOWPF");
+          const bool wpf = L.ks && L.cp.S == 1 && L.cp.ntaps[0] == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWPF");
           if (wpf) { if (L.qb == 1) hipLaunchKernelGGL((k_convb<1, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp); else hipLaunchKernelGGL((k_convb<2, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp); }
           else if (L.ks) { if (L.qb == 1) SMI_CB(1, true, 4, 1); else SMI_CB(2, true, 4, 1); }
           else { if (L.qb == 1) SMI_CB(1, false, 4, 1); else SMI_CB(2, false, 4, 1); }
@@ -1322,7 +1326,7 @@ int run_launch(const Launch& L, hipStream_t st) {
           for (int r = 0; r < L.cp.S; ++r) mt = L.cp.ntaps[r] > mt ? L.cp.ntaps[r] : mt;
           // (measured at one / two utterances, 150 frames: 7-tap convs 71 -> 62 us at 456 blocks but 101 -> 115 at 912; the first transposed conv,
           // 2 taps per phase, 85 -> 129 us: stride-1 layers with four taps or more on at most two blocks per CU)
-          const bool wall = L.chg == 2 && mt >= 4 && L.cp.S == 1 && (long long)L.grid.x * L.grid.y * L.grid.z <= 512 && !smi_env("SPARKMI_CB_NOWALL");
+          const bool wall = L.chg == 2 && mt >= 4 && L.cp.S == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWALL");
 #define SMI_CBW(QB_, NC_) hipLaunchKernelGGL((k_convb<QB_, true, 2, NC_, false, true>), L.grid, dim3(256), L.lds, st, L.cp)
           if (wall) { if (L.qb == 1) { if (wide) SMI_CBW(1, 2); else SMI_CBW(1, 1); } else SMI_CBW(2, 2); }
           else if (L.qb == 1) { if (wide) SMI_CB(1, true, 2, 2); else SMI_CB(1, true, 2, 1); }
@@ -1338,7 +1342,7 @@ int run_launch(const Launch& L, hipStream_t st) {
       } else if (L.chg == 4) {      // 1-tap layers: 128-channel chunks, narrow rows
         if (L.ks) {
           // measured (profiles/README.md): pays up to about two blocks per CU, costs beyond (fewer waves fit)
-          const bool wpf = (long long)L.grid.x * L.grid.y * L.grid.z <= 512;
+          const bool wpf = plan_grid_blocks(L) <= 512;
           if (L.qb == 1 && wpf) hipLaunchKernelGGL((k_conv<1, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp);
           else if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, true, 4, 1>), L.grid, dim3(256), L.lds, st, L.cp);
           else if (wpf) hipLaunchKernelGGL((k_conv<2, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp);
@@ -1399,11 +1403,23 @@ int run_launch(const Launch& L, hipStream_t st) {
   return SMI_OK;
 }
 
-// Build one conv launch.  X/Y strides are in floats; Lmax = padded INPUT length (time units).
+// The shape a launch plan is chosen for where that is not the call's own (smi_voc_forward_rows): ONE row of `frames` frames, in a
+// call whose grids cover rows of up to `ext_frames` frames.  A layer that works at Lmax = up * ext_frames positions plans for
+// up * frames (the per-utterance vector projections, Lmax = 1, for 1).
+struct PlanShape {
+  int frames, ext_frames;
+  int len(int Lmax) const { return Lmax % ext_frames == 0 ? Lmax / ext_frames * frames : Lmax; }
+};
+
+// Build one conv launch.  X/Y strides are in floats; Lmax = padded INPUT length (time units).  The call shape (B, Lmax) plays two
+// roles: the PLAN shape picks tile width, channel split, wave count, chunk size and kernel form -- the summation order -- and the
+// EXTENT sizes the grid.  With `ps` the plan is that of ps's one row and only the extent comes from (B, Lmax): blocks beyond a
+// row's own length exit, so every row carries the bits of its plan shape.
 Launch make_conv_w(const std::string& name, const float* W, const float* bias,
                    int Cout, int Cin, int K, int dil, int S, int pad, const float* X, int xstride, long long xb,
                  float* Y, float* Ys, const float* alpha, const float* R, int ystride, long long yb,
-                 const int* lens, int B, int Lmax, int act, int istr = 1, const int* olens = nullptr, bool bf = false) {
+                 const int* lens, int B, int Lmax, int act, int istr = 1, const int* olens = nullptr, bool bf = false,
+                   const PlanShape* ps = nullptr) {
   // Lmax = padded OUTPUT positions per phase (= input length for stride-1 convs and transposed convs)
   // bf: the weights are packed as bf16 planes (PACK_CONV_B / PACK_CONVT_B) and the layer runs on k_convb
   Launch L;
@@ -1424,6 +1440,8 @@ Launch make_conv_w(const std::string& name, const float* W, const float* bias,
     for (int i = 0; i < g.ntaps[r]; ++i) p.off[r][i] = g.off[r][i];
   }
   const int cot = pad32(Cout) / 32;
+  const int eB = B, eL = Lmax;   // the extent; from here to the grid, (B, Lmax) is the plan shape
+  if (ps) { B = 1; Lmax = ps->len(Lmax); }
   // waves split the input channels when there are few time tiles and many channels
   // 64-column time tiles unless that leaves most CUs idle (short sequences): then 32-column tiles double the blocks
   const long long blocks64 = (long long)((Lmax + 63) / 64) * cot * B * S;
@@ -1472,6 +1490,13 @@ Launch make_conv_w(const std::string& name, const float* W, const float* bias,
         L.lds = (size_t)2 * 8 * xwt * 16;
       }
     }
+  }
+  if (ps) {   // the plan's grid is remembered, the launch covers the extent
+    L.plan_blocks = (long long)L.grid.x * L.grid.y * L.grid.z;
+    const int cols = 32 * L.qb;
+    L.grid.x = (eL + cols - 1) / cols;
+    L.grid.z *= eB;
+    B = eB; Lmax = eL;
   }
   L.gemv = false;   // set by the caller for the per-utterance vector projections (use_gemv)
   size_t lds = (size_t)8 * L.nwv * L.chg * p.xw * 4;

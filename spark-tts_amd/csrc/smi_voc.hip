@@ -177,15 +177,15 @@ const float* ent(const smi_voc* h, const std::string& name) { return wsrc(h).get
 Launch make_conv(const WSrc& w, const std::string& name, const std::string& wname, const char* bname,
                  int Cout, int Cin, int K, int dil, int S, int pad, const float* X, int xstride, long long xb,
                  float* Y, float* Ys, const float* alpha, const float* R, int ystride, long long yb,
-                 const int* lens, int B, int Lmax, int act) {
+                 const int* lens, int B, int Lmax, int act, const PlanShape* ps = nullptr) {
   return make_conv_w(name, w.get(wname), bname ? w.get(bname) : nullptr, Cout, Cin, K, dil, S, pad, X, xstride, xb, Y, Ys,
-                     alpha, R, ystride, yb, lens, B, Lmax, act, 1, nullptr, w.is_bf(wname));
+                     alpha, R, ystride, yb, lens, B, Lmax, act, 1, nullptr, w.is_bf(wname), ps);
 }
 Launch make_conv(const smi_voc* h, const std::string& name, const std::string& wname, const char* bname,
                  int Cout, int Cin, int K, int dil, int S, int pad, const float* X, int xstride, long long xb,
                  float* Y, float* Ys, const float* alpha, const float* R, int ystride, long long yb,
-                 const int* lens, int B, int Lmax, int act) {
-  return make_conv(wsrc(h), name, wname, bname, Cout, Cin, K, dil, S, pad, X, xstride, xb, Y, Ys, alpha, R, ystride, yb, lens, B, Lmax, act);
+                 const int* lens, int B, int Lmax, int act, const PlanShape* ps = nullptr) {
+  return make_conv(wsrc(h), name, wname, bname, Cout, Cin, K, dil, S, pad, X, xstride, xb, Y, Ys, alpha, R, ystride, yb, lens, B, Lmax, act, ps);
 }
 
 // ---- launch builders shared by smi_voc_forward and the one-block entry points (smi_voc_block_run): the same kernels,
@@ -197,12 +197,13 @@ Launch make_conv(const smi_voc* h, const std::string& name, const std::string& w
 // with it).  The fused form (k_resunit, below) cannot write over US -- a block's neighbours still read their halo columns from it --
 // and leaves the Snake'd output in A, which it does not otherwise need.  Returns the buffer that holds it (null: none asked for).
 float* add_res_unit(std::vector<Launch>& P, const WSrc& w, const std::string& u, int C, int dil, const float* U, float* US,
-                    float* A, float* rawout, bool want_us, const float* next_alpha, int L, long long bs, const int* lens, int B) {
+                    float* A, float* rawout, bool want_us, const float* next_alpha, int L, long long bs, const int* lens, int B,
+                    const PlanShape* ps = nullptr) {
   float* US_out = want_us ? US : nullptr;
   P.push_back(make_conv(w, u + ".conv7", u + ".1.weight", (u + ".1.bias").c_str(), C, C, 7, dil, 1, 3 * dil, US, L, bs,
-                        nullptr, A, w.get(u + ".2.alpha"), nullptr, L, bs, lens, B, L, ACT_NONE));
+                        nullptr, A, w.get(u + ".2.alpha"), nullptr, L, bs, lens, B, L, ACT_NONE, ps));
   P.push_back(make_conv(w, u + ".conv1+res", u + ".3.weight", (u + ".3.bias").c_str(), C, C, 1, 1, 1, 0, A, L, bs,
-                        rawout, US_out, next_alpha, U, L, bs, lens, B, L, ACT_NONE));
+                        rawout, US_out, next_alpha, U, L, bs, lens, B, L, ACT_NONE, ps));
   // C = 96 / 192 on the bf16-split pipe with one output tile per wave (not the channel-split mode of short sequences): the two
   // launches become one k_resunit (SPARKMI_RESFUSE=0: two launches, A/B).  The choice depends on the layer and on whether the
   // grid fills the chip, as every launch plan does -- never on a row's neighbours.
@@ -233,16 +234,16 @@ float* add_res_unit(std::vector<Launch>& P, const WSrc& w, const std::string& u,
 // the function returns which (a fused unit flips the two; see add_res_unit).
 float* add_dec_block(std::vector<Launch>& P, const WSrc& w, const std::string& b, int cin, int cout, int k, int s, const float* s_in,
                    int Lin, long long bs_in, float* U, float* US, float* A, float* raw_final, const float* next_alpha, long long bs,
-                   const int* lens_in, const int* lens_out, int B) {
+                   const int* lens_in, const int* lens_out, int B, const PlanShape* ps = nullptr) {
   const int Lout = Lin * s;
   P.push_back(make_conv(w, b + ".convT", b + ".1.weight", (b + ".1.bias").c_str(), cout, cin, k, 1, s, (k - s) / 2, s_in, Lin, bs_in,
-                        U, US, w.get(b + ".2.block.0.alpha"), nullptr, Lout, bs, lens_in, B, Lin, ACT_NONE));
+                        U, US, w.get(b + ".2.block.0.alpha"), nullptr, Lout, bs, lens_in, B, Lin, ACT_NONE, ps));
   for (int r = 0; r < 3; ++r) {
     const std::string u = b + "." + std::to_string(r + 2) + ".block";
     const int dil = r == 0 ? 1 : (r == 1 ? 3 : 9);
     const bool last = r == 2;
     const float* na = last ? next_alpha : w.get(b + "." + std::to_string(r + 3) + ".block.0.alpha");
-    float* out = add_res_unit(P, w, u, cout, dil, U, US, A, last ? raw_final : U, !(last && !next_alpha), na, Lout, bs, lens_out, B);
+    float* out = add_res_unit(P, w, u, cout, dil, U, US, A, last ? raw_final : U, !(last && !next_alpha), na, Lout, bs, lens_out, B, ps);
     if (out && out != US) { A = US; US = out; }   // the Snake'd stream now lives in the other buffer; the old one is the next unit's scratch
   }
   return US;
@@ -263,12 +264,12 @@ void add_lnorm(std::vector<Launch>& P, const WSrc& w, const std::string& name, c
 
 // ConvNeXtBlock (blocks/vocos.py:26-62): x += gamma * pwconv2(GELU(pwconv1(norm(dwconv7(x))))); n, m: scratch
 void add_convnext(std::vector<Launch>& P, const WSrc& w, const std::string& b, int D, int I, float* x, float* n, float* m,
-                  const float* ada, int ada_stride, int T, long long bs, const int* lens, int B) {
+                  const float* ada, int ada_stride, int T, long long bs, const int* lens, int B, const PlanShape* ps = nullptr) {
   add_lnorm(P, w, b + ".dwconv+norm", b + ".norm", ada, ada_stride, w.get(b + ".dwconv.weight"), w.get(b + ".dwconv.bias"), x, n, 0, D, T, bs, lens, B);
   P.push_back(make_conv(w, b + ".pwconv1", b + ".pwconv1.weight", (b + ".pwconv1.bias").c_str(), I, D, 1, 1, 1, 0, n, T, bs, m,
-                        nullptr, nullptr, nullptr, T, bs, lens, B, T, ACT_GELU));
+                        nullptr, nullptr, nullptr, T, bs, lens, B, T, ACT_GELU, ps));
   P.push_back(make_conv(w, b + ".pwconv2", b + ".pwconv2.weight", (b + ".pwconv2.bias").c_str(), D, I, 1, 1, 1, 0, m, T, bs, x,
-                        nullptr, nullptr, x, T, bs, lens, B, T, ACT_NONE));
+                        nullptr, nullptr, x, T, bs, lens, B, T, ACT_NONE, ps));
   P.back().cp.gamma = w.get(b + ".gamma");
 }
 
@@ -440,32 +441,21 @@ int smi_voc_destroy(smi_voc* h) {
   return SMI_OK;
 }
 
-int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host, const int32_t* glob_dev, int B, int T,
-                    float* wav_dev, void* stream) {
-  SMI_REQUIRE(h && sem_dev && lens_host && glob_dev && wav_dev, "smi_voc_forward: null argument");
+}  // extern "C"
+
+namespace {
+
+// The launch list of one forward over rows row0 .. row0 + B of a call (their lengths sit in h->lens_dev): T is the extent -- the
+// longest of these rows, and the row stride of the working buffers; semstride / wavstride are the row strides of the CALLER's
+// sem_dev / wav_dev, which sem_dev / glob_dev / wav_dev point into at row0.  ps null: the plan shape is (B, T) (smi_voc_forward);
+// else the plan is ps's one row (smi_voc_forward_rows).
+int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int semstride, const int32_t* glob_dev, int B, int T,
+                float* wav_dev, long long wavstride, int row0, const PlanShape* ps) {
   const smi_voc_cfg& c = h->cfg;
-  SMI_REQUIRE(B >= 1 && B <= c.max_batch, "smi_voc_forward: B=%d outside 1..%d", B, c.max_batch);
-  SMI_REQUIRE(T >= 1 && T <= c.max_frames, "smi_voc_forward: T_max=%d outside 1..%d", T, c.max_frames);
-  hipStream_t st = (hipStream_t)stream;
-  // valid lengths at every resolution: lens_dev[s][b] = lens[b] * prod(rates[0..s))
-  std::vector<int32_t>& hl = h->host_lens;
-  hl.assign((size_t)8 * c.max_batch, 0);
-  for (int b = 0; b < B; ++b) {
-    SMI_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "smi_voc_forward: lens[%d]=%d outside 1..%d", b, lens_host[b], T);
-    int up = 1;
-    for (int s = 0; s <= c.dec_nblocks; ++s) {
-      hl[(size_t)s * c.max_batch + b] = lens_host[b] * up;
-      if (s < c.dec_nblocks) up *= c.dec_rates[s];
-    }
-    hl[(size_t)7 * c.max_batch + b] = 1;   // length-1 "sequences" for the d-vector GEMVs
-  }
-  SMI_HIP(hipMemcpyAsync(h->lens_dev, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st));
-  auto lens_at = [&](int s) { return (const int*)(h->lens_dev + (size_t)s * c.max_batch); };
+  auto lens_at = [&](int s) { return (const int*)(h->lens_dev + (size_t)s * c.max_batch + row0); };
   const int* len1 = lens_at(7);
   const int* len0 = lens_at(0);
 
-  std::vector<Launch>& P = h->prog;
-  P.clear();
   const long long bs = (long long)h->buf_floats;
   float* bufs[4] = {h->buf[0], h->buf[1], h->buf[2], h->buf[3]};
   // a buffer that none of the listed live activations occupies
@@ -497,7 +487,7 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
   }
   P.push_back(make_conv(h, "spk_project", "speaker_encoder.project.weight", "speaker_encoder.project.bias",
                         c.spk_out_dim, latn, 1, 1, 1, 0, lat, 1, latn, dvec, nullptr, nullptr, nullptr, 1, c.spk_out_dim,
-                        len1, B, 1, ACT_NONE));
+                        len1, B, 1, ACT_NONE, ps));
   auto use_gemv = [&](Launch& L) { L.gemv = true; L.grid = dim3((L.cp.Cout + 31) / 32, B); };
   use_gemv(P.back());
   // all AdaLayerNorm scale/shift projections of the condition in one GEMM (vocos.py:105-108)
@@ -508,25 +498,25 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
       if (e.name.rfind("cat:", 0) == 0 && e.kind == PACK_RAW) bn = e.name;
     }
     P.push_back(make_conv(h, "adaln_params", wn, bn.c_str(), ada_stride, c.pre_cond_dim, 1, 1, 1, 0, dvec, 1, c.spk_out_dim,
-                          ada, nullptr, nullptr, nullptr, 1, ada_stride, len1, B, 1, ACT_NONE));
+                          ada, nullptr, nullptr, nullptr, 1, ada_stride, len1, B, 1, ACT_NONE, ps));
     use_gemv(P.back());
   }
   // --- semantic tokens -> codebook rows -> out_project (factorized_vector_quantize.py:154-167)
   float* zc = bufs[0];
   {
     Launch L; L.kind = 2; L.name = "codebook"; L.flops = 0;
-    L.sem = sem_dev; L.semstride = T; L.cb = ent(h, "quantizer.codebook.weight"); L.D = c.codebook_dim; L.cbsize = c.codebook_size;
+    L.sem = sem_dev; L.semstride = semstride; L.cb = ent(h, "quantizer.codebook.weight"); L.D = c.codebook_dim; L.cbsize = c.codebook_size;
     L.lens = len0; L.Z = zc; L.zstride = T; L.zb = bs; L.grid = dim3((T + 127) / 128, B);
     P.push_back(L);
   }
   float* zq = other({zc});
   P.push_back(make_conv(h, "vq_out_project", "quantizer.out_project.weight", "quantizer.out_project.bias", c.vq_input_dim,
-                        c.codebook_dim, 1, 1, 1, 0, zc, T, bs, zq, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE));
+                        c.codebook_dim, 1, 1, 1, 0, zc, T, bs, zq, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
   if (h->debug) { Launch cp = P.back(); cp.cp.Y = h->dbg[0]; cp.name = "vq_out_project(dbg)"; P.push_back(cp); }
   // --- prenet (feat_decoder.py:78-94)
   float* cur = other({zq});
   P.push_back(make_conv(h, "prenet.linear_pre", "prenet.linear_pre.weight", "prenet.linear_pre.bias", D, c.pre_input_channels, 1,
-                        1, 1, 0, zq, T, bs, cur, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE));
+                        1, 1, 0, zq, T, bs, cur, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
   P.back().cp.out_scale = c.pre_num_down > 0 ? 3.0f : 1.0f;   // first SamplingBlock(ratio 1): 3x
   int ada_idx = 0;
   const WSrc ws = wsrc(h);
@@ -538,13 +528,13 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
   auto vocos = [&](const std::string& p, int nl, bool ada_norm, int triple_out) {
     float* n = other({cur});          // conv / norm output
     P.push_back(make_conv(h, p + ".embed", p + ".embed.weight", (p + ".embed.bias").c_str(), D, D, 7, 1, 1, 3, cur, T, bs, n,
-                          nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE));
+                          nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
     float* x = other({n});            // residual stream (cur is dead once embed has run)
     lnorm(p + ".norm", p + ".norm", ada_norm, n, x, 0);
     float* m = other({x, n});         // MLP hidden
     for (int j = 0; j < nl; ++j) {
       const float* ap = ada_norm ? ada + (size_t)(ada_idx++) * 2 * D : nullptr;
-      add_convnext(P, ws, p + ".convnext." + std::to_string(j), D, I, x, n, m, ap, ada_stride, T, bs, len0, B);
+      add_convnext(P, ws, p + ".convnext." + std::to_string(j), D, I, x, n, m, ap, ada_stride, T, bs, len0, B, ps);
     }
     lnorm(p + ".final_layer_norm", p + ".final_layer_norm", false, x, n, triple_out);
     cur = n;
@@ -552,11 +542,11 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
   for (int i = 0; i < c.pre_num_down; ++i)
     vocos("prenet.downsample." + std::to_string(i) + ".1", 2, false, (i + 1 < c.pre_num_down) ? 1 : 0);
   vocos("prenet.vocos_backbone", c.pre_layers, c.pre_cond_dim > 0, 0);
-  SMI_REQUIRE(!c.pre_tanh_final, "smi_voc_forward: use_tanh_at_final is not supported");
+  SMI_REQUIRE(!c.pre_tanh_final, "smi_voc: use_tanh_at_final is not supported");
   // prenet.linear, then + d_vector per utterance (bicodec.py:185-186)
   float* x0 = other({cur});
   P.push_back(make_conv(h, "prenet.linear+d", "prenet.linear.weight", "prenet.linear.bias", c.pre_out_channels, D, 1, 1, 1, 0, cur, T,
-                        bs, x0, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE));
+                        bs, x0, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
   P.back().cp.bbias = dvec;
   if (h->debug) { Launch cp = P.back(); cp.cp.Y = h->dbg[1]; cp.name = "prenet.linear+d(dbg)"; P.push_back(cp); }
   // --- WaveGenerator (wave_generator.py:56-88)
@@ -566,7 +556,7 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
   {
     const std::string a0 = "decoder.model.1.block.0.alpha";
     P.push_back(make_conv(h, "decoder.conv_in", "decoder.model.0.weight", "decoder.model.0.bias", ch, c.dec_in, 7, 1, 1, 3, x0, T, bs,
-                          h->debug ? h->dbg[2] : nullptr, s_in, ent(h, a0), nullptr, T, bs, len0, B, T, ACT_NONE));
+                          h->debug ? h->dbg[2] : nullptr, s_in, ent(h, a0), nullptr, T, bs, len0, B, T, ACT_NONE, ps));
   }
   for (int i = 0; i < c.dec_nblocks; ++i) {
     const int cin = ch >> i, cout = ch >> (i + 1), k = c.dec_ksizes[i], s = c.dec_rates[i];
@@ -580,16 +570,16 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
     const std::string next_alpha = i + 1 < c.dec_nblocks ? "decoder.model." + std::to_string(i + 2) + ".block.0.alpha"
                                                          : "decoder.model." + std::to_string(c.dec_nblocks + 1) + ".alpha";
     s_in = add_dec_block(P, ws, b, cin, cout, k, s, s_in, Lcur, bs, U, US, A, h->debug ? h->dbg[3 + i] : nullptr, ent(h, next_alpha), bs,
-                         lens_at(i), lens_at(i + 1), B);
+                         lens_at(i), lens_at(i + 1), B, ps);
     Lcur = Lout;
   }
   const int clast = ch >> c.dec_nblocks;
   const int hop = Lcur / T;
   {
     const std::string n = "decoder.model." + std::to_string(c.dec_nblocks + 2);
-    // final conv7 -> tanh, written straight into the caller's waveform buffer [B][hop*T]
+    // final conv7 -> tanh, written straight into the caller's waveform buffer [B][wavstride]
     P.push_back(make_conv(h, "decoder.conv_out+tanh", n + ".weight", (n + ".bias").c_str(), 1, clast, 7, 1, 1, 3, s_in, Lcur, bs,
-                          wav_dev, nullptr, nullptr, nullptr, Lcur, Lcur, lens_at(c.dec_nblocks), B, Lcur, ACT_TANH));
+                          wav_dev, nullptr, nullptr, nullptr, Lcur, wavstride, lens_at(c.dec_nblocks), B, Lcur, ACT_TANH, ps));
     {   // C -> 1: a thread per output sample instead of a 32-row MFMA tile with one live row (SPARKMI_VOC_C1=0: the MFMA kernel)
       Launch& L = P.back();
       const char* e = smi_env("SPARKMI_VOC_C1");
@@ -599,12 +589,132 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
         L.c1 = true; L.c1_len = Lcur;
       }
     }
-    Launch Z; Z.kind = 4; Z.name = "zero_tail"; Z.flops = 0; Z.wav = wav_dev; Z.wstride = Lcur; Z.lens = len0; Z.hop = hop;
-    Z.grid = dim3((Lcur + 255) / 256, B);
+    Launch Z; Z.kind = 4; Z.name = "zero_tail"; Z.flops = 0; Z.wav = wav_dev; Z.wstride = (int)wavstride; Z.lens = len0; Z.hop = hop;
+    Z.grid = dim3((unsigned)((wavstride + 255) / 256), B);
     P.push_back(Z);
   }
-  int rc = check_launches(P, "smi_voc_forward");
+  return SMI_OK;
+}
+
+// Every choice a launch list makes from its plan shape, launch by launch: two rows may share a launch sequence when these agree.
+std::vector<long long> plan_signature(const std::vector<Launch>& P) {
+  std::vector<long long> sig;
+  for (const Launch& L : P) {
+    sig.push_back(L.kind);
+    if (L.kind == 0) {
+      const bool mfma = !L.gemv && !L.c1;   // (the vector projections and the one-channel conv size their grids from the extent alone)
+      for (long long v : {(long long)L.qb, (long long)L.ks, (long long)L.chg, (long long)L.nwv, (long long)L.tph, (long long)L.gemv, (long long)L.c1,
+                          (long long)L.bf, (long long)L.cp.xw, (long long)L.lds, (long long)(mfma ? L.grid.y : 0), (long long)(mfma && plan_grid_blocks(L) <= 512)})
+        sig.push_back(v);
+    } else if (L.kind == 5) {
+      for (long long v : {(long long)L.res_nwv, (long long)L.rp.xw, (long long)L.lds}) sig.push_back(v);
+    } else if (L.kind == 1) {
+      sig.push_back(L.cpt);
+    }
+  }
+  return sig;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host, const int32_t* glob_dev, int B, int T,
+                    float* wav_dev, void* stream) {
+  SMI_REQUIRE(h && sem_dev && lens_host && glob_dev && wav_dev, "smi_voc_forward: null argument");
+  const smi_voc_cfg& c = h->cfg;
+  SMI_REQUIRE(B >= 1 && B <= c.max_batch, "smi_voc_forward: B=%d outside 1..%d", B, c.max_batch);
+  SMI_REQUIRE(T >= 1 && T <= c.max_frames, "smi_voc_forward: T_max=%d outside 1..%d", T, c.max_frames);
+  hipStream_t st = (hipStream_t)stream;
+  // valid lengths at every resolution: lens_dev[s][b] = lens[b] * prod(rates[0..s))
+  std::vector<int32_t>& hl = h->host_lens;
+  hl.assign((size_t)8 * c.max_batch, 0);
+  for (int b = 0; b < B; ++b) {
+    SMI_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "smi_voc_forward: lens[%d]=%d outside 1..%d", b, lens_host[b], T);
+    int up = 1;
+    for (int s = 0; s <= c.dec_nblocks; ++s) {
+      hl[(size_t)s * c.max_batch + b] = lens_host[b] * up;
+      if (s < c.dec_nblocks) up *= c.dec_rates[s];
+    }
+    hl[(size_t)7 * c.max_batch + b] = 1;   // length-1 "sequences" for the d-vector GEMVs
+  }
+  SMI_HIP(hipMemcpyAsync(h->lens_dev, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st));
+  std::vector<Launch>& P = h->prog;
+  P.clear();
+  long long hop = 1;
+  for (int i = 0; i < c.dec_nblocks; ++i) hop *= c.dec_rates[i];
+  int rc = voc_program(h, P, sem_dev, T, glob_dev, B, T, wav_dev, hop * T, 0, nullptr);
   if (rc) return rc;
+  if ((rc = check_launches(P, "smi_voc_forward"))) return rc;
+  for (const Launch& L : P)
+    if ((rc = run_launch(L, st))) return rc;
+  h->lastB = B; h->lastT = T;
+  return SMI_OK;
+}
+
+// A ragged batch whose rows carry their solo bits (include/sparkmi.h).  A row's plan is the launch list smi_voc_forward builds for
+// that row alone, (1, lens[b]); consecutive rows with equal plans (plan_signature) run as one launch sequence with that plan and
+// the extent (rows of the run, its longest row).  The launch list is rebuilt per call, as smi_voc_forward's is.
+int smi_voc_forward_rows(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host, const int32_t* glob_dev, int B, int T,
+                         float* wav_dev, void* stream) {
+  SMI_REQUIRE(h && sem_dev && lens_host && glob_dev && wav_dev, "smi_voc_forward_rows: null argument");
+  const smi_voc_cfg& c = h->cfg;
+  SMI_REQUIRE(B >= 1 && B <= c.max_batch, "smi_voc_forward_rows: B=%d outside 1..%d", B, c.max_batch);
+  SMI_REQUIRE(T >= 1 && T <= c.max_frames, "smi_voc_forward_rows: T_max=%d outside 1..%d", T, c.max_frames);
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int32_t>& hl = h->host_lens;
+  hl.assign((size_t)8 * c.max_batch, 0);
+  for (int b = 0; b < B; ++b) {
+    SMI_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "smi_voc_forward_rows: lens[%d]=%d outside 1..%d", b, lens_host[b], T);
+    int up = 1;
+    for (int s = 0; s <= c.dec_nblocks; ++s) {
+      hl[(size_t)s * c.max_batch + b] = lens_host[b] * up;
+      if (s < c.dec_nblocks) up *= c.dec_rates[s];
+    }
+    hl[(size_t)7 * c.max_batch + b] = 1;
+  }
+  long long hop = 1;
+  for (int i = 0; i < c.dec_nblocks; ++i) hop *= c.dec_rates[i];
+  int rc;
+  // the plan of every distinct length: the choices of that row's own smi_voc_forward (pointers do not enter a signature)
+  std::vector<std::pair<int, std::vector<long long>>> plans;
+  auto plan_of = [&](int len, const std::vector<long long>** out) -> int {
+    for (const auto& pl : plans)
+      if (pl.first == len) { *out = &pl.second; return SMI_OK; }
+    std::vector<Launch> solo;
+    const int rcs = voc_program(h, solo, sem_dev, len, glob_dev, 1, len, wav_dev, hop * len, 0, nullptr);
+    if (rcs) return rcs;
+    plans.emplace_back(len, plan_signature(solo));
+    *out = &plans.back().second;
+    return SMI_OK;
+  };
+  plans.reserve((size_t)B);   // (plan_of hands out pointers into it)
+  std::vector<Launch>& P = h->prog;
+  P.clear();
+  std::vector<Launch> G;
+  for (int r0 = 0; r0 < B;) {
+    const std::vector<long long>* sig = nullptr;
+    if ((rc = plan_of(lens_host[r0], &sig))) return rc;
+    int r1 = r0 + 1, Tg = lens_host[r0];
+    for (; r1 < B; ++r1) {
+      const std::vector<long long>* s2 = nullptr;
+      if ((rc = plan_of(lens_host[r1], &s2))) return rc;
+      if (*s2 != *sig) break;
+      Tg = lens_host[r1] > Tg ? lens_host[r1] : Tg;
+    }
+    const PlanShape ps{lens_host[r0], Tg};
+    G.clear();
+    if ((rc = voc_program(h, G, sem_dev + (size_t)r0 * T, T, glob_dev + (size_t)r0 * c.spk_token_num, r1 - r0, Tg,
+                          wav_dev + (size_t)r0 * hop * T, hop * T, r0, &ps))) return rc;
+    if (plan_signature(G) != *sig) {
+      smi_set_error("smi_voc_forward_rows: the launch list of rows %d..%d does not carry the plan of a %d-frame row", r0, r1 - 1, lens_host[r0]);
+      return SMI_EINVAL;
+    }
+    P.insert(P.end(), G.begin(), G.end());
+    r0 = r1;
+  }
+  if ((rc = check_launches(P, "smi_voc_forward_rows"))) return rc;
+  SMI_HIP(hipMemcpyAsync(h->lens_dev, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st));
   for (const Launch& L : P)
     if ((rc = run_launch(L, st))) return rc;
   h->lastB = B; h->lastT = T;

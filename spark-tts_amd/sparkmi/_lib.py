@@ -128,6 +128,7 @@ SYMBOLS = {
                                   _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_admit_constrained": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams),
                                        _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(C.c_int32), _VP]),
+    "smi_llm_poll": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_status": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_forward_logits": (_I, [_VP, _P(C.c_int64), _I, _VP, _VP]),
     "smi_llm_steps": (_I, [_VP]),
@@ -138,6 +139,7 @@ SYMBOLS = {
     "smi_voc_create": (_I, [_P(VocCfg), _VP, _SZ, _P(_VP)]),
     "smi_voc_destroy": (_I, [_VP]),
     "smi_voc_forward": (_I, [_VP, _VP, _P(C.c_int32), _VP, _I, _I, _VP, _VP]),
+    "smi_voc_forward_rows": (_I, [_VP, _VP, _P(C.c_int32), _VP, _I, _I, _VP, _VP]),
     "smi_voc_debug_stage": (_I, [_VP, _I, _VP, _SZ, _P(_SZ), _VP]),
     "smi_voc_num_launches": (_I, [_VP]),
     "smi_voc_time_launch": (_I, [_VP, _I, _I, _P(C.c_float), _P(C.c_double), C.c_char_p, _I, _VP]),

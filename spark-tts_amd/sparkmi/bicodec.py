@@ -234,6 +234,41 @@ class BiCodecVocoder:
         self._keep = (sem, glob)   # inputs must stay alive until the stream has consumed them
         return wav
 
+    @torch.no_grad()
+    def detokenize_rows(self, semantic_tokens: torch.Tensor, global_tokens: torch.Tensor,
+                        lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """``detokenize`` for a ragged batch whose rows keep the bits of their solo runs (``smi_voc_forward_rows``): row b equals,
+        bit for bit, ``detokenize`` of that row alone, whatever else is in the call and wherever the row sits -- what a server
+        needs to vocode the chunks of many requests in one call.  The rows are sorted by length first, so rows with equal
+        launch plans are neighbours and share one launch sequence, and the result is put back in the caller's order; more than
+        ``max_batch`` rows go in several calls.  (B, T) + (B, 1, Ntok) -> (B, 1, hop*T), zero beyond hop*length."""
+        sem = semantic_tokens.to(torch.int64)
+        if sem.ndim == 1:
+            sem = sem[None]
+        B, T = sem.shape
+        glob = global_tokens.to(torch.int32).reshape(B, -1)
+        if glob.shape[1] != self.cfg.spk_token_num:
+            raise ValueError(f"expected {self.cfg.spk_token_num} global tokens per row, got {glob.shape[1]}")
+        lens = np.full(B, T, np.int32) if lengths is None else np.asarray(lengths, np.int32)
+        order = np.argsort(lens, kind="stable")
+        wav = torch.zeros((B, 1, self.hop * T), dtype=torch.float32, device=self.device)
+        keep = []
+        for i in range(0, B, self.max_batch):
+            rows = order[i: i + self.max_batch]
+            idx = torch.from_numpy(rows.astype(np.int64))
+            l = np.ascontiguousarray(lens[rows])
+            Tm = int(l.max())
+            s = sem[idx.to(sem.device), :Tm].to(self.device).contiguous()
+            g = glob[idx.to(glob.device)].to(self.device).contiguous()
+            w = torch.empty((len(rows), self.hop * Tm), dtype=torch.float32, device=self.device)
+            self._lib.check(self._lib.smi_voc_forward_rows(
+                self._h, C.c_void_p(s.data_ptr()), l.ctypes.data_as(C.POINTER(C.c_int32)),
+                C.c_void_p(g.data_ptr()), len(rows), Tm, C.c_void_p(w.data_ptr()), self._stream()), "smi_voc_forward_rows")
+            wav[idx.to(self.device), 0, : self.hop * Tm] = w
+            keep.append((s, g, w))
+        self._keep = keep   # inputs must stay alive until the stream has consumed them
+        return wav
+
     # ------------------------------------------------------------------ test / bench entries
     def debug_stage(self, stage: int, channels: int, length: int, batch: int) -> torch.Tensor:
         """Stage activation of the last forward as (B, C, L).  -1 = d-vector (returns (B, out_dim));

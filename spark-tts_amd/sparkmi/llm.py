@@ -526,6 +526,26 @@ class SparkLLM:
                                                   fin.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_slots_tokens")
         return [(out[i, : n[i]].tolist(), bool(fin[i])) for i in range(len(arr))]
 
+    def poll(self, slots: Sequence[int], from_: Sequence[int], cap: int):
+        """[(new ids, count, finished)] of several slots (live, or retired and not yet reused): the ids slot i has emitted from
+        its own offset ``from_[i]`` on, at most ``cap`` of them, the tokens it has emitted so far and its eos flag -- one small
+        device round trip (``smi_llm_poll``: a gather kernel and one copy of ``len(slots) * (8 + 8 * cap)`` bytes), where
+        ``slots_tokens`` copies the whole history.  Equal to ``slots_tokens`` of the same slots, sliced."""
+        arr = np.asarray(list(slots), dtype=np.int32)
+        frm = np.asarray(list(from_), dtype=np.int32)
+        if arr.shape != frm.shape:
+            raise ValueError(f"poll: {len(arr)} slots, {len(frm)} offsets")
+        cap = int(cap)
+        out = np.zeros((len(arr), max(cap, 1)), dtype=np.int64)
+        n = np.zeros(len(arr), dtype=np.int32)
+        cnt = np.zeros(len(arr), dtype=np.int32)
+        fin = np.zeros(len(arr), dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._lib.check(self._lib.smi_llm_poll(self._h, arr.ctypes.data_as(i32), frm.ctypes.data_as(i32), len(arr),
+                                               out.ctypes.data_as(C.POINTER(C.c_int64)), cap, n.ctypes.data_as(i32),
+                                               cnt.ctypes.data_as(i32), fin.ctypes.data_as(i32), self._stream()), "smi_llm_poll")
+        return [(out[i, : n[i]].tolist(), int(cnt[i]), bool(fin[i])) for i in range(len(arr))]
+
     def slots_logprobs(self, slots: Sequence[int], cap: int) -> List[np.ndarray]:
         """Per-token log-probabilities (float32, one per token of ``slots_tokens``) of several slots whose sequences were
         admitted with ``return_log_probs``, live or retired and not yet reused, in one device round trip."""

@@ -5,8 +5,9 @@ Same constructor and ``inference()`` signature, same attributes (``device``, ``m
 strings, same token parsing, same float32 numpy waveform.  The two heavy calls run on the HIP
 kernels: ``self.model.generate`` (``SparkLLM``) and ``self.audio_tokenizer.detokenize``
 (``BiCodecTokenizer``).  Keyword-only additions: ``do_sample``, ``max_new_tokens``,
-``prompt_tokens`` (pre-computed prompt audio tokens), ``inference_batch`` and
-``inference_stream`` (chunked vocoding while the LLM generates, the reference's decoupled Triton mode).
+``prompt_tokens`` (pre-computed prompt audio tokens), ``inference_batch``,
+``inference_stream`` (chunked vocoding while the LLM generates, the reference's decoupled Triton mode), ``serve`` (in-flight
+batching) and ``serve_stream`` (both at once: chunked audio for every live request of an in-flight batch).
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS
                   num_returns, penalty_neutral)
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
-from .streaming import ChunkScheduler
+from .streaming import ChunkScheduler, StreamMux
 from .weights import load_llm_state
 
 
@@ -468,3 +469,133 @@ class SparkTTS:
                 yield i, w
             else:
                 yield i, w, _lp_info(toks, lps[: len(toks)])
+
+    @torch.no_grad()
+    def serve_stream(self, requests, temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *, do_sample: bool = True,
+                     max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8,
+                     audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
+                     audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1):
+        """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
+        answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
+        yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
+        them (join with ``streaming.crossfade``), while up to ``max_batch`` requests are live.  Requests enter free slots as in
+        ``serve`` (one admission fills all free slots; budget ``max_positions - len(ids) - decode_stride``), so the sampling,
+        penalty, ``allowed_token_ids`` and ``speech_tokens_only`` keys work per request, and a request's tokens -- cut at the
+        first eos -- are those of the admission path for that request alone.  Every chunk is the vocoder's output for that
+        chunk's tokens alone, bit for bit, whoever else is live: the ready chunks of all requests go through ONE
+        ``detokenize_rows`` call per poll.  Between polls (every ``decode_stride`` steps) only the new ids cross to the host
+        (``SparkLLM.poll``).  The vocoder call runs on a HIP stream of its own -- its inputs come from the host, so it waits
+        for nothing of the LLM, and the LLM's stream never waits for it -- and the next ``decode_stride`` steps are enqueued
+        before the host waits for the waveforms.  ``num_return_sequences`` and ``return_log_probs`` are refused (ValueError,
+        before anything reaches the device)."""
+
+        def checked(reqs):   # a request's keys, checked before it reaches the device
+            for i, r in enumerate(reqs):
+                for k in (FORK_KEY,) + tuple(LOGPROB_KEYS):
+                    if k in r:
+                        raise ValueError(f"request {i}: {k} is not supported by serve_stream")
+                yield r
+
+        if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
+            for _ in checked(requests):
+                pass
+        decode_stride = int(decode_stride)
+        if decode_stride < 1:
+            raise ValueError("decode_stride must be >= 1")
+        voc = self.audio_tokenizer.model
+        ntok, hop = voc.cfg.spk_token_num, voc.hop
+        mux = StreamMux(ntok, self._map, self._parse, frame_rate=self.sample_rate // hop,
+                        audio_chunk_duration=audio_chunk_duration, max_audio_chunk_duration=max_audio_chunk_duration,
+                        audio_chunk_size_scale_factor=audio_chunk_size_scale_factor,
+                        audio_chunk_overlap_duration=audio_chunk_overlap_duration)
+        if getattr(self, "_voc_stream", None) is None:
+            self._voc_stream = torch.cuda.Stream(device=self.device)
+        vs = self._voc_stream
+
+        def llm_requests():
+            for i, r in enumerate(checked(requests)):
+                if r.get("gender") is not None:
+                    prompt, g = self.process_prompt_control(r["gender"], r.get("pitch"), r.get("speed"), r["text"]), None
+                else:
+                    prompt, g = self.process_prompt(r["text"], r.get("prompt_speech_path"), r.get("prompt_text"), r.get("prompt_tokens"))
+                    g = torch.as_tensor(g).reshape(-1).tolist()
+                    if len(g) != ntok:
+                        raise ValueError(f"request {i}: {len(g)} global tokens, the speaker encoder needs {ntok}")
+                ids = self.tokenizer([prompt], return_tensors="pt").input_ids[0].tolist()
+                budget = min(max_new_tokens, self._max_positions - len(ids) - decode_stride)
+                if budget < 1:
+                    raise ValueError(f"request {i}: a prompt of {len(ids)} tokens leaves no room in max_positions={self._max_positions}")
+                yield i, ids, budget, g, _request_sampling(r, self.speech_token_ids)
+
+        def vocode(chunks):   # every ready chunk of every request in one ragged call, enqueued on the vocoder's own stream
+            rows = [c for c in chunks if c[2]]
+            wav = None
+            if rows:
+                lens = [len(c[2]) for c in rows]
+                sem_t = torch.zeros((len(rows), max(lens)), dtype=torch.long)
+                for b, c in enumerate(rows):
+                    sem_t[b, : lens[b]] = torch.tensor(c[2])
+                glob_t = torch.tensor([mux.global_ids(c[0]) for c in rows], dtype=torch.long).unsqueeze(1)
+                with torch.cuda.stream(vs):
+                    wav = voc.detokenize_rows(sem_t, glob_t, lengths=lens)
+            return chunks, wav
+
+        def collect(job):     # the host waits for the vocoder's stream only
+            chunks, wav = job
+            if wav is not None:
+                with torch.cuda.stream(vs):
+                    wav = wav.squeeze(1).cpu().numpy()
+            b = 0
+            for key, _, sem, last in chunks:
+                if sem:
+                    yield key, wav[b, : len(sem) * hop].copy(), last
+                    b += 1
+                else:
+                    yield key, np.zeros(0, dtype=np.float32), last
+
+        self.model.set_sampling(do_sample, temperature, int(top_k), float(top_p), seed)
+        it = llm_requests()
+        pending = next(it, None)
+        live: Dict[int, list] = {}    # slot -> [index, budget, tokens read so far]
+        started, job = False, None
+        try:
+            while pending is not None or live:
+                batch = []
+                while pending is not None and len(live) + len(batch) < self._max_batch:
+                    batch.append(pending)
+                    pending = next(it, None)
+                if batch:             # all free slots are filled by ONE admission, as SparkLLM.serve does
+                    if not started:
+                        self.model.session_begin(self._eos)
+                        started = True
+                    slots = self.model.admit([r[1] for r in batch], [r[4] for r in batch])
+                    for slot, r in zip(slots, batch):
+                        live[slot] = [r[0], int(r[2]), 0]
+                        mux.open(r[0], r[3])
+                self.model.decode(decode_stride)   # enqueued: it runs while the host collects the previous poll's chunks
+                if job is not None:
+                    yield from collect(job)
+                    job = None
+                order = list(live)
+                cap = decode_stride + (1 if any(live[s][2] == 0 for s in order) else 0)   # (+ the token the admission emitted)
+                got = self.model.poll(order, [live[s][2] for s in order], cap)
+                ready, leave = [], []
+                for slot, (new, count, fin) in zip(order, got):
+                    key, budget, off = live[slot]
+                    new = new[: budget - off]
+                    live[slot][2] = off + len(new)
+                    done = (bool(fin) or count >= budget) and live[slot][2] >= min(count, budget)   # (and every id of it is read)
+                    ready += mux.push(key, new, done)
+                    if done:
+                        leave.append(slot)
+                if ready:
+                    job = vocode(ready)
+                if leave:             # their last chunks are flushed (mux.push above); their rows are dropped on the device
+                    self.model.retire_many(leave)
+                    for slot in leave:
+                        mux.close(live.pop(slot)[0])
+            if job is not None:
+                yield from collect(job)
+                job = None
+        finally:
+            vs.synchronize()   # an abandoned stream leaves no vocoder work behind (the handle's scratch is shared with detokenize)

@@ -8,12 +8,14 @@ stream into chunks that overlap by ``audio_chunk_overlap_duration`` and grow by
 cross-fades consecutive chunks over the overlap (``runtime/triton_trtllm/client_grpc.py:390-415``).
 
 ``ChunkScheduler`` is the pure host logic (no GPU), ``crossfade`` the client-side reconstruction;
-``SparkTTS.inference_stream`` (pipeline.py) drives the HIP LLM and vocoder with them.
+``SparkTTS.inference_stream`` (pipeline.py) drives the HIP LLM and vocoder with them.  ``StreamMux`` is the same logic for many
+requests at once -- the decoupled chunk loop answering every live request of an in-flight batch (run.sh:49-65) -- and
+``SparkTTS.serve_stream`` drives it.
 """
 from __future__ import annotations
 
 import math
-from typing import Iterable, Iterator, List, Sequence
+from typing import Callable, Dict, Hashable, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -81,3 +83,132 @@ def stream_chunks(token_iter: Iterator[Sequence[int]], scheduler: ChunkScheduler
             yield c
     for c in scheduler.flush():
         yield c
+
+
+class _Stream:
+    """One request of a ``StreamMux``."""
+
+    def __init__(self, sched: ChunkScheduler, global_ids: Optional[List[int]]):
+        self.sched = sched
+        self.given = global_ids is not None          # clone mode: the request brought its global ids
+        self.glob: List[int] = list(global_ids) if global_ids is not None else []
+        self.ids: List[int] = []                     # every generated id so far (the whole-history parser needs them)
+        self.tables = True                           # still on the id tables (no ordinary text id seen)
+        self.n_sem = 0                               # semantic tokens handed to the scheduler
+        self.held: List[List[int]] = []              # ready chunks waiting for the speaker tokens
+        self.index = 0                               # chunks released so far
+        self.finished = False
+
+
+class StreamMux:
+    """Chunked vocoding for many concurrent requests, host side only (no GPU, no torch): per request key an incremental token
+    parser, the speaker-token gate and a ``ChunkScheduler``.
+
+    ``tables``: an object with ``sem`` / ``glob`` (id -> bicodec index), ``special`` (ids to skip) and ``usable``
+    (``pipeline._TokenMap``), or None; ``parse``: a callable ids -> (semantic ids, global ids) over a request's WHOLE history
+    (``SparkTTS._parse``), or None.  While every id of a request is in the tables it is parsed id by id; the first id that is
+    not (an ordinary text token) moves that request to ``parse`` for good, as ``_TokenMap.fast_parse`` falls back.  One of the
+    two must be given.
+
+    The gate: a clone request brings its global ids (``open(key, global_ids)``) and its chunks are released as they become
+    ready; a control-mode request (no global ids) must first have GENERATED ``spk_token_num`` of them -- its ready chunks wait
+    until then and are released in order, as ``inference_stream`` does.  ``global_ids(key)`` is what a released chunk is
+    vocoded with."""
+
+    def __init__(self, spk_token_num: int, tables=None, parse: Optional[Callable] = None, *, frame_rate: int = 50,
+                 audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
+                 audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1):
+        if tables is not None and not getattr(tables, "usable", True):
+            tables = None
+        if tables is None and parse is None:
+            raise ValueError("StreamMux needs id tables or a parse callable")
+        self.ntok = int(spk_token_num)
+        self._tables, self._parse = tables, parse
+        self._sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor,
+                            audio_chunk_overlap_duration, frame_rate)
+        ChunkScheduler(*self._sched_args)   # the argument checks, once, before any request
+        self._streams: Dict[Hashable, _Stream] = {}
+
+    def open(self, key: Hashable, global_ids: Optional[Sequence[int]] = None) -> None:
+        """A new request; ``global_ids``: the speaker tokens a clone request brings (None: they will be generated)."""
+        if key in self._streams:
+            raise ValueError(f"request {key}: already open")
+        g = None if global_ids is None else [int(t) for t in global_ids]
+        self._streams[key] = _Stream(ChunkScheduler(*self._sched_args), g)
+
+    def global_ids(self, key: Hashable) -> Optional[List[int]]:
+        """The speaker tokens of an open request, or None while a control-mode request has not generated them all."""
+        st = self._streams[key]
+        if st.given:
+            return st.glob
+        return st.glob[: self.ntok] if len(st.glob) >= self.ntok else None
+
+    def _feed(self, st: _Stream, new_ids: Sequence[int]) -> List[int]:
+        """The semantic tokens ``new_ids`` add; generated global tokens go to the gate."""
+        st.ids.extend(int(t) for t in new_ids)
+        if st.tables and self._tables is not None:
+            sem, glob = [], []
+            for t in new_ids:
+                t = int(t)
+                if t in self._tables.sem:
+                    sem.append(self._tables.sem[t])
+                elif t in self._tables.glob:
+                    glob.append(self._tables.glob[t])
+                elif t not in self._tables.special:
+                    if self._parse is None:
+                        raise ValueError(f"id {t} is neither a bicodec token nor a special token, and no parse callable was given")
+                    st.tables = False
+                    break
+            if st.tables:
+                if not st.given:
+                    st.glob.extend(glob)
+                st.n_sem += len(sem)
+                return sem
+        st.tables = False
+        sem, glob = self._parse(st.ids)
+        new = [int(t) for t in sem[st.n_sem:]]
+        st.n_sem = len(sem)
+        if not st.given:
+            st.glob = [int(t) for t in glob]
+        return new
+
+    def push(self, key: Hashable, new_ids: Sequence[int], finished: bool) -> List[Tuple[Hashable, int, List[int], bool]]:
+        """The ids ``key`` has generated since its last push (``finished``: there will be no more) -> the chunks that are
+        ready now, ``[(key, chunk_index, semantic ids, last)]`` in order.  Whatever the granularity of the pushes, a request's
+        chunks are those of one ``ChunkScheduler`` fed its semantic ids in one go; ``last`` is on exactly one chunk, the final
+        one.  (A request that ends exactly on a chunk boundary with a zero overlap, in a push after the one that released that
+        chunk, has nothing left to flush: it ends with an empty chunk that carries the flag.)  A request not opened yet is
+        opened here as a control-mode one."""
+        if key not in self._streams:
+            self.open(key)
+        st = self._streams[key]
+        if st.finished:
+            raise ValueError(f"request {key}: push after its last one")
+        ready = st.sched.push(self._feed(st, new_ids))
+        if finished:
+            st.finished = True
+            ready += st.sched.flush()
+        st.held += ready
+        if self.global_ids(key) is None:
+            return []                      # control mode: the speaker tokens come first; close() reports their absence
+        out = []
+        for chunk in st.held:
+            out.append((key, st.index, chunk, False))
+            st.index += 1
+        st.held = []
+        if finished and st.n_sem > 0:
+            if not out:
+                out.append((key, st.index, [], True))
+                st.index += 1
+            else:
+                out[-1] = out[-1][:3] + (True,)
+        return out
+
+    def close(self, key: Hashable) -> None:
+        """The end of a request: forgets it, and raises the ``ValueError`` that ``SparkTTS.serve`` raises for a request that
+        generated no semantic token or has a wrong number of global tokens."""
+        st = self._streams.pop(key)
+        if len(st.glob) != self.ntok:
+            raise ValueError(f"request {key}: {len(st.glob)} global tokens, the speaker encoder needs {self.ntok}")
+        if st.n_sem == 0:
+            raise ValueError(f"request {key}: the model generated no semantic tokens")
