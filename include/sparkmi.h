@@ -294,6 +294,55 @@ typedef struct smi_allow_params {
 int smi_llm_admit_constrained(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
                               const int32_t* n_return, const smi_sample_params* params, const smi_penalty_params* pens,
                               const int32_t* return_log_probs, const smi_allow_params* allow, int32_t* slots_out, void* stream);
+/* Per-request sequence bias, banned and stop token sequences (TensorRT-LLM's per-request embedding_bias / bad_words_list /
+ * stop_words_list inputs, runtime/triton_trtllm/model_repo/tensorrt_llm/config.pbtxt; transformers'
+ * SequenceBiasLogitsProcessor, and NoBadWordsLogitsProcessor = the same with bias -inf).
+ * smi_llm_admit_biased = smi_llm_admit_constrained plus one smi_seq_params record per OUTPUT sequence ([N], like the other
+ * records; seq = NULL: exactly smi_llm_admit_constrained).
+ *   Stage 0b, after the allowed-set stage 0 and before the penalty stages 1-3 (transformers puts sequence_bias ahead of the
+ *   repetition penalty, TensorRT-LLM adds embedding_bias first; the stage is additive and does not commute with the
+ *   multiplicative repetition penalty, so the order is part of the contract).  Let ctx = the sequence's prompt followed by
+ *   the tokens it has generated so far, at the step that chooses the next token.  Bias entry i (bias_len[i] = L ids
+ *   bias_ids[i][0 .. L), value bias[i]) APPLIES to its last id when L <= len(ctx) and ctx's last L - 1 ids equal the entry's
+ *   first L - 1; an entry of length 1 always applies.  The prompt counts as context, as in transformers (the library keeps the
+ *   prompt's last SMI_MAX_SEQ_LEN - 1 ids with the record; the takes of a fork get their prompt's).  Per id, the applying
+ *   biases are summed in fp32 starting from 0: the length-1 entry first, then the longer entries in record order (transformers'
+ *   order); the logit then becomes x + total, one fp32 add.  A bias is finite or -inf; -inf bans the id at that step
+ *   (bad_words_list / bad_words_ids).  An id outside the row's allowed set stays -inf.  Log-probabilities
+ *   (smi_llm_admit_logprobs) are taken after this stage, as after the others; selection is unchanged.
+ *   Stop sequences: after a token is emitted, let g = the tokens the sequence has GENERATED, the new one included.  Stop
+ *   sequence j (stop_len[j] = L ids stop_ids[j][0 .. L)) is met when len(g) >= L, g's last L ids equal it and len(g) >= the
+ *   row's min_new_tokens.  From there the slot behaves exactly as after an eos id: the same finished flag in smi_llm_status /
+ *   smi_llm_poll / smi_llm_slots_tokens, the same treatment in the later steps of the same smi_llm_decode call; the matched
+ *   tokens stay in the history, as an eos id does.  Matching is on generated tokens only (TensorRT-LLM's semantics): a prompt
+ *   that ends in the sequence does not stop the row.
+ *   Neutral: n_bias = 0 and n_stop = 0; that row takes the route and the bits it gets without a record.
+ *   Checked before anything of the handle is touched (SMI_EINVAL, no slot, page, page reference or admission number taken):
+ *   0 <= n_bias <= SMI_MAX_BIAS_SEQS, 0 <= n_stop <= SMI_MAX_STOP_SEQS, every length in 1..SMI_MAX_SEQ_LEN, every id in
+ *   [0, vocab_size), no bias NaN or +inf, the bias entries pairwise distinct sequences and the stop sequences likewise,
+ *   reserved = 0, and a survivor: the row's allowed set (the whole vocabulary without one) minus the distinct last ids of its
+ *   -inf entries -- whatever their length: a conservative static bound -- holds at least one id, and with min_new_tokens > 0 at
+ *   least one id that is not an eos id.
+ *   Independence: a row's tokens and log-probabilities do not depend on what else is live, nor on whether its step read the
+ *   restricted lm_head -- bit for bit, with either KV dtype, paged or contiguous.
+ * Static generation (smi_llm_prefill) has none of this. */
+#define SMI_MAX_BIAS_SEQS 32
+#define SMI_MAX_STOP_SEQS 8
+#define SMI_MAX_SEQ_LEN 8
+typedef struct smi_seq_params {
+  int32_t n_bias;                                          /* 0 .. SMI_MAX_BIAS_SEQS */
+  int32_t n_stop;                                          /* 0 .. SMI_MAX_STOP_SEQS */
+  int32_t bias_len[SMI_MAX_BIAS_SEQS];                     /* 1 .. SMI_MAX_SEQ_LEN */
+  float bias[SMI_MAX_BIAS_SEQS];                           /* finite or -inf */
+  int32_t bias_ids[SMI_MAX_BIAS_SEQS * SMI_MAX_SEQ_LEN];   /* entry i: bias_ids[i * SMI_MAX_SEQ_LEN + 0 .. bias_len[i]) */
+  int32_t stop_len[SMI_MAX_STOP_SEQS];                     /* 1 .. SMI_MAX_SEQ_LEN */
+  int32_t stop_ids[SMI_MAX_STOP_SEQS * SMI_MAX_SEQ_LEN];   /* sequence j: stop_ids[j * SMI_MAX_SEQ_LEN + 0 .. stop_len[j]) */
+  int32_t reserved[2];                                     /* 0 */
+} smi_seq_params;
+int smi_llm_admit_biased(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
+                         const int32_t* n_return, const smi_sample_params* params, const smi_penalty_params* pens,
+                         const int32_t* return_log_probs, const smi_allow_params* allow, const smi_seq_params* seq,
+                         int32_t* slots_out, void* stream);
 int smi_llm_retire(smi_llm* h, int slot, void* stream);
 int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished, void* stream);
 /* Several sequences leave at once with no host round trip (the device row list is compacted in place), and the tokens of

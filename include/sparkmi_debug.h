@@ -98,6 +98,17 @@ int smi_llm_debug_penalize(smi_llm* h, const float* logits_host, int n_rows, con
  * partition).  lp_out [n_rows]: z[tok] / T - logsumexp(z / T).  Synchronises; ends the current generation. */
 int smi_llm_debug_logprob(smi_llm* h, const float* logits_host, int n_rows, const float* temperature_host, const int32_t* tokens_host,
                           float* lp_out);
+/* Tests: the bias stage (stage 0b inside k_penalize) and k_finalize's stop match alone, as a step launches them for n_rows
+ * rows (n_rows <= max_slots), on caller rows: logits_host [n_rows][vocab_size]; seq [n_rows] records (smi_llm_admit_biased's
+ * checks, without an allowed set); ctx_host [n_rows][ctx_cap] int64: row m's context ctx_len_host[m] ids long, of which the
+ * first prompt_len_host[m] (>= 1) are its prompt and the rest the tokens it has generated; min_new_host [n_rows] (null: 0)
+ * the rows' min_new_tokens for the stop match; eos ids: the last smi_llm_session_begin's.  The row maxima the kernels read
+ * are left as the lm_head leaves them (per-set maxima over a contiguous partition).  logits_out [n_rows][vocab_size]: the
+ * rows after the stage; token_out [n_rows]: the arg-max k_finalize emits; finished_out [n_rows]: the flag it leaves (an eos
+ * id, or a stop sequence met by the generated tokens with the new one).  Synchronises; ends the current generation. */
+int smi_llm_debug_seqbias(smi_llm* h, const float* logits_host, int n_rows, const smi_seq_params* seq, const int64_t* ctx_host,
+                          const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, const int32_t* min_new_host,
+                          float* logits_out, int32_t* token_out, int32_t* finished_out);
 
 #ifdef __cplusplus
 }

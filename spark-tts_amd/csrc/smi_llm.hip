@@ -78,6 +78,22 @@ struct Ctl {
   AllowRec allow[SMI_MAX_ROWS];   // per KV slot: the sequence's allowed-token ranges (smi_llm_admit_constrained; n = 0: none)
 };
 
+// One sequence's bias entries and stop sequences (smi_seq_params as admitted) with the tail of its prompt, 1616 bytes; all zero:
+// none.  The records live in an array of their own beside Ctl (smi_llm::seq, one per KV slot): a kernel gets the array only in a
+// step whose graph key says that some live row has an entry, and an admission uploads only the records that change, so a
+// session without records neither reads nor copies them.
+struct SeqRec {
+  int32_t n_bias, n_stop;
+  int32_t plen;                         // prompt length (the prompt counts as context for the bias entries)
+  int32_t n_ptail;                      // min(plen, SMI_MAX_SEQ_LEN - 1) prompt ids kept in ptail
+  int32_t ptail[SMI_MAX_SEQ_LEN];       // ptail[SMI_MAX_SEQ_LEN - 1 - q] = the prompt's q-th id from its end, q = 1 .. n_ptail
+  int32_t blen[SMI_MAX_BIAS_SEQS];
+  float bias[SMI_MAX_BIAS_SEQS];
+  int32_t bids[SMI_MAX_BIAS_SEQS][SMI_MAX_SEQ_LEN];
+  int32_t slen[SMI_MAX_STOP_SEQS];
+  int32_t sids[SMI_MAX_STOP_SEQS][SMI_MAX_SEQ_LEN];
+};
+
 // stage 0: the id lies in one of the record's ranges
 __device__ __forceinline__ bool allow_has(const AllowRec* a, int id) {
   const int n = a->n;
@@ -3246,7 +3262,56 @@ struct PenP {
   int* pidx;
   int V, nblk, per;       // per: ids per set, a multiple of 4 (per * nblk >= V)
   int hs;                 // the handle samples
+  const SeqRec* seq;      // non-null (some live row has a bias entry): per-slot bias entries, stage 0b
+  const int64_t* ghist;   // [max_steps][kMaxRows] generated tokens per slot (the context of stage 0b)
+  int max_steps;
 };
+
+// Stage 0b (smi_llm_admit_biased) for one wave: lane e < n_bias takes entry e, decides whether it applies at this step (its first
+// L - 1 ids against the context tail: the generated tokens, then the stored prompt tail) and adds up, for its last id, the
+// applying entries' biases in the contract's order (the length-1 entry, then the longer ones in record order).  The first
+// applying entry of every distinct id inside [i0, i1) then leaves (id, total) in the wave's LDS list; returns the list's length.
+// *any: some entry of the row applies (the same in every wave of the row).
+__device__ __forceinline__ int seq_bias_list(const SeqRec* sq, const RowDesc& rd, const int64_t* ghist, int max_steps, int lane,
+                                             int i0, int i1, int* l_id, float* l_tot, bool* any) {
+  const int nb = sq->n_bias, gen = rd.flags;
+  bool app = false;
+  int last = -1, len = 0;
+  float bias = 0.f;
+  if (lane < nb) {
+    len = sq->blen[lane]; bias = sq->bias[lane]; last = sq->bids[lane][len - 1];
+    app = len <= sq->plen + gen;
+    for (int k = 1; k < len && app; ++k) {   // the context's k-th id from its end
+      int c = -1;
+      if (k <= gen) { if (gen - k < max_steps) c = (int)ghist[(size_t)(gen - k) * kMaxRows + rd.slot]; }
+      else if (k - gen <= sq->n_ptail) c = sq->ptail[SMI_MAX_SEQ_LEN - 1 - (k - gen)];
+      app = c == sq->bids[lane][len - 1 - k];
+    }
+  }
+  const unsigned long long am = __ballot(app);
+  *any = am != 0;
+  if (!am) return 0;
+  float tot = 0.f;
+  bool first = true;
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass)
+    for (int f = 0; f < nb; ++f) {
+      const int lf = __shfl(last, f, 64), nf = __shfl(len, f, 64);
+      const float bf = __shfl(bias, f, 64);
+      if (((am >> f) & 1ull) && lf == last) {
+        if ((nf == 1) == (pass == 0)) tot += bf;
+        if (f < lane) first = false;
+      }
+    }
+  const bool own = app && first && last >= i0 && last < i1;
+  const unsigned long long om = __ballot(own);
+  if (own) {
+    const int at = __popcll(om & ((1ull << lane) - 1ull));
+    l_id[at] = last; l_tot[at] = tot;
+  }
+  __builtin_amdgcn_wave_barrier();
+  return __popcll(om);
+}
 
 // stages 1..3 on one logit (fp32, each operation rounded on its own: the build compiles with -ffp-contract=off)
 __device__ __forceinline__ float pen_logit(float x, uint32_t h, const PenRec& r, bool mask, int id, const int* eos) {
@@ -3272,15 +3337,32 @@ __device__ __forceinline__ void pen_best(float v, int i, float& bv, int& bi) {
 // restricted lm_head leaves unwritten outside the union of the rows' tiles included), and the row's maxima are rebuilt over
 // this kernel's partition -- so the sampler, k_logprob and k_finalize see the same dense row and the same maxima whichever
 // lm_head form ran.  A constrained, unpenalised row takes stage 0 alone.
+// Stage 0b (smi_llm_admit_biased) runs here as well, between stage 0 and the penalties: a row with bias entries takes this
+// route, each wave works out the (id, total) pairs of its own set (seq_bias_list) and adds them as it passes the ids -- no extra
+// pass over the row, nothing written that the row's consumers do not read, and the set's maximum is exact because it is taken
+// after the add.  A row that has bias entries but none that applies at this step (and no other record) leaves like a plain row.
 __global__ __launch_bounds__(256) void k_penalize(PenP p) {
+  __shared__ int s_bid[kPenWaves][SMI_MAX_BIAS_SEQS];
+  __shared__ float s_btot[kPenWaves][SMI_MAX_BIAS_SEQS];
   const int m = blockIdx.y;
   const RowDesc rd = p.rows[m];
   const PenRec r = p.ctl->pen[rd.slot];
   const AllowRec* al = &p.ctl->allow[rd.slot];
   const bool con = al->n > 0;
-  if (!r.on && !con) return;   // neither penalised nor constrained: the lm_head's maxima stand
+  const SeqRec* sq = p.seq ? &p.seq[rd.slot] : nullptr;
+  const bool bia = sq && sq->n_bias > 0;
+  if (!r.on && !con && !bia) return;   // neither penalised, constrained nor biased: the lm_head's maxima stand
   const int lane = threadIdx.x & 63, set = blockIdx.x * kPenWaves + (threadIdx.x >> 6);
   if (set >= p.nblk) return;
+  int nbl = 0;   // stage 0b: ids of this wave's set whose logit takes a bias total at this step
+  if (bia) {
+    bool any;
+    nbl = seq_bias_list(sq, rd, p.ghist, p.max_steps, lane, set * p.per, min(set * p.per + p.per, p.V), s_bid[threadIdx.x >> 6],
+                        s_btot[threadIdx.x >> 6], &any);
+    if (!any && !r.on && !con) return;   // no entry applies at this step: the row is the lm_head's, its maxima stand
+  }
+  const int* l_id = s_bid[threadIdx.x >> 6];
+  const float* l_tot = s_btot[threadIdx.x >> 6];
   // the sampler and k_logprob read the logits; k_finalize of a row that does neither only the maxima
   const bool wb = rec_samples(p.ctl->samp[rd.slot], p.hs) || p.ctl->lp[rd.slot];
   const bool mask = rd.flags < r.min_new;
@@ -3301,6 +3383,14 @@ __global__ __launch_bounds__(256) void k_penalize(PenP p) {
         if (!allow_has(al, i + 2)) x.z = -INFINITY;
         if (!allow_has(al, i + 3)) x.w = -INFINITY;
       }
+      for (int e = 0; e < nbl; ++e) {   // x + total: one fp32 add (an id outside the allowed set stays -inf)
+        const int d = l_id[e] - i;
+        const float t = l_tot[e];
+        if (d == 0) x.x += t;
+        if (d == 1) x.y += t;
+        if (d == 2) x.z += t;
+        if (d == 3) x.w += t;
+      }
       if (r.on) {
         const uint2 hh = *(const uint2*)(hs + i);
         x.x = pen_logit(x.x, hh.x & 0xffffu, r, mask, i, eos);
@@ -3315,6 +3405,8 @@ __global__ __launch_bounds__(256) void k_penalize(PenP p) {
     for (int i = i0 + lane; i < i1; i += 64) {
       float x = lg[i];
       if (con && !allow_has(al, i)) x = -INFINITY;
+      for (int e = 0; e < nbl; ++e)
+        if (l_id[e] == i) x += l_tot[e];
       if (r.on) x = pen_logit(x, hs[i], r, mask, i, eos);
       if (wb) lg[i] = x;
       pen_best(x, i, bv, bi);
@@ -3423,7 +3515,24 @@ struct FinP {
   unsigned char* xs;     // first layer's operand
   float* sspart; int npart;
   int exact;             // exact-weights arena: Wlm is fp32 [vocab][K]
+  const SeqRec* seq;     // non-null (some live row has a stop sequence): per-slot stop sequences
 };
+
+// The sequence in slot sl has just emitted `tok` as its token number `step` (0-based): some stop sequence of its record equals
+// the last ids it has generated, and it has emitted at least min_new tokens (smi_llm_admit_biased).  The earlier tokens come
+// from the slot's history, which earlier launches wrote.
+__device__ __forceinline__ bool seq_stop(const SeqRec& q, const int64_t* hist, int sl, int step, int tok, int min_new, int max_steps) {
+  bool stop = false;
+  if (step + 1 < min_new) return false;
+  for (int s = 0; s < q.n_stop; ++s) {
+    const int L = q.slen[s];
+    if (step + 1 < L || step >= max_steps) continue;
+    bool eq = q.sids[s][L - 1] == tok;
+    for (int k = 1; k < L && eq; ++k) eq = hist[(size_t)(step - k) * kMaxRows + sl] == (int64_t)q.sids[s][L - 1 - k];
+    stop |= eq;
+  }
+  return stop;
+}
 
 // One block per row: arg-max over the lm_head blocks' partials (or the sampled token), per-row
 // bookkeeping, and the next step's residual row / first-norm operand.  The per-row step index lives
@@ -3499,6 +3608,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinP p) {
       bool stop = false;   // HF generate(): any id of generation_config.eos_token_id ends the sequence
 #pragma unroll
       for (int e = 0; e < SMI_MAX_EOS; ++e) stop |= e < p.ctl->n_eos && (long long)bi == p.ctl->eos[e];
+      if (p.seq && p.seq[sl].n_stop > 0) stop |= seq_stop(p.seq[sl], p.hist, sl, step, bi, p.ctl->pen[sl].min_new, p.max_steps);
       if (stop) p.finished[sl] = 1;
     }
     rd.token = bi;
@@ -3637,6 +3747,11 @@ struct smi_llm {
   int slot_lp[kMaxRows];        // host: the sequence in this slot (live or being admitted) returns log-probabilities (Ctl::lp)
   int slot_allow[kMaxRows];     // host: the sequence in this slot (live or being admitted) is constrained (Ctl::allow, n > 0)
   int lm_restrict;              // host: every row of the steps being issued is constrained (the restricted lm_head may run)
+  int slot_bias[kMaxRows];      // host: the sequence in this slot (live or being admitted) has bias entries (SeqRec::n_bias > 0)
+  int slot_stop[kMaxRows];      // host: ... has stop sequences (SeqRec::n_stop > 0)
+  int seq_dirty[kMaxRows];      // host: the slot's device record is not all zero (an admission without a record clears it)
+  SeqRec* seq;                  // device: per-slot bias / stop records [kMaxRows] (smi_llm_admit_biased)
+  std::vector<SeqRec> hseq;     // host: what the device records hold
   int* tlist;                   // device: {count, vocabulary tiles ascending} -- the union of the constrained slots' tiles
   std::vector<int32_t> host_tlist;
   float* lp;                    // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
@@ -3661,7 +3776,7 @@ struct smi_llm {
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
   int gu1_lo;           // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (SPARKMI_GU1_LO; default 4)
   int gu1_rows;         // rows up to which gate_up runs its one-batch, three-tile shape (SPARKMI_GU1_ROWS; default 32)
-  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen, graph_lp, graph_allow;   // the step graph in use (owned by graph_cache)
+  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen, graph_lp, graph_allow, graph_seq;   // the step graph in use (owned by graph_cache)
   // every exec remembers the stream it last ran on: a caller may alternate streams, and an exec is destroyed only after THAT
   // stream has drained (graphs_flush)
   std::map<hipGraphExec_t, hipStream_t> graph_last;
@@ -3674,7 +3789,9 @@ struct smi_llm {
   // a step in which no row samples is the greedy step exactly.  Likewise the penalty bit only adds the logits rows and
   // k_penalize: a step in which no row is penalised is the step without penalties exactly; and the log-probability bit only
   // adds the logits rows and k_logprob.  The constraint bits: some row constrained (the full lm_head writes the logits rows and
-  // k_penalize applies stage 0), and every row constrained (the restricted lm_head, whose tile list is device data).
+  // k_penalize applies stage 0), and every row constrained (the restricted lm_head, whose tile list is device data).  The
+  // sequence bits: some row has a bias entry (the logits rows, and k_penalize gets the records: stage 0b), some row has a stop
+  // sequence (k_finalize gets the records); with both clear neither kernel is handed the record array.
   std::map<uint64_t, hipGraphExec_t> graph_cache;
   hipEvent_t ev0, ev1;
   // host staging
@@ -3779,24 +3896,37 @@ bool allow_any(const smi_llm* L) {
     if (L->slot_allow[sl]) return true;
   return false;
 }
+// Some live / just-admitted row has bias entries / stop sequences (smi_llm_admit_biased).
+bool bias_any(const smi_llm* L) {
+  for (int sl = 0; sl < kMaxRows; ++sl)
+    if (L->slot_bias[sl]) return true;
+  return false;
+}
+bool stop_any(const smi_llm* L) {
+  for (int sl = 0; sl < kMaxRows; ++sl)
+    if (L->slot_stop[sl]) return true;
+  return false;
+}
+// the sequence bits of a step: 1 = some row has a bias entry, 2 = some row has a stop sequence
+int seq_bits(const smi_llm* L) { return (bias_any(L) ? 1 : 0) | (stop_any(L) ? 2 : 0); }
 // The step's lm_head reads only the tiles of the union (k_lm / k_lm32 with RT = 1): every row of the step is constrained, and the
 // persistent kernels run (K <= 32 tiles, bf16 weights; the generic EPI_LM GEMM and the exact-weights mode take the full path).
 bool lm_restricted(const smi_llm* L) {
   return L->lm_restrict && L->KTh <= 32 && !L->exact && allow_any(L);
 }
-// Some row of the step reads the logits rows: a sampling, penalised or log-probability row, or a constrained row whose stage 0
+// Some row of the step reads the logits rows: a sampling, penalised, biased or log-probability row, or a constrained row whose stage 0
 // runs in k_penalize (every constrained row of a full-lm_head step; on the restricted path k_penalize then also runs, so the
 // rows it hands on are dense).
 bool logits_needed(const smi_llm* L) {
-  return samp_any(L) || pen_any(L) || lp_any(L) || (allow_any(L) && !lm_restricted(L));
+  return samp_any(L) || pen_any(L) || lp_any(L) || bias_any(L) || (allow_any(L) && !lm_restricted(L));
 }
 // the constraint bits of a step: 1 = some row constrained, 2 = every row (restricted lm_head)
 int allow_bits(const smi_llm* L) { return allow_any(L) ? (lm_restricted(L) ? 3 : 1) : 0; }
 // the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | sample << 25 | penalty << 26 | log-probs << 27 |
-// constraints << 28 (2 bits) | steps per replay << 32
+// constraints << 28 (2 bits) | sequence bits << 30 (2 bits) | steps per replay << 32
 uint64_t graph_key(const smi_llm* L, int samp, int pen, int lp, int K) {
   return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)samp << 25) |
-         ((uint64_t)pen << 26) | ((uint64_t)lp << 27) | ((uint64_t)allow_bits(L) << 28) | ((uint64_t)K << 32);
+         ((uint64_t)pen << 26) | ((uint64_t)lp << 27) | ((uint64_t)allow_bits(L) << 28) | ((uint64_t)seq_bits(L) << 30) | ((uint64_t)K << 32);
 }
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
@@ -4043,7 +4173,7 @@ int eng_create(smi_llm* L) {
 // only: lm_head, the sampler and k_finalize stay launches, so a sampling record applies to the engine's row as to any other)
 bool eng_usable(const smi_llm* L, const RowDesc* rows, int M) {
   return L->eng.enabled && L->eng_on && M == 1 && rows == L->rows && L->identity_slots && !L->paged && L->attn_seg <= 1 && !L->stamps_on &&
-         !lp_any(L);   // (a step with a log-probability row keeps to the launch path)
+         !lp_any(L) && !seq_bits(L);   // (a step with a log-probability, biased or stop-sequence row keeps to the launch path)
 }
 
 int eng_launch(smi_llm* L, hipStream_t st) {
@@ -4403,10 +4533,11 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       f.tok = nullptr;
       f.hs = L->do_sample;
       f.phist = nullptr;
-      if (pen_any(L) || (allow_any(L) && logits_needed(L))) {   // rows neither penalised nor constrained leave k_penalize at once
+      if (pen_any(L) || bias_any(L) || (allow_any(L) && logits_needed(L))) {   // rows neither penalised, biased nor constrained leave k_penalize at once
         PenP pp;
         pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
         pp.V = c.vocab_size; pp.nblk = lm_blocks_for(L, M); pp.per = pen_set_ids(pp.V, pp.nblk); pp.hs = L->do_sample;
+        pp.seq = bias_any(L) ? L->seq : nullptr; pp.ghist = L->hist; pp.max_steps = L->max_steps;
         hipLaunchKernelGGL(k_penalize, dim3((pp.nblk + kPenWaves - 1) / kPenWaves, M), dim3(256), 0, st, pp);
         SMI_LAUNCH_CHECK();
         f.phist = L->phist;
@@ -4435,6 +4566,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
       f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
       f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
+      f.seq = stop_any(L) ? L->seq : nullptr;
       hipLaunchKernelGGL(k_finalize, dim3(M), dim3(256), 0, st, f);
       SMI_LAUNCH_CHECK();
       return SMI_OK;
@@ -4764,9 +4896,11 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
-  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; L->graph_lp = 0; L->graph_allow = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
+  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; L->graph_lp = 0; L->graph_allow = 0; L->graph_seq = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
   memset(L->slot_lp, 0, sizeof(L->slot_lp)); L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
   memset(L->slot_allow, 0, sizeof(L->slot_allow)); L->lm_restrict = 0; L->tlist = nullptr;
+  memset(L->slot_bias, 0, sizeof(L->slot_bias)); memset(L->slot_stop, 0, sizeof(L->slot_stop)); memset(L->seq_dirty, 0, sizeof(L->seq_dirty));
+  L->seq = nullptr; L->hseq.assign(kMaxRows, SeqRec{});
   L->poll_dev = nullptr; L->poll_host = nullptr;
   L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
@@ -4830,6 +4964,9 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   // the restricted lm_head's tile list (smi_llm_admit_constrained): {count, tiles}; zeros = no tile, entry 0 a valid tile index
   SMI_ALLOC(L->tlist, ((size_t)L->NTlm + 1) * 4);
   SMI_HIP(hipMemset(L->tlist, 0, ((size_t)L->NTlm + 1) * 4));
+  // per-slot bias / stop records (smi_llm_admit_biased): all zero = none
+  SMI_ALLOC(L->seq, (size_t)kMaxRows * sizeof(SeqRec));
+  SMI_HIP(hipMemset(L->seq, 0, (size_t)kMaxRows * sizeof(SeqRec)));
   // smi_llm_poll's staging: {count, finished, ids[cap]} per listed slot, cap <= max_steps, and its pinned host copy
   SMI_ALLOC(L->poll_dev, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8);
 #undef SMI_ALLOC
@@ -4907,7 +5044,7 @@ int smi_llm_destroy(smi_llm* L) {
   eng_destroy(L);
   void* ptrs[] = {L->h, L->qbuf, L->xs_h, L->xs_attn, L->xs_act, L->sspart, L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
                   L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab, L->apart,
-                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist, L->poll_dev};
+                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist, L->poll_dev, L->seq};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (L->poll_host) (void)hipHostFree(L->poll_host);
@@ -5097,6 +5234,8 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   memset(L->slot_lp, 0, sizeof(L->slot_lp));
   memset(L->hctl.allow, 0, sizeof(L->hctl.allow)); // and is not constrained
   memset(L->slot_allow, 0, sizeof(L->slot_allow));
+  memset(L->slot_bias, 0, sizeof(L->slot_bias));   // and has no bias entries or stop sequences
+  memset(L->slot_stop, 0, sizeof(L->slot_stop));
   L->lm_restrict = 0;
   L->admit_seq = B;
   { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
@@ -5134,6 +5273,8 @@ int smi_llm_session_begin(smi_llm* L, const int64_t* eos_ids, int n_eos, void* s
   memset(L->slot_lp, 0, sizeof(L->slot_lp));
   memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
   memset(L->slot_allow, 0, sizeof(L->slot_allow));
+  memset(L->slot_bias, 0, sizeof(L->slot_bias));
+  memset(L->slot_stop, 0, sizeof(L->slot_stop));
   L->lm_restrict = 0;
   L->admit_seq = 0;
   if (L->paged)
@@ -5351,6 +5492,89 @@ int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, in
 int smi_llm_admit_constrained(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
                               const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
                               const smi_allow_params* allow, int32_t* slots_out, void* stream) {
+  return smi_llm_admit_biased(L, ids, lens, n, P_max, n_ret, params, pens, want_lp, allow, nullptr, slots_out, stream);
+}
+
+// Checks of one bias / stop record (smi_llm_admit_biased, smi_llm_debug_seqbias; before anything of the handle is touched).
+// al / pen: the take's allow and penalty records or null (al has passed validate_allow).
+static int validate_seq(const smi_llm* L, const smi_seq_params& q, const smi_allow_params* al, const smi_penalty_params* pen, int j) {
+  const int V = L->cfg.vocab_size;
+  SMI_REQUIRE(q.n_bias >= 0 && q.n_bias <= SMI_MAX_BIAS_SEQS, "smi_llm_admit_biased: seq[%d].n_bias=%d outside 0..%d", j, q.n_bias, SMI_MAX_BIAS_SEQS);
+  SMI_REQUIRE(q.n_stop >= 0 && q.n_stop <= SMI_MAX_STOP_SEQS, "smi_llm_admit_biased: seq[%d].n_stop=%d outside 0..%d", j, q.n_stop, SMI_MAX_STOP_SEQS);
+  SMI_REQUIRE(q.reserved[0] == 0 && q.reserved[1] == 0, "smi_llm_admit_biased: seq[%d].reserved must be 0", j);
+  auto same = [](const int32_t* a, int la, const int32_t* b, int lb) { return la == lb && memcmp(a, b, (size_t)la * 4) == 0; };
+  for (int i = 0; i < q.n_bias; ++i) {
+    const int len = q.bias_len[i];
+    const int32_t* e = q.bias_ids + (size_t)i * SMI_MAX_SEQ_LEN;
+    SMI_REQUIRE(len >= 1 && len <= SMI_MAX_SEQ_LEN, "smi_llm_admit_biased: seq[%d].bias_len[%d]=%d outside 1..%d", j, i, len, SMI_MAX_SEQ_LEN);
+    for (int t = 0; t < len; ++t)
+      SMI_REQUIRE(e[t] >= 0 && e[t] < V, "smi_llm_admit_biased: seq[%d] bias entry %d holds id %d outside [0, %d)", j, i, e[t], V);
+    SMI_REQUIRE(!std::isnan(q.bias[i]) && !(std::isinf(q.bias[i]) && q.bias[i] > 0.f),
+                "smi_llm_admit_biased: seq[%d].bias[%d] must be finite or -inf", j, i);
+    for (int f = 0; f < i; ++f)
+      SMI_REQUIRE(!same(e, len, q.bias_ids + (size_t)f * SMI_MAX_SEQ_LEN, q.bias_len[f]),
+                  "smi_llm_admit_biased: seq[%d] bias entries %d and %d are the same sequence", j, f, i);
+  }
+  for (int i = 0; i < q.n_stop; ++i) {
+    const int len = q.stop_len[i];
+    const int32_t* e = q.stop_ids + (size_t)i * SMI_MAX_SEQ_LEN;
+    SMI_REQUIRE(len >= 1 && len <= SMI_MAX_SEQ_LEN, "smi_llm_admit_biased: seq[%d].stop_len[%d]=%d outside 1..%d", j, i, len, SMI_MAX_SEQ_LEN);
+    for (int t = 0; t < len; ++t)
+      SMI_REQUIRE(e[t] >= 0 && e[t] < V, "smi_llm_admit_biased: seq[%d] stop sequence %d holds id %d outside [0, %d)", j, i, e[t], V);
+    for (int f = 0; f < i; ++f)
+      SMI_REQUIRE(!same(e, len, q.stop_ids + (size_t)f * SMI_MAX_SEQ_LEN, q.stop_len[f]),
+                  "smi_llm_admit_biased: seq[%d] stop sequences %d and %d are the same", j, f, i);
+  }
+  // a survivor: the allowed set (or the vocabulary) minus the distinct last ids of the -inf entries -- and minus the eos ids while
+  // min_new_tokens bans them -- is not empty
+  const bool con = al && al->n_ranges > 0;
+  auto allowed = [&](long long id) {
+    if (!con) return true;
+    for (int i = 0; i < al->n_ranges; ++i)
+      if (id >= al->lo[i] && id < al->hi[i]) return true;
+    return false;
+  };
+  long covered = V;
+  if (con) { covered = 0; for (int i = 0; i < al->n_ranges; ++i) covered += al->hi[i] - al->lo[i]; }
+  std::vector<long long> gone;   // distinct ids of the set that cannot be chosen
+  auto drop = [&](long long id) {
+    if (id < 0 || id >= V || !allowed(id)) return;
+    for (long long g : gone) if (g == id) return;
+    gone.push_back(id);
+  };
+  for (int i = 0; i < q.n_bias; ++i)
+    if (std::isinf(q.bias[i])) drop(q.bias_ids[(size_t)i * SMI_MAX_SEQ_LEN + q.bias_len[i] - 1]);
+  SMI_REQUIRE(covered > (long)gone.size(), "smi_llm_admit_biased: seq[%d] bans every id the row could emit", j);
+  if (pen && pen->min_new_tokens > 0) {
+    for (int e = 0; e < L->hctl.n_eos; ++e) drop(L->hctl.eos[e]);
+    SMI_REQUIRE(covered > (long)gone.size(), "smi_llm_admit_biased: seq[%d] leaves only eos ids but min_new_tokens=%d bans them", j, pen->min_new_tokens);
+  }
+  return SMI_OK;
+}
+
+// The device record of a bias / stop record admitted with the prompt ids[0 .. len); all zero for none and for a neutral one.
+static SeqRec seq_record(const smi_seq_params* q, const int64_t* ids, int len) {
+  SeqRec r;
+  memset(&r, 0, sizeof(r));
+  if (!q || (q->n_bias == 0 && q->n_stop == 0)) return r;
+  r.n_bias = q->n_bias; r.n_stop = q->n_stop; r.plen = len;
+  r.n_ptail = len < SMI_MAX_SEQ_LEN - 1 ? len : SMI_MAX_SEQ_LEN - 1;
+  for (int k = 1; k <= r.n_ptail; ++k) r.ptail[SMI_MAX_SEQ_LEN - 1 - k] = (int32_t)ids[len - k];
+  for (int i = 0; i < q->n_bias; ++i) {
+    r.blen[i] = q->bias_len[i]; r.bias[i] = q->bias[i];
+    for (int t = 0; t < q->bias_len[i]; ++t) r.bids[i][t] = q->bias_ids[(size_t)i * SMI_MAX_SEQ_LEN + t];
+  }
+  for (int i = 0; i < q->n_stop; ++i) {
+    r.slen[i] = q->stop_len[i];
+    for (int t = 0; t < q->stop_len[i]; ++t) r.sids[i][t] = q->stop_ids[(size_t)i * SMI_MAX_SEQ_LEN + t];
+  }
+  return r;
+}
+
+// smi_llm_admit_constrained plus one bias / stop record per take (seq = null: exactly smi_llm_admit_constrained).
+int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
+                         const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
+                         const smi_allow_params* allow, const smi_seq_params* seq, int32_t* slots_out, void* stream) {
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
   const int slot_cap = L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows;
@@ -5373,6 +5597,11 @@ int smi_llm_admit_constrained(smi_llm* L, const int64_t* ids, const int32_t* len
       SMI_REQUIRE(want_lp[j] == 0 || want_lp[j] == 1, "smi_llm_admit_logprobs: return_log_probs[%d]=%d must be 0 or 1", j, want_lp[j]);
   if (allow)
     for (int j = 0; j < N; ++j) { const int rca = validate_allow(L, allow[j], pens ? &pens[j] : nullptr, j); if (rca) return rca; }
+  if (seq)
+    for (int j = 0; j < N; ++j) {
+      const int rcq = validate_seq(L, seq[j], allow ? &allow[j] : nullptr, pens ? &pens[j] : nullptr, j);
+      if (rcq) return rcq;
+    }
   hipStream_t st = (hipStream_t)stream;
   int rc;
   std::vector<RowDesc> live;
@@ -5447,6 +5676,7 @@ int smi_llm_admit_constrained(smi_llm* L, const int64_t* ids, const int32_t* len
       L->hctl.pen[slots[j]] = old_pen[j]; L->slot_pen[slots[j]] = 0;
       L->hctl.lp[slots[j]] = old_lp[j]; L->slot_lp[slots[j]] = 0;
       L->hctl.allow[slots[j]] = old_allow[j]; L->slot_allow[slots[j]] = 0;
+      L->slot_bias[slots[j]] = 0; L->slot_stop[slots[j]] = 0;   // (seq_dirty stays: the next admission rewrites the device record)
     }
     L->admit_seq = seq0;
     if (L->paged)
@@ -5458,6 +5688,24 @@ int smi_llm_admit_constrained(smi_llm* L, const int64_t* ids, const int32_t* len
     return SMI_EHIP;
   }
   if ((rc = allow_tiles_upload(L, st))) { undo(); return rc; }   // the union now holds the new takes' tiles
+  // the bias / stop records of the new takes (a fork's followers get their prompt's tail); a slot whose device record is all
+  // zero and stays so is not touched
+  for (int j = 0; j < N; ++j) {
+    const int sl = slots[j];
+    const SeqRec rec = seq_record(seq ? &seq[j] : nullptr, ids + (size_t)src[j] * P_max, lens_j[j]);
+    const int on = rec.n_bias > 0 || rec.n_stop > 0;
+    L->slot_bias[sl] = rec.n_bias > 0; L->slot_stop[sl] = rec.n_stop > 0;
+    if (!on && !L->seq_dirty[sl]) continue;
+    L->hseq[(size_t)sl] = rec;
+    L->seq_dirty[sl] = on;
+    // (pageable source: staged before the call returns; hseq[sl] is rewritten only by a later admission into the slot)
+    if (hipMemcpyAsync(L->seq + sl, &L->hseq[(size_t)sl], sizeof(SeqRec), hipMemcpyHostToDevice, st) != hipSuccess) {
+      L->seq_dirty[sl] = 1;
+      undo();
+      smi_set_error("smi_llm_admit_biased: uploading the sequence records failed");
+      return SMI_EHIP;
+    }
+  }
   // the fork copy's work list: each follower gets the leader's positions it does not share -- 0 .. L-2 (contiguous), S P .. L-2
   // (paged); position L-1 and on are written by the follower's own steps
   std::vector<RowDesc> fork;
@@ -5533,6 +5781,7 @@ int smi_llm_retire(smi_llm* L, int slot, void* stream) {
   L->slot_pen[slot] = 0;
   L->slot_lp[slot] = 0;   // (Ctl::lp stays: the slot's log-probabilities stay readable until it is reused)
   L->slot_allow[slot] = 0;
+  L->slot_bias[slot] = 0; L->slot_stop[slot] = 0;
   if (L->paged) pages_release(L, slot);   // its pages go back to the pool (stale table entries are never read: no live row names the slot)
   if ((rc = allow_tiles_upload(L, st))) return rc;
   return session_set_rows(L, live, st);
@@ -5562,6 +5811,7 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
     L->slot_pen[slots[i]] = 0;
     L->slot_lp[slots[i]] = 0;
     L->slot_allow[slots[i]] = 0;
+    L->slot_bias[slots[i]] = 0; L->slot_stop[slots[i]] = 0;
     if (L->paged) pages_release(L, slots[i]);
   }
   L->live_order = keep;
@@ -5709,13 +5959,13 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     L->attn_seg = segs_for(bound);
     if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
   }
-  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0, lpb = lp_any(L) ? 1 : 0, alw = allow_bits(L);
+  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0, lpb = lp_any(L) ? 1 : 0, alw = allow_bits(L), sqb = seq_bits(L);
   if (L->cfg.use_graph && n_steps > 0 && (!L->graph || L->graph_B != L->B || L->graph_seg != L->attn_seg || L->graph_ident != L->identity_slots ||
-                                          L->graph_samp != samp || L->graph_pen != pen || L->graph_lp != lpb || L->graph_allow != alw)) {
+                                          L->graph_samp != samp || L->graph_pen != pen || L->graph_lp != lpb || L->graph_allow != alw || L->graph_seq != sqb)) {
     const uint64_t key = graph_key(L, samp, pen, lpb, 0);
     auto hit = L->graph_cache.find(key);
     L->graph = hit != L->graph_cache.end() ? hit->second : nullptr;
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw; L->graph_seq = sqb;
   }
   if (L->cfg.use_graph && n_steps > 0 && !L->graph) {
     const uint64_t key = graph_key(L, samp, pen, lpb, 0);
@@ -5734,7 +5984,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     }
     (void)hipStreamDestroy(cs);
     (void)hipGetLastError();
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw;
+    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw; L->graph_seq = sqb;
     if (!L->graph) { smi_set_error("hipGraph capture of the decode step failed"); return SMI_EHIP; }
     L->graph_cache[key] = L->graph;
   }
@@ -6285,6 +6535,7 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
   PenP pp;
   pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
   pp.V = (int)V; pp.nblk = nblk; pp.per = pen_set_ids((int)V, nblk); pp.hs = 0;
+  pp.seq = nullptr; pp.ghist = L->hist; pp.max_steps = L->max_steps;
   hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());
@@ -6363,12 +6614,102 @@ int smi_llm_debug_logprob(smi_llm* L, const float* logits_host, int n_rows, cons
   f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
   f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
   f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
+  f.seq = nullptr;
   hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());
   SMI_HIP(hipMemcpy(lp_out, L->lp, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
   memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
+  L->started = 0;   // rows, controls, the lm_head partials and the histories no longer belong to a generation
+  return SMI_OK;
+}
+
+// Tests: the bias stage and k_finalize's stop match alone on caller rows (see sparkmi_debug.h).
+int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, const smi_seq_params* seq, const int64_t* ctx_host,
+                          const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, const int32_t* min_new_host,
+                          float* logits_out, int32_t* token_out, int32_t* finished_out) {
+  SMI_REQUIRE(L && logits_host && seq && ctx_host && ctx_len_host && prompt_len_host && logits_out && token_out && finished_out,
+              "smi_llm_debug_seqbias: null argument");
+  SMI_REQUIRE(n_rows >= 1 && n_rows <= L->cfg.max_slots && n_rows <= kMaxRows, "smi_llm_debug_seqbias: n_rows=%d outside 1..max_slots", n_rows);
+  const int V = L->cfg.vocab_size;
+  for (int m = 0; m < n_rows; ++m) {
+    const int rcq = validate_seq(L, seq[m], nullptr, nullptr, m);
+    if (rcq) return rcq;
+    SMI_REQUIRE(prompt_len_host[m] >= 1 && prompt_len_host[m] <= ctx_len_host[m] && ctx_len_host[m] <= ctx_cap,
+                "smi_llm_debug_seqbias: row %d: 1 <= prompt_len <= ctx_len <= ctx_cap does not hold", m);
+    SMI_REQUIRE(ctx_len_host[m] - prompt_len_host[m] < L->max_steps, "smi_llm_debug_seqbias: row %d: more generated tokens than the history holds", m);
+    SMI_REQUIRE(!min_new_host || (min_new_host[m] >= 0 && min_new_host[m] <= L->cfg.max_positions), "smi_llm_debug_seqbias: min_new[%d] out of range", m);
+    for (int t = 0; t < ctx_len_host[m]; ++t)
+      SMI_REQUIRE(ctx_host[(size_t)m * ctx_cap + t] >= 0 && ctx_host[(size_t)m * ctx_cap + t] < V, "smi_llm_debug_seqbias: ctx[%d][%d] outside the vocabulary", m, t);
+  }
+  const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
+  // the row maxima as the lm_head leaves them: (maximum, lowest id) of each contiguous set
+  std::vector<float> pv((size_t)n_rows * nblk, -INFINITY);
+  std::vector<int32_t> pi((size_t)n_rows * nblk, 0x7fffffff);
+  for (int m = 0; m < n_rows; ++m)
+    for (int j = 0; j < nblk; ++j)
+      for (int i = j * per; i < V && i < (j + 1) * per; ++i) {
+        const float x = logits_host[(size_t)m * V + i];
+        if (x > pv[(size_t)m * nblk + j]) { pv[(size_t)m * nblk + j] = x; pi[(size_t)m * nblk + j] = i; }
+      }
+  SMI_HIP(hipDeviceSynchronize());
+  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
+  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
+  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
+  int max_gen = 0;
+  for (int m = 0; m < n_rows; ++m) {
+    const int gen = ctx_len_host[m] - prompt_len_host[m];
+    max_gen = gen > max_gen ? gen : max_gen;
+    rows[m] = RowDesc{m, 0, 0, gen};
+    L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: k_penalize writes its processed logits back; k_finalize gets no
+    L->hctl.samp[m].top_k = 1; L->hctl.samp[m].inv_temp = 1.f; L->hctl.samp[m].top_p = 1.f;   // sampler tokens and takes the arg-max)
+    if (min_new_host && min_new_host[m] > 0) {   // only min_new of a neutral penalty record: the stop match reads it
+      L->hctl.pen[m].rep = 1.f; L->hctl.pen[m].min_new = min_new_host[m];
+    }
+    L->hseq[(size_t)m] = seq_record(&seq[m], ctx_host + (size_t)m * ctx_cap, prompt_len_host[m]);
+    if (L->hseq[(size_t)m].plen == 0) L->hseq[(size_t)m].plen = prompt_len_host[m];
+    L->seq_dirty[m] = 1;
+  }
+  if (max_gen > 0) {   // the generated tokens of every row, as k_finalize would have left them
+    std::vector<int64_t> hist((size_t)max_gen * kMaxRows, 0);
+    for (int m = 0; m < n_rows; ++m)
+      for (int t = prompt_len_host[m]; t < ctx_len_host[m]; ++t) hist[(size_t)(t - prompt_len_host[m]) * kMaxRows + m] = ctx_host[(size_t)m * ctx_cap + t];
+    SMI_HIP(hipMemcpy(L->hist, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
+  }
+  SMI_HIP(hipMemcpy(L->seq, L->hseq.data(), (size_t)n_rows * sizeof(SeqRec), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
+  PenP pp;
+  pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
+  pp.V = V; pp.nblk = nblk; pp.per = per; pp.hs = 0;
+  pp.seq = L->seq; pp.ghist = L->hist; pp.max_steps = L->max_steps;
+  hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
+  SMI_LAUNCH_CHECK();
+  FinP f;
+  f.tok = nullptr; f.hs = 0; f.phist = nullptr;
+  f.lp = nullptr; f.lp_part = nullptr; f.lp_rowc = nullptr; f.logits = L->logits;
+  f.pval = L->pval; f.pidx = L->pidx; f.M = n_rows; f.KT = L->KTh; f.V = V; f.nblk = nblk;
+  f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
+  f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
+  f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
+  f.seq = L->seq;
+  hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
+  SMI_LAUNCH_CHECK();
+  SMI_HIP(hipDeviceSynchronize());
+  SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n_rows * V * 4, hipMemcpyDeviceToHost));
+  SMI_HIP(hipMemcpy(finished_out, L->finished, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+  std::vector<RowDesc> after(kMaxRows);
+  SMI_HIP(hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost));
+  for (int m = 0; m < n_rows; ++m) token_out[m] = after[m].token;
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
   L->started = 0;   // rows, controls, the lm_head partials and the histories no longer belong to a generation
   return SMI_OK;
 }

@@ -97,6 +97,17 @@ class AllowParams(C.Structure):
                 ("hi", C.c_int32 * SMI_MAX_ALLOW_RANGES)]
 
 
+SMI_MAX_BIAS_SEQS, SMI_MAX_STOP_SEQS, SMI_MAX_SEQ_LEN = 32, 8, 8
+
+
+class SeqParams(C.Structure):
+    """smi_seq_params: one admitted sequence's bias entries and stop sequences (smi_llm_admit_biased)"""
+    _fields_ = [("n_bias", C.c_int32), ("n_stop", C.c_int32), ("bias_len", C.c_int32 * SMI_MAX_BIAS_SEQS),
+                ("bias", C.c_float * SMI_MAX_BIAS_SEQS), ("bias_ids", C.c_int32 * (SMI_MAX_BIAS_SEQS * SMI_MAX_SEQ_LEN)),
+                ("stop_len", C.c_int32 * SMI_MAX_STOP_SEQS), ("stop_ids", C.c_int32 * (SMI_MAX_STOP_SEQS * SMI_MAX_SEQ_LEN)),
+                ("reserved", C.c_int32 * 2)]
+
+
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
 _P = C.POINTER
 SYMBOLS = {
@@ -128,6 +139,8 @@ SYMBOLS = {
                                   _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_admit_constrained": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams),
                                        _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(C.c_int32), _VP]),
+    "smi_llm_admit_biased": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams),
+                                  _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(SeqParams), _P(C.c_int32), _VP]),
     "smi_llm_poll": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_status": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_forward_logits": (_I, [_VP, _P(C.c_int64), _I, _VP, _VP]),
@@ -173,6 +186,8 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_logprob": (_I, [_VP, _P(C.c_float), _I, _P(C.c_float), _P(C.c_int32), _P(C.c_float)]),
     "smi_llm_debug_penalize": (_I, [_VP, _P(C.c_float), _I, _P(C.c_uint16), _P(PenaltyParams), _P(C.c_int32), _P(C.c_float),
                                     _P(C.c_int32)]),
+    "smi_llm_debug_seqbias": (_I, [_VP, _P(C.c_float), _I, _P(SeqParams), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _I,
+                                   _P(C.c_int32), _P(C.c_float), _P(C.c_int32), _P(C.c_int32)]),
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),

@@ -86,6 +86,111 @@ def allow_records(requests: Optional[Sequence[Optional[Mapping]]], n: int, vocab
     return recs
 
 
+# keys of the per-request sequence bias, banned and stop token sequences, in the same dicts (smi_llm_admit_biased;
+# include/sparkmi.h states the semantics): sequence_bias = [(ids, bias), ...] (transformers' SequenceBiasLogitsProcessor; a
+# bias is finite or -inf), bad_words_ids = [ids, ...] (= bias -inf: NoBadWordsLogitsProcessor), stop_sequences = [ids, ...]
+SEQ_KEYS = ("sequence_bias", "bad_words_ids", "stop_sequences")
+
+
+def _id_seq(ids, vocab_size: int, what: str) -> tuple:
+    if isinstance(ids, (str, bytes)) or not isinstance(ids, Iterable):
+        raise ValueError(f"{what} must be a sequence of token ids, not {ids!r}")
+    out = []
+    for v in ids:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: {v!r} is not an integer token id")
+        if not 0 <= int(v) < vocab_size:
+            raise ValueError(f"{what}: id {int(v)} outside [0, {vocab_size})")
+        out.append(int(v))
+    if not 1 <= len(out) <= _lib.SMI_MAX_SEQ_LEN:
+        raise ValueError(f"{what}: {len(out)} ids, a sequence holds 1..{_lib.SMI_MAX_SEQ_LEN}")
+    return tuple(out)
+
+
+def _seq_list(v, what: str) -> list:
+    if isinstance(v, (str, bytes, Mapping)) or not isinstance(v, Iterable):
+        raise ValueError(f"{what} must be a list, not {v!r}")
+    return list(v)
+
+
+def seq_entries(d: Optional[Mapping], vocab_size: int, what: str = "sampling"):
+    """(bias entries [(ids, float32 bias)], stop sequences [ids]) of one request dict, checked: ``sequence_bias`` entries first,
+    then ``bad_words_ids`` as bias -inf.  ValueError, before any device call, for a malformed list, a sequence of 0 or more
+    than ``SMI_MAX_SEQ_LEN`` ids, an id outside the vocabulary, a bias that is NaN or +inf, a sequence listed twice, or more
+    than ``SMI_MAX_BIAS_SEQS`` / ``SMI_MAX_STOP_SEQS`` entries."""
+    bias, stops = [], []
+    if d is None:
+        return bias, stops
+    if d.get("sequence_bias") is not None:
+        for k, e in enumerate(_seq_list(d["sequence_bias"], f"{what}.sequence_bias")):
+            if isinstance(e, (str, bytes)) or not isinstance(e, Sequence) or len(e) != 2:
+                raise ValueError(f"{what}.sequence_bias[{k}] must be (ids, bias), not {e!r}")
+            ids, b = e
+            if isinstance(b, (bool, np.bool_)) or not isinstance(b, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{what}.sequence_bias[{k}]: bias {b!r} is not a number")
+            b = np.float32(b)
+            if np.isnan(b) or b == np.inf:
+                raise ValueError(f"{what}.sequence_bias[{k}]: bias must be finite or -inf, not {e[1]!r}")
+            bias.append((_id_seq(ids, vocab_size, f"{what}.sequence_bias[{k}]"), b))
+    if d.get("bad_words_ids") is not None:
+        for k, ids in enumerate(_seq_list(d["bad_words_ids"], f"{what}.bad_words_ids")):
+            bias.append((_id_seq(ids, vocab_size, f"{what}.bad_words_ids[{k}]"), np.float32(-np.inf)))
+    if d.get("stop_sequences") is not None:
+        for k, ids in enumerate(_seq_list(d["stop_sequences"], f"{what}.stop_sequences")):
+            stops.append(_id_seq(ids, vocab_size, f"{what}.stop_sequences[{k}]"))
+    if len(bias) > _lib.SMI_MAX_BIAS_SEQS:
+        raise ValueError(f"{what}: {len(bias)} bias / banned sequences, at most {_lib.SMI_MAX_BIAS_SEQS} are supported")
+    if len(stops) > _lib.SMI_MAX_STOP_SEQS:
+        raise ValueError(f"{what}: {len(stops)} stop sequences, at most {_lib.SMI_MAX_STOP_SEQS} are supported")
+    if len({ids for ids, _ in bias}) != len(bias):
+        raise ValueError(f"{what}: a sequence is listed twice among sequence_bias / bad_words_ids")
+    if len(set(stops)) != len(stops):
+        raise ValueError(f"{what}: a sequence is listed twice among stop_sequences")
+    return bias, stops
+
+
+def seq_records(requests: Optional[Sequence[Optional[Mapping]]], n: int, vocab_size: int, eos_ids: Sequence[int] = ()):
+    """One ``smi_seq_params`` per prompt from the ``SEQ_KEYS`` of the request dicts, or None when no request carries one (the
+    admission then keeps the route and bits it has without them).  A request without a key gets a neutral record.  Every rule
+    of ``smi_llm_admit_biased`` is checked here first (``seq_entries``), the survivor rule included: the request's
+    ``allowed_token_ids`` (the vocabulary without the key) minus the last ids of its -inf entries must hold an id, and with
+    ``min_new_tokens`` > 0 an id that is not one of ``eos_ids``."""
+    if requests is None:
+        return None
+    requests = list(requests)
+    if len(requests) != n:
+        raise ValueError(f"sampling: {len(requests)} entries for {n} prompts")
+    if not any(d is not None and any(d.get(k) is not None for k in SEQ_KEYS) for d in requests):
+        return None
+    recs = (_lib.SeqParams * n)()
+    L = _lib.SMI_MAX_SEQ_LEN
+    for i, d in enumerate(requests):
+        bias, stops = seq_entries(d, vocab_size, f"sampling[{i}]")
+        gone = {ids[-1] for ids, b in bias if b == -np.inf}
+        if gone:
+            allowed = None if d.get(ALLOW_KEY) is None else set(int(v) for v in d[ALLOW_KEY])
+            size = vocab_size if allowed is None else len(allowed)
+            if allowed is not None:
+                gone &= allowed
+            if size <= len(gone):
+                raise ValueError(f"sampling[{i}]: the banned ids leave nothing the request could emit")
+            if int(d.get("min_new_tokens", 0) or 0) > 0:
+                gone |= {int(e) for e in eos_ids if 0 <= int(e) < vocab_size and (allowed is None or int(e) in allowed)}
+                if size <= len(gone):
+                    raise ValueError(f"sampling[{i}]: the banned ids leave only eos ids, which min_new_tokens bans")
+        r = recs[i]
+        r.n_bias, r.n_stop = len(bias), len(stops)
+        for k, (ids, b) in enumerate(bias):
+            r.bias_len[k], r.bias[k] = len(ids), float(b)
+            for t, v in enumerate(ids):
+                r.bias_ids[k * L + t] = v
+        for k, ids in enumerate(stops):
+            r.stop_len[k] = len(ids)
+            for t, v in enumerate(ids):
+                r.stop_ids[k * L + t] = v
+    return recs
+
+
 # key of a request's number of takes (TensorRT-LLM's num_return_sequences; smi_llm_admit_forked): SparkLLM.serve and SparkTTS
 # requests take it out of the dict before its records are built
 FORK_KEY = "num_return_sequences"
@@ -111,6 +216,9 @@ def expand_takes(sampling: Optional[Sequence[Optional[Mapping]]], n_return: Sequ
     for d, k in zip(sampling, n_return):
         if d is not None and d.get(ALLOW_KEY) is not None and not isinstance(d[ALLOW_KEY], (list, tuple)):
             d = dict(d, **{ALLOW_KEY: tuple(d[ALLOW_KEY])})   # a one-shot iterable serves every take
+        for key in SEQ_KEYS:                                  # the bias / banned / stop lists likewise: every take carries them
+            if d is not None and d.get(key) is not None and not isinstance(d[key], (list, tuple)):
+                d = dict(d, **{key: tuple(_seq_list(d[key], key))})
         for j in range(k):
             if d is None:
                 out.append(None)
@@ -189,7 +297,7 @@ def sampling_records(sampling: Optional[Sequence[Optional[Mapping]]], n: int, de
         raise ValueError(f"sampling: {len(sampling)} entries for {n} prompts")
     if all(d is None for d in sampling):
         return None
-    known = SAMPLING_KEYS + PENALTY_KEYS + LOGPROB_KEYS + (ALLOW_KEY,)
+    known = SAMPLING_KEYS + PENALTY_KEYS + LOGPROB_KEYS + (ALLOW_KEY,) + SEQ_KEYS
     for i, d in enumerate(sampling):
         bad = set(d or ()) - set(known)
         if bad:
@@ -416,6 +524,7 @@ class SparkLLM:
     def session_begin(self, eos_token_id: EosLike = None) -> None:
         """Empty in-flight-batching session: sequences are admitted and retired between decode steps."""
         eos_arr, n_eos = self._eos_args(eos_token_id)
+        self._session_eos = self._eos_list(eos_token_id)
         self._lib.check(self._lib.smi_llm_session_begin(self._h, eos_arr, n_eos, self._stream()), "smi_llm_session_begin")
 
     def admit(self, prompts: Sequence[Sequence[int]], sampling: Optional[Sequence[Optional[Mapping]]] = None,
@@ -427,7 +536,9 @@ class SparkLLM:
         some request carries ``return_log_probs`` (``LOGPROB_KEYS``, a bool) through ``smi_llm_admit_logprobs``, and the
         flagged sequences' log-probabilities are read with ``slots_logprobs``.  An admission in which some request carries
         ``allowed_token_ids`` (``ALLOW_KEY``: an iterable of ids; ``allow_records``) goes through ``smi_llm_admit_constrained``:
-        that sequence emits only ids of its set (eos ids are not added to it).
+        that sequence emits only ids of its set (eos ids are not added to it).  An admission in which some request carries
+        ``sequence_bias`` / ``bad_words_ids`` / ``stop_sequences`` (``SEQ_KEYS``; ``seq_records``) goes through
+        ``smi_llm_admit_biased``.
         ``n_return``: one int >= 1 per prompt -- that many takes of the prompt, its prompt prefilled once
         (``smi_llm_admit_forked``); ``sampling`` stays one dict per prompt and is expanded per take (``expand_takes``).  The
         result is then the flat, prompt-major slot list; None (the default) keeps today's route and bits."""
@@ -444,7 +555,14 @@ class SparkLLM:
         pens = penalty_records(sampling, n)
         flags = logprob_flags(sampling, n)
         allow = allow_records(sampling, n, self.cfg.vocab_size)
-        if allow is not None:
+        seqs = seq_records(sampling, n, self.cfg.vocab_size, getattr(self, "_session_eos", ()))
+        if seqs is not None:
+            self._lib.check(self._lib.smi_llm_admit_biased(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, None, recs, pens,
+                                                      None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      allow, seqs, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                            "smi_llm_admit_biased")
+        elif allow is not None:
             self._lib.check(self._lib.smi_llm_admit_constrained(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
                                                            lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, None, recs, pens,
                                                            None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -483,6 +601,7 @@ class SparkLLM:
         pens = penalty_records(takes, N)
         flags = logprob_flags(takes, N)
         allow = allow_records(takes, N, self.cfg.vocab_size)
+        seqs = seq_records(takes, N, self.cfg.vocab_size, getattr(self, "_session_eos", ()))
         lens = np.array([len(p) for p in prompts], dtype=np.int32)
         pmax = int(lens.max())
         ids = np.zeros((n, pmax), dtype=np.int64)
@@ -490,6 +609,14 @@ class SparkLLM:
             ids[b, : len(p)] = np.asarray(p, dtype=np.int64)
         nret = np.asarray(n_return, dtype=np.int32)
         slots = np.zeros(N, dtype=np.int32)
+        if seqs is not None:
+            self._lib.check(self._lib.smi_llm_admit_biased(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
+                                                      nret.ctypes.data_as(C.POINTER(C.c_int32)), recs, pens,
+                                                      None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      allow, seqs, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
+                            "smi_llm_admit_biased")
+            return slots.tolist()
         if allow is not None:
             self._lib.check(self._lib.smi_llm_admit_constrained(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
                                                            lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
@@ -703,9 +830,10 @@ class SparkLLM:
             on_prefilled()
         live = {slot: i for i, slot in enumerate(slots)}
         done = 1                                   # tokens every live row has emitted (the prefill emits the first)
+        stops = eos or any(d is not None and d.get("stop_sequences") for d in (sampling or ()))   # some row can finish early
         while live:
             fin = None
-            if eos:
+            if stops:
                 _, fin = self.status()             # one device round trip
             leave = [slot for slot, i in live.items() if done >= row_want[i] or (fin is not None and fin[slot])]
             if leave:
@@ -715,7 +843,7 @@ class SparkLLM:
             if not live:
                 break
             steps = min(row_want[i] for i in live.values()) - done
-            if eos:
+            if stops:
                 steps = min(steps, check_every)
             self.decode(steps)
             done += steps
@@ -891,6 +1019,37 @@ class SparkLLM:
                                                          out.ctypes.data_as(C.POINTER(C.c_float)),
                                                          am.ctypes.data_as(C.POINTER(C.c_int32))), "smi_llm_debug_penalize")
         return out, am
+
+    def debug_seqbias(self, logits: np.ndarray, requests: Sequence[Optional[Mapping]], contexts: Sequence[Sequence[int]],
+                      prompt_lens: Sequence[int], min_new: Optional[Sequence[int]] = None):
+        """The bias stage and ``k_finalize``'s stop match alone (``smi_llm_debug_seqbias``) on caller rows: ``logits`` [n][vocab]
+        f32, one request dict (``SEQ_KEYS``) or None and one context (prompt + generated ids, the first ``prompt_lens[i]`` the
+        prompt) per row.  Returns (the rows after the stage, the arg-max token per row, the finished flag per row)."""
+        self._need_diag("debug_seqbias")
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        n = lg.shape[0]
+        if lg.shape != (n, self.cfg.vocab_size) or len(requests) != n or len(contexts) != n or len(prompt_lens) != n:
+            raise ValueError("debug_seqbias: logits [n][vocab], n requests, n contexts, n prompt lengths")
+        recs = seq_records(list(requests), n, self.cfg.vocab_size)
+        if recs is None:
+            recs = (_lib.SeqParams * n)()
+        cl = np.asarray([len(c) for c in contexts], dtype=np.int32)
+        cap = int(cl.max())
+        ctx = np.zeros((n, cap), dtype=np.int64)
+        for i, c in enumerate(contexts):
+            ctx[i, : len(c)] = np.asarray(c, dtype=np.int64)
+        pl = np.ascontiguousarray(prompt_lens, dtype=np.int32)
+        mn = None if min_new is None else np.ascontiguousarray(min_new, dtype=np.int32)
+        out = np.empty_like(lg)
+        tok = np.zeros(n, dtype=np.int32)
+        fin = np.zeros(n, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._lib.check(self._lib.smi_llm_debug_seqbias(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), n, recs,
+                                                        ctx.ctypes.data_as(C.POINTER(C.c_int64)), cl.ctypes.data_as(i32),
+                                                        pl.ctypes.data_as(i32), cap, None if mn is None else mn.ctypes.data_as(i32),
+                                                        out.ctypes.data_as(C.POINTER(C.c_float)), tok.ctypes.data_as(i32),
+                                                        fin.ctypes.data_as(i32)), "smi_llm_debug_seqbias")
+        return out, tok, fin
 
     def debug_logprob(self, logits: np.ndarray, temperature: Sequence[float], tokens: Sequence[int]) -> np.ndarray:
         """The log-probability kernels alone (``smi_llm_debug_logprob``: k_logprob and k_finalize's combine) on caller rows:

@@ -20,8 +20,8 @@ import torch
 from . import _lib
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
-from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SparkLLM, eos_ids_from_generation_config,
-                  num_returns, penalty_neutral)
+from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SEQ_KEYS, SparkLLM,
+                  eos_ids_from_generation_config, num_returns, penalty_neutral, seq_entries)
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
 from .streaming import ChunkScheduler, StreamMux
@@ -32,12 +32,41 @@ from .weights import load_llm_state
 SPEECH_ONLY_KEY = "speech_tokens_only"
 
 
-def _request_sampling(r: dict, speech_ids=None) -> Optional[dict]:
+# request key: a bias on the end token -- sugar for one length-1 ``sequence_bias`` entry per eos id of the session (-inf: the
+# request runs to its token budget; a large positive value: it ends at the first token min_new_tokens lets it)
+EOS_BIAS_KEY = "eos_bias"
+
+
+def _request_seq(r: dict, eos: Sequence[int], vocab_size: int, what: str = "request") -> dict:
+    """The ``sequence_bias`` / ``bad_words_ids`` / ``stop_sequences`` keys (``SEQ_KEYS``) a request dict carries, as lists, with
+    ``eos_bias`` folded into ``sequence_bias``; checked (``seq_entries``: ValueError before anything reaches the device)."""
+    d = {}
+    for k in SEQ_KEYS:
+        if r.get(k) is not None:
+            v = r[k]
+            if isinstance(v, (str, bytes, dict)) or not hasattr(v, "__iter__"):
+                raise ValueError(f"{what}: {k} must be a list, not {v!r}")
+            d[k] = list(v)
+    if r.get(EOS_BIAS_KEY) is not None:
+        b = r[EOS_BIAS_KEY]
+        if isinstance(b, (bool, np.bool_)) or not isinstance(b, (int, float, np.integer, np.floating)) or np.isnan(b) or b == np.inf:
+            raise ValueError(f"{what}: {EOS_BIAS_KEY} must be a finite number or -inf, not {b!r}")
+        if not eos:
+            raise ValueError(f"{what}: {EOS_BIAS_KEY} needs an eos id, the model has none")
+        d["sequence_bias"] = list(d.get("sequence_bias", [])) + [((int(e),), float(b)) for e in dict.fromkeys(int(e) for e in eos)]
+    if d:
+        seq_entries(d, vocab_size, what)
+    return d
+
+
+def _request_sampling(r: dict, speech_ids=None, eos: Sequence[int] = (), vocab_size: Optional[int] = None) -> Optional[dict]:
     """The sampling keys (``SAMPLING_KEYS``) and penalty keys (``PENALTY_KEYS``) a request dict carries, or None: the
     call-level arguments apply unchanged.  Penalty keys that ask for no penalty are dropped, so such a request keeps the
     route (and the bits) of the same request without them.  ``return_log_probs`` (``LOGPROB_KEYS``) is kept when True.
     ``allowed_token_ids`` (``ALLOW_KEY``) and ``speech_tokens_only`` (``SPEECH_ONLY_KEY``: True -> ``speech_ids()``) become
-    the request's allowed-token set (both given: their intersection); include/sparkmi.h, smi_llm_admit_constrained."""
+    the request's allowed-token set (both given: their intersection); include/sparkmi.h, smi_llm_admit_constrained.
+    With ``vocab_size`` given, ``sequence_bias`` / ``bad_words_ids`` / ``stop_sequences`` (``SEQ_KEYS``) and ``eos_bias``
+    (``EOS_BIAS_KEY``, over the eos ids ``eos``) are checked and carried too (``_request_seq``; smi_llm_admit_biased)."""
     d = {k: r[k] for k in SAMPLING_KEYS if k in r}
     speech = r.get(SPEECH_ONLY_KEY, False)
     if not isinstance(speech, (bool, np.bool_)):
@@ -57,6 +86,8 @@ def _request_sampling(r: dict, speech_ids=None) -> Optional[dict]:
             raise ValueError(f"{k} must be a bool, not {r[k]!r}")
         if r.get(k):
             d[k] = True
+    if vocab_size is not None:
+        d.update(_request_seq(r, eos, vocab_size))
     return d or None
 
 
@@ -262,7 +293,7 @@ class SparkTTS:
         if room < 1:
             raise ValueError(f"a prompt of {max(len(i) for i in ids)} tokens does not fit max_positions={self._max_positions}")
         max_new_tokens = min(int(max_new_tokens), room)
-        sampling = [_request_sampling(r, self.speech_token_ids) for r in requests]
+        sampling = [_request_sampling(r, self.speech_token_ids, self._eos, self.model.cfg.vocab_size) for r in requests]
         if return_log_probs:
             sampling = [dict(d or {}, return_log_probs=True) for d in sampling]
         owner = list(range(len(ids)))   # request of every generated row
@@ -398,6 +429,7 @@ class SparkTTS:
             for i, r in enumerate(reqs):
                 if FORK_KEY in r:
                     forks[i] = _take_counts([r], self._max_batch)[0]
+                _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 yield r
 
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
@@ -416,7 +448,7 @@ class SparkTTS:
                     prompt, g = self.process_prompt(r["text"], r.get("prompt_speech_path"), r.get("prompt_text"), r.get("prompt_tokens"))
                 globals_[i] = g
                 ids = self.tokenizer([prompt], return_tensors="pt").input_ids[0].tolist()
-                d = _request_sampling(r, self.speech_token_ids)
+                d = _request_sampling(r, self.speech_token_ids, self._eos, self.model.cfg.vocab_size)
                 if FORK_KEY in r:
                     d = dict(d or {}, **{FORK_KEY: forks[i]})
                 yield i, ids, min(max_new_tokens, self._max_positions - len(ids) - decode_stride), self._eos, d
@@ -494,6 +526,7 @@ class SparkTTS:
                 for k in (FORK_KEY,) + tuple(LOGPROB_KEYS):
                     if k in r:
                         raise ValueError(f"request {i}: {k} is not supported by serve_stream")
+                _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 yield r
 
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
@@ -525,7 +558,7 @@ class SparkTTS:
                 budget = min(max_new_tokens, self._max_positions - len(ids) - decode_stride)
                 if budget < 1:
                     raise ValueError(f"request {i}: a prompt of {len(ids)} tokens leaves no room in max_positions={self._max_positions}")
-                yield i, ids, budget, g, _request_sampling(r, self.speech_token_ids)
+                yield i, ids, budget, g, _request_sampling(r, self.speech_token_ids, self._eos, self.model.cfg.vocab_size)
 
         def vocode(chunks):   # every ready chunk of every request in one ragged call, enqueued on the vocoder's own stream
             rows = [c for c in chunks if c[2]]
