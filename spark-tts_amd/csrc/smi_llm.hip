@@ -3742,13 +3742,11 @@ struct smi_llm {
   int max_len, steps_launched;  // host-side bound on cache positions in use
   // sampling state (smi_llm_set_sampling)
   int do_sample, top_k; float temperature, top_p; unsigned long long seed;
-  int slot_samp[kMaxRows];      // host: the record of the sequence in this slot (live or being admitted) is SMI_SAMPLING_SAMPLE
-  int slot_pen[kMaxRows];       // host: the sequence in this slot (live or being admitted) has a penalty record (PenRec::on)
-  int slot_lp[kMaxRows];        // host: the sequence in this slot (live or being admitted) returns log-probabilities (Ctl::lp)
-  int slot_allow[kMaxRows];     // host: the sequence in this slot (live or being admitted) is constrained (Ctl::allow, n > 0)
+  // host: what the record set of the sequence in each slot (live or being admitted) asks of a step, F_* bits: its sampling record
+  // is SMI_SAMPLING_SAMPLE, it has a penalty record (PenRec::on), returns log-probabilities (Ctl::lp), is constrained
+  // (Ctl::allow, n > 0), has bias entries (SeqRec::n_bias > 0), has stop sequences (SeqRec::n_stop > 0)
+  uint8_t slot_feat[kMaxRows];
   int lm_restrict;              // host: every row of the steps being issued is constrained (the restricted lm_head may run)
-  int slot_bias[kMaxRows];      // host: the sequence in this slot (live or being admitted) has bias entries (SeqRec::n_bias > 0)
-  int slot_stop[kMaxRows];      // host: ... has stop sequences (SeqRec::n_stop > 0)
   int seq_dirty[kMaxRows];      // host: the slot's device record is not all zero (an admission without a record clears it)
   SeqRec* seq;                  // device: per-slot bias / stop records [kMaxRows] (smi_llm_admit_biased)
   std::vector<SeqRec> hseq;     // host: what the device records hold
@@ -3776,13 +3774,13 @@ struct smi_llm {
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
   int gu1_lo;           // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (SPARKMI_GU1_LO; default 4)
   int gu1_rows;         // rows up to which gate_up runs its one-batch, three-tile shape (SPARKMI_GU1_ROWS; default 32)
-  hipGraphExec_t graph; int graph_B, graph_seg, graph_ident, graph_samp, graph_pen, graph_lp, graph_allow, graph_seq;   // the step graph in use (owned by graph_cache)
+  hipGraphExec_t graph; uint64_t graph_id;   // the one-step graph in use (owned by graph_cache) and its graph_key
   // every exec remembers the stream it last ran on: a caller may alternate streams, and an exec is destroyed only after THAT
   // stream has drained (graphs_flush)
   std::map<hipGraphExec_t, hipStream_t> graph_last;
-  // One captured decode step per (row count, context segments, slots-are-rows, some row may sample, some row is penalised,
-  // steps per replay): in-flight batching changes
-  // the row count at every admission / retirement, and re-capturing the ~100-node step each time cost more than the steps saved.
+  // One captured decode step per graph_key (row count, context segments, slots-are-rows, the step's feature mask, restricted
+  // lm_head, steps per replay): in-flight batching changes the row count at every admission / retirement, and re-capturing the
+  // ~100-node step each time cost more than the steps saved.
   // Everything else a step reads is device data (row descriptors, stop ids, seed, the per-slot sampling records) or fixed at
   // create; the handle's sampler settings and the attention-partials buffer are kernel arguments, so a change of either empties
   // the cache (graphs_flush).  The sample bit decides only whether lm_head writes the logits rows and the sampler kernels run:
@@ -3870,63 +3868,46 @@ int pages_ensure(smi_llm* L, const int* slots, const int* tokens, int n, hipStre
   return SMI_OK;
 }
 KvMap kv_map(const smi_llm* L) { return KvMap{L->paged ? L->ptab : nullptr, L->pshift, L->ppslot}; }
-// Some row of the step may sample: the handle does, or a live / just-admitted sequence's record says SMI_SAMPLING_SAMPLE.  (An
-// over-estimate is harmless: the rows that do not sample leave the sampler kernels at once and k_finalize takes their arg-max.)
-bool samp_any(const smi_llm* L) {
-  if (L->do_sample) return true;
-  for (int sl = 0; sl < kMaxRows; ++sl)
-    if (L->slot_samp[sl]) return true;
-  return false;
+// What a sequence's record set asks of a step (smi_llm::slot_feat).
+enum : uint8_t { F_SAMPLE = 1, F_PEN = 2, F_LP = 4, F_ALLOW = 8, F_BIAS = 16, F_STOP = 32 };
+// The features of the steps being issued: the OR over EVERY slot, live or being admitted -- not only the step's rows -- plus
+// F_SAMPLE when the handle samples.  An over-estimate is harmless: a row without a feature leaves that feature's kernels at
+// once (the sampler kernels, k_penalize, k_logprob) and k_finalize takes its arg-max, so its bits are those of the step without.
+// What each bit adds to a step: the comment at smi_llm::graph_cache.
+unsigned step_feat(const smi_llm* L) {
+  unsigned f = L->do_sample ? F_SAMPLE : 0;
+  for (int sl = 0; sl < kMaxRows; ++sl) f |= L->slot_feat[sl];
+  return f;
 }
-// Some live / just-admitted row has a penalty record: lm_head writes the logits rows and k_penalize runs.
-bool pen_any(const smi_llm* L) {
-  for (int sl = 0; sl < kMaxRows; ++sl)
-    if (L->slot_pen[sl]) return true;
-  return false;
+// The sequence in `slot` has left (or was not admitted after all): its features no longer count.  Its records stay -- the
+// slot's log-probabilities stay readable until it is reused (Ctl::lp), and seq_dirty says what the device record holds.
+void slot_clear(smi_llm* L, int slot) { L->slot_feat[slot] = 0; }
+// A new generation / session: every sequence inherits the handle's settings, has no penalties, keeps no log-probabilities, is
+// not constrained and has no bias entries or stop sequences (seq_dirty stays: the device records are as they were).
+void slots_clear(smi_llm* L) {
+  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
+  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
+  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
+  memset(L->slot_feat, 0, sizeof(L->slot_feat));
+  L->lm_restrict = 0;
 }
-// Some live / just-admitted row returns log-probabilities: lm_head writes the logits rows and k_logprob runs.
-bool lp_any(const smi_llm* L) {
-  for (int sl = 0; sl < kMaxRows; ++sl)
-    if (L->slot_lp[sl]) return true;
-  return false;
-}
-// Some live / just-admitted row is constrained (smi_llm_admit_constrained).
-bool allow_any(const smi_llm* L) {
-  for (int sl = 0; sl < kMaxRows; ++sl)
-    if (L->slot_allow[sl]) return true;
-  return false;
-}
-// Some live / just-admitted row has bias entries / stop sequences (smi_llm_admit_biased).
-bool bias_any(const smi_llm* L) {
-  for (int sl = 0; sl < kMaxRows; ++sl)
-    if (L->slot_bias[sl]) return true;
-  return false;
-}
-bool stop_any(const smi_llm* L) {
-  for (int sl = 0; sl < kMaxRows; ++sl)
-    if (L->slot_stop[sl]) return true;
-  return false;
-}
-// the sequence bits of a step: 1 = some row has a bias entry, 2 = some row has a stop sequence
-int seq_bits(const smi_llm* L) { return (bias_any(L) ? 1 : 0) | (stop_any(L) ? 2 : 0); }
 // The step's lm_head reads only the tiles of the union (k_lm / k_lm32 with RT = 1): every row of the step is constrained, and the
 // persistent kernels run (K <= 32 tiles, bf16 weights; the generic EPI_LM GEMM and the exact-weights mode take the full path).
-bool lm_restricted(const smi_llm* L) {
-  return L->lm_restrict && L->KTh <= 32 && !L->exact && allow_any(L);
+bool lm_restricted(const smi_llm* L, unsigned feat) {
+  return L->lm_restrict && L->KTh <= 32 && !L->exact && (feat & F_ALLOW);
 }
 // Some row of the step reads the logits rows: a sampling, penalised, biased or log-probability row, or a constrained row whose stage 0
 // runs in k_penalize (every constrained row of a full-lm_head step; on the restricted path k_penalize then also runs, so the
 // rows it hands on are dense).
-bool logits_needed(const smi_llm* L) {
-  return samp_any(L) || pen_any(L) || lp_any(L) || bias_any(L) || (allow_any(L) && !lm_restricted(L));
+bool logits_needed(const smi_llm* L, unsigned feat) {
+  return (feat & (F_SAMPLE | F_PEN | F_LP | F_BIAS)) || ((feat & F_ALLOW) && !lm_restricted(L, feat));
 }
-// the constraint bits of a step: 1 = some row constrained, 2 = every row (restricted lm_head)
-int allow_bits(const smi_llm* L) { return allow_any(L) ? (lm_restricted(L) ? 3 : 1) : 0; }
-// the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | sample << 25 | penalty << 26 | log-probs << 27 |
-// constraints << 28 (2 bits) | sequence bits << 30 (2 bits) | steps per replay << 32
-uint64_t graph_key(const smi_llm* L, int samp, int pen, int lp, int K) {
-  return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)samp << 25) |
-         ((uint64_t)pen << 26) | ((uint64_t)lp << 27) | ((uint64_t)allow_bits(L) << 28) | ((uint64_t)seq_bits(L) << 30) | ((uint64_t)K << 32);
+// the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | feature mask << 25 (6 bits) | restricted lm_head << 31 |
+// steps per replay << 32
+uint64_t graph_key(const smi_llm* L, unsigned feat, int K) {
+  return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)feat << 25) |
+         ((uint64_t)(lm_restricted(L, feat) ? 1 : 0) << 31) | ((uint64_t)K << 32);
 }
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
@@ -4173,7 +4154,7 @@ int eng_create(smi_llm* L) {
 // only: lm_head, the sampler and k_finalize stay launches, so a sampling record applies to the engine's row as to any other)
 bool eng_usable(const smi_llm* L, const RowDesc* rows, int M) {
   return L->eng.enabled && L->eng_on && M == 1 && rows == L->rows && L->identity_slots && !L->paged && L->attn_seg <= 1 && !L->stamps_on &&
-         !lp_any(L) && !seq_bits(L);   // (a step with a log-probability, biased or stop-sequence row keeps to the launch path)
+         !(step_feat(L) & (F_LP | F_BIAS | F_STOP));   // (a step with a log-probability, biased or stop-sequence row keeps to the launch path)
 }
 
 int eng_launch(smi_llm* L, hipStream_t st) {
@@ -4247,6 +4228,39 @@ LpP lp_params(const smi_llm* L, int M) {
   lp.V = L->cfg.vocab_size; lp.per = pen_set_ids(lp.V, kLpBlocks); lp.inv_temp = 1.0f / L->temperature; lp.hs = L->do_sample;
   lp.part = L->lp_part; lp.rowc = L->lp_rowc;
   return lp;
+}
+
+// k_penalize's arguments for a step of M rows; a caller whose rows have bias entries adds the sequence records (PenP::seq)
+PenP pen_params(const smi_llm* L, int M) {
+  PenP pp;
+  pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
+  pp.V = L->cfg.vocab_size; pp.nblk = lm_blocks_for(L, M); pp.per = pen_set_ids(pp.V, pp.nblk); pp.hs = L->do_sample;
+  pp.seq = nullptr; pp.ghist = L->hist; pp.max_steps = L->max_steps;
+  return pp;
+}
+
+// the sampler kernels' arguments for a step of M rows (the handle's settings; the lm_head's maxima as the top-k bound)
+SampleP sample_params(const smi_llm* L, int M) {
+  SampleP sp;
+  sp.logits = L->logits; sp.V = L->cfg.vocab_size; sp.top_k = L->top_k; sp.inv_temp = 1.0f / L->temperature;
+  sp.top_p = L->top_p; sp.hs = L->do_sample; sp.ctl = L->ctl; sp.rows = L->rows; sp.tok = L->tok;
+  sp.pval = L->pval; sp.nblk = lm_blocks_for(L, M);
+  sp.cand_v = L->cand_v; sp.cand_i = L->cand_i; sp.cand_n = L->cand_n;
+  return sp;
+}
+
+// k_finalize's arguments for a step of M rows in which no row samples, is penalised, returns log-probabilities or has a stop
+// sequence: the caller adds what the kernels it ran before left (FinP::tok, phist, lp*) and the stop records (FinP::seq)
+FinP fin_params(const smi_llm* L, int M) {
+  FinP f;
+  f.tok = nullptr; f.hs = L->do_sample; f.phist = nullptr;
+  f.lp = nullptr; f.lp_part = nullptr; f.lp_rowc = nullptr; f.logits = L->logits;
+  f.pval = L->pval; f.pidx = L->pidx; f.M = M; f.KT = L->KTh; f.V = L->cfg.vocab_size; f.nblk = lm_blocks_for(L, M);
+  f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
+  f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
+  f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
+  f.seq = nullptr;
+  return f;
 }
 
 int segs_for(int ctx_bound) { return ctx_bound <= kAttnSeg ? 1 : (ctx_bound + kAttnSeg - 1) / kAttnSeg; }
@@ -4381,7 +4395,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
       case KLM:
         p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh; p.XS = L->xs_h;
-        p.Y = logits ? logits : (logits_needed(L) ? L->logits : nullptr);
+        p.Y = logits ? logits : (logits_needed(L, step_feat(L)) ? L->logits : nullptr);
         p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
         SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
         return launch_gemm_x<PRO_NORM, EPI_LM>(L, p, st);
@@ -4481,13 +4495,14 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
           if (M <= 32) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 2, 0>(L, p, st);
           return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 1, 0>(L, p, st);
       }
-    case KLM:
+    case KLM: {
+      const unsigned feat = step_feat(L);
       p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh;
       p.XS = L->xs_h;
-      p.Y = logits ? logits : (logits_needed(L) ? L->logits : nullptr);
+      p.Y = logits ? logits : (logits_needed(L, feat) ? L->logits : nullptr);
       p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
       p.stamps = L->stamps_on ? L->stamps : nullptr;
-      if (L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L)) {   // every row constrained: only the union's tiles
+      if (L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L, feat)) {   // every row constrained: only the union's tiles
         p.tlist = L->tlist; p.ctl = L->ctl;
         const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
         const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
@@ -4528,45 +4543,33 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       }
       SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
       return launch_gemm<4, 4, 2, 1, PRO_NORM, EPI_LM>(L, p, st);
+    }
     case KFIN: {
-      FinP f;
-      f.tok = nullptr;
-      f.hs = L->do_sample;
-      f.phist = nullptr;
-      if (pen_any(L) || bias_any(L) || (allow_any(L) && logits_needed(L))) {   // rows neither penalised, biased nor constrained leave k_penalize at once
-        PenP pp;
-        pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
-        pp.V = c.vocab_size; pp.nblk = lm_blocks_for(L, M); pp.per = pen_set_ids(pp.V, pp.nblk); pp.hs = L->do_sample;
-        pp.seq = bias_any(L) ? L->seq : nullptr; pp.ghist = L->hist; pp.max_steps = L->max_steps;
+      const unsigned feat = step_feat(L);
+      FinP f = fin_params(L, M);
+      // rows neither penalised, biased nor constrained leave k_penalize at once
+      if ((feat & (F_PEN | F_BIAS)) || ((feat & F_ALLOW) && logits_needed(L, feat))) {
+        PenP pp = pen_params(L, M);
+        if (feat & F_BIAS) pp.seq = L->seq;
         hipLaunchKernelGGL(k_penalize, dim3((pp.nblk + kPenWaves - 1) / kPenWaves, M), dim3(256), 0, st, pp);
         SMI_LAUNCH_CHECK();
         f.phist = L->phist;
       }
-      if (samp_any(L)) {   // rows that do not sample leave both sampler kernels at once
-        SampleP sp;
-        sp.logits = L->logits; sp.V = c.vocab_size; sp.top_k = L->top_k; sp.inv_temp = 1.0f / L->temperature;
-        sp.top_p = L->top_p; sp.hs = L->do_sample; sp.ctl = L->ctl; sp.rows = L->rows; sp.tok = L->tok;
-        sp.pval = L->pval; sp.nblk = lm_blocks_for(L, M);
-        sp.cand_v = L->cand_v; sp.cand_i = L->cand_i; sp.cand_n = L->cand_n;
+      if (feat & F_SAMPLE) {   // rows that do not sample leave both sampler kernels at once
+        const SampleP sp = sample_params(L, M);
         hipLaunchKernelGGL(k_sample_scan, dim3(kScanBlocks, M), dim3(256), 0, st, sp);
         SMI_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_sample, dim3(M), dim3(1024), 0, st, sp);
         SMI_LAUNCH_CHECK();
         f.tok = L->tok;
       }
-      f.lp = nullptr; f.lp_part = nullptr; f.lp_rowc = nullptr; f.logits = L->logits;
-      if (lp_any(L)) {   // unflagged rows leave k_logprob at once
-        LpP lp = lp_params(L, M);
+      if (feat & F_LP) {   // unflagged rows leave k_logprob at once
+        const LpP lp = lp_params(L, M);
         hipLaunchKernelGGL(k_logprob, dim3(kLpBlocks, M), dim3(256), 0, st, lp);
         SMI_LAUNCH_CHECK();
         f.lp = L->lp; f.lp_part = L->lp_part; f.lp_rowc = L->lp_rowc;
       }
-      f.pval = L->pval; f.pidx = L->pidx; f.M = M; f.KT = L->KTh; f.V = c.vocab_size;
-      f.nblk = lm_blocks_for(L, M);
-      f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
-      f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
-      f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
-      f.seq = stop_any(L) ? L->seq : nullptr;
+      if (feat & F_STOP) f.seq = L->seq;
       hipLaunchKernelGGL(k_finalize, dim3(M), dim3(256), 0, st, f);
       SMI_LAUNCH_CHECK();
       return SMI_OK;
@@ -4896,10 +4899,10 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
-  L->graph = nullptr; L->graph_B = 0; L->graph_seg = 1; L->graph_ident = 1; L->graph_samp = 0; L->graph_pen = 0; L->graph_lp = 0; L->graph_allow = 0; L->graph_seq = 0; memset(L->slot_samp, 0, sizeof(L->slot_samp)); memset(L->slot_pen, 0, sizeof(L->slot_pen));
-  memset(L->slot_lp, 0, sizeof(L->slot_lp)); L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
-  memset(L->slot_allow, 0, sizeof(L->slot_allow)); L->lm_restrict = 0; L->tlist = nullptr;
-  memset(L->slot_bias, 0, sizeof(L->slot_bias)); memset(L->slot_stop, 0, sizeof(L->slot_stop)); memset(L->seq_dirty, 0, sizeof(L->seq_dirty));
+  L->graph = nullptr; L->graph_id = 0; slots_clear(L);
+  L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
+  L->tlist = nullptr;
+  memset(L->seq_dirty, 0, sizeof(L->seq_dirty));
   L->seq = nullptr; L->hseq.assign(kMaxRows, SeqRec{});
   L->poll_dev = nullptr; L->poll_host = nullptr;
   L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
@@ -5226,17 +5229,7 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   }
   for (int b = 0; b < B; ++b) L->plen[b] = lens[b];
   for (int b = 0; b < kMaxRows; ++b) L->hctl.seqid[b] = b;
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));   // every sequence inherits the handle's settings
-  memset(L->slot_samp, 0, sizeof(L->slot_samp));
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));     // and has no penalties
-  memset(L->slot_pen, 0, sizeof(L->slot_pen));
-  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));       // and keeps no log-probabilities
-  memset(L->slot_lp, 0, sizeof(L->slot_lp));
-  memset(L->hctl.allow, 0, sizeof(L->hctl.allow)); // and is not constrained
-  memset(L->slot_allow, 0, sizeof(L->slot_allow));
-  memset(L->slot_bias, 0, sizeof(L->slot_bias));   // and has no bias entries or stop sequences
-  memset(L->slot_stop, 0, sizeof(L->slot_stop));
-  L->lm_restrict = 0;
+  slots_clear(L);
   L->admit_seq = B;
   { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
   SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
@@ -5265,17 +5258,7 @@ int smi_llm_session_begin(smi_llm* L, const int64_t* eos_ids, int n_eos, void* s
   SMI_REQUIRE(L, "smi_llm_session_begin: null handle");
   hipStream_t st = (hipStream_t)stream;
   memset(L->hctl.seqid, 0, sizeof(L->hctl.seqid));
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
-  memset(L->slot_samp, 0, sizeof(L->slot_samp));
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
-  memset(L->slot_pen, 0, sizeof(L->slot_pen));
-  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
-  memset(L->slot_lp, 0, sizeof(L->slot_lp));
-  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
-  memset(L->slot_allow, 0, sizeof(L->slot_allow));
-  memset(L->slot_bias, 0, sizeof(L->slot_bias));
-  memset(L->slot_stop, 0, sizeof(L->slot_stop));
-  L->lm_restrict = 0;
+  slots_clear(L);
   L->admit_seq = 0;
   if (L->paged)
     for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
@@ -5298,7 +5281,7 @@ static int session_set_rows(smi_llm* L, const std::vector<RowDesc>& live, hipStr
   L->identity_slots = 1;
   for (int b = 0; b < L->B; ++b) L->identity_slots &= live[b].slot == b;
   L->lm_restrict = L->B > 0;
-  for (int b = 0; b < L->B; ++b) L->lm_restrict &= L->slot_allow[live[b].slot];
+  for (int b = 0; b < L->B; ++b) L->lm_restrict &= (L->slot_feat[live[b].slot] & F_ALLOW) != 0;
   L->live_order.clear();
   for (int b = 0; b < L->B; ++b) L->live_order.push_back(live[b].slot);
   L->graph = nullptr;   // (the next decode picks the cached step of the new row count)
@@ -5375,10 +5358,6 @@ static int pen_histories(smi_llm* L, const int64_t* ids, const int32_t* lens, in
   return SMI_OK;
 }
 
-int smi_llm_admit(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, int32_t* slots_out, void* stream) {
-  return smi_llm_admit_sampled(L, ids, lens, n, P_max, nullptr, slots_out, stream);
-}
-
 // Checks of one penalty record (smi_llm_admit_penalized, smi_llm_debug_penalize).
 static int validate_penalty(const smi_llm* L, const smi_penalty_params& r, int b) {
   SMI_REQUIRE(std::isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f,
@@ -5402,21 +5381,6 @@ static PenRec pen_record(const smi_penalty_params* pp) {
   r.rep = pp->repetition_penalty; r.pres = pp->presence_penalty; r.freq = pp->frequency_penalty;
   r.min_new = pp->min_new_tokens; r.prompt = pp->penalize_prompt; r.on = 1;
   return r;
-}
-
-int smi_llm_admit_sampled(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
-                          int32_t* slots_out, void* stream) {
-  return smi_llm_admit_penalized(L, ids, lens, n, P_max, params, nullptr, slots_out, stream);
-}
-
-int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
-                            const smi_penalty_params* pens, int32_t* slots_out, void* stream) {
-  return smi_llm_admit_logprobs(L, ids, lens, n, P_max, params, pens, nullptr, slots_out, stream);
-}
-
-int smi_llm_admit_logprobs(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
-                           const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out, void* stream) {
-  return smi_llm_admit_forked(L, ids, lens, n, P_max, nullptr, params, pens, want_lp, slots_out, stream);
 }
 
 // Checks of one allow record (smi_llm_admit_constrained; before anything of the handle is touched).  pen: the take's penalty
@@ -5463,10 +5427,10 @@ static AllowRec allow_record(const smi_allow_params* a, int V) {
 // The restricted lm_head's tile list -> device, in stream order: the 16-id vocabulary tiles that hold an id of some constrained
 // slot's set (live or being admitted), ascending.  Nothing to do while no slot is constrained (the list is not read).
 static int allow_tiles_upload(smi_llm* L, hipStream_t st) {
-  if (!allow_any(L)) return SMI_OK;
+  if (!(step_feat(L) & F_ALLOW)) return SMI_OK;
   std::vector<char> mark((size_t)L->NTlm, 0);
   for (int sl = 0; sl < kMaxRows; ++sl) {
-    if (!L->slot_allow[sl]) continue;
+    if (!(L->slot_feat[sl] & F_ALLOW)) continue;
     const AllowRec& a = L->hctl.allow[sl];
     for (int i = 0; i < a.n; ++i)
       for (int t = a.lo[i] >> 4; t <= (a.hi[i] - 1) >> 4; ++t) mark[(size_t)t] = 1;
@@ -5479,20 +5443,6 @@ static int allow_tiles_upload(smi_llm* L, hipStream_t st) {
   // (pageable source: staged before the call returns; host_tlist is rebuilt only by the next admission or retirement)
   SMI_HIP(hipMemcpyAsync(L->tlist, T.data(), T.size() * 4, hipMemcpyHostToDevice, st));
   return SMI_OK;
-}
-
-// n_ret[b] takes of prompt b; the records are per take (N = sum of n_ret).  n_ret = null or all ones: the plain admission.
-int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
-                         const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out,
-                         void* stream) {
-  return smi_llm_admit_constrained(L, ids, lens, n, P_max, n_ret, params, pens, want_lp, nullptr, slots_out, stream);
-}
-
-// smi_llm_admit_forked plus one allow record per take (allow = null: exactly smi_llm_admit_forked).
-int smi_llm_admit_constrained(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
-                              const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
-                              const smi_allow_params* allow, int32_t* slots_out, void* stream) {
-  return smi_llm_admit_biased(L, ids, lens, n, P_max, n_ret, params, pens, want_lp, allow, nullptr, slots_out, stream);
 }
 
 // Checks of one bias / stop record (smi_llm_admit_biased, smi_llm_debug_seqbias; before anything of the handle is touched).
@@ -5571,10 +5521,39 @@ static SeqRec seq_record(const smi_seq_params* q, const int64_t* ids, int len) {
   return r;
 }
 
-// smi_llm_admit_constrained plus one bias / stop record per take (seq = null: exactly smi_llm_admit_constrained).
-int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
-                         const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
-                         const smi_allow_params* allow, const smi_seq_params* seq, int32_t* slots_out, void* stream) {
+// One admission, as the smi_llm_admit* entry points hand it over.  n_ret[b] takes of prompt b (null or all ones: one each);
+// the record arrays hold one record per take (N = sum of n_ret), and a null array is no record for any take.  An entry point
+// names the members it takes; the ones after them are null, so a new kind of record is a new last member.
+struct AdmitReq {
+  const int64_t* ids; const int32_t* lens; int n, P_max;
+  const int32_t* n_ret;
+  const smi_sample_params* params;
+  const smi_penalty_params* pens;
+  const int32_t* want_lp;
+  const smi_allow_params* allow;
+  const smi_seq_params* seq;
+};
+
+// What a KV slot holds of its sequence on the host: the admission number, the records of Ctl and the feature bits.
+struct SlotRecs {
+  int32_t seqid; SampRec samp; PenRec pen; int32_t lp; AllowRec allow; uint8_t feat;
+};
+static SlotRecs recs_get(const smi_llm* L, int sl) {
+  return SlotRecs{L->hctl.seqid[sl], L->hctl.samp[sl], L->hctl.pen[sl], L->hctl.lp[sl], L->hctl.allow[sl], L->slot_feat[sl]};
+}
+static void recs_put(smi_llm* L, int sl, const SlotRecs& r) {
+  L->hctl.seqid[sl] = r.seqid; L->hctl.samp[sl] = r.samp; L->hctl.pen[sl] = r.pen; L->hctl.lp[sl] = r.lp; L->hctl.allow[sl] = r.allow;
+  L->slot_feat[sl] = r.feat;
+}
+
+static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t st) {
+  const int64_t* ids = rq.ids;
+  const int32_t *lens = rq.lens, *n_ret = rq.n_ret, *want_lp = rq.want_lp;
+  const int n = rq.n, P_max = rq.P_max;
+  const smi_sample_params* params = rq.params;
+  const smi_penalty_params* pens = rq.pens;
+  const smi_allow_params* allow = rq.allow;
+  const smi_seq_params* seq = rq.seq;
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
   const int slot_cap = L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows;
@@ -5602,7 +5581,6 @@ int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, in
       const int rcq = validate_seq(L, seq[j], allow ? &allow[j] : nullptr, pens ? &pens[j] : nullptr, j);
       if (rcq) return rcq;
     }
-  hipStream_t st = (hipStream_t)stream;
   int rc;
   std::vector<RowDesc> live;
   if ((rc = session_live_rows(L, live, st))) return rc;
@@ -5646,38 +5624,24 @@ int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, in
       return rc;
     }
   }
-  const int seq0 = L->admit_seq;
-  int32_t old_seqid[kMaxRows];
-  SampRec old_rec[kMaxRows];
-  PenRec old_pen[kMaxRows];
-  int32_t old_lp[kMaxRows];
-  AllowRec old_allow[kMaxRows];
-  for (int j = 0; j < N; ++j) { old_seqid[j] = L->hctl.seqid[slots[j]]; L->hctl.seqid[slots[j]] = L->admit_seq++; }
   // the records go up with the sequence numbers, before the admission's own step: its finalize emits the first token
+  const int seq0 = L->admit_seq;
+  SlotRecs old[kMaxRows];
   for (int j = 0; j < N; ++j) {
-    old_rec[j] = L->hctl.samp[slots[j]];
-    L->hctl.samp[slots[j]] = samp_record(params ? &params[j] : nullptr, L->cfg.vocab_size);
-    L->slot_samp[slots[j]] = L->hctl.samp[slots[j]].mode == SMI_SAMPLING_SAMPLE;
-    old_pen[j] = L->hctl.pen[slots[j]];
-    L->hctl.pen[slots[j]] = pen_record(pens ? &pens[j] : nullptr);
-    L->slot_pen[slots[j]] = L->hctl.pen[slots[j]].on;
-    old_lp[j] = L->hctl.lp[slots[j]];
-    L->hctl.lp[slots[j]] = want_lp ? want_lp[j] : 0;
-    L->slot_lp[slots[j]] = L->hctl.lp[slots[j]];
-    old_allow[j] = L->hctl.allow[slots[j]];
-    L->hctl.allow[slots[j]] = allow_record(allow ? &allow[j] : nullptr, L->cfg.vocab_size);
-    L->slot_allow[slots[j]] = L->hctl.allow[slots[j]].n > 0;
+    old[j] = recs_get(L, slots[j]);
+    SlotRecs r;
+    r.seqid = L->admit_seq++;
+    r.samp = samp_record(params ? &params[j] : nullptr, L->cfg.vocab_size);
+    r.pen = pen_record(pens ? &pens[j] : nullptr);
+    r.lp = want_lp ? want_lp[j] : 0;
+    r.allow = allow_record(allow ? &allow[j] : nullptr, L->cfg.vocab_size);
+    r.feat = (r.samp.mode == SMI_SAMPLING_SAMPLE ? F_SAMPLE : 0) | (r.pen.on ? F_PEN : 0) | (r.lp ? F_LP : 0) | (r.allow.n > 0 ? F_ALLOW : 0);
+    recs_put(L, slots[j], r);   // (F_BIAS / F_STOP: with the sequence records below)
   }
   // undo: nothing was admitted -- sequence numbers, records and pages (and page references) as before (the device copy is
-  // rewritten by the next admission)
+  // rewritten by the next admission; seq_dirty stays: the next admission rewrites the device record)
   auto undo = [&]() {
-    for (int j = 0; j < N; ++j) {
-      L->hctl.seqid[slots[j]] = old_seqid[j]; L->hctl.samp[slots[j]] = old_rec[j]; L->slot_samp[slots[j]] = 0;
-      L->hctl.pen[slots[j]] = old_pen[j]; L->slot_pen[slots[j]] = 0;
-      L->hctl.lp[slots[j]] = old_lp[j]; L->slot_lp[slots[j]] = 0;
-      L->hctl.allow[slots[j]] = old_allow[j]; L->slot_allow[slots[j]] = 0;
-      L->slot_bias[slots[j]] = 0; L->slot_stop[slots[j]] = 0;   // (seq_dirty stays: the next admission rewrites the device record)
-    }
+    for (int j = 0; j < N; ++j) { recs_put(L, slots[j], old[j]); slot_clear(L, slots[j]); }
     L->admit_seq = seq0;
     if (L->paged)
       for (int j = 0; j < N; ++j) pages_release(L, slots[j]);
@@ -5694,7 +5658,7 @@ int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, in
     const int sl = slots[j];
     const SeqRec rec = seq_record(seq ? &seq[j] : nullptr, ids + (size_t)src[j] * P_max, lens_j[j]);
     const int on = rec.n_bias > 0 || rec.n_stop > 0;
-    L->slot_bias[sl] = rec.n_bias > 0; L->slot_stop[sl] = rec.n_stop > 0;
+    L->slot_feat[sl] |= (rec.n_bias > 0 ? F_BIAS : 0) | (rec.n_stop > 0 ? F_STOP : 0);
     if (!on && !L->seq_dirty[sl]) continue;
     L->hseq[(size_t)sl] = rec;
     L->seq_dirty[sl] = on;
@@ -5752,7 +5716,7 @@ int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, in
   L->identity_slots = 1;
   for (int j = 0; j < N; ++j) L->identity_slots &= slots[j] == j;
   L->lm_restrict = 1;   // the admission's step runs over the new rows alone
-  for (int j = 0; j < N; ++j) L->lm_restrict &= L->slot_allow[slots[j]];
+  for (int j = 0; j < N; ++j) L->lm_restrict &= (L->slot_feat[slots[j]] & F_ALLOW) != 0;
   if ((rc = launch_embed(L, L->rows, N, st)) || (rc = launch_step(L, N, st))) { L->B = oldB; L->lm_restrict = 0; return rc; }
   std::vector<RowDesc> fresh;
   if ((rc = session_live_rows(L, fresh, st))) return rc;
@@ -5763,6 +5727,38 @@ int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, in
     slots_out[j] = slots[j];
   }
   return session_set_rows(L, live, st);
+}
+
+// The exported admissions: each is the next one with null for what it does not take (include/sparkmi.h).
+int smi_llm_admit(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, int32_t* slots_out, void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max}, slots_out, (hipStream_t)stream);
+}
+int smi_llm_admit_sampled(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
+                          int32_t* slots_out, void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max, nullptr, params}, slots_out, (hipStream_t)stream);
+}
+int smi_llm_admit_penalized(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
+                            const smi_penalty_params* pens, int32_t* slots_out, void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max, nullptr, params, pens}, slots_out, (hipStream_t)stream);
+}
+int smi_llm_admit_logprobs(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const smi_sample_params* params,
+                           const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out, void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max, nullptr, params, pens, want_lp}, slots_out, (hipStream_t)stream);
+}
+int smi_llm_admit_forked(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
+                         const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp, int32_t* slots_out,
+                         void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max, n_ret, params, pens, want_lp}, slots_out, (hipStream_t)stream);
+}
+int smi_llm_admit_constrained(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
+                              const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
+                              const smi_allow_params* allow, int32_t* slots_out, void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max, n_ret, params, pens, want_lp, allow}, slots_out, (hipStream_t)stream);
+}
+int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
+                         const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
+                         const smi_allow_params* allow, const smi_seq_params* seq, int32_t* slots_out, void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max, n_ret, params, pens, want_lp, allow, seq}, slots_out, (hipStream_t)stream);
 }
 
 int smi_llm_retire(smi_llm* L, int slot, void* stream) {
@@ -5777,11 +5773,7 @@ int smi_llm_retire(smi_llm* L, int slot, void* stream) {
     if (live[i].slot == slot) { live.erase(live.begin() + (long)i); break; }
   L->slot_busy[slot] = 0;
   L->slot_len[slot] = 0;
-  L->slot_samp[slot] = 0;
-  L->slot_pen[slot] = 0;
-  L->slot_lp[slot] = 0;   // (Ctl::lp stays: the slot's log-probabilities stay readable until it is reused)
-  L->slot_allow[slot] = 0;
-  L->slot_bias[slot] = 0; L->slot_stop[slot] = 0;
+  slot_clear(L, slot);
   if (L->paged) pages_release(L, slot);   // its pages go back to the pool (stale table entries are never read: no live row names the slot)
   if ((rc = allow_tiles_upload(L, st))) return rc;
   return session_set_rows(L, live, st);
@@ -5807,11 +5799,7 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
   for (int i = 0; i < n; ++i) {
     L->slot_busy[slots[i]] = 0;
     L->slot_len[slots[i]] = 0;
-    L->slot_samp[slots[i]] = 0;
-    L->slot_pen[slots[i]] = 0;
-    L->slot_lp[slots[i]] = 0;
-    L->slot_allow[slots[i]] = 0;
-    L->slot_bias[slots[i]] = 0; L->slot_stop[slots[i]] = 0;
+    slot_clear(L, slots[i]);
     if (L->paged) pages_release(L, slots[i]);
   }
   L->live_order = keep;
@@ -5819,7 +5807,7 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
   L->identity_slots = 1;
   for (int b = 0; b < L->B; ++b) L->identity_slots &= keep[b] == b;
   L->lm_restrict = L->B > 0;
-  for (int b = 0; b < L->B; ++b) L->lm_restrict &= L->slot_allow[keep[b]];
+  for (int b = 0; b < L->B; ++b) L->lm_restrict &= (L->slot_feat[keep[b]] & F_ALLOW) != 0;
   { const int rct = allow_tiles_upload(L, st); if (rct) return rct; }
   L->graph = nullptr;
   if (L->B == 0) return SMI_OK;
@@ -5921,6 +5909,25 @@ int smi_llm_slot_tokens(smi_llm* L, int slot, int64_t* out, int cap, int32_t* n_
   return SMI_OK;
 }
 
+// K back-to-back decode steps over the live rows, captured on a stream of its own and instantiated: *out, or null when the
+// capture or the instantiation failed (the runtime's error state is cleared either way).
+static int capture_steps(smi_llm* L, int K, hipGraphExec_t* out) {
+  *out = nullptr;
+  hipStream_t cs;
+  SMI_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+  hipGraph_t g = nullptr;
+  if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    int rc = SMI_OK;
+    for (int k = 0; k < K && rc == SMI_OK; ++k) rc = launch_step(L, L->B, cs);
+    const hipError_t e = hipStreamEndCapture(cs, &g);
+    if (rc == SMI_OK && e == hipSuccess && g && hipGraphInstantiate(out, g, nullptr, nullptr, 0) != hipSuccess) *out = nullptr;
+    if (g) (void)hipGraphDestroy(g);
+  }
+  (void)hipStreamDestroy(cs);
+  (void)hipGetLastError();
+  return SMI_OK;
+}
+
 int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
   SMI_REQUIRE(L, "smi_llm_decode: null handle");
   if (!L->started) { smi_set_error("smi_llm_decode before smi_llm_prefill"); return SMI_ESTATE; }
@@ -5959,68 +5966,41 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
     L->attn_seg = segs_for(bound);
     if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
   }
-  const int samp = samp_any(L) ? 1 : 0, pen = pen_any(L) ? 1 : 0, lpb = lp_any(L) ? 1 : 0, alw = allow_bits(L), sqb = seq_bits(L);
-  if (L->cfg.use_graph && n_steps > 0 && (!L->graph || L->graph_B != L->B || L->graph_seg != L->attn_seg || L->graph_ident != L->identity_slots ||
-                                          L->graph_samp != samp || L->graph_pen != pen || L->graph_lp != lpb || L->graph_allow != alw || L->graph_seq != sqb)) {
-    const uint64_t key = graph_key(L, samp, pen, lpb, 0);
-    auto hit = L->graph_cache.find(key);
-    L->graph = hit != L->graph_cache.end() ? hit->second : nullptr;
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw; L->graph_seq = sqb;
-  }
-  if (L->cfg.use_graph && n_steps > 0 && !L->graph) {
-    const uint64_t key = graph_key(L, samp, pen, lpb, 0);
-    if (L->graph_cache.size() >= 192) graphs_flush(L);
-    hipStream_t cs;
-    SMI_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-      rc = launch_step(L, L->B, cs);
-      hipError_t e2 = hipStreamEndCapture(cs, &g);
-      if (rc == SMI_OK && e2 == hipSuccess && g) {
-        if (hipGraphInstantiate(&L->graph, g, nullptr, nullptr, 0) != hipSuccess) L->graph = nullptr;
-      }
-      if (g) (void)hipGraphDestroy(g);
+  const unsigned feat = step_feat(L);
+  if (L->cfg.use_graph && n_steps > 0) {
+    const uint64_t key = graph_key(L, feat, 0);
+    if (!L->graph || L->graph_id != key) {
+      auto hit = L->graph_cache.find(key);
+      L->graph = hit != L->graph_cache.end() ? hit->second : nullptr;
+      L->graph_id = key;
     }
-    (void)hipStreamDestroy(cs);
-    (void)hipGetLastError();
-    L->graph_B = L->B; L->graph_seg = L->attn_seg; L->graph_ident = L->identity_slots; L->graph_samp = samp; L->graph_pen = pen; L->graph_lp = lpb; L->graph_allow = alw; L->graph_seq = sqb;
-    if (!L->graph) { smi_set_error("hipGraph capture of the decode step failed"); return SMI_EHIP; }
-    L->graph_cache[key] = L->graph;
+    if (!L->graph) {
+      if (L->graph_cache.size() >= 192) graphs_flush(L);
+      if ((rc = capture_steps(L, 1, &L->graph))) return rc;
+      if (!L->graph) { smi_set_error("hipGraph capture of the decode step failed"); return SMI_EHIP; }
+      L->graph_cache[key] = L->graph;
+    }
   }
   // Several steps per replay (SPARKMI_GRAPH_STEPS = K, default 8; 1: off): a step needs nothing from the host, so K of them are
   // captured back to back into one graph; the call replays it n_steps / K times and the one-step graph for the rest.  One replay
   // boundary costs ~5 us that a kernel boundary inside a graph does not: graph step at one row 548.6 -> 544.5 us (K = 4 .. 25
-  // alike; profiles/r03_graph_steps.txt).  The K-step graph of a (rows, segments) key is only built by a call long enough to
-  // replay it twice (a capture of 8 x 98 nodes is not free; short serving strides keep to the one-step graph).
+  // alike; profiles/r03_graph_steps.txt).  The K-step graph of a key is only built by a call long enough to replay it twice (a
+  // capture of 8 x 98 nodes is not free; short serving strides keep to the one-step graph); a failed capture leaves the call to
+  // the one-step graph.
   int s0 = 0;
   if (L->cfg.use_graph && L->graph_steps > 1 && n_steps >= L->graph_steps) {
     const int K = L->graph_steps;
-    const uint64_t keyk = graph_key(L, samp, pen, lpb, K);
+    const uint64_t keyk = graph_key(L, feat, K);
     hipGraphExec_t gk = nullptr;
     auto hit = L->graph_cache.find(keyk);
     if (hit != L->graph_cache.end()) gk = hit->second;
     else if (n_steps >= 2 * K && L->graph_cache.size() < 192) {
-      hipStream_t cs;
-      SMI_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-      if (e == hipSuccess) {
-        rc = SMI_OK;
-        for (int k = 0; k < K && rc == SMI_OK; ++k) rc = launch_step(L, L->B, cs);
-        hipError_t e2 = hipStreamEndCapture(cs, &g);
-        if (rc == SMI_OK && e2 == hipSuccess && g && hipGraphInstantiate(&gk, g, nullptr, nullptr, 0) != hipSuccess) gk = nullptr;
-        if (g) (void)hipGraphDestroy(g);
-      }
-      (void)hipStreamDestroy(cs);
-      (void)hipGetLastError();
+      if ((rc = capture_steps(L, K, &gk))) return rc;
       if (gk) L->graph_cache[keyk] = gk;
     }
-    if (gk) {
-      for (; s0 + K <= n_steps; s0 += K) {
-        SMI_HIP(hipGraphLaunch(gk, st));
-        L->graph_last[gk] = st;
-      }
+    for (; gk && s0 + K <= n_steps; s0 += K) {
+      SMI_HIP(hipGraphLaunch(gk, st));
+      L->graph_last[gk] = st;
     }
   }
   for (int s = s0; s < n_steps; ++s) {
@@ -6490,11 +6470,9 @@ int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint6
   SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
   SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
-  SampleP sp;
-  sp.logits = L->logits; sp.V = V; sp.top_k = L->top_k; sp.inv_temp = 1.0f / L->temperature;
-  sp.top_p = L->top_p; sp.hs = 1; sp.ctl = L->ctl; sp.rows = L->rows; sp.tok = L->tok;
-  sp.pval = use_bound ? L->pval : nullptr; sp.nblk = nblk;
-  sp.cand_v = L->cand_v; sp.cand_i = L->cand_i; sp.cand_n = L->cand_n;
+  SampleP sp = sample_params(L, n_rows);
+  sp.hs = 1;
+  if (!use_bound) sp.pval = nullptr;
   hipLaunchKernelGGL(k_sample_scan, dim3(kScanBlocks, n_rows), dim3(256), 0, 0, sp);
   SMI_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sample, dim3(n_rows), dim3(1024), 0, 0, sp);
@@ -6527,15 +6505,13 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
     rows[m] = RowDesc{m, 0, 0, emitted_host[m]};
     L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: the kernel writes its processed logits back)
     PenRec& r = L->hctl.pen[m];
-    r.rep = pens[m].repetition_penalty; r.pres = pens[m].presence_penalty; r.freq = pens[m].frequency_penalty;
-    r.min_new = pens[m].min_new_tokens; r.prompt = pens[m].penalize_prompt; r.on = 1;   // a neutral record too: the identity
+    r = pen_record(&pens[m]);
+    if (!r.on) { r.rep = 1.f; r.prompt = pens[m].penalize_prompt; r.on = 1; }   // a neutral record runs too: as the identity
   }
   SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
-  PenP pp;
-  pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
-  pp.V = (int)V; pp.nblk = nblk; pp.per = pen_set_ids((int)V, nblk); pp.hs = 0;
-  pp.seq = nullptr; pp.ghist = L->hist; pp.max_steps = L->max_steps;
+  PenP pp = pen_params(L, n_rows);
+  pp.hs = 0;
   hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());
@@ -6607,14 +6583,9 @@ int smi_llm_debug_logprob(smi_llm* L, const float* logits_host, int n_rows, cons
   lp.hs = 0;
   hipLaunchKernelGGL(k_logprob, dim3(kLpBlocks, n_rows), dim3(256), 0, 0, lp);
   SMI_LAUNCH_CHECK();
-  FinP f;
-  f.tok = L->tok; f.hs = 0; f.phist = nullptr;
-  f.lp = L->lp; f.lp_part = L->lp_part; f.lp_rowc = L->lp_rowc; f.logits = L->logits;
-  f.pval = L->pval; f.pidx = L->pidx; f.M = n_rows; f.KT = L->KTh; f.V = V; f.nblk = nblk;
-  f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
-  f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
-  f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
-  f.seq = nullptr;
+  FinP f = fin_params(L, n_rows);
+  f.tok = L->tok; f.hs = 0;
+  f.lp = L->lp; f.lp_part = L->lp_part; f.lp_rowc = L->lp_rowc;
   hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());
@@ -6686,20 +6657,12 @@ int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, cons
   SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
   SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
-  PenP pp;
-  pp.logits = L->logits; pp.hist = L->phist; pp.ctl = L->ctl; pp.rows = L->rows; pp.pval = L->pval; pp.pidx = L->pidx;
-  pp.V = V; pp.nblk = nblk; pp.per = per; pp.hs = 0;
-  pp.seq = L->seq; pp.ghist = L->hist; pp.max_steps = L->max_steps;
+  PenP pp = pen_params(L, n_rows);
+  pp.hs = 0; pp.seq = L->seq;
   hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
   SMI_LAUNCH_CHECK();
-  FinP f;
-  f.tok = nullptr; f.hs = 0; f.phist = nullptr;
-  f.lp = nullptr; f.lp_part = nullptr; f.lp_rowc = nullptr; f.logits = L->logits;
-  f.pval = L->pval; f.pidx = L->pidx; f.M = n_rows; f.KT = L->KTh; f.V = V; f.nblk = nblk;
-  f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
-  f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
-  f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
-  f.seq = L->seq;
+  FinP f = fin_params(L, n_rows);
+  f.hs = 0; f.seq = L->seq;
   hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());

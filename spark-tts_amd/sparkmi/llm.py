@@ -529,108 +529,46 @@ class SparkLLM:
 
     def admit(self, prompts: Sequence[Sequence[int]], sampling: Optional[Sequence[Optional[Mapping]]] = None,
               n_return: Optional[Sequence[int]] = None) -> List[int]:
-        """Prefill new prompts into free KV slots (first token emitted); returns their slot ids.  ``sampling``: one dict
-        (``SAMPLING_KEYS``, ``PENALTY_KEYS``) or None per prompt -- that sequence's own token selection (``sampling_records``)
-        and logits penalties (``penalty_records``); None everywhere (the default): every sequence follows ``set_sampling``,
-        unpenalised.  A request with any non-neutral penalty goes through ``smi_llm_admit_penalized``; an admission in which
-        some request carries ``return_log_probs`` (``LOGPROB_KEYS``, a bool) through ``smi_llm_admit_logprobs``, and the
-        flagged sequences' log-probabilities are read with ``slots_logprobs``.  An admission in which some request carries
-        ``allowed_token_ids`` (``ALLOW_KEY``: an iterable of ids; ``allow_records``) goes through ``smi_llm_admit_constrained``:
-        that sequence emits only ids of its set (eos ids are not added to it).  An admission in which some request carries
-        ``sequence_bias`` / ``bad_words_ids`` / ``stop_sequences`` (``SEQ_KEYS``; ``seq_records``) goes through
-        ``smi_llm_admit_biased``.
-        ``n_return``: one int >= 1 per prompt -- that many takes of the prompt, its prompt prefilled once
-        (``smi_llm_admit_forked``); ``sampling`` stays one dict per prompt and is expanded per take (``expand_takes``).  The
-        result is then the flat, prompt-major slot list; None (the default) keeps today's route and bits."""
+        """Prefill new prompts into free KV slots (first token emitted); returns their slot ids.  ``sampling``: one dict or
+        None per prompt; None everywhere (the default): every sequence follows ``set_sampling`` and carries no record.  The
+        keys of a dict make up to five records for its sequence: its own token selection (``SAMPLING_KEYS``;
+        ``sampling_records``), logits penalties (``PENALTY_KEYS``; ``penalty_records``), ``return_log_probs`` (``LOGPROB_KEYS``,
+        a bool; ``logprob_flags`` -- the flagged sequences' log-probabilities are read with ``slots_logprobs``),
+        ``allowed_token_ids`` (``ALLOW_KEY``: an iterable of ids; ``allow_records`` -- the sequence emits only ids of its set,
+        eos ids are not added to it) and ``sequence_bias`` / ``bad_words_ids`` / ``stop_sequences`` (``SEQ_KEYS``;
+        ``seq_records``).  ``n_return``: one int >= 1 per prompt -- that many takes of the prompt, its prompt prefilled once;
+        ``sampling`` stays one dict per prompt and is expanded per take (``expand_takes``), and the result is the flat,
+        prompt-major slot list.
+        Every admission is one ``smi_llm_admit_biased`` call.  A kind of record that no request asks for is passed as NULL, and
+        so is ``n_return`` None: by the contract of include/sparkmi.h that is exactly the narrower entry point
+        (``smi_llm_admit`` when all are NULL), with its route and bits."""
+        n = N = len(prompts)
+        takes, nret = sampling, None
         if n_return is not None:
-            return self._admit_forked(prompts, sampling, n_return)
-        n = len(prompts)
+            n_return = [num_returns(k, f"n_return[{b}]") for b, k in enumerate(n_return)]
+            if len(n_return) != n or n == 0:
+                raise ValueError(f"n_return: {len(n_return)} entries for {n} prompts")
+            N = sum(n_return)
+            if N > self.max_slots:
+                raise ValueError(f"{N} takes > max_slots={self.max_slots}")
+            takes = expand_takes(sampling, n_return)
+            nret = np.asarray(n_return, dtype=np.int32)
         lens = np.array([len(p) for p in prompts], dtype=np.int32)
         pmax = int(lens.max())
         ids = np.zeros((n, pmax), dtype=np.int64)
         for b, p in enumerate(prompts):
             ids[b, : len(p)] = np.asarray(p, dtype=np.int64)
-        slots = np.zeros(n, dtype=np.int32)
-        recs = sampling_records(sampling, n, self._sampling)
-        pens = penalty_records(sampling, n)
-        flags = logprob_flags(sampling, n)
-        allow = allow_records(sampling, n, self.cfg.vocab_size)
-        seqs = seq_records(sampling, n, self.cfg.vocab_size, getattr(self, "_session_eos", ()))
-        if seqs is not None:
-            self._lib.check(self._lib.smi_llm_admit_biased(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                      lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, None, recs, pens,
-                                                      None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      allow, seqs, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                            "smi_llm_admit_biased")
-        elif allow is not None:
-            self._lib.check(self._lib.smi_llm_admit_constrained(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                           lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, None, recs, pens,
-                                                           None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                           allow, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                            "smi_llm_admit_constrained")
-        elif flags is not None:
-            self._lib.check(self._lib.smi_llm_admit_logprobs(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                        lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs, pens,
-                                                        flags.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                        slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                            "smi_llm_admit_logprobs")
-        elif pens is not None:
-            self._lib.check(self._lib.smi_llm_admit_penalized(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                         lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs, pens,
-                                                         slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                            "smi_llm_admit_penalized")
-        elif recs is None:
-            self._lib.check(self._lib.smi_llm_admit(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               n, pmax, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_admit")
-        else:
-            self._lib.check(self._lib.smi_llm_admit_sampled(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                       lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax, recs,
-                                                       slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()), "smi_llm_admit_sampled")
-        return slots.tolist()
-
-    def _admit_forked(self, prompts, sampling, n_return) -> List[int]:
-        n_return = [num_returns(k, f"n_return[{b}]") for b, k in enumerate(n_return)]
-        n = len(prompts)
-        if len(n_return) != n or n == 0:
-            raise ValueError(f"n_return: {len(n_return)} entries for {n} prompts")
-        N = sum(n_return)
-        if N > self.max_slots:
-            raise ValueError(f"{N} takes > max_slots={self.max_slots}")
-        takes = expand_takes(sampling, n_return)
         recs = sampling_records(takes, N, self._sampling)
         pens = penalty_records(takes, N)
         flags = logprob_flags(takes, N)
         allow = allow_records(takes, N, self.cfg.vocab_size)
         seqs = seq_records(takes, N, self.cfg.vocab_size, getattr(self, "_session_eos", ()))
-        lens = np.array([len(p) for p in prompts], dtype=np.int32)
-        pmax = int(lens.max())
-        ids = np.zeros((n, pmax), dtype=np.int64)
-        for b, p in enumerate(prompts):
-            ids[b, : len(p)] = np.asarray(p, dtype=np.int64)
-        nret = np.asarray(n_return, dtype=np.int32)
         slots = np.zeros(N, dtype=np.int32)
-        if seqs is not None:
-            self._lib.check(self._lib.smi_llm_admit_biased(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                      lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
-                                                      nret.ctypes.data_as(C.POINTER(C.c_int32)), recs, pens,
-                                                      None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      allow, seqs, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                            "smi_llm_admit_biased")
-            return slots.tolist()
-        if allow is not None:
-            self._lib.check(self._lib.smi_llm_admit_constrained(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                           lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
-                                                           nret.ctypes.data_as(C.POINTER(C.c_int32)), recs, pens,
-                                                           None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                           allow, slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                            "smi_llm_admit_constrained")
-            return slots.tolist()
-        self._lib.check(self._lib.smi_llm_admit_forked(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                      lens.ctypes.data_as(C.POINTER(C.c_int32)), n, pmax,
-                                                      nret.ctypes.data_as(C.POINTER(C.c_int32)), recs, pens,
-                                                      None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      slots.ctypes.data_as(C.POINTER(C.c_int32)), self._stream()),
-                        "smi_llm_admit_forked")
+        i32 = C.POINTER(C.c_int32)
+        self._lib.check(self._lib.smi_llm_admit_biased(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), lens.ctypes.data_as(i32), n, pmax,
+                                                       None if nret is None else nret.ctypes.data_as(i32), recs, pens,
+                                                       None if flags is None else flags.ctypes.data_as(i32), allow, seqs,
+                                                       slots.ctypes.data_as(i32), self._stream()), "smi_llm_admit")
         return slots.tolist()
 
     def retire(self, slot: int) -> None:
