@@ -3687,6 +3687,14 @@ Layout make_layout(const smi_llm_cfg* c) {
   return L;
 }
 
+// The activation buffers of one pass over the layers, for some number of rows (gemm_operands / attn_operands name them to the
+// kernels).
+struct Work {
+  float *h, *q;                             // residual rows [rows][H]; QKV's query output [rows][Q]
+  unsigned char *xs_h, *xs_attn, *xs_act;   // GEMM operands as exact bf16 triples ([K/32][3][4][M][16 B])
+  float* ss;                                // [rows][NTh * 4] partial sums of squares of h (RMSNorm), one per 4 columns
+};
+
 }  // namespace
 
 struct smi_llm {
@@ -3695,11 +3703,8 @@ struct smi_llm {
   const unsigned char* arena;
   int H, Q, KV, I, KTh, KTq, KTi, NTqkv, NTh, NTgu, NTlm;
   // device scratch
-  float *h, *qbuf;
-  unsigned char *xs_h, *xs_attn, *xs_act;   // GEMM operands as exact bf16 triples ([K/32][3][4][M][16 B])
-  float* sspart;       // [kMaxRows][NTh * 4] partial sums of squares of h (RMSNorm), one per 4 columns
-  // prefill workspace for up to big_rows rows at once (allocated at the first multi-chunk prefill)
-  float *bh, *bq; unsigned char *bxs_h, *bxs_attn, *bxs_act; float* bss; int big_rows;
+  Work dec;            // the decode rows' workspace (kMaxRows rows)
+  Work big; int big_rows;   // prefill workspace for up to big_rows rows at once (allocated at the first multi-chunk prefill)
   float4* pslab; size_t pslab_bytes;   // k_pgemm split-K partial sums (prompt rows passes of up to kPgSplitRows rows)
   int pf_long;          // prompt rows (len - 1) from which a sequence's prompt runs through the prefill-GEMM family (default 65)
   int pg_split_rows;    // passes of up to this many rows take the few-row prefill GEMM shapes / split-K (kPgSplitRows; SPARKMI_PG_SPLIT_ROWS: A/B, same bits)
@@ -3730,16 +3735,16 @@ struct smi_llm {
   std::vector<int32_t> free_pages;
   std::vector<int32_t> page_ref;   // [kv_pages] slots whose table rows hold the page (> 1: shared by forked takes)
   int slot_pages[kMaxRows];     // pages a slot holds
-  int plen[kMaxRows];           // plain (non-session) generation: prompt length per slot
   Ctl hctl; Ctl* ctl;   // host copy / device block of the generation controls
   int admit_seq;        // sequences admitted so far in this generation / session (sampler stream ids)
-  // continuous batching (smi_llm_session_*): live rows map to arbitrary KV slots
+  // One bookkeeping for plain generation and sessions: a sequence sits in a KV slot (slot_busy / slot_len) and the live rows map
+  // to slots through live_order.  smi_llm_prefill is slots 0 .. B-1 in order; in a session (continuous batching) admissions and
+  // retirements change the set, so rows map to arbitrary slots.  `session` only gates admit / retire.
   int session, identity_slots;
-  std::vector<int> live_order;   // session: the KV slot of every live row, in row order (what the device row list holds)
+  std::vector<int> live_order;   // the KV slot of every live row, in row order (what the device row list holds)
   int attn_seg;                        // context segments per (head, row) of the attention launches being issued (1 = unsplit)
   float* apart; size_t apart_floats;   // segment partials [rows][heads][attn_seg][66]
   int slot_busy[kMaxRows], slot_len[kMaxRows];      // host: slot in use; prompt length + tokens emitted (cache positions used)
-  int max_len, steps_launched;  // host-side bound on cache positions in use
   // sampling state (smi_llm_set_sampling)
   int do_sample, top_k; float temperature, top_p; unsigned long long seed;
   // host: what the record set of the sequence in each slot (live or being admitted) asks of a step, F_* bits: its sampling record
@@ -4171,7 +4176,7 @@ int eng_launch(smi_llm* L, hipStream_t st) {
   p.off_ln1 = L->lay.off[SMI_LLM_LN1]; p.off_bqkv = L->lay.off[SMI_LLM_BQKV]; p.off_ln2 = L->lay.off[SMI_LLM_LN2];
   p.final_norm = (const float*)(L->arena + L->lay.off[SMI_LLM_FINAL_NORM]);
   p.rope = (const float2*)(L->arena + L->lay.off[SMI_LLM_ROPE]);
-  p.rows = L->rows; p.h = L->h; p.ss_in = L->sspart; p.xs_out = L->xs_h; p.ss_out = L->sspart;
+  p.rows = L->rows; p.h = L->dec.h; p.ss_in = L->dec.ss; p.xs_out = L->dec.xs_h; p.ss_out = L->dec.ss;
   p.kcache = (uint16_t*)L->kcache; p.vcache = (uint16_t*)L->vcache; p.kv_layer_elems = L->kv_layer_elems;
   p.gran = E.gran; p.serial = E.words; p.err = E.words + 4; p.arrive = E.words + 8;
   p.timeout_ticks = E.timeout_ticks;
@@ -4257,8 +4262,8 @@ FinP fin_params(const smi_llm* L, int M) {
   f.lp = nullptr; f.lp_part = nullptr; f.lp_rowc = nullptr; f.logits = L->logits;
   f.pval = L->pval; f.pidx = L->pidx; f.M = M; f.KT = L->KTh; f.V = L->cfg.vocab_size; f.nblk = lm_blocks_for(L, M);
   f.rows = L->rows; f.hist = L->hist; f.count = L->count; f.finished = L->finished; f.step = L->step;
-  f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->h; f.max_steps = L->max_steps;
-  f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->xs_h; f.sspart = L->sspart; f.npart = L->NTh * 4; f.exact = L->exact;
+  f.ctl = L->ctl; f.Wlm = (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0); f.h = L->dec.h; f.max_steps = L->max_steps;
+  f.gamma0 = (const float*)sec(L, SMI_LLM_LN1, 0); f.xs = L->dec.xs_h; f.sspart = L->dec.ss; f.npart = L->NTh * 4; f.exact = L->exact;
   f.seq = nullptr;
   return f;
 }
@@ -4366,50 +4371,73 @@ int launch_gemm_x(const smi_llm* L, const GemmP& p, hipStream_t st) {
   return SMI_OK;
 }
 
+// The operands of GEMM kernel `which` (KQKV, KO, KGU, KD, KLM) of `layer` for M rows in workspace w: what follows from the model
+// and the workspace alone.  npart: RMSNorm partials per row as the producer of the kernel's operand left them in w.ss.  What
+// belongs to one launch path is that caller's: prefetch descriptors, the fused o_proj's fields, Yin, wperm (the bf16 tile order
+// of W_down: the exact-weights path reads fp32 [N][K]), kseg / slab, stamps, the restricted lm_head's lists and lm_head's Y.
+GemmP gemm_operands(const smi_llm* L, int which, int layer, const Work& w, const RowDesc* rows, int M, int npart) {
+  const smi_llm_cfg& c = L->cfg;
+  GemmP p;
+  memset(&p, 0, sizeof(p));
+  p.M = M; p.rows = rows; p.eps = c.rms_eps; p.sspart = w.ss; p.npart = npart;
+  switch (which) {
+    case KQKV:
+      p.W = (const uint4*)sec(L, SMI_LLM_WQKV, layer); p.NT = L->NTqkv; p.KT = L->KTh; p.XS = w.xs_h;
+      p.Y = w.q; p.bias = (const float*)sec(L, SMI_LLM_BQKV, layer); p.rope = (const float2*)sec(L, SMI_LLM_ROPE, 0);
+      p.kcache = kv_layer(L, L->kcache, layer); p.vcache = kv_layer(L, L->vcache, layer);
+      p.q_dim = L->Q; p.kv_dim = L->KV; p.n_kv = c.num_kv_heads; p.max_pos = c.max_positions; p.km = kv_map(L);
+      break;
+    case KO:   // h += Wo attn; emits the post-attention norm's operand
+      p.W = (const uint4*)sec(L, SMI_LLM_WO, layer); p.NT = L->NTh; p.KT = L->KTq; p.XS = w.xs_attn; p.Y = w.h;
+      p.XSout = w.xs_h; p.gamma_next = (const float*)sec(L, SMI_LLM_LN2, layer); p.ssout = w.ss;
+      break;
+    case KGU:
+      p.W = (const uint4*)sec(L, SMI_LLM_WGU, layer); p.NT = L->NTgu; p.KT = L->KTh; p.XS = w.xs_h; p.XSout = w.xs_act;
+      break;
+    case KD:   // h += Wd act; emits the next layer's input-norm operand (or the final norm's)
+      p.W = (const uint4*)sec(L, SMI_LLM_WD, layer); p.NT = L->NTh; p.KT = L->KTi; p.XS = w.xs_act; p.Y = w.h;
+      p.XSout = w.xs_h; p.ssout = w.ss;
+      p.gamma_next = layer + 1 < c.num_layers ? (const float*)sec(L, SMI_LLM_LN1, layer + 1) : (const float*)sec(L, SMI_LLM_FINAL_NORM, 0);
+      break;
+    case KLM:
+      p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh; p.XS = w.xs_h;
+      p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
+      break;
+  }
+  return p;
+}
+
+// The model-derived part of the attention's arguments for M rows in workspace w (the fused o_proj's fields, slot_is_row and the
+// prefetch descriptor are the decode caller's).
+AttnP attn_operands(const smi_llm* L, int layer, const Work& w, const RowDesc* rows, int M) {
+  const smi_llm_cfg& c = L->cfg;
+  AttnP a;
+  memset(&a, 0, sizeof(a));
+  a.q = w.q; a.kcache = kv_layer(L, L->kcache, layer); a.vcache = kv_layer(L, L->vcache, layer);
+  a.rows = rows; a.xs_out = w.xs_attn; a.M = M; a.q_dim = L->Q; a.n_kv = c.num_kv_heads;
+  a.group = c.num_heads / c.num_kv_heads; a.max_pos = c.max_positions; a.n_heads = c.num_heads; a.km = kv_map(L);
+  return a;
+}
+
 int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, float* logits, hipStream_t st) {
   const smi_llm_cfg& c = L->cfg;
   const bool fused = fuse_o_now(L, rows, M);
-  GemmP p;
-  memset(&p, 0, sizeof(p));
-  p.M = M; p.rows = rows; p.eps = c.rms_eps; p.sspart = L->sspart; p.npart = L->NTh * 4;
-  if (L->exact && which != KATTN && which != KFIN) {
+  GemmP p = gemm_operands(L, which, layer, L->dec, rows, M, L->NTh * 4);
+  if (which == KLM) p.Y = logits ? logits : (logits_needed(L, step_feat(L)) ? L->logits : nullptr);
+  if (L->exact) {
     // verification mode: same operands, scalars and epilogues, fp32 weights, one exact fp32 FMA chain per output (k_gemm_x)
     switch (which) {
-      case KQKV:
-        p.W = (const uint4*)sec(L, SMI_LLM_WQKV, layer); p.NT = L->NTqkv; p.KT = L->KTh; p.XS = L->xs_h;
-        p.Y = L->qbuf; p.bias = (const float*)sec(L, SMI_LLM_BQKV, layer); p.rope = (const float2*)sec(L, SMI_LLM_ROPE, 0);
-        p.kcache = kv_layer(L, L->kcache, layer); p.vcache = kv_layer(L, L->vcache, layer);
-        p.q_dim = L->Q; p.kv_dim = L->KV; p.n_kv = c.num_kv_heads; p.max_pos = c.max_positions; p.km = kv_map(L);
-        return launch_gemm_x<PRO_NORM, EPI_QKV>(L, p, st);
-      case KO:
-        p.W = (const uint4*)sec(L, SMI_LLM_WO, layer); p.NT = L->NTh; p.KT = L->KTq; p.XS = L->xs_attn; p.Y = L->h;
-        p.XSout = L->xs_h; p.gamma_next = (const float*)sec(L, SMI_LLM_LN2, layer); p.ssout = L->sspart;
-        return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
-      case KGU:
-        p.W = (const uint4*)sec(L, SMI_LLM_WGU, layer); p.NT = L->NTgu; p.KT = L->KTh; p.XS = L->xs_h; p.XSout = L->xs_act;
-        return launch_gemm_x<PRO_NORM, EPI_SWIGLU>(L, p, st);
-      case KD:
-        p.W = (const uint4*)sec(L, SMI_LLM_WD, layer); p.NT = L->NTh; p.KT = L->KTi; p.XS = L->xs_act; p.Y = L->h;
-        p.XSout = L->xs_h; p.ssout = L->sspart;
-        p.gamma_next = layer + 1 < c.num_layers ? (const float*)sec(L, SMI_LLM_LN1, layer + 1) : (const float*)sec(L, SMI_LLM_FINAL_NORM, 0);
-        return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
+      case KQKV: return launch_gemm_x<PRO_NORM, EPI_QKV>(L, p, st);
+      case KO: return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
+      case KGU: return launch_gemm_x<PRO_NORM, EPI_SWIGLU>(L, p, st);
+      case KD: return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
       case KLM:
-        p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh; p.XS = L->xs_h;
-        p.Y = logits ? logits : (logits_needed(L, step_feat(L)) ? L->logits : nullptr);
-        p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
         SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
         return launch_gemm_x<PRO_NORM, EPI_LM>(L, p, st);
     }
   }
   switch (which) {
     case KQKV:
-      p.W = (const uint4*)sec(L, SMI_LLM_WQKV, layer); p.NT = L->NTqkv; p.KT = L->KTh;
-      p.XS = L->xs_h;
-      p.Y = L->qbuf; p.bias = (const float*)sec(L, SMI_LLM_BQKV, layer);
-      p.rope = (const float2*)sec(L, SMI_LLM_ROPE, 0);
-      p.kcache = kv_layer(L, L->kcache, layer); p.vcache = kv_layer(L, L->vcache, layer);
-      p.q_dim = L->Q; p.kv_dim = L->KV; p.n_kv = c.num_kv_heads; p.max_pos = c.max_positions; p.km = kv_map(L);
-      // helpers: first half of this layer's gate_up slices (consumer block b reads weight tile row b)
       // helpers: the first pf_qkv_eighths / 8 of this layer's gate_up slices (consumer block b reads weight tile row b).  Measured
       // at one row, graph step, one box (profiles/r03_prefetch.txt): 8/8 600 us, 6/8 569, 4/8 564, 2/8 559 (default), none 566-571
       p.pf = PfDesc{sec(L, SMI_LLM_WGU, layer), L->KTh * 1024, L->NTgu, 0, ((L->NTgu + 7) / 8 * L->pf_qkv_eighths + 7) / 8};
@@ -4419,27 +4447,20 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         default: return launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 0>(L, p, st);   // measured best (profiles/README.md)
       }
     case KATTN: {
-      AttnP a;
-      memset(&a, 0, sizeof(a));
-      a.q = L->qbuf; a.kcache = kv_layer(L, L->kcache, layer); a.vcache = kv_layer(L, L->vcache, layer);
-      a.rows = rows; a.xs_out = L->xs_attn; a.M = M; a.q_dim = L->Q; a.n_kv = c.num_kv_heads;
-      a.group = c.num_heads / c.num_kv_heads; a.max_pos = c.max_positions; a.n_heads = c.num_heads; a.km = kv_map(L);
+      AttnP a = attn_operands(L, layer, L->dec, rows, M);
       a.slot_is_row = rows == L->rows && L->identity_slots;   // the live decode rows are (slot b, ...) in order (contiguous cache: slots contiguous; paged: through the page table)
       // helpers: second half of this layer's gate_up slices
       a.pf = PfDesc{sec(L, SMI_LLM_WGU, layer), L->KTh * 1024, L->NTgu, (L->NTgu / 8 + 1) / 2, (L->NTgu + 7) / 8};
       if (fused) { a.Wo = (const uint4*)sec(L, SMI_LLM_WO, layer); a.NTo = L->NTh; a.part_o = L->part_o; }
       if (fuse2_now(L, rows, M)) {
         a.Wo = (const uint4*)sec(L, SMI_LLM_WO, layer); a.NTo = L->NTh; a.part_o = L->part_o; a.cnt = L->fuse_cnt;
-        a.h = L->h; a.gamma_next = (const float*)sec(L, SMI_LLM_LN2, layer); a.xs_next = L->xs_h; a.ssout = L->sspart;
+        a.h = L->dec.h; a.gamma_next = (const float*)sec(L, SMI_LLM_LN2, layer); a.xs_next = L->dec.xs_h; a.ssout = L->dec.ss;
       }
       return c.kv_dtype ? launch_attn<1>(L, a, 1, st) : launch_attn<0>(L, a, 1, st);
     }
-    case KO:   // h += Wo attn; emits the post-attention norm's operand
+    case KO:
       if (fused) return SMI_OK;   // done by the attention kernel (per-head partials) and gate_up's prologue
       if (fuse2_now(L, rows, M)) return SMI_OK;   // done by the attention kernel (per-head partials + last-arriver head sum and epilogue)
-      p.W = (const uint4*)sec(L, SMI_LLM_WO, layer); p.NT = L->NTh; p.KT = L->KTq;
-      p.XS = L->xs_attn; p.Y = L->h;
-      p.XSout = L->xs_h; p.gamma_next = (const float*)sec(L, SMI_LLM_LN2, layer); p.ssout = L->sspart;
       // no helpers here: warming down_proj's 8.7 MB from o_proj (or from attention / gate_up) stretches the
       // producer by more than the consumer gains (measured, profiles/README.md), so down_proj stays cold
       switch (L->tune[1]) {
@@ -4452,10 +4473,8 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
           return launch_oproj(L, p, M, st);
       }
     case KGU:
-      p.W = (const uint4*)sec(L, SMI_LLM_WGU, layer); p.NT = L->NTgu; p.KT = L->KTh;
-      p.XS = L->xs_h; p.XSout = L->xs_act;
       if (fused) {
-        p.part_o = L->part_o; p.n_oheads = c.num_heads; p.hres = L->h; p.h2out = L->h2;
+        p.part_o = L->part_o; p.n_oheads = c.num_heads; p.hres = L->dec.h; p.h2out = L->h2;
         if (const char* e = smi_env("SPARKMI_FAKE_OHEADS")) p.n_oheads = atoi(e);   // TIMING ONLY (diagnostics build): gate_up reads that many partials -- wrong sums (profiles/r04_gate_up_two_tiles_and_fewer_partials.txt)
         if (L->pf_inline && layer + 1 < c.num_layers && L->NTqkv % 8 == 0) {   // SPARKMI_PF_INLINE=0: off (A/B)
           p.pf2_base = sec(L, SMI_LLM_WQKV, layer + 1); p.pf2_slice = L->KTh * 1024; p.pf2_nslices = L->NTqkv;
@@ -4471,13 +4490,9 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         default:   // 69 VGPRs (>= 6 waves per SIMD): all 608 blocks are resident at once, no second round (step 745 -> 705 us)
           return launch_gemm<1, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 2, 6>(L, p, st);
       }
-    case KD:   // h += Wd act; emits the next layer's input-norm operand (or the final norm's)
-      p.W = (const uint4*)sec(L, SMI_LLM_WD, layer); p.NT = L->NTh; p.KT = L->KTi; p.wperm = L->wd_parts;
-      p.XS = L->xs_act; p.Y = L->h;
+    case KD:
+      p.wperm = L->wd_parts;
       if (fused) p.Yin = L->h2;   // h + o_proj, left there by gate_up's block 0
-      p.XSout = L->xs_h; p.ssout = L->sspart;
-      p.gamma_next = layer + 1 < c.num_layers ? (const float*)sec(L, SMI_LLM_LN1, layer + 1)
-                                              : (const float*)sec(L, SMI_LLM_FINAL_NORM, 0);
       // helpers: the next layer's QKV slices (its o_proj slices ride along: same slice size, contiguous-ish)
       if (layer + 1 < c.num_layers) p.pf = PfDesc{sec(L, SMI_LLM_WQKV, layer + 1), L->KTh * 1024, L->NTqkv, 0, (L->NTqkv + 7) / 8};
       if (M >= L->dc_min && M <= kMaxRows && !L->tune[3] && !L->stamps_on && p.KT <= 160 && p.NT % 4 == 0)
@@ -4497,10 +4512,6 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       }
     case KLM: {
       const unsigned feat = step_feat(L);
-      p.W = (const uint4*)sec(L, SMI_LLM_LM_HEAD, 0); p.NT = L->NTlm; p.KT = L->KTh;
-      p.XS = L->xs_h;
-      p.Y = logits ? logits : (logits_needed(L, feat) ? L->logits : nullptr);
-      p.V = c.vocab_size; p.pval = L->pval; p.pidx = L->pidx;
       p.stamps = L->stamps_on ? L->stamps : nullptr;
       if (L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L, feat)) {   // every row constrained: only the union's tiles
         p.tlist = L->tlist; p.ctl = L->ctl;
@@ -4634,14 +4645,8 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
   const int nseg_o = (L->KTq + kseg_o - 1) / kseg_o, nseg_d = (L->KTi + kseg_d - 1) / kseg_d;
   int rc;
   for (int l = 0; l < c.num_layers; ++l) {
-    GemmP p;
-    memset(&p, 0, sizeof(p));
-    p.M = M; p.rows = rows; p.eps = c.rms_eps; p.sspart = L->bss; p.npart = np_from_d;
     // QKV
-    p.W = (const uint4*)sec(L, SMI_LLM_WQKV, l); p.NT = L->NTqkv; p.KT = L->KTh; p.XS = L->bxs_h;
-    p.Y = L->bq; p.bias = (const float*)sec(L, SMI_LLM_BQKV, l); p.rope = (const float2*)sec(L, SMI_LLM_ROPE, 0);
-    p.kcache = kv_layer(L, L->kcache, l); p.vcache = kv_layer(L, L->vcache, l);
-    p.q_dim = L->Q; p.kv_dim = L->KV; p.n_kv = c.num_kv_heads; p.max_pos = c.max_positions; p.km = kv_map(L);
+    const GemmP p = gemm_operands(L, KQKV, l, L->big, rows, M, np_from_d);
     if (gq) rc = launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV>(L, p, st);
     else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_QKV>(L, p, st);
     else if (few) rc = launch_pgemm<PRO_NORM, EPI_QKV, 2, 2, 6, 1, 0, 4>(L, p, st);
@@ -4649,11 +4654,7 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
     if (rc) return rc;
     if (l == c.num_layers - 1) break;
     // attention
-    AttnP a;
-    memset(&a, 0, sizeof(a));
-    a.q = L->bq; a.kcache = p.kcache; a.vcache = p.vcache; a.rows = rows; a.xs_out = L->bxs_attn; a.M = M;
-    a.q_dim = L->Q; a.n_kv = c.num_kv_heads; a.group = c.num_heads / c.num_kv_heads; a.max_pos = c.max_positions;
-    a.n_heads = c.num_heads; a.slot_is_row = 0; a.km = kv_map(L);
+    const AttnP a = attn_operands(L, l, L->big, rows, M);   // (slot_is_row = 0: prompt rows name their slot)
     if (L->tune2 & 1024) {   // SPARKMI_TUNE2 bit 1024: the decode attention kernel per prompt row (the path before k_attn_pf)
       if ((rc = c.kv_dtype ? launch_attn<1>(L, a, 0, st) : launch_attn<0>(L, a, 0, st))) return rc;
     } else {
@@ -4666,11 +4667,7 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
       SMI_LAUNCH_CHECK();
     }
     // o_proj
-    GemmP o;
-    memset(&o, 0, sizeof(o));
-    o.M = M; o.rows = rows; o.eps = c.rms_eps; o.sspart = L->bss; o.npart = np_from_d;
-    o.W = (const uint4*)sec(L, SMI_LLM_WO, l); o.NT = L->NTh; o.KT = L->KTq; o.XS = L->bxs_attn; o.Y = L->bh;
-    o.XSout = L->bxs_h; o.gamma_next = (const float*)sec(L, SMI_LLM_LN2, l); o.ssout = L->bss;
+    GemmP o = gemm_operands(L, KO, l, L->big, rows, M, np_from_d);
     o.kseg = kseg_o;
     if (go) rc = launch_oproj(L, o, M, st);
     else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, o, st);
@@ -4678,10 +4675,7 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
     else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, o, st);
     if (rc) return rc;
     // gate_up
-    GemmP g;
-    memset(&g, 0, sizeof(g));
-    g.M = M; g.rows = rows; g.eps = c.rms_eps; g.sspart = L->bss; g.npart = np_from_o;
-    g.W = (const uint4*)sec(L, SMI_LLM_WGU, l); g.NT = L->NTgu; g.KT = L->KTh; g.XS = L->bxs_h; g.XSout = L->bxs_act;
+    const GemmP g = gemm_operands(L, KGU, l, L->big, rows, M, np_from_o);
     if (gg) rc = launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 2>(L, g, st);
     else if (L->tune2 & 512) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU>(L, g, st);
     else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 4>(L, g, st);
@@ -4690,12 +4684,8 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
     else rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 2, 0, 1>(L, g, st);
     if (rc) return rc;
     // down
-    GemmP d;
-    memset(&d, 0, sizeof(d));
-    d.M = M; d.rows = rows; d.eps = c.rms_eps; d.sspart = L->bss; d.npart = np_from_o;
-    d.W = (const uint4*)sec(L, SMI_LLM_WD, l); d.NT = L->NTh; d.KT = L->KTi; d.XS = L->bxs_act; d.Y = L->bh; d.wperm = L->wd_parts;
-    d.XSout = L->bxs_h; d.ssout = L->bss; d.gamma_next = (const float*)sec(L, SMI_LLM_LN1, l + 1);
-    d.kseg = kseg_d;
+    GemmP d = gemm_operands(L, KD, l, L->big, rows, M, np_from_o);   // (never the last layer's: gamma_next is the next LN1)
+    d.wperm = L->wd_parts; d.kseg = kseg_d;
     if (gd) rc = launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID>(L, d, st);
     else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, d, st);
     else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, d, st, nseg_d);
@@ -4705,33 +4695,39 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
   return SMI_OK;
 }
 
+// A workspace for R rows, allocated in the struct's order (a failure leaves what it got: work_free / smi_llm_destroy release it).
+bool work_alloc(const smi_llm* L, Work& w, size_t R) {
+  return hipMalloc((void**)&w.h, R * L->H * 4) == hipSuccess && hipMalloc((void**)&w.q, R * L->Q * 4) == hipSuccess &&
+         hipMalloc((void**)&w.xs_h, R * L->H * 6) == hipSuccess && hipMalloc((void**)&w.xs_attn, R * L->Q * 6) == hipSuccess &&
+         hipMalloc((void**)&w.xs_act, R * L->I * 6) == hipSuccess && hipMalloc((void**)&w.ss, R * L->NTh * 4 * 4) == hipSuccess;
+}
+void work_free(Work& w) {
+  void* ptrs[] = {w.h, w.q, w.xs_h, w.xs_attn, w.xs_act, w.ss};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  w = Work{};
+}
+
 int ensure_big(smi_llm* L, int rows) {
   if (rows <= L->big_rows) return SMI_OK;
-  void* old[] = {L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab};
-  for (void* q : old)
-    if (q) (void)hipFree(q);
-  L->bh = L->bq = nullptr; L->bxs_h = L->bxs_attn = L->bxs_act = nullptr; L->bss = nullptr; L->big_rows = 0;
+  work_free(L->big);
+  L->big_rows = 0;
+  if (L->pslab) (void)hipFree(L->pslab);
   L->pslab = nullptr; L->pslab_bytes = 0;
-  const size_t R = (size_t)rows;
   {   // split-K partial sums: up to kPgSegD segments x NTh tiles x (min(rows, kPgSplitRows) / 16) m-tiles x 1 KiB
     const size_t mt = ((size_t)(rows < kPgSplitRows ? rows : kPgSplitRows) + 15) / 16;
     const size_t bytes = (size_t)16 * L->NTh * mt * 1024;
     if (hipMalloc((void**)&L->pslab, bytes) != hipSuccess) { smi_set_error("hipMalloc(prefill split-K slab, %zu bytes) failed", bytes); return SMI_ENOMEM; }
     L->pslab_bytes = bytes;
   }
-  if (hipMalloc((void**)&L->bh, R * L->H * 4) != hipSuccess || hipMalloc((void**)&L->bq, R * L->Q * 4) != hipSuccess ||
-      hipMalloc((void**)&L->bxs_h, R * L->H * 6) != hipSuccess || hipMalloc((void**)&L->bxs_attn, R * L->Q * 6) != hipSuccess ||
-      hipMalloc((void**)&L->bxs_act, R * L->I * 6) != hipSuccess || hipMalloc((void**)&L->bss, R * L->NTh * 4 * 4) != hipSuccess) {
-    smi_set_error("hipMalloc(prefill workspace for %d rows) failed", rows);
-    return SMI_ENOMEM;
-  }
+  if (!work_alloc(L, L->big, (size_t)rows)) { smi_set_error("hipMalloc(prefill workspace for %d rows) failed", rows); return SMI_ENOMEM; }
   L->big_rows = rows;
   return SMI_OK;
 }
 
 int launch_embed(smi_llm* L, const RowDesc* rows, int M, hipStream_t st) {
   hipLaunchKernelGGL(k_embed, dim3((M + 3) / 4), dim3(256), 0, st, (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0), L->KTh, rows, M,
-                     (const float*)sec(L, SMI_LLM_LN1, 0), L->h, L->xs_h, L->sspart, L->NTh * 4, L->exact);
+                     (const float*)sec(L, SMI_LLM_LN1, 0), L->dec.h, L->dec.xs_h, L->dec.ss, L->NTh * 4, L->exact);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }
@@ -4850,7 +4846,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->max_steps = cfg->max_positions;
   L->do_sample = 0; L->top_k = 50; L->temperature = 0.8f; L->top_p = 0.95f; L->seed = 0; L->logits = nullptr; L->tok = nullptr; L->cand_v = nullptr; L->cand_i = nullptr; L->cand_n = nullptr; L->stamps = nullptr; L->stamps_on = 0;
   { L->tune[0] = L->tune[1] = L->tune[2] = L->tune[3] = 0; const char* e = smi_env("SPARKMI_TUNE"); if (e) sscanf(e, "%d,%d,%d,%d", &L->tune[0], &L->tune[1], &L->tune[2], &L->tune[3]); }
-  L->bh = L->bq = nullptr; L->bxs_h = L->bxs_attn = L->bxs_act = nullptr; L->bss = nullptr; L->big_rows = 0;
+  L->dec = Work{}; L->big = Work{}; L->big_rows = 0;
   L->pslab = nullptr; L->pslab_bytes = 0;
   // helper-block prefetch per producer: bit 0 QKV (gate_up's first half), bit 1 attention (second half), bit 2 down_proj (the next
   // layer's QKV / o_proj); SPARKMI_PREFETCH=<mask> picks, SPARKMI_NO_PREFETCH=1 is mask 0
@@ -4909,7 +4905,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
   const size_t esz = cfg->kv_dtype ? 4 : 2;
   L->paged = cfg->kv_page_tokens > 0; L->pshift = 0; L->ppslot = 0; L->ptab = nullptr;
-  memset(L->slot_pages, 0, sizeof(L->slot_pages)); memset(L->plen, 0, sizeof(L->plen));
+  memset(L->slot_pages, 0, sizeof(L->slot_pages));
   L->kv_layer_elems = (size_t)cfg->max_slots * cfg->num_kv_heads * cfg->max_positions * kHeadDim;
   if (L->paged) {
     while ((1 << L->pshift) < cfg->kv_page_tokens) ++L->pshift;
@@ -4926,12 +4922,11 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
     smi_llm_destroy(L);                                                            \
     return SMI_ENOMEM;                                                             \
   }
-  SMI_ALLOC(L->h, (size_t)kMaxRows * L->H * 4);
-  SMI_ALLOC(L->qbuf, (size_t)kMaxRows * L->Q * 4);
-  SMI_ALLOC(L->xs_h, (size_t)kMaxRows * L->H * 6);
-  SMI_ALLOC(L->xs_attn, (size_t)kMaxRows * L->Q * 6);
-  SMI_ALLOC(L->xs_act, (size_t)kMaxRows * L->I * 6);
-  SMI_ALLOC(L->sspart, (size_t)kMaxRows * L->NTh * 4 * 4);
+  if (!work_alloc(L, L->dec, kMaxRows)) {
+    smi_set_error("hipMalloc(decode workspace for %d rows) failed", kMaxRows);
+    smi_llm_destroy(L);
+    return SMI_ENOMEM;
+  }
   SMI_ALLOC(L->part_o, (size_t)kFuse2Max * kMaxOHeads * L->H * 4);
   SMI_ALLOC(L->fuse_cnt, (size_t)kFuse2Max * kFuseQB * 4);
   SMI_HIP(hipMemset(L->fuse_cnt, 0, (size_t)kFuse2Max * kFuseQB * 4));
@@ -4980,12 +4975,12 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
     return SMI_ENOMEM;
   }
   if (hipMemset(L->kcache, 0, kvbytes) != hipSuccess || hipMemset(L->vcache, 0, kvbytes) != hipSuccess ||
-      hipMemset(L->h, 0, (size_t)kMaxRows * L->H * 4) != hipSuccess ||
-      hipMemset(L->xs_h, 0, (size_t)kMaxRows * L->H * 6) != hipSuccess ||
-      hipMemset(L->xs_attn, 0, (size_t)kMaxRows * L->Q * 6) != hipSuccess ||
-      hipMemset(L->xs_act, 0, (size_t)kMaxRows * L->I * 6) != hipSuccess ||
-      hipMemset(L->sspart, 0, (size_t)kMaxRows * L->NTh * 4 * 4) != hipSuccess ||
-      hipMemset(L->qbuf, 0, (size_t)kMaxRows * L->Q * 4) != hipSuccess ||
+      hipMemset(L->dec.h, 0, (size_t)kMaxRows * L->H * 4) != hipSuccess ||
+      hipMemset(L->dec.xs_h, 0, (size_t)kMaxRows * L->H * 6) != hipSuccess ||
+      hipMemset(L->dec.xs_attn, 0, (size_t)kMaxRows * L->Q * 6) != hipSuccess ||
+      hipMemset(L->dec.xs_act, 0, (size_t)kMaxRows * L->I * 6) != hipSuccess ||
+      hipMemset(L->dec.ss, 0, (size_t)kMaxRows * L->NTh * 4 * 4) != hipSuccess ||
+      hipMemset(L->dec.q, 0, (size_t)kMaxRows * L->Q * 4) != hipSuccess ||
       hipMemset(L->rows, 0, kMaxRows * sizeof(RowDesc)) != hipSuccess ||
       hipMemset(L->count, 0, kMaxRows * 4) != hipSuccess || hipMemset(L->finished, 0, kMaxRows * 4) != hipSuccess ||
       hipMemset(L->step, 0, 4) != hipSuccess) {
@@ -5045,8 +5040,10 @@ int smi_llm_destroy(smi_llm* L) {
   if (!L) return SMI_OK;
   graphs_flush(L);
   eng_destroy(L);
-  void* ptrs[] = {L->h, L->qbuf, L->xs_h, L->xs_attn, L->xs_act, L->sspart, L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
-                  L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->bh, L->bq, L->bxs_h, L->bxs_attn, L->bxs_act, L->bss, L->pslab, L->apart,
+  work_free(L->dec);
+  work_free(L->big);
+  void* ptrs[] = {L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
+                  L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->pslab, L->apart,
                   L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist, L->poll_dev, L->seq};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
@@ -5180,7 +5177,7 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
       }
       const bool d_grouped = L->pg_forced ? M < L->pg_min[3] : pass_family[ps] == PF_GROUPED;   // who leaves the RMSNorm partials of the layer input
       hipLaunchKernelGGL(k_embed, dim3((M + 3) / 4), dim3(256), 0, st, (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0), L->KTh, rows, M,
-                         (const float*)sec(L, SMI_LLM_LN1, 0), L->bh, L->bxs_h, L->bss, d_grouped ? L->NTh * 4 : L->NTh, 0);
+                         (const float*)sec(L, SMI_LLM_LN1, 0), L->big.h, L->big.xs_h, L->big.ss, d_grouped ? L->NTh * 4 : L->NTh, 0);
       SMI_LAUNCH_CHECK();
       if ((rc = launch_layers_big(L, rows, M, pass_family[ps], st))) return rc;
     }
@@ -5195,16 +5192,52 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
   return SMI_OK;
 }
 
-// eos ids + seed + the slots' sequence numbers -> device (before anything of the generation is enqueued)
-static int upload_ctl(smi_llm* L, const int64_t* eos_ids, int n_eos, hipStream_t st) {
+// The live set changed: rows 0 .. n-1 of the device row list belong to slots[0 .. n-1], in that order.  The next decode picks the
+// cached step of the new row count.
+static void live_set(smi_llm* L, const int* slots, int n) {
+  L->B = n;
+  L->live_order.assign(slots, slots + n);
+  L->identity_slots = 1;
+  L->lm_restrict = n > 0;
+  for (int b = 0; b < n; ++b) {
+    L->identity_slots &= slots[b] == b;
+    L->lm_restrict &= (L->slot_feat[slots[b]] & F_ALLOW) != 0;
+  }
+  L->graph = nullptr;
+}
+
+static int validate_eos(const int64_t* eos_ids, int n_eos) {
   SMI_REQUIRE(n_eos >= 0 && n_eos <= SMI_MAX_EOS && (n_eos == 0 || eos_ids), "eos list: 0..%d ids", SMI_MAX_EOS);
+  return SMI_OK;
+}
+
+// A new generation (nseq > 0: its sequences are numbered 0 .. nseq-1 up front) or session (nseq = 0: admissions number them).  No
+// slot holds a sequence: records, pages, lengths, live rows; eos ids + seed + the slots' sequence numbers and the zeroed counters
+// go to the device before anything of the generation is enqueued.  `started` is set only when all of it went through.
+static int gen_reset(smi_llm* L, const int64_t* eos_ids, int n_eos, int nseq, hipStream_t st) {
+  L->started = 0;
+  for (int b = 0; b < kMaxRows; ++b) L->hctl.seqid[b] = nseq ? b : 0;
+  slots_clear(L);
+  L->admit_seq = nseq;
+  if (L->paged)
+    for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
+  memset(L->slot_busy, 0, sizeof(L->slot_busy));
+  memset(L->slot_len, 0, sizeof(L->slot_len));
+  live_set(L, nullptr, 0);
   for (int e = 0; e < SMI_MAX_EOS; ++e) L->hctl.eos[e] = e < n_eos ? (long long)eos_ids[e] : -1;
   L->hctl.n_eos = n_eos;
   L->hctl.seed = L->seed;
   SMI_HIP(hipMemcpyAsync(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice, st));
+  SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
+  SMI_HIP(hipMemsetAsync(L->finished, 0, kMaxRows * 4, st));
+  SMI_HIP(hipMemsetAsync(L->step, 0, 4, st));
+  L->session = nseq == 0;
+  L->started = 1;
   return SMI_OK;
 }
 
+// Plain generation is the session state with slots 0 .. B-1 busy: the rows are written by the prefill plan itself, so nothing
+// is read back from the device (admit does) and the call does not synchronise.
 int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, int P_max, const int64_t* eos_ids, int n_eos,
                     void* stream) {
   SMI_REQUIRE(L && ids && lens, "smi_llm_prefill: null argument");
@@ -5212,8 +5245,8 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   hipStream_t st = (hipStream_t)stream;
   int32_t slots[kMaxRows];
   for (int b = 0; b < kMaxRows; ++b) slots[b] = b;
-  { const int rcv = validate_prompts(L, ids, lens, B, P_max); if (rcv) return rcv; }   // nothing touched yet
-  SMI_REQUIRE(n_eos >= 0 && n_eos <= SMI_MAX_EOS && (n_eos == 0 || eos_ids), "eos list: 0..%d ids", SMI_MAX_EOS);
+  int rc;
+  if ((rc = validate_prompts(L, ids, lens, B, P_max)) || (rc = validate_eos(eos_ids, n_eos))) return rc;   // nothing touched yet
   if (L->paged) {   // a new generation: every page back to the pool, then what the prompts need
     // the demand is checked against the WHOLE pool first (everything is about to be free), so a prompt set that cannot fit
     // fails here with the previous generation's pages, table and `started` flag untouched
@@ -5223,26 +5256,14 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
       smi_set_error("KV page pool too small for these prompts: %ld pages of %d tokens needed, the pool has %d", need, 1 << L->pshift, L->cfg.kv_pages);
       return SMI_ENOMEM;
     }
-    for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
-    int rcp = pages_ensure(L, slots, lens, B, st);
-    if (rcp) { L->started = 0; return rcp; }   // (cannot happen after the check above; the old generation is gone by now)
   }
-  for (int b = 0; b < B; ++b) L->plen[b] = lens[b];
-  for (int b = 0; b < kMaxRows; ++b) L->hctl.seqid[b] = b;
-  slots_clear(L);
-  L->admit_seq = B;
-  { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
-  SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
-  SMI_HIP(hipMemsetAsync(L->finished, 0, kMaxRows * 4, st));
-  SMI_HIP(hipMemsetAsync(L->step, 0, 4, st));
-  L->B = B; L->started = 1; L->session = 0; L->identity_slots = 1;
-  L->max_len = 0;
-  for (int b = 0; b < B; ++b) L->max_len = lens[b] > L->max_len ? lens[b] : L->max_len;
-  L->steps_launched = 1;
+  if ((rc = gen_reset(L, eos_ids, n_eos, B, st))) return rc;
+  if ((rc = pages_ensure(L, slots, lens, B, st))) { L->started = 0; return rc; }   // (cannot happen after the check above; the old generation is gone by now)
+  for (int b = 0; b < B; ++b) { L->slot_busy[b] = 1; L->slot_len[b] = lens[b] + 1; }   // (the first step, enqueued below, takes position lens[b])
+  live_set(L, slots, B);
   // the captured decode step is kept across utterances: eos ids and the seed live in device memory (Ctl); smi_llm_decode
   // re-captures only when the row count, the context-segment count or the slot mapping differ from the captured ones
   size_t tail = 0;
-  int rc;
   if ((rc = prefill_prompts(L, ids, lens, B, P_max, slots, &tail, st))) { L->started = 0; return rc; }
   if (hipMemcpyAsync(L->rows, L->plan + tail, kMaxRows * sizeof(RowDesc), hipMemcpyDeviceToDevice, st) != hipSuccess) {
     L->started = 0;
@@ -5256,35 +5277,15 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
 // ---- continuous batching: sequences join (admit) and leave (retire) between decode steps ----
 int smi_llm_session_begin(smi_llm* L, const int64_t* eos_ids, int n_eos, void* stream) {
   SMI_REQUIRE(L, "smi_llm_session_begin: null handle");
-  hipStream_t st = (hipStream_t)stream;
-  memset(L->hctl.seqid, 0, sizeof(L->hctl.seqid));
-  slots_clear(L);
-  L->admit_seq = 0;
-  if (L->paged)
-    for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
-  { int rc0 = upload_ctl(L, eos_ids, n_eos, st); if (rc0) return rc0; }
-  SMI_HIP(hipMemsetAsync(L->count, 0, kMaxRows * 4, st));
-  SMI_HIP(hipMemsetAsync(L->finished, 0, kMaxRows * 4, st));
-  SMI_HIP(hipMemsetAsync(L->step, 0, 4, st));
-  L->B = 0; L->started = 1; L->session = 1; L->identity_slots = 1;
-  L->live_order.clear();
-  L->max_len = 0; L->steps_launched = 0;
-  memset(L->slot_busy, 0, sizeof(L->slot_busy));
-  memset(L->slot_len, 0, sizeof(L->slot_len));
-  L->graph = nullptr;
-  return SMI_OK;
+  { const int rcv = validate_eos(eos_ids, n_eos); if (rcv) return rcv; }
+  return gen_reset(L, eos_ids, n_eos, 0, (hipStream_t)stream);
 }
 
 // the live row set changed: refresh the device rows, the per-row residual / operand state, and drop the graph
 static int session_set_rows(smi_llm* L, const std::vector<RowDesc>& live, hipStream_t st) {
-  L->B = (int)live.size();
-  L->identity_slots = 1;
-  for (int b = 0; b < L->B; ++b) L->identity_slots &= live[b].slot == b;
-  L->lm_restrict = L->B > 0;
-  for (int b = 0; b < L->B; ++b) L->lm_restrict &= (L->slot_feat[live[b].slot] & F_ALLOW) != 0;
-  L->live_order.clear();
-  for (int b = 0; b < L->B; ++b) L->live_order.push_back(live[b].slot);
-  L->graph = nullptr;   // (the next decode picks the cached step of the new row count)
+  int slots[kMaxRows];
+  for (size_t b = 0; b < live.size(); ++b) slots[b] = live[b].slot;
+  live_set(L, slots, (int)live.size());
   if (L->B == 0) return SMI_OK;
   L->host_rows.assign(kMaxRows, RowDesc{0, 0, 0, 0});
   for (int b = 0; b < L->B; ++b) L->host_rows[b] = live[b];
@@ -5710,14 +5711,13 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
   } else if ((rc = pen_histories(L, ids, lens, n, P_max, slots, st))) {
     return rc;
   }
-  L->graph = nullptr;
-  const int oldB = L->B;
-  L->B = N;
-  L->identity_slots = 1;
-  for (int j = 0; j < N; ++j) L->identity_slots &= slots[j] == j;
-  L->lm_restrict = 1;   // the admission's step runs over the new rows alone
-  for (int j = 0; j < N; ++j) L->lm_restrict &= (L->slot_feat[slots[j]] & F_ALLOW) != 0;
-  if ((rc = launch_embed(L, L->rows, N, st)) || (rc = launch_step(L, N, st))) { L->B = oldB; L->lm_restrict = 0; return rc; }
+  const std::vector<int> before = L->live_order;
+  live_set(L, slots, N);   // the admission's step runs over the new rows alone
+  if ((rc = launch_embed(L, L->rows, N, st)) || (rc = launch_step(L, N, st))) {
+    live_set(L, before.data(), (int)before.size());
+    L->lm_restrict = 0;
+    return rc;
+  }
   std::vector<RowDesc> fresh;
   if ((rc = session_live_rows(L, fresh, st))) return rc;
   for (int j = 0; j < N; ++j) {
@@ -5802,14 +5802,8 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
     slot_clear(L, slots[i]);
     if (L->paged) pages_release(L, slots[i]);
   }
-  L->live_order = keep;
-  L->B = (int)keep.size();
-  L->identity_slots = 1;
-  for (int b = 0; b < L->B; ++b) L->identity_slots &= keep[b] == b;
-  L->lm_restrict = L->B > 0;
-  for (int b = 0; b < L->B; ++b) L->lm_restrict &= (L->slot_feat[keep[b]] & F_ALLOW) != 0;
+  live_set(L, keep.data(), (int)keep.size());
   { const int rct = allow_tiles_upload(L, st); if (rct) return rct; }
-  L->graph = nullptr;
   if (L->B == 0) return SMI_OK;
   return launch_embed(L, L->rows, L->B, st);
 }
@@ -5911,6 +5905,20 @@ int smi_llm_slot_tokens(smi_llm* L, int slot, int64_t* out, int cap, int32_t* n_
 
 // K back-to-back decode steps over the live rows, captured on a stream of its own and instantiated: *out, or null when the
 // capture or the instantiation failed (the runtime's error state is cleared either way).
+// Every sequence of the generation or session -- the busy slots -- and the cache positions each will have used after n_steps more
+// steps; returns how many there are, *bound the largest of their lengths.
+static int busy_after(const smi_llm* L, int n_steps, int* sl, int* len, int* bound) {
+  int n = 0;
+  *bound = 0;
+  for (int s = 0; s < kMaxRows; ++s)
+    if (L->slot_busy[s]) {
+      sl[n] = s; len[n] = L->slot_len[s] + n_steps;
+      *bound = len[n] > *bound ? len[n] : *bound;
+      ++n;
+    }
+  return n;
+}
+
 static int capture_steps(smi_llm* L, int K, hipGraphExec_t* out) {
   *out = nullptr;
   hipStream_t cs;
@@ -5932,42 +5940,20 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
   SMI_REQUIRE(L, "smi_llm_decode: null handle");
   if (!L->started) { smi_set_error("smi_llm_decode before smi_llm_prefill"); return SMI_ESTATE; }
   SMI_REQUIRE(n_steps >= 0, "smi_llm_decode: n_steps < 0");
-  if (L->session) {
-    if (L->B == 0 || n_steps == 0) return SMI_OK;
-    for (int sl = 0; sl < kMaxRows; ++sl)
-      if (L->slot_busy[sl])
-        SMI_REQUIRE(L->slot_len[sl] + n_steps <= L->cfg.max_positions, "smi_llm_decode: %d more steps would take slot %d past max_positions=%d",
-                    n_steps, sl, L->cfg.max_positions);
-  } else {
-    SMI_REQUIRE(L->max_len + L->steps_launched + n_steps <= L->cfg.max_positions,
-                "smi_llm_decode: %d more steps would pass max_positions=%d (prompt %d, %d steps so far)", n_steps,
-                L->cfg.max_positions, L->max_len, L->steps_launched);
-  }
+  if (L->B == 0 || n_steps == 0) return SMI_OK;
+  int sl[kMaxRows], need[kMaxRows], bound = 0;
+  const int n = busy_after(L, n_steps, sl, need, &bound);
+  for (int i = 0; i < n; ++i)
+    SMI_REQUIRE(need[i] <= L->cfg.max_positions, "smi_llm_decode: %d more steps would take slot %d past max_positions=%d", n_steps, sl[i],
+                L->cfg.max_positions);
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  if (L->paged && n_steps > 0) {   // every live sequence grows by n_steps positions: their pages first, all or nothing
-    int sl[kMaxRows], need[kMaxRows], n = 0;
-    if (L->session) {
-      for (int s2 = 0; s2 < kMaxRows; ++s2)
-        if (L->slot_busy[s2]) { sl[n] = s2; need[n++] = L->slot_len[s2] + n_steps; }
-    } else {
-      for (int b = 0; b < L->B; ++b) { sl[n] = b; need[n++] = L->plen[b] + L->steps_launched + n_steps; }
-    }
-    for (int i = 0; i < n; ++i) need[i] = need[i] < L->cfg.max_positions ? need[i] : L->cfg.max_positions;
-    if ((rc = pages_ensure(L, sl, need, n, st))) return rc;
-  }
-  {   // context bound of this call -> attention segments (the partial buffer must exist before a capture starts)
-    int bound = L->max_len + L->steps_launched + n_steps;
-    if (L->session) {
-      bound = 0;
-      for (int sl = 0; sl < kMaxRows; ++sl)
-        if (L->slot_busy[sl] && L->slot_len[sl] + n_steps > bound) bound = L->slot_len[sl] + n_steps;
-    }
-    L->attn_seg = segs_for(bound);
-    if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
-  }
+  if ((rc = pages_ensure(L, sl, need, n, st))) return rc;   // paged cache: the pages of those positions first, all or nothing
+  // context bound of this call -> attention segments (the partial buffer must exist before a capture starts)
+  L->attn_seg = segs_for(bound);
+  if (L->attn_seg > 1 && (rc = ensure_apart(L, (size_t)kMaxRows * L->cfg.num_heads * L->attn_seg * 66))) return rc;
   const unsigned feat = step_feat(L);
-  if (L->cfg.use_graph && n_steps > 0) {
+  if (L->cfg.use_graph) {
     const uint64_t key = graph_key(L, feat, 0);
     if (!L->graph || L->graph_id != key) {
       auto hit = L->graph_cache.find(key);
@@ -6011,10 +5997,7 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
       return rc;
     }
   }
-  L->steps_launched += n_steps;
-  if (L->session)
-    for (int sl = 0; sl < kMaxRows; ++sl)
-      if (L->slot_busy[sl]) L->slot_len[sl] += n_steps;
+  for (int i = 0; i < n; ++i) L->slot_len[sl[i]] = need[i];
   return SMI_OK;
 }
 
@@ -6217,8 +6200,10 @@ int smi_llm_time_kernel(smi_llm* L, int kernel, int layer, int iters, float* ms_
   } else {
     const int nl = L->cfg.num_layers;
     if (kernel == KFIN) {
-      SMI_REQUIRE(L->max_len + L->steps_launched + iters + 1 <= L->cfg.max_positions, "smi_llm_time_kernel: finalize probe would pass max_positions");
-      L->steps_launched += iters + 1;
+      int sl[kMaxRows], len[kMaxRows], bound = 0;
+      const int n = busy_after(L, iters + 1, sl, len, &bound);
+      SMI_REQUIRE(bound <= L->cfg.max_positions, "smi_llm_time_kernel: finalize probe would pass max_positions");
+      for (int i = 0; i < n; ++i) L->slot_len[sl[i]] = len[i];
     }
     if ((rc = launch_one(L, kernel, layer % nl, L->rows, L->B, nullptr, st))) return rc;
     SMI_HIP(hipEventRecord(L->ev0, st));
@@ -6302,7 +6287,7 @@ int smi_llm_engine_plan(const smi_llm_cfg* cfg, int ncu, int32_t* stats) {
 int smi_llm_debug_hidden(smi_llm* L, float* out_host, int n) {
   SMI_REQUIRE(L && out_host && n >= L->H, "smi_llm_debug_hidden: out holds %d floats, %d needed", n, L ? L->H : 0);
   SMI_HIP(hipDeviceSynchronize());
-  SMI_HIP(hipMemcpy(out_host, L->h, (size_t)L->H * 4, hipMemcpyDeviceToHost));
+  SMI_HIP(hipMemcpy(out_host, L->dec.h, (size_t)L->H * 4, hipMemcpyDeviceToHost));
   return eng_check(L);
 }
 
@@ -6315,13 +6300,13 @@ int smi_llm_debug_read(smi_llm* L, int what, void* out_host, size_t cap, size_t*
   size_t n = 0;
   const size_t R = L->B > 0 ? (size_t)L->B : 1;   // buffers 0..4 and 6 hold one entry per live row
   switch (what) {
-    case 0: src = L->qbuf; n = R * L->Q * 4; break;
-    case 1: src = L->xs_attn; n = R * L->Q * 6; break;
-    case 2: src = L->xs_act; n = R * L->I * 6; break;
-    case 3: src = L->xs_h; n = R * L->H * 6; break;
-    case 4: src = L->h; n = R * L->H * 4; break;
+    case 0: src = L->dec.q; n = R * L->Q * 4; break;
+    case 1: src = L->dec.xs_attn; n = R * L->Q * 6; break;
+    case 2: src = L->dec.xs_act; n = R * L->I * 6; break;
+    case 3: src = L->dec.xs_h; n = R * L->H * 6; break;
+    case 4: src = L->dec.h; n = R * L->H * 4; break;
     case 5: src = L->eng.gran; n = L->eng.gran ? (size_t)2 * L->eng.gran_per_buf * 8 : 0; break;
-    case 6: src = L->sspart; n = R * L->H; break;
+    case 6: src = L->dec.ss; n = R * L->H; break;
     case 7: src = L->kcache; n = (size_t)L->cfg.max_positions * kHeadDim * 2; break;
     case 8: src = L->h2; n = (size_t)L->H * 4; break;
     default: smi_set_error("smi_llm_debug_read: what=%d", what); return SMI_EINVAL;
@@ -6422,8 +6407,8 @@ int smi_llm_debug_layer(smi_llm* L, int layer, int M, const int32_t* rows_host, 
   int rc = SMI_OK;
   if (hipMemcpy(src, hidden_host, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_layer: upload failed"); }
   if (rc == SMI_OK) {
-    hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, src, L->KTh, M, (const float*)sec(L, SMI_LLM_LN1, layer), L->h, L->xs_h,
-                       L->sspart, L->NTh * 4);
+    hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, src, L->KTh, M, (const float*)sec(L, SMI_LLM_LN1, layer), L->dec.h, L->dec.xs_h,
+                       L->dec.ss, L->NTh * 4);
     if (hipGetLastError() != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_layer: k_load_hidden launch failed"); }
   }
   const bool fused = fuse_o_now(L, L->rows, M);
@@ -6443,31 +6428,54 @@ int smi_llm_debug_raw_stamps(smi_llm* L, unsigned long long* out, int n) {
   return SMI_OK;
 }
 
+// ---- kernel-alone runs (the four entries below): the state around them, and the table the lm_head would have left
+// Before: the device idle, every record clean, rows 0 .. n-1 = slots 0 .. n-1 with flags[m] tokens emitted (null: none).  The
+// caller then writes the records its kernel reads and uploads the controls.
+static int alone_begin(smi_llm* L, int n, const int32_t* flags) {
+  SMI_HIP(hipDeviceSynchronize());
+  slots_clear(L);
+  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
+  for (int m = 0; m < n; ++m) rows[m] = RowDesc{m, 0, 0, flags ? flags[m] : 0};
+  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
+  return SMI_OK;
+}
+// After: clean records again; rows, controls, the lm_head partials and the histories no longer belong to a generation.
+static void alone_end(smi_llm* L) {
+  slots_clear(L);
+  L->started = 0;
+}
+// (maximum, lowest id) of each of the nblk contiguous sets of `per` ids of every logits row [n_rows][V], as the lm_head leaves
+// them: pv / pi [n_rows][nblk]
+static void block_maxima(const float* logits, int n_rows, int V, int nblk, int per, std::vector<float>& pv, std::vector<int32_t>& pi) {
+  pv.assign((size_t)n_rows * nblk, -INFINITY);
+  pi.assign((size_t)n_rows * nblk, 0x7fffffff);
+  for (int m = 0; m < n_rows; ++m)
+    for (int j = 0; j < nblk; ++j)
+      for (int i = j * per; i < V && i < (j + 1) * per; ++i) {
+        const float x = logits[(size_t)m * V + i];
+        if (x > pv[(size_t)m * nblk + j]) { pv[(size_t)m * nblk + j] = x; pi[(size_t)m * nblk + j] = i; }
+      }
+}
+
 // Tests: the sampler alone on a caller's logits row (see sparkmi_debug.h).
 int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint64_t seed, int use_bound, int32_t* tokens_out) {
   SMI_REQUIRE(L && tokens_out && n_rows >= 1 && n_rows <= kMaxRows, "smi_llm_debug_sample: bad argument");
   SMI_REQUIRE(L->do_sample, "smi_llm_debug_sample: smi_llm_set_sampling(do_sample = 1, ...) first");
   const int V = L->cfg.vocab_size;
   const int nblk = lm_blocks_for(L, n_rows);
-  SMI_HIP(hipDeviceSynchronize());
+  { const int rcb = alone_begin(L, kMaxRows, nullptr); if (rcb) return rcb; }   // (clean records: every row inherits the handle's settings)
   if (logits_host) {
-    for (int m = 0; m < kMaxRows; ++m) SMI_HIP(hipMemcpy(L->logits + (size_t)m * V, logits_host, (size_t)V * 4, hipMemcpyHostToDevice));
     // what the lm_head blocks would have left: one maximum per block; here block j holds the j-th contiguous share of the row
-    std::vector<float> pv((size_t)kMaxRows * L->lm_cap, -INFINITY);
-    const int per = (V + nblk - 1) / nblk;
-    for (int j = 0; j < nblk; ++j) {
-      float mx = -INFINITY;
-      for (int i = j * per; i < V && i < (j + 1) * per; ++i) mx = logits_host[i] > mx ? logits_host[i] : mx;
-      for (int m = 0; m < kMaxRows; ++m) pv[(size_t)m * nblk + j] = mx;
+    std::vector<float> pv;
+    std::vector<int32_t> pi;
+    block_maxima(logits_host, 1, V, nblk, (V + nblk - 1) / nblk, pv, pi);
+    for (int m = 0; m < kMaxRows; ++m) {
+      SMI_HIP(hipMemcpy(L->logits + (size_t)m * V, logits_host, (size_t)V * 4, hipMemcpyHostToDevice));
+      SMI_HIP(hipMemcpy(L->pval + (size_t)m * nblk, pv.data(), (size_t)nblk * 4, hipMemcpyHostToDevice));
     }
-    SMI_HIP(hipMemcpy(L->pval, pv.data(), (size_t)kMaxRows * nblk * 4, hipMemcpyHostToDevice));
   }
-  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
-  for (int m = 0; m < kMaxRows; ++m) { rows[m].slot = m; L->hctl.seqid[m] = m; }
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));   // every row inherits the handle's settings
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
+  for (int m = 0; m < kMaxRows; ++m) L->hctl.seqid[m] = m;
   L->hctl.seed = seed;
-  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
   SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
   SampleP sp = sample_params(L, n_rows);
@@ -6479,7 +6487,7 @@ int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint6
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());
   SMI_HIP(hipMemcpy(tokens_out, L->tok, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
-  L->started = 0;   // rows, controls and the lm_head partials no longer belong to a generation
+  alone_end(L);
   return SMI_OK;
 }
 
@@ -6494,21 +6502,15 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
   }
   const size_t V = (size_t)L->cfg.vocab_size;
   const int nblk = lm_blocks_for(L, n_rows);
-  SMI_HIP(hipDeviceSynchronize());
+  { const int rcb = alone_begin(L, n_rows, emitted_host); if (rcb) return rcb; }
   SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->phist, hist_host, (size_t)n_rows * V * 2, hipMemcpyHostToDevice));
-  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
-  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
   for (int m = 0; m < n_rows; ++m) {
-    rows[m] = RowDesc{m, 0, 0, emitted_host[m]};
     L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: the kernel writes its processed logits back)
     PenRec& r = L->hctl.pen[m];
     r = pen_record(&pens[m]);
     if (!r.on) { r.rep = 1.f; r.prompt = pens[m].penalize_prompt; r.on = 1; }   // a neutral record runs too: as the identity
   }
-  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
   PenP pp = pen_params(L, n_rows);
   pp.hs = 0;
@@ -6530,10 +6532,7 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
     }
     argmax_out[m] = bi;
   }
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
-  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
-  L->started = 0;   // rows, controls and the lm_head partials no longer belong to a generation
+  alone_end(L);
   return SMI_OK;
 }
 
@@ -6549,34 +6548,21 @@ int smi_llm_debug_logprob(smi_llm* L, const float* logits_host, int n_rows, cons
   }
   SMI_REQUIRE(L->max_steps >= 1, "smi_llm_debug_logprob: no history");
   const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
-  // the row maxima as the lm_head leaves them: (maximum, lowest id) of each contiguous set
-  std::vector<float> pv((size_t)n_rows * nblk, -INFINITY);
-  std::vector<int32_t> pi((size_t)n_rows * nblk, 0x7fffffff);
-  for (int m = 0; m < n_rows; ++m)
-    for (int j = 0; j < nblk; ++j)
-      for (int i = j * per; i < V && i < (j + 1) * per; ++i) {
-        const float x = logits_host[(size_t)m * V + i];
-        if (x > pv[(size_t)m * nblk + j]) { pv[(size_t)m * nblk + j] = x; pi[(size_t)m * nblk + j] = i; }
-      }
-  SMI_HIP(hipDeviceSynchronize());
+  std::vector<float> pv;
+  std::vector<int32_t> pi;
+  block_maxima(logits_host, n_rows, V, nblk, per, pv, pi);
+  { const int rcb = alone_begin(L, n_rows, nullptr); if (rcb) return rcb; }
   SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->tok, tokens_host, (size_t)n_rows * 4, hipMemcpyHostToDevice));
-  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
-  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
-  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
-  for (int m = 0; m < n_rows; ++m) {
-    rows[m] = RowDesc{m, 0, 0, 0};   // token index 0: k_finalize writes lp[0][m]
+  for (int m = 0; m < n_rows; ++m) {   // (no tokens emitted: k_finalize writes lp[0][m])
     SampRec& r = L->hctl.samp[m];
     r.mode = SMI_SAMPLING_SAMPLE;    // a sampling row: its token is the caller's (L->tok) and its z is scaled by 1/T
     r.inv_temp = 1.0f / temperature_host[m];
     r.top_k = 1; r.top_p = 1.f;
     L->hctl.lp[m] = 1;
   }
-  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
   SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
   LpP lp = lp_params(L, n_rows);
@@ -6590,9 +6576,7 @@ int smi_llm_debug_logprob(smi_llm* L, const float* logits_host, int n_rows, cons
   SMI_LAUNCH_CHECK();
   SMI_HIP(hipDeviceSynchronize());
   SMI_HIP(hipMemcpy(lp_out, L->lp, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
-  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
-  L->started = 0;   // rows, controls, the lm_head partials and the histories no longer belong to a generation
+  alone_end(L);
   return SMI_OK;
 }
 
@@ -6615,29 +6599,20 @@ int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, cons
       SMI_REQUIRE(ctx_host[(size_t)m * ctx_cap + t] >= 0 && ctx_host[(size_t)m * ctx_cap + t] < V, "smi_llm_debug_seqbias: ctx[%d][%d] outside the vocabulary", m, t);
   }
   const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
-  // the row maxima as the lm_head leaves them: (maximum, lowest id) of each contiguous set
-  std::vector<float> pv((size_t)n_rows * nblk, -INFINITY);
-  std::vector<int32_t> pi((size_t)n_rows * nblk, 0x7fffffff);
-  for (int m = 0; m < n_rows; ++m)
-    for (int j = 0; j < nblk; ++j)
-      for (int i = j * per; i < V && i < (j + 1) * per; ++i) {
-        const float x = logits_host[(size_t)m * V + i];
-        if (x > pv[(size_t)m * nblk + j]) { pv[(size_t)m * nblk + j] = x; pi[(size_t)m * nblk + j] = i; }
-      }
-  SMI_HIP(hipDeviceSynchronize());
+  std::vector<float> pv;
+  std::vector<int32_t> pi;
+  block_maxima(logits_host, n_rows, V, nblk, per, pv, pi);
+  int32_t gen[kMaxRows];   // tokens emitted so far, per row
+  int max_gen = 0;
+  for (int m = 0; m < n_rows; ++m) {
+    gen[m] = ctx_len_host[m] - prompt_len_host[m];
+    max_gen = gen[m] > max_gen ? gen[m] : max_gen;
+  }
+  { const int rcb = alone_begin(L, n_rows, gen); if (rcb) return rcb; }
   SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
-  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
-  memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
-  memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
-  int max_gen = 0;
   for (int m = 0; m < n_rows; ++m) {
-    const int gen = ctx_len_host[m] - prompt_len_host[m];
-    max_gen = gen > max_gen ? gen : max_gen;
-    rows[m] = RowDesc{m, 0, 0, gen};
     L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: k_penalize writes its processed logits back; k_finalize gets no
     L->hctl.samp[m].top_k = 1; L->hctl.samp[m].inv_temp = 1.f; L->hctl.samp[m].top_p = 1.f;   // sampler tokens and takes the arg-max)
     if (min_new_host && min_new_host[m] > 0) {   // only min_new of a neutral penalty record: the stop match reads it
@@ -6654,7 +6629,6 @@ int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, cons
     SMI_HIP(hipMemcpy(L->hist, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
   }
   SMI_HIP(hipMemcpy(L->seq, L->hseq.data(), (size_t)n_rows * sizeof(SeqRec), hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
   SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
   PenP pp = pen_params(L, n_rows);
@@ -6671,9 +6645,7 @@ int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, cons
   std::vector<RowDesc> after(kMaxRows);
   SMI_HIP(hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost));
   for (int m = 0; m < n_rows; ++m) token_out[m] = after[m].token;
-  memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
-  memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
-  L->started = 0;   // rows, controls, the lm_head partials and the histories no longer belong to a generation
+  alone_end(L);
   return SMI_OK;
 }
 

@@ -706,3 +706,67 @@ def test_paged_kv_cache_serves_more_sequences_than_it_could_reserve(tiny):
     assert small.kv_pages() == (6, 6)
     with pytest.raises(SparkMIError):
         _llm(cfg, syn, max_positions=250, kv_page_tokens=16, kv_pages=8)      # page size must divide max_positions
+
+
+def test_plain_generation_grows_its_pages_during_decode(tiny):
+    """Plain (prefill + decode) generation on a paged cache keeps its lengths in the same per-slot records as a session: three
+    ragged prompts, decode calls of 3, 13 and 20 steps so that every slot crosses a 16-token page boundary inside some call
+    (captured steps).  Tokens equal the contiguous cache's and generate_ragged's (the session path) with equal budgets, bit
+    for bit, and the pool afterwards lacks exactly ceil((len + steps) / 16) pages per slot."""
+    cfg, syn = tiny
+    rng = np.random.Generator(np.random.PCG64(2718))
+    prompts = [rng.integers(0, cfg.vocab_size, size=n).tolist() for n in (5, 17, 30)]
+    calls, page, pool = (3, 13, 20), 16, 16
+    steps = 1 + sum(calls)                                    # the prefill's own step emits the first token
+    paged = _llm(cfg, syn, max_slots=3, max_positions=96, kv_page_tokens=page, kv_pages=pool, use_graph=True)
+    paged.prefill(prompts)
+    held = [-(-len(p) // page) for p in prompts]
+    assert paged.kv_pages() == (pool, pool - sum(held))
+    done = 1
+    for n in calls:
+        paged.decode(n)
+        done += n
+        grown = [-(-(len(p) + done) // page) for p in prompts]
+        assert any(g > h for g, h in zip(grown, held))        # some slot crossed a boundary in this call
+        held = grown
+        assert paged.kv_pages() == (pool, pool - sum(held))
+    assert held == [3, 4, 5]                                  # every slot crossed one
+    got = paged.tokens(steps)
+    assert [len(t) for t in got] == [steps] * 3
+    assert got == _llm(cfg, syn, max_slots=3, max_positions=96).generate_ids(prompts, steps)
+    assert paged.kv_pages() == (pool, pool - sum(-(-(len(p) + steps) // page) for p in prompts))
+    assert paged.generate_ragged(prompts, [steps] * 3) == got
+
+
+def test_position_limit_is_kept_per_slot_and_state_gates_hold(tiny):
+    """max_positions: the decode call that lands exactly on it succeeds, one more step is refused with nothing enqueued (the
+    tokens stay readable) -- for a plain generation and for a session with one slot at the limit and one not.  After a plain
+    prefill, admit / retire / retire_many are still refused as outside a session."""
+    from sparkmi._lib import SparkMIError
+    cfg, syn = tiny
+    rng = np.random.Generator(np.random.PCG64(1618))
+    p10, p4 = rng.integers(0, cfg.vocab_size, size=10).tolist(), rng.integers(0, cfg.vocab_size, size=4).tolist()
+    single = _llm(cfg, syn, max_positions=64)
+    want10, want4 = single.generate_ids([p10], 54)[0], single.generate_ids([p4], 60)[0]   # 10 + 54 == 4 + 60 == max_positions
+    llm = _llm(cfg, syn, max_slots=2, max_positions=64)
+    llm.prefill([p10, p4])
+    llm.decode(53)                                            # 10 + 1 + 53 == max_positions
+    with pytest.raises(SparkMIError, match=r"code -1\).*max_positions=64"):
+        llm.decode(1)
+    assert llm.tokens(64) == [want10, want4[:54]]
+    for call in (lambda: llm.admit([p4]), lambda: llm.retire(0), lambda: llm.retire_many([0, 1])):
+        with pytest.raises(SparkMIError, match=r"code -4\).*outside a session"):
+            call()
+    assert llm.tokens(64) == [want10, want4[:54]]
+    llm.session_begin(None)
+    a, = llm.admit([p10])
+    b, = llm.admit([p4])
+    llm.decode(53)
+    with pytest.raises(SparkMIError, match=rf"code -1\).*slot {a} past max_positions=64"):
+        llm.decode(1)
+    assert llm.slot_tokens(a, 64)[0] == want10 and llm.slot_tokens(b, 64)[0] == want4[:54]
+    llm.retire(a)                                             # the slot at the limit leaves: the other one goes on
+    llm.decode(6)
+    assert llm.slot_tokens(b, 64)[0] == want4
+    with pytest.raises(SparkMIError, match=rf"code -1\).*slot {b} past max_positions=64"):
+        llm.decode(1)
