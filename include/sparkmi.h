@@ -343,6 +343,34 @@ int smi_llm_admit_biased(smi_llm* h, const int64_t* ids_host, const int32_t* len
                          const int32_t* n_return, const smi_sample_params* params, const smi_penalty_params* pens,
                          const int32_t* return_log_probs, const smi_allow_params* allow, const smi_seq_params* seq,
                          int32_t* slots_out, void* stream);
+/* No repeated n-grams (transformers' no_repeat_ngram_size / NoRepeatNGramLogitsProcessor; TensorRT-LLM's sampling-config field
+ * of the same name).  smi_llm_admit_ngram = smi_llm_admit_biased plus no_repeat_ngram [N]: one int32 n per OUTPUT sequence
+ * (NULL, or all zeros: exactly smi_llm_admit_biased).  n = 0: none; valid values 0 .. SMI_MAX_NGRAM.
+ *   Let ctx = the sequence's full prompt followed by the tokens it has generated so far, at the step that chooses the next
+ *   token, L = len(ctx).  The prompt counts, as in transformers (the library keeps every flagged slot's prompt ids on the
+ *   device; the takes of a fork see their prompt's ids and their own generated ids).  If L + 1 < n nothing is banned.
+ *   Otherwise let tail = ctx[L-n+1 .. L) (n - 1 ids, empty for n = 1): for every i in [0, L-n] with ctx[i .. i+n-1) == tail
+ *   the logit of id ctx[i+n-1] becomes -inf.  Nothing else of the row changes: no finite logit moves by a bit.  So no n-gram
+ *   of the context is ever emitted twice.
+ *   Stage order: between the penalty stages 1-3 and the min_new_tokens mask, transformers' place for it.  It writes only
+ *   -inf, and every other stage maps -inf to -inf, so the result is the same wherever the ban is physically applied (the
+ *   library applies it to the lm_head's row, before stage 0).  Log-probabilities (smi_llm_admit_logprobs) are taken after it;
+ *   selection is unchanged.
+ *   Neutral: n = 0; that row takes the route and the bits it gets without the record.
+ *   Checked with the other records before anything of the handle is touched (SMI_EINVAL, no slot, page, page reference or
+ *   admission number taken): 0 <= n <= SMI_MAX_NGRAM, and for n > 0 the survivor rule: a step bans at most
+ *   L - n + 1 <= max_positions - 1 distinct ids, so the row's static survivor count -- its allowed set (the whole vocabulary
+ *   without one) minus the distinct last ids of its -inf bias entries, minus the eos ids when min_new_tokens > 0 -- must be at
+ *   least max_positions.  Conservative and static, like smi_llm_admit_biased's bound: no row ever reaches selection with
+ *   every logit -inf.
+ *   Independence: a row's tokens and log-probabilities do not depend on what else is live, nor on whether its step read the
+ *   restricted lm_head -- bit for bit, with either KV dtype, paged or contiguous.
+ * Static generation (smi_llm_prefill) has none of this. */
+#define SMI_MAX_NGRAM 64
+int smi_llm_admit_ngram(smi_llm* h, const int64_t* ids_host, const int32_t* lens_host, int n, int P_max,
+                        const int32_t* n_return, const smi_sample_params* params, const smi_penalty_params* pens,
+                        const int32_t* return_log_probs, const smi_allow_params* allow, const smi_seq_params* seq,
+                        const int32_t* no_repeat_ngram, int32_t* slots_out, void* stream);
 int smi_llm_retire(smi_llm* h, int slot, void* stream);
 int smi_llm_slot_tokens(smi_llm* h, int slot, int64_t* out_host, int cap, int32_t* n_out, int32_t* finished, void* stream);
 /* Several sequences leave at once with no host round trip (the device row list is compacted in place), and the tokens of

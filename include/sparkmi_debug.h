@@ -109,6 +109,14 @@ int smi_llm_debug_logprob(smi_llm* h, const float* logits_host, int n_rows, cons
 int smi_llm_debug_seqbias(smi_llm* h, const float* logits_host, int n_rows, const smi_seq_params* seq, const int64_t* ctx_host,
                           const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, const int32_t* min_new_host,
                           float* logits_out, int32_t* token_out, int32_t* finished_out);
+/* Tests: the n-gram ban (k_ngram_ban), k_penalize and k_finalize alone, as a step launches them for n_rows rows
+ * (n_rows <= max_slots), on caller rows: logits_host [n_rows][vocab_size]; ngram_host [n_rows] each row's
+ * no_repeat_ngram_size (0 .. SMI_MAX_NGRAM); ctx_host [n_rows][ctx_cap] int64: row m's context ctx_len_host[m] ids long, of
+ * which the first prompt_len_host[m] (0 .. ctx_len, at most max_positions) go to the slot's prompt store and the rest to the
+ * token history.  logits_out [n_rows][vocab_size]: the rows after the stage; token_out [n_rows]: the arg-max k_finalize
+ * emits (lowest id on ties).  Synchronises; ends the current generation. */
+int smi_llm_debug_ngram(smi_llm* h, const float* logits_host, int n_rows, const int32_t* ngram_host, const int64_t* ctx_host,
+                        const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, float* logits_out, int32_t* token_out);
 
 #ifdef __cplusplus
 }

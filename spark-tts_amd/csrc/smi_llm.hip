@@ -76,6 +76,8 @@ struct Ctl {
   PenRec pen[SMI_MAX_ROWS];       // per KV slot: the sequence's penalty record (smi_llm_admit_penalized)
   int32_t lp[SMI_MAX_ROWS];       // per KV slot: 1 = the sequence returns per-token log-probabilities (smi_llm_admit_logprobs)
   AllowRec allow[SMI_MAX_ROWS];   // per KV slot: the sequence's allowed-token ranges (smi_llm_admit_constrained; n = 0: none)
+  int32_t ngram[SMI_MAX_ROWS];    // per KV slot: the sequence's no_repeat_ngram_size (smi_llm_admit_ngram; 0: none)
+  int32_t ngplen[SMI_MAX_ROWS];   // per KV slot: prompt ids held in the slot's row of the context store (ngram > 0 only)
 };
 
 // One sequence's bias entries and stop sequences (smi_seq_params as admitted) with the tail of its prompt, 1616 bytes; all zero:
@@ -3351,7 +3353,8 @@ __global__ __launch_bounds__(256) void k_penalize(PenP p) {
   const bool con = al->n > 0;
   const SeqRec* sq = p.seq ? &p.seq[rd.slot] : nullptr;
   const bool bia = sq && sq->n_bias > 0;
-  if (!r.on && !con && !bia) return;   // neither penalised, constrained nor biased: the lm_head's maxima stand
+  const bool ngr = p.ctl->ngram[rd.slot] > 0;   // k_ngram_ban may have written -inf into the row: its maxima are rebuilt here
+  if (!r.on && !con && !bia && !ngr) return;   // neither penalised, constrained, biased nor n-gram banned: the lm_head's maxima stand
   const int lane = threadIdx.x & 63, set = blockIdx.x * kPenWaves + (threadIdx.x >> 6);
   if (set >= p.nblk) return;
   int nbl = 0;   // stage 0b: ids of this wave's set whose logit takes a bias total at this step
@@ -3359,7 +3362,7 @@ __global__ __launch_bounds__(256) void k_penalize(PenP p) {
     bool any;
     nbl = seq_bias_list(sq, rd, p.ghist, p.max_steps, lane, set * p.per, min(set * p.per + p.per, p.V), s_bid[threadIdx.x >> 6],
                         s_btot[threadIdx.x >> 6], &any);
-    if (!any && !r.on && !con) return;   // no entry applies at this step: the row is the lm_head's, its maxima stand
+    if (!any && !r.on && !con && !ngr) return;   // no entry applies at this step: the row is the lm_head's, its maxima stand
   }
   const int* l_id = s_bid[threadIdx.x >> 6];
   const float* l_tot = s_btot[threadIdx.x >> 6];
@@ -3417,6 +3420,57 @@ __global__ __launch_bounds__(256) void k_penalize(PenP p) {
   if (lane == 0) {
     p.pval[(size_t)m * p.nblk + set] = bv;   // an empty set (per * nblk > V): (-inf, no id), below every real entry
     p.pidx[(size_t)m * p.nblk + set] = bi;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// no_repeat_ngram_size (smi_llm_admit_ngram; include/sparkmi.h states the semantics).  The context of the sequence in a slot is
+// its prompt ids (the slot's row of the context store, written at admission) followed by the ids it has generated (the slot's
+// column of the token history, which k_finalize writes); n and the prompt length are in Ctl.  k_ngram_ban runs after the
+// lm_head and before k_penalize: grid (1, M) x 256, a row with n = 0 leaves at once.  A flagged row copies its context into
+// LDS (or reads it in place when it does not fit), lane t takes the start positions t, t + 256, ...: where the n - 1 ids from
+// there equal the context's last n - 1 ids, the id that followed gets -inf in the row's logits.  Plain stores: duplicates
+// write the same value.  The stage only ever writes -inf, so the stages of k_penalize, which map -inf to -inf, give the same
+// row whether they ran before or after it; k_penalize treats the row as active and rebuilds its maxima.
+// ------------------------------------------------------------------------------------------
+struct NgramP {
+  float* logits;          // [M][V]
+  const Ctl* ctl;         // per-slot n and prompt length
+  const RowDesc* rows;
+  const int32_t* pctx;    // [max_slots][max_pos] prompt ids per slot
+  const int64_t* ghist;   // [max_steps][kMaxRows] generated tokens per slot
+  int V, max_pos, max_steps;
+  int lds_ids;            // ids the dynamic LDS holds beside the tail (0: the context is read in place)
+};
+
+__global__ __launch_bounds__(256) void k_ngram_ban(NgramP p) {
+  extern __shared__ int32_t s_ng[];   // [SMI_MAX_NGRAM] tail, then [lds_ids] context
+  const int m = blockIdx.y, tid = threadIdx.x;
+  const RowDesc rd = p.rows[m];
+  const int n = p.ctl->ngram[rd.slot];
+  if (n <= 0 || n > SMI_MAX_NGRAM) return;
+  const int plen = min(p.ctl->ngplen[rd.slot], p.max_pos), gen = min(rd.flags, p.max_steps);
+  const int L = plen + gen;
+  if (L + 1 < n) return;
+  const int32_t* pc = p.pctx + (size_t)rd.slot * p.max_pos;
+  const int64_t* gh = p.ghist + rd.slot;
+  auto ctx_global = [&](int i) { return i < plen ? pc[i] : (int32_t)gh[(size_t)(i - plen) * kMaxRows]; };
+  int32_t* s_tail = s_ng;
+  int32_t* s_ctx = s_ng + SMI_MAX_NGRAM;
+  const bool in_lds = L <= p.lds_ids;
+  if (tid < n - 1) s_tail[tid] = ctx_global(L - n + 1 + tid);
+  if (in_lds)
+    for (int i = tid; i < L; i += 256) s_ctx[i] = ctx_global(i);
+  __syncthreads();
+  float* lg = p.logits + (size_t)m * p.V;
+  for (int i = tid; i <= L - n; i += 256) {   // i + n - 1 <= L - 1: every read lies inside the context
+    bool eq = true;
+    if (in_lds) { for (int k = 0; k < n - 1 && eq; ++k) eq = s_ctx[i + k] == s_tail[k]; }
+    else { for (int k = 0; k < n - 1 && eq; ++k) eq = ctx_global(i + k) == s_tail[k]; }
+    if (eq) {
+      const int id = in_lds ? s_ctx[i + n - 1] : ctx_global(i + n - 1);
+      if ((unsigned)id < (unsigned)p.V) lg[id] = -INFINITY;
+    }
   }
 }
 
@@ -3749,12 +3803,15 @@ struct smi_llm {
   int do_sample, top_k; float temperature, top_p; unsigned long long seed;
   // host: what the record set of the sequence in each slot (live or being admitted) asks of a step, F_* bits: its sampling record
   // is SMI_SAMPLING_SAMPLE, it has a penalty record (PenRec::on), returns log-probabilities (Ctl::lp), is constrained
-  // (Ctl::allow, n > 0), has bias entries (SeqRec::n_bias > 0), has stop sequences (SeqRec::n_stop > 0)
+  // (Ctl::allow, n > 0), has bias entries (SeqRec::n_bias > 0), has stop sequences (SeqRec::n_stop > 0), bans repeated
+  // n-grams (Ctl::ngram > 0)
   uint8_t slot_feat[kMaxRows];
   int lm_restrict;              // host: every row of the steps being issued is constrained (the restricted lm_head may run)
   int seq_dirty[kMaxRows];      // host: the slot's device record is not all zero (an admission without a record clears it)
   SeqRec* seq;                  // device: per-slot bias / stop records [kMaxRows] (smi_llm_admit_biased)
   std::vector<SeqRec> hseq;     // host: what the device records hold
+  int32_t* pctx;                // device: prompt ids [max_slots][max_positions], the n-gram ban's context store (smi_llm_admit_ngram)
+  std::vector<int32_t> host_pctx;   // host staging of the rows an admission writes
   int* tlist;                   // device: {count, vocabulary tiles ascending} -- the union of the constrained slots' tiles
   std::vector<int32_t> host_tlist;
   float* lp;                    // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
@@ -3794,7 +3851,8 @@ struct smi_llm {
   // adds the logits rows and k_logprob.  The constraint bits: some row constrained (the full lm_head writes the logits rows and
   // k_penalize applies stage 0), and every row constrained (the restricted lm_head, whose tile list is device data).  The
   // sequence bits: some row has a bias entry (the logits rows, and k_penalize gets the records: stage 0b), some row has a stop
-  // sequence (k_finalize gets the records); with both clear neither kernel is handed the record array.
+  // sequence (k_finalize gets the records); with both clear neither kernel is handed the record array.  The n-gram bit: some
+  // row has no_repeat_ngram_size > 0 (the logits rows, k_ngram_ban before k_penalize); with it clear the step is the step without.
   std::map<uint64_t, hipGraphExec_t> graph_cache;
   hipEvent_t ev0, ev1;
   // host staging
@@ -3874,7 +3932,8 @@ int pages_ensure(smi_llm* L, const int* slots, const int* tokens, int n, hipStre
 }
 KvMap kv_map(const smi_llm* L) { return KvMap{L->paged ? L->ptab : nullptr, L->pshift, L->ppslot}; }
 // What a sequence's record set asks of a step (smi_llm::slot_feat).
-enum : uint8_t { F_SAMPLE = 1, F_PEN = 2, F_LP = 4, F_ALLOW = 8, F_BIAS = 16, F_STOP = 32 };
+enum : uint8_t { F_SAMPLE = 1, F_PEN = 2, F_LP = 4, F_ALLOW = 8, F_BIAS = 16, F_STOP = 32, F_NGRAM = 64 };
+constexpr int kFeatBits = 7;   // bits of the feature mask in graph_key
 // The features of the steps being issued: the OR over EVERY slot, live or being admitted -- not only the step's rows -- plus
 // F_SAMPLE when the handle samples.  An over-estimate is harmless: a row without a feature leaves that feature's kernels at
 // once (the sampler kernels, k_penalize, k_logprob) and k_finalize takes its arg-max, so its bits are those of the step without.
@@ -3888,12 +3947,15 @@ unsigned step_feat(const smi_llm* L) {
 // slot's log-probabilities stay readable until it is reused (Ctl::lp), and seq_dirty says what the device record holds.
 void slot_clear(smi_llm* L, int slot) { L->slot_feat[slot] = 0; }
 // A new generation / session: every sequence inherits the handle's settings, has no penalties, keeps no log-probabilities, is
-// not constrained and has no bias entries or stop sequences (seq_dirty stays: the device records are as they were).
+// not constrained, has no bias entries or stop sequences (seq_dirty stays: the device records are as they were) and bans no
+// n-grams.
 void slots_clear(smi_llm* L) {
   memset(L->hctl.samp, 0, sizeof(L->hctl.samp));
   memset(L->hctl.pen, 0, sizeof(L->hctl.pen));
   memset(L->hctl.lp, 0, sizeof(L->hctl.lp));
   memset(L->hctl.allow, 0, sizeof(L->hctl.allow));
+  memset(L->hctl.ngram, 0, sizeof(L->hctl.ngram));
+  memset(L->hctl.ngplen, 0, sizeof(L->hctl.ngplen));
   memset(L->slot_feat, 0, sizeof(L->slot_feat));
   L->lm_restrict = 0;
 }
@@ -3902,17 +3964,17 @@ void slots_clear(smi_llm* L) {
 bool lm_restricted(const smi_llm* L, unsigned feat) {
   return L->lm_restrict && L->KTh <= 32 && !L->exact && (feat & F_ALLOW);
 }
-// Some row of the step reads the logits rows: a sampling, penalised, biased or log-probability row, or a constrained row whose stage 0
+// Some row of the step reads the logits rows: a sampling, penalised, biased, n-gram or log-probability row, or a constrained row whose stage 0
 // runs in k_penalize (every constrained row of a full-lm_head step; on the restricted path k_penalize then also runs, so the
 // rows it hands on are dense).
 bool logits_needed(const smi_llm* L, unsigned feat) {
-  return (feat & (F_SAMPLE | F_PEN | F_LP | F_BIAS)) || ((feat & F_ALLOW) && !lm_restricted(L, feat));
+  return (feat & (F_SAMPLE | F_PEN | F_LP | F_BIAS | F_NGRAM)) || ((feat & F_ALLOW) && !lm_restricted(L, feat));
 }
-// the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | feature mask << 25 (6 bits) | restricted lm_head << 31 |
-// steps per replay << 32
+// the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | feature mask << 25 (kFeatBits = 7 bits: 25..31) |
+// restricted lm_head << 32 | steps per replay << 33
 uint64_t graph_key(const smi_llm* L, unsigned feat, int K) {
   return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)feat << 25) |
-         ((uint64_t)(lm_restricted(L, feat) ? 1 : 0) << 31) | ((uint64_t)K << 32);
+         ((uint64_t)(lm_restricted(L, feat) ? 1 : 0) << (25 + kFeatBits)) | ((uint64_t)K << (26 + kFeatBits));
 }
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
@@ -4159,7 +4221,7 @@ int eng_create(smi_llm* L) {
 // only: lm_head, the sampler and k_finalize stay launches, so a sampling record applies to the engine's row as to any other)
 bool eng_usable(const smi_llm* L, const RowDesc* rows, int M) {
   return L->eng.enabled && L->eng_on && M == 1 && rows == L->rows && L->identity_slots && !L->paged && L->attn_seg <= 1 && !L->stamps_on &&
-         !(step_feat(L) & (F_LP | F_BIAS | F_STOP));   // (a step with a log-probability, biased or stop-sequence row keeps to the launch path)
+         !(step_feat(L) & (F_LP | F_BIAS | F_STOP | F_NGRAM));   // (a step with a log-probability, biased, stop-sequence or n-gram row keeps to the launch path)
 }
 
 int eng_launch(smi_llm* L, hipStream_t st) {
@@ -4242,6 +4304,16 @@ PenP pen_params(const smi_llm* L, int M) {
   pp.V = L->cfg.vocab_size; pp.nblk = lm_blocks_for(L, M); pp.per = pen_set_ids(pp.V, pp.nblk); pp.hs = L->do_sample;
   pp.seq = nullptr; pp.ghist = L->hist; pp.max_steps = L->max_steps;
   return pp;
+}
+
+// k_ngram_ban's arguments and dynamic LDS for a step: the tail, and the whole context when max_positions ids fit in 48 KiB
+NgramP ngram_params(const smi_llm* L, size_t* lds) {
+  NgramP np;
+  np.logits = L->logits; np.ctl = L->ctl; np.rows = L->rows; np.pctx = L->pctx; np.ghist = L->hist;
+  np.V = L->cfg.vocab_size; np.max_pos = L->cfg.max_positions; np.max_steps = L->max_steps;
+  np.lds_ids = L->cfg.max_positions <= 12288 - SMI_MAX_NGRAM ? L->cfg.max_positions : 0;
+  *lds = (size_t)(SMI_MAX_NGRAM + np.lds_ids) * 4;
+  return np;
 }
 
 // the sampler kernels' arguments for a step of M rows (the handle's settings; the lm_head's maxima as the top-k bound)
@@ -4558,8 +4630,14 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KFIN: {
       const unsigned feat = step_feat(L);
       FinP f = fin_params(L, M);
-      // rows neither penalised, biased nor constrained leave k_penalize at once
-      if ((feat & (F_PEN | F_BIAS)) || ((feat & F_ALLOW) && logits_needed(L, feat))) {
+      if (feat & F_NGRAM) {   // rows with n = 0 leave at once; the others get -inf at the ids that would repeat an n-gram
+        size_t lds;
+        const NgramP np = ngram_params(L, &lds);
+        hipLaunchKernelGGL(k_ngram_ban, dim3(1, M), dim3(256), lds, st, np);
+        SMI_LAUNCH_CHECK();
+      }
+      // rows neither penalised, biased, n-gram banned nor constrained leave k_penalize at once
+      if ((feat & (F_PEN | F_BIAS | F_NGRAM)) || ((feat & F_ALLOW) && logits_needed(L, feat))) {
         PenP pp = pen_params(L, M);
         if (feat & F_BIAS) pp.seq = L->seq;
         hipLaunchKernelGGL(k_penalize, dim3((pp.nblk + kPenWaves - 1) / kPenWaves, M), dim3(256), 0, st, pp);
@@ -4900,6 +4978,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->tlist = nullptr;
   memset(L->seq_dirty, 0, sizeof(L->seq_dirty));
   L->seq = nullptr; L->hseq.assign(kMaxRows, SeqRec{});
+  L->pctx = nullptr;
   L->poll_dev = nullptr; L->poll_host = nullptr;
   L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
@@ -4965,6 +5044,9 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   // per-slot bias / stop records (smi_llm_admit_biased): all zero = none
   SMI_ALLOC(L->seq, (size_t)kMaxRows * sizeof(SeqRec));
   SMI_HIP(hipMemset(L->seq, 0, (size_t)kMaxRows * sizeof(SeqRec)));
+  // the n-gram ban's prompt ids per slot (smi_llm_admit_ngram): a row is written by the admission that reads it
+  SMI_ALLOC(L->pctx, (size_t)cfg->max_slots * cfg->max_positions * 4);
+  SMI_HIP(hipMemset(L->pctx, 0, (size_t)cfg->max_slots * cfg->max_positions * 4));
   // smi_llm_poll's staging: {count, finished, ids[cap]} per listed slot, cap <= max_steps, and its pinned host copy
   SMI_ALLOC(L->poll_dev, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8);
 #undef SMI_ALLOC
@@ -5044,7 +5126,7 @@ int smi_llm_destroy(smi_llm* L) {
   work_free(L->big);
   void* ptrs[] = {L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
                   L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->pslab, L->apart,
-                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist, L->poll_dev, L->seq};
+                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist, L->poll_dev, L->seq, L->pctx};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (L->poll_host) (void)hipHostFree(L->poll_host);
@@ -5446,6 +5528,33 @@ static int allow_tiles_upload(smi_llm* L, hipStream_t st) {
   return SMI_OK;
 }
 
+// The static survivor count of a take: the ids of its allowed set (the vocabulary without one) minus the distinct last ids of
+// its -inf bias entries, minus the eos ids when min_new_tokens > 0.  al / pen / q: the take's records or null.
+static long survivors(const smi_llm* L, const smi_allow_params* al, const smi_penalty_params* pen, const smi_seq_params* q) {
+  const int V = L->cfg.vocab_size;
+  const bool con = al && al->n_ranges > 0;
+  auto allowed = [&](long long id) {
+    if (!con) return true;
+    for (int i = 0; i < al->n_ranges; ++i)
+      if (id >= al->lo[i] && id < al->hi[i]) return true;
+    return false;
+  };
+  long covered = V;
+  if (con) { covered = 0; for (int i = 0; i < al->n_ranges; ++i) covered += al->hi[i] - al->lo[i]; }
+  std::vector<long long> gone;   // distinct ids of the set that cannot be chosen
+  auto drop = [&](long long id) {
+    if (id < 0 || id >= V || !allowed(id)) return;
+    for (long long g : gone) if (g == id) return;
+    gone.push_back(id);
+  };
+  if (q)
+    for (int i = 0; i < q->n_bias; ++i)
+      if (std::isinf(q->bias[i])) drop(q->bias_ids[(size_t)i * SMI_MAX_SEQ_LEN + q->bias_len[i] - 1]);
+  if (pen && pen->min_new_tokens > 0)
+    for (int e = 0; e < L->hctl.n_eos; ++e) drop(L->hctl.eos[e]);
+  return covered - (long)gone.size();
+}
+
 // Checks of one bias / stop record (smi_llm_admit_biased, smi_llm_debug_seqbias; before anything of the handle is touched).
 // al / pen: the take's allow and penalty records or null (al has passed validate_allow).
 static int validate_seq(const smi_llm* L, const smi_seq_params& q, const smi_allow_params* al, const smi_penalty_params* pen, int j) {
@@ -5476,30 +5585,24 @@ static int validate_seq(const smi_llm* L, const smi_seq_params& q, const smi_all
       SMI_REQUIRE(!same(e, len, q.stop_ids + (size_t)f * SMI_MAX_SEQ_LEN, q.stop_len[f]),
                   "smi_llm_admit_biased: seq[%d] stop sequences %d and %d are the same", j, f, i);
   }
-  // a survivor: the allowed set (or the vocabulary) minus the distinct last ids of the -inf entries -- and minus the eos ids while
-  // min_new_tokens bans them -- is not empty
-  const bool con = al && al->n_ranges > 0;
-  auto allowed = [&](long long id) {
-    if (!con) return true;
-    for (int i = 0; i < al->n_ranges; ++i)
-      if (id >= al->lo[i] && id < al->hi[i]) return true;
-    return false;
-  };
-  long covered = V;
-  if (con) { covered = 0; for (int i = 0; i < al->n_ranges; ++i) covered += al->hi[i] - al->lo[i]; }
-  std::vector<long long> gone;   // distinct ids of the set that cannot be chosen
-  auto drop = [&](long long id) {
-    if (id < 0 || id >= V || !allowed(id)) return;
-    for (long long g : gone) if (g == id) return;
-    gone.push_back(id);
-  };
-  for (int i = 0; i < q.n_bias; ++i)
-    if (std::isinf(q.bias[i])) drop(q.bias_ids[(size_t)i * SMI_MAX_SEQ_LEN + q.bias_len[i] - 1]);
-  SMI_REQUIRE(covered > (long)gone.size(), "smi_llm_admit_biased: seq[%d] bans every id the row could emit", j);
-  if (pen && pen->min_new_tokens > 0) {
-    for (int e = 0; e < L->hctl.n_eos; ++e) drop(L->hctl.eos[e]);
-    SMI_REQUIRE(covered > (long)gone.size(), "smi_llm_admit_biased: seq[%d] leaves only eos ids but min_new_tokens=%d bans them", j, pen->min_new_tokens);
-  }
+  // a survivor is left, with the eos ids and again without them while min_new_tokens bans them
+  SMI_REQUIRE(survivors(L, al, nullptr, &q) > 0, "smi_llm_admit_biased: seq[%d] bans every id the row could emit", j);
+  if (pen && pen->min_new_tokens > 0)
+    SMI_REQUIRE(survivors(L, al, pen, &q) > 0, "smi_llm_admit_biased: seq[%d] leaves only eos ids but min_new_tokens=%d bans them", j, pen->min_new_tokens);
+  return SMI_OK;
+}
+
+// Checks of one no_repeat_ngram_size (smi_llm_admit_ngram; before anything of the handle is touched).  al / pen / q: the take's
+// allow, penalty and bias records or null (they have passed their own checks).  A step bans at most max_positions - 1 distinct
+// ids, so a row with n > 0 needs max_positions survivors: the allowed set (or the vocabulary) minus the distinct last ids of
+// the -inf bias entries, minus the eos ids when min_new_tokens > 0 -- then no row reaches selection with every logit -inf.
+static int validate_ngram(const smi_llm* L, int32_t n, const smi_allow_params* al, const smi_penalty_params* pen, const smi_seq_params* q, int j) {
+  SMI_REQUIRE(n >= 0 && n <= SMI_MAX_NGRAM, "smi_llm_admit_ngram: no_repeat_ngram[%d]=%d outside 0..%d", j, n, SMI_MAX_NGRAM);
+  if (n == 0) return SMI_OK;
+  const long left = survivors(L, al, pen, q);
+  SMI_REQUIRE(left >= (long)L->cfg.max_positions,
+              "smi_llm_admit_ngram: no_repeat_ngram[%d]=%d needs %d selectable ids (max_positions), the row has %ld", j, n,
+              L->cfg.max_positions, left);
   return SMI_OK;
 }
 
@@ -5533,17 +5636,20 @@ struct AdmitReq {
   const int32_t* want_lp;
   const smi_allow_params* allow;
   const smi_seq_params* seq;
+  const int32_t* ngram;
 };
 
 // What a KV slot holds of its sequence on the host: the admission number, the records of Ctl and the feature bits.
 struct SlotRecs {
-  int32_t seqid; SampRec samp; PenRec pen; int32_t lp; AllowRec allow; uint8_t feat;
+  int32_t seqid; SampRec samp; PenRec pen; int32_t lp; AllowRec allow; int32_t ngram, ngplen; uint8_t feat;
 };
 static SlotRecs recs_get(const smi_llm* L, int sl) {
-  return SlotRecs{L->hctl.seqid[sl], L->hctl.samp[sl], L->hctl.pen[sl], L->hctl.lp[sl], L->hctl.allow[sl], L->slot_feat[sl]};
+  return SlotRecs{L->hctl.seqid[sl], L->hctl.samp[sl], L->hctl.pen[sl], L->hctl.lp[sl], L->hctl.allow[sl], L->hctl.ngram[sl],
+                  L->hctl.ngplen[sl], L->slot_feat[sl]};
 }
 static void recs_put(smi_llm* L, int sl, const SlotRecs& r) {
   L->hctl.seqid[sl] = r.seqid; L->hctl.samp[sl] = r.samp; L->hctl.pen[sl] = r.pen; L->hctl.lp[sl] = r.lp; L->hctl.allow[sl] = r.allow;
+  L->hctl.ngram[sl] = r.ngram; L->hctl.ngplen[sl] = r.ngplen;
   L->slot_feat[sl] = r.feat;
 }
 
@@ -5555,6 +5661,7 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
   const smi_penalty_params* pens = rq.pens;
   const smi_allow_params* allow = rq.allow;
   const smi_seq_params* seq = rq.seq;
+  const int32_t* ngram = rq.ngram;
   SMI_REQUIRE(L && ids && lens && slots_out, "smi_llm_admit: null argument");
   if (!L->started || !L->session) { smi_set_error("smi_llm_admit outside a session (smi_llm_session_begin first)"); return SMI_ESTATE; }
   const int slot_cap = L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows;
@@ -5581,6 +5688,11 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
     for (int j = 0; j < N; ++j) {
       const int rcq = validate_seq(L, seq[j], allow ? &allow[j] : nullptr, pens ? &pens[j] : nullptr, j);
       if (rcq) return rcq;
+    }
+  if (ngram)
+    for (int j = 0; j < N; ++j) {
+      const int rcn = validate_ngram(L, ngram[j], allow ? &allow[j] : nullptr, pens ? &pens[j] : nullptr, seq ? &seq[j] : nullptr, j);
+      if (rcn) return rcn;
     }
   int rc;
   std::vector<RowDesc> live;
@@ -5636,7 +5748,10 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
     r.pen = pen_record(pens ? &pens[j] : nullptr);
     r.lp = want_lp ? want_lp[j] : 0;
     r.allow = allow_record(allow ? &allow[j] : nullptr, L->cfg.vocab_size);
-    r.feat = (r.samp.mode == SMI_SAMPLING_SAMPLE ? F_SAMPLE : 0) | (r.pen.on ? F_PEN : 0) | (r.lp ? F_LP : 0) | (r.allow.n > 0 ? F_ALLOW : 0);
+    r.ngram = ngram ? ngram[j] : 0;
+    r.ngplen = r.ngram > 0 ? lens_j[j] : 0;
+    r.feat = (r.samp.mode == SMI_SAMPLING_SAMPLE ? F_SAMPLE : 0) | (r.pen.on ? F_PEN : 0) | (r.lp ? F_LP : 0) | (r.allow.n > 0 ? F_ALLOW : 0) |
+             (r.ngram > 0 ? F_NGRAM : 0);
     recs_put(L, slots[j], r);   // (F_BIAS / F_STOP: with the sequence records below)
   }
   // undo: nothing was admitted -- sequence numbers, records and pages (and page references) as before (the device copy is
@@ -5669,6 +5784,26 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
       undo();
       smi_set_error("smi_llm_admit_biased: uploading the sequence records failed");
       return SMI_EHIP;
+    }
+  }
+  // the prompt ids of the takes that ban n-grams -> their slots' rows of the context store (a fork's followers get their
+  // leader's prompt); a slot admitted without the feature never reads its row
+  if (ngram) {
+    std::vector<int32_t>& H = L->host_pctx;
+    H.clear();
+    for (int j = 0; j < N; ++j)
+      if (ngram[j] > 0)
+        for (int t = 0; t < lens_j[j]; ++t) H.push_back((int32_t)ids[(size_t)src[j] * P_max + t]);
+    size_t at = 0;
+    for (int j = 0; j < N; ++j) {
+      if (ngram[j] <= 0) continue;
+      // (pageable source: staged before the call returns; host_pctx is rebuilt only by the next admission)
+      if (hipMemcpyAsync(L->pctx + (size_t)slots[j] * L->cfg.max_positions, H.data() + at, (size_t)lens_j[j] * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
+        undo();
+        smi_set_error("smi_llm_admit_ngram: uploading the prompt ids failed");
+        return SMI_EHIP;
+      }
+      at += (size_t)lens_j[j];
     }
   }
   // the fork copy's work list: each follower gets the leader's positions it does not share -- 0 .. L-2 (contiguous), S P .. L-2
@@ -5759,6 +5894,12 @@ int smi_llm_admit_biased(smi_llm* L, const int64_t* ids, const int32_t* lens, in
                          const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
                          const smi_allow_params* allow, const smi_seq_params* seq, int32_t* slots_out, void* stream) {
   return admit(L, AdmitReq{ids, lens, n, P_max, n_ret, params, pens, want_lp, allow, seq}, slots_out, (hipStream_t)stream);
+}
+int smi_llm_admit_ngram(smi_llm* L, const int64_t* ids, const int32_t* lens, int n, int P_max, const int32_t* n_ret,
+                        const smi_sample_params* params, const smi_penalty_params* pens, const int32_t* want_lp,
+                        const smi_allow_params* allow, const smi_seq_params* seq, const int32_t* no_repeat_ngram, int32_t* slots_out,
+                        void* stream) {
+  return admit(L, AdmitReq{ids, lens, n, P_max, n_ret, params, pens, want_lp, allow, seq, no_repeat_ngram}, slots_out, (hipStream_t)stream);
 }
 
 int smi_llm_retire(smi_llm* L, int slot, void* stream) {
@@ -6642,6 +6783,72 @@ int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, cons
   SMI_HIP(hipDeviceSynchronize());
   SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n_rows * V * 4, hipMemcpyDeviceToHost));
   SMI_HIP(hipMemcpy(finished_out, L->finished, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+  std::vector<RowDesc> after(kMaxRows);
+  SMI_HIP(hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost));
+  for (int m = 0; m < n_rows; ++m) token_out[m] = after[m].token;
+  alone_end(L);
+  return SMI_OK;
+}
+
+// Tests: the n-gram ban, k_penalize and k_finalize alone on caller rows (see sparkmi_debug.h).
+int smi_llm_debug_ngram(smi_llm* L, const float* logits_host, int n_rows, const int32_t* ngram_host, const int64_t* ctx_host,
+                        const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, float* logits_out, int32_t* token_out) {
+  SMI_REQUIRE(L && logits_host && ngram_host && ctx_host && ctx_len_host && prompt_len_host && logits_out && token_out,
+              "smi_llm_debug_ngram: null argument");
+  SMI_REQUIRE(n_rows >= 1 && n_rows <= L->cfg.max_slots && n_rows <= kMaxRows, "smi_llm_debug_ngram: n_rows=%d outside 1..max_slots", n_rows);
+  const int V = L->cfg.vocab_size, P = L->cfg.max_positions;
+  for (int m = 0; m < n_rows; ++m) {
+    SMI_REQUIRE(ngram_host[m] >= 0 && ngram_host[m] <= SMI_MAX_NGRAM, "smi_llm_debug_ngram: ngram[%d]=%d outside 0..%d", m, ngram_host[m], SMI_MAX_NGRAM);
+    SMI_REQUIRE(prompt_len_host[m] >= 0 && prompt_len_host[m] <= ctx_len_host[m] && ctx_len_host[m] <= ctx_cap && prompt_len_host[m] <= P,
+                "smi_llm_debug_ngram: row %d: 0 <= prompt_len <= ctx_len <= ctx_cap, prompt_len <= max_positions does not hold", m);
+    SMI_REQUIRE(ctx_len_host[m] - prompt_len_host[m] < L->max_steps, "smi_llm_debug_ngram: row %d: more generated tokens than the history holds", m);
+    for (int t = 0; t < ctx_len_host[m]; ++t)
+      SMI_REQUIRE(ctx_host[(size_t)m * ctx_cap + t] >= 0 && ctx_host[(size_t)m * ctx_cap + t] < V, "smi_llm_debug_ngram: ctx[%d][%d] outside the vocabulary", m, t);
+  }
+  const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
+  std::vector<float> pv;
+  std::vector<int32_t> pi;
+  block_maxima(logits_host, n_rows, V, nblk, per, pv, pi);
+  int32_t gen[kMaxRows];   // tokens emitted so far, per row
+  int max_gen = 0;
+  for (int m = 0; m < n_rows; ++m) {
+    gen[m] = ctx_len_host[m] - prompt_len_host[m];
+    max_gen = gen[m] > max_gen ? gen[m] : max_gen;
+  }
+  { const int rcb = alone_begin(L, n_rows, gen); if (rcb) return rcb; }
+  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
+  std::vector<int32_t> pctx((size_t)n_rows * P, 0);
+  for (int m = 0; m < n_rows; ++m) {
+    L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: k_penalize writes its processed logits back; k_finalize gets no
+    L->hctl.samp[m].top_k = 1; L->hctl.samp[m].inv_temp = 1.f; L->hctl.samp[m].top_p = 1.f;   // sampler tokens and takes the arg-max)
+    L->hctl.ngram[m] = ngram_host[m]; L->hctl.ngplen[m] = prompt_len_host[m];
+    for (int t = 0; t < prompt_len_host[m]; ++t) pctx[(size_t)m * P + t] = (int32_t)ctx_host[(size_t)m * ctx_cap + t];
+  }
+  SMI_HIP(hipMemcpy(L->pctx, pctx.data(), pctx.size() * 4, hipMemcpyHostToDevice));
+  if (max_gen > 0) {   // the generated tokens of every row, as k_finalize would have left them
+    std::vector<int64_t> hist((size_t)max_gen * kMaxRows, 0);
+    for (int m = 0; m < n_rows; ++m)
+      for (int t = prompt_len_host[m]; t < ctx_len_host[m]; ++t) hist[(size_t)(t - prompt_len_host[m]) * kMaxRows + m] = ctx_host[(size_t)m * ctx_cap + t];
+    SMI_HIP(hipMemcpy(L->hist, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
+  }
+  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
+  size_t lds;
+  const NgramP np = ngram_params(L, &lds);
+  hipLaunchKernelGGL(k_ngram_ban, dim3(1, n_rows), dim3(256), lds, 0, np);
+  SMI_LAUNCH_CHECK();
+  PenP pp = pen_params(L, n_rows);
+  pp.hs = 0;
+  hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
+  SMI_LAUNCH_CHECK();
+  FinP f = fin_params(L, n_rows);
+  f.hs = 0;
+  hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
+  SMI_LAUNCH_CHECK();
+  SMI_HIP(hipDeviceSynchronize());
+  SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n_rows * V * 4, hipMemcpyDeviceToHost));
   std::vector<RowDesc> after(kMaxRows);
   SMI_HIP(hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost));
   for (int m = 0; m < n_rows; ++m) token_out[m] = after[m].token;

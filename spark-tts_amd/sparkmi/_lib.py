@@ -98,6 +98,7 @@ class AllowParams(C.Structure):
 
 
 SMI_MAX_BIAS_SEQS, SMI_MAX_STOP_SEQS, SMI_MAX_SEQ_LEN = 32, 8, 8
+SMI_MAX_NGRAM = 64
 
 
 class SeqParams(C.Structure):
@@ -141,6 +142,8 @@ SYMBOLS = {
                                        _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(C.c_int32), _VP]),
     "smi_llm_admit_biased": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams),
                                   _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(SeqParams), _P(C.c_int32), _VP]),
+    "smi_llm_admit_ngram": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams),
+                                 _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(SeqParams), _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_poll": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_status": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_forward_logits": (_I, [_VP, _P(C.c_int64), _I, _VP, _VP]),
@@ -188,6 +191,8 @@ DEBUG_SYMBOLS = {
                                     _P(C.c_int32)]),
     "smi_llm_debug_seqbias": (_I, [_VP, _P(C.c_float), _I, _P(SeqParams), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _I,
                                    _P(C.c_int32), _P(C.c_float), _P(C.c_int32), _P(C.c_int32)]),
+    "smi_llm_debug_ngram": (_I, [_VP, _P(C.c_float), _I, _P(C.c_int32), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _I,
+                                 _P(C.c_float), _P(C.c_int32)]),
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),

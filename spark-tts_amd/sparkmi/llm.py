@@ -191,6 +191,37 @@ def seq_records(requests: Optional[Sequence[Optional[Mapping]]], n: int, vocab_s
     return recs
 
 
+# key of a request's n-gram ban, in the same dicts (transformers' / TensorRT-LLM's no_repeat_ngram_size; smi_llm_admit_ngram;
+# include/sparkmi.h states the semantics): an int 0 .. SMI_MAX_NGRAM, 0 = none
+NGRAM_KEY = "no_repeat_ngram_size"
+
+
+def ngram_size(v, what: str = NGRAM_KEY) -> int:
+    """A ``no_repeat_ngram_size``: an int (a bool is refused) in 0 .. ``SMI_MAX_NGRAM``; ValueError otherwise, before any device
+    call."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{what} must be an int, not {v!r}")
+    if not 0 <= int(v) <= _lib.SMI_MAX_NGRAM:
+        raise ValueError(f"{what}={int(v)} outside 0..{_lib.SMI_MAX_NGRAM}")
+    return int(v)
+
+
+def ngram_records(requests: Optional[Sequence[Optional[Mapping]]], n: int):
+    """One int32 ``no_repeat_ngram_size`` per prompt from the ``NGRAM_KEY`` of the request dicts, or None when no request asks
+    for a ban (no key, or 0 everywhere: the admission then keeps the route and bits it has without it).  Every value is checked
+    here first (``ngram_size``); the survivor rule is the library's."""
+    if requests is None:
+        return None
+    requests = list(requests)
+    if len(requests) != n:
+        raise ValueError(f"sampling: {len(requests)} entries for {n} prompts")
+    sizes = np.zeros(n, dtype=np.int32)
+    for i, d in enumerate(requests):
+        if d is not None and d.get(NGRAM_KEY) is not None:
+            sizes[i] = ngram_size(d[NGRAM_KEY], f"sampling[{i}].{NGRAM_KEY}")
+    return sizes if sizes.any() else None
+
+
 # key of a request's number of takes (TensorRT-LLM's num_return_sequences; smi_llm_admit_forked): SparkLLM.serve and SparkTTS
 # requests take it out of the dict before its records are built
 FORK_KEY = "num_return_sequences"
@@ -297,7 +328,7 @@ def sampling_records(sampling: Optional[Sequence[Optional[Mapping]]], n: int, de
         raise ValueError(f"sampling: {len(sampling)} entries for {n} prompts")
     if all(d is None for d in sampling):
         return None
-    known = SAMPLING_KEYS + PENALTY_KEYS + LOGPROB_KEYS + (ALLOW_KEY,) + SEQ_KEYS
+    known = SAMPLING_KEYS + PENALTY_KEYS + LOGPROB_KEYS + (ALLOW_KEY,) + SEQ_KEYS + (NGRAM_KEY,)
     for i, d in enumerate(sampling):
         bad = set(d or ()) - set(known)
         if bad:
@@ -531,15 +562,15 @@ class SparkLLM:
               n_return: Optional[Sequence[int]] = None) -> List[int]:
         """Prefill new prompts into free KV slots (first token emitted); returns their slot ids.  ``sampling``: one dict or
         None per prompt; None everywhere (the default): every sequence follows ``set_sampling`` and carries no record.  The
-        keys of a dict make up to five records for its sequence: its own token selection (``SAMPLING_KEYS``;
+        keys of a dict make up to six records for its sequence: its own token selection (``SAMPLING_KEYS``;
         ``sampling_records``), logits penalties (``PENALTY_KEYS``; ``penalty_records``), ``return_log_probs`` (``LOGPROB_KEYS``,
         a bool; ``logprob_flags`` -- the flagged sequences' log-probabilities are read with ``slots_logprobs``),
         ``allowed_token_ids`` (``ALLOW_KEY``: an iterable of ids; ``allow_records`` -- the sequence emits only ids of its set,
         eos ids are not added to it) and ``sequence_bias`` / ``bad_words_ids`` / ``stop_sequences`` (``SEQ_KEYS``;
-        ``seq_records``).  ``n_return``: one int >= 1 per prompt -- that many takes of the prompt, its prompt prefilled once;
+        ``seq_records``), and ``no_repeat_ngram_size`` (``NGRAM_KEY``; ``ngram_records``).  ``n_return``: one int >= 1 per prompt -- that many takes of the prompt, its prompt prefilled once;
         ``sampling`` stays one dict per prompt and is expanded per take (``expand_takes``), and the result is the flat,
         prompt-major slot list.
-        Every admission is one ``smi_llm_admit_biased`` call.  A kind of record that no request asks for is passed as NULL, and
+        Every admission is one ``smi_llm_admit_ngram`` call.  A kind of record that no request asks for is passed as NULL, and
         so is ``n_return`` None: by the contract of include/sparkmi.h that is exactly the narrower entry point
         (``smi_llm_admit`` when all are NULL), with its route and bits."""
         n = N = len(prompts)
@@ -563,12 +594,14 @@ class SparkLLM:
         flags = logprob_flags(takes, N)
         allow = allow_records(takes, N, self.cfg.vocab_size)
         seqs = seq_records(takes, N, self.cfg.vocab_size, getattr(self, "_session_eos", ()))
+        ngr = ngram_records(takes, N)
         slots = np.zeros(N, dtype=np.int32)
         i32 = C.POINTER(C.c_int32)
-        self._lib.check(self._lib.smi_llm_admit_biased(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), lens.ctypes.data_as(i32), n, pmax,
-                                                       None if nret is None else nret.ctypes.data_as(i32), recs, pens,
-                                                       None if flags is None else flags.ctypes.data_as(i32), allow, seqs,
-                                                       slots.ctypes.data_as(i32), self._stream()), "smi_llm_admit")
+        self._lib.check(self._lib.smi_llm_admit_ngram(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64)), lens.ctypes.data_as(i32), n, pmax,
+                                                      None if nret is None else nret.ctypes.data_as(i32), recs, pens,
+                                                      None if flags is None else flags.ctypes.data_as(i32), allow, seqs,
+                                                      None if ngr is None else ngr.ctypes.data_as(i32),
+                                                      slots.ctypes.data_as(i32), self._stream()), "smi_llm_admit")
         return slots.tolist()
 
     def retire(self, slot: int) -> None:
@@ -988,6 +1021,31 @@ class SparkLLM:
                                                         out.ctypes.data_as(C.POINTER(C.c_float)), tok.ctypes.data_as(i32),
                                                         fin.ctypes.data_as(i32)), "smi_llm_debug_seqbias")
         return out, tok, fin
+
+    def debug_ngram(self, logits: np.ndarray, sizes: Sequence[int], contexts: Sequence[Sequence[int]], prompt_lens: Sequence[int]):
+        """The n-gram ban, ``k_penalize`` and ``k_finalize`` alone (``smi_llm_debug_ngram``) on caller rows: ``logits`` [n][vocab]
+        f32, one ``no_repeat_ngram_size`` and one context (prompt + generated ids, the first ``prompt_lens[i]`` -- 0 or more --
+        the prompt) per row.  Returns (the rows after the stage, the arg-max token per row)."""
+        self._need_diag("debug_ngram")
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        n = lg.shape[0]
+        if lg.shape != (n, self.cfg.vocab_size) or len(sizes) != n or len(contexts) != n or len(prompt_lens) != n:
+            raise ValueError("debug_ngram: logits [n][vocab], n sizes, n contexts, n prompt lengths")
+        ng = np.asarray([ngram_size(v) for v in sizes], dtype=np.int32)
+        cl = np.asarray([len(c) for c in contexts], dtype=np.int32)
+        cap = max(int(cl.max()), 1)
+        ctx = np.zeros((n, cap), dtype=np.int64)
+        for i, c in enumerate(contexts):
+            ctx[i, : len(c)] = np.asarray(c, dtype=np.int64)
+        pl = np.ascontiguousarray(prompt_lens, dtype=np.int32)
+        out = np.empty_like(lg)
+        tok = np.zeros(n, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._lib.check(self._lib.smi_llm_debug_ngram(self._h, lg.ctypes.data_as(C.POINTER(C.c_float)), n, ng.ctypes.data_as(i32),
+                                                      ctx.ctypes.data_as(C.POINTER(C.c_int64)), cl.ctypes.data_as(i32),
+                                                      pl.ctypes.data_as(i32), cap, out.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      tok.ctypes.data_as(i32)), "smi_llm_debug_ngram")
+        return out, tok
 
     def debug_logprob(self, logits: np.ndarray, temperature: Sequence[float], tokens: Sequence[int]) -> np.ndarray:
         """The log-probability kernels alone (``smi_llm_debug_logprob``: k_logprob and k_finalize's combine) on caller rows:

@@ -20,8 +20,8 @@ import torch
 from . import _lib
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
-from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, PENALTY_KEYS, SAMPLING_KEYS, SEQ_KEYS, SparkLLM,
-                  eos_ids_from_generation_config, num_returns, penalty_neutral, seq_entries)
+from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, NGRAM_KEY, PENALTY_KEYS, SAMPLING_KEYS, SEQ_KEYS, SparkLLM,
+                  eos_ids_from_generation_config, ngram_size, num_returns, penalty_neutral, seq_entries)
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
 from .streaming import ChunkScheduler, StreamMux
@@ -66,7 +66,9 @@ def _request_sampling(r: dict, speech_ids=None, eos: Sequence[int] = (), vocab_s
     ``allowed_token_ids`` (``ALLOW_KEY``) and ``speech_tokens_only`` (``SPEECH_ONLY_KEY``: True -> ``speech_ids()``) become
     the request's allowed-token set (both given: their intersection); include/sparkmi.h, smi_llm_admit_constrained.
     With ``vocab_size`` given, ``sequence_bias`` / ``bad_words_ids`` / ``stop_sequences`` (``SEQ_KEYS``) and ``eos_bias``
-    (``EOS_BIAS_KEY``, over the eos ids ``eos``) are checked and carried too (``_request_seq``; smi_llm_admit_biased)."""
+    (``EOS_BIAS_KEY``, over the eos ids ``eos``) are checked and carried too (``_request_seq``; smi_llm_admit_biased).
+    ``no_repeat_ngram_size`` (``NGRAM_KEY``) is checked (``ngram_size``: an int in 0 .. SMI_MAX_NGRAM, not a bool) and kept when
+    it is > 0 (smi_llm_admit_ngram); 0 is dropped, so such a request keeps the route of the request without the key."""
     d = {k: r[k] for k in SAMPLING_KEYS if k in r}
     speech = r.get(SPEECH_ONLY_KEY, False)
     if not isinstance(speech, (bool, np.bool_)):
@@ -86,6 +88,8 @@ def _request_sampling(r: dict, speech_ids=None, eos: Sequence[int] = (), vocab_s
             raise ValueError(f"{k} must be a bool, not {r[k]!r}")
         if r.get(k):
             d[k] = True
+    if r.get(NGRAM_KEY) is not None and ngram_size(r[NGRAM_KEY]) > 0:
+        d[NGRAM_KEY] = ngram_size(r[NGRAM_KEY])
     if vocab_size is not None:
         d.update(_request_seq(r, eos, vocab_size))
     return d or None
@@ -221,7 +225,7 @@ class SparkTTS:
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                   min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False,
                   num_return_sequences: int = 1, allowed_token_ids: Optional[Sequence[int]] = None,
-                  speech_tokens_only: bool = False):
+                  speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate``.  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
@@ -232,17 +236,21 @@ class SparkTTS:
         takes vocoded together -- the same as ``inference_batch`` of the request n times; with its own ``seed``, take j is
         the call alone with ``seed + j``.  ``allowed_token_ids`` (an iterable of ids) / ``speech_tokens_only=True`` (the
         tokenizer's added vocabulary and the eos ids: every ordinary BPE text id is banned): every generated id lies in that
-        set (include/sparkmi.h, smi_llm_admit_constrained; eos ids are not added to an ``allowed_token_ids`` set)."""
+        set (include/sparkmi.h, smi_llm_admit_constrained; eos ids are not added to an ``allowed_token_ids`` set).
+        ``no_repeat_ngram_size=n > 0`` (transformers' argument of that name; include/sparkmi.h, smi_llm_admit_ngram): no run of n
+        ids occurs twice in prompt + generated ids, which rules out the looping failure of the speech-token generator."""
         n_takes = num_returns(num_return_sequences)
         if n_takes > self._max_batch:
             raise ValueError(f"num_return_sequences={n_takes} > max_batch={self._max_batch}")
+        n_gram = ngram_size(no_repeat_ngram_size)   # (a bool is refused here as it is in the request key)
         pen = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                    frequency_penalty=frequency_penalty, min_new_tokens=min_new_tokens, penalize_prompt=penalize_prompt)
         return self.inference_batch([dict(text=text, prompt_speech_path=prompt_speech_path, prompt_text=prompt_text,
                                           gender=gender, pitch=pitch, speed=speed, prompt_tokens=prompt_tokens, **pen,
                                           **({FORK_KEY: n_takes} if n_takes > 1 else {}),
                                           **({ALLOW_KEY: allowed_token_ids} if allowed_token_ids is not None else {}),
-                                          **({SPEECH_ONLY_KEY: speech_tokens_only} if speech_tokens_only else {}))],
+                                          **({SPEECH_ONLY_KEY: speech_tokens_only} if speech_tokens_only else {}),
+                                          **({NGRAM_KEY: n_gram} if n_gram > 0 else {}))],
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                                     max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs)[0]
 
@@ -262,8 +270,8 @@ class SparkTTS:
         (waveform, info), info as in ``inference``; such a batch runs through the admission path.
         A request's ``num_return_sequences`` key (an int >= 1): that many takes of it, its prompt prefilled once; its result
         is a list of one result per take.  All takes together are at most ``max_batch``.  A request's ``allowed_token_ids``
-        / ``speech_tokens_only`` keys (as in ``inference``) restrict its generated ids; such a batch runs through the
-        admission path."""
+        / ``speech_tokens_only`` keys (as in ``inference``) restrict its generated ids, and its ``no_repeat_ngram_size`` key
+        (as in ``inference``) bans repeated n-grams; such a batch runs through the admission path."""
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         n_takes = _take_counts(requests, self._max_batch)
