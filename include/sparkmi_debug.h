@@ -1,5 +1,5 @@
 /*
- * sparkmi_debug.h -- diagnostics and test entry points of the LLM half.  NOT part of the product ABI: these symbols exist
+ * sparkmi_debug.h -- diagnostics and test entry points (the LLM half; the conv kernel forms of the vocoder / encoder).  NOT part of the product ABI: these symbols exist
  * only in libsparkmi_diag.so (spark-tts_amd/csrc built with -DSMI_DIAG), which also exports everything sparkmi.h declares and
  * -- unlike libsparkmi.so -- honours the SPARKMI_* environment switches listed in DESIGN.md 6.1.  Loaded by tools/, by
  * bench.py's per-kernel probes and by the tests that look inside a step (tests/test_llm_ops_gpu.py, test_engine_gpu.py).
@@ -117,6 +117,82 @@ int smi_llm_debug_seqbias(smi_llm* h, const float* logits_host, int n_rows, cons
  * emits (lowest id on ties).  Synchronises; ends the current generation. */
 int smi_llm_debug_ngram(smi_llm* h, const float* logits_host, int n_rows, const int32_t* ngram_host, const int64_t* ctx_host,
                         const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, float* logits_out, int32_t* token_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Conv kernel forms (csrc/smi_net.h): which instantiation of k_conv / k_convb / k_convbT / k_conv_c1 / k_gemv1 the launch
+ * builder picks for a layer and a call shape, and one conv on caller tensors run through exactly that choice
+ * (tests/test_conv_forms_cpu.py, tests/test_conv_forms_gpu.py).
+ * ---------------------------------------------------------------------------------------- */
+enum { SMI_CONV_K_CONV = 0, SMI_CONV_K_CONVB = 1, SMI_CONV_K_CONVBT = 2, SMI_CONV_K_C1 = 3, SMI_CONV_K_GEMV = 4 };
+typedef struct smi_conv_form {
+  int32_t kernel;      /* SMI_CONV_K_* */
+  int32_t qb;          /* 32-column time sub-tiles per wave */
+  int32_t ks;          /* the waves split the input channels of one output tile */
+  int32_t chg;         /* a staged chunk holds 32 * chg input channels */
+  int32_t nc;          /* the staged row is up to 64 * nc columns wide */
+  int32_t nwv;         /* waves per block */
+  int32_t wpf, wall;   /* small-grid forms: weights one chunk ahead / all taps' weights together */
+  int32_t tph;         /* k_convbT: output phases per block; k_conv_c1: taps */
+} smi_conv_form;
+/* the table run_launch dispatches from: smi_conv_form_count() entries, index -> record */
+int smi_conv_form_count(void);
+int smi_conv_form_get(int index, smi_conv_form* out);
+
+/* One conv layer and one call shape.  Conv1d: S = 1, out[q] = sum W[co][ci][j] x[ci][q * istr + j * dil - pad] with either
+ * istr = 1 and 2 * pad = dil * (K - 1) (length-preserving, as every stride-1 layer of the models), or istr > 1 and pad = 0 (the
+ * feature encoder's strided convs: L_out = (L - K) / istr + 1, exact pipe only -- k_convb stages with unit stride).
+ * ConvTranspose1d: S > 1, pad = (K - S) / 2, L_out = L * S.  L is the longest row's INPUT length and the row stride of X;
+ * Y / Ys / R are [B][Cout][L_out].  gemv = 1: the per-utterance vector projection (k_gemv1; K = 1, L = 1, X [B][Cin],
+ * Y [B][Cout], act none / ReLU (3) / sigmoid (4)); c1 = 1: the one-output-channel 7-tap conv (k_conv_c1) -- the two forms the
+ * callers of make_conv_w select themselves.  plan_frames > 0: the plan is that of ONE row of plan_frames input positions in a
+ * call whose longest row has plan_ext_frames = L (PlanShape).  act: 0 none, 1 GELU, 2 tanh, 3 ReLU. */
+typedef struct smi_conv_case {
+  int32_t Cout, Cin, K, dil, S, pad, istr, act;
+  int32_t bf;          /* 1: bf16-split pipe (weights packed with pack_conv_b), 0: exact fp32 (pack_conv) */
+  int32_t B, L;
+  int32_t has_R;       /* a residual operand enters the plan (it keeps a transposed conv off k_convbT) */
+  int32_t plan_frames, plan_ext_frames;
+  int32_t gemv, c1;
+} smi_conv_case;
+typedef struct smi_conv_plan_info {
+  smi_conv_form form;
+  int32_t form_index;  /* its index in the table */
+  int32_t xw;          /* staged row width */
+  int32_t grid[3];
+  int32_t lout;        /* output positions per row (all phases) */
+  int64_t lds_bytes;
+  int64_t plan_blocks; /* blocks of the grid the plan was chosen for */
+} smi_conv_plan_info;
+/* what make_conv_w builds for the case: host only, no GPU call */
+int smi_conv_plan(const smi_conv_case* c, smi_conv_plan_info* out);
+/* device operands of smi_conv_run; null = absent.  R may alias Y.  bbias [B][Cout]; bias / gamma / beta / alpha [Cout] */
+typedef struct smi_conv_operands {
+  const float* W;
+  const float* X;
+  const float* X2;
+  const float* bias;
+  const float* bbias;
+  const float* gamma;
+  const float* beta;
+  const float* R;
+  const float* alpha;
+  float* Y;
+  float* Ys;
+  float out_scale;     /* 1 or 3 */
+  int32_t reserved;
+} smi_conv_operands;
+/* Builds the launch with make_conv_w, applies the staging limits the vocoder and the encoder apply to their launch lists, runs
+ * it, synchronises and reports the plan.  lens_host [B] valid INPUT lengths (null: all L); a strided conv's valid output
+ * lengths are derived from them.  X must be readable for at least Cout floats (absent epilogue operands read it). */
+int smi_conv_run(const smi_conv_case* c, const smi_conv_operands* io, const int32_t* lens_host, smi_conv_plan_info* plan, void* stream);
+/* The launches smi_voc_block_run would build for (cfg, B, L), without running: kind 0 a conv (form), 1 k_dwln (cpt = the
+ * instantiated channels per thread), 5 k_resunit (res_nwv waves).  *n = launches (at most cap are written). */
+typedef struct smi_block_launch_info {
+  char name[64];
+  int32_t kind, form_index, res_nwv, cpt;
+  smi_conv_form form;
+} smi_block_launch_info;
+int smi_voc_block_plan(const smi_voc_block_cfg* cfg, int B, int L, smi_block_launch_info* out, int cap, int32_t* n);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@ The state dict uses the reference module tree's key names after ``remove_weight_
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -20,8 +21,22 @@ import torch
 import torch.nn.functional as F
 
 
+_DTYPE = [torch.float32]
+
+
+@contextlib.contextmanager
+def precision(dtype: torch.dtype):
+    """Run the oracle's arithmetic in ``dtype`` (float64: the high-precision reference of tests/test_conv_forms_gpu.py);
+    the default, and what the golden vectors pin, is the reference's own fp32."""
+    _DTYPE.append(dtype)
+    try:
+        yield
+    finally:
+        _DTYPE.pop()
+
+
 def _t(sd, name) -> torch.Tensor:
-    return torch.as_tensor(np.asarray(sd[name]), dtype=torch.float32)
+    return torch.as_tensor(np.asarray(sd[name]), dtype=_DTYPE[-1])
 
 
 def snake(x: torch.Tensor, alpha: torch.Tensor) -> torch.Tensor:

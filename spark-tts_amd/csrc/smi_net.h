@@ -1301,86 +1301,139 @@ struct Launch {
 // blocks of the grid a launch's plan was made for: the small-grid kernel forms (WPF, WALL) are part of the plan
 inline long long plan_grid_blocks(const Launch& L) { return L.plan_blocks ? L.plan_blocks : (long long)L.grid.x * L.grid.y * L.grid.z; }
 
+// ------------------------------------------------------------------------------------------
+// The kernel form of a conv launch: which instantiation of k_conv / k_convb / k_convbT / k_conv_c1 / k_gemv1 runs it.
+// conv_form() is the ONE place where a launch's fields (and, in the diagnostics build, the SPARKMI_* A/B switches) become
+// template arguments; kConvForms is the ONE list of instantiations.  run_launch() looks the form up in the table, and
+// the diagnostics entry points (include/sparkmi_debug.h) enumerate the same table and report the same records, so the
+// list of forms a test covers and the launches cannot diverge.
+// ------------------------------------------------------------------------------------------
+enum { CONV_K_CONV = 0, CONV_K_CONVB = 1, CONV_K_CONVBT = 2, CONV_K_C1 = 3, CONV_K_GEMV = 4 };
+struct ConvForm {
+  int kernel;   // CONV_K_*
+  int qb;       // 32-column time sub-tiles per wave
+  int ks;       // waves split the input channels of one output tile
+  int chg;      // a staged chunk holds 32 * chg input channels
+  int nc;       // the staged row is up to 64 * nc columns wide
+  int nwv;      // waves per block
+  int wpf;      // one-tap layers on a small grid: weights requested one chunk ahead
+  int wall;     // several taps on a small grid: all taps' weights of a chunk requested together
+  int tph;      // k_convbT: output phases per block (k_conv_c1: its taps)
+};
+inline bool operator==(const ConvForm& a, const ConvForm& b) {
+  return a.kernel == b.kernel && a.qb == b.qb && a.ks == b.ks && a.chg == b.chg && a.nc == b.nc && a.nwv == b.nwv && a.wpf == b.wpf &&
+         a.wall == b.wall && a.tph == b.tph;
+}
+
+ConvForm conv_form(const Launch& L) {
+  ConvForm f{CONV_K_CONV, L.qb == 1 ? 1 : 2, 0, 1, 2, 4, 0, 0, 0};
+  if (L.gemv) return ConvForm{CONV_K_GEMV, 0, 0, 0, 0, 4, 0, 0, 0};
+  if (L.c1) return ConvForm{CONV_K_C1, 0, 0, 0, 0, 4, 0, 0, 7};   // one output channel, 7 taps: a thread per output sample (k_conv_c1)
+  if (L.bf && L.tph) return ConvForm{CONV_K_CONVBT, 1, 0, 2, 1, 4, 0, 0, L.tph == 4 ? 4 : 5};   // transposed conv, several output phases per block
+  if (L.bf) {            // bf16-split matrix pipe (k_convb): weights packed as two bf16 planes
+    f.kernel = CONV_K_CONVB;
+    const bool wide = L.cp.xw > 64;
+    if (L.chg == 4) {
+      // one tap, channels split over the waves, at most two blocks per CU: the chunk's weights are requested one chunk ahead (WPF)
+      const bool wpf = L.ks && L.cp.S == 1 && L.cp.ntaps[0] == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWPF");
+      f.chg = 4; f.nc = 1; f.ks = L.ks; f.wpf = wpf;
+    } else if (L.ks) {
+      // several taps on a grid of about a block per CU: all taps' weights of a chunk requested together (WALL)
+      int mt = 0;
+      for (int r = 0; r < L.cp.S; ++r) mt = L.cp.ntaps[r] > mt ? L.cp.ntaps[r] : mt;
+      // (measured at one / two utterances, 150 frames: 7-tap convs 71 -> 62 us at 456 blocks but 101 -> 115 at 912; the first transposed conv,
+      // 2 taps per phase, 85 -> 129 us: stride-1 layers with four taps or more on at most two blocks per CU)
+      const bool wall = L.chg == 2 && mt >= 4 && L.cp.S == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWALL");
+      f.ks = 1; f.chg = 2; f.wall = wall; f.nc = (f.qb == 1 && !wide) ? 1 : 2;
+    } else if (L.chg == 2) {    // few taps per phase, rows wider than 64 columns (transposed convs): 64-channel chunks
+      f.chg = 2; f.nc = 2;
+    } else {
+      f.nc = (f.qb == 1 && !wide) ? 1 : 2;
+    }
+    return f;
+  }
+  if (L.chg == 4) {      // 1-tap layers: 128-channel chunks, narrow rows
+    f.chg = 4; f.nc = 1; f.ks = L.ks;
+    // measured (profiles/README.md): pays up to about two blocks per CU, costs beyond (fewer waves fit)
+    f.wpf = L.ks && plan_grid_blocks(L) <= 512;
+  } else if (L.nwv == 3) {      // three output tiles per block (never channel-split)
+    f.nwv = 3; f.nc = L.cp.xw > 128 ? 3 : 2;
+  } else if (L.cp.xw > 128) {   // strided convs: up to 192 staged columns
+    f.nc = 3; f.ks = L.ks;
+  } else {
+    f.ks = L.ks;
+  }
+  return f;
+}
+
+typedef void (*ConvLaunchFn)(const Launch&, hipStream_t);
+template <int QB, bool KS, int CHG, int NC, bool WPF, int NWV>
+void launch_k_conv(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_conv<QB, KS, CHG, NC, WPF, NWV>), L.grid, dim3(64 * NWV), L.lds, st, L.cp); }
+template <int QB, bool KS, int CHG, int NC, bool WPF, bool WALL>
+void launch_k_convb(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_convb<QB, KS, CHG, NC, WPF, WALL>), L.grid, dim3(256), L.lds, st, L.cp); }
+template <int PH>
+void launch_k_convbT(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_convbT<PH>), L.grid, dim3(256), L.lds, st, L.cp); }
+inline void launch_k_conv_c1(const Launch& L, hipStream_t st) {
+  hipLaunchKernelGGL((k_conv_c1<7>), dim3((L.c1_len + 255) / 256, L.grid.z), dim3(256), (size_t)L.cp.Cin * 7 * 4, st, L.cp);
+}
+inline void launch_k_gemv1(const Launch& L, hipStream_t st) { hipLaunchKernelGGL(k_gemv1, L.grid, dim3(256), 0, st, L.cp); }
+
+struct ConvFormEntry { ConvForm form; ConvLaunchFn launch; };
+#define SMI_F_CONV(QB_, KS_, CHG_, NC_, WPF_, NWV_) {{CONV_K_CONV, QB_, KS_, CHG_, NC_, NWV_, WPF_, 0, 0}, launch_k_conv<QB_, KS_, CHG_, NC_, WPF_, NWV_>}
+#define SMI_F_CONVB(QB_, KS_, CHG_, NC_, WPF_, WALL_) {{CONV_K_CONVB, QB_, KS_, CHG_, NC_, 4, WPF_, WALL_, 0}, launch_k_convb<QB_, KS_, CHG_, NC_, WPF_, WALL_>}
+// every instantiation the library carries (the order is the enumeration order of smi_conv_form_entry)
+const ConvFormEntry kConvForms[] = {
+  // exact-fp32 matrix pipe: 32-channel chunks, rows up to 128 columns
+  SMI_F_CONV(1, false, 1, 2, false, 4), SMI_F_CONV(2, false, 1, 2, false, 4), SMI_F_CONV(1, true, 1, 2, false, 4), SMI_F_CONV(2, true, 1, 2, false, 4),
+  // strided convs: up to 192 staged columns
+  SMI_F_CONV(1, false, 1, 3, false, 4), SMI_F_CONV(2, false, 1, 3, false, 4), SMI_F_CONV(1, true, 1, 3, false, 4), SMI_F_CONV(2, true, 1, 3, false, 4),
+  // three output tiles per block
+  SMI_F_CONV(1, false, 1, 2, false, 3), SMI_F_CONV(2, false, 1, 2, false, 3), SMI_F_CONV(1, false, 1, 3, false, 3), SMI_F_CONV(2, false, 1, 3, false, 3),
+  // 1-tap layers: 128-channel chunks
+  SMI_F_CONV(1, false, 4, 1, false, 4), SMI_F_CONV(2, false, 4, 1, false, 4), SMI_F_CONV(1, true, 4, 1, false, 4), SMI_F_CONV(2, true, 4, 1, false, 4),
+  SMI_F_CONV(1, true, 4, 1, true, 4), SMI_F_CONV(2, true, 4, 1, true, 4),
+  // bf16-split matrix pipe: one output tile per wave, 32- / 64- / 128-channel chunks
+  SMI_F_CONVB(1, false, 1, 1, false, false), SMI_F_CONVB(1, false, 1, 2, false, false), SMI_F_CONVB(2, false, 1, 2, false, false),
+  SMI_F_CONVB(1, false, 2, 2, false, false), SMI_F_CONVB(2, false, 2, 2, false, false),
+  SMI_F_CONVB(1, false, 4, 1, false, false), SMI_F_CONVB(2, false, 4, 1, false, false),
+  // channel-split: 64-channel chunks (plain and WALL), 128-channel chunks (plain and WPF)
+  SMI_F_CONVB(1, true, 2, 1, false, false), SMI_F_CONVB(1, true, 2, 2, false, false), SMI_F_CONVB(2, true, 2, 2, false, false),
+  SMI_F_CONVB(1, true, 2, 1, false, true), SMI_F_CONVB(1, true, 2, 2, false, true), SMI_F_CONVB(2, true, 2, 2, false, true),
+  SMI_F_CONVB(1, true, 4, 1, false, false), SMI_F_CONVB(2, true, 4, 1, false, false),
+  SMI_F_CONVB(1, true, 4, 1, true, false), SMI_F_CONVB(2, true, 4, 1, true, false),
+  // transposed convs with 4 / 5 output phases per block
+  {{CONV_K_CONVBT, 1, 0, 2, 1, 4, 0, 0, 4}, launch_k_convbT<4>}, {{CONV_K_CONVBT, 1, 0, 2, 1, 4, 0, 0, 5}, launch_k_convbT<5>},
+  // one output channel (7 taps); one vector per utterance
+  {{CONV_K_C1, 0, 0, 0, 0, 4, 0, 0, 7}, launch_k_conv_c1}, {{CONV_K_GEMV, 0, 0, 0, 0, 4, 0, 0, 0}, launch_k_gemv1},
+};
+#undef SMI_F_CONV
+#undef SMI_F_CONVB
+constexpr int kNumConvForms = (int)(sizeof(kConvForms) / sizeof(kConvForms[0]));
+inline int conv_form_index(const ConvForm& f) {
+  for (int i = 0; i < kNumConvForms; ++i)
+    if (kConvForms[i].form == f) return i;
+  return -1;
+}
+
+// the k_dwln instantiation (channels per thread) that covers a layer of ceil(C / 32) channels per thread
+inline int dwln_form(int cpt) { return cpt <= 2 ? 2 : (cpt <= 4 ? 4 : (cpt <= 12 ? 12 : (cpt <= 16 ? 16 : 32))); }
+
 int run_launch(const Launch& L, hipStream_t st) {
   switch (L.kind) {
-    case 0:
-      if (L.gemv) {
-        hipLaunchKernelGGL(k_gemv1, L.grid, dim3(256), 0, st, L.cp);
-      } else if (L.c1) {            // one output channel, 7 taps: a thread per output sample (k_conv_c1)
-        hipLaunchKernelGGL((k_conv_c1<7>), dim3((L.c1_len + 255) / 256, L.grid.z), dim3(256), (size_t)L.cp.Cin * 7 * 4, st, L.cp);
-      } else if (L.bf && L.tph) {   // transposed conv, several output phases per block (k_convbT)
-        if (L.tph == 4) hipLaunchKernelGGL((k_convbT<4>), L.grid, dim3(256), L.lds, st, L.cp);
-        else hipLaunchKernelGGL((k_convbT<5>), L.grid, dim3(256), L.lds, st, L.cp);
-      } else if (L.bf) {            // bf16-split matrix pipe (k_convb): weights packed as two bf16 planes
-#define SMI_CB(QB_, KS_, CHG_, NC_) hipLaunchKernelGGL((k_convb<QB_, KS_, CHG_, NC_>), L.grid, dim3(256), L.lds, st, L.cp)
-        const bool wide = L.cp.xw > 64;
-        if (L.chg == 4) {
-          // one tap, channels split over the waves, at most two blocks per CU: the chunk's weights are requested one chunk ahead (WPF)
-          const bool wpf = L.ks && L.cp.S == 1 && L.cp.ntaps[0] == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWPF");
-          if (wpf) { if (L.qb == 1) hipLaunchKernelGGL((k_convb<1, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp); else hipLaunchKernelGGL((k_convb<2, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp); }
-          else if (L.ks) { if (L.qb == 1) SMI_CB(1, true, 4, 1); else SMI_CB(2, true, 4, 1); }
-          else { if (L.qb == 1) SMI_CB(1, false, 4, 1); else SMI_CB(2, false, 4, 1); }
-        } else if (L.ks) {
-          // several taps on a grid of about a block per CU: all taps' weights of a chunk requested together (WALL)
-          int mt = 0;
-          for (int r = 0; r < L.cp.S; ++r) mt = L.cp.ntaps[r] > mt ? L.cp.ntaps[r] : mt;
-          // (measured at one / two utterances, 150 frames: 7-tap convs 71 -> 62 us at 456 blocks but 101 -> 115 at 912; the first transposed conv,
-          // 2 taps per phase, 85 -> 129 us: stride-1 layers with four taps or more on at most two blocks per CU)
-          const bool wall = L.chg == 2 && mt >= 4 && L.cp.S == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWALL");
-#define SMI_CBW(QB_, NC_) hipLaunchKernelGGL((k_convb<QB_, true, 2, NC_, false, true>), L.grid, dim3(256), L.lds, st, L.cp)
-          if (wall) { if (L.qb == 1) { if (wide) SMI_CBW(1, 2); else SMI_CBW(1, 1); } else SMI_CBW(2, 2); }
-          else if (L.qb == 1) { if (wide) SMI_CB(1, true, 2, 2); else SMI_CB(1, true, 2, 1); }
-          else SMI_CB(2, true, 2, 2);
-#undef SMI_CBW
-        } else if (L.chg == 2) {    // few taps per phase, rows wider than 64 columns (transposed convs): 64-channel chunks
-          if (L.qb == 1) SMI_CB(1, false, 2, 2); else SMI_CB(2, false, 2, 2);
-        } else {
-          if (L.qb == 1) { if (wide) SMI_CB(1, false, 1, 2); else SMI_CB(1, false, 1, 1); }
-          else SMI_CB(2, false, 1, 2);
-        }
-#undef SMI_CB
-      } else if (L.chg == 4) {      // 1-tap layers: 128-channel chunks, narrow rows
-        if (L.ks) {
-          // measured (profiles/README.md): pays up to about two blocks per CU, costs beyond (fewer waves fit)
-          const bool wpf = plan_grid_blocks(L) <= 512;
-          if (L.qb == 1 && wpf) hipLaunchKernelGGL((k_conv<1, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp);
-          else if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, true, 4, 1>), L.grid, dim3(256), L.lds, st, L.cp);
-          else if (wpf) hipLaunchKernelGGL((k_conv<2, true, 4, 1, true>), L.grid, dim3(256), L.lds, st, L.cp);
-          else hipLaunchKernelGGL((k_conv<2, true, 4, 1>), L.grid, dim3(256), L.lds, st, L.cp);
-        } else {
-          if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, false, 4, 1>), L.grid, dim3(256), L.lds, st, L.cp);
-          else hipLaunchKernelGGL((k_conv<2, false, 4, 1>), L.grid, dim3(256), L.lds, st, L.cp);
-        }
-      } else if (L.nwv == 3) {      // three output tiles per block (never channel-split)
-        if (L.cp.xw > 128) {
-          if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, false, 1, 3, false, 3>), L.grid, dim3(192), L.lds, st, L.cp);
-          else hipLaunchKernelGGL((k_conv<2, false, 1, 3, false, 3>), L.grid, dim3(192), L.lds, st, L.cp);
-        } else {
-          if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, false, 1, 2, false, 3>), L.grid, dim3(192), L.lds, st, L.cp);
-          else hipLaunchKernelGGL((k_conv<2, false, 1, 2, false, 3>), L.grid, dim3(192), L.lds, st, L.cp);
-        }
-      } else if (L.cp.xw > 128) {   // strided convs: up to 192 staged columns
-        if (L.ks) {
-          if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, true, 1, 3>), L.grid, dim3(256), L.lds, st, L.cp);
-          else hipLaunchKernelGGL((k_conv<2, true, 1, 3>), L.grid, dim3(256), L.lds, st, L.cp);
-        } else {
-          if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, false, 1, 3>), L.grid, dim3(256), L.lds, st, L.cp);
-          else hipLaunchKernelGGL((k_conv<2, false, 1, 3>), L.grid, dim3(256), L.lds, st, L.cp);
-        }
-      } else if (L.ks) {
-        if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, true, 1, 2>), L.grid, dim3(256), L.lds, st, L.cp);
-        else hipLaunchKernelGGL((k_conv<2, true, 1, 2>), L.grid, dim3(256), L.lds, st, L.cp);
-      } else {
-        if (L.qb == 1) hipLaunchKernelGGL((k_conv<1, false, 1, 2>), L.grid, dim3(256), L.lds, st, L.cp);
-        else hipLaunchKernelGGL((k_conv<2, false, 1, 2>), L.grid, dim3(256), L.lds, st, L.cp);
-      }
+    case 0: {
+      const int fi = conv_form_index(conv_form(L));
+      SMI_REQUIRE(fi >= 0, "%s: no kernel instantiation for this launch plan", L.name.c_str());
+      kConvForms[fi].launch(L, st);
       break;
+    }
     case 1:
-      if (L.cpt <= 2) hipLaunchKernelGGL(k_dwln<2>, L.grid, dim3(256), 0, st, L.lp);
-      else if (L.cpt <= 4) hipLaunchKernelGGL(k_dwln<4>, L.grid, dim3(256), 0, st, L.lp);
-      else if (L.cpt <= 12) hipLaunchKernelGGL(k_dwln<12>, L.grid, dim3(256), 0, st, L.lp);
-      else if (L.cpt <= 16) hipLaunchKernelGGL(k_dwln<16>, L.grid, dim3(256), 0, st, L.lp);
-      else hipLaunchKernelGGL(k_dwln<32>, L.grid, dim3(256), 0, st, L.lp);
+      switch (dwln_form(L.cpt)) {
+        case 2: hipLaunchKernelGGL(k_dwln<2>, L.grid, dim3(256), 0, st, L.lp); break;
+        case 4: hipLaunchKernelGGL(k_dwln<4>, L.grid, dim3(256), 0, st, L.lp); break;
+        case 12: hipLaunchKernelGGL(k_dwln<12>, L.grid, dim3(256), 0, st, L.lp); break;
+        case 16: hipLaunchKernelGGL(k_dwln<16>, L.grid, dim3(256), 0, st, L.lp); break;
+        default: hipLaunchKernelGGL(k_dwln<32>, L.grid, dim3(256), 0, st, L.lp); break;
+      }
       break;
     case 2:
       hipLaunchKernelGGL(k_codebook, L.grid, dim3(128), 0, st, L.sem, L.semstride, L.cb, L.D, L.cbsize, L.lens, L.Z, L.zstride, L.zb);

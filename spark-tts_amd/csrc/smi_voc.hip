@@ -352,6 +352,29 @@ VocLayout block_layout(const smi_voc_block_cfg* c) {
   return L;
 }
 
+// The launch list of one block on the working buffers of smi_voc_block_run: [0] input / x, [1] snake(input) / n, [2] U or m,
+// [3] US, [4] A; lens = {lens_in[64], lens_out[64], ones[64]}.  Returns the buffer that holds the block's output.  Host only
+// (smi_voc_block_plan builds the same list on placeholder pointers to report its kernel forms).
+float* block_program(std::vector<Launch>& P, const smi_voc_block_cfg& c, const WSrc& w, float* const buf[5], float* ada, const float* cond_dev,
+                     const int* lens, long long bs, int B, int L) {
+  const int* lens_in = lens; const int* lens_out = lens + 64; const int* len1 = lens + 128;
+  if (c.kind == SMI_VOC_BLOCK_RESUNIT) {
+    add_res_unit(P, w, "L.block", c.C, c.dil, buf[0], buf[1], buf[4], buf[2], false, nullptr, L, bs, lens_in, B);
+    return buf[2];
+  }
+  if (c.kind == SMI_VOC_BLOCK_DECBLOCK) {
+    add_dec_block(P, w, "L.block", c.C, c.Cout, c.K, c.S, buf[1], L, bs, buf[2], buf[3], buf[4], buf[0], nullptr, bs, lens_in, lens_out, B);
+    return buf[0];
+  }
+  if (c.cond_dim > 0) {   // all scale / shift projections of the condition in one GEMV (vocos.py:105-108), as smi_voc_forward does
+    P.push_back(make_conv(w, "adaln_params", "cat:L.norm.scale.weight|L.norm.shift.weight", "cat:L.norm.scale.bias|L.norm.shift.bias",
+                          2 * c.C, c.cond_dim, 1, 1, 1, 0, cond_dev, 1, c.cond_dim, ada, nullptr, nullptr, nullptr, 1, 2 * c.C, len1, B, 1, ACT_NONE));
+    P.back().gemv = true; P.back().grid = dim3((2 * c.C + 31) / 32, B);
+  }
+  add_convnext(P, w, "L", c.C, c.I, buf[0], buf[1], buf[2], c.cond_dim > 0 ? ada : nullptr, 2 * c.C, L, bs, lens_in, B);
+  return buf[0];
+}
+
 int layout_entry(const VocLayout& L, int index, char* name, int name_cap, size_t* offset, size_t* bytes, int32_t* info, const char* who) {
   SMI_REQUIRE(index >= 0 && index < (int)L.e.size(), "%s: index %d out of range", who, index);
   const Entry& e = L.e[index];
@@ -817,27 +840,15 @@ int smi_voc_block_run(const smi_voc_block_cfg* cfg, const void* arena_dev, size_
     fail(hipMemcpy2DAsync(dst, (size_t)bs * 4, src, (size_t)C * len * 4, (size_t)C * len * 4, (size_t)B, hipMemcpyDeviceToDevice, st), "copy in");
   };
   std::vector<Launch> P;
-  const int* lens_in = lens; const int* lens_out = lens + 64; const int* len1 = lens + 128;
-  float* result = nullptr;
   if (c.kind == SMI_VOC_BLOCK_RESUNIT) {
     copy_in(buf[0], x_dev, c.C, L);
     copy_in(buf[1], xs_dev, c.C, L);
-    add_res_unit(P, w, "L.block", c.C, c.dil, buf[0], buf[1], buf[4], buf[2], false, nullptr, L, bs, lens_in, B);
-    result = buf[2];
   } else if (c.kind == SMI_VOC_BLOCK_DECBLOCK) {
     copy_in(buf[1], xs_dev, c.C, L);
-    add_dec_block(P, w, "L.block", c.C, c.Cout, c.K, c.S, buf[1], L, bs, buf[2], buf[3], buf[4], buf[0], nullptr, bs, lens_in, lens_out, B);
-    result = buf[0];
   } else {
     copy_in(buf[0], x_dev, c.C, L);
-    if (c.cond_dim > 0) {   // all scale / shift projections of the condition in one GEMV (vocos.py:105-108), as smi_voc_forward does
-      P.push_back(make_conv(w, "adaln_params", "cat:L.norm.scale.weight|L.norm.shift.weight", "cat:L.norm.scale.bias|L.norm.shift.bias",
-                            2 * c.C, c.cond_dim, 1, 1, 1, 0, cond_dev, 1, c.cond_dim, ada, nullptr, nullptr, nullptr, 1, 2 * c.C, len1, B, 1, ACT_NONE));
-      P.back().gemv = true; P.back().grid = dim3((2 * c.C + 31) / 32, B);
-    }
-    add_convnext(P, w, "L", c.C, c.I, buf[0], buf[1], buf[2], c.cond_dim > 0 ? ada : nullptr, 2 * c.C, L, bs, lens_in, B);
-    result = buf[0];
   }
+  float* result = block_program(P, c, w, buf, ada, cond_dev, lens, bs, B, L);
   if (rc == SMI_OK) rc = check_launches(P, "smi_voc_block_run");
   for (size_t i = 0; i < P.size() && rc == SMI_OK; ++i) rc = run_launch(P[i], st);
   if (rc == SMI_OK)
@@ -848,3 +859,174 @@ int smi_voc_block_run(const smi_voc_block_cfg* cfg, const void* arena_dev, size_
 }
 
 }  // extern "C"
+
+#ifdef SMI_DIAG   // ---- include/sparkmi_debug.h: the conv kernel forms, exported by libsparkmi_diag.so only
+namespace {
+
+smi_conv_form form_record(const ConvForm& f) { return smi_conv_form{f.kernel, f.qb, f.ks, f.chg, f.nc, f.nwv, f.wpf, f.wall, f.tph}; }
+
+int conv_case_lout(const smi_conv_case& c, int n) {   // output positions of a row of n input positions
+  if (c.S > 1) return n * c.S;
+  if (c.istr > 1) return n < (c.K - 1) * c.dil + 1 ? 0 : (n - (c.K - 1) * c.dil - 1) / c.istr + 1;
+  return n;
+}
+
+// one conv launch for a case, through make_conv_w and the two caller overrides, with the checks the launch lists get
+int conv_case_launch(const smi_conv_case* cp, const smi_conv_operands& io, const int* lens, const int* olens, Launch& L, const char* who) {
+  SMI_REQUIRE(cp, "%s: case is null", who);
+  const smi_conv_case& c = *cp;
+  SMI_REQUIRE(c.Cout >= 1 && c.Cout <= 8192 && c.Cin >= 1 && c.Cin <= 8192 && c.B >= 1 && c.B <= 4096 && c.L >= 1 && c.L <= (1 << 20),
+              "%s: Cout / Cin / B / L out of range", who);
+  SMI_REQUIRE(c.dil >= 1 && c.K >= 1 && c.S >= 1 && c.S <= kMaxPhases && c.istr >= 1, "%s: bad K / dil / S / istr", who);
+  SMI_REQUIRE(c.act == ACT_NONE || c.act == ACT_GELU || c.act == ACT_TANH || c.act == ACT_RELU || (c.gemv && c.act == ACT_SIGMOID), "%s: bad act", who);
+  if (c.S > 1) {
+    SMI_REQUIRE(c.istr == 1 && c.dil == 1 && c.K >= c.S && (c.K - c.S) % 2 == 0 && c.pad == (c.K - c.S) / 2 && (c.K + c.S - 1) / c.S <= kMaxTaps,
+                "%s: a transposed conv needs istr = dil = 1, K >= S, (K - S) even, pad = (K - S) / 2, at most %d taps per phase", who, kMaxTaps);
+  } else {
+    SMI_REQUIRE(c.K <= kMaxTaps, "%s: at most %d taps", who, kMaxTaps);
+    if (c.istr == 1) SMI_REQUIRE(2 * c.pad == c.dil * (c.K - 1), "%s: a stride-1 conv keeps its length: 2 * pad = dil * (K - 1)", who);
+    else SMI_REQUIRE(c.pad == 0 && !c.bf, "%s: a strided conv has pad = 0 and runs on the exact pipe (k_convb stages with unit stride)", who);
+  }
+  SMI_REQUIRE(!(c.gemv && c.c1), "%s: gemv and c1 exclude each other", who);
+  SMI_REQUIRE(c.plan_frames == 0 || (c.plan_frames >= 1 && c.plan_ext_frames == c.L && c.plan_frames <= c.L && !c.gemv && !c.c1 && c.istr == 1),
+              "%s: a plan shape is one row of 1..L frames with plan_ext_frames = L (unit input stride)", who);
+  const int lout = conv_case_lout(c, c.L);
+  SMI_REQUIRE(lout >= 1, "%s: L = %d gives no output", who, c.L);
+  const PlanShape ps{c.plan_frames, c.plan_ext_frames};
+  const float* R = io.R ? io.R : (c.has_R ? io.X : nullptr);
+  const int Lmax = c.S > 1 ? c.L : lout;   // output positions per phase
+  if (c.gemv) {
+    SMI_REQUIRE(!c.bf && c.K == 1 && c.S == 1 && c.istr == 1 && c.L == 1 && !io.X2 && !io.bbias && !io.gamma && !io.beta && !io.R && !c.has_R && !io.Ys &&
+                io.out_scale == 1.0f && (c.act == ACT_NONE || c.act == ACT_RELU || c.act == ACT_SIGMOID),
+                "%s: the vector projection is an exact 1-tap layer on L = 1 with bias and ReLU / sigmoid only", who);
+    L = make_conv_w("conv", io.W, io.bias, c.Cout, c.Cin, 1, 1, 1, 0, io.X, 1, c.Cin, io.Y, nullptr, nullptr, nullptr, 1, c.Cout, lens, c.B, 1, c.act);
+    L.gemv = true; L.grid = dim3((c.Cout + 31) / 32, c.B);
+    return SMI_OK;
+  }
+  L = make_conv_w("conv", io.W, io.bias, c.Cout, c.Cin, c.K, c.dil, c.S, c.pad, io.X, c.L, (long long)c.Cin * c.L, io.Y, io.Ys, io.alpha, R,
+                  lout, (long long)c.Cout * lout, lens, c.B, Lmax, c.act, c.istr, c.istr > 1 ? olens : nullptr, c.bf != 0, c.plan_frames ? &ps : nullptr);
+  ConvP& q = L.cp;
+  q.X2 = io.X2; q.bbias = io.bbias; q.gamma = io.gamma; q.beta = io.beta; q.out_scale = io.out_scale;
+  SMI_REQUIRE(q.out_scale == 1.0f || q.out_scale == 3.0f, "%s: out_scale is 1 or 3", who);
+  SMI_REQUIRE(!(L.bf && q.X2), "%s: the bf16-split kernels stage X only (no second input)", who);
+  if (c.c1) {   // the vocoder's own conditions for the one-channel kernel (voc_program)
+    SMI_REQUIRE(!L.bf && q.Cout == 1 && q.S == 1 && q.istr == 1 && q.ntaps[0] == 7 && !q.X2 && !q.bbias && !q.gamma && !q.beta && !q.R && !q.Ys &&
+                q.out_scale == 1.0f && q.Cin * 7 * 4 <= 48 * 1024, "%s: k_conv_c1 is an exact 7-tap conv to one channel with bias and activation only", who);
+    L.c1 = true; L.c1_len = Lmax;
+    return SMI_OK;
+  }
+  SMI_REQUIRE(L.lds <= 64 * 1024, "%s: the launch needs %zu bytes of LDS", who, L.lds);
+  if (c.istr > 1) SMI_REQUIRE(q.xw <= 192 && (L.chg == 1 || q.xw <= 64), "%s: the launch stages %d columns", who, q.xw);   // the encoder's limit
+  else SMI_REQUIRE(q.xw <= 128 && (L.chg != 4 || q.xw <= 64), "%s: the launch stages %d columns", who, q.xw);             // check_launches
+  if (L.tph) SMI_REQUIRE(!q.bbias && !q.gamma && !q.beta && !q.R && !q.X2 && q.out_scale == 1.0f && q.act == ACT_NONE,
+                         "%s: the multi-phase transposed conv has a bias / Snake epilogue only", who);
+  return SMI_OK;
+}
+
+int conv_plan_info(const smi_conv_case& c, const Launch& L, smi_conv_plan_info* out, const char* who) {
+  const ConvForm f = conv_form(L);
+  const int fi = conv_form_index(f);
+  SMI_REQUIRE(fi >= 0, "%s: no kernel instantiation for this launch plan", who);
+  memset(out, 0, sizeof(*out));
+  out->form = form_record(f); out->form_index = fi; out->xw = L.cp.xw;
+  out->grid[0] = (int)L.grid.x; out->grid[1] = (int)L.grid.y; out->grid[2] = (int)L.grid.z;
+  if (L.c1) { out->grid[0] = (L.c1_len + 255) / 256; out->grid[1] = (int)L.grid.z; out->grid[2] = 1; }
+  out->lout = c.gemv ? 1 : conv_case_lout(c, c.L);
+  out->lds_bytes = L.c1 ? (long long)L.cp.Cin * 7 * 4 : (L.gemv ? 0 : (long long)L.lds);
+  out->plan_blocks = plan_grid_blocks(L);
+  return SMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smi_conv_form_count(void) { return kNumConvForms; }
+
+int smi_conv_form_get(int index, smi_conv_form* out) {
+  SMI_REQUIRE(out && index >= 0 && index < kNumConvForms, "smi_conv_form_get: index %d out of range", index);
+  *out = form_record(kConvForms[index].form);
+  return SMI_OK;
+}
+
+int smi_conv_plan(const smi_conv_case* c, smi_conv_plan_info* out) {
+  SMI_REQUIRE(out, "smi_conv_plan: out is null");
+  smi_conv_operands io;
+  memset(&io, 0, sizeof(io));
+  io.out_scale = 1.0f;
+  io.W = io.X = (const float*)(uintptr_t)256;   // placeholders: never dereferenced on the host
+  io.Y = (float*)(uintptr_t)512;
+  Launch L;
+  int rc = conv_case_launch(c, io, nullptr, (const int*)(uintptr_t)768, L, "smi_conv_plan");
+  if (rc) return rc;
+  return conv_plan_info(*c, L, out, "smi_conv_plan");
+}
+
+int smi_conv_run(const smi_conv_case* c, const smi_conv_operands* io, const int32_t* lens_host, smi_conv_plan_info* plan, void* stream) {
+  SMI_REQUIRE(c && io && io->W && io->X && (io->Y || io->Ys), "smi_conv_run: null argument");
+  SMI_REQUIRE(!io->Ys || io->alpha, "smi_conv_run: Ys needs alpha");
+  SMI_REQUIRE(!c->has_R == !io->R, "smi_conv_run: has_R and the R operand disagree");
+  SMI_REQUIRE(c->B >= 1 && c->B <= 4096, "smi_conv_run: B out of range");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = c->B;
+  std::vector<int32_t> hl((size_t)2 * B);
+  for (int b = 0; b < B; ++b) {
+    const int n = c->gemv ? 1 : (lens_host ? lens_host[b] : c->L);
+    SMI_REQUIRE(n >= 1 && n <= c->L, "smi_conv_run: lens[%d]=%d outside 1..%d", b, n, c->L);
+    hl[b] = n; hl[(size_t)B + b] = c->gemv ? 1 : conv_case_lout(*c, n);
+  }
+  int* lens = nullptr;
+  if (hipMalloc((void**)&lens, hl.size() * 4) != hipSuccess) { smi_set_error("smi_conv_run: device allocation failed"); return SMI_ENOMEM; }
+  Launch L;
+  int rc = conv_case_launch(c, *io, lens, lens + B, L, "smi_conv_run");
+  smi_conv_plan_info info;
+  if (rc == SMI_OK) rc = conv_plan_info(*c, L, &info, "smi_conv_run");
+  auto fail = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == SMI_OK) { smi_set_error("smi_conv_run: %s: %s", what, hipGetErrorString(e)); rc = SMI_EHIP; } };
+  if (rc == SMI_OK) fail(hipMemcpyAsync(lens, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st), "lens upload");
+  if (rc == SMI_OK) rc = run_launch(L, st);
+  fail(hipStreamSynchronize(st), "synchronize");
+  (void)hipFree(lens);
+  if (rc == SMI_OK && plan) *plan = info;
+  return rc;
+}
+
+int smi_voc_block_plan(const smi_voc_block_cfg* cfg, int B, int L, smi_block_launch_info* out, int cap, int32_t* n) {
+  SMI_REQUIRE(block_cfg_ok(cfg), "smi_voc_block_plan: config outside the kernel contract");
+  SMI_REQUIRE(n && B >= 1 && B <= 64 && L >= 1 && L <= (1 << 20) && cap >= 0 && (out || cap == 0), "smi_voc_block_plan: bad B / L / output");
+  const smi_voc_block_cfg& c = *cfg;
+  VocLayout lay = block_layout(cfg);
+  // placeholder addresses (distinct, non-null, never dereferenced): the builders only compare and store them
+  const WSrc w{&lay.e, (const unsigned char*)(uintptr_t)(1 << 20)};
+  float* buf[5];
+  for (int i = 0; i < 5; ++i) buf[i] = (float*)(((uintptr_t)1 << 40) + ((uintptr_t)i << 34));
+  float* ada = (float*)((uintptr_t)1 << 39);
+  const int* lens = (const int*)((uintptr_t)1 << 38);
+  const int Lout = c.kind == SMI_VOC_BLOCK_DECBLOCK ? L * c.S : L;
+  const int Cres = c.kind == SMI_VOC_BLOCK_DECBLOCK ? c.Cout : c.C;
+  const int Cmax = std::max(std::max(c.C, Cres), c.kind == SMI_VOC_BLOCK_CONVNEXT ? c.I : 1);
+  const long long bs = (long long)smi_align_up((size_t)Cmax * Lout, 64);
+  std::vector<Launch> P;
+  block_program(P, c, w, buf, ada, (const float*)((uintptr_t)1 << 37), lens, bs, B, L);
+  int rc = check_launches(P, "smi_voc_block_plan");
+  if (rc) return rc;
+  *n = (int32_t)P.size();
+  for (size_t i = 0; i < P.size() && (int)i < cap; ++i) {
+    smi_block_launch_info& o = out[i];
+    memset(&o, 0, sizeof(o));
+    strncpy(o.name, P[i].name.c_str(), sizeof(o.name) - 1);
+    o.kind = P[i].kind; o.form_index = -1;
+    if (P[i].kind == 0) {
+      const ConvForm f = conv_form(P[i]);
+      o.form = form_record(f); o.form_index = conv_form_index(f);
+      SMI_REQUIRE(o.form_index >= 0, "smi_voc_block_plan: %s: no kernel instantiation for this launch plan", P[i].name.c_str());
+    } else if (P[i].kind == 1) {
+      o.cpt = dwln_form(P[i].cpt);
+    } else if (P[i].kind == 5) {
+      o.res_nwv = P[i].res_nwv;
+    }
+  }
+  return SMI_OK;
+}
+
+}  // extern "C"
+#endif   // SMI_DIAG

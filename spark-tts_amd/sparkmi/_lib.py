@@ -50,6 +50,34 @@ class VocBlockCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kind", "C", "Cout", "K", "S", "dil", "I", "cond_dim", "exact_fp32")]
 
 
+class ConvForm(C.Structure):
+    """smi_conv_form: one instantiation of the conv kernels (include/sparkmi_debug.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "qb", "ks", "chg", "nc", "nwv", "wpf", "wall", "tph")]
+
+    def key(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_)
+
+
+class ConvCase(C.Structure):
+    """smi_conv_case: one conv layer and one call shape"""
+    _fields_ = [(n, C.c_int32) for n in ("Cout", "Cin", "K", "dil", "S", "pad", "istr", "act", "bf", "B", "L", "has_R",
+                                         "plan_frames", "plan_ext_frames", "gemv", "c1")]
+
+
+class ConvPlanInfo(C.Structure):
+    _fields_ = [("form", ConvForm), ("form_index", C.c_int32), ("xw", C.c_int32), ("grid", C.c_int32 * 3), ("lout", C.c_int32),
+                ("lds_bytes", C.c_int64), ("plan_blocks", C.c_int64)]
+
+
+class ConvOperands(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("W", "X", "X2", "bias", "bbias", "gamma", "beta", "R", "alpha", "Y", "Ys")] + [
+        ("out_scale", C.c_float), ("reserved", C.c_int32)]
+
+
+class BlockLaunchInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 64)] + [(n, C.c_int32) for n in ("kind", "form_index", "res_nwv", "cpt")] + [("form", ConvForm)]
+
+
 class EncCfg(C.Structure):
     _fields_ = ([("w2v_conv_dim", C.c_int32), ("w2v_nconv", C.c_int32), ("w2v_kernel", C.c_int32 * 8), ("w2v_stride", C.c_int32 * 8)]
                 + [(n, C.c_int32) for n in ("w2v_hidden", "w2v_layers", "w2v_heads", "w2v_inter", "w2v_pos_k", "w2v_pos_groups")]
@@ -196,6 +224,11 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),
+    "smi_conv_form_count": (_I, []),
+    "smi_conv_form_get": (_I, [_I, _P(ConvForm)]),
+    "smi_conv_plan": (_I, [_P(ConvCase), _P(ConvPlanInfo)]),
+    "smi_conv_run": (_I, [_P(ConvCase), _P(ConvOperands), _P(C.c_int32), _P(ConvPlanInfo), _VP]),
+    "smi_voc_block_plan": (_I, [_P(VocBlockCfg), _I, _I, _P(BlockLaunchInfo), _I, _P(C.c_int32)]),
 }
 
 DIAG_PATH = LIB_PATH.with_name("libsparkmi_diag.so")

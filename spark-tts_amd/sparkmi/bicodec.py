@@ -170,6 +170,100 @@ def run_block(kind: int, params: Mapping[str, np.ndarray], x: Optional[torch.Ten
     return y
 
 
+CONV_KERNELS = ("k_conv", "k_convb", "k_convbT", "k_conv_c1", "k_gemv1")
+ACT_NONE, ACT_GELU, ACT_TANH, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3, 4
+
+
+def form_name(key) -> str:
+    """A readable name of a conv kernel form (``_lib.ConvForm.key()``)"""
+    kernel, qb, ks, chg, nc, nwv, wpf, wall, tph = key
+    n = CONV_KERNELS[kernel]
+    if kernel == 2:
+        return f"{n}<{tph}>"
+    if kernel in (3, 4):
+        return n
+    return f"{n}<qb{qb},{'ks' if ks else 'co'},chg{chg},nc{nc}" + (",wpf" if wpf else "") + (",wall" if wall else "") + (",3w" if nwv == 3 else "") + ">"
+
+
+def conv_forms() -> List[tuple]:
+    """The table of instantiated conv kernel forms the library dispatches from (diagnostics build; no GPU call)."""
+    d = _lib.diag()
+    out = []
+    for i in range(d.smi_conv_form_count()):
+        f = _lib.ConvForm()
+        d.check(d.smi_conv_form_get(i, C.byref(f)), "smi_conv_form_get")
+        out.append(f.key())
+    return out
+
+
+def conv_case(Cout: int, Cin: int, K: int = 1, dil: int = 1, S: int = 1, istr: int = 1, act: int = 0, bf: bool = False, B: int = 1,
+              L: int = 1, has_R: bool = False, plan_frames: int = 0, gemv: bool = False, c1: bool = False) -> _lib.ConvCase:
+    """``smi_conv_case`` with the padding the models use: length-preserving for stride-1 convs, 0 for strided convs,
+    (K - S) / 2 for transposed convs."""
+    pad = (K - S) // 2 if S > 1 else (0 if istr > 1 else dil * (K - 1) // 2)
+    return _lib.ConvCase(Cout=Cout, Cin=Cin, K=K, dil=dil, S=S, pad=pad, istr=istr, act=act, bf=int(bf), B=B, L=L, has_R=int(has_R),
+                         plan_frames=plan_frames, plan_ext_frames=L if plan_frames else 0, gemv=int(gemv), c1=int(c1))
+
+
+def plan_conv(case: _lib.ConvCase) -> _lib.ConvPlanInfo:
+    """What the launch builder picks for ``case`` (kernel form, staged width, grid, LDS): host only, no GPU call."""
+    d = _lib.diag()
+    info = _lib.ConvPlanInfo()
+    d.check(d.smi_conv_plan(C.byref(case), C.byref(info)), "smi_conv_plan")
+    return info
+
+
+def plan_block(kind: int, B: int, L: int, *, C_: int, Cout: int = 0, K: int = 0, S: int = 1, dil: int = 1, I: int = 0, cond_dim: int = 0,
+               exact_fp32: bool = False) -> List[dict]:
+    """The launches ``run_block`` would make for this block and call shape (host only): name, kind (0 conv, 1 k_dwln,
+    5 k_resunit), the conv's form key, k_resunit's wave count, k_dwln's channels per thread."""
+    d = _lib.diag()
+    cs = _lib.VocBlockCfg(kind=kind, C=C_, Cout=Cout, K=K, S=S, dil=dil, I=I, cond_dim=cond_dim, exact_fp32=int(exact_fp32))
+    out = (_lib.BlockLaunchInfo * 16)()
+    n = C.c_int32()
+    d.check(d.smi_voc_block_plan(C.byref(cs), B, L, out, 16, C.byref(n)), "smi_voc_block_plan")
+    return [dict(name=o.name.decode(), kind=o.kind, form=o.form.key() if o.kind == 0 else None, res_nwv=o.res_nwv, cpt=o.cpt)
+            for o in out[: n.value]]
+
+
+@torch.no_grad()
+def run_conv(case: _lib.ConvCase, w: np.ndarray, x: torch.Tensor, *, bias=None, bbias=None, gamma=None, beta=None, R=None, alpha=None,
+             x2=None, lens: Optional[Sequence[int]] = None, out_scale: float = 1.0, want_y: bool = True, want_ys: bool = False,
+             r_aliases_y: bool = False, fill: float = 0.0):
+    """ONE conv layer on the HIP kernels (``smi_conv_run``, diagnostics build), built by ``make_conv_w`` -- the op-level seam for
+    a single kernel form.  ``w``: Conv1d weights (Cout, Cin, K) or ConvTranspose1d weights (Cin, Cout, K), packed here with
+    ``pack_conv`` / ``pack_conv_b``; ``x`` (B, Cin, L) on the GPU ((B, Cin) for gemv).  The outputs are pre-filled with ``fill``
+    (``r_aliases_y``: Y starts as a copy of R and is the residual operand).  Returns (y, ys, plan)."""
+    d = _lib.diag()
+    _lib.require_gfx950()
+    dev = x.device
+    transposed = case.S > 1
+    kind = (PACK_CONVT_B if case.bf else PACK_CONVT) if transposed else (PACK_CONV_B if case.bf else PACK_CONV)
+    packed = (pack_conv_b if case.bf else pack_conv)(np.asarray(w, np.float32), kind, case.S, case.pad)
+    wd = torch.from_numpy(packed).to(dev)
+    # absent epilogue operands read the first Cout floats of X: keep that much readable behind a short input
+    xbuf = torch.zeros(max(x.numel(), case.Cout) + 64, dtype=torch.float32, device=dev)
+    xbuf[: x.numel()] = x.reshape(-1).float()
+    info = plan_conv(case)
+    shape = (case.B, case.Cout) if case.gemv else (case.B, case.Cout, info.lout)
+    up = lambda a: None if a is None else torch.as_tensor(np.asarray(a, np.float32) if not torch.is_tensor(a) else a).float().to(dev).contiguous()
+    ops = [up(a) for a in (x2, bias, bbias, gamma, beta, R, alpha)]
+    y = ys = None
+    if want_y:
+        y = ops[5].clone() if r_aliases_y else torch.full(shape, fill, dtype=torch.float32, device=dev)
+    if want_ys:
+        ys = torch.full(shape, fill, dtype=torch.float32, device=dev)
+    ptr = lambda a: None if a is None else a.data_ptr()
+    io = _lib.ConvOperands(W=wd.data_ptr(), X=xbuf.data_ptr(), X2=ptr(ops[0]), bias=ptr(ops[1]), bbias=ptr(ops[2]), gamma=ptr(ops[3]),
+                           beta=ptr(ops[4]), R=ptr(y) if r_aliases_y else ptr(ops[5]), alpha=ptr(ops[6]), Y=ptr(y), Ys=ptr(ys),
+                           out_scale=out_scale)
+    hl = (C.c_int32 * case.B)(*[int(v) for v in lens]) if lens is not None else None
+    plan = _lib.ConvPlanInfo()
+    d.check(d.smi_conv_run(C.byref(case), C.byref(io), hl, C.byref(plan), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+            "smi_conv_run")
+    return y, ys, plan
+
+
 class BiCodecVocoder:
     """The vocoder half of BiCodec on one MI355X."""
 
