@@ -55,7 +55,9 @@ int smi_llm_debug_hidden(smi_llm* h, float* out_host, int n);
  * M rows after smi_llm_debug_layer).  what: 0 q [M][q_dim] f32, 1 / 2 / 3 the operand
  * triples of o_proj / down_proj / the next norm ([K / 32][3][4][M][16 B]), 4 the residual rows, 5 the engine's
  * granules [2][per buffer] u64 {tag << 32 | f32 bits}, 6 partial sums of squares [hidden / 4], 7 K rows of layer 0, slot 0,
- * kv head 0 (bf16), 8 h + o_proj of the fused one-row path. */
+ * kv head 0 (bf16), 8 h + o_proj of the fused one-row path.  16 .. 20: the prefill workspace after smi_llm_debug_prefill_layer, for
+ * its M rows: 16 q [M][q_dim] f32, 17 / 18 / 19 the operand triples of o_proj / down_proj / the next norm (same layout, this M),
+ * 20 the residual rows [M][hidden] f32.  cap must hold the buffer (M rows x 4864 x 6 B at the 0.5B shape: size it from M). */
 int smi_llm_debug_read(smi_llm* h, int what, void* out_host, size_t cap, size_t* got);
 
 /* Op-level tests of the LLM half: ONE decoder layer's kernels, stage by stage, on caller-given rows -- launched by the functions a
@@ -73,6 +75,23 @@ int smi_llm_debug_read(smi_llm* h, int what, void* out_host, size_t cap, size_t*
 int smi_llm_debug_set_kv(smi_llm* h, int layer, int slot, int pos0, int n, const float* k_host, const float* v_host);
 int smi_llm_debug_get_kv(smi_llm* h, int layer, int slot, int pos0, int n, float* k_host, float* v_host);
 int smi_llm_debug_layer(smi_llm* h, int layer, int M, const int32_t* rows_host, const float* hidden_host, int stage);
+/* Op-level tests of the PROMPT pass (tests/test_llm_prefill_ops_gpu.py): one decoder layer's kernels as a pass over more than 64
+ * prompt rows launches them -- k_pgemm in its few-row (split-K o_proj / down_proj + k_resid_comb) and many-row shapes, k_attn_pf<f32>,
+ * k_attn_pf<bf16>, k_attn_pf2 on its 16-row tiles, or (family = SMI_PF_GROUPED) the row-grouped decode GEMMs -- through the per-layer
+ * launch function every layer of a real pass goes through, on ONE row group in the prefill workspace.
+ *   smi_llm_debug_prefill_layer: seq_host = n_seq (KV slot, first position, rows) triples, each sequence in its own slot; sequence
+ *     b's rows are positions pos0 .. pos0 + n - 1 of its slot, in plan order.  pos0 > 0: the tail group of a prompt that straddles a
+ *     4096-row group -- the caller fills positions 0 .. pos0 - 1 with smi_llm_debug_set_kv first.  hidden_host [M][hidden], M = the
+ *     sum of the row counts (1 .. 4096): the residual rows entering `layer`.  Runs the layer's kernels up to and including `stage`:
+ *     0 QKV (+ bias, RoPE, K/V append: smi_llm_debug_read(16), _get_kv), 1 attention (17), 2 o_proj + residual (20), 3 gate_up +
+ *     SwiGLU (18), 4 down_proj + residual (20), 5 = stage 4, then layer + 1's QKV (16, _get_kv of layer + 1) -- the one reader of
+ *     the RMSNorm partials down_proj leaves.  The last layer takes stage 0 only (a pass launches nothing after its K/V append): any
+ *     other stage is SMI_EINVAL, as are a paged cache, M = 0 and a position outside the cache.  Ends the current generation.
+ *   smi_llm_pf_tiles: host only, no GPU call -- the tiles the pass builds for k_attn_pf2 from M (slot, pos) rows: out[i] =
+ *     (first row, rows, slot, first position) of tile i, *n = the number of tiles (at most cap are written). */
+enum { SMI_PF_GROUPED = 1, SMI_PF_PGEMM = 2 };
+int smi_llm_debug_prefill_layer(smi_llm* h, int layer, int stage, int n_seq, const int32_t* seq_host, const float* hidden_host, int family);
+int smi_llm_pf_tiles(const int32_t* rows_host, int M, int32_t* out, int cap, int32_t* n);
 /* Diagnostics: the raw stamp buffer (u64 s_memrealtime ticks, 10 ns) after smi_llm_debug_stamps; n entries. */
 int smi_llm_debug_raw_stamps(smi_llm* h, unsigned long long* out, int n);
 /* Tests: the sampler alone (k_sample_scan + k_sample, exactly as a decode step launches them) on a caller's logits row --

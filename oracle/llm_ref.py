@@ -154,7 +154,7 @@ def rope_angles(cfg, positions) -> np.ndarray:
 
 
 def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.ndarray], vcache: Dict[int, np.ndarray],
-                     own_kv: bool = True) -> Dict[str, np.ndarray]:
+                     own_kv: bool = True, qkv_only: bool = False) -> Dict[str, np.ndarray]:
     """One Qwen2 decoder layer (MQ Qwen2DecoderLayer) on M caller rows, every product and sum in float64.
 
     ``weights``: ``name -> array`` under HF names; ``rows``: (M, 2) (KV slot, position) pairs; ``x``: (M, hidden) residual rows
@@ -163,7 +163,8 @@ def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.nda
     when there is one and ``own_kv`` is set, else ``kcache[s][t]`` (``own_kv=False``: the caches already hold the rows' K/V,
     e.g. as a bf16 cache stored them).  Returns what ``SparkLLM.debug_layer`` returns for stages 0-4, in its layouts:
     q (M, heads, hd), k / v (M, kv heads, hd) after bias and RoPE, attn (M, heads * hd), h_mid (M, hidden) after o_proj +
-    residual, act (M, intermediate) = silu(gate) * up, h_out (M, hidden) after down_proj + residual."""
+    residual, act (M, intermediate) = silu(gate) * up, h_out (M, hidden) after down_proj + residual.  ``qkv_only``: q, k, v alone
+    (the caches are not read)."""
     p = f"model.layers.{layer}."
     w = lambda n: np.asarray(weights[p + n], dtype=np.float64)  # noqa: E731
     nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
@@ -185,6 +186,8 @@ def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.nda
     v = (xn @ w("self_attn.v_proj.weight").T + w("self_attn.v_proj.bias")).reshape(M, nkv, hd)
     ang = rope_angles(cfg, rows[:, 1])
     q, k = rope(q, ang), rope(k, ang)
+    if qkv_only:
+        return {"q": q, "k": k, "v": v}
     attn = np.zeros((M, nh * hd))
     rep = nh // nkv
     for i, (s, pos) in enumerate(rows):                              # MQ:150-173 eager attention, GQA by repeat_kv
@@ -193,9 +196,8 @@ def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.nda
         if own_kv:
             K = np.concatenate([K, np.zeros((pos + 1 - len(K), nkv, hd))])
             V = np.concatenate([V, np.zeros((pos + 1 - len(V), nkv, hd))])
-            for j, (s2, p2) in enumerate(rows):
-                if s2 == s and p2 <= pos:
-                    K[p2], V[p2] = k[j], v[j]
+            own = np.flatnonzero((rows[:, 0] == s) & (rows[:, 1] <= pos))     # (a position named twice: the later row's, as a loop would)
+            K[rows[own, 1]], V[rows[own, 1]] = k[own], v[own]
         assert K.shape[0] == V.shape[0] == pos + 1, f"row {i} (slot {s}, pos {pos}): keys for {K.shape[0]} positions"
         Kr, Vr = np.repeat(K, rep, axis=1), np.repeat(V, rep, axis=1)          # (T, nh, hd)
         sc = np.einsum("hd,thd->ht", q[i], Kr) * hd ** -0.5

@@ -3777,6 +3777,7 @@ struct smi_llm {
   int pf_ntiles;
   std::vector<PfTile> host_tiles;
   int attn_pf2;         // bf16 KV: prefill attention on the matrix pipes (SPARKMI_ATTN_PF2=0: one wave per (row, head))
+  int dbg_pf_rows;      // diagnostics: rows the last smi_llm_debug_prefill_layer left in the big workspace (smi_llm_debug_read 16 .. 20)
   size_t plan_cap;     // rows
   float* pval; int* pidx; int lm_blocks, lm_cap;
   int64_t* hist; int32_t *count, *finished, *step;
@@ -4703,11 +4704,18 @@ int launch_pgemm(const smi_llm* L, GemmP p, hipStream_t st, int nsplit = 1) {
   return SMI_OK;
 }
 
-// All layers for M (> 32) prompt rows living in the big workspace: K/V of every row appended, hidden
-// states of the last layer never needed (no prompt row except each sequence's last feeds lm_head).
+// RMSNorm partials per row that a layer's QKV finds in the big workspace: [rows][NT * 4] as the row-grouped down_proj leaves them,
+// [rows][NT] as the prefill GEMM and its split-K combine do.  The kernel that fills a pass's layer-0 input (k_embed) is told the same.
+int pf_nparts_in(const smi_llm* L, int M, int family) {
+  const bool gd = L->pg_forced ? M < L->pg_min[3] : family != PF_PGEMM;
+  return gd ? L->NTh * 4 : L->NTh;
+}
+
+// Layer l of a pass over M (> 32) prompt rows living in the big workspace: its kernels KQKV .. last_kernel (KD: the whole layer;
+// the last layer ends after its K/V append whatever last_kernel says -- no prompt row's hidden state feeds lm_head).
 // Up to kPgemmMinRows rows the decode GEMM runs with one block row per 32 rows (same bits as 32-row
 // chunks, one launch instead of M / 32); beyond, the LDS-shared prefill GEMM (k_pgemm) takes over.
-int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStream_t st) {
+int launch_layer_big(smi_llm* L, int l, const RowDesc* rows, int M, int family, int last_kernel, hipStream_t st) {
   const smi_llm_cfg& c = L->cfg;
   // Which GEMM family: decided by the CALLER from the sequences' own lengths (prefill_prompts), the same for all four kernels of
   // the pass.  Diagnostics (SPARKMI_PGEMM_MIN_* set): per kernel by the pass's row count, as in round 3 -- every mix is
@@ -4716,58 +4724,64 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
   const bool pg = family == PF_PGEMM;
   const bool gq = L->pg_forced ? M < L->pg_min[0] : !pg, go = L->pg_forced ? M < L->pg_min[1] : !pg,
              gg = L->pg_forced ? M < L->pg_min[2] : !pg, gd = L->pg_forced ? M < L->pg_min[3] : !pg;
-  const int np_from_d = gd ? L->NTh * 4 : L->NTh, np_from_o = go ? L->NTh * 4 : L->NTh;
+  const int np_from_d = pf_nparts_in(L, M, family), np_from_o = go ? L->NTh * 4 : L->NTh;
   // few rows: 64-column tiles (more blocks) and a deeper ring; o_proj / down_proj as one block per K segment + in-order combine
   const bool few = M <= L->pg_split_rows && !(L->tune2 & 16384);
   const int kseg_o = (L->KTq + kPgSegO - 1) / kPgSegO, kseg_d = (L->KTi + kPgSegD - 1) / kPgSegD;
   const int nseg_o = (L->KTq + kseg_o - 1) / kseg_o, nseg_d = (L->KTi + kseg_d - 1) / kseg_d;
   int rc;
-  for (int l = 0; l < c.num_layers; ++l) {
-    // QKV
-    const GemmP p = gemm_operands(L, KQKV, l, L->big, rows, M, np_from_d);
-    if (gq) rc = launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV>(L, p, st);
-    else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_QKV>(L, p, st);
-    else if (few) rc = launch_pgemm<PRO_NORM, EPI_QKV, 2, 2, 6, 1, 0, 4>(L, p, st);
-    else rc = launch_pgemm<PRO_NORM, EPI_QKV, 6, 2, 3, 1>(L, p, st);
-    if (rc) return rc;
-    if (l == c.num_layers - 1) break;
-    // attention
-    const AttnP a = attn_operands(L, l, L->big, rows, M);   // (slot_is_row = 0: prompt rows name their slot)
-    if (L->tune2 & 1024) {   // SPARKMI_TUNE2 bit 1024: the decode attention kernel per prompt row (the path before k_attn_pf)
-      if ((rc = c.kv_dtype ? launch_attn<1>(L, a, 0, st) : launch_attn<0>(L, a, 0, st))) return rc;
-    } else {
-      const dim3 ag((unsigned)((M + kAttnWaves - 1) / kAttnWaves), (unsigned)c.num_heads);
-      if (!c.kv_dtype && L->attn_pf2 && L->pf_ntiles > 0 && c.head_dim == 64) {   // bf16 KV: tiles of 16 rows on the matrix pipes
-        const int tasks = L->pf_ntiles * c.num_heads;
-        hipLaunchKernelGGL(k_attn_pf2, dim3((tasks + 3) / 4), dim3(256), 0, st, a, (const PfTile*)L->pf_tiles, L->pf_ntiles);
-      } else if (c.kv_dtype) hipLaunchKernelGGL((k_attn_pf<1>), ag, dim3(kAttnWaves * 64), 0, st, a);
-      else hipLaunchKernelGGL((k_attn_pf<0>), ag, dim3(kAttnWaves * 64), 0, st, a);
-      SMI_LAUNCH_CHECK();
-    }
-    // o_proj
-    GemmP o = gemm_operands(L, KO, l, L->big, rows, M, np_from_d);
-    o.kseg = kseg_o;
-    if (go) rc = launch_oproj(L, o, M, st);
-    else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, o, st);
-    else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, o, st, nseg_o);
-    else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, o, st);
-    if (rc) return rc;
-    // gate_up
-    const GemmP g = gemm_operands(L, KGU, l, L->big, rows, M, np_from_o);
-    if (gg) rc = launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 2>(L, g, st);
-    else if (L->tune2 & 512) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU>(L, g, st);
-    else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 4>(L, g, st);
-    else if (L->tune2 & 32768) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 3>(L, g, st);
-    else if (few) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 2, 2, 4, 0, 0, 4>(L, g, st);   // 64 KiB ring: two blocks per CU, the 304 blocks of a 127-row prompt in one round (ring of 6: 1.2 rounds, 30 us)
-    else rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 2, 0, 1>(L, g, st);
-    if (rc) return rc;
-    // down
-    GemmP d = gemm_operands(L, KD, l, L->big, rows, M, np_from_o);   // (never the last layer's: gamma_next is the next LN1)
-    d.wperm = L->wd_parts; d.kseg = kseg_d;
-    if (gd) rc = launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID>(L, d, st);
-    else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, d, st);
-    else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, d, st, nseg_d);
-    else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, d, st);
+  // QKV
+  const GemmP p = gemm_operands(L, KQKV, l, L->big, rows, M, np_from_d);
+  if (gq) rc = launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV>(L, p, st);
+  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_QKV>(L, p, st);
+  else if (few) rc = launch_pgemm<PRO_NORM, EPI_QKV, 2, 2, 6, 1, 0, 4>(L, p, st);
+  else rc = launch_pgemm<PRO_NORM, EPI_QKV, 6, 2, 3, 1>(L, p, st);
+  if (rc || last_kernel == KQKV || l == c.num_layers - 1) return rc;
+  // attention
+  const AttnP a = attn_operands(L, l, L->big, rows, M);   // (slot_is_row = 0: prompt rows name their slot)
+  if (L->tune2 & 1024) {   // SPARKMI_TUNE2 bit 1024: the decode attention kernel per prompt row (the path before k_attn_pf)
+    if ((rc = c.kv_dtype ? launch_attn<1>(L, a, 0, st) : launch_attn<0>(L, a, 0, st))) return rc;
+  } else {
+    const dim3 ag((unsigned)((M + kAttnWaves - 1) / kAttnWaves), (unsigned)c.num_heads);
+    if (!c.kv_dtype && L->attn_pf2 && L->pf_ntiles > 0 && c.head_dim == 64) {   // bf16 KV: tiles of 16 rows on the matrix pipes
+      const int tasks = L->pf_ntiles * c.num_heads;
+      hipLaunchKernelGGL(k_attn_pf2, dim3((tasks + 3) / 4), dim3(256), 0, st, a, (const PfTile*)L->pf_tiles, L->pf_ntiles);
+    } else if (c.kv_dtype) hipLaunchKernelGGL((k_attn_pf<1>), ag, dim3(kAttnWaves * 64), 0, st, a);
+    else hipLaunchKernelGGL((k_attn_pf<0>), ag, dim3(kAttnWaves * 64), 0, st, a);
+    SMI_LAUNCH_CHECK();
+  }
+  if (last_kernel == KATTN) return SMI_OK;
+  // o_proj
+  GemmP o = gemm_operands(L, KO, l, L->big, rows, M, np_from_d);
+  o.kseg = kseg_o;
+  if (go) rc = launch_oproj(L, o, M, st);
+  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, o, st);
+  else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, o, st, nseg_o);
+  else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, o, st);
+  if (rc || last_kernel == KO) return rc;
+  // gate_up
+  const GemmP g = gemm_operands(L, KGU, l, L->big, rows, M, np_from_o);
+  if (gg) rc = launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 2>(L, g, st);
+  else if (L->tune2 & 512) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU>(L, g, st);
+  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 4>(L, g, st);
+  else if (L->tune2 & 32768) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 3>(L, g, st);
+  else if (few) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 2, 2, 4, 0, 0, 4>(L, g, st);   // 64 KiB ring: two blocks per CU, the 304 blocks of a 127-row prompt in one round (ring of 6: 1.2 rounds, 30 us)
+  else rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 2, 0, 1>(L, g, st);
+  if (rc || last_kernel == KGU) return rc;
+  // down
+  GemmP d = gemm_operands(L, KD, l, L->big, rows, M, np_from_o);   // (never the last layer's: gamma_next is the next LN1)
+  d.wperm = L->wd_parts; d.kseg = kseg_d;
+  if (gd) rc = launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID>(L, d, st);
+  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, d, st);
+  else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, d, st, nseg_d);
+  else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, d, st);
+  return rc;
+}
+
+// All layers for the M prompt rows of one pass: K/V of every row appended, hidden states of the last layer never needed.
+int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStream_t st) {
+  for (int l = 0; l < L->cfg.num_layers; ++l) {
+    const int rc = launch_layer_big(L, l, rows, M, family, KD, st);
     if (rc) return rc;
   }
   return SMI_OK;
@@ -4972,6 +4986,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->exact = cfg->weights_exact;
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
+  L->dbg_pf_rows = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
   L->graph = nullptr; L->graph_id = 0; slots_clear(L);
   L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
@@ -5155,6 +5170,38 @@ int smi_llm_set_sampling(smi_llm* L, int do_sample, float temperature, int top_k
   return SMI_OK;
 }
 
+// Prefill attention tiles of a row group (k_attn_pf2): runs of up to 16 rows that are consecutive tokens of one KV slot.  Host only.
+static void pf_tiles_build(const RowDesc* rows, int M, std::vector<PfTile>& T) {
+  T.clear();
+  for (int i = 0; i < M;) {
+    const RowDesc& a0 = rows[i];
+    int n = 1;
+    while (n < 16 && i + n < M && rows[i + n].slot == a0.slot && rows[i + n].pos == a0.pos + n) ++n;
+    T.push_back(PfTile{i, n, a0.slot, a0.pos});
+    i += n;
+  }
+}
+
+// The tiles of the row group in flight (host_rows: its M rows on the host), built and sent to L->pf_tiles where the cache type and
+// the handle's settings take k_attn_pf2; L->pf_ntiles = 0 otherwise.
+static int pf_tiles_upload(smi_llm* L, const RowDesc* host_rows, int M, hipStream_t st) {
+  L->pf_ntiles = 0;
+  if (L->cfg.kv_dtype || !L->attn_pf2) return SMI_OK;
+  std::vector<PfTile>& T = L->host_tiles;
+  pf_tiles_build(host_rows, M, T);
+  if (T.size() > L->pf_tiles_cap) {
+    if (L->pf_tiles) (void)hipFree(L->pf_tiles);
+    L->pf_tiles = nullptr; L->pf_tiles_cap = 0;
+    const size_t cap = T.size() + 256;
+    if (hipMalloc((void**)&L->pf_tiles, cap * sizeof(PfTile)) != hipSuccess) { smi_set_error("hipMalloc(prefill attention tiles) failed"); return SMI_ENOMEM; }
+    L->pf_tiles_cap = cap;
+  }
+  // (pageable source: staged before the call returns; host_tiles is rebuilt only by the next group, behind this copy)
+  SMI_HIP(hipMemcpyAsync(L->pf_tiles, T.data(), T.size() * sizeof(PfTile), hipMemcpyHostToDevice, st));
+  L->pf_ntiles = (int)T.size();
+  return SMI_OK;
+}
+
 // Runs every prompt token but each sequence's last through the layers (K/V appended at slots[b]) and leaves the n
 // "last prompt token" rows at L->plan + *tail_off (device) and in L->host_rows (host) for the first step.
 // Argument checks of a prefill / admission, made BEFORE anything of the handle's state (KV pages, sequence numbers, the
@@ -5234,32 +5281,9 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
       const size_t r0 = pass_off[ps] + q0;
       const int M = (int)((pass_rows[ps] - q0) < kBigRows ? (pass_rows[ps] - q0) : kBigRows);
       const RowDesc* rows = L->plan + r0;
-      // prefill attention tiles of this row group: runs of up to 16 rows that are consecutive tokens of one KV slot
-      L->pf_ntiles = 0;
-      if (!L->cfg.kv_dtype && L->attn_pf2) {
-        std::vector<PfTile>& T = L->host_tiles;
-        T.clear();
-        for (int i = 0; i < M;) {
-          const RowDesc& a0 = L->host_rows[r0 + i];
-          int n = 1;
-          while (n < 16 && i + n < M && L->host_rows[r0 + i + n].slot == a0.slot && L->host_rows[r0 + i + n].pos == a0.pos + n) ++n;
-          T.push_back(PfTile{i, n, a0.slot, a0.pos});
-          i += n;
-        }
-        if (T.size() > L->pf_tiles_cap) {
-          if (L->pf_tiles) (void)hipFree(L->pf_tiles);
-          L->pf_tiles = nullptr; L->pf_tiles_cap = 0;
-          const size_t cap = T.size() + 256;
-          if (hipMalloc((void**)&L->pf_tiles, cap * sizeof(PfTile)) != hipSuccess) { smi_set_error("hipMalloc(prefill attention tiles) failed"); return SMI_ENOMEM; }
-          L->pf_tiles_cap = cap;
-        }
-        // (pageable source: staged before the call returns; host_tiles is rebuilt only by the next group, behind this copy)
-        SMI_HIP(hipMemcpyAsync(L->pf_tiles, T.data(), T.size() * sizeof(PfTile), hipMemcpyHostToDevice, st));
-        L->pf_ntiles = (int)T.size();
-      }
-      const bool d_grouped = L->pg_forced ? M < L->pg_min[3] : pass_family[ps] == PF_GROUPED;   // who leaves the RMSNorm partials of the layer input
+      if ((rc = pf_tiles_upload(L, L->host_rows.data() + r0, M, st))) return rc;
       hipLaunchKernelGGL(k_embed, dim3((M + 3) / 4), dim3(256), 0, st, (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0), L->KTh, rows, M,
-                         (const float*)sec(L, SMI_LLM_LN1, 0), L->big.h, L->big.xs_h, L->big.ss, d_grouped ? L->NTh * 4 : L->NTh, 0);
+                         (const float*)sec(L, SMI_LLM_LN1, 0), L->big.h, L->big.xs_h, L->big.ss, pf_nparts_in(L, M, pass_family[ps]), 0);
       SMI_LAUNCH_CHECK();
       if ((rc = launch_layers_big(L, rows, M, pass_family[ps], st))) return rc;
     }
@@ -6434,12 +6458,14 @@ int smi_llm_debug_hidden(smi_llm* L, float* out_host, int n) {
 
 // Tests / debugging: raw copy of one scratch buffer (what: 0 q [Q] f32, 1 attention operand triples, 2 act triples, 3 h operand
 // triples, 4 h [H] f32, 5 engine granules [2][per buffer] u64, 6 partial sums of squares [H / 4], 7 layer-0 K cache of slot 0
-// head 0, 8 h + o_proj [H] (fused path)); returns the bytes copied in *got.
+// head 0, 8 h + o_proj [H] (fused path), 16 .. 20 the prefill workspace's q, attention triples, act triples, h triples, h for the
+// rows of the last smi_llm_debug_prefill_layer); returns the bytes copied in *got.
 int smi_llm_debug_read(smi_llm* L, int what, void* out_host, size_t cap, size_t* got) {
   SMI_REQUIRE(L && out_host && got, "smi_llm_debug_read: null argument");
   const void* src = nullptr;
   size_t n = 0;
   const size_t R = L->B > 0 ? (size_t)L->B : 1;   // buffers 0..4 and 6 hold one entry per live row
+  const size_t P = (size_t)L->dbg_pf_rows;        // buffers 16..20: the rows of the last smi_llm_debug_prefill_layer
   switch (what) {
     case 0: src = L->dec.q; n = R * L->Q * 4; break;
     case 1: src = L->dec.xs_attn; n = R * L->Q * 6; break;
@@ -6450,6 +6476,11 @@ int smi_llm_debug_read(smi_llm* L, int what, void* out_host, size_t cap, size_t*
     case 6: src = L->dec.ss; n = R * L->H; break;
     case 7: src = L->kcache; n = (size_t)L->cfg.max_positions * kHeadDim * 2; break;
     case 8: src = L->h2; n = (size_t)L->H * 4; break;
+    case 16: src = L->big.q; n = P * L->Q * 4; break;
+    case 17: src = L->big.xs_attn; n = P * L->Q * 6; break;
+    case 18: src = L->big.xs_act; n = P * L->I * 6; break;
+    case 19: src = L->big.xs_h; n = P * L->H * 6; break;
+    case 20: src = L->big.h; n = P * L->H * 4; break;
     default: smi_set_error("smi_llm_debug_read: what=%d", what); return SMI_EINVAL;
   }
   SMI_REQUIRE(src && n <= cap, "smi_llm_debug_read: buffer %d holds %zu bytes, out holds %zu", what, n, cap);
@@ -6558,6 +6589,71 @@ int smi_llm_debug_layer(smi_llm* L, int layer, int M, const int32_t* rows_host, 
   if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_layer: kernels failed: %s", hipGetErrorString(hipGetLastError())); }
   (void)hipFree(src);
   return rc;
+}
+
+// The prompt pass's counterpart of smi_llm_debug_layer: n_seq runs of consecutive positions (seq_host: (slot, first position, rows)
+// triples, plan order) as ONE row group in the big workspace, layer `layer`'s kernels up to `stage` through launch_layer_big -- the
+// function every layer of a real pass goes through -- with the tiles of pf_tiles_upload and the partial layout of pf_nparts_in.
+// stage 5: the whole layer, then the next layer's QKV (the one reader of the RMSNorm partials down_proj leaves).
+int smi_llm_debug_prefill_layer(smi_llm* L, int layer, int stage, int n_seq, const int32_t* seq_host, const float* hidden_host, int family) {
+  static_assert(SMI_PF_GROUPED == PF_GROUPED && SMI_PF_PGEMM == PF_PGEMM, "sparkmi_debug.h names the pass families");
+  SMI_REQUIRE(L && seq_host && hidden_host && n_seq >= 1, "smi_llm_debug_prefill_layer: bad argument");
+  SMI_REQUIRE(family == PF_GROUPED || family == PF_PGEMM, "smi_llm_debug_prefill_layer: family %d", family);
+  SMI_REQUIRE(layer >= 0 && layer < L->cfg.num_layers && stage >= 0 && stage <= 5, "smi_llm_debug_prefill_layer: layer %d stage %d", layer, stage);
+  SMI_REQUIRE(stage == 0 || layer < L->cfg.num_layers - 1, "smi_llm_debug_prefill_layer: the last layer of a prompt pass ends with its K/V append (stage 0 only)");
+  SMI_REQUIRE(!L->paged, "smi_llm_debug_prefill_layer needs a contiguous KV cache");
+  SMI_REQUIRE(!L->exact, "smi_llm_debug_prefill_layer: the exact-weights mode has no prompt pass of its own (it runs chunks)");
+  long long total = 0;
+  int longest = 0;
+  for (int b = 0; b < n_seq; ++b) {
+    const int sl = seq_host[3 * b], p0 = seq_host[3 * b + 1], n = seq_host[3 * b + 2];
+    SMI_REQUIRE(sl >= 0 && sl < L->cfg.max_slots && p0 >= 0 && n >= 1 && n <= L->cfg.max_positions && p0 <= L->cfg.max_positions - n,
+                "smi_llm_debug_prefill_layer: sequence %d = (slot %d, positions %d .. +%d) outside the cache", b, sl, p0, n);
+    for (int a = 0; a < b; ++a) SMI_REQUIRE(seq_host[3 * a] != sl, "smi_llm_debug_prefill_layer: sequences %d and %d share slot %d", a, b, sl);
+    total += n;
+    longest = p0 + n > longest ? p0 + n : longest;
+  }
+  SMI_REQUIRE(total >= 1 && total <= 4096, "smi_llm_debug_prefill_layer: %lld rows (a row group holds 1 .. 4096)", total);
+  const int M = (int)total;
+  SMI_HIP(hipDeviceSynchronize());
+  graphs_flush(L);
+  L->B = 0; L->session = 0; L->started = 0; L->dbg_pf_rows = 0;
+  L->attn_seg = segs_for(longest);
+  int rc;
+  if ((rc = ensure_plan(L, (size_t)M))) return rc;
+  if ((rc = ensure_big(L, M))) return rc;
+  L->host_rows.clear();
+  for (int b = 0; b < n_seq; ++b)
+    for (int t = 0; t < seq_host[3 * b + 2]; ++t) L->host_rows.push_back(RowDesc{seq_host[3 * b], seq_host[3 * b + 1] + t, 0, 0});
+  SMI_HIP(hipMemcpy(L->plan, L->host_rows.data(), (size_t)M * sizeof(RowDesc), hipMemcpyHostToDevice));
+  if ((rc = pf_tiles_upload(L, L->host_rows.data(), M, 0))) return rc;
+  float* src = nullptr;
+  SMI_HIP(hipMalloc((void**)&src, (size_t)M * L->H * 4));
+  if (hipMemcpy(src, hidden_host, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_prefill_layer: upload failed"); }
+  if (rc == SMI_OK) {
+    hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, src, L->KTh, M, (const float*)sec(L, SMI_LLM_LN1, layer), L->big.h, L->big.xs_h,
+                       L->big.ss, pf_nparts_in(L, M, family));
+    if (hipGetLastError() != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_prefill_layer: k_load_hidden launch failed"); }
+  }
+  if (rc == SMI_OK) rc = launch_layer_big(L, layer, L->plan, M, family, stage < 5 ? KQKV + stage : KD, 0);
+  if (rc == SMI_OK && stage == 5) rc = launch_layer_big(L, layer + 1, L->plan, M, family, KQKV, 0);
+  if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_prefill_layer: kernels failed: %s", hipGetErrorString(hipGetLastError())); }
+  (void)hipFree(src);
+  if (rc == SMI_OK) L->dbg_pf_rows = M;
+  return rc;
+}
+
+// Host only: the k_attn_pf2 tiles pf_tiles_build makes of M (slot, pos) rows, as (m0, n, slot, pos0) quadruples; *n = their count
+// (at most cap are written).
+int smi_llm_pf_tiles(const int32_t* rows_host, int M, int32_t* out, int cap, int32_t* n) {
+  SMI_REQUIRE(rows_host && n && M >= 0 && cap >= 0 && (out || cap == 0), "smi_llm_pf_tiles: bad argument");
+  std::vector<RowDesc> rows((size_t)M);
+  for (int m = 0; m < M; ++m) rows[m] = RowDesc{rows_host[2 * m], rows_host[2 * m + 1], 0, 0};
+  std::vector<PfTile> T;
+  pf_tiles_build(rows.data(), M, T);
+  for (size_t i = 0; i < T.size() && i < (size_t)cap; ++i) { out[4 * i] = T[i].m0; out[4 * i + 1] = T[i].n; out[4 * i + 2] = T[i].slot; out[4 * i + 3] = T[i].pos0; }
+  *n = (int32_t)T.size();
+  return SMI_OK;
 }
 
 // Diagnostics: the stamp buffer of the last smi_llm_debug_stamps launch as it is (10 ns ticks of s_memrealtime; k_lm32 leaves

@@ -224,6 +224,8 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),
+    "smi_llm_debug_prefill_layer": (_I, [_VP, _I, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),
+    "smi_llm_pf_tiles": (_I, [_P(C.c_int32), _I, _P(C.c_int32), _I, _P(C.c_int32)]),
     "smi_conv_form_count": (_I, []),
     "smi_conv_form_get": (_I, [_I, _P(ConvForm)]),
     "smi_conv_plan": (_I, [_P(ConvCase), _P(ConvPlanInfo)]),

@@ -878,10 +878,11 @@ class SparkLLM:
         self._lib.check(self._lib.smi_llm_debug_hidden(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "smi_llm_debug_hidden")
         return out
 
-    def debug_read(self, what: int) -> np.ndarray:
-        """Raw bytes of one scratch buffer (include/sparkmi_debug.h: smi_llm_debug_read)."""
+    def debug_read(self, what: int, nbytes: int = 1 << 22) -> np.ndarray:
+        """Raw bytes of one scratch buffer (include/sparkmi_debug.h: smi_llm_debug_read); ``nbytes``: room for the buffer asked
+        for (the prefill workspace's buffers are sized by their row count)."""
         self._need_diag("debug_read")
-        buf = np.zeros(1 << 22, dtype=np.uint8)
+        buf = np.zeros(int(nbytes), dtype=np.uint8)
         got = C.c_size_t(0)
         self._lib.check(self._lib.smi_llm_debug_read(self._h, int(what), buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(got)),
                    "smi_llm_debug_read")
@@ -928,21 +929,48 @@ class SparkLLM:
         assert hidden.shape == (M, c.hidden_size)
         self._lib.check(self._lib.smi_llm_debug_layer(self._h, layer, M, rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                                       hidden.ctypes.data_as(C.POINTER(C.c_float)), stage), "smi_llm_debug_layer")
+        fused_one = stage == 2 and M == 1 and int(rows[0, 0]) == 0 and self.debug_fused_o()   # (fuse_o_now: the row sits in slot 0)
+        return self._stage_outputs(layer, stage, M, [(int(s), int(p), 1) for s, p in rows], (0, 1, 2, 8 if fused_one else 4))
+
+    def _stage_outputs(self, layer: int, stage: int, M: int, runs, bufs) -> dict:
+        """Stage ``stage``'s outputs for M rows in transformers' layouts.  ``runs``: (slot, first position, rows) of the K/V rows
+        the call appended, in row order; ``bufs``: smi_llm_debug_read's ids of (q, attention triples, act triples, h)."""
+        c = self.cfg
         nh, Q = c.num_attention_heads, c.num_attention_heads * 64
         unpair = (np.arange(64) >> 1) + 32 * (np.arange(64) & 1)          # kernel row i of a head holds transformers' dim unpair[i]
         if stage == 0:
-            qk = self.debug_read(0).view(np.float32).reshape(M, nh, 64)
+            qk = self.debug_read(bufs[0], M * Q * 4).view(np.float32).reshape(M, nh, 64)
             q = np.empty_like(qk)
             q[:, :, unpair] = qk
-            kv = [self.debug_get_kv(layer, int(s), int(p), 1) for s, p in rows]
+            kv = [self.debug_get_kv(layer, s, p, n) for s, p, n in runs]
             return {"q": q, "k": np.concatenate([k for k, _ in kv]), "v": np.concatenate([v for _, v in kv])}
         if stage == 1:
-            t = self._from_triples(self.debug_read(1), Q, M).reshape(M, 2, nh, 32)     # k tile = half * heads + head
+            t = self._from_triples(self.debug_read(bufs[1], M * Q * 6), Q, M).reshape(M, 2, nh, 32)     # k tile = half * heads + head
             return {"attn": np.ascontiguousarray(t.transpose(0, 2, 1, 3)).reshape(M, Q)}
         if stage == 3:
-            return {"act": self._from_triples(self.debug_read(2), c.intermediate_size, M)}
-        fused_one = stage == 2 and M == 1 and int(rows[0, 0]) == 0 and self.debug_fused_o()   # (fuse_o_now: the row sits in slot 0)
-        return {"h": self.debug_read(8 if fused_one else 4).view(np.float32).reshape(M, c.hidden_size)[:M].copy()}
+            return {"act": self._from_triples(self.debug_read(bufs[2], M * c.intermediate_size * 6), c.intermediate_size, M)}
+        return {"h": self.debug_read(bufs[3], M * c.hidden_size * 4).view(np.float32).reshape(M, c.hidden_size)[:M].copy()}
+
+    PF_GROUPED, PF_PGEMM = 1, 2      # include/sparkmi_debug.h: SMI_PF_*
+
+    def debug_prefill_layer(self, layer: int, seqs, hidden: np.ndarray, stage: int, family: int = 2) -> dict:
+        """One layer of the PROMPT pass up to ``stage`` on caller rows (``smi_llm_debug_prefill_layer``): ``seqs`` = (slot, first
+        position, rows) per sequence, ``hidden`` (M, hidden) fp32 for the M = sum of rows, ``family`` PF_PGEMM / PF_GROUPED.
+        Returns ``debug_layer``'s dicts for stages 0-4; stage 5 (the layer, then layer + 1's QKV) returns stage 0's dict for
+        layer + 1."""
+        self._need_diag("debug_prefill_layer")
+        c = self.cfg
+        seqs = np.ascontiguousarray(np.asarray(seqs, dtype=np.int32).reshape(-1, 3))
+        M = int(seqs[:, 2].sum())
+        hidden = np.ascontiguousarray(hidden, dtype=np.float32)
+        assert hidden.shape == (M, c.hidden_size)
+        self._lib.check(self._lib.smi_llm_debug_prefill_layer(self._h, layer, stage, seqs.shape[0], seqs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                              hidden.ctypes.data_as(C.POINTER(C.c_float)), family),
+                        "smi_llm_debug_prefill_layer")
+        runs = [(int(s), int(p), int(n)) for s, p, n in seqs]
+        if stage == 5:
+            return self._stage_outputs(layer + 1, 0, M, runs, (16, 17, 18, 20))
+        return self._stage_outputs(layer, stage, M, runs, (16, 17, 18, 20))
 
     def debug_fused_o(self) -> bool:
         """One live row in slot 0 takes the fused attention + o_proj kernel (smi_llm.hip: fuse_o_now) unless SPARKMI_NO_FUSE_O=1 was set
