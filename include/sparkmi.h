@@ -391,6 +391,48 @@ int smi_llm_slots_tokens(smi_llm* h, const int32_t* slots, int n, int64_t* out_h
  * SMI_EINVAL, nothing written. */
 int smi_llm_poll(smi_llm* h, const int32_t* slots, const int32_t* from, int n, int64_t* out_host, int cap, int32_t* n_out,
                  int32_t* count, int32_t* finished, void* stream);
+/* Park and resume: a sequence leaves its KV slot as a snapshot ("blob") in CALLER-OWNED device memory and comes back later into
+ * any free slot, with not one bit changed -- so more requests may be open than there are decode rows (a streaming server parks
+ * the requests that are far ahead of their listeners).  The library keeps no pointer to a blob: it may be freed, copied or
+ * restored more than once as soon as the call's work on the stream has run.
+ *   smi_llm_slot_blob_bytes: the snapshot size of the sequence now in `slot` (host arithmetic, no device work).  It depends on
+ *     the sequence's cache positions, tokens emitted and record set: a part belonging to a feature the sequence does not use
+ *     takes no space (the penalty history row, 2 * vocab_size bytes, only with a penalty record; the prompt ids,
+ *     4 * prompt length bytes, only with no_repeat_ngram_size; the log-probabilities only with return_log_probs; the bias /
+ *     stop record only with one).
+ *   smi_llm_slots_save: writes the complete state of each listed busy slot into blobs_dev[i] (16-byte aligned, caps[i] bytes
+ *     available; used[i] = bytes written = smi_llm_slot_blob_bytes).  A snapshot, not a move: the slots stay exactly as they
+ *     were; parking is a save followed by smi_llm_retire_many.  Between decode calls of a session, on the caller's stream,
+ *     outside any capture; it touches no cached step graph (like smi_llm_poll) and does not synchronise.
+ *   Blob layout (all of it device memory; every part starts on a 16-byte boundary): a header -- magic, sizes, the feature byte,
+ *     a stamp of the handle's configuration, of the handle and of the session (the smi_llm_session_begin it was saved in),
+ *     cache length, prompt length, the admission number (sampler stream id), the sampling / penalty / log-probability /
+ *     allowed-set / n-gram records as admitted, a checksum of those host-written bytes, and 32 bytes the gather kernel writes:
+ *     the row descriptor (position, last token, token index), count, finished -- then the bias / stop record if the sequence
+ *     has one, then K/V [layer][K, V][kv head][position][row] for the positions written so far, the sequence's column of
+ *     the token history, of the log-probabilities, its penalty history row and its prompt ids.  The host part travels IN the
+ *     blob's header: a blob is self-contained.  Nothing in it names the slot it came from: saving a restored sequence again
+ *     gives the same bytes.  Not in it, because they are session state: the eos list, the handle's sampler settings and seed.
+ *     A blob belongs to the handle and session that wrote it and goes back nowhere else: the handle and session stamps decide
+ *     that.  The configuration stamp (a hash of the raw smi_llm_cfg bytes) is checked first and only words the refusal of a
+ *     blob from a handle built otherwise; it is no means of telling whether two handles' configurations are compatible.
+ *   smi_llm_slots_restore: puts each snapshot (bytes[i] = its used size) into a free KV slot -- the lowest free ones, in order,
+ *     returned in slots_out; not necessarily the slot or row position it came from -- through an admission's bookkeeping:
+ *     slot and pages (pages of its own, whatever the original shared with a fork's other takes; all or nothing), records,
+ *     feature byte, and the re-embedding of every live row.  The sequence keeps its admission number; no new one is given
+ *     out.  The sampler stream is keyed by (seed; token index, admission number) and every decode kernel treats rows
+ *     independently, so the restored sequence emits exactly the tokens (log-probabilities, stops) it would have emitted
+ *     without the park.  Restoring a snapshot whose original is still live is allowed: both continue with the same stream
+ *     and emit the same tokens.  Synchronises the stream (it reads the headers back, as an admission reads the live rows).
+ *   Refusals, each changing nothing: outside a session SMI_ESTATE; a blob saved under another configuration, by another
+ *     handle or in an earlier session of this one SMI_ESTATE; a truncated or corrupt blob (magic, checksum, sizes that do not
+ *     add up to bytes[i], impossible lengths), a cap below the needed size, a slot that is not busy or listed twice, a
+ *     misaligned address SMI_EINVAL; fewer free slots than n SMI_ESTATE; a page pool that cannot hold all n SMI_ENOMEM
+ *     (nothing allocated).  The payload behind the header is not checksummed: every bound the scatter uses comes from the
+ *     checked header, so a damaged payload can change the sequence's tokens but cannot write outside its slot. */
+int smi_llm_slot_blob_bytes(smi_llm* h, int slot, size_t* bytes);
+int smi_llm_slots_save(smi_llm* h, const int32_t* slots, int n, void* const* blobs_dev, const size_t* caps, size_t* used, void* stream);
+int smi_llm_slots_restore(smi_llm* h, const void* const* blobs_dev, const size_t* bytes, int n, int32_t* slots_out, void* stream);
 /* count_host / finished_host [SMI_MAX_ROWS]: tokens emitted and eos flag per KV slot, one round trip. */
 int smi_llm_status(smi_llm* h, int32_t* count_host, int32_t* finished_host, void* stream);
 /* Test/teacher-forcing entry: feeds ids_host[0..S) at positions 0..S-1 of slot 0 (cache reset) and

@@ -27,7 +27,9 @@
 #include "smi_common.h"
 #include <stdio.h>
 #include <string.h>
+#include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -3800,6 +3802,9 @@ struct smi_llm {
   int attn_seg;                        // context segments per (head, row) of the attention launches being issued (1 = unsplit)
   float* apart; size_t apart_floats;   // segment partials [rows][heads][attn_seg][66]
   int slot_busy[kMaxRows], slot_len[kMaxRows];      // host: slot in use; prompt length + tokens emitted (cache positions used)
+  int slot_plen[kMaxRows];      // host: the prompt length of the sequence in the slot (slot_len - slot_plen = its token index)
+  uint64_t handle_id, session_gen;   // blob stamps: this handle among the process's, and its generations / sessions so far (gen_reset)
+  std::vector<unsigned char> host_blob;   // host staging of the blob headers a save uploads
   // sampling state (smi_llm_set_sampling)
   int do_sample, top_k; float temperature, top_p; unsigned long long seed;
   // host: what the record set of the sequence in each slot (live or being admitted) asks of a step, F_* bits: its sampling record
@@ -4882,6 +4887,152 @@ __global__ __launch_bounds__(64) void k_poll(const int64_t* hist, const int32_t*
   for (int t = from + (int)threadIdx.x; t < end; t += 64) rec[1 + (t - from)] = hist[(size_t)t * kMaxRows + sl];
 }
 
+// ------------------------------------------------------------------------------------------
+// Park and resume (smi_llm_slots_save / smi_llm_slots_restore; include/sparkmi.h states the contract).  A sequence's snapshot
+// ("blob") is one contiguous piece of caller-owned device memory:
+//   BlobHdr                      host-written fields (lengths, stamps, the records as admitted), and 32 bytes the gather kernel
+//                                writes: the row descriptor (slot field zero), count, finished
+//   SeqRec                       only with bias entries / stop sequences
+//   K/V   [layer][K, V][kv head][position 0 .. npos)[row bytes]   npos = cache positions written = len - 1
+//   hist  [nhist] int64          the sequence's column of the history, dense (nhist = len - plen = its token index)
+//   lp    [nhist] f32            only with return_log_probs
+//   phist [vocab] u16            only with a penalty record
+//   pctx  [plen] int32           only with no_repeat_ngram_size
+// every part starts on a 16-byte boundary (the tail of a part is padding, written as zero by the save and never read).
+// Nothing in a blob names the slot it came from.
+// ------------------------------------------------------------------------------------------
+struct BlobHdr {
+  char magic[8];                  // "SMISLOT1"
+  uint32_t hdr_bytes;             // sizeof(BlobHdr) (+ sizeof(SeqRec)): where the K/V part starts
+  uint32_t feat;                  // the slot's feature byte (smi_llm::slot_feat)
+  uint64_t total_bytes;
+  uint64_t cfg_stamp;             // FNV-1a of the handle's smi_llm_cfg
+  uint64_t handle_id, session_gen;   // which handle, which smi_llm_session_begin of it
+  int32_t len, plen, nhist, seqid;   // slot_len, prompt length, history entries, admission number
+  uint64_t reserved;              // 0
+  uint64_t check;                 // FNV-1a of the host-written bytes of the header (this field and `dev` as zero), SeqRec included
+  struct Dev { RowDesc row; int32_t count, finished, pad[2]; } dev;   // written by k_slot_cols<true>
+  SampRec samp; PenRec pen; int32_t lp, ngram, ngplen, pad; AllowRec allow;
+};
+static_assert(sizeof(BlobHdr) % 16 == 0 && sizeof(SeqRec) % 16 == 0 && offsetof(BlobHdr, dev) % 16 == 0, "blob parts are 16-byte aligned");
+
+// One listed slot of a save / restore call.  Offsets are in 16-byte units from the blob's start; 0 = the sequence has no such part.
+struct SlotXfer {
+  unsigned char* blob;
+  int32_t slot, npos, nhist, npctx;
+  uint32_t o_kv, o_hist, o_lp, o_phist, o_pctx, pad;
+};
+struct ParkP {
+  SlotXfer s[kMaxRows];
+  unsigned char* kcache;      // layer 0's K cache (layer l at + l * layer_bytes)
+  unsigned char* vcache;
+  size_t layer_bytes;
+  int n_kv, max_pos;
+  int piece_shift;            // log2(16-byte pieces per 64-element row): 3 (bf16) or 4 (f32)
+  KvMap km;
+  RowDesc* rows; int B;       // the live row list (save: the slot's row goes into the blob)
+  int64_t* hist; float* lp; uint16_t* phist; int32_t* pctx;
+  int32_t *count, *finished;
+  int V;
+};
+constexpr int kParkPieces = 4;   // 16-byte pieces per thread of k_slot_kv, all loads before the stores
+
+// The K/V part: cache positions [0, npos) of each listed slot <-> its blob, every layer, K and V, every kv head, in 16-byte
+// pieces, the cache side addressed through KvMap as k_kv_fork does (bf16 / f32, contiguous / paged: the same code); the blob side
+// is dense, so consecutive lanes touch consecutive pieces on both sides (a cache row is 128 or 256 contiguous bytes).
+// grid: x = blocks of 256 * kParkPieces (position, piece) pairs of the call's longest slot, y = listed slot,
+// z = (layer, K / V, kv head).  A block past its own slot's last piece exits at once.
+template <bool SAVE>
+__global__ __launch_bounds__(256) void k_slot_kv(ParkP p) {
+  const SlotXfer& x = p.s[blockIdx.y];
+  const int total = x.npos << p.piece_shift;   // pieces of one (layer, K / V, kv head) plane
+  const int u0 = (int)blockIdx.x * (256 * kParkPieces) + (int)threadIdx.x;
+  if ((int)blockIdx.x * (256 * kParkPieces) >= total) return;
+  const int kvh = (int)blockIdx.z % p.n_kv, isv = ((int)blockIdx.z / p.n_kv) & 1, layer = (int)blockIdx.z / (2 * p.n_kv);
+  unsigned char* base = (isv ? p.vcache : p.kcache) + (size_t)layer * p.layer_bytes;
+  const size_t rb = (size_t)16 << p.piece_shift;   // bytes of one row
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // (a native vector: c[] and v[] below stay in registers)
+  u32x4* plane = (u32x4*)x.blob + (size_t)x.o_kv + (size_t)blockIdx.z * (size_t)total;
+  // Every thread forms all its addresses and issues all its loads before its first store.  A piece past the plane's end is
+  // clamped to the last one (total >= 1 here), so the loads are unconditional; only the stores are predicated.
+  u32x4* c[kParkPieces];
+  u32x4 v[kParkPieces];
+#pragma unroll
+  for (int k = 0; k < kParkPieces; ++k) {
+    const int u = min(u0 + 256 * k, total - 1);
+    const int pos = u >> p.piece_shift, piece = u & ((1 << p.piece_shift) - 1);
+    c[k] = (u32x4*)(base + kv_row(p.km, x.slot, kvh, p.n_kv, p.max_pos, pos) * rb) + piece;
+    v[k] = SAVE ? *c[k] : plane[u];
+  }
+#pragma unroll
+  for (int k = 0; k < kParkPieces; ++k) {
+    if (u0 + 256 * k >= total) continue;
+    if (SAVE) plane[u0 + 256 * k] = v[k];
+    else *c[k] = v[k];
+  }
+}
+
+// The rest of a sequence's device state: its column of hist (and of lp), strided by kMaxRows on the engine side and dense in
+// the blob; its row of phist; its row of pctx up to the prompt length; count / finished and (save) its row descriptor.  Only
+// the parts the SlotXfer names.  grid: x = a few blocks that stride over each part, y = listed slot.
+template <bool SAVE>
+__global__ __launch_bounds__(256) void k_slot_cols(ParkP p) {
+  const SlotXfer& x = p.s[blockIdx.y];
+  const int sl = x.slot;
+  const int t0 = (int)(blockIdx.x * 256 + threadIdx.x), T = (int)gridDim.x * 256;
+  uint4* b16 = (uint4*)x.blob;
+  {
+    int64_t* bh = (int64_t*)(b16 + x.o_hist);
+    for (int t = t0; t < (SAVE ? (x.nhist + 1) & ~1 : x.nhist); t += T) {   // (save: the part's padding is written as zero)
+      if (SAVE) bh[t] = t < x.nhist ? p.hist[(size_t)t * kMaxRows + sl] : 0;
+      else p.hist[(size_t)t * kMaxRows + sl] = bh[t];
+    }
+  }
+  if (x.o_lp) {
+    float* bl = (float*)(b16 + x.o_lp);
+    for (int t = t0; t < (SAVE ? (x.nhist + 3) & ~3 : x.nhist); t += T) {
+      if (SAVE) bl[t] = t < x.nhist ? p.lp[(size_t)t * kMaxRows + sl] : 0.f;
+      else p.lp[(size_t)t * kMaxRows + sl] = bl[t];
+    }
+  }
+  if (x.o_phist) {
+    uint16_t* row = p.phist + (size_t)sl * p.V;
+    if ((p.V & 7) == 0) {   // every slot's row starts on a 16-byte boundary
+      uint4 *r4 = (uint4*)row, *bp = b16 + x.o_phist;
+      for (int t = t0; t < (p.V >> 3); t += T) {
+        if (SAVE) bp[t] = r4[t];
+        else r4[t] = bp[t];
+      }
+    } else {
+      uint16_t* bp = (uint16_t*)(b16 + x.o_phist);
+      for (int t = t0; t < (SAVE ? (p.V + 7) & ~7 : p.V); t += T) {
+        if (SAVE) bp[t] = t < p.V ? row[t] : (uint16_t)0;
+        else row[t] = bp[t];
+      }
+    }
+  }
+  if (x.o_pctx) {
+    int32_t *row = p.pctx + (size_t)sl * p.max_pos, *bp = (int32_t*)(b16 + x.o_pctx);
+    for (int t = t0; t < (SAVE ? (x.npctx + 3) & ~3 : x.npctx); t += T) {
+      if (SAVE) bp[t] = t < x.npctx ? row[t] : 0;
+      else row[t] = bp[t];
+    }
+  }
+  if (blockIdx.x == 0) {
+    BlobHdr::Dev* d = (BlobHdr::Dev*)(x.blob + offsetof(BlobHdr, dev));
+    if (SAVE) {
+      if ((int)threadIdx.x < p.B && p.rows[threadIdx.x].slot == sl) {   // exactly one live row names a busy slot
+        const RowDesc* r = p.rows + threadIdx.x;
+        d->row.slot = 0; d->row.pos = r->pos; d->row.token = r->token; d->row.flags = r->flags;
+        d->count = p.count[sl]; d->finished = p.finished[sl]; d->pad[0] = 0; d->pad[1] = 0;
+      }
+    } else if (threadIdx.x == 0) {   // (the host puts the row into the live row list)
+      p.count[sl] = d->count;
+      p.finished[sl] = d->finished;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -4997,6 +5148,8 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->poll_dev = nullptr; L->poll_host = nullptr;
   L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
   L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
+  memset(L->slot_plen, 0, sizeof(L->slot_plen));
+  { static std::atomic<uint64_t> handles{0}; L->handle_id = ++handles; L->session_gen = 0; }
   const size_t esz = cfg->kv_dtype ? 4 : 2;
   L->paged = cfg->kv_page_tokens > 0; L->pshift = 0; L->ppslot = 0; L->ptab = nullptr;
   memset(L->slot_pages, 0, sizeof(L->slot_pages));
@@ -5329,6 +5482,8 @@ static int gen_reset(smi_llm* L, const int64_t* eos_ids, int n_eos, int nseq, hi
     for (int b = 0; b < kMaxRows; ++b) pages_release(L, b);
   memset(L->slot_busy, 0, sizeof(L->slot_busy));
   memset(L->slot_len, 0, sizeof(L->slot_len));
+  memset(L->slot_plen, 0, sizeof(L->slot_plen));
+  ++L->session_gen;   // blobs of the earlier sessions are refused from here on
   live_set(L, nullptr, 0);
   for (int e = 0; e < SMI_MAX_EOS; ++e) L->hctl.eos[e] = e < n_eos ? (long long)eos_ids[e] : -1;
   L->hctl.n_eos = n_eos;
@@ -5365,7 +5520,7 @@ int smi_llm_prefill(smi_llm* L, const int64_t* ids, const int32_t* lens, int B, 
   }
   if ((rc = gen_reset(L, eos_ids, n_eos, B, st))) return rc;
   if ((rc = pages_ensure(L, slots, lens, B, st))) { L->started = 0; return rc; }   // (cannot happen after the check above; the old generation is gone by now)
-  for (int b = 0; b < B; ++b) { L->slot_busy[b] = 1; L->slot_len[b] = lens[b] + 1; }   // (the first step, enqueued below, takes position lens[b])
+  for (int b = 0; b < B; ++b) { L->slot_busy[b] = 1; L->slot_len[b] = lens[b] + 1; L->slot_plen[b] = lens[b]; }   // (the first step, enqueued below, takes position lens[b])
   live_set(L, slots, B);
   // the captured decode step is kept across utterances: eos ids and the seed live in device memory (Ctl); smi_llm_decode
   // re-captures only when the row count, the context-segment count or the slot mapping differ from the captured ones
@@ -5677,6 +5832,69 @@ static void recs_put(smi_llm* L, int sl, const SlotRecs& r) {
   L->slot_feat[sl] = r.feat;
 }
 
+// ---- the steps every way into a KV slot shares: an admission (admit) and the return of a parked sequence
+// (smi_llm_slots_restore) take slots, install records and enter the live row list through these ----
+// The n lowest free KV slots, in order; returns how many there are (fewer than n: the caller refuses).
+static int slots_take_free(const smi_llm* L, int n, int32_t* slots) {
+  const int slot_cap = L->cfg.max_slots < kMaxRows ? L->cfg.max_slots : kMaxRows;
+  int k = 0;
+  for (int sl = 0; sl < slot_cap && k < n; ++sl)
+    if (!L->slot_busy[sl]) slots[k++] = sl;
+  return k;
+}
+// The records of N new sequences go into their slots, on the host and on the device: Ctl (with the sequence numbers), the union
+// of the constrained slots' tiles, the bias / stop records (which add F_BIAS / F_STOP to the feature byte).  A slot whose device
+// bias / stop record is all zero and stays so is not touched.  old[] receives what the slots held; on an error the caller
+// calls recs_withdraw.
+static int recs_install(smi_llm* L, const char* who, const int32_t* slots, int N, const SlotRecs* recs, const SeqRec* seqs, SlotRecs* old,
+                        hipStream_t st) {
+  for (int j = 0; j < N; ++j) {
+    old[j] = recs_get(L, slots[j]);
+    recs_put(L, slots[j], recs[j]);
+  }
+  if (hipMemcpyAsync(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice, st) != hipSuccess) {
+    smi_set_error("%s: uploading the generation controls failed", who);
+    return SMI_EHIP;
+  }
+  { const int rc = allow_tiles_upload(L, st); if (rc) return rc; }   // the union now holds the new sequences' tiles
+  for (int j = 0; j < N; ++j) {
+    const int sl = slots[j];
+    const SeqRec& rec = seqs[j];
+    const int on = rec.n_bias > 0 || rec.n_stop > 0;
+    L->slot_feat[sl] |= (rec.n_bias > 0 ? F_BIAS : 0) | (rec.n_stop > 0 ? F_STOP : 0);
+    if (!on && !L->seq_dirty[sl]) continue;
+    L->hseq[(size_t)sl] = rec;
+    L->seq_dirty[sl] = on;
+    // (pageable source: staged before the call returns; hseq[sl] is rewritten only by a later entry into the slot)
+    if (hipMemcpyAsync(L->seq + sl, &L->hseq[(size_t)sl], sizeof(SeqRec), hipMemcpyHostToDevice, st) != hipSuccess) {
+      L->seq_dirty[sl] = 1;
+      smi_set_error("%s: uploading the sequence records failed", who);
+      return SMI_EHIP;
+    }
+  }
+  return SMI_OK;
+}
+// Nobody entered after all: records and pages (and page references) as before (the device copy is rewritten by the next entry;
+// seq_dirty stays: the next entry rewrites the device record).
+static void recs_withdraw(smi_llm* L, const int32_t* slots, int N, const SlotRecs* old) {
+  for (int j = 0; j < N; ++j) { recs_put(L, slots[j], old[j]); slot_clear(L, slots[j]); }
+  if (L->paged)
+    for (int j = 0; j < N; ++j) pages_release(L, slots[j]);
+}
+// The N sequences are in their slots: busy, with their lengths, their rows behind the live ones; every live row is re-embedded
+// from E[token] (session_set_rows).
+static int slots_enter(smi_llm* L, std::vector<RowDesc>& live, const int32_t* slots, int N, const RowDesc* rows, const int32_t* plen,
+                       const int32_t* len, int32_t* slots_out, hipStream_t st) {
+  for (int j = 0; j < N; ++j) {
+    live.push_back(rows[j]);
+    L->slot_busy[slots[j]] = 1;
+    L->slot_len[slots[j]] = len[j];
+    L->slot_plen[slots[j]] = plen[j];
+    slots_out[j] = slots[j];
+  }
+  return session_set_rows(L, live, st);
+}
+
 static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t st) {
   const int64_t* ids = rq.ids;
   const int32_t *lens = rq.lens, *n_ret = rq.n_ret, *want_lp = rq.want_lp;
@@ -5722,10 +5940,7 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
   std::vector<RowDesc> live;
   if ((rc = session_live_rows(L, live, st))) return rc;
   int32_t slots[kMaxRows];   // one per take, lowest free first
-  int k = 0;
-  for (int sl = 0; sl < L->cfg.max_slots && k < N; ++sl)
-    if (!L->slot_busy[sl]) slots[k++] = sl;
-  SMI_REQUIRE(k == N, "smi_llm_admit: no free KV slot");
+  SMI_REQUIRE(slots_take_free(L, N, slots) == N, "smi_llm_admit: no free KV slot");
   if ((rc = validate_prompts(L, ids, lens, n, P_max))) return rc;   // nothing touched yet
   // take j belongs to prompt src[j]; the first take of a prompt is its leader, the slot its prompt rows are prefilled in
   int32_t src[kMaxRows], lead[kMaxRows], lens_j[kMaxRows];
@@ -5763,10 +5978,10 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
   }
   // the records go up with the sequence numbers, before the admission's own step: its finalize emits the first token
   const int seq0 = L->admit_seq;
-  SlotRecs old[kMaxRows];
+  SlotRecs old[kMaxRows], recs[kMaxRows];
+  std::vector<SeqRec> seqs((size_t)N);   // the bias / stop records of the new takes (a fork's followers get their prompt's tail)
   for (int j = 0; j < N; ++j) {
-    old[j] = recs_get(L, slots[j]);
-    SlotRecs r;
+    SlotRecs& r = recs[j];
     r.seqid = L->admit_seq++;
     r.samp = samp_record(params ? &params[j] : nullptr, L->cfg.vocab_size);
     r.pen = pen_record(pens ? &pens[j] : nullptr);
@@ -5775,41 +5990,15 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
     r.ngram = ngram ? ngram[j] : 0;
     r.ngplen = r.ngram > 0 ? lens_j[j] : 0;
     r.feat = (r.samp.mode == SMI_SAMPLING_SAMPLE ? F_SAMPLE : 0) | (r.pen.on ? F_PEN : 0) | (r.lp ? F_LP : 0) | (r.allow.n > 0 ? F_ALLOW : 0) |
-             (r.ngram > 0 ? F_NGRAM : 0);
-    recs_put(L, slots[j], r);   // (F_BIAS / F_STOP: with the sequence records below)
+             (r.ngram > 0 ? F_NGRAM : 0);   // (F_BIAS / F_STOP: recs_install, from the sequence record)
+    seqs[(size_t)j] = seq_record(seq ? &seq[j] : nullptr, ids + (size_t)src[j] * P_max, lens_j[j]);
   }
-  // undo: nothing was admitted -- sequence numbers, records and pages (and page references) as before (the device copy is
-  // rewritten by the next admission; seq_dirty stays: the next admission rewrites the device record)
+  // undo: nothing was admitted -- sequence numbers, records and pages (and page references) as before
   auto undo = [&]() {
-    for (int j = 0; j < N; ++j) { recs_put(L, slots[j], old[j]); slot_clear(L, slots[j]); }
+    recs_withdraw(L, slots, N, old);
     L->admit_seq = seq0;
-    if (L->paged)
-      for (int j = 0; j < N; ++j) pages_release(L, slots[j]);
   };
-  if (hipMemcpyAsync(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice, st) != hipSuccess) {
-    undo();
-    smi_set_error("smi_llm_admit: uploading the generation controls failed");
-    return SMI_EHIP;
-  }
-  if ((rc = allow_tiles_upload(L, st))) { undo(); return rc; }   // the union now holds the new takes' tiles
-  // the bias / stop records of the new takes (a fork's followers get their prompt's tail); a slot whose device record is all
-  // zero and stays so is not touched
-  for (int j = 0; j < N; ++j) {
-    const int sl = slots[j];
-    const SeqRec rec = seq_record(seq ? &seq[j] : nullptr, ids + (size_t)src[j] * P_max, lens_j[j]);
-    const int on = rec.n_bias > 0 || rec.n_stop > 0;
-    L->slot_feat[sl] |= (rec.n_bias > 0 ? F_BIAS : 0) | (rec.n_stop > 0 ? F_STOP : 0);
-    if (!on && !L->seq_dirty[sl]) continue;
-    L->hseq[(size_t)sl] = rec;
-    L->seq_dirty[sl] = on;
-    // (pageable source: staged before the call returns; hseq[sl] is rewritten only by a later admission into the slot)
-    if (hipMemcpyAsync(L->seq + sl, &L->hseq[(size_t)sl], sizeof(SeqRec), hipMemcpyHostToDevice, st) != hipSuccess) {
-      L->seq_dirty[sl] = 1;
-      undo();
-      smi_set_error("smi_llm_admit_biased: uploading the sequence records failed");
-      return SMI_EHIP;
-    }
-  }
+  if ((rc = recs_install(L, "smi_llm_admit", slots, N, recs, seqs.data(), old, st))) { undo(); return rc; }
   // the prompt ids of the takes that ban n-grams -> their slots' rows of the context store (a fork's followers get their
   // leader's prompt); a slot admitted without the feature never reads its row
   if (ngram) {
@@ -5879,13 +6068,9 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
   }
   std::vector<RowDesc> fresh;
   if ((rc = session_live_rows(L, fresh, st))) return rc;
-  for (int j = 0; j < N; ++j) {
-    live.push_back(fresh[j]);
-    L->slot_busy[slots[j]] = 1;
-    L->slot_len[slots[j]] = lens_j[j] + 1;
-    slots_out[j] = slots[j];
-  }
-  return session_set_rows(L, live, st);
+  int32_t len_j[kMaxRows];
+  for (int j = 0; j < N; ++j) len_j[j] = lens_j[j] + 1;
+  return slots_enter(L, live, slots, N, fresh.data(), lens_j, len_j, slots_out, st);
 }
 
 // The exported admissions: each is the next one with null for what it does not take (include/sparkmi.h).
@@ -5971,6 +6156,221 @@ int smi_llm_retire_many(smi_llm* L, const int32_t* slots, int n, void* stream) {
   { const int rct = allow_tiles_upload(L, st); if (rct) return rct; }
   if (L->B == 0) return SMI_OK;
   return launch_embed(L, L->rows, L->B, st);
+}
+
+// ---- park and resume: a sequence leaves its KV slot as a blob in caller-owned device memory and comes back later, into any
+// free slot (include/sparkmi.h; the blob's layout is at BlobHdr) ----
+static uint64_t fnv1a(const void* data, size_t n, uint64_t h = 1469598103934665603ull) {
+  const unsigned char* b = (const unsigned char*)data;
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+  return h;
+}
+static size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+// Where the parts of a blob lie, from what its header says: a sequence of `len` cache positions (len - 1 of them written),
+// prompt length plen, feature byte feat.  Part offsets in bytes (0: absent).
+struct BlobLay { size_t hdr, kv, hist, lp, phist, pctx, total; int npos, nhist, npctx; };
+static BlobLay blob_layout(const smi_llm* L, int len, int plen, unsigned feat) {
+  BlobLay b;
+  memset(&b, 0, sizeof(b));
+  b.npos = len - 1;
+  b.nhist = len - plen < L->max_steps ? len - plen : L->max_steps;
+  b.npctx = (feat & F_NGRAM) ? plen : 0;
+  b.hdr = sizeof(BlobHdr) + ((feat & (F_BIAS | F_STOP)) ? sizeof(SeqRec) : 0);
+  const size_t pos_bytes = (size_t)L->cfg.num_layers * 2 * L->cfg.num_kv_heads * kHeadDim * (L->cfg.kv_dtype ? 4 : 2);
+  size_t o = b.hdr;
+  b.kv = o; o += (size_t)b.npos * pos_bytes;
+  b.hist = o; o += up16((size_t)b.nhist * 8);
+  if (feat & F_LP) { b.lp = o; o += up16((size_t)b.nhist * 4); }
+  if (feat & F_PEN) { b.phist = o; o += up16((size_t)L->cfg.vocab_size * 2); }
+  if (feat & F_NGRAM) { b.pctx = o; o += up16((size_t)b.npctx * 4); }
+  b.total = o;
+  return b;
+}
+static SlotXfer blob_xfer(const BlobLay& b, void* blob, int slot) {
+  SlotXfer x;
+  memset(&x, 0, sizeof(x));
+  x.blob = (unsigned char*)blob; x.slot = slot; x.npos = b.npos; x.nhist = b.nhist; x.npctx = b.npctx;
+  x.o_kv = (uint32_t)(b.kv >> 4); x.o_hist = (uint32_t)(b.hist >> 4); x.o_lp = (uint32_t)(b.lp >> 4);
+  x.o_phist = (uint32_t)(b.phist >> 4); x.o_pctx = (uint32_t)(b.pctx >> 4);
+  return x;
+}
+// the feature byte a record set gives (admit builds the same bits record by record)
+static unsigned recs_feat(const BlobHdr& h, const SeqRec* q) {
+  return (h.samp.mode == SMI_SAMPLING_SAMPLE ? F_SAMPLE : 0) | (h.pen.on ? F_PEN : 0) | (h.lp ? F_LP : 0) | (h.allow.n > 0 ? F_ALLOW : 0) |
+         (h.ngram > 0 ? F_NGRAM : 0) | (q && q->n_bias > 0 ? F_BIAS : 0) | (q && q->n_stop > 0 ? F_STOP : 0);
+}
+// The header's checksum: its host-written bytes (`check` and the kernel-written `dev` as zero) and the SeqRec behind it.
+static uint64_t blob_check(const unsigned char* hdr, size_t hdr_bytes) {
+  BlobHdr h;
+  memcpy(&h, hdr, sizeof(h));
+  h.check = 0;
+  memset(&h.dev, 0, sizeof(h.dev));
+  return fnv1a(hdr + sizeof(BlobHdr), hdr_bytes - sizeof(BlobHdr), fnv1a(&h, sizeof(h)));
+}
+// the two launches of a save (SAVE) or restore over the listed slots; every bound comes from host-checked values
+static int park_launch(smi_llm* L, bool save, const SlotXfer* xs, int n, hipStream_t st) {
+  ParkP p;
+  memset(&p, 0, sizeof(p));
+  int npos = 0, items = 1;
+  const int V = L->cfg.vocab_size;
+  for (int i = 0; i < n; ++i) {
+    p.s[i] = xs[i];
+    npos = xs[i].npos > npos ? xs[i].npos : npos;
+    const int ph = xs[i].o_phist ? ((V & 7) ? V : V >> 3) : 0;
+    const int m = xs[i].nhist > ph ? (xs[i].nhist > xs[i].npctx ? xs[i].nhist : xs[i].npctx) : (ph > xs[i].npctx ? ph : xs[i].npctx);
+    items = m > items ? m : items;
+  }
+  p.kcache = (unsigned char*)L->kcache; p.vcache = (unsigned char*)L->vcache;
+  p.piece_shift = L->cfg.kv_dtype ? 4 : 3;
+  p.layer_bytes = L->kv_layer_elems * (L->cfg.kv_dtype ? 4 : 2);
+  p.n_kv = L->cfg.num_kv_heads; p.max_pos = L->cfg.max_positions;
+  p.km = kv_map(L);
+  p.rows = L->rows; p.B = L->B;
+  p.hist = L->hist; p.lp = L->lp; p.phist = L->phist; p.pctx = L->pctx; p.count = L->count; p.finished = L->finished;
+  p.V = V;
+  if (npos > 0) {
+    const unsigned per = 256 * kParkPieces;
+    const dim3 grid((unsigned)((((size_t)npos << p.piece_shift) + per - 1) / per), (unsigned)n, (unsigned)(L->cfg.num_layers * 2 * L->cfg.num_kv_heads));
+    if (save) hipLaunchKernelGGL(k_slot_kv<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_slot_kv<false>, grid, dim3(256), 0, st, p);
+    SMI_LAUNCH_CHECK();
+  }
+  const int bx = (items + 255) / 256;
+  const dim3 cgrid((unsigned)(bx < 64 ? bx : 64), (unsigned)n);
+  if (save) hipLaunchKernelGGL(k_slot_cols<true>, cgrid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL(k_slot_cols<false>, cgrid, dim3(256), 0, st, p);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+static int park_state(const smi_llm* L, const char* who) {
+  if (!L->started || !L->session) { smi_set_error("%s outside a session (smi_llm_session_begin first)", who); return SMI_ESTATE; }
+  return SMI_OK;
+}
+
+int smi_llm_slot_blob_bytes(smi_llm* L, int slot, size_t* bytes) {
+  SMI_REQUIRE(L && bytes, "smi_llm_slot_blob_bytes: null argument");
+  { const int rcs = park_state(L, "smi_llm_slot_blob_bytes"); if (rcs) return rcs; }
+  SMI_REQUIRE(slot >= 0 && slot < kMaxRows && L->slot_busy[slot], "smi_llm_slot_blob_bytes: slot %d is not busy", slot);
+  *bytes = blob_layout(L, L->slot_len[slot], L->slot_plen[slot], L->slot_feat[slot]).total;
+  return SMI_OK;
+}
+
+int smi_llm_slots_save(smi_llm* L, const int32_t* slots, int n, void* const* blobs_dev, const size_t* caps, size_t* used, void* stream) {
+  SMI_REQUIRE(L && slots && blobs_dev && caps && used && n >= 1 && n <= kMaxRows, "smi_llm_slots_save: bad argument");
+  { const int rcs = park_state(L, "smi_llm_slots_save"); if (rcs) return rcs; }
+  SMI_REQUIRE((int)L->live_order.size() == L->B, "smi_llm_slots_save: live row list out of step");
+  unsigned long long seen = 0;
+  BlobLay lay[kMaxRows];
+  size_t stage = 0;
+  for (int i = 0; i < n; ++i) {   // every check before the first byte is written
+    const int sl = slots[i];
+    SMI_REQUIRE(sl >= 0 && sl < kMaxRows && L->slot_busy[sl] && !((seen >> sl) & 1ull), "smi_llm_slots_save: slot %d is not busy (or listed twice)", sl);
+    seen |= 1ull << sl;
+    lay[i] = blob_layout(L, L->slot_len[sl], L->slot_plen[sl], L->slot_feat[sl]);
+    SMI_REQUIRE(blobs_dev[i] && ((uintptr_t)blobs_dev[i] & 15) == 0, "smi_llm_slots_save: blobs_dev[%d] must be a 16-byte aligned device address", i);
+    SMI_REQUIRE(caps[i] >= lay[i].total, "smi_llm_slots_save: caps[%d]=%zu, the sequence in slot %d needs %zu bytes", i, caps[i], sl, lay[i].total);
+    stage += lay[i].hdr;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  L->host_blob.assign(stage, 0);
+  SlotXfer xs[kMaxRows];
+  size_t at = 0;
+  for (int i = 0; i < n; ++i) {
+    const int sl = slots[i];
+    unsigned char* hb = L->host_blob.data() + at;
+    BlobHdr h;
+    memset(&h, 0, sizeof(h));
+    memcpy(h.magic, "SMISLOT1", 8);
+    h.hdr_bytes = (uint32_t)lay[i].hdr; h.feat = L->slot_feat[sl]; h.total_bytes = lay[i].total;
+    h.cfg_stamp = fnv1a(&L->cfg, sizeof(L->cfg)); h.handle_id = L->handle_id; h.session_gen = L->session_gen;
+    h.len = L->slot_len[sl]; h.plen = L->slot_plen[sl]; h.nhist = lay[i].nhist; h.seqid = L->hctl.seqid[sl];
+    h.samp = L->hctl.samp[sl]; h.pen = L->hctl.pen[sl]; h.lp = L->hctl.lp[sl]; h.ngram = L->hctl.ngram[sl]; h.ngplen = L->hctl.ngplen[sl];
+    h.allow = L->hctl.allow[sl];
+    memcpy(hb, &h, sizeof(h));
+    if (lay[i].hdr > sizeof(BlobHdr)) memcpy(hb + sizeof(BlobHdr), &L->hseq[(size_t)sl], sizeof(SeqRec));
+    h.check = blob_check(hb, lay[i].hdr);
+    memcpy(hb, &h, sizeof(h));
+    // (pageable source: staged before the call returns; host_blob is rebuilt only by the next save)
+    SMI_HIP(hipMemcpyAsync(blobs_dev[i], hb, lay[i].hdr, hipMemcpyHostToDevice, st));
+    xs[i] = blob_xfer(lay[i], blobs_dev[i], sl);
+    used[i] = lay[i].total;
+    at += lay[i].hdr;
+  }
+  return park_launch(L, true, xs, n, st);
+}
+
+int smi_llm_slots_restore(smi_llm* L, const void* const* blobs_dev, const size_t* bytes, int n, int32_t* slots_out, void* stream) {
+  SMI_REQUIRE(L && blobs_dev && bytes && slots_out && n >= 1 && n <= kMaxRows, "smi_llm_slots_restore: bad argument");
+  { const int rcs = park_state(L, "smi_llm_slots_restore"); if (rcs) return rcs; }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t hmax = sizeof(BlobHdr) + sizeof(SeqRec);
+  for (int i = 0; i < n; ++i) {
+    SMI_REQUIRE(blobs_dev[i] && ((uintptr_t)blobs_dev[i] & 15) == 0, "smi_llm_slots_restore: blobs_dev[%d] must be a 16-byte aligned device address", i);
+    SMI_REQUIRE(bytes[i] >= sizeof(BlobHdr), "smi_llm_slots_restore: blob %d is truncated (%zu bytes)", i, bytes[i]);
+  }
+  std::vector<unsigned char> hh((size_t)n * hmax, 0);
+  for (int i = 0; i < n; ++i)
+    SMI_HIP(hipMemcpyAsync(hh.data() + (size_t)i * hmax, blobs_dev[i], bytes[i] < hmax ? bytes[i] : hmax, hipMemcpyDeviceToHost, st));
+  SMI_HIP(hipStreamSynchronize(st));
+  // every blob is checked before anything of the handle is touched
+  BlobLay lay[kMaxRows];
+  const uint64_t stamp = fnv1a(&L->cfg, sizeof(L->cfg));
+  for (int i = 0; i < n; ++i) {
+    const unsigned char* hb = hh.data() + (size_t)i * hmax;
+    BlobHdr h;
+    memcpy(&h, hb, sizeof(h));
+    SMI_REQUIRE(memcmp(h.magic, "SMISLOT1", 8) == 0, "smi_llm_slots_restore: blob %d is not a sequence snapshot", i);
+    SMI_REQUIRE((h.hdr_bytes == sizeof(BlobHdr) || h.hdr_bytes == hmax) && h.hdr_bytes <= bytes[i] && h.feat < (1u << kFeatBits) &&
+                (h.hdr_bytes == hmax) == ((h.feat & (F_BIAS | F_STOP)) != 0), "smi_llm_slots_restore: blob %d has a corrupt header", i);
+    SMI_REQUIRE(h.check == blob_check(hb, h.hdr_bytes), "smi_llm_slots_restore: blob %d has a corrupt header (checksum)", i);
+    if (h.cfg_stamp != stamp) { smi_set_error("smi_llm_slots_restore: blob %d was saved under another configuration", i); return SMI_ESTATE; }
+    if (h.handle_id != L->handle_id || h.session_gen != L->session_gen) {
+      smi_set_error("smi_llm_slots_restore: blob %d is of another handle or an earlier session of this one", i);
+      return SMI_ESTATE;
+    }
+    SMI_REQUIRE(h.plen >= 1 && h.len > h.plen && h.len <= L->cfg.max_positions, "smi_llm_slots_restore: blob %d has corrupt lengths", i);
+    lay[i] = blob_layout(L, h.len, h.plen, h.feat);
+    SMI_REQUIRE(lay[i].total == h.total_bytes && h.nhist == lay[i].nhist, "smi_llm_slots_restore: blob %d has a corrupt header (sizes)", i);
+    SMI_REQUIRE(bytes[i] == lay[i].total, "smi_llm_slots_restore: blob %d is %zu bytes, its header says %zu", i, bytes[i], lay[i].total);
+    const SeqRec* q = h.hdr_bytes == hmax ? (const SeqRec*)(hb + sizeof(BlobHdr)) : nullptr;
+    SMI_REQUIRE(recs_feat(h, q) == h.feat && h.ngplen == ((h.feat & F_NGRAM) ? h.plen : 0) && (!q || q->plen == h.plen),
+                "smi_llm_slots_restore: blob %d: records and feature byte disagree", i);
+    SMI_REQUIRE(h.dev.row.pos == h.len - 1 && h.dev.row.flags == h.len - h.plen && h.dev.row.token >= 0 && h.dev.row.token < L->cfg.vocab_size &&
+                h.dev.count >= 0 && h.dev.count <= h.dev.row.flags && (h.dev.finished == 0 || h.dev.finished == 1),
+                "smi_llm_slots_restore: blob %d has a corrupt row state", i);
+  }
+  int32_t slots[kMaxRows];   // lowest free first, as an admission takes them
+  { const int k = slots_take_free(L, n, slots);
+    if (k < n) { smi_set_error("smi_llm_slots_restore: %d snapshots, %d free KV slots", n, k); return SMI_ESTATE; } }
+  // what the headers say, as the shared admission steps take it: the records (the sequence keeps its admission number;
+  // admit_seq does not move), the bias / stop records, the rows, the lengths
+  SlotRecs old[kMaxRows], recs[kMaxRows];
+  std::vector<SeqRec> seqs((size_t)n);
+  RowDesc rows[kMaxRows];
+  int32_t lens[kMaxRows], plens[kMaxRows];
+  SlotXfer xs[kMaxRows];
+  for (int i = 0; i < n; ++i) {
+    const unsigned char* hb = hh.data() + (size_t)i * hmax;
+    BlobHdr h;
+    memcpy(&h, hb, sizeof(h));
+    recs[i] = SlotRecs{h.seqid, h.samp, h.pen, h.lp, h.allow, h.ngram, h.ngplen, (uint8_t)h.feat};
+    memset(&seqs[(size_t)i], 0, sizeof(SeqRec));
+    if (h.hdr_bytes == hmax) memcpy(&seqs[(size_t)i], hb + sizeof(BlobHdr), sizeof(SeqRec));
+    rows[i] = h.dev.row;
+    rows[i].slot = slots[i];
+    lens[i] = h.len; plens[i] = h.plen;
+    xs[i] = blob_xfer(lay[i], const_cast<void*>(blobs_dev[i]), slots[i]);
+  }
+  int rc;
+  std::vector<RowDesc> live;
+  if ((rc = session_live_rows(L, live, st))) return rc;
+  // pages of its own, whatever the original shared; all or nothing: a short pool restores nobody (the slots hold no page yet)
+  if (L->paged && (rc = pages_ensure(L, slots, lens, n, st))) return rc;
+  if ((rc = recs_install(L, "smi_llm_slots_restore", slots, n, recs, seqs.data(), old, st)) || (rc = park_launch(L, false, xs, n, st))) {
+    recs_withdraw(L, slots, n, old);
+    return rc;
+  }
+  return slots_enter(L, live, slots, n, rows, plens, lens, slots_out, st);
 }
 
 // Tokens of several slots in one device round trip: out_host [n][cap], n_out[n], finished[n].

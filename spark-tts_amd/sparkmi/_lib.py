@@ -173,6 +173,9 @@ SYMBOLS = {
     "smi_llm_admit_ngram": (_I, [_VP, _P(C.c_int64), _P(C.c_int32), _I, _I, _P(C.c_int32), _P(SampleParams),
                                  _P(PenaltyParams), _P(C.c_int32), _P(AllowParams), _P(SeqParams), _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_poll": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int64), _I, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _VP]),
+    "smi_llm_slot_blob_bytes": (_I, [_VP, _I, _P(_SZ)]),
+    "smi_llm_slots_save": (_I, [_VP, _P(C.c_int32), _I, _P(_VP), _P(_SZ), _P(_SZ), _VP]),
+    "smi_llm_slots_restore": (_I, [_VP, _P(_VP), _P(_SZ), _I, _P(C.c_int32), _VP]),
     "smi_llm_status": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _VP]),
     "smi_llm_forward_logits": (_I, [_VP, _P(C.c_int64), _I, _VP, _VP]),
     "smi_llm_steps": (_I, [_VP]),

@@ -613,6 +613,50 @@ class SparkLLM:
         self._lib.check(self._lib.smi_llm_retire_many(self._h, arr.ctypes.data_as(C.POINTER(C.c_int32)), len(arr), self._stream()),
                    "smi_llm_retire_many")
 
+    def slot_blob_bytes(self, slot: int) -> int:
+        """Bytes of the snapshot ``save_slots`` would write for the sequence now in ``slot`` (host arithmetic only)."""
+        nb = C.c_size_t(0)
+        self._lib.check(self._lib.smi_llm_slot_blob_bytes(self._h, int(slot), C.byref(nb)), "smi_llm_slot_blob_bytes")
+        return int(nb.value)
+
+    def save_slots(self, slots: Sequence[int]) -> List[torch.Tensor]:
+        """One snapshot per listed busy slot: a ``torch.uint8`` device tensor of ``slot_blob_bytes`` bytes holding the sequence's
+        complete state (``smi_llm_slots_save``; the layout is in include/sparkmi.h).  The slots stay as they were.  The caller
+        owns the tensors; ``restore_slots`` puts one back, any time later in the same session."""
+        arr = np.asarray(list(slots), dtype=np.int32)
+        n = len(arr)
+        # (sizes first: an unknown slot raises here, before anything is allocated)
+        blobs = [torch.empty(self.slot_blob_bytes(int(s)), dtype=torch.uint8, device=self.device) for s in arr]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.data_ptr() for b in blobs])
+        caps = (C.c_size_t * max(n, 1))(*[b.numel() for b in blobs])
+        used = (C.c_size_t * max(n, 1))()
+        self._lib.check(self._lib.smi_llm_slots_save(self._h, arr.ctypes.data_as(C.POINTER(C.c_int32)), n, ptrs, caps, used,
+                                                     self._stream()), "smi_llm_slots_save")
+        assert [int(u) for u in used[:n]] == [b.numel() for b in blobs]
+        return blobs
+
+    def restore_slots(self, blobs: Sequence[torch.Tensor]) -> List[int]:
+        """Each snapshot goes into a free KV slot (the lowest free ones, in order; not necessarily where it came from) and its
+        sequence continues exactly where it was saved; returns the slots (``smi_llm_slots_restore``)."""
+        blobs = list(blobs)
+        n = len(blobs)
+        for b in blobs:
+            if not (isinstance(b, torch.Tensor) and b.dtype == torch.uint8 and b.is_cuda and b.is_contiguous() and b.dim() == 1):
+                raise ValueError("restore_slots: a blob is a contiguous 1-D torch.uint8 device tensor")
+        ptrs = (C.c_void_p * max(n, 1))(*[b.data_ptr() for b in blobs])
+        nbytes = (C.c_size_t * max(n, 1))(*[b.numel() for b in blobs])
+        slots = np.zeros(max(n, 1), dtype=np.int32)
+        self._lib.check(self._lib.smi_llm_slots_restore(self._h, ptrs, nbytes, n, slots.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        self._stream()), "smi_llm_slots_restore")
+        return slots[:n].tolist()
+
+    def park(self, slots: Sequence[int]) -> List[torch.Tensor]:
+        """``save_slots`` followed by ``retire_many``: the sequences leave their slots (and pages) and live on in the returned
+        snapshots until ``restore_slots``."""
+        blobs = self.save_slots(slots)
+        self.retire_many(slots)
+        return blobs
+
     def slots_tokens(self, slots: Sequence[int], cap: int):
         """[(tokens, finished)] of several slots (live or retired and not yet reused) in one device round trip."""
         arr = np.asarray(list(slots), dtype=np.int32)

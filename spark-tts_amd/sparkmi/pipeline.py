@@ -11,6 +11,7 @@ batching) and ``serve_stream`` (both at once: chunked audio for every live reque
 """
 from __future__ import annotations
 
+import math
 from pathlib import Path
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple, Union
 
@@ -24,7 +25,7 @@ from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, NGRAM_KEY, PENALTY_KEYS, SA
                   eos_ids_from_generation_config, ngram_size, num_returns, penalty_neutral, seq_entries)
 from .pipeline_text import (GENDER_MAP, LEVELS_MAP, TASK_TOKEN_MAP, build_clone_prompt,
                             build_control_prompt, parse_global, parse_semantic)
-from .streaming import ChunkScheduler, StreamMux
+from .streaming import ChunkScheduler, Pacer, StreamMux
 from .weights import load_llm_state
 
 
@@ -35,6 +36,28 @@ SPEECH_ONLY_KEY = "speech_tokens_only"
 # request key: a bias on the end token -- sugar for one length-1 ``sequence_bias`` entry per eos id of the session (-inf: the
 # request runs to its token budget; a large positive value: it ends at the first token min_new_tokens lets it)
 EOS_BIAS_KEY = "eos_bias"
+
+
+def _stream_pacing(max_batch: int, max_open=None, max_ahead=None, resume_ahead=None):
+    """``serve_stream``'s pacing keywords, checked before anything reaches the device: (max_open, max_ahead, resume_ahead) with
+    the defaults filled in.  ``max_open``: an int >= 1 (None: ``max_batch``); ``max_ahead`` > 0 seconds (None: no parking);
+    0 <= ``resume_ahead`` <= ``max_ahead`` (None: ``max_ahead / 2``).  ``max_ahead`` without ``max_open > max_batch`` is
+    accepted and inert."""
+    if max_open is None:
+        max_open = int(max_batch)
+    elif isinstance(max_open, bool) or not isinstance(max_open, (int, np.integer)) or max_open < 1:
+        raise ValueError(f"max_open must be an int >= 1, not {max_open!r}")
+    for name, v in (("max_ahead", max_ahead), ("resume_ahead", resume_ahead)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v)):
+            raise ValueError(f"{name} must be a finite number of seconds, not {v!r}")
+    if max_ahead is not None and not max_ahead > 0:
+        raise ValueError(f"max_ahead must be > 0, not {max_ahead!r}")
+    if resume_ahead is not None:
+        if resume_ahead < 0 or (max_ahead is not None and resume_ahead > max_ahead):
+            raise ValueError(f"resume_ahead must lie in [0, max_ahead], not {resume_ahead!r}")
+    elif max_ahead is not None:
+        resume_ahead = max_ahead / 2
+    return int(max_open), None if max_ahead is None else float(max_ahead), None if resume_ahead is None else float(resume_ahead)
 
 
 def _request_seq(r: dict, eos: Sequence[int], vocab_size: int, what: str = "request") -> dict:
@@ -514,7 +537,9 @@ class SparkTTS:
     def serve_stream(self, requests, temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *, do_sample: bool = True,
                      max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8,
                      audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
-                     audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1):
+                     audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
+                     max_open: Optional[int] = None, max_ahead: Optional[float] = None, resume_ahead: Optional[float] = None,
+                     clock=None, pacer: Optional[Pacer] = None):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -527,7 +552,21 @@ class SparkTTS:
         (``SparkLLM.poll``).  The vocoder call runs on a HIP stream of its own -- its inputs come from the host, so it waits
         for nothing of the LLM, and the LLM's stream never waits for it -- and the next ``decode_stride`` steps are enqueued
         before the host waits for the waveforms.  ``num_return_sequences`` and ``return_log_probs`` are refused (ValueError,
-        before anything reaches the device)."""
+        before anything reaches the device).
+
+        Parking (``streaming.Pacer``): with ``max_open`` > ``max_batch`` and ``max_ahead`` (seconds) given, up to ``max_open``
+        requests are open at once.  After a poll, a live request whose lead -- audio yielded minus the ``clock`` time since its
+        first chunk -- exceeds ``max_ahead`` gives its row to a waiting one: its sequence is parked (one ``SparkLLM.park`` per
+        poll) while its chunks keep coming out; it is resumed (``restore_slots``, one call per poll, before the admission of
+        new requests) once its lead has fallen below ``resume_ahead`` (default ``max_ahead / 2``), or as soon as a row would
+        otherwise idle.  ``clock``: a callable returning seconds (default ``time.monotonic``).  The defaults (``max_open``
+        None) are the loop without any of this: no save, no restore, no extra kernel or round trip; ``max_ahead`` without
+        ``max_open > max_batch`` is accepted and inert.  Guarantee: a request's chunks -- samples, boundaries and ``last``
+        flags -- are bit for bit those of the same call without parking, which are those of the request alone: a parked
+        sequence comes back with every bit of its state, whatever the schedule did to it, greedy and sampled with any seed
+        alike.  ``pacer``: a ``Pacer`` of the caller's, built for this ``max_batch``, in place of the four keywords (ValueError if
+        both are given); its ``parks`` / ``resumes`` then tell the caller what the schedule did.  Nothing of a call is kept on
+        ``self``."""
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
@@ -545,6 +584,16 @@ class SparkTTS:
             raise ValueError("decode_stride must be >= 1")
         voc = self.audio_tokenizer.model
         ntok, hop = voc.cfg.spk_token_num, voc.hop
+        if pacer is None:
+            max_open, max_ahead, resume_ahead = _stream_pacing(self._max_batch, max_open, max_ahead, resume_ahead)
+            pacer = Pacer(self._max_batch, max_open, max_ahead, resume_ahead, self.sample_rate // hop, clock)
+        else:
+            if any(v is not None for v in (max_open, max_ahead, resume_ahead, clock)):
+                raise ValueError("pacer= takes the place of max_open, max_ahead, resume_ahead and clock: give one or the other")
+            if not isinstance(pacer, Pacer) or pacer.max_batch != self._max_batch:
+                raise ValueError(f"pacer must be a streaming.Pacer for max_batch={self._max_batch}")
+            max_open = pacer.max_open
+        overlap = math.ceil(audio_chunk_overlap_duration * (self.sample_rate // hop))   # frames a chunk shares with its predecessor
         mux = StreamMux(ntok, self._map, self._parse, frame_rate=self.sample_rate // hop,
                         audio_chunk_duration=audio_chunk_duration, max_audio_chunk_duration=max_audio_chunk_duration,
                         audio_chunk_size_scale_factor=audio_chunk_size_scale_factor,
@@ -587,7 +636,11 @@ class SparkTTS:
                 with torch.cuda.stream(vs):
                     wav = wav.squeeze(1).cpu().numpy()
             b = 0
-            for key, _, sem, last in chunks:
+            for key, index, sem, last in chunks:
+                if pacer.active:
+                    pacer.yielded(key, max(0, len(sem) - (overlap if index else 0)))
+                    if last:          # nothing more is yielded for it: the pacer forgets the request here, not at its retirement
+                        pacer.close(key)
                 if sem:
                     yield key, wav[b, : len(sem) * hop].copy(), last
                     b += 1
@@ -598,13 +651,25 @@ class SparkTTS:
         it = llm_requests()
         pending = next(it, None)
         live: Dict[int, list] = {}    # slot -> [index, budget, tokens read so far]
+        parked: Dict[int, tuple] = {}  # index -> (snapshot, its live entry): open requests that hold no row (Pacer)
         started, job = False, None
         try:
-            while pending is not None or live:
+            while pending is not None or live or parked:
+                # free rows go to the parked requests that are running out of lead, then to new requests, then to any parked one
+                back = pacer.to_resume(list(parked), self._max_batch - len(live), True) if parked else []
                 batch = []
-                while pending is not None and len(live) + len(batch) < self._max_batch:
+                while (pending is not None and len(live) + len(back) + len(batch) < self._max_batch
+                       and len(live) + len(parked) + len(batch) < max_open):
                     batch.append(pending)
                     pending = next(it, None)
+                if parked:
+                    rest = [k for k in parked if k not in back]
+                    back += pacer.to_resume(rest, self._max_batch - len(live) - len(back) - len(batch), False)
+                if back:              # ONE restore, ahead of the admission; a snapshot is dropped once its request is back
+                    entries = [parked.pop(k) for k in back]
+                    for slot, (_, entry) in zip(self.model.restore_slots([e[0] for e in entries]), entries):
+                        live[slot] = entry
+                    del entries
                 if batch:             # all free slots are filled by ONE admission, as SparkLLM.serve does
                     if not started:
                         self.model.session_begin(self._eos)
@@ -635,8 +700,16 @@ class SparkTTS:
                     self.model.retire_many(leave)
                     for slot in leave:
                         mux.close(live.pop(slot)[0])
+                if pacer.active and live:   # the requests far enough ahead of their listeners make room for the waiting ones
+                    by_key = {live[s][0]: s for s in live}
+                    out = [by_key[k] for k in pacer.to_park(list(by_key), list(parked), pending is not None)]
+                    if out:           # ONE save + retire_many; their mux entries stay open, their ready chunks are vocoded as usual
+                        for slot, blob in zip(out, self.model.park(out)):
+                            entry = live.pop(slot)
+                            parked[entry[0]] = (blob, entry)
             if job is not None:
                 yield from collect(job)
                 job = None
         finally:
+            parked.clear()     # the snapshots of requests that never resumed go with the generator
             vs.synchronize()   # an abandoned stream leaves no vocoder work behind (the handle's scratch is shared with detokenize)

@@ -212,3 +212,94 @@ class StreamMux:
             raise ValueError(f"request {key}: {len(st.glob)} global tokens, the speaker encoder needs {self.ntok}")
         if st.n_sem == 0:
             raise ValueError(f"request {key}: the model generated no semantic tokens")
+
+
+class Pacer:
+    """Which open requests of a ``serve_stream`` loop run, host side only (no GPU, no torch).  The engine produces a request's
+    audio many times faster than a listener hears it, so a request that is far enough ahead of its listener can give its decode
+    row to one that is waiting: it is *parked* (its sequence leaves its KV slot as a snapshot, ``SparkLLM.park``) and *resumed*
+    later (``SparkLLM.restore_slots``), and more requests can be open than there are rows.
+
+    ``max_batch``: decode rows.  ``max_open``: requests that may be open (admitted and not finished) at once; None or a value
+    <= ``max_batch``: the pacer is inert.  ``max_ahead`` (seconds; None: inert): a request may be parked once its lead exceeds
+    it.  ``resume_ahead`` (seconds, default ``max_ahead / 2``): a parked request whose lead has fallen below it is resumed before
+    anything else gets a row.  ``clock``: a callable returning seconds (default ``time.monotonic``).
+
+    A request's *lead* is the audio yielded for it so far (``yielded``), in seconds, minus the clock time since its first chunk
+    was yielded; before its first chunk it is minus infinity, so a request that has not spoken yet is never parked.
+
+    Every decision is a pure function of the calls made and the clock; ties break by request key (the request index).
+      ``to_park(live, parked, pending)``: the live, unfinished requests to park now.  A request qualifies only if its lead
+        exceeds ``max_ahead`` and somebody is waiting -- a pending request while fewer than ``max_open`` are open, or a parked
+        request.  Of those that qualify, only as many are parked as there are waiters that the free rows cannot serve (a row
+        is never emptied to be handed straight back), largest lead first.
+      ``to_resume(parked, free_rows, urgent)``: the parked requests that get ``free_rows`` rows, smallest lead first;
+        ``urgent=True``: only those whose lead has fallen below ``resume_ahead``.  Rows go to (1) the urgent ones, (2) pending
+        requests, (3) any parked request -- the caller asks with ``urgent=True``, admits, then asks with ``urgent=False``, so
+        no row idles while a parked request exists.
+    ``parks`` / ``resumes`` count the requests ``to_park`` / ``to_resume`` have named."""
+
+    def __init__(self, max_batch: int, max_open: Optional[int] = None, max_ahead: Optional[float] = None,
+                 resume_ahead: Optional[float] = None, frame_rate: int = 50, clock: Optional[Callable[[], float]] = None):
+        import time
+        self.max_batch = int(max_batch)
+        self.max_open = self.max_batch if max_open is None else int(max_open)
+        self.max_ahead = None if max_ahead is None else float(max_ahead)
+        if self.max_batch < 1 or self.max_open < 1:
+            raise ValueError("Pacer: max_batch and max_open must be >= 1")
+        if self.max_ahead is not None and not self.max_ahead > 0:
+            raise ValueError("Pacer: max_ahead must be > 0")
+        if resume_ahead is None:
+            resume_ahead = None if self.max_ahead is None else self.max_ahead / 2
+        elif self.max_ahead is not None and not 0 <= float(resume_ahead) <= self.max_ahead:
+            raise ValueError("Pacer: 0 <= resume_ahead <= max_ahead")
+        self.resume_ahead = None if resume_ahead is None else float(resume_ahead)
+        self.frame_rate = float(frame_rate)
+        self.clock = clock if clock is not None else time.monotonic
+        self.active = self.max_ahead is not None and self.max_open > self.max_batch
+        self._first: Dict[Hashable, float] = {}    # key -> clock at its first chunk
+        self._frames: Dict[Hashable, int] = {}     # key -> frames yielded
+        self.parks = 0
+        self.resumes = 0
+
+    def yielded(self, key: Hashable, frames: int) -> None:
+        """A chunk of ``frames`` new audio frames of request ``key`` has just been handed to its listener."""
+        if key not in self._first:
+            self._first[key] = self.clock()
+            self._frames[key] = 0
+        self._frames[key] += int(frames)
+
+    def close(self, key: Hashable) -> None:
+        self._first.pop(key, None)
+        self._frames.pop(key, None)
+
+    def lead(self, key: Hashable, now: Optional[float] = None) -> float:
+        if key not in self._first:
+            return -math.inf
+        now = self.clock() if now is None else now
+        return self._frames[key] / self.frame_rate - (now - self._first[key])
+
+    def to_park(self, live: Sequence[Hashable], parked: Sequence[Hashable], pending: bool) -> List[Hashable]:
+        if not self.active:
+            return []
+        n_open = len(live) + len(parked)
+        waiters = len(parked) + (1 if pending and n_open < self.max_open else 0)
+        want = waiters - (self.max_batch - len(live))
+        if want <= 0:
+            return []
+        now = self.clock()
+        cands = sorted((-self.lead(k, now), k) for k in live if self.lead(k, now) > self.max_ahead)
+        out = [k for _, k in cands[:want]]
+        self.parks += len(out)
+        return out
+
+    def to_resume(self, parked: Sequence[Hashable], free_rows: int, urgent: bool) -> List[Hashable]:
+        if free_rows <= 0 or not parked:
+            return []
+        now = self.clock()
+        cands = sorted((self.lead(k, now), k) for k in parked)
+        if urgent:
+            cands = [c for c in cands if c[0] < self.resume_ahead]
+        out = [k for _, k in cands[:free_rows]]
+        self.resumes += len(out)
+        return out
