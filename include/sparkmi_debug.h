@@ -1,5 +1,5 @@
 /*
- * sparkmi_debug.h -- diagnostics and test entry points (the LLM half; the conv kernel forms of the vocoder / encoder).  NOT part of the product ABI: these symbols exist
+ * sparkmi_debug.h -- diagnostics and test entry points (the LLM half; the conv kernel forms of the vocoder / encoder; the prompt encoder's launch list).  NOT part of the product ABI: these symbols exist
  * only in libsparkmi_diag.so (spark-tts_amd/csrc built with -DSMI_DIAG), which also exports everything sparkmi.h declares and
  * -- unlike libsparkmi.so -- honours the SPARKMI_* environment switches listed in DESIGN.md 6.1.  Loaded by tools/, by
  * bench.py's per-kernel probes and by the tests that look inside a step (tests/test_llm_ops_gpu.py, test_engine_gpu.py).
@@ -212,6 +212,28 @@ typedef struct smi_block_launch_info {
   smi_conv_form form;
 } smi_block_launch_info;
 int smi_voc_block_plan(const smi_voc_block_cfg* cfg, int B, int L, smi_block_launch_info* out, int cap, int32_t* n);
+
+/* ------------------------------------------------------------------------------------------
+ * Prompt encoder (csrc/smi_enc.hip): its OWN launch list, one launch at a time, on caller-written buffers -- the grid, block,
+ * dynamic LDS size and arguments are those of a real encode of the same (n_samples, n_ref), because the list is the one
+ * smi_enc_forward's graph path builds (tests/test_enc_ops_gpu.py).
+ *   smi_enc_debug_build: builds the launch list on the handle-owned in_wav / in_ref / out_sem / out_glob buffers, uploads the
+ *     length slots and runs nothing.  smi_enc_forward's argument checks apply (SMI_EINVAL before any GPU call).  The captured
+ *     graphs of the handle are left alone.  *n_frames = wav2vec2 frames, *n_launches = launches of the list.
+ *   smi_enc_debug_launch: launch `index` of the list: name (at most cap bytes) and info[8] = {kind (0 conv, 1 k_dwln,
+ *     9 one of the encoder's small kernels), grid x, y, z, threads per block, dynamic LDS bytes, k_dwln's instantiated channels
+ *     per thread (kind 1, else 0), 0}.
+ *   smi_enc_debug_io: synchronous copy between host_ptr and `floats` 4-byte words at offset_floats of a named handle buffer
+ *     (write = 1: host -> buffer).  Names: wavn cf0 cf1 h x wide att acc feat e0 e1 e2 ew frames dft mag mel ec_a ec_b ec_c
+ *     ec_cat ec_lat ec_vec pctx pq pkv po pff pg pout fsqb in_wav in_ref out_sem (int64 ids: two words each) out_glob (int32).
+ *     A range outside the buffer is SMI_EINVAL.
+ *   smi_enc_debug_run: launches first .. last of the list, ONCE each and in order, then synchronises; the first error.
+ *     (smi_enc_time_launch runs a launch iters + 1 times: wrong for the in-place launches.)
+ * ---------------------------------------------------------------------------------------- */
+int smi_enc_debug_build(smi_enc* h, int n_samples, int n_ref, int* n_frames, int* n_launches, void* stream);
+int smi_enc_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* info);
+int smi_enc_debug_io(smi_enc* h, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats);
+int smi_enc_debug_run(smi_enc* h, int first, int last, void* stream);
 
 #ifdef __cplusplus
 }

@@ -313,6 +313,9 @@ struct EncLayout {
   size_t total;
 };
 
+constexpr int kMaxKeys = 2040;        // k_mha: 8 score rows of Tk floats + the Q and V tiles within the 96 KB dynamic LDS window
+constexpr int kMaxSpkTokens = 1024;   // k_geglu's block
+
 bool enc_cfg_ok(const smi_enc_cfg* c) {
   if (!c) return false;
   if (c->w2v_nconv < 2 || c->w2v_nconv > 8 || c->w2v_conv_dim < 32 || c->w2v_conv_dim % 32 || c->w2v_conv_dim > 1024) return false;
@@ -325,7 +328,8 @@ bool enc_cfg_ok(const smi_enc_cfg* c) {
   if (c->enc_in != c->w2v_hidden || c->enc_dim < 1 || c->enc_dim > 1024 || c->enc_layers < 1 || c->enc_num_down < 0) return false;
   if (c->codebook_dim < 1 || c->codebook_dim > 16 || c->codebook_size < 1) return false;
   if (c->n_fft < 16 || c->n_fft % 2 || c->win_length > c->n_fft || c->hop_length < 1 || c->num_mels < 1) return false;
-  if (c->ecapa_channels % 64 || c->ecapa_channels < 64 || c->spk_latent < 1 || c->spk_tokens < 1) return false;
+  // k_geglu runs one block of 64 * ceil(spk_tokens / 64) threads per channel: at most 1024 threads
+  if (c->ecapa_channels % 64 || c->ecapa_channels < 64 || c->spk_latent < 1 || c->spk_tokens < 1 || c->spk_tokens > kMaxSpkTokens) return false;
   if (c->fsq_dims < 1 || c->fsq_dims > 8 || c->perc_depth < 1 || c->perc_heads < 1 || c->perc_ff_inner < 1) return false;
   if (c->max_samples < 400 || c->max_ref_samples < c->n_fft) return false;
   return true;
@@ -563,6 +567,13 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
     return SMI_EINVAL;
   }
   const smi_enc_cfg& c = h->cfg;
+  // the perceiver attends over its latents and one context column per mel frame: the longest reference clip must fit k_mha
+  if (c.spk_tokens + c.max_ref_samples / c.hop_length + 1 > kMaxKeys) {
+    smi_set_error("smi_enc_create: spk_tokens=%d + %d mel frames of max_ref_samples=%d exceed the attention kernel's %d-key score buffer",
+                  c.spk_tokens, c.max_ref_samples / c.hop_length + 1, c.max_ref_samples, kMaxKeys);
+    delete h;
+    return SMI_EINVAL;
+  }
   // frame counts at the longest input
   int n = c.max_samples;
   std::vector<int> Ts;
@@ -619,8 +630,16 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
     h->use_graph = !(e && e[0] == '0');
   }
   // more than the default dynamic LDS window for the attention / positional-conv kernels (per device, before any capture)
-  (void)hipFuncSetAttribute((const void*)k_mha, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  (void)hipFuncSetAttribute((const void*)k_posconv, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  {
+    const hipError_t e1 = hipFuncSetAttribute((const void*)k_mha, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    const hipError_t e2 = e1 == hipSuccess ? hipFuncSetAttribute((const void*)k_posconv, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) : e1;
+    if (e2 != hipSuccess) {
+      smi_set_error("smi_enc_create: could not raise the dynamic LDS window of %s to 96 KB: %s", e1 != hipSuccess ? "k_mha" : "k_posconv",
+                    hipGetErrorString(e2));
+      smi_enc_destroy(h);
+      return SMI_EHIP;
+    }
+  }
   bool ok = true;
   for (auto& kv : h->buf_floats) {
     float* p = nullptr;
@@ -696,11 +715,16 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
   }
   const int T = Ts.back();
   SMI_REQUIRE(T >= 2, "smi_enc_forward: %d samples give %d frames", n_samples, T);
-  SMI_REQUIRE(T <= 2040, "smi_enc_forward: %d frames exceed the attention kernel's 2040-key score buffer", T);
+  SMI_REQUIRE(T <= kMaxKeys, "smi_enc_forward: %d frames exceed the attention kernel's %d-key score buffer", T, kMaxKeys);
   const int Tm = n_ref / c.hop_length + 1;
+  SMI_REQUIRE(c.spk_tokens + Tm <= kMaxKeys, "smi_enc_forward: %d speaker tokens + %d mel frames exceed the attention kernel's %d-key score buffer",
+              c.spk_tokens, Tm, kMaxKeys);
   auto B = [&](const char* n) { return h->buf.at(n); };
-  auto closure = [&](const std::string& name, double flops, std::function<void(hipStream_t)> fn) {
-    Launch L; L.kind = 9; L.name = name; L.flops = flops; L.fn = std::move(fn);
+  // a small kernel: the launch runs with the grid / block / dynamic LDS recorded here (what smi_enc_debug_launch reports)
+  using Geo = std::function<void(hipStream_t, dim3, dim3, size_t)>;
+  auto closure = [&](const std::string& name, double flops, dim3 grid, int blk, size_t lds, Geo fn) {
+    Launch L; L.kind = 9; L.name = name; L.flops = flops; L.grid = grid; L.blk = blk; L.lds = lds;
+    L.fn = [=](hipStream_t s) { fn(s, grid, dim3(blk), lds); };
     P.push_back(std::move(L));
   };
   auto stage = [&](const std::string& name, const float* p, int rows, int cols, int stride) { h->stages[name] = {p, rows, cols, stride}; };
@@ -710,7 +734,7 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     LnP& p = L.lp; memset(&p, 0, sizeof(p));
     p.X = X; p.Y = Y; p.dww = dww; p.dwb = dwb; p.lens = slot(Tn); p.C = C; p.stride = stride; p.bs = 0; p.triple = triple;
     p.w = ent(h, pfx + ".weight"); p.bsh = ent(h, pfx + ".bias"); p.eps = eps; p.gelu = gelu;
-    L.cpt = (C + 31) / 32; L.grid = dim3((Tn + 7) / 8, 1);
+    L.cpt = (C + 31) / 32; L.grid = dim3((Tn + 7) / 8, 1); L.blk = 256; L.lds = 0;
     P.push_back(L);
   };
   // Linear / Conv1d on [C][T] activations (B = 1).  Returns the launch for epilogue tweaks.
@@ -725,15 +749,16 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
                  int heads, int Tq, int Tk) {
     MhaP m{Q, K, V, O, qs, ks, vs, os, Tq, Tk, 0.125f};
     const size_t lds = (size_t)(512 + 8 * Tk + 64 * 65) * 4;
-    const dim3 grid((Tq + 7) / 8, heads);
-    closure(name, 4.0 * heads * 64.0 * Tq * Tk, [=](hipStream_t s) {
-      hipLaunchKernelGGL(k_mha, grid, dim3(256), lds, s, m);
+    closure(name, 4.0 * heads * 64.0 * Tq * Tk, dim3((Tq + 7) / 8, heads), 256, lds, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_mha, g, b, l, s, m);
     });
   };
 
   // ================= wav2vec2 =================
   float* wavn = B("wavn");
-  closure("w2v.normalize", 4.0 * n_samples, [=](hipStream_t s) { hipLaunchKernelGGL(k_wavnorm, dim3(1), dim3(1024), 0, s, wav_dev, n_samples, wavn); });
+  closure("w2v.normalize", 4.0 * n_samples, dim3(1), 1024, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+    hipLaunchKernelGGL(k_wavnorm, g, b, l, s, wav_dev, n_samples, wavn);
+  });
   stage("input_values", wavn, 1, n_samples, n_samples);
   const int CD = c.w2v_conv_dim;
   float* cf[2] = {B("cf0"), B("cf1")};
@@ -743,8 +768,8 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     const float* b0 = ent(h, "w2v.feature_extractor.conv_layers.0.conv.bias");
     float* Y = cf[0];
     const int K0 = c.w2v_kernel[0], S0 = c.w2v_stride[0], T0 = Ts[0];
-    closure("w2v.conv0", 2.0 * CD * K0 * T0, [=](hipStream_t s) {
-      hipLaunchKernelGGL(k_conv0, dim3((T0 + 255) / 256, CD), dim3(256), 0, s, wavn, W0, b0, K0, S0, Y, CD, T0, T0);
+    closure("w2v.conv0", 2.0 * CD * K0 * T0, dim3((T0 + 255) / 256, CD), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_conv0, g, b, l, s, wavn, W0, b0, K0, S0, Y, CD, T0, T0);
     });
     lnorm("w2v.conv0.ln+gelu", "w2v.feature_extractor.conv_layers.0.layer_norm", nullptr, nullptr, cf[0], cf[1], CD, T0, T0, 1e-5f, 1, 0);
     cur = 1;
@@ -769,13 +794,15 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     const float* bp = ent(h, "w2v.encoder.pos_conv_embed.conv.bias");
     const int Cg = Hd / c.w2v_pos_groups, K = c.w2v_pos_k;
     const size_t lds = (size_t)Cg * (64 + K - 1) * 4;
-    closure("w2v.pos_conv+gelu+res", 2.0 * Hd * Cg * K * T, [=](hipStream_t s) {
-      hipLaunchKernelGGL(k_posconv, dim3((T + 63) / 64, Hd / 16), dim3(256), lds, s, x, Wp, bp, hbuf, Hd, Cg, K, T, T);
+    closure("w2v.pos_conv+gelu+res", 2.0 * Hd * Cg * K * T, dim3((T + 63) / 64, Hd / 16), 256, lds, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_posconv, g, b, l, s, x, Wp, bp, hbuf, Hd, Cg, K, T, T);
     });
   }
   {   // test view of hidden_states[0] (the residual stream is updated in place by the layers)
     float* d0 = B("dbg_hs0");
-    closure("w2v.hs0(dbg copy)", 0.0, [=](hipStream_t s) { hipLaunchKernelGGL(k_copy2d, dim3((T + 255) / 256, Hd), dim3(256), 0, s, hbuf, T, d0, T, Hd, T); });
+    closure("w2v.hs0(dbg copy)", 0.0, dim3((T + 255) / 256, Hd), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_copy2d, g, b, l, s, hbuf, T, d0, T, Hd, T);
+    });
     stage("hs0", d0, Hd, T, T);
   }
   const long long nHT = (long long)Hd * T;
@@ -784,8 +811,8 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     for (int k = 0; k < 3; ++k) {
       if (c.w2v_taps[k] != idx) continue;
       const int mode = k;
-      closure("w2v.tap" + std::to_string(idx), 1.0 * nHT, [=](hipStream_t s) {
-        hipLaunchKernelGGL(k_tap, dim3((unsigned)((nHT + 255) / 256)), dim3(256), 0, s, hbuf, acc, feat, nHT, mode);
+      closure("w2v.tap" + std::to_string(idx), 1.0 * nHT, dim3((unsigned)((nHT + 255) / 256)), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+        hipLaunchKernelGGL(k_tap, g, b, l, s, hbuf, acc, feat, nHT, mode);
       });
     }
   };
@@ -837,18 +864,22 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
          nullptr, T, T, T, ACT_NONE, 1);
     const float *cbn = h->cbn, *c2 = h->c2;
     const int Dc = c.codebook_dim, nc = c.codebook_size;
-    closure("quantizer.argmax", 2.0 * T * nc * Dc, [=](hipStream_t s) { hipLaunchKernelGGL(k_vq, dim3(T), dim3(256), 0, s, e0, Dc, T, T, cbn, c2, nc, sem_dev); });
+    closure("quantizer.argmax", 2.0 * T * nc * Dc, dim3(T), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_vq, g, b, l, s, e0, Dc, T, T, cbn, c2, nc, sem_dev);
+    });
   }
 
   // ================= mel + ECAPA-TDNN latent + perceiver + FSQ =================
   {
     const int nf = c.n_fft / 2 + 1, nfft = c.n_fft, hop = c.hop_length;
     float *fr = B("frames"), *dft = B("dft"), *mag = B("mag"), *mel = B("mel");
-    closure("mel.frames", 1.0 * nfft * Tm, [=](hipStream_t s) {
-      hipLaunchKernelGGL(k_frames, dim3((Tm + 255) / 256, nfft), dim3(256), 0, s, ref_dev, n_ref, nfft, hop, fr, Tm, Tm);
+    closure("mel.frames", 1.0 * nfft * Tm, dim3((Tm + 255) / 256, nfft), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_frames, g, b, l, s, ref_dev, n_ref, nfft, hop, fr, Tm, Tm);
     });
     conv("mel.dft", "mel.dft", "", 2 * nf, nfft, 1, 1, 0, fr, Tm, dft, nullptr, Tm, Tm, Tm, ACT_NONE, 1);
-    closure("mel.magnitude", 4.0 * nf * Tm, [=](hipStream_t s) { hipLaunchKernelGGL(k_mag, dim3((Tm + 255) / 256, nf), dim3(256), 0, s, dft, nf, Tm, Tm, mag); });
+    closure("mel.magnitude", 4.0 * nf * Tm, dim3((Tm + 255) / 256, nf), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_mag, g, b, l, s, dft, nf, Tm, Tm, mag);
+    });
     conv("mel.filterbank", "mel.fb", "", c.num_mels, nf, 1, 1, 0, mag, Tm, mel, nullptr, Tm, Tm, Tm, ACT_NONE, 1);
     stage("mel", mel, c.num_mels, Tm, Tm);
     // ---- ECAPA-TDNN (ecapa_tdnn.py:186-197): bn(relu(conv(x))) fused as ReLU + affine in the conv epilogue
@@ -879,11 +910,15 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
       {
         const float* src = y0 + (size_t)7 * W * Tm;
         float* dst = y1 + (size_t)7 * W * Tm;
-        closure(b + ".1.passthrough", 0.0, [=](hipStream_t s) { hipLaunchKernelGGL(k_copy2d, dim3((Tm + 255) / 256, W), dim3(256), 0, s, src, Tm, dst, Tm, W, Tm); });
+        closure(b + ".1.passthrough", 0.0, dim3((Tm + 255) / 256, W), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
+          hipLaunchKernelGGL(k_copy2d, g, bl, l, s, src, Tm, dst, Tm, W, Tm);
+        });
       }
       crb(b + ".2", b + ".2", C, C, 1, 1, 0, y1, nullptr, y0);
       float *mean = evec, *s1 = evec + C, *s2 = evec + C + 128;
-      closure(b + ".3.mean", 1.0 * C * Tm, [=](hipStream_t s) { hipLaunchKernelGGL(k_rowmean, dim3((C + 3) / 4), dim3(256), 0, s, y0, C, Tm, Tm, mean); });
+      closure(b + ".3.mean", 1.0 * C * Tm, dim3((C + 3) / 4), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
+        hipLaunchKernelGGL(k_rowmean, g, bl, l, s, y0, C, Tm, Tm, mean);
+      });
       const int* len1 = slot(1);
       P.push_back(make_conv_w(b + ".3.linear1", ent(h, b + ".3.linear1.weight"), ent(h, b + ".3.linear1.bias"), 128, C, 1, 1, 1, 0, mean, 1, C, s1,
                               nullptr, nullptr, nullptr, 1, 128, len1, 1, 1, ACT_RELU));
@@ -893,7 +928,9 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
       P.back().gemv = true; P.back().grid = dim3((C + 31) / 32, 1);
       float* outl = ecat + (size_t)(li - 2) * C * Tm;
       const float* xi = xin;
-      closure(b + ".3.scale+res", 2.0 * C * Tm, [=](hipStream_t s) { hipLaunchKernelGGL(k_se, dim3((Tm + 255) / 256, C), dim3(256), 0, s, xi, y0, s2, outl, Tm, Tm, Tm); });
+      closure(b + ".3.scale+res", 2.0 * C * Tm, dim3((Tm + 255) / 256, C), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
+        hipLaunchKernelGGL(k_se, g, bl, l, s, xi, y0, s2, outl, Tm, Tm, Tm);
+      });
       xin = outl;
     }
     conv(se + ".conv+relu", se + ".conv.weight", se + ".conv.bias", c.ecapa_out, 3 * C, 1, 1, 0, ecat, Tm, elat, nullptr, Tm, Tm, Tm, ACT_RELU, 1);
@@ -904,7 +941,9 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     float *ctx = B("pctx"), *pq = B("pq"), *pkv = B("pkv"), *po = B("po"), *pff = B("pff"), *pg = B("pg"), *pout = B("pout");
     {
       const float* lt = ent(h, "transpose:" + ps + ".latents");
-      closure(ps + ".latents", 0.0, [=](hipStream_t s) { hipLaunchKernelGGL(k_copy2d, dim3(1, Ld), dim3(256), 0, s, lt, Nt, ctx, Tk, Ld, Nt); });
+      closure(ps + ".latents", 0.0, dim3((Nt + 255) / 256, Ld), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+        hipLaunchKernelGGL(k_copy2d, g, b, l, s, lt, Nt, ctx, Tk, Ld, Nt);
+      });
     }
     conv(ps + ".proj_context", ps + ".proj_context.weight", ps + ".proj_context.bias", Ld, c.ecapa_out, 1, 1, 0, elat, Tm, ctx + Nt, nullptr, Tk,
          Tm, Tm, ACT_NONE, 1);
@@ -915,12 +954,16 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
       mha(a + ".attend", pq, Nt, pkv, Tk, pkv + (size_t)inner * Tk, Tk, po, Nt, c.perc_heads, Nt, Tk);
       conv(a + ".to_out+res", a + ".to_out.weight", "", Ld, inner, 1, 1, 0, po, Nt, ctx, ctx, Tk, Nt, Nt, ACT_NONE, 1);
       conv(f + ".0", f + ".0.weight", f + ".0.bias", 2 * FI, Ld, 1, 1, 0, ctx, Tk, pff, nullptr, Nt, Nt, Nt, ACT_NONE, 1);
-      closure(f + ".geglu", 10.0 * FI * Nt, [=](hipStream_t s) { hipLaunchKernelGGL(k_geglu, dim3(1, FI), dim3(64 * ((Nt + 63) / 64)), 0, s, pff, FI, Nt, Nt, pg); });
+      closure(f + ".geglu", 10.0 * FI * Nt, dim3(1, FI), 64 * ((Nt + 63) / 64), 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+        hipLaunchKernelGGL(k_geglu, g, b, l, s, pff, FI, Nt, Nt, pg);
+      });
       conv(f + ".2+res", f + ".2.weight", f + ".2.bias", Ld, FI, 1, 1, 0, pg, Nt, ctx, ctx, Tk, Nt, Nt, ACT_NONE, 1);
     }
     {
       const float* gm = ent(h, ps + ".norm.gamma");
-      closure(ps + ".norm", 4.0 * Ld * Nt, [=](hipStream_t s) { hipLaunchKernelGGL(k_rmsn, dim3((Nt + 63) / 64), dim3(64), 0, s, ctx, Ld, Nt, Tk, gm, pout, Nt); });
+      closure(ps + ".norm", 4.0 * Ld * Nt, dim3((Nt + 63) / 64), 64, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+        hipLaunchKernelGGL(k_rmsn, g, b, l, s, ctx, Ld, Nt, Tk, gm, pout, Nt);
+      });
     }
     stage("perceiver", pout, Ld, Nt, Nt);
     FsqQP q;
@@ -928,7 +971,9 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     q.X = pout; q.W = ent(h, "speaker_encoder.quantizer.project_in.weight"); q.b = ent(h, "speaker_encoder.quantizer.project_in.bias");
     q.out = glob_dev; q.bounded = B("fsqb"); q.latent = Ld; q.stride = Nt; q.Ntok = Nt; q.nd = c.fsq_dims;
     for (int j = 0; j < 8; ++j) q.levels[j] = j < c.fsq_dims ? c.fsq_levels[j] : 1;
-    closure("speaker_encoder.quantizer", 2.0 * Nt * Ld * c.fsq_dims, [=](hipStream_t s) { hipLaunchKernelGGL(k_fsq_quant, dim3((Nt + 63) / 64), dim3(64), 0, s, q); });
+    closure("speaker_encoder.quantizer", 2.0 * Nt * Ld * c.fsq_dims, dim3((Nt + 63) / 64), 64, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_fsq_quant, g, b, l, s, q);
+    });
     stage("fsq_bounded", B("fsqb"), Nt, c.fsq_dims, c.fsq_dims);
   }
 
@@ -1055,6 +1100,66 @@ int smi_enc_debug_stage(smi_enc* h, const char* name, float* out_dev, size_t max
 }
 
 int smi_enc_num_launches(smi_enc* h) { return h ? (int)h->prog.size() : 0; }
+
+#ifdef SMI_DIAG   // ---- include/sparkmi_debug.h: the encoder's launch list one launch at a time, exported by libsparkmi_diag.so only
+
+int smi_enc_debug_build(smi_enc* h, int n_samples, int n_ref, int* n_frames, int* n_launches, void* stream) {
+  SMI_REQUIRE(h && n_frames && n_launches, "smi_enc_debug_build: null argument");
+  const smi_enc_cfg& c = h->cfg;
+  SMI_REQUIRE(n_samples >= 400 && n_samples <= c.max_samples, "smi_enc_debug_build: n_samples=%d outside 400..%d", n_samples, c.max_samples);
+  SMI_REQUIRE(n_ref > c.n_fft / 2 && n_ref <= c.max_ref_samples, "smi_enc_debug_build: n_ref=%d outside %d..%d", n_ref, c.n_fft / 2 + 1,
+              c.max_ref_samples);
+  hipStream_t st = (hipStream_t)stream;
+  h->prog_key = {-1, -1};
+  int rc = enc_build(h, h->buf.at("in_wav"), n_samples, h->buf.at("in_ref"), n_ref, (int64_t*)h->buf.at("out_sem"), (int32_t*)h->buf.at("out_glob"),
+                     n_frames);
+  if (rc) { h->prog.clear(); return rc; }
+  SMI_HIP(hipMemcpyAsync(h->lens_dev, h->host_lens.data(), h->host_lens.size() * 4, hipMemcpyHostToDevice, st));
+  SMI_HIP(hipStreamSynchronize(st));
+  *n_launches = (int)h->prog.size();
+  return SMI_OK;
+}
+
+int smi_enc_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* info) {
+  SMI_REQUIRE(h && info, "smi_enc_debug_launch: null argument");
+  SMI_REQUIRE(index >= 0 && index < (int)h->prog.size(), "smi_enc_debug_launch: index %d out of range", index);
+  const Launch& L = h->prog[index];
+  if (name && cap > 0) { strncpy(name, L.name.c_str(), (size_t)cap - 1); name[cap - 1] = 0; }
+  info[0] = L.kind; info[1] = (int32_t)L.grid.x; info[2] = (int32_t)L.grid.y; info[3] = (int32_t)L.grid.z;
+  info[4] = L.kind == 0 ? 64 * L.nwv : L.blk;
+  info[5] = (int32_t)L.lds;
+  info[6] = L.kind == 1 ? dwln_form(L.cpt) : 0;
+  info[7] = 0;
+  return SMI_OK;
+}
+
+int smi_enc_debug_io(smi_enc* h, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats) {
+  SMI_REQUIRE(h && buffer_name && host_ptr, "smi_enc_debug_io: null argument");
+  auto it = h->buf.find(buffer_name);
+  SMI_REQUIRE(it != h->buf.end(), "smi_enc_debug_io: unknown buffer '%s'", buffer_name);
+  const size_t have = h->buf_floats.at(buffer_name);
+  SMI_REQUIRE(offset_floats <= have && floats <= have - offset_floats, "smi_enc_debug_io: %zu floats at %zu outside '%s' (%zu floats)", floats,
+              offset_floats, buffer_name, have);
+  SMI_HIP(hipDeviceSynchronize());
+  if (write) SMI_HIP(hipMemcpy(it->second + offset_floats, host_ptr, floats * 4, hipMemcpyHostToDevice));
+  else SMI_HIP(hipMemcpy(host_ptr, it->second + offset_floats, floats * 4, hipMemcpyDeviceToHost));
+  return SMI_OK;
+}
+
+int smi_enc_debug_run(smi_enc* h, int first, int last, void* stream) {
+  SMI_REQUIRE(h, "smi_enc_debug_run: null handle");
+  SMI_REQUIRE(first >= 0 && first <= last && last < (int)h->prog.size(), "smi_enc_debug_run: launches %d..%d outside 0..%d", first, last,
+              (int)h->prog.size() - 1);
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = first; i <= last; ++i) {
+    const int rc = run_launch(h->prog[i], st);
+    if (rc) return rc;
+  }
+  SMI_HIP(hipStreamSynchronize(st));
+  return SMI_OK;
+}
+
+#endif   // SMI_DIAG
 
 int smi_enc_time_launch(smi_enc* h, int index, int iters, float* ms_avg, double* flops, char* name, int name_cap, void* stream) {
   SMI_REQUIRE(h && ms_avg && iters > 0, "smi_enc_time_launch: bad argument");

@@ -1287,6 +1287,7 @@ struct Launch {
   std::string name;
   double flops;
   ConvP cp; int qb; bool ks; int chg; int nwv = 4; bool gemv; bool bf = false; bool c1 = false; int c1_len = 0; dim3 grid; size_t lds;
+  int blk = 0;       // kind 9: threads per block of the closure's launch (with grid and lds: the record the diagnostics report)
   int tph = 0;       // k_convbT: output phases per block of a transposed conv (0: k_convb, one phase per block)
   long long plan_blocks = 0;   // blocks of the grid the plan was chosen for, where that is not the launch's own (PlanShape); 0: the launch's
   ResP rp; int res_nwv = 0;   // kind 5: a fused ResidualUnit (k_resunit) with res_nwv waves per block

@@ -234,6 +234,10 @@ DEBUG_SYMBOLS = {
     "smi_conv_plan": (_I, [_P(ConvCase), _P(ConvPlanInfo)]),
     "smi_conv_run": (_I, [_P(ConvCase), _P(ConvOperands), _P(C.c_int32), _P(ConvPlanInfo), _VP]),
     "smi_voc_block_plan": (_I, [_P(VocBlockCfg), _I, _I, _P(BlockLaunchInfo), _I, _P(C.c_int32)]),
+    "smi_enc_debug_build": (_I, [_VP, _I, _I, _P(_I), _P(_I), _VP]),
+    "smi_enc_debug_launch": (_I, [_VP, _I, C.c_char_p, _I, _P(C.c_int32)]),
+    "smi_enc_debug_io": (_I, [_VP, C.c_char_p, _I, _VP, _SZ, _SZ]),
+    "smi_enc_debug_run": (_I, [_VP, _I, _I, _VP]),
 }
 
 DIAG_PATH = LIB_PATH.with_name("libsparkmi_diag.so")

@@ -308,3 +308,49 @@ class BiCodecEncoder:
         self._lib.check(self._lib.smi_enc_time_launch(self._h, index, iters, C.byref(ms), C.byref(fl), name, 512, self._stream()),
                    "smi_enc_time_launch")
         return name.value.decode(), float(ms.value), float(fl.value)
+
+    # ---- include/sparkmi_debug.h: the encoder's own launch list, one launch at a time (diag=True only)
+    def _need_diag(self):
+        if not self._lib.is_diag:
+            raise _lib.SparkMIError("the launch-level entry points exist in libsparkmi_diag.so only: build the encoder with diag=True")
+
+    def debug_build(self, n_samples: int, n_ref: int) -> Tuple[int, int]:
+        """The launch list of an encode of (n_samples, n_ref) on the handle-owned buffers; nothing runs.  (frames, launches)."""
+        self._need_diag()
+        nf, nl = C.c_int(0), C.c_int(0)
+        self._lib.check(self._lib.smi_enc_debug_build(self._h, int(n_samples), int(n_ref), C.byref(nf), C.byref(nl), self._stream()),
+                        "smi_enc_debug_build")
+        return nf.value, nl.value
+
+    def debug_launches(self):
+        """[{index, name, kind, grid (x, y, z), block, lds, cpt}] of the list debug_build (or the last eager encode) left."""
+        self._need_diag()
+        out = []
+        name, info = C.create_string_buffer(512), (C.c_int32 * 8)()
+        for i in range(self.launches()):
+            self._lib.check(self._lib.smi_enc_debug_launch(self._h, i, name, 512, info), "smi_enc_debug_launch")
+            out.append(dict(index=i, name=name.value.decode(), kind=info[0], grid=(info[1], info[2], info[3]), block=info[4],
+                            lds=info[5], cpt=info[6]))
+        return out
+
+    def debug_io(self, buffer: str, data: Optional[np.ndarray] = None, offset: int = 0, count: int = 0,
+                 dtype=np.float32) -> Optional[np.ndarray]:
+        """``data`` given: written at ``offset`` (4-byte words) of the named buffer; else ``count`` words are read and returned
+        viewed as ``dtype`` (out_sem holds int64 ids, out_glob int32)."""
+        self._need_diag()
+        if data is not None:
+            a = np.ascontiguousarray(data)
+            assert a.dtype.itemsize in (4, 8)
+            self._lib.check(self._lib.smi_enc_debug_io(self._h, buffer.encode(), 1, C.c_void_p(a.ctypes.data), int(offset),
+                                                       a.nbytes // 4), "smi_enc_debug_io")
+            return None
+        out = np.empty(int(count), dtype=np.float32)
+        self._lib.check(self._lib.smi_enc_debug_io(self._h, buffer.encode(), 0, C.c_void_p(out.ctypes.data), int(offset), int(count)),
+                        "smi_enc_debug_io")
+        return out.view(dtype)
+
+    def debug_run(self, first: int, last: Optional[int] = None) -> None:
+        """Launches first .. last of the list, once each and in order, then synchronises."""
+        self._need_diag()
+        self._lib.check(self._lib.smi_enc_debug_run(self._h, int(first), int(first if last is None else last), self._stream()),
+                        "smi_enc_debug_run")
