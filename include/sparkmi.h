@@ -534,7 +534,7 @@ int smi_voc_block_run(const smi_voc_block_cfg* cfg, const void* arena_dev, size_
  * = zero-mean/unit-variance wav -> wav2vec2 (layers below the last tapped hidden state) -> mean of
  * three hidden states -> BiCodec Encoder -> cosine VQ arg-max (semantic ids); reference clip -> mel
  * -> ECAPA-TDNN latent -> perceiver resampler -> FSQ (global ids)  (sparktts/models/bicodec.py:151-169).
- * One utterance per call, as the reference's tokenize().
+ * One utterance per call, as the reference's tokenize() (smi_enc_forward), or a ragged batch (smi_enc_forward_rows).
  * ---------------------------------------------------------------------------------------- */
 typedef struct smi_enc smi_enc;
 
@@ -577,6 +577,24 @@ int smi_enc_destroy(smi_enc* h);
  * sem_dev [>= frames] int64 out, glob_dev [spk_tokens] int32 out; *n_frames = wav2vec2 frames produced. */
 int smi_enc_forward(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_dev, int n_ref,
                     int64_t* sem_dev, int32_t* glob_dev, int* n_frames, void* stream);
+/* A ragged batch of B prompts in one call.  wav_dev [B][wav_stride] f32 (row b valid for n_samples_host[b]), ref_dev
+ * [B][ref_stride] f32 (n_ref_host[b]); sem_dev [B][sem_stride] int64 out: row b receives n_frames_host[b] ids, entries beyond are
+ * left untouched; glob_dev [B][spk_tokens] int32 out.  Row b's ids -- and every intermediate activation -- equal, bit for bit,
+ * smi_enc_forward of that row alone on a handle of the same config, whatever else is in the call and wherever the row sits.
+ * (The conv launch builder picks tile width, channel split and kernel form from its call shape, and the ids are arg-max and
+ * rounding decisions, so a batch planned as a whole would not do.)  Here every such choice is taken as if the call were the
+ * row's own; consecutive rows whose choices agree in every launch run as ONE launch sequence whose grids cover their count and
+ * their longest row (a shorter row's spare blocks exit; attention is over the row's own keys), so the call costs one launch
+ * sequence per run of equal plans: sort the rows by length (BiCodecEncoder.tokenize_rows does).  Every row gets
+ * smi_enc_forward's argument checks before anything reaches the device.  The launches are eager (no graph); the solo path, its
+ * graph cache and its debug views are neither read nor disturbed.
+ * smi_enc_rows_reserve allocates (or re-allocates, when the arguments change) the rows workspace: max_rows rows of up to
+ * max_row_samples (<= max_samples) / max_row_ref_samples (<= max_ref_samples); smi_enc_forward_rows allocates nothing and
+ * returns SMI_EINVAL without a reserve or beyond it.  smi_enc_destroy frees it. */
+int smi_enc_rows_reserve(smi_enc* h, int max_rows, int max_row_samples, int max_row_ref_samples);
+int smi_enc_forward_rows(smi_enc* h, const float* wav_dev, long long wav_stride, const int32_t* n_samples_host,
+                         const float* ref_dev, long long ref_stride, const int32_t* n_ref_host, int B,
+                         int64_t* sem_dev, long long sem_stride, int32_t* glob_dev, int32_t* n_frames_host, void* stream);
 /* Test entry: copies a named internal activation of the last forward ("feat", "z", "mel", "ecapa_latent",
  * "perceiver", "hs0", "conv_feats", "input_values", ...) to out_dev as [rows][cols] f32; dims[2] = {rows, cols}. */
 int smi_enc_debug_stage(smi_enc* h, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream);

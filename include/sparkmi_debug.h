@@ -235,6 +235,24 @@ int smi_enc_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* in
 int smi_enc_debug_io(smi_enc* h, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats);
 int smi_enc_debug_run(smi_enc* h, int first, int last, void* stream);
 
+/* The rows list (smi_enc_forward_rows) the same way; smi_enc_rows_reserve first.
+ *   smi_enc_rows_debug_build: builds the list of B rows of (n_samples[b], n_ref[b]) on the workspace's own in_wav / in_ref /
+ *     out_sem / out_glob buffers (row b's in its slab), uploads the length arrays and runs nothing.  smi_enc_forward_rows'
+ *     argument checks apply.  n_frames[B]; *n_runs runs, run_start[i] (at most run_cap written) = first row of run i.
+ *   smi_enc_rows_debug_runs: the same run table of the list the last build or the last smi_enc_forward_rows left.
+ *   smi_enc_rows_debug_launch: as smi_enc_debug_launch; grid z is the number of rows of the launch's run (times the phases of a conv).
+ *   smi_enc_rows_debug_io: as smi_enc_debug_io on row `row`'s copy of the named buffer (any reserved row, used or not); a copy
+ *     that leaves the buffer's per-row size is SMI_EINVAL.  Inside a run a [C][T] buffer's row stride is the run's longest row.
+ *   smi_enc_rows_debug_run: launches first .. last of the rows list, once each and in order, then synchronises.
+ *   smi_enc_rows_debug_stage: smi_enc_debug_stage for row `row` of the last smi_enc_forward_rows. */
+int smi_enc_rows_debug_build(smi_enc* h, const int32_t* n_samples, const int32_t* n_ref, int B, int32_t* n_frames, int* n_launches,
+                             int32_t* run_start, int run_cap, int* n_runs, void* stream);
+int smi_enc_rows_debug_runs(smi_enc* h, int32_t* run_start, int run_cap, int* n_runs, int* n_launches);
+int smi_enc_rows_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* info);
+int smi_enc_rows_debug_io(smi_enc* h, int row, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats);
+int smi_enc_rows_debug_run(smi_enc* h, int first, int last, void* stream);
+int smi_enc_rows_debug_stage(smi_enc* h, int row, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

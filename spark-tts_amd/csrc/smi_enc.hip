@@ -26,10 +26,16 @@ namespace {
 // small kernels
 // ------------------------------------------------------------------------------------------
 
-// (x - mean) / sqrt(var + 1e-7), feature_extraction_wav2vec2.py zero_mean_unit_var_norm; one block.
-__global__ __launch_bounds__(1024) void k_wavnorm(const float* x, int n, float* y) {
+// Every kernel below carries a row dimension: block z is row b of the launch, the row's lengths come from device arrays indexed by
+// b (one per length kind) and its buffers sit b batch strides on.  A row's arithmetic depends on its own lengths only and blocks
+// beyond a row's own extent exit without writing, so a row of a ragged launch carries the bits of its solo launch (one row,
+// batch strides 0: smi_enc_forward's list).
+
+// (x - mean) / sqrt(var + 1e-7), feature_extraction_wav2vec2.py zero_mean_unit_var_norm; one block per row.
+__global__ __launch_bounds__(1024) void k_wavnorm(const float* x, long long xbs, const int* ns, float* y, long long ybs) {
   __shared__ double red[1024];
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x, n = ns[blockIdx.z];
+  x += blockIdx.z * xbs; y += blockIdx.z * ybs;
   double s = 0.0;
   for (int i = tid; i < n; i += 1024) s += (double)x[i];
   red[tid] = s;
@@ -48,9 +54,11 @@ __global__ __launch_bounds__(1024) void k_wavnorm(const float* x, int n, float* 
 }
 
 // first feature-encoder conv: Conv1d(1 -> C, K, stride), no padding.  W [C][K].
-__global__ void k_conv0(const float* x, const float* W, const float* bias, int K, int stride, float* Y, int C, int T, int ystride) {
+__global__ void k_conv0(const float* x, const float* W, const float* bias, int K, int stride, float* Y, int C, const int* Ts, int ystride,
+                        long long bs) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
-  if (t >= T) return;
+  if (t >= Ts[blockIdx.z]) return;
+  x += blockIdx.z * bs; Y += blockIdx.z * bs;
   float acc = 0.f;
   for (int k = 0; k < K; ++k) acc += W[c * K + k] * x[t * stride + k];
   Y[(long long)c * ystride + t] = acc + (bias ? bias[c] : 0.f);
@@ -60,9 +68,12 @@ __global__ void k_conv0(const float* x, const float* W, const float* bias, int K
 //   sum_{ci < Cg, k < K} W[c][ci][k] * x[g*Cg + ci][t + k - K/2]);  the SamePad layer drops the extra last frame.
 // Block = 16 output channels of one group x 64 frames; wave w computes channels 4w..4w+3 (weights wave-uniform).
 __global__ __launch_bounds__(256) void k_posconv(const float* X, const float* W, const float* bias, float* Y, int C, int Cg, int K,
-                                                 int T, int stride) {
+                                                 const int* Ts, int stride, long long bs) {
   extern __shared__ float xs[];            // [Cg][64 + K - 1]
   const int t0 = blockIdx.x * 64, cot = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int T = Ts[blockIdx.z];
+  if (t0 >= T) return;                     // (a block beyond the row: the launch covers the longest row)
+  X += blockIdx.z * bs; Y += blockIdx.z * bs;
   const int co0 = cot * 16 + wave * 4, g = (cot * 16) / Cg;
   const int xw = 64 + K - 1;
   for (int i = threadIdx.x; i < Cg * xw; i += 256) {
@@ -96,11 +107,16 @@ struct MhaP {
   const float *Q, *K, *V;
   float* O;
   int qs, ks, vs, os;   // row strides
-  int Tq, Tk;
+  int Tq, Tk;           // (set by the kernel from the two arrays)
   float scale;
+  const int *Tqs, *Tks; // [rows] queries / keys of each row
+  long long bs;         // batch stride of the four buffers
 };
 __global__ __launch_bounds__(256) void k_mha(MhaP p) {
   extern __shared__ float sm[];
+  p.Tq = p.Tqs[blockIdx.z]; p.Tk = p.Tks[blockIdx.z];
+  if ((int)blockIdx.x * 8 >= p.Tq) return;
+  p.Q += blockIdx.z * p.bs; p.K += blockIdx.z * p.bs; p.V += blockIdx.z * p.bs; p.O += blockIdx.z * p.bs;
   float* qs = sm;                       // [64][8]
   float* S = sm + 512;                  // [8][Tk]
   float* Vs = S + 8 * p.Tk;             // [64][65]
@@ -171,10 +187,22 @@ __global__ void k_tap(const float* h, float* acc, float* out, long long n, int m
   else out[i] = (acc[i] + h[i]) / 3.0f;
 }
 
+// the same over rows of a ragged launch: [Hd][stride] per row, indexed by (channel, frame) -- a row's own T is not its stride
+__global__ void k_tap_rows(const float* h, float* acc, float* out, const int* Ts, int stride, long long bs, int mode) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= Ts[blockIdx.z]) return;
+  const long long i = blockIdx.z * bs + (long long)blockIdx.y * stride + t;
+  if (mode == 0) acc[i] = h[i];
+  else if (mode == 1) acc[i] = acc[i] + h[i];
+  else out[i] = (acc[i] + h[i]) / 3.0f;
+}
+
 // framed, reflect-padded reference clip: F[k][t] = xpad[t*hop + k], xpad = reflect pad of n_fft/2 (torch.stft center=True)
-__global__ void k_frames(const float* x, int n, int n_fft, int hop, float* F, int T, int stride) {
+__global__ void k_frames(const float* x, long long xbs, const int* ns, int n_fft, int hop, float* F, const int* Ts, int stride, long long bs) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
-  if (t >= T) return;
+  if (t >= Ts[blockIdx.z]) return;
+  const int n = ns[blockIdx.z];
+  x += blockIdx.z * xbs; F += blockIdx.z * bs;
   int i = t * hop + k - n_fft / 2;
   if (i < 0) i = -i;
   if (i >= n) i = 2 * (n - 1) - i;
@@ -182,17 +210,20 @@ __global__ void k_frames(const float* x, int n, int n_fft, int hop, float* F, in
 }
 
 // |re + i im| of the DFT rows: D [2*nf][stride] (re rows then im rows) -> M [nf][stride]
-__global__ void k_mag(const float* D, int nf, int T, int stride, float* M) {
+__global__ void k_mag(const float* D, int nf, const int* Ts, int stride, float* M, long long bs) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
-  if (t >= T) return;
+  if (t >= Ts[blockIdx.z]) return;
+  D += blockIdx.z * bs; M += blockIdx.z * bs;
   const float re = D[(long long)f * stride + t], im = D[(long long)(nf + f) * stride + t];
   M[(long long)f * stride + t] = sqrtf(re * re + im * im);
 }
 
 // mean over time of every channel (SE_Connect, ecapa_tdnn.py:104): one wave per channel
-__global__ __launch_bounds__(256) void k_rowmean(const float* X, int C, int T, int stride, float* out) {
+__global__ __launch_bounds__(256) void k_rowmean(const float* X, int C, const int* Ts, int stride, float* out, long long bs) {
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
+  const int T = Ts[blockIdx.z];
+  X += blockIdx.z * bs; out += blockIdx.z * bs;
   float s = 0.f;
   for (int t = lane; t < T; t += 64) s += X[(long long)c * stride + t];
   s = smi_wave_sum(s);
@@ -200,23 +231,26 @@ __global__ __launch_bounds__(256) void k_rowmean(const float* X, int C, int T, i
 }
 
 // SE_Res2Block tail: out[c][t] = xin[c][t] + y[c][t] * s[c]   (ecapa_tdnn.py:107,133)
-__global__ void k_se(const float* xin, const float* y, const float* s, float* out, int T, int istride, int ostride) {
+__global__ void k_se(const float* xin, const float* y, const float* s, float* out, const int* Ts, int istride, int ostride, long long bs) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
-  if (t >= T) return;
+  if (t >= Ts[blockIdx.z]) return;
+  xin += blockIdx.z * bs; y += blockIdx.z * bs; s += blockIdx.z * bs; out += blockIdx.z * bs;
   out[(long long)c * ostride + t] = xin[(long long)c * istride + t] + y[(long long)c * istride + t] * s[c];
 }
 
 // GEGLU (perceiver_encoder.py:213-216): Y[c][t] = gelu(X[inner + c][t]) * X[c][t]
-__global__ void k_geglu(const float* X, int inner, int T, int stride, float* Y) {
+__global__ void k_geglu(const float* X, int inner, int T, int stride, float* Y, long long bs) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
   if (t >= T) return;
+  X += blockIdx.z * bs; Y += blockIdx.z * bs;
   Y[(long long)c * stride + t] = gelu_f(X[(long long)(inner + c) * stride + t]) * X[(long long)c * stride + t];
 }
 
 // perceiver RMSNorm over channels of T columns: x / max(||x||, 1e-12) * sqrt(C) * gamma (perceiver_encoder.py:180-191)
-__global__ void k_rmsn(const float* X, int C, int T, int stride, const float* gamma, float* Y, int ystride) {
+__global__ void k_rmsn(const float* X, int C, int T, int stride, const float* gamma, float* Y, int ystride, long long bs) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
+  X += blockIdx.z * bs; Y += blockIdx.z * bs;
   float ss = 0.f;
   for (int c = 0; c < C; ++c) { const float v = X[(long long)c * stride + t]; ss += v * v; }
   const float nrm = fmaxf(sqrtf(ss), 1e-12f);
@@ -237,11 +271,13 @@ __global__ void k_cbnorm(const float* cb, int n, int D, float* out, float* c2) {
 }
 
 // cosine-VQ arg-max of one frame per block: -(|e|^2 - 2 e.c + |c|^2), lowest index on ties (torch .max(1)[1])
-__global__ __launch_bounds__(256) void k_vq(const float* Ze, int D, int T, int stride, const float* cbn, const float* c2, int ncode,
-                                            int64_t* sem) {
+__global__ __launch_bounds__(256) void k_vq(const float* Ze, int D, const int* Ts, int stride, long long bs, const float* cbn, const float* c2,
+                                            int ncode, int64_t* sem, long long sem_bs) {
   __shared__ float bv[256];
   __shared__ int bi[256];
   const int t = blockIdx.x, tid = threadIdx.x;
+  if (t >= Ts[blockIdx.z]) return;
+  Ze += blockIdx.z * bs; sem += blockIdx.z * sem_bs;
   float e[16];
   float ss = 0.f;
   for (int d = 0; d < D; ++d) { e[d] = Ze[(long long)d * stride + t]; ss += e[d] * e[d]; }
@@ -277,10 +313,13 @@ struct FsqQP {
   float* bounded;     // [Ntok][nd] (debug) or null
   int latent, stride, Ntok, nd;
   int levels[8];
+  long long bs, obs;  // batch strides of X and bounded, of out
 };
 __global__ void k_fsq_quant(FsqQP p) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.Ntok) return;
+  p.X += blockIdx.z * p.bs; p.out += blockIdx.z * p.obs;
+  if (p.bounded) p.bounded += blockIdx.z * p.bs;
   int idx = 0, basis = 1;
   for (int j = 0; j < p.nd; ++j) {
     float z = 0.f;
@@ -300,9 +339,9 @@ __global__ void k_fsq_quant(FsqQP p) {
   p.out[t] = idx;
 }
 
-__global__ void k_copy2d(const float* src, int sstride, float* dst, int dstride, int rows, int cols) {
+__global__ void k_copy2d(const float* src, int sstride, long long sbs, float* dst, int dstride, long long dbs, int rows, const int* cols) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-  if (t < cols && r < rows) dst[(long long)r * dstride + t] = src[(long long)r * sstride + t];
+  if (t < cols[blockIdx.z] && r < rows) dst[blockIdx.z * dbs + (long long)r * dstride + t] = src[blockIdx.z * sbs + (long long)r * sstride + t];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -469,6 +508,63 @@ EncLayout enc_layout(const smi_enc_cfg* c) {
 
 int conv_out_len(int n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 
+// every working buffer of an encode of up to max_samples / max_ref_samples (floats): the handle's own set and a slab of the rows workspace
+std::map<std::string, size_t> enc_buffers(const smi_enc_cfg& c, int max_samples, int max_ref_samples) {
+  std::map<std::string, size_t> out;
+  // frame counts at the longest input
+  int n = max_samples;
+  std::vector<int> Ts;
+  for (int i = 0; i < c.w2v_nconv; ++i) { n = conv_out_len(n, c.w2v_kernel[i], c.w2v_stride[i]); Ts.push_back(n); }
+  const int T0 = Ts[0] + 8, T = Ts.back() + 8;
+  const int Tm = max_ref_samples / c.hop_length + 1 + 8;
+  const int nf = c.n_fft / 2 + 1;
+  auto want = [&](const std::string& name, size_t floats) { out[name] = floats; };
+  want("wavn", (size_t)max_samples + 64);
+  want("cf0", (size_t)c.w2v_conv_dim * T0);
+  want("cf1", (size_t)c.w2v_conv_dim * T0);
+  const int Hh = c.w2v_hidden;
+  const int wide = c.w2v_inter > 3 * Hh ? c.w2v_inter : 3 * Hh;
+  want("h", (size_t)Hh * T);
+  want("x", (size_t)Hh * T);
+  want("wide", (size_t)wide * T);
+  want("att", (size_t)Hh * T);
+  want("acc", (size_t)Hh * T);
+  want("feat", (size_t)Hh * T);
+  want("dbg_hs0", (size_t)Hh * T);
+  const int D = c.enc_dim;
+  const int ew = c.enc_inter > c.enc_out ? c.enc_inter : c.enc_out;
+  want("e0", (size_t)(D > c.codebook_dim ? D : c.codebook_dim) * T);
+  want("e1", (size_t)D * T);
+  want("e2", (size_t)D * T);
+  want("ew", (size_t)ew * T);
+  want("frames", (size_t)c.n_fft * Tm);
+  want("dft", (size_t)2 * nf * Tm);
+  want("mag", (size_t)nf * Tm);
+  want("mel", (size_t)c.num_mels * Tm);
+  const int C = c.ecapa_channels;
+  want("ec_a", (size_t)C * Tm);
+  want("ec_b", (size_t)C * Tm);
+  want("ec_c", (size_t)C * Tm);
+  want("ec_cat", (size_t)3 * C * Tm);
+  want("ec_lat", (size_t)c.ecapa_out * Tm);
+  want("ec_vec", (size_t)4 * (C + 128));
+  const int Tc = c.spk_tokens + Tm;
+  const int inner = c.perc_heads * 64;
+  want("pctx", (size_t)c.spk_latent * Tc);
+  want("pq", (size_t)inner * c.spk_tokens);
+  want("pkv", (size_t)2 * inner * Tc);
+  want("po", (size_t)inner * c.spk_tokens);
+  want("pff", (size_t)2 * c.perc_ff_inner * c.spk_tokens);
+  want("pg", (size_t)c.perc_ff_inner * c.spk_tokens);
+  want("pout", (size_t)c.spk_latent * c.spk_tokens);
+  want("fsqb", (size_t)c.spk_tokens * 8);
+  want("in_wav", (size_t)max_samples + 64);
+  want("in_ref", (size_t)max_ref_samples + 64);
+  want("out_sem", (size_t)2 * T);           // int64 ids
+  want("out_glob", (size_t)c.spk_tokens + 64);
+  return out;
+}
+
 }  // namespace
 
 struct smi_enc {
@@ -504,6 +600,21 @@ struct smi_enc {
   bool use_graph = true;
   hipStream_t gstream = nullptr;            // graph launches of callers on the null stream (which cannot be captured) run here
   hipEvent_t gev0 = nullptr, gev1 = nullptr;
+  // smi_enc_forward_rows: its own workspace, length arrays, launch list and debug views -- nothing above is read or written by it.
+  // The workspace is max_rows slabs; a slab holds every working buffer of the solo path, sized for the reserved row, at `off`.
+  struct Rows {
+    int max_rows = 0, max_samples = 0, max_ref = 0;
+    float* ws = nullptr;
+    long long slab = 0;                     // floats per row: the one batch stride of every buffer
+    std::map<std::string, size_t> off, floats;
+    int* lens_dev = nullptr;                // [length kind][max_rows]
+    std::vector<int32_t> host_lens;
+    std::vector<Launch> prog;
+    std::vector<int> run_start;             // first row of every run of the last list
+    std::vector<std::map<std::string, Stage>> stages;   // per row
+    std::map<std::pair<int, int>, std::vector<long long>> sigs;   // (n_samples, n_ref) -> the plan signature of that row's solo list
+    int lastB = 0;
+  } rows;
 };
 
 namespace {
@@ -574,57 +685,7 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
     delete h;
     return SMI_EINVAL;
   }
-  // frame counts at the longest input
-  int n = c.max_samples;
-  std::vector<int> Ts;
-  for (int i = 0; i < c.w2v_nconv; ++i) { n = conv_out_len(n, c.w2v_kernel[i], c.w2v_stride[i]); Ts.push_back(n); }
-  const int T0 = Ts[0] + 8, T = Ts.back() + 8;
-  const int Tm = c.max_ref_samples / c.hop_length + 1 + 8;
-  const int nf = c.n_fft / 2 + 1;
-  auto want = [&](const std::string& name, size_t floats) { h->buf_floats[name] = floats; };
-  want("wavn", (size_t)c.max_samples + 64);
-  want("cf0", (size_t)c.w2v_conv_dim * T0);
-  want("cf1", (size_t)c.w2v_conv_dim * T0);
-  const int Hh = c.w2v_hidden;
-  const int wide = c.w2v_inter > 3 * Hh ? c.w2v_inter : 3 * Hh;
-  want("h", (size_t)Hh * T);
-  want("x", (size_t)Hh * T);
-  want("wide", (size_t)wide * T);
-  want("att", (size_t)Hh * T);
-  want("acc", (size_t)Hh * T);
-  want("feat", (size_t)Hh * T);
-  want("dbg_hs0", (size_t)Hh * T);
-  const int D = c.enc_dim;
-  const int ew = c.enc_inter > c.enc_out ? c.enc_inter : c.enc_out;
-  want("e0", (size_t)(D > c.codebook_dim ? D : c.codebook_dim) * T);
-  want("e1", (size_t)D * T);
-  want("e2", (size_t)D * T);
-  want("ew", (size_t)ew * T);
-  want("frames", (size_t)c.n_fft * Tm);
-  want("dft", (size_t)2 * nf * Tm);
-  want("mag", (size_t)nf * Tm);
-  want("mel", (size_t)c.num_mels * Tm);
-  const int C = c.ecapa_channels;
-  want("ec_a", (size_t)C * Tm);
-  want("ec_b", (size_t)C * Tm);
-  want("ec_c", (size_t)C * Tm);
-  want("ec_cat", (size_t)3 * C * Tm);
-  want("ec_lat", (size_t)c.ecapa_out * Tm);
-  want("ec_vec", (size_t)4 * (C + 128));
-  const int Tc = c.spk_tokens + Tm;
-  const int inner = c.perc_heads * 64;
-  want("pctx", (size_t)c.spk_latent * Tc);
-  want("pq", (size_t)inner * c.spk_tokens);
-  want("pkv", (size_t)2 * inner * Tc);
-  want("po", (size_t)inner * c.spk_tokens);
-  want("pff", (size_t)2 * c.perc_ff_inner * c.spk_tokens);
-  want("pg", (size_t)c.perc_ff_inner * c.spk_tokens);
-  want("pout", (size_t)c.spk_latent * c.spk_tokens);
-  want("fsqb", (size_t)c.spk_tokens * 8);
-  want("in_wav", (size_t)c.max_samples + 64);
-  want("in_ref", (size_t)c.max_ref_samples + 64);
-  want("out_sem", (size_t)2 * T);           // int64 ids
-  want("out_glob", (size_t)c.spk_tokens + 64);
+  h->buf_floats = enc_buffers(c, c.max_samples, c.max_ref_samples);
   {
     const char* e = smi_env("SPARKMI_ENC_GRAPH");
     h->use_graph = !(e && e[0] == '0');
@@ -675,6 +736,8 @@ int smi_enc_destroy(smi_enc* h) {
   if (h->cbn) (void)hipFree(h->cbn);
   if (h->c2) (void)hipFree(h->c2);
   if (h->lens_dev) (void)hipFree(h->lens_dev);
+  if (h->rows.ws) (void)hipFree(h->rows.ws);
+  if (h->rows.lens_dev) (void)hipFree(h->rows.lens_dev);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   for (auto& kv : h->graphs)
@@ -693,61 +756,94 @@ int smi_enc_destroy(smi_enc* h) {
 
 namespace {
 
-// The launch sequence of one encode (h->prog), its length slots (h->host_lens) and debug views (h->stages); nothing runs here.
-int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_dev, int n_ref, int64_t* sem_dev, int32_t* glob_dev,
-              int* n_frames) {
+// Every length a launch reads, by kind: the feature encoder's layer outputs (the last is T, the frame count), the two inputs,
+// mel frames Tm, perceiver keys Tk = Nt + Tm, and the two constants the vector projections and the latent-side layers use.
+enum { LK_T0 = 0 /* .. LK_T0 + 7 */, LK_NS = 8, LK_NREF = 9, LK_TM = 10, LK_TK = 11, LK_ONE = 12, LK_NT = 13, LK_COUNT = 14 };
+struct RowLens { int v[LK_COUNT]; };
+
+RowLens row_lens(const smi_enc_cfg& c, int n_samples, int n_ref) {
+  RowLens r;
+  memset(&r, 0, sizeof(r));
+  int n = n_samples;
+  for (int i = 0; i < c.w2v_nconv; ++i) { n = conv_out_len(n, c.w2v_kernel[i], c.w2v_stride[i]); r.v[LK_T0 + i] = n; }
+  r.v[LK_NS] = n_samples; r.v[LK_NREF] = n_ref;
+  r.v[LK_TM] = n_ref / c.hop_length + 1; r.v[LK_TK] = c.spk_tokens + r.v[LK_TM];
+  r.v[LK_ONE] = 1; r.v[LK_NT] = c.spk_tokens;
+  return r;
+}
+
+// What one launch sequence covers.  Solo (smi_enc_forward): one row, extent = plan = the row's own lengths, the handle's buffers,
+// lengths in de-duplicated slots.  Rows (smi_enc_forward_rows): rows r0 .. r0 + B of a call whose launch plans agree; `ext` (the
+// longest row, kind by kind) sizes grids, row strides and dynamic LDS, `plan` (the first row's own lengths) picks every conv
+// launch's tiling and kernel form (PlanShape), and each row's lengths are read from rows.lens_dev[kind][r0 + b].
+struct EncSpan {
+  bool rows;
+  int r0, B;
+  RowLens ext, plan;
+  const RowLens* own;      // [B] each row's lengths (debug views)
+  const float* wav; long long wav_bs;
+  const float* ref; long long ref_bs;
+  int64_t* sem; long long sem_bs;
+  int32_t* glob; long long glob_bs;
+};
+
+// The launch sequence of one span (P), the solo path's length slots (hl) and the debug views of its rows (stages[0 .. B), or
+// null); nothing runs here and nothing of the handle changes.
+int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::vector<int32_t>& hl, std::map<std::string, smi_enc::Stage>* stages) {
   const smi_enc_cfg& c = h->cfg;
-  std::vector<Launch>& P = h->prog;
-  P.clear();
-  h->stages.clear();
-  // ---- length slots (device ints the conv / LN kernels read)
-  std::vector<int32_t>& hl = h->host_lens;
-  hl.clear();
+  const RowLens& E = sp.ext;
+  const int kT = LK_T0 + c.w2v_nconv - 1;
+  const int T = E.v[kT], Tm = E.v[LK_TM], n_samples = E.v[LK_NS];
+  // ---- lengths on the device: solo, a slot per distinct value; rows, the span's part of the array of that kind
   auto slot = [&](int v) -> const int* {
     for (size_t i = 0; i < hl.size(); ++i) if (hl[i] == v) return h->lens_dev + i;
     hl.push_back(v);
     return h->lens_dev + (hl.size() - 1);
   };
-  std::vector<int> Ts;
-  {
-    int n = n_samples;
-    for (int i = 0; i < c.w2v_nconv; ++i) { n = conv_out_len(n, c.w2v_kernel[i], c.w2v_stride[i]); Ts.push_back(n); }
-  }
-  const int T = Ts.back();
-  SMI_REQUIRE(T >= 2, "smi_enc_forward: %d samples give %d frames", n_samples, T);
-  SMI_REQUIRE(T <= kMaxKeys, "smi_enc_forward: %d frames exceed the attention kernel's %d-key score buffer", T, kMaxKeys);
-  const int Tm = n_ref / c.hop_length + 1;
-  SMI_REQUIRE(c.spk_tokens + Tm <= kMaxKeys, "smi_enc_forward: %d speaker tokens + %d mel frames exceed the attention kernel's %d-key score buffer",
-              c.spk_tokens, Tm, kMaxKeys);
-  auto B = [&](const char* n) { return h->buf.at(n); };
+  auto len = [&](int kind) -> const int* {
+    return sp.rows ? h->rows.lens_dev + (size_t)kind * h->rows.max_rows + sp.r0 : slot(E.v[kind]);
+  };
+  const long long bs = sp.rows ? h->rows.slab : 0;      // one batch stride for every working buffer
+  const unsigned nB = (unsigned)sp.B;
+  auto B = [&](const char* n) -> float* { return sp.rows ? h->rows.ws + sp.r0 * bs + h->rows.off.at(n) : h->buf.at(n); };
   // a small kernel: the launch runs with the grid / block / dynamic LDS recorded here (what smi_enc_debug_launch reports)
   using Geo = std::function<void(hipStream_t, dim3, dim3, size_t)>;
   auto closure = [&](const std::string& name, double flops, dim3 grid, int blk, size_t lds, Geo fn) {
-    Launch L; L.kind = 9; L.name = name; L.flops = flops; L.grid = grid; L.blk = blk; L.lds = lds;
+    Launch L; L.kind = 9; L.name = name; L.flops = flops * sp.B; grid.z = nB; L.grid = grid; L.blk = blk; L.lds = lds;
     L.fn = [=](hipStream_t s) { fn(s, grid, dim3(blk), lds); };
     P.push_back(std::move(L));
   };
-  auto stage = [&](const std::string& name, const float* p, int rows, int cols, int stride) { h->stages[name] = {p, rows, cols, stride}; };
+  // cols: a length kind (>= 0) or the literal -cols
+  auto stage = [&](const std::string& name, const float* p, int rows, int cols, int stride) {
+    if (!stages) return;
+    for (int b = 0; b < sp.B; ++b) stages[b][name] = {p + b * bs, rows, cols >= 0 ? sp.own[b].v[cols] : -cols, stride};
+  };
   auto lnorm = [&](const std::string& name, const std::string& pfx, const float* dww, const float* dwb, const float* X, float* Y, int C,
-                   int Tn, int stride, float eps, int gelu, int triple) {
-    Launch L; L.kind = 1; L.name = name; L.flops = (dww ? 14.0 : 0.0) * C * Tn + 8.0 * C * Tn;
+                   int kind, float eps, int gelu, int triple) {
+    const int Tn = E.v[kind];
+    Launch L; L.kind = 1; L.name = name; L.flops = ((dww ? 14.0 : 0.0) * C * Tn + 8.0 * C * Tn) * sp.B;
     LnP& p = L.lp; memset(&p, 0, sizeof(p));
-    p.X = X; p.Y = Y; p.dww = dww; p.dwb = dwb; p.lens = slot(Tn); p.C = C; p.stride = stride; p.bs = 0; p.triple = triple;
+    p.X = X; p.Y = Y; p.dww = dww; p.dwb = dwb; p.lens = len(kind); p.C = C; p.stride = Tn; p.bs = bs; p.triple = triple;
     p.w = ent(h, pfx + ".weight"); p.bsh = ent(h, pfx + ".bias"); p.eps = eps; p.gelu = gelu;
-    L.cpt = (C + 31) / 32; L.grid = dim3((Tn + 7) / 8, 1); L.blk = 256; L.lds = 0;
+    L.cpt = (C + 31) / 32; L.grid = dim3((Tn + 7) / 8, nB); L.blk = 256; L.lds = 0;
     P.push_back(L);
   };
-  // Linear / Conv1d on [C][T] activations (B = 1).  Returns the launch for epilogue tweaks.
+  // Linear / Conv1d on [C][T] activations: input lengths of kind kin, output lengths of kind kout; row strides are the span's
+  // extents, the plan is the plan row's own output length.  Returns the launch for epilogue tweaks.
   auto conv = [&](const std::string& name, const std::string& wname, const std::string& bname, int Cout, int Cin, int K, int dil, int pad,
-                  const float* X, int xstride, float* Y, const float* R, int ystride, int Tin, int Tout, int act, int istr) -> Launch& {
-    P.push_back(make_conv_w(name, ent(h, wname), bname.empty() ? nullptr : ent(h, bname), Cout, Cin, K, dil, 1, pad, X, xstride, 0, Y,
-                            nullptr, nullptr, R, ystride, 0, slot(Tin), 1, Tout, act, istr, Tin == Tout ? nullptr : slot(Tout),
-                            ent_is_bf(h, wname)));
+                  const float* X, int xstride, float* Y, const float* R, int ystride, int kin, int kout, int act, int istr) -> Launch& {
+    const PlanShape ps{0, 0, sp.plan.v[kout]};
+    const bool same = sp.rows ? kin == kout : E.v[kin] == E.v[kout];
+    P.push_back(make_conv_w(name, ent(h, wname), bname.empty() ? nullptr : ent(h, bname), Cout, Cin, K, dil, 1, pad, X, xstride, bs, Y,
+                            nullptr, nullptr, R, ystride, bs, len(kin), sp.B, E.v[kout], act, istr, same ? nullptr : len(kout),
+                            ent_is_bf(h, wname), sp.rows ? &ps : nullptr));
     return P.back();
   };
+  // attention of every row over its own kq queries and kk keys; the score rows in LDS are sized by the span's longest row
   auto mha = [&](const std::string& name, const float* Q, int qs, const float* K, int ks, const float* V, int vs, float* O, int os,
-                 int heads, int Tq, int Tk) {
-    MhaP m{Q, K, V, O, qs, ks, vs, os, Tq, Tk, 0.125f};
+                 int heads, int kq, int kk) {
+    MhaP m{Q, K, V, O, qs, ks, vs, os, 0, 0, 0.125f, len(kq), len(kk), bs};
+    const int Tq = E.v[kq], Tk = E.v[kk];
     const size_t lds = (size_t)(512 + 8 * Tk + 64 * 65) * 4;
     closure(name, 4.0 * heads * 64.0 * Tq * Tk, dim3((Tq + 7) / 8, heads), 256, lds, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
       hipLaunchKernelGGL(k_mha, g, b, l, s, m);
@@ -756,85 +852,98 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
 
   // ================= wav2vec2 =================
   float* wavn = B("wavn");
-  closure("w2v.normalize", 4.0 * n_samples, dim3(1), 1024, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-    hipLaunchKernelGGL(k_wavnorm, g, b, l, s, wav_dev, n_samples, wavn);
-  });
-  stage("input_values", wavn, 1, n_samples, n_samples);
+  {
+    const float* wav = sp.wav;
+    const long long wbs = sp.wav_bs;
+    const int* ns = len(LK_NS);
+    closure("w2v.normalize", 4.0 * n_samples, dim3(1), 1024, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+      hipLaunchKernelGGL(k_wavnorm, g, b, l, s, wav, wbs, ns, wavn, bs);
+    });
+  }
+  stage("input_values", wavn, 1, LK_NS, n_samples);
   const int CD = c.w2v_conv_dim;
   float* cf[2] = {B("cf0"), B("cf1")};
-  int cur = 0, Tc = Ts[0];
+  int cur = 0;
   {
     const float* W0 = ent(h, "w2v.feature_extractor.conv_layers.0.conv.weight");
     const float* b0 = ent(h, "w2v.feature_extractor.conv_layers.0.conv.bias");
     float* Y = cf[0];
-    const int K0 = c.w2v_kernel[0], S0 = c.w2v_stride[0], T0 = Ts[0];
+    const int K0 = c.w2v_kernel[0], S0 = c.w2v_stride[0], T0 = E.v[LK_T0];
+    const int* t0s = len(LK_T0);
     closure("w2v.conv0", 2.0 * CD * K0 * T0, dim3((T0 + 255) / 256, CD), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-      hipLaunchKernelGGL(k_conv0, g, b, l, s, wavn, W0, b0, K0, S0, Y, CD, T0, T0);
+      hipLaunchKernelGGL(k_conv0, g, b, l, s, wavn, W0, b0, K0, S0, Y, CD, t0s, T0, bs);
     });
-    lnorm("w2v.conv0.ln+gelu", "w2v.feature_extractor.conv_layers.0.layer_norm", nullptr, nullptr, cf[0], cf[1], CD, T0, T0, 1e-5f, 1, 0);
+    lnorm("w2v.conv0.ln+gelu", "w2v.feature_extractor.conv_layers.0.layer_norm", nullptr, nullptr, cf[0], cf[1], CD, LK_T0, 1e-5f, 1, 0);
     cur = 1;
   }
   for (int i = 1; i < c.w2v_nconv; ++i) {
     const std::string p = "w2v.feature_extractor.conv_layers." + std::to_string(i);
-    const int Tn = Ts[i];
+    const int Tc = E.v[LK_T0 + i - 1], Tn = E.v[LK_T0 + i];
     // conv reads cf[cur] (stride Tc), writes cf[1-cur] (stride Tn); LN + GELU back into cf[cur] with stride Tn
-    conv(p + ".conv", p + ".conv.weight", p + ".conv.bias", CD, CD, c.w2v_kernel[i], 1, 0, cf[cur], Tc, cf[1 - cur], nullptr, Tn, Tc, Tn,
-         ACT_NONE, c.w2v_stride[i]);
-    lnorm(p + ".ln+gelu", p + ".layer_norm", nullptr, nullptr, cf[1 - cur], cf[cur], CD, Tn, Tn, 1e-5f, 1, 0);
-    Tc = Tn;
+    conv(p + ".conv", p + ".conv.weight", p + ".conv.bias", CD, CD, c.w2v_kernel[i], 1, 0, cf[cur], Tc, cf[1 - cur], nullptr, Tn, LK_T0 + i - 1,
+         LK_T0 + i, ACT_NONE, c.w2v_stride[i]);
+    lnorm(p + ".ln+gelu", p + ".layer_norm", nullptr, nullptr, cf[1 - cur], cf[cur], CD, LK_T0 + i, 1e-5f, 1, 0);
   }
-  stage("conv_feats", cf[cur], CD, T, T);
+  stage("conv_feats", cf[cur], CD, kT, T);
   const int Hd = c.w2v_hidden, I = c.w2v_inter;
   float *hbuf = B("h"), *x = B("x"), *wide = B("wide"), *att = B("att"), *acc = B("acc"), *feat = B("feat");
-  lnorm("w2v.feature_projection.ln", "w2v.feature_projection.layer_norm", nullptr, nullptr, cf[cur], cf[1 - cur], CD, T, T, c.w2v_eps, 0, 0);
+  const int* Tlen = len(kT);
+  lnorm("w2v.feature_projection.ln", "w2v.feature_projection.layer_norm", nullptr, nullptr, cf[cur], cf[1 - cur], CD, kT, c.w2v_eps, 0, 0);
   conv("w2v.feature_projection.projection", "w2v.feature_projection.projection.weight", "w2v.feature_projection.projection.bias", Hd, CD, 1, 1,
-       0, cf[1 - cur], T, x, nullptr, T, T, T, ACT_NONE, 1);
+       0, cf[1 - cur], T, x, nullptr, T, kT, kT, ACT_NONE, 1);
   {
     const float* Wp = ent(h, "w2v.encoder.pos_conv_embed.conv.weight");
     const float* bp = ent(h, "w2v.encoder.pos_conv_embed.conv.bias");
     const int Cg = Hd / c.w2v_pos_groups, K = c.w2v_pos_k;
     const size_t lds = (size_t)Cg * (64 + K - 1) * 4;
     closure("w2v.pos_conv+gelu+res", 2.0 * Hd * Cg * K * T, dim3((T + 63) / 64, Hd / 16), 256, lds, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-      hipLaunchKernelGGL(k_posconv, g, b, l, s, x, Wp, bp, hbuf, Hd, Cg, K, T, T);
+      hipLaunchKernelGGL(k_posconv, g, b, l, s, x, Wp, bp, hbuf, Hd, Cg, K, Tlen, T, bs);
     });
   }
   {   // test view of hidden_states[0] (the residual stream is updated in place by the layers)
     float* d0 = B("dbg_hs0");
     closure("w2v.hs0(dbg copy)", 0.0, dim3((T + 255) / 256, Hd), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-      hipLaunchKernelGGL(k_copy2d, g, b, l, s, hbuf, T, d0, T, Hd, T);
+      hipLaunchKernelGGL(k_copy2d, g, b, l, s, hbuf, T, bs, d0, T, bs, Hd, Tlen);
     });
-    stage("hs0", d0, Hd, T, T);
+    stage("hs0", d0, Hd, kT, T);
   }
   const long long nHT = (long long)Hd * T;
+  const bool rows = sp.rows;
   auto tap = [&](int idx) {
     // hidden_states[idx] is the residual stream before layer idx
     for (int k = 0; k < 3; ++k) {
       if (c.w2v_taps[k] != idx) continue;
       const int mode = k;
-      closure("w2v.tap" + std::to_string(idx), 1.0 * nHT, dim3((unsigned)((nHT + 255) / 256)), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-        hipLaunchKernelGGL(k_tap, g, b, l, s, hbuf, acc, feat, nHT, mode);
-      });
+      // rows: a row's [Hd][T] block has the span's stride, so the kernel indexes by (channel, frame); solo: one flat array
+      if (rows)
+        closure("w2v.tap" + std::to_string(idx), 1.0 * nHT, dim3((T + 255) / 256, Hd), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+          hipLaunchKernelGGL(k_tap_rows, g, b, l, s, hbuf, acc, feat, Tlen, T, bs, mode);
+        });
+      else
+        closure("w2v.tap" + std::to_string(idx), 1.0 * nHT, dim3((unsigned)((nHT + 255) / 256)), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+          hipLaunchKernelGGL(k_tap, g, b, l, s, hbuf, acc, feat, nHT, mode);
+        });
     }
   };
   SMI_REQUIRE(c.w2v_taps[0] < c.w2v_taps[1] && c.w2v_taps[1] < c.w2v_taps[2], "smi_enc_forward: hidden-state taps must be increasing");
   tap(0);
   for (int l = 0; l < c.w2v_layers; ++l) {
     const std::string p = "w2v.encoder.layers." + std::to_string(l);
-    lnorm(p + ".ln1", p + ".layer_norm", nullptr, nullptr, hbuf, x, Hd, T, T, c.w2v_eps, 0, 0);
+    lnorm(p + ".ln1", p + ".layer_norm", nullptr, nullptr, hbuf, x, Hd, kT, c.w2v_eps, 0, 0);
     conv(p + ".qkv", "cat:" + p + ".attention.q_proj.weight|" + p + ".attention.k_proj.weight|" + p + ".attention.v_proj.weight",
          "cat:" + p + ".attention.q_proj.bias|" + p + ".attention.k_proj.bias|" + p + ".attention.v_proj.bias", 3 * Hd, Hd, 1, 1, 0, x, T,
-         wide, nullptr, T, T, T, ACT_NONE, 1);
-    mha(p + ".attention", wide, T, wide + (size_t)Hd * T, T, wide + (size_t)2 * Hd * T, T, att, T, c.w2v_heads, T, T);
-    conv(p + ".out_proj+res", p + ".attention.out_proj.weight", p + ".attention.out_proj.bias", Hd, Hd, 1, 1, 0, att, T, hbuf, hbuf, T, T, T,
+         wide, nullptr, T, kT, kT, ACT_NONE, 1);
+    mha(p + ".attention", wide, T, wide + (size_t)Hd * T, T, wide + (size_t)2 * Hd * T, T, att, T, c.w2v_heads, kT, kT);
+    conv(p + ".out_proj+res", p + ".attention.out_proj.weight", p + ".attention.out_proj.bias", Hd, Hd, 1, 1, 0, att, T, hbuf, hbuf, T, kT, kT,
          ACT_NONE, 1);
-    lnorm(p + ".ln2", p + ".final_layer_norm", nullptr, nullptr, hbuf, x, Hd, T, T, c.w2v_eps, 0, 0);
+    lnorm(p + ".ln2", p + ".final_layer_norm", nullptr, nullptr, hbuf, x, Hd, kT, c.w2v_eps, 0, 0);
     conv(p + ".ffn1+gelu", p + ".feed_forward.intermediate_dense.weight", p + ".feed_forward.intermediate_dense.bias", I, Hd, 1, 1, 0, x, T,
-         wide, nullptr, T, T, T, ACT_GELU, 1);
+         wide, nullptr, T, kT, kT, ACT_GELU, 1);
     conv(p + ".ffn2+res", p + ".feed_forward.output_dense.weight", p + ".feed_forward.output_dense.bias", Hd, I, 1, 1, 0, wide, T, hbuf, hbuf,
-         T, T, T, ACT_NONE, 1);
+         T, kT, kT, ACT_NONE, 1);
     tap(l + 1);
   }
-  stage("feat", feat, Hd, T, T);
+  stage("feat", feat, Hd, kT, T);
 
   // ================= BiCodec encoder + VQ (feat_encoder.py:76-87) =================
   {
@@ -844,28 +953,30 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     int cin = Hd;
     // Vocos backbone: embed conv7 -> LN -> nl x ConvNeXt -> final LN (vocos.py:324-335); result in e1 ([D][T])
     auto vocos = [&](const std::string& p, int nl, int triple_out) {
-      conv(p + ".embed", p + ".embed.weight", p + ".embed.bias", D, cin, 7, 1, 3, in, T, e0, nullptr, T, T, T, ACT_NONE, 1);
-      lnorm(p + ".norm", p + ".norm", nullptr, nullptr, e0, e2, D, T, T, 1e-6f, 0, 0);     // residual stream in e2
+      conv(p + ".embed", p + ".embed.weight", p + ".embed.bias", D, cin, 7, 1, 3, in, T, e0, nullptr, T, kT, kT, ACT_NONE, 1);
+      lnorm(p + ".norm", p + ".norm", nullptr, nullptr, e0, e2, D, kT, 1e-6f, 0, 0);     // residual stream in e2
       for (int j = 0; j < nl; ++j) {
         const std::string b = p + ".convnext." + std::to_string(j);
-        lnorm(b + ".dwconv+norm", b + ".norm", ent(h, b + ".dwconv.weight"), ent(h, b + ".dwconv.bias"), e2, e0, D, T, T, 1e-6f, 0, 0);
-        conv(b + ".pwconv1", b + ".pwconv1.weight", b + ".pwconv1.bias", EI, D, 1, 1, 0, e0, T, ew, nullptr, T, T, T, ACT_GELU, 1);
-        Launch& L = conv(b + ".pwconv2", b + ".pwconv2.weight", b + ".pwconv2.bias", D, EI, 1, 1, 0, ew, T, e2, e2, T, T, T, ACT_NONE, 1);
+        lnorm(b + ".dwconv+norm", b + ".norm", ent(h, b + ".dwconv.weight"), ent(h, b + ".dwconv.bias"), e2, e0, D, kT, 1e-6f, 0, 0);
+        conv(b + ".pwconv1", b + ".pwconv1.weight", b + ".pwconv1.bias", EI, D, 1, 1, 0, e0, T, ew, nullptr, T, kT, kT, ACT_GELU, 1);
+        Launch& L = conv(b + ".pwconv2", b + ".pwconv2.weight", b + ".pwconv2.bias", D, EI, 1, 1, 0, ew, T, e2, e2, T, kT, kT, ACT_NONE, 1);
         L.cp.gamma = ent(h, b + ".gamma");
       }
-      lnorm(p + ".final_layer_norm", p + ".final_layer_norm", nullptr, nullptr, e2, e1, D, T, T, 1e-6f, 0, triple_out);
+      lnorm(p + ".final_layer_norm", p + ".final_layer_norm", nullptr, nullptr, e2, e1, D, kT, 1e-6f, 0, triple_out);
       in = e1; cin = D;
     };
     vocos("encoder.encoder", c.enc_layers, c.enc_num_down > 0 ? 1 : 0);   // SamplingBlock(ratio 1) = 3x (samper.py:79-100)
     for (int i = 0; i < c.enc_num_down; ++i) vocos("encoder.downsample." + std::to_string(i) + ".1", 2, (i + 1 < c.enc_num_down) ? 1 : 0);
-    conv("encoder.project", "encoder.project.weight", "encoder.project.bias", c.enc_out, D, 1, 1, 0, e1, T, ew, nullptr, T, T, T, ACT_NONE, 1);
-    stage("z", ew, c.enc_out, T, T);
+    conv("encoder.project", "encoder.project.weight", "encoder.project.bias", c.enc_out, D, 1, 1, 0, e1, T, ew, nullptr, T, kT, kT, ACT_NONE, 1);
+    stage("z", ew, c.enc_out, kT, T);
     conv("quantizer.in_project", "quantizer.in_project.weight", "quantizer.in_project.bias", c.codebook_dim, c.enc_out, 1, 1, 0, ew, T, e0,
-         nullptr, T, T, T, ACT_NONE, 1);
+         nullptr, T, kT, kT, ACT_NONE, 1);
     const float *cbn = h->cbn, *c2 = h->c2;
     const int Dc = c.codebook_dim, nc = c.codebook_size;
+    int64_t* sem = sp.sem;
+    const long long sbs = sp.sem_bs;
     closure("quantizer.argmax", 2.0 * T * nc * Dc, dim3(T), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-      hipLaunchKernelGGL(k_vq, g, b, l, s, e0, Dc, T, T, cbn, c2, nc, sem_dev);
+      hipLaunchKernelGGL(k_vq, g, b, l, s, e0, Dc, Tlen, T, bs, cbn, c2, nc, sem, sbs);
     });
   }
 
@@ -873,22 +984,28 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
   {
     const int nf = c.n_fft / 2 + 1, nfft = c.n_fft, hop = c.hop_length;
     float *fr = B("frames"), *dft = B("dft"), *mag = B("mag"), *mel = B("mel");
-    closure("mel.frames", 1.0 * nfft * Tm, dim3((Tm + 255) / 256, nfft), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-      hipLaunchKernelGGL(k_frames, g, b, l, s, ref_dev, n_ref, nfft, hop, fr, Tm, Tm);
-    });
-    conv("mel.dft", "mel.dft", "", 2 * nf, nfft, 1, 1, 0, fr, Tm, dft, nullptr, Tm, Tm, Tm, ACT_NONE, 1);
+    const int* Tmlen = len(LK_TM);
+    {
+      const float* ref = sp.ref;
+      const long long rbs = sp.ref_bs;
+      const int* nrs = len(LK_NREF);
+      closure("mel.frames", 1.0 * nfft * Tm, dim3((Tm + 255) / 256, nfft), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+        hipLaunchKernelGGL(k_frames, g, b, l, s, ref, rbs, nrs, nfft, hop, fr, Tmlen, Tm, bs);
+      });
+    }
+    conv("mel.dft", "mel.dft", "", 2 * nf, nfft, 1, 1, 0, fr, Tm, dft, nullptr, Tm, LK_TM, LK_TM, ACT_NONE, 1);
     closure("mel.magnitude", 4.0 * nf * Tm, dim3((Tm + 255) / 256, nf), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-      hipLaunchKernelGGL(k_mag, g, b, l, s, dft, nf, Tm, Tm, mag);
+      hipLaunchKernelGGL(k_mag, g, b, l, s, dft, nf, Tmlen, Tm, mag, bs);
     });
-    conv("mel.filterbank", "mel.fb", "", c.num_mels, nf, 1, 1, 0, mag, Tm, mel, nullptr, Tm, Tm, Tm, ACT_NONE, 1);
-    stage("mel", mel, c.num_mels, Tm, Tm);
+    conv("mel.filterbank", "mel.fb", "", c.num_mels, nf, 1, 1, 0, mag, Tm, mel, nullptr, Tm, LK_TM, LK_TM, ACT_NONE, 1);
+    stage("mel", mel, c.num_mels, LK_TM, Tm);
     // ---- ECAPA-TDNN (ecapa_tdnn.py:186-197): bn(relu(conv(x))) fused as ReLU + affine in the conv epilogue
     const int C = c.ecapa_channels, W = C / 8;
     const std::string se = "speaker_encoder.speaker_encoder";
     float *ea = B("ec_a"), *eb = B("ec_b"), *ec = B("ec_c"), *ecat = B("ec_cat"), *elat = B("ec_lat"), *evec = B("ec_vec");
     auto crb = [&](const std::string& name, const std::string& p, int co, int ci, int k, int dil, int pad, const float* X, const float* X2,
                    float* Y) {
-      Launch& L = conv(name, p + ".conv.weight", p + ".conv.bias", co, ci, k, dil, pad, X, Tm, Y, nullptr, Tm, Tm, Tm, ACT_RELU, 1);
+      Launch& L = conv(name, p + ".conv.weight", p + ".conv.bias", co, ci, k, dil, pad, X, Tm, Y, nullptr, Tm, LK_TM, LK_TM, ACT_RELU, 1);
       L.cp.gamma = ent(h, "bnscale:" + p + ".bn"); L.cp.beta = ent(h, "bnshift:" + p + ".bn"); L.cp.X2 = X2;
     };
     crb(se + ".layer1", se + ".layer1", C, c.num_mels, 5, 1, 2, mel, nullptr, ea);
@@ -902,8 +1019,8 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
       for (int j = 0; j < 7; ++j) {
         const std::string cj = b + ".1.convs." + std::to_string(j);
         // sp = conv(out_{j-1} + spx[j]) -> relu -> bn  (ecapa_tdnn.py:50-58); branch j reads slice j of y0, writes slice j of y1
-        Launch& L = conv(cj, cj + ".weight", cj + ".bias", W, W, 3, dil, dil, y0 + (size_t)j * W * Tm, Tm, y1 + (size_t)j * W * Tm, nullptr, Tm, Tm,
-                         Tm, ACT_RELU, 1);
+        Launch& L = conv(cj, cj + ".weight", cj + ".bias", W, W, 3, dil, dil, y0 + (size_t)j * W * Tm, Tm, y1 + (size_t)j * W * Tm, nullptr, Tm,
+                         LK_TM, LK_TM, ACT_RELU, 1);
         L.cp.gamma = ent(h, "bnscale:" + b + ".1.bns." + std::to_string(j)); L.cp.beta = ent(h, "bnshift:" + b + ".1.bns." + std::to_string(j));
         if (j >= 1) L.cp.X2 = y1 + (size_t)(j - 1) * W * Tm;
       }
@@ -911,70 +1028,76 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
         const float* src = y0 + (size_t)7 * W * Tm;
         float* dst = y1 + (size_t)7 * W * Tm;
         closure(b + ".1.passthrough", 0.0, dim3((Tm + 255) / 256, W), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
-          hipLaunchKernelGGL(k_copy2d, g, bl, l, s, src, Tm, dst, Tm, W, Tm);
+          hipLaunchKernelGGL(k_copy2d, g, bl, l, s, src, Tm, bs, dst, Tm, bs, W, Tmlen);
         });
       }
       crb(b + ".2", b + ".2", C, C, 1, 1, 0, y1, nullptr, y0);
       float *mean = evec, *s1 = evec + C, *s2 = evec + C + 128;
       closure(b + ".3.mean", 1.0 * C * Tm, dim3((C + 3) / 4), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
-        hipLaunchKernelGGL(k_rowmean, g, bl, l, s, y0, C, Tm, Tm, mean);
+        hipLaunchKernelGGL(k_rowmean, g, bl, l, s, y0, C, Tmlen, Tm, mean, bs);
       });
-      const int* len1 = slot(1);
-      P.push_back(make_conv_w(b + ".3.linear1", ent(h, b + ".3.linear1.weight"), ent(h, b + ".3.linear1.bias"), 128, C, 1, 1, 1, 0, mean, 1, C, s1,
-                              nullptr, nullptr, nullptr, 1, 128, len1, 1, 1, ACT_RELU));
-      P.back().gemv = true; P.back().grid = dim3(4, 1);
-      P.push_back(make_conv_w(b + ".3.linear2", ent(h, b + ".3.linear2.weight"), ent(h, b + ".3.linear2.bias"), C, 128, 1, 1, 1, 0, s1, 1, 128, s2,
-                              nullptr, nullptr, nullptr, 1, C, len1, 1, 1, ACT_SIGMOID));
-      P.back().gemv = true; P.back().grid = dim3((C + 31) / 32, 1);
+      // the two vector projections: one vector per row (k_gemv1: block y is the row)
+      const int* len1 = len(LK_ONE);
+      const PlanShape ps1{0, 0, 1};
+      P.push_back(make_conv_w(b + ".3.linear1", ent(h, b + ".3.linear1.weight"), ent(h, b + ".3.linear1.bias"), 128, C, 1, 1, 1, 0, mean, 1,
+                              sp.rows ? bs : C, s1, nullptr, nullptr, nullptr, 1, sp.rows ? bs : 128, len1, sp.B, 1, ACT_RELU, 1, nullptr, false,
+                              sp.rows ? &ps1 : nullptr));
+      P.back().gemv = true; P.back().grid = dim3(4, nB);
+      P.push_back(make_conv_w(b + ".3.linear2", ent(h, b + ".3.linear2.weight"), ent(h, b + ".3.linear2.bias"), C, 128, 1, 1, 1, 0, s1, 1,
+                              sp.rows ? bs : 128, s2, nullptr, nullptr, nullptr, 1, sp.rows ? bs : C, len1, sp.B, 1, ACT_SIGMOID, 1, nullptr, false,
+                              sp.rows ? &ps1 : nullptr));
+      P.back().gemv = true; P.back().grid = dim3((C + 31) / 32, nB);
       float* outl = ecat + (size_t)(li - 2) * C * Tm;
       const float* xi = xin;
       closure(b + ".3.scale+res", 2.0 * C * Tm, dim3((Tm + 255) / 256, C), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
-        hipLaunchKernelGGL(k_se, g, bl, l, s, xi, y0, s2, outl, Tm, Tm, Tm);
+        hipLaunchKernelGGL(k_se, g, bl, l, s, xi, y0, s2, outl, Tmlen, Tm, Tm, bs);
       });
       xin = outl;
     }
-    conv(se + ".conv+relu", se + ".conv.weight", se + ".conv.bias", c.ecapa_out, 3 * C, 1, 1, 0, ecat, Tm, elat, nullptr, Tm, Tm, Tm, ACT_RELU, 1);
-    stage("ecapa_latent", elat, c.ecapa_out, Tm, Tm);
+    conv(se + ".conv+relu", se + ".conv.weight", se + ".conv.bias", c.ecapa_out, 3 * C, 1, 1, 0, ecat, Tm, elat, nullptr, Tm, LK_TM, LK_TM, ACT_RELU, 1);
+    stage("ecapa_latent", elat, c.ecapa_out, LK_TM, Tm);
     // ---- perceiver resampler (perceiver_encoder.py:297-350): ctx buffer = [latents | projected context] along time
     const std::string ps = "speaker_encoder.perceiver_sampler";
-    const int Ld = c.spk_latent, Nt = c.spk_tokens, Tk = Nt + Tm, inner = c.perc_heads * 64, FI = c.perc_ff_inner;
+    const int Ld = c.spk_latent, Nt = c.spk_tokens, Tk = E.v[LK_TK], inner = c.perc_heads * 64, FI = c.perc_ff_inner;
     float *ctx = B("pctx"), *pq = B("pq"), *pkv = B("pkv"), *po = B("po"), *pff = B("pff"), *pg = B("pg"), *pout = B("pout");
+    const int* Ntlen = len(LK_NT);
     {
       const float* lt = ent(h, "transpose:" + ps + ".latents");
       closure(ps + ".latents", 0.0, dim3((Nt + 255) / 256, Ld), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-        hipLaunchKernelGGL(k_copy2d, g, b, l, s, lt, Nt, ctx, Tk, Ld, Nt);
+        hipLaunchKernelGGL(k_copy2d, g, b, l, s, lt, Nt, 0LL, ctx, Tk, bs, Ld, Ntlen);
       });
     }
     conv(ps + ".proj_context", ps + ".proj_context.weight", ps + ".proj_context.bias", Ld, c.ecapa_out, 1, 1, 0, elat, Tm, ctx + Nt, nullptr, Tk,
-         Tm, Tm, ACT_NONE, 1);
+         LK_TM, LK_TM, ACT_NONE, 1);
     for (int i = 0; i < c.perc_depth; ++i) {
       const std::string a = ps + ".layers." + std::to_string(i) + ".0", f = ps + ".layers." + std::to_string(i) + ".1";
-      conv(a + ".to_q", a + ".to_q.weight", "", inner, Ld, 1, 1, 0, ctx, Tk, pq, nullptr, Nt, Nt, Nt, ACT_NONE, 1);
-      conv(a + ".to_kv", a + ".to_kv.weight", "", 2 * inner, Ld, 1, 1, 0, ctx, Tk, pkv, nullptr, Tk, Tk, Tk, ACT_NONE, 1);
-      mha(a + ".attend", pq, Nt, pkv, Tk, pkv + (size_t)inner * Tk, Tk, po, Nt, c.perc_heads, Nt, Tk);
-      conv(a + ".to_out+res", a + ".to_out.weight", "", Ld, inner, 1, 1, 0, po, Nt, ctx, ctx, Tk, Nt, Nt, ACT_NONE, 1);
-      conv(f + ".0", f + ".0.weight", f + ".0.bias", 2 * FI, Ld, 1, 1, 0, ctx, Tk, pff, nullptr, Nt, Nt, Nt, ACT_NONE, 1);
+      conv(a + ".to_q", a + ".to_q.weight", "", inner, Ld, 1, 1, 0, ctx, Tk, pq, nullptr, Nt, LK_NT, LK_NT, ACT_NONE, 1);
+      conv(a + ".to_kv", a + ".to_kv.weight", "", 2 * inner, Ld, 1, 1, 0, ctx, Tk, pkv, nullptr, Tk, LK_TK, LK_TK, ACT_NONE, 1);
+      mha(a + ".attend", pq, Nt, pkv, Tk, pkv + (size_t)inner * Tk, Tk, po, Nt, c.perc_heads, LK_NT, LK_TK);
+      conv(a + ".to_out+res", a + ".to_out.weight", "", Ld, inner, 1, 1, 0, po, Nt, ctx, ctx, Tk, LK_NT, LK_NT, ACT_NONE, 1);
+      conv(f + ".0", f + ".0.weight", f + ".0.bias", 2 * FI, Ld, 1, 1, 0, ctx, Tk, pff, nullptr, Nt, LK_NT, LK_NT, ACT_NONE, 1);
       closure(f + ".geglu", 10.0 * FI * Nt, dim3(1, FI), 64 * ((Nt + 63) / 64), 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-        hipLaunchKernelGGL(k_geglu, g, b, l, s, pff, FI, Nt, Nt, pg);
+        hipLaunchKernelGGL(k_geglu, g, b, l, s, pff, FI, Nt, Nt, pg, bs);
       });
-      conv(f + ".2+res", f + ".2.weight", f + ".2.bias", Ld, FI, 1, 1, 0, pg, Nt, ctx, ctx, Tk, Nt, Nt, ACT_NONE, 1);
+      conv(f + ".2+res", f + ".2.weight", f + ".2.bias", Ld, FI, 1, 1, 0, pg, Nt, ctx, ctx, Tk, LK_NT, LK_NT, ACT_NONE, 1);
     }
     {
       const float* gm = ent(h, ps + ".norm.gamma");
       closure(ps + ".norm", 4.0 * Ld * Nt, dim3((Nt + 63) / 64), 64, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-        hipLaunchKernelGGL(k_rmsn, g, b, l, s, ctx, Ld, Nt, Tk, gm, pout, Nt);
+        hipLaunchKernelGGL(k_rmsn, g, b, l, s, ctx, Ld, Nt, Tk, gm, pout, Nt, bs);
       });
     }
-    stage("perceiver", pout, Ld, Nt, Nt);
+    stage("perceiver", pout, Ld, -Nt, Nt);
     FsqQP q;
     memset(&q, 0, sizeof(q));
     q.X = pout; q.W = ent(h, "speaker_encoder.quantizer.project_in.weight"); q.b = ent(h, "speaker_encoder.quantizer.project_in.bias");
-    q.out = glob_dev; q.bounded = B("fsqb"); q.latent = Ld; q.stride = Nt; q.Ntok = Nt; q.nd = c.fsq_dims;
+    q.out = sp.glob; q.bounded = B("fsqb"); q.latent = Ld; q.stride = Nt; q.Ntok = Nt; q.nd = c.fsq_dims;
+    q.bs = bs; q.obs = sp.glob_bs;
     for (int j = 0; j < 8; ++j) q.levels[j] = j < c.fsq_dims ? c.fsq_levels[j] : 1;
     closure("speaker_encoder.quantizer", 2.0 * Nt * Ld * c.fsq_dims, dim3((Nt + 63) / 64), 64, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
       hipLaunchKernelGGL(k_fsq_quant, g, b, l, s, q);
     });
-    stage("fsq_bounded", B("fsqb"), Nt, c.fsq_dims, c.fsq_dims);
+    stage("fsq_bounded", B("fsqb"), Nt, -c.fsq_dims, c.fsq_dims);
   }
 
   SMI_REQUIRE(hl.size() <= 64, "smi_enc_forward: too many distinct lengths");
@@ -986,7 +1109,35 @@ int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_
     }
     if (L.kind == 1) SMI_REQUIRE(L.lp.w && L.lp.bsh && L.cpt <= 32, "smi_enc_forward: LayerNorm %s: missing weights or too many channels", L.name.c_str());
   }
-  *n_frames = T;
+  return SMI_OK;
+}
+
+// smi_enc_forward's argument checks on one row's lengths
+int enc_check_row(const smi_enc_cfg& c, const char* who, int n_samples, int n_ref, int max_samples, int max_ref) {
+  SMI_REQUIRE(n_samples >= 400 && n_samples <= max_samples, "%s: n_samples=%d outside 400..%d", who, n_samples, max_samples);
+  SMI_REQUIRE(n_ref > c.n_fft / 2 && n_ref <= max_ref, "%s: n_ref=%d outside %d..%d", who, n_ref, c.n_fft / 2 + 1, max_ref);
+  const RowLens r = row_lens(c, n_samples, n_ref);
+  const int T = r.v[LK_T0 + c.w2v_nconv - 1];
+  SMI_REQUIRE(T >= 2, "%s: %d samples give %d frames", who, n_samples, T);
+  SMI_REQUIRE(T <= kMaxKeys, "%s: %d frames exceed the attention kernel's %d-key score buffer", who, T, kMaxKeys);
+  SMI_REQUIRE(r.v[LK_TK] <= kMaxKeys, "%s: %d speaker tokens + %d mel frames exceed the attention kernel's %d-key score buffer", who,
+              c.spk_tokens, r.v[LK_TM], kMaxKeys);
+  return SMI_OK;
+}
+
+// The launch sequence of one solo encode (h->prog), its length slots (h->host_lens) and debug views (h->stages); nothing runs here.
+int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_dev, int n_ref, int64_t* sem_dev, int32_t* glob_dev,
+              int* n_frames) {
+  const smi_enc_cfg& c = h->cfg;
+  h->prog.clear();
+  h->stages.clear();
+  h->host_lens.clear();
+  int rc = enc_check_row(c, "smi_enc_forward", n_samples, n_ref, c.max_samples, c.max_ref_samples);
+  if (rc) return rc;
+  const RowLens own = row_lens(c, n_samples, n_ref);
+  const EncSpan sp{false, 0, 1, own, own, &own, wav_dev, 0, ref_dev, 0, sem_dev, 0, glob_dev, 0};
+  if ((rc = enc_program(h, sp, h->prog, h->host_lens, &h->stages))) return rc;
+  *n_frames = own.v[LK_T0 + c.w2v_nconv - 1];
   return SMI_OK;
 }
 
@@ -1086,6 +1237,126 @@ int smi_enc_forward(smi_enc* h, const float* wav_dev, int n_samples, const float
   return SMI_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The rows launch list (h->rows.prog, .run_start, .stages, .host_lens) of B rows; nothing runs and nothing of the solo path is
+// touched.  A row's plan is the signature of the list smi_enc_forward builds for it alone; consecutive rows with equal plans form
+// a run: one launch sequence with the first row's plan and the extent (rows of the run, its longest row of every length kind).
+int enc_rows_build(smi_enc* h, const char* who, const float* wav, long long wav_bs, const int32_t* ns, const float* ref, long long ref_bs,
+                   const int32_t* nref, int B, int64_t* sem, long long sem_bs, int32_t* glob, long long glob_bs, int32_t* n_frames) {
+  const smi_enc_cfg& c = h->cfg;
+  smi_enc::Rows& R = h->rows;
+  R.prog.clear(); R.run_start.clear(); R.stages.clear(); R.lastB = 0;
+  SMI_REQUIRE(R.ws, "%s: no rows workspace (smi_enc_rows_reserve first)", who);
+  SMI_REQUIRE(B >= 1 && B <= R.max_rows, "%s: B=%d outside the reserved 1..%d rows", who, B, R.max_rows);
+  int rc;
+  for (int b = 0; b < B; ++b)
+    if ((rc = enc_check_row(c, who, ns[b], nref[b], R.max_samples, R.max_ref))) return rc;
+  const int kT = LK_T0 + c.w2v_nconv - 1;
+  std::vector<RowLens> own((size_t)B);
+  std::vector<const std::vector<long long>*> sig((size_t)B);
+  if (R.sigs.size() > 1024) R.sigs.clear();   // (before the first lookup: the pointers below stay valid across insertions)
+  for (int b = 0; b < B; ++b) {
+    own[b] = row_lens(c, ns[b], nref[b]);
+    const std::pair<int, int> key(ns[b], nref[b]);
+    auto it = R.sigs.find(key);
+    if (it == R.sigs.end()) {
+      // the choices of that row's own smi_enc_forward (pointers do not enter a signature)
+      std::vector<Launch> solo;
+      std::vector<int32_t> hl;
+      const EncSpan sp{false, 0, 1, own[b], own[b], &own[b], wav, 0, ref, 0, sem, 0, glob, 0};
+      if ((rc = enc_program(h, sp, solo, hl, nullptr))) return rc;
+      it = R.sigs.emplace(key, plan_signature(solo)).first;
+    }
+    sig[b] = &it->second;
+  }
+  R.stages.resize((size_t)B);
+  R.host_lens.assign((size_t)LK_COUNT * R.max_rows, 0);
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < LK_COUNT; ++k) R.host_lens[(size_t)k * R.max_rows + b] = own[b].v[k];
+  std::vector<Launch> G;
+  std::vector<int32_t> none;
+  for (int r0 = 0; r0 < B;) {
+    int r1 = r0 + 1, mns = ns[r0], mref = nref[r0];
+    for (; r1 < B && *sig[r1] == *sig[r0]; ++r1) {
+      mns = ns[r1] > mns ? ns[r1] : mns;
+      mref = nref[r1] > mref ? nref[r1] : mref;
+    }
+    // (every length kind grows with its input, so the longest row of each kind is that of the longest wav / reference clip)
+    const EncSpan sp{true, r0, r1 - r0, row_lens(c, mns, mref), own[r0], &own[r0], wav + r0 * wav_bs, wav_bs, ref + r0 * ref_bs, ref_bs,
+                     sem + r0 * sem_bs, sem_bs, glob + r0 * glob_bs, glob_bs};
+    G.clear();
+    if ((rc = enc_program(h, sp, G, none, &R.stages[r0]))) { R.prog.clear(); return rc; }
+    if (plan_signature(G) != *sig[r0]) {
+      R.prog.clear();
+      smi_set_error("%s: the launch list of rows %d..%d does not carry the plan of a row of %d samples / %d reference samples", who, r0, r1 - 1,
+                    ns[r0], nref[r0]);
+      return SMI_EINVAL;
+    }
+    R.run_start.push_back(r0);
+    R.prog.insert(R.prog.end(), G.begin(), G.end());
+    r0 = r1;
+  }
+  for (int b = 0; b < B; ++b) n_frames[b] = own[b].v[kT];
+  R.lastB = B;
+  return SMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smi_enc_rows_reserve(smi_enc* h, int max_rows, int max_row_samples, int max_row_ref_samples) {
+  SMI_REQUIRE(h, "smi_enc_rows_reserve: null handle");
+  const smi_enc_cfg& c = h->cfg;
+  SMI_REQUIRE(max_rows >= 1 && max_rows <= 4096, "smi_enc_rows_reserve: max_rows=%d outside 1..4096", max_rows);
+  SMI_REQUIRE(max_row_samples >= 400 && max_row_samples <= c.max_samples, "smi_enc_rows_reserve: max_row_samples=%d outside 400..%d",
+              max_row_samples, c.max_samples);
+  SMI_REQUIRE(max_row_ref_samples > c.n_fft / 2 && max_row_ref_samples <= c.max_ref_samples,
+              "smi_enc_rows_reserve: max_row_ref_samples=%d outside %d..%d", max_row_ref_samples, c.n_fft / 2 + 1, c.max_ref_samples);
+  smi_enc::Rows& R = h->rows;
+  if (R.ws && R.max_rows == max_rows && R.max_samples == max_row_samples && R.max_ref == max_row_ref_samples) return SMI_OK;
+  SMI_HIP(hipDeviceSynchronize());      // a rows call may still be reading the workspace that goes
+  if (R.ws) (void)hipFree(R.ws);
+  if (R.lens_dev) (void)hipFree(R.lens_dev);
+  R.ws = nullptr; R.lens_dev = nullptr; R.max_rows = 0;
+  R.prog.clear(); R.run_start.clear(); R.stages.clear(); R.lastB = 0;
+  R.floats = enc_buffers(c, max_row_samples, max_row_ref_samples);
+  R.off.clear();
+  size_t o = 0;
+  for (const auto& kv : R.floats) { R.off[kv.first] = o; o += smi_align_up(kv.second, 64); }
+  R.slab = (long long)o;
+  if (hipMalloc((void**)&R.ws, (size_t)max_rows * o * 4) != hipSuccess ||
+      hipMalloc((void**)&R.lens_dev, (size_t)LK_COUNT * max_rows * 4) != hipSuccess) {
+    if (R.ws) (void)hipFree(R.ws);
+    R.ws = nullptr; R.lens_dev = nullptr;
+    smi_set_error("smi_enc_rows_reserve: device allocation of %d rows x %zu bytes failed", max_rows, o * 4);
+    return SMI_EHIP;
+  }
+  R.max_rows = max_rows; R.max_samples = max_row_samples; R.max_ref = max_row_ref_samples;
+  return SMI_OK;
+}
+
+int smi_enc_forward_rows(smi_enc* h, const float* wav_dev, long long wav_stride, const int32_t* n_samples_host, const float* ref_dev,
+                         long long ref_stride, const int32_t* n_ref_host, int B, int64_t* sem_dev, long long sem_stride, int32_t* glob_dev,
+                         int32_t* n_frames_host, void* stream) {
+  SMI_REQUIRE(h && wav_dev && n_samples_host && ref_dev && n_ref_host && sem_dev && glob_dev && n_frames_host,
+              "smi_enc_forward_rows: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = enc_rows_build(h, "smi_enc_forward_rows", wav_dev, wav_stride, n_samples_host, ref_dev, ref_stride, n_ref_host, B, sem_dev, sem_stride,
+                          glob_dev, h->cfg.spk_tokens, n_frames_host);
+  if (rc) return rc;
+  for (int b = 0; b < B; ++b) {
+    SMI_REQUIRE(wav_stride >= n_samples_host[b] && ref_stride >= n_ref_host[b] && sem_stride >= n_frames_host[b],
+                "smi_enc_forward_rows: row %d (%d samples, %d reference samples, %d frames) exceeds a row stride", b, n_samples_host[b],
+                n_ref_host[b], n_frames_host[b]);
+  }
+  SMI_HIP(hipMemcpyAsync(h->rows.lens_dev, h->rows.host_lens.data(), h->rows.host_lens.size() * 4, hipMemcpyHostToDevice, st));
+  return enc_run(h->rows.prog, st);
+}
+
 int smi_enc_debug_stage(smi_enc* h, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream) {
   SMI_REQUIRE(h && name && out_dev && dims, "smi_enc_debug_stage: null argument");
   SMI_REQUIRE(h->last_frames > 0, "smi_enc_debug_stage: no forward has run");
@@ -1156,6 +1427,89 @@ int smi_enc_debug_run(smi_enc* h, int first, int last, void* stream) {
     if (rc) return rc;
   }
   SMI_HIP(hipStreamSynchronize(st));
+  return SMI_OK;
+}
+
+// ---- the rows list (smi_enc_forward_rows) the same way
+int smi_enc_rows_debug_build(smi_enc* h, const int32_t* n_samples, const int32_t* n_ref, int B, int32_t* n_frames, int* n_launches,
+                             int32_t* run_start, int run_cap, int* n_runs, void* stream) {
+  SMI_REQUIRE(h && n_samples && n_ref && n_frames && n_launches && n_runs, "smi_enc_rows_debug_build: null argument");
+  smi_enc::Rows& R = h->rows;
+  SMI_REQUIRE(R.ws, "smi_enc_rows_debug_build: no rows workspace (smi_enc_rows_reserve first)");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = enc_rows_build(h, "smi_enc_rows_debug_build", R.ws + R.off.at("in_wav"), R.slab, n_samples, R.ws + R.off.at("in_ref"), R.slab, n_ref, B,
+                          (int64_t*)(R.ws + R.off.at("out_sem")), R.slab / 2, (int32_t*)(R.ws + R.off.at("out_glob")), R.slab, n_frames);
+  if (rc) return rc;
+  SMI_HIP(hipMemcpyAsync(R.lens_dev, R.host_lens.data(), R.host_lens.size() * 4, hipMemcpyHostToDevice, st));
+  SMI_HIP(hipStreamSynchronize(st));
+  *n_launches = (int)R.prog.size();
+  *n_runs = (int)R.run_start.size();
+  for (int i = 0; run_start && i < run_cap && i < (int)R.run_start.size(); ++i) run_start[i] = R.run_start[i];
+  return SMI_OK;
+}
+
+int smi_enc_rows_debug_runs(smi_enc* h, int32_t* run_start, int run_cap, int* n_runs, int* n_launches) {
+  SMI_REQUIRE(h && n_runs && n_launches, "smi_enc_rows_debug_runs: null argument");
+  *n_runs = (int)h->rows.run_start.size();
+  *n_launches = (int)h->rows.prog.size();
+  for (int i = 0; run_start && i < run_cap && i < *n_runs; ++i) run_start[i] = h->rows.run_start[i];
+  return SMI_OK;
+}
+
+int smi_enc_rows_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* info) {
+  SMI_REQUIRE(h && info, "smi_enc_rows_debug_launch: null argument");
+  SMI_REQUIRE(index >= 0 && index < (int)h->rows.prog.size(), "smi_enc_rows_debug_launch: index %d out of range", index);
+  const Launch& L = h->rows.prog[index];
+  if (name && cap > 0) { strncpy(name, L.name.c_str(), (size_t)cap - 1); name[cap - 1] = 0; }
+  info[0] = L.kind; info[1] = (int32_t)L.grid.x; info[2] = (int32_t)L.grid.y; info[3] = (int32_t)L.grid.z;
+  info[4] = L.kind == 0 ? 64 * L.nwv : L.blk;
+  info[5] = (int32_t)L.lds;
+  info[6] = L.kind == 1 ? dwln_form(L.cpt) : 0;
+  info[7] = 0;
+  return SMI_OK;
+}
+
+int smi_enc_rows_debug_io(smi_enc* h, int row, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats) {
+  SMI_REQUIRE(h && buffer_name && host_ptr, "smi_enc_rows_debug_io: null argument");
+  smi_enc::Rows& R = h->rows;
+  SMI_REQUIRE(R.ws, "smi_enc_rows_debug_io: no rows workspace (smi_enc_rows_reserve first)");
+  SMI_REQUIRE(row >= 0 && row < R.max_rows, "smi_enc_rows_debug_io: row %d outside the reserved 0..%d", row, R.max_rows - 1);
+  auto it = R.floats.find(buffer_name);
+  SMI_REQUIRE(it != R.floats.end(), "smi_enc_rows_debug_io: unknown buffer '%s'", buffer_name);
+  const size_t have = it->second;
+  SMI_REQUIRE(offset_floats <= have && floats <= have - offset_floats, "smi_enc_rows_debug_io: %zu floats at %zu outside '%s' (%zu floats a row)",
+              floats, offset_floats, buffer_name, have);
+  float* p = R.ws + (long long)row * R.slab + R.off.at(buffer_name) + offset_floats;
+  SMI_HIP(hipDeviceSynchronize());
+  if (write) SMI_HIP(hipMemcpy(p, host_ptr, floats * 4, hipMemcpyHostToDevice));
+  else SMI_HIP(hipMemcpy(host_ptr, p, floats * 4, hipMemcpyDeviceToHost));
+  return SMI_OK;
+}
+
+int smi_enc_rows_debug_run(smi_enc* h, int first, int last, void* stream) {
+  SMI_REQUIRE(h, "smi_enc_rows_debug_run: null handle");
+  SMI_REQUIRE(first >= 0 && first <= last && last < (int)h->rows.prog.size(), "smi_enc_rows_debug_run: launches %d..%d outside 0..%d", first, last,
+              (int)h->rows.prog.size() - 1);
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = first; i <= last; ++i) {
+    const int rc = run_launch(h->rows.prog[i], st);
+    if (rc) return rc;
+  }
+  SMI_HIP(hipStreamSynchronize(st));
+  return SMI_OK;
+}
+
+int smi_enc_rows_debug_stage(smi_enc* h, int row, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream) {
+  SMI_REQUIRE(h && name && out_dev && dims, "smi_enc_rows_debug_stage: null argument");
+  SMI_REQUIRE(row >= 0 && row < h->rows.lastB && row < (int)h->rows.stages.size(), "smi_enc_rows_debug_stage: row %d outside the last rows call (%d rows)",
+              row, h->rows.lastB);
+  auto it = h->rows.stages[row].find(name);
+  SMI_REQUIRE(it != h->rows.stages[row].end(), "smi_enc_rows_debug_stage: unknown stage '%s'", name);
+  const smi_enc::Stage& s = it->second;
+  SMI_REQUIRE((size_t)s.rows * s.cols <= max_floats, "smi_enc_rows_debug_stage: output buffer too small");
+  SMI_HIP(hipMemcpy2DAsync(out_dev, (size_t)s.cols * 4, s.ptr, (size_t)s.stride * 4, (size_t)s.cols * 4, s.rows, hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream));
+  dims[0] = s.rows; dims[1] = s.cols;
   return SMI_OK;
 }
 

@@ -1459,10 +1459,13 @@ int run_launch(const Launch& L, hipStream_t st) {
 
 // The shape a launch plan is chosen for where that is not the call's own (smi_voc_forward_rows): ONE row of `frames` frames, in a
 // call whose grids cover rows of up to `ext_frames` frames.  A layer that works at Lmax = up * ext_frames positions plans for
-// up * frames (the per-utterance vector projections, Lmax = 1, for 1).
+// up * frames (the per-utterance vector projections, Lmax = 1, for 1).  Where a layer's length is no multiple of a frame count (the
+// prompt encoder: the strided convs' output lengths, mel frames, perceiver keys) the builder names the plan row's length of that
+// very layer in plan_len, and nothing is derived.
 struct PlanShape {
   int frames, ext_frames;
-  int len(int Lmax) const { return Lmax % ext_frames == 0 ? Lmax / ext_frames * frames : Lmax; }
+  int plan_len = 0;     // > 0: the plan row's length at this launch, as given
+  int len(int Lmax) const { return plan_len > 0 ? plan_len : (Lmax % ext_frames == 0 ? Lmax / ext_frames * frames : Lmax); }
 };
 
 // Build one conv launch.  X/Y strides are in floats; Lmax = padded INPUT length (time units).  The call shape (B, Lmax) plays two
@@ -1560,6 +1563,25 @@ Launch make_conv_w(const std::string& name, const float* W, const float* bias,
   for (int r = 0; r < S; ++r) taps += g.ntaps[r];
   L.flops = 2.0 * Cout * Cin * taps * Lmax * B;   // all phases together cover S*Lmax outputs
   return L;
+}
+
+// Every choice a launch list makes from its plan shape, launch by launch: two rows may share a launch sequence when these agree.
+std::vector<long long> plan_signature(const std::vector<Launch>& P) {
+  std::vector<long long> sig;
+  for (const Launch& L : P) {
+    sig.push_back(L.kind);
+    if (L.kind == 0) {
+      const bool mfma = !L.gemv && !L.c1;   // (the vector projections and the one-channel conv size their grids from the extent alone)
+      for (long long v : {(long long)L.qb, (long long)L.ks, (long long)L.chg, (long long)L.nwv, (long long)L.tph, (long long)L.gemv, (long long)L.c1,
+                          (long long)L.bf, (long long)L.cp.xw, (long long)L.lds, (long long)(mfma ? L.grid.y : 0), (long long)(mfma && plan_grid_blocks(L) <= 512)})
+        sig.push_back(v);
+    } else if (L.kind == 5) {
+      for (long long v : {(long long)L.res_nwv, (long long)L.rp.xw, (long long)L.lds}) sig.push_back(v);
+    } else if (L.kind == 1) {
+      sig.push_back(L.cpt);
+    }
+  }
+  return sig;
 }
 
 }  // namespace

@@ -619,25 +619,6 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
   return SMI_OK;
 }
 
-// Every choice a launch list makes from its plan shape, launch by launch: two rows may share a launch sequence when these agree.
-std::vector<long long> plan_signature(const std::vector<Launch>& P) {
-  std::vector<long long> sig;
-  for (const Launch& L : P) {
-    sig.push_back(L.kind);
-    if (L.kind == 0) {
-      const bool mfma = !L.gemv && !L.c1;   // (the vector projections and the one-channel conv size their grids from the extent alone)
-      for (long long v : {(long long)L.qb, (long long)L.ks, (long long)L.chg, (long long)L.nwv, (long long)L.tph, (long long)L.gemv, (long long)L.c1,
-                          (long long)L.bf, (long long)L.cp.xw, (long long)L.lds, (long long)(mfma ? L.grid.y : 0), (long long)(mfma && plan_grid_blocks(L) <= 512)})
-        sig.push_back(v);
-    } else if (L.kind == 5) {
-      for (long long v : {(long long)L.res_nwv, (long long)L.rp.xw, (long long)L.lds}) sig.push_back(v);
-    } else if (L.kind == 1) {
-      sig.push_back(L.cpt);
-    }
-  }
-  return sig;
-}
-
 }  // namespace
 
 extern "C" {

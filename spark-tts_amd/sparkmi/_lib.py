@@ -200,6 +200,9 @@ SYMBOLS = {
     "smi_enc_create": (_I, [_P(EncCfg), _VP, _SZ, _P(_VP)]),
     "smi_enc_destroy": (_I, [_VP]),
     "smi_enc_forward": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _P(_I), _VP]),
+    "smi_enc_rows_reserve": (_I, [_VP, _I, _I, _I]),
+    "smi_enc_forward_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _VP, C.c_longlong, _P(C.c_int32), _I, _VP, C.c_longlong, _VP,
+                                  _P(C.c_int32), _VP]),
     "smi_enc_debug_stage": (_I, [_VP, C.c_char_p, _VP, _SZ, _P(C.c_int32), _VP]),
     "smi_enc_num_launches": (_I, [_VP]),
     "smi_enc_time_launch": (_I, [_VP, _I, _I, _P(C.c_float), _P(C.c_double), C.c_char_p, _I, _VP]),
@@ -238,6 +241,12 @@ DEBUG_SYMBOLS = {
     "smi_enc_debug_launch": (_I, [_VP, _I, C.c_char_p, _I, _P(C.c_int32)]),
     "smi_enc_debug_io": (_I, [_VP, C.c_char_p, _I, _VP, _SZ, _SZ]),
     "smi_enc_debug_run": (_I, [_VP, _I, _I, _VP]),
+    "smi_enc_rows_debug_build": (_I, [_VP, _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int32), _P(_I), _P(C.c_int32), _I, _P(_I), _VP]),
+    "smi_enc_rows_debug_runs": (_I, [_VP, _P(C.c_int32), _I, _P(_I), _P(_I)]),
+    "smi_enc_rows_debug_launch": (_I, [_VP, _I, C.c_char_p, _I, _P(C.c_int32)]),
+    "smi_enc_rows_debug_io": (_I, [_VP, _I, C.c_char_p, _I, _VP, _SZ, _SZ]),
+    "smi_enc_rows_debug_run": (_I, [_VP, _I, _I, _VP]),
+    "smi_enc_rows_debug_stage": (_I, [_VP, _I, C.c_char_p, _VP, _SZ, _P(C.c_int32), _VP]),
 }
 
 DIAG_PATH = LIB_PATH.with_name("libsparkmi_diag.so")

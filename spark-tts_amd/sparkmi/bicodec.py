@@ -476,6 +476,11 @@ class BiCodecTokenizer:
         wavs, refs = zip(*[self.process_audio(p) for p in audio_paths])
         return self._encoder().tokenize_many(list(wavs), [r.numpy() for r in refs])
 
+    def tokenize_rows(self, audio_paths: Sequence[str]):
+        """``tokenize_many``'s result from ONE ragged call on one handle (``BiCodecEncoder.tokenize_rows``): the same ids, bit for bit."""
+        wavs, refs = zip(*[self.process_audio(p) for p in audio_paths])
+        return self._encoder().tokenize_rows(list(wavs), [r.numpy() for r in refs])
+
     def detokenize(self, global_tokens: torch.Tensor, semantic_tokens: torch.Tensor) -> np.ndarray:
         """(B, Ntok) global ids, (B, T) semantic ids -> waveform: (hop*T,) for B == 1 else (B, hop*T)."""
         global_tokens = global_tokens.unsqueeze(1)

@@ -200,6 +200,42 @@ def pack_enc_arena(t: TokCfg, w2v_state: Mapping[str, np.ndarray], tok_state_fol
     return arena
 
 
+# --------------------------------------------------------------------------- row planning of tokenize_rows (host, no device)
+def plan_rows(wcfg: Wav2Vec2Cfg, n_samples: Sequence[int], n_ref: Sequence[int]) -> dict:
+    """How ``tokenize_rows`` lays a ragged batch out: ``order[j]`` = the caller's index of the j-th row of the call (rows sorted
+    by (samples, reference samples), stably, so that rows of equal launch plans sit next to each other); the sorted lengths; the
+    frame count of every sorted row; the row strides of the padded tensors; ``inverse[i]`` = the row of the caller's prompt i."""
+    if len(n_samples) != len(n_ref) or not len(n_samples):
+        raise ValueError("tokenize_rows: one reference clip per prompt, at least one prompt")
+    order = sorted(range(len(n_samples)), key=lambda i: (int(n_samples[i]), int(n_ref[i])))
+    ns = [int(n_samples[i]) for i in order]
+    nr = [int(n_ref[i]) for i in order]
+    frames = [wcfg.frames(n) for n in ns]
+    inverse = [0] * len(order)
+    for j, i in enumerate(order):
+        inverse[i] = j
+    return dict(order=order, inverse=inverse, n_samples=ns, n_ref=nr, frames=frames,
+                wav_stride=max(ns), ref_stride=max(nr), sem_stride=max(max(frames), 1))
+
+
+def pack_rows(arrays: Sequence[np.ndarray], order: Sequence[int], stride: int) -> np.ndarray:
+    """[rows][stride] float32, row j = arrays[order[j]] followed by zeros"""
+    out = np.zeros((len(order), stride), dtype=np.float32)
+    for j, i in enumerate(order):
+        a = np.asarray(arrays[i], dtype=np.float32).reshape(-1)
+        out[j, : a.size] = a
+    return out
+
+
+def grow_reservation(cur: Optional[Tuple[int, int, int]], need: Tuple[int, int, int]) -> Optional[Tuple[int, int, int]]:
+    """The rows workspace as (rows, samples a row, reference samples a row).  None: the call fits the current reservation and
+    nothing is re-allocated; else the new reservation -- in every dimension the larger of the current one and the call's need,
+    so a reservation never shrinks and a mix of call shapes settles after a few calls."""
+    if cur is not None and all(n <= c for n, c in zip(need, cur)):
+        return None
+    return tuple(need) if cur is None else tuple(max(n, c) for n, c in zip(need, cur))
+
+
 class BiCodecEncoder:
     """wav (+ reference clip) -> (global ids (1, 1, Ntok) int32, semantic ids (1, T) int64) on one MI355X."""
 
@@ -292,6 +328,49 @@ class BiCodecEncoder:
             cur.wait_event(ev)
         return out
 
+    # ---- smi_enc_forward_rows: a ragged batch in one launch sequence per run of equal plans
+    def _rows_reserve(self, rows: int, samples: int, ref: int) -> None:
+        self._lib.check(self._lib.smi_enc_rows_reserve(self._h, int(rows), int(samples), int(ref)), "smi_enc_rows_reserve")
+
+    def _rows_forward(self, wav: np.ndarray, n_samples: Sequence[int], ref: np.ndarray, n_ref: Sequence[int], sem_stride: int):
+        """The device call on packed [B][stride] host arrays: (sem [B][sem_stride] int64, glob [B][Ntok] int32, frames)."""
+        B = len(n_samples)
+        w = torch.from_numpy(wav).to(self.device)
+        r = torch.from_numpy(ref).to(self.device)
+        sem = torch.empty((B, sem_stride), dtype=torch.int64, device=self.device)
+        glob = torch.empty((B, self.tcfg.spk_token_num), dtype=torch.int32, device=self.device)
+        ns, nr, nf = (C.c_int32 * B)(*n_samples), (C.c_int32 * B)(*n_ref), (C.c_int32 * B)()
+        self._lib.check(self._lib.smi_enc_forward_rows(self._h, C.c_void_p(w.data_ptr()), wav.shape[1], ns, C.c_void_p(r.data_ptr()), ref.shape[1],
+                                                       nr, B, C.c_void_p(sem.data_ptr()), sem_stride, C.c_void_p(glob.data_ptr()), nf,
+                                                       self._stream()), "smi_enc_forward_rows")
+        return sem, glob, list(nf)
+
+    @torch.no_grad()
+    def tokenize_rows(self, wavs: Sequence[np.ndarray], refs: Sequence[np.ndarray]):
+        """Several prompts in ONE call (smi_enc_forward_rows): the ids of every prompt are, bit for bit, those of
+        ``tokenize_arrays`` of that prompt alone.  The rows are sorted by length (rows of equal launch plans then share a launch
+        sequence), packed into one padded tensor each, and the result is handed back in the caller's order as
+        [(global (1, 1, Ntok) int32, semantic (1, T) int64)], like ``tokenize_many``.  The rows workspace is reserved on the
+        first call and re-reserved only when a call exceeds it (``grow_reservation``)."""
+        ns = [int(np.asarray(w).size) for w in wavs]
+        nr = [int(np.asarray(r).size) for r in refs]
+        for n in ns:
+            if n > self.max_samples:
+                raise ValueError(f"prompt of {n} samples exceeds max_samples={self.max_samples}")
+        for n in nr:
+            if n > self.max_ref:
+                raise ValueError(f"reference clip of {n} samples exceeds max_ref_samples={self.max_ref}")
+        plan = plan_rows(self.wcfg, ns, nr)
+        new = grow_reservation(getattr(self, "_rows_reserved", None), (len(ns), plan["wav_stride"], plan["ref_stride"]))
+        if new is not None:
+            self._rows_reserve(*new)
+            self._rows_reserved = new
+        sem, glob, frames = self._rows_forward(pack_rows(wavs, plan["order"], plan["wav_stride"]), plan["n_samples"],
+                                               pack_rows(refs, plan["order"], plan["ref_stride"]), plan["n_ref"], plan["sem_stride"])
+        assert frames == plan["frames"], (frames, plan["frames"])
+        ntok = self.tcfg.spk_token_num
+        return [(glob[j].view(1, 1, ntok), sem[j: j + 1, : frames[j]]) for j in plan["inverse"]]
+
     def debug_stage(self, name: str) -> torch.Tensor:
         out = torch.empty(64 * 1024 * 1024 // 4, dtype=torch.float32, device=self.device)
         dims = (C.c_int32 * 2)()
@@ -348,6 +427,67 @@ class BiCodecEncoder:
         self._lib.check(self._lib.smi_enc_debug_io(self._h, buffer.encode(), 0, C.c_void_p(out.ctypes.data), int(offset), int(count)),
                         "smi_enc_debug_io")
         return out.view(dtype)
+
+    # ---- the rows list the same way (diag=True only)
+    def rows_reserve(self, rows: int, samples: int, ref: int) -> None:
+        self._rows_reserve(rows, samples, ref)
+        self._rows_reserved = (int(rows), int(samples), int(ref))
+
+    def rows_debug_build(self, n_samples: Sequence[int], n_ref: Sequence[int]):
+        """The rows list of (n_samples[b], n_ref[b]) on the workspace's own buffers; nothing runs.  (frames [B], launches, run starts)."""
+        self._need_diag()
+        B = len(n_samples)
+        ns, nr, nf, rs = (C.c_int32 * B)(*n_samples), (C.c_int32 * B)(*n_ref), (C.c_int32 * B)(), (C.c_int32 * B)()
+        nl, nruns = C.c_int(0), C.c_int(0)
+        self._lib.check(self._lib.smi_enc_rows_debug_build(self._h, ns, nr, B, nf, C.byref(nl), rs, B, C.byref(nruns), self._stream()),
+                        "smi_enc_rows_debug_build")
+        return list(nf), nl.value, list(rs)[: nruns.value]
+
+    def rows_debug_runs(self):
+        """(run starts, launches) of the list the last rows build or rows call left"""
+        self._need_diag()
+        rs = (C.c_int32 * 4096)()
+        nl, nruns = C.c_int(0), C.c_int(0)
+        self._lib.check(self._lib.smi_enc_rows_debug_runs(self._h, rs, 4096, C.byref(nruns), C.byref(nl)), "smi_enc_rows_debug_runs")
+        return list(rs)[: nruns.value], nl.value
+
+    def rows_debug_launches(self):
+        self._need_diag()
+        out = []
+        name, info = C.create_string_buffer(512), (C.c_int32 * 8)()
+        for i in range(self.rows_debug_runs()[1]):
+            self._lib.check(self._lib.smi_enc_rows_debug_launch(self._h, i, name, 512, info), "smi_enc_rows_debug_launch")
+            out.append(dict(index=i, name=name.value.decode(), kind=info[0], grid=(info[1], info[2], info[3]), block=info[4],
+                            lds=info[5], cpt=info[6]))
+        return out
+
+    def rows_debug_io(self, row: int, buffer: str, data: Optional[np.ndarray] = None, offset: int = 0, count: int = 0,
+                      dtype=np.float32) -> Optional[np.ndarray]:
+        """debug_io on row ``row``'s copy of the named workspace buffer"""
+        self._need_diag()
+        if data is not None:
+            a = np.ascontiguousarray(data)
+            assert a.dtype.itemsize in (4, 8)
+            self._lib.check(self._lib.smi_enc_rows_debug_io(self._h, int(row), buffer.encode(), 1, C.c_void_p(a.ctypes.data), int(offset),
+                                                            a.nbytes // 4), "smi_enc_rows_debug_io")
+            return None
+        out = np.empty(int(count), dtype=np.float32)
+        self._lib.check(self._lib.smi_enc_rows_debug_io(self._h, int(row), buffer.encode(), 0, C.c_void_p(out.ctypes.data), int(offset),
+                                                        int(count)), "smi_enc_rows_debug_io")
+        return out.view(dtype)
+
+    def rows_debug_run(self, first: int, last: Optional[int] = None) -> None:
+        self._need_diag()
+        self._lib.check(self._lib.smi_enc_rows_debug_run(self._h, int(first), int(first if last is None else last), self._stream()),
+                        "smi_enc_rows_debug_run")
+
+    def rows_debug_stage(self, row: int, name: str) -> torch.Tensor:
+        self._need_diag()
+        out = torch.empty(16 * 1024 * 1024 // 4, dtype=torch.float32, device=self.device)
+        dims = (C.c_int32 * 2)()
+        self._lib.check(self._lib.smi_enc_rows_debug_stage(self._h, int(row), name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims,
+                                                           self._stream()), "smi_enc_rows_debug_stage")
+        return out[: dims[0] * dims[1]].reshape(dims[0], dims[1]).clone()
 
     def debug_run(self, first: int, last: Optional[int] = None) -> None:
         """Launches first .. last of the list, once each and in order, then synchronises."""

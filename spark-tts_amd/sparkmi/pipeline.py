@@ -280,7 +280,7 @@ class SparkTTS:
     @torch.no_grad()
     def inference_batch(self, requests: Sequence[dict], temperature: float = 0.8, top_k: float = 50,
                         top_p: float = 0.95, *, do_sample: bool = True, max_new_tokens: int = 3000,
-                        seed: Optional[int] = None, return_log_probs: bool = False) -> List:
+                        seed: Optional[int] = None, return_log_probs: bool = False, prompt_encode: str = "streams") -> List:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
@@ -294,16 +294,22 @@ class SparkTTS:
         A request's ``num_return_sequences`` key (an int >= 1): that many takes of it, its prompt prefilled once; its result
         is a list of one result per take.  All takes together are at most ``max_batch``.  A request's ``allowed_token_ids``
         / ``speech_tokens_only`` keys (as in ``inference``) restrict its generated ids, and its ``no_repeat_ngram_size`` key
-        (as in ``inference``) bans repeated n-grams; such a batch runs through the admission path."""
+        (as in ``inference``) bans repeated n-grams; such a batch runs through the admission path.
+        ``prompt_encode``: how the batch's prompt files are encoded -- "streams" (default): side by side on parallel HIP streams
+        (``tokenize_many``); "rows": as one ragged call on one handle (``tokenize_rows``).  The ids are equal bit for bit, so
+        the waveforms are the same."""
+        if prompt_encode not in ("streams", "rows"):
+            raise ValueError(f"prompt_encode must be 'streams' or 'rows', not {prompt_encode!r}")
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         n_takes = _take_counts(requests, self._max_batch)
         prompts, globals_ = [], []
-        # voice-clone requests that come with prompt FILES: all their prompt encodes run side by side (parallel HIP streams)
+        # voice-clone requests that come with prompt FILES: all their prompt encodes run together (parallel HIP streams, or one ragged call)
         need = [i for i, r in enumerate(requests)
                 if r.get("gender") is None and r.get("prompt_tokens") is None and r.get("prompt_speech_path") is not None]
         if len(need) > 1:
-            toks = self.audio_tokenizer.tokenize_many([requests[i]["prompt_speech_path"] for i in need])
+            paths = [requests[i]["prompt_speech_path"] for i in need]
+            toks = self.audio_tokenizer.tokenize_rows(paths) if prompt_encode == "rows" else self.audio_tokenizer.tokenize_many(paths)
             requests = [dict(r) for r in requests]
             for i, t in zip(need, toks):
                 requests[i]["prompt_tokens"] = t
