@@ -136,6 +136,41 @@ int smi_llm_debug_seqbias(smi_llm* h, const float* logits_host, int n_rows, cons
  * emits (lowest id on ties).  Synchronises; ends the current generation. */
 int smi_llm_debug_ngram(smi_llm* h, const float* logits_host, int n_rows, const int32_t* ngram_host, const int64_t* ctx_host,
                         const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, float* logits_out, int32_t* token_out);
+/* Op-level tests of the HEAD of a decode step (tests/test_head_ops_gpu.py): the final RMSNorm, the lm_head and
+ * the token pick -- launch_one(KLM) then launch_one(KFIN), the two calls a step ends with -- alone on caller rows.  Rows 0 .. M - 1
+ * sit in slots 0 .. M - 1 (M <= max_slots) at position 0 with no token emitted; every record is clean except what follows.
+ *   hidden [M][hidden]: the residual rows leaving the last layer.  k_load_hidden leaves them, their operand triples under the
+ *     FINAL norm's weight and their sums of squares where the last down_proj leaves them.
+ *   allow [M] or null: smi_llm_admit_constrained's records (its checks apply).  When every row's record is not neutral the
+ *     tile list is built by the function an admission builds it with, and the restricted lm_head runs.
+ *   reads [M] or null: 1 = the row reads its logits -- a neutral sampling record (top_k = 1, T = 1, top_p = 1) is installed in
+ *     its slot, so the step's feature mask has the sampling bit and the lm_head stores the logits rows in the handle's own
+ *     buffer, as in a real step (no logits pointer is passed to launch_one).  With SMI_HEAD_FIN such a row's token is the
+ *     sampler's: the arg-max, or ANY id that ties with it (TopKLogitsWarper keeps ties).
+ *   flags: SMI_HEAD_FIN also runs launch_one(KFIN); SMI_HEAD_POISON fills the handle's logits buffer with quiet NaNs first.
+ * Outputs, each nullable: logits_lm / logits_fin [M][vocab_size] = the handle's logits rows after KLM / after KFIN (whatever
+ * the buffer holds where nothing was stored); pval / pidx [M][nblk] as the lm_head left them (pcap = entries each holds;
+ * fewer than M * nblk: SMI_EINVAL); tokens [M] (SMI_HEAD_FIN).  nblk = the partial columns k_finalize reads (lm_blocks_for);
+ * form / grid / block / launches: the kernel form the lm_head launch site named, its grid (x, y) and block size, and how many
+ * launches of it the call made (a pass per 32 rows).  After SMI_HEAD_FIN smi_llm_debug_read's buffers 4, 3 and 6 hold the next
+ * step's residual rows, first-norm operand triples and sums-of-squares partials of the M rows.  Synchronises; ends the
+ * current generation. */
+enum { SMI_HEAD_FIN = 1, SMI_HEAD_POISON = 2 };
+typedef struct smi_head_io {
+  const float* hidden;
+  const smi_allow_params* allow;
+  const int32_t* reads;
+  int32_t flags;
+  int32_t pcap;
+  float* logits_lm;
+  float* logits_fin;
+  float* pval;
+  int32_t* pidx;
+  int32_t* tokens;
+  int32_t nblk, launches, grid[2], block;   /* out */
+  char form[32];                            /* out */
+} smi_head_io;
+int smi_llm_debug_head(smi_llm* h, int M, smi_head_io* io);
 
 /* ------------------------------------------------------------------------------------------
  * Conv kernel forms (csrc/smi_net.h): which instantiation of k_conv / k_convb / k_convbT / k_conv_c1 / k_gemv1 the launch

@@ -767,7 +767,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_gemm(GemmP p) {
   SMI_STAMP(6);
   if (EPI == EPI_LM) {
     __syncthreads();
-    if (tid < M) {
+    if (tid < MT * 16 && mbase + tid < M) {   // this block row's rows (33 .. 64 rows: two block rows of 32)
       float bv = -INFINITY;
       int bi = 0x7fffffff;
 #pragma unroll
@@ -776,8 +776,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_gemm(GemmP p) {
         int oi = besti[nb * 32 + tid];
         if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
       }
-      p.pval[(size_t)tid * p.work_blocks + blockIdx.x] = bv;   // [row][block]: finalize reads a row contiguously
-      p.pidx[(size_t)tid * p.work_blocks + blockIdx.x] = bi;
+      p.pval[(size_t)(mbase + tid) * p.work_blocks + blockIdx.x] = bv;   // [row][block]: finalize reads a row contiguously
+      p.pidx[(size_t)(mbase + tid) * p.work_blocks + blockIdx.x] = bi;
     }
   }
 }
@@ -3242,7 +3242,7 @@ __global__ __launch_bounds__(1024) void k_sample(SampleP p) {
       if (i0 + e < keep && u < before + pre[e]) pick = i0 + e;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_xor(pick, d, 64); pick = v < pick ? v : pick; }
-    if (tid == 0) p.tok[m] = si[pick];
+    if (tid == 0) p.tok[m] = n > 0 ? si[pick] : 0;   // no finite logit (NaN weights / inputs): no candidate, token 0 as k_finalize's guard gives a greedy row
   }
 }
 
@@ -3866,8 +3866,17 @@ struct smi_llm {
 #ifdef SMI_DIAG
   EngState eng;         // one-row decode engine (smi_eng.h); eng.enabled = 0: the launch path everywhere
   int eng_on;           // runtime switch (smi_llm_set_engine; SPARKMI_ENGINE=0 at create)
+  // the lm_head launches since smi_llm_debug_head last cleared the note: the form's name, its grid and block, the launches
+  mutable char lm_note_form[32]; mutable int lm_note_grid[2], lm_note_block, lm_note_n;
 #endif
 };
+#ifdef SMI_DIAG   // (diagnostics) every lm_head launch site names the kernel form it starts: smi_llm_debug_head reports it
+#define SMI_LM_NOTE(L_, form_, gx_, gy_, blk_) do { const smi_llm* ln_ = (L_); \
+    snprintf(ln_->lm_note_form, sizeof(ln_->lm_note_form), "%s", form_); ln_->lm_note_grid[0] = (int)(gx_); ln_->lm_note_grid[1] = (int)(gy_); \
+    ln_->lm_note_block = (int)(blk_); ++ln_->lm_note_n; } while (0)
+#else
+#define SMI_LM_NOTE(L_, form_, gx_, gy_, blk_) do { } while (0)
+#endif
 
 namespace {
 
@@ -4049,7 +4058,7 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
   static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>>::reg);
   SMI_REQUIRE(lds <= (size_t)kLdsBigBytes, "k_gemm: %zu bytes of LDS", lds);
   const int groups = (p.M + MT * 16 - 1) / (MT * 16);   // one block row per MT*16 rows (more than one: prefill, or 17..32 rows as 2 x 16)
-  SMI_REQUIRE(groups == 1 || EPI != EPI_LM, "lm_head takes at most 32 rows per launch");
+  if constexpr (EPI == EPI_LM) SMI_LM_NOTE(L, MT == 2 ? "k_gemm<2,EPI_LM>" : "k_gemm<1,EPI_LM>", work + helpers, groups, NW * 64);
   constexpr int kLean = (MT == 1 && EPI != EPI_LM) ? 1 : 0;
   if (kLean && p.ldsb > 0 && !p.stamps && p.M == 1 && p.lt_shift == 4) {
     if constexpr (PRO == PRO_NORM && EPI == EPI_SWIGLU && H == 1 && MT == 1) {
@@ -4443,6 +4452,7 @@ int launch_down_chains(const smi_llm* L, const GemmP& p, hipStream_t st) {
 template <int PRO, int EPI>
 int launch_gemm_x(const smi_llm* L, const GemmP& p, hipStream_t st) {
   const dim3 grid((p.NT + 3) / 4, (p.M + 15) / 16);
+  if constexpr (EPI == EPI_LM) SMI_LM_NOTE(L, "k_gemm_x<EPI_LM>", grid.x, grid.y, 256);
   if (L->cfg.kv_dtype) hipLaunchKernelGGL((k_gemm_x<PRO, EPI, 1>), grid, dim3(256), 0, st, p, (const float*)p.W);
   else hipLaunchKernelGGL((k_gemm_x<PRO, EPI, 0>), grid, dim3(256), 0, st, p, (const float*)p.W);
   SMI_LAUNCH_CHECK();
@@ -4596,16 +4606,20 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
         const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
         if (M <= 16) {
+          SMI_LM_NOTE(L, "k_lm<1,RT>", L->lm_blocks, 1, 256);
           hipLaunchKernelGGL((k_lm<1, 1>), dim3(L->lm_blocks), dim3(256), lds, st, p, 0, 0);
           SMI_LAUNCH_CHECK();
           return SMI_OK;
         }
         for (int m0 = 0; m0 < M; m0 += 32) {   // the kernel the full path picks for this row count, in its restricted form
           if (!(L->tune2 & 8192) && lds32 <= 150 * 1024) {
+            SMI_LM_NOTE(L, L->KTh <= 28 ? "k_lm32<7,RT>" : "k_lm32<8,RT>", lm_blocks_for(L, M), 1, 256);
             if (L->KTh <= 28) hipLaunchKernelGGL((k_lm32<7, 1>), dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, 0, m0);
             else hipLaunchKernelGGL((k_lm32<8, 1>), dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, 0, m0);
-          } else
+          } else {
+            SMI_LM_NOTE(L, "k_lm<2,RT>", lm_blocks_for(L, M), 1, 512);
             hipLaunchKernelGGL((k_lm<2, 1>), dim3(lm_blocks_for(L, M)), dim3(512), 2 * lds, st, p, 0, m0);
+          }
           SMI_LAUNCH_CHECK();
         }
         return SMI_OK;
@@ -4614,6 +4628,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         const int ngroups = (L->NTlm + 1) / 2;
         const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
         if (M <= 16) {
+          SMI_LM_NOTE(L, "k_lm<1>", L->lm_blocks, 1, 256);
           hipLaunchKernelGGL(k_lm<1>, dim3(L->lm_blocks), dim3(256), lds, st, p, ngroups, 0);
           SMI_LAUNCH_CHECK();
         } else {              // 32 rows per pass: one 4-wave block per CU, the second m-tile's operands in LDS (k_lm32);
@@ -4621,10 +4636,13 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
           const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
           for (int m0 = 0; m0 < M; m0 += 32) {
             if (!(L->tune2 & 8192) && lds32 <= 150 * 1024) {
+              SMI_LM_NOTE(L, L->KTh <= 28 ? "k_lm32<7>" : "k_lm32<8>", lm_blocks_for(L, M), 1, 256);
               if (L->KTh <= 28) hipLaunchKernelGGL(k_lm32<7>, dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, ngroups, m0);
               else hipLaunchKernelGGL(k_lm32<8>, dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, ngroups, m0);
-            } else
+            } else {
+              SMI_LM_NOTE(L, "k_lm<2>", lm_blocks_for(L, M), 1, 512);
               hipLaunchKernelGGL(k_lm<2>, dim3(lm_blocks_for(L, M)), dim3(512), 2 * lds, st, p, ngroups, m0);
+            }
             SMI_LAUNCH_CHECK();
           }
         }
@@ -7350,6 +7368,77 @@ int smi_llm_debug_ngram(smi_llm* L, const float* logits_host, int n_rows, const 
   for (int m = 0; m < n_rows; ++m) token_out[m] = after[m].token;
   alone_end(L);
   return SMI_OK;
+}
+
+// smi_llm_debug_head between alone_begin and alone_end: whatever it returns, the caller frees *psrc and restores the clean records
+static int head_run(smi_llm* L, int M, smi_head_io* io, int V, int nblk, float** psrc) {
+  graphs_flush(L);
+  L->B = M; L->identity_slots = 1; L->session = 0; L->started = 0; L->attn_seg = 1;
+  L->lm_restrict = io->allow != nullptr;
+  for (int m = 0; m < M; ++m) {
+    L->hctl.seqid[m] = m;
+    if (io->reads && io->reads[m]) {   // a neutral sampling record, as smi_llm_debug_seqbias installs it; here the step's features see it too
+      L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;
+      L->hctl.samp[m].top_k = 1; L->hctl.samp[m].inv_temp = 1.f; L->hctl.samp[m].top_p = 1.f;
+      L->slot_feat[m] |= F_SAMPLE;
+    }
+    if (io->allow) {
+      L->hctl.allow[m] = allow_record(&io->allow[m], V);
+      if (L->hctl.allow[m].n > 0) L->slot_feat[m] |= F_ALLOW;
+    }
+    L->lm_restrict &= (L->slot_feat[m] & F_ALLOW) != 0;   // live_set's rule
+  }
+  L->hctl.seed = 0;
+  { const int rct = allow_tiles_upload(L, 0); if (rct) return rct; }
+  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
+  SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
+  if (io->flags & SMI_HEAD_POISON) SMI_HIP(hipMemset(L->logits, 0xff, (size_t)kMaxRows * V * 4));   // 0xffffffff: a quiet NaN
+  SMI_HIP(hipMalloc((void**)psrc, (size_t)M * L->H * 4));
+  int rc = SMI_OK;
+  if (hipMemcpy(*psrc, io->hidden, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: upload failed"); }
+  if (rc == SMI_OK) {
+    hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, *psrc, L->KTh, M, (const float*)sec(L, SMI_LLM_FINAL_NORM, 0), L->dec.h,
+                       L->dec.xs_h, L->dec.ss, L->NTh * 4);
+    if (hipGetLastError() != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: k_load_hidden launch failed"); }
+  }
+  L->lm_note_n = 0; L->lm_note_form[0] = 0; L->lm_note_grid[0] = L->lm_note_grid[1] = L->lm_note_block = 0;
+  if (rc == SMI_OK) rc = launch_one(L, KLM, 0, L->rows, M, nullptr, 0);
+  if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: lm_head failed: %s", hipGetErrorString(hipGetLastError())); }
+  io->nblk = nblk; io->launches = L->lm_note_n; io->grid[0] = L->lm_note_grid[0]; io->grid[1] = L->lm_note_grid[1]; io->block = L->lm_note_block;
+  memcpy(io->form, L->lm_note_form, sizeof(io->form));
+  if (rc == SMI_OK && io->logits_lm && hipMemcpy(io->logits_lm, L->logits, (size_t)M * V * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
+  if (rc == SMI_OK && io->pval && hipMemcpy(io->pval, L->pval, (size_t)M * nblk * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
+  if (rc == SMI_OK && io->pidx && hipMemcpy(io->pidx, L->pidx, (size_t)M * nblk * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
+  if (rc == SMI_OK && (io->flags & SMI_HEAD_FIN)) {
+    rc = launch_one(L, KFIN, 0, L->rows, M, nullptr, 0);
+    if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: finalize failed: %s", hipGetErrorString(hipGetLastError())); }
+    if (rc == SMI_OK && io->logits_fin && hipMemcpy(io->logits_fin, L->logits, (size_t)M * V * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
+    if (rc == SMI_OK && io->tokens) {
+      std::vector<RowDesc> after(kMaxRows);
+      if (hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
+      for (int m = 0; m < M; ++m) io->tokens[m] = after[m].token;
+    }
+  }
+  return rc;
+}
+
+// Tests: the head of a decode step alone on caller rows -- launch_one(KLM), then launch_one(KFIN) -- (see sparkmi_debug.h).
+int smi_llm_debug_head(smi_llm* L, int M, smi_head_io* io) {
+  SMI_REQUIRE(L && io && io->hidden, "smi_llm_debug_head: null argument");
+  SMI_REQUIRE(M >= 1 && M <= L->cfg.max_slots && M <= kMaxRows, "smi_llm_debug_head: M=%d outside 1..max_slots", M);
+  SMI_REQUIRE((io->flags & ~(SMI_HEAD_FIN | SMI_HEAD_POISON)) == 0, "smi_llm_debug_head: flags=%d", io->flags);
+  const int V = L->cfg.vocab_size, nblk = lm_blocks_for(L, M);
+  SMI_REQUIRE((!io->pval && !io->pidx) || (size_t)io->pcap >= (size_t)M * nblk, "smi_llm_debug_head: pval / pidx hold %d entries, %d rows x %d columns needed",
+              io->pcap, M, nblk);
+  if (io->allow)
+    for (int m = 0; m < M; ++m) { const int rcv = validate_allow(L, io->allow[m], nullptr, m); if (rcv) return rcv; }
+  { const int rcb = alone_begin(L, M, nullptr); if (rcb) return rcb; }
+  float* src = nullptr;
+  const int rc = head_run(L, M, io, V, nblk, &src);
+  if (src) (void)hipFree(src);
+  alone_end(L);
+  return rc;
 }
 
 // Diagnostics (SPARKMI_ENGINE_STAMPS=1): out[3][layers][16] microseconds since the first stamp of the last engine launch:

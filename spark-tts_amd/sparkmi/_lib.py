@@ -137,6 +137,17 @@ class SeqParams(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+SMI_HEAD_FIN, SMI_HEAD_POISON = 1, 2
+
+
+class HeadIO(C.Structure):
+    """smi_head_io: the operands, switches and outputs of smi_llm_debug_head (include/sparkmi_debug.h)"""
+    _fields_ = [("hidden", C.POINTER(C.c_float)), ("allow", C.POINTER(AllowParams)), ("reads", C.POINTER(C.c_int32)),
+                ("flags", C.c_int32), ("pcap", C.c_int32), ("logits_lm", C.POINTER(C.c_float)), ("logits_fin", C.POINTER(C.c_float)),
+                ("pval", C.POINTER(C.c_float)), ("pidx", C.POINTER(C.c_int32)), ("tokens", C.POINTER(C.c_int32)),
+                ("nblk", C.c_int32), ("launches", C.c_int32), ("grid", C.c_int32 * 2), ("block", C.c_int32), ("form", C.c_char * 32)]
+
+
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
 _P = C.POINTER
 SYMBOLS = {
@@ -227,6 +238,7 @@ DEBUG_SYMBOLS = {
                                    _P(C.c_int32), _P(C.c_float), _P(C.c_int32), _P(C.c_int32)]),
     "smi_llm_debug_ngram": (_I, [_VP, _P(C.c_float), _I, _P(C.c_int32), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _I,
                                  _P(C.c_float), _P(C.c_int32)]),
+    "smi_llm_debug_head": (_I, [_VP, _I, _P(HeadIO)]),
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),

@@ -1094,6 +1094,56 @@ class SparkLLM:
                                                         fin.ctypes.data_as(i32)), "smi_llm_debug_seqbias")
         return out, tok, fin
 
+    def debug_head(self, hidden: np.ndarray, reads: Optional[Sequence[int]] = None, allow: Optional[Sequence[Optional[Sequence]]] = None,
+                   finalize: bool = True, poison: bool = False) -> dict:
+        """The head of a decode step alone (``smi_llm_debug_head``): the final RMSNorm, the lm_head and -- ``finalize`` -- the
+        token pick, on ``hidden`` (M, hidden) fp32 = the residual rows leaving the last layer, rows in slots 0 .. M - 1.
+        ``reads[m]`` = 1: row m reads its logits (a neutral sampling record); ``allow[m]``: the row's (lo, hi) ranges or None
+        (no constraint); ``poison``: the logits buffer is filled with NaNs first.  Returns {"form", "grid", "block", "launches",
+        "nblk", "logits_lm" (M, vocab), "pval" / "pidx" (M, nblk), and with ``finalize`` "logits_fin", "tokens", "h" (M, hidden),
+        "g" (M, hidden: the next first-norm operand, re-summed from its triples), "ss" (M, hidden / 4)}."""
+        self._need_diag("debug_head")
+        c = self.cfg
+        hidden = np.ascontiguousarray(hidden, dtype=np.float32)
+        M = hidden.shape[0]
+        if hidden.shape != (M, c.hidden_size) or (reads is not None and len(reads) != M) or (allow is not None and len(allow) != M):
+            raise ValueError("debug_head: hidden [M][hidden], M read flags, M allow entries")
+        io = _lib.HeadIO()
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        io.hidden = hidden.ctypes.data_as(fp)
+        if reads is not None:
+            rd = np.ascontiguousarray(reads, dtype=np.int32)
+            io.reads = rd.ctypes.data_as(ip)
+        if allow is not None:
+            recs = (_lib.AllowParams * M)()
+            for i, ranges in enumerate(allow):
+                for j, (lo, hi) in enumerate(ranges or ()):
+                    recs[i].lo[j], recs[i].hi[j] = int(lo), int(hi)
+                recs[i].n_ranges = len(ranges or ())
+            io.allow = recs
+        io.flags = (_lib.SMI_HEAD_FIN if finalize else 0) | (_lib.SMI_HEAD_POISON if poison else 0)
+        cap = ((c.vocab_size + 15) // 16 + 3) // 4   # lm_cap: the most partial columns a row has
+        lg_lm = np.empty((M, c.vocab_size), np.float32)
+        lg_fin = np.empty((M, c.vocab_size), np.float32)
+        pval = np.empty(M * cap, np.float32)
+        pidx = np.empty(M * cap, np.int32)
+        tok = np.full(M, -1, np.int32)
+        io.pcap = M * cap
+        io.logits_lm, io.logits_fin = lg_lm.ctypes.data_as(fp), lg_fin.ctypes.data_as(fp)
+        io.pval, io.pidx, io.tokens = pval.ctypes.data_as(fp), pidx.ctypes.data_as(ip), tok.ctypes.data_as(ip)
+        self._lib.check(self._lib.smi_llm_debug_head(self._h, M, C.byref(io)), "smi_llm_debug_head")
+        nblk = int(io.nblk)
+        out = {"form": io.form.decode(), "grid": (int(io.grid[0]), int(io.grid[1])), "block": int(io.block), "launches": int(io.launches),
+               "nblk": nblk, "logits_lm": lg_lm, "pval": pval[: M * nblk].reshape(M, nblk).copy(),
+               "pidx": pidx[: M * nblk].reshape(M, nblk).copy()}
+        if finalize:
+            H = c.hidden_size
+            out.update(logits_fin=lg_fin, tokens=tok,
+                       h=self.debug_read(4, M * H * 4).view(np.float32).reshape(M, H).copy(),
+                       g=self._from_triples(self.debug_read(3, M * H * 6), H, M),
+                       ss=self.debug_read(6, M * H).view(np.float32).reshape(M, H // 4).copy())
+        return out
+
     def debug_ngram(self, logits: np.ndarray, sizes: Sequence[int], contexts: Sequence[Sequence[int]], prompt_lens: Sequence[int]):
         """The n-gram ban, ``k_penalize`` and ``k_finalize`` alone (``smi_llm_debug_ngram``) on caller rows: ``logits`` [n][vocab]
         f32, one ``no_repeat_ngram_size`` and one context (prompt + generated ids, the first ``prompt_lens[i]`` -- 0 or more --
