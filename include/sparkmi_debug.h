@@ -94,7 +94,8 @@ int smi_llm_debug_prefill_layer(smi_llm* h, int layer, int stage, int n_seq, con
 int smi_llm_pf_tiles(const int32_t* rows_host, int M, int32_t* out, int cap, int32_t* n);
 /* Diagnostics: the raw stamp buffer (u64 s_memrealtime ticks, 10 ns) after smi_llm_debug_stamps; n entries. */
 int smi_llm_debug_raw_stamps(smi_llm* h, unsigned long long* out, int n);
-/* Tests: the sampler alone (k_sample_scan + k_sample, exactly as a decode step launches them) on a caller's logits row --
+/* Tests: the sampler alone (k_sample_scan + k_sample, through launch_sampler, the one function a decode step too starts them
+ * from) on a caller's logits row --
  * the reference's default decoding chain, cli/SparkTTS.py:166-168,197-204 -> transformers' TemperatureLogitsWarper ->
  * TopKLogitsWarper -> TopPLogitsWarper -> multinomial.  logits_host [vocab_size] is replicated to every row (null: the rows
  * of the previous call stay), n_rows rows draw one token each from the streams (seed; token index 0, sequence number = row),
@@ -102,7 +103,8 @@ int smi_llm_debug_raw_stamps(smi_llm* h, unsigned long long* out, int n);
  * (block j = the j-th contiguous share of the row, as many blocks as the lm_head launch of n_rows rows leaves); 0: the exact
  * radix selection.  Parameters come from smi_llm_set_sampling.  Synchronises; ends the current generation. */
 int smi_llm_debug_sample(smi_llm* h, const float* logits_host, int n_rows, uint64_t seed, int use_bound, int32_t* tokens_out);
-/* Tests: the penalty kernel alone (k_penalize, as a step launches it for n_rows rows, n_rows <= max_slots) on caller rows:
+/* Tests: the penalty kernel alone (k_penalize, through the step's launch_penalize for n_rows rows, n_rows <= max_slots) on
+ * caller rows:
  * logits_host [n_rows][vocab_size], hist_host [n_rows][vocab_size] history entries (bit 15: the id is in the prompt, bits 0..14:
  * its count among the generated tokens), pens [n_rows] records (smi_llm_admit_penalized's checks), emitted_host [n_rows]
  * tokens each row has emitted; eos ids: the last smi_llm_session_begin's.  logits_out [n_rows][vocab_size]: the processed rows;
@@ -110,15 +112,15 @@ int smi_llm_debug_sample(smi_llm* h, const float* logits_host, int n_rows, uint6
  * generation. */
 int smi_llm_debug_penalize(smi_llm* h, const float* logits_host, int n_rows, const uint16_t* hist_host, const smi_penalty_params* pens,
                            const int32_t* emitted_host, float* logits_out, int32_t* argmax_out);
-/* Tests: the log-probability kernels alone (k_logprob and k_finalize's combine, as a step launches them for n_rows rows,
- * n_rows <= max_slots) on caller rows: logits_host [n_rows][vocab_size] (the processed logits z before temperature),
+/* Tests: the log-probability kernels alone (k_logprob and k_finalize's combine, through the step's launch_logprob and
+ * launch_finalize for n_rows rows, n_rows <= max_slots) on caller rows: logits_host [n_rows][vocab_size] (the processed logits z before temperature),
  * temperature_host [n_rows] (finite, > 0; each row is a sampling row with 1/T, T = 1: unscaled), tokens_host [n_rows] the
  * emitted ids.  The row maxima the kernel reads are left as the lm_head leaves them (per-set maxima over a contiguous
  * partition).  lp_out [n_rows]: z[tok] / T - logsumexp(z / T).  Synchronises; ends the current generation. */
 int smi_llm_debug_logprob(smi_llm* h, const float* logits_host, int n_rows, const float* temperature_host, const int32_t* tokens_host,
                           float* lp_out);
-/* Tests: the bias stage (stage 0b inside k_penalize) and k_finalize's stop match alone, as a step launches them for n_rows
- * rows (n_rows <= max_slots), on caller rows: logits_host [n_rows][vocab_size]; seq [n_rows] records (smi_llm_admit_biased's
+/* Tests: the bias stage (stage 0b inside k_penalize) and k_finalize's stop match alone, through the step's launch_penalize
+ * and launch_finalize for n_rows rows (n_rows <= max_slots), on caller rows: logits_host [n_rows][vocab_size]; seq [n_rows] records (smi_llm_admit_biased's
  * checks, without an allowed set); ctx_host [n_rows][ctx_cap] int64: row m's context ctx_len_host[m] ids long, of which the
  * first prompt_len_host[m] (>= 1) are its prompt and the rest the tokens it has generated; min_new_host [n_rows] (null: 0)
  * the rows' min_new_tokens for the stop match; eos ids: the last smi_llm_session_begin's.  The row maxima the kernels read
@@ -128,8 +130,8 @@ int smi_llm_debug_logprob(smi_llm* h, const float* logits_host, int n_rows, cons
 int smi_llm_debug_seqbias(smi_llm* h, const float* logits_host, int n_rows, const smi_seq_params* seq, const int64_t* ctx_host,
                           const int32_t* ctx_len_host, const int32_t* prompt_len_host, int ctx_cap, const int32_t* min_new_host,
                           float* logits_out, int32_t* token_out, int32_t* finished_out);
-/* Tests: the n-gram ban (k_ngram_ban), k_penalize and k_finalize alone, as a step launches them for n_rows rows
- * (n_rows <= max_slots), on caller rows: logits_host [n_rows][vocab_size]; ngram_host [n_rows] each row's
+/* Tests: the n-gram ban (k_ngram_ban), k_penalize and k_finalize alone, through the step's launch_ngram_ban, launch_penalize
+ * and launch_finalize for n_rows rows (n_rows <= max_slots), on caller rows: logits_host [n_rows][vocab_size]; ngram_host [n_rows] each row's
  * no_repeat_ngram_size (0 .. SMI_MAX_NGRAM); ctx_host [n_rows][ctx_cap] int64: row m's context ctx_len_host[m] ids long, of
  * which the first prompt_len_host[m] (0 .. ctx_len, at most max_positions) go to the slot's prompt store and the rest to the
  * token history.  logits_out [n_rows][vocab_size]: the rows after the stage; token_out [n_rows]: the arg-max k_finalize

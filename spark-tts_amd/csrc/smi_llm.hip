@@ -4355,6 +4355,49 @@ FinP fin_params(const smi_llm* L, int M) {
   return f;
 }
 
+#define SMI_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)   // a failed step ends the composition
+
+// The token pick's kernels, one launcher each: the only place a kernel's grid, block and dynamic LDS are written.  A decode
+// step (launch_one(KFIN)) and the kernel-alone diagnostics (smi_llm_debug_*) are compositions of these, over M rows of L->rows.
+int launch_ngram_ban(const smi_llm* L, int M, hipStream_t st) {
+  size_t lds;
+  const NgramP np = ngram_params(L, &lds);
+  hipLaunchKernelGGL(k_ngram_ban, dim3(1, M), dim3(256), lds, st, np);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+// seq: the sequence records when some row has a bias entry (stage 0b), else null
+int launch_penalize(const smi_llm* L, int M, const SeqRec* seq, hipStream_t st) {
+  PenP pp = pen_params(L, M);
+  pp.seq = seq;
+  hipLaunchKernelGGL(k_penalize, dim3((pp.nblk + kPenWaves - 1) / kPenWaves, M), dim3(256), 0, st, pp);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+// k_sample_scan + k_sample, never apart.  use_bound: the lm_head's maxima bound the top-k candidates (a step: always); false:
+// the exact radix selection
+int launch_sampler(const smi_llm* L, int M, bool use_bound, hipStream_t st) {
+  SampleP sp = sample_params(L, M);
+  if (!use_bound) sp.pval = nullptr;
+  hipLaunchKernelGGL(k_sample_scan, dim3(kScanBlocks, M), dim3(256), 0, st, sp);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_sample, dim3(M), dim3(1024), 0, st, sp);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+int launch_logprob(const smi_llm* L, int M, hipStream_t st) {
+  const LpP lp = lp_params(L, M);
+  hipLaunchKernelGGL(k_logprob, dim3(kLpBlocks, M), dim3(256), 0, st, lp);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+// f: fin_params plus what the kernels launched before it left (tok, phist, lp*) and the stop records (seq)
+int launch_finalize(const FinP& f, hipStream_t st) {
+  hipLaunchKernelGGL(k_finalize, dim3(f.M), dim3(256), 0, st, f);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
 int segs_for(int ctx_bound) { return ctx_bound <= kAttnSeg ? 1 : (ctx_bound + kAttnSeg - 1) / kAttnSeg; }
 
 // attention (+ the segment merge when the context bound of the current call exceeds one segment)
@@ -4507,6 +4550,39 @@ AttnP attn_operands(const smi_llm* L, int layer, const Work& w, const RowDesc* r
   return a;
 }
 
+// The persistent lm_head (KTh <= 32): 16 rows' operand resident in the registers of a 4-wave group.  RT = 1: the restricted form
+// of the same kernel for the same row count (the groups come from p.tlist, so ngroups = 0; the rows' own ranges through p.ctl).
+template <int RT>
+int launch_lm_persistent(const smi_llm* L, const GemmP& p, int M, int ngroups, hipStream_t st) {
+  const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
+  if (M <= 16) {
+    SMI_LM_NOTE(L, RT ? "k_lm<1,RT>" : "k_lm<1>", L->lm_blocks, 1, 256);
+    hipLaunchKernelGGL((k_lm<1, RT>), dim3(L->lm_blocks), dim3(256), lds, st, p, ngroups, 0);
+    SMI_LAUNCH_CHECK();
+    return SMI_OK;
+  }
+  // 32 rows per pass: one 4-wave block per CU, the second m-tile's operands in LDS (k_lm32);
+  // SPARKMI_TUNE2 bit 8192: the two-group kernel (k_lm<2>) for A/B
+  const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
+  const int blocks = lm_blocks_for(L, M);
+  for (int m0 = 0; m0 < M; m0 += 32) {
+    if (!(L->tune2 & 8192) && lds32 <= 150 * 1024) {
+      if (L->KTh <= 28) {
+        SMI_LM_NOTE(L, RT ? "k_lm32<7,RT>" : "k_lm32<7>", blocks, 1, 256);
+        hipLaunchKernelGGL((k_lm32<7, RT>), dim3(blocks), dim3(256), lds32, st, p, ngroups, m0);
+      } else {
+        SMI_LM_NOTE(L, RT ? "k_lm32<8,RT>" : "k_lm32<8>", blocks, 1, 256);
+        hipLaunchKernelGGL((k_lm32<8, RT>), dim3(blocks), dim3(256), lds32, st, p, ngroups, m0);
+      }
+    } else {
+      SMI_LM_NOTE(L, RT ? "k_lm<2,RT>" : "k_lm<2>", blocks, 1, 512);
+      hipLaunchKernelGGL((k_lm<2, RT>), dim3(blocks), dim3(512), 2 * lds, st, p, ngroups, m0);
+    }
+    SMI_LAUNCH_CHECK();
+  }
+  return SMI_OK;
+}
+
 int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, float* logits, hipStream_t st) {
   const smi_llm_cfg& c = L->cfg;
   const bool fused = fuse_o_now(L, rows, M);
@@ -4603,51 +4679,9 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       p.stamps = L->stamps_on ? L->stamps : nullptr;
       if (L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L, feat)) {   // every row constrained: only the union's tiles
         p.tlist = L->tlist; p.ctl = L->ctl;
-        const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
-        const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
-        if (M <= 16) {
-          SMI_LM_NOTE(L, "k_lm<1,RT>", L->lm_blocks, 1, 256);
-          hipLaunchKernelGGL((k_lm<1, 1>), dim3(L->lm_blocks), dim3(256), lds, st, p, 0, 0);
-          SMI_LAUNCH_CHECK();
-          return SMI_OK;
-        }
-        for (int m0 = 0; m0 < M; m0 += 32) {   // the kernel the full path picks for this row count, in its restricted form
-          if (!(L->tune2 & 8192) && lds32 <= 150 * 1024) {
-            SMI_LM_NOTE(L, L->KTh <= 28 ? "k_lm32<7,RT>" : "k_lm32<8,RT>", lm_blocks_for(L, M), 1, 256);
-            if (L->KTh <= 28) hipLaunchKernelGGL((k_lm32<7, 1>), dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, 0, m0);
-            else hipLaunchKernelGGL((k_lm32<8, 1>), dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, 0, m0);
-          } else {
-            SMI_LM_NOTE(L, "k_lm<2,RT>", lm_blocks_for(L, M), 1, 512);
-            hipLaunchKernelGGL((k_lm<2, 1>), dim3(lm_blocks_for(L, M)), dim3(512), 2 * lds, st, p, 0, m0);
-          }
-          SMI_LAUNCH_CHECK();
-        }
-        return SMI_OK;
+        return launch_lm_persistent<1>(L, p, M, 0, st);
       }
-      if (L->KTh <= 32) {   // persistent path: 16 rows' operand resident in the registers of a 4-wave group
-        const int ngroups = (L->NTlm + 1) / 2;
-        const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
-        if (M <= 16) {
-          SMI_LM_NOTE(L, "k_lm<1>", L->lm_blocks, 1, 256);
-          hipLaunchKernelGGL(k_lm<1>, dim3(L->lm_blocks), dim3(256), lds, st, p, ngroups, 0);
-          SMI_LAUNCH_CHECK();
-        } else {              // 32 rows per pass: one 4-wave block per CU, the second m-tile's operands in LDS (k_lm32);
-                              // SPARKMI_TUNE2 bit 8192: the two-group kernel (k_lm<2>) for A/B
-          const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
-          for (int m0 = 0; m0 < M; m0 += 32) {
-            if (!(L->tune2 & 8192) && lds32 <= 150 * 1024) {
-              SMI_LM_NOTE(L, L->KTh <= 28 ? "k_lm32<7>" : "k_lm32<8>", lm_blocks_for(L, M), 1, 256);
-              if (L->KTh <= 28) hipLaunchKernelGGL(k_lm32<7>, dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, ngroups, m0);
-              else hipLaunchKernelGGL(k_lm32<8>, dim3(lm_blocks_for(L, M)), dim3(256), lds32, st, p, ngroups, m0);
-            } else {
-              SMI_LM_NOTE(L, "k_lm<2>", lm_blocks_for(L, M), 1, 512);
-              hipLaunchKernelGGL(k_lm<2>, dim3(lm_blocks_for(L, M)), dim3(512), 2 * lds, st, p, ngroups, m0);
-            }
-            SMI_LAUNCH_CHECK();
-          }
-        }
-        return SMI_OK;
-      }
+      if (L->KTh <= 32) return launch_lm_persistent<0>(L, p, M, (L->NTlm + 1) / 2, st);
       SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
       return launch_gemm<4, 4, 2, 1, PRO_NORM, EPI_LM>(L, p, st);
     }
@@ -4655,37 +4689,23 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       const unsigned feat = step_feat(L);
       FinP f = fin_params(L, M);
       if (feat & F_NGRAM) {   // rows with n = 0 leave at once; the others get -inf at the ids that would repeat an n-gram
-        size_t lds;
-        const NgramP np = ngram_params(L, &lds);
-        hipLaunchKernelGGL(k_ngram_ban, dim3(1, M), dim3(256), lds, st, np);
-        SMI_LAUNCH_CHECK();
+        SMI_TRY(launch_ngram_ban(L, M, st));
       }
       // rows neither penalised, biased, n-gram banned nor constrained leave k_penalize at once
       if ((feat & (F_PEN | F_BIAS | F_NGRAM)) || ((feat & F_ALLOW) && logits_needed(L, feat))) {
-        PenP pp = pen_params(L, M);
-        if (feat & F_BIAS) pp.seq = L->seq;
-        hipLaunchKernelGGL(k_penalize, dim3((pp.nblk + kPenWaves - 1) / kPenWaves, M), dim3(256), 0, st, pp);
-        SMI_LAUNCH_CHECK();
+        SMI_TRY(launch_penalize(L, M, (feat & F_BIAS) ? L->seq : nullptr, st));
         f.phist = L->phist;
       }
       if (feat & F_SAMPLE) {   // rows that do not sample leave both sampler kernels at once
-        const SampleP sp = sample_params(L, M);
-        hipLaunchKernelGGL(k_sample_scan, dim3(kScanBlocks, M), dim3(256), 0, st, sp);
-        SMI_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_sample, dim3(M), dim3(1024), 0, st, sp);
-        SMI_LAUNCH_CHECK();
+        SMI_TRY(launch_sampler(L, M, true, st));
         f.tok = L->tok;
       }
       if (feat & F_LP) {   // unflagged rows leave k_logprob at once
-        const LpP lp = lp_params(L, M);
-        hipLaunchKernelGGL(k_logprob, dim3(kLpBlocks, M), dim3(256), 0, st, lp);
-        SMI_LAUNCH_CHECK();
+        SMI_TRY(launch_logprob(L, M, st));
         f.lp = L->lp; f.lp_part = L->lp_part; f.lp_rowc = L->lp_rowc;
       }
       if (feat & F_STOP) f.seq = L->seq;
-      hipLaunchKernelGGL(k_finalize, dim3(M), dim3(256), 0, st, f);
-      SMI_LAUNCH_CHECK();
-      return SMI_OK;
+      return launch_finalize(f, st);
     }
   }
   smi_set_error("launch_one: bad kernel id %d", which);
@@ -7083,22 +7103,33 @@ int smi_llm_debug_raw_stamps(smi_llm* L, unsigned long long* out, int n) {
   return SMI_OK;
 }
 
-// ---- kernel-alone runs (the four entries below): the state around them, and the table the lm_head would have left
-// Before: the device idle, every record clean, rows 0 .. n-1 = slots 0 .. n-1 with flags[m] tokens emitted (null: none).  The
-// caller then writes the records its kernel reads and uploads the controls.
-static int alone_begin(smi_llm* L, int n, const int32_t* flags) {
-  SMI_HIP(hipDeviceSynchronize());
-  slots_clear(L);
-  std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
-  for (int m = 0; m < n; ++m) rows[m] = RowDesc{m, 0, 0, flags ? flags[m] : 0};
-  SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
-  return SMI_OK;
-}
-// After: clean records again; rows, controls, the lm_head partials and the histories no longer belong to a generation.
-static void alone_end(smi_llm* L) {
-  slots_clear(L);
-  L->started = 0;
-}
+// ---- kernel-alone runs (the six entries below): the state around them, and the table the lm_head would have left.  Each entry
+// stages its rows, writes the records its kernels read, commits the controls, composes the stage launchers a decode step is
+// composed of (launch_ngram_ban .. launch_finalize; smi_llm_debug_head: launch_one itself) and fetches what they left.
+// The scope of one run.  Before: the device idle, every record clean, rows 0 .. n-1 = slots 0 .. n-1 with flags[m] tokens emitted
+// (null: none); rc says whether that held.  After, on every way out: clean records again, `dev` freed; rows, controls, the lm_head
+// partials and the histories no longer belong to a generation.
+struct Alone {
+  smi_llm* L;
+  float* dev = nullptr;   // a device buffer of the run (smi_llm_debug_head's hidden rows)
+  int rc;
+  Alone(smi_llm* L_, int n, const int32_t* flags) : L(L_), rc(begin(n, flags)) {}
+  Alone(const Alone&) = delete;
+  Alone& operator=(const Alone&) = delete;
+  ~Alone() {
+    if (dev) (void)hipFree(dev);
+    slots_clear(L);
+    L->started = 0;
+  }
+  int begin(int n, const int32_t* flags) {
+    SMI_HIP(hipDeviceSynchronize());
+    slots_clear(L);
+    std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
+    for (int m = 0; m < n; ++m) rows[m] = RowDesc{m, 0, 0, flags ? flags[m] : 0};
+    SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
+    return SMI_OK;
+  }
+};
 // (maximum, lowest id) of each of the nblk contiguous sets of `per` ids of every logits row [n_rows][V], as the lm_head leaves
 // them: pv / pi [n_rows][nblk]
 static void block_maxima(const float* logits, int n_rows, int V, int nblk, int per, std::vector<float>& pv, std::vector<int32_t>& pi) {
@@ -7111,6 +7142,84 @@ static void block_maxima(const float* logits, int n_rows, int V, int nblk, int p
         if (x > pv[(size_t)m * nblk + j]) { pv[(size_t)m * nblk + j] = x; pi[(size_t)m * nblk + j] = i; }
       }
 }
+// Row staging: the caller's logits [n][V] into the handle's rows and, per > 0, their maxima over nblk contiguous sets of `per`
+// ids where the lm_head leaves them.  copies > 1: the n rows again in the next n rows, and so on.
+static int alone_rows(smi_llm* L, const float* logits, int n, int nblk, int per, int copies = 1) {
+  const size_t V = (size_t)L->cfg.vocab_size;
+  std::vector<float> pv;
+  std::vector<int32_t> pi;
+  if (per > 0) block_maxima(logits, n, (int)V, nblk, per, pv, pi);
+  for (size_t c = 0; c < (size_t)copies; ++c) {
+    SMI_HIP(hipMemcpy(L->logits + c * n * V, logits, (size_t)n * V * 4, hipMemcpyHostToDevice));
+    if (per > 0) {
+      SMI_HIP(hipMemcpy(L->pval + c * n * nblk, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
+      SMI_HIP(hipMemcpy(L->pidx + c * n * nblk, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
+    }
+  }
+  return SMI_OK;
+}
+// Row m's context ctx[m][0 .. ctx_len[m]), of which the first prompt_len[m] ids are its prompt: the checks of `who`
+// (smi_llm_debug_seqbias: a prompt of 1 or more ids; smi_llm_debug_ngram, `store`: 0 or more, which must fit the prompt store);
+// *gen = the tokens the row has emitted.
+static int alone_ctx_check(const smi_llm* L, const char* who, int m, const int64_t* ctx, const int32_t* ctx_len, const int32_t* prompt_len,
+                           int ctx_cap, bool store, int32_t* gen) {
+  const int V = L->cfg.vocab_size, lo = store ? 0 : 1;
+  SMI_REQUIRE(prompt_len[m] >= lo && prompt_len[m] <= ctx_len[m] && ctx_len[m] <= ctx_cap && (!store || prompt_len[m] <= L->cfg.max_positions),
+              "%s: row %d: %d <= prompt_len <= ctx_len <= ctx_cap%s does not hold", who, m, lo, store ? ", prompt_len <= max_positions" : "");
+  SMI_REQUIRE(ctx_len[m] - prompt_len[m] < L->max_steps, "%s: row %d: more generated tokens than the history holds", who, m);
+  for (int t = 0; t < ctx_len[m]; ++t)
+    SMI_REQUIRE(ctx[(size_t)m * ctx_cap + t] >= 0 && ctx[(size_t)m * ctx_cap + t] < V, "%s: ctx[%d][%d] outside the vocabulary", who, m, t);
+  *gen = ctx_len[m] - prompt_len[m];
+  return SMI_OK;
+}
+// Context staging: the generated tokens of every row into the token history, as k_finalize would have left them, and -- `store`
+// -- the prompts into the slots' rows of the prompt store.
+static int alone_contexts(smi_llm* L, int n, const int64_t* ctx, const int32_t* ctx_len, const int32_t* prompt_len, int ctx_cap, bool store) {
+  const int P = L->cfg.max_positions;
+  int max_gen = 0;
+  for (int m = 0; m < n; ++m) max_gen = ctx_len[m] - prompt_len[m] > max_gen ? ctx_len[m] - prompt_len[m] : max_gen;
+  if (store) {
+    std::vector<int32_t> pctx((size_t)n * P, 0);
+    for (int m = 0; m < n; ++m)
+      for (int t = 0; t < prompt_len[m]; ++t) pctx[(size_t)m * P + t] = (int32_t)ctx[(size_t)m * ctx_cap + t];
+    SMI_HIP(hipMemcpy(L->pctx, pctx.data(), pctx.size() * 4, hipMemcpyHostToDevice));
+  }
+  if (max_gen > 0) {
+    std::vector<int64_t> hist((size_t)max_gen * kMaxRows, 0);
+    for (int m = 0; m < n; ++m)
+      for (int t = prompt_len[m]; t < ctx_len[m]; ++t) hist[(size_t)(t - prompt_len[m]) * kMaxRows + m] = ctx[(size_t)m * ctx_cap + t];
+    SMI_HIP(hipMemcpy(L->hist, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
+  }
+  return SMI_OK;
+}
+// A sampling row that keeps only its arg-max: k_penalize writes such a row's processed logits back, and k_finalize, handed no
+// sampler tokens, takes the arg-max.
+static SampRec samp_neutral() {
+  SampRec r;
+  memset(&r, 0, sizeof(r));
+  r.mode = SMI_SAMPLING_SAMPLE; r.top_k = 1; r.inv_temp = 1.f; r.top_p = 1.f;
+  return r;
+}
+// Commit: the controls as the entry wrote them, no row finished and -- where the sampler runs -- empty candidate lists.
+static int alone_commit(smi_llm* L, bool sampler) {
+  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
+  if (sampler) SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
+  return SMI_OK;
+}
+// Fetch: wait for the launches, then what the caller asks for of the first n rows (each nullable): the logits rows [n][V], the
+// tokens k_finalize left in the row descriptors, the finished flags.
+static int alone_fetch(smi_llm* L, int n, float* logits_out, int32_t* token_out, int32_t* finished_out) {
+  SMI_HIP(hipDeviceSynchronize());
+  if (logits_out) SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n * L->cfg.vocab_size * 4, hipMemcpyDeviceToHost));
+  if (finished_out) SMI_HIP(hipMemcpy(finished_out, L->finished, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (token_out) {
+    std::vector<RowDesc> after((size_t)n);
+    SMI_HIP(hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost));
+    for (int m = 0; m < n; ++m) token_out[m] = after[m].token;
+  }
+  return SMI_OK;
+}
 
 // Tests: the sampler alone on a caller's logits row (see sparkmi_debug.h).
 int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint64_t seed, int use_bound, int32_t* tokens_out) {
@@ -7118,31 +7227,16 @@ int smi_llm_debug_sample(smi_llm* L, const float* logits_host, int n_rows, uint6
   SMI_REQUIRE(L->do_sample, "smi_llm_debug_sample: smi_llm_set_sampling(do_sample = 1, ...) first");
   const int V = L->cfg.vocab_size;
   const int nblk = lm_blocks_for(L, n_rows);
-  { const int rcb = alone_begin(L, kMaxRows, nullptr); if (rcb) return rcb; }   // (clean records: every row inherits the handle's settings)
-  if (logits_host) {
-    // what the lm_head blocks would have left: one maximum per block; here block j holds the j-th contiguous share of the row
-    std::vector<float> pv;
-    std::vector<int32_t> pi;
-    block_maxima(logits_host, 1, V, nblk, (V + nblk - 1) / nblk, pv, pi);
-    for (int m = 0; m < kMaxRows; ++m) {
-      SMI_HIP(hipMemcpy(L->logits + (size_t)m * V, logits_host, (size_t)V * 4, hipMemcpyHostToDevice));
-      SMI_HIP(hipMemcpy(L->pval + (size_t)m * nblk, pv.data(), (size_t)nblk * 4, hipMemcpyHostToDevice));
-    }
-  }
+  Alone run(L, kMaxRows, nullptr);   // (clean records: every row inherits the handle's settings)
+  SMI_TRY(run.rc);
+  // what the lm_head blocks would have left: one maximum per block; here block j holds the j-th contiguous share of the row
+  if (logits_host) SMI_TRY(alone_rows(L, logits_host, 1, nblk, (V + nblk - 1) / nblk, kMaxRows));
   for (int m = 0; m < kMaxRows; ++m) L->hctl.seqid[m] = m;
   L->hctl.seed = seed;
-  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
-  SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
-  SampleP sp = sample_params(L, n_rows);
-  sp.hs = 1;
-  if (!use_bound) sp.pval = nullptr;
-  hipLaunchKernelGGL(k_sample_scan, dim3(kScanBlocks, n_rows), dim3(256), 0, 0, sp);
-  SMI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sample, dim3(n_rows), dim3(1024), 0, 0, sp);
-  SMI_LAUNCH_CHECK();
+  SMI_TRY(alone_commit(L, true));
+  SMI_TRY(launch_sampler(L, n_rows, use_bound != 0, 0));
   SMI_HIP(hipDeviceSynchronize());
   SMI_HIP(hipMemcpy(tokens_out, L->tok, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
-  alone_end(L);
   return SMI_OK;
 }
 
@@ -7151,14 +7245,12 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
                            const int32_t* emitted_host, float* logits_out, int32_t* argmax_out) {
   SMI_REQUIRE(L && logits_host && hist_host && pens && emitted_host && logits_out && argmax_out, "smi_llm_debug_penalize: null argument");
   SMI_REQUIRE(n_rows >= 1 && n_rows <= L->cfg.max_slots && n_rows <= kMaxRows, "smi_llm_debug_penalize: n_rows=%d outside 1..max_slots", n_rows);
-  for (int m = 0; m < n_rows; ++m) {
-    const int rcp = validate_penalty(L, pens[m], m);
-    if (rcp) return rcp;
-  }
+  for (int m = 0; m < n_rows; ++m) SMI_TRY(validate_penalty(L, pens[m], m));
   const size_t V = (size_t)L->cfg.vocab_size;
   const int nblk = lm_blocks_for(L, n_rows);
-  { const int rcb = alone_begin(L, n_rows, emitted_host); if (rcb) return rcb; }
-  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
+  Alone run(L, n_rows, emitted_host);
+  SMI_TRY(run.rc);
+  SMI_TRY(alone_rows(L, logits_host, n_rows, nblk, 0));
   SMI_HIP(hipMemcpy(L->phist, hist_host, (size_t)n_rows * V * 2, hipMemcpyHostToDevice));
   for (int m = 0; m < n_rows; ++m) {
     L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: the kernel writes its processed logits back)
@@ -7166,13 +7258,9 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
     r = pen_record(&pens[m]);
     if (!r.on) { r.rep = 1.f; r.prompt = pens[m].penalize_prompt; r.on = 1; }   // a neutral record runs too: as the identity
   }
-  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
-  PenP pp = pen_params(L, n_rows);
-  pp.hs = 0;
-  hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
-  SMI_LAUNCH_CHECK();
-  SMI_HIP(hipDeviceSynchronize());
-  SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n_rows * V * 4, hipMemcpyDeviceToHost));
+  SMI_TRY(alone_commit(L, false));
+  SMI_TRY(launch_penalize(L, n_rows, nullptr, 0));
+  SMI_TRY(alone_fetch(L, n_rows, logits_out, nullptr, nullptr));
   std::vector<float> pv((size_t)n_rows * nblk);
   std::vector<int32_t> pi((size_t)n_rows * nblk);
   SMI_HIP(hipMemcpy(pv.data(), L->pval, pv.size() * 4, hipMemcpyDeviceToHost));
@@ -7187,7 +7275,6 @@ int smi_llm_debug_penalize(smi_llm* L, const float* logits_host, int n_rows, con
     }
     argmax_out[m] = bi;
   }
-  alone_end(L);
   return SMI_OK;
 }
 
@@ -7202,36 +7289,25 @@ int smi_llm_debug_logprob(smi_llm* L, const float* logits_host, int n_rows, cons
     SMI_REQUIRE(tokens_host[m] >= 0 && tokens_host[m] < V, "smi_llm_debug_logprob: tokens[%d]=%d outside the vocabulary", m, tokens_host[m]);
   }
   SMI_REQUIRE(L->max_steps >= 1, "smi_llm_debug_logprob: no history");
-  const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
-  std::vector<float> pv;
-  std::vector<int32_t> pi;
-  block_maxima(logits_host, n_rows, V, nblk, per, pv, pi);
-  { const int rcb = alone_begin(L, n_rows, nullptr); if (rcb) return rcb; }
-  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
+  const int nblk = lm_blocks_for(L, n_rows);
+  Alone run(L, n_rows, nullptr);
+  SMI_TRY(run.rc);
+  SMI_TRY(alone_rows(L, logits_host, n_rows, nblk, pen_set_ids(V, nblk)));
   SMI_HIP(hipMemcpy(L->tok, tokens_host, (size_t)n_rows * 4, hipMemcpyHostToDevice));
   for (int m = 0; m < n_rows; ++m) {   // (no tokens emitted: k_finalize writes lp[0][m])
     SampRec& r = L->hctl.samp[m];
-    r.mode = SMI_SAMPLING_SAMPLE;    // a sampling row: its token is the caller's (L->tok) and its z is scaled by 1/T
+    r = samp_neutral();              // a sampling row: its token is the caller's (L->tok) and its z is scaled by 1/T
     r.inv_temp = 1.0f / temperature_host[m];
-    r.top_k = 1; r.top_p = 1.f;
     L->hctl.lp[m] = 1;
   }
-  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
-  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
-  LpP lp = lp_params(L, n_rows);
-  lp.hs = 0;
-  hipLaunchKernelGGL(k_logprob, dim3(kLpBlocks, n_rows), dim3(256), 0, 0, lp);
-  SMI_LAUNCH_CHECK();
+  SMI_TRY(alone_commit(L, false));
+  SMI_TRY(launch_logprob(L, n_rows, 0));
   FinP f = fin_params(L, n_rows);
-  f.tok = L->tok; f.hs = 0;
+  f.tok = L->tok;
   f.lp = L->lp; f.lp_part = L->lp_part; f.lp_rowc = L->lp_rowc;
-  hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
-  SMI_LAUNCH_CHECK();
+  SMI_TRY(launch_finalize(f, 0));
   SMI_HIP(hipDeviceSynchronize());
   SMI_HIP(hipMemcpy(lp_out, L->lp, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
-  alone_end(L);
   return SMI_OK;
 }
 
@@ -7242,34 +7318,18 @@ int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, cons
   SMI_REQUIRE(L && logits_host && seq && ctx_host && ctx_len_host && prompt_len_host && logits_out && token_out && finished_out,
               "smi_llm_debug_seqbias: null argument");
   SMI_REQUIRE(n_rows >= 1 && n_rows <= L->cfg.max_slots && n_rows <= kMaxRows, "smi_llm_debug_seqbias: n_rows=%d outside 1..max_slots", n_rows);
-  const int V = L->cfg.vocab_size;
-  for (int m = 0; m < n_rows; ++m) {
-    const int rcq = validate_seq(L, seq[m], nullptr, nullptr, m);
-    if (rcq) return rcq;
-    SMI_REQUIRE(prompt_len_host[m] >= 1 && prompt_len_host[m] <= ctx_len_host[m] && ctx_len_host[m] <= ctx_cap,
-                "smi_llm_debug_seqbias: row %d: 1 <= prompt_len <= ctx_len <= ctx_cap does not hold", m);
-    SMI_REQUIRE(ctx_len_host[m] - prompt_len_host[m] < L->max_steps, "smi_llm_debug_seqbias: row %d: more generated tokens than the history holds", m);
-    SMI_REQUIRE(!min_new_host || (min_new_host[m] >= 0 && min_new_host[m] <= L->cfg.max_positions), "smi_llm_debug_seqbias: min_new[%d] out of range", m);
-    for (int t = 0; t < ctx_len_host[m]; ++t)
-      SMI_REQUIRE(ctx_host[(size_t)m * ctx_cap + t] >= 0 && ctx_host[(size_t)m * ctx_cap + t] < V, "smi_llm_debug_seqbias: ctx[%d][%d] outside the vocabulary", m, t);
-  }
-  const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
-  std::vector<float> pv;
-  std::vector<int32_t> pi;
-  block_maxima(logits_host, n_rows, V, nblk, per, pv, pi);
   int32_t gen[kMaxRows];   // tokens emitted so far, per row
-  int max_gen = 0;
   for (int m = 0; m < n_rows; ++m) {
-    gen[m] = ctx_len_host[m] - prompt_len_host[m];
-    max_gen = gen[m] > max_gen ? gen[m] : max_gen;
+    SMI_TRY(validate_seq(L, seq[m], nullptr, nullptr, m));
+    SMI_REQUIRE(!min_new_host || (min_new_host[m] >= 0 && min_new_host[m] <= L->cfg.max_positions), "smi_llm_debug_seqbias: min_new[%d] out of range", m);
+    SMI_TRY(alone_ctx_check(L, "smi_llm_debug_seqbias", m, ctx_host, ctx_len_host, prompt_len_host, ctx_cap, false, &gen[m]));
   }
-  { const int rcb = alone_begin(L, n_rows, gen); if (rcb) return rcb; }
-  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
+  const int nblk = lm_blocks_for(L, n_rows);
+  Alone run(L, n_rows, gen);
+  SMI_TRY(run.rc);
+  SMI_TRY(alone_rows(L, logits_host, n_rows, nblk, pen_set_ids(L->cfg.vocab_size, nblk)));
   for (int m = 0; m < n_rows; ++m) {
-    L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: k_penalize writes its processed logits back; k_finalize gets no
-    L->hctl.samp[m].top_k = 1; L->hctl.samp[m].inv_temp = 1.f; L->hctl.samp[m].top_p = 1.f;   // sampler tokens and takes the arg-max)
+    L->hctl.samp[m] = samp_neutral();
     if (min_new_host && min_new_host[m] > 0) {   // only min_new of a neutral penalty record: the stop match reads it
       L->hctl.pen[m].rep = 1.f; L->hctl.pen[m].min_new = min_new_host[m];
     }
@@ -7277,31 +7337,14 @@ int smi_llm_debug_seqbias(smi_llm* L, const float* logits_host, int n_rows, cons
     if (L->hseq[(size_t)m].plen == 0) L->hseq[(size_t)m].plen = prompt_len_host[m];
     L->seq_dirty[m] = 1;
   }
-  if (max_gen > 0) {   // the generated tokens of every row, as k_finalize would have left them
-    std::vector<int64_t> hist((size_t)max_gen * kMaxRows, 0);
-    for (int m = 0; m < n_rows; ++m)
-      for (int t = prompt_len_host[m]; t < ctx_len_host[m]; ++t) hist[(size_t)(t - prompt_len_host[m]) * kMaxRows + m] = ctx_host[(size_t)m * ctx_cap + t];
-    SMI_HIP(hipMemcpy(L->hist, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
-  }
+  SMI_TRY(alone_contexts(L, n_rows, ctx_host, ctx_len_host, prompt_len_host, ctx_cap, false));
   SMI_HIP(hipMemcpy(L->seq, L->hseq.data(), (size_t)n_rows * sizeof(SeqRec), hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
-  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
-  PenP pp = pen_params(L, n_rows);
-  pp.hs = 0; pp.seq = L->seq;
-  hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
-  SMI_LAUNCH_CHECK();
+  SMI_TRY(alone_commit(L, false));
+  SMI_TRY(launch_penalize(L, n_rows, L->seq, 0));
   FinP f = fin_params(L, n_rows);
-  f.hs = 0; f.seq = L->seq;
-  hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
-  SMI_LAUNCH_CHECK();
-  SMI_HIP(hipDeviceSynchronize());
-  SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n_rows * V * 4, hipMemcpyDeviceToHost));
-  SMI_HIP(hipMemcpy(finished_out, L->finished, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
-  std::vector<RowDesc> after(kMaxRows);
-  SMI_HIP(hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost));
-  for (int m = 0; m < n_rows; ++m) token_out[m] = after[m].token;
-  alone_end(L);
-  return SMI_OK;
+  f.seq = L->seq;
+  SMI_TRY(launch_finalize(f, 0));
+  return alone_fetch(L, n_rows, logits_out, token_out, finished_out);
 }
 
 // Tests: the n-gram ban, k_penalize and k_finalize alone on caller rows (see sparkmi_debug.h).
@@ -7310,117 +7353,25 @@ int smi_llm_debug_ngram(smi_llm* L, const float* logits_host, int n_rows, const 
   SMI_REQUIRE(L && logits_host && ngram_host && ctx_host && ctx_len_host && prompt_len_host && logits_out && token_out,
               "smi_llm_debug_ngram: null argument");
   SMI_REQUIRE(n_rows >= 1 && n_rows <= L->cfg.max_slots && n_rows <= kMaxRows, "smi_llm_debug_ngram: n_rows=%d outside 1..max_slots", n_rows);
-  const int V = L->cfg.vocab_size, P = L->cfg.max_positions;
+  int32_t gen[kMaxRows];   // tokens emitted so far, per row
   for (int m = 0; m < n_rows; ++m) {
     SMI_REQUIRE(ngram_host[m] >= 0 && ngram_host[m] <= SMI_MAX_NGRAM, "smi_llm_debug_ngram: ngram[%d]=%d outside 0..%d", m, ngram_host[m], SMI_MAX_NGRAM);
-    SMI_REQUIRE(prompt_len_host[m] >= 0 && prompt_len_host[m] <= ctx_len_host[m] && ctx_len_host[m] <= ctx_cap && prompt_len_host[m] <= P,
-                "smi_llm_debug_ngram: row %d: 0 <= prompt_len <= ctx_len <= ctx_cap, prompt_len <= max_positions does not hold", m);
-    SMI_REQUIRE(ctx_len_host[m] - prompt_len_host[m] < L->max_steps, "smi_llm_debug_ngram: row %d: more generated tokens than the history holds", m);
-    for (int t = 0; t < ctx_len_host[m]; ++t)
-      SMI_REQUIRE(ctx_host[(size_t)m * ctx_cap + t] >= 0 && ctx_host[(size_t)m * ctx_cap + t] < V, "smi_llm_debug_ngram: ctx[%d][%d] outside the vocabulary", m, t);
+    SMI_TRY(alone_ctx_check(L, "smi_llm_debug_ngram", m, ctx_host, ctx_len_host, prompt_len_host, ctx_cap, true, &gen[m]));
   }
-  const int nblk = lm_blocks_for(L, n_rows), per = pen_set_ids(V, nblk);
-  std::vector<float> pv;
-  std::vector<int32_t> pi;
-  block_maxima(logits_host, n_rows, V, nblk, per, pv, pi);
-  int32_t gen[kMaxRows];   // tokens emitted so far, per row
-  int max_gen = 0;
+  const int nblk = lm_blocks_for(L, n_rows);
+  Alone run(L, n_rows, gen);
+  SMI_TRY(run.rc);
+  SMI_TRY(alone_rows(L, logits_host, n_rows, nblk, pen_set_ids(L->cfg.vocab_size, nblk)));
   for (int m = 0; m < n_rows; ++m) {
-    gen[m] = ctx_len_host[m] - prompt_len_host[m];
-    max_gen = gen[m] > max_gen ? gen[m] : max_gen;
-  }
-  { const int rcb = alone_begin(L, n_rows, gen); if (rcb) return rcb; }
-  SMI_HIP(hipMemcpy(L->logits, logits_host, (size_t)n_rows * V * 4, hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->pval, pv.data(), pv.size() * 4, hipMemcpyHostToDevice));
-  SMI_HIP(hipMemcpy(L->pidx, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
-  std::vector<int32_t> pctx((size_t)n_rows * P, 0);
-  for (int m = 0; m < n_rows; ++m) {
-    L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;   // (a sampling row: k_penalize writes its processed logits back; k_finalize gets no
-    L->hctl.samp[m].top_k = 1; L->hctl.samp[m].inv_temp = 1.f; L->hctl.samp[m].top_p = 1.f;   // sampler tokens and takes the arg-max)
+    L->hctl.samp[m] = samp_neutral();
     L->hctl.ngram[m] = ngram_host[m]; L->hctl.ngplen[m] = prompt_len_host[m];
-    for (int t = 0; t < prompt_len_host[m]; ++t) pctx[(size_t)m * P + t] = (int32_t)ctx_host[(size_t)m * ctx_cap + t];
   }
-  SMI_HIP(hipMemcpy(L->pctx, pctx.data(), pctx.size() * 4, hipMemcpyHostToDevice));
-  if (max_gen > 0) {   // the generated tokens of every row, as k_finalize would have left them
-    std::vector<int64_t> hist((size_t)max_gen * kMaxRows, 0);
-    for (int m = 0; m < n_rows; ++m)
-      for (int t = prompt_len_host[m]; t < ctx_len_host[m]; ++t) hist[(size_t)(t - prompt_len_host[m]) * kMaxRows + m] = ctx_host[(size_t)m * ctx_cap + t];
-    SMI_HIP(hipMemcpy(L->hist, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
-  }
-  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
-  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
-  size_t lds;
-  const NgramP np = ngram_params(L, &lds);
-  hipLaunchKernelGGL(k_ngram_ban, dim3(1, n_rows), dim3(256), lds, 0, np);
-  SMI_LAUNCH_CHECK();
-  PenP pp = pen_params(L, n_rows);
-  pp.hs = 0;
-  hipLaunchKernelGGL(k_penalize, dim3((nblk + kPenWaves - 1) / kPenWaves, n_rows), dim3(256), 0, 0, pp);
-  SMI_LAUNCH_CHECK();
-  FinP f = fin_params(L, n_rows);
-  f.hs = 0;
-  hipLaunchKernelGGL(k_finalize, dim3(n_rows), dim3(256), 0, 0, f);
-  SMI_LAUNCH_CHECK();
-  SMI_HIP(hipDeviceSynchronize());
-  SMI_HIP(hipMemcpy(logits_out, L->logits, (size_t)n_rows * V * 4, hipMemcpyDeviceToHost));
-  std::vector<RowDesc> after(kMaxRows);
-  SMI_HIP(hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost));
-  for (int m = 0; m < n_rows; ++m) token_out[m] = after[m].token;
-  alone_end(L);
-  return SMI_OK;
-}
-
-// smi_llm_debug_head between alone_begin and alone_end: whatever it returns, the caller frees *psrc and restores the clean records
-static int head_run(smi_llm* L, int M, smi_head_io* io, int V, int nblk, float** psrc) {
-  graphs_flush(L);
-  L->B = M; L->identity_slots = 1; L->session = 0; L->started = 0; L->attn_seg = 1;
-  L->lm_restrict = io->allow != nullptr;
-  for (int m = 0; m < M; ++m) {
-    L->hctl.seqid[m] = m;
-    if (io->reads && io->reads[m]) {   // a neutral sampling record, as smi_llm_debug_seqbias installs it; here the step's features see it too
-      L->hctl.samp[m].mode = SMI_SAMPLING_SAMPLE;
-      L->hctl.samp[m].top_k = 1; L->hctl.samp[m].inv_temp = 1.f; L->hctl.samp[m].top_p = 1.f;
-      L->slot_feat[m] |= F_SAMPLE;
-    }
-    if (io->allow) {
-      L->hctl.allow[m] = allow_record(&io->allow[m], V);
-      if (L->hctl.allow[m].n > 0) L->slot_feat[m] |= F_ALLOW;
-    }
-    L->lm_restrict &= (L->slot_feat[m] & F_ALLOW) != 0;   // live_set's rule
-  }
-  L->hctl.seed = 0;
-  { const int rct = allow_tiles_upload(L, 0); if (rct) return rct; }
-  SMI_HIP(hipMemcpy(L->ctl, &L->hctl, sizeof(Ctl), hipMemcpyHostToDevice));
-  SMI_HIP(hipMemset(L->finished, 0, kMaxRows * 4));
-  SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
-  if (io->flags & SMI_HEAD_POISON) SMI_HIP(hipMemset(L->logits, 0xff, (size_t)kMaxRows * V * 4));   // 0xffffffff: a quiet NaN
-  SMI_HIP(hipMalloc((void**)psrc, (size_t)M * L->H * 4));
-  int rc = SMI_OK;
-  if (hipMemcpy(*psrc, io->hidden, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: upload failed"); }
-  if (rc == SMI_OK) {
-    hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, *psrc, L->KTh, M, (const float*)sec(L, SMI_LLM_FINAL_NORM, 0), L->dec.h,
-                       L->dec.xs_h, L->dec.ss, L->NTh * 4);
-    if (hipGetLastError() != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: k_load_hidden launch failed"); }
-  }
-  L->lm_note_n = 0; L->lm_note_form[0] = 0; L->lm_note_grid[0] = L->lm_note_grid[1] = L->lm_note_block = 0;
-  if (rc == SMI_OK) rc = launch_one(L, KLM, 0, L->rows, M, nullptr, 0);
-  if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: lm_head failed: %s", hipGetErrorString(hipGetLastError())); }
-  io->nblk = nblk; io->launches = L->lm_note_n; io->grid[0] = L->lm_note_grid[0]; io->grid[1] = L->lm_note_grid[1]; io->block = L->lm_note_block;
-  memcpy(io->form, L->lm_note_form, sizeof(io->form));
-  if (rc == SMI_OK && io->logits_lm && hipMemcpy(io->logits_lm, L->logits, (size_t)M * V * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
-  if (rc == SMI_OK && io->pval && hipMemcpy(io->pval, L->pval, (size_t)M * nblk * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
-  if (rc == SMI_OK && io->pidx && hipMemcpy(io->pidx, L->pidx, (size_t)M * nblk * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
-  if (rc == SMI_OK && (io->flags & SMI_HEAD_FIN)) {
-    rc = launch_one(L, KFIN, 0, L->rows, M, nullptr, 0);
-    if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_head: finalize failed: %s", hipGetErrorString(hipGetLastError())); }
-    if (rc == SMI_OK && io->logits_fin && hipMemcpy(io->logits_fin, L->logits, (size_t)M * V * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
-    if (rc == SMI_OK && io->tokens) {
-      std::vector<RowDesc> after(kMaxRows);
-      if (hipMemcpy(after.data(), L->rows, after.size() * sizeof(RowDesc), hipMemcpyDeviceToHost) != hipSuccess) rc = SMI_EHIP;
-      for (int m = 0; m < M; ++m) io->tokens[m] = after[m].token;
-    }
-  }
-  return rc;
+  SMI_TRY(alone_contexts(L, n_rows, ctx_host, ctx_len_host, prompt_len_host, ctx_cap, true));
+  SMI_TRY(alone_commit(L, false));
+  SMI_TRY(launch_ngram_ban(L, n_rows, 0));
+  SMI_TRY(launch_penalize(L, n_rows, nullptr, 0));
+  SMI_TRY(launch_finalize(fin_params(L, n_rows), 0));
+  return alone_fetch(L, n_rows, logits_out, token_out, nullptr);
 }
 
 // Tests: the head of a decode step alone on caller rows -- launch_one(KLM), then launch_one(KFIN) -- (see sparkmi_debug.h).
@@ -7432,13 +7383,45 @@ int smi_llm_debug_head(smi_llm* L, int M, smi_head_io* io) {
   SMI_REQUIRE((!io->pval && !io->pidx) || (size_t)io->pcap >= (size_t)M * nblk, "smi_llm_debug_head: pval / pidx hold %d entries, %d rows x %d columns needed",
               io->pcap, M, nblk);
   if (io->allow)
-    for (int m = 0; m < M; ++m) { const int rcv = validate_allow(L, io->allow[m], nullptr, m); if (rcv) return rcv; }
-  { const int rcb = alone_begin(L, M, nullptr); if (rcb) return rcb; }
-  float* src = nullptr;
-  const int rc = head_run(L, M, io, V, nblk, &src);
-  if (src) (void)hipFree(src);
-  alone_end(L);
-  return rc;
+    for (int m = 0; m < M; ++m) SMI_TRY(validate_allow(L, io->allow[m], nullptr, m));
+  Alone run(L, M, nullptr);
+  SMI_TRY(run.rc);
+  graphs_flush(L);
+  L->B = M; L->identity_slots = 1; L->session = 0; L->started = 0; L->attn_seg = 1;
+  L->lm_restrict = io->allow != nullptr;
+  for (int m = 0; m < M; ++m) {
+    L->hctl.seqid[m] = m;
+    if (io->reads && io->reads[m]) {   // a neutral sampling record; here the step's features see it too
+      L->hctl.samp[m] = samp_neutral();
+      L->slot_feat[m] |= F_SAMPLE;
+    }
+    if (io->allow) {
+      L->hctl.allow[m] = allow_record(&io->allow[m], V);
+      if (L->hctl.allow[m].n > 0) L->slot_feat[m] |= F_ALLOW;
+    }
+    L->lm_restrict &= (L->slot_feat[m] & F_ALLOW) != 0;   // live_set's rule
+  }
+  L->hctl.seed = 0;
+  SMI_TRY(allow_tiles_upload(L, 0));
+  SMI_TRY(alone_commit(L, true));
+  if (io->flags & SMI_HEAD_POISON) SMI_HIP(hipMemset(L->logits, 0xff, (size_t)kMaxRows * V * 4));   // 0xffffffff: a quiet NaN
+  SMI_HIP(hipMalloc((void**)&run.dev, (size_t)M * L->H * 4));
+  SMI_HIP(hipMemcpy(run.dev, io->hidden, (size_t)M * L->H * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, run.dev, L->KTh, M, (const float*)sec(L, SMI_LLM_FINAL_NORM, 0), L->dec.h,
+                     L->dec.xs_h, L->dec.ss, L->NTh * 4);
+  SMI_LAUNCH_CHECK();
+  L->lm_note_n = 0; L->lm_note_form[0] = 0; L->lm_note_grid[0] = L->lm_note_grid[1] = L->lm_note_block = 0;
+  SMI_TRY(launch_one(L, KLM, 0, L->rows, M, nullptr, 0));
+  SMI_TRY(alone_fetch(L, M, io->logits_lm, nullptr, nullptr));
+  io->nblk = nblk; io->launches = L->lm_note_n; io->grid[0] = L->lm_note_grid[0]; io->grid[1] = L->lm_note_grid[1]; io->block = L->lm_note_block;
+  memcpy(io->form, L->lm_note_form, sizeof(io->form));
+  if (io->pval) SMI_HIP(hipMemcpy(io->pval, L->pval, (size_t)M * nblk * 4, hipMemcpyDeviceToHost));
+  if (io->pidx) SMI_HIP(hipMemcpy(io->pidx, L->pidx, (size_t)M * nblk * 4, hipMemcpyDeviceToHost));
+  if (io->flags & SMI_HEAD_FIN) {
+    SMI_TRY(launch_one(L, KFIN, 0, L->rows, M, nullptr, 0));
+    SMI_TRY(alone_fetch(L, M, io->logits_fin, io->tokens, nullptr));
+  }
+  return SMI_OK;
 }
 
 // Diagnostics (SPARKMI_ENGINE_STAMPS=1): out[3][layers][16] microseconds since the first stamp of the last engine launch:

@@ -1063,6 +1063,17 @@ class SparkLLM:
                                                          am.ctypes.data_as(C.POINTER(C.c_int32))), "smi_llm_debug_penalize")
         return out, am
 
+    @staticmethod
+    def _pack_contexts(contexts: Sequence[Sequence[int]], prompt_lens: Sequence[int]):
+        """What ``debug_seqbias`` / ``debug_ngram`` hand the library: the contexts zero-padded to (n, cap) int64, their lengths and
+        the prompt lengths as int32, cap (at least 1)."""
+        cl = np.asarray([len(c) for c in contexts], dtype=np.int32)
+        cap = max(int(cl.max()), 1)
+        ctx = np.zeros((len(contexts), cap), dtype=np.int64)
+        for i, c in enumerate(contexts):
+            ctx[i, : len(c)] = np.asarray(c, dtype=np.int64)
+        return ctx, cl, np.ascontiguousarray(prompt_lens, dtype=np.int32), cap
+
     def debug_seqbias(self, logits: np.ndarray, requests: Sequence[Optional[Mapping]], contexts: Sequence[Sequence[int]],
                       prompt_lens: Sequence[int], min_new: Optional[Sequence[int]] = None):
         """The bias stage and ``k_finalize``'s stop match alone (``smi_llm_debug_seqbias``) on caller rows: ``logits`` [n][vocab]
@@ -1076,12 +1087,7 @@ class SparkLLM:
         recs = seq_records(list(requests), n, self.cfg.vocab_size)
         if recs is None:
             recs = (_lib.SeqParams * n)()
-        cl = np.asarray([len(c) for c in contexts], dtype=np.int32)
-        cap = int(cl.max())
-        ctx = np.zeros((n, cap), dtype=np.int64)
-        for i, c in enumerate(contexts):
-            ctx[i, : len(c)] = np.asarray(c, dtype=np.int64)
-        pl = np.ascontiguousarray(prompt_lens, dtype=np.int32)
+        ctx, cl, pl, cap = self._pack_contexts(contexts, prompt_lens)
         mn = None if min_new is None else np.ascontiguousarray(min_new, dtype=np.int32)
         out = np.empty_like(lg)
         tok = np.zeros(n, dtype=np.int32)
@@ -1154,12 +1160,7 @@ class SparkLLM:
         if lg.shape != (n, self.cfg.vocab_size) or len(sizes) != n or len(contexts) != n or len(prompt_lens) != n:
             raise ValueError("debug_ngram: logits [n][vocab], n sizes, n contexts, n prompt lengths")
         ng = np.asarray([ngram_size(v) for v in sizes], dtype=np.int32)
-        cl = np.asarray([len(c) for c in contexts], dtype=np.int32)
-        cap = max(int(cl.max()), 1)
-        ctx = np.zeros((n, cap), dtype=np.int64)
-        for i, c in enumerate(contexts):
-            ctx[i, : len(c)] = np.asarray(c, dtype=np.int64)
-        pl = np.ascontiguousarray(prompt_lens, dtype=np.int32)
+        ctx, cl, pl, cap = self._pack_contexts(contexts, prompt_lens)
         out = np.empty_like(lg)
         tok = np.zeros(n, dtype=np.int32)
         i32 = C.POINTER(C.c_int32)
