@@ -255,7 +255,7 @@ int smi_voc_block_plan(const smi_voc_block_cfg* cfg, int B, int L, smi_block_lau
  * dynamic LDS size and arguments are those of a real encode of the same (n_samples, n_ref), because the list is the one
  * smi_enc_forward's graph path builds (tests/test_enc_ops_gpu.py).
  *   smi_enc_debug_build: builds the launch list on the handle-owned in_wav / in_ref / out_sem / out_glob buffers, uploads the
- *     length slots and runs nothing.  smi_enc_forward's argument checks apply (SMI_EINVAL before any GPU call).  The captured
+ *     row's lengths and runs nothing.  smi_enc_forward's argument checks apply (SMI_EINVAL before any GPU call).  The captured
  *     graphs of the handle are left alone.  *n_frames = wav2vec2 frames, *n_launches = launches of the list.
  *   smi_enc_debug_launch: launch `index` of the list: name (at most cap bytes) and info[8] = {kind (0 conv, 1 k_dwln,
  *     9 one of the encoder's small kernels), grid x, y, z, threads per block, dynamic LDS bytes, k_dwln's instantiated channels

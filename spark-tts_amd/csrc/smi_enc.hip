@@ -18,6 +18,7 @@
 // (smi_net.h); attention and the 128-tap grouped positional conv are VALU kernels (small: T <= ~1500).
 #include "smi_net.h"
 #include <math.h>
+#include <algorithm>
 #include <map>
 
 namespace {
@@ -28,8 +29,8 @@ namespace {
 
 // Every kernel below carries a row dimension: block z is row b of the launch, the row's lengths come from device arrays indexed by
 // b (one per length kind) and its buffers sit b batch strides on.  A row's arithmetic depends on its own lengths only and blocks
-// beyond a row's own extent exit without writing, so a row of a ragged launch carries the bits of its solo launch (one row,
-// batch strides 0: smi_enc_forward's list).
+// beyond a row's own extent exit without writing, so a row of a ragged launch carries the bits of its solo launch (the same
+// kernels over one row: smi_enc_forward's list).
 
 // (x - mean) / sqrt(var + 1e-7), feature_extraction_wav2vec2.py zero_mean_unit_var_norm; one block per row.
 __global__ __launch_bounds__(1024) void k_wavnorm(const float* x, long long xbs, const int* ns, float* y, long long ybs) {
@@ -179,16 +180,8 @@ __global__ __launch_bounds__(256) void k_mha(MhaP p) {
 }
 
 // hidden-state taps: mode 0: acc = h; 1: acc = acc + h; 2: out = (acc + h) / 3   (audio_tokenizer.py:96-98)
-__global__ void k_tap(const float* h, float* acc, float* out, long long n, int mode) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (mode == 0) acc[i] = h[i];
-  else if (mode == 1) acc[i] = acc[i] + h[i];
-  else out[i] = (acc[i] + h[i]) / 3.0f;
-}
-
-// the same over rows of a ragged launch: [Hd][stride] per row, indexed by (channel, frame) -- a row's own T is not its stride
-__global__ void k_tap_rows(const float* h, float* acc, float* out, const int* Ts, int stride, long long bs, int mode) {
+// [Hd][stride] per row, indexed by (channel, frame) -- a row's own T is not its stride
+__global__ void k_tap(const float* h, float* acc, float* out, const int* Ts, int stride, long long bs, int mode) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= Ts[blockIdx.z]) return;
   const long long i = blockIdx.z * bs + (long long)blockIdx.y * stride + t;
@@ -508,7 +501,7 @@ EncLayout enc_layout(const smi_enc_cfg* c) {
 
 int conv_out_len(int n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
 
-// every working buffer of an encode of up to max_samples / max_ref_samples (floats): the handle's own set and a slab of the rows workspace
+// every working buffer of an encode of up to max_samples / max_ref_samples (floats): one row's slab of a workspace
 std::map<std::string, size_t> enc_buffers(const smi_enc_cfg& c, int max_samples, int max_ref_samples) {
   std::map<std::string, size_t> out;
   // frame counts at the longest input
@@ -565,30 +558,46 @@ std::map<std::string, size_t> enc_buffers(const smi_enc_cfg& c, int max_samples,
   return out;
 }
 
+// Every length a launch reads, by kind: the feature encoder's layer outputs (the last is T, the frame count), the two inputs,
+// mel frames Tm, perceiver keys Tk = Nt + Tm, and the two constants the vector projections and the latent-side layers use.
+enum { LK_T0 = 0 /* .. LK_T0 + 7 */, LK_NS = 8, LK_NREF = 9, LK_TM = 10, LK_TK = 11, LK_ONE = 12, LK_NT = 13, LK_COUNT = 14 };
+struct RowLens { int v[LK_COUNT]; };
+
 }  // namespace
 
 struct smi_enc {
   smi_enc_cfg cfg;
   EncLayout lay;
   const unsigned char* arena;
-  std::map<std::string, float*> buf;        // named device buffers
-  std::map<std::string, size_t> buf_floats;
   float *cbn, *c2;                          // normalised codebook, |c|^2
-  int* lens_dev;                            // length slots
-  std::vector<int32_t> host_lens;
-  std::vector<Launch> prog;
   struct Stage { const float* ptr; int rows, cols, stride; };
-  std::map<std::string, Stage> stages;      // debug views of the last forward
+  // A workspace: max_rows slabs, a slab holding every working buffer of one row (enc_buffers) at `off`, the rows' lengths by
+  // kind, and the launch list last built on it with its debug views.  The handle has two: `solo` (one row of the config's own
+  // limits, allocated at create; smi_enc_forward and its graphs) and `rows` (smi_enc_rows_reserve; smi_enc_forward_rows).
+  struct Ws {
+    int max_rows = 0, max_samples = 0, max_ref = 0;
+    float* ws = nullptr;
+    long long slab = 0;                     // floats per row: the one batch stride of every buffer
+    std::map<std::string, size_t> off, floats;
+    int* lens_dev = nullptr;                // [length kind][max_rows]
+    std::vector<int32_t> host_lens;
+    std::vector<Launch> prog;
+    std::vector<int> run_start;             // first row of every run of the last list
+    std::vector<std::map<std::string, Stage>> stages;   // per row: debug views of the last list
+    int lastB = 0;
+    float* at(int row, const char* name) const { return ws + row * slab + off.at(name); }
+  } solo, rows;
+  std::map<std::pair<int, int>, std::vector<long long>> sigs;   // (n_samples, n_ref) -> the plan signature of that row's one-row list
   int last_frames;
   hipEvent_t ev0, ev1;
   // One hipGraph per (n_samples, n_ref): the ~260 launches of an encode replayed as one graph launch.  The graph reads the
-  // prompt from / leaves the ids in handle-owned buffers (in_wav, in_ref, out_sem, out_glob), so it does not depend on the
-  // caller's pointers; the length slots are uploaded before every launch (they differ from key to key).
+  // prompt from / leaves the ids in handle-owned buffers (in_wav, in_ref, out_sem, out_glob of the solo workspace), so it does
+  // not depend on the caller's pointers; the row's lengths are uploaded before every launch (they differ from key to key).
   struct Graph {
     hipGraphExec_t exec = nullptr;
     std::vector<int32_t> lens;
     std::vector<Launch> prog;
-    std::map<std::string, Stage> stages;
+    std::vector<std::map<std::string, Stage>> stages;
     int frames = 0;
     unsigned long long used = 0;
     hipStream_t last = nullptr; bool launched = false;   // the stream of its last launch: synchronised before the exec is destroyed
@@ -600,21 +609,6 @@ struct smi_enc {
   bool use_graph = true;
   hipStream_t gstream = nullptr;            // graph launches of callers on the null stream (which cannot be captured) run here
   hipEvent_t gev0 = nullptr, gev1 = nullptr;
-  // smi_enc_forward_rows: its own workspace, length arrays, launch list and debug views -- nothing above is read or written by it.
-  // The workspace is max_rows slabs; a slab holds every working buffer of the solo path, sized for the reserved row, at `off`.
-  struct Rows {
-    int max_rows = 0, max_samples = 0, max_ref = 0;
-    float* ws = nullptr;
-    long long slab = 0;                     // floats per row: the one batch stride of every buffer
-    std::map<std::string, size_t> off, floats;
-    int* lens_dev = nullptr;                // [length kind][max_rows]
-    std::vector<int32_t> host_lens;
-    std::vector<Launch> prog;
-    std::vector<int> run_start;             // first row of every run of the last list
-    std::vector<std::map<std::string, Stage>> stages;   // per row
-    std::map<std::pair<int, int>, std::vector<long long>> sigs;   // (n_samples, n_ref) -> the plan signature of that row's solo list
-    int lastB = 0;
-  } rows;
 };
 
 namespace {
@@ -628,6 +622,29 @@ bool ent_is_bf(const smi_enc* h, const std::string& name) {
   for (const Entry& e : h->lay.e)
     if (e.name == name) return e.kind == PACK_CONV_B || e.kind == PACK_CONVT_B;
   return false;
+}
+
+void ws_free(smi_enc::Ws& W) {
+  if (W.ws) (void)hipFree(W.ws);
+  if (W.lens_dev) (void)hipFree(W.lens_dev);
+  W = smi_enc::Ws();
+}
+
+// W becomes a workspace of max_rows rows of up to max_samples / max_ref; what it held is freed first.  On failure W is empty.
+int ws_alloc(const smi_enc_cfg& c, smi_enc::Ws& W, const char* who, int max_rows, int max_samples, int max_ref) {
+  ws_free(W);
+  W.floats = enc_buffers(c, max_samples, max_ref);
+  size_t o = 0;
+  for (const auto& kv : W.floats) { W.off[kv.first] = o; o += smi_align_up(kv.second, 64); }
+  W.slab = (long long)o;
+  if (hipMalloc((void**)&W.ws, (size_t)max_rows * o * 4) != hipSuccess ||
+      hipMalloc((void**)&W.lens_dev, (size_t)LK_COUNT * max_rows * 4) != hipSuccess) {
+    ws_free(W);
+    smi_set_error("%s: device allocation of %d rows x %zu bytes failed", who, max_rows, o * 4);
+    return SMI_EHIP;
+  }
+  W.max_rows = max_rows; W.max_samples = max_samples; W.max_ref = max_ref;
+  return SMI_OK;
 }
 
 }  // namespace
@@ -671,7 +688,7 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
   h->cfg = *cfg;
   h->lay = enc_layout(cfg);
   h->arena = (const unsigned char*)arena_dev;
-  h->cbn = h->c2 = nullptr; h->lens_dev = nullptr; h->ev0 = h->ev1 = nullptr; h->last_frames = 0;
+  h->cbn = h->c2 = nullptr; h->ev0 = h->ev1 = nullptr; h->last_frames = 0;
   if (arena_bytes < h->lay.total) {
     smi_set_error("smi_enc_create: arena is %zu bytes, layout needs %zu", arena_bytes, h->lay.total);
     delete h;
@@ -685,7 +702,6 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
     delete h;
     return SMI_EINVAL;
   }
-  h->buf_floats = enc_buffers(c, c.max_samples, c.max_ref_samples);
   {
     const char* e = smi_env("SPARKMI_ENC_GRAPH");
     h->use_graph = !(e && e[0] == '0');
@@ -701,15 +717,9 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
       return SMI_EHIP;
     }
   }
-  bool ok = true;
-  for (auto& kv : h->buf_floats) {
-    float* p = nullptr;
-    if (hipMalloc((void**)&p, kv.second * 4) != hipSuccess) { ok = false; break; }
-    h->buf[kv.first] = p;
-  }
-  ok = ok && hipMalloc((void**)&h->cbn, (size_t)c.codebook_size * c.codebook_dim * 4) == hipSuccess &&
+  const bool ok = ws_alloc(c, h->solo, "smi_enc_create", 1, c.max_samples, c.max_ref_samples) == SMI_OK &&
+       hipMalloc((void**)&h->cbn, (size_t)c.codebook_size * c.codebook_dim * 4) == hipSuccess &&
        hipMalloc((void**)&h->c2, (size_t)c.codebook_size * 4) == hipSuccess &&
-       hipMalloc((void**)&h->lens_dev, 64 * 4) == hipSuccess &&
        hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess &&
        hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking) == hipSuccess &&
        hipEventCreateWithFlags(&h->gev0, hipEventDisableTiming) == hipSuccess &&
@@ -732,12 +742,10 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
 
 int smi_enc_destroy(smi_enc* h) {
   if (!h) return SMI_OK;
-  for (auto& kv : h->buf) if (kv.second) (void)hipFree(kv.second);
   if (h->cbn) (void)hipFree(h->cbn);
   if (h->c2) (void)hipFree(h->c2);
-  if (h->lens_dev) (void)hipFree(h->lens_dev);
-  if (h->rows.ws) (void)hipFree(h->rows.ws);
-  if (h->rows.lens_dev) (void)hipFree(h->rows.lens_dev);
+  ws_free(h->solo);
+  ws_free(h->rows);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   for (auto& kv : h->graphs)
@@ -756,11 +764,6 @@ int smi_enc_destroy(smi_enc* h) {
 
 namespace {
 
-// Every length a launch reads, by kind: the feature encoder's layer outputs (the last is T, the frame count), the two inputs,
-// mel frames Tm, perceiver keys Tk = Nt + Tm, and the two constants the vector projections and the latent-side layers use.
-enum { LK_T0 = 0 /* .. LK_T0 + 7 */, LK_NS = 8, LK_NREF = 9, LK_TM = 10, LK_TK = 11, LK_ONE = 12, LK_NT = 13, LK_COUNT = 14 };
-struct RowLens { int v[LK_COUNT]; };
-
 RowLens row_lens(const smi_enc_cfg& c, int n_samples, int n_ref) {
   RowLens r;
   memset(&r, 0, sizeof(r));
@@ -772,12 +775,12 @@ RowLens row_lens(const smi_enc_cfg& c, int n_samples, int n_ref) {
   return r;
 }
 
-// What one launch sequence covers.  Solo (smi_enc_forward): one row, extent = plan = the row's own lengths, the handle's buffers,
-// lengths in de-duplicated slots.  Rows (smi_enc_forward_rows): rows r0 .. r0 + B of a call whose launch plans agree; `ext` (the
-// longest row, kind by kind) sizes grids, row strides and dynamic LDS, `plan` (the first row's own lengths) picks every conv
-// launch's tiling and kernel form (PlanShape), and each row's lengths are read from rows.lens_dev[kind][r0 + b].
+// What one launch sequence covers: rows r0 .. r0 + B of workspace W, whose launch plans agree.  `ext` (the longest row, kind by
+// kind) sizes grids, row strides and dynamic LDS, `plan` (the first row's own lengths) picks every conv launch's tiling and
+// kernel form (PlanShape), and each row's lengths are read from W.lens_dev[kind][r0 + b].  smi_enc_forward's list is the span of
+// one row on the solo workspace: ext = plan = the row's own lengths.
 struct EncSpan {
-  bool rows;
+  const smi_enc::Ws* W;
   int r0, B;
   RowLens ext, plan;
   const RowLens* own;      // [B] each row's lengths (debug views)
@@ -787,25 +790,18 @@ struct EncSpan {
   int32_t* glob; long long glob_bs;
 };
 
-// The launch sequence of one span (P), the solo path's length slots (hl) and the debug views of its rows (stages[0 .. B), or
-// null); nothing runs here and nothing of the handle changes.
-int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::vector<int32_t>& hl, std::map<std::string, smi_enc::Stage>* stages) {
+// The launch sequence of one span (P) and the debug views of its rows (stages[0 .. B), or null); nothing runs here and nothing
+// of the handle changes.
+int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::map<std::string, smi_enc::Stage>* stages) {
   const smi_enc_cfg& c = h->cfg;
+  const smi_enc::Ws& W = *sp.W;
   const RowLens& E = sp.ext;
   const int kT = LK_T0 + c.w2v_nconv - 1;
   const int T = E.v[kT], Tm = E.v[LK_TM], n_samples = E.v[LK_NS];
-  // ---- lengths on the device: solo, a slot per distinct value; rows, the span's part of the array of that kind
-  auto slot = [&](int v) -> const int* {
-    for (size_t i = 0; i < hl.size(); ++i) if (hl[i] == v) return h->lens_dev + i;
-    hl.push_back(v);
-    return h->lens_dev + (hl.size() - 1);
-  };
-  auto len = [&](int kind) -> const int* {
-    return sp.rows ? h->rows.lens_dev + (size_t)kind * h->rows.max_rows + sp.r0 : slot(E.v[kind]);
-  };
-  const long long bs = sp.rows ? h->rows.slab : 0;      // one batch stride for every working buffer
+  auto len = [&](int kind) -> const int* { return W.lens_dev + (size_t)kind * W.max_rows + sp.r0; };
+  const long long bs = W.slab;      // one batch stride for every working buffer
   const unsigned nB = (unsigned)sp.B;
-  auto B = [&](const char* n) -> float* { return sp.rows ? h->rows.ws + sp.r0 * bs + h->rows.off.at(n) : h->buf.at(n); };
+  auto B = [&](const char* n) -> float* { return W.at(sp.r0, n); };
   // a small kernel: the launch runs with the grid / block / dynamic LDS recorded here (what smi_enc_debug_launch reports)
   using Geo = std::function<void(hipStream_t, dim3, dim3, size_t)>;
   auto closure = [&](const std::string& name, double flops, dim3 grid, int blk, size_t lds, Geo fn) {
@@ -833,10 +829,9 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::vect
   auto conv = [&](const std::string& name, const std::string& wname, const std::string& bname, int Cout, int Cin, int K, int dil, int pad,
                   const float* X, int xstride, float* Y, const float* R, int ystride, int kin, int kout, int act, int istr) -> Launch& {
     const PlanShape ps{0, 0, sp.plan.v[kout]};
-    const bool same = sp.rows ? kin == kout : E.v[kin] == E.v[kout];
     P.push_back(make_conv_w(name, ent(h, wname), bname.empty() ? nullptr : ent(h, bname), Cout, Cin, K, dil, 1, pad, X, xstride, bs, Y,
-                            nullptr, nullptr, R, ystride, bs, len(kin), sp.B, E.v[kout], act, istr, same ? nullptr : len(kout),
-                            ent_is_bf(h, wname), sp.rows ? &ps : nullptr));
+                            nullptr, nullptr, R, ystride, bs, len(kin), sp.B, E.v[kout], act, istr, kin == kout ? nullptr : len(kout),
+                            ent_is_bf(h, wname), &ps));
     return P.back();
   };
   // attention of every row over its own kq queries and kk keys; the score rows in LDS are sized by the span's longest row
@@ -907,22 +902,14 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::vect
     });
     stage("hs0", d0, Hd, kT, T);
   }
-  const long long nHT = (long long)Hd * T;
-  const bool rows = sp.rows;
   auto tap = [&](int idx) {
     // hidden_states[idx] is the residual stream before layer idx
     for (int k = 0; k < 3; ++k) {
       if (c.w2v_taps[k] != idx) continue;
       const int mode = k;
-      // rows: a row's [Hd][T] block has the span's stride, so the kernel indexes by (channel, frame); solo: one flat array
-      if (rows)
-        closure("w2v.tap" + std::to_string(idx), 1.0 * nHT, dim3((T + 255) / 256, Hd), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-          hipLaunchKernelGGL(k_tap_rows, g, b, l, s, hbuf, acc, feat, Tlen, T, bs, mode);
-        });
-      else
-        closure("w2v.tap" + std::to_string(idx), 1.0 * nHT, dim3((unsigned)((nHT + 255) / 256)), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
-          hipLaunchKernelGGL(k_tap, g, b, l, s, hbuf, acc, feat, nHT, mode);
-        });
+      closure("w2v.tap" + std::to_string(idx), 1.0 * Hd * T, dim3((T + 255) / 256, Hd), 256, 0, [=](hipStream_t s, dim3 g, dim3 b, size_t l) {
+        hipLaunchKernelGGL(k_tap, g, b, l, s, hbuf, acc, feat, Tlen, T, bs, mode);
+      });
     }
   };
   SMI_REQUIRE(c.w2v_taps[0] < c.w2v_taps[1] && c.w2v_taps[1] < c.w2v_taps[2], "smi_enc_forward: hidden-state taps must be increasing");
@@ -1040,12 +1027,10 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::vect
       const int* len1 = len(LK_ONE);
       const PlanShape ps1{0, 0, 1};
       P.push_back(make_conv_w(b + ".3.linear1", ent(h, b + ".3.linear1.weight"), ent(h, b + ".3.linear1.bias"), 128, C, 1, 1, 1, 0, mean, 1,
-                              sp.rows ? bs : C, s1, nullptr, nullptr, nullptr, 1, sp.rows ? bs : 128, len1, sp.B, 1, ACT_RELU, 1, nullptr, false,
-                              sp.rows ? &ps1 : nullptr));
+                              bs, s1, nullptr, nullptr, nullptr, 1, bs, len1, sp.B, 1, ACT_RELU, 1, nullptr, false, &ps1));
       P.back().gemv = true; P.back().grid = dim3(4, nB);
       P.push_back(make_conv_w(b + ".3.linear2", ent(h, b + ".3.linear2.weight"), ent(h, b + ".3.linear2.bias"), C, 128, 1, 1, 1, 0, s1, 1,
-                              sp.rows ? bs : 128, s2, nullptr, nullptr, nullptr, 1, sp.rows ? bs : C, len1, sp.B, 1, ACT_SIGMOID, 1, nullptr, false,
-                              sp.rows ? &ps1 : nullptr));
+                              bs, s2, nullptr, nullptr, nullptr, 1, bs, len1, sp.B, 1, ACT_SIGMOID, 1, nullptr, false, &ps1));
       P.back().gemv = true; P.back().grid = dim3((C + 31) / 32, nB);
       float* outl = ecat + (size_t)(li - 2) * C * Tm;
       const float* xi = xin;
@@ -1100,7 +1085,6 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::vect
     stage("fsq_bounded", B("fsqb"), Nt, -c.fsq_dims, c.fsq_dims);
   }
 
-  SMI_REQUIRE(hl.size() <= 64, "smi_enc_forward: too many distinct lengths");
   for (const Launch& L : P) {
     if (L.kind == 0) {
       SMI_REQUIRE(L.cp.W, "smi_enc_forward: arena entry for %s not found", L.name.c_str());
@@ -1125,27 +1109,97 @@ int enc_check_row(const smi_enc_cfg& c, const char* who, int n_samples, int n_re
   return SMI_OK;
 }
 
-// The launch sequence of one solo encode (h->prog), its length slots (h->host_lens) and debug views (h->stages); nothing runs here.
-int enc_build(smi_enc* h, const float* wav_dev, int n_samples, const float* ref_dev, int n_ref, int64_t* sem_dev, int32_t* glob_dev,
-              int* n_frames) {
-  const smi_enc_cfg& c = h->cfg;
-  h->prog.clear();
-  h->stages.clear();
-  h->host_lens.clear();
-  int rc = enc_check_row(c, "smi_enc_forward", n_samples, n_ref, c.max_samples, c.max_ref_samples);
-  if (rc) return rc;
-  const RowLens own = row_lens(c, n_samples, n_ref);
-  const EncSpan sp{false, 0, 1, own, own, &own, wav_dev, 0, ref_dev, 0, sem_dev, 0, glob_dev, 0};
-  if ((rc = enc_program(h, sp, h->prog, h->host_lens, &h->stages))) return rc;
-  *n_frames = own.v[LK_T0 + c.w2v_nconv - 1];
-  return SMI_OK;
-}
-
 int enc_run(const std::vector<Launch>& P, hipStream_t st) {
   for (const Launch& L : P) {
     int rc = run_launch(L, st);
     if (rc) return rc;
   }
+  return SMI_OK;
+}
+
+// The launch list of B rows on workspace W (W.prog, .run_start, .stages, .host_lens); nothing runs.  A row's plan is the
+// signature of its one-row list; consecutive rows with equal plans form a run: one launch sequence with the first row's plan and
+// the extent (rows of the run, its longest row of every length kind).  A call of one row is that one-row list itself.
+int enc_build(smi_enc* h, smi_enc::Ws& W, const char* who, const float* wav, long long wav_bs, const int32_t* ns, const float* ref,
+              long long ref_bs, const int32_t* nref, int B, int64_t* sem, long long sem_bs, int32_t* glob, long long glob_bs, int32_t* n_frames) {
+  const smi_enc_cfg& c = h->cfg;
+  W.prog.clear(); W.run_start.clear(); W.stages.clear(); W.lastB = 0;
+  SMI_REQUIRE(W.ws, "%s: no rows workspace (smi_enc_rows_reserve first)", who);
+  SMI_REQUIRE(B >= 1 && B <= W.max_rows, "%s: B=%d outside the reserved 1..%d rows", who, B, W.max_rows);
+  int rc;
+  for (int b = 0; b < B; ++b)
+    if ((rc = enc_check_row(c, who, ns[b], nref[b], W.max_samples, W.max_ref))) return rc;
+  const int kT = LK_T0 + c.w2v_nconv - 1;
+  std::vector<RowLens> own((size_t)B);
+  std::vector<const std::vector<long long>*> sig((size_t)B, nullptr);
+  if (h->sigs.size() > 1024) h->sigs.clear();   // (before the first lookup: the pointers below stay valid across insertions)
+  for (int b = 0; b < B; ++b) {
+    own[b] = row_lens(c, ns[b], nref[b]);
+    if (B == 1) break;                          // (nothing to group: the list below is the row's own plan)
+    const std::pair<int, int> key(ns[b], nref[b]);
+    auto it = h->sigs.find(key);
+    if (it == h->sigs.end()) {
+      // the choices of that row's one-row list (pointers do not enter a signature)
+      std::vector<Launch> one;
+      const EncSpan sp{&h->solo, 0, 1, own[b], own[b], &own[b], wav, 0, ref, 0, sem, 0, glob, 0};
+      if ((rc = enc_program(h, sp, one, nullptr))) return rc;
+      it = h->sigs.emplace(key, plan_signature(one)).first;
+    }
+    sig[b] = &it->second;
+  }
+  W.stages.resize((size_t)B);
+  W.host_lens.assign((size_t)LK_COUNT * W.max_rows, 0);
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < LK_COUNT; ++k) W.host_lens[(size_t)k * W.max_rows + b] = own[b].v[k];
+  const std::vector<int> runs = plan_runs(sig);
+  std::vector<Launch> G;
+  for (size_t i = 0; i + 1 < runs.size(); ++i) {
+    const int r0 = runs[i], r1 = runs[i + 1];
+    // (every length kind grows with its input, so the longest row of each kind is that of the longest wav / reference clip)
+    const EncSpan sp{&W, r0, r1 - r0, row_lens(c, *std::max_element(ns + r0, ns + r1), *std::max_element(nref + r0, nref + r1)), own[r0], &own[r0],
+                     wav + r0 * wav_bs, wav_bs, ref + r0 * ref_bs, ref_bs, sem + r0 * sem_bs, sem_bs, glob + r0 * glob_bs, glob_bs};
+    G.clear();
+    if ((rc = enc_program(h, sp, G, &W.stages[r0]))) { W.prog.clear(); return rc; }
+    if (sig[r0] && plan_signature(G) != *sig[r0]) {
+      W.prog.clear();
+      smi_set_error("%s: the launch list of rows %d..%d does not carry the plan of a row of %d samples / %d reference samples", who, r0, r1 - 1,
+                    ns[r0], nref[r0]);
+      return SMI_EINVAL;
+    }
+    W.run_start.push_back(r0);
+    W.prog.insert(W.prog.end(), G.begin(), G.end());
+  }
+  for (int b = 0; b < B; ++b) n_frames[b] = own[b].v[kT];
+  W.lastB = B;
+  return SMI_OK;
+}
+
+// smi_enc_forward's list: one row on the solo workspace
+int enc_build_solo(smi_enc* h, const char* who, const float* wav_dev, int n_samples, const float* ref_dev, int n_ref, int64_t* sem_dev,
+                   int32_t* glob_dev, int* n_frames) {
+  const int32_t ns = n_samples, nr = n_ref;
+  int32_t nf = 0;
+  const int rc = enc_build(h, h->solo, who, wav_dev, 0, &ns, ref_dev, 0, &nr, 1, sem_dev, 0, glob_dev, 0, &nf);
+  *n_frames = nf;
+  return rc;
+}
+
+int enc_upload_lens(const smi_enc::Ws& W, hipStream_t st) {
+  SMI_HIP(hipMemcpyAsync(W.lens_dev, W.host_lens.data(), W.host_lens.size() * 4, hipMemcpyHostToDevice, st));
+  return SMI_OK;
+}
+
+// one debug view of row `row` of the list last built on W, copied out densely
+int enc_stage(const smi_enc::Ws& W, const char* who, int row, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream) {
+  SMI_REQUIRE(name && out_dev && dims, "%s: null argument", who);
+  SMI_REQUIRE(row >= 0 && row < W.lastB && row < (int)W.stages.size(), "%s: row %d outside the last rows call (%d rows)", who, row, W.lastB);
+  auto it = W.stages[row].find(name);
+  SMI_REQUIRE(it != W.stages[row].end(), "%s: unknown stage '%s'", who, name);
+  const smi_enc::Stage& s = it->second;
+  SMI_REQUIRE((size_t)s.rows * s.cols <= max_floats, "%s: output buffer too small", who);
+  SMI_HIP(hipMemcpy2DAsync(out_dev, (size_t)s.cols * 4, s.ptr, (size_t)s.stride * 4, (size_t)s.cols * 4, s.rows, hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream));
+  dims[0] = s.rows; dims[1] = s.cols;
   return SMI_OK;
 }
 
@@ -1157,6 +1211,7 @@ int smi_enc_forward(smi_enc* h, const float* wav_dev, int n_samples, const float
                     int32_t* glob_dev, int* n_frames, void* stream) {
   SMI_REQUIRE(h && wav_dev && ref_dev && sem_dev && glob_dev && n_frames, "smi_enc_forward: null argument");
   const smi_enc_cfg& c = h->cfg;
+  smi_enc::Ws& S = h->solo;
   SMI_REQUIRE(n_samples >= 400 && n_samples <= c.max_samples, "smi_enc_forward: n_samples=%d outside 400..%d", n_samples, c.max_samples);
   SMI_REQUIRE(n_ref > c.n_fft / 2 && n_ref <= c.max_ref_samples, "smi_enc_forward: n_ref=%d outside %d..%d", n_ref, c.n_fft / 2 + 1,
               c.max_ref_samples);
@@ -1169,16 +1224,16 @@ int smi_enc_forward(smi_enc* h, const float* wav_dev, int n_samples, const float
     eager = h->seen[key]++ == 0;
   }
   if (eager) {
-    if ((rc = enc_build(h, wav_dev, n_samples, ref_dev, n_ref, sem_dev, glob_dev, n_frames))) return rc;
     h->prog_key = {-1, -1};
-    SMI_HIP(hipMemcpyAsync(h->lens_dev, h->host_lens.data(), h->host_lens.size() * 4, hipMemcpyHostToDevice, st));
-    if ((rc = enc_run(h->prog, st))) return rc;
+    if ((rc = enc_build_solo(h, "smi_enc_forward", wav_dev, n_samples, ref_dev, n_ref, sem_dev, glob_dev, n_frames))) return rc;
+    if ((rc = enc_upload_lens(S, st))) return rc;
+    if ((rc = enc_run(S.prog, st))) return rc;
     h->last_frames = *n_frames;
     return SMI_OK;
   }
-  float *in_wav = h->buf.at("in_wav"), *in_ref = h->buf.at("in_ref");
-  int64_t* out_sem = (int64_t*)h->buf.at("out_sem");
-  int32_t* out_glob = (int32_t*)h->buf.at("out_glob");
+  float *in_wav = S.at(0, "in_wav"), *in_ref = S.at(0, "in_ref");
+  int64_t* out_sem = (int64_t*)S.at(0, "out_sem");
+  int32_t* out_glob = (int32_t*)S.at(0, "out_glob");
   // the null stream cannot be captured: such callers' encodes run on the handle's own stream, fenced by events on both sides
   hipStream_t run = st ? st : h->gstream;
   if (!st) {
@@ -1198,10 +1253,10 @@ int smi_enc_forward(smi_enc* h, const float* wav_dev, int n_samples, const float
       h->graphs.erase(old);
     }
     int T = 0;
-    if ((rc = enc_build(h, in_wav, n_samples, in_ref, n_ref, out_sem, out_glob, &T))) return rc;
+    if ((rc = enc_build_solo(h, "smi_enc_forward", in_wav, n_samples, in_ref, n_ref, out_sem, out_glob, &T))) return rc;
     smi_enc::Graph g;
-    g.lens = h->host_lens; g.prog = h->prog; g.stages = h->stages; g.frames = T;
-    SMI_HIP(hipMemcpyAsync(h->lens_dev, g.lens.data(), g.lens.size() * 4, hipMemcpyHostToDevice, run));
+    g.lens = S.host_lens; g.prog = S.prog; g.stages = S.stages; g.frames = T;
+    SMI_HIP(hipMemcpyAsync(S.lens_dev, g.lens.data(), g.lens.size() * 4, hipMemcpyHostToDevice, run));
     SMI_HIP(hipStreamSynchronize(run));      // (the pageable source above must be read before g.lens moves into the map)
     SMI_HIP(hipStreamBeginCapture(run, hipStreamCaptureModeRelaxed));
     rc = enc_run(g.prog, run);
@@ -1218,9 +1273,9 @@ int smi_enc_forward(smi_enc* h, const float* wav_dev, int n_samples, const float
     h->prog_key = key;
     it = h->graphs.emplace(key, std::move(g)).first;
   } else {
-    if (h->prog_key != key) { h->prog = it->second.prog; h->prog_key = key; }
-    h->stages = it->second.stages;
-    SMI_HIP(hipMemcpyAsync(h->lens_dev, it->second.lens.data(), it->second.lens.size() * 4, hipMemcpyHostToDevice, run));
+    if (h->prog_key != key) { S.prog = it->second.prog; h->prog_key = key; }
+    S.stages = it->second.stages; S.lastB = 1;
+    SMI_HIP(hipMemcpyAsync(S.lens_dev, it->second.lens.data(), it->second.lens.size() * 4, hipMemcpyHostToDevice, run));
   }
   it->second.used = ++h->tick;
   SMI_HIP(hipGraphLaunch(it->second.exec, run));
@@ -1237,77 +1292,6 @@ int smi_enc_forward(smi_enc* h, const float* wav_dev, int n_samples, const float
   return SMI_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// The rows launch list (h->rows.prog, .run_start, .stages, .host_lens) of B rows; nothing runs and nothing of the solo path is
-// touched.  A row's plan is the signature of the list smi_enc_forward builds for it alone; consecutive rows with equal plans form
-// a run: one launch sequence with the first row's plan and the extent (rows of the run, its longest row of every length kind).
-int enc_rows_build(smi_enc* h, const char* who, const float* wav, long long wav_bs, const int32_t* ns, const float* ref, long long ref_bs,
-                   const int32_t* nref, int B, int64_t* sem, long long sem_bs, int32_t* glob, long long glob_bs, int32_t* n_frames) {
-  const smi_enc_cfg& c = h->cfg;
-  smi_enc::Rows& R = h->rows;
-  R.prog.clear(); R.run_start.clear(); R.stages.clear(); R.lastB = 0;
-  SMI_REQUIRE(R.ws, "%s: no rows workspace (smi_enc_rows_reserve first)", who);
-  SMI_REQUIRE(B >= 1 && B <= R.max_rows, "%s: B=%d outside the reserved 1..%d rows", who, B, R.max_rows);
-  int rc;
-  for (int b = 0; b < B; ++b)
-    if ((rc = enc_check_row(c, who, ns[b], nref[b], R.max_samples, R.max_ref))) return rc;
-  const int kT = LK_T0 + c.w2v_nconv - 1;
-  std::vector<RowLens> own((size_t)B);
-  std::vector<const std::vector<long long>*> sig((size_t)B);
-  if (R.sigs.size() > 1024) R.sigs.clear();   // (before the first lookup: the pointers below stay valid across insertions)
-  for (int b = 0; b < B; ++b) {
-    own[b] = row_lens(c, ns[b], nref[b]);
-    const std::pair<int, int> key(ns[b], nref[b]);
-    auto it = R.sigs.find(key);
-    if (it == R.sigs.end()) {
-      // the choices of that row's own smi_enc_forward (pointers do not enter a signature)
-      std::vector<Launch> solo;
-      std::vector<int32_t> hl;
-      const EncSpan sp{false, 0, 1, own[b], own[b], &own[b], wav, 0, ref, 0, sem, 0, glob, 0};
-      if ((rc = enc_program(h, sp, solo, hl, nullptr))) return rc;
-      it = R.sigs.emplace(key, plan_signature(solo)).first;
-    }
-    sig[b] = &it->second;
-  }
-  R.stages.resize((size_t)B);
-  R.host_lens.assign((size_t)LK_COUNT * R.max_rows, 0);
-  for (int b = 0; b < B; ++b)
-    for (int k = 0; k < LK_COUNT; ++k) R.host_lens[(size_t)k * R.max_rows + b] = own[b].v[k];
-  std::vector<Launch> G;
-  std::vector<int32_t> none;
-  for (int r0 = 0; r0 < B;) {
-    int r1 = r0 + 1, mns = ns[r0], mref = nref[r0];
-    for (; r1 < B && *sig[r1] == *sig[r0]; ++r1) {
-      mns = ns[r1] > mns ? ns[r1] : mns;
-      mref = nref[r1] > mref ? nref[r1] : mref;
-    }
-    // (every length kind grows with its input, so the longest row of each kind is that of the longest wav / reference clip)
-    const EncSpan sp{true, r0, r1 - r0, row_lens(c, mns, mref), own[r0], &own[r0], wav + r0 * wav_bs, wav_bs, ref + r0 * ref_bs, ref_bs,
-                     sem + r0 * sem_bs, sem_bs, glob + r0 * glob_bs, glob_bs};
-    G.clear();
-    if ((rc = enc_program(h, sp, G, none, &R.stages[r0]))) { R.prog.clear(); return rc; }
-    if (plan_signature(G) != *sig[r0]) {
-      R.prog.clear();
-      smi_set_error("%s: the launch list of rows %d..%d does not carry the plan of a row of %d samples / %d reference samples", who, r0, r1 - 1,
-                    ns[r0], nref[r0]);
-      return SMI_EINVAL;
-    }
-    R.run_start.push_back(r0);
-    R.prog.insert(R.prog.end(), G.begin(), G.end());
-    r0 = r1;
-  }
-  for (int b = 0; b < B; ++b) n_frames[b] = own[b].v[kT];
-  R.lastB = B;
-  return SMI_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int smi_enc_rows_reserve(smi_enc* h, int max_rows, int max_row_samples, int max_row_ref_samples) {
   SMI_REQUIRE(h, "smi_enc_rows_reserve: null handle");
   const smi_enc_cfg& c = h->cfg;
@@ -1316,27 +1300,10 @@ int smi_enc_rows_reserve(smi_enc* h, int max_rows, int max_row_samples, int max_
               max_row_samples, c.max_samples);
   SMI_REQUIRE(max_row_ref_samples > c.n_fft / 2 && max_row_ref_samples <= c.max_ref_samples,
               "smi_enc_rows_reserve: max_row_ref_samples=%d outside %d..%d", max_row_ref_samples, c.n_fft / 2 + 1, c.max_ref_samples);
-  smi_enc::Rows& R = h->rows;
+  smi_enc::Ws& R = h->rows;
   if (R.ws && R.max_rows == max_rows && R.max_samples == max_row_samples && R.max_ref == max_row_ref_samples) return SMI_OK;
   SMI_HIP(hipDeviceSynchronize());      // a rows call may still be reading the workspace that goes
-  if (R.ws) (void)hipFree(R.ws);
-  if (R.lens_dev) (void)hipFree(R.lens_dev);
-  R.ws = nullptr; R.lens_dev = nullptr; R.max_rows = 0;
-  R.prog.clear(); R.run_start.clear(); R.stages.clear(); R.lastB = 0;
-  R.floats = enc_buffers(c, max_row_samples, max_row_ref_samples);
-  R.off.clear();
-  size_t o = 0;
-  for (const auto& kv : R.floats) { R.off[kv.first] = o; o += smi_align_up(kv.second, 64); }
-  R.slab = (long long)o;
-  if (hipMalloc((void**)&R.ws, (size_t)max_rows * o * 4) != hipSuccess ||
-      hipMalloc((void**)&R.lens_dev, (size_t)LK_COUNT * max_rows * 4) != hipSuccess) {
-    if (R.ws) (void)hipFree(R.ws);
-    R.ws = nullptr; R.lens_dev = nullptr;
-    smi_set_error("smi_enc_rows_reserve: device allocation of %d rows x %zu bytes failed", max_rows, o * 4);
-    return SMI_EHIP;
-  }
-  R.max_rows = max_rows; R.max_samples = max_row_samples; R.max_ref = max_row_ref_samples;
-  return SMI_OK;
+  return ws_alloc(c, R, "smi_enc_rows_reserve", max_rows, max_row_samples, max_row_ref_samples);
 }
 
 int smi_enc_forward_rows(smi_enc* h, const float* wav_dev, long long wav_stride, const int32_t* n_samples_host, const float* ref_dev,
@@ -1345,56 +1312,56 @@ int smi_enc_forward_rows(smi_enc* h, const float* wav_dev, long long wav_stride,
   SMI_REQUIRE(h && wav_dev && n_samples_host && ref_dev && n_ref_host && sem_dev && glob_dev && n_frames_host,
               "smi_enc_forward_rows: null argument");
   hipStream_t st = (hipStream_t)stream;
-  int rc = enc_rows_build(h, "smi_enc_forward_rows", wav_dev, wav_stride, n_samples_host, ref_dev, ref_stride, n_ref_host, B, sem_dev, sem_stride,
-                          glob_dev, h->cfg.spk_tokens, n_frames_host);
+  int rc = enc_build(h, h->rows, "smi_enc_forward_rows", wav_dev, wav_stride, n_samples_host, ref_dev, ref_stride, n_ref_host, B, sem_dev, sem_stride,
+                     glob_dev, h->cfg.spk_tokens, n_frames_host);
   if (rc) return rc;
   for (int b = 0; b < B; ++b) {
     SMI_REQUIRE(wav_stride >= n_samples_host[b] && ref_stride >= n_ref_host[b] && sem_stride >= n_frames_host[b],
                 "smi_enc_forward_rows: row %d (%d samples, %d reference samples, %d frames) exceeds a row stride", b, n_samples_host[b],
                 n_ref_host[b], n_frames_host[b]);
   }
-  SMI_HIP(hipMemcpyAsync(h->rows.lens_dev, h->rows.host_lens.data(), h->rows.host_lens.size() * 4, hipMemcpyHostToDevice, st));
+  if ((rc = enc_upload_lens(h->rows, st))) return rc;
   return enc_run(h->rows.prog, st);
 }
 
 int smi_enc_debug_stage(smi_enc* h, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream) {
-  SMI_REQUIRE(h && name && out_dev && dims, "smi_enc_debug_stage: null argument");
+  SMI_REQUIRE(h, "smi_enc_debug_stage: null argument");
   SMI_REQUIRE(h->last_frames > 0, "smi_enc_debug_stage: no forward has run");
-  auto it = h->stages.find(name);
-  SMI_REQUIRE(it != h->stages.end(), "smi_enc_debug_stage: unknown stage '%s'", name);
-  const smi_enc::Stage& s = it->second;
-  SMI_REQUIRE((size_t)s.rows * s.cols <= max_floats, "smi_enc_debug_stage: output buffer too small");
-  SMI_HIP(hipMemcpy2DAsync(out_dev, (size_t)s.cols * 4, s.ptr, (size_t)s.stride * 4, (size_t)s.cols * 4, s.rows, hipMemcpyDeviceToDevice,
-                           (hipStream_t)stream));
-  dims[0] = s.rows; dims[1] = s.cols;
-  return SMI_OK;
+  return enc_stage(h->solo, "smi_enc_debug_stage", 0, name, out_dev, max_floats, dims, stream);
 }
 
-int smi_enc_num_launches(smi_enc* h) { return h ? (int)h->prog.size() : 0; }
+int smi_enc_num_launches(smi_enc* h) { return h ? (int)h->solo.prog.size() : 0; }
 
-#ifdef SMI_DIAG   // ---- include/sparkmi_debug.h: the encoder's launch list one launch at a time, exported by libsparkmi_diag.so only
+int smi_enc_time_launch(smi_enc* h, int index, int iters, float* ms_avg, double* flops, char* name, int name_cap, void* stream) {
+  SMI_REQUIRE(h && ms_avg && iters > 0, "smi_enc_time_launch: bad argument");
+  SMI_REQUIRE(index >= 0 && index < (int)h->solo.prog.size(), "smi_enc_time_launch: index %d out of range", index);
+  return time_launch(h->solo.prog[index], h->ev0, h->ev1, iters, ms_avg, flops, name, name_cap, (hipStream_t)stream);
+}
 
-int smi_enc_debug_build(smi_enc* h, int n_samples, int n_ref, int* n_frames, int* n_launches, void* stream) {
-  SMI_REQUIRE(h && n_frames && n_launches, "smi_enc_debug_build: null argument");
-  const smi_enc_cfg& c = h->cfg;
-  SMI_REQUIRE(n_samples >= 400 && n_samples <= c.max_samples, "smi_enc_debug_build: n_samples=%d outside 400..%d", n_samples, c.max_samples);
-  SMI_REQUIRE(n_ref > c.n_fft / 2 && n_ref <= c.max_ref_samples, "smi_enc_debug_build: n_ref=%d outside %d..%d", n_ref, c.n_fft / 2 + 1,
-              c.max_ref_samples);
-  hipStream_t st = (hipStream_t)stream;
-  h->prog_key = {-1, -1};
-  int rc = enc_build(h, h->buf.at("in_wav"), n_samples, h->buf.at("in_ref"), n_ref, (int64_t*)h->buf.at("out_sem"), (int32_t*)h->buf.at("out_glob"),
-                     n_frames);
-  if (rc) { h->prog.clear(); return rc; }
-  SMI_HIP(hipMemcpyAsync(h->lens_dev, h->host_lens.data(), h->host_lens.size() * 4, hipMemcpyHostToDevice, st));
+}  // extern "C"
+
+#ifdef SMI_DIAG   // ---- include/sparkmi_debug.h: the encoder's launch lists one launch at a time, exported by libsparkmi_diag.so only
+
+namespace {
+
+// Each entry below exists for the solo list (smi_enc_debug_*: the solo workspace, row 0) and for the rows list
+// (smi_enc_rows_debug_*: the rows workspace); `who` is the calling entry's name.
+int dbg_build(smi_enc* h, smi_enc::Ws& W, const char* who, const int32_t* ns, const int32_t* nref, int B, int32_t* n_frames, int* n_launches,
+              hipStream_t st) {
+  SMI_REQUIRE(W.ws, "%s: no rows workspace (smi_enc_rows_reserve first)", who);
+  int rc = enc_build(h, W, who, W.at(0, "in_wav"), W.slab, ns, W.at(0, "in_ref"), W.slab, nref, B, (int64_t*)W.at(0, "out_sem"), W.slab / 2,
+                     (int32_t*)W.at(0, "out_glob"), W.slab, n_frames);
+  if (rc) return rc;
+  if ((rc = enc_upload_lens(W, st))) return rc;
   SMI_HIP(hipStreamSynchronize(st));
-  *n_launches = (int)h->prog.size();
+  *n_launches = (int)W.prog.size();
   return SMI_OK;
 }
 
-int smi_enc_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* info) {
-  SMI_REQUIRE(h && info, "smi_enc_debug_launch: null argument");
-  SMI_REQUIRE(index >= 0 && index < (int)h->prog.size(), "smi_enc_debug_launch: index %d out of range", index);
-  const Launch& L = h->prog[index];
+int dbg_launch(const smi_enc::Ws& W, const char* who, int index, char* name, int cap, int32_t* info) {
+  SMI_REQUIRE(info, "%s: null argument", who);
+  SMI_REQUIRE(index >= 0 && index < (int)W.prog.size(), "%s: index %d out of range", who, index);
+  const Launch& L = W.prog[index];
   if (name && cap > 0) { strncpy(name, L.name.c_str(), (size_t)cap - 1); name[cap - 1] = 0; }
   info[0] = L.kind; info[1] = (int32_t)L.grid.x; info[2] = (int32_t)L.grid.y; info[3] = (int32_t)L.grid.z;
   info[4] = L.kind == 0 ? 64 * L.nwv : L.blk;
@@ -1404,48 +1371,68 @@ int smi_enc_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* in
   return SMI_OK;
 }
 
-int smi_enc_debug_io(smi_enc* h, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats) {
-  SMI_REQUIRE(h && buffer_name && host_ptr, "smi_enc_debug_io: null argument");
-  auto it = h->buf.find(buffer_name);
-  SMI_REQUIRE(it != h->buf.end(), "smi_enc_debug_io: unknown buffer '%s'", buffer_name);
-  const size_t have = h->buf_floats.at(buffer_name);
-  SMI_REQUIRE(offset_floats <= have && floats <= have - offset_floats, "smi_enc_debug_io: %zu floats at %zu outside '%s' (%zu floats)", floats,
+int dbg_io(const smi_enc::Ws& W, const char* who, int row, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats) {
+  SMI_REQUIRE(buffer_name && host_ptr, "%s: null argument", who);
+  SMI_REQUIRE(W.ws, "%s: no rows workspace (smi_enc_rows_reserve first)", who);
+  SMI_REQUIRE(row >= 0 && row < W.max_rows, "%s: row %d outside the reserved 0..%d", who, row, W.max_rows - 1);
+  auto it = W.floats.find(buffer_name);
+  SMI_REQUIRE(it != W.floats.end(), "%s: unknown buffer '%s'", who, buffer_name);
+  const size_t have = it->second;
+  SMI_REQUIRE(offset_floats <= have && floats <= have - offset_floats, "%s: %zu floats at %zu outside '%s' (%zu floats a row)", who, floats,
               offset_floats, buffer_name, have);
+  float* p = W.at(row, buffer_name) + offset_floats;
   SMI_HIP(hipDeviceSynchronize());
-  if (write) SMI_HIP(hipMemcpy(it->second + offset_floats, host_ptr, floats * 4, hipMemcpyHostToDevice));
-  else SMI_HIP(hipMemcpy(host_ptr, it->second + offset_floats, floats * 4, hipMemcpyDeviceToHost));
+  if (write) SMI_HIP(hipMemcpy(p, host_ptr, floats * 4, hipMemcpyHostToDevice));
+  else SMI_HIP(hipMemcpy(host_ptr, p, floats * 4, hipMemcpyDeviceToHost));
   return SMI_OK;
 }
 
-int smi_enc_debug_run(smi_enc* h, int first, int last, void* stream) {
-  SMI_REQUIRE(h, "smi_enc_debug_run: null handle");
-  SMI_REQUIRE(first >= 0 && first <= last && last < (int)h->prog.size(), "smi_enc_debug_run: launches %d..%d outside 0..%d", first, last,
-              (int)h->prog.size() - 1);
-  hipStream_t st = (hipStream_t)stream;
+int dbg_run(const smi_enc::Ws& W, const char* who, int first, int last, hipStream_t st) {
+  SMI_REQUIRE(first >= 0 && first <= last && last < (int)W.prog.size(), "%s: launches %d..%d outside 0..%d", who, first, last,
+              (int)W.prog.size() - 1);
   for (int i = first; i <= last; ++i) {
-    const int rc = run_launch(h->prog[i], st);
+    const int rc = run_launch(W.prog[i], st);
     if (rc) return rc;
   }
   SMI_HIP(hipStreamSynchronize(st));
   return SMI_OK;
 }
 
-// ---- the rows list (smi_enc_forward_rows) the same way
+}  // namespace
+
+extern "C" {
+
+int smi_enc_debug_build(smi_enc* h, int n_samples, int n_ref, int* n_frames, int* n_launches, void* stream) {
+  SMI_REQUIRE(h && n_frames && n_launches, "smi_enc_debug_build: null argument");
+  h->prog_key = {-1, -1};
+  const int32_t ns = n_samples, nr = n_ref;
+  int32_t nf = 0;
+  const int rc = dbg_build(h, h->solo, "smi_enc_debug_build", &ns, &nr, 1, &nf, n_launches, (hipStream_t)stream);
+  *n_frames = nf;
+  return rc;
+}
+
+int smi_enc_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* info) {
+  SMI_REQUIRE(h, "smi_enc_debug_launch: null argument");
+  return dbg_launch(h->solo, "smi_enc_debug_launch", index, name, cap, info);
+}
+
+int smi_enc_debug_io(smi_enc* h, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats) {
+  SMI_REQUIRE(h, "smi_enc_debug_io: null argument");
+  return dbg_io(h->solo, "smi_enc_debug_io", 0, buffer_name, write, host_ptr, offset_floats, floats);
+}
+
+int smi_enc_debug_run(smi_enc* h, int first, int last, void* stream) {
+  SMI_REQUIRE(h, "smi_enc_debug_run: null handle");
+  return dbg_run(h->solo, "smi_enc_debug_run", first, last, (hipStream_t)stream);
+}
+
 int smi_enc_rows_debug_build(smi_enc* h, const int32_t* n_samples, const int32_t* n_ref, int B, int32_t* n_frames, int* n_launches,
                              int32_t* run_start, int run_cap, int* n_runs, void* stream) {
   SMI_REQUIRE(h && n_samples && n_ref && n_frames && n_launches && n_runs, "smi_enc_rows_debug_build: null argument");
-  smi_enc::Rows& R = h->rows;
-  SMI_REQUIRE(R.ws, "smi_enc_rows_debug_build: no rows workspace (smi_enc_rows_reserve first)");
-  hipStream_t st = (hipStream_t)stream;
-  int rc = enc_rows_build(h, "smi_enc_rows_debug_build", R.ws + R.off.at("in_wav"), R.slab, n_samples, R.ws + R.off.at("in_ref"), R.slab, n_ref, B,
-                          (int64_t*)(R.ws + R.off.at("out_sem")), R.slab / 2, (int32_t*)(R.ws + R.off.at("out_glob")), R.slab, n_frames);
+  const int rc = dbg_build(h, h->rows, "smi_enc_rows_debug_build", n_samples, n_ref, B, n_frames, n_launches, (hipStream_t)stream);
   if (rc) return rc;
-  SMI_HIP(hipMemcpyAsync(R.lens_dev, R.host_lens.data(), R.host_lens.size() * 4, hipMemcpyHostToDevice, st));
-  SMI_HIP(hipStreamSynchronize(st));
-  *n_launches = (int)R.prog.size();
-  *n_runs = (int)R.run_start.size();
-  for (int i = 0; run_start && i < run_cap && i < (int)R.run_start.size(); ++i) run_start[i] = R.run_start[i];
-  return SMI_OK;
+  return smi_enc_rows_debug_runs(h, run_start, run_cap, n_runs, n_launches);
 }
 
 int smi_enc_rows_debug_runs(smi_enc* h, int32_t* run_start, int run_cap, int* n_runs, int* n_launches) {
@@ -1457,82 +1444,25 @@ int smi_enc_rows_debug_runs(smi_enc* h, int32_t* run_start, int run_cap, int* n_
 }
 
 int smi_enc_rows_debug_launch(smi_enc* h, int index, char* name, int cap, int32_t* info) {
-  SMI_REQUIRE(h && info, "smi_enc_rows_debug_launch: null argument");
-  SMI_REQUIRE(index >= 0 && index < (int)h->rows.prog.size(), "smi_enc_rows_debug_launch: index %d out of range", index);
-  const Launch& L = h->rows.prog[index];
-  if (name && cap > 0) { strncpy(name, L.name.c_str(), (size_t)cap - 1); name[cap - 1] = 0; }
-  info[0] = L.kind; info[1] = (int32_t)L.grid.x; info[2] = (int32_t)L.grid.y; info[3] = (int32_t)L.grid.z;
-  info[4] = L.kind == 0 ? 64 * L.nwv : L.blk;
-  info[5] = (int32_t)L.lds;
-  info[6] = L.kind == 1 ? dwln_form(L.cpt) : 0;
-  info[7] = 0;
-  return SMI_OK;
+  SMI_REQUIRE(h, "smi_enc_rows_debug_launch: null argument");
+  return dbg_launch(h->rows, "smi_enc_rows_debug_launch", index, name, cap, info);
 }
 
 int smi_enc_rows_debug_io(smi_enc* h, int row, const char* buffer_name, int write, void* host_ptr, size_t offset_floats, size_t floats) {
-  SMI_REQUIRE(h && buffer_name && host_ptr, "smi_enc_rows_debug_io: null argument");
-  smi_enc::Rows& R = h->rows;
-  SMI_REQUIRE(R.ws, "smi_enc_rows_debug_io: no rows workspace (smi_enc_rows_reserve first)");
-  SMI_REQUIRE(row >= 0 && row < R.max_rows, "smi_enc_rows_debug_io: row %d outside the reserved 0..%d", row, R.max_rows - 1);
-  auto it = R.floats.find(buffer_name);
-  SMI_REQUIRE(it != R.floats.end(), "smi_enc_rows_debug_io: unknown buffer '%s'", buffer_name);
-  const size_t have = it->second;
-  SMI_REQUIRE(offset_floats <= have && floats <= have - offset_floats, "smi_enc_rows_debug_io: %zu floats at %zu outside '%s' (%zu floats a row)",
-              floats, offset_floats, buffer_name, have);
-  float* p = R.ws + (long long)row * R.slab + R.off.at(buffer_name) + offset_floats;
-  SMI_HIP(hipDeviceSynchronize());
-  if (write) SMI_HIP(hipMemcpy(p, host_ptr, floats * 4, hipMemcpyHostToDevice));
-  else SMI_HIP(hipMemcpy(host_ptr, p, floats * 4, hipMemcpyDeviceToHost));
-  return SMI_OK;
+  SMI_REQUIRE(h, "smi_enc_rows_debug_io: null argument");
+  return dbg_io(h->rows, "smi_enc_rows_debug_io", row, buffer_name, write, host_ptr, offset_floats, floats);
 }
 
 int smi_enc_rows_debug_run(smi_enc* h, int first, int last, void* stream) {
   SMI_REQUIRE(h, "smi_enc_rows_debug_run: null handle");
-  SMI_REQUIRE(first >= 0 && first <= last && last < (int)h->rows.prog.size(), "smi_enc_rows_debug_run: launches %d..%d outside 0..%d", first, last,
-              (int)h->rows.prog.size() - 1);
-  hipStream_t st = (hipStream_t)stream;
-  for (int i = first; i <= last; ++i) {
-    const int rc = run_launch(h->rows.prog[i], st);
-    if (rc) return rc;
-  }
-  SMI_HIP(hipStreamSynchronize(st));
-  return SMI_OK;
+  return dbg_run(h->rows, "smi_enc_rows_debug_run", first, last, (hipStream_t)stream);
 }
 
 int smi_enc_rows_debug_stage(smi_enc* h, int row, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream) {
-  SMI_REQUIRE(h && name && out_dev && dims, "smi_enc_rows_debug_stage: null argument");
-  SMI_REQUIRE(row >= 0 && row < h->rows.lastB && row < (int)h->rows.stages.size(), "smi_enc_rows_debug_stage: row %d outside the last rows call (%d rows)",
-              row, h->rows.lastB);
-  auto it = h->rows.stages[row].find(name);
-  SMI_REQUIRE(it != h->rows.stages[row].end(), "smi_enc_rows_debug_stage: unknown stage '%s'", name);
-  const smi_enc::Stage& s = it->second;
-  SMI_REQUIRE((size_t)s.rows * s.cols <= max_floats, "smi_enc_rows_debug_stage: output buffer too small");
-  SMI_HIP(hipMemcpy2DAsync(out_dev, (size_t)s.cols * 4, s.ptr, (size_t)s.stride * 4, (size_t)s.cols * 4, s.rows, hipMemcpyDeviceToDevice,
-                           (hipStream_t)stream));
-  dims[0] = s.rows; dims[1] = s.cols;
-  return SMI_OK;
-}
-
-#endif   // SMI_DIAG
-
-int smi_enc_time_launch(smi_enc* h, int index, int iters, float* ms_avg, double* flops, char* name, int name_cap, void* stream) {
-  SMI_REQUIRE(h && ms_avg && iters > 0, "smi_enc_time_launch: bad argument");
-  SMI_REQUIRE(index >= 0 && index < (int)h->prog.size(), "smi_enc_time_launch: index %d out of range", index);
-  hipStream_t st = (hipStream_t)stream;
-  const Launch& L = h->prog[index];
-  int rc = run_launch(L, st);
-  if (rc) return rc;
-  SMI_HIP(hipEventRecord(h->ev0, st));
-  for (int i = 0; i < iters; ++i)
-    if ((rc = run_launch(L, st))) return rc;
-  SMI_HIP(hipEventRecord(h->ev1, st));
-  SMI_HIP(hipEventSynchronize(h->ev1));
-  float ms = 0.f;
-  SMI_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *ms_avg = ms / iters;
-  if (flops) *flops = L.flops;
-  if (name && name_cap > 0) { strncpy(name, L.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
-  return SMI_OK;
+  SMI_REQUIRE(h, "smi_enc_rows_debug_stage: null argument");
+  return enc_stage(h->rows, "smi_enc_rows_debug_stage", row, name, out_dev, max_floats, dims, stream);
 }
 
 }  // extern "C"
+
+#endif   // SMI_DIAG

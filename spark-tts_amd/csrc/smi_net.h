@@ -1584,4 +1584,31 @@ std::vector<long long> plan_signature(const std::vector<Launch>& P) {
   return sig;
 }
 
+// Run boundaries of a call's rows: consecutive rows with equal plan signatures form a run.  {first row of every run ..., rows}.
+inline std::vector<int> plan_runs(const std::vector<const std::vector<long long>*>& sig) {
+  std::vector<int> runs;
+  for (size_t r = 0; r < sig.size(); ++r)
+    if (r == 0 || *sig[r] != *sig[runs.back()]) runs.push_back((int)r);
+  runs.push_back((int)sig.size());
+  return runs;
+}
+
+// One launch timed alone: once to warm, then `iters` times between two events (smi_voc_time_launch, smi_enc_time_launch).
+inline int time_launch(const Launch& L, hipEvent_t ev0, hipEvent_t ev1, int iters, float* ms_avg, double* flops, char* name, int name_cap,
+                       hipStream_t st) {
+  int rc = run_launch(L, st);
+  if (rc) return rc;
+  SMI_HIP(hipEventRecord(ev0, st));
+  for (int i = 0; i < iters; ++i)
+    if ((rc = run_launch(L, st))) return rc;
+  SMI_HIP(hipEventRecord(ev1, st));
+  SMI_HIP(hipEventSynchronize(ev1));
+  float ms = 0.f;
+  SMI_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+  *ms_avg = ms / iters;
+  if (flops) *flops = L.flops;
+  if (name && name_cap > 0) { strncpy(name, L.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
+  return SMI_OK;
+}
+
 }  // namespace

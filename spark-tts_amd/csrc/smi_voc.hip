@@ -20,6 +20,8 @@
 // Ragged batches: every kernel masks loads beyond the row's own length, so each row equals an
 // un-padded B=1 run of that row.
 #include "smi_net.h"
+#include <algorithm>
+#include <map>
 
 namespace {
 
@@ -619,6 +621,26 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
   return SMI_OK;
 }
 
+// The call's shape checks and h->host_lens, the valid lengths at every resolution: [s][b] = lens[b] * prod(rates[0..s)), and
+// [7][b] = 1, the length-1 "sequences" of the d-vector GEMVs.
+int voc_host_lens(smi_voc* h, const char* who, const int32_t* lens_host, int B, int T) {
+  const smi_voc_cfg& c = h->cfg;
+  SMI_REQUIRE(B >= 1 && B <= c.max_batch, "%s: B=%d outside 1..%d", who, B, c.max_batch);
+  SMI_REQUIRE(T >= 1 && T <= c.max_frames, "%s: T_max=%d outside 1..%d", who, T, c.max_frames);
+  std::vector<int32_t>& hl = h->host_lens;
+  hl.assign((size_t)8 * c.max_batch, 0);
+  for (int b = 0; b < B; ++b) {
+    SMI_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "%s: lens[%d]=%d outside 1..%d", who, b, lens_host[b], T);
+    int up = 1;
+    for (int s = 0; s <= c.dec_nblocks; ++s) {
+      hl[(size_t)s * c.max_batch + b] = lens_host[b] * up;
+      if (s < c.dec_nblocks) up *= c.dec_rates[s];
+    }
+    hl[(size_t)7 * c.max_batch + b] = 1;
+  }
+  return SMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -627,27 +649,16 @@ int smi_voc_forward(smi_voc* h, const int64_t* sem_dev, const int32_t* lens_host
                     float* wav_dev, void* stream) {
   SMI_REQUIRE(h && sem_dev && lens_host && glob_dev && wav_dev, "smi_voc_forward: null argument");
   const smi_voc_cfg& c = h->cfg;
-  SMI_REQUIRE(B >= 1 && B <= c.max_batch, "smi_voc_forward: B=%d outside 1..%d", B, c.max_batch);
-  SMI_REQUIRE(T >= 1 && T <= c.max_frames, "smi_voc_forward: T_max=%d outside 1..%d", T, c.max_frames);
   hipStream_t st = (hipStream_t)stream;
-  // valid lengths at every resolution: lens_dev[s][b] = lens[b] * prod(rates[0..s))
-  std::vector<int32_t>& hl = h->host_lens;
-  hl.assign((size_t)8 * c.max_batch, 0);
-  for (int b = 0; b < B; ++b) {
-    SMI_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "smi_voc_forward: lens[%d]=%d outside 1..%d", b, lens_host[b], T);
-    int up = 1;
-    for (int s = 0; s <= c.dec_nblocks; ++s) {
-      hl[(size_t)s * c.max_batch + b] = lens_host[b] * up;
-      if (s < c.dec_nblocks) up *= c.dec_rates[s];
-    }
-    hl[(size_t)7 * c.max_batch + b] = 1;   // length-1 "sequences" for the d-vector GEMVs
-  }
+  int rc = voc_host_lens(h, "smi_voc_forward", lens_host, B, T);
+  if (rc) return rc;
+  const std::vector<int32_t>& hl = h->host_lens;
   SMI_HIP(hipMemcpyAsync(h->lens_dev, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st));
   std::vector<Launch>& P = h->prog;
   P.clear();
   long long hop = 1;
   for (int i = 0; i < c.dec_nblocks; ++i) hop *= c.dec_rates[i];
-  int rc = voc_program(h, P, sem_dev, T, glob_dev, B, T, wav_dev, hop * T, 0, nullptr);
+  rc = voc_program(h, P, sem_dev, T, glob_dev, B, T, wav_dev, hop * T, 0, nullptr);
   if (rc) return rc;
   if ((rc = check_launches(P, "smi_voc_forward"))) return rc;
   for (const Launch& L : P)
@@ -663,59 +674,40 @@ int smi_voc_forward_rows(smi_voc* h, const int64_t* sem_dev, const int32_t* lens
                          float* wav_dev, void* stream) {
   SMI_REQUIRE(h && sem_dev && lens_host && glob_dev && wav_dev, "smi_voc_forward_rows: null argument");
   const smi_voc_cfg& c = h->cfg;
-  SMI_REQUIRE(B >= 1 && B <= c.max_batch, "smi_voc_forward_rows: B=%d outside 1..%d", B, c.max_batch);
-  SMI_REQUIRE(T >= 1 && T <= c.max_frames, "smi_voc_forward_rows: T_max=%d outside 1..%d", T, c.max_frames);
   hipStream_t st = (hipStream_t)stream;
-  std::vector<int32_t>& hl = h->host_lens;
-  hl.assign((size_t)8 * c.max_batch, 0);
-  for (int b = 0; b < B; ++b) {
-    SMI_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "smi_voc_forward_rows: lens[%d]=%d outside 1..%d", b, lens_host[b], T);
-    int up = 1;
-    for (int s = 0; s <= c.dec_nblocks; ++s) {
-      hl[(size_t)s * c.max_batch + b] = lens_host[b] * up;
-      if (s < c.dec_nblocks) up *= c.dec_rates[s];
-    }
-    hl[(size_t)7 * c.max_batch + b] = 1;
-  }
+  int rc = voc_host_lens(h, "smi_voc_forward_rows", lens_host, B, T);
+  if (rc) return rc;
+  const std::vector<int32_t>& hl = h->host_lens;
   long long hop = 1;
   for (int i = 0; i < c.dec_nblocks; ++i) hop *= c.dec_rates[i];
-  int rc;
   // the plan of every distinct length: the choices of that row's own smi_voc_forward (pointers do not enter a signature)
-  std::vector<std::pair<int, std::vector<long long>>> plans;
-  auto plan_of = [&](int len, const std::vector<long long>** out) -> int {
-    for (const auto& pl : plans)
-      if (pl.first == len) { *out = &pl.second; return SMI_OK; }
-    std::vector<Launch> solo;
-    const int rcs = voc_program(h, solo, sem_dev, len, glob_dev, 1, len, wav_dev, hop * len, 0, nullptr);
-    if (rcs) return rcs;
-    plans.emplace_back(len, plan_signature(solo));
-    *out = &plans.back().second;
-    return SMI_OK;
-  };
-  plans.reserve((size_t)B);   // (plan_of hands out pointers into it)
+  std::map<int, std::vector<long long>> plans;
+  std::vector<const std::vector<long long>*> sig((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    auto it = plans.find(lens_host[b]);
+    if (it == plans.end()) {
+      std::vector<Launch> solo;
+      if ((rc = voc_program(h, solo, sem_dev, lens_host[b], glob_dev, 1, lens_host[b], wav_dev, hop * lens_host[b], 0, nullptr))) return rc;
+      it = plans.emplace(lens_host[b], plan_signature(solo)).first;
+    }
+    sig[b] = &it->second;
+  }
+  const std::vector<int> runs = plan_runs(sig);
   std::vector<Launch>& P = h->prog;
   P.clear();
   std::vector<Launch> G;
-  for (int r0 = 0; r0 < B;) {
-    const std::vector<long long>* sig = nullptr;
-    if ((rc = plan_of(lens_host[r0], &sig))) return rc;
-    int r1 = r0 + 1, Tg = lens_host[r0];
-    for (; r1 < B; ++r1) {
-      const std::vector<long long>* s2 = nullptr;
-      if ((rc = plan_of(lens_host[r1], &s2))) return rc;
-      if (*s2 != *sig) break;
-      Tg = lens_host[r1] > Tg ? lens_host[r1] : Tg;
-    }
+  for (size_t i = 0; i + 1 < runs.size(); ++i) {
+    const int r0 = runs[i], r1 = runs[i + 1];
+    const int Tg = *std::max_element(lens_host + r0, lens_host + r1);
     const PlanShape ps{lens_host[r0], Tg};
     G.clear();
     if ((rc = voc_program(h, G, sem_dev + (size_t)r0 * T, T, glob_dev + (size_t)r0 * c.spk_token_num, r1 - r0, Tg,
                           wav_dev + (size_t)r0 * hop * T, hop * T, r0, &ps))) return rc;
-    if (plan_signature(G) != *sig) {
+    if (plan_signature(G) != *sig[r0]) {
       smi_set_error("smi_voc_forward_rows: the launch list of rows %d..%d does not carry the plan of a %d-frame row", r0, r1 - 1, lens_host[r0]);
       return SMI_EINVAL;
     }
     P.insert(P.end(), G.begin(), G.end());
-    r0 = r1;
   }
   if ((rc = check_launches(P, "smi_voc_forward_rows"))) return rc;
   SMI_HIP(hipMemcpyAsync(h->lens_dev, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st));
@@ -751,21 +743,7 @@ int smi_voc_num_launches(smi_voc* h) { return h ? (int)h->prog.size() : 0; }
 int smi_voc_time_launch(smi_voc* h, int index, int iters, float* ms_avg, double* flops, char* name, int name_cap, void* stream) {
   SMI_REQUIRE(h && ms_avg && iters > 0, "smi_voc_time_launch: bad argument");
   SMI_REQUIRE(index >= 0 && index < (int)h->prog.size(), "smi_voc_time_launch: index %d out of range", index);
-  hipStream_t st = (hipStream_t)stream;
-  const Launch& L = h->prog[index];
-  int rc = run_launch(L, st);
-  if (rc) return rc;
-  SMI_HIP(hipEventRecord(h->ev0, st));
-  for (int i = 0; i < iters; ++i)
-    if ((rc = run_launch(L, st))) return rc;
-  SMI_HIP(hipEventRecord(h->ev1, st));
-  SMI_HIP(hipEventSynchronize(h->ev1));
-  float ms = 0.f;
-  SMI_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  *ms_avg = ms / iters;
-  if (flops) *flops = L.flops;
-  if (name && name_cap > 0) { strncpy(name, L.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
-  return SMI_OK;
+  return time_launch(h->prog[index], h->ev0, h->ev1, iters, ms_avg, flops, name, name_cap, (hipStream_t)stream);
 }
 
 // ---- one block of the vocoder on caller tensors (op-level tests; include/sparkmi.h)

@@ -371,12 +371,40 @@ class BiCodecEncoder:
         ntok = self.tcfg.spk_token_num
         return [(glob[j].view(1, 1, ntok), sem[j: j + 1, : frames[j]]) for j in plan["inverse"]]
 
-    def debug_stage(self, name: str) -> torch.Tensor:
-        out = torch.empty(64 * 1024 * 1024 // 4, dtype=torch.float32, device=self.device)
+    # ---- the solo and the rows entry points share their bodies: `entry` is the C entry's name, `row` its leading row argument
+    def _stage(self, entry: str, row: tuple, name: str, mib: int) -> torch.Tensor:
+        out = torch.empty(mib * 1024 * 1024 // 4, dtype=torch.float32, device=self.device)
         dims = (C.c_int32 * 2)()
-        self._lib.check(self._lib.smi_enc_debug_stage(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims, self._stream()),
-                   "smi_enc_debug_stage")
+        self._lib.check(getattr(self._lib, entry)(self._h, *row, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims, self._stream()), entry)
         return out[: dims[0] * dims[1]].reshape(dims[0], dims[1]).clone()
+
+    def _launch_records(self, entry: str, count: int):
+        self._need_diag()
+        out = []
+        name, info = C.create_string_buffer(512), (C.c_int32 * 8)()
+        for i in range(count):
+            self._lib.check(getattr(self._lib, entry)(self._h, i, name, 512, info), entry)
+            out.append(dict(index=i, name=name.value.decode(), kind=info[0], grid=(info[1], info[2], info[3]), block=info[4],
+                            lds=info[5], cpt=info[6]))
+        return out
+
+    def _io(self, entry: str, row: tuple, buffer: str, data: Optional[np.ndarray], offset: int, count: int, dtype) -> Optional[np.ndarray]:
+        self._need_diag()
+        if data is not None:
+            a = np.ascontiguousarray(data)
+            assert a.dtype.itemsize in (4, 8)
+            self._lib.check(getattr(self._lib, entry)(self._h, *row, buffer.encode(), 1, C.c_void_p(a.ctypes.data), int(offset), a.nbytes // 4), entry)
+            return None
+        out = np.empty(int(count), dtype=np.float32)
+        self._lib.check(getattr(self._lib, entry)(self._h, *row, buffer.encode(), 0, C.c_void_p(out.ctypes.data), int(offset), int(count)), entry)
+        return out.view(dtype)
+
+    def _run(self, entry: str, first: int, last: Optional[int]) -> None:
+        self._need_diag()
+        self._lib.check(getattr(self._lib, entry)(self._h, int(first), int(first if last is None else last), self._stream()), entry)
+
+    def debug_stage(self, name: str) -> torch.Tensor:
+        return self._stage("smi_enc_debug_stage", (), name, 64)
 
     def launches(self) -> int:
         return self._lib.smi_enc_num_launches(self._h)
@@ -403,30 +431,17 @@ class BiCodecEncoder:
 
     def debug_launches(self):
         """[{index, name, kind, grid (x, y, z), block, lds, cpt}] of the list debug_build (or the last eager encode) left."""
-        self._need_diag()
-        out = []
-        name, info = C.create_string_buffer(512), (C.c_int32 * 8)()
-        for i in range(self.launches()):
-            self._lib.check(self._lib.smi_enc_debug_launch(self._h, i, name, 512, info), "smi_enc_debug_launch")
-            out.append(dict(index=i, name=name.value.decode(), kind=info[0], grid=(info[1], info[2], info[3]), block=info[4],
-                            lds=info[5], cpt=info[6]))
-        return out
+        return self._launch_records("smi_enc_debug_launch", self.launches())
 
     def debug_io(self, buffer: str, data: Optional[np.ndarray] = None, offset: int = 0, count: int = 0,
                  dtype=np.float32) -> Optional[np.ndarray]:
         """``data`` given: written at ``offset`` (4-byte words) of the named buffer; else ``count`` words are read and returned
         viewed as ``dtype`` (out_sem holds int64 ids, out_glob int32)."""
-        self._need_diag()
-        if data is not None:
-            a = np.ascontiguousarray(data)
-            assert a.dtype.itemsize in (4, 8)
-            self._lib.check(self._lib.smi_enc_debug_io(self._h, buffer.encode(), 1, C.c_void_p(a.ctypes.data), int(offset),
-                                                       a.nbytes // 4), "smi_enc_debug_io")
-            return None
-        out = np.empty(int(count), dtype=np.float32)
-        self._lib.check(self._lib.smi_enc_debug_io(self._h, buffer.encode(), 0, C.c_void_p(out.ctypes.data), int(offset), int(count)),
-                        "smi_enc_debug_io")
-        return out.view(dtype)
+        return self._io("smi_enc_debug_io", (), buffer, data, offset, count, dtype)
+
+    def debug_run(self, first: int, last: Optional[int] = None) -> None:
+        """Launches first .. last of the list, once each and in order, then synchronises."""
+        self._run("smi_enc_debug_run", first, last)
 
     # ---- the rows list the same way (diag=True only)
     def rows_reserve(self, rows: int, samples: int, ref: int) -> None:
@@ -453,44 +468,16 @@ class BiCodecEncoder:
 
     def rows_debug_launches(self):
         self._need_diag()
-        out = []
-        name, info = C.create_string_buffer(512), (C.c_int32 * 8)()
-        for i in range(self.rows_debug_runs()[1]):
-            self._lib.check(self._lib.smi_enc_rows_debug_launch(self._h, i, name, 512, info), "smi_enc_rows_debug_launch")
-            out.append(dict(index=i, name=name.value.decode(), kind=info[0], grid=(info[1], info[2], info[3]), block=info[4],
-                            lds=info[5], cpt=info[6]))
-        return out
+        return self._launch_records("smi_enc_rows_debug_launch", self.rows_debug_runs()[1])
 
     def rows_debug_io(self, row: int, buffer: str, data: Optional[np.ndarray] = None, offset: int = 0, count: int = 0,
                       dtype=np.float32) -> Optional[np.ndarray]:
         """debug_io on row ``row``'s copy of the named workspace buffer"""
-        self._need_diag()
-        if data is not None:
-            a = np.ascontiguousarray(data)
-            assert a.dtype.itemsize in (4, 8)
-            self._lib.check(self._lib.smi_enc_rows_debug_io(self._h, int(row), buffer.encode(), 1, C.c_void_p(a.ctypes.data), int(offset),
-                                                            a.nbytes // 4), "smi_enc_rows_debug_io")
-            return None
-        out = np.empty(int(count), dtype=np.float32)
-        self._lib.check(self._lib.smi_enc_rows_debug_io(self._h, int(row), buffer.encode(), 0, C.c_void_p(out.ctypes.data), int(offset),
-                                                        int(count)), "smi_enc_rows_debug_io")
-        return out.view(dtype)
+        return self._io("smi_enc_rows_debug_io", (int(row),), buffer, data, offset, count, dtype)
 
     def rows_debug_run(self, first: int, last: Optional[int] = None) -> None:
-        self._need_diag()
-        self._lib.check(self._lib.smi_enc_rows_debug_run(self._h, int(first), int(first if last is None else last), self._stream()),
-                        "smi_enc_rows_debug_run")
+        self._run("smi_enc_rows_debug_run", first, last)
 
     def rows_debug_stage(self, row: int, name: str) -> torch.Tensor:
         self._need_diag()
-        out = torch.empty(16 * 1024 * 1024 // 4, dtype=torch.float32, device=self.device)
-        dims = (C.c_int32 * 2)()
-        self._lib.check(self._lib.smi_enc_rows_debug_stage(self._h, int(row), name.encode(), C.c_void_p(out.data_ptr()), out.numel(), dims,
-                                                           self._stream()), "smi_enc_rows_debug_stage")
-        return out[: dims[0] * dims[1]].reshape(dims[0], dims[1]).clone()
-
-    def debug_run(self, first: int, last: Optional[int] = None) -> None:
-        """Launches first .. last of the list, once each and in order, then synchronises."""
-        self._need_diag()
-        self._lib.check(self._lib.smi_enc_debug_run(self._h, int(first), int(first if last is None else last), self._stream()),
-                        "smi_enc_debug_run")
+        return self._stage("smi_enc_rows_debug_stage", (int(row),), name, 16)

@@ -236,7 +236,7 @@ def test_tap_three_modes():
     # mode 0 (first tap): acc = h, the same bits
     enc.debug_io("h", h); enc.debug_io("acc", np.full((H, Tn), SENTINEL))
     l = _run(enc, f"w2v.tap{a}")
-    assert l["grid"] == ((n + 255) // 256, 1, 1) and l["block"] == 256
+    assert l["grid"] == ((Tn + 255) // 256, H, 1) and l["block"] == 256            # (channel, frame): the form the rows list runs
     assert ec.accept_equal(enc.debug_io("acc", count=n).reshape(H, Tn), h)
     # mode 1 (second tap): acc += h, in place -- one run
     enc.debug_io("acc", acc0)

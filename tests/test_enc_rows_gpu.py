@@ -177,6 +177,54 @@ def test_solo_path_is_undisturbed_by_a_rows_call():
         _same(rows[b], {k: _solo(False)[b][k] for k in ("sem", "glob", "feat")}, f"rows row {b}")
 
 
+def test_solo_list_is_the_one_row_rows_list():
+    """build-only: smi_enc_forward's list is the rows builder's list of that one row, launch record by launch record"""
+    enc = _pair(False)[0]
+    wavs, refs = _inputs()
+    enc.rows_reserve(len(wavs), max(len(w) for w in wavs), max(len(r) for r in refs))
+    for t, r in zip(FRAMES, N_REF):
+        n = ec.samples_for(t)
+        frames, count = enc.debug_build(n, r)
+        solo = enc.debug_launches()
+        rframes, rcount, starts = enc.rows_debug_build([n], [r])
+        rows = enc.rows_debug_launches()
+        assert (frames, count, starts) == (t, rcount, [0]) and rframes == [t] and len(solo) == len(rows) == count > 0
+        for a, b in zip(solo, rows):
+            for field in ("index", "name", "kind", "grid", "block", "lds", "cpt"):
+                assert a[field] == b[field], (t, r, field, a, b)
+    wcfg, tcfg, vcfg = T.tiny_wav2vec2(), T.tiny_tok(), C.tiny_bicodec()
+    long_enc = _make(wcfg, tcfg, vcfg, max_seconds=41.0, ref_seconds=1.0)[0]
+    with pytest.raises(SparkMIError, match=r"code -1.*2041 frames"):
+        long_enc.debug_build(ec.samples_for(2041), 200)
+    assert long_enc.launches() == 0 and long_enc.debug_launches() == []                # refused before anything was built
+
+
+def test_graph_cache_round_robin():
+    """Ten (samples, reference samples) keys on one handle that caches eight graphs, each encoded three times in round-robin
+    order.  Round one runs every key eagerly; round two captures every key, and the ninth and tenth captures evict the two least
+    recently used graphs; round three finds its key evicted every time (ten keys through eight entries, oldest first), so it
+    captures again and evicts in turn; a last pass over the eight keys then cached replays them.  A rows call sits between rounds
+    two and three.  Every result (sem, glob, feat) carries the bits of its key's first."""
+    wcfg, tcfg, vcfg = T.tiny_wav2vec2(), T.tiny_tok(), C.tiny_bicodec()
+    enc = _make(wcfg, tcfg, vcfg, max_seconds=1.0, ref_seconds=1.0)[0]
+    rng = np.random.default_rng(19)
+    keys = [(ec.samples_for(2 + i), 129 + i) for i in range(10)]
+    wavs = [(0.1 * rng.standard_normal(n) + 0.01).astype(np.float32) for n, _ in keys]
+    refs = [(0.2 * rng.standard_normal(r)).astype(np.float32) for _, r in keys]
+    first = [_solo_run(enc, w, r, ("feat",)) for w, r in zip(wavs, refs)]
+    for i, f in enumerate(first):
+        assert f["sem"].shape == (2 + i,)
+    for rnd in (2, 3):
+        if rnd == 3:
+            enc.rows_reserve(3, max(len(w) for w in wavs), max(len(r) for r in refs))
+            for j, got in zip((9, 0, 4), _rows_call(enc, [wavs[j] for j in (9, 0, 4)], [refs[j] for j in (9, 0, 4)], ("feat",))):
+                _same(got, first[j], f"rows call, key {j}")
+        for i in range(10):
+            _same(_solo_run(enc, wavs[i], refs[i], ("feat",)), first[i], f"round {rnd}, key {i}")
+    for i in range(2, 10):
+        _same(_solo_run(enc, wavs[i], refs[i], ("feat",)), first[i], f"replay, key {i}")
+
+
 def test_tokenize_rows_returns_the_callers_order():
     enc = _pair(False)[0]
     wavs, refs = _inputs()
