@@ -55,7 +55,9 @@ int smi_llm_debug_hidden(smi_llm* h, float* out_host, int n);
  * M rows after smi_llm_debug_layer).  what: 0 q [M][q_dim] f32, 1 / 2 / 3 the operand
  * triples of o_proj / down_proj / the next norm ([K / 32][3][4][M][16 B]), 4 the residual rows, 5 the engine's
  * granules [2][per buffer] u64 {tag << 32 | f32 bits}, 6 partial sums of squares [hidden / 4], 7 K rows of layer 0, slot 0,
- * kv head 0 (bf16), 8 h + o_proj of the fused one-row path.  16 .. 20: the prefill workspace after smi_llm_debug_prefill_layer, for
+ * kv head 0 (bf16), 8 h + o_proj of the fused one-row path, 9 the live rows' logits [rows][vocab] f32 as the last step's lm_head left
+ * them (written only by a step that needs them: sampling, penalties, log-probabilities; a restricted lm_head writes the listed
+ * tiles only).  16 .. 20: the prefill workspace after smi_llm_debug_prefill_layer, for
  * its M rows: 16 q [M][q_dim] f32, 17 / 18 / 19 the operand triples of o_proj / down_proj / the next norm (same layout, this M),
  * 20 the residual rows [M][hidden] f32.  cap must hold the buffer (M rows x 4864 x 6 B at the 0.5B shape: size it from M). */
 int smi_llm_debug_read(smi_llm* h, int what, void* out_host, size_t cap, size_t* got);

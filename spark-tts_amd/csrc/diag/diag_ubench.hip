@@ -58,7 +58,58 @@ __global__ void ub_xcc(XArg a) {
   if (acc == 0x12345678u) a.out[1] = 1.0f;
   if (blockIdx.x == 0 && threadIdx.x == 0) a.out[0] = a.out[0] + 1.0f;
 }
+// Kernel-argument round trip at entry: the same tiny kernel (a handful of blocks, one small load from an address taken from its
+// arguments, helper-block test first) in two forms.  ub_karg_struct takes a 328-byte struct by value, like GemmP: the helper test
+// and the address wait for s_loads of two of its 64-byte lines.  ub_karg_hot takes the values on that path as 12 dwords of leading
+// scalar parameters in front of the same struct: built with -amdgpu-kernarg-preload-count they are in SGPRs when the wave
+// starts (where the firmware preloads; otherwise the compatibility block in front of the entry loads them).  Neither form reads
+// blockDim or gridDim: those live in the implicit arguments behind the struct and would cost both the same scalar load.
+struct KArg { const float* in; float* out; int pad0[60]; int work_blocks; int n; int pad1[16]; };   // 328 bytes, fields on lines 0 and 4
+static_assert(sizeof(KArg) == 328, "KArg: the size class of GemmP");
+__global__ void ub_karg_struct(KArg a) {
+  if ((int)blockIdx.x >= a.work_blocks) return;
+  const float v = a.in[(blockIdx.x * 256u + threadIdx.x) & (unsigned)a.n];
+  if (v == 12345.0f) a.out[1] = v;
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.out[0] = v + 1.0f;
+}
+__global__ void ub_karg_hot(const float* in, float* out, const float* in2, const float* in3, int work_blocks, int n, int h6, int h7, KArg a) {
+  if ((int)blockIdx.x >= work_blocks) return;
+  const float v = in[(blockIdx.x * 256u + threadIdx.x) & (unsigned)n];
+  if (v == 12345.0f) out[1] = v + (float)(h6 + h7) + (in2 == in3 ? 1.0f : 0.0f) + (float)a.pad1[3];   // never taken: keeps every parameter live
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = v + 1.0f;
+}
 }  // namespace
+
+// chain of n_kernels dependent launches of one form (0: struct by value, 1: hot leading parameters + struct), graph replay
+extern "C" int smi_ubench_kernarg(int form, int grid, int block, int n_kernels, int iters, const void* buf, float* scratch,
+                                  float* us_per_kernel, void* stream) {
+  if (grid < 1 || block < 1 || block > 1024 || n_kernels < 1 || iters < 1) { smi_set_error("ubench_kernarg: bad sizes"); return SMI_EINVAL; }
+  hipStream_t st = (hipStream_t)stream, cs;
+  SMI_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+  hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
+  KArg a = {};
+  a.in = (const float*)buf; a.out = scratch; a.work_blocks = grid; a.n = 1023;   // reads buf[0 .. 1023]
+  SMI_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+  for (int i = 0; i < n_kernels; ++i) {
+    if (form == 0) hipLaunchKernelGGL(ub_karg_struct, dim3(grid), dim3(block), 0, cs, a);
+    else hipLaunchKernelGGL(ub_karg_hot, dim3(grid), dim3(block), 0, cs, a.in, a.out, a.in, a.in, a.work_blocks, a.n, 0, 0, a);
+  }
+  SMI_HIP(hipStreamEndCapture(cs, &g));
+  SMI_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+  hipEvent_t e0, e1;
+  SMI_HIP(hipEventCreate(&e0)); SMI_HIP(hipEventCreate(&e1));
+  SMI_HIP(hipGraphLaunch(ge, st));
+  SMI_HIP(hipEventRecord(e0, st));
+  for (int i = 0; i < iters; ++i) SMI_HIP(hipGraphLaunch(ge, st));
+  SMI_HIP(hipEventRecord(e1, st));
+  SMI_HIP(hipEventSynchronize(e1));
+  float ms = 0;
+  SMI_HIP(hipEventElapsedTime(&ms, e0, e1));
+  *us_per_kernel = ms * 1e3f / ((float)iters * n_kernels);
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  (void)hipGraphExecDestroy(ge); (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs);
+  return SMI_OK;
+}
 
 // chain of n kernels; kernel i streams region i (cold), and with helpers > 0 also prefetches region i+1
 extern "C" int smi_ubench_xcc(int work_blocks, int helper_blocks, int block, int loads, int n_kernels, int iters,

@@ -267,13 +267,19 @@ __device__ __forceinline__ void smi_kernarg_lines(const GemmP& p) {
   asm volatile("" ::"s"(p.W), "s"(p.bias), "s"(p.work_blocks), "s"(p.pf.base), "s"(p.Yin), "s"(gridDim.x));
 }
 
+// Hot entries (one-row decode): a second __global__ entry of a one-row kernel whose LEADING parameters are the values on the
+// address path of its first loads and of the helper-block test -- pointers first, then ints, at most 14 dwords -- followed by the
+// usual struct.  Built with -amdgpu-kernarg-preload-count (Makefile) those dwords are in SGPRs when the wave starts, so the
+// first weight / K / V / partial loads leave without a scalar round trip to the kernel-argument segment in front of them (the
+// struct's other lines are requested by the compiler where the epilogue needs them, behind those loads).  The launcher passes
+// the hot values from the same struct it passes behind them; the body is shared with the struct-only entry, which every other
+// instantiation keeps.  A kernel whose first parameter is a struct gets no preload and compiles as without the flag.
 template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int KVF32, int H = 1, int OCC = 1, int LEAN = 0, int NOH = kMaxOHeads>
-__global__ __launch_bounds__(NW * 64, OCC) void k_gemm(GemmP p) {
+__device__ __forceinline__ void gemm_body(const GemmP& p) {
   static_assert(H == 1 || ((H == 2 || H == 4) && NTB == 1 && EPI == EPI_RESID), "row-split tiles: RESID, one tile per block");
   static_assert(PRO != PRO_FUSEDO || (LEAN == 2 && MT == 1 && EPI == EPI_SWIGLU), "PRO_FUSEDO: the one-row gate_up kernel");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if constexpr (LEAN == 2) smi_kernarg_lines(p);
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, NW * 64);
     return;
@@ -782,6 +788,35 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_gemm(GemmP p) {
   }
 }
 
+template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int KVF32, int H = 1, int OCC = 1, int LEAN = 0, int NOH = kMaxOHeads>
+__global__ __launch_bounds__(NW * 64, OCC) void k_gemm(GemmP p) {
+  if constexpr (LEAN == 2) smi_kernarg_lines(p);
+  gemm_body<MT, NTB, NW, U, WB, PRO, EPI, KVF32, H, OCC, LEAN, NOH>(p);
+}
+// Hot entry of the one-row QKV (PRO_NORM: a = XS, b = sspart, c = rows, n = npart) and gate_up (PRO_FUSEDO: a = part_o, b = hres,
+// c = gam, n = n_oheads) kernels: 13 dwords (ldsb: left in the struct, the compiler fetches it at entry together with a helper
+// field and the work path then waits for that load in front of its first loads)
+template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int KVF32, int H = 1, int OCC = 1, int LEAN = 0, int NOH = kMaxOHeads>
+__global__ __launch_bounds__(NW * 64, OCC) void k_gemm_hot(const uint4* W, const void* a, const void* b, const void* c, int KT, int NT,
+                                                           int work_blocks, int n, int ldsb, GemmP p) {
+  static_assert(LEAN == 2 && (PRO == PRO_FUSEDO || (PRO == PRO_NORM && EPI == EPI_QKV)), "hot entries: the one-row QKV and gate_up kernels");
+  GemmP q = p;
+  q.W = W; q.KT = KT; q.NT = NT; q.work_blocks = work_blocks; q.ldsb = ldsb;
+  if constexpr (PRO == PRO_FUSEDO) { q.part_o = (const float*)a; q.hres = (const float*)b; q.gam = (const float*)c; q.n_oheads = n; }
+  else { q.XS = (const unsigned char*)a; q.sspart = (const float*)b; q.rows = (const RowDesc*)c; q.npart = n; }
+  gemm_body<MT, NTB, NW, U, WB, PRO, EPI, KVF32, H, OCC, LEAN, NOH>(q);
+}
+// the hot entry's launch: the hot values come from the struct that travels behind them
+template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int KVF32, int H, int OCC, int NOH = kMaxOHeads>
+void launch_gemm_hot(const GemmP& p, dim3 grid, size_t lds, hipStream_t st) {
+  if constexpr (PRO == PRO_FUSEDO)
+    hipLaunchKernelGGL((k_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, KVF32, H, OCC, 2, NOH>), grid, dim3(NW * 64), lds, st, p.W, (const void*)p.part_o,
+                       (const void*)p.hres, (const void*)p.gam, p.KT, p.NT, p.work_blocks, p.n_oheads, p.ldsb, p);
+  else
+    hipLaunchKernelGGL((k_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, KVF32, H, OCC, 2, NOH>), grid, dim3(NW * 64), lds, st, p.W, (const void*)p.XS,
+                       (const void*)p.sspart, (const void*)p.rows, p.KT, p.NT, p.work_blocks, p.npart, p.ldsb, p);
+}
+
 // ------------------------------------------------------------------------------------------
 // One-row RESID GEMV with four row parts per weight tile (down_proj at batch 1), FULL load instructions.
 // k_gemm<.., H = 4> gives each of 16 waves one chain (k tiles kt mod 16) and, a part being 4 of a tile's 16 rows, loads with
@@ -794,10 +829,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void k_gemm(GemmP p) {
 // diag_gemv.hip): 5.92 -> 3.98 us per launch.  TPC = k tiles per chain the registers hold (KT <= 16 * TPC).
 // ------------------------------------------------------------------------------------------
 template <int TPC>
-__global__ __launch_bounds__(256) void k_down1(GemmP p) {
+__device__ __forceinline__ void down1_body(const GemmP& p) {
   __shared__ __attribute__((aligned(16))) float red[16 * 4];   // read and written as float4
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  smi_kernarg_lines(p);
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, 256);
     return;
@@ -866,6 +900,26 @@ __global__ __launch_bounds__(256) void k_down1(GemmP p) {
     *(uint2*)(p.XSout + o + 2 * pl) = make_uint2(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16));
     p.ssout[(size_t)nt * 4 + part] = ssq;
   }
+}
+template <int TPC>
+__global__ __launch_bounds__(256) void k_down1(GemmP p) {
+  smi_kernarg_lines(p);
+  down1_body<TPC>(p);
+}
+// Hot entry (12 dwords): the weight and operand addresses, the epilogue's two early loads (res = the residual row's source,
+// Yin or else Y) and the helper test
+template <int TPC>
+__global__ __launch_bounds__(256) void k_down1_hot(const uint4* W, const unsigned char* XS, const float* res, const float* gamma_next, int KT,
+                                                   int NT, int work_blocks, int wperm, GemmP p) {
+  GemmP q = p;
+  q.W = W; q.XS = XS; q.Yin = res; q.gamma_next = gamma_next; q.KT = KT; q.NT = NT; q.work_blocks = work_blocks; q.wperm = wperm;
+  __builtin_assume(q.Yin != nullptr);
+  down1_body<TPC>(q);
+}
+template <int TPC>
+void launch_down1_hot(const GemmP& p, int grid, hipStream_t st) {
+  hipLaunchKernelGGL(k_down1_hot<TPC>, dim3(grid), dim3(256), 0, st, p.W, p.XS, (const float*)(p.Yin ? p.Yin : p.Y), p.gamma_next, p.KT, p.NT,
+                     p.work_blocks, p.wperm, p);
 }
 
 // The same for 2 .. 8 rows (k_downS<TPC, MG>, rows in MG groups of four): a wave's load instruction still carries four chains'
@@ -2244,7 +2298,7 @@ __device__ __forceinline__ void attn_put_pieces(unsigned char* xs, int d, uint32
 // another: nothing can dead-lock and there is nothing to time out.  The o_proj launch (and its boundary) is gone for these row
 // counts; gate_up reads an ordinary operand (with more rows the per-head partials would be re-read by every gate_up block).
 template <int KVF32, int ONE = 0, int FUSE = 0, int PG = 0>
-__global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP p) {
+__device__ __forceinline__ void attn_body(const AttnP& p) {
   static_assert(!FUSE || (FUSE == 1 && ONE == 1) || (FUSE == 2 && ONE == 2), "fused o_proj: one row (per-head partials for gate_up) or 2..8 rows (last-arriver head sum)");
   constexpr int LPT = KVF32 ? 16 : 8;   // lanes per token row (each lane 16 bytes)
   constexpr int DPL = kHeadDim / LPT;   // dims per lane
@@ -2261,13 +2315,6 @@ __global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP
   __shared__ __attribute__((aligned(16))) unsigned char xsl[FUSE == 1 ? kAttnWaves * 2 * 3 * 4 * 16 : FUSE ? 2 * 3 * 4 * 16 : 16];
   __shared__ unsigned int s_last;   // FUSE == 2: this block was the last of its (row, quarter) to arrive
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if constexpr (ONE == 1) {
-    // one row: every 64-byte line of kernel arguments the block reads is requested at entry, together (the compiler asked
-    // for them one after the other -- the helper test, then q / K / V's addresses -- three scalar round trips in a row in
-    // front of the first global load)
-    if constexpr (FUSE) asm volatile("" ::"s"(p.q), "s"(p.work_blocks), "s"(p.Wo), "s"(gridDim.x));
-    else asm volatile("" ::"s"(p.q), "s"(p.work_blocks), "s"(gridDim.x));
-  }
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, (FUSE ? 2 : 1) * kAttnWaves * 64);
     return;
@@ -2536,6 +2583,32 @@ __global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP
     }
     if (tid == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
   }
+}
+template <int KVF32, int ONE = 0, int FUSE = 0, int PG = 0>
+__global__ __launch_bounds__((FUSE ? 2 : 1) * kAttnWaves * 64) void k_attn(AttnP p) {
+  if constexpr (ONE == 1) {
+    // one row: every 64-byte line of kernel arguments the block reads is requested at entry, together (the compiler asked
+    // for them one after the other -- the helper test, then q / K / V's addresses -- three scalar round trips in a row in
+    // front of the first global load)
+    if constexpr (FUSE) asm volatile("" ::"s"(p.q), "s"(p.work_blocks), "s"(p.Wo), "s"(gridDim.x));
+    else asm volatile("" ::"s"(p.q), "s"(p.work_blocks), "s"(gridDim.x));
+  }
+  attn_body<KVF32, ONE, FUSE, PG>(p);
+}
+// Hot entry of the one-row fused attention + o_proj (contiguous KV slots), 14 dwords: the descriptor, q, K, V and W_o
+// addresses, the helper test and the ints of the address arithmetic (hg = n_heads | group << 16: one dword for two small counts)
+template <int KVF32>
+__global__ __launch_bounds__(2 * kAttnWaves * 64) void k_attn_hot(const float* q, const void* kcache, const void* vcache, const RowDesc* rows,
+                                                                  const uint4* Wo, int work_blocks, int max_pos, int NTo, int hg, AttnP p) {
+  AttnP a = p;
+  a.q = q; a.kcache = kcache; a.vcache = vcache; a.rows = rows; a.Wo = Wo; a.work_blocks = work_blocks; a.max_pos = max_pos; a.NTo = NTo;
+  a.n_heads = hg & 0xffff; a.group = hg >> 16;
+  attn_body<KVF32, 1, 1, 0>(a);
+}
+template <int KVF32>
+void launch_attn_hot(const AttnP& a, int grid, hipStream_t st) {
+  hipLaunchKernelGGL(k_attn_hot<KVF32>, dim3(grid), dim3(2 * kAttnWaves * 64), 0, st, a.q, a.kcache, a.vcache, a.rows, a.Wo, a.work_blocks,
+                     a.max_pos, a.NTo, a.n_heads | (a.group << 16), a);
 }
 
 // Prompt rows (prefill of more than one chunk): one WAVE per (row, head), eight consecutive rows of one head per
@@ -4006,6 +4079,10 @@ void graphs_flush(smi_llm* L) {
   L->graph = nullptr;
 }
 
+// SPARKMI_TUNE2 bits (diagnostics): a one-row kernel keeps its struct-only entry instead of the hot one, for A/B runs
+// of one build -- 8388608 QKV, 16777216 fused attention, 33554432 gate_up, 67108864 down_proj
+constexpr int kColdQkv = 8388608, kColdAttn = 16777216, kColdGateUp = 33554432, kColdDown = 67108864;
+
 template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int H = 1, int OCC = 1>
 int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
   const int work = (p.NT + NTB - 1) / NTB * H;
@@ -4015,9 +4092,13 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
     // one row: four chains per wave, full load instructions (k_down1; same bits).  SPARKMI_TUNE2 bit 1048576 keeps k_gemm (A/B)
     if (p.M == 1 && !p.stamps && p.KT <= 160 && !(L->tune2 & 1048576)) {
       const int helpers = (L->prefetch_mask & 4) && p.pf.base && work < 232 ? ((L->tune2 & 4194304) ? 224 : (256 - work) / 8 * 8) : 0;   // bit 4194304: as many helper blocks as work blocks (they share the CUs)
-      if (p.KT <= 32) hipLaunchKernelGGL(k_down1<2>, dim3(work + helpers), dim3(256), 0, st, p);
-      else if (p.KT <= 96) hipLaunchKernelGGL(k_down1<6>, dim3(work + helpers), dim3(256), 0, st, p);
-      else hipLaunchKernelGGL(k_down1<10>, dim3(work + helpers), dim3(256), 0, st, p);
+      if (L->tune2 & kColdDown) {   // SPARKMI_TUNE2 bit kColdDown: the struct-only entry (A/B)
+        if (p.KT <= 32) hipLaunchKernelGGL(k_down1<2>, dim3(work + helpers), dim3(256), 0, st, p);
+        else if (p.KT <= 96) hipLaunchKernelGGL(k_down1<6>, dim3(work + helpers), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(k_down1<10>, dim3(work + helpers), dim3(256), 0, st, p);
+      } else if (p.KT <= 32) launch_down1_hot<2>(p, work + helpers, st);
+      else if (p.KT <= 96) launch_down1_hot<6>(p, work + helpers, st);
+      else launch_down1_hot<10>(p, work + helpers, st);
       SMI_LAUNCH_CHECK();
       return SMI_OK;
     }
@@ -4064,11 +4145,29 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
     if constexpr (PRO == PRO_NORM && EPI == EPI_SWIGLU && H == 1 && MT == 1) {
       if (p.part_o) {   // one row behind the fused o_proj: the operand is built in the kernel from the per-head partials
 #ifndef SMI_NOH16   // (A/B build: make variant NAME=noh16 VARFLAGS=-DSMI_NOH16 keeps the 16-slot form)
-        if (p.n_oheads == 14) hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2, 14>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
-        else if (p.n_oheads == 4) hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2, 4>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
-        else
+        // the adopted block shape at the two fused head counts starts through the hot entry (SPARKMI_TUNE2 bit kColdGateUp: the
+        // struct-only entry, A/B); tune sweeps and the generic head-count form (no product shape reaches it) keep the struct entry
+        constexpr bool kHotGU = NW == 8 && U == 2 && WB == 2 && OCC == 6 && NTB == 1;
+        const bool hot = kHotGU && !(L->tune2 & kColdGateUp);
+        if (p.n_oheads == 14) {
+          if constexpr (kHotGU) if (hot) launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 14>(p, dim3(work + helpers, groups), lds + 1024, st);
+          if (!hot) hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2, 14>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
+        } else if (p.n_oheads == 4) {
+          if constexpr (kHotGU) if (hot) launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 4>(p, dim3(work + helpers, groups), lds + 1024, st);
+          if (!hot) hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2, 4>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
+        } else
 #endif
         hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
+        SMI_LAUNCH_CHECK();
+        return SMI_OK;
+      }
+    }
+    if constexpr (PRO == PRO_NORM && EPI == EPI_QKV && kLean && NW == 16 && U == 2 && WB == 1) {
+      // one-row QKV in its adopted block shape: the hot entry (SPARKMI_TUNE2 bit kColdQkv: the struct-only entry, A/B); the tune
+      // sweeps' shapes keep the struct entry
+      if (!(L->tune2 & kColdQkv)) {
+        if (L->cfg.kv_dtype) launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>(p, dim3(work + helpers, groups), lds, st);
+        else launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>(p, dim3(work + helpers, groups), lds, st);
         SMI_LAUNCH_CHECK();
         return SMI_OK;
       }
@@ -4424,6 +4523,8 @@ int launch_attn(smi_llm* L, AttnP a, int helpers_ok, hipStream_t st) {
 #endif
   if (fuse && pg)
     hipLaunchKernelGGL((k_attn<KVF32, 1, 1, 1>), dim3(a.work_blocks + helpers), dim3(2 * kAttnWaves * 64), 0, st, a);
+  else if (fuse && !(L->tune2 & kColdAttn) && a.n_heads < 65536 && a.group < 32768)   // SPARKMI_TUNE2 bit kColdAttn: the struct-only entry (A/B)
+    launch_attn_hot<KVF32>(a, a.work_blocks + helpers, st);
   else if (fuse)
     hipLaunchKernelGGL((k_attn<KVF32, 1, 1>), dim3(a.work_blocks + helpers), dim3(2 * kAttnWaves * 64), 0, st, a);
   else if (a.M == 1 && a.nseg == 1 && a.slot_is_row && pg)
@@ -6896,7 +6997,7 @@ int smi_llm_debug_hidden(smi_llm* L, float* out_host, int n) {
 
 // Tests / debugging: raw copy of one scratch buffer (what: 0 q [Q] f32, 1 attention operand triples, 2 act triples, 3 h operand
 // triples, 4 h [H] f32, 5 engine granules [2][per buffer] u64, 6 partial sums of squares [H / 4], 7 layer-0 K cache of slot 0
-// head 0, 8 h + o_proj [H] (fused path), 16 .. 20 the prefill workspace's q, attention triples, act triples, h triples, h for the
+// head 0, 8 h + o_proj [H] (fused path), 9 the live rows' logits [rows][V] f32 as the last step's lm_head left them, 16 .. 20 the prefill workspace's q, attention triples, act triples, h triples, h for the
 // rows of the last smi_llm_debug_prefill_layer); returns the bytes copied in *got.
 int smi_llm_debug_read(smi_llm* L, int what, void* out_host, size_t cap, size_t* got) {
   SMI_REQUIRE(L && out_host && got, "smi_llm_debug_read: null argument");
@@ -6914,6 +7015,7 @@ int smi_llm_debug_read(smi_llm* L, int what, void* out_host, size_t cap, size_t*
     case 6: src = L->dec.ss; n = R * L->H; break;
     case 7: src = L->kcache; n = (size_t)L->cfg.max_positions * kHeadDim * 2; break;
     case 8: src = L->h2; n = (size_t)L->H * 4; break;
+    case 9: src = L->logits; n = R * L->cfg.vocab_size * 4; break;
     case 16: src = L->big.q; n = P * L->Q * 4; break;
     case 17: src = L->big.xs_attn; n = P * L->Q * 6; break;
     case 18: src = L->big.xs_act; n = P * L->I * 6; break;

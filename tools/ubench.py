@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Launch-floor microbenchmarks on the GPU box: python tools/ubench.py"""
+"""Launch-floor microbenchmarks on the GPU box: python tools/ubench.py
+   python tools/ubench.py kernarg   only the kernel-argument round trip (struct by value against preloaded leading parameters)"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "spark-tts_amd"))
@@ -11,6 +12,29 @@ l.smi_last_error.restype = C.c_char_p
 f = l.smi_ubench_chain
 f.restype = C.c_int
 f.argtypes = [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+def kernarg():
+    """chain of dependent tiny launches, graph replay: 328-byte struct by value against 12 preloaded dwords in front of it"""
+    fk = l.smi_ubench_kernarg
+    fk.restype = C.c_int
+    fk.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p]
+    kb = torch.zeros(4096, dtype=torch.float32, device="cuda")
+    ks = torch.zeros(64, dtype=torch.float32, device="cuda")
+    kst = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    def one(form, grid, block):
+        us = C.c_float(0)
+        rc = fk(form, grid, block, 96, 200, C.c_void_p(kb.data_ptr()), C.c_void_p(ks.data_ptr()), C.byref(us), kst)
+        assert rc == 0, l.smi_last_error()
+        return us.value
+    for grid, block in ((8, 256), (72, 256), (224, 256), (56, 1024)):
+        one(0, grid, block); one(1, grid, block)
+        rows = [(one(0, grid, block), one(1, grid, block)) for _ in range(5)]   # alternating
+        a, b = sorted(r[0] for r in rows), sorted(r[1] for r in rows)
+        d = sorted(r[0] - r[1] for r in rows)
+        print(f"kernarg grid {grid:4d} x {block:4d}  struct {a[2]:6.3f} us/launch [{a[0]:.3f} .. {a[4]:.3f}]  "
+              f"hot {b[2]:6.3f} [{b[0]:.3f} .. {b[4]:.3f}]  struct - hot {d[2]:+.3f} [{d[0]:+.3f} .. {d[4]:+.3f}]", flush=True)
+if sys.argv[1:] == ["kernarg"]:
+    kernarg()
+    sys.exit(0)
 buf = torch.zeros(1 << 28, dtype=torch.uint8, device="cuda")      # 256 MiB
 scr = torch.zeros(64, dtype=torch.float32, device="cuda")
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -55,3 +79,4 @@ runx("xcc-affine, no prefetch (cold)", 304, 0, 256, 14)
 runx("xcc-affine + helpers prefetch next", 304, 208, 256, 14)
 runx("xcc-affine, no prefetch (cold)", 56, 0, 1024, 10)
 runx("xcc-affine + helpers prefetch next", 56, 200, 1024, 10)
+kernarg()
