@@ -601,6 +601,56 @@ int smi_enc_debug_stage(smi_enc* h, const char* name, float* out_dev, size_t max
 int smi_enc_num_launches(smi_enc* h);
 int smi_enc_time_launch(smi_enc* h, int index, int iters, float* ms_avg, double* flops, char* name, int name_cap, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Audio front / back end on the device: a rational resampler with scipy.signal.resample_poly's arithmetic (what
+ * sparkmi/encoder.py: load_audio runs on the host; NOT the reference's soxr VHQ), and the voice prompt's preparation
+ * (sparktts/utils/audio.py: audio_volume_normalize; audio_tokenizer.py:57-72: get_ref_clip) written straight into the buffers
+ * smi_enc_forward_rows reads.  Opt-in: nothing else of the library calls it.
+ *
+ * Resampling.  For an input row x[0 .. n), a ratio up/down in lowest terms and taps h[0 .. 2H]:
+ *     n_out = ceil(n * up / down)                                               (smi_rs_out_len)
+ *     y[k]  = sum over j of x[j] * h[H + k * down - j * up],   0 <= j < n, tap index in [0, 2H]   (zero-padded edges)
+ * With h = firwin(2H + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up and H = 10 * max(up, down) this is
+ * resample_poly(x, up, down) (sparkmi/audio.py: resample_taps computes those taps with numpy alone).  Taps are data the caller
+ * registers once per ratio (smi_rs_register: float64 on the host, rounded to fp32 once, kept on the device by the handle).
+ * A sample is summed in ascending j, in fp32, in one accumulator, product and sum rounded separately: its bits depend on its
+ * row's samples and ratio alone -- not on the row's place in the call, the other rows, the strides or the tiling.  up = down = 1
+ * needs no filter and copies the row.  Indices are 32-bit: n * up and n_out * down must stay below 2^31.
+ *
+ * smi_rs_create reserves nothing but limits: max_rows (1..64) rows a call, max_in / max_out samples a row (1..2^24); a call
+ * beyond them is refused.  One launch covers every row of a call (the row index is in the grid; rows may carry different
+ * ratios); the calls are asynchronous on the caller's stream and never synchronise.  Every argument of every row is checked
+ * before anything reaches the device: a bad one returns SMI_EINVAL, names the argument in smi_last_error and launches nothing. */
+typedef struct smi_rs smi_rs;
+int smi_rs_create(int max_rows, int max_in, int max_out, smi_rs** out);
+int smi_rs_destroy(smi_rs* h);
+/* taps_host [n_taps] float64, n_taps = 2H + 1 odd.  Synchronous (one small copy); a ratio is registered once.  A filter whose taps
+ * plus the input window of one 1024-sample output tile exceed 16384 floats (the kernel stages both in 64 KiB of LDS) is refused. */
+int smi_rs_register(smi_rs* h, int up, int down, const double* taps_host, int n_taps);
+/* ceil(n * up / down); -1 for a negative n or a non-positive up / down.  Pure host arithmetic. */
+long long smi_rs_out_len(long long n, int up, int down);
+/* in_dev [B][in_stride] f32 (row b valid for n_in_host[b]); out_dev [B][out_stride] f32: row b receives its n_out samples and
+ * zeros from there to out_stride. */
+int smi_rs_resample_rows(smi_rs* h, const float* in_dev, long long in_stride, const int32_t* n_in_host, const int32_t* up_host,
+                         const int32_t* down_host, int B, float* out_dev, long long out_stride, void* stream);
+/* Prompt preparation: raw mono rows at their own rates -> wav_dev [B][wav_stride] (the model-rate prompt, zeros past n_out) and
+ * ref_dev [B][ref_stride] (the reference clip, zeros past ref_len_host[b]), in two launches:
+ *   1. resample, as smi_rs_resample_rows;
+ *   2. normalize = 1: audio_volume_normalize with its quirks.  temp = sort(|y|) of the resampled row; peak = temp[-1]; peak < 0.1:
+ *      gain 0.1 / max(peak, 1e-3); of temp only the values > 0.01 count, n of them; n <= 10: done; else volume =
+ *      mean(temp[int(0.9 n) .. int(0.99 n))) -- peak and temp are taken BEFORE the < 0.1 rescale --, the gain is multiplied by
+ *      clip(0.2 / volume, 0.1, 10), and divided by the scaled peak if that exceeds 1.  The ranks are selected exactly (a radix
+ *      select on the bit patterns of |y|, ties by counts) and the range is summed in 64-bit fixed point (every counted value is
+ *      a multiple of 2^-30; exact while |y| < 2^13), so the statistic has no summation order: the gain, formed in float64, is
+ *      reproducible bit for bit and independent of the batch.  Each sample becomes fl32(float64(y) * gain) -- one rounding,
+ *      where the host path rounds per stage.  gain_out_dev [B] float64 (may be null) receives the gain (1 with normalize = 0);
+ *   3. ref[i] = wav[i mod n_out] for i < ref_len_host[b], of the normalized samples.
+ * n_out_host [B] (may be null) receives the rows' lengths.  in_dev must not overlap wav_dev. */
+int smi_rs_prompt_rows(smi_rs* h, const float* in_dev, long long in_stride, const int32_t* n_in_host, const int32_t* up_host,
+                       const int32_t* down_host, int B, int normalize, float* wav_dev, long long wav_stride,
+                       const int32_t* ref_len_host, float* ref_dev, long long ref_stride, double* gain_out_dev,
+                       int32_t* n_out_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,13 @@ SYMBOLS = {
     "smi_enc_debug_stage": (_I, [_VP, C.c_char_p, _VP, _SZ, _P(C.c_int32), _VP]),
     "smi_enc_num_launches": (_I, [_VP]),
     "smi_enc_time_launch": (_I, [_VP, _I, _I, _P(C.c_float), _P(C.c_double), C.c_char_p, _I, _VP]),
+    "smi_rs_create": (_I, [_I, _I, _I, _P(_VP)]),
+    "smi_rs_destroy": (_I, [_VP]),
+    "smi_rs_register": (_I, [_VP, _I, _I, _P(C.c_double), _I]),
+    "smi_rs_out_len": (C.c_longlong, [C.c_longlong, _I, _I]),
+    "smi_rs_resample_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, C.c_longlong, _VP]),
+    "smi_rs_prompt_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _I, _VP, C.c_longlong,
+                                _P(C.c_int32), _VP, C.c_longlong, _VP, _P(C.c_int32), _VP]),
 }
 
 # include/sparkmi_debug.h: exported by libsparkmi_diag.so only

@@ -1,0 +1,158 @@
+"""Audio preparation on the device (``smi_rs_*``, ``csrc/smi_audio.hip``): a rational resampler with
+``scipy.signal.resample_poly``'s arithmetic and the voice prompt's volume normalisation and reference clip, written into the
+buffers ``smi_enc_forward_rows`` reads.  The same resampler brings the vocoder's 16 kHz rows to a caller's output rate.
+
+The device path follows ``resample_poly`` (the host path's resampler, ``encoder.load_audio``), not the reference's soxr VHQ, and
+it works in fp32 where the host works in float64: its 16 kHz samples differ from the host path's by fp32 rounding, so prompt ids
+may differ between the two at near-ties.  Nothing here imports scipy: the taps are computed with numpy alone.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from .encoder import grow_reservation
+
+MAX_ROWS = 64            # rows of one smi_rs_* call (their descriptors travel as kernel arguments)
+KAISER_BETA = 5.0        # resample_poly's default window
+
+
+def ratio(sr_in: int, sr_out: int) -> Tuple[int, int]:
+    """(up, down) in lowest terms that takes ``sr_in`` to ``sr_out``"""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in < 1 or sr_out < 1:
+        raise ValueError(f"sample rates must be positive, not {sr_in} -> {sr_out}")
+    g = math.gcd(sr_in, sr_out)
+    return sr_out // g, sr_in // g
+
+
+def out_len(n: int, up: int, down: int) -> int:
+    """ceil(n * up / down): the length ``resample_poly`` returns (``smi_rs_out_len``)"""
+    return -((-int(n) * int(up)) // int(down))
+
+
+def resample_taps(up: int, down: int) -> np.ndarray:
+    """float64 [2H + 1], H = 10 max(up, down): ``firwin(2H + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up`` -- the
+    low-pass ``resample_poly(x, up, down)`` designs for itself -- with numpy alone: the windowed sinc
+    cutoff sinc(cutoff m) kaiser(2H + 1, 5), normalised to unit gain at DC, times ``up``."""
+    up, down = int(up), int(down)
+    if up < 1 or down < 1 or math.gcd(up, down) != 1:
+        raise ValueError(f"up/down = {up}/{down} must be positive and in lowest terms")
+    m_rate = max(up, down)
+    half = 10 * m_rate
+    cutoff = 1.0 / m_rate
+    m = np.arange(2 * half + 1, dtype=np.float64) - half
+    h = cutoff * np.sinc(cutoff * m) * np.kaiser(2 * half + 1, KAISER_BETA)
+    h /= np.sum(h)
+    return h * up
+
+
+class DeviceAudio:
+    """Owns one ``smi_rs`` handle: registers a ratio's taps on first use and keeps (rows, input samples, output samples) as a
+    reservation that only grows (``encoder.grow_reservation``).  A grown reservation is a new handle, so its ratios are
+    registered again as they come.  ``lib``: the loaded library (tests pass a stand-in to watch the bookkeeping)."""
+
+    def __init__(self, device="cuda:0", diag: bool = False, lib=None):
+        self._lib = lib if lib is not None else _lib.pick(diag)
+        self._fake = lib is not None
+        self.device = device
+        if not self._fake:
+            import torch
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise _lib.SparkMIError("DeviceAudio runs on an MI355X only (device must be cuda:N); there is no CPU path")
+        self._h = C.c_void_p()
+        self.reserved: Optional[Tuple[int, int, int]] = None
+        self.registered: set = set()
+
+    # ---- handle, reservation, filters
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.smi_rs_destroy(self._h)
+            self._h = C.c_void_p()
+            self.registered = set()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reserve(self, rows: int, n_in: int, n_out: int) -> None:
+        if rows > MAX_ROWS:
+            raise ValueError(f"{rows} rows in one call, the device audio path takes at most {MAX_ROWS}")
+        new = grow_reservation(self.reserved, (int(rows), int(n_in), int(n_out)))
+        if new is None:
+            return
+        self.close()
+        h = C.c_void_p()
+        self._lib.check(self._lib.smi_rs_create(*new, C.byref(h)), "smi_rs_create")
+        self._h, self.reserved = h, new
+
+    def register(self, up: int, down: int) -> None:
+        key = (int(up), int(down))
+        if key == (1, 1) or key in self.registered:
+            return
+        taps = np.ascontiguousarray(resample_taps(*key), dtype=np.float64)
+        self._lib.check(self._lib.smi_rs_register(self._h, key[0], key[1], taps.ctypes.data_as(C.POINTER(C.c_double)), taps.size),
+                        "smi_rs_register")
+        self.registered.add(key)
+
+    def _prepare(self, n_in: Sequence[int], ups: Sequence[int], downs: Sequence[int]) -> List[int]:
+        if not (len(n_in) == len(ups) == len(downs)) or not len(n_in):
+            raise ValueError("one (up, down) per row, at least one row")
+        n_out = [out_len(n, u, d) for n, u, d in zip(n_in, ups, downs)]
+        self.reserve(len(n_in), max(n_in), max(n_out))
+        for u, d in zip(ups, downs):
+            self.register(u, d)
+        return n_out
+
+    def _stream(self) -> C.c_void_p:
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    # ---- device calls
+    def resample_rows(self, x, n_in: Sequence[int], ups: Sequence[int], downs: Sequence[int], out_stride: Optional[int] = None):
+        """``x``: [B][in_stride] float32 on the device, row b valid for ``n_in[b]``.  Returns (y [B][out_stride] float32 on the
+        device -- row b holds its ``n_out[b]`` samples, then zeros --, n_out)."""
+        import torch
+        B = len(n_in)
+        if x.dim() != 2 or x.shape[0] != B or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError("resample_rows takes a contiguous [B][in_stride] float32 tensor on the device")
+        n_out = self._prepare(n_in, ups, downs)
+        stride = max(n_out) if out_stride is None else int(out_stride)
+        y = torch.empty((B, stride), dtype=torch.float32, device=self.device)
+        i32 = lambda v: (C.c_int32 * B)(*[int(a) for a in v])   # noqa: E731
+        self._lib.check(self._lib.smi_rs_resample_rows(self._h, C.c_void_p(x.data_ptr()), x.shape[1], i32(n_in), i32(ups), i32(downs), B,
+                                                       C.c_void_p(y.data_ptr()), stride, self._stream()), "smi_rs_resample_rows")
+        return y, n_out
+
+    def prompt_rows(self, raw, n_in: Sequence[int], ups: Sequence[int], downs: Sequence[int], ref_len: Sequence[int],
+                    normalize: bool = True, wav_stride: Optional[int] = None, ref_stride: Optional[int] = None):
+        """``raw``: [B][in_stride] float32 mono rows on the device at their own rates.  Returns (wav [B][wav_stride], ref
+        [B][ref_stride], gain [B] float64, n_out): what ``load_audio(..., volume_normalize)`` + ``get_ref_clip`` give row by
+        row, zero-padded like ``pack_rows``, all on the device."""
+        import torch
+        B = len(n_in)
+        if raw.dim() != 2 or raw.shape[0] != B or raw.dtype != torch.float32 or not raw.is_contiguous() or not raw.is_cuda:
+            raise ValueError("prompt_rows takes a contiguous [B][in_stride] float32 tensor on the device")
+        if len(ref_len) != B:
+            raise ValueError("one reference length per row")
+        n_out = self._prepare(n_in, ups, downs)
+        ws = max(n_out) if wav_stride is None else int(wav_stride)
+        rs = max(int(r) for r in ref_len) if ref_stride is None else int(ref_stride)
+        wav = torch.empty((B, ws), dtype=torch.float32, device=self.device)
+        ref = torch.empty((B, rs), dtype=torch.float32, device=self.device)
+        gain = torch.empty((B,), dtype=torch.float64, device=self.device)
+        i32 = lambda v: (C.c_int32 * B)(*[int(a) for a in v])   # noqa: E731
+        got = (C.c_int32 * B)()
+        self._lib.check(self._lib.smi_rs_prompt_rows(self._h, C.c_void_p(raw.data_ptr()), raw.shape[1], i32(n_in), i32(ups), i32(downs), B,
+                                                     int(bool(normalize)), C.c_void_p(wav.data_ptr()), ws, i32(ref_len),
+                                                     C.c_void_p(ref.data_ptr()), rs, C.c_void_p(gain.data_ptr()), got, self._stream()),
+                        "smi_rs_prompt_rows")
+        assert list(got) == n_out, (list(got), n_out)
+        return wav, ref, gain, n_out

@@ -476,8 +476,23 @@ class BiCodecTokenizer:
         wavs, refs = zip(*[self.process_audio(p) for p in audio_paths])
         return self._encoder().tokenize_many(list(wavs), [r.numpy() for r in refs])
 
-    def tokenize_rows(self, audio_paths: Sequence[str]):
-        """``tokenize_many``'s result from ONE ragged call on one handle (``BiCodecEncoder.tokenize_rows``): the same ids, bit for bit."""
+    def tokenize_rows(self, audio_paths: Sequence[str], prompt_audio: str = "host"):
+        """``tokenize_many``'s result from ONE ragged call on one handle (``BiCodecEncoder.tokenize_rows``): the same ids, bit for bit.
+        ``prompt_audio="device"``: the files are only read here (channel 0, one upload); resampling, volume normalisation and the
+        reference clip run on the device (``BiCodecEncoder.tokenize_rows_device``).  That path follows ``resample_poly`` in fp32
+        -- like the host path it is not the reference's soxr VHQ --, so its ids may differ from the host path's at near-ties."""
+        if prompt_audio not in ("host", "device"):
+            raise ValueError(f"prompt_audio must be 'host' or 'device', not {prompt_audio!r}")
+        if prompt_audio == "device":
+            from .encoder import read_audio
+            raws, rates = [], []
+            for p in audio_paths:
+                a, sr = read_audio(p)
+                raws.append(np.asarray(a[:, 0] if a.ndim > 1 else a, dtype=np.float32))
+                rates.append(int(sr))
+            c = self.config
+            ref_len = int(c.sample_rate * c.ref_segment_duration) // c.latent_hop_length * c.latent_hop_length
+            return self._encoder().tokenize_rows_device(raws, rates, ref_len, volume_normalize=bool(c.volume_normalize))
         wavs, refs = zip(*[self.process_audio(p) for p in audio_paths])
         return self._encoder().tokenize_rows(list(wavs), [r.numpy() for r in refs])
 

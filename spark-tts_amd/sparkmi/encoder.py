@@ -6,6 +6,7 @@ Host side of the row (cheap, numpy): reading the file, channel selection, volume
 the reference clip (``sparktts/utils/audio.py:34-110``, ``audio_tokenizer.py:57-83``).  Resampling
 uses ``scipy.signal.resample_poly`` where the reference uses soxr VHQ (absent offline): prompts that
 are already at the model's 16 kHz -- the shipped examples -- take exactly the reference's path.
+``tokenize_rows_device`` does the same preparation on the device for a whole batch (``sparkmi/audio.py``, opt-in).
 """
 from __future__ import annotations
 
@@ -265,6 +266,9 @@ class BiCodecEncoder:
         if getattr(self, "_h", None) is not None and self._h:
             self._lib.smi_enc_destroy(self._h)
             self._h = C.c_void_p()
+        if getattr(self, "_audio", None) is not None:
+            self._audio.close()
+            self._audio = None
 
     def __del__(self):
         try:
@@ -334,13 +338,16 @@ class BiCodecEncoder:
 
     def _rows_forward(self, wav: np.ndarray, n_samples: Sequence[int], ref: np.ndarray, n_ref: Sequence[int], sem_stride: int):
         """The device call on packed [B][stride] host arrays: (sem [B][sem_stride] int64, glob [B][Ntok] int32, frames)."""
+        return self._rows_forward_device(torch.from_numpy(wav).to(self.device), n_samples, torch.from_numpy(ref).to(self.device),
+                                         n_ref, sem_stride)
+
+    def _rows_forward_device(self, w: torch.Tensor, n_samples: Sequence[int], r: torch.Tensor, n_ref: Sequence[int], sem_stride: int):
+        """``_rows_forward`` on packed [B][stride] float32 tensors that are on the device already"""
         B = len(n_samples)
-        w = torch.from_numpy(wav).to(self.device)
-        r = torch.from_numpy(ref).to(self.device)
         sem = torch.empty((B, sem_stride), dtype=torch.int64, device=self.device)
         glob = torch.empty((B, self.tcfg.spk_token_num), dtype=torch.int32, device=self.device)
         ns, nr, nf = (C.c_int32 * B)(*n_samples), (C.c_int32 * B)(*n_ref), (C.c_int32 * B)()
-        self._lib.check(self._lib.smi_enc_forward_rows(self._h, C.c_void_p(w.data_ptr()), wav.shape[1], ns, C.c_void_p(r.data_ptr()), ref.shape[1],
+        self._lib.check(self._lib.smi_enc_forward_rows(self._h, C.c_void_p(w.data_ptr()), w.shape[1], ns, C.c_void_p(r.data_ptr()), r.shape[1],
                                                        nr, B, C.c_void_p(sem.data_ptr()), sem_stride, C.c_void_p(glob.data_ptr()), nf,
                                                        self._stream()), "smi_enc_forward_rows")
         return sem, glob, list(nf)
@@ -360,16 +367,65 @@ class BiCodecEncoder:
         for n in nr:
             if n > self.max_ref:
                 raise ValueError(f"reference clip of {n} samples exceeds max_ref_samples={self.max_ref}")
+        plan = self._rows_plan(ns, nr)
+        return self._rows_result(plan, *self._rows_forward(pack_rows(wavs, plan["order"], plan["wav_stride"]), plan["n_samples"],
+                                                           pack_rows(refs, plan["order"], plan["ref_stride"]), plan["n_ref"],
+                                                           plan["sem_stride"]))
+
+    def _rows_plan(self, ns: Sequence[int], nr: Sequence[int]) -> dict:
+        """``plan_rows`` of the call, with the rows workspace grown to hold it"""
         plan = plan_rows(self.wcfg, ns, nr)
         new = grow_reservation(getattr(self, "_rows_reserved", None), (len(ns), plan["wav_stride"], plan["ref_stride"]))
         if new is not None:
             self._rows_reserve(*new)
             self._rows_reserved = new
-        sem, glob, frames = self._rows_forward(pack_rows(wavs, plan["order"], plan["wav_stride"]), plan["n_samples"],
-                                               pack_rows(refs, plan["order"], plan["ref_stride"]), plan["n_ref"], plan["sem_stride"])
-        assert frames == plan["frames"], (frames, plan["frames"])
+        return plan
+
+    def _rows_result(self, plan: dict, sem: torch.Tensor, glob: torch.Tensor, frames: Sequence[int]):
+        assert list(frames) == plan["frames"], (frames, plan["frames"])
         ntok = self.tcfg.spk_token_num
         return [(glob[j].view(1, 1, ntok), sem[j: j + 1, : frames[j]]) for j in plan["inverse"]]
+
+    # ---- the same call with the prompts prepared on the device (sparkmi/audio.py, smi_rs_prompt_rows)
+    def device_audio(self):
+        if getattr(self, "_audio", None) is None:
+            from .audio import DeviceAudio
+            self._audio = DeviceAudio(self.device, diag=self._lib.is_diag)
+        return self._audio
+
+    @torch.no_grad()
+    def prepare_rows_device(self, raws: Sequence[np.ndarray], rates: Sequence[int], ref_len: int, volume_normalize: bool = True):
+        """Raw mono prompts at their own sample rates -> (plan, wav [B][wav_stride], ref [B][ref_stride], gain [B] float64) on the
+        device, rows in the plan's order: one upload of the packed raw rows and one ``smi_rs_prompt_rows``.  The lengths come from
+        ``audio.out_len`` on the host, so nothing is read back."""
+        from .audio import out_len, ratio
+        if len(raws) != len(rates) or not len(raws):
+            raise ValueError("tokenize_rows_device: one sample rate per prompt, at least one prompt")
+        raws = [np.asarray(a, dtype=np.float32).reshape(-1) for a in raws]
+        ud = [ratio(sr, self.tcfg.sample_rate) for sr in rates]
+        ns = [out_len(a.size, u, d) for a, (u, d) in zip(raws, ud)]
+        for n in ns:
+            if n > self.max_samples:
+                raise ValueError(f"prompt of {n} samples exceeds max_samples={self.max_samples}")
+        if ref_len > self.max_ref:
+            raise ValueError(f"reference clip of {ref_len} samples exceeds max_ref_samples={self.max_ref}")
+        plan = self._rows_plan(ns, [int(ref_len)] * len(ns))
+        order = plan["order"]
+        raw = torch.from_numpy(pack_rows(raws, order, max(a.size for a in raws))).to(self.device)
+        wav, ref, gain, n_out = self.device_audio().prompt_rows(
+            raw, [raws[i].size for i in order], [ud[i][0] for i in order], [ud[i][1] for i in order], plan["n_ref"],
+            normalize=volume_normalize, wav_stride=plan["wav_stride"], ref_stride=plan["ref_stride"])
+        assert n_out == plan["n_samples"], (n_out, plan["n_samples"])
+        return plan, wav, ref, gain
+
+    @torch.no_grad()
+    def tokenize_rows_device(self, raws: Sequence[np.ndarray], rates: Sequence[int], ref_len: int, volume_normalize: bool = True):
+        """``tokenize_rows`` of prompts that are resampled, volume-normalised and clipped on the device: raw mono samples and
+        their sample rates in, [(global, semantic)] in the caller's order out.  The ids are those of ``tokenize_arrays`` of the
+        device-prepared rows; those rows follow ``resample_poly`` in fp32, so they differ from the host path's by fp32 rounding
+        and the ids of the two paths may differ at near-ties."""
+        plan, wav, ref, _ = self.prepare_rows_device(raws, rates, ref_len, volume_normalize)
+        return self._rows_result(plan, *self._rows_forward_device(wav, plan["n_samples"], ref, plan["n_ref"], plan["sem_stride"]))
 
     # ---- the solo and the rows entry points share their bodies: `entry` is the C entry's name, `row` its leading row argument
     def _stage(self, entry: str, row: tuple, name: str, mib: int) -> torch.Tensor:

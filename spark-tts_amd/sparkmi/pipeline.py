@@ -248,8 +248,9 @@ class SparkTTS:
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                   min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False,
                   num_return_sequences: int = 1, allowed_token_ids: Optional[Sequence[int]] = None,
-                  speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0):
-        """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate``.  The penalties
+                  speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0, output_sample_rate: Optional[int] = None):
+        """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate`` (or at ``output_sample_rate``,
+        as in ``inference_batch``).  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
         penalty.  ``return_log_probs=True``: (waveform, info) with info = {``token_ids``: the generated ids,
@@ -275,12 +276,37 @@ class SparkTTS:
                                           **({SPEECH_ONLY_KEY: speech_tokens_only} if speech_tokens_only else {}),
                                           **({NGRAM_KEY: n_gram} if n_gram > 0 else {}))],
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
-                                    max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs)[0]
+                                    max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs,
+                                    output_sample_rate=output_sample_rate)[0]
+
+    def _output_ratio(self, output_sample_rate: Optional[int]) -> Optional[Tuple[int, int]]:
+        """(up, down) from the model's rate to ``output_sample_rate``; None when the vocoder's rows go out as they are"""
+        if output_sample_rate is None:
+            return None
+        if isinstance(output_sample_rate, bool) or int(output_sample_rate) != output_sample_rate or int(output_sample_rate) < 1:
+            raise ValueError(f"output_sample_rate must be a positive integer or None, not {output_sample_rate!r}")
+        if int(output_sample_rate) == int(self.sample_rate):
+            return None
+        from .audio import ratio
+        return ratio(self.sample_rate, int(output_sample_rate))
+
+    @staticmethod
+    def _no_stream_rate(output_sample_rate: Optional[int], who: str) -> None:
+        if output_sample_rate is not None:
+            raise ValueError(f"{who}: output_sample_rate is not supported for streamed chunks (the resampler keeps no filter "
+                             "state across chunk edges); resample the joined waveform, or use inference / inference_batch")
+
+    def _device_audio(self):
+        if getattr(self, "_audio", None) is None:
+            from .audio import DeviceAudio
+            self._audio = DeviceAudio(self.device)
+        return self._audio
 
     @torch.no_grad()
     def inference_batch(self, requests: Sequence[dict], temperature: float = 0.8, top_k: float = 50,
                         top_p: float = 0.95, *, do_sample: bool = True, max_new_tokens: int = 3000,
-                        seed: Optional[int] = None, return_log_probs: bool = False, prompt_encode: str = "streams") -> List:
+                        seed: Optional[int] = None, return_log_probs: bool = False, prompt_encode: str = "streams",
+                        prompt_audio: str = "host", output_sample_rate: Optional[int] = None) -> List:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
@@ -297,9 +323,21 @@ class SparkTTS:
         (as in ``inference``) bans repeated n-grams; such a batch runs through the admission path.
         ``prompt_encode``: how the batch's prompt files are encoded -- "streams" (default): side by side on parallel HIP streams
         (``tokenize_many``); "rows": as one ragged call on one handle (``tokenize_rows``).  The ids are equal bit for bit, so
-        the waveforms are the same."""
+        the waveforms are the same.
+        ``prompt_audio``: where the prompt files are resampled, volume-normalised and clipped -- "host" (default): numpy / scipy,
+        file by file, as ever; "device" (needs ``prompt_encode="rows"``): in one device call for all of them
+        (``BiCodecTokenizer.tokenize_rows``).  Both follow ``resample_poly``, not the reference's soxr VHQ; the device path works in
+        fp32, so its prompt ids may differ from the host path's at near-ties.
+        ``output_sample_rate``: None or the model's rate: the vocoder's rows as they are.  Another rate (24000, 44100, 48000,
+        8000, ...): every row is resampled on the device (``sparkmi/audio.py``, ``resample_poly``'s arithmetic in fp32) before
+        the copy to the host; row b then has ``audio.out_len`` of its own length."""
         if prompt_encode not in ("streams", "rows"):
             raise ValueError(f"prompt_encode must be 'streams' or 'rows', not {prompt_encode!r}")
+        if prompt_audio not in ("host", "device"):
+            raise ValueError(f"prompt_audio must be 'host' or 'device', not {prompt_audio!r}")
+        if prompt_audio == "device" and prompt_encode != "rows":
+            raise ValueError("prompt_audio='device' prepares the prompts for the rows encode: pass prompt_encode='rows'")
+        out_ratio = self._output_ratio(output_sample_rate)
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         n_takes = _take_counts(requests, self._max_batch)
@@ -307,9 +345,12 @@ class SparkTTS:
         # voice-clone requests that come with prompt FILES: all their prompt encodes run together (parallel HIP streams, or one ragged call)
         need = [i for i, r in enumerate(requests)
                 if r.get("gender") is None and r.get("prompt_tokens") is None and r.get("prompt_speech_path") is not None]
-        if len(need) > 1:
+        if len(need) > 1 or (need and prompt_audio == "device"):
             paths = [requests[i]["prompt_speech_path"] for i in need]
-            toks = self.audio_tokenizer.tokenize_rows(paths) if prompt_encode == "rows" else self.audio_tokenizer.tokenize_many(paths)
+            if prompt_audio == "device":
+                toks = self.audio_tokenizer.tokenize_rows(paths, prompt_audio="device")
+            else:
+                toks = self.audio_tokenizer.tokenize_rows(paths) if prompt_encode == "rows" else self.audio_tokenizer.tokenize_many(paths)
             requests = [dict(r) for r in requests]
             for i, t in zip(need, toks):
                 requests[i]["prompt_tokens"] = t
@@ -378,9 +419,13 @@ class SparkTTS:
         for b, s in enumerate(sems):
             sem_t[b, : len(s)] = torch.tensor(s)
         wav = self.audio_tokenizer.model.detokenize(sem_t, torch.stack(globs).unsqueeze(1), lengths=lens)
-        wav = wav.squeeze(1).cpu().numpy()
         hop = self.audio_tokenizer.model.hop
-        out = [wav[b, : lens[b] * hop].copy() for b in range(len(sems))]
+        n_wav = [n * hop for n in lens]
+        wav = wav.squeeze(1)
+        if out_ratio is not None:   # rows at the caller's rate, still on the device
+            wav, n_wav = self._device_audio().resample_rows(wav, n_wav, [out_ratio[0]] * len(lens), [out_ratio[1]] * len(lens))
+        wav = wav.cpu().numpy()
+        out = [wav[b, : n_wav[b]].copy() for b in range(len(sems))]
         out = [(w, infos[b]) if infos[b] is not None else w for b, w in enumerate(out)]
         if n_takes is None:
             return out
@@ -397,12 +442,15 @@ class SparkTTS:
                          prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                          audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
                          audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
-                         decode_stride: int = 10) -> Iterator[np.ndarray]:
+                         decode_stride: int = 10, output_sample_rate: Optional[int] = None) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
         (client_grpc.py:390-415).  Every chunk is the vocoder's output for that chunk's tokens alone.
-        ``decode_stride`` = decode steps enqueued between host checks for new tokens."""
+        ``decode_stride`` = decode steps enqueued between host checks for new tokens.  The chunks are at ``sample_rate``:
+        ``output_sample_rate`` is refused here (ValueError) -- a resampled chunk would need the filter's state across the
+        chunk edges, which the device resampler does not keep yet."""
+        self._no_stream_rate(output_sample_rate, "inference_stream")
         if gender is not None:
             prompt, glob = self.process_prompt_control(gender, pitch, speed, text), None
         else:
@@ -545,7 +593,7 @@ class SparkTTS:
                      audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
                      audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
                      max_open: Optional[int] = None, max_ahead: Optional[float] = None, resume_ahead: Optional[float] = None,
-                     clock=None, pacer: Optional[Pacer] = None):
+                     clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -572,7 +620,8 @@ class SparkTTS:
         sequence comes back with every bit of its state, whatever the schedule did to it, greedy and sampled with any seed
         alike.  ``pacer``: a ``Pacer`` of the caller's, built for this ``max_batch``, in place of the four keywords (ValueError if
         both are given); its ``parks`` / ``resumes`` then tell the caller what the schedule did.  Nothing of a call is kept on
-        ``self``."""
+        ``self``.  The chunks are at ``sample_rate``: ``output_sample_rate`` is refused (ValueError), as in ``inference_stream``."""
+        self._no_stream_rate(output_sample_rate, "serve_stream")
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
