@@ -901,12 +901,7 @@ __device__ __forceinline__ void down1_body(const GemmP& p) {
     p.ssout[(size_t)nt * 4 + part] = ssq;
   }
 }
-template <int TPC>
-__global__ __launch_bounds__(256) void k_down1(GemmP p) {
-  smi_kernarg_lines(p);
-  down1_body<TPC>(p);
-}
-// Hot entry (12 dwords): the weight and operand addresses, the epilogue's two early loads (res = the residual row's source,
+// The one entry, a hot one (12 dwords): the weight and operand addresses, the epilogue's two early loads (res = the residual row's source,
 // Yin or else Y) and the helper test
 template <int TPC>
 __global__ __launch_bounds__(256) void k_down1_hot(const uint4* W, const unsigned char* XS, const float* res, const float* gamma_next, int KT,
@@ -3835,14 +3830,11 @@ struct smi_llm {
   Work dec;            // the decode rows' workspace (kMaxRows rows)
   Work big; int big_rows;   // prefill workspace for up to big_rows rows at once (allocated at the first multi-chunk prefill)
   float4* pslab; size_t pslab_bytes;   // k_pgemm split-K partial sums (prompt rows passes of up to kPgSplitRows rows)
-  int pf_long;          // prompt rows (len - 1) from which a sequence's prompt runs through the prefill-GEMM family (default 65)
   int pg_split_rows;    // passes of up to this many rows take the few-row prefill GEMM shapes / split-K (kPgSplitRows; SPARKMI_PG_SPLIT_ROWS: A/B, same bits)
   int pg_forced;        // diagnostics: SPARKMI_PGEMM_MIN_* set -- kernels picked per launch by the pass's row count, as in round 3
   float *part_o, *h2;  // fused o_proj (one row): per-head partials [heads][H]; h + o_proj [H]
   float4* dpart;       // chain-split down_proj (k_downC): [16 chains][NTh][4 m-tiles][64] chain sums
-  int dc_min;          // rows from which down_proj runs chain-split (default 7; SPARKMI_DC_MIN in the diagnostics build)
   int fuse_o;          // config allows the fused o_proj (SPARKMI_NO_FUSE_O=1 turns it off)
-  int fuse1_last;      // diagnostics (SPARKMI_FUSE1_LAST=1): ONE live row also takes the last-arriver form instead of per-head partials summed by every gate_up block (A/B for DESIGN 3.9)
   int fuse2_rows;      // rows up to which 2+ live rows take the fused attention + o_proj with the last-arriver head sum (diagnostics: SPARKMI_FUSE2_ROWS; default 0 = off: measured slower)
   unsigned int* fuse_cnt;   // [kFuse2Max][kFuseQB] arrival counters of that kernel (zero between launches)
   RowDesc* rows;       // live decode rows [kMaxRows]
@@ -3903,18 +3895,14 @@ struct smi_llm {
   float* cand_v; int* cand_i; unsigned int* cand_n;   // sampler candidate lists
   unsigned long long* stamps; int stamps_on;
   int max_steps;
-  int tune[4];   // SPARKMI_TUNE block-shape selectors (diagnostics)
-  int graph_steps;      // decode steps captured per graph replay (SPARKMI_GRAPH_STEPS, default 8; 1: one)
   int pf_inline;        // gate_up's work blocks touch the next layer's QKV weights (SPARKMI_PF_INLINE=0: off)
   int pf_qkv_eighths;   // SPARKMI_PF_QKV: how much of gate_up QKV's helpers prefetch, in eighths (default 2)
   int prefetch_mask, prefetch_rows;  // same-XCD L2 prefetch by helper blocks: one bit per producer kernel, up to this many live rows (smi_llm_create)
-  int tune2;     // SPARKMI_TUNE2 bit mask (diagnostics)
+  int tune2;     // SPARKMI_TUNE2 bit mask (diagnostics; the kTune2* bits)
   int pgemm_min_rows;   // prompt rows from which the prefill GEMM replaces row-grouped decode GEMMs (SPARKMI_PGEMM_MIN_ROWS)
   int pg_min[4];        // ... per kernel (QKV, o_proj, gate_up, down; SPARKMI_PGEMM_MIN_QKV / _O / _GU / _D override the common value)
   int wd_parts;         // W_down tiles are stored row-part-major (smi_llm_cfg.wd_plain == 0; include/sparkmi.h)
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
-  int gu1_lo;           // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (SPARKMI_GU1_LO; default 4)
-  int gu1_rows;         // rows up to which gate_up runs its one-batch, three-tile shape (SPARKMI_GU1_ROWS; default 32)
   hipGraphExec_t graph; uint64_t graph_id;   // the one-step graph in use (owned by graph_cache) and its graph_key
   // every exec remembers the stream it last ran on: a caller may alternate streams, and an exec is destroyed only after THAT
   // stream has drained (graphs_flush)
@@ -4079,9 +4067,26 @@ void graphs_flush(smi_llm* L) {
   L->graph = nullptr;
 }
 
-// SPARKMI_TUNE2 bits (diagnostics): a one-row kernel keeps its struct-only entry instead of the hot one, for A/B runs
-// of one build -- 8388608 QKV, 16777216 fused attention, 33554432 gate_up, 67108864 down_proj
-constexpr int kColdQkv = 8388608, kColdAttn = 16777216, kColdGateUp = 33554432, kColdDown = 67108864;
+// SPARKMI_TUNE2 bits (diagnostics), each the older form of a kernel kept for the parity tests: 8192 k_lm<2> in place of
+// k_lm32, 16384 the register-staged k_pgemm in place of the ring forms, 1048576 / 2097152 k_gemm<.., H = 4> in place of k_down1 / k_downS
+constexpr int kTune2Lm2 = 8192, kTune2PgemmRegs = 16384, kTune2GemmDown1 = 1048576, kTune2GemmDownS = 2097152;
+// Fixed choices of the launch path
+constexpr int kPgSplitRows = 512;        // passes of up to this many rows run o_proj / down_proj in k_pgemm's split-K form
+// A sequence's prompt rows take the kernel family ITS OWN length selects (never the call's total): up to kMaxRows rows the
+// decode kernels in chunks, from kPfLong rows the prefill-GEMM family (k_pgemm + k_attn_pf2), in between (empty: kPfLong =
+// kMaxRows + 1) the row-grouped decode GEMMs -- so its K/V rows, and with a bf16 cache its tokens, do not depend on what else is in the call.
+constexpr int kPfLong = kMaxRows + 1;    // prompt rows (len - 1) from which a sequence's prompt runs through the prefill-GEMM family
+// rows from which down_proj runs chain-split (k_downC): graph step at 0.5B, same box (profiles/r04_batch_ab.txt): 4 rows 641 (k_downS) vs
+// 692 us (chains), 8 rows 728 vs 713, 16 rows 790 (k_gemm<.., H = 4>) vs 744, 32 rows 892 vs 859
+// (5 / 6 rows: 731 / 728 us with the chains, the same as k_downS within noise -- the chains take over from 7)
+constexpr int kDcMin = 7;
+constexpr int kGu1Lo = 4;                // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (launch_gemm)
+constexpr int kGu1Rows = 32;             // rows up to which gate_up runs its one-batch, three-tile shape (launch_gemm)
+// Decode steps captured per graph replay: a step needs nothing from the host, so K of them are captured back to back into one
+// graph.  One replay boundary costs ~5 us that a kernel boundary inside a graph does not: graph step at one row 548.6 -> 544.5 us
+// (K = 4 .. 25 alike; profiles/r03_graph_steps.txt).
+constexpr int kGraphSteps = 8;
+constexpr int kPgSegO = 2, kPgSegD = 8;  // K segments of the prefill o_proj / down_proj sums (fixed: part of the association)
 
 template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int H = 1, int OCC = 1>
 int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
@@ -4089,20 +4094,16 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
   p.work_blocks = work;
   p.stamps = L->stamps_on ? L->stamps : nullptr;
   if constexpr (MT == 1 && NTB == 1 && NW == 16 && H == 4 && PRO == PRO_PLAIN && EPI == EPI_RESID) {
-    // one row: four chains per wave, full load instructions (k_down1; same bits).  SPARKMI_TUNE2 bit 1048576 keeps k_gemm (A/B)
-    if (p.M == 1 && !p.stamps && p.KT <= 160 && !(L->tune2 & 1048576)) {
-      const int helpers = (L->prefetch_mask & 4) && p.pf.base && work < 232 ? ((L->tune2 & 4194304) ? 224 : (256 - work) / 8 * 8) : 0;   // bit 4194304: as many helper blocks as work blocks (they share the CUs)
-      if (L->tune2 & kColdDown) {   // SPARKMI_TUNE2 bit kColdDown: the struct-only entry (A/B)
-        if (p.KT <= 32) hipLaunchKernelGGL(k_down1<2>, dim3(work + helpers), dim3(256), 0, st, p);
-        else if (p.KT <= 96) hipLaunchKernelGGL(k_down1<6>, dim3(work + helpers), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_down1<10>, dim3(work + helpers), dim3(256), 0, st, p);
-      } else if (p.KT <= 32) launch_down1_hot<2>(p, work + helpers, st);
+    // one row: four chains per wave, full load instructions (k_down1_hot; same bits).  SPARKMI_TUNE2 bit kTune2GemmDown1 keeps k_gemm (A/B)
+    if (p.M == 1 && !p.stamps && p.KT <= 160 && !(L->tune2 & kTune2GemmDown1)) {
+      const int helpers = (L->prefetch_mask & 4) && p.pf.base && work < 232 ? (256 - work) / 8 * 8 : 0;
+      if (p.KT <= 32) launch_down1_hot<2>(p, work + helpers, st);
       else if (p.KT <= 96) launch_down1_hot<6>(p, work + helpers, st);
       else launch_down1_hot<10>(p, work + helpers, st);
       SMI_LAUNCH_CHECK();
       return SMI_OK;
     }
-    if (p.M >= 2 && p.M <= 8 && !p.stamps && p.KT <= 160 && !(L->tune2 & 2097152)) {   // SPARKMI_TUNE2 bit 2097152 keeps k_gemm (A/B)
+    if (p.M >= 2 && p.M <= 8 && !p.stamps && p.KT <= 160 && !(L->tune2 & kTune2GemmDownS)) {   // SPARKMI_TUNE2 bit kTune2GemmDownS keeps k_gemm (A/B)
       const dim3 g(work), b(256);
       if (p.M <= 4) {
         if (p.KT <= 32) hipLaunchKernelGGL((k_downS<2, 1>), g, b, 0, st, p);
@@ -4125,8 +4126,8 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
     const int tw = (p.KT + NW - 1) / NW;               // k tiles per wave
     const size_t per_wave = (size_t)tw * 12 * p.M * 16;
     // (blocks of 14+ waves are alone on their CU anyway: down_proj's ten k tiles per wave then fit up to 3 rows -- 2 rows: down_proj
-    // 8.7 -> 7.3 us, graph step 718 -> 690 us; at 4 rows (123 KB) a tie, so the cap stays below it.  SPARKMI_TUNE2 bit 524288: 40 KB for all)
-    if (per_wave * NW <= (size_t)((NW >= 14 && !(L->tune2 & 524288)) ? 96 : 40) * 1024) {
+    // 8.7 -> 7.3 us, graph step 718 -> 690 us; at 4 rows (123 KB) a tie, so the cap stays below it)
+    if (per_wave * NW <= (size_t)(NW >= 14 ? 96 : 40) * 1024) {
       p.ldsb = (int)per_wave;
       int sh = 4;                                       // 16 lanes fetch 12 pieces (M = 1)
       while ((1 << sh) < 12 * p.M) ++sh;
@@ -4144,35 +4145,25 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
   if (kLean && p.ldsb > 0 && !p.stamps && p.M == 1 && p.lt_shift == 4) {
     if constexpr (PRO == PRO_NORM && EPI == EPI_SWIGLU && H == 1 && MT == 1) {
       if (p.part_o) {   // one row behind the fused o_proj: the operand is built in the kernel from the per-head partials
-#ifndef SMI_NOH16   // (A/B build: make variant NAME=noh16 VARFLAGS=-DSMI_NOH16 keeps the 16-slot form)
-        // the adopted block shape at the two fused head counts starts through the hot entry (SPARKMI_TUNE2 bit kColdGateUp: the
-        // struct-only entry, A/B); tune sweeps and the generic head-count form (no product shape reaches it) keep the struct entry
-        constexpr bool kHotGU = NW == 8 && U == 2 && WB == 2 && OCC == 6 && NTB == 1;
-        const bool hot = kHotGU && !(L->tune2 & kColdGateUp);
-        if (p.n_oheads == 14) {
-          if constexpr (kHotGU) if (hot) launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 14>(p, dim3(work + helpers, groups), lds + 1024, st);
-          if (!hot) hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2, 14>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
-        } else if (p.n_oheads == 4) {
-          if constexpr (kHotGU) if (hot) launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 4>(p, dim3(work + helpers, groups), lds + 1024, st);
-          if (!hot) hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2, 4>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
-        } else
-#endif
+        // the adopted block shape at the two fused head counts starts through the hot entry; the generic head-count form (no
+        // product shape reaches it) keeps the struct entry
+        if constexpr (NW == 8 && U == 2 && WB == 2 && OCC == 6 && NTB == 1) {
+          if (p.n_oheads == 14 || p.n_oheads == 4) {
+            if (p.n_oheads == 14) launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 14>(p, dim3(work + helpers, groups), lds + 1024, st);
+            else launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 4>(p, dim3(work + helpers, groups), lds + 1024, st);
+            SMI_LAUNCH_CHECK();
+            return SMI_OK;
+          }
+        }
         hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
         SMI_LAUNCH_CHECK();
         return SMI_OK;
       }
     }
-    if constexpr (PRO == PRO_NORM && EPI == EPI_QKV && kLean && NW == 16 && U == 2 && WB == 1) {
-      // one-row QKV in its adopted block shape: the hot entry (SPARKMI_TUNE2 bit kColdQkv: the struct-only entry, A/B); the tune
-      // sweeps' shapes keep the struct entry
-      if (!(L->tune2 & kColdQkv)) {
-        if (L->cfg.kv_dtype) launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>(p, dim3(work + helpers, groups), lds, st);
-        else launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>(p, dim3(work + helpers, groups), lds, st);
-        SMI_LAUNCH_CHECK();
-        return SMI_OK;
-      }
-    }
-    if (L->cfg.kv_dtype)
+    if constexpr (PRO == PRO_NORM && EPI == EPI_QKV && kLean && NW == 16 && U == 2 && WB == 1) {   // one-row QKV in its adopted block shape: the hot entry
+      if (L->cfg.kv_dtype) launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>(p, dim3(work + helpers, groups), lds, st);
+      else launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>(p, dim3(work + helpers, groups), lds, st);
+    } else if (L->cfg.kv_dtype)
       hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC, 2 * kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
     else
       hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC, 2 * kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
@@ -4198,30 +4189,29 @@ int launch_gemm(const smi_llm* L, const GemmP& p, hipStream_t st) {
   // a tile's k -> wave map does not change.  (Measured at M = 32: gate_up 19.4 -> 13.7 us with N2 = 2, 14.4 with 4;
   // QKV / o_proj / down / lm_head lose with fewer blocks.)
   if (p.M > 16) {
-    if constexpr (N2 > 1) {
+    if constexpr (N2 > 1) {   // (gate_up)
       // 17..32 rows: three n tiles per block and ALL of a wave's k tiles in one batch -- every load of the block leaves at
       // entry (one memory round trip instead of two dependent ones; 233 VGPRs, one 8-wave block per CU, 203 blocks):
       // gate_up 12.8 -> 10.5 us, batch-32 step 1047 -> 998 us.  Beyond 32 rows (two block rows = 406 blocks, two rounds
-      // at one block per CU) and with SPARKMI_TUNE2 bit 2048 the two-tile, two-batch shape stays.
+      // at one block per CU) the two-tile, two-batch shape stays.
       // (five n tiles per block in two batches -- 244 blocks, one round: 13.3 us against 10.3, step 947 -> 1017: not a rounds problem)
-      if (p.M <= L->gu1_rows && !(L->tune2 & 2048)) return launch_gemm_kv<2, 3, NW, 4, 1, PRO, EPI>(L, p, st);
+      if (p.M <= kGu1Rows) return launch_gemm_kv<2, 3, NW, 4, 1, PRO, EPI>(L, p, st);
       return launch_gemm_kv<2, NTB * N2, NW, 2, 1, PRO, EPI>(L, p, st);   // two k tiles in flight: 13.9 -> 13.6 us at 32 rows, 18.5 -> 17.5 at 64
-    }
-    // few n tiles (N = 896 / 1152): 16-row blocks in two block rows put twice the CUs to work and halve the operand
-    // bytes per CU (measured at M = 32; SPARKMI_TUNE2 bit 0 keeps 32-row blocks)
-    // (WB batches of weight tiles requested at entry, as at 16 rows and fewer: down_proj's five batches then wait for L2
-    // operand round trips only, not for five dependent HBM round trips; SPARKMI_TUNE2 bit 4096 keeps WB = 1 for A/B)
-    if constexpr (N2 == 0) {
-      if (!(L->tune2 & 1)) return (L->tune2 & 4096) ? launch_gemm_kv<1, NTB, NW, U, 1, PRO, EPI, H>(L, p, st) : launch_gemm_kv<1, NTB, NW, U, WB, PRO, EPI, H>(L, p, st);
-    }
-    return launch_gemm_kv<2, NTB, NW, (NW >= 16 || NTB >= 4 ? 2 : (U > 4 ? 4 : U)), 1, PRO, EPI>(L, p, st);
+    } else if constexpr (N2 == 0) {
+      // few n tiles (N = 896 / 1152): 16-row blocks in two block rows put twice the CUs to work and halve the operand
+      // bytes per CU (measured at M = 32)
+      // (WB batches of weight tiles requested at entry, as at 16 rows and fewer: down_proj's five batches then wait for L2
+      // operand round trips only, not for five dependent HBM round trips)
+      return launch_gemm_kv<1, NTB, NW, U, WB, PRO, EPI, H>(L, p, st);
+    } else
+      return launch_gemm_kv<2, NTB, NW, (NW >= 16 || NTB >= 4 ? 2 : (U > 4 ? 4 : U)), 1, PRO, EPI>(L, p, st);
   }
   if constexpr (N2 > 1) {
-    // gate_up at gu1_lo..16 rows: three n tiles per block and all of a wave's k tiles in one batch, as at 17..32 rows -- every load
+    // gate_up at kGu1Lo..16 rows: three n tiles per block and all of a wave's k tiles in one batch, as at 17..32 rows -- every load
     // of the block leaves at entry (one memory round trip).  8 rows 8.0 -> 6.9 us (graph step 801 -> 773 us), 16 rows 9.5 -> 7.9
     // (855 -> 817), 5 rows 763 -> 751, 4 rows 749 -> 742, 2 rows a tie (below 4 rows the operands staged through wave-private LDS
-    // stay); same bits (the k tile -> wave map does not change).  SPARKMI_GU1_LO sets the first row count (A/B).
-    if (p.M >= L->gu1_lo && !(L->tune2 & 131072)) return launch_gemm_kv<1, 3, NW, 4, 1, PRO, EPI>(L, p, st);
+    // stay); same bits (the k tile -> wave map does not change).
+    if (p.M >= kGu1Lo) return launch_gemm_kv<1, 3, NW, 4, 1, PRO, EPI>(L, p, st);
   }
   return launch_gemm_kv<1, NTB, NW, U, WB, PRO, EPI, H, OCC>(L, p, st);
 }
@@ -4262,7 +4252,6 @@ int eng_create(smi_llm* L) {
   if (c.kv_dtype != 0) return skip("f32 KV cache");
   if (L->exact) return skip("exact-weights mode");
   if (L->paged) return skip("paged KV cache");
-  if (L->tune[0] || L->tune[1] || L->tune[2] || L->tune[3]) return skip("SPARKMI_TUNE set");
   int dev = 0, ncu = 0;
   SMI_HIP(hipGetDevice(&dev));
   SMI_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -4380,8 +4369,6 @@ int eng_check(smi_llm* L) {
 
 enum { KQKV = 0, KATTN, KO, KGU, KD, KLM, KFIN };
 enum { PF_GROUPED = 1, PF_PGEMM = 2 };   // kernel family of a pass over prompt rows (launch_layers_big)
-constexpr int kPgSplitRows = 512;        // passes of up to this many rows run o_proj / down_proj in k_pgemm's split-K form
-constexpr int kPgSegO = 2, kPgSegD = 8;  // K segments of the prefill o_proj / down_proj sums (fixed: part of the association)
 
 int ensure_apart(smi_llm* L, size_t floats) {
   if (floats <= L->apart_floats) return SMI_OK;
@@ -4501,7 +4488,7 @@ int segs_for(int ctx_bound) { return ctx_bound <= kAttnSeg ? 1 : (ctx_bound + kA
 
 // attention (+ the segment merge when the context bound of the current call exceeds one segment)
 template <int KVF32>
-int launch_attn(smi_llm* L, AttnP a, int helpers_ok, hipStream_t st) {
+int launch_attn(smi_llm* L, AttnP a, hipStream_t st) {
   a.nseg = L->attn_seg < 1 ? 1 : L->attn_seg;
   a.work_blocks = a.n_heads * a.M * a.nseg;
   const bool fuse = a.M == 1 && a.nseg == 1 && a.slot_is_row && a.part_o && !a.cnt;
@@ -4512,7 +4499,7 @@ int launch_attn(smi_llm* L, AttnP a, int helpers_ok, hipStream_t st) {
     if (rc) return rc;
     a.part = L->apart;
   }
-  const int helpers = (helpers_ok && (L->prefetch_mask & 2) && a.M <= L->prefetch_rows && a.work_blocks < 232) ? (256 - a.work_blocks) / 8 * 8 : 0;
+  const int helpers = ((L->prefetch_mask & 2) && a.M <= L->prefetch_rows && a.work_blocks < 232) ? (256 - a.work_blocks) / 8 * 8 : 0;
   const bool pg = a.km.ptab != nullptr;   // paged cache: the slot == row kernels look the token's page up (PG)
 #ifdef SMI_DIAG   // measured, not adopted: the product library does not carry these instantiations
   if (fuse2 && pg)
@@ -4523,7 +4510,7 @@ int launch_attn(smi_llm* L, AttnP a, int helpers_ok, hipStream_t st) {
 #endif
   if (fuse && pg)
     hipLaunchKernelGGL((k_attn<KVF32, 1, 1, 1>), dim3(a.work_blocks + helpers), dim3(2 * kAttnWaves * 64), 0, st, a);
-  else if (fuse && !(L->tune2 & kColdAttn) && a.n_heads < 65536 && a.group < 32768)   // SPARKMI_TUNE2 bit kColdAttn: the struct-only entry (A/B)
+  else if (fuse && a.n_heads < 65536 && a.group < 32768)   // the hot entry (beyond the bounds: the struct-only one)
     launch_attn_hot<KVF32>(a, a.work_blocks + helpers, st);
   else if (fuse)
     hipLaunchKernelGGL((k_attn<KVF32, 1, 1>), dim3(a.work_blocks + helpers), dim3(2 * kAttnWaves * 64), 0, st, a);
@@ -4549,12 +4536,12 @@ int launch_attn(smi_llm* L, AttnP a, int helpers_ok, hipStream_t st) {
 // (k_attn<.., FUSE>), gate_up builds its operand from those partials (PRO_FUSEDO) and down_proj adds its residual from h2;
 // the o_proj kernel is not launched.  The predicate is the one launch_attn picks the one-row kernel by.
 bool fuse_o_now(const smi_llm* L, const RowDesc* rows, int M) {
-  return L->fuse_o && !L->fuse1_last && M == 1 && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
+  return L->fuse_o && M == 1 && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
 }
 // 2 .. fuse2_rows live rows, each in its own slot, one context segment: the attention kernel also computes the o_proj and the last
 // block of a (row, quarter) to arrive finishes the rows (k_attn<.., FUSE = 2>); the o_proj kernel is not launched.
 bool fuse2_now(const smi_llm* L, const RowDesc* rows, int M) {
-  return L->fuse_o && M >= (L->fuse1_last ? 1 : 2) && M <= L->fuse2_rows && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
+  return L->fuse_o && M >= 2 && M <= L->fuse2_rows && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
 }
 
 // o_proj: NW = number of heads, so that wave w sums head w's two (head-interleaved) k tiles -- the per-head partial the
@@ -4663,11 +4650,11 @@ int launch_lm_persistent(const smi_llm* L, const GemmP& p, int M, int ngroups, h
     return SMI_OK;
   }
   // 32 rows per pass: one 4-wave block per CU, the second m-tile's operands in LDS (k_lm32);
-  // SPARKMI_TUNE2 bit 8192: the two-group kernel (k_lm<2>) for A/B
+  // SPARKMI_TUNE2 bit kTune2Lm2: the two-group kernel (k_lm<2>) for A/B
   const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
   const int blocks = lm_blocks_for(L, M);
   for (int m0 = 0; m0 < M; m0 += 32) {
-    if (!(L->tune2 & 8192) && lds32 <= 150 * 1024) {
+    if (!(L->tune2 & kTune2Lm2) && lds32 <= 150 * 1024) {
       if (L->KTh <= 28) {
         SMI_LM_NOTE(L, RT ? "k_lm32<7,RT>" : "k_lm32<7>", blocks, 1, 256);
         hipLaunchKernelGGL((k_lm32<7, RT>), dim3(blocks), dim3(256), lds32, st, p, ngroups, m0);
@@ -4706,11 +4693,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       // helpers: the first pf_qkv_eighths / 8 of this layer's gate_up slices (consumer block b reads weight tile row b).  Measured
       // at one row, graph step, one box (profiles/r03_prefetch.txt): 8/8 600 us, 6/8 569, 4/8 564, 2/8 559 (default), none 566-571
       p.pf = PfDesc{sec(L, SMI_LLM_WGU, layer), L->KTh * 1024, L->NTgu, 0, ((L->NTgu + 7) / 8 * L->pf_qkv_eighths + 7) / 8};
-      switch (L->tune[0]) {   // SPARKMI_TUNE=q,o,g,d: block-shape sweeps (diagnostics; NW changes the summation order)
-        case 1: return launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_QKV>(L, p, st);
-        case 3: return launch_gemm<1, 4, 8, 1, PRO_NORM, EPI_QKV>(L, p, st);
-        default: return launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 0>(L, p, st);   // measured best (profiles/README.md)
-      }
+      return launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 0>(L, p, st);   // measured best (profiles/README.md)
     case KATTN: {
       AttnP a = attn_operands(L, layer, L->dec, rows, M);
       a.slot_is_row = rows == L->rows && L->identity_slots;   // the live decode rows are (slot b, ...) in order (contiguous cache: slots contiguous; paged: through the page table)
@@ -4721,60 +4704,39 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         a.Wo = (const uint4*)sec(L, SMI_LLM_WO, layer); a.NTo = L->NTh; a.part_o = L->part_o; a.cnt = L->fuse_cnt;
         a.h = L->dec.h; a.gamma_next = (const float*)sec(L, SMI_LLM_LN2, layer); a.xs_next = L->dec.xs_h; a.ssout = L->dec.ss;
       }
-      return c.kv_dtype ? launch_attn<1>(L, a, 1, st) : launch_attn<0>(L, a, 1, st);
+      return c.kv_dtype ? launch_attn<1>(L, a, st) : launch_attn<0>(L, a, st);
     }
     case KO:
       if (fused) return SMI_OK;   // done by the attention kernel (per-head partials) and gate_up's prologue
       if (fuse2_now(L, rows, M)) return SMI_OK;   // done by the attention kernel (per-head partials + last-arriver head sum and epilogue)
       // no helpers here: warming down_proj's 8.7 MB from o_proj (or from attention / gate_up) stretches the
       // producer by more than the consumer gains (measured, profiles/README.md), so down_proj stays cold
-      switch (L->tune[1]) {
-        case 2: return launch_gemm<1, 16, 2, 1, PRO_PLAIN, EPI_RESID>(L, p, st);
-        case 3: return launch_gemm<1, 4, 8, 1, PRO_PLAIN, EPI_RESID>(L, p, st);
-        case 4: return launch_gemm<1, 8, 4, 1, PRO_PLAIN, EPI_RESID, 2>(L, p, st);
-        case 5: return launch_gemm<1, 8, 4, 1, PRO_PLAIN, EPI_RESID>(L, p, st);
-        case 6: return launch_gemm<1, 8, 4, 1, PRO_PLAIN, EPI_RESID, 4>(L, p, st);
-        default:   // four row parts up to 8 rows: 629.8 -> 626.0 us per step once the prologues were down to one round trip
-          return launch_oproj(L, p, M, st);
-      }
+      // four row parts up to 8 rows: 629.8 -> 626.0 us per step once the prologues were down to one round trip
+      return launch_oproj(L, p, M, st);
     case KGU:
       if (fused) {
         p.part_o = L->part_o; p.n_oheads = c.num_heads; p.hres = L->dec.h; p.h2out = L->h2;
-        if (const char* e = smi_env("SPARKMI_FAKE_OHEADS")) p.n_oheads = atoi(e);   // TIMING ONLY (diagnostics build): gate_up reads that many partials -- wrong sums (profiles/r04_gate_up_two_tiles_and_fewer_partials.txt)
         if (L->pf_inline && layer + 1 < c.num_layers && L->NTqkv % 8 == 0) {   // SPARKMI_PF_INLINE=0: off (A/B)
           p.pf2_base = sec(L, SMI_LLM_WQKV, layer + 1); p.pf2_slice = L->KTh * 1024; p.pf2_nslices = L->NTqkv;
         }
         p.gam = (const float*)sec(L, SMI_LLM_LN2, layer);
       }
-      switch (L->tune[2]) {
-        case 2: return launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_SWIGLU>(L, p, st);
-        case 5: return launch_gemm<2, 4, 8, 1, PRO_NORM, EPI_SWIGLU>(L, p, st);
-        case 6: return launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 2, 6>(L, p, st);   // spills at 80 VGPRs: 2.4x slower
-        case 7: return launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 2>(L, p, st);      // 114 VGPRs: 2 blocks per CU, 96 of 608 wait
-        case 8: return launch_gemm<2, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 2, 4>(L, p, st);   // two tiles per block: half the blocks re-read the fused o_proj partials
-        default:   // 69 VGPRs (>= 6 waves per SIMD): all 608 blocks are resident at once, no second round (step 745 -> 705 us)
-          return launch_gemm<1, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 2, 6>(L, p, st);
-      }
+      // 69 VGPRs (>= 6 waves per SIMD): all 608 blocks are resident at once, no second round (step 745 -> 705 us)
+      return launch_gemm<1, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 2, 6>(L, p, st);
     case KD:
       p.wperm = L->wd_parts;
       if (fused) p.Yin = L->h2;   // h + o_proj, left there by gate_up's block 0
       // helpers: the next layer's QKV slices (its o_proj slices ride along: same slice size, contiguous-ish)
       if (layer + 1 < c.num_layers) p.pf = PfDesc{sec(L, SMI_LLM_WQKV, layer + 1), L->KTh * 1024, L->NTqkv, 0, (L->NTqkv + 7) / 8};
-      if (M >= L->dc_min && M <= kMaxRows && !L->tune[3] && !L->stamps_on && p.KT <= 160 && p.NT % 4 == 0)
-        return launch_down_chains(L, p, st);   // 9 .. 64 rows: the 16 chains on 16 different blocks + an in-order combine (k_downC)
-      switch (L->tune[3]) {
-        case 2: return launch_gemm<1, 16, 3, 4, PRO_PLAIN, EPI_RESID>(L, p, st);
-        case 4: return launch_gemm<1, 8, 10, 2, PRO_PLAIN, EPI_RESID>(L, p, st);
-        case 5: return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 2>(L, p, st);
-        case 6: return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID>(L, p, st);
-        default:   // few rows: 4-row parts (224 blocks, -0.7 us); same bits either way, the zero-fed MFMAs cost at M > 8
-          // row parts (H blocks per weight tile) while the operand re-reads they cost stay small: measured step at
-          // 16 / 32 / 64 rows with H = 1 | 2 | 4: 930 | 915 | 900, 1064 | 1055 | 1161, 1318 | 1443 | 1671 us
-          if (M <= 8) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4>(L, p, st);
-          if (M <= 16) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4, 0>(L, p, st);
-          if (M <= 32) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 2, 0>(L, p, st);
-          return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 1, 0>(L, p, st);
-      }
+      if (M >= kDcMin && M <= kMaxRows && !L->stamps_on && p.KT <= 160 && p.NT % 4 == 0)
+        return launch_down_chains(L, p, st);   // kDcMin .. 64 rows: the 16 chains on 16 different blocks + an in-order combine (k_downC)
+      // few rows: 4-row parts (224 blocks, -0.7 us); same bits either way, the zero-fed MFMAs cost at M > 8
+      // row parts (H blocks per weight tile) while the operand re-reads they cost stay small: measured step at
+      // 16 / 32 / 64 rows with H = 1 | 2 | 4: 930 | 915 | 900, 1064 | 1055 | 1161, 1318 | 1443 | 1671 us
+      if (M <= 8) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4>(L, p, st);
+      if (M <= 16) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4, 0>(L, p, st);
+      if (M <= 32) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 2, 0>(L, p, st);
+      return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 1, 0>(L, p, st);
     case KLM: {
       const unsigned feat = step_feat(L);
       p.stamps = L->stamps_on ? L->stamps : nullptr;
@@ -4870,45 +4832,39 @@ int launch_layer_big(smi_llm* L, int l, const RowDesc* rows, int M, int family, 
              gg = L->pg_forced ? M < L->pg_min[2] : !pg, gd = L->pg_forced ? M < L->pg_min[3] : !pg;
   const int np_from_d = pf_nparts_in(L, M, family), np_from_o = go ? L->NTh * 4 : L->NTh;
   // few rows: 64-column tiles (more blocks) and a deeper ring; o_proj / down_proj as one block per K segment + in-order combine
-  const bool few = M <= L->pg_split_rows && !(L->tune2 & 16384);
+  const bool few = M <= L->pg_split_rows && !(L->tune2 & kTune2PgemmRegs);
   const int kseg_o = (L->KTq + kPgSegO - 1) / kPgSegO, kseg_d = (L->KTi + kPgSegD - 1) / kPgSegD;
   const int nseg_o = (L->KTq + kseg_o - 1) / kseg_o, nseg_d = (L->KTi + kseg_d - 1) / kseg_d;
   int rc;
   // QKV
   const GemmP p = gemm_operands(L, KQKV, l, L->big, rows, M, np_from_d);
   if (gq) rc = launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV>(L, p, st);
-  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_QKV>(L, p, st);
+  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_NORM, EPI_QKV>(L, p, st);
   else if (few) rc = launch_pgemm<PRO_NORM, EPI_QKV, 2, 2, 6, 1, 0, 4>(L, p, st);
   else rc = launch_pgemm<PRO_NORM, EPI_QKV, 6, 2, 3, 1>(L, p, st);
   if (rc || last_kernel == KQKV || l == c.num_layers - 1) return rc;
   // attention
   const AttnP a = attn_operands(L, l, L->big, rows, M);   // (slot_is_row = 0: prompt rows name their slot)
-  if (L->tune2 & 1024) {   // SPARKMI_TUNE2 bit 1024: the decode attention kernel per prompt row (the path before k_attn_pf)
-    if ((rc = c.kv_dtype ? launch_attn<1>(L, a, 0, st) : launch_attn<0>(L, a, 0, st))) return rc;
-  } else {
-    const dim3 ag((unsigned)((M + kAttnWaves - 1) / kAttnWaves), (unsigned)c.num_heads);
-    if (!c.kv_dtype && L->attn_pf2 && L->pf_ntiles > 0 && c.head_dim == 64) {   // bf16 KV: tiles of 16 rows on the matrix pipes
-      const int tasks = L->pf_ntiles * c.num_heads;
-      hipLaunchKernelGGL(k_attn_pf2, dim3((tasks + 3) / 4), dim3(256), 0, st, a, (const PfTile*)L->pf_tiles, L->pf_ntiles);
-    } else if (c.kv_dtype) hipLaunchKernelGGL((k_attn_pf<1>), ag, dim3(kAttnWaves * 64), 0, st, a);
-    else hipLaunchKernelGGL((k_attn_pf<0>), ag, dim3(kAttnWaves * 64), 0, st, a);
-    SMI_LAUNCH_CHECK();
-  }
+  const dim3 ag((unsigned)((M + kAttnWaves - 1) / kAttnWaves), (unsigned)c.num_heads);
+  if (!c.kv_dtype && L->attn_pf2 && L->pf_ntiles > 0 && c.head_dim == 64) {   // bf16 KV: tiles of 16 rows on the matrix pipes
+    const int tasks = L->pf_ntiles * c.num_heads;
+    hipLaunchKernelGGL(k_attn_pf2, dim3((tasks + 3) / 4), dim3(256), 0, st, a, (const PfTile*)L->pf_tiles, L->pf_ntiles);
+  } else if (c.kv_dtype) hipLaunchKernelGGL((k_attn_pf<1>), ag, dim3(kAttnWaves * 64), 0, st, a);
+  else hipLaunchKernelGGL((k_attn_pf<0>), ag, dim3(kAttnWaves * 64), 0, st, a);
+  SMI_LAUNCH_CHECK();
   if (last_kernel == KATTN) return SMI_OK;
   // o_proj
   GemmP o = gemm_operands(L, KO, l, L->big, rows, M, np_from_d);
   o.kseg = kseg_o;
   if (go) rc = launch_oproj(L, o, M, st);
-  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, o, st);
+  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, o, st);
   else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, o, st, nseg_o);
   else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, o, st);
   if (rc || last_kernel == KO) return rc;
   // gate_up
   const GemmP g = gemm_operands(L, KGU, l, L->big, rows, M, np_from_o);
   if (gg) rc = launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 2>(L, g, st);
-  else if (L->tune2 & 512) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU>(L, g, st);
-  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 4>(L, g, st);
-  else if (L->tune2 & 32768) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 3>(L, g, st);
+  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 4>(L, g, st);
   else if (few) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 2, 2, 4, 0, 0, 4>(L, g, st);   // 64 KiB ring: two blocks per CU, the 304 blocks of a 127-row prompt in one round (ring of 6: 1.2 rounds, 30 us)
   else rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 2, 0, 1>(L, g, st);
   if (rc || last_kernel == KGU) return rc;
@@ -4916,7 +4872,7 @@ int launch_layer_big(smi_llm* L, int l, const RowDesc* rows, int M, int family, 
   GemmP d = gemm_operands(L, KD, l, L->big, rows, M, np_from_o);   // (never the last layer's: gamma_next is the next LN1)
   d.wperm = L->wd_parts; d.kseg = kseg_d;
   if (gd) rc = launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID>(L, d, st);
-  else if (L->tune2 & 16384) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, d, st);
+  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, d, st);
   else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, d, st, nseg_d);
   else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, d, st);
   return rc;
@@ -5227,7 +5183,6 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->lm_blocks = L->lm_cap < 512 ? L->lm_cap : 512;    // persistent path: 2 resident blocks per CU
   L->max_steps = cfg->max_positions;
   L->do_sample = 0; L->top_k = 50; L->temperature = 0.8f; L->top_p = 0.95f; L->seed = 0; L->logits = nullptr; L->tok = nullptr; L->cand_v = nullptr; L->cand_i = nullptr; L->cand_n = nullptr; L->stamps = nullptr; L->stamps_on = 0;
-  { L->tune[0] = L->tune[1] = L->tune[2] = L->tune[3] = 0; const char* e = smi_env("SPARKMI_TUNE"); if (e) sscanf(e, "%d,%d,%d,%d", &L->tune[0], &L->tune[1], &L->tune[2], &L->tune[3]); }
   L->dec = Work{}; L->big = Work{}; L->big_rows = 0;
   L->pslab = nullptr; L->pslab_bytes = 0;
   // helper-block prefetch per producer: bit 0 QKV (gate_up's first half), bit 1 attention (second half), bit 2 down_proj (the next
@@ -5238,20 +5193,14 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->prefetch_mask = 1; L->prefetch_rows = 1;
   if (const char* e = smi_env("SPARKMI_PREFETCH")) { L->prefetch_mask = atoi(e) & 7; L->prefetch_rows = 8; }
   if (smi_env("SPARKMI_NO_PREFETCH")) L->prefetch_mask = 0;
-  { const char* e = smi_env("SPARKMI_GRAPH_STEPS"); L->graph_steps = e ? atoi(e) : 8; if (L->graph_steps < 1 || L->graph_steps > 32) L->graph_steps = 8; }
   { const char* e = smi_env("SPARKMI_PF_INLINE"); L->pf_inline = !(e && e[0] == '0'); }
   { const char* e = smi_env("SPARKMI_PF_QKV"); L->pf_qkv_eighths = e ? atoi(e) : 2; if (L->pf_qkv_eighths < 0 || L->pf_qkv_eighths > 8) L->pf_qkv_eighths = 2; }
   L->part_o = nullptr; L->h2 = nullptr; L->dpart = nullptr; L->fuse_cnt = nullptr;
-  { const char* e = smi_env("SPARKMI_FUSE1_LAST"); L->fuse1_last = e && e[0] == '1'; }
   // OFF by default (diagnostics build: SPARKMI_FUSE2_ROWS=n enables it up to n <= 8 rows).  Measured at 0.5B, graph step, one box
   // (profiles/r04_fused_oproj_last_arriver.txt): 8 rows 730 -> 863 us (attention 3.9 -> 14.1 us for the 4.3-us o_proj launch it
-  // replaces), 2 rows 616 -> 640, one row (SPARKMI_FUSE1_LAST=1, against the per-head partials every gate_up block sums) 543 -> 581:
+  // replaces), 2 rows 616 -> 640, one row (a retired switch, against the per-head partials every gate_up block sums) 543 -> 581:
   // the arrival count + the reads of write-through partials cost 3-4 us at one row, where a kernel boundary costs 1.8.
   { const char* e = smi_env("SPARKMI_FUSE2_ROWS"); L->fuse2_rows = e ? atoi(e) : 0; if (L->fuse2_rows > kFuse2Max) L->fuse2_rows = kFuse2Max; }
-  // rows from which down_proj runs chain-split (k_downC): graph step at 0.5B, same box (profiles/r04_batch_ab.txt): 4 rows 641 (k_downS) vs
-  // 692 us (chains), 8 rows 728 vs 713, 16 rows 790 (k_gemm<.., H = 4>) vs 744, 32 rows 892 vs 859
-  // (5 / 6 rows: 731 / 728 us with the chains, the same as k_downS within noise -- the chains take over from 7)
-  { const char* e = smi_env("SPARKMI_DC_MIN"); L->dc_min = e ? atoi(e) : 7; }
   L->fuse_o = !smi_env("SPARKMI_NO_FUSE_O") && (cfg->num_heads == 14 || cfg->num_heads == 4) && cfg->num_heads <= kMaxOHeads &&
               L->NTh % kFuseQB == 0 && L->NTh / kFuseQB <= kAttnWaves * kFuseOT && L->KTh * 8 <= 256;
   { const char* e = smi_env("SPARKMI_TUNE2"); L->tune2 = e ? atoi(e) : 0; }
@@ -5265,13 +5214,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
     L->pg_forced = common;
     for (int i = 0; i < 4; ++i) { const char* e = smi_env(names[i]); L->pg_forced |= e != nullptr; L->pg_min[i] = e ? atoi(e) : common ? L->pgemm_min_rows : dflt[i]; }
   }
-  // A sequence's prompt rows take the kernel family ITS OWN length selects (never the call's total): up to kMaxRows rows the
-  // decode kernels in chunks, from pf_long rows the prefill-GEMM family (k_pgemm + k_attn_pf2), in between (empty by default)
-  // the row-grouped decode GEMMs -- so its K/V rows, and with a bf16 cache its tokens, do not depend on what else is in the call.
   { const char* e = smi_env("SPARKMI_PG_SPLIT_ROWS"); L->pg_split_rows = e ? atoi(e) : kPgSplitRows; if (L->pg_split_rows > kPgSplitRows) L->pg_split_rows = kPgSplitRows; }
-  { const char* e = smi_env("SPARKMI_PF_LONG"); L->pf_long = e ? atoi(e) : kMaxRows + 1; if (L->pf_long < kMaxRows + 1) L->pf_long = kMaxRows + 1; }
-  { const char* e = smi_env("SPARKMI_GU1_ROWS"); L->gu1_rows = e ? atoi(e) : 32; }
-  { const char* e = smi_env("SPARKMI_GU1_LO"); L->gu1_lo = e ? atoi(e) : 4; }
   L->wd_parts = cfg->wd_plain ? 0 : 1;   // the arena's W_down tile order comes with its config (never from the environment)
   L->exact = cfg->weights_exact;
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
@@ -5526,8 +5469,8 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
   // Every prompt token but each sequence's last is a row (slot, pos, token); the B last tokens run as the first regular step
   // (lm_head + argmax).  WHICH kernels a sequence's prompt rows run through is decided by ITS OWN row count alone:
   //   class 0  up to kMaxRows rows        the decode kernels, kMaxRows-row chunks (rows are independent there: any chunking, same bits)
-  //   class 1  kMaxRows + 1 .. pf_long-1  row-grouped decode GEMMs + the prefill attention (empty by default: pf_long = kMaxRows + 1)
-  //   class 2  pf_long rows and more      the prefill GEMM family (k_pgemm, segmented o_proj / down_proj sums) + the prefill attention
+  //   class 1  kMaxRows + 1 .. kPfLong-1  row-grouped decode GEMMs + the prefill attention (empty: kPfLong = kMaxRows + 1)
+  //   class 2  kPfLong rows and more      the prefill GEMM family (k_pgemm, segmented o_proj / down_proj sums) + the prefill attention
   // and every class is its own pass over the layers, so a sequence's K/V rows -- and, K/V being rounded to bf16, its tokens --
   // are the same bits whatever else the call holds (round 3 picked the kernels from the call's TOTAL rows).
   // Diagnostics keep the old single pass: SPARKMI_PREFILL_CHUNKS (chunks only), SPARKMI_PGEMM_MIN_* (per kernel by total rows);
@@ -5537,7 +5480,7 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
     const int r = lens[b] - 1;
     if (chunks_only) return 0;
     if (L->pg_forced) return total > (size_t)kMaxRows ? 3 : 0;   // 3: one pass, kernels by the pass's row count (launch_layers_big)
-    return r <= kMaxRows ? 0 : r < L->pf_long ? 1 : 2;
+    return r <= kMaxRows ? 0 : r < kPfLong ? 1 : 2;
   };
   size_t ncls[4] = {0, 0, 0, 0};
   for (int b = 0; b < B; ++b) ncls[cls_of(b)] += lens[b] - 1;
@@ -6671,15 +6614,12 @@ int smi_llm_decode(smi_llm* L, int n_steps, void* stream) {
       L->graph_cache[key] = L->graph;
     }
   }
-  // Several steps per replay (SPARKMI_GRAPH_STEPS = K, default 8; 1: off): a step needs nothing from the host, so K of them are
-  // captured back to back into one graph; the call replays it n_steps / K times and the one-step graph for the rest.  One replay
-  // boundary costs ~5 us that a kernel boundary inside a graph does not: graph step at one row 548.6 -> 544.5 us (K = 4 .. 25
-  // alike; profiles/r03_graph_steps.txt).  The K-step graph of a key is only built by a call long enough to replay it twice (a
-  // capture of 8 x 98 nodes is not free; short serving strides keep to the one-step graph); a failed capture leaves the call to
-  // the one-step graph.
+  // Several steps per replay (K = kGraphSteps): the call replays the K-step graph n_steps / K times and the one-step graph for the
+  // rest.  The K-step graph of a key is only built by a call long enough to replay it twice (a capture of 8 x 98 nodes is not
+  // free; short serving strides keep to the one-step graph); a failed capture leaves the call to the one-step graph.
   int s0 = 0;
-  if (L->cfg.use_graph && L->graph_steps > 1 && n_steps >= L->graph_steps) {
-    const int K = L->graph_steps;
+  if (L->cfg.use_graph && n_steps >= kGraphSteps) {
+    constexpr int K = kGraphSteps;
     const uint64_t keyk = graph_key(L, feat, K);
     hipGraphExec_t gk = nullptr;
     auto hit = L->graph_cache.find(keyk);

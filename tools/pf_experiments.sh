@@ -17,6 +17,4 @@ run A=1
 run SPARKMI_PF_QKV=6
 run SPARKMI_PF_QKV=8
 run SPARKMI_PF_QKV=2
-run SPARKMI_PREFETCH=5 SPARKMI_TUNE2=4194304
-run SPARKMI_PREFETCH=4 SPARKMI_TUNE2=4194304
 done

@@ -42,8 +42,6 @@ if len(sys.argv) > 1 and sys.argv[1] == "mix2":
 if len(sys.argv) > 1 and sys.argv[1] == "pf2":   # prefill attention: 16-row tiles on the matrix pipes vs one wave per (row, head)
     os.environ.setdefault("PF_SIZES", "1x128,1x460,8x460,32x128,1x1000")
     modes = (("attn tiles (k_attn_pf2)", {}), ("attn per row (k_attn_pf)", {"SPARKMI_ATTN_PF2": "0"}))
-if len(sys.argv) > 1 and sys.argv[1] == "gu1":   # gate_up's one-batch shape beyond 32 rows (row-grouped prefill)
-    modes = tuple((f"grouped gu1<={r}", {"SPARKMI_PGEMM_MIN_ROWS": "100000", "SPARKMI_GU1_ROWS": str(r)}) for r in (32, 128, 100000))
 if len(sys.argv) > 1 and sys.argv[1] == "r04":   # round 4: kernels by each sequence's own length; few-row shapes + split-K up to 512 rows
     os.environ.setdefault("PF_SIZES", "1x128,1x66,1x256,1x460,4x128,8x460,32x128")
     modes = (("default (own length: prefill GEMM family, few-row shapes <= 512 rows)", {}), ("many-row shapes at any size", {"SPARKMI_PG_SPLIT_ROWS": "0"}),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Round-4 batch decode A/B on one box (GPU box): python tools/r04_batch_ab.py 32 16 8
 For each row count: eager per-kernel loops, in-sequence per-kernel times (as inside the graph) and the graph step, for the
-default build path and with the chain-split down_proj turned off (SPARKMI_DC_MIN=1000: the round-3 kernels)."""
+default build path and, at 2 .. 8 rows, with the fused attention + o_proj (SPARKMI_FUSE2_ROWS)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r'''
@@ -24,8 +24,6 @@ print("B", B, os.environ.get("AB_TAG"), "eager", eager, "in-seq", seq, "graph st
 ''' % ROOT
 for B in sys.argv[1:] or ["32"]:
     for rep in range(2):
-        variants = (("new", {}), ("old-down", {"SPARKMI_DC_MIN": "1000"})) if int(B) > 8 else (("fused o_proj (FUSE2)", {}), ("separate o_proj", {"SPARKMI_FUSE2_ROWS": "0"}))
-        if int(B) == 1:
-            variants = (("per-head partials summed by gate_up (default)", {}), ("last-arriver head sum", {"SPARKMI_FUSE1_LAST": "1"}))
+        variants = (("default", {}),) if int(B) > 8 or int(B) == 1 else (("fused o_proj (FUSE2)", {}), ("separate o_proj", {"SPARKMI_FUSE2_ROWS": "0"}))
         for tag, env in variants:
             subprocess.run([sys.executable, "-c", code], env=dict(os.environ, AB_B=B, AB_TAG=tag, **env), check=False)

@@ -25,8 +25,6 @@ for v in sys.argv[1:] or ["0", "1", "2", "3", "4", "5", "6", "7"]:
     if v.startswith("env:"):
         k, val = v[4:].split("=", 1)
         env = dict(os.environ, SPARKMI_VARIANT=v, **{k: val})
-    if v.startswith("tune:"):
-        env = dict(os.environ, SPARKMI_TUNE=v[5:], SPARKMI_VARIANT=v)
     if v.startswith("lib:"):
         env = dict(os.environ, SPARKMI_LIB=os.path.join(ROOT, v[4:]), SPARKMI_VARIANT="lib")
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True)
