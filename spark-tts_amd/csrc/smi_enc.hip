@@ -15,11 +15,13 @@
 //
 // Activations are [C][T] fp32 (time contiguous), one utterance per call like the reference's tokenize().
 // Dense contractions run on the exact-fp32 matrix pipe through the vocoder's implicit-GEMM kernel
-// (smi_net.h); attention and the 128-tap grouped positional conv are VALU kernels (small: T <= ~1500).
+// (smi_net.hip); attention and the 128-tap grouped positional conv are VALU kernels (small: T <= ~1500).
 #include "smi_net.h"
 #include <math.h>
 #include <algorithm>
 #include <map>
+
+using namespace smi_net;
 
 namespace {
 
@@ -380,7 +382,7 @@ EncLayout enc_layout(const smi_enc_cfg* c) {
     add(name, PACK_CONV, Cout, Cin, K, (size_t)conv_geom(Cout, Cin, K, 1, 0, 1).floats);
   };
   // convb: the dense stride-1 layers that carry the FLOPs (wav2vec2's transformer projections, the BiCodec encoder's
-  // ConvNeXt stack) -- on the bf16-split matrix pipe (k_convb, smi_net.h) unless the handle asks for exact fp32
+  // ConvNeXt stack) -- on the bf16-split matrix pipe (k_convb, smi_net.hip) unless the handle asks for exact fp32
   auto convb = [&](const std::string& name, int Cout, int Cin, int K) {
     const bool bf = !c->exact_fp32 && Cin >= 32 && Cout >= 32;
     add(name, bf ? PACK_CONV_B : PACK_CONV, Cout, Cin, K, (size_t)conv_geom(Cout, Cin, K, 1, 0, 1, bf).floats);

@@ -32,6 +32,7 @@
 #include <cstddef>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -276,6 +277,7 @@ __device__ __forceinline__ void smi_kernarg_lines(const GemmP& p) {
 // instantiation keeps.  A kernel whose first parameter is a struct gets no preload and compiles as without the flag.
 template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int KVF32, int H = 1, int OCC = 1, int LEAN = 0, int NOH = kMaxOHeads>
 __device__ __forceinline__ void gemm_body(const GemmP& p) {
+  static_assert(EPI == EPI_QKV || KVF32 == 0, "the cache type is a parameter of the kernels that write the cache");
   static_assert(H == 1 || ((H == 2 || H == 4) && NTB == 1 && EPI == EPI_RESID), "row-split tiles: RESID, one tile per block");
   static_assert(PRO != PRO_FUSEDO || (LEAN == 2 && MT == 1 && EPI == EPI_SWIGLU), "PRO_FUSEDO: the one-row gate_up kernel");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1023,6 +1025,7 @@ __global__ __launch_bounds__(256) void k_downS(GemmP p) {
 // ------------------------------------------------------------------------------------------
 template <int PRO, int EPI, int KVF32>
 __global__ __launch_bounds__(256) void k_gemm_x(GemmP p, const float* W32) {
+  static_assert(EPI == EPI_QKV || KVF32 == 0, "the cache type is a parameter of the kernels that write the cache");
   __shared__ float bestv[4][16];
   __shared__ int besti[4][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1373,6 +1376,7 @@ __device__ __forceinline__ void smi_keep4(const uint4& v) { asm volatile("" ::"v
 // MTB (ring form only): m-tiles per block, 8 (128 rows) or 4 (64 rows: the few-row shapes -- twice the blocks for a 127-row prompt).
 template <int PRO, int EPI, int KVF32, int NTW = 2, int WR = 1, int RING = 0, int XMAP = 0, int TWO = 0, int MTB = 8>
 __global__ __launch_bounds__(256, TWO ? 2 : 1) void k_pgemm(GemmP p) {
+  static_assert(EPI == EPI_QKV || KVF32 == 0, "the cache type is a parameter of the kernels that write the cache");
   static_assert(MTB == 8 || (MTB == 4 && RING >= 3 && !TWO), "64-row tiles: ring form");
   constexpr int ROWS = MTB * 16, PIECES = 3 * 4 * ROWS;   // 1536 (768) 16-byte pieces per k tile; NTW weight tiles per wave
   constexpr int MTW = MTB / WR, NWC = 4 / WR;                      // m-tiles per wave, waves across the block's columns
@@ -3960,6 +3964,15 @@ struct LdsBig {
 };
 constexpr int kLdsBigBytes = 160 * 1024;   // the window every LdsBig kernel is opted in to
 
+// The KV cache's element type as a template argument of a GEMM launch: f(kv) with kv() = 1 for an f32 cache where the epilogue
+// appends to the cache (EPI_QKV), and the constant 0 for every other epilogue -- those kernels never read it, so they exist once.
+template <int EPI, class F>
+auto with_kvf32(const smi_llm* L, F&& f) {
+  if constexpr (EPI == EPI_QKV)
+    if (L->cfg.kv_dtype) return f(std::integral_constant<int, 1>{});
+  return f(std::integral_constant<int, 0>{});
+}
+
 // ---- paged KV cache: host-side page allocator.  A slot's row of the table lists the pages of its positions in order.  A page
 // may sit in several rows (the leading pages of a forked admission's takes, pages_share); page_ref counts them, and a page goes
 // back to the pool when its last holder lets go of it.
@@ -4135,9 +4148,9 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
       lds += per_wave * NW;
     }
   }
-  // more than the default dynamic LDS window: both cache types' instantiations were opted in by smi_llm_create (LdsBig)
-  static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>>::reg);
+  // more than the default dynamic LDS window: the instantiation (QKV: both cache types') was opted in by smi_llm_create (LdsBig)
   static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>>::reg);
+  if constexpr (EPI == EPI_QKV) static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>>::reg);
   SMI_REQUIRE(lds <= (size_t)kLdsBigBytes, "k_gemm: %zu bytes of LDS", lds);
   const int groups = (p.M + MT * 16 - 1) / (MT * 16);   // one block row per MT*16 rows (more than one: prefill, or 17..32 rows as 2 x 16)
   if constexpr (EPI == EPI_LM) SMI_LM_NOTE(L, MT == 2 ? "k_gemm<2,EPI_LM>" : "k_gemm<1,EPI_LM>", work + helpers, groups, NW * 64);
@@ -4161,21 +4174,19 @@ int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
       }
     }
     if constexpr (PRO == PRO_NORM && EPI == EPI_QKV && kLean && NW == 16 && U == 2 && WB == 1) {   // one-row QKV in its adopted block shape: the hot entry
-      if (L->cfg.kv_dtype) launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>(p, dim3(work + helpers, groups), lds, st);
-      else launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>(p, dim3(work + helpers, groups), lds, st);
-    } else if (L->cfg.kv_dtype)
-      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC, 2 * kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
-    else
-      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC, 2 * kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
+      with_kvf32<EPI>(L, [&](auto kv) { launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC>(p, dim3(work + helpers, groups), lds, st); });
+    } else
+      with_kvf32<EPI>(L, [&](auto kv) {
+        hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, 2 * kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
+      });
   } else if (kLean && p.ldsb > 0 && !p.stamps) {
-    if (L->cfg.kv_dtype)
-      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC, kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
-    else
-      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC, kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
-  } else if (L->cfg.kv_dtype)
-    hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
-  else
-    hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
+    with_kvf32<EPI>(L, [&](auto kv) {
+      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
+    });
+  } else
+    with_kvf32<EPI>(L, [&](auto kv) {
+      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
+    });
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }
@@ -4584,8 +4595,7 @@ template <int PRO, int EPI>
 int launch_gemm_x(const smi_llm* L, const GemmP& p, hipStream_t st) {
   const dim3 grid((p.NT + 3) / 4, (p.M + 15) / 16);
   if constexpr (EPI == EPI_LM) SMI_LM_NOTE(L, "k_gemm_x<EPI_LM>", grid.x, grid.y, 256);
-  if (L->cfg.kv_dtype) hipLaunchKernelGGL((k_gemm_x<PRO, EPI, 1>), grid, dim3(256), 0, st, p, (const float*)p.W);
-  else hipLaunchKernelGGL((k_gemm_x<PRO, EPI, 0>), grid, dim3(256), 0, st, p, (const float*)p.W);
+  with_kvf32<EPI>(L, [&](auto kv) { hipLaunchKernelGGL((k_gemm_x<PRO, EPI, kv()>), grid, dim3(256), 0, st, p, (const float*)p.W); });
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }
@@ -4785,9 +4795,9 @@ int launch_pgemm(const smi_llm* L, GemmP p, hipStream_t st, int nsplit = 1) {
   const dim3 grid2((p.NT + cols - 1) / cols, (p.M + rows - 1) / rows);
   dim3 grid = XMAP ? dim3(grid2.x * grid2.y) : grid2;
   constexpr size_t lds = (RING ? (size_t)RING * (12 * rows + cols * 64) : (size_t)2 * 12 * rows) * 16 + (TWO ? 0 : rows * 4);
-  if constexpr (lds > 64 * 1024) {   // both cache types' instantiations were opted in by smi_llm_create (LdsBig)
-    static_cast<void>(LdsBig<k_pgemm<PRO, EPI, 1, NTW, WR, RING, XMAP, TWO, MTB>>::reg);
+  if constexpr (lds > 64 * 1024) {   // the instantiation (QKV: both cache types') was opted in by smi_llm_create (LdsBig)
     static_cast<void>(LdsBig<k_pgemm<PRO, EPI, 0, NTW, WR, RING, XMAP, TWO, MTB>>::reg);
+    if constexpr (EPI == EPI_QKV) static_cast<void>(LdsBig<k_pgemm<PRO, EPI, 1, NTW, WR, RING, XMAP, TWO, MTB>>::reg);
     static_assert(lds <= (size_t)kLdsBigBytes, "k_pgemm: LDS beyond the opted-in window");
   }
   const int mtiles = (p.M + 15) / 16;
@@ -4797,8 +4807,7 @@ int launch_pgemm(const smi_llm* L, GemmP p, hipStream_t st, int nsplit = 1) {
     p.slab = L->pslab; p.slab_mt = mtiles;
     grid = dim3(grid2.x * grid2.y, nsplit);
   }
-  if (L->cfg.kv_dtype) hipLaunchKernelGGL((k_pgemm<PRO, EPI, 1, NTW, WR, RING, XMAP, TWO, MTB>), grid, dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((k_pgemm<PRO, EPI, 0, NTW, WR, RING, XMAP, TWO, MTB>), grid, dim3(256), lds, st, p);
+  with_kvf32<EPI>(L, [&](auto kv) { hipLaunchKernelGGL((k_pgemm<PRO, EPI, kv(), NTW, WR, RING, XMAP, TWO, MTB>), grid, dim3(256), lds, st, p); });
   SMI_LAUNCH_CHECK();
   if (nsplit > 1) {
     DownCP d;

@@ -23,6 +23,8 @@
 #include <algorithm>
 #include <map>
 
+using namespace smi_net;
+
 namespace {
 
 struct VocLayout {
@@ -900,11 +902,11 @@ int conv_plan_info(const smi_conv_case& c, const Launch& L, smi_conv_plan_info* 
 
 extern "C" {
 
-int smi_conv_form_count(void) { return kNumConvForms; }
+int smi_conv_form_count(void) { return conv_form_count(); }
 
 int smi_conv_form_get(int index, smi_conv_form* out) {
-  SMI_REQUIRE(out && index >= 0 && index < kNumConvForms, "smi_conv_form_get: index %d out of range", index);
-  *out = form_record(kConvForms[index].form);
+  SMI_REQUIRE(out && index >= 0 && index < conv_form_count(), "smi_conv_form_get: index %d out of range", index);
+  *out = form_record(conv_form_at(index));
   return SMI_OK;
 }
 
