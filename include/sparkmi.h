@@ -651,6 +651,64 @@ int smi_rs_prompt_rows(smi_rs* h, const float* in_dev, long long in_stride, cons
                        const int32_t* ref_len_host, float* ref_dev, long long ref_stride, double* gain_out_dev,
                        int32_t* n_out_host, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stream joiner: the overlapping chunks of a streamed request become one contiguous, playable stream on the device, at the
+ * model's rate or at any registered-style ratio up/down of it.  State is kept across chunk edges per stream (a slot of the
+ * handle): the held tail for the fade and the resampler's last input samples.  Opt-in: nothing else of the library calls it.
+ *
+ * Join.  A stream's chunks c_0 .. c_{m-1} have L_i samples; `overlap` = n samples; fade_in = linspace(0, 1, n) and fade_out =
+ * linspace(1, 0, n) are float64 tables the caller uploads at creation (the device computes no linspace).  t is the held tail,
+ * the last n samples of c_{i-1}:
+ *     c_0, the only chunk:     emits c_0                                   holds nothing
+ *     c_0, not last:           emits c_0[:L-n]                             holds c_0[L-n:]
+ *     c_i, i >= 1, not last:   emits fade(c_i[:n], t), then c_i[n:L-n]     holds c_i[L-n:]
+ *     c_i, i >= 1, last:       emits fade(c_i[:n], t), then c_i[n:]        holds nothing
+ *     fade(a, t)[q] = fl32( fl64(fl64(a[q]) * fade_in[q]) + fl64(fl64(t[q]) * fade_out[q]) )
+ * -- two float64 products rounded separately, one float64 add, one rounding to fp32, no FMA.  Where every L_i >= 2n the joined
+ * stream is sparkmi/streaming.py: crossfade(chunks, n) cast to fp32, bit for bit; its length is sum L_i - n (m - 1).  Two cases
+ * are defined here and not by crossfade: n = 0 is plain concatenation (crossfade degenerates), and a last chunk with
+ * n <= L < 2n follows the table (crossfade would repeat samples).  A chunk that is not the last needs L >= 2n and a last chunk
+ * with i >= 1 needs L >= n: anything else is SMI_EINVAL.  An empty last chunk is valid where those rules allow it (n = 0, or the
+ * only chunk) and flushes the resampler.
+ *
+ * Resample with state.  x is the joined stream, N samples so far; up/down and taps h[0 .. 2H] as for smi_rs_register.  Output k is
+ * exactly the sum smi_rs_resample_rows forms for the whole stream: j ascending from ceil((k down - H) / up), clamped at 0, to
+ * floor((k down + H) / up), clamped at the stream's end; fp32, one accumulator, product and sum rounded separately.  After a push
+ * that is not the last the stream has emitted K(N) = max(0, ceil((N up - H) / down)) outputs in all, after the last one
+ * ceil(N up / down); a push emits the difference, which may be 0.  The handle keeps ceil((2H + down) / up) + 1 input samples of
+ * history per stream, which is enough; the latency is H / up input samples.  up = down = 1 needs no filter: the join's output is
+ * emitted as it is, with no latency.
+ *
+ * Guarantees: the concatenation of a stream's pieces is, bit for bit, smi_rs_resample_rows of its whole joined waveform, whatever
+ * the granularity of the pushes, the stream's slot, its row in a call and the other rows.  A piece's length is pure host
+ * arithmetic (smi_join_piece_len); nothing synchronises.  A stream is refused (SMI_EINVAL) before N up or K down reaches 2^31.
+ *
+ * The per-stream counters (chunk index, N, K) live on the host, the tails and histories on the device in two sets that a
+ * stream uses in turn: a push reads one and writes the other, so one launch serves a call whatever B.  All pushes of a handle
+ * must go to one HIP stream (or be ordered by the caller). */
+typedef struct smi_join smi_join;
+/* max_streams (1..4096) slots; max_chunk (1..2^24) samples a chunk; overlap = n (0..max_chunk / 2); fade_*_host [n] float64 (may
+ * be null for n = 0); taps_host [n_taps] float64, n_taps = 2H + 1 odd, LDS-limited as in smi_rs_register (ignored for 1/1).
+ * Synchronous (one allocation, small copies). */
+int smi_join_create(int max_streams, int max_chunk, int overlap, const double* fade_in_host, const double* fade_out_host, int up, int down,
+                    const double* taps_host, int n_taps, smi_join** out);
+int smi_join_destroy(smi_join* h);
+/* A new stream in slot `stream`: chunk index, N and K are zero.  Host only.  A stream closes with its last chunk. */
+int smi_join_open(smi_join* h, int stream);
+/* One ready chunk per row: chunks_dev [B][stride] f32 (row b valid for len_host[b]), of the open streams stream_host[b], each at
+ * most once in a call; last_host[b] = 1 on a stream's last chunk.  out_dev [B][out_stride] f32: row b receives its piece and
+ * zeros from there to out_stride (>= 1 and >= the longest piece).  n_out_host [B] (may be null) receives the pieces' lengths,
+ * filled before the launch.  B <= 64.  One launch, asynchronous on `stream`.  Every argument of every row is checked before
+ * anything changes or is launched: a bad one returns SMI_EINVAL and names the argument in smi_last_error.  chunks_dev must not
+ * overlap out_dev. */
+int smi_join_push_rows(smi_join* h, const float* chunks_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                       const int32_t* last_host, int B, float* out_dev, long long out_stride, int32_t* n_out_host, void* stream);
+/* The piece length of one push, pure host arithmetic: a stream with n_before joined samples and k_before emitted outputs takes a
+ * chunk of len samples (first = 1: its first chunk; last = 1: its last); n_after / k_after (may be null) receive the counters
+ * after it.  n_taps = 2H + 1 (1 for up = down = 1).  -1 for a length the rules above refuse or a bad argument. */
+long long smi_join_piece_len(int overlap, int up, int down, int n_taps, int first, long long n_before, long long k_before, long long len,
+                             int last, long long* n_after, long long* k_after);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,10 @@
 //                11 / 11 / 9 bits), a fixed-point sum of the selected range in 64-bit integers (every |x| > 0.01 is a multiple of
 //                2^-30, so the sum is exact and its order does not matter), the combined gain in float64, the scaled samples and
 //                the tiled reference clip.  Only integer LDS atomics: no floating-point atomic anywhere.
+//   k_join_rows  the stream joiner (smi_join_*), grid as k_rs_rows: the overlapping chunks of streamed requests become one
+//                contiguous stream per request, cross-faded in float64 and resampled with k_rs_rows' own sums (rs_tile_sums);
+//                a block assembles its input window in LDS from the stream's history, the fade region and the chunk's body.
+//                Tails and histories live in two sets a stream uses in turn, so one launch reads its state and writes the next.
 #include <vector>
 
 #include "smi_common.h"
@@ -20,6 +24,7 @@
 #define RS_LDS_FLOATS 16384     // taps + input window of one tile: 64 KiB of LDS
 #define RS_POOL_FLOATS (1 << 18)
 #define RS_MAX_SAMPLES (1 << 24)
+#define JN_MAX_STREAMS 4096     // slots of one smi_join handle
 #define PR_BLOCK 1024
 #define PR_BINS 2048
 
@@ -53,6 +58,26 @@ __device__ __forceinline__ int rs_jhi(int kd, int up, int half) { return (int)((
 // input samples a tile's window may span, for sizing the LDS
 inline long long rs_window(int up, int down, int half) { return ((long long)(RS_TILE - 1) * down + 2LL * half) / up + 3; }
 
+// The sums of one tile, shared by k_rs_rows and k_join_rows: output k_first + i goes to y[i], i < n_write; an output at or past
+// n_out is a zero.  xw[0] is input sample j0 of the row (or of the joined stream), jmax the last input sample there is.
+__device__ __forceinline__ void rs_tile_sums(const float* ht, const float* xw, int j0, int jmax, int k_first, int n_out, int up, int down,
+                                             int half, float* __restrict__ y, int n_write) {
+  for (int i = threadIdx.x; i < n_write; i += RS_BLOCK) {
+    const int k = k_first + i;
+    float acc = 0.f;
+    if (k < n_out) {
+      const int kd = k * down;
+      const int jl = rs_jlo(kd, up, half);
+      const int jh = min(rs_jhi(kd, up, half), jmax);
+      int t = half + kd - jl * up;   // tap of the first term, in [0, 2H]
+      const int w = jl - j0;
+      const int n = jh - jl + 1;
+      for (int m = 0; m < n; ++m, t -= up) acc = acc + xw[w + m] * ht[t];
+    }
+    y[i] = acc;
+  }
+}
+
 __global__ __launch_bounds__(RS_BLOCK) void k_rs_rows(RsArgs a, const float* __restrict__ taps, const float* __restrict__ in,
                                                       long long in_stride, float* __restrict__ out, long long out_stride) {
   extern __shared__ __attribute__((aligned(16))) float rs_lds[];
@@ -81,20 +106,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_rows(RsArgs a, const float* __r
   for (int i = tid; i < ntaps; i += RS_BLOCK) ht[i] = h[i];
   for (int i = tid; i < nwin; i += RS_BLOCK) xw[i] = x[j0 + i];
   __syncthreads();
-  for (int i = tid; i < RS_TILE && k0 + i < out_stride; i += RS_BLOCK) {
-    const long long k = k0 + i;
-    float acc = 0.f;
-    if (k < r.n_out) {
-      const int kd = (int)k * r.down;
-      const int jl = rs_jlo(kd, r.up, r.half);
-      const int jh = min(rs_jhi(kd, r.up, r.half), r.n_in - 1);
-      int t = r.half + kd - jl * r.up;   // tap of the first term, in [0, 2H]
-      const int w = jl - j0;
-      const int n = jh - jl + 1;
-      for (int m = 0; m < n; ++m, t -= r.up) acc = acc + xw[w + m] * ht[t];
-    }
-    y[k] = acc;
-  }
+  rs_tile_sums(ht, xw, j0, r.n_in - 1, (int)k0, r.n_out, r.up, r.down, r.half, y + k0, (int)min((long long)RS_TILE, out_stride - k0));
 }
 
 // ---- k_rs_prompt's block-wide helpers (PR_BLOCK threads)
@@ -223,6 +235,86 @@ __global__ __launch_bounds__(PR_BLOCK) void k_rs_prompt(PrArgs a, int normalize,
     for (int i = tid; i < n; i += PR_BLOCK) x[i] = (float)((double)x[i] * gain);
 }
 
+// ---- the stream joiner (smi_join_*)
+struct JnRow {
+  int32_t slot, set;        // the stream's slot; the state set this push reads (it writes the other one)
+  int32_t len, n_fade;      // chunk samples; leading samples that are faded with the held tail (0 for a stream's first chunk)
+  int32_t n_old, n_new;     // joined samples before / after this push
+  int32_t k_old, k_new;     // outputs emitted before / after this push
+  int32_t keep;             // 1: the chunk's last `overlap` samples become the held tail
+};
+struct JnArgs {
+  JnRow r[RS_MAX_ROWS];
+};
+struct JnState {
+  float* tail;              // [2][max_streams][overlap]
+  float* hist;              // [2][max_streams][hs]: the last hs joined samples, hist[q] = x[N - hs + q]
+  const double* fade_in;    // [overlap]
+  const double* fade_out;   // [overlap]
+  const float* taps;        // [2H + 1]
+  int32_t max_streams, overlap, hs, up, down, half;
+};
+
+// sample j of the joined stream, n_old - hs <= j < n_new: from the history, the fade region or the chunk's body
+__device__ __forceinline__ float jn_sample(int j, const JnRow& r, int hs, const float* __restrict__ c, const float* __restrict__ hist,
+                                           const float* __restrict__ tail, const double* __restrict__ fi, const double* __restrict__ fo) {
+  if (j < r.n_old) return hist[j - (r.n_old - hs)];
+  const int q = j - r.n_old;
+  const float a = c[q];
+  if (q < r.n_fade) return (float)((double)a * fi[q] + (double)tail[q] * fo[q]);
+  return a;
+}
+
+// grid (tiles of RS_TILE output samples, rows), as k_rs_rows.  Block (t, b) assembles the window of its tile from the stream's
+// history, the fade region and the chunk's body in LDS and sums its outputs with k_rs_rows' loop; tile 0 of a row also writes
+// the stream's next state -- tail and history -- into the state set this launch does not read.
+__global__ __launch_bounds__(RS_BLOCK) void k_join_rows(JnArgs a, JnState s, const float* __restrict__ in, long long in_stride,
+                                                        float* __restrict__ out, long long out_stride) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const JnRow r = a.r[blockIdx.y];
+  const long long k0 = (long long)blockIdx.x * RS_TILE;   // of this push's piece
+  if (k0 >= out_stride) return;
+  const int tid = threadIdx.x;
+  const float* c = in + (size_t)blockIdx.y * in_stride;
+  float* y = out + (size_t)blockIdx.y * out_stride;
+  const size_t per_t = (size_t)s.max_streams * s.overlap, per_h = (size_t)s.max_streams * s.hs;
+  const float* tail = s.tail + r.set * per_t + (size_t)r.slot * s.overlap;
+  const float* hist = s.hist + r.set * per_h + (size_t)r.slot * s.hs;
+  if (blockIdx.x == 0) {   // the next state, from what this launch only reads
+    float* tail2 = s.tail + (1 - r.set) * per_t + (size_t)r.slot * s.overlap;
+    float* hist2 = s.hist + (1 - r.set) * per_h + (size_t)r.slot * s.hs;
+    if (r.keep)
+      for (int q = tid; q < s.overlap; q += RS_BLOCK) tail2[q] = c[r.len - s.overlap + q];
+    for (int q = tid; q < s.hs; q += RS_BLOCK) {
+      const int j = r.n_new - s.hs + q;
+      hist2[q] = j < 0 ? 0.f : jn_sample(j, r, s.hs, c, hist, tail, s.fade_in, s.fade_out);
+    }
+  }
+  const int n_piece = r.k_new - r.k_old;
+  const int n_write = (int)min((long long)RS_TILE, out_stride - k0);
+  if (k0 >= n_piece) {   // padding past the piece: zeros
+    for (int i = tid; i < n_write; i += RS_BLOCK) y[k0 + i] = 0.f;
+    return;
+  }
+  if (s.up == 1 && s.down == 1) {   // the join alone: k_old = n_old
+    for (int i = tid; i < n_write; i += RS_BLOCK)
+      y[k0 + i] = k0 + i < n_piece ? jn_sample(r.n_old + (int)k0 + i, r, s.hs, c, hist, tail, s.fade_in, s.fade_out) : 0.f;
+    return;
+  }
+  const int ntaps = 2 * s.half + 1;
+  float* ht = rs_lds;
+  float* xw = rs_lds + ntaps;
+  const int kf = r.k_old + (int)k0;                                  // of the stream
+  const int klast = min(kf + RS_TILE, r.k_new) - 1;
+  const int j0 = rs_jlo(kf * s.down, s.up, s.half);                 // >= n_old - hs: checked on the host
+  const int j1 = min(rs_jhi(klast * s.down, s.up, s.half), r.n_new - 1);
+  const int nwin = j1 - j0 + 1;   // <= rs_window(): checked at creation
+  for (int i = tid; i < ntaps; i += RS_BLOCK) ht[i] = s.taps[i];
+  for (int i = tid; i < nwin; i += RS_BLOCK) xw[i] = jn_sample(j0 + i, r, s.hs, c, hist, tail, s.fade_in, s.fade_out);
+  __syncthreads();
+  rs_tile_sums(ht, xw, j0, r.n_new - 1, kf, r.k_new, s.up, s.down, s.half, y + k0, n_write);
+}
+
 }  // namespace
 
 struct smi_rs {
@@ -230,6 +322,19 @@ struct smi_rs {
   float* pool;
   int pool_used;
   std::vector<Filter> filters;
+};
+
+// a stream's counters live on the host: a push's piece length is known before its launch
+struct JnStream {
+  int open = 0, set = 0;
+  long long chunks = 0, n = 0, k = 0;   // chunks pushed, joined samples N, outputs emitted K
+};
+struct smi_join {
+  JnState s;
+  int max_chunk, n_taps;
+  size_t lds;
+  char* pool;
+  std::vector<JnStream> streams;
 };
 
 static const Filter* rs_find(const smi_rs* h, int up, int down) {
@@ -367,6 +472,156 @@ int smi_rs_prompt_rows(smi_rs* h, const float* in_dev, long long in_stride, cons
   SMI_LAUNCH_CHECK();
   if (n_out_host)
     for (int b = 0; b < B; ++b) n_out_host[b] = A.r[b].n_out;
+  return SMI_OK;
+}
+
+long long smi_join_piece_len(int overlap, int up, int down, int n_taps, int first, long long n_before, long long k_before, long long len,
+                             int last, long long* n_after, long long* k_after) {
+  if (overlap < 0 || up < 1 || down < 1 || n_taps < 1 || !(n_taps & 1) || n_before < 0 || k_before < 0 || len < 0) return -1;
+  if (!last && len < 2LL * overlap) return -1;
+  if (last && !first && len < overlap) return -1;
+  const long long n = n_before + len - (last ? 0 : overlap);
+  long long k = n;
+  if (!(up == 1 && down == 1)) {
+    const long long half = n_taps / 2;
+    if (last) k = rs_out_len(n, up, down);
+    else k = n * up <= half ? 0 : (n * up - half + down - 1) / down;
+  }
+  if (k < k_before) return -1;
+  if (n_after) *n_after = n;
+  if (k_after) *k_after = k;
+  return k - k_before;
+}
+
+int smi_join_create(int max_streams, int max_chunk, int overlap, const double* fade_in_host, const double* fade_out_host, int up, int down,
+                    const double* taps_host, int n_taps, smi_join** out) {
+  SMI_REQUIRE(out, "smi_join_create: null out");
+  *out = nullptr;
+  SMI_REQUIRE(max_streams >= 1 && max_streams <= JN_MAX_STREAMS, "smi_join_create: max_streams=%d outside 1..%d", max_streams, JN_MAX_STREAMS);
+  SMI_REQUIRE(max_chunk >= 1 && max_chunk <= RS_MAX_SAMPLES, "smi_join_create: max_chunk=%d outside 1..%d", max_chunk, RS_MAX_SAMPLES);
+  SMI_REQUIRE(overlap >= 0 && 2LL * overlap <= max_chunk, "smi_join_create: overlap=%d outside 0..max_chunk/2 (max_chunk=%d)", overlap, max_chunk);
+  SMI_REQUIRE(overlap == 0 || (fade_in_host && fade_out_host), "smi_join_create: null fade table with overlap=%d", overlap);
+  SMI_REQUIRE(up >= 1 && down >= 1, "smi_join_create: up=%d, down=%d: both must be positive", up, down);
+  const bool copy = up == 1 && down == 1;
+  int half = 0;
+  if (!copy) {
+    SMI_REQUIRE(taps_host, "smi_join_create: null taps_host with up/down = %d/%d", up, down);
+    SMI_REQUIRE(n_taps >= 1 && (n_taps & 1), "smi_join_create: n_taps=%d must be odd (taps h[0 .. 2H])", n_taps);
+    half = n_taps / 2;
+    const long long fl = (long long)n_taps + rs_window(up, down, half);
+    SMI_REQUIRE(fl <= RS_LDS_FLOATS, "smi_join_create: n_taps=%d with up/down = %d/%d needs %lld floats of LDS a tile, above %d", n_taps, up,
+                down, fl, RS_LDS_FLOATS);
+  }
+  const long long outs = rs_out_len(max_chunk, up, down) + 1;
+  SMI_REQUIRE(outs <= RS_MAX_SAMPLES, "smi_join_create: max_chunk=%d at up/down = %d/%d gives pieces of %lld samples, above %d", max_chunk, up,
+              down, outs, RS_MAX_SAMPLES);
+  char arch[128];
+  const int rc = smi_device_check(arch, sizeof(arch));
+  if (rc) return rc;
+  smi_join* h = new smi_join();
+  h->max_chunk = max_chunk; h->n_taps = copy ? 1 : n_taps; h->pool = nullptr;
+  JnState& s = h->s;
+  s.max_streams = max_streams; s.overlap = overlap; s.up = up; s.down = down; s.half = half;
+  s.hs = copy ? 0 : (int)((2LL * half + down + up - 1) / up) + 1;
+  h->lds = copy ? 0 : ((size_t)n_taps + (size_t)rs_window(up, down, half)) * sizeof(float);
+  // one allocation: the two fade tables (float64), then the taps, the two tail sets and the two history sets (fp32)
+  const size_t n_tail = 2 * (size_t)max_streams * overlap, n_hist = 2 * (size_t)max_streams * s.hs;
+  const size_t f64 = 2 * (size_t)overlap * sizeof(double);
+  const size_t bytes = f64 + ((size_t)h->n_taps + n_tail + n_hist) * sizeof(float);
+  if (hipMalloc((void**)&h->pool, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    delete h;
+    smi_set_error("smi_join_create: device allocation of %zu bytes of stream state failed", bytes);
+    return SMI_ENOMEM;
+  }
+  double* fd = (double*)h->pool;
+  float* ff = (float*)(h->pool + f64);
+  s.fade_in = fd; s.fade_out = fd + overlap;
+  s.taps = ff; s.tail = ff + h->n_taps; s.hist = s.tail + n_tail;
+  std::vector<float> t((size_t)h->n_taps, 0.f);
+  if (!copy)
+    for (int i = 0; i < n_taps; ++i) t[i] = (float)taps_host[i];
+  hipError_t e = hipMemset(h->pool, 0, bytes);
+  if (e == hipSuccess && overlap) e = hipMemcpy(fd, fade_in_host, (size_t)overlap * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && overlap) e = hipMemcpy(fd + overlap, fade_out_host, (size_t)overlap * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ff, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    smi_set_error("smi_join_create: upload of the fade tables and taps: %s", hipGetErrorString(e));
+    (void)hipFree(h->pool);
+    delete h;
+    return SMI_EHIP;
+  }
+  h->streams.assign((size_t)max_streams, JnStream{});
+  *out = h;
+  return SMI_OK;
+}
+
+int smi_join_destroy(smi_join* h) {
+  if (!h) return SMI_OK;
+  if (h->pool) (void)hipFree(h->pool);
+  delete h;
+  return SMI_OK;
+}
+
+int smi_join_open(smi_join* h, int stream) {
+  SMI_REQUIRE(h, "smi_join_open: null handle");
+  SMI_REQUIRE(stream >= 0 && stream < h->s.max_streams, "smi_join_open: stream=%d outside 0..%d", stream, h->s.max_streams - 1);
+  JnStream& st = h->streams[(size_t)stream];
+  st.open = 1; st.chunks = 0; st.n = 0; st.k = 0;   // (st.set goes on alternating: a first chunk reads no state)
+  return SMI_OK;
+}
+
+int smi_join_push_rows(smi_join* h, const float* chunks_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                       const int32_t* last_host, int B, float* out_dev, long long out_stride, int32_t* n_out_host, void* stream) {
+  SMI_REQUIRE(h && chunks_dev && stream_host && len_host && last_host && out_dev, "smi_join_push_rows: null argument");
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "smi_join_push_rows: B=%d outside 1..%d", B, RS_MAX_ROWS);
+  SMI_REQUIRE(stride >= 1, "smi_join_push_rows: stride=%lld must be positive", stride);
+  const JnState& s = h->s;
+  JnArgs A;
+  long long n_new[RS_MAX_ROWS], k_new[RS_MAX_ROWS], need = 1;
+  for (int b = 0; b < B; ++b) {
+    const int id = stream_host[b];
+    SMI_REQUIRE(id >= 0 && id < s.max_streams, "smi_join_push_rows: stream[%d]=%d outside 0..%d", b, id, s.max_streams - 1);
+    for (int c = 0; c < b; ++c)
+      SMI_REQUIRE(stream_host[c] != id, "smi_join_push_rows: stream[%d]=%d is row %d's stream too (one chunk of a stream a call)", b, id, c);
+    const JnStream& st = h->streams[(size_t)id];
+    SMI_REQUIRE(st.open, "smi_join_push_rows: stream[%d]=%d is not open (smi_join_open; a stream closes with its last chunk)", b, id);
+    const int len = len_host[b], last = last_host[b];
+    SMI_REQUIRE(last == 0 || last == 1, "smi_join_push_rows: last[%d]=%d is neither 0 nor 1", b, last);
+    SMI_REQUIRE(len >= 0 && len <= h->max_chunk && len <= stride, "smi_join_push_rows: len[%d]=%d outside 0..min(max_chunk=%d, stride=%lld)", b,
+                len, h->max_chunk, stride);
+    SMI_REQUIRE(last || len >= 2LL * s.overlap, "smi_join_push_rows: len[%d]=%d of a chunk that is not the last is below 2 * overlap = %d", b,
+                len, 2 * s.overlap);
+    SMI_REQUIRE(!last || st.chunks == 0 || len >= s.overlap, "smi_join_push_rows: len[%d]=%d of a last chunk is below overlap = %d", b, len,
+                s.overlap);
+    const long long piece = smi_join_piece_len(s.overlap, s.up, s.down, 2 * s.half + 1, st.chunks == 0, st.n, st.k, len, last, &n_new[b], &k_new[b]);
+    SMI_REQUIRE(piece >= 0, "smi_join_push_rows: len[%d]=%d gives no valid piece", b, len);
+    SMI_REQUIRE(n_new[b] * s.up < (1LL << 31) && (k_new[b] + 1) * s.down < (1LL << 31),
+                "smi_join_push_rows: stream[%d]=%d would reach N * up = %lld, K * down = %lld: 2^31 is the limit of a stream", b, id,
+                n_new[b] * s.up, k_new[b] * s.down);
+    if (piece > 0 && s.hs > 0) {   // the first output's window starts inside the history
+      const long long a0 = st.k * s.down - s.half;
+      const long long jlo = a0 <= 0 ? 0 : (a0 + s.up - 1) / s.up;
+      SMI_REQUIRE(jlo >= st.n - s.hs, "smi_join_push_rows: stream[%d]=%d needs %lld samples of history, the handle keeps %d", b, id,
+                  st.n - jlo, s.hs);
+    }
+    JnRow& r = A.r[b];
+    r.slot = id; r.set = st.set; r.len = len; r.n_fade = st.chunks ? s.overlap : 0;
+    r.n_old = (int32_t)st.n; r.n_new = (int32_t)n_new[b]; r.k_old = (int32_t)st.k; r.k_new = (int32_t)k_new[b];
+    r.keep = last ? 0 : 1;
+    if (piece > need) need = piece;
+  }
+  SMI_REQUIRE(out_stride >= need && out_stride <= RS_MAX_SAMPLES, "smi_join_push_rows: out_stride=%lld outside %lld (the longest piece)..%d",
+              out_stride, need, RS_MAX_SAMPLES);
+  for (int b = 0; b < B; ++b) {
+    JnStream& st = h->streams[(size_t)stream_host[b]];
+    if (n_out_host) n_out_host[b] = (int32_t)(k_new[b] - st.k);
+    st.n = n_new[b]; st.k = k_new[b]; st.chunks += 1; st.set ^= 1;
+    if (last_host[b]) st.open = 0;
+  }
+  const int tiles = (int)((out_stride + RS_TILE - 1) / RS_TILE);
+  hipLaunchKernelGGL(k_join_rows, dim3(tiles, B), dim3(RS_BLOCK), h->lds, (hipStream_t)stream, A, h->s, chunks_dev, stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
   return SMI_OK;
 }
 

@@ -224,6 +224,13 @@ SYMBOLS = {
     "smi_rs_resample_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, C.c_longlong, _VP]),
     "smi_rs_prompt_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _I, _VP, C.c_longlong,
                                 _P(C.c_int32), _VP, C.c_longlong, _VP, _P(C.c_int32), _VP]),
+    "smi_join_create": (_I, [_I, _I, _I, _P(C.c_double), _P(C.c_double), _I, _I, _P(C.c_double), _I, _P(_VP)]),
+    "smi_join_destroy": (_I, [_VP]),
+    "smi_join_open": (_I, [_VP, _I]),
+    "smi_join_push_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, C.c_longlong,
+                                _P(C.c_int32), _VP]),
+    "smi_join_piece_len": (C.c_longlong, [_I, _I, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _I, _P(C.c_longlong),
+                                          _P(C.c_longlong)]),
 }
 
 # include/sparkmi_debug.h: exported by libsparkmi_diag.so only

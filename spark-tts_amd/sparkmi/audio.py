@@ -5,6 +5,9 @@ buffers ``smi_enc_forward_rows`` reads.  The same resampler brings the vocoder's
 The device path follows ``resample_poly`` (the host path's resampler, ``encoder.load_audio``), not the reference's soxr VHQ, and
 it works in fp32 where the host works in float64: its 16 kHz samples differ from the host path's by fp32 rounding, so prompt ids
 may differ between the two at near-ties.  Nothing here imports scipy: the taps are computed with numpy alone.
+
+``StreamJoiner`` (``smi_join_*``) is the streaming form of that output end: overlapping chunks in, contiguous pieces out,
+cross-faded and resampled with the state kept across chunk edges on the device.
 """
 from __future__ import annotations
 
@@ -156,3 +159,132 @@ class DeviceAudio:
                         "smi_rs_prompt_rows")
         assert list(got) == n_out, (list(got), n_out)
         return wav, ref, gain, n_out
+
+
+class StreamJoiner:
+    """Owns one ``smi_join`` handle (include/sparkmi.h): the overlapping chunks of streamed requests become contiguous, playable
+    pieces on the device, cross-faded over ``overlap`` samples and, with ``up/down`` other than 1/1, resampled with the filter's
+    state kept across chunk edges.  Request keys map to the handle's stream slots: ``open(key)`` takes a free slot, ``push``
+    sends one poll's ready chunks, and a key's slot is free again after its last push.  ``max_streams`` slots suffice for a
+    caller that never has more than that many requests between their ``open`` and their last ``push`` -- ``serve_stream`` sizes
+    it as max(max_open, max_batch), the requests that can be admitted and unfinished at once.  All pushes go to the current HIP
+    stream at the time of the call: keep them on one stream.  ``lib``: a stand-in library (tests watch the bookkeeping)."""
+
+    def __init__(self, max_streams: int, max_chunk: int, overlap: int, up: int = 1, down: int = 1, device="cuda:0",
+                 diag: bool = False, lib=None):
+        from .streaming import join_history
+        self._lib = lib if lib is not None else _lib.pick(diag)
+        self._fake = lib is not None
+        self.device = device
+        if not self._fake:
+            import torch
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise _lib.SparkMIError("StreamJoiner runs on an MI355X only (device must be cuda:N); there is no CPU path")
+        self.max_streams, self.max_chunk, self.overlap = int(max_streams), int(max_chunk), int(overlap)
+        self.up, self.down = int(up), int(down)
+        if math.gcd(self.up, self.down) != 1:
+            raise ValueError(f"up/down = {up}/{down} must be in lowest terms")
+        copy = self.up == 1 and self.down == 1
+        taps = np.zeros(1) if copy else np.ascontiguousarray(resample_taps(self.up, self.down), dtype=np.float64)
+        self.half = 0 if copy else taps.size // 2
+        self.history = join_history(self.up, self.down, self.half)
+        fi = np.ascontiguousarray(np.linspace(0, 1, self.overlap), dtype=np.float64)
+        fo = np.ascontiguousarray(np.linspace(1, 0, self.overlap), dtype=np.float64)
+        pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))   # noqa: E731
+        self._h = C.c_void_p()
+        self._lib.check(self._lib.smi_join_create(self.max_streams, self.max_chunk, self.overlap, pd(fi), pd(fo), self.up, self.down,
+                                                  pd(taps), 1 if copy else int(taps.size), C.byref(self._h)), "smi_join_create")
+        self._free: List[int] = list(range(self.max_streams))   # (open() hands out the lowest free slot)
+        self._open: dict = {}       # key -> [slot, chunks pushed, N, K]
+        self.calls = 0              # smi_join_push_rows calls so far: one launch each
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.smi_join_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """forget every open key (an abandoned stream's slots come back)"""
+        self._free = list(range(self.max_streams))
+        self._open = {}
+
+    def slot(self, key) -> Optional[int]:
+        return self._open[key][0] if key in self._open else None
+
+    def open(self, key) -> int:
+        if key in self._open:
+            raise ValueError(f"request {key}: already open")
+        if not self._free:
+            raise ValueError(f"StreamJoiner: all {self.max_streams} stream slots are in use")
+        s = min(self._free)
+        self._free.remove(s)
+        self._lib.check(self._lib.smi_join_open(self._h, s), "smi_join_open")
+        self._open[key] = [s, 0, 0, 0]
+        return s
+
+    def piece_lengths(self, rows: Sequence[Tuple]) -> List[int]:
+        """the piece lengths ``push(x, rows)`` would return, without pushing (pure host arithmetic)"""
+        from .streaming import join_piece_len
+        state = {k: list(v) for k, v in self._open.items()}
+        out = []
+        for key, length, last in rows:
+            st = state.setdefault(key, [None, 0, 0, 0])
+            piece, st[2], st[3] = join_piece_len(self.overlap, self.up, self.down, self.half, st[1] == 0, st[2], st[3], length, last)
+            st[1] += 1
+            out.append(piece)
+        return out
+
+    def push(self, x, rows: Sequence[Tuple]):
+        """``x``: [B][stride] float32 on the device, row b the ready chunk of request ``rows[b] = (key, length, last)``; a key not
+        open yet is opened.  Returns (out [B][out_stride] float32 on the device -- row b holds its piece, then zeros --, the
+        pieces' lengths); a length may be 0.  A request that appears twice (its last full chunk and its flush) makes two device
+        calls (``streaming.split_calls``), each one launch; everything is enqueued on the current stream and nothing waits."""
+        from .streaming import join_piece_len, split_calls
+        B = len(rows)
+        if not B:
+            raise ValueError("push takes at least one row")
+        if not self._fake:
+            import torch
+            if x.dim() != 2 or x.shape[0] != B or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+                raise ValueError("push takes a contiguous [B][stride] float32 tensor on the device, one row per chunk")
+        want = self.piece_lengths(rows)      # raises for a bad length before anything is opened or pushed
+        for key, _, _ in rows:
+            if key not in self._open:
+                self.open(key)
+        stride = max(1, max(want))
+        in_stride = 1 if self._fake else int(x.shape[1])
+        out = None
+        if not self._fake:
+            out = torch.empty((B, stride), dtype=torch.float32, device=self.device)
+        got_all: List[int] = []
+        for a, b in split_calls([r[0] for r in rows]):
+            n = b - a
+            i32 = lambda v: (C.c_int32 * n)(*[int(t) for t in v])   # noqa: E731
+            got = (C.c_int32 * n)()
+            src = C.c_void_p(0 if self._fake else x.data_ptr() + 4 * a * in_stride)
+            dst = C.c_void_p(0 if self._fake else out.data_ptr() + 4 * a * stride)
+            self._lib.check(self._lib.smi_join_push_rows(self._h, src, in_stride, i32(self._open[r[0]][0] for r in rows[a:b]),
+                                                         i32(r[1] for r in rows[a:b]), i32(bool(r[2]) for r in rows[a:b]), n, dst, stride,
+                                                         got, None if self._fake else self._stream()), "smi_join_push_rows")
+            self.calls += 1
+            got_all += list(got)
+            for key, length, last in rows[a:b]:
+                st = self._open[key]
+                _, st[2], st[3] = join_piece_len(self.overlap, self.up, self.down, self.half, st[1] == 0, st[2], st[3], length, last)
+                st[1] += 1
+                if last:
+                    self._free.append(self._open.pop(key)[0])
+        if not self._fake:
+            assert got_all == want, (got_all, want)
+        return out, want
+
+    def _stream(self) -> C.c_void_p:
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

@@ -7,7 +7,8 @@ kernels: ``self.model.generate`` (``SparkLLM``) and ``self.audio_tokenizer.detok
 (``BiCodecTokenizer``).  Keyword-only additions: ``do_sample``, ``max_new_tokens``,
 ``prompt_tokens`` (pre-computed prompt audio tokens), ``inference_batch``,
 ``inference_stream`` (chunked vocoding while the LLM generates, the reference's decoupled Triton mode), ``serve`` (in-flight
-batching) and ``serve_stream`` (both at once: chunked audio for every live request of an in-flight batch).
+batching) and ``serve_stream`` (both at once: chunked audio for every live request of an in-flight batch); the two streaming
+calls take ``joined=True`` for contiguous, playable pieces at any output rate (the chunks joined on the device).
 """
 from __future__ import annotations
 
@@ -293,8 +294,30 @@ class SparkTTS:
     @staticmethod
     def _no_stream_rate(output_sample_rate: Optional[int], who: str) -> None:
         if output_sample_rate is not None:
-            raise ValueError(f"{who}: output_sample_rate is not supported for streamed chunks (the resampler keeps no filter "
-                             "state across chunk edges); resample the joined waveform, or use inference / inference_batch")
+            raise ValueError(f"{who}: output_sample_rate is not supported for overlapping chunks (a chunk alone has no filter "
+                             "state across its edges); pass joined=True for contiguous pieces at that rate, or use inference / "
+                             "inference_batch")
+
+    def _stream_joiner(self, who: str, output_sample_rate: Optional[int], max_streams: int, audio_chunk_duration: float,
+                       max_audio_chunk_duration: float, audio_chunk_size_scale_factor: float, audio_chunk_overlap_duration: float):
+        """The ``StreamJoiner`` of a ``joined=True`` call, its slots all free.  Everything is checked before any device call:
+        the rate, the scheduler's arguments, and that the first chunk holds two overlaps (every later chunk that is not a
+        request's last is at least as long, and a last chunk may be as short as one overlap)."""
+        from .audio import StreamJoiner
+        up, down = self._output_ratio(output_sample_rate) or (1, 1)
+        hop = self.audio_tokenizer.model.hop
+        sched = ChunkScheduler(audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor,
+                               audio_chunk_overlap_duration, self.sample_rate // hop)
+        if 2 * sched.overlap > sched.chunk_size:
+            raise ValueError(f"{who}: joined=True needs a first chunk of at least two overlaps: audio_chunk_duration gives "
+                             f"{sched.chunk_size} frames, audio_chunk_overlap_duration {sched.overlap}")
+        key = (int(max_streams), max(sched.chunk_size, sched.max_chunk_size) * hop, sched.overlap * hop, up, down)
+        if getattr(self, "_joiners", None) is None:
+            self._joiners = {}
+        if key not in self._joiners:
+            self._joiners[key] = StreamJoiner(*key, device=self.device)
+        self._joiners[key].reset()
+        return self._joiners[key]
 
     def _device_audio(self):
         if getattr(self, "_audio", None) is None:
@@ -442,15 +465,27 @@ class SparkTTS:
                          prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                          audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
                          audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
-                         decode_stride: int = 10, output_sample_rate: Optional[int] = None) -> Iterator[np.ndarray]:
+                         decode_stride: int = 10, output_sample_rate: Optional[int] = None,
+                         joined: bool = False) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
         (client_grpc.py:390-415).  Every chunk is the vocoder's output for that chunk's tokens alone.
         ``decode_stride`` = decode steps enqueued between host checks for new tokens.  The chunks are at ``sample_rate``:
-        ``output_sample_rate`` is refused here (ValueError) -- a resampled chunk would need the filter's state across the
-        chunk edges, which the device resampler does not keep yet."""
-        self._no_stream_rate(output_sample_rate, "inference_stream")
+        with ``joined=False`` a given ``output_sample_rate`` is refused (ValueError) -- a resampled chunk would need the
+        filter's state across the chunk edges.
+
+        ``joined=True``: yields contiguous, playable float32 pieces instead -- a listener plays them one after the other.
+        The chunks are cross-faded on the device (include/sparkmi.h, smi_join_*; ``audio.StreamJoiner``): the pieces'
+        concatenation is ``crossfade`` of the chunks cast to float32, bit for bit, ``semantic tokens * hop`` samples in
+        all.  ``output_sample_rate`` is then accepted (None or ``sample_rate``: the model's rate): the pieces'
+        concatenation is, bit for bit, what ``inference_batch(output_sample_rate=...)``'s resampler gives for that joined
+        waveform, the filter's state being kept across the chunk edges; a piece that would be empty is not yielded.
+        Refused (ValueError, before any device call) if the first chunk is shorter than two overlaps."""
+        if not joined:
+            self._no_stream_rate(output_sample_rate, "inference_stream")
+        joiner = self._stream_joiner("inference_stream", output_sample_rate, 1, audio_chunk_duration, max_audio_chunk_duration,
+                                     audio_chunk_size_scale_factor, audio_chunk_overlap_duration) if joined else None
         if gender is not None:
             prompt, glob = self.process_prompt_control(gender, pitch, speed, text), None
         else:
@@ -472,6 +507,15 @@ class SparkTTS:
             wav = voc.detokenize(torch.tensor([chunk], dtype=torch.long), glob.reshape(1, 1, -1), lengths=[len(chunk)])
             return wav.reshape(-1)[: len(chunk) * hop].cpu().numpy().copy()
 
+        def piece(chunk: List[int], last: bool) -> np.ndarray:   # the chunk's share of the joined stream; only that crosses to the host
+            if chunk:
+                wav = voc.detokenize(torch.tensor([chunk], dtype=torch.long), glob.reshape(1, 1, -1), lengths=[len(chunk)]).reshape(1, -1)
+            else:
+                wav = torch.zeros((1, 1), dtype=torch.float32, device=self.device)
+            out, lens = joiner.push(wav, [(0, len(chunk) * hop, last)])
+            return out[0, : lens[0]].cpu().numpy().copy()
+
+        pushed = 0
         while True:
             toks = self.model.tokens(max_new_tokens)[0]
             sem, gl = self._parse(toks)
@@ -482,9 +526,18 @@ class SparkTTS:
             done = produced >= max_new_tokens or self.model.all_done()
             if done:
                 pending += sched.flush()
-            if glob is not None:
+            if glob is not None and joiner is None:
                 for chunk in pending:
                     yield vocode(chunk)
+                pending = []
+            elif glob is not None:
+                if done and pushed + len(pending) > 0 and not pending:
+                    pending = [[]]                      # nothing left to flush: an empty last chunk empties the resampler
+                for ci, chunk in enumerate(pending):
+                    w = piece(chunk, done and ci == len(pending) - 1)
+                    pushed += 1
+                    if w.size:
+                        yield w
                 pending = []
             if done:
                 break
@@ -593,7 +646,7 @@ class SparkTTS:
                      audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
                      audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
                      max_open: Optional[int] = None, max_ahead: Optional[float] = None, resume_ahead: Optional[float] = None,
-                     clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None):
+                     clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None, joined: bool = False):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -620,8 +673,25 @@ class SparkTTS:
         sequence comes back with every bit of its state, whatever the schedule did to it, greedy and sampled with any seed
         alike.  ``pacer``: a ``Pacer`` of the caller's, built for this ``max_batch``, in place of the four keywords (ValueError if
         both are given); its ``parks`` / ``resumes`` then tell the caller what the schedule did.  Nothing of a call is kept on
-        ``self``.  The chunks are at ``sample_rate``: ``output_sample_rate`` is refused (ValueError), as in ``inference_stream``."""
-        self._no_stream_rate(output_sample_rate, "serve_stream")
+        ``self``.  The chunks are at ``sample_rate``: with ``joined=False`` a given ``output_sample_rate`` is refused (ValueError),
+        as in ``inference_stream``.
+
+        ``joined=True``: yields ``(index, piece, last)`` with contiguous, playable float32 pieces -- a listener plays a request's
+        pieces one after the other; a piece may be empty, and ``last`` is on exactly one piece of a request.  The vocoder's rows
+        stay on the device: the join (include/sparkmi.h, smi_join_*; ``audio.StreamJoiner``) runs on the vocoder's own stream
+        right behind ``detokenize_rows``, one launch per poll (two in a poll in which a request has both its last full chunk
+        and its flush ready), and only the pieces cross to the host -- the overlaps no longer travel.  Per request the pieces'
+        concatenation is ``crossfade`` of its ``joined=False`` chunks cast to float32, bit for bit (``semantic tokens * hop``
+        samples); with ``output_sample_rate`` (accepted here; None or ``sample_rate``: the model's rate) it is, bit for bit,
+        what ``inference_batch``'s resampler gives for that joined waveform, whoever else is live, with or without parking.
+        The joiner's state is keyed by request, not by KV slot, so park and resume do not touch it; it has
+        max(``max_open``, ``max_batch``) stream slots -- the requests that can be admitted and not yet through their last
+        chunk at once, since a request's last chunk is pushed in the poll that retires it -- so the slots cannot run out.  The
+        ``Pacer`` counts frames yielded as without it.  (The joiner's handle stays on ``self`` for the next call with the same
+        sizes and rate; its slots are all freed when a call begins, so nothing of a request outlives its call.)  Refused
+        (ValueError, before any device call) if the first chunk is shorter than two overlaps."""
+        if not joined:
+            self._no_stream_rate(output_sample_rate, "serve_stream")
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
@@ -653,6 +723,8 @@ class SparkTTS:
                         audio_chunk_duration=audio_chunk_duration, max_audio_chunk_duration=max_audio_chunk_duration,
                         audio_chunk_size_scale_factor=audio_chunk_size_scale_factor,
                         audio_chunk_overlap_duration=audio_chunk_overlap_duration)
+        joiner = self._stream_joiner("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), audio_chunk_duration,
+                                     max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration) if joined else None
         if getattr(self, "_voc_stream", None) is None:
             self._voc_stream = torch.cuda.Stream(device=self.device)
         vs = self._voc_stream
@@ -683,9 +755,32 @@ class SparkTTS:
                 glob_t = torch.tensor([mux.global_ids(c[0]) for c in rows], dtype=torch.long).unsqueeze(1)
                 with torch.cuda.stream(vs):
                     wav = voc.detokenize_rows(sem_t, glob_t, lengths=lens)
+            if joiner is not None:   # the join, right behind the vocoder on its stream: the rows never leave the device
+                with torch.cuda.stream(vs):
+                    x = wav.squeeze(1) if wav is not None else torch.zeros((len(chunks), 1), dtype=torch.float32, device=self.device)
+                    if wav is not None and len(rows) != len(chunks):   # an empty last chunk gets a row of its own (zero overlap only)
+                        at = iter(range(len(rows)))
+                        idx = torch.tensor([next(at) if c[2] else len(rows) for c in chunks], device=self.device)
+                        x = torch.cat([x, torch.zeros((1, x.shape[1]), dtype=torch.float32, device=self.device)])[idx].contiguous()
+                    out, n_out = joiner.push(x, [(c[0], len(c[2]) * hop, c[3]) for c in chunks])
+                return chunks, (x, out, n_out)
             return chunks, wav
 
+        def collect_joined(job):
+            chunks, (_, out, n_out) = job
+            with torch.cuda.stream(vs):
+                out = out.cpu().numpy()
+            for b, (key, index, sem, last) in enumerate(chunks):
+                if pacer.active:
+                    pacer.yielded(key, max(0, len(sem) - (overlap if index else 0)))
+                    if last:
+                        pacer.close(key)
+                yield key, out[b, : n_out[b]].copy(), last
+
         def collect(job):     # the host waits for the vocoder's stream only
+            if joiner is not None:
+                yield from collect_joined(job)
+                return
             chunks, wav = job
             if wav is not None:
                 with torch.cuda.stream(vs):

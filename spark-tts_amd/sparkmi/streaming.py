@@ -10,7 +10,8 @@ cross-fades consecutive chunks over the overlap (``runtime/triton_trtllm/client_
 ``ChunkScheduler`` is the pure host logic (no GPU), ``crossfade`` the client-side reconstruction;
 ``SparkTTS.inference_stream`` (pipeline.py) drives the HIP LLM and vocoder with them.  ``StreamMux`` is the same logic for many
 requests at once -- the decoupled chunk loop answering every live request of an in-flight batch (run.sh:49-65) -- and
-``SparkTTS.serve_stream`` drives it.
+``SparkTTS.serve_stream`` drives it.  ``join_piece_len``, ``join_history`` and ``split_calls`` are the host arithmetic of the
+device-side stream joiner (``joined=True``; include/sparkmi.h, smi_join_*), which does on the device what ``crossfade`` does here.
 """
 from __future__ import annotations
 
@@ -72,6 +73,54 @@ def crossfade(chunks: Sequence[np.ndarray], overlap_samples: int) -> np.ndarray:
         out.append(chunks[i][n:-n])
     out.append(chunks[-1][-n:])
     return np.concatenate(out)
+
+
+# ---- joined streaming (include/sparkmi.h, smi_join_*): the host arithmetic of the device-side stream joiner, no torch
+JOIN_MAX_ROWS = 64     # rows of one smi_join_push_rows call
+
+
+def join_history(up: int, down: int, half: int) -> int:
+    """input samples of history a stream keeps for taps h[0 .. 2 half]: ceil((2H + down) / up) + 1 (0 for up = down = 1)"""
+    if up == 1 and down == 1:
+        return 0
+    return -((-(2 * int(half) + int(down))) // int(up)) + 1
+
+
+def join_piece_len(overlap: int, up: int, down: int, half: int, first: bool, n_before: int, k_before: int, length: int,
+                   last: bool) -> Tuple[int, int, int]:
+    """(piece length, N after, K after) of one push -- the twin of ``smi_join_piece_len``: a stream with ``n_before`` joined
+    samples and ``k_before`` emitted outputs takes a chunk of ``length`` samples.  A chunk that is not the last needs
+    ``length >= 2 overlap``, a last chunk that is not the first ``length >= overlap`` (ValueError).  The joined stream grows by
+    ``length`` (last) or ``length - overlap`` (the tail is held back for the next fade); a stream that goes on has emitted
+    ``max(0, ceil((N up - H) / down))`` outputs, a finished one ``ceil(N up / down)``; at 1/1 the piece is the joined samples."""
+    overlap, up, down, half, length = int(overlap), int(up), int(down), int(half), int(length)
+    if not last and length < 2 * overlap:
+        raise ValueError(f"a chunk of {length} samples that is not the last is shorter than 2 * overlap = {2 * overlap}")
+    if last and not first and length < overlap:
+        raise ValueError(f"a last chunk of {length} samples is shorter than the overlap of {overlap}")
+    n = int(n_before) + length - (0 if last else overlap)
+    if up == 1 and down == 1:
+        k = n
+    elif last:
+        k = -((-n * up) // down)
+    else:
+        k = max(0, -((-(n * up - half)) // down))
+    return k - int(k_before), n, k
+
+
+def split_calls(keys: Sequence[Hashable], max_rows: int = JOIN_MAX_ROWS) -> List[Tuple[int, int]]:
+    """One poll's ready chunks, in order, as row ranges [(start, stop)] of joiner calls: a request appears at most once in a
+    call (it can have two chunks ready in one poll, its last full chunk and its flush), a call has at most ``max_rows`` rows,
+    and the order of a request's chunks is kept because the ranges are consecutive."""
+    out, start, seen = [], 0, set()
+    for i, k in enumerate(keys):
+        if k in seen or i - start >= max_rows:
+            out.append((start, i))
+            start, seen = i, set()
+        seen.add(k)
+    if len(keys) > start:
+        out.append((start, len(keys)))
+    return out
 
 
 def stream_chunks(token_iter: Iterator[Sequence[int]], scheduler: ChunkScheduler) -> Iterator[List[int]]:
