@@ -94,6 +94,36 @@ int smi_llm_debug_layer(smi_llm* h, int layer, int M, const int32_t* rows_host, 
 enum { SMI_PF_GROUPED = 1, SMI_PF_PGEMM = 2 };
 int smi_llm_debug_prefill_layer(smi_llm* h, int layer, int stage, int n_seq, const int32_t* seq_host, const float* hidden_host, int family);
 int smi_llm_pf_tiles(const int32_t* rows_host, int M, int32_t* out, int cap, int32_t* n);
+/* Which kernel form each GEMM of a layer and the lm_head start with (tests/test_gemm_forms_cpu.py): host only, no
+ * GPU call -- the pick functions the launch sites themselves call, on plain values.
+ *   cfg, M: the model shape and the row count (a decode step: 1 .. 64; a prompt pass's row group: 1 .. 4096).
+ *   layer_pos: first, middle or last layer (the last layer's down_proj has no next layer to prefetch for).
+ *   flags: the switches a pick reads; -1 in a field = what smi_llm_create leaves there when no SPARKMI_* switch is set (fused:
+ *     then 1 at one decode row of a shape that has the fused o_proj); null = every field so.
+ *   out[5]: QKV, o_proj, gate_up, down_proj, lm_head.  kernel: the instantiation by name, template arguments as numbers in the
+ *     kernel's own order ("k_gemm<1,1,16,2,1,1,2,0,1,1,2,16>"; a pair: "k_downC<10,1>+k_resid_comb<0,0>"), empty with launches = 0
+ *     where nothing is launched (o_proj done by the attention kernel); grid (x, y) in blocks, block in threads and dynamic LDS
+ *     bytes of the (first) kernel; grid2: blocks of 64 threads of the k_resid_comb of a pair; launches: kernels started (2 for a
+ *     pair, one pass per 32 rows for the persistent lm_head above 16 rows). */
+typedef struct smi_gemm_flags {
+  int32_t pass;            /* 0: decode rows; SMI_PF_GROUPED / SMI_PF_PGEMM: a prompt pass's row group, every kernel in that family */
+  int32_t fused;           /* decode: 1 = one row with the fused o_proj in effect, 2 = its 2 .. 8-row form (SPARKMI_FUSE2_ROWS), 0 = neither */
+  int32_t stamps;          /* in-kernel phase stamps on (smi_llm_debug_stamps) */
+  int32_t exact;           /* exact-weights mode (smi_llm_cfg.weights_exact) */
+  int32_t tune2;           /* SPARKMI_TUNE2 bits */
+  int32_t prefetch_mask, prefetch_rows;   /* helper-block prefetch: producer bits (1 QKV, 4 down_proj) and the row bound */
+  int32_t kv_f32;          /* cache type (smi_llm_cfg.kv_dtype) */
+  int32_t pg_split_rows;   /* SPARKMI_PG_SPLIT_ROWS */
+  int32_t lm_restricted;   /* every row constrained: the restricted lm_head */
+  int32_t lm_blocks;       /* blocks of the persistent lm_head */
+} smi_gemm_flags;
+typedef struct smi_gemm_form_info {
+  char kernel[96];
+  int32_t grid[2], block, launches, grid2;
+  int64_t lds_bytes;
+} smi_gemm_form_info;
+enum { SMI_LAYER_FIRST = 0, SMI_LAYER_MIDDLE = 1, SMI_LAYER_LAST = 2 };
+int smi_llm_gemm_forms(const smi_llm_cfg* cfg, int M, int layer_pos, const smi_gemm_flags* flags, smi_gemm_form_info* out);
 /* Diagnostics: the raw stamp buffer (u64 s_memrealtime ticks, 10 ns) after smi_llm_debug_stamps; n entries. */
 int smi_llm_debug_raw_stamps(smi_llm* h, unsigned long long* out, int n);
 /* Tests: the sampler alone (k_sample_scan + k_sample, through launch_sampler, the one function a decode step too starts them

@@ -13,7 +13,7 @@ struct EngGeom {
 inline EngGeom eng_geom(int H, int Q, int KV, int I, int n_heads) {
   EngGeom g;
   memset(&g, 0, sizeof(g));
-  const int NWo = (n_heads == 14 || n_heads == 4) ? n_heads : 8;   // launch_oproj's wave count
+  const int NWo = (n_heads == 14 || n_heads == 4) ? n_heads : 8;   // the o_proj forms' wave count (pick_o)
   const int KT[4] = {H / 32, Q / 32, H / 32, I / 32}, NW[4] = {16, NWo, 8, 16};
   const int np[4] = {(Q + 2 * KV) / 4, H / 4, 2 * I / 4, H / 4};
   for (int ph = 0; ph < 4; ++ph) {

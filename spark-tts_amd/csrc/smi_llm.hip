@@ -4084,147 +4084,370 @@ void graphs_flush(smi_llm* L) {
 // k_lm32, 16384 the register-staged k_pgemm in place of the ring forms, 1048576 / 2097152 k_gemm<.., H = 4> in place of k_down1 / k_downS
 constexpr int kTune2Lm2 = 8192, kTune2PgemmRegs = 16384, kTune2GemmDown1 = 1048576, kTune2GemmDownS = 2097152;
 // Fixed choices of the launch path
-constexpr int kPgSplitRows = 512;        // passes of up to this many rows run o_proj / down_proj in k_pgemm's split-K form
 // A sequence's prompt rows take the kernel family ITS OWN length selects (never the call's total): up to kMaxRows rows the
 // decode kernels in chunks, from kPfLong rows the prefill-GEMM family (k_pgemm + k_attn_pf2), in between (empty: kPfLong =
 // kMaxRows + 1) the row-grouped decode GEMMs -- so its K/V rows, and with a bf16 cache its tokens, do not depend on what else is in the call.
 constexpr int kPfLong = kMaxRows + 1;    // prompt rows (len - 1) from which a sequence's prompt runs through the prefill-GEMM family
-// rows from which down_proj runs chain-split (k_downC): graph step at 0.5B, same box (profiles/r04_batch_ab.txt): 4 rows 641 (k_downS) vs
-// 692 us (chains), 8 rows 728 vs 713, 16 rows 790 (k_gemm<.., H = 4>) vs 744, 32 rows 892 vs 859
-// (5 / 6 rows: 731 / 728 us with the chains, the same as k_downS within noise -- the chains take over from 7)
-constexpr int kDcMin = 7;
-constexpr int kGu1Lo = 4;                // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile (launch_gemm)
-constexpr int kGu1Rows = 32;             // rows up to which gate_up runs its one-batch, three-tile shape (launch_gemm)
 // Decode steps captured per graph replay: a step needs nothing from the host, so K of them are captured back to back into one
 // graph.  One replay boundary costs ~5 us that a kernel boundary inside a graph does not: graph step at one row 548.6 -> 544.5 us
 // (K = 4 .. 25 alike; profiles/r03_graph_steps.txt).
 constexpr int kGraphSteps = 8;
 constexpr int kPgSegO = 2, kPgSegD = 8;  // K segments of the prefill o_proj / down_proj sums (fixed: part of the association)
+enum { PF_GROUPED = 1, PF_PGEMM = 2 };   // kernel family of a pass over prompt rows (launch_layers_big)
 
-template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int H = 1, int OCC = 1>
-int launch_gemm_kv(const smi_llm* L, GemmP p, hipStream_t st) {
-  const int work = (p.NT + NTB - 1) / NTB * H;
-  p.work_blocks = work;
-  p.stamps = L->stamps_on ? L->stamps : nullptr;
-  if constexpr (MT == 1 && NTB == 1 && NW == 16 && H == 4 && PRO == PRO_PLAIN && EPI == EPI_RESID) {
-    // one row: four chains per wave, full load instructions (k_down1_hot; same bits).  SPARKMI_TUNE2 bit kTune2GemmDown1 keeps k_gemm (A/B)
-    if (p.M == 1 && !p.stamps && p.KT <= 160 && !(L->tune2 & kTune2GemmDown1)) {
-      const int helpers = (L->prefetch_mask & 4) && p.pf.base && work < 232 ? (256 - work) / 8 * 8 : 0;
-      if (p.KT <= 32) launch_down1_hot<2>(p, work + helpers, st);
-      else if (p.KT <= 96) launch_down1_hot<6>(p, work + helpers, st);
-      else launch_down1_hot<10>(p, work + helpers, st);
-      SMI_LAUNCH_CHECK();
-      return SMI_OK;
-    }
-    if (p.M >= 2 && p.M <= 8 && !p.stamps && p.KT <= 160 && !(L->tune2 & kTune2GemmDownS)) {   // SPARKMI_TUNE2 bit kTune2GemmDownS keeps k_gemm (A/B)
-      const dim3 g(work), b(256);
-      if (p.M <= 4) {
-        if (p.KT <= 32) hipLaunchKernelGGL((k_downS<2, 1>), g, b, 0, st, p);
-        else if (p.KT <= 96) hipLaunchKernelGGL((k_downS<6, 1>), g, b, 0, st, p);
-        else hipLaunchKernelGGL((k_downS<10, 1>), g, b, 0, st, p);
-      } else {
-        if (p.KT <= 32) hipLaunchKernelGGL((k_downS<2, 2>), g, b, 0, st, p);
-        else if (p.KT <= 96) hipLaunchKernelGGL((k_downS<6, 2>), g, b, 0, st, p);
-        else hipLaunchKernelGGL((k_downS<10, 2>), g, b, 0, st, p);
-      }
-      SMI_LAUNCH_CHECK();
-      return SMI_OK;
-    }
-  }
-  // idle CUs warm the L2 of their own XCD for a later kernel (decode with few rows only)
-  const int helpers = ((L->prefetch_mask & (EPI == EPI_QKV ? 1 : 4)) && p.pf.base && p.M <= L->prefetch_rows && work < 232) ? (256 - work) / 8 * 8 : 0;
-  size_t lds = (size_t)NW * NTB * MT * 1024 + 32 * 4 + NTB * 32 * 8;
-  p.ldsb = 0; p.lt_shift = 0;
-  if (MT == 1 && p.M <= 5) {
-    const int tw = (p.KT + NW - 1) / NW;               // k tiles per wave
-    const size_t per_wave = (size_t)tw * 12 * p.M * 16;
-    // (blocks of 14+ waves are alone on their CU anyway: down_proj's ten k tiles per wave then fit up to 3 rows -- 2 rows: down_proj
-    // 8.7 -> 7.3 us, graph step 718 -> 690 us; at 4 rows (123 KB) a tie, so the cap stays below it)
-    if (per_wave * NW <= (size_t)(NW >= 14 ? 96 : 40) * 1024) {
-      p.ldsb = (int)per_wave;
-      int sh = 4;                                       // 16 lanes fetch 12 pieces (M = 1)
-      while ((1 << sh) < 12 * p.M) ++sh;
-      p.lt_shift = sh;
-      lds += per_wave * NW;
-    }
-  }
-  // more than the default dynamic LDS window: the instantiation (QKV: both cache types') was opted in by smi_llm_create (LdsBig)
-  static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 0, H, OCC>>::reg);
-  if constexpr (EPI == EPI_QKV) static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, 1, H, OCC>>::reg);
-  SMI_REQUIRE(lds <= (size_t)kLdsBigBytes, "k_gemm: %zu bytes of LDS", lds);
-  const int groups = (p.M + MT * 16 - 1) / (MT * 16);   // one block row per MT*16 rows (more than one: prefill, or 17..32 rows as 2 x 16)
-  if constexpr (EPI == EPI_LM) SMI_LM_NOTE(L, MT == 2 ? "k_gemm<2,EPI_LM>" : "k_gemm<1,EPI_LM>", work + helpers, groups, NW * 64);
-  constexpr int kLean = (MT == 1 && EPI != EPI_LM) ? 1 : 0;
-  if (kLean && p.ldsb > 0 && !p.stamps && p.M == 1 && p.lt_shift == 4) {
-    if constexpr (PRO == PRO_NORM && EPI == EPI_SWIGLU && H == 1 && MT == 1) {
-      if (p.part_o) {   // one row behind the fused o_proj: the operand is built in the kernel from the per-head partials
-        // the adopted block shape at the two fused head counts starts through the hot entry; the generic head-count form (no
-        // product shape reaches it) keeps the struct entry
-        if constexpr (NW == 8 && U == 2 && WB == 2 && OCC == 6 && NTB == 1) {
-          if (p.n_oheads == 14 || p.n_oheads == 4) {
-            if (p.n_oheads == 14) launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 14>(p, dim3(work + helpers, groups), lds + 1024, st);
-            else launch_gemm_hot<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 4>(p, dim3(work + helpers, groups), lds + 1024, st);
-            SMI_LAUNCH_CHECK();
-            return SMI_OK;
-          }
-        }
-        hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO_FUSEDO, EPI, 0, H, OCC, 2>), dim3(work + helpers, groups), dim3(NW * 64), lds + 1024, st, p);
-        SMI_LAUNCH_CHECK();
-        return SMI_OK;
-      }
-    }
-    if constexpr (PRO == PRO_NORM && EPI == EPI_QKV && kLean && NW == 16 && U == 2 && WB == 1) {   // one-row QKV in its adopted block shape: the hot entry
-      with_kvf32<EPI>(L, [&](auto kv) { launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC>(p, dim3(work + helpers, groups), lds, st); });
-    } else
-      with_kvf32<EPI>(L, [&](auto kv) {
-        hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, 2 * kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
-      });
-  } else if (kLean && p.ldsb > 0 && !p.stamps) {
-    with_kvf32<EPI>(L, [&](auto kv) {
-      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, kLean>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
-    });
-  } else
-    with_kvf32<EPI>(L, [&](auto kv) {
-      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC>), dim3(work + helpers, groups), dim3(NW * 64), lds, st, p);
-    });
-  SMI_LAUNCH_CHECK();
-  return SMI_OK;
+// ------------------------------------------------------------------------------------------
+// Kernel forms of the layer GEMMs (QKV, o_proj, gate_up, down_proj) and lm_head.
+// A form names ONE launch: one kernel instantiation -- or k_downC / the split-K k_pgemm together with its k_resid_comb.  The
+// tables below are the only place a template tuple is written: a row gives the form its id (GF_<id>), its launcher (launch_form)
+// and its name (gemm_form_name).  Which form runs is decided once per kernel by a pick (pick_qkv, pick_o, pick_gu, pick_d,
+// pick_lm): a host function of plain values -- the operand's shape, the row count and the switches (PickEnv) -- that returns the
+// form with its grid, block, dynamic LDS and the fields the kernel splits its work by (GemmPick).  The launch sites (launch_one,
+// launch_layer_big) read "operands, pick, launch"; smi_llm_gemm_forms (sparkmi_debug.h) reports the picks without a GPU, and
+// DESIGN.md 3.4 has the table kernel x rows -> form.
+// ------------------------------------------------------------------------------------------
+// k_gemm / k_gemm_hot:  id | MT, NTB, NW, U, WB, PRO, EPI, H, OCC, LEAN, NOH, hot entry.  KVF32 is no column: the cache's type where
+// the epilogue appends to the cache (EPI_QKV), else 0.  LEAN 1: the operand staged through wave-private LDS (2 .. 5 rows),
+// LEAN 2: that at one row.  NW (the k-tile -> wave map) is fixed per kernel for every row count, so every form of a kernel sums
+// in the same order; only the batch depth U shrinks for two m-tiles (register budget).
+// o_proj: NW = number of heads, so that wave w sums head w's two (head-interleaved) k tiles -- the per-head partial the fused
+// path produces -- and the block's in-order sum over the waves is the fused consumer's in-order sum over the heads; other head
+// counts: no fused path (smi_llm_create leaves fuse_o off), eight waves.
+#define SMI_O_FORMS(X, NW, U) \
+  X(O##NW##_H4_L0, 1, 1, NW, U, 1, PRO_PLAIN, EPI_RESID, 4, 1, 0, kMaxOHeads, 0) \
+  X(O##NW##_H4_L1, 1, 1, NW, U, 1, PRO_PLAIN, EPI_RESID, 4, 1, 1, kMaxOHeads, 0) \
+  X(O##NW##_H4_L2, 1, 1, NW, U, 1, PRO_PLAIN, EPI_RESID, 4, 1, 2, kMaxOHeads, 0) \
+  X(O##NW##_H1, 1, 1, NW, U, 1, PRO_PLAIN, EPI_RESID, 1, 1, 0, kMaxOHeads, 0)
+#define SMI_KGEMM_FORMS(X) \
+  X(QKV_L0, 1, 1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 1, 0, kMaxOHeads, 0)   /* measured best (profiles/README.md) */ \
+  X(QKV_L1, 1, 1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 1, 1, kMaxOHeads, 0) \
+  X(QKV_HOT, 1, 1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 1, 2, kMaxOHeads, 1) \
+  X(QKV_2M, 2, 1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 1, 0, kMaxOHeads, 0)   /* a prompt pass's row group above 16 rows */ \
+  SMI_O_FORMS(X, 14, 2) SMI_O_FORMS(X, 4, 2) SMI_O_FORMS(X, 8, 4) \
+  /* gate_up up to 3 rows: 69 VGPRs (>= 6 waves per SIMD), all 608 blocks resident at once, no second round (step 745 -> 705 us) */ \
+  X(GU_L0, 1, 1, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 6, 0, kMaxOHeads, 0) \
+  X(GU_L1, 1, 1, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 6, 1, kMaxOHeads, 0) \
+  X(GU_L2, 1, 1, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 6, 2, kMaxOHeads, 0) \
+  /* one row behind the fused o_proj: the operand is built in the kernel from the per-head partials (14 / 4 heads) */ \
+  X(GU_FO14, 1, 1, 8, 2, 2, PRO_FUSEDO, EPI_SWIGLU, 1, 6, 2, 14, 1) \
+  X(GU_FO4, 1, 1, 8, 2, 2, PRO_FUSEDO, EPI_SWIGLU, 1, 6, 2, 4, 1) \
+  X(GU3_L0, 1, 3, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 1, 0, kMaxOHeads, 0) \
+  X(GU3_L1, 1, 3, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 1, 1, kMaxOHeads, 0) \
+  X(GU_2M3, 2, 3, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 1, 0, kMaxOHeads, 0) \
+  X(GU_2M2, 2, 2, 8, 2, 1, PRO_NORM, EPI_SWIGLU, 1, 1, 0, kMaxOHeads, 0) \
+  /* a prompt pass's row group below kGu1Lo rows (the remainder group of a long pass) */ \
+  X(GUP_L0, 1, 1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 1, 0, kMaxOHeads, 0) \
+  X(GUP_L1, 1, 1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 1, 1, kMaxOHeads, 0) \
+  X(GUP_L2, 1, 1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 1, 2, kMaxOHeads, 0) \
+  /* down_proj on k_gemm (stamps on, KT > 160, NT % 4 != 0, SPARKMI_TUNE2): H row parts per weight tile */ \
+  X(D_H4_L0, 1, 1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4, 1, 0, kMaxOHeads, 0) \
+  X(D_H4_L1, 1, 1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4, 1, 1, kMaxOHeads, 0) \
+  X(D_H4_L2, 1, 1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4, 1, 2, kMaxOHeads, 0) \
+  X(D_H2, 1, 1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 2, 1, 0, kMaxOHeads, 0) \
+  X(D_H1_L0, 1, 1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 1, 1, 0, kMaxOHeads, 0) \
+  X(D_H1_L1, 1, 1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 1, 1, 1, kMaxOHeads, 0)   /* (L1, L2: a prompt pass's row group of 1 .. 5 rows) */ \
+  X(D_H1_L2, 1, 1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 1, 1, 2, kMaxOHeads, 0) \
+  X(D_2M, 2, 1, 16, 2, 1, PRO_PLAIN, EPI_RESID, 1, 1, 0, kMaxOHeads, 0)   /* a prompt pass's row group above 16 rows */ \
+  X(LM_1M, 1, 4, 4, 2, 1, PRO_NORM, EPI_LM, 1, 1, 0, kMaxOHeads, 0)        /* lm_head with more than 32 k tiles */ \
+  X(LM_2M, 2, 4, 4, 2, 1, PRO_NORM, EPI_LM, 1, 1, 0, kMaxOHeads, 0)
+// down_proj's own kernels:  id | kernel, TPC (k tiles per chain: KT <= 16 * TPC), MG (k_downS: row groups of four) or MTN (k_downC: m-tiles)
+enum { DN_DOWN1 = 1, DN_DOWNS, DN_DOWNC };
+#define SMI_DOWN_FORMS_T(X, T) \
+  X(D1_##T, DN_DOWN1, T, 0) X(DS_##T##_1, DN_DOWNS, T, 1) X(DS_##T##_2, DN_DOWNS, T, 2) \
+  X(DC_##T##_1, DN_DOWNC, T, 1) X(DC_##T##_2, DN_DOWNC, T, 2) X(DC_##T##_4, DN_DOWNC, T, 4)
+#define SMI_DOWN_FORMS(X) SMI_DOWN_FORMS_T(X, 2) SMI_DOWN_FORMS_T(X, 6) SMI_DOWN_FORMS_T(X, 10)
+// k_pgemm (a prompt pass's row group):  id | PRO, EPI, NTW, WR, RING, XMAP, TWO, MTB.  REGS: the register-staged form
+// (SPARKMI_TUNE2 bit kTune2PgemmRegs); FEW: up to pg_split_rows rows, 64-column tiles (more blocks) and a deeper ring -- RES_FEW
+// with one block per K segment + the in-order combine (split-K); MANY: beyond.
+#define SMI_PGEMM_FORMS(X) \
+  X(PG_QKV_REGS, PRO_NORM, EPI_QKV, 2, 1, 0, 0, 0, 8) \
+  X(PG_QKV_FEW, PRO_NORM, EPI_QKV, 2, 2, 6, 1, 0, 4) \
+  X(PG_QKV_MANY, PRO_NORM, EPI_QKV, 6, 2, 3, 1, 0, 8) \
+  X(PG_RES_REGS, PRO_PLAIN, EPI_RESID, 2, 1, 0, 0, 0, 8) \
+  X(PG_RES_FEW, PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4) \
+  X(PG_RES_MANY, PRO_PLAIN, EPI_RESID, 4, 2, 4, 1, 0, 8) \
+  X(PG_GU_REGS, PRO_NORM, EPI_SWIGLU, 4, 1, 0, 0, 0, 8) \
+  /* 64 KiB ring: two blocks per CU, the 304 blocks of a 127-row prompt in one round (ring of 6: 1.2 rounds, 30 us) */ \
+  X(PG_GU_FEW, PRO_NORM, EPI_SWIGLU, 2, 2, 4, 0, 0, 4) \
+  X(PG_GU_MANY, PRO_NORM, EPI_SWIGLU, 8, 2, 2, 0, 1, 8)
+// the persistent lm_head (KT <= 32):  id | k_lm32?, HV (k_lm) or UW (k_lm32), RT (the restricted form), the name smi_llm_debug_head reports
+#define SMI_LM_FORMS(X) \
+  X(LM1, 0, 1, 0, "k_lm<1>") X(LM1_RT, 0, 1, 1, "k_lm<1,RT>") X(LM2, 0, 2, 0, "k_lm<2>") X(LM2_RT, 0, 2, 1, "k_lm<2,RT>") \
+  X(LM32_7, 1, 7, 0, "k_lm32<7>") X(LM32_7_RT, 1, 7, 1, "k_lm32<7,RT>") X(LM32_8, 1, 8, 0, "k_lm32<8>") X(LM32_8_RT, 1, 8, 1, "k_lm32<8,RT>")
+// exact-weights mode (k_gemm_x: fp32 matrices, one exact fp32 FMA chain per output):  id | PRO, EPI
+#define SMI_X_FORMS(X) \
+  X(X_QKV, PRO_NORM, EPI_QKV) X(X_RESID, PRO_PLAIN, EPI_RESID) X(X_GU, PRO_NORM, EPI_SWIGLU) X(X_LM, PRO_NORM, EPI_LM)
+
+enum GemmForm : int {
+  GF_BAD = -1,    // no form for these values: the launch is refused
+  GF_NONE = 0,    // nothing to launch (o_proj done by the attention kernel)
+#define X(id, ...) GF_##id,
+  SMI_KGEMM_FORMS(X) GF_KG_END, SMI_DOWN_FORMS(X) GF_DN_END, SMI_PGEMM_FORMS(X) GF_PG_END, SMI_LM_FORMS(X) GF_LM_END, SMI_X_FORMS(X) GF_X_END
+#undef X
+};
+struct KgShape { int MT, NTB, NW, U, WB, PRO, EPI, H, OCC, LEAN, NOH, hot; };
+struct DnShape { int kernel, TPC, N; };
+struct PgShape { int PRO, EPI, NTW, WR, RING, XMAP, TWO, MTB; };
+struct LmShape { int k32, A, RT; const char* note; };
+struct XShape { int PRO, EPI; };
+#define X(id, ...) {__VA_ARGS__},
+constexpr KgShape kKgShape[] = {SMI_KGEMM_FORMS(X)};
+constexpr DnShape kDnShape[] = {SMI_DOWN_FORMS(X)};
+constexpr PgShape kPgShape[] = {SMI_PGEMM_FORMS(X)};
+constexpr LmShape kLmShape[] = {SMI_LM_FORMS(X)};
+constexpr XShape kXShape[] = {SMI_X_FORMS(X)};
+#undef X
+constexpr const KgShape& kg_shape(int form) { return kKgShape[form - GF_NONE - 1]; }
+constexpr const DnShape& dn_shape(int form) { return kDnShape[form - GF_KG_END - 1]; }
+constexpr const PgShape& pg_shape(int form) { return kPgShape[form - GF_DN_END - 1]; }
+constexpr const LmShape& lm_shape(int form) { return kLmShape[form - GF_PG_END - 1]; }
+constexpr const XShape& x_shape(int form) { return kXShape[form - GF_LM_END - 1]; }
+// k_pgemm's dynamic LDS: the operand (and, ring forms, weight) stages + the rows' norm factors
+constexpr size_t pgemm_lds(int NTW, int WR, int RING, int TWO, int MTB) {
+  const int cols = (4 / WR) * NTW, rows = MTB * 16;
+  return (RING ? (size_t)RING * (12 * rows + cols * 64) : (size_t)2 * 12 * rows) * 16 + (TWO ? 0 : rows * 4);
 }
 
-// NW (the k-tile -> wave map) is fixed per kernel type for every M; only the batch depth U shrinks
-// for two m-tiles (register budget), which does not change any summation order.
-template <int NTB, int NW, int U, int WB, int PRO, int EPI, int H = 1, int N2 = 1, int OCC = 1>
-int launch_gemm(const smi_llm* L, const GemmP& p, hipStream_t st) {
+// The switches a pick reads, as plain values (pick_env: as a handle holds them).
+struct PickEnv {
+  int pass;            // 0: decode rows; PF_GROUPED / PF_PGEMM: a prompt pass's row group and this kernel's family
+  int fused;           // decode: 1 = one row with the fused o_proj in effect, 2 = 2 .. fuse2_rows rows with it (SPARKMI_FUSE2_ROWS)
+  int stamps, exact, tune2;
+  int pf_mask, pf_rows, has_pf;   // helper-block prefetch: the producers' mask, the row bound, and whether this launch has a target
+  int kv_f32;
+  int pg_split_rows;
+  int lm_restricted;   // the step's lm_head reads only the constrained rows' tiles
+  int lm_blocks;       // blocks of the persistent lm_head
+};
+// One launch as a pick decided it.
+struct GemmPick {
+  int form = GF_BAD, kv_f32 = 0;
+  int launches = 0;                          // kernels started: 2 with a combine, one per 32 rows for the persistent lm_head above 16
+  int gx = 0, gy = 1, block = 0; size_t lds = 0;
+  int gx2 = 0;                               // blocks (of 64) of the k_resid_comb that follows
+  int work_blocks = 0, ldsb = 0, lt_shift = 0, kseg = 0;   // GemmP's fields of the same names
+  int nsplit = 1, mtiles = 0;                // split-K: K segments (= grid y) and 16-row tiles of the slab
+  int lm_groups = 0;                         // the persistent lm_head's ngroups argument
+};
+
+// idle CUs warm the L2 of their own XCD for a later kernel (decode with few rows only): (256 - work) / 8 * 8 extra blocks where
+// the producer's mask bit, a target and the row bound allow and the work leaves room
+int helper_blocks(const PickEnv& e, int bit, int M, int work) {
+  return (e.pf_mask & bit) && e.has_pf && M <= e.pf_rows && work < 232 ? (256 - work) / 8 * 8 : 0;
+}
+
+// The k_gemm block shape of form f0 (its LEAN 0 form) over M rows; f1 / f2: the shape's LEAN 1 / one-row forms where the shape
+// runs at such row counts.  One m-tile, up to 5 rows: the operand is staged through wave-private LDS while it fits the cap -- then
+// one row takes LEAN 2, 2 .. 5 rows LEAN 1; 6 rows and more, or stamps on, take LEAN 0.
+GemmPick pick_kgemm(int f0, int f1, int f2, int KT, int NT, int M, const PickEnv& e) {
+  const KgShape& s = kg_shape(f0);
+  GemmPick k;
+  k.kv_f32 = s.EPI == EPI_QKV ? e.kv_f32 : 0;
+  k.work_blocks = (NT + s.NTB - 1) / s.NTB * s.H;
+  k.lds = (size_t)s.NW * s.NTB * s.MT * 1024 + 32 * 4 + s.NTB * 32 * 8;
+  if (s.MT == 1 && M <= 5) {
+    const int tw = (KT + s.NW - 1) / s.NW;               // k tiles per wave
+    const size_t per_wave = (size_t)tw * 12 * M * 16;
+    // (blocks of 14+ waves are alone on their CU anyway: down_proj's ten k tiles per wave then fit up to 3 rows -- 2 rows: down_proj
+    // 8.7 -> 7.3 us, graph step 718 -> 690 us; at 4 rows (123 KB) a tie, so the cap stays below it)
+    if (per_wave * s.NW <= (size_t)(s.NW >= 14 ? 96 : 40) * 1024) {
+      k.ldsb = (int)per_wave;
+      int sh = 4;                                         // 16 lanes fetch 12 pieces (M = 1)
+      while ((1 << sh) < 12 * M) ++sh;
+      k.lt_shift = sh;
+      k.lds += per_wave * s.NW;
+    }
+  }
+  const int lean = s.MT == 1 && s.EPI != EPI_LM && k.ldsb > 0 && !e.stamps ? (M == 1 ? 2 : 1) : 0;
+  k.form = lean == 2 ? f2 : lean == 1 ? f1 : f0;
+  k.gx = k.work_blocks + helper_blocks(e, s.EPI == EPI_QKV ? 1 : 4, M, k.work_blocks);
+  k.gy = (M + s.MT * 16 - 1) / (s.MT * 16);   // one block row per MT * 16 rows
+  k.block = s.NW * 64;
+  k.launches = 1;
+  return k;
+}
+GemmPick pick_x(int form, int NT, int M, const PickEnv& e) {
+  GemmPick k;
+  k.form = form; k.kv_f32 = x_shape(form).EPI == EPI_QKV ? e.kv_f32 : 0;
+  k.gx = (NT + 3) / 4; k.gy = (M + 15) / 16; k.block = 256; k.launches = 1;
+  return k;
+}
+// nsplit > 1 (PG_RES_FEW): one block per (tile, K segment) writes its segment's sums to the slab and k_resid_comb adds the
+// segments in order and runs the epilogue -- the few-row form of the segmented sum (GemmP::kseg), same bits as the in-block form
+GemmPick pick_pgemm(int form, int NT, int M, int kseg, int nsplit, const PickEnv& e) {
+  const PgShape& s = pg_shape(form);
+  const int cols = (4 / s.WR) * s.NTW, rows = s.MTB * 16;   // weight tiles / rows per block
+  const int bx = (NT + cols - 1) / cols, by = (M + rows - 1) / rows;
+  GemmPick k;
+  k.form = form; k.kv_f32 = s.EPI == EPI_QKV ? e.kv_f32 : 0;
+  k.gx = s.XMAP || nsplit > 1 ? bx * by : bx; k.gy = nsplit > 1 ? nsplit : s.XMAP ? 1 : by;
+  k.block = 256; k.lds = pgemm_lds(s.NTW, s.WR, s.RING, s.TWO, s.MTB);
+  k.kseg = kseg; k.nsplit = nsplit; k.mtiles = (M + 15) / 16;
+  k.launches = nsplit > 1 ? 2 : 1;
+  if (nsplit > 1) k.gx2 = NT * k.mtiles;
+  return k;
+}
+// a prompt pass's row group on k_pgemm: regs / few / many = the kernel's three forms; K in nseg segments (0: one sum)
+constexpr int kPgSplitRows = 512;        // passes of up to this many rows run o_proj / down_proj in k_pgemm's split-K form
+GemmPick pick_pgemm_rows(int regs, int few, int many, int KT, int NT, int M, int nseg, const PickEnv& e) {
+  const int kseg = nseg ? (KT + nseg - 1) / nseg : 0;
+  if (e.tune2 & kTune2PgemmRegs) return pick_pgemm(regs, NT, M, kseg, 1, e);
+  if (M <= e.pg_split_rows) return pick_pgemm(few, NT, M, kseg, kseg ? (KT + kseg - 1) / kseg : 1, e);
+  return pick_pgemm(many, NT, M, kseg, 1, e);
+}
+
+GemmPick pick_qkv(int KT, int NT, int M, const PickEnv& e) {
+  if (e.exact) return pick_x(GF_X_QKV, NT, M, e);
+  if (e.pass == PF_PGEMM) return pick_pgemm_rows(GF_PG_QKV_REGS, GF_PG_QKV_FEW, GF_PG_QKV_MANY, KT, NT, M, 0, e);
+  // decode rows stay one m-tile with a block row per 16 rows: few n tiles (N = 1152), so 16-row blocks put twice the CUs to
+  // work and halve the operand bytes per CU (measured at M = 32); a prompt pass's row group takes two m-tiles above 16 rows
+  if (e.pass == PF_GROUPED && M > 16) return pick_kgemm(GF_QKV_2M, GF_BAD, GF_BAD, KT, NT, M, e);
+  return pick_kgemm(GF_QKV_L0, GF_QKV_L1, GF_QKV_HOT, KT, NT, M, e);
+}
+GemmPick pick_o(int KT, int NT, int heads, int M, const PickEnv& e) {
+  if (e.exact) return pick_x(GF_X_RESID, NT, M, e);
+  GemmPick k;
+  if (e.pass == PF_PGEMM) return pick_pgemm_rows(GF_PG_RES_REGS, GF_PG_RES_FEW, GF_PG_RES_MANY, KT, NT, M, kPgSegO, e);
+  if (e.pass == 0 && e.fused) {   // done by the attention kernel (per-head partials) and gate_up's prologue / the last-arriver head sum
+    k.form = GF_NONE;
+    return k;
+  }
+  // no helpers here: warming down_proj's 8.7 MB from o_proj (or from attention / gate_up) stretches the
+  // producer by more than the consumer gains (measured, profiles/README.md), so down_proj stays cold
+  // four row parts up to 8 rows: 629.8 -> 626.0 us per step once the prologues were down to one round trip; beyond, one part
+  // and a block row per 16 rows (few n tiles, as QKV)
+  const int h4 = heads == 14 ? GF_O14_H4_L0 : heads == 4 ? GF_O4_H4_L0 : GF_O8_H4_L0;
+  k = M <= 8 ? pick_kgemm(h4, h4 + 1, h4 + 2, KT, NT, M, e) : pick_kgemm(h4 + 3, GF_BAD, GF_BAD, KT, NT, M, e);
+  if (e.pass) k.kseg = (KT + kPgSegO - 1) / kPgSegO;   // (a pass's o_proj operands carry it in every family)
+  return k;
+}
+constexpr int kGu1Lo = 4;                // rows from which (up to 16) gate_up runs the one-batch, three-tile shape with one m-tile
+constexpr int kGu1Rows = 32;             // rows up to which gate_up runs its one-batch, three-tile shape
+GemmPick pick_gu(int KT, int NT, int heads, int M, const PickEnv& e) {
+  if (e.exact) return pick_x(GF_X_GU, NT, M, e);
+  if (e.pass == PF_PGEMM) return pick_pgemm_rows(GF_PG_GU_REGS, GF_PG_GU_FEW, GF_PG_GU_MANY, KT, NT, M, 0, e);
   // two m-tiles: the operand triples (12 * M pieces per k tile) outweigh the weight tile 6:1, so where there are
-  // n tiles to spare (gate_up: 608) a block takes N2 of them per operand fetch.  Any NTB gives the same bits:
-  // a tile's k -> wave map does not change.  (Measured at M = 32: gate_up 19.4 -> 13.7 us with N2 = 2, 14.4 with 4;
+  // n tiles to spare (gate_up: 608) a block takes several of them per operand fetch.  Any NTB gives the same bits:
+  // a tile's k -> wave map does not change.  (Measured at M = 32: gate_up 19.4 -> 13.7 us with two, 14.4 with 4;
   // QKV / o_proj / down / lm_head lose with fewer blocks.)
-  if (p.M > 16) {
-    if constexpr (N2 > 1) {   // (gate_up)
-      // 17..32 rows: three n tiles per block and ALL of a wave's k tiles in one batch -- every load of the block leaves at
-      // entry (one memory round trip instead of two dependent ones; 233 VGPRs, one 8-wave block per CU, 203 blocks):
-      // gate_up 12.8 -> 10.5 us, batch-32 step 1047 -> 998 us.  Beyond 32 rows (two block rows = 406 blocks, two rounds
-      // at one block per CU) the two-tile, two-batch shape stays.
-      // (five n tiles per block in two batches -- 244 blocks, one round: 13.3 us against 10.3, step 947 -> 1017: not a rounds problem)
-      if (p.M <= kGu1Rows) return launch_gemm_kv<2, 3, NW, 4, 1, PRO, EPI>(L, p, st);
-      return launch_gemm_kv<2, NTB * N2, NW, 2, 1, PRO, EPI>(L, p, st);   // two k tiles in flight: 13.9 -> 13.6 us at 32 rows, 18.5 -> 17.5 at 64
-    } else if constexpr (N2 == 0) {
-      // few n tiles (N = 896 / 1152): 16-row blocks in two block rows put twice the CUs to work and halve the operand
-      // bytes per CU (measured at M = 32)
-      // (WB batches of weight tiles requested at entry, as at 16 rows and fewer: down_proj's five batches then wait for L2
-      // operand round trips only, not for five dependent HBM round trips)
-      return launch_gemm_kv<1, NTB, NW, U, WB, PRO, EPI, H>(L, p, st);
-    } else
-      return launch_gemm_kv<2, NTB, NW, (NW >= 16 || NTB >= 4 ? 2 : (U > 4 ? 4 : U)), 1, PRO, EPI>(L, p, st);
+  // 17..32 rows: three n tiles per block and ALL of a wave's k tiles in one batch -- every load of the block leaves at
+  // entry (one memory round trip instead of two dependent ones; 233 VGPRs, one 8-wave block per CU, 203 blocks):
+  // gate_up 12.8 -> 10.5 us, batch-32 step 1047 -> 998 us.  Beyond 32 rows (two block rows = 406 blocks, two rounds
+  // at one block per CU) the two-tile, two-batch shape stays: two k tiles in flight, 13.9 -> 13.6 us at 32 rows, 18.5 -> 17.5 at 64.
+  // (five n tiles per block in two batches -- 244 blocks, one round: 13.3 us against 10.3, step 947 -> 1017: not a rounds problem)
+  if (M > kGu1Rows) return pick_kgemm(GF_GU_2M2, GF_BAD, GF_BAD, KT, NT, M, e);
+  if (M > 16) return pick_kgemm(GF_GU_2M3, GF_BAD, GF_BAD, KT, NT, M, e);
+  // kGu1Lo..16 rows: three n tiles per block and all of a wave's k tiles in one batch, as at 17..32 rows -- every load
+  // of the block leaves at entry (one memory round trip).  8 rows 8.0 -> 6.9 us (graph step 801 -> 773 us), 16 rows 9.5 -> 7.9
+  // (855 -> 817), 5 rows 763 -> 751, 4 rows 749 -> 742, 2 rows a tie (below 4 rows the operands staged through wave-private LDS
+  // stay); same bits (the k tile -> wave map does not change).
+  if (M >= kGu1Lo) return pick_kgemm(GF_GU3_L0, GF_GU3_L1, GF_BAD, KT, NT, M, e);
+  if (e.pass) return pick_kgemm(GF_GUP_L0, GF_GUP_L1, GF_GUP_L2, KT, NT, M, e);
+  GemmPick k = pick_kgemm(GF_GU_L0, GF_GU_L1, GF_GU_L2, KT, NT, M, e);
+  if (e.fused == 1 && k.form == GF_GU_L2) {   // the hot entry of the two fused head counts; + the heads' norm partials in LDS
+    k.form = heads == 14 ? GF_GU_FO14 : heads == 4 ? GF_GU_FO4 : GF_BAD;
+    k.lds += 1024;
   }
-  if constexpr (N2 > 1) {
-    // gate_up at kGu1Lo..16 rows: three n tiles per block and all of a wave's k tiles in one batch, as at 17..32 rows -- every load
-    // of the block leaves at entry (one memory round trip).  8 rows 8.0 -> 6.9 us (graph step 801 -> 773 us), 16 rows 9.5 -> 7.9
-    // (855 -> 817), 5 rows 763 -> 751, 4 rows 749 -> 742, 2 rows a tie (below 4 rows the operands staged through wave-private LDS
-    // stay); same bits (the k tile -> wave map does not change).
-    if (p.M >= kGu1Lo) return launch_gemm_kv<1, 3, NW, 4, 1, PRO, EPI>(L, p, st);
+  return k;
+}
+// rows from which down_proj runs chain-split (k_downC): graph step at 0.5B, same box (profiles/r04_batch_ab.txt): 4 rows 641 (k_downS) vs
+// 692 us (chains), 8 rows 728 vs 713, 16 rows 790 (k_gemm<.., H = 4>) vs 744, 32 rows 892 vs 859
+// (5 / 6 rows: 731 / 728 us with the chains, the same as k_downS within noise -- the chains take over from 7)
+constexpr int kDcMin = 7;
+GemmPick pick_d(int KT, int NT, int M, const PickEnv& e) {
+  if (e.exact) return pick_x(GF_X_RESID, NT, M, e);
+  if (e.pass == PF_PGEMM) return pick_pgemm_rows(GF_PG_RES_REGS, GF_PG_RES_FEW, GF_PG_RES_MANY, KT, NT, M, kPgSegD, e);
+  GemmPick k;
+  if (e.pass) {   // a prompt pass's row group on k_gemm
+    k = M > 16 ? pick_kgemm(GF_D_2M, GF_BAD, GF_BAD, KT, NT, M, e) : pick_kgemm(GF_D_H1_L0, GF_D_H1_L1, GF_D_H1_L2, KT, NT, M, e);
+    k.kseg = (KT + kPgSegD - 1) / kPgSegD;   // (a pass's down_proj operands carry it in every family)
+    return k;
   }
-  return launch_gemm_kv<1, NTB, NW, U, WB, PRO, EPI, H, OCC>(L, p, st);
+  const bool own = !e.stamps && KT <= 160;   // down_proj's own kernels: a chain's k tiles in registers (TPC <= 10), no stamps
+  const int t = GF_D1_2 + (KT <= 32 ? 0 : KT <= 96 ? 1 : 2) * (GF_D1_6 - GF_D1_2);   // the TPC = 2 / 6 / 10 forms
+  if (own && M >= kDcMin && M <= kMaxRows && NT % 4 == 0) {
+    // kDcMin .. 64 rows: the 16 chains on 16 different blocks + an in-order combine (k_downC, k_resid_comb); 1 / 2 / 4 m-tiles
+    const int mtn = M <= 16 ? 1 : M <= 32 ? 2 : 4;
+    k.form = t + (GF_DC_2_1 - GF_D1_2) + (mtn == 1 ? 0 : mtn == 2 ? 1 : 2);
+    k.gx = NT / 4 * 16; k.block = 256; k.gx2 = NT * mtn; k.launches = 2;
+    k.lds = (size_t)dn_shape(k.form).TPC * 12 * (M < mtn * 16 ? M : mtn * 16) * 16;   // > 64 KiB from 35 rows at TPC = 10
+    return k;
+  }
+  k.work_blocks = NT * 4;   // four row parts per weight tile
+  // one row: four chains per wave, full load instructions (k_down1_hot; same bits).  SPARKMI_TUNE2 bit kTune2GemmDown1 keeps k_gemm (A/B)
+  if (own && M == 1 && !(e.tune2 & kTune2GemmDown1)) {
+    k.form = t; k.gx = k.work_blocks + helper_blocks(e, 4, M, k.work_blocks); k.block = 256; k.launches = 1;
+    return k;
+  }
+  // 2 .. 8 rows in groups of four (k_downS).  SPARKMI_TUNE2 bit kTune2GemmDownS keeps k_gemm (A/B)
+  if (own && M >= 2 && M <= 8 && !(e.tune2 & kTune2GemmDownS)) {
+    k.form = t + (M <= 4 ? GF_DS_2_1 : GF_DS_2_2) - GF_D1_2; k.gx = k.work_blocks; k.block = 256; k.launches = 1;
+    return k;
+  }
+  // k_gemm: 4-row parts at few rows (224 blocks, -0.7 us); same bits either way, the zero-fed MFMAs cost at M > 8
+  // row parts (H blocks per weight tile) while the operand re-reads they cost stay small: measured step at
+  // 16 / 32 / 64 rows with H = 1 | 2 | 4: 930 | 915 | 900, 1064 | 1055 | 1161, 1318 | 1443 | 1671 us
+  // (one m-tile and a block row per 16 rows at every row count: WB batches of weight tiles requested at entry, so down_proj's
+  // five batches wait for L2 operand round trips only, not for five dependent HBM round trips)
+  if (M <= 16) return pick_kgemm(GF_D_H4_L0, GF_D_H4_L1, GF_D_H4_L2, KT, NT, M, e);
+  if (M <= 32) return pick_kgemm(GF_D_H2, GF_BAD, GF_BAD, KT, NT, M, e);
+  return pick_kgemm(GF_D_H1_L0, GF_BAD, GF_BAD, KT, NT, M, e);
+}
+// blocks of the persistent lm_head for M rows: lm_blocks, two resident per CU, up to 16 rows; one per CU beyond
+int lm_pass_blocks(int lm_blocks, int M) { return M <= 16 ? lm_blocks : (lm_blocks < 256 ? lm_blocks : 256); }
+GemmPick pick_lm(int KT, int NT, int M, const PickEnv& e) {
+  if (e.exact) return pick_x(GF_X_LM, NT, M, e);
+  if (KT > 32) return pick_kgemm(M > 16 ? GF_LM_2M : GF_LM_1M, GF_BAD, GF_BAD, KT, NT, M, e);
+  // The persistent lm_head: 16 rows' operand resident in the registers of a 4-wave group.  Restricted: the same kernel for the same
+  // row count, its groups from the tile list (ngroups = 0)
+  GemmPick k;
+  const int rt = e.lm_restricted ? 1 : 0;
+  const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
+  k.gx = lm_pass_blocks(e.lm_blocks, M); k.lm_groups = rt ? 0 : (NT + 1) / 2;
+  if (M <= 16) {
+    k.form = GF_LM1 + rt; k.block = 256; k.lds = lds; k.launches = 1;
+    return k;
+  }
+  // 32 rows per pass: one 4-wave block per CU, the second m-tile's operands in LDS (k_lm32);
+  // SPARKMI_TUNE2 bit kTune2Lm2: the two-group kernel (k_lm<2>) for A/B
+  const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)KT * 12 * 16 * 16;
+  k.launches = (M + 31) / 32;
+  if (!(e.tune2 & kTune2Lm2) && lds32 <= 150 * 1024) {
+    k.form = (KT <= 28 ? GF_LM32_7 : GF_LM32_8) + rt; k.block = 256; k.lds = lds32;
+  } else {
+    k.form = GF_LM2 + rt; k.block = 512; k.lds = 2 * lds;
+  }
+  return k;
+}
+
+// the form's kernel(s) by name, template arguments as numbers (as a kernel trace prints them, without blanks)
+void gemm_form_name(const GemmPick& k, char* out, size_t n) {
+  const int f = k.form;
+  if (f <= GF_NONE) snprintf(out, n, "%s", "");
+  else if (f < GF_KG_END) {
+    const KgShape& s = kg_shape(f);
+    snprintf(out, n, "%s<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d>", s.hot ? "k_gemm_hot" : "k_gemm", s.MT, s.NTB, s.NW, s.U, s.WB, s.PRO, s.EPI,
+             k.kv_f32, s.H, s.OCC, s.LEAN, s.NOH);
+  } else if (f < GF_DN_END) {
+    const DnShape& s = dn_shape(f);
+    if (s.kernel == DN_DOWN1) snprintf(out, n, "k_down1_hot<%d>", s.TPC);
+    else if (s.kernel == DN_DOWNS) snprintf(out, n, "k_downS<%d,%d>", s.TPC, s.N);
+    else snprintf(out, n, "k_downC<%d,%d>+k_resid_comb<0,0>", s.TPC, s.N);
+  } else if (f < GF_PG_END) {
+    const PgShape& s = pg_shape(f);
+    snprintf(out, n, "k_pgemm<%d,%d,%d,%d,%d,%d,%d,%d,%d>%s", s.PRO, s.EPI, k.kv_f32, s.NTW, s.WR, s.RING, s.XMAP, s.TWO, s.MTB,
+             k.nsplit > 1 ? "+k_resid_comb<1,1>" : "");
+  } else if (f < GF_LM_END) {
+    const LmShape& s = lm_shape(f);
+    snprintf(out, n, "%s<%d,%d>", s.k32 ? "k_lm32" : "k_lm", s.A, s.RT);
+  } else {
+    const XShape& s = x_shape(f);
+    snprintf(out, n, "k_gemm_x<%d,%d,%d>", s.PRO, s.EPI, k.kv_f32);
+  }
+}
+// the name of an lm_head form as smi_llm_debug_head reports it (null: not an lm_head form)
+const char* lm_form_note(int form) {
+  if (form > GF_PG_END && form < GF_LM_END) return lm_shape(form).note;
+  return form == GF_LM_1M ? "k_gemm<1,EPI_LM>" : form == GF_LM_2M ? "k_gemm<2,EPI_LM>" : form == GF_X_LM ? "k_gemm_x<EPI_LM>" : nullptr;
 }
 
 const unsigned char* sec(const smi_llm* L, int s, int layer) {
@@ -4379,7 +4602,6 @@ int eng_check(smi_llm* L) {
 #endif   // SMI_DIAG
 
 enum { KQKV = 0, KATTN, KO, KGU, KD, KLM, KFIN };
-enum { PF_GROUPED = 1, PF_PGEMM = 2 };   // kernel family of a pass over prompt rows (launch_layers_big)
 
 int ensure_apart(smi_llm* L, size_t floats) {
   if (floats <= L->apart_floats) return SMI_OK;
@@ -4394,7 +4616,7 @@ int ensure_apart(smi_llm* L, size_t floats) {
 // lm_head partial columns (= persistent blocks) finalize / the sampler read for M live rows
 int lm_blocks_for(const smi_llm* L, int M) {
   if (L->KTh > 32 || L->exact) return L->lm_cap;
-  return M <= 16 ? L->lm_blocks : (L->lm_blocks < 256 ? L->lm_blocks : 256);
+  return lm_pass_blocks(L->lm_blocks, M);
 }
 
 // ids per set of k_penalize's partition of a row into nblk sets: a multiple of 4 (aligned float4 sets)
@@ -4546,6 +4768,10 @@ int launch_attn(smi_llm* L, AttnP a, hipStream_t st) {
 // One live row in its own slot, one context segment: the attention kernel also computes its head's share of the o_proj
 // (k_attn<.., FUSE>), gate_up builds its operand from those partials (PRO_FUSEDO) and down_proj adds its residual from h2;
 // the o_proj kernel is not launched.  The predicate is the one launch_attn picks the one-row kernel by.
+// (the shapes that have the fused path: the two head counts with a gate_up form of their own, hidden tiles the attention blocks share out)
+bool fuse_o_fits(int heads, int NTh, int KTh) {
+  return (heads == 14 || heads == 4) && heads <= kMaxOHeads && NTh % kFuseQB == 0 && NTh / kFuseQB <= kAttnWaves * kFuseOT && KTh * 8 <= 256;
+}
 bool fuse_o_now(const smi_llm* L, const RowDesc* rows, int M) {
   return L->fuse_o && M == 1 && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
 }
@@ -4555,49 +4781,111 @@ bool fuse2_now(const smi_llm* L, const RowDesc* rows, int M) {
   return L->fuse_o && M >= 2 && M <= L->fuse2_rows && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
 }
 
-// o_proj: NW = number of heads, so that wave w sums head w's two (head-interleaved) k tiles -- the per-head partial the
-// fused path produces -- and the block's in-order sum over the waves is the fused consumer's in-order sum over the heads.
-int launch_oproj(const smi_llm* L, const GemmP& p, int M, hipStream_t st) {
-  switch (L->cfg.num_heads) {
-    case 14: return M <= 8 ? launch_gemm<1, 14, 2, 1, PRO_PLAIN, EPI_RESID, 4>(L, p, st) : launch_gemm<1, 14, 2, 1, PRO_PLAIN, EPI_RESID, 1, 0>(L, p, st);
-    case 4: return M <= 8 ? launch_gemm<1, 4, 2, 1, PRO_PLAIN, EPI_RESID, 4>(L, p, st) : launch_gemm<1, 4, 2, 1, PRO_PLAIN, EPI_RESID, 1, 0>(L, p, st);
-    default:   // other head counts: no fused path (smi_llm_create leaves fuse_o off), eight waves as before
-      return M <= 8 ? launch_gemm<1, 8, 4, 1, PRO_PLAIN, EPI_RESID, 4>(L, p, st) : launch_gemm<1, 8, 4, 1, PRO_PLAIN, EPI_RESID, 1, 0>(L, p, st);
+// ---- The forms' launchers, one per table: the template arguments are a table row's, everything else is the pick's.  A launcher
+// enters exactly the instantiations it starts in LdsBig (both cache types where the epilogue appends to the cache).
+template <int MT, int NTB, int NW, int U, int WB, int PRO, int EPI, int H, int OCC, int LEAN, int NOH, int HOT>
+int launch_kgemm_form(const smi_llm* L, const GemmP& p, const GemmPick& k, hipStream_t st) {
+  SMI_REQUIRE(k.lds <= (size_t)kLdsBigBytes, "k_gemm: %zu bytes of LDS", k.lds);
+  with_kvf32<EPI>(L, [&](auto kv) {
+    if constexpr (HOT) {   // the hot values come from the struct that travels behind them (launch_gemm_hot)
+      static_assert(LEAN == 2, "hot entries: the one-row kernels");
+      static_cast<void>(LdsBig<k_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, LEAN, NOH>>::reg);
+      launch_gemm_hot<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, NOH>(p, dim3(k.gx, k.gy), k.lds, st);
+    } else {
+      static_cast<void>(LdsBig<k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, LEAN, NOH>>::reg);
+      hipLaunchKernelGGL((k_gemm<MT, NTB, NW, U, WB, PRO, EPI, kv(), H, OCC, LEAN, NOH>), dim3(k.gx, k.gy), dim3(NW * 64), k.lds, st, p);
+    }
+  });
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+// down_proj's own kernels; DN_DOWNC: the chains split over blocks (k_downC) and the in-order combine + RESID epilogue (k_resid_comb)
+template <int KERNEL, int TPC, int N>
+int launch_down_form(const smi_llm* L, const GemmP& p, const GemmPick& k, hipStream_t st) {
+  if constexpr (KERNEL == DN_DOWN1) launch_down1_hot<TPC>(p, k.gx, st);
+  else if constexpr (KERNEL == DN_DOWNS) hipLaunchKernelGGL((k_downS<TPC, N>), dim3(k.gx), dim3(256), 0, st, p);
+  else {
+    DownCP d;
+    d.W = p.W; d.NT = p.NT; d.KT = p.KT; d.M = p.M; d.wperm = p.wperm; d.XS = p.XS; d.part = L->dpart;
+    d.Y = p.Y; d.Yin = p.Yin; d.gamma_next = p.gamma_next; d.XSout = p.XSout; d.ssout = p.ssout;
+    static_cast<void>(LdsBig<k_downC<TPC, N>>::reg);
+    SMI_REQUIRE(k.lds <= (size_t)kLdsBigBytes, "k_downC: %zu bytes of LDS", k.lds);
+    hipLaunchKernelGGL((k_downC<TPC, N>), dim3(k.gx), dim3(256), k.lds, st, d);
+    SMI_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_resid_comb<0, 0>), dim3(k.gx2), dim3(64), 0, st, d, 16, N);
   }
-}
-
-// down_proj with the chains split over blocks (k_downC) and the in-order combine + RESID epilogue (k_resid_comb)
-template <int TPC, int MTN>
-int launch_down_chains_t(const smi_llm* L, const DownCP& d, hipStream_t st) {
-  const size_t lds = (size_t)TPC * 12 * (d.M < MTN * 16 ? d.M : MTN * 16) * 16;   // > 64 KiB from 35 rows at TPC = 10
-  static_cast<void>(LdsBig<k_downC<TPC, MTN>>::reg);                               // (opted in by smi_llm_create)
-  SMI_REQUIRE(lds <= (size_t)kLdsBigBytes, "k_downC: %zu bytes of LDS", lds);
-  hipLaunchKernelGGL((k_downC<TPC, MTN>), dim3(d.NT / 4 * 16), dim3(256), lds, st, d);
-  SMI_LAUNCH_CHECK();
-  hipLaunchKernelGGL((k_resid_comb<0, 0>), dim3(d.NT * MTN), dim3(64), 0, st, d, 16, MTN);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }
-
-int launch_down_chains(const smi_llm* L, const GemmP& p, hipStream_t st) {
-  DownCP d;
-  d.W = p.W; d.NT = p.NT; d.KT = p.KT; d.M = p.M; d.wperm = p.wperm; d.XS = p.XS; d.part = L->dpart;
-  d.Y = p.Y; d.Yin = p.Yin; d.gamma_next = p.gamma_next; d.XSout = p.XSout; d.ssout = p.ssout;
-#define SMI_DC(TPC_) (p.M <= 16 ? launch_down_chains_t<TPC_, 1>(L, d, st) : p.M <= 32 ? launch_down_chains_t<TPC_, 2>(L, d, st) : launch_down_chains_t<TPC_, 4>(L, d, st))
-  if (p.KT <= 32) return SMI_DC(2);
-  if (p.KT <= 96) return SMI_DC(6);
-  return SMI_DC(10);
-#undef SMI_DC
+// One prefill GEMM over a row group with k_pgemm; k.nsplit > 1: split-K through L->pslab + k_resid_comb
+template <int PRO, int EPI, int NTW, int WR, int RING, int XMAP, int TWO, int MTB>
+int launch_pgemm_form(const smi_llm* L, GemmP p, const GemmPick& k, hipStream_t st) {
+  if constexpr (pgemm_lds(NTW, WR, RING, TWO, MTB) > 64 * 1024) {
+    static_assert(pgemm_lds(NTW, WR, RING, TWO, MTB) <= (size_t)kLdsBigBytes, "k_pgemm: LDS beyond the opted-in window");
+    with_kvf32<EPI>(L, [&](auto kv) { static_cast<void>(LdsBig<k_pgemm<PRO, EPI, kv(), NTW, WR, RING, XMAP, TWO, MTB>>::reg); });
+  }
+  if (k.nsplit > 1) {
+    SMI_REQUIRE(EPI == EPI_RESID && XMAP && RING >= 3 && p.kseg > 0 && k.nsplit <= 16, "launch_pgemm_form: split-K is the RESID ring form's");
+    SMI_REQUIRE(L->pslab && (size_t)k.nsplit * p.NT * k.mtiles * 1024 <= L->pslab_bytes, "launch_pgemm_form: partial slab too small");
+    p.slab = L->pslab; p.slab_mt = k.mtiles;
+  }
+  with_kvf32<EPI>(L, [&](auto kv) {
+    hipLaunchKernelGGL((k_pgemm<PRO, EPI, kv(), NTW, WR, RING, XMAP, TWO, MTB>), dim3(k.gx, k.gy), dim3(256), k.lds, st, p);
+  });
+  SMI_LAUNCH_CHECK();
+  if (k.nsplit > 1) {
+    DownCP d;
+    d.W = nullptr; d.NT = p.NT; d.KT = p.KT; d.M = p.M; d.wperm = 0; d.XS = nullptr; d.part = L->pslab;
+    d.Y = p.Y; d.Yin = p.Yin; d.gamma_next = p.gamma_next; d.XSout = p.XSout; d.ssout = p.ssout;
+    hipLaunchKernelGGL((k_resid_comb<1, 1>), dim3(k.gx2), dim3(64), 0, st, d, k.nsplit, k.mtiles);
+    SMI_LAUNCH_CHECK();
+  }
+  return SMI_OK;
 }
-
-// exact-weights mode: the GEMM of launch_one's kernel `which` on k_gemm_x (p prepared as for k_gemm; W = fp32 [N][K])
+// the persistent lm_head: one launch up to 16 rows, else one pass per 32 rows
+template <int K32, int A, int RT>
+int launch_lm_form(const smi_llm*, const GemmP& p, const GemmPick& k, hipStream_t st) {
+  for (int i = 0; i < k.launches; ++i) {
+    if constexpr (K32) hipLaunchKernelGGL((k_lm32<A, RT>), dim3(k.gx), dim3(256), k.lds, st, p, k.lm_groups, 32 * i);
+    else hipLaunchKernelGGL((k_lm<A, RT>), dim3(k.gx), dim3(256 * A), k.lds, st, p, k.lm_groups, 32 * i);
+    SMI_LAUNCH_CHECK();
+  }
+  return SMI_OK;
+}
+// exact-weights mode: p prepared as for k_gemm, W = fp32 [N][K]
 template <int PRO, int EPI>
-int launch_gemm_x(const smi_llm* L, const GemmP& p, hipStream_t st) {
-  const dim3 grid((p.NT + 3) / 4, (p.M + 15) / 16);
-  if constexpr (EPI == EPI_LM) SMI_LM_NOTE(L, "k_gemm_x<EPI_LM>", grid.x, grid.y, 256);
-  with_kvf32<EPI>(L, [&](auto kv) { hipLaunchKernelGGL((k_gemm_x<PRO, EPI, kv()>), grid, dim3(256), 0, st, p, (const float*)p.W); });
+int launch_x_form(const smi_llm* L, const GemmP& p, const GemmPick& k, hipStream_t st) {
+  with_kvf32<EPI>(L, [&](auto kv) { hipLaunchKernelGGL((k_gemm_x<PRO, EPI, kv()>), dim3(k.gx, k.gy), dim3(256), 0, st, p, (const float*)p.W); });
   SMI_LAUNCH_CHECK();
   return SMI_OK;
+}
+
+// Starts the picked form on the operands p: the pick's derived fields go into p, the form's table row names the kernel.
+int launch_form(const smi_llm* L, GemmP p, const GemmPick& k, hipStream_t st) {
+  p.work_blocks = k.work_blocks; p.ldsb = k.ldsb; p.lt_shift = k.lt_shift; p.kseg = k.kseg;
+  if (k.form < GF_KG_END || (k.form > GF_PG_END && k.form < GF_LM_END)) p.stamps = L->stamps_on ? L->stamps : nullptr;
+  if (lm_form_note(k.form))   // (diagnostics) the lm_head's form, grid and block for smi_llm_debug_head
+    for (int i = 0; i < k.launches; ++i) SMI_LM_NOTE(L, lm_form_note(k.form), k.gx, k.gy, k.block);
+  switch (k.form) {
+    case GF_NONE: return SMI_OK;
+#define X(id, ...) case GF_##id: return launch_kgemm_form<__VA_ARGS__>(L, p, k, st);
+    SMI_KGEMM_FORMS(X)
+#undef X
+#define X(id, ...) case GF_##id: return launch_down_form<__VA_ARGS__>(L, p, k, st);
+    SMI_DOWN_FORMS(X)
+#undef X
+#define X(id, ...) case GF_##id: return launch_pgemm_form<__VA_ARGS__>(L, p, k, st);
+    SMI_PGEMM_FORMS(X)
+#undef X
+#define X(id, k32, a, rt, note) case GF_##id: return launch_lm_form<k32, a, rt>(L, p, k, st);
+    SMI_LM_FORMS(X)
+#undef X
+#define X(id, ...) case GF_##id: return launch_x_form<__VA_ARGS__>(L, p, k, st);
+    SMI_X_FORMS(X)
+#undef X
+  }
+  smi_set_error("launch_form: no kernel form for these rows and switches (form %d)", k.form);   // a missing kernel is an error
+  return SMI_EINVAL;
 }
 
 // The operands of GEMM kernel `which` (KQKV, KO, KGU, KD, KLM) of `layer` for M rows in workspace w: what follows from the model
@@ -4648,62 +4936,46 @@ AttnP attn_operands(const smi_llm* L, int layer, const Work& w, const RowDesc* r
   return a;
 }
 
-// The persistent lm_head (KTh <= 32): 16 rows' operand resident in the registers of a 4-wave group.  RT = 1: the restricted form
-// of the same kernel for the same row count (the groups come from p.tlist, so ngroups = 0; the rows' own ranges through p.ctl).
-template <int RT>
-int launch_lm_persistent(const smi_llm* L, const GemmP& p, int M, int ngroups, hipStream_t st) {
-  const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
-  if (M <= 16) {
-    SMI_LM_NOTE(L, RT ? "k_lm<1,RT>" : "k_lm<1>", L->lm_blocks, 1, 256);
-    hipLaunchKernelGGL((k_lm<1, RT>), dim3(L->lm_blocks), dim3(256), lds, st, p, ngroups, 0);
-    SMI_LAUNCH_CHECK();
-    return SMI_OK;
+// The switches the picks read, as the handle holds them, for a kernel of a decode step (pass 0) or of a prompt pass's family.
+PickEnv pick_env(const smi_llm* L, int pass) {
+  PickEnv e{};
+  e.pass = pass; e.stamps = L->stamps_on; e.exact = L->exact; e.tune2 = L->tune2;
+  e.pf_mask = L->prefetch_mask; e.pf_rows = L->prefetch_rows;
+  e.kv_f32 = L->cfg.kv_dtype ? 1 : 0; e.pg_split_rows = L->pg_split_rows; e.lm_blocks = L->lm_blocks;
+  return e;
+}
+// The pick of GEMM kernel `which` (KQKV, KO, KGU, KD, KLM) over M rows at the handle's shape.
+GemmPick pick_gemm(const smi_llm* L, int which, int M, const PickEnv& e) {
+  switch (which) {
+    case KQKV: return pick_qkv(L->KTh, L->NTqkv, M, e);
+    case KO: return pick_o(L->KTq, L->NTh, L->cfg.num_heads, M, e);
+    case KGU: return pick_gu(L->KTh, L->NTgu, L->cfg.num_heads, M, e);
+    case KD: return pick_d(L->KTi, L->NTh, M, e);
+    case KLM: return pick_lm(L->KTh, L->NTlm, M, e);
   }
-  // 32 rows per pass: one 4-wave block per CU, the second m-tile's operands in LDS (k_lm32);
-  // SPARKMI_TUNE2 bit kTune2Lm2: the two-group kernel (k_lm<2>) for A/B
-  const size_t lds32 = (size_t)4 * 2 * 2 * 1024 + 32 * 4 + 2 * 32 * 8 + (size_t)L->KTh * 12 * 16 * 16;
-  const int blocks = lm_blocks_for(L, M);
-  for (int m0 = 0; m0 < M; m0 += 32) {
-    if (!(L->tune2 & kTune2Lm2) && lds32 <= 150 * 1024) {
-      if (L->KTh <= 28) {
-        SMI_LM_NOTE(L, RT ? "k_lm32<7,RT>" : "k_lm32<7>", blocks, 1, 256);
-        hipLaunchKernelGGL((k_lm32<7, RT>), dim3(blocks), dim3(256), lds32, st, p, ngroups, m0);
-      } else {
-        SMI_LM_NOTE(L, RT ? "k_lm32<8,RT>" : "k_lm32<8>", blocks, 1, 256);
-        hipLaunchKernelGGL((k_lm32<8, RT>), dim3(blocks), dim3(256), lds32, st, p, ngroups, m0);
-      }
-    } else {
-      SMI_LM_NOTE(L, RT ? "k_lm<2,RT>" : "k_lm<2>", blocks, 1, 512);
-      hipLaunchKernelGGL((k_lm<2, RT>), dim3(blocks), dim3(512), 2 * lds, st, p, ngroups, m0);
-    }
-    SMI_LAUNCH_CHECK();
-  }
-  return SMI_OK;
+  return GemmPick{};
 }
 
+// One kernel of a decode step over M rows: operands, pick, launch.
 int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, float* logits, hipStream_t st) {
   const smi_llm_cfg& c = L->cfg;
   const bool fused = fuse_o_now(L, rows, M);
   GemmP p = gemm_operands(L, which, layer, L->dec, rows, M, L->NTh * 4);
   if (which == KLM) p.Y = logits ? logits : (logits_needed(L, step_feat(L)) ? L->logits : nullptr);
-  if (L->exact) {
+  PickEnv e = pick_env(L, 0);
+  e.fused = fused ? 1 : fuse2_now(L, rows, M) ? 2 : 0;
+  if (L->exact && which != KATTN && which != KFIN) {
     // verification mode: same operands, scalars and epilogues, fp32 weights, one exact fp32 FMA chain per output (k_gemm_x)
-    switch (which) {
-      case KQKV: return launch_gemm_x<PRO_NORM, EPI_QKV>(L, p, st);
-      case KO: return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
-      case KGU: return launch_gemm_x<PRO_NORM, EPI_SWIGLU>(L, p, st);
-      case KD: return launch_gemm_x<PRO_PLAIN, EPI_RESID>(L, p, st);
-      case KLM:
-        SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
-        return launch_gemm_x<PRO_NORM, EPI_LM>(L, p, st);
-    }
+    SMI_REQUIRE(which != KLM || (L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
+    return launch_form(L, p, pick_gemm(L, which, M, e), st);
   }
   switch (which) {
     case KQKV:
       // helpers: the first pf_qkv_eighths / 8 of this layer's gate_up slices (consumer block b reads weight tile row b).  Measured
       // at one row, graph step, one box (profiles/r03_prefetch.txt): 8/8 600 us, 6/8 569, 4/8 564, 2/8 559 (default), none 566-571
       p.pf = PfDesc{sec(L, SMI_LLM_WGU, layer), L->KTh * 1024, L->NTgu, 0, ((L->NTgu + 7) / 8 * L->pf_qkv_eighths + 7) / 8};
-      return launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV, 1, 0>(L, p, st);   // measured best (profiles/README.md)
+      e.has_pf = p.pf.base != nullptr;
+      return launch_form(L, p, pick_gemm(L, KQKV, M, e), st);
     case KATTN: {
       AttnP a = attn_operands(L, layer, L->dec, rows, M);
       a.slot_is_row = rows == L->rows && L->identity_slots;   // the live decode rows are (slot b, ...) in order (contiguous cache: slots contiguous; paged: through the page table)
@@ -4716,13 +4988,8 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       }
       return c.kv_dtype ? launch_attn<1>(L, a, st) : launch_attn<0>(L, a, st);
     }
-    case KO:
-      if (fused) return SMI_OK;   // done by the attention kernel (per-head partials) and gate_up's prologue
-      if (fuse2_now(L, rows, M)) return SMI_OK;   // done by the attention kernel (per-head partials + last-arriver head sum and epilogue)
-      // no helpers here: warming down_proj's 8.7 MB from o_proj (or from attention / gate_up) stretches the
-      // producer by more than the consumer gains (measured, profiles/README.md), so down_proj stays cold
-      // four row parts up to 8 rows: 629.8 -> 626.0 us per step once the prologues were down to one round trip
-      return launch_oproj(L, p, M, st);
+    case KO:   // (fused: done by the attention kernel, nothing to launch -- pick_o)
+      return launch_form(L, p, pick_gemm(L, KO, M, e), st);
     case KGU:
       if (fused) {
         p.part_o = L->part_o; p.n_oheads = c.num_heads; p.hres = L->dec.h; p.h2out = L->h2;
@@ -4731,32 +4998,20 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
         }
         p.gam = (const float*)sec(L, SMI_LLM_LN2, layer);
       }
-      // 69 VGPRs (>= 6 waves per SIMD): all 608 blocks are resident at once, no second round (step 745 -> 705 us)
-      return launch_gemm<1, 8, 2, 2, PRO_NORM, EPI_SWIGLU, 1, 2, 6>(L, p, st);
+      return launch_form(L, p, pick_gemm(L, KGU, M, e), st);
     case KD:
       p.wperm = L->wd_parts;
       if (fused) p.Yin = L->h2;   // h + o_proj, left there by gate_up's block 0
       // helpers: the next layer's QKV slices (its o_proj slices ride along: same slice size, contiguous-ish)
       if (layer + 1 < c.num_layers) p.pf = PfDesc{sec(L, SMI_LLM_WQKV, layer + 1), L->KTh * 1024, L->NTqkv, 0, (L->NTqkv + 7) / 8};
-      if (M >= kDcMin && M <= kMaxRows && !L->stamps_on && p.KT <= 160 && p.NT % 4 == 0)
-        return launch_down_chains(L, p, st);   // kDcMin .. 64 rows: the 16 chains on 16 different blocks + an in-order combine (k_downC)
-      // few rows: 4-row parts (224 blocks, -0.7 us); same bits either way, the zero-fed MFMAs cost at M > 8
-      // row parts (H blocks per weight tile) while the operand re-reads they cost stay small: measured step at
-      // 16 / 32 / 64 rows with H = 1 | 2 | 4: 930 | 915 | 900, 1064 | 1055 | 1161, 1318 | 1443 | 1671 us
-      if (M <= 8) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4>(L, p, st);
-      if (M <= 16) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 4, 0>(L, p, st);
-      if (M <= 32) return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 2, 0>(L, p, st);
-      return launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID, 1, 0>(L, p, st);
+      e.has_pf = p.pf.base != nullptr;
+      return launch_form(L, p, pick_gemm(L, KD, M, e), st);
     case KLM: {
-      const unsigned feat = step_feat(L);
-      p.stamps = L->stamps_on ? L->stamps : nullptr;
-      if (L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L, feat)) {   // every row constrained: only the union's tiles
-        p.tlist = L->tlist; p.ctl = L->ctl;
-        return launch_lm_persistent<1>(L, p, M, 0, st);
-      }
-      if (L->KTh <= 32) return launch_lm_persistent<0>(L, p, M, (L->NTlm + 1) / 2, st);
-      SMI_REQUIRE((L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
-      return launch_gemm<4, 4, 2, 1, PRO_NORM, EPI_LM>(L, p, st);
+      // every row constrained: only the union's tiles (the groups come from p.tlist, the rows' own ranges through p.ctl)
+      e.lm_restricted = L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L, step_feat(L));
+      if (e.lm_restricted) { p.tlist = L->tlist; p.ctl = L->ctl; }
+      SMI_REQUIRE(L->KTh <= 32 || (L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
+      return launch_form(L, p, pick_gemm(L, KLM, M, e), st);
     }
     case KFIN: {
       const unsigned feat = step_feat(L);
@@ -4785,40 +5040,6 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
   return SMI_EINVAL;
 }
 
-// One prefill GEMM over M rows (any M) with k_pgemm; `which` as in launch_one (GEMM kernels only).
-// nsplit > 1 (RESID with XMAP only): one block per (tile, K segment) writes its segment's sums to L->pslab and k_resid_comb adds
-// the segments in order and runs the epilogue -- the few-row form of the segmented sum (GemmP::kseg), same bits as the in-block form.
-template <int PRO, int EPI, int NTW = 2, int WR = 1, int RING = 0, int XMAP = 0, int TWO = 0, int MTB = 8>
-int launch_pgemm(const smi_llm* L, GemmP p, hipStream_t st, int nsplit = 1) {
-  constexpr int cols = (4 / WR) * NTW;   // weight tiles per block
-  constexpr int rows = MTB * 16;
-  const dim3 grid2((p.NT + cols - 1) / cols, (p.M + rows - 1) / rows);
-  dim3 grid = XMAP ? dim3(grid2.x * grid2.y) : grid2;
-  constexpr size_t lds = (RING ? (size_t)RING * (12 * rows + cols * 64) : (size_t)2 * 12 * rows) * 16 + (TWO ? 0 : rows * 4);
-  if constexpr (lds > 64 * 1024) {   // the instantiation (QKV: both cache types') was opted in by smi_llm_create (LdsBig)
-    static_cast<void>(LdsBig<k_pgemm<PRO, EPI, 0, NTW, WR, RING, XMAP, TWO, MTB>>::reg);
-    if constexpr (EPI == EPI_QKV) static_cast<void>(LdsBig<k_pgemm<PRO, EPI, 1, NTW, WR, RING, XMAP, TWO, MTB>>::reg);
-    static_assert(lds <= (size_t)kLdsBigBytes, "k_pgemm: LDS beyond the opted-in window");
-  }
-  const int mtiles = (p.M + 15) / 16;
-  if (nsplit > 1) {
-    SMI_REQUIRE(EPI == EPI_RESID && XMAP && RING >= 3 && p.kseg > 0 && nsplit <= 16, "launch_pgemm: split-K is the RESID ring form's");
-    SMI_REQUIRE(L->pslab && (size_t)nsplit * p.NT * mtiles * 1024 <= L->pslab_bytes, "launch_pgemm: partial slab too small");
-    p.slab = L->pslab; p.slab_mt = mtiles;
-    grid = dim3(grid2.x * grid2.y, nsplit);
-  }
-  with_kvf32<EPI>(L, [&](auto kv) { hipLaunchKernelGGL((k_pgemm<PRO, EPI, kv(), NTW, WR, RING, XMAP, TWO, MTB>), grid, dim3(256), lds, st, p); });
-  SMI_LAUNCH_CHECK();
-  if (nsplit > 1) {
-    DownCP d;
-    d.W = nullptr; d.NT = p.NT; d.KT = p.KT; d.M = p.M; d.wperm = 0; d.XS = nullptr; d.part = L->pslab;
-    d.Y = p.Y; d.Yin = p.Yin; d.gamma_next = p.gamma_next; d.XSout = p.XSout; d.ssout = p.ssout;
-    hipLaunchKernelGGL((k_resid_comb<1, 1>), dim3(p.NT * mtiles), dim3(64), 0, st, d, nsplit, mtiles);
-    SMI_LAUNCH_CHECK();
-  }
-  return SMI_OK;
-}
-
 // RMSNorm partials per row that a layer's QKV finds in the big workspace: [rows][NT * 4] as the row-grouped down_proj leaves them,
 // [rows][NT] as the prefill GEMM and its split-K combine do.  The kernel that fills a pass's layer-0 input (k_embed) is told the same.
 int pf_nparts_in(const smi_llm* L, int M, int family) {
@@ -4840,17 +5061,13 @@ int launch_layer_big(smi_llm* L, int l, const RowDesc* rows, int M, int family, 
   const bool gq = L->pg_forced ? M < L->pg_min[0] : !pg, go = L->pg_forced ? M < L->pg_min[1] : !pg,
              gg = L->pg_forced ? M < L->pg_min[2] : !pg, gd = L->pg_forced ? M < L->pg_min[3] : !pg;
   const int np_from_d = pf_nparts_in(L, M, family), np_from_o = go ? L->NTh * 4 : L->NTh;
-  // few rows: 64-column tiles (more blocks) and a deeper ring; o_proj / down_proj as one block per K segment + in-order combine
-  const bool few = M <= L->pg_split_rows && !(L->tune2 & kTune2PgemmRegs);
-  const int kseg_o = (L->KTq + kPgSegO - 1) / kPgSegO, kseg_d = (L->KTi + kPgSegD - 1) / kPgSegD;
-  const int nseg_o = (L->KTq + kseg_o - 1) / kseg_o, nseg_d = (L->KTi + kseg_d - 1) / kseg_d;
+  // each kernel: operands, pick (by its family and the row count; the k_pgemm forms and the split-K segments: pick_pgemm_rows), launch
+  auto launch = [&](int which, bool grouped, const GemmP& p) {
+    return launch_form(L, p, pick_gemm(L, which, M, pick_env(L, grouped ? PF_GROUPED : PF_PGEMM)), st);
+  };
   int rc;
   // QKV
-  const GemmP p = gemm_operands(L, KQKV, l, L->big, rows, M, np_from_d);
-  if (gq) rc = launch_gemm<1, 16, 2, 1, PRO_NORM, EPI_QKV>(L, p, st);
-  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_NORM, EPI_QKV>(L, p, st);
-  else if (few) rc = launch_pgemm<PRO_NORM, EPI_QKV, 2, 2, 6, 1, 0, 4>(L, p, st);
-  else rc = launch_pgemm<PRO_NORM, EPI_QKV, 6, 2, 3, 1>(L, p, st);
+  rc = launch(KQKV, gq, gemm_operands(L, KQKV, l, L->big, rows, M, np_from_d));
   if (rc || last_kernel == KQKV || l == c.num_layers - 1) return rc;
   // attention
   const AttnP a = attn_operands(L, l, L->big, rows, M);   // (slot_is_row = 0: prompt rows name their slot)
@@ -4863,28 +5080,15 @@ int launch_layer_big(smi_llm* L, int l, const RowDesc* rows, int M, int family, 
   SMI_LAUNCH_CHECK();
   if (last_kernel == KATTN) return SMI_OK;
   // o_proj
-  GemmP o = gemm_operands(L, KO, l, L->big, rows, M, np_from_d);
-  o.kseg = kseg_o;
-  if (go) rc = launch_oproj(L, o, M, st);
-  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, o, st);
-  else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, o, st, nseg_o);
-  else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, o, st);
+  rc = launch(KO, go, gemm_operands(L, KO, l, L->big, rows, M, np_from_d));
   if (rc || last_kernel == KO) return rc;
   // gate_up
-  const GemmP g = gemm_operands(L, KGU, l, L->big, rows, M, np_from_o);
-  if (gg) rc = launch_gemm<1, 8, 4, 1, PRO_NORM, EPI_SWIGLU, 1, 2>(L, g, st);
-  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 4>(L, g, st);
-  else if (few) rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 2, 2, 4, 0, 0, 4>(L, g, st);   // 64 KiB ring: two blocks per CU, the 304 blocks of a 127-row prompt in one round (ring of 6: 1.2 rounds, 30 us)
-  else rc = launch_pgemm<PRO_NORM, EPI_SWIGLU, 8, 2, 2, 0, 1>(L, g, st);
+  rc = launch(KGU, gg, gemm_operands(L, KGU, l, L->big, rows, M, np_from_o));
   if (rc || last_kernel == KGU) return rc;
   // down
   GemmP d = gemm_operands(L, KD, l, L->big, rows, M, np_from_o);   // (never the last layer's: gamma_next is the next LN1)
-  d.wperm = L->wd_parts; d.kseg = kseg_d;
-  if (gd) rc = launch_gemm<1, 16, 2, 5, PRO_PLAIN, EPI_RESID>(L, d, st);
-  else if (L->tune2 & kTune2PgemmRegs) rc = launch_pgemm<PRO_PLAIN, EPI_RESID>(L, d, st);
-  else if (few) rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 2, 2, 6, 1, 0, 4>(L, d, st, nseg_d);
-  else rc = launch_pgemm<PRO_PLAIN, EPI_RESID, 4, 2, 4, 1>(L, d, st);
-  return rc;
+  d.wperm = L->wd_parts;
+  return launch(KD, gd, d);
 }
 
 // All layers for the M prompt rows of one pass: K/V of every row appended, hidden states of the last layer never needed.
@@ -5210,8 +5414,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   // replaces), 2 rows 616 -> 640, one row (a retired switch, against the per-head partials every gate_up block sums) 543 -> 581:
   // the arrival count + the reads of write-through partials cost 3-4 us at one row, where a kernel boundary costs 1.8.
   { const char* e = smi_env("SPARKMI_FUSE2_ROWS"); L->fuse2_rows = e ? atoi(e) : 0; if (L->fuse2_rows > kFuse2Max) L->fuse2_rows = kFuse2Max; }
-  L->fuse_o = !smi_env("SPARKMI_NO_FUSE_O") && (cfg->num_heads == 14 || cfg->num_heads == 4) && cfg->num_heads <= kMaxOHeads &&
-              L->NTh % kFuseQB == 0 && L->NTh / kFuseQB <= kAttnWaves * kFuseOT && L->KTh * 8 <= 256;
+  L->fuse_o = !smi_env("SPARKMI_NO_FUSE_O") && fuse_o_fits(cfg->num_heads, L->NTh, L->KTh);
   { const char* e = smi_env("SPARKMI_TUNE2"); L->tune2 = e ? atoi(e) : 0; }
   { const char* e = smi_env("SPARKMI_PGEMM_MIN_ROWS"); L->pgemm_min_rows = e ? atoi(e) : 1280; }
   {
@@ -7142,6 +7345,52 @@ int smi_llm_pf_tiles(const int32_t* rows_host, int M, int32_t* out, int cap, int
   pf_tiles_build(rows.data(), M, T);
   for (size_t i = 0; i < T.size() && i < (size_t)cap; ++i) { out[4 * i] = T[i].m0; out[4 * i + 1] = T[i].n; out[4 * i + 2] = T[i].slot; out[4 * i + 3] = T[i].pos0; }
   *n = (int32_t)T.size();
+  return SMI_OK;
+}
+
+// Host only: the picks of a layer's four GEMMs and of lm_head (out[0..5): QKV, o_proj, gate_up, down_proj, lm_head) for M rows at
+// cfg's shape -- the functions launch_one / launch_layer_big pick with.  flags: the switches as plain values, -1 = as
+// smi_llm_create leaves the field without any switch; null: all of them.
+int smi_llm_gemm_forms(const smi_llm_cfg* cfg, int M, int layer_pos, const smi_gemm_flags* flags, smi_gemm_form_info* out) {
+  SMI_REQUIRE(cfg_ok(cfg) && out && M >= 1, "smi_llm_gemm_forms: invalid argument");
+  SMI_REQUIRE(layer_pos >= SMI_LAYER_FIRST && layer_pos <= SMI_LAYER_LAST, "smi_llm_gemm_forms: layer position %d", layer_pos);
+  smi_gemm_flags f;
+  if (flags) f = *flags;
+  else memset(&f, 0xff, sizeof(f));
+  SMI_REQUIRE(f.pass == -1 || f.pass == 0 || f.pass == PF_GROUPED || f.pass == PF_PGEMM, "smi_llm_gemm_forms: pass %d", f.pass);
+  SMI_REQUIRE(f.pass > 0 || M <= kMaxRows, "smi_llm_gemm_forms: a decode step has 1 .. %d rows", kMaxRows);
+  const int H = cfg->hidden_size, Q = cfg->num_heads * cfg->head_dim, KV = cfg->num_kv_heads * cfg->head_dim, I = cfg->intermediate_size;
+  const int KTh = H / 32, KTq = Q / 32, KTi = I / 32, NTqkv = (Q + 2 * KV) / 16, NTh = H / 16, NTgu = 2 * I / 16;
+  const int NTlm = (int)(make_layout(cfg).vpad / 16), lm_cap = (NTlm + 3) / 4;
+  PickEnv e{};
+  e.pass = f.pass < 0 ? 0 : f.pass;
+  e.exact = f.exact < 0 ? cfg->weights_exact : f.exact;
+  e.fused = f.fused < 0 ? (e.pass == 0 && M == 1 && !e.exact && fuse_o_fits(cfg->num_heads, NTh, KTh) ? 1 : 0) : f.fused;
+  e.stamps = f.stamps < 0 ? 0 : f.stamps; e.tune2 = f.tune2 < 0 ? 0 : f.tune2;
+  e.pf_mask = f.prefetch_mask < 0 ? 1 : f.prefetch_mask; e.pf_rows = f.prefetch_rows < 0 ? 1 : f.prefetch_rows;
+  e.kv_f32 = f.kv_f32 < 0 ? (cfg->kv_dtype ? 1 : 0) : f.kv_f32;
+  e.pg_split_rows = f.pg_split_rows < 0 ? kPgSplitRows : f.pg_split_rows;
+  e.lm_restricted = f.lm_restricted < 0 ? 0 : f.lm_restricted;
+  e.lm_blocks = f.lm_blocks < 0 ? (lm_cap < 512 ? lm_cap : 512) : f.lm_blocks;
+  SMI_REQUIRE(!e.lm_restricted || (KTh <= 32 && !e.exact), "smi_llm_gemm_forms: the restricted lm_head is the persistent kernels'");
+  GemmPick k[5];
+  e.has_pf = e.pass == 0;                                   // QKV's helpers: this layer's gate_up slices
+  k[0] = pick_qkv(KTh, NTqkv, M, e);
+  e.has_pf = 0;
+  k[1] = pick_o(KTq, NTh, cfg->num_heads, M, e);
+  k[2] = pick_gu(KTh, NTgu, cfg->num_heads, M, e);
+  e.has_pf = e.pass == 0 && layer_pos != SMI_LAYER_LAST;    // down_proj's: the next layer's QKV slices
+  k[3] = pick_d(KTi, NTh, M, e);
+  e.has_pf = 0; e.pass = 0;
+  k[4] = pick_lm(KTh, NTlm, M <= kMaxRows ? M : kMaxRows, e);
+  for (int i = 0; i < 5; ++i) {
+    SMI_REQUIRE(k[i].form != GF_BAD, "smi_llm_gemm_forms: kernel %d has no form for %d rows and these switches", i, M);
+    smi_gemm_form_info& o = out[i];
+    memset(&o, 0, sizeof(o));
+    gemm_form_name(k[i], o.kernel, sizeof(o.kernel));
+    o.launches = k[i].launches;
+    if (k[i].launches) { o.grid[0] = k[i].gx; o.grid[1] = k[i].gy; o.block = k[i].block; o.grid2 = k[i].gx2; o.lds_bytes = (int64_t)k[i].lds; }
+  }
   return SMI_OK;
 }
 

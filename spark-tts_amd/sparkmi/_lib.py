@@ -148,6 +148,25 @@ class HeadIO(C.Structure):
                 ("nblk", C.c_int32), ("launches", C.c_int32), ("grid", C.c_int32 * 2), ("block", C.c_int32), ("form", C.c_char * 32)]
 
 
+class GemmFlags(C.Structure):
+    """smi_gemm_flags: the switches a GEMM pick reads (smi_llm_gemm_forms); -1 = what smi_llm_create leaves without a switch"""
+    _fields_ = [(n, C.c_int32) for n in ("pass_", "fused", "stamps", "exact", "tune2", "prefetch_mask", "prefetch_rows", "kv_f32",
+                                         "pg_split_rows", "lm_restricted", "lm_blocks")]
+
+    def __init__(self, **kw):
+        super().__init__(**{n: kw.pop(n, -1) for n, _ in self._fields_})
+        if kw:
+            raise TypeError(f"GemmFlags: unknown field(s) {sorted(kw)}")
+
+
+class GemmFormInfo(C.Structure):
+    """smi_gemm_form_info: one picked launch (smi_llm_gemm_forms)"""
+    _fields_ = [("kernel", C.c_char * 96), ("grid", C.c_int32 * 2), ("block", C.c_int32), ("launches", C.c_int32), ("grid2", C.c_int32),
+                ("lds_bytes", C.c_int64)]
+
+
+SMI_LAYER_FIRST, SMI_LAYER_MIDDLE, SMI_LAYER_LAST = 0, 1, 2
+
 _VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
 _P = C.POINTER
 SYMBOLS = {
@@ -258,6 +277,7 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),
     "smi_llm_debug_prefill_layer": (_I, [_VP, _I, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),
     "smi_llm_pf_tiles": (_I, [_P(C.c_int32), _I, _P(C.c_int32), _I, _P(C.c_int32)]),
+    "smi_llm_gemm_forms": (_I, [_P(LLMCfg), _I, _I, _P(GemmFlags), _P(GemmFormInfo)]),
     "smi_conv_form_count": (_I, []),
     "smi_conv_form_get": (_I, [_I, _P(ConvForm)]),
     "smi_conv_plan": (_I, [_P(ConvCase), _P(ConvPlanInfo)]),
