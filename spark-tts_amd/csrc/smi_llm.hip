@@ -281,7 +281,14 @@ __device__ __forceinline__ void gemm_body(const GemmP& p) {
   static_assert(H == 1 || ((H == 2 || H == 4) && NTB == 1 && EPI == EPI_RESID), "row-split tiles: RESID, one tile per block");
   static_assert(PRO != PRO_FUSEDO || (LEAN == 2 && MT == 1 && EPI == EPI_SWIGLU), "PRO_FUSEDO: the one-row gate_up kernel");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // QHOT: the one-row QKV.  Its first MFMA waits for the operand staging load and the RMSNorm partials -- written by the previous
+  // launch, a full memory round trip away -- so these are requested first, from preloaded values only, before the row
+  // descriptor and any other field of the struct is read (below).  Its wave index is a scalar, so tile indices, clamps and tile
+  // base addresses are computed once per wave on the scalar unit and a load's address is a scalar base plus a 32-bit lane offset.
+  // (The same scalar wave index in gate_up and k_down1, with k_down1's block-id division replaced by compares: built, same
+  // bits, no faster on the step -- profiles/entry_loads_vs_parent.txt -- so they keep the parent's code.)
+  constexpr bool QHOT = LEAN == 2 && EPI == EPI_QKV && PRO == PRO_NORM && MT == 1 && NTB == 1 && WB == 1 && H == 1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = QHOT ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, NW * 64);
     return;
@@ -385,9 +392,66 @@ __device__ __forceinline__ void gemm_body(const GemmP& p) {
     }
     __builtin_amdgcn_sched_barrier(0);
   }
+  float qs0 = 0.f, qs1 = 0.f, qs2 = 0.f, qs3 = 0.f;   // QHOT: wave 0's RMSNorm partials (ss0 .. ss3 below)
+  if constexpr (QHOT) {
+    // Every address here is a preloaded base (W, XS, sspart) plus 32-bit offsets; a wave without a k tile (KT < NW) requests
+    // nothing.  The operand goes first: loads return in issue order, and the weights behind it are mostly L2-warm (gate_up and
+    // down_proj touch them) -- measured against weights first, graph step 487.9 against 489.4 us.
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const int tw = (KT - wave + NW - 1) / NW;          // this wave's k tiles
+    const int tl = lane >> 4, r = lane & 15;           // 16 lanes fetch a tile's 12 pieces: four tiles per round
+    u32x4 v0 = {0u, 0u, 0u, 0u};
+    auto req_w = [&]() {
 #pragma unroll
-  for (int b = 0; b < WB; ++b)
-    if (wave + b * NW * U < KT) load_w(w[b], wave + b * NW * U);
+      for (int u = 0; u < U; ++u) {
+        int j = wave + u * NW;
+        j = j < KT ? j : KT - 1;
+        const unsigned char* wb = (const unsigned char*)p.W + (((size_t)bx * KT + j) << 10);   // block bx is n tile bx (< NT)
+        w[0][u][0] = smi_ldw((const uint4*)(wb + (uint32_t)lane * 16u));
+      }
+    };
+    auto req_x = [&]() {
+      v0 = *(const u32x4*)(p.XS + (uint32_t)((wave + (tl < tw ? tl : tw - 1) * NW) * 192 + (r < 12 ? r : 11) * 16));
+      if (p.npart <= 256 && wave == 0) {   // ss_pre (below): the one row is wave 0's
+        const int last = p.npart - 1;
+        const unsigned char* sp = (const unsigned char*)p.sspart;
+        qs0 = *(const float*)(sp + (uint32_t)(lane < last ? lane : last) * 4u);
+        qs1 = *(const float*)(sp + (uint32_t)(lane + 64 < last ? lane + 64 : last) * 4u);
+        qs2 = *(const float*)(sp + (uint32_t)(lane + 128 < last ? lane + 128 : last) * 4u);
+        qs3 = *(const float*)(sp + (uint32_t)(lane + 192 < last ? lane + 192 : last) * 4u);
+      }
+    };
+    unsigned long long rdesc = 0;
+    if (tw > 0) {
+      req_x();
+      req_w();
+    }
+    // the row's descriptor sits at a uniform address, so it comes through the SCALAR cache (not counted by vmcnt).  Requested
+    // here, behind the vector requests; nothing looks at it before the wait below -- the compiler does not know that the pair is
+    // still being written, so no instruction may name it in between (tests/test_entry_waits_cpu.py reads the built library for
+    // that).  The descriptor is rewritten by k_finalize
+    // every step; like every compiler-scalarised load of data an earlier kernel wrote, this relies on the scalar-cache
+    // invalidate of the dispatch's acquire fence (with `glc` the load is 1.3 us slower: 630 -> 662 us per step).
+    if (wave == 0) asm volatile("s_load_dwordx2 %0, %1, 0x0" : "=s"(rdesc) : "s"(p.rows) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (tw > 0) {
+      // the staging wait: operand and partials (issued first: a counted wait, the two weight tiles behind them stay in flight)
+      asm volatile("" : "+v"(v0), "+v"(qs0), "+v"(qs1), "+v"(qs2), "+v"(qs3));
+      unsigned char* qbw = smem + (size_t)NW * NTB * MT * 1024 + 32 * 4 + NTB * 32 * 8 + (size_t)wave * p.ldsb;
+      if (tl < tw && r < 12) *(u32x4*)(qbw + ((size_t)tl * 12 + r) * 16) = v0;
+    }
+    // RoPE, bias and the KV append are epilogue work: the descriptor and the struct's other lines are first used from here on
+    if (wave == 0) {
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rdesc) : : "memory");
+      erd[0].slot = (int32_t)(uint32_t)rdesc;
+      erd[0].pos = (int32_t)(uint32_t)(rdesc >> 32);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
+#pragma unroll
+    for (int b = 0; b < WB; ++b)
+      if (wave + b * NW * U < KT) load_w(w[b], wave + b * NW * U);
+  }
   // PRO_FUSEDO (gate_up at one row, 608 blocks): every block also touches its share -- one wave-instruction, a dword per 64-byte
   // line -- of the NEXT layer's QKV weights, right behind its own weight loads: the 2 MB are then in the L2 of the XCD whose QKV
   // blocks read them (consumer slice s is read by block s; 72 slices, 8 XCDs: block j takes slice j mod 72 -- same XCD) when
@@ -403,21 +467,11 @@ __device__ __forceinline__ void gemm_body(const GemmP& p) {
       pf2v = *(const uint32_t*)(p.pf2_base + (size_t)sl * p.pf2_slice + (size_t)ln * 64);
     }
   }
-  if constexpr (LEAN == 2 && EPI == EPI_QKV) {
-    // one row: its descriptor sits at a uniform address, so it comes through the SCALAR cache -- not counted by vmcnt,
-    // hence the RoPE load that needs the position no longer waits for the weight tiles issued above (the compiler's
-    // counted wait for a vector load of the descriptor was vmcnt(1): descriptor AND weights).  The descriptor is rewritten
-    // by k_finalize every step; like every compiler-scalarised load of data an earlier kernel wrote, this relies on the
-    // scalar-cache invalidate of the dispatch's acquire fence (with `glc` the load is 1.3 us slower: 630 -> 662 us per step).
-    if (wave < NTB && nt0 + wave < NT) {
-      unsigned long long sp;
-      asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(sp) : "s"(p.rows) : "memory");
-      erd[0].slot = (int32_t)(uint32_t)sp;
-      erd[0].pos = (int32_t)(uint32_t)(sp >> 32);
-    }
-  }
+  static_assert(LEAN != 2 || EPI != EPI_QKV || QHOT, "one row, QKV: the form that reads its row descriptor above (QHOT)");
   // ---- epilogue operands that do not depend on the GEMM: requested BEFORE the operand staging below, so that the
-  // staging wait covers them too (behind it, the first MFMA waited one more L2 round trip for the bias / residual row)
+  // staging wait covers them too (behind it, the first MFMA waited one more L2 round trip for the bias / residual row).
+  // (Not so for QHOT: its staging is done by here, so bias and RoPE are requested BEHIND the staging wait -- they need the
+  // descriptor and the struct's lines, which that form reads only there -- and are in flight under the norm factor and the MFMAs.)
   float4 epre[MT], egam = make_float4(0.f, 0.f, 0.f, 0.f);
   float2 erope[MT][2];
   if (wave < NTB && nt0 + wave < NT) {
@@ -444,7 +498,7 @@ __device__ __forceinline__ void gemm_body(const GemmP& p) {
   const bool vlds = LEAN || (MT == 1 && p.ldsb > 0);
   // LEAN PRO_NORM kernels: the partial sums of squares of the row this wave owns (row `wave` of the group) are requested
   // together with its first staging round
-  float ss0 = 0.f, ss1 = 0.f, ss2 = 0.f, ss3 = 0.f;
+  float ss0 = qs0, ss1 = qs1, ss2 = qs2, ss3 = qs3;   // zeros, except QHOT: requested above
   const bool ss_pre = LEAN >= 1 && PRO == PRO_NORM && p.npart <= 256 && wave < MT * 16 && mbase + wave < M;
   unsigned char* bw = smem + (size_t)NW * NTB * MT * 1024 + 32 * 4 + NTB * 32 * 8 + (size_t)wave * p.ldsb;
   float* ssp = (float*)(smem + (size_t)NW * NTB * MT * 1024 + 32 * 4 + NTB * 32 * 8 + (size_t)NW * p.ldsb);   // PRO_FUSEDO: [K / 4] partial sums of squares
@@ -506,7 +560,9 @@ __device__ __forceinline__ void gemm_body(const GemmP& p) {
       }
     } else {
       int t0 = 0;
-      if constexpr (LEAN >= 1 && PRO == PRO_NORM) {
+      if constexpr (QHOT) {
+        if (tw > 0) t0 = per;   // the first round is in LDS already (above)
+      } else if constexpr (LEAN >= 1 && PRO == PRO_NORM) {
         // first staging round and this wave's RMSNorm partials (if it owns a row) behind ONE wait: two round trips -> one
         if (tw > 0) {
           typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -2228,7 +2284,8 @@ constexpr int kAttnSeg = 1024;   // tokens per segment (a multiple of the chunk 
 constexpr int kFuseQB = 4;       // fused o_proj: blocks per head -- each repeats the head's attention (latency-bound, the CUs are idle anyway)
                                  // and takes a quarter of W_o's n tiles: a CU pulls 28 KB of cold weights instead of 112 KB
 constexpr int kFuse2Max = 8;     // rows up to which several live rows take the fused attention + o_proj (FUSE = 2: last-arriver head sum)
-constexpr int kFuseOT = 2;       // W_o n tiles per wave (8 waves x 2 x 4 blocks x 16 = hidden sizes up to 1024)
+constexpr int kFuseMaxPos = 1 << 23;   // positions per slot up to which the one-row fused kernel runs: 2^23 * 64 dims * 4 B < 2^32 (32-bit K / V piece offsets)
+constexpr int kFuseOT = 2;      // W_o n tiles per wave (8 waves x 2 x 4 blocks x 16 = hidden sizes up to 1024)
 
 // k_attn's merge step 2, across the waves, for head dim d: each wave's sums rescaled to the block maximum and added in wave
 // order.  Every form of the kernel runs this one piece of code (the fused one-row kernel in each of its o_proj waves), so the
@@ -2313,10 +2370,21 @@ __device__ __forceinline__ void attn_body(const AttnP& p) {
   // FUSE: this head's output as B-operand pieces (FUSE == 1: one copy per o_proj wave, each wave merges for itself)
   __shared__ __attribute__((aligned(16))) unsigned char xsl[FUSE == 1 ? kAttnWaves * 2 * 3 * 4 * 16 : FUSE ? 2 * 3 * 4 * 16 : 16];
   __shared__ unsigned int s_last;   // FUSE == 2: this block was the last of its (row, quarter) to arrive
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // AHOT: the one-row fused kernel.  The wave index is a scalar (the o_proj waves' tile addresses and the attention waves' token
+  // index are then scalar base + lane offset), and the block id is split into (quarter, head) and the head into its KV head
+  // by compare-and-subtract on the scalar unit instead of three integer divisions in front of the q / K / V requests.
+  constexpr bool AHOT = ONE == 1 && FUSE == 1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = AHOT ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   if ((int)blockIdx.x >= p.work_blocks) {
     pf_run(p.pf, (int)blockIdx.x - p.work_blocks, (int)gridDim.x - p.work_blocks, tid, (FUSE ? 2 : 1) * kAttnWaves * 64);
     return;
+  }
+  int a_head = (int)blockIdx.x, a_q = 0, a_kvh = 0;   // AHOT: work_blocks = kFuseQB * n_heads, block = quarter * n_heads + head
+  if constexpr (AHOT) {
+    static_assert(kFuseQB == 4, "the quarter of a block id is found in two steps");
+    if (a_head >= 2 * p.n_heads) { a_head -= 2 * p.n_heads; a_q = 2; }
+    if (a_head >= p.n_heads) { a_head -= p.n_heads; a_q += 1; }
+    for (int h = a_head; h >= p.group; h -= p.group) ++a_kvh;   // head / group: at most n_kv - 1 trips
   }
   // FUSE == 2: natural block order (row, quarter, head), head fastest -- the 7 query heads of a KV group and the four quarter
   // blocks of a row are neighbours; XCD x takes the x-th contiguous eighth of it (as the unfused batched kernel does)
@@ -2325,7 +2393,8 @@ __device__ __forceinline__ void attn_body(const AttnP& p) {
     const unsigned total = (unsigned)p.work_blocks, xcd = fbid & 7u, slot = fbid >> 3, q8 = total >> 3, r8 = total & 7u;
     fbid = xcd * q8 + (xcd < r8 ? xcd : r8) + slot;
   }
-  const int f_head = FUSE ? (int)(fbid % (unsigned)p.n_heads) : 0, f_q = FUSE ? (int)(fbid / (unsigned)p.n_heads) % kFuseQB : 0,
+  const int f_head = AHOT ? a_head : FUSE ? (int)(fbid % (unsigned)p.n_heads) : 0,
+            f_q = AHOT ? a_q : FUSE ? (int)(fbid / (unsigned)p.n_heads) % kFuseQB : 0,
             f_row = FUSE == 2 ? (int)(fbid / (unsigned)(p.n_heads * kFuseQB)) : 0;
   if constexpr (FUSE) {
     if (wave >= kAttnWaves) {   // the o_proj waves: tiles (nt, half * n_heads + head), nt = fq * fper + (wave - 8) + 8 i
@@ -2389,13 +2458,13 @@ __device__ __forceinline__ void attn_body(const AttnP& p) {
     const unsigned total = (unsigned)p.work_blocks, xcd = bid & 7u, slot = bid >> 3, q8 = total >> 3, r8 = total & 7u;
     bid = xcd * q8 + (xcd < r8 ? xcd : r8) + slot;
   }
-  const int head = FUSE == 2 ? f_head : ONE == 1 ? (FUSE ? (int)bid % p.n_heads : (int)bid) : ONE == 2 ? (int)bid % p.n_heads : (int)(bid / p.nseg) % p.n_heads,
+  const int head = (FUSE == 2 || AHOT) ? f_head : ONE == 1 ? (FUSE ? (int)bid % p.n_heads : (int)bid) : ONE == 2 ? (int)bid % p.n_heads : (int)(bid / p.nseg) % p.n_heads,
             m = FUSE == 2 ? f_row : ONE == 1 ? 0 : ONE == 2 ? (int)bid / p.n_heads : (int)bid / (p.nseg * p.n_heads),
             seg = ONE ? 0 : (int)bid % p.nseg;
   const int tl = lane / LPT, dl = lane % LPT;
   const int grp = wave * TPW + tl;
   const RowDesc rd = p.rows[m];
-  const int kvh = head / p.group;
+  const int kvh = AHOT ? a_kvh : head / p.group;
   // decode rows use slot == row, so the K/V addresses do not depend on the descriptor and the first
   // chunk's loads leave together with it (positions beyond ctx are valid cache memory, masked later)
   const bool sir = ONE || p.slot_is_row;
@@ -2425,6 +2494,13 @@ __device__ __forceinline__ void attn_body(const AttnP& p) {
     for (int u = 0; u < UNR; ++u) {
       const int t = c0 + u * NGRP + grp;
       const int tc = sir ? (t < p.max_pos ? t : p.max_pos - 1) : (t < ctx ? t : ctx - 1);
+      if constexpr (AHOT && !PG) {   // the (slot 0, KV head) row's base is a scalar; a token's piece is a 32-bit offset from it
+        constexpr uint32_t ES = KVF32 ? 4u : 2u;   // (max_pos * 64 * ES < 2^32: smi_llm_create leaves fuse_o off beyond kFuseMaxPos positions)
+        const uint32_t o = ((uint32_t)tc * kHeadDim + (uint32_t)(dl * DPL)) * ES;
+        kr[u] = *(const uint4*)((const unsigned char*)p.kcache + rowbase * (kHeadDim * ES) + o);
+        vr[u] = *(const uint4*)((const unsigned char*)p.vcache + rowbase * (kHeadDim * ES) + o);
+        continue;
+      }
       const size_t off = ((ONE && !PG) ? rowbase + tc : kv_row(p.km, slot, kvh, p.n_kv, p.max_pos, tc)) * kHeadDim + dl * DPL;
       if (KVF32) {
         kr[u] = *(const uint4*)((const float*)p.kcache + off);
@@ -4724,7 +4800,8 @@ template <int KVF32>
 int launch_attn(smi_llm* L, AttnP a, hipStream_t st) {
   a.nseg = L->attn_seg < 1 ? 1 : L->attn_seg;
   a.work_blocks = a.n_heads * a.M * a.nseg;
-  const bool fuse = a.M == 1 && a.nseg == 1 && a.slot_is_row && a.part_o && !a.cnt;
+  // (the one-row fused kernel addresses a token's K / V piece by a 32-bit byte offset inside the KV head's row: kFuseMaxPos)
+  const bool fuse = a.M == 1 && a.nseg == 1 && a.slot_is_row && a.part_o && !a.cnt && a.max_pos <= kFuseMaxPos;
   const bool fuse2 = a.nseg == 1 && a.slot_is_row && a.part_o && a.cnt;   // (a.cnt is only set by fuse2_now)   // 2 .. 8 rows: fused o_proj + last-arriver head sum
   if (fuse || fuse2) a.work_blocks *= kFuseQB;
   if (a.nseg > 1) {
@@ -5430,6 +5507,7 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->wd_parts = cfg->wd_plain ? 0 : 1;   // the arena's W_down tile order comes with its config (never from the environment)
   L->exact = cfg->weights_exact;
   if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
+  if (cfg->max_positions > kFuseMaxPos) L->fuse_o = 0;   // (the one-row fused kernel's 32-bit K / V piece offsets)
   L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
   L->dbg_pf_rows = 0;
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
