@@ -322,6 +322,11 @@ int smi_enc_rows_debug_io(smi_enc* h, int row, const char* buffer_name, int writ
 int smi_enc_rows_debug_run(smi_enc* h, int first, int last, void* stream);
 int smi_enc_rows_debug_stage(smi_enc* h, int row, const char* name, float* out_dev, size_t max_floats, int32_t* dims, void* stream);
 
+/* Device memory the library's handles and entry points hold in this process right now (every allocation has one owner,
+ * csrc/smi_common.h: DevBuf): *live_buffers allocations of *live_bytes bytes in all, pinned host staging included.  Either
+ * pointer may be null.  Both return to their earlier values when a handle is destroyed (tests/test_dev_owner_gpu.py). */
+int smi_debug_dev_memory(long long* live_buffers, long long* live_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -319,7 +319,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_join_rows(JnArgs a, JnState s, con
 
 struct smi_rs {
   int max_rows, max_in, max_out;
-  float* pool;
+  DevBuf<float> pool;
   int pool_used;
   std::vector<Filter> filters;
 };
@@ -333,7 +333,7 @@ struct smi_join {
   JnState s;
   int max_chunk, n_taps;
   size_t lds;
-  char* pool;
+  DevBuf<char> pool;
   std::vector<JnStream> streams;
 };
 
@@ -391,11 +391,9 @@ int smi_rs_create(int max_rows, int max_in, int max_out, smi_rs** out) {
   if (rc) return rc;
   smi_rs* h = new smi_rs();
   h->max_rows = max_rows; h->max_in = max_in; h->max_out = max_out;
-  h->pool = nullptr; h->pool_used = 0;
-  if (hipMalloc((void**)&h->pool, (size_t)RS_POOL_FLOATS * sizeof(float)) != hipSuccess) {
+  if (h->pool.alloc((size_t)RS_POOL_FLOATS * sizeof(float), "smi_rs_create: tap pool")) {
     (void)hipGetLastError();
     delete h;
-    smi_set_error("smi_rs_create: device allocation of the tap pool failed");
     return SMI_ENOMEM;
   }
   *out = h;
@@ -403,8 +401,6 @@ int smi_rs_create(int max_rows, int max_in, int max_out, smi_rs** out) {
 }
 
 int smi_rs_destroy(smi_rs* h) {
-  if (!h) return SMI_OK;
-  if (h->pool) (void)hipFree(h->pool);
   delete h;
   return SMI_OK;
 }
@@ -519,7 +515,7 @@ int smi_join_create(int max_streams, int max_chunk, int overlap, const double* f
   const int rc = smi_device_check(arch, sizeof(arch));
   if (rc) return rc;
   smi_join* h = new smi_join();
-  h->max_chunk = max_chunk; h->n_taps = copy ? 1 : n_taps; h->pool = nullptr;
+  h->max_chunk = max_chunk; h->n_taps = copy ? 1 : n_taps;
   JnState& s = h->s;
   s.max_streams = max_streams; s.overlap = overlap; s.up = up; s.down = down; s.half = half;
   s.hs = copy ? 0 : (int)((2LL * half + down + up - 1) / up) + 1;
@@ -528,13 +524,12 @@ int smi_join_create(int max_streams, int max_chunk, int overlap, const double* f
   const size_t n_tail = 2 * (size_t)max_streams * overlap, n_hist = 2 * (size_t)max_streams * s.hs;
   const size_t f64 = 2 * (size_t)overlap * sizeof(double);
   const size_t bytes = f64 + ((size_t)h->n_taps + n_tail + n_hist) * sizeof(float);
-  if (hipMalloc((void**)&h->pool, bytes) != hipSuccess) {
+  if (h->pool.alloc(bytes, "smi_join_create: stream state")) {
     (void)hipGetLastError();
     delete h;
-    smi_set_error("smi_join_create: device allocation of %zu bytes of stream state failed", bytes);
     return SMI_ENOMEM;
   }
-  double* fd = (double*)h->pool;
+  double* fd = (double*)h->pool.get();
   float* ff = (float*)(h->pool + f64);
   s.fade_in = fd; s.fade_out = fd + overlap;
   s.taps = ff; s.tail = ff + h->n_taps; s.hist = s.tail + n_tail;
@@ -547,7 +542,6 @@ int smi_join_create(int max_streams, int max_chunk, int overlap, const double* f
   if (e == hipSuccess) e = hipMemcpy(ff, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     smi_set_error("smi_join_create: upload of the fade tables and taps: %s", hipGetErrorString(e));
-    (void)hipFree(h->pool);
     delete h;
     return SMI_EHIP;
   }
@@ -557,8 +551,6 @@ int smi_join_create(int max_streams, int max_chunk, int overlap, const double* f
 }
 
 int smi_join_destroy(smi_join* h) {
-  if (!h) return SMI_OK;
-  if (h->pool) (void)hipFree(h->pool);
   delete h;
   return SMI_OK;
 }

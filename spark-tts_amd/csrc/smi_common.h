@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdlib.h>
+#include <atomic>
 #include "sparkmi.h"
 #ifdef SMI_DIAG
 #include "sparkmi_debug.h"
@@ -54,6 +55,61 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 static inline size_t smi_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Owner of one hipMalloc allocation (PINNED: one hipHostMalloc allocation).  Every device buffer of a handle and every device
+// temporary of an entry point is one of these: it is freed when its owner goes, on every path.  The owner frees and never waits:
+// a caller whose kernels may still use the buffer synchronises first, as it did before the buffer had an owner.
+// alloc / alloc_zero / ensure return SMI_OK, SMI_ENOMEM (the allocation failed) or SMI_EHIP (the zeroing failed) with the error
+// text set, and leave the owner empty on failure.  g_smi_dev_live / g_smi_dev_bytes (smi_core.hip) count what all owners of the
+// process hold.
+extern std::atomic<long long> g_smi_dev_live, g_smi_dev_bytes;
+template <class T, bool PINNED = false>
+class DevBuf {
+  T* p_ = nullptr;
+  size_t bytes_ = 0;
+
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { reset(); p_ = o.p_; bytes_ = o.bytes_; o.p_ = nullptr; o.bytes_ = 0; }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  operator T*() const { return p_; }
+  T* get() const { return p_; }   // (for a cast to another pointer type)
+  T* operator->() const { return p_; }
+  size_t bytes() const { return bytes_; }
+  void reset() {
+    if (!p_) return;
+    (void)(PINNED ? hipHostFree((void*)p_) : hipFree((void*)p_));
+    --g_smi_dev_live; g_smi_dev_bytes -= (long long)bytes_;
+    p_ = nullptr; bytes_ = 0;
+  }
+  int alloc(size_t bytes, const char* what) {
+    reset();
+    void* q = nullptr;
+    if ((PINNED ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes)) != hipSuccess) {
+      smi_set_error("%s(%s, %zu bytes) failed", PINNED ? "hipHostMalloc" : "hipMalloc", what, bytes);
+      return SMI_ENOMEM;
+    }
+    if (q) { p_ = (T*)q; bytes_ = bytes; ++g_smi_dev_live; g_smi_dev_bytes += (long long)bytes; }
+    return SMI_OK;
+  }
+  int alloc_zero(size_t bytes, const char* what) {
+    if (int rc = alloc(bytes, what)) return rc;
+    if (p_ && hipMemset((void*)p_, 0, bytes) != hipSuccess) {
+      reset();
+      smi_set_error("hipMemset(%s, %zu bytes) failed", what, bytes);
+      return SMI_EHIP;
+    }
+    return SMI_OK;
+  }
+  // grow-only: what is large enough stays (same address); the caller chooses the slack and flushes what holds the old address
+  int ensure(size_t bytes, const char* what) { return bytes <= bytes_ ? SMI_OK : alloc(bytes, what); }
+};
 
 #ifdef __HIPCC__
 __device__ __forceinline__ float smi_bf16_to_f32(uint32_t b) { return __uint_as_float(b << 16); }

@@ -13,6 +13,8 @@ void smi_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+std::atomic<long long> g_smi_dev_live{0}, g_smi_dev_bytes{0};   // what the DevBuf owners of the process hold (smi_common.h)
+
 extern "C" {
 
 int smi_version(void) { return SMI_ABI_VERSION; }
@@ -34,5 +36,13 @@ int smi_device_check(char* name, int n) {
   }
   return SMI_OK;
 }
+
+#ifdef SMI_DIAG
+int smi_debug_dev_memory(long long* live_buffers, long long* live_bytes) {
+  if (live_buffers) *live_buffers = g_smi_dev_live.load();
+  if (live_bytes) *live_bytes = g_smi_dev_bytes.load();
+  return SMI_OK;
+}
+#endif
 
 }  // extern "C"

@@ -571,17 +571,17 @@ struct smi_enc {
   smi_enc_cfg cfg;
   EncLayout lay;
   const unsigned char* arena;
-  float *cbn, *c2;                          // normalised codebook, |c|^2
+  DevBuf<float> cbn, c2;                    // normalised codebook, |c|^2
   struct Stage { const float* ptr; int rows, cols, stride; };
   // A workspace: max_rows slabs, a slab holding every working buffer of one row (enc_buffers) at `off`, the rows' lengths by
   // kind, and the launch list last built on it with its debug views.  The handle has two: `solo` (one row of the config's own
   // limits, allocated at create; smi_enc_forward and its graphs) and `rows` (smi_enc_rows_reserve; smi_enc_forward_rows).
   struct Ws {
     int max_rows = 0, max_samples = 0, max_ref = 0;
-    float* ws = nullptr;
+    DevBuf<float> ws;
     long long slab = 0;                     // floats per row: the one batch stride of every buffer
     std::map<std::string, size_t> off, floats;
-    int* lens_dev = nullptr;                // [length kind][max_rows]
+    DevBuf<int> lens_dev;                   // [length kind][max_rows]
     std::vector<int32_t> host_lens;
     std::vector<Launch> prog;
     std::vector<int> run_start;             // first row of every run of the last list
@@ -626,23 +626,15 @@ bool ent_is_bf(const smi_enc* h, const std::string& name) {
   return false;
 }
 
-void ws_free(smi_enc::Ws& W) {
-  if (W.ws) (void)hipFree(W.ws);
-  if (W.lens_dev) (void)hipFree(W.lens_dev);
-  W = smi_enc::Ws();
-}
-
 // W becomes a workspace of max_rows rows of up to max_samples / max_ref; what it held is freed first.  On failure W is empty.
 int ws_alloc(const smi_enc_cfg& c, smi_enc::Ws& W, const char* who, int max_rows, int max_samples, int max_ref) {
-  ws_free(W);
+  W = smi_enc::Ws();
   W.floats = enc_buffers(c, max_samples, max_ref);
   size_t o = 0;
   for (const auto& kv : W.floats) { W.off[kv.first] = o; o += smi_align_up(kv.second, 64); }
   W.slab = (long long)o;
-  if (hipMalloc((void**)&W.ws, (size_t)max_rows * o * 4) != hipSuccess ||
-      hipMalloc((void**)&W.lens_dev, (size_t)LK_COUNT * max_rows * 4) != hipSuccess) {
-    ws_free(W);
-    smi_set_error("%s: device allocation of %d rows x %zu bytes failed", who, max_rows, o * 4);
+  if (W.ws.alloc((size_t)max_rows * o * 4, who) || W.lens_dev.alloc((size_t)LK_COUNT * max_rows * 4, who)) {
+    W = smi_enc::Ws();
     return SMI_EHIP;
   }
   W.max_rows = max_rows; W.max_samples = max_samples; W.max_ref = max_ref;
@@ -690,7 +682,6 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
   h->cfg = *cfg;
   h->lay = enc_layout(cfg);
   h->arena = (const unsigned char*)arena_dev;
-  h->cbn = h->c2 = nullptr; h->ev0 = h->ev1 = nullptr; h->last_frames = 0;
   if (arena_bytes < h->lay.total) {
     smi_set_error("smi_enc_create: arena is %zu bytes, layout needs %zu", arena_bytes, h->lay.total);
     delete h;
@@ -719,15 +710,16 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
       return SMI_EHIP;
     }
   }
-  const bool ok = ws_alloc(c, h->solo, "smi_enc_create", 1, c.max_samples, c.max_ref_samples) == SMI_OK &&
-       hipMalloc((void**)&h->cbn, (size_t)c.codebook_size * c.codebook_dim * 4) == hipSuccess &&
-       hipMalloc((void**)&h->c2, (size_t)c.codebook_size * 4) == hipSuccess &&
-       hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess &&
-       hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking) == hipSuccess &&
-       hipEventCreateWithFlags(&h->gev0, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&h->gev1, hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    smi_set_error("smi_enc_create: device allocation failed");
+  if (ws_alloc(c, h->solo, "smi_enc_create", 1, c.max_samples, c.max_ref_samples) ||
+      h->cbn.alloc((size_t)c.codebook_size * c.codebook_dim * 4, "smi_enc_create: cbn") || h->c2.alloc((size_t)c.codebook_size * 4, "smi_enc_create: c2")) {
+    smi_enc_destroy(h);
+    return SMI_EHIP;
+  }
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
+      hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&h->gev0, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&h->gev1, hipEventDisableTiming) != hipSuccess) {
+    smi_set_error("smi_enc_create: event / stream creation failed");
     smi_enc_destroy(h);
     return SMI_EHIP;
   }
@@ -744,10 +736,6 @@ int smi_enc_create(const smi_enc_cfg* cfg, const void* arena_dev, size_t arena_b
 
 int smi_enc_destroy(smi_enc* h) {
   if (!h) return SMI_OK;
-  if (h->cbn) (void)hipFree(h->cbn);
-  if (h->c2) (void)hipFree(h->c2);
-  ws_free(h->solo);
-  ws_free(h->rows);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   for (auto& kv : h->graphs)

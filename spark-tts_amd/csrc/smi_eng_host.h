@@ -157,11 +157,11 @@ inline bool eng_build_plan(int H, int Q, int KV, int I, int n_heads, int ncu, En
 
 struct EngState {
   int enabled = 0, ncu = 0, maxlen = 0, lds = 0, gran_per_buf = 0;
-  EngCuPlan* plan = nullptr;
-  unsigned char* stream = nullptr;
-  smi_u64* gran = nullptr;
-  unsigned* words = nullptr;          // [0] serial, [4..7] err, [8] arrive
-  unsigned long long* stamps = nullptr;
+  DevBuf<EngCuPlan> plan;
+  DevBuf<unsigned char> stream;
+  DevBuf<smi_u64> gran;
+  DevBuf<unsigned> words;             // [0] serial, [4..7] err, [8] arrive
+  DevBuf<unsigned long long> stamps;
   unsigned timeout_ticks = 0;
   int ld_burst = 16, ld_sleep = 0, poll_quiet = 1;
   int edge_delay[5] = {16, 16, 16, 16, 16};

@@ -3894,9 +3894,24 @@ Layout make_layout(const smi_llm_cfg* c) {
 // The activation buffers of one pass over the layers, for some number of rows (gemm_operands / attn_operands name them to the
 // kernels).
 struct Work {
-  float *h, *q;                             // residual rows [rows][H]; QKV's query output [rows][Q]
-  unsigned char *xs_h, *xs_attn, *xs_act;   // GEMM operands as exact bf16 triples ([K/32][3][4][M][16 B])
-  float* ss;                                // [rows][NTh * 4] partial sums of squares of h (RMSNorm), one per 4 columns
+  DevBuf<float> h, q;                             // residual rows [rows][H]; QKV's query output [rows][Q]
+  DevBuf<unsigned char> xs_h, xs_attn, xs_act;    // GEMM operands as exact bf16 triples ([K/32][3][4][M][16 B])
+  DevBuf<float> ss;                               // [rows][NTh * 4] partial sums of squares of h (RMSNorm), one per 4 columns
+};
+
+// The diagnostics switches of the launch path, read once per handle by read_switches; the product build reads no
+// environment and gets the defaults.
+struct Switches {
+  int prefetch_mask, prefetch_rows;   // same-XCD L2 prefetch by helper blocks: one bit per producer kernel, up to this many live rows
+  int pf_qkv_eighths;   // how much of gate_up QKV's helpers prefetch, in eighths
+  int pf_inline;        // gate_up's work blocks touch the next layer's QKV weights
+  int tune2;            // bit mask (the kTune2* bits)
+  int fuse2_rows;       // rows up to which 2+ live rows take the fused attention + o_proj with the last-arriver head sum
+  int pg_split_rows;    // passes of up to this many rows take the few-row prefill GEMM shapes / split-K
+  int pg_min[4];        // prompt rows from which the prefill GEMM replaces the row-grouped decode GEMM, per kernel (QKV, o_proj, gate_up, down)
+  int pg_forced;        // a SPARKMI_PGEMM_MIN_* is set: kernels picked per launch by the pass's row count, as in round 3
+  int attn_pf2;         // bf16 KV: prefill attention on the matrix pipes
+  int no_fuse_o;        // one-row decode with the separate o_proj kernel
 };
 
 }  // namespace
@@ -3909,49 +3924,44 @@ struct smi_llm {
   // device scratch
   Work dec;            // the decode rows' workspace (kMaxRows rows)
   Work big; int big_rows;   // prefill workspace for up to big_rows rows at once (allocated at the first multi-chunk prefill)
-  float4* pslab; size_t pslab_bytes;   // k_pgemm split-K partial sums (prompt rows passes of up to kPgSplitRows rows)
-  int pg_split_rows;    // passes of up to this many rows take the few-row prefill GEMM shapes / split-K (kPgSplitRows; SPARKMI_PG_SPLIT_ROWS: A/B, same bits)
-  int pg_forced;        // diagnostics: SPARKMI_PGEMM_MIN_* set -- kernels picked per launch by the pass's row count, as in round 3
-  float *part_o, *h2;  // fused o_proj (one row): per-head partials [heads][H]; h + o_proj [H]
-  float4* dpart;       // chain-split down_proj (k_downC): [16 chains][NTh][4 m-tiles][64] chain sums
-  int fuse_o;          // config allows the fused o_proj (SPARKMI_NO_FUSE_O=1 turns it off)
-  int fuse2_rows;      // rows up to which 2+ live rows take the fused attention + o_proj with the last-arriver head sum (diagnostics: SPARKMI_FUSE2_ROWS; default 0 = off: measured slower)
-  unsigned int* fuse_cnt;   // [kFuse2Max][kFuseQB] arrival counters of that kernel (zero between launches)
-  RowDesc* rows;       // live decode rows [kMaxRows]
-  RowDesc* plan;       // prefill plan
-  PfTile* pf_tiles;     // prefill attention tiles of the row group in flight (k_attn_pf2)
-  size_t pf_tiles_cap;
+  DevBuf<float4> pslab;     // k_pgemm split-K partial sums (prompt rows passes of up to kPgSplitRows rows)
+  Switches sw;          // the diagnostics switches (read_switches)
+  DevBuf<float> part_o, h2;   // fused o_proj (one row): per-head partials [heads][H]; h + o_proj [H]
+  DevBuf<float4> dpart;       // chain-split down_proj (k_downC): [16 chains][NTh][4 m-tiles][64] chain sums
+  int fuse_o;          // config allows the fused o_proj (and Switches::no_fuse_o is clear)
+  DevBuf<unsigned int> fuse_cnt;   // [kFuse2Max][kFuseQB] arrival counters of that kernel (zero between launches)
+  DevBuf<RowDesc> rows;       // live decode rows [kMaxRows]
+  DevBuf<RowDesc> plan;       // prefill plan (grows on demand: ensure_plan)
+  DevBuf<PfTile> pf_tiles;    // prefill attention tiles of the row group in flight (k_attn_pf2; grows on demand)
   int pf_ntiles;
   std::vector<PfTile> host_tiles;
-  int attn_pf2;         // bf16 KV: prefill attention on the matrix pipes (SPARKMI_ATTN_PF2=0: one wave per (row, head))
   int dbg_pf_rows;      // diagnostics: rows the last smi_llm_debug_prefill_layer left in the big workspace (smi_llm_debug_read 16 .. 20)
-  size_t plan_cap;     // rows
-  float* pval; int* pidx; int lm_blocks, lm_cap;
-  int64_t* hist; int32_t *count, *finished, *step;
-  void *kcache, *vcache; size_t kv_layer_elems;
+  DevBuf<float> pval; DevBuf<int> pidx; int lm_blocks, lm_cap;
+  DevBuf<int64_t> hist; DevBuf<int32_t> count, finished, step;
+  DevBuf<void> kcache, vcache; size_t kv_layer_elems;
   int B; int started;
   // paged KV cache (cfg.kv_page_tokens > 0): page table [max_slots][ppslot] on the device, mirrored on the host
   int paged, pshift, ppslot;
-  int32_t* ptab;
+  DevBuf<int32_t> ptab;
   std::vector<int32_t> hptab;
   std::vector<int32_t> free_pages;
   std::vector<int32_t> page_ref;   // [kv_pages] slots whose table rows hold the page (> 1: shared by forked takes)
   int slot_pages[kMaxRows];     // pages a slot holds
-  Ctl hctl; Ctl* ctl;   // host copy / device block of the generation controls
+  Ctl hctl; DevBuf<Ctl> ctl;   // host copy / device block of the generation controls
   int admit_seq;        // sequences admitted so far in this generation / session (sampler stream ids)
   // One bookkeeping for plain generation and sessions: a sequence sits in a KV slot (slot_busy / slot_len) and the live rows map
   // to slots through live_order.  smi_llm_prefill is slots 0 .. B-1 in order; in a session (continuous batching) admissions and
   // retirements change the set, so rows map to arbitrary slots.  `session` only gates admit / retire.
-  int session, identity_slots;
+  int session, identity_slots = 1;
   std::vector<int> live_order;   // the KV slot of every live row, in row order (what the device row list holds)
-  int attn_seg;                        // context segments per (head, row) of the attention launches being issued (1 = unsplit)
-  float* apart; size_t apart_floats;   // segment partials [rows][heads][attn_seg][66]
+  int attn_seg = 1;                    // context segments per (head, row) of the attention launches being issued (1 = unsplit)
+  DevBuf<float> apart;                 // segment partials [rows][heads][attn_seg][66] (grows on demand: ensure_apart)
   int slot_busy[kMaxRows], slot_len[kMaxRows];      // host: slot in use; prompt length + tokens emitted (cache positions used)
   int slot_plen[kMaxRows];      // host: the prompt length of the sequence in the slot (slot_len - slot_plen = its token index)
   uint64_t handle_id, session_gen;   // blob stamps: this handle among the process's, and its generations / sessions so far (gen_reset)
   std::vector<unsigned char> host_blob;   // host staging of the blob headers a save uploads
   // sampling state (smi_llm_set_sampling)
-  int do_sample, top_k; float temperature, top_p; unsigned long long seed;
+  int do_sample, top_k = 50; float temperature = 0.8f, top_p = 0.95f; unsigned long long seed;
   // host: what the record set of the sequence in each slot (live or being admitted) asks of a step, F_* bits: its sampling record
   // is SMI_SAMPLING_SAMPLE, it has a penalty record (PenRec::on), returns log-probabilities (Ctl::lp), is constrained
   // (Ctl::allow, n > 0), has bias entries (SeqRec::n_bias > 0), has stop sequences (SeqRec::n_stop > 0), bans repeated
@@ -3959,28 +3969,22 @@ struct smi_llm {
   uint8_t slot_feat[kMaxRows];
   int lm_restrict;              // host: every row of the steps being issued is constrained (the restricted lm_head may run)
   int seq_dirty[kMaxRows];      // host: the slot's device record is not all zero (an admission without a record clears it)
-  SeqRec* seq;                  // device: per-slot bias / stop records [kMaxRows] (smi_llm_admit_biased)
+  DevBuf<SeqRec> seq;           // device: per-slot bias / stop records [kMaxRows] (smi_llm_admit_biased)
   std::vector<SeqRec> hseq;     // host: what the device records hold
-  int32_t* pctx;                // device: prompt ids [max_slots][max_positions], the n-gram ban's context store (smi_llm_admit_ngram)
+  DevBuf<int32_t> pctx;         // device: prompt ids [max_slots][max_positions], the n-gram ban's context store (smi_llm_admit_ngram)
   std::vector<int32_t> host_pctx;   // host staging of the rows an admission writes
-  int* tlist;                   // device: {count, vocabulary tiles ascending} -- the union of the constrained slots' tiles
+  DevBuf<int> tlist;            // device: {count, vocabulary tiles ascending} -- the union of the constrained slots' tiles
   std::vector<int32_t> host_tlist;
-  float* lp;                    // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
-  float* lp_part; float2* lp_rowc;   // k_logprob -> k_finalize: [kMaxRows][kLpBlocks] partial sums, [kMaxRows] (max, 1/T)
-  uint16_t* phist;              // penalty histories [max_slots][vocab] (k_penalize, k_finalize)
-  int64_t* poll_dev; int64_t* poll_host;   // smi_llm_poll: device staging / pinned host copy, [kMaxRows][1 + max_steps] words
-  int32_t* pen_idx; size_t pen_idx_cap;   // admission: slot * vocab + id of the prompt tokens whose bit k_pen_prompt sets
+  DevBuf<float> lp;             // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
+  DevBuf<float> lp_part; DevBuf<float2> lp_rowc;   // k_logprob -> k_finalize: [kMaxRows][kLpBlocks] partial sums, [kMaxRows] (max, 1/T)
+  DevBuf<uint16_t> phist;       // penalty histories [max_slots][vocab] (k_penalize, k_finalize)
+  DevBuf<int64_t> poll_dev; DevBuf<int64_t, true> poll_host;   // smi_llm_poll: device staging / pinned host copy, [kMaxRows][1 + max_steps] words
+  DevBuf<int32_t> pen_idx;      // admission: slot * vocab + id of the prompt tokens whose bit k_pen_prompt sets (grows on demand)
   std::vector<int32_t> host_pen_idx;
-  float* logits; int* tok;
-  float* cand_v; int* cand_i; unsigned int* cand_n;   // sampler candidate lists
-  unsigned long long* stamps; int stamps_on;
+  DevBuf<float> logits; DevBuf<int> tok;
+  DevBuf<float> cand_v; DevBuf<int> cand_i; DevBuf<unsigned int> cand_n;   // sampler candidate lists
+  DevBuf<unsigned long long> stamps; int stamps_on;
   int max_steps;
-  int pf_inline;        // gate_up's work blocks touch the next layer's QKV weights (SPARKMI_PF_INLINE=0: off)
-  int pf_qkv_eighths;   // SPARKMI_PF_QKV: how much of gate_up QKV's helpers prefetch, in eighths (default 2)
-  int prefetch_mask, prefetch_rows;  // same-XCD L2 prefetch by helper blocks: one bit per producer kernel, up to this many live rows (smi_llm_create)
-  int tune2;     // SPARKMI_TUNE2 bit mask (diagnostics; the kTune2* bits)
-  int pgemm_min_rows;   // prompt rows from which the prefill GEMM replaces row-grouped decode GEMMs (SPARKMI_PGEMM_MIN_ROWS)
-  int pg_min[4];        // ... per kernel (QKV, o_proj, gate_up, down; SPARKMI_PGEMM_MIN_QKV / _O / _GU / _D override the common value)
   int wd_parts;         // W_down tiles are stored row-part-major (smi_llm_cfg.wd_plain == 0; include/sparkmi.h)
   int exact;            // smi_llm_cfg.weights_exact: fp32 matrices, every GEMM on k_gemm_x (verification mode)
   hipGraphExec_t graph; uint64_t graph_id;   // the one-step graph in use (owned by graph_cache) and its graph_key
@@ -4039,6 +4043,23 @@ struct LdsBig {
   static inline const bool reg = lds_big_register((const void*)F);
 };
 constexpr int kLdsBigBytes = 160 * 1024;   // the window every LdsBig kernel is opted in to
+int lds_big_opt_in() {
+  static std::mutex mu;
+  static bool done[64] = {};
+  int dev = 0;
+  std::lock_guard<std::mutex> lk(mu);
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    smi_set_error("smi_llm_create: no current device");
+    return SMI_EHIP;
+  }
+  for (size_t i = 0; i < lds_big_kernels().size() && !done[dev]; ++i)
+    if (hipFuncSetAttribute(lds_big_kernels()[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBigBytes) != hipSuccess) {
+      smi_set_error("smi_llm_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(hipGetLastError()));
+      return SMI_EHIP;
+    }
+  done[dev] = true;
+  return SMI_OK;
+}
 
 // The KV cache's element type as a template argument of a GEMM launch: f(kv) with kv() = 1 for an f32 cache where the epilogue
 // appends to the cache (EPI_QKV), and the constant 0 for every other epilogue -- those kernels never read it, so they exist once.
@@ -4537,7 +4558,6 @@ void* kv_layer(const smi_llm* L, void* base, int layer) {
 }
 
 #ifndef SMI_DIAG   // product build: no engine (the launch path everywhere)
-inline void eng_destroy(smi_llm*) {}
 inline bool eng_usable(const smi_llm*, const RowDesc*, int) { return false; }
 inline int eng_launch(smi_llm*, hipStream_t) { return SMI_OK; }
 inline int eng_check(smi_llm*) { return SMI_OK; }
@@ -4545,15 +4565,13 @@ inline int eng_check(smi_llm*) { return SMI_OK; }
 // ---- one-row decode engine (smi_eng.h): build at create, launch in place of the 4 x layers launches of a one-row step
 void eng_destroy(smi_llm* L) {
   EngState& E = L->eng;
-  void* ptrs[] = {E.plan, E.stream, E.gran, E.words, E.stamps};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  E.plan = nullptr; E.stream = nullptr; E.gran = nullptr; E.words = nullptr; E.stamps = nullptr; E.enabled = 0;
+  E.plan.reset(); E.stream.reset(); E.gran.reset(); E.words.reset(); E.stamps.reset();
+  E.enabled = 0;
 }
 
 // Not an error when the engine does not apply (other KV type, paged cache, odd shapes, small device): `why` says so and the
-// launch path is used.  An allocation failure IS reported.
-int eng_create(smi_llm* L) {
+// launch path is used.  An allocation failure IS reported.  (eng_create releases what a build that did not finish left.)
+int eng_build(smi_llm* L) {
   EngState& E = L->eng;
   const smi_llm_cfg& c = L->cfg;
   E.enabled = 0;
@@ -4580,31 +4598,16 @@ int eng_create(smi_llm* L) {
   { const char* e = smi_env("SPARKMI_ENGINE_TIMEOUT_MS"); const double ms = e ? atof(e) : 500.0; E.timeout_ticks = (unsigned)((ms > 1.0 ? ms : 1.0) * 1e5); }
   const size_t ncw = (size_t)ncu;   // one stream per CU
   const size_t stream_bytes = (size_t)c.num_layers * ncw * P.maxlen * 1024;
-  uint32_t* desc_dev = nullptr;
-  uint16_t* lens_dev = nullptr;
-  auto oom = [&](const char* what, size_t bytes) {
-    smi_set_error("hipMalloc(engine %s, %zu bytes) failed", what, bytes);
-    if (desc_dev) (void)hipFree(desc_dev);
-    if (lens_dev) (void)hipFree(lens_dev);
-    eng_destroy(L);
-    return SMI_ENOMEM;
-  };
-  if (hipMalloc((void**)&E.plan, P.cu.size() * sizeof(EngCuPlan)) != hipSuccess) return oom("plan", P.cu.size() * sizeof(EngCuPlan));
-  if (hipMalloc((void**)&E.stream, stream_bytes) != hipSuccess) return oom("weight stream", stream_bytes);
-  if (hipMalloc((void**)&E.gran, (size_t)2 * E.gran_per_buf * 8) != hipSuccess) return oom("granules", (size_t)2 * E.gran_per_buf * 8);
-  if (hipMalloc((void**)&E.words, 256) != hipSuccess) return oom("words", 256);
-  if (hipMalloc((void**)&E.stamps, (size_t)3 * c.num_layers * 16 * 8) != hipSuccess) return oom("stamps", (size_t)3 * c.num_layers * 128);
-  if (hipMalloc((void**)&desc_dev, P.desc.size() * 4) != hipSuccess) return oom("descriptors", P.desc.size() * 4);
-  if (hipMalloc((void**)&lens_dev, P.lens.size() * 2) != hipSuccess) return oom("lengths", P.lens.size() * 2);
-  // (a failing copy / memset frees the two temporaries and the engine's buffers like a failing allocation does)
-#define SMI_ENG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { smi_set_error("%s: %s", #call, hipGetErrorString(e_)); \
-    (void)hipFree(desc_dev); (void)hipFree(lens_dev); eng_destroy(L); return SMI_EHIP; } } while (0)
-  SMI_ENG_HIP(hipMemcpy(E.plan, P.cu.data(), P.cu.size() * sizeof(EngCuPlan), hipMemcpyHostToDevice));
-  SMI_ENG_HIP(hipMemcpy(desc_dev, P.desc.data(), P.desc.size() * 4, hipMemcpyHostToDevice));
-  SMI_ENG_HIP(hipMemcpy(lens_dev, P.lens.data(), P.lens.size() * 2, hipMemcpyHostToDevice));
-  SMI_ENG_HIP(hipMemset(E.gran, 0, (size_t)2 * E.gran_per_buf * 8));
-  SMI_ENG_HIP(hipMemset(E.words, 0, 256));
-  SMI_ENG_HIP(hipMemset(E.stamps, 0, (size_t)3 * c.num_layers * 128));
+  DevBuf<uint32_t> desc_dev;   // the two temporaries of the packing launch
+  DevBuf<uint16_t> lens_dev;
+  int rc;
+  if ((rc = E.plan.alloc(P.cu.size() * sizeof(EngCuPlan), "engine plan")) || (rc = E.stream.alloc(stream_bytes, "engine weight stream")) ||
+      (rc = E.gran.alloc_zero((size_t)2 * E.gran_per_buf * 8, "engine granules")) || (rc = E.words.alloc_zero(256, "engine words")) ||
+      (rc = E.stamps.alloc_zero((size_t)3 * c.num_layers * 16 * 8, "engine stamps")) ||
+      (rc = desc_dev.alloc(P.desc.size() * 4, "engine descriptors")) || (rc = lens_dev.alloc(P.lens.size() * 2, "engine lengths"))) return rc;
+  SMI_HIP(hipMemcpy(E.plan, P.cu.data(), P.cu.size() * sizeof(EngCuPlan), hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(desc_dev, P.desc.data(), P.desc.size() * 4, hipMemcpyHostToDevice));
+  SMI_HIP(hipMemcpy(lens_dev, P.lens.data(), P.lens.size() * 2, hipMemcpyHostToDevice));
   EngPackP pk;
   memset(&pk, 0, sizeof(pk));
   pk.desc = desc_dev; pk.lens = lens_dev; pk.maxlen = P.maxlen; pk.ncw = (int)ncw;
@@ -4612,22 +4615,24 @@ int eng_create(smi_llm* L) {
   const int secs[4] = {SMI_LLM_WQKV, SMI_LLM_WO, SMI_LLM_WGU, SMI_LLM_WD};
   for (int ph = 0; ph < 4; ++ph) { pk.woff[ph] = L->lay.off[secs[ph]]; pk.KT[ph] = P.g.KT[ph]; pk.NW[ph] = P.g.NW[ph]; pk.wperm[ph] = 0; }
   pk.wperm[EPH_DOWN] = L->wd_parts;
-  pk.out = (uint4*)E.stream;
+  pk.out = (uint4*)E.stream.get();
   const size_t imgs = ncw * P.maxlen;
   hipLaunchKernelGGL(k_eng_pack, dim3((unsigned)((imgs + 3) / 4), (unsigned)c.num_layers), dim3(256), 0, 0, pk);
-  SMI_ENG_HIP(hipGetLastError());
-  SMI_ENG_HIP(hipDeviceSynchronize());
-#undef SMI_ENG_HIP
-  (void)hipFree(desc_dev);
-  (void)hipFree(lens_dev);
+  SMI_HIP(hipGetLastError());
+  SMI_HIP(hipDeviceSynchronize());   // (the packing launch is done before its two temporaries go)
   if (hipFuncSetAttribute((const void*)k_engine, hipFuncAttributeMaxDynamicSharedMemorySize, E.lds) != hipSuccess) {
     (void)hipGetLastError();
-    eng_destroy(L);
     return skip("hipFuncSetAttribute(LDS) refused");
   }
   snprintf(E.why, sizeof(E.why), "on: %d CUs, %d images per wave and layer at most, %d B of LDS", ncu, P.maxlen, E.lds);
   E.enabled = 1;
   return SMI_OK;
+}
+
+int eng_create(smi_llm* L) {
+  const int rc = eng_build(L);
+  if (rc || !L->eng.enabled) eng_destroy(L);
+  return rc;
 }
 
 // the one-row step the engine stands for: one live sequence in slot 0, contiguous bf16 cache, one context segment (its layers
@@ -4652,7 +4657,7 @@ int eng_launch(smi_llm* L, hipStream_t st) {
   p.final_norm = (const float*)(L->arena + L->lay.off[SMI_LLM_FINAL_NORM]);
   p.rope = (const float2*)(L->arena + L->lay.off[SMI_LLM_ROPE]);
   p.rows = L->rows; p.h = L->dec.h; p.ss_in = L->dec.ss; p.xs_out = L->dec.xs_h; p.ss_out = L->dec.ss;
-  p.kcache = (uint16_t*)L->kcache; p.vcache = (uint16_t*)L->vcache; p.kv_layer_elems = L->kv_layer_elems;
+  p.kcache = (uint16_t*)L->kcache.get(); p.vcache = (uint16_t*)L->vcache.get(); p.kv_layer_elems = L->kv_layer_elems;
   p.gran = E.gran; p.serial = E.words; p.err = E.words + 4; p.arrive = E.words + 8;
   p.timeout_ticks = E.timeout_ticks;
   p.ld_burst = E.ld_burst; p.ld_sleep = E.ld_sleep; p.poll_quiet = E.poll_quiet;
@@ -4680,13 +4685,9 @@ int eng_check(smi_llm* L) {
 enum { KQKV = 0, KATTN, KO, KGU, KD, KLM, KFIN };
 
 int ensure_apart(smi_llm* L, size_t floats) {
-  if (floats <= L->apart_floats) return SMI_OK;
+  if (floats * 4 <= L->apart.bytes()) return SMI_OK;
   graphs_flush(L);   // captured steps hold the old buffer's address
-  if (L->apart) (void)hipFree(L->apart);
-  L->apart = nullptr; L->apart_floats = 0;
-  if (hipMalloc((void**)&L->apart, floats * 4) != hipSuccess) { smi_set_error("hipMalloc(attention partials, %zu floats) failed", floats); return SMI_ENOMEM; }
-  L->apart_floats = floats;
-  return SMI_OK;
+  return L->apart.ensure(floats * 4, "attention partials");
 }
 
 // lm_head partial columns (= persistent blocks) finalize / the sampler read for M live rows
@@ -4809,7 +4810,7 @@ int launch_attn(smi_llm* L, AttnP a, hipStream_t st) {
     if (rc) return rc;
     a.part = L->apart;
   }
-  const int helpers = ((L->prefetch_mask & 2) && a.M <= L->prefetch_rows && a.work_blocks < 232) ? (256 - a.work_blocks) / 8 * 8 : 0;
+  const int helpers = ((L->sw.prefetch_mask & 2) && a.M <= L->sw.prefetch_rows && a.work_blocks < 232) ? (256 - a.work_blocks) / 8 * 8 : 0;
   const bool pg = a.km.ptab != nullptr;   // paged cache: the slot == row kernels look the token's page up (PG)
 #ifdef SMI_DIAG   // measured, not adopted: the product library does not carry these instantiations
   if (fuse2 && pg)
@@ -4855,7 +4856,7 @@ bool fuse_o_now(const smi_llm* L, const RowDesc* rows, int M) {
 // 2 .. fuse2_rows live rows, each in its own slot, one context segment: the attention kernel also computes the o_proj and the last
 // block of a (row, quarter) to arrive finishes the rows (k_attn<.., FUSE = 2>); the o_proj kernel is not launched.
 bool fuse2_now(const smi_llm* L, const RowDesc* rows, int M) {
-  return L->fuse_o && M >= 2 && M <= L->fuse2_rows && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
+  return L->fuse_o && M >= 2 && M <= L->sw.fuse2_rows && rows == L->rows && L->identity_slots && L->attn_seg <= 1;
 }
 
 // ---- The forms' launchers, one per table: the template arguments are a table row's, everything else is the pick's.  A launcher
@@ -4903,7 +4904,7 @@ int launch_pgemm_form(const smi_llm* L, GemmP p, const GemmPick& k, hipStream_t 
   }
   if (k.nsplit > 1) {
     SMI_REQUIRE(EPI == EPI_RESID && XMAP && RING >= 3 && p.kseg > 0 && k.nsplit <= 16, "launch_pgemm_form: split-K is the RESID ring form's");
-    SMI_REQUIRE(L->pslab && (size_t)k.nsplit * p.NT * k.mtiles * 1024 <= L->pslab_bytes, "launch_pgemm_form: partial slab too small");
+    SMI_REQUIRE(L->pslab && (size_t)k.nsplit * p.NT * k.mtiles * 1024 <= L->pslab.bytes(), "launch_pgemm_form: partial slab too small");
     p.slab = L->pslab; p.slab_mt = k.mtiles;
   }
   with_kvf32<EPI>(L, [&](auto kv) {
@@ -4922,6 +4923,7 @@ int launch_pgemm_form(const smi_llm* L, GemmP p, const GemmPick& k, hipStream_t 
 // the persistent lm_head: one launch up to 16 rows, else one pass per 32 rows
 template <int K32, int A, int RT>
 int launch_lm_form(const smi_llm*, const GemmP& p, const GemmPick& k, hipStream_t st) {
+  if constexpr (K32) static_cast<void>(LdsBig<k_lm32<A, RT>>::reg);   // 16 rows' operand triples in LDS: 86 KB at K = 896
   for (int i = 0; i < k.launches; ++i) {
     if constexpr (K32) hipLaunchKernelGGL((k_lm32<A, RT>), dim3(k.gx), dim3(256), k.lds, st, p, k.lm_groups, 32 * i);
     else hipLaunchKernelGGL((k_lm<A, RT>), dim3(k.gx), dim3(256 * A), k.lds, st, p, k.lm_groups, 32 * i);
@@ -5016,9 +5018,9 @@ AttnP attn_operands(const smi_llm* L, int layer, const Work& w, const RowDesc* r
 // The switches the picks read, as the handle holds them, for a kernel of a decode step (pass 0) or of a prompt pass's family.
 PickEnv pick_env(const smi_llm* L, int pass) {
   PickEnv e{};
-  e.pass = pass; e.stamps = L->stamps_on; e.exact = L->exact; e.tune2 = L->tune2;
-  e.pf_mask = L->prefetch_mask; e.pf_rows = L->prefetch_rows;
-  e.kv_f32 = L->cfg.kv_dtype ? 1 : 0; e.pg_split_rows = L->pg_split_rows; e.lm_blocks = L->lm_blocks;
+  e.pass = pass; e.stamps = L->stamps_on; e.exact = L->exact; e.tune2 = L->sw.tune2;
+  e.pf_mask = L->sw.prefetch_mask; e.pf_rows = L->sw.prefetch_rows;
+  e.kv_f32 = L->cfg.kv_dtype ? 1 : 0; e.pg_split_rows = L->sw.pg_split_rows; e.lm_blocks = L->lm_blocks;
   return e;
 }
 // The pick of GEMM kernel `which` (KQKV, KO, KGU, KD, KLM) over M rows at the handle's shape.
@@ -5050,7 +5052,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KQKV:
       // helpers: the first pf_qkv_eighths / 8 of this layer's gate_up slices (consumer block b reads weight tile row b).  Measured
       // at one row, graph step, one box (profiles/r03_prefetch.txt): 8/8 600 us, 6/8 569, 4/8 564, 2/8 559 (default), none 566-571
-      p.pf = PfDesc{sec(L, SMI_LLM_WGU, layer), L->KTh * 1024, L->NTgu, 0, ((L->NTgu + 7) / 8 * L->pf_qkv_eighths + 7) / 8};
+      p.pf = PfDesc{sec(L, SMI_LLM_WGU, layer), L->KTh * 1024, L->NTgu, 0, ((L->NTgu + 7) / 8 * L->sw.pf_qkv_eighths + 7) / 8};
       e.has_pf = p.pf.base != nullptr;
       return launch_form(L, p, pick_gemm(L, KQKV, M, e), st);
     case KATTN: {
@@ -5070,7 +5072,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
     case KGU:
       if (fused) {
         p.part_o = L->part_o; p.n_oheads = c.num_heads; p.hres = L->dec.h; p.h2out = L->h2;
-        if (L->pf_inline && layer + 1 < c.num_layers && L->NTqkv % 8 == 0) {   // SPARKMI_PF_INLINE=0: off (A/B)
+        if (L->sw.pf_inline && layer + 1 < c.num_layers && L->NTqkv % 8 == 0) {   // SPARKMI_PF_INLINE=0: off (A/B)
           p.pf2_base = sec(L, SMI_LLM_WQKV, layer + 1); p.pf2_slice = L->KTh * 1024; p.pf2_nslices = L->NTqkv;
         }
         p.gam = (const float*)sec(L, SMI_LLM_LN2, layer);
@@ -5120,7 +5122,7 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
 // RMSNorm partials per row that a layer's QKV finds in the big workspace: [rows][NT * 4] as the row-grouped down_proj leaves them,
 // [rows][NT] as the prefill GEMM and its split-K combine do.  The kernel that fills a pass's layer-0 input (k_embed) is told the same.
 int pf_nparts_in(const smi_llm* L, int M, int family) {
-  const bool gd = L->pg_forced ? M < L->pg_min[3] : family != PF_PGEMM;
+  const bool gd = L->sw.pg_forced ? M < L->sw.pg_min[3] : family != PF_PGEMM;
   return gd ? L->NTh * 4 : L->NTh;
 }
 
@@ -5135,8 +5137,8 @@ int launch_layer_big(smi_llm* L, int l, const RowDesc* rows, int M, int family, 
   // parity-tested.  The RESID kernels leave the RMSNorm partials as [rows][NT * 4] (grouped) or [rows][NT] (prefill GEMM and
   // its split-K combine); their consumers are told which.
   const bool pg = family == PF_PGEMM;
-  const bool gq = L->pg_forced ? M < L->pg_min[0] : !pg, go = L->pg_forced ? M < L->pg_min[1] : !pg,
-             gg = L->pg_forced ? M < L->pg_min[2] : !pg, gd = L->pg_forced ? M < L->pg_min[3] : !pg;
+  const bool gq = L->sw.pg_forced ? M < L->sw.pg_min[0] : !pg, go = L->sw.pg_forced ? M < L->sw.pg_min[1] : !pg,
+             gg = L->sw.pg_forced ? M < L->sw.pg_min[2] : !pg, gd = L->sw.pg_forced ? M < L->sw.pg_min[3] : !pg;
   const int np_from_d = pf_nparts_in(L, M, family), np_from_o = go ? L->NTh * 4 : L->NTh;
   // each kernel: operands, pick (by its family and the row count; the k_pgemm forms and the split-K segments: pick_pgemm_rows), launch
   auto launch = [&](int which, bool grouped, const GemmP& p) {
@@ -5149,7 +5151,7 @@ int launch_layer_big(smi_llm* L, int l, const RowDesc* rows, int M, int family, 
   // attention
   const AttnP a = attn_operands(L, l, L->big, rows, M);   // (slot_is_row = 0: prompt rows name their slot)
   const dim3 ag((unsigned)((M + kAttnWaves - 1) / kAttnWaves), (unsigned)c.num_heads);
-  if (!c.kv_dtype && L->attn_pf2 && L->pf_ntiles > 0 && c.head_dim == 64) {   // bf16 KV: tiles of 16 rows on the matrix pipes
+  if (!c.kv_dtype && L->sw.attn_pf2 && L->pf_ntiles > 0 && c.head_dim == 64) {   // bf16 KV: tiles of 16 rows on the matrix pipes
     const int tasks = L->pf_ntiles * c.num_heads;
     hipLaunchKernelGGL(k_attn_pf2, dim3((tasks + 3) / 4), dim3(256), 0, st, a, (const PfTile*)L->pf_tiles, L->pf_ntiles);
   } else if (c.kv_dtype) hipLaunchKernelGGL((k_attn_pf<1>), ag, dim3(kAttnWaves * 64), 0, st, a);
@@ -5177,32 +5179,26 @@ int launch_layers_big(smi_llm* L, const RowDesc* rows, int M, int family, hipStr
   return SMI_OK;
 }
 
-// A workspace for R rows, allocated in the struct's order (a failure leaves what it got: work_free / smi_llm_destroy release it).
-bool work_alloc(const smi_llm* L, Work& w, size_t R) {
-  return hipMalloc((void**)&w.h, R * L->H * 4) == hipSuccess && hipMalloc((void**)&w.q, R * L->Q * 4) == hipSuccess &&
-         hipMalloc((void**)&w.xs_h, R * L->H * 6) == hipSuccess && hipMalloc((void**)&w.xs_attn, R * L->Q * 6) == hipSuccess &&
-         hipMalloc((void**)&w.xs_act, R * L->I * 6) == hipSuccess && hipMalloc((void**)&w.ss, R * L->NTh * 4 * 4) == hipSuccess;
-}
-void work_free(Work& w) {
-  void* ptrs[] = {w.h, w.q, w.xs_h, w.xs_attn, w.xs_act, w.ss};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  w = Work{};
+// A workspace for R rows, allocated in the struct's order and zeroed where `zero` (the decode rows').
+int work_alloc(const smi_llm* L, Work& w, size_t R, bool zero) {
+  int rc;
+  auto a = [&](auto& buf, size_t bytes, const char* what) { return zero ? buf.alloc_zero(bytes, what) : buf.alloc(bytes, what); };
+  if ((rc = a(w.h, R * L->H * 4, "workspace h")) || (rc = a(w.q, R * L->Q * 4, "workspace q")) ||
+      (rc = a(w.xs_h, R * L->H * 6, "workspace xs_h")) || (rc = a(w.xs_attn, R * L->Q * 6, "workspace xs_attn")) ||
+      (rc = a(w.xs_act, R * L->I * 6, "workspace xs_act")) || (rc = a(w.ss, R * L->NTh * 4 * 4, "workspace ss"))) return rc;
+  return SMI_OK;
 }
 
+// The prefill workspace and its split-K slab grow together: both go, then both come back (the slab first) for `rows` rows.
 int ensure_big(smi_llm* L, int rows) {
   if (rows <= L->big_rows) return SMI_OK;
-  work_free(L->big);
+  L->big = Work{};
   L->big_rows = 0;
-  if (L->pslab) (void)hipFree(L->pslab);
-  L->pslab = nullptr; L->pslab_bytes = 0;
-  {   // split-K partial sums: up to kPgSegD segments x NTh tiles x (min(rows, kPgSplitRows) / 16) m-tiles x 1 KiB
-    const size_t mt = ((size_t)(rows < kPgSplitRows ? rows : kPgSplitRows) + 15) / 16;
-    const size_t bytes = (size_t)16 * L->NTh * mt * 1024;
-    if (hipMalloc((void**)&L->pslab, bytes) != hipSuccess) { smi_set_error("hipMalloc(prefill split-K slab, %zu bytes) failed", bytes); return SMI_ENOMEM; }
-    L->pslab_bytes = bytes;
-  }
-  if (!work_alloc(L, L->big, (size_t)rows)) { smi_set_error("hipMalloc(prefill workspace for %d rows) failed", rows); return SMI_ENOMEM; }
+  L->pslab.reset();
+  // split-K partial sums: up to kPgSegD segments x NTh tiles x (min(rows, kPgSplitRows) / 16) m-tiles x 1 KiB
+  const size_t mt = ((size_t)(rows < kPgSplitRows ? rows : kPgSplitRows) + 15) / 16;
+  int rc;
+  if ((rc = L->pslab.alloc((size_t)16 * L->NTh * mt * 1024, "prefill split-K slab")) || (rc = work_alloc(L, L->big, (size_t)rows, false))) return rc;
   L->big_rows = rows;
   return SMI_OK;
 }
@@ -5239,16 +5235,8 @@ int launch_step(smi_llm* L, int M, hipStream_t st) {
 }
 
 int ensure_plan(smi_llm* L, size_t rows) {
-  if (rows <= L->plan_cap) return SMI_OK;
-  if (L->plan) (void)hipFree(L->plan);
-  L->plan = nullptr; L->plan_cap = 0;
-  size_t cap = rows + 1024;
-  if (hipMalloc((void**)&L->plan, cap * sizeof(RowDesc)) != hipSuccess) {
-    smi_set_error("hipMalloc(prefill plan, %zu rows) failed", cap);
-    return SMI_ENOMEM;
-  }
-  L->plan_cap = cap;
-  return SMI_OK;
+  if (rows * sizeof(RowDesc) <= L->plan.bytes()) return SMI_OK;
+  return L->plan.ensure((rows + 1024) * sizeof(RowDesc), "prefill plan");
 }
 
 // smi_llm_poll's gather: one block per listed slot.  Word 0 of the slot's staging record holds {count, finished}, words 1 .. cap the
@@ -5418,6 +5406,40 @@ __global__ __launch_bounds__(256) void k_slot_cols(ParkP p) {
   }
 }
 
+// The diagnostics switches, in the order of DESIGN 6.1, each with what was measured for its default.
+Switches read_switches() {
+  Switches w;
+  // helper-block prefetch per producer: bit 0 QKV (gate_up's first half), bit 1 attention (second half), bit 2 down_proj (the next
+  // layer's QKV / o_proj); SPARKMI_PREFETCH=<mask> picks, SPARKMI_NO_PREFETCH=1 is mask 0
+  // Default since k_down1 (round 3): QKV's helpers at ONE row only.  Measured on one box, alternating processes, graph step at one
+  // row: mask 0 566-571 us, 1 563-564, 2 581, 3 583, 4 597, 5 602, 6 658, 7 665 (down_proj's 256-thread blocks make slow helpers);
+  // at 4 rows mask 0 727 us, 3 748, 7 739-745 (profiles/r03_prefetch.txt).  SPARKMI_PREFETCH=<mask> applies up to 8 rows as before.
+  w.prefetch_mask = 1; w.prefetch_rows = 1;
+  if (const char* e = smi_env("SPARKMI_PREFETCH")) { w.prefetch_mask = atoi(e) & 7; w.prefetch_rows = 8; }
+  { const char* e = smi_env("SPARKMI_PF_QKV"); w.pf_qkv_eighths = e ? atoi(e) : 2; if (w.pf_qkv_eighths < 0 || w.pf_qkv_eighths > 8) w.pf_qkv_eighths = 2; }
+  if (smi_env("SPARKMI_NO_PREFETCH")) w.prefetch_mask = 0;
+  { const char* e = smi_env("SPARKMI_PF_INLINE"); w.pf_inline = !(e && e[0] == '0'); }
+  { const char* e = smi_env("SPARKMI_TUNE2"); w.tune2 = e ? atoi(e) : 0; }
+  // OFF by default (diagnostics build: SPARKMI_FUSE2_ROWS=n enables it up to n <= 8 rows).  Measured at 0.5B, graph step, one box
+  // (profiles/r04_fused_oproj_last_arriver.txt): 8 rows 730 -> 863 us (attention 3.9 -> 14.1 us for the 4.3-us o_proj launch it
+  // replaces), 2 rows 616 -> 640, one row (a retired switch, against the per-head partials every gate_up block sums) 543 -> 581:
+  // the arrival count + the reads of write-through partials cost 3-4 us at one row, where a kernel boundary costs 1.8.
+  { const char* e = smi_env("SPARKMI_FUSE2_ROWS"); w.fuse2_rows = e ? atoi(e) : 0; if (w.fuse2_rows > kFuse2Max) w.fuse2_rows = kFuse2Max; }
+  { const char* e = smi_env("SPARKMI_PG_SPLIT_ROWS"); w.pg_split_rows = e ? atoi(e) : kPgSplitRows; if (w.pg_split_rows > kPgSplitRows) w.pg_split_rows = kPgSplitRows; }
+  {
+    const char* names[4] = {"SPARKMI_PGEMM_MIN_QKV", "SPARKMI_PGEMM_MIN_O", "SPARKMI_PGEMM_MIN_GU", "SPARKMI_PGEMM_MIN_D"};
+    // measured crossovers (tools/prefill_time.py mix / mix2, profiles/README.md): gate_up from ~300 rows (its grouped form re-reads
+    // the operand triples once per 32 columns), down_proj from ~900, the two short-K GEMMs from ~1300
+    const int dflt[4] = {1280, 1280, 288, 896};
+    const char* common = smi_env("SPARKMI_PGEMM_MIN_ROWS");   // all four kernels alike; a kernel's own switch overrides it
+    w.pg_forced = common != nullptr;
+    for (int i = 0; i < 4; ++i) { const char* e = smi_env(names[i]); w.pg_forced |= e != nullptr; w.pg_min[i] = e ? atoi(e) : common ? atoi(common) : dflt[i]; }
+  }
+  { const char* e = smi_env("SPARKMI_ATTN_PF2"); w.attn_pf2 = !(e && e[0] == '0'); }
+  w.no_fuse_o = smi_env("SPARKMI_NO_FUSE_O") != nullptr;
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5463,7 +5485,8 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
                 tag.num_heads == cfg->num_heads && tag.num_kv_heads == cfg->num_kv_heads && tag.intermediate_size == cfg->intermediate_size &&
                 tag.max_positions == cfg->max_positions, "smi_llm_create: the arena was packed for other dimensions than this config");
   }
-  smi_llm* L = new smi_llm();
+  // shapes
+  smi_llm* L = new smi_llm();   // value-initialised: every field is zero / empty but those whose declaration names a default
   L->cfg = *cfg; L->lay = lay; L->arena = (const unsigned char*)arena_dev;
   L->H = cfg->hidden_size; L->Q = cfg->num_heads * cfg->head_dim; L->KV = cfg->num_kv_heads * cfg->head_dim;
   L->I = cfg->intermediate_size;
@@ -5472,59 +5495,12 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   L->lm_cap = (L->NTlm + 3) / 4;                       // partial-argmax slots (two-m-tile path: one per block)
   L->lm_blocks = L->lm_cap < 512 ? L->lm_cap : 512;    // persistent path: 2 resident blocks per CU
   L->max_steps = cfg->max_positions;
-  L->do_sample = 0; L->top_k = 50; L->temperature = 0.8f; L->top_p = 0.95f; L->seed = 0; L->logits = nullptr; L->tok = nullptr; L->cand_v = nullptr; L->cand_i = nullptr; L->cand_n = nullptr; L->stamps = nullptr; L->stamps_on = 0;
-  L->dec = Work{}; L->big = Work{}; L->big_rows = 0;
-  L->pslab = nullptr; L->pslab_bytes = 0;
-  // helper-block prefetch per producer: bit 0 QKV (gate_up's first half), bit 1 attention (second half), bit 2 down_proj (the next
-  // layer's QKV / o_proj); SPARKMI_PREFETCH=<mask> picks, SPARKMI_NO_PREFETCH=1 is mask 0
-  // Default since k_down1 (round 3): QKV's helpers at ONE row only.  Measured on one box, alternating processes, graph step at one
-  // row: mask 0 566-571 us, 1 563-564, 2 581, 3 583, 4 597, 5 602, 6 658, 7 665 (down_proj's 256-thread blocks make slow helpers);
-  // at 4 rows mask 0 727 us, 3 748, 7 739-745 (profiles/r03_prefetch.txt).  SPARKMI_PREFETCH=<mask> applies up to 8 rows as before.
-  L->prefetch_mask = 1; L->prefetch_rows = 1;
-  if (const char* e = smi_env("SPARKMI_PREFETCH")) { L->prefetch_mask = atoi(e) & 7; L->prefetch_rows = 8; }
-  if (smi_env("SPARKMI_NO_PREFETCH")) L->prefetch_mask = 0;
-  { const char* e = smi_env("SPARKMI_PF_INLINE"); L->pf_inline = !(e && e[0] == '0'); }
-  { const char* e = smi_env("SPARKMI_PF_QKV"); L->pf_qkv_eighths = e ? atoi(e) : 2; if (L->pf_qkv_eighths < 0 || L->pf_qkv_eighths > 8) L->pf_qkv_eighths = 2; }
-  L->part_o = nullptr; L->h2 = nullptr; L->dpart = nullptr; L->fuse_cnt = nullptr;
-  // OFF by default (diagnostics build: SPARKMI_FUSE2_ROWS=n enables it up to n <= 8 rows).  Measured at 0.5B, graph step, one box
-  // (profiles/r04_fused_oproj_last_arriver.txt): 8 rows 730 -> 863 us (attention 3.9 -> 14.1 us for the 4.3-us o_proj launch it
-  // replaces), 2 rows 616 -> 640, one row (a retired switch, against the per-head partials every gate_up block sums) 543 -> 581:
-  // the arrival count + the reads of write-through partials cost 3-4 us at one row, where a kernel boundary costs 1.8.
-  { const char* e = smi_env("SPARKMI_FUSE2_ROWS"); L->fuse2_rows = e ? atoi(e) : 0; if (L->fuse2_rows > kFuse2Max) L->fuse2_rows = kFuse2Max; }
-  L->fuse_o = !smi_env("SPARKMI_NO_FUSE_O") && fuse_o_fits(cfg->num_heads, L->NTh, L->KTh);
-  { const char* e = smi_env("SPARKMI_TUNE2"); L->tune2 = e ? atoi(e) : 0; }
-  { const char* e = smi_env("SPARKMI_PGEMM_MIN_ROWS"); L->pgemm_min_rows = e ? atoi(e) : 1280; }
-  {
-    const char* names[4] = {"SPARKMI_PGEMM_MIN_QKV", "SPARKMI_PGEMM_MIN_O", "SPARKMI_PGEMM_MIN_GU", "SPARKMI_PGEMM_MIN_D"};
-    // measured crossovers (tools/prefill_time.py mix / mix2, profiles/README.md): gate_up from ~300 rows (its grouped form re-reads
-    // the operand triples once per 32 columns), down_proj from ~900, the two short-K GEMMs from ~1300
-    const int dflt[4] = {1280, 1280, 288, 896};
-    const bool common = smi_env("SPARKMI_PGEMM_MIN_ROWS") != nullptr;
-    L->pg_forced = common;
-    for (int i = 0; i < 4; ++i) { const char* e = smi_env(names[i]); L->pg_forced |= e != nullptr; L->pg_min[i] = e ? atoi(e) : common ? L->pgemm_min_rows : dflt[i]; }
-  }
-  { const char* e = smi_env("SPARKMI_PG_SPLIT_ROWS"); L->pg_split_rows = e ? atoi(e) : kPgSplitRows; if (L->pg_split_rows > kPgSplitRows) L->pg_split_rows = kPgSplitRows; }
   L->wd_parts = cfg->wd_plain ? 0 : 1;   // the arena's W_down tile order comes with its config (never from the environment)
   L->exact = cfg->weights_exact;
-  if (L->exact) L->fuse_o = 0;           // (the fused o_proj reads bf16 tiles)
-  if (cfg->max_positions > kFuseMaxPos) L->fuse_o = 0;   // (the one-row fused kernel's 32-bit K / V piece offsets)
-  L->pf_tiles = nullptr; L->pf_tiles_cap = 0; L->pf_ntiles = 0;
-  L->dbg_pf_rows = 0;
-  { const char* e = smi_env("SPARKMI_ATTN_PF2"); L->attn_pf2 = !(e && e[0] == '0'); }
-  L->graph = nullptr; L->graph_id = 0; slots_clear(L);
-  L->lp = nullptr; L->lp_part = nullptr; L->lp_rowc = nullptr;
-  L->tlist = nullptr;
-  memset(L->seq_dirty, 0, sizeof(L->seq_dirty));
-  L->seq = nullptr; L->hseq.assign(kMaxRows, SeqRec{});
-  L->pctx = nullptr;
-  L->poll_dev = nullptr; L->poll_host = nullptr;
-  L->phist = nullptr; L->pen_idx = nullptr; L->pen_idx_cap = 0; L->plan = nullptr; L->plan_cap = 0; L->B = 0; L->started = 0; L->ctl = nullptr; L->admit_seq = 0; memset(&L->hctl, 0, sizeof(L->hctl));
-  L->session = 0; L->identity_slots = 1; L->attn_seg = 1; L->apart = nullptr; L->apart_floats = 0; memset(L->slot_busy, 0, sizeof(L->slot_busy)); memset(L->slot_len, 0, sizeof(L->slot_len));
-  memset(L->slot_plen, 0, sizeof(L->slot_plen));
-  { static std::atomic<uint64_t> handles{0}; L->handle_id = ++handles; L->session_gen = 0; }
+  L->hseq.assign(kMaxRows, SeqRec{});
+  { static std::atomic<uint64_t> handles{0}; L->handle_id = ++handles; }
   const size_t esz = cfg->kv_dtype ? 4 : 2;
-  L->paged = cfg->kv_page_tokens > 0; L->pshift = 0; L->ppslot = 0; L->ptab = nullptr;
-  memset(L->slot_pages, 0, sizeof(L->slot_pages));
+  L->paged = cfg->kv_page_tokens > 0;
   L->kv_layer_elems = (size_t)cfg->max_slots * cfg->num_kv_heads * cfg->max_positions * kHeadDim;
   if (L->paged) {
     while ((1 << L->pshift) < cfg->kv_page_tokens) ++L->pshift;
@@ -5535,125 +5511,70 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
     L->page_ref.assign((size_t)cfg->kv_pages, 0);
   }
   const size_t kvbytes = L->kv_layer_elems * esz * cfg->num_layers;
-#define SMI_ALLOC(ptr, bytes)                                                      \
-  if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) {                          \
-    smi_set_error("hipMalloc(%s, %zu bytes) failed", #ptr, (size_t)(bytes));       \
-    smi_llm_destroy(L);                                                            \
-    return SMI_ENOMEM;                                                             \
-  }
-  if (!work_alloc(L, L->dec, kMaxRows)) {
-    smi_set_error("hipMalloc(decode workspace for %d rows) failed", kMaxRows);
-    smi_llm_destroy(L);
-    return SMI_ENOMEM;
-  }
-  SMI_ALLOC(L->part_o, (size_t)kFuse2Max * kMaxOHeads * L->H * 4);
-  SMI_ALLOC(L->fuse_cnt, (size_t)kFuse2Max * kFuseQB * 4);
-  SMI_HIP(hipMemset(L->fuse_cnt, 0, (size_t)kFuse2Max * kFuseQB * 4));
-  SMI_ALLOC(L->h2, (size_t)L->H * 4);
-  SMI_ALLOC(L->dpart, (size_t)16 * L->NTh * 4 * 64 * 16);
-  SMI_ALLOC(L->rows, kMaxRows * sizeof(RowDesc));
-  SMI_ALLOC(L->pval, (size_t)L->lm_cap * kMaxRows * 4);
-  SMI_ALLOC(L->pidx, (size_t)L->lm_cap * kMaxRows * 4);
-  SMI_ALLOC(L->hist, (size_t)L->max_steps * kMaxRows * 8);
-  SMI_ALLOC(L->count, kMaxRows * 4);
-  SMI_ALLOC(L->finished, kMaxRows * 4);
-  SMI_ALLOC(L->step, 4);
-  SMI_ALLOC(L->ctl, sizeof(Ctl));
-  SMI_HIP(hipMemset(L->ctl, 0, sizeof(Ctl)));
-  if (L->paged) {
-    SMI_ALLOC(L->ptab, L->hptab.size() * 4);
-    SMI_HIP(hipMemset(L->ptab, 0, L->hptab.size() * 4));
-  }
-  SMI_ALLOC(L->logits, (size_t)kMaxRows * cfg->vocab_size * 4);
-  SMI_ALLOC(L->phist, (size_t)cfg->max_slots * cfg->vocab_size * 2);   // (a penalised admission zeroes its slot's row)
-  SMI_ALLOC(L->tok, kMaxRows * 4);
-  SMI_ALLOC(L->cand_v, (size_t)kMaxRows * kCandCap * 4);
-  SMI_ALLOC(L->cand_i, (size_t)kMaxRows * kCandCap * 4);
-  SMI_ALLOC(L->cand_n, kMaxRows * 4);
-  SMI_HIP(hipMemset(L->cand_n, 0, kMaxRows * 4));
-  SMI_ALLOC(L->stamps, (size_t)4096 * 8 * 8);
-  SMI_ALLOC(L->kcache, kvbytes);
-  SMI_ALLOC(L->vcache, kvbytes);
-  // log-probabilities (smi_llm_admit_logprobs), after everything else: the other buffers keep the placement they had without them
-  SMI_ALLOC(L->lp, (size_t)L->max_steps * kMaxRows * 4);
-  SMI_ALLOC(L->lp_part, (size_t)kMaxRows * kLpBlocks * 4);
-  SMI_ALLOC(L->lp_rowc, (size_t)kMaxRows * sizeof(float2));
+  // switches
+  L->sw = read_switches();
+  // the fused o_proj reads bf16 tiles; the one-row fused kernel has 32-bit K / V piece offsets
+  L->fuse_o = !L->sw.no_fuse_o && fuse_o_fits(cfg->num_heads, L->NTh, L->KTh) && !L->exact && cfg->max_positions <= kFuseMaxPos;
+  // device memory, in this order: a buffer's address depends on what was allocated before it, so a new buffer goes to the end
+  // of the list and the earlier ones keep the placement they had without it (a: as allocated, z: zeroed)
+  int rc = work_alloc(L, L->dec, kMaxRows, true);
+  auto a = [&](auto& buf, size_t bytes, const char* what) { if (!rc) rc = buf.alloc(bytes, what); };
+  auto z = [&](auto& buf, size_t bytes, const char* what) { if (!rc) rc = buf.alloc_zero(bytes, what); };
+  a(L->part_o, (size_t)kFuse2Max * kMaxOHeads * L->H * 4, "part_o");
+  z(L->fuse_cnt, (size_t)kFuse2Max * kFuseQB * 4, "fuse_cnt");
+  a(L->h2, (size_t)L->H * 4, "h2");
+  a(L->dpart, (size_t)16 * L->NTh * 4 * 64 * 16, "dpart");
+  z(L->rows, kMaxRows * sizeof(RowDesc), "rows");
+  a(L->pval, (size_t)L->lm_cap * kMaxRows * 4, "pval");
+  a(L->pidx, (size_t)L->lm_cap * kMaxRows * 4, "pidx");
+  a(L->hist, (size_t)L->max_steps * kMaxRows * 8, "hist");
+  z(L->count, kMaxRows * 4, "count");
+  z(L->finished, kMaxRows * 4, "finished");
+  z(L->step, 4, "step");
+  z(L->ctl, sizeof(Ctl), "ctl");
+  if (L->paged) z(L->ptab, L->hptab.size() * 4, "ptab");
+  a(L->logits, (size_t)kMaxRows * cfg->vocab_size * 4, "logits");
+  a(L->phist, (size_t)cfg->max_slots * cfg->vocab_size * 2, "phist");   // (a penalised admission zeroes its slot's row)
+  a(L->tok, kMaxRows * 4, "tok");
+  a(L->cand_v, (size_t)kMaxRows * kCandCap * 4, "cand_v");
+  a(L->cand_i, (size_t)kMaxRows * kCandCap * 4, "cand_i");
+  z(L->cand_n, kMaxRows * 4, "cand_n");
+  a(L->stamps, (size_t)4096 * 8 * 8, "stamps");
+  z(L->kcache, kvbytes, "kcache");
+  z(L->vcache, kvbytes, "vcache");
+  // log-probabilities (smi_llm_admit_logprobs)
+  a(L->lp, (size_t)L->max_steps * kMaxRows * 4, "lp");
+  a(L->lp_part, (size_t)kMaxRows * kLpBlocks * 4, "lp_part");
+  a(L->lp_rowc, (size_t)kMaxRows * sizeof(float2), "lp_rowc");
   // the restricted lm_head's tile list (smi_llm_admit_constrained): {count, tiles}; zeros = no tile, entry 0 a valid tile index
-  SMI_ALLOC(L->tlist, ((size_t)L->NTlm + 1) * 4);
-  SMI_HIP(hipMemset(L->tlist, 0, ((size_t)L->NTlm + 1) * 4));
+  z(L->tlist, ((size_t)L->NTlm + 1) * 4, "tlist");
   // per-slot bias / stop records (smi_llm_admit_biased): all zero = none
-  SMI_ALLOC(L->seq, (size_t)kMaxRows * sizeof(SeqRec));
-  SMI_HIP(hipMemset(L->seq, 0, (size_t)kMaxRows * sizeof(SeqRec)));
+  z(L->seq, (size_t)kMaxRows * sizeof(SeqRec), "seq");
   // the n-gram ban's prompt ids per slot (smi_llm_admit_ngram): a row is written by the admission that reads it
-  SMI_ALLOC(L->pctx, (size_t)cfg->max_slots * cfg->max_positions * 4);
-  SMI_HIP(hipMemset(L->pctx, 0, (size_t)cfg->max_slots * cfg->max_positions * 4));
+  z(L->pctx, (size_t)cfg->max_slots * cfg->max_positions * 4, "pctx");
   // smi_llm_poll's staging: {count, finished, ids[cap]} per listed slot, cap <= max_steps, and its pinned host copy
-  SMI_ALLOC(L->poll_dev, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8);
-#undef SMI_ALLOC
-  if (hipHostMalloc((void**)&L->poll_host, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8, hipHostMallocDefault) != hipSuccess) {
-    L->poll_host = nullptr;
-    smi_set_error("hipHostMalloc(poll_host, %zu bytes) failed", (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8);
-    smi_llm_destroy(L);
-    return SMI_ENOMEM;
-  }
-  if (hipMemset(L->kcache, 0, kvbytes) != hipSuccess || hipMemset(L->vcache, 0, kvbytes) != hipSuccess ||
-      hipMemset(L->dec.h, 0, (size_t)kMaxRows * L->H * 4) != hipSuccess ||
-      hipMemset(L->dec.xs_h, 0, (size_t)kMaxRows * L->H * 6) != hipSuccess ||
-      hipMemset(L->dec.xs_attn, 0, (size_t)kMaxRows * L->Q * 6) != hipSuccess ||
-      hipMemset(L->dec.xs_act, 0, (size_t)kMaxRows * L->I * 6) != hipSuccess ||
-      hipMemset(L->dec.ss, 0, (size_t)kMaxRows * L->NTh * 4 * 4) != hipSuccess ||
-      hipMemset(L->dec.q, 0, (size_t)kMaxRows * L->Q * 4) != hipSuccess ||
-      hipMemset(L->rows, 0, kMaxRows * sizeof(RowDesc)) != hipSuccess ||
-      hipMemset(L->count, 0, kMaxRows * 4) != hipSuccess || hipMemset(L->finished, 0, kMaxRows * 4) != hipSuccess ||
-      hipMemset(L->step, 0, 4) != hipSuccess) {
-    smi_set_error("hipMemset of scratch failed");
-    smi_llm_destroy(L);
-    return SMI_EHIP;
-  }
-  // k_lm32 stages 16 rows' operand triples in LDS (86 KB at K = 896): opt in to the large dynamic window here, once per
-  // handle (= per device), outside any stream capture
-  if (hipFuncSetAttribute((const void*)k_lm32<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-  if (hipFuncSetAttribute((const void*)k_lm32<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-  if (hipFuncSetAttribute((const void*)k_lm32<7, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-  if (hipFuncSetAttribute((const void*)k_lm32<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
-  {   // and so do the k_gemm / k_pgemm / k_downC instantiations whose launches may pass 64 KiB (LdsBig), once per device
-    static std::mutex mu;
-    static bool done[64] = {};
-    int dev = 0;
-    std::lock_guard<std::mutex> lk(mu);
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-      smi_set_error("smi_llm_create: no current device");
-      smi_llm_destroy(L);
-      return SMI_EHIP;
-    }
-    for (size_t i = 0; i < lds_big_kernels().size() && !done[dev]; ++i)
-      if (hipFuncSetAttribute(lds_big_kernels()[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBigBytes) != hipSuccess) {
-        smi_set_error("smi_llm_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(hipGetLastError()));
-        smi_llm_destroy(L);
-        return SMI_EHIP;
-      }
-    done[dev] = true;
-  }
-  if (hipEventCreate(&L->ev0) != hipSuccess || hipEventCreate(&L->ev1) != hipSuccess) {
+  a(L->poll_dev, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8, "poll_dev");
+  a(L->poll_host, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8, "poll_host");
+  // the large LDS window of every LdsBig kernel, once per device and outside any stream capture
+  if (!rc) rc = lds_big_opt_in();
+  if (!rc && (hipEventCreate(&L->ev0) != hipSuccess || hipEventCreate(&L->ev1) != hipSuccess)) {
     smi_set_error("hipEventCreate failed");
-    smi_llm_destroy(L);
-    return SMI_EHIP;
+    rc = SMI_EHIP;
   }
   // The one-row decode engine is opt-in (SPARKMI_ENGINE=1, or smi_llm_set_engine later: it is built on first request --
   // 0.8 GB of re-packed weights): measured on MI355X at the 0.5B shape a layer takes 26.3 us in the engine against 23.4 us
   // as four launches -- five in-launch hand-offs of 2.5-4.5 us cost more than the four kernel boundaries they replace
   // (profiles/r03_engine_ab.txt).
 #ifdef SMI_DIAG
-  L->eng_on = 0;
   snprintf(L->eng.why, sizeof(L->eng.why), "off (opt-in: SPARKMI_ENGINE=1 or smi_llm_set_engine)");
   { const char* e = smi_env("SPARKMI_ENGINE");
-    if (e && e[0] == '1') {
-      const int rce = eng_create(L);
-      if (rce) { smi_llm_destroy(L); return rce; }
-      L->eng_on = L->eng.enabled;
-    }
+    if (!rc && e && e[0] == '1' && !(rc = eng_create(L))) L->eng_on = L->eng.enabled;
   }
 #endif
+  if (rc) {
+    smi_llm_destroy(L);
+    return rc;
+  }
   *out = L;
   return SMI_OK;
 }
@@ -5661,18 +5582,9 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
 int smi_llm_destroy(smi_llm* L) {
   if (!L) return SMI_OK;
   graphs_flush(L);
-  eng_destroy(L);
-  work_free(L->dec);
-  work_free(L->big);
-  void* ptrs[] = {L->part_o, L->h2, L->dpart, L->fuse_cnt, L->rows, L->plan, L->pf_tiles, L->pval, L->pidx, L->hist,
-                  L->count, L->finished, L->step, L->ctl, L->ptab, L->kcache, L->vcache, L->logits, L->tok, L->cand_v, L->cand_i, L->cand_n, L->stamps, L->pslab, L->apart,
-                  L->phist, L->pen_idx, L->lp, L->lp_part, L->lp_rowc, L->tlist, L->poll_dev, L->seq, L->pctx};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  if (L->poll_host) (void)hipHostFree(L->poll_host);
   if (L->ev0) (void)hipEventDestroy(L->ev0);
   if (L->ev1) (void)hipEventDestroy(L->ev1);
-  delete L;
+  delete L;   // every device buffer goes with its owner
   return SMI_OK;
 }
 
@@ -5711,16 +5623,11 @@ static void pf_tiles_build(const RowDesc* rows, int M, std::vector<PfTile>& T) {
 // the handle's settings take k_attn_pf2; L->pf_ntiles = 0 otherwise.
 static int pf_tiles_upload(smi_llm* L, const RowDesc* host_rows, int M, hipStream_t st) {
   L->pf_ntiles = 0;
-  if (L->cfg.kv_dtype || !L->attn_pf2) return SMI_OK;
+  if (L->cfg.kv_dtype || !L->sw.attn_pf2) return SMI_OK;
   std::vector<PfTile>& T = L->host_tiles;
   pf_tiles_build(host_rows, M, T);
-  if (T.size() > L->pf_tiles_cap) {
-    if (L->pf_tiles) (void)hipFree(L->pf_tiles);
-    L->pf_tiles = nullptr; L->pf_tiles_cap = 0;
-    const size_t cap = T.size() + 256;
-    if (hipMalloc((void**)&L->pf_tiles, cap * sizeof(PfTile)) != hipSuccess) { smi_set_error("hipMalloc(prefill attention tiles) failed"); return SMI_ENOMEM; }
-    L->pf_tiles_cap = cap;
-  }
+  if (T.size() * sizeof(PfTile) > L->pf_tiles.bytes())
+    if (int rc = L->pf_tiles.ensure((T.size() + 256) * sizeof(PfTile), "prefill attention tiles")) return rc;
   // (pageable source: staged before the call returns; host_tiles is rebuilt only by the next group, behind this copy)
   SMI_HIP(hipMemcpyAsync(L->pf_tiles, T.data(), T.size() * sizeof(PfTile), hipMemcpyHostToDevice, st));
   L->pf_ntiles = (int)T.size();
@@ -5769,7 +5676,7 @@ static int prefill_prompts(smi_llm* L, const int64_t* ids, const int32_t* lens, 
   auto cls_of = [&](int b) -> int {
     const int r = lens[b] - 1;
     if (chunks_only) return 0;
-    if (L->pg_forced) return total > (size_t)kMaxRows ? 3 : 0;   // 3: one pass, kernels by the pass's row count (launch_layers_big)
+    if (L->sw.pg_forced) return total > (size_t)kMaxRows ? 3 : 0;   // 3: one pass, kernels by the pass's row count (launch_layers_big)
     return r <= kMaxRows ? 0 : r < kPfLong ? 1 : 2;
   };
   size_t ncls[4] = {0, 0, 0, 0};
@@ -5978,13 +5885,8 @@ static int pen_histories(smi_llm* L, const int64_t* ids, const int32_t* lens, in
       for (int t = 0; t < lens[b]; ++t) idx.push_back((int32_t)((size_t)slots[b] * V + (size_t)ids[(size_t)b * P_max + t]));
   }
   if (idx.empty()) return SMI_OK;
-  if (idx.size() > L->pen_idx_cap) {
-    if (L->pen_idx) (void)hipFree(L->pen_idx);
-    L->pen_idx = nullptr; L->pen_idx_cap = 0;
-    const size_t cap = idx.size() + 4096;
-    if (hipMalloc((void**)&L->pen_idx, cap * 4) != hipSuccess) { smi_set_error("hipMalloc(penalty prompt ids) failed"); return SMI_ENOMEM; }
-    L->pen_idx_cap = cap;
-  }
+  if (idx.size() * 4 > L->pen_idx.bytes())
+    if (int rc = L->pen_idx.ensure((idx.size() + 4096) * 4, "penalty prompt ids")) return rc;
   // (pageable source: staged before the call returns; host_pen_idx is rebuilt only by the next admission)
   SMI_HIP(hipMemcpyAsync(L->pen_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_pen_prompt, dim3((unsigned)((idx.size() + 255) / 256)), dim3(256), 0, st, L->phist, L->pen_idx, (int)idx.size());
@@ -6407,7 +6309,7 @@ static int admit(smi_llm* L, const AdmitReq& rq, int32_t* slots_out, hipStream_t
   if (!fork.empty()) {   // after the leaders' prompt rows, before the takes' first step
     ForkP fp;
     fp.work = (const int4*)(L->plan + tail + kMaxRows);
-    fp.kcache = (unsigned char*)L->kcache; fp.vcache = (unsigned char*)L->vcache;
+    fp.kcache = (unsigned char*)L->kcache.get(); fp.vcache = (unsigned char*)L->vcache.get();
     fp.piece_shift = L->cfg.kv_dtype ? 4 : 3;
     fp.layer_bytes = L->kv_layer_elems * (L->cfg.kv_dtype ? 4 : 2);
     fp.n_kv = L->cfg.num_kv_heads; fp.max_pos = L->cfg.max_positions;
@@ -6592,7 +6494,7 @@ static int park_launch(smi_llm* L, bool save, const SlotXfer* xs, int n, hipStre
     const int m = xs[i].nhist > ph ? (xs[i].nhist > xs[i].npctx ? xs[i].nhist : xs[i].npctx) : (ph > xs[i].npctx ? ph : xs[i].npctx);
     items = m > items ? m : items;
   }
-  p.kcache = (unsigned char*)L->kcache; p.vcache = (unsigned char*)L->vcache;
+  p.kcache = (unsigned char*)L->kcache.get(); p.vcache = (unsigned char*)L->vcache.get();
   p.piece_shift = L->cfg.kv_dtype ? 4 : 3;
   p.layer_bytes = L->kv_layer_elems * (L->cfg.kv_dtype ? 4 : 2);
   p.n_kv = L->cfg.num_kv_heads; p.max_pos = L->cfg.max_positions;
@@ -7344,11 +7246,11 @@ int smi_llm_debug_layer(smi_llm* L, int layer, int M, const int32_t* rows_host, 
   SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   L->B = M; L->identity_slots = ident; L->session = 0; L->started = 0;
   L->attn_seg = segs_for(maxpos + 1);
-  float* src = nullptr;
-  SMI_HIP(hipMalloc((void**)&src, (size_t)M * L->H * 4));
+  DevBuf<float> src;
+  if (src.alloc((size_t)M * L->H * 4, "smi_llm_debug_layer: hidden rows")) return SMI_EHIP;
+  if (hipMemcpy(src, hidden_host, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { smi_set_error("smi_llm_debug_layer: upload failed"); return SMI_EHIP; }
   int rc = SMI_OK;
-  if (hipMemcpy(src, hidden_host, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_layer: upload failed"); }
-  if (rc == SMI_OK) {
+  {   // from here every way out passes the synchronise below: the kernels are done before src goes
     hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, src, L->KTh, M, (const float*)sec(L, SMI_LLM_LN1, layer), L->dec.h, L->dec.xs_h,
                        L->dec.ss, L->NTh * 4);
     if (hipGetLastError() != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_layer: k_load_hidden launch failed"); }
@@ -7357,7 +7259,6 @@ int smi_llm_debug_layer(smi_llm* L, int layer, int M, const int32_t* rows_host, 
   const int last = (fused && stage == 2) ? KGU : KQKV + stage;   // one fused row: h + o_proj is formed by gate_up's prologue (read buffer 8)
   for (int k = KQKV; k <= last && rc == SMI_OK; ++k) rc = launch_one(L, k, layer, L->rows, M, nullptr, 0);
   if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_layer: kernels failed: %s", hipGetErrorString(hipGetLastError())); }
-  (void)hipFree(src);
   return rc;
 }
 
@@ -7397,10 +7298,10 @@ int smi_llm_debug_prefill_layer(smi_llm* L, int layer, int stage, int n_seq, con
     for (int t = 0; t < seq_host[3 * b + 2]; ++t) L->host_rows.push_back(RowDesc{seq_host[3 * b], seq_host[3 * b + 1] + t, 0, 0});
   SMI_HIP(hipMemcpy(L->plan, L->host_rows.data(), (size_t)M * sizeof(RowDesc), hipMemcpyHostToDevice));
   if ((rc = pf_tiles_upload(L, L->host_rows.data(), M, 0))) return rc;
-  float* src = nullptr;
-  SMI_HIP(hipMalloc((void**)&src, (size_t)M * L->H * 4));
-  if (hipMemcpy(src, hidden_host, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_prefill_layer: upload failed"); }
-  if (rc == SMI_OK) {
+  DevBuf<float> src;
+  if (src.alloc((size_t)M * L->H * 4, "smi_llm_debug_prefill_layer: hidden rows")) return SMI_EHIP;
+  if (hipMemcpy(src, hidden_host, (size_t)M * L->H * 4, hipMemcpyHostToDevice) != hipSuccess) { smi_set_error("smi_llm_debug_prefill_layer: upload failed"); return SMI_EHIP; }
+  {   // from here every way out passes the synchronise below: the kernels are done before src goes
     hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, src, L->KTh, M, (const float*)sec(L, SMI_LLM_LN1, layer), L->big.h, L->big.xs_h,
                        L->big.ss, pf_nparts_in(L, M, family));
     if (hipGetLastError() != hipSuccess) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_prefill_layer: k_load_hidden launch failed"); }
@@ -7408,7 +7309,6 @@ int smi_llm_debug_prefill_layer(smi_llm* L, int layer, int stage, int n_seq, con
   if (rc == SMI_OK) rc = launch_layer_big(L, layer, L->plan, M, family, stage < 5 ? KQKV + stage : KD, 0);
   if (rc == SMI_OK && stage == 5) rc = launch_layer_big(L, layer + 1, L->plan, M, family, KQKV, 0);
   if (hipDeviceSynchronize() != hipSuccess && rc == SMI_OK) { rc = SMI_EHIP; smi_set_error("smi_llm_debug_prefill_layer: kernels failed: %s", hipGetErrorString(hipGetLastError())); }
-  (void)hipFree(src);
   if (rc == SMI_OK) L->dbg_pf_rows = M;
   return rc;
 }
@@ -7485,17 +7385,16 @@ int smi_llm_debug_raw_stamps(smi_llm* L, unsigned long long* out, int n) {
 // stages its rows, writes the records its kernels read, commits the controls, composes the stage launchers a decode step is
 // composed of (launch_ngram_ban .. launch_finalize; smi_llm_debug_head: launch_one itself) and fetches what they left.
 // The scope of one run.  Before: the device idle, every record clean, rows 0 .. n-1 = slots 0 .. n-1 with flags[m] tokens emitted
-// (null: none); rc says whether that held.  After, on every way out: clean records again, `dev` freed; rows, controls, the lm_head
+// (null: none); rc says whether that held.  After, on every way out: clean records again, `dev` freed (with the scope); rows, controls, the lm_head
 // partials and the histories no longer belong to a generation.
 struct Alone {
   smi_llm* L;
-  float* dev = nullptr;   // a device buffer of the run (smi_llm_debug_head's hidden rows)
+  DevBuf<float> dev;      // a device buffer of the run (smi_llm_debug_head's hidden rows)
   int rc;
   Alone(smi_llm* L_, int n, const int32_t* flags) : L(L_), rc(begin(n, flags)) {}
   Alone(const Alone&) = delete;
   Alone& operator=(const Alone&) = delete;
   ~Alone() {
-    if (dev) (void)hipFree(dev);
     slots_clear(L);
     L->started = 0;
   }
@@ -7783,7 +7682,7 @@ int smi_llm_debug_head(smi_llm* L, int M, smi_head_io* io) {
   SMI_TRY(allow_tiles_upload(L, 0));
   SMI_TRY(alone_commit(L, true));
   if (io->flags & SMI_HEAD_POISON) SMI_HIP(hipMemset(L->logits, 0xff, (size_t)kMaxRows * V * 4));   // 0xffffffff: a quiet NaN
-  SMI_HIP(hipMalloc((void**)&run.dev, (size_t)M * L->H * 4));
+  if (run.dev.alloc((size_t)M * L->H * 4, "smi_llm_debug_head: hidden rows")) return SMI_EHIP;
   SMI_HIP(hipMemcpy(run.dev, io->hidden, (size_t)M * L->H * 4, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_load_hidden, dim3((M + 3) / 4), dim3(256), 0, 0, run.dev, L->KTh, M, (const float*)sec(L, SMI_LLM_FINAL_NORM, 0), L->dec.h,
                      L->dec.xs_h, L->dec.ss, L->NTh * 4);

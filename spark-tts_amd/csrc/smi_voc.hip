@@ -147,11 +147,11 @@ struct smi_voc {
   smi_voc_cfg cfg;
   VocLayout lay;
   const unsigned char* arena;
-  float* buf[4];        // activation ping-pong buffers [max_batch][maxC x maxL]
-  size_t buf_floats;    // per batch item
-  float* small;         // d-vector path + AdaLN params
-  int* lens_dev;        // [8][max_batch] valid lengths per resolution
-  float* dbg[8]; size_t dbg_floats[8]; int debug;
+  DevBuf<float> buf[4];   // activation ping-pong buffers [max_batch][maxC x maxL]
+  size_t buf_floats;      // per batch item
+  DevBuf<float> small;    // d-vector path + AdaLN params
+  DevBuf<int> lens_dev;   // [8][max_batch] valid lengths per resolution
+  DevBuf<float> dbg[8]; size_t dbg_floats[8]; int debug;
   std::vector<Launch> prog;
   std::vector<int32_t> host_lens;   // staging for the async H2D copy (must outlive the call)
   int lastB, lastT;
@@ -419,9 +419,6 @@ int smi_voc_create(const smi_voc_cfg* cfg, const void* arena_dev, size_t arena_b
   SMI_REQUIRE(((uintptr_t)arena_dev & 255) == 0, "smi_voc_create: arena must be 256-byte aligned");
   smi_voc* h = new smi_voc();
   h->cfg = *cfg; h->lay = lay; h->arena = (const unsigned char*)arena_dev;
-  h->lastB = h->lastT = 0; h->small = nullptr; h->lens_dev = nullptr; h->ev0 = h->ev1 = nullptr;
-  for (int i = 0; i < 4; ++i) h->buf[i] = nullptr;
-  for (int i = 0; i < 8; ++i) { h->dbg[i] = nullptr; h->dbg_floats[i] = 0; }
   const char* dbg = smi_env("SPARKMI_VOC_DEBUG");
   h->debug = dbg && dbg[0] == '1';
   // largest activation: channels x length over all stages
@@ -436,19 +433,19 @@ int smi_voc_create(const smi_voc_cfg* cfg, const void* arena_dev, size_t arena_b
   h->buf_floats = smi_align_up(mx, 64);
   const size_t small_floats = (size_t)cfg->max_batch *
       ((size_t)cfg->spk_latent_dim * cfg->spk_token_num + cfg->spk_out_dim + (size_t)(1 + cfg->pre_layers) * 2 * cfg->pre_dim + 64);
-  bool ok = true;
-  for (int i = 0; i < 4 && ok; ++i) ok = hipMalloc((void**)&h->buf[i], h->buf_floats * cfg->max_batch * 4) == hipSuccess;
-  ok = ok && hipMalloc((void**)&h->small, small_floats * 4) == hipSuccess;
-  ok = ok && hipMalloc((void**)&h->lens_dev, 8 * cfg->max_batch * 4 + 64) == hipSuccess;
-  if (ok && h->debug) {
-    for (int i = 0; i < 8 && ok; ++i) {
-      h->dbg_floats[i] = h->buf_floats * cfg->max_batch;
-      ok = hipMalloc((void**)&h->dbg[i], h->dbg_floats[i] * 4) == hipSuccess;
-    }
+  int rc = SMI_OK;
+  for (int i = 0; i < 4 && !rc; ++i) rc = h->buf[i].alloc(h->buf_floats * cfg->max_batch * 4, "vocoder activation buffer");
+  if (!rc) rc = h->small.alloc(small_floats * 4, "vocoder small");
+  if (!rc) rc = h->lens_dev.alloc(8 * cfg->max_batch * 4 + 64, "vocoder lens_dev");
+  for (int i = 0; i < 8 && !rc && h->debug; ++i) {
+    h->dbg_floats[i] = h->buf_floats * cfg->max_batch;
+    rc = h->dbg[i].alloc(h->dbg_floats[i] * 4, "vocoder debug buffer");
   }
-  ok = ok && hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess;
-  if (!ok) {
-    smi_set_error("smi_voc_create: device allocation failed (%zu floats per activation buffer x %d)", h->buf_floats, cfg->max_batch);
+  if (!rc && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess)) {
+    smi_set_error("smi_voc_create: hipEventCreate failed");
+    rc = SMI_ENOMEM;
+  }
+  if (rc) {
     smi_voc_destroy(h);
     return SMI_ENOMEM;
   }
@@ -458,10 +455,6 @@ int smi_voc_create(const smi_voc_cfg* cfg, const void* arena_dev, size_t arena_b
 
 int smi_voc_destroy(smi_voc* h) {
   if (!h) return SMI_OK;
-  for (int i = 0; i < 4; ++i) if (h->buf[i]) (void)hipFree(h->buf[i]);
-  for (int i = 0; i < 8; ++i) if (h->dbg[i]) (void)hipFree(h->dbg[i]);
-  if (h->small) (void)hipFree(h->small);
-  if (h->lens_dev) (void)hipFree(h->lens_dev);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   delete h;
@@ -774,26 +767,19 @@ int smi_voc_block_run(const smi_voc_block_cfg* cfg, const void* arena_dev, size_
   const int Cmax = std::max(std::max(Cin, Cres), c.kind == SMI_VOC_BLOCK_CONVNEXT ? c.I : 1);
   const long long bs = (long long)smi_align_up((size_t)Cmax * Lout, 64);   // one batch stride for every working buffer, as in the vocoder
   // working buffers: [0] input / x, [1] snake(input) / n, [2] U or m, [3] US, [4] A ; ints: lens_in, lens_out, ones ; ada
-  float* buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  float* ada = nullptr;
-  int* lens = nullptr;
-  auto cleanup = [&]() {
-    for (float* f : buf) if (f) (void)hipFree(f);
-    if (ada) (void)hipFree(ada);
-    if (lens) (void)hipFree(lens);
-  };
-  bool ok = true;
-  for (int i = 0; i < 5 && ok; ++i) ok = hipMalloc((void**)&buf[i], (size_t)bs * B * 4) == hipSuccess;
-  ok = ok && hipMalloc((void**)&ada, (size_t)B * 2 * c.C * 4 + 256) == hipSuccess;
-  ok = ok && hipMalloc((void**)&lens, (size_t)3 * 64 * 4) == hipSuccess;
-  if (!ok) { cleanup(); smi_set_error("smi_voc_block_run: device allocation failed"); return SMI_ENOMEM; }
+  DevBuf<float> own[5], ada;
+  DevBuf<int> lens;
+  int rc = SMI_OK;
+  for (int i = 0; i < 5 && !rc; ++i) rc = own[i].alloc((size_t)bs * B * 4, "smi_voc_block_run: working buffer");
+  if (rc || (rc = ada.alloc((size_t)B * 2 * c.C * 4 + 256, "smi_voc_block_run: ada")) || (rc = lens.alloc((size_t)3 * 64 * 4, "smi_voc_block_run: lens"))) return rc;
+  float* const buf[5] = {own[0], own[1], own[2], own[3], own[4]};
   std::vector<int32_t> hl((size_t)3 * 64, 0);
   for (int b = 0; b < B; ++b) {
     const int n = lens_host ? lens_host[b] : L;
-    if (n < 1 || n > L) { cleanup(); smi_set_error("smi_voc_block_run: lens[%d]=%d outside 1..%d", b, n, L); return SMI_EINVAL; }
+    SMI_REQUIRE(n >= 1 && n <= L, "smi_voc_block_run: lens[%d]=%d outside 1..%d", b, n, L);
     hl[b] = n; hl[64 + b] = n * (Lout / L); hl[128 + b] = 1;
   }
-  int rc = SMI_OK;
+  // from here every way out passes the synchronise at the end: the stream is done with the buffers before they go
   auto fail = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == SMI_OK) { smi_set_error("smi_voc_block_run: %s: %s", what, hipGetErrorString(e)); rc = SMI_EHIP; } };
   fail(hipMemcpyAsync(lens, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st), "lens upload");
   for (int i = 0; i < 5; ++i) fail(hipMemsetAsync(buf[i], 0, (size_t)bs * B * 4, st), "memset");
@@ -815,7 +801,6 @@ int smi_voc_block_run(const smi_voc_block_cfg* cfg, const void* arena_dev, size_
   if (rc == SMI_OK)
     fail(hipMemcpy2DAsync(y_dev, (size_t)Cres * Lout * 4, result, (size_t)bs * 4, (size_t)Cres * Lout * 4, (size_t)B, hipMemcpyDeviceToDevice, st), "copy out");
   fail(hipStreamSynchronize(st), "synchronize");
-  cleanup();
   return rc;
 }
 
@@ -936,17 +921,17 @@ int smi_conv_run(const smi_conv_case* c, const smi_conv_operands* io, const int3
     SMI_REQUIRE(n >= 1 && n <= c->L, "smi_conv_run: lens[%d]=%d outside 1..%d", b, n, c->L);
     hl[b] = n; hl[(size_t)B + b] = c->gemv ? 1 : conv_case_lout(*c, n);
   }
-  int* lens = nullptr;
-  if (hipMalloc((void**)&lens, hl.size() * 4) != hipSuccess) { smi_set_error("smi_conv_run: device allocation failed"); return SMI_ENOMEM; }
+  DevBuf<int> lens;
+  int rc = lens.alloc(hl.size() * 4, "smi_conv_run: lens");
+  if (rc) return rc;
   Launch L;
-  int rc = conv_case_launch(c, *io, lens, lens + B, L, "smi_conv_run");
+  rc = conv_case_launch(c, *io, lens, lens + B, L, "smi_conv_run");
   smi_conv_plan_info info;
   if (rc == SMI_OK) rc = conv_plan_info(*c, L, &info, "smi_conv_run");
   auto fail = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == SMI_OK) { smi_set_error("smi_conv_run: %s: %s", what, hipGetErrorString(e)); rc = SMI_EHIP; } };
   if (rc == SMI_OK) fail(hipMemcpyAsync(lens, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st), "lens upload");
   if (rc == SMI_OK) rc = run_launch(L, st);
-  fail(hipStreamSynchronize(st), "synchronize");
-  (void)hipFree(lens);
+  fail(hipStreamSynchronize(st), "synchronize");   // (before lens goes)
   if (rc == SMI_OK && plan) *plan = info;
   return rc;
 }

@@ -293,6 +293,7 @@ DEBUG_SYMBOLS = {
     "smi_enc_rows_debug_io": (_I, [_VP, _I, C.c_char_p, _I, _VP, _SZ, _SZ]),
     "smi_enc_rows_debug_run": (_I, [_VP, _I, _I, _VP]),
     "smi_enc_rows_debug_stage": (_I, [_VP, _I, C.c_char_p, _VP, _SZ, _P(C.c_int32), _VP]),
+    "smi_debug_dev_memory": (_I, [_P(C.c_longlong), _P(C.c_longlong)]),
 }
 
 DIAG_PATH = LIB_PATH.with_name("libsparkmi_diag.so")
