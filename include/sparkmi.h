@@ -709,6 +709,54 @@ int smi_join_push_rows(smi_join* h, const float* chunks_dev, long long stride, c
 long long smi_join_piece_len(int overlap, int up, int down, int n_taps, int first, long long n_before, long long k_before, long long len,
                              int last, long long* n_after, long long* k_after);
 
+/* ------------------------------------------------------------------------------------------
+ * Long-form audio edge: the speech bounds of vocoded rows and their assembly into one waveform with pauses and fades, for text
+ * that is generated sentence by sentence (sparkmi/pipeline.py: inference_long).  Free functions: no handle and no state, every
+ * buffer is the caller's; asynchronous on the caller's stream; opt-in like the rest of this unit.  Every argument of every row
+ * is checked before anything reaches the device: a bad one returns SMI_EINVAL, names the argument in smi_last_error and
+ * launches nothing.
+ *
+ * Speech bounds (smi_trim_rows): the arithmetic of detect_speech_boundaries (sparktts/utils/audio.py:186-225), which
+ * remove_silence_on_both_ends applies.  For a row x[0 .. n), window W >= 1, step s >= 1, threshold thr >= 0, margin m >= 0 and
+ * n >= W:
+ *     windows  x[i s .. i s + W),  i = 0 .. floor((n - W) / s)
+ *     window i is speech when  S_i = sum of fl64(x)^2 over the window  >=  fl64(thr) * fl64(thr) * fl64(W)
+ *         (float64 throughout; every square is the exact product of the fp32 sample; the reference compares
+ *          sqrt(mean(x^2)) >= thr in fp32, which is the same test up to fp32 rounding at the threshold)
+ *     start = max(0, first s - m),   end = min(n, last s + m)      (first / last: the first / last speech window)
+ * end counts from the last speech window's START plus the margin, not from its end: that is the reference's behaviour.  The
+ * reference passes W = int(0.1 sr), s = W / 10 (integer), m = 2 W, thr = 0.01.  Two cases are defined here and not by the
+ * reference, which raises in both: n < W: the row is kept whole, (0, n); no window is speech: (0, 0), an empty piece.
+ * Two launches whatever B: k_trim_scan, grid (tiles of 64 windows, rows) -- a block stages the samples its windows span in LDS
+ * once, a wave sums a window from there (lane l takes samples l, l + 64, ... in ascending order, then a fixed butterfly) and
+ * the block writes its tile's first and last speech window to work_dev --, then k_trim_bounds, one wave a row.  No atomics.
+ * Guarantee: a row's bounds depend on its samples, n and the parameters alone -- not on B, the row's place, the strides, what
+ * lies past n or the grid.  64 windows must fit the LDS: 63 s + W <= 16320, else SMI_EINVAL.  n <= 2^24, B <= 64.
+ *
+ * Assembly (smi_concat_rows): piece b is p = x_b[start_b .. end_b), L samples, behind gap_b >= 0 samples of silence; f >= 0
+ * is the fade length, f' = min(f, L / 2) (integer division):
+ *     w_q = fl64(q + 1) / fl64(f' + 1)                              (one correctly rounded float64 division)
+ *     p[q] and p[L - 1 - q], q < f', become fl32( fl64(p[.]) * w_q )   (one float64 product, one rounding; no FMA, no table)
+ * -- where the two edges meet in a piece of odd length the middle sample is untouched.  out holds the pieces in row order, each
+ * behind its gap, then zeros from the total length to cap.  An empty piece (end = start) writes nothing, and neither is its gap
+ * written.  One launch for the whole call, grid (tiles of 1024 samples, B + 1): row b writes gap b and piece b, row B the
+ * zeros.  A sample's bits depend on its piece and f alone.  Lengths and offsets are host arithmetic (smi_concat_layout). */
+/* int32 elements of work_dev that smi_trim_rows needs for B rows of at most n_max samples; -1 for a bad argument.  Pure host. */
+long long smi_trim_work_len(long long n_max, int window, int step, int B);
+/* in_dev [B][in_stride] f32 (row b valid for n_host[b], 0 .. min(in_stride, 2^24)); work_dev [work_len] int32 scratch (contents
+ * do not matter before, mean nothing after); bounds_dev [B][2] int32 receives (start, end) of every row. */
+int smi_trim_rows(const float* in_dev, long long in_stride, const int32_t* n_host, int B, int window, int step, double threshold,
+                  int margin, int32_t* work_dev, long long work_len, int32_t* bounds_dev, void* stream);
+/* The total length of the assembled waveform; offset_host [B] (may be null) receives where each piece begins in it (behind its
+ * gap; for an empty piece: where it would).  -1 for B outside 1..64, a negative start or gap, or end < start.  Pure host. */
+long long smi_concat_layout(const int32_t* start_host, const int32_t* end_host, const int32_t* gap_host, int B, long long* offset_host);
+/* in_dev [B][in_stride] f32, row b valid for n_host[b]; 0 <= start_host[b] <= end_host[b] <= n_host[b]; out_dev [cap] f32,
+ * cap >= max(1, total), below 2^31; must not overlap in_dev.  offset_host [B] / total_host (may be null) as smi_concat_layout,
+ * filled before the launch. */
+int smi_concat_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host,
+                    const int32_t* gap_host, int B, int fade, float* out_dev, long long cap, long long* offset_host, long long* total_host,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

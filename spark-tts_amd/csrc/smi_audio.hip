@@ -14,6 +14,10 @@
 //                contiguous stream per request, cross-faded in float64 and resampled with k_rs_rows' own sums (rs_tile_sums);
 //                a block assembles its input window in LDS from the stream's history, the fade region and the chunk's body.
 //                Tails and histories live in two sets a stream uses in turn, so one launch reads its state and writes the next.
+//   k_trim_scan, k_trim_bounds   the speech bounds of rows (smi_trim_rows): window energies in float64, summed from LDS; no atomics.
+//   k_concat_rows                trimmed rows into one waveform with gaps and faded edges (smi_concat_rows): one launch.
+#include <limits.h>
+
 #include <vector>
 
 #include "smi_common.h"
@@ -27,6 +31,10 @@
 #define JN_MAX_STREAMS 4096     // slots of one smi_join handle
 #define PR_BLOCK 1024
 #define PR_BINS 2048
+#define TR_TILE 64              // windows a block of k_trim_scan
+#define TR_BLOCK 256
+#define TR_LDS_FLOATS (RS_LDS_FLOATS - 64)   // samples of one tile; the block's few words of static LDS fit beside them in 64 KiB
+#define CC_TILE 1024            // output samples a block of k_concat_rows
 
 namespace {
 
@@ -313,6 +321,112 @@ __global__ __launch_bounds__(RS_BLOCK) void k_join_rows(JnArgs a, JnState s, con
   for (int i = tid; i < nwin; i += RS_BLOCK) xw[i] = jn_sample(j0 + i, r, s.hs, c, hist, tail, s.fade_in, s.fade_out);
   __syncthreads();
   rs_tile_sums(ht, xw, j0, r.n_new - 1, kf, r.k_new, s.up, s.down, s.half, y + k0, n_write);
+}
+
+// ---- speech bounds of rows (smi_trim_*) and assembly of trimmed rows (smi_concat_*)
+struct TrArgs {
+  int32_t n[RS_MAX_ROWS];
+};
+
+// grid (tiles of TR_TILE windows, rows).  A block stages the samples its windows span in LDS once (coalesced), then each of its
+// four waves sums whole windows from there: lane l adds the exact float64 squares of samples l, l + 64, ... of the window in
+// ascending order, and the 64 partial sums meet in a fixed xor butterfly -- a window's sum depends on its samples alone.  The
+// block writes the first and the last speech window of its tile (INT_MAX / -1: none) to work[row][tile]: no atomics, no state.
+__global__ __launch_bounds__(TR_BLOCK) void k_trim_scan(TrArgs a, const float* __restrict__ in, long long in_stride, int W, int s,
+                                                        double level, int tiles, int32_t* __restrict__ work) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  __shared__ int32_t wf[TR_BLOCK / 64], wl[TR_BLOCK / 64];
+  const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = a.n[b];
+  const int nwin = n >= W ? (n - W) / s + 1 : 0;
+  const int i0 = t * TR_TILE;
+  int first = INT_MAX, last = -1;
+  if (i0 < nwin) {
+    const int cnt = min(TR_TILE, nwin - i0);
+    const float* x = in + (size_t)b * in_stride + (size_t)i0 * s;
+    const int span = (cnt - 1) * s + W;   // i0 s + span <= n; span <= TR_LDS_FLOATS: checked on the host
+    for (int i = tid; i < span; i += TR_BLOCK) rs_lds[i] = x[i];
+    __syncthreads();
+    for (int w = wave; w < cnt; w += TR_BLOCK / 64) {
+      const float* p = rs_lds + w * s;
+      double acc = 0.0;
+      for (int q = lane; q < W; q += 64) {
+        const double v = (double)p[q];
+        acc = acc + v * v;
+      }
+      for (int o = 32; o; o >>= 1) acc = acc + __shfl_xor(acc, o);
+      if (acc >= level) {   // (the same in every lane: the butterfly's sums are bitwise equal)
+        first = min(first, i0 + w);
+        last = i0 + w;
+      }
+    }
+  }
+  if (lane == 0) { wf[wave] = first; wl[wave] = last; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < TR_BLOCK / 64; ++i) { first = min(first, wf[i]); last = max(last, wl[i]); }
+    work[2 * ((size_t)b * tiles + t)] = first;
+    work[2 * ((size_t)b * tiles + t) + 1] = last;
+  }
+}
+
+// one wave per row: the tiles' results become the row's bounds
+__global__ __launch_bounds__(64) void k_trim_bounds(TrArgs a, int W, int s, int margin, int tiles, const int32_t* __restrict__ work,
+                                                    int32_t* __restrict__ bounds) {
+  const int b = blockIdx.x, n = a.n[b];
+  int first = INT_MAX, last = -1;
+  for (int t = threadIdx.x; t < tiles; t += 64) {
+    first = min(first, work[2 * ((size_t)b * tiles + t)]);
+    last = max(last, work[2 * ((size_t)b * tiles + t) + 1]);
+  }
+  for (int o = 32; o; o >>= 1) {
+    first = min(first, __shfl_xor(first, o));
+    last = max(last, __shfl_xor(last, o));
+  }
+  if (threadIdx.x) return;
+  int lo = 0, hi = 0;
+  if (n < W) hi = n;
+  else if (last >= 0) {
+    lo = (int)max(0LL, (long long)first * s - margin);
+    hi = (int)min((long long)n, (long long)last * s + margin);
+  }
+  bounds[2 * b] = lo;
+  bounds[2 * b + 1] = hi;
+}
+
+struct CcRow {
+  int32_t src, len, off, lead, fade;   // first sample of the piece in its row; its length; its place in `out`; zeros before it; f'
+};
+struct CcArgs {
+  CcRow r[RS_MAX_ROWS];
+};
+
+// grid (tiles of CC_TILE samples, B + 1).  Row b < B writes piece b's span of `out`: its gap, then the piece, the first and the
+// last f' samples weighted.  Row B writes the zeros from the total length to cap.
+__global__ __launch_bounds__(RS_BLOCK) void k_concat_rows(CcArgs a, int B, const float* __restrict__ in, long long in_stride,
+                                                          float* __restrict__ out, long long total, long long cap) {
+  const int b = blockIdx.y;
+  const long long k0 = (long long)blockIdx.x * CC_TILE;
+  if (b == B) {
+    for (long long k = total + k0 + threadIdx.x; k < min(cap, total + k0 + CC_TILE); k += RS_BLOCK) out[k] = 0.f;
+    return;
+  }
+  const CcRow r = a.r[b];
+  if (r.len == 0 || k0 >= (long long)r.lead + r.len) return;
+  const float* p = in + (size_t)b * in_stride + r.src;
+  float* y = out + ((long long)r.off - r.lead);
+  const double den = (double)(r.fade + 1);
+  const int end = (int)min((long long)r.lead + r.len, k0 + CC_TILE);
+  for (int k = (int)k0 + threadIdx.x; k < end; k += RS_BLOCK) {
+    float v = 0.f;
+    if (k >= r.lead) {
+      const int q = k - r.lead;
+      const int e = min(q, r.len - 1 - q);   // distance to the nearer edge
+      v = p[q];
+      if (e < r.fade) v = (float)((double)v * ((double)(e + 1) / den));
+    }
+    y[k] = v;
+  }
 }
 
 }  // namespace
@@ -613,6 +727,92 @@ int smi_join_push_rows(smi_join* h, const float* chunks_dev, long long stride, c
   }
   const int tiles = (int)((out_stride + RS_TILE - 1) / RS_TILE);
   hipLaunchKernelGGL(k_join_rows, dim3(tiles, B), dim3(RS_BLOCK), h->lds, (hipStream_t)stream, A, h->s, chunks_dev, stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+long long smi_trim_work_len(long long n_max, int window, int step, int B) {
+  if (n_max < 0 || n_max > RS_MAX_SAMPLES || window < 1 || step < 1 || B < 1 || B > RS_MAX_ROWS) return -1;
+  const long long nwin = n_max >= window ? (n_max - window) / step + 1 : 0;
+  const long long tiles = nwin ? (nwin + TR_TILE - 1) / TR_TILE : 1;
+  return 2 * tiles * B;
+}
+
+int smi_trim_rows(const float* in_dev, long long in_stride, const int32_t* n_host, int B, int window, int step, double threshold,
+                  int margin, int32_t* work_dev, long long work_len, int32_t* bounds_dev, void* stream) {
+  SMI_REQUIRE(in_dev && n_host && work_dev && bounds_dev, "smi_trim_rows: null argument");
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "smi_trim_rows: B=%d outside 1..%d", B, RS_MAX_ROWS);
+  SMI_REQUIRE(window >= 1 && window <= RS_MAX_SAMPLES, "smi_trim_rows: window=%d outside 1..%d", window, RS_MAX_SAMPLES);
+  SMI_REQUIRE(step >= 1 && step <= RS_MAX_SAMPLES, "smi_trim_rows: step=%d outside 1..%d", step, RS_MAX_SAMPLES);
+  SMI_REQUIRE((long long)(TR_TILE - 1) * step + window <= TR_LDS_FLOATS,
+              "smi_trim_rows: window=%d with step=%d: %d windows span %lld samples, above %d (the kernel stages them in 64 KiB of LDS)", window,
+              step, TR_TILE, (long long)(TR_TILE - 1) * step + window, TR_LDS_FLOATS);
+  SMI_REQUIRE(threshold >= 0.0 && threshold <= 1e150, "smi_trim_rows: threshold=%g outside 0..1e150", threshold);   // (NaN fails too)
+  SMI_REQUIRE(margin >= 0 && margin <= RS_MAX_SAMPLES, "smi_trim_rows: margin=%d outside 0..%d", margin, RS_MAX_SAMPLES);
+  SMI_REQUIRE(in_stride >= 1, "smi_trim_rows: in_stride=%lld must be positive", in_stride);
+  TrArgs A;
+  int n_max = 0;
+  for (int b = 0; b < B; ++b) {
+    SMI_REQUIRE(n_host[b] >= 0 && n_host[b] <= RS_MAX_SAMPLES && n_host[b] <= in_stride, "smi_trim_rows: n[%d]=%d outside 0..min(%d, in_stride=%lld)",
+                b, n_host[b], RS_MAX_SAMPLES, in_stride);
+    A.n[b] = n_host[b];
+    if (n_host[b] > n_max) n_max = n_host[b];
+  }
+  const long long need = smi_trim_work_len(n_max, window, step, B);
+  SMI_REQUIRE(work_len >= need, "smi_trim_rows: work_len=%lld below %lld (smi_trim_work_len)", work_len, need);
+  const int tiles = (int)(need / (2 * B));
+  const size_t lds = ((size_t)(TR_TILE - 1) * step + window) * sizeof(float);
+  hipLaunchKernelGGL(k_trim_scan, dim3(tiles, B), dim3(TR_BLOCK), lds, (hipStream_t)stream, A, in_dev, in_stride, window, step,
+                     threshold * threshold * (double)window, tiles, work_dev);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_trim_bounds, dim3(B), dim3(64), 0, (hipStream_t)stream, A, window, step, margin, tiles, work_dev, bounds_dev);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+long long smi_concat_layout(const int32_t* start_host, const int32_t* end_host, const int32_t* gap_host, int B, long long* offset_host) {
+  if (!start_host || !end_host || !gap_host || B < 1 || B > RS_MAX_ROWS) return -1;
+  long long total = 0;
+  for (int b = 0; b < B; ++b) {
+    if (start_host[b] < 0 || end_host[b] < start_host[b] || gap_host[b] < 0) return -1;
+    if (end_host[b] > start_host[b]) total += gap_host[b];
+    if (offset_host) offset_host[b] = total;
+    total += end_host[b] - start_host[b];
+  }
+  return total;
+}
+
+int smi_concat_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host,
+                    const int32_t* gap_host, int B, int fade, float* out_dev, long long cap, long long* offset_host, long long* total_host,
+                    void* stream) {
+  SMI_REQUIRE(in_dev && n_host && start_host && end_host && gap_host && out_dev, "smi_concat_rows: null argument");
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "smi_concat_rows: B=%d outside 1..%d", B, RS_MAX_ROWS);
+  SMI_REQUIRE(fade >= 0 && fade <= RS_MAX_SAMPLES, "smi_concat_rows: fade=%d outside 0..%d", fade, RS_MAX_SAMPLES);
+  SMI_REQUIRE(in_stride >= 1, "smi_concat_rows: in_stride=%lld must be positive", in_stride);
+  for (int b = 0; b < B; ++b) {
+    SMI_REQUIRE(n_host[b] >= 0 && n_host[b] <= RS_MAX_SAMPLES && n_host[b] <= in_stride,
+                "smi_concat_rows: n[%d]=%d outside 0..min(%d, in_stride=%lld)", b, n_host[b], RS_MAX_SAMPLES, in_stride);
+    SMI_REQUIRE(start_host[b] >= 0, "smi_concat_rows: start[%d]=%d is negative", b, start_host[b]);
+    SMI_REQUIRE(end_host[b] >= start_host[b], "smi_concat_rows: end[%d]=%d below start[%d]=%d", b, end_host[b], b, start_host[b]);
+    SMI_REQUIRE(end_host[b] <= n_host[b], "smi_concat_rows: end[%d]=%d above n[%d]=%d", b, end_host[b], b, n_host[b]);
+    SMI_REQUIRE(gap_host[b] >= 0 && gap_host[b] <= RS_MAX_SAMPLES, "smi_concat_rows: gap[%d]=%d outside 0..%d", b, gap_host[b], RS_MAX_SAMPLES);
+  }
+  long long off[RS_MAX_ROWS];
+  const long long total = smi_concat_layout(start_host, end_host, gap_host, B, off);
+  SMI_REQUIRE(cap >= 1 && cap >= total && cap < (1LL << 31), "smi_concat_rows: cap=%lld outside max(1, the total length %lld)..2^31 - 1", cap, total);
+  CcArgs A;
+  long long longest = cap - total;
+  for (int b = 0; b < B; ++b) {
+    CcRow& r = A.r[b];
+    r.src = start_host[b]; r.len = end_host[b] - start_host[b]; r.off = (int32_t)off[b];
+    r.lead = r.len ? gap_host[b] : 0;
+    r.fade = fade < r.len / 2 ? fade : r.len / 2;
+    if ((long long)r.lead + r.len > longest) longest = (long long)r.lead + r.len;
+    if (offset_host) offset_host[b] = off[b];
+  }
+  if (total_host) *total_host = total;
+  const int tiles = longest ? (int)((longest + CC_TILE - 1) / CC_TILE) : 1;
+  hipLaunchKernelGGL(k_concat_rows, dim3(tiles, B + 1), dim3(RS_BLOCK), 0, (hipStream_t)stream, A, B, in_dev, in_stride, out_dev, total, cap);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

@@ -250,6 +250,11 @@ SYMBOLS = {
                                 _P(C.c_int32), _VP]),
     "smi_join_piece_len": (C.c_longlong, [_I, _I, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _I, _P(C.c_longlong),
                                           _P(C.c_longlong)]),
+    "smi_trim_work_len": (C.c_longlong, [C.c_longlong, _I, _I, _I]),
+    "smi_trim_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _I, _I, _I, C.c_double, _I, _VP, C.c_longlong, _VP, _VP]),
+    "smi_concat_layout": (C.c_longlong, [_P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_longlong)]),
+    "smi_concat_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _I, _VP, C.c_longlong,
+                             _P(C.c_longlong), _P(C.c_longlong), _VP]),
 }
 
 # include/sparkmi_debug.h: exported by libsparkmi_diag.so only

@@ -8,6 +8,9 @@ may differ between the two at near-ties.  Nothing here imports scipy: the taps a
 
 ``StreamJoiner`` (``smi_join_*``) is the streaming form of that output end: overlapping chunks in, contiguous pieces out,
 cross-faded and resampled with the state kept across chunk edges on the device.
+
+``DeviceAudio.trim_rows`` / ``concat_rows`` (``smi_trim_rows``, ``smi_concat_rows``) are the audio edge of long-form synthesis:
+the speech bounds of vocoded rows, and the trimmed rows as one waveform with pauses and faded edges.
 """
 from __future__ import annotations
 
@@ -159,6 +162,66 @@ class DeviceAudio:
                         "smi_rs_prompt_rows")
         assert list(got) == n_out, (list(got), n_out)
         return wav, ref, gain, n_out
+
+    def _rows(self, x, n: Sequence[int], who: str) -> int:
+        import torch
+        B = len(n)
+        if x.dim() != 2 or x.shape[0] != B or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+            raise ValueError(f"{who} takes a contiguous [B][stride] float32 tensor on the device, one length per row")
+        return B
+
+    def trim_rows(self, x, n: Sequence[int], window: int, step: int, threshold: float, margin: int) -> List[Tuple[int, int]]:
+        """The speech bounds of rows (include/sparkmi.h, smi_trim_rows; ``detect_speech_boundaries``' arithmetic).  ``x``:
+        [B][stride] float32 on the device, row b valid for ``n[b]``.  Returns [(start, end)] per row: (0, n) for a row shorter
+        than ``window``, (0, 0) for a row without a speech window.  Two launches and one copy of 8 B bytes to the host, which
+        waits for it: the only synchronisation of the long-form path."""
+        import torch
+        B = self._rows(x, n, "trim_rows")
+        need = self._lib.smi_trim_work_len(max(0, max(int(v) for v in n)) if B else 0, int(window), int(step), max(1, min(B, MAX_ROWS)))
+        work = torch.empty((max(2, int(need)),), dtype=torch.int32, device=self.device)
+        bounds = torch.empty((max(1, B), 2), dtype=torch.int32, device=self.device)
+        self._lib.check(self._lib.smi_trim_rows(C.c_void_p(x.data_ptr()), x.shape[1], (C.c_int32 * B)(*[int(v) for v in n]), B, int(window),
+                                                int(step), float(threshold), int(margin), C.c_void_p(work.data_ptr()), work.numel(),
+                                                C.c_void_p(bounds.data_ptr()), self._stream()), "smi_trim_rows")
+        return [(int(a), int(b)) for a, b in bounds.cpu().tolist()]
+
+    def concat_layout(self, bounds: Sequence[Tuple[int, int]], gaps: Sequence[int]) -> Tuple[List[int], int]:
+        """(the offset of every piece in the assembled waveform, its total length): ``smi_concat_layout``, pure host arithmetic"""
+        B = len(bounds)
+        if len(gaps) != B:
+            raise ValueError("one gap per row")
+        i32 = lambda v: (C.c_int32 * B)(*[int(a) for a in v])   # noqa: E731
+        off = (C.c_longlong * max(1, B))()
+        total = self._lib.smi_concat_layout(i32(b[0] for b in bounds), i32(b[1] for b in bounds), i32(gaps), B, off)
+        if total < 0:
+            raise ValueError(f"concat_layout: 1..{MAX_ROWS} rows with 0 <= start <= end and gap >= 0, not {list(bounds)}, {list(gaps)}")
+        return list(off)[:B], int(total)
+
+    def concat_rows(self, x, bounds: Sequence[Tuple[int, int]], gaps: Sequence[int], fade: int, out=None,
+                    n: Optional[Sequence[int]] = None):
+        """Pieces ``x[b, start_b : end_b]`` into one waveform on the device, each non-empty piece behind ``gaps[b]`` zeros, its
+        first and last min(``fade``, length // 2) samples weighted (include/sparkmi.h, smi_concat_rows).  ``n``: the rows' valid
+        lengths (end <= n is checked; None: the stride).  ``out``: a contiguous 1-D float32 tensor on the device to write to (zeros from the total
+        length to its end); None: one of exactly the total length (at least one sample).  Returns (out, total).  One launch,
+        nothing waits."""
+        import torch
+        if n is None:
+            n = [x.shape[1]] * len(bounds)
+        B = self._rows(x, n, "concat_rows")
+        if len(bounds) != B or len(gaps) != B:
+            raise ValueError("one (start, end) and one gap per row")
+        i32 = lambda v: (C.c_int32 * B)(*[int(a) for a in v])   # noqa: E731
+        st, en, gp = i32(b[0] for b in bounds), i32(b[1] for b in bounds), i32(gaps)
+        if out is None:
+            total = self._lib.smi_concat_layout(st, en, gp, B, None)
+            out = torch.empty((max(1, int(total)),), dtype=torch.float32, device=self.device)   # (a bad row: the call below names it)
+        elif out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("concat_rows: out must be a contiguous 1-D float32 tensor on the device")
+        total = C.c_longlong()
+        self._lib.check(self._lib.smi_concat_rows(C.c_void_p(x.data_ptr()), x.shape[1], i32(n), st, en, gp, B, int(fade),
+                                                  C.c_void_p(out.data_ptr()), out.numel(), None, C.byref(total), self._stream()),
+                        "smi_concat_rows")
+        return out, int(total.value)
 
 
 class StreamJoiner:

@@ -8,7 +8,9 @@ kernels: ``self.model.generate`` (``SparkLLM``) and ``self.audio_tokenizer.detok
 ``prompt_tokens`` (pre-computed prompt audio tokens), ``inference_batch``,
 ``inference_stream`` (chunked vocoding while the LLM generates, the reference's decoupled Triton mode), ``serve`` (in-flight
 batching) and ``serve_stream`` (both at once: chunked audio for every live request of an in-flight batch); the two streaming
-calls take ``joined=True`` for contiguous, playable pieces at any output rate (the chunks joined on the device).
+calls take ``joined=True`` for contiguous, playable pieces at any output rate (the chunks joined on the device);
+``inference_long`` / ``inference_long_stream`` (text of any length: sentences as the rows of one in-flight session, their
+waveforms trimmed and joined on the device).
 """
 from __future__ import annotations
 
@@ -547,6 +549,34 @@ class SparkTTS:
         if glob is None:
             raise ValueError(f"{ntok} global tokens were not generated; the speaker encoder needs them")
 
+    # ------------------------------------------------------------------ finished requests: tokens -> rows -> waveforms on the device
+    def _cut_eos(self, toks: List[int]) -> List[int]:
+        """``toks`` up to and including its first eos id"""
+        stops = [toks.index(e) for e in self._eos if e in toks]
+        return toks[: min(stops) + 1] if stops else toks
+
+    def _speech_row(self, i, toks: Sequence[int], glob) -> Tuple[List[int], torch.Tensor]:
+        """(semantic token values, global token ids) of request ``i``'s generated ids; ``glob``: the prompt's global token ids,
+        or None when the ids carry them (voice creation)"""
+        sem, gl = self._parse(toks)
+        g = torch.tensor(gl, dtype=torch.long) if glob is None else torch.as_tensor(glob).reshape(-1).long()
+        ntok = self.audio_tokenizer.model.cfg.spk_token_num
+        if g.numel() != ntok:
+            raise ValueError(f"request {i}: {g.numel()} global tokens, the speaker encoder needs {ntok}")
+        if not sem:
+            raise ValueError(f"request {i}: the model generated no semantic tokens")
+        return sem, g
+
+    def _vocode_rows(self, rows: Sequence[Tuple[List[int], torch.Tensor]]):
+        """One ragged vocoder call for ``rows`` of (semantic values, global ids): (waveforms [B][stride] float32 on the device,
+        row b valid for ``lens[b] * hop`` samples; lens, in frames)"""
+        lens = [len(sem) for sem, _ in rows]
+        sem_t = torch.zeros((len(rows), max(lens)), dtype=torch.long)
+        for b, (sem, _) in enumerate(rows):
+            sem_t[b, : len(sem)] = torch.tensor(sem)
+        wav = self.audio_tokenizer.model.detokenize(sem_t, torch.stack([g for _, g in rows]).unsqueeze(1), lengths=lens)
+        return wav.squeeze(1), lens
+
     @torch.no_grad()
     def serve(self, requests, temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *, do_sample: bool = True,
               max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False):
@@ -573,8 +603,7 @@ class SparkTTS:
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
             for _ in checked(requests):
                 pass
-        voc = self.audio_tokenizer.model
-        ntok, hop = voc.cfg.spk_token_num, voc.hop
+        hop = self.audio_tokenizer.model.hop
         globals_: Dict[int, Optional[torch.Tensor]] = {}
         self.model.set_sampling(do_sample, temperature, int(top_k), float(top_p), seed)
 
@@ -597,22 +626,11 @@ class SparkTTS:
                 lps = None
                 if isinstance(toks, tuple):
                     toks, lps = toks
-                stops = [toks.index(e) for e in self._eos if e in toks]
-                if stops:
-                    toks = toks[: min(stops) + 1]
-                sem, glob = self._parse(toks)
-                g = torch.tensor(glob, dtype=torch.long) if globals_[i] is None else torch.as_tensor(globals_[i]).reshape(-1).long()
-                if g.numel() != ntok:
-                    raise ValueError(f"request {i}: {g.numel()} global tokens, the speaker encoder needs {ntok}")
-                if not sem:
-                    raise ValueError(f"request {i}: the model generated no semantic tokens")
-                rows.append((sem, g))
+                toks = self._cut_eos(toks)
+                rows.append(self._speech_row(i, toks, globals_[i]))
                 infos.append(None if lps is None else _lp_info(toks, lps[: len(toks)]))
-            lens = [len(sem) for sem, _ in rows]
-            sem_t = torch.zeros((len(rows), max(lens)), dtype=torch.long)
-            for b, (sem, _) in enumerate(rows):
-                sem_t[b, : len(sem)] = torch.tensor(sem)
-            wav = voc.detokenize(sem_t, torch.stack([g for _, g in rows]).unsqueeze(1), lengths=lens).squeeze(1).cpu().numpy()
+            wav, lens = self._vocode_rows(rows)
+            wav = wav.cpu().numpy()
             return [(wav[b, : lens[b] * hop].copy(), infos[b]) if infos[b] is not None else wav[b, : lens[b] * hop].copy()
                     for b in range(len(rows))]
 
@@ -624,17 +642,9 @@ class SparkTTS:
             lps = None
             if isinstance(toks, tuple):   # a flagged request: (tokens, log-probabilities)
                 toks, lps = toks
-            stops = [toks.index(e) for e in self._eos if e in toks]
-            if stops:
-                toks = toks[: min(stops) + 1]
-            sem, glob = self._parse(toks)
-            g = torch.tensor(glob, dtype=torch.long) if globals_[i] is None else torch.as_tensor(globals_[i]).reshape(-1).long()
-            if g.numel() != ntok:
-                raise ValueError(f"request {i}: {g.numel()} global tokens, the speaker encoder needs {ntok}")
-            if not sem:
-                raise ValueError(f"request {i}: the model generated no semantic tokens")
-            wav = voc.detokenize(torch.tensor([sem], dtype=torch.long), g.reshape(1, 1, -1), lengths=[len(sem)])
-            w = wav.reshape(-1)[: len(sem) * hop].cpu().numpy().copy()
+            toks = self._cut_eos(toks)
+            wav, lens = self._vocode_rows([self._speech_row(i, toks, globals_[i])])
+            w = wav[0, : lens[0] * hop].cpu().numpy().copy()
             if lps is None:
                 yield i, w
             else:
@@ -863,3 +873,211 @@ class SparkTTS:
         finally:
             parked.clear()     # the snapshots of requests that never resumed go with the generator
             vs.synchronize()   # an abandoned stream leaves no vocoder work behind (the handle's scratch is shared with detokenize)
+
+    # ------------------------------------------------------------------ long text: sentences as rows, trimmed and joined on the device
+    def _long_pieces(self, text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
+                     max_new_tokens, seed, prompt_tokens, keys: dict, max_width, min_width, pause, trim, trim_threshold, fade, eager: bool,
+                     info: dict):
+        """The engine of ``inference_long`` and ``inference_long_stream``: yields (first sentence, joined [total] float32 on the
+        device, [(offset in it, gap, length) per sentence]) for runs of consecutive sentences in text order -- with ``eager``
+        as soon as the next sentence due and those behind it are done, else in runs of ``max_batch`` once all are done.  Fills
+        ``info``.  Everything is checked before anything reaches the device."""
+        from .longform import control_prefix, control_prompt_ids, ready_run, sentence_seeds, split_text, trim_params
+        sentences = split_text(text, max_width, min_width)
+        for name, v in (("pause", pause), ("fade", fade), ("trim_threshold", trim_threshold)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"{name} must be a finite number >= 0, not {v!r}")
+        n_sent, sr, decode_stride = len(sentences), int(self.sample_rate), 8
+        gap, fade_n = int(round(pause * sr)), int(round(fade * sr))
+        window, step, margin = trim_params(sr)
+        seeds = sentence_seeds(seed, n_sent)
+        reqs = [dict(keys, text=s, **({} if seeds[k] is None else {"seed": seeds[k]})) for k, s in enumerate(sentences)]
+        sampling = [_request_sampling(r, self.speech_token_ids, self._eos, self.model.cfg.vocab_size) for r in reqs]
+        tokenize = lambda p: self.tokenizer([p], return_tensors="pt").input_ids[0].tolist()   # noqa: E731
+        voc = self.audio_tokenizer.model
+        hop = voc.hop
+        if gender is None:    # voice cloning: the prompt is encoded once, every sentence's prompt carries its tokens
+            if prompt_tokens is None:
+                prompt_tokens = self.audio_tokenizer.tokenize(prompt_speech_path)
+            glob = torch.as_tensor(prompt_tokens[0]).reshape(-1).long()
+            sessions = [list(range(n_sent))]
+        else:                 # voice creation: sentence 0 alone decides the style values and the speaker tokens of all
+            build_control_prompt(gender, pitch, speed, sentences[0])
+            glob = None
+            sessions = [[0]] + ([list(range(1, n_sent))] if n_sent > 1 else [])
+        prefix: List[int] = []
+        budgets: Dict[int, int] = {}
+        info.update(sentences=sentences, token_ids=[None] * n_sent, bounds=[None] * n_sent, offsets=[None] * n_sent, truncated=[], silent=[])
+        audio = self._device_audio()
+        tokens: Dict[int, List[int]] = {}
+        state = {"due": 0, "total": 0, "spoken": False}
+
+        def llm_requests(ks):
+            for k in ks:
+                if gender is None:
+                    ids = tokenize(self.process_prompt(sentences[k], None, prompt_text, prompt_tokens)[0])
+                else:
+                    ids = control_prompt_ids(tokenize, gender, pitch, speed, sentences[k], prefix)
+                budgets[k] = min(int(max_new_tokens), self._max_positions - len(ids) - decode_stride, self._max_frames)
+                if budgets[k] < 1:
+                    raise ValueError(f"sentence {k}: a prompt of {len(ids)} tokens leaves no room in max_positions={self._max_positions}")
+                yield k, ids, budgets[k], self._eos, sampling[k]
+
+        def flush(ks):   # consecutive sentences: one ragged vocoder call, their bounds, one assembly launch
+            rows = [self._speech_row(k, tokens[k], glob) for k in ks]
+            wav, lens = self._vocode_rows(rows)
+            wav = wav.contiguous()
+            n = [f * hop for f in lens]
+            bounds = audio.trim_rows(wav, n, window, step, float(trim_threshold), margin) if trim else [(0, v) for v in n]
+            gaps = []
+            for a, b in bounds:
+                gaps.append(gap if b > a and state["spoken"] else 0)
+                state["spoken"] = state["spoken"] or b > a
+            offs, total = audio.concat_layout(bounds, gaps)
+            out = None
+            if total:
+                out, _ = audio.concat_rows(wav, bounds, gaps, fade_n, n=n)
+            for k, (a, b), o, g in zip(ks, bounds, offs, gaps):
+                info["bounds"][k], info["offsets"][k] = (a, b), state["total"] + o
+                if b == a:
+                    info["silent"].append(k)
+            res = ks[0], out, [(o - g, g, b - a) for (a, b), o, g in zip(bounds, offs, gaps)]
+            state["total"] += total
+            state["due"] = ks[-1] + 1
+            for k in ks:
+                del tokens[k]
+            return res
+
+        for ks in sessions:
+            self.model.set_sampling(do_sample, temperature, int(top_k), float(top_p), seed)
+            for k, toks in self.model.serve(llm_requests(ks), max_live=self._max_batch, decode_stride=decode_stride):
+                full = len(toks) >= budgets[k]
+                toks = self._cut_eos(toks)
+                if full and not any(e in toks for e in self._eos):
+                    info["truncated"].append(k)
+                info["token_ids"][k] = tokens[k] = list(toks)
+                if gender is not None and k == 0:
+                    prefix, gl = control_prefix(toks, self._map.sem, self._map.glob, voc.cfg.spk_token_num)
+                    glob = torch.tensor(gl, dtype=torch.long)
+                while eager:
+                    run = ready_run(tokens, state["due"], self._max_batch)
+                    if not run:
+                        break
+                    yield flush(run)
+            while state["due"] < ks[-1] + 1:
+                yield flush(ready_run(tokens, state["due"], self._max_batch))
+        info["truncated"].sort()
+        info["silent"].sort()
+
+    def _long_keys(self, prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
+                   min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size) -> dict:
+        """the request keys every sentence of a long text shares, as ``inference`` builds them for one utterance"""
+        if gender is None and prompt_tokens is None and prompt_speech_path is None:
+            raise ValueError("inference_long needs a voice: prompt_speech_path or prompt_tokens (cloning), or gender / pitch / speed (creation)")
+        n_gram = ngram_size(no_repeat_ngram_size)
+        return dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                    min_new_tokens=min_new_tokens, penalize_prompt=penalize_prompt,
+                    **({ALLOW_KEY: allowed_token_ids} if allowed_token_ids is not None else {}),
+                    **({SPEECH_ONLY_KEY: speech_tokens_only} if speech_tokens_only else {}),
+                    **({NGRAM_KEY: n_gram} if n_gram > 0 else {}))
+
+    @torch.no_grad()
+    def inference_long(self, text: str, prompt_speech_path: Path = None, prompt_text: str = None,
+                       gender: str = None, pitch: str = None, speed: str = None,
+                       temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *,
+                       do_sample: bool = True, max_new_tokens: int = 3000, seed: Optional[int] = None,
+                       prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                       min_new_tokens: int = 0, penalize_prompt: bool = True, allowed_token_ids: Optional[Sequence[int]] = None,
+                       speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0,
+                       max_width: int = 300, min_width: int = 20, pause: float = 0.25, trim: bool = True,
+                       trim_threshold: float = 0.01, fade: float = 0.005, output_sample_rate: Optional[int] = None,
+                       return_info: bool = False):
+        """A text of any length -> one float32 waveform: the text is cut into sentences (``longform.split_text``: ``max_width``,
+        ``min_width``), the sentences are generated with the same voice as the requests of one in-flight session (up to
+        ``max_batch`` live; ``max_new_tokens`` is per sentence), vocoded in ragged calls, cut at their speech bounds
+        (``trim``, ``trim_threshold``: ``remove_silence_on_both_ends``' arithmetic; include/sparkmi.h, smi_trim_rows) and joined
+        in text order with ``pause`` seconds of silence between them and ``fade`` seconds of fade at every piece's edges
+        (smi_concat_rows).  The waveforms stay on the device up to the one copy of the result; only the bounds (8 bytes a
+        sentence) cross before it.
+
+        Voice cloning: the prompt audio is encoded once (or ``prompt_tokens`` is taken as given); sentence k has the tokens of
+        ``inference(sentence_k, ..., prompt_tokens=...)`` through the admission path.  Voice creation (``gender`` given):
+        sentence 0 runs alone; the ids it generated before its first semantic token -- the style values and the global-token
+        block -- are appended to the control prompt of every later sentence, which therefore continues from the same style and
+        speaker tokens and generates semantic tokens only; all are vocoded with sentence 0's global tokens.  ValueError if
+        sentence 0 gives no complete global block.  ``seed=s``: sentence k carries ``s + k``; None: the handle's key.
+
+        ``output_sample_rate``: the joined waveform is resampled on the device (``audio.DeviceAudio.resample_rows``) before the
+        copy.  ``return_info=True``: (waveform, info) with ``sentences``, ``token_ids`` (per sentence, up to and including its
+        eos), ``bounds`` (per sentence, in samples of its untrimmed row), ``offsets`` (of the pieces in the joined waveform at the
+        model's rate), ``truncated`` (the sentences that used their whole budget -- the room left in ``max_positions`` and
+        ``max_frames`` bound it -- without an eos) and ``silent`` (those with an empty piece, which also get no pause)."""
+        out_ratio = self._output_ratio(output_sample_rate)
+        keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
+                               min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
+        info: dict = {}
+        parts = [out for _, out, _ in self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p,
+                                                        do_sample, max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim,
+                                                        trim_threshold, fade, False, info) if out is not None]
+        if not parts:
+            wav = np.zeros(0, dtype=np.float32)
+        else:
+            joined = parts[0] if len(parts) == 1 else torch.cat(parts)   # (more sentences than max_batch: one run each)
+            if out_ratio is not None:
+                y, n_out = self._device_audio().resample_rows(joined.reshape(1, -1), [joined.numel()], [out_ratio[0]], [out_ratio[1]])
+                joined = y[0, : n_out[0]]
+            wav = joined.cpu().numpy().copy()
+        return (wav, info) if return_info else wav
+
+    @torch.no_grad()
+    def inference_long_stream(self, text: str, prompt_speech_path: Path = None, prompt_text: str = None,
+                              gender: str = None, pitch: str = None, speed: str = None,
+                              temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *,
+                              do_sample: bool = True, max_new_tokens: int = 3000, seed: Optional[int] = None,
+                              prompt_tokens: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                              repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                              min_new_tokens: int = 0, penalize_prompt: bool = True, allowed_token_ids: Optional[Sequence[int]] = None,
+                              speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0,
+                              max_width: int = 300, min_width: int = 20, pause: float = 0.25, trim: bool = True,
+                              trim_threshold: float = 0.01, fade: float = 0.005,
+                              output_sample_rate: Optional[int] = None) -> Iterator[np.ndarray]:
+        """``inference_long`` piece by piece: yields contiguous float32 pieces in text order, sentence k's pause + trimmed and faded
+        piece as soon as k and every sentence before it are done (an empty piece is not yielded).  At the model's rate the
+        pieces' concatenation is ``inference_long``'s waveform bit for bit: a piece's bits are its own (include/sparkmi.h,
+        smi_concat_rows).  With ``output_sample_rate`` the pieces go through a ``StreamJoiner`` with ``overlap = 0`` -- plain
+        concatenation with the resampler's state kept across the pieces -- and the concatenation of what is yielded (the last
+        piece is the resampler's flush) is bit for bit ``inference_long(..., output_sample_rate=...)``."""
+        out_ratio = self._output_ratio(output_sample_rate)
+        keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
+                               min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
+        pieces = self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
+                                   max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim, trim_threshold, fade, True, {})
+        joiner = None
+        for _, out, spans in pieces:
+            if out is None:
+                continue
+            if out_ratio is None:
+                host = out.cpu().numpy()
+                for start, g, length in spans:
+                    if length:
+                        yield host[start: start + g + length].copy()
+                continue
+            if joiner is None:   # (pieces of up to a pause and a whole vocoder row)
+                from .audio import StreamJoiner
+                key = (1, int(round(pause * self.sample_rate)) + self._max_frames * self.audio_tokenizer.model.hop, 0) + tuple(out_ratio)
+                if getattr(self, "_joiners", None) is None:
+                    self._joiners = {}
+                if key not in self._joiners:
+                    self._joiners[key] = StreamJoiner(*key, device=self.device)
+                joiner = self._joiners[key]
+                joiner.reset()
+            for start, g, length in spans:
+                if length:
+                    y, n_out = joiner.push(out[start: start + g + length].reshape(1, -1), [(0, g + length, False)])
+                    if n_out[0]:
+                        yield y[0, : n_out[0]].cpu().numpy().copy()
+        if joiner is not None:   # an empty last chunk empties the resampler
+            y, n_out = joiner.push(torch.zeros((1, 1), dtype=torch.float32, device=self.device), [(0, 0, True)])
+            if n_out[0]:
+                yield y[0, : n_out[0]].cpu().numpy().copy()
