@@ -757,6 +757,63 @@ int smi_concat_rows(const float* in_dev, long long in_stride, const int32_t* n_h
                     const int32_t* gap_host, int B, int fade, float* out_dev, long long cap, long long* offset_host, long long* total_host,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Output loudness: the programme loudness of rows after ITU-R BS.1770 (K-weighting, 400 ms blocks, absolute and relative gate)
+ * and the gain that brings each row to a target under a peak ceiling, measured and applied on the device.  Free functions like
+ * the long-form edge above: no handle, no state, asynchronous on the caller's stream, never synchronising, opt-in.  Every
+ * argument of every row is checked before anything reaches the device: a bad one returns SMI_EINVAL, names the argument in
+ * smi_last_error and launches nothing.  B <= 64, n <= 2^24.
+ *
+ * A row is measured over a span x[start .. end) of L samples.  Samples before start and from end on are never read; the filter
+ * starts from zero state (zero input and output history) at start.
+ *
+ * K-weighting.  Two cascaded biquads in direct form I, float64; coef_host[10] = b0 b1 b2 a1 a2 of stage 1, then of stage 2, is
+ * data the caller passes (sparkmi/audio.py: k_weighting derives it for a sample rate; the device designs no filter).  Every
+ * fp32 sample enters as its exact float64 value v.  With the stage's last inputs v1, v2 and last outputs y1, y2:
+ *     w = ((fl(b0 v) + fl(b1 v1)) + fl(b2 v2)) - fl(a2 y2),    y = w - fl(a1 y1)
+ * -- every product and sum rounded on its own (no FMA), in that order; stage 2 takes stage 1's y as its v.
+ * Segments.  The span is cut into segments of 128 samples (a constant of the arithmetic, not of the call).  The state of the
+ * cascade, s = (y1, y2 of stage 1, y1, y2 of stage 2), at the start of segment k + 1 is
+ *     s_{k+1} = T s_k + e_k,   s_0 = 0
+ * where e_k is the state at the end of segment k filtered from s = 0 (with its true input history: the two samples before it),
+ * T is the 4x4 matrix whose column i is unit state i after 128 samples of silence -- computed on the host in float64 by the
+ * recurrence above --, and row i of the product is (((fl(T_i0 s_0) + fl(T_i1 s_1)) + fl(T_i2 s_2)) + fl(T_i3 s_3)) + e_i.  Each
+ * segment is then filtered from s_k.  In exact arithmetic that is the sequential filter; in float64 it differs from it by
+ * rounding only (DESIGN.md 4.1.3 derives the bound).
+ * Blocks.  block = the caller's sample count for 400 ms, a multiple of 4; hop = block / 4.  Block j covers [j hop, j hop + block)
+ * for j = 0 .. floor((L - block) / hop); a tail shorter than a hop is dropped.  y^2 is summed in ascending sample order within
+ * a hop part (the piece of a hop inside one segment), the parts of a hop in ascending order from 0, and
+ *     z_j = (((H_j + H_{j+1}) + H_{j+2}) + H_{j+3}) / fl64(block).
+ * Gates, both in the linear domain.  A = 10^((-70 + 0.691) / 10), computed once on the host.  Block j passes the absolute gate
+ * when z_j > A; of those, it passes the relative gate when z_j > fl64(0.1 * (sum of the passing z / their count)).  A sum over
+ * blocks takes j = t, t + 256, ... in ascending order for t = 0 .. 255, then adds the 256 partial sums in a fixed tree (t and
+ * t + 128, then t and t + 64, ...).  loudness = -0.691 + 10 log10(sum of the z passing both gates / their count).
+ * Defined here where the standard is silent:  1 <= L < block: one block, the whole span, z = (the hop sums in ascending
+ * order) / fl64(L), and the absolute gate alone;  no block passes, or L = 0: loudness = -inf, gain = 1, limit = 0.
+ * Peak.  peak = max |x| over the span, exact.  It is a SAMPLE peak: the 4x oversampled true peak is not measured.
+ * Gain, float64, formed on the device:  g = 10^((target - loudness) / 20);  g = min(g, 10^(max_gain_db / 20)) (limit = 1 where
+ * that binds);  if g * peak > ceiling then g = ceiling / peak (limit = 2).  A NaN target measures only: g = 1, limit = 0.
+ * Apply (smi_gain_rows).  out[i] = fl32(fl64(x[i]) * g): one float64 product, one rounding, no FMA.
+ *
+ * Launches, whatever B: k_loud_seg, grid (tiles of 64 segments, rows) -- a wave stages its tile in LDS with coalesced reads and
+ * each lane filters one segment from zero state --; k_loud_carry, one wave a row, the recurrence of s_k; k_loud_energy, the
+ * grid of k_loud_seg, each segment again from s_k, writing hop parts and the segment's max |x|; k_loud_gate, one block a row.
+ * smi_gain_rows is one launch, grid (tiles of 1024 samples, rows).  No atomics.  Guarantee: a row's four stats, bit for bit,
+ * depend on its span and the parameters alone -- not on B, the row's place, the strides, what lies outside the span or the grid. */
+/* float64 elements of work_dev that smi_loud_rows needs for B rows of at most n_max samples; -1 for a bad argument.  Pure host. */
+long long smi_loud_work_len(long long n_max, int block, int B);
+/* in_dev [B][in_stride] f32, row b valid for n_host[b]; 0 <= start_host[b] <= end_host[b] <= n_host[b] (both null: the whole
+ * row); target_host [B] float64 (LUFS; NaN: measure only); max_gain_db >= 0; ceiling > 0; work_dev [work_len] float64 scratch
+ * (contents do not matter before, mean nothing after); stats_dev [B][4] float64 receives (loudness, peak, gain, limit). */
+int smi_loud_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                  const double* coef_host, int block, const double* target_host, double max_gain_db, double ceiling, double* work_dev,
+                  long long work_len, double* stats_dev, void* stream);
+/* Row b of out_dev [B][out_stride] receives the row's n samples -- the span times stats_dev[b][2], read from the device, the
+ * rest copied -- and zeros from n to out_stride (>= the longest row).  out_dev == in_dev with equal strides is allowed (in
+ * place); any other overlap is refused. */
+int smi_gain_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                  const double* stats_dev, float* out_dev, long long out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

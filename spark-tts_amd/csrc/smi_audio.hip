@@ -16,8 +16,13 @@
 //                Tails and histories live in two sets a stream uses in turn, so one launch reads its state and writes the next.
 //   k_trim_scan, k_trim_bounds   the speech bounds of rows (smi_trim_rows): window energies in float64, summed from LDS; no atomics.
 //   k_concat_rows                trimmed rows into one waveform with gaps and faded edges (smi_concat_rows): one launch.
+//   k_loud_seg, k_loud_carry, k_loud_energy, k_loud_gate   programme loudness of rows (smi_loud_rows; BS.1770 K-weighting and
+//                gates) and the gain to a target: the serial filter is cut into segments of LD_SEG samples, one lane each, that
+//                run from zero state; one wave per row carries the true states across; a second pass sums y^2.  No atomics.
+//   k_gain_rows                  rows times their gain, read from the device (smi_gain_rows).
 #include <limits.h>
 
+#include <cmath>
 #include <vector>
 
 #include "smi_common.h"
@@ -35,6 +40,12 @@
 #define TR_BLOCK 256
 #define TR_LDS_FLOATS (RS_LDS_FLOATS - 64)   // samples of one tile; the block's few words of static LDS fit beside them in 64 KiB
 #define CC_TILE 1024            // output samples a block of k_concat_rows
+#define LD_SEG 128              // samples one lane filters in a row (smi_loud_rows): a constant of the arithmetic, never of the call
+#define LD_LANES 64             // segments a block of k_loud_seg / k_loud_energy: one wave
+#define LD_TILE (LD_SEG * LD_LANES)
+#define LD_PITCH (LD_SEG + 1)   // floats between two segments in LDS
+#define LD_GATE 256             // threads of k_loud_gate
+#define GN_TILE 1024            // samples a block of k_gain_rows
 
 namespace {
 
@@ -429,6 +440,257 @@ __global__ __launch_bounds__(RS_BLOCK) void k_concat_rows(CcArgs a, int B, const
   }
 }
 
+// ---- programme loudness of rows and the gain that brings them to a target (smi_loud_rows, smi_gain_rows)
+struct LdRow {
+  int32_t n, start, len;   // the row's samples; the span x[start .. start + len)
+};
+struct LdArgs {
+  LdRow r[RS_MAX_ROWS];
+};
+struct LdCoef {
+  double b[2][3], a1[2], a2[2];   // the two biquads of the K-weighting
+  double T[4][4];                 // zero-input transition of the cascade's state over LD_SEG steps (ld_transition)
+};
+struct LdTargets {
+  double t[RS_MAX_ROWS];
+};
+struct LdLayout {                 // float64 offsets into a row's part of work_dev
+  long long row, e, s, pk, parts, hops;
+  int32_t pps;                    // hop parts a segment can hold: (LD_SEG - 1) / hop + 2
+};
+// the cascade in direct form I: the last two inputs, the last two outputs of stage 1 and of stage 2
+struct LdState {
+  double x1, x2, p1, p2, q1, q2;
+};
+
+// One sample through both biquads: every product and sum rounded on its own, in this order.  The previous output enters last,
+// so the chain from sample to sample is one product and one difference a stage.
+__host__ __device__ __forceinline__ double ld_step(const LdCoef& c, LdState& s, double v) {
+  const double w = ((c.b[0][0] * v + c.b[0][1] * s.x1) + c.b[0][2] * s.x2) - c.a2[0] * s.p2;
+  const double y = w - c.a1[0] * s.p1;
+  const double u = ((c.b[1][0] * y + c.b[1][1] * s.p1) + c.b[1][2] * s.p2) - c.a2[1] * s.q2;
+  const double o = u - c.a1[1] * s.q1;
+  s.x2 = s.x1; s.x1 = v;
+  s.p2 = s.p1; s.p1 = y;
+  s.q2 = s.q1; s.q1 = o;
+  return o;
+}
+
+// T[.][i]: where unit state i stands after LD_SEG samples of silence (the input history is zero too)
+inline void ld_transition(LdCoef& c) {
+  for (int i = 0; i < 4; ++i) {
+    LdState s = {0.0, 0.0, i == 0 ? 1.0 : 0.0, i == 1 ? 1.0 : 0.0, i == 2 ? 1.0 : 0.0, i == 3 ? 1.0 : 0.0};
+    for (int t = 0; t < LD_SEG; ++t) ld_step(c, s, 0.0);
+    c.T[0][i] = s.p1; c.T[1][i] = s.p2; c.T[2][i] = s.q1; c.T[3][i] = s.q2;
+  }
+}
+
+// A block of one wave stages its tile -- LD_LANES segments of LD_SEG samples -- in LDS with coalesced reads; lane l then walks
+// segment l at lds[l * LD_PITCH ..] (the odd pitch puts the 64 lanes on 64 banks).  Returns the samples of this lane's segment
+// (0: none) and sets the input history from the two samples before it; the span's first segment starts from silence.
+__device__ __forceinline__ int ld_stage(const LdRow& r, const float* __restrict__ x, float* lds, LdState& s) {
+  const int t0 = blockIdx.x * LD_TILE, tid = threadIdx.x;
+  const int cnt = min(LD_TILE, r.len - t0);
+  for (int i = tid; i < cnt; i += LD_LANES) lds[(i / LD_SEG) * LD_PITCH + (i % LD_SEG)] = x[t0 + i];
+  __syncthreads();
+  const int i0 = t0 + tid * LD_SEG;
+  s.x1 = i0 >= 1 && i0 < r.len ? (double)x[i0 - 1] : 0.0;
+  s.x2 = i0 >= 2 && i0 < r.len ? (double)x[i0 - 2] : 0.0;
+  return max(0, min(LD_SEG, r.len - i0));
+}
+
+// grid (tiles of LD_TILE samples, rows): every segment but the row's last from zero state; its end state goes to E[segment]
+__global__ __launch_bounds__(LD_LANES) void k_loud_seg(LdArgs a, LdCoef c, const float* __restrict__ in, long long in_stride,
+                                                       double* __restrict__ work, LdLayout lay) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const LdRow r = a.r[blockIdx.y];
+  if ((long long)blockIdx.x * LD_TILE >= r.len) return;
+  LdState s = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  ld_stage(r, in + (size_t)blockIdx.y * in_stride + r.start, rs_lds, s);
+  const int k = blockIdx.x * LD_LANES + threadIdx.x;
+  const int nseg = (r.len + LD_SEG - 1) / LD_SEG;
+  if (k >= nseg - 1) return;   // (the last segment's end is nobody's start; every other segment is whole)
+  const float* seg = rs_lds + threadIdx.x * LD_PITCH;
+  for (int t = 0; t < LD_SEG; ++t) ld_step(c, s, (double)seg[t]);
+  double* E = work + (size_t)blockIdx.y * lay.row + lay.e + 4 * (size_t)k;
+  E[0] = s.p1; E[1] = s.p2; E[2] = s.q1; E[3] = s.q2;
+}
+
+// one wave per row: S[0] = 0, S[k + 1] = T S[k] + E[k].  The wave stages 64 end states in LDS at a time; every lane runs the
+// same recurrence from there and lane t keeps S[k0 + t], so the stores are coalesced.
+__global__ __launch_bounds__(64) void k_loud_carry(LdArgs a, LdCoef c, double* __restrict__ work, LdLayout lay) {
+  __shared__ double e[64][4];
+  const LdRow r = a.r[blockIdx.x];
+  const int nseg = (r.len + LD_SEG - 1) / LD_SEG, lane = threadIdx.x;
+  const double* E = work + (size_t)blockIdx.x * lay.row + lay.e;
+  double* S = work + (size_t)blockIdx.x * lay.row + lay.s;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  for (int k0 = 0; k0 < nseg; k0 += 64) {
+    if (k0 + lane < nseg - 1)
+      for (int i = 0; i < 4; ++i) e[lane][i] = E[4 * (size_t)(k0 + lane) + i];
+    __syncthreads();
+    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+    const int cnt = min(64, nseg - k0);
+    for (int t = 0; t < cnt; ++t) {
+      if (lane == t) { m0 = s0; m1 = s1; m2 = s2; m3 = s3; }
+      if (k0 + t < nseg - 1) {
+        const double n0 = (((c.T[0][0] * s0 + c.T[0][1] * s1) + c.T[0][2] * s2) + c.T[0][3] * s3) + e[t][0];
+        const double n1 = (((c.T[1][0] * s0 + c.T[1][1] * s1) + c.T[1][2] * s2) + c.T[1][3] * s3) + e[t][1];
+        const double n2 = (((c.T[2][0] * s0 + c.T[2][1] * s1) + c.T[2][2] * s2) + c.T[2][3] * s3) + e[t][2];
+        const double n3 = (((c.T[3][0] * s0 + c.T[3][1] * s1) + c.T[3][2] * s2) + c.T[3][3] * s3) + e[t][3];
+        s0 = n0; s1 = n1; s2 = n2; s3 = n3;
+      }
+    }
+    if (lane < cnt) {
+      double* d = S + 4 * (size_t)(k0 + lane);
+      d[0] = m0; d[1] = m1; d[2] = m2; d[3] = m3;
+    }
+    __syncthreads();
+  }
+}
+
+// grid as k_loud_seg: every segment again, from its true start state.  y^2 is summed in ascending sample order into one sum per
+// hop part -- the piece of a hop that lies in this segment -- and written to P[segment][part]; max |x| of the segment to PK.
+__global__ __launch_bounds__(LD_LANES) void k_loud_energy(LdArgs a, LdCoef c, int hop, const float* __restrict__ in, long long in_stride,
+                                                          double* __restrict__ work, LdLayout lay) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const LdRow r = a.r[blockIdx.y];
+  if ((long long)blockIdx.x * LD_TILE >= r.len) return;
+  LdState s = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int m = ld_stage(r, in + (size_t)blockIdx.y * in_stride + r.start, rs_lds, s);
+  if (m == 0) return;
+  const int k = blockIdx.x * LD_LANES + threadIdx.x;
+  double* row = work + (size_t)blockIdx.y * lay.row;
+  const double* S = row + lay.s + 4 * (size_t)k;
+  s.p1 = S[0]; s.p2 = S[1]; s.q1 = S[2]; s.q2 = S[3];
+  double* P = row + lay.parts + (size_t)k * lay.pps;
+  const float* seg = rs_lds + threadIdx.x * LD_PITCH;
+  int i = k * LD_SEG;                    // of the span
+  int edge = (i / hop + 1) * hop;        // where the hop that holds sample i ends
+  int p = 0, held = 0;
+  double acc = 0.0;
+  uint32_t pk = 0;
+  for (int t = 0; t < m; ++t) {
+    const float v = seg[t];
+    pk = max(pk, __float_as_uint(v) & 0x7FFFFFFFu);
+    const double o = ld_step(c, s, (double)v);
+    acc = acc + o * o;
+    held = 1;
+    if (++i == edge) {
+      P[p++] = acc;
+      acc = 0.0;
+      held = 0;
+      edge += hop;
+    }
+  }
+  if (held) P[p] = acc;
+  row[lay.pk + k] = (double)__uint_as_float(pk);
+}
+
+// ---- k_loud_gate's block-wide sums (LD_GATE threads): a fixed tree, the same whatever the grid
+__device__ __forceinline__ double ld_block_sum(double v, double* s) {
+  __syncthreads();
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = LD_GATE / 2; o; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + o];
+    __syncthreads();
+  }
+  return s[0];
+}
+__device__ __forceinline__ double ld_block_max(double v, double* s) {
+  __syncthreads();
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = LD_GATE / 2; o; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + o]);
+    __syncthreads();
+  }
+  return s[0];
+}
+// mean square of block j (of the whole span where it is shorter than a block)
+__device__ __forceinline__ double ld_z(const double* H, int j, int len, int block, int nh) {
+  if (len >= block) return (((H[j] + H[j + 1]) + H[j + 2]) + H[j + 3]) / (double)block;
+  double t = 0.0;
+  for (int h = 0; h < nh; ++h) t = t + H[h];
+  return t / (double)len;
+}
+
+// one block per row: hop parts into hops (ascending), hops into blocks, both gates, the loudness, the gain and its limits.
+// Thread t sums the blocks j = t, t + LD_GATE, ... in ascending order, then the fixed tree: a sum depends on the row alone.
+__global__ __launch_bounds__(LD_GATE) void k_loud_gate(LdArgs a, LdTargets tg, int block, double abs_gate, double max_gain_db, double ceiling,
+                                                       double* __restrict__ work, LdLayout lay, double* __restrict__ stats) {
+  __shared__ double red[LD_GATE];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const LdRow r = a.r[b];
+  const int len = r.len, hop = block / 4;
+  double* row = work + (size_t)b * lay.row;
+  double* H = row + lay.hops;
+  const double* P = row + lay.parts;
+  const int nh = (int)(((long long)len + hop - 1) / hop);
+  const int nseg = (len + LD_SEG - 1) / LD_SEG;
+  for (int h = tid; h < nh; h += LD_GATE) {
+    const long long lo = (long long)h * hop, hi = min((long long)len, lo + hop) - 1;
+    double t = 0.0;
+    for (int k = (int)(lo / LD_SEG); k <= (int)(hi / LD_SEG); ++k) t = t + P[(size_t)k * lay.pps + (h - (int)(((long long)k * LD_SEG) / hop))];
+    H[h] = t;
+  }
+  double pk = 0.0;
+  for (int k = tid; k < nseg; k += LD_GATE) pk = fmax(pk, row[lay.pk + k]);
+  const double peak = ld_block_max(pk, red);   // (its barriers also publish H to the block)
+  const int nblk = len >= block ? (len - block) / hop + 1 : (len >= 1 ? 1 : 0);
+  double sum = 0.0, cnt = 0.0;
+  for (int j = tid; j < nblk; j += LD_GATE) {
+    const double z = ld_z(H, j, len, block, nh);
+    if (z > abs_gate) { sum = sum + z; cnt = cnt + 1.0; }
+  }
+  const double sum1 = ld_block_sum(sum, red), cnt1 = ld_block_sum(cnt, red);
+  double sum2 = sum1, cnt2 = cnt1;
+  if (len >= block && cnt1 > 0.0) {
+    const double rel = 0.1 * (sum1 / cnt1);
+    sum = 0.0; cnt = 0.0;
+    for (int j = tid; j < nblk; j += LD_GATE) {
+      const double z = ld_z(H, j, len, block, nh);
+      if (z > abs_gate && z > rel) { sum = sum + z; cnt = cnt + 1.0; }
+    }
+    sum2 = ld_block_sum(sum, red);
+    cnt2 = ld_block_sum(cnt, red);
+  }
+  if (tid) return;
+  double loud = -INFINITY, g = 1.0, limit = 0.0;
+  if (cnt2 > 0.0) {
+    loud = -0.691 + 10.0 * log10(sum2 / cnt2);
+    const double target = tg.t[b];
+    if (target == target) {   // (a NaN target: measure only)
+      g = pow(10.0, (target - loud) / 20.0);
+      const double gmax = pow(10.0, max_gain_db / 20.0);
+      if (g > gmax) { g = gmax; limit = 1.0; }
+      if (g * peak > ceiling) { g = ceiling / peak; limit = 2.0; }
+    }
+  }
+  double* st = stats + 4 * (size_t)b;
+  st[0] = loud; st[1] = peak; st[2] = g; st[3] = limit;
+}
+
+// grid (tiles of GN_TILE samples, rows): the span times the row's gain, the rest of the row as it is, zeros from n to the stride
+__global__ __launch_bounds__(RS_BLOCK) void k_gain_rows(LdArgs a, const double* __restrict__ stats, const float* in, long long in_stride,
+                                                        float* out, long long out_stride) {
+  const LdRow r = a.r[blockIdx.y];
+  const double g = stats[4 * (size_t)blockIdx.y + 2];
+  const float* x = in + (size_t)blockIdx.y * in_stride;
+  float* y = out + (size_t)blockIdx.y * out_stride;
+  const long long k0 = (long long)blockIdx.x * GN_TILE;
+  const long long end = min(out_stride, k0 + GN_TILE);
+  for (long long i = k0 + threadIdx.x; i < end; i += RS_BLOCK) {
+    float v = 0.f;
+    if (i < r.n) {
+      v = x[i];
+      if (i >= r.start && i < (long long)r.start + r.len) v = (float)((double)v * g);
+    }
+    y[i] = v;
+  }
+}
+
 }  // namespace
 
 struct smi_rs {
@@ -813,6 +1075,118 @@ int smi_concat_rows(const float* in_dev, long long in_stride, const int32_t* n_h
   if (total_host) *total_host = total;
   const int tiles = longest ? (int)((longest + CC_TILE - 1) / CC_TILE) : 1;
   hipLaunchKernelGGL(k_concat_rows, dim3(tiles, B + 1), dim3(RS_BLOCK), 0, (hipStream_t)stream, A, B, in_dev, in_stride, out_dev, total, cap);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// where the parts of one row's scratch lie; the total is smi_loud_work_len
+static LdLayout ld_layout(long long n_max, int block) {
+  const int hop = block / 4;
+  const long long nseg = n_max ? (n_max + LD_SEG - 1) / LD_SEG : 1, nhop = n_max ? (n_max + hop - 1) / hop : 1;
+  LdLayout l;
+  l.pps = (LD_SEG - 1) / hop + 2;
+  l.e = 0;
+  l.s = l.e + 4 * nseg;
+  l.pk = l.s + 4 * nseg;
+  l.parts = l.pk + nseg;
+  l.hops = l.parts + nseg * l.pps;
+  l.row = l.hops + nhop;
+  return l;
+}
+
+// the rows of a loudness / gain call: every check, then the descriptors
+static int ld_rows_args(const char* who, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B, long long in_stride,
+                        LdArgs& A, int& n_max, int& len_max) {
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "%s: B=%d outside 1..%d", who, B, RS_MAX_ROWS);
+  SMI_REQUIRE((start_host == nullptr) == (end_host == nullptr), "%s: start_host and end_host must both be given or both be null", who);
+  SMI_REQUIRE(in_stride >= 1, "%s: in_stride=%lld must be positive", who, in_stride);
+  n_max = 0; len_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const int n = n_host[b];
+    SMI_REQUIRE(n >= 0 && n <= RS_MAX_SAMPLES && n <= in_stride, "%s: n[%d]=%d outside 0..min(%d, in_stride=%lld)", who, b, n, RS_MAX_SAMPLES,
+                in_stride);
+    const int st = start_host ? start_host[b] : 0, en = end_host ? end_host[b] : n;
+    SMI_REQUIRE(st >= 0, "%s: start[%d]=%d is negative", who, b, st);
+    SMI_REQUIRE(en >= st, "%s: end[%d]=%d below start[%d]=%d", who, b, en, b, st);
+    SMI_REQUIRE(en <= n, "%s: end[%d]=%d above n[%d]=%d", who, b, en, b, n);
+    A.r[b].n = n; A.r[b].start = st; A.r[b].len = en - st;
+    if (n > n_max) n_max = n;
+    if (en - st > len_max) len_max = en - st;
+  }
+  return SMI_OK;
+}
+
+extern "C" {
+
+long long smi_loud_work_len(long long n_max, int block, int B) {
+  if (n_max < 0 || n_max > RS_MAX_SAMPLES || block < 4 || block > RS_MAX_SAMPLES || (block & 3) || B < 1 || B > RS_MAX_ROWS) return -1;
+  return ld_layout(n_max, block).row * B;
+}
+
+int smi_loud_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                  const double* coef_host, int block, const double* target_host, double max_gain_db, double ceiling, double* work_dev,
+                  long long work_len, double* stats_dev, void* stream) {
+  SMI_REQUIRE(in_dev && n_host && coef_host && target_host && work_dev && stats_dev, "smi_loud_rows: null argument");
+  SMI_REQUIRE(block >= 4 && block <= RS_MAX_SAMPLES && !(block & 3), "smi_loud_rows: block=%d must be a multiple of 4 in 4..%d", block,
+              RS_MAX_SAMPLES);
+  for (int i = 0; i < 10; ++i)
+    SMI_REQUIRE(std::isfinite(coef_host[i]), "smi_loud_rows: coef[%d]=%g is not finite", i, coef_host[i]);
+  SMI_REQUIRE(std::isfinite(max_gain_db) && max_gain_db >= 0.0, "smi_loud_rows: max_gain_db=%g must be finite and >= 0", max_gain_db);
+  SMI_REQUIRE(std::isfinite(ceiling) && ceiling > 0.0, "smi_loud_rows: ceiling=%g must be finite and > 0", ceiling);
+  LdArgs A;
+  int n_max = 0, len_max = 0;
+  const int rc = ld_rows_args("smi_loud_rows", n_host, start_host, end_host, B, in_stride, A, n_max, len_max);
+  if (rc) return rc;
+  LdTargets T;
+  for (int b = 0; b < B; ++b) {
+    SMI_REQUIRE(!std::isinf(target_host[b]), "smi_loud_rows: target[%d]=%g must be finite, or NaN to measure only", b, target_host[b]);
+    T.t[b] = target_host[b];
+  }
+  const long long need = smi_loud_work_len(n_max, block, B);
+  SMI_REQUIRE(work_len >= need, "smi_loud_rows: work_len=%lld below %lld (smi_loud_work_len)", work_len, need);
+  const LdLayout lay = ld_layout(n_max, block);
+  LdCoef c;
+  for (int st = 0; st < 2; ++st) {
+    for (int i = 0; i < 3; ++i) c.b[st][i] = coef_host[5 * st + i];
+    c.a1[st] = coef_host[5 * st + 3];
+    c.a2[st] = coef_host[5 * st + 4];
+  }
+  ld_transition(c);
+  const double abs_gate = pow(10.0, (-70.0 + 0.691) / 10.0);
+  const int tiles = len_max ? (len_max + LD_TILE - 1) / LD_TILE : 1;
+  const size_t lds = (size_t)LD_LANES * LD_PITCH * sizeof(float);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_loud_seg, dim3(tiles, B), dim3(LD_LANES), lds, s, A, c, in_dev, in_stride, work_dev, lay);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loud_carry, dim3(B), dim3(64), 0, s, A, c, work_dev, lay);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loud_energy, dim3(tiles, B), dim3(LD_LANES), lds, s, A, c, block / 4, in_dev, in_stride, work_dev, lay);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loud_gate, dim3(B), dim3(LD_GATE), 0, s, A, T, block, abs_gate, max_gain_db, ceiling, work_dev, lay, stats_dev);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+int smi_gain_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                  const double* stats_dev, float* out_dev, long long out_stride, void* stream) {
+  SMI_REQUIRE(in_dev && n_host && stats_dev && out_dev, "smi_gain_rows: null argument");
+  LdArgs A;
+  int n_max = 0, len_max = 0;
+  const int rc = ld_rows_args("smi_gain_rows", n_host, start_host, end_host, B, in_stride, A, n_max, len_max);
+  if (rc) return rc;
+  SMI_REQUIRE(out_stride >= 1 && out_stride >= n_max && out_stride <= RS_MAX_SAMPLES, "smi_gain_rows: out_stride=%lld outside max(1, the longest row %d)..%d",
+              out_stride, n_max, RS_MAX_SAMPLES);
+  if (!(out_dev == in_dev && out_stride == in_stride)) {   // in place, row on row, or apart
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + ((size_t)(B - 1) * in_stride + n_max) * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_gain_rows: out_dev overlaps in_dev (only out_dev == in_dev with equal strides is allowed)");
+  }
+  const int tiles = (int)((out_stride + GN_TILE - 1) / GN_TILE);
+  hipLaunchKernelGGL(k_gain_rows, dim3(tiles, B), dim3(RS_BLOCK), 0, (hipStream_t)stream, A, stats_dev, in_dev, in_stride, out_dev, out_stride);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

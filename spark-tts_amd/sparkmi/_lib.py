@@ -255,6 +255,10 @@ SYMBOLS = {
     "smi_concat_layout": (C.c_longlong, [_P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_longlong)]),
     "smi_concat_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _I, _VP, C.c_longlong,
                              _P(C.c_longlong), _P(C.c_longlong), _VP]),
+    "smi_loud_work_len": (C.c_longlong, [C.c_longlong, _I, _I]),
+    "smi_loud_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_double), _I, _P(C.c_double),
+                           C.c_double, C.c_double, _VP, C.c_longlong, _VP, _VP]),
+    "smi_gain_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, _VP, C.c_longlong, _VP]),
 }
 
 # include/sparkmi_debug.h: exported by libsparkmi_diag.so only

@@ -11,6 +11,10 @@ cross-faded and resampled with the state kept across chunk edges on the device.
 
 ``DeviceAudio.trim_rows`` / ``concat_rows`` (``smi_trim_rows``, ``smi_concat_rows``) are the audio edge of long-form synthesis:
 the speech bounds of vocoded rows, and the trimmed rows as one waveform with pauses and faded edges.
+
+``DeviceAudio.loudness_rows`` / ``gain_rows`` (``smi_loud_rows``, ``smi_gain_rows``) level the output: the programme loudness of
+rows after ITU-R BS.1770 and the gain that brings each to a target under a peak ceiling, measured and applied on the device.
+``k_weighting`` designs the weighting filter's coefficients for a sample rate with numpy alone.
 """
 from __future__ import annotations
 
@@ -55,6 +59,56 @@ def resample_taps(up: int, down: int) -> np.ndarray:
     h = cutoff * np.sinc(cutoff * m) * np.kaiser(2 * half + 1, KAISER_BETA)
     h /= np.sum(h)
     return h * up
+
+
+# The analog prototypes of BS.1770's two weighting stages, as they are commonly restated from the standard's 48 kHz table: a
+# high shelf (1681.97 Hz, +3.9998 dB, Q 0.70718) and a high pass (38.135 Hz, Q 0.50033), to the digits that reproduce the table.
+K_SHELF = (1681.974450955533, 3.999843853973347, 0.7071752369554196)
+K_SHELF_VB = 0.4996667741545416      # the band gain is the shelf gain to this power
+K_HIGHPASS = (38.13547087602444, 0.5003270373238773)
+PEAK_CEILING = 10 ** (-1 / 20)      # -1 dBFS, a sample peak
+
+
+def k_weighting(sr: int) -> np.ndarray:
+    """float64 [10]: ``b0 b1 b2 a1 a2`` of the high shelf, then of the high pass, of BS.1770's K-weighting at ``sr`` Hz -- the
+    bilinear transform of the analog prototypes with pre-warping (K = tan(pi f0 / sr)).  At 48 kHz this is the standard's own
+    table; ``smi_loud_rows`` takes the coefficients as data."""
+    sr = int(sr)
+    if sr < 1:
+        raise ValueError(f"sample rate must be positive, not {sr}")
+    f0, gain_db, q = K_SHELF
+    if 2 * f0 >= sr:
+        raise ValueError(f"sample rate {sr} is below twice the shelf's corner ({f0:.0f} Hz)")
+    k = math.tan(math.pi * f0 / sr)
+    vh = 10.0 ** (gain_db / 20.0)
+    vb = vh ** K_SHELF_VB
+    a0 = 1.0 + k / q + k * k
+    shelf = [(vh + vb * k / q + k * k) / a0, 2.0 * (k * k - vh) / a0, (vh - vb * k / q + k * k) / a0,
+             2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0]
+    f0, q = K_HIGHPASS
+    k = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + k / q + k * k
+    return np.array(shelf + [1.0, -2.0, 1.0, 2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0], dtype=np.float64)
+
+
+def loudness_block(sr: int) -> int:
+    """the sample count of a 400 ms block at ``sr`` Hz, as four whole hops: ``4 * round(0.1 * sr)``"""
+    return 4 * int(round(0.1 * int(sr)))
+
+
+def check_loudness(loudness, peak_ceiling, max_gain_db) -> None:
+    """the three loudness arguments of the ``SparkTTS`` calls, checked before anything reaches the device"""
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, not {v!r}")
+    if loudness is not None:
+        number("loudness", loudness)
+    number("peak_ceiling", peak_ceiling)
+    number("max_gain_db", max_gain_db)
+    if not peak_ceiling > 0:
+        raise ValueError(f"peak_ceiling must be > 0, not {peak_ceiling!r}")
+    if max_gain_db < 0:
+        raise ValueError(f"max_gain_db must be >= 0, not {max_gain_db!r}")
 
 
 class DeviceAudio:
@@ -222,6 +276,63 @@ class DeviceAudio:
                                                   C.c_void_p(out.data_ptr()), out.numel(), None, C.byref(total), self._stream()),
                         "smi_concat_rows")
         return out, int(total.value)
+
+    def _spans(self, spans, B: int):
+        if spans is None:
+            return None, None
+        if len(spans) != B:
+            raise ValueError("one (start, end) per row")
+        return (C.c_int32 * B)(*[int(s[0]) for s in spans]), (C.c_int32 * B)(*[int(s[1]) for s in spans])
+
+    def loudness_rows(self, x, n: Sequence[int], spans: Optional[Sequence[Tuple[int, int]]] = None,
+                      targets: Optional[Sequence[Optional[float]]] = None, max_gain_db: float = 20.0, ceiling: float = PEAK_CEILING,
+                      sr: int = 16000, block: Optional[int] = None, coef: Optional[np.ndarray] = None):
+        """The programme loudness (BS.1770; include/sparkmi.h, smi_loud_rows) of rows and the gain that brings each to its target.
+        ``x``: [B][stride] float32 on the device, row b valid for ``n[b]``; ``spans``: (start, end) per row, None: the whole
+        rows; ``targets``: LUFS per row, None (the row, or all of them): measure only, gain 1.  ``sr`` gives the weighting
+        (``k_weighting``) and the block (``loudness_block``); ``coef`` / ``block`` replace them.  Returns stats [B][4] float64 on
+        the device: (loudness, peak, gain, limit -- 0 none, 1 ``max_gain_db``, 2 ``ceiling``).  Four launches, nothing waits and
+        nothing is copied.  The scratch is the object's own and only grows."""
+        import torch
+        B = self._rows(x, n, "loudness_rows")
+        st, en = self._spans(spans, B)
+        block = loudness_block(sr) if block is None else int(block)
+        coef = np.ascontiguousarray(k_weighting(sr) if coef is None else coef, dtype=np.float64)
+        if coef.shape != (10,):
+            raise ValueError("coef holds b0 b1 b2 a1 a2 of two stages: 10 values")
+        tg = [None] * B if targets is None else list(targets)
+        if len(tg) != B:
+            raise ValueError("one target per row")
+        tg = (C.c_double * B)(*[math.nan if t is None else float(t) for t in tg])
+        need = self._lib.smi_loud_work_len(max(0, max(int(v) for v in n)) if B else 0, block, max(1, min(B, MAX_ROWS)))
+        work = getattr(self, "_loud_work", None)
+        if work is None or work.numel() < need:
+            work = self._loud_work = torch.empty((max(1, int(need)),), dtype=torch.float64, device=self.device)
+        stats = torch.empty((max(1, B), 4), dtype=torch.float64, device=self.device)
+        self._lib.check(self._lib.smi_loud_rows(C.c_void_p(x.data_ptr()), x.shape[1], (C.c_int32 * B)(*[int(v) for v in n]), st, en, B,
+                                                coef.ctypes.data_as(C.POINTER(C.c_double)), block, tg, float(max_gain_db), float(ceiling),
+                                                C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(stats.data_ptr()), self._stream()),
+                        "smi_loud_rows")
+        return stats
+
+    def gain_rows(self, x, n: Sequence[int], stats, spans: Optional[Sequence[Tuple[int, int]]] = None, out=None):
+        """Rows times their gain (include/sparkmi.h, smi_gain_rows): row b's span becomes fl32(fl64(x) * stats[b, 2]), the gain read
+        on the device; the rest of the row is copied and the row is zeros from ``n[b]`` to the stride.  ``out``: None: a new
+        [B][stride] tensor; ``x`` itself: in place; another contiguous [B][out_stride] float32 tensor on the device that does not
+        overlap ``x``.  Returns ``out``.  One launch, nothing waits."""
+        import torch
+        B = self._rows(x, n, "gain_rows")
+        st, en = self._spans(spans, B)
+        if stats.dim() != 2 or stats.shape[0] < B or stats.shape[1] != 4 or stats.dtype != torch.float64 or not stats.is_contiguous() or not stats.is_cuda:
+            raise ValueError("gain_rows takes the [B][4] float64 stats of loudness_rows, on the device")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.dim() != 2 or out.shape[0] != B or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("gain_rows: out must be a contiguous [B][out_stride] float32 tensor on the device")
+        self._lib.check(self._lib.smi_gain_rows(C.c_void_p(x.data_ptr()), x.shape[1], (C.c_int32 * B)(*[int(v) for v in n]), st, en, B,
+                                                C.c_void_p(stats.data_ptr()), C.c_void_p(out.data_ptr()), out.shape[1], self._stream()),
+                        "smi_gain_rows")
+        return out
 
 
 class StreamJoiner:

@@ -10,7 +10,8 @@ kernels: ``self.model.generate`` (``SparkLLM``) and ``self.audio_tokenizer.detok
 batching) and ``serve_stream`` (both at once: chunked audio for every live request of an in-flight batch); the two streaming
 calls take ``joined=True`` for contiguous, playable pieces at any output rate (the chunks joined on the device);
 ``inference_long`` / ``inference_long_stream`` (text of any length: sentences as the rows of one in-flight session, their
-waveforms trimmed and joined on the device).
+waveforms trimmed and joined on the device); ``loudness`` / ``peak_ceiling`` / ``max_gain_db`` on every call that returns whole
+utterances (the output at a programme loudness after BS.1770, measured and scaled on the device).
 """
 from __future__ import annotations
 
@@ -22,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .audio import PEAK_CEILING, check_loudness
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
 from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, NGRAM_KEY, PENALTY_KEYS, SAMPLING_KEYS, SEQ_KEYS, SparkLLM,
@@ -39,6 +41,11 @@ SPEECH_ONLY_KEY = "speech_tokens_only"
 # request key: a bias on the end token -- sugar for one length-1 ``sequence_bias`` entry per eos id of the session (-inf: the
 # request runs to its token budget; a large positive value: it ends at the first token min_new_tokens lets it)
 EOS_BIAS_KEY = "eos_bias"
+
+
+# request key: the programme loudness (LUFS) the request's waveform is brought to; it overrides the call's ``loudness``
+LOUDNESS_KEY = "loudness"
+LIMITED = (None, "max_gain", "ceiling")   # what bounded a row's gain (include/sparkmi.h, smi_loud_rows: limit 0 / 1 / 2)
 
 
 def _stream_pacing(max_batch: int, max_open=None, max_ahead=None, resume_ahead=None):
@@ -251,9 +258,11 @@ class SparkTTS:
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
                   min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False,
                   num_return_sequences: int = 1, allowed_token_ids: Optional[Sequence[int]] = None,
-                  speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0, output_sample_rate: Optional[int] = None):
+                  speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0, output_sample_rate: Optional[int] = None,
+                  loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate`` (or at ``output_sample_rate``,
-        as in ``inference_batch``).  The penalties
+        as in ``inference_batch``; ``loudness`` / ``peak_ceiling`` / ``max_gain_db``: the output's programme loudness, as
+        there).  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
         penalty.  ``return_log_probs=True``: (waveform, info) with info = {``token_ids``: the generated ids,
@@ -280,7 +289,8 @@ class SparkTTS:
                                           **({NGRAM_KEY: n_gram} if n_gram > 0 else {}))],
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                                     max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs,
-                                    output_sample_rate=output_sample_rate)[0]
+                                    output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
+                                    max_gain_db=max_gain_db)[0]
 
     def _output_ratio(self, output_sample_rate: Optional[int]) -> Optional[Tuple[int, int]]:
         """(up, down) from the model's rate to ``output_sample_rate``; None when the vocoder's rows go out as they are"""
@@ -327,11 +337,47 @@ class SparkTTS:
             self._audio = DeviceAudio(self.device)
         return self._audio
 
+    @staticmethod
+    def _loudness_targets(requests: Sequence[dict], loudness, peak_ceiling, max_gain_db) -> List[Optional[float]]:
+        """every request's loudness target (its own ``loudness`` key, else the call's; None: left as vocoded), all checked"""
+        check_loudness(loudness, peak_ceiling, max_gain_db)
+        out = []
+        for i, r in enumerate(requests):
+            t = r.get(LOUDNESS_KEY, loudness)
+            try:
+                check_loudness(t, peak_ceiling, max_gain_db)
+            except ValueError as e:
+                raise ValueError(f"request {i}: {e}") from None
+            out.append(None if t is None else float(t))
+        return out
+
+    def _normalize_rows(self, wav, n: Sequence[int], targets: Sequence[Optional[float]], peak_ceiling: float, max_gain_db: float,
+                        spans=None):
+        """Vocoded rows to their loudness targets, in place and on the device (``audio.DeviceAudio.loudness_rows`` /
+        ``gain_rows``: five launches for all rows, nothing waits).  Returns the rows' stats [B][4] on the device, or None where
+        no row has a target -- then nothing is launched."""
+        if all(t is None for t in targets):
+            return None
+        audio = self._device_audio()
+        stats = audio.loudness_rows(wav, n, spans=spans, targets=targets, max_gain_db=max_gain_db, ceiling=peak_ceiling, sr=self.sample_rate)
+        audio.gain_rows(wav, n, stats, spans=spans, out=wav)
+        return stats
+
+    @staticmethod
+    def _loudness_info(stats, targets: Sequence[Optional[float]]) -> List[Optional[dict]]:
+        """one small copy: per row with a target {``loudness`` (LUFS before the gain), ``gain``, ``limited`` (None, "max_gain" or
+        "ceiling")}, None for a row without one"""
+        if stats is None:
+            return [None] * len(targets)
+        host = stats.cpu().tolist()
+        return [None if t is None else dict(loudness=row[0], gain=row[2], limited=LIMITED[int(row[3])]) for t, row in zip(targets, host)]
+
     @torch.no_grad()
     def inference_batch(self, requests: Sequence[dict], temperature: float = 0.8, top_k: float = 50,
                         top_p: float = 0.95, *, do_sample: bool = True, max_new_tokens: int = 3000,
                         seed: Optional[int] = None, return_log_probs: bool = False, prompt_encode: str = "streams",
-                        prompt_audio: str = "host", output_sample_rate: Optional[int] = None) -> List:
+                        prompt_audio: str = "host", output_sample_rate: Optional[int] = None,
+                        loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0) -> List:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
@@ -355,7 +401,14 @@ class SparkTTS:
         fp32, so its prompt ids may differ from the host path's at near-ties.
         ``output_sample_rate``: None or the model's rate: the vocoder's rows as they are.  Another rate (24000, 44100, 48000,
         8000, ...): every row is resampled on the device (``sparkmi/audio.py``, ``resample_poly``'s arithmetic in fp32) before
-        the copy to the host; row b then has ``audio.out_len`` of its own length."""
+        the copy to the host; row b then has ``audio.out_len`` of its own length.
+        ``loudness`` (LUFS, e.g. -23 or -16; None: the rows as vocoded, no extra launch) or a request's own ``loudness`` key,
+        which overrides it: the whole vocoded row is brought to that programme loudness (ITU-R BS.1770; include/sparkmi.h,
+        smi_loud_rows) on the device, after vocoding and before the resampling -- by a gain of at most ``max_gain_db`` that
+        keeps the sample peak at or below ``peak_ceiling`` (a sample peak, not a true peak); a silent row is left as it is.
+        All rows go through the same two device calls.  ``self.last_loudness`` then holds, per request (per take where it
+        has takes), None or {``loudness``: measured before the gain, ``gain``, ``limited``: None / "max_gain" / "ceiling"}."""
+        targets = self._loudness_targets(requests, loudness, peak_ceiling, max_gain_db)
         if prompt_encode not in ("streams", "rows"):
             raise ValueError(f"prompt_encode must be 'streams' or 'rows', not {prompt_encode!r}")
         if prompt_audio not in ("host", "device"):
@@ -447,16 +500,26 @@ class SparkTTS:
         hop = self.audio_tokenizer.model.hop
         n_wav = [n * hop for n in lens]
         wav = wav.squeeze(1)
+        row_targets = [targets[b] for b in owner]
+        stats = None
+        if any(t is not None for t in row_targets):
+            wav = wav.contiguous()
+            stats = self._normalize_rows(wav, n_wav, row_targets, peak_ceiling, max_gain_db)
         if out_ratio is not None:   # rows at the caller's rate, still on the device
             wav, n_wav = self._device_audio().resample_rows(wav, n_wav, [out_ratio[0]] * len(lens), [out_ratio[1]] * len(lens))
         wav = wav.cpu().numpy()
+        loud = self._loudness_info(stats, row_targets)
         out = [wav[b, : n_wav[b]].copy() for b in range(len(sems))]
         out = [(w, infos[b]) if infos[b] is not None else w for b, w in enumerate(out)]
         if n_takes is None:
+            self.last_loudness = loud
             return out
         res: List = [[] for _ in requests]
+        per: List = [[] for _ in requests]
         for i, b in enumerate(owner):
             res[b].append(out[i])
+            per[b].append(loud[i])
+        self.last_loudness = [per[b] if FORK_KEY in r else per[b][0] for b, r in enumerate(requests)]
         return [res[b] if FORK_KEY in r else res[b][0] for b, r in enumerate(requests)]
 
     @torch.no_grad()
@@ -483,7 +546,10 @@ class SparkTTS:
         all.  ``output_sample_rate`` is then accepted (None or ``sample_rate``: the model's rate): the pieces'
         concatenation is, bit for bit, what ``inference_batch(output_sample_rate=...)``'s resampler gives for that joined
         waveform, the filter's state being kept across the chunk edges; a piece that would be empty is not yielded.
-        Refused (ValueError, before any device call) if the first chunk is shorter than two overlaps."""
+        Refused (ValueError, before any device call) if the first chunk is shorter than two overlaps.
+
+        There is no ``loudness`` here: the integrated loudness of BS.1770 is a property of the whole utterance, which a
+        chunk that must leave before the utterance ends cannot know (``inference`` / ``inference_long_stream`` take it)."""
         if not joined:
             self._no_stream_rate(output_sample_rate, "inference_stream")
         joiner = self._stream_joiner("inference_stream", output_sample_rate, 1, audio_chunk_duration, max_audio_chunk_duration,
@@ -579,7 +645,8 @@ class SparkTTS:
 
     @torch.no_grad()
     def serve(self, requests, temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *, do_sample: bool = True,
-              max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False):
+              max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False,
+              loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0):
         """In-flight batching front end (the functional analogue of the reference's Triton deployment,
         runtime/triton_trtllm/run.sh:50-65): ``requests`` is an iterable of the dicts ``inference_batch`` takes;
         yields ``(index, waveform)`` as each utterance finishes.  Up to ``max_batch`` utterances are live; a new
@@ -590,14 +657,21 @@ class SparkTTS:
         ``inference`` (up to and including the first eos id, like the waveform's tokens).  A request's
         ``num_return_sequences`` key (an int >= 1, at most ``max_batch``): that many takes of it, admitted together once
         that many slots are free, its prompt prefilled once; it yields ``(index, [one result per take])`` when all of its
-        takes have finished, each take a waveform or a (waveform, info) pair, vocoded together."""
+        takes have finished, each take a waveform or a (waveform, info) pair, vocoded together.
+        ``loudness`` / ``peak_ceiling`` / ``max_gain_db`` and a request's own ``loudness`` key as in ``inference_batch``: each
+        waveform is brought to its target on the device before its copy; ``self.last_loudness[index]`` holds what was measured
+        (a list for a request with takes) once the request has been yielded."""
         forks: Dict[int, int] = {}   # request index -> takes, for the requests that carry num_return_sequences
+        goals: Dict[int, Optional[float]] = {}   # request index -> loudness target
+        check_loudness(loudness, peak_ceiling, max_gain_db)
+        self.last_loudness = {}
 
         def checked(reqs):   # each request's takes, checked before the request reaches the device
             for i, r in enumerate(reqs):
                 if FORK_KEY in r:
                     forks[i] = _take_counts([r], self._max_batch)[0]
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
+                goals[i] = self._loudness_targets([r], loudness, peak_ceiling, max_gain_db)[0]
                 yield r
 
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
@@ -630,9 +704,19 @@ class SparkTTS:
                 rows.append(self._speech_row(i, toks, globals_[i]))
                 infos.append(None if lps is None else _lp_info(toks, lps[: len(toks)]))
             wav, lens = self._vocode_rows(rows)
+            wav = normalized(i, wav, lens, True)
             wav = wav.cpu().numpy()
             return [(wav[b, : lens[b] * hop].copy(), infos[b]) if infos[b] is not None else wav[b, : lens[b] * hop].copy()
                     for b in range(len(rows))]
+
+        def normalized(i, wav, lens, takes):   # the vocoded rows of request i at its loudness target, still on the device
+            if goals[i] is None:
+                return wav
+            wav = wav.contiguous()
+            stats = self._normalize_rows(wav, [f * hop for f in lens], [goals[i]] * len(lens), peak_ceiling, max_gain_db)
+            got = self._loudness_info(stats, [goals[i]] * len(lens))
+            self.last_loudness[i] = got if takes else got[0]
+            return wav
 
         for i, toks in self.model.serve(llm_requests(), max_live=self._max_batch, decode_stride=decode_stride,
                                         return_log_probs=return_log_probs):
@@ -644,7 +728,7 @@ class SparkTTS:
                 toks, lps = toks
             toks = self._cut_eos(toks)
             wav, lens = self._vocode_rows([self._speech_row(i, toks, globals_[i])])
-            w = wav[0, : lens[0] * hop].cpu().numpy().copy()
+            w = normalized(i, wav, lens, False)[0, : lens[0] * hop].cpu().numpy().copy()
             if lps is None:
                 yield i, w
             else:
@@ -699,7 +783,10 @@ class SparkTTS:
         chunk at once, since a request's last chunk is pushed in the poll that retires it -- so the slots cannot run out.  The
         ``Pacer`` counts frames yielded as without it.  (The joiner's handle stays on ``self`` for the next call with the same
         sizes and rate; its slots are all freed when a call begins, so nothing of a request outlives its call.)  Refused
-        (ValueError, before any device call) if the first chunk is shorter than two overlaps."""
+        (ValueError, before any device call) if the first chunk is shorter than two overlaps.
+
+        There is no ``loudness`` here, as in ``inference_stream``: integrated loudness needs the whole utterance (``serve``
+        takes it)."""
         if not joined:
             self._no_stream_rate(output_sample_rate, "serve_stream")
 
@@ -877,11 +964,13 @@ class SparkTTS:
     # ------------------------------------------------------------------ long text: sentences as rows, trimmed and joined on the device
     def _long_pieces(self, text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
                      max_new_tokens, seed, prompt_tokens, keys: dict, max_width, min_width, pause, trim, trim_threshold, fade, eager: bool,
-                     info: dict):
+                     info: dict, loudness=None, peak_ceiling=PEAK_CEILING, max_gain_db=20.0):
         """The engine of ``inference_long`` and ``inference_long_stream``: yields (first sentence, joined [total] float32 on the
         device, [(offset in it, gap, length) per sentence]) for runs of consecutive sentences in text order -- with ``eager``
         as soon as the next sentence due and those behind it are done, else in runs of ``max_batch`` once all are done.  Fills
-        ``info``.  Everything is checked before anything reaches the device."""
+        ``info``.  With ``loudness``, every sentence's trimmed piece is brought to that programme loudness in place before the
+        assembly.  Everything is checked before anything reaches the device."""
+        check_loudness(loudness, peak_ceiling, max_gain_db)
         from .longform import control_prefix, control_prompt_ids, ready_run, sentence_seeds, split_text, trim_params
         sentences = split_text(text, max_width, min_width)
         for name, v in (("pause", pause), ("fade", fade), ("trim_threshold", trim_threshold)):
@@ -908,6 +997,8 @@ class SparkTTS:
         prefix: List[int] = []
         budgets: Dict[int, int] = {}
         info.update(sentences=sentences, token_ids=[None] * n_sent, bounds=[None] * n_sent, offsets=[None] * n_sent, truncated=[], silent=[])
+        if loudness is not None:
+            info.update(loudness=[None] * n_sent, gain=[None] * n_sent, limited=[None] * n_sent)
         audio = self._device_audio()
         tokens: Dict[int, List[int]] = {}
         state = {"due": 0, "total": 0, "spoken": False}
@@ -934,9 +1025,15 @@ class SparkTTS:
                 gaps.append(gap if b > a and state["spoken"] else 0)
                 state["spoken"] = state["spoken"] or b > a
             offs, total = audio.concat_layout(bounds, gaps)
+            stats = None
+            if loudness is not None:   # each piece to the target on its own trimmed span, in place, before the assembly
+                stats = self._normalize_rows(wav, n, [float(loudness)] * len(ks), peak_ceiling, max_gain_db, spans=bounds)
             out = None
             if total:
                 out, _ = audio.concat_rows(wav, bounds, gaps, fade_n, n=n)
+            if stats is not None:      # (one small copy, like the bounds', behind everything that was enqueued)
+                for k, d in zip(ks, self._loudness_info(stats, [loudness] * len(ks))):
+                    info["loudness"][k], info["gain"][k], info["limited"][k] = d["loudness"], d["gain"], d["limited"]
             for k, (a, b), o, g in zip(ks, bounds, offs, gaps):
                 info["bounds"][k], info["offsets"][k] = (a, b), state["total"] + o
                 if b == a:
@@ -992,7 +1089,8 @@ class SparkTTS:
                        speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0,
                        max_width: int = 300, min_width: int = 20, pause: float = 0.25, trim: bool = True,
                        trim_threshold: float = 0.01, fade: float = 0.005, output_sample_rate: Optional[int] = None,
-                       return_info: bool = False):
+                       return_info: bool = False, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
+                       max_gain_db: float = 20.0):
         """A text of any length -> one float32 waveform: the text is cut into sentences (``longform.split_text``: ``max_width``,
         ``min_width``), the sentences are generated with the same voice as the requests of one in-flight session (up to
         ``max_batch`` live; ``max_new_tokens`` is per sentence), vocoded in ragged calls, cut at their speech bounds
@@ -1012,14 +1110,23 @@ class SparkTTS:
         copy.  ``return_info=True``: (waveform, info) with ``sentences``, ``token_ids`` (per sentence, up to and including its
         eos), ``bounds`` (per sentence, in samples of its untrimmed row), ``offsets`` (of the pieces in the joined waveform at the
         model's rate), ``truncated`` (the sentences that used their whole budget -- the room left in ``max_positions`` and
-        ``max_frames`` bound it -- without an eos) and ``silent`` (those with an empty piece, which also get no pause)."""
+        ``max_frames`` bound it -- without an eos) and ``silent`` (those with an empty piece, which also get no pause).
+
+        ``loudness`` (LUFS; None: the pieces as vocoded, no extra launch): every sentence is an independent generation and
+        comes out at its own level, so each trimmed piece is brought to that programme loudness on its own (ITU-R BS.1770;
+        include/sparkmi.h, smi_loud_rows / smi_gain_rows: trim, measure over the piece, scale in place, assemble) by a gain of at
+        most ``max_gain_db`` that keeps its sample peak at or below ``peak_ceiling``; a silent sentence is untouched.  ``info``
+        then also holds ``loudness`` (measured before the gain), ``gain`` and ``limited`` (None, "max_gain" or "ceiling") per
+        sentence."""
+        check_loudness(loudness, peak_ceiling, max_gain_db)
         out_ratio = self._output_ratio(output_sample_rate)
         keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
                                min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
         info: dict = {}
         parts = [out for _, out, _ in self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p,
                                                         do_sample, max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim,
-                                                        trim_threshold, fade, False, info) if out is not None]
+                                                        trim_threshold, fade, False, info, loudness, peak_ceiling, max_gain_db)
+                 if out is not None]
         if not parts:
             wav = np.zeros(0, dtype=np.float32)
         else:
@@ -1041,18 +1148,23 @@ class SparkTTS:
                               speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0,
                               max_width: int = 300, min_width: int = 20, pause: float = 0.25, trim: bool = True,
                               trim_threshold: float = 0.01, fade: float = 0.005,
-                              output_sample_rate: Optional[int] = None) -> Iterator[np.ndarray]:
+                              output_sample_rate: Optional[int] = None, loudness: Optional[float] = None,
+                              peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0) -> Iterator[np.ndarray]:
         """``inference_long`` piece by piece: yields contiguous float32 pieces in text order, sentence k's pause + trimmed and faded
         piece as soon as k and every sentence before it are done (an empty piece is not yielded).  At the model's rate the
         pieces' concatenation is ``inference_long``'s waveform bit for bit: a piece's bits are its own (include/sparkmi.h,
         smi_concat_rows).  With ``output_sample_rate`` the pieces go through a ``StreamJoiner`` with ``overlap = 0`` -- plain
         concatenation with the resampler's state kept across the pieces -- and the concatenation of what is yielded (the last
-        piece is the resampler's flush) is bit for bit ``inference_long(..., output_sample_rate=...)``."""
+        piece is the resampler's flush) is bit for bit ``inference_long(..., output_sample_rate=...)``.  ``loudness`` /
+        ``peak_ceiling`` / ``max_gain_db`` as in ``inference_long``: a sentence's loudness is measured over its own piece, so
+        the pieces stay bit for bit those of ``inference_long``."""
+        check_loudness(loudness, peak_ceiling, max_gain_db)
         out_ratio = self._output_ratio(output_sample_rate)
         keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
                                min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
         pieces = self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
-                                   max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim, trim_threshold, fade, True, {})
+                                   max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim, trim_threshold, fade, True, {},
+                                   loudness, peak_ceiling, max_gain_db)
         joiner = None
         for _, out, spans in pieces:
             if out is None:
