@@ -142,7 +142,12 @@ int smi_llm_prefill(smi_llm* h, const int64_t* ids_host, const int32_t* lens_hos
  * on ties, like torch.argmax).  do_sample = 1: the reference's default at cli/SparkTTS.py:197-204 --
  * temperature, then top-k (1..256), then nucleus top-p, one multinomial draw per step from a
  * Philox stream keyed by (seed; the sequence's admission number, its own token index): reproducible per
- * seed whatever else is in the batch, statistically (not bitwise) equivalent to transformers' sampler. */
+ * seed whatever else is in the batch, statistically (not bitwise) equivalent to transformers' sampler.
+ * Ids that tie with the k-th largest logit all stay, as in TopKLogitsWarper (-0.0 ties with +0.0), up to the 256 ranks the
+ * sampler sorts: of more survivors, the 256 first in (logit descending, id ascending) order are the ones drawn from.  A -inf
+ * logit is never drawn; a row with no finite logit gives token 0.  The draw itself is exact integer arithmetic and an exactly
+ * sorted inverse CDF: tests/sample_ref.py names the token of every draw and tests/test_sample_draws_gpu.py holds the kernels
+ * to it. */
 int smi_llm_set_sampling(smi_llm* h, int do_sample, float temperature, int top_k, float top_p, uint64_t seed);
 /* Run n_steps more decode steps for all B sequences (finished ones keep stepping; their
  * tokens are not counted).  Asynchronous. */

@@ -13,8 +13,9 @@ Pinning: ``tests/golden/gen_golden_sampling.py`` runs transformers' own three wa
 logits rows (the tiny model's, a 166 000-entry row, a row with a tie at the k-th value and a row whose nucleus
 cut falls next to a cumulative probability) and stores the surviving ids and probabilities in
 ``tests/golden/sampling.npz``; ``tests/test_oracle_sampling.py`` requires equality.  The draw itself is not
-restated: the product uses its own counter-based stream (Philox keyed per sequence), so the GPU tests compare
-empirical frequencies with these probabilities.
+restated HERE: the product uses its own counter-based stream (Philox keyed per sequence), so the GPU tests that
+use this module compare empirical frequencies with these probabilities.  ``tests/sample_ref.py`` restates the
+stream and the draw, and ``tests/test_sample_draws_gpu.py`` holds the kernels to it token by token.
 """
 from __future__ import annotations
 

@@ -3112,8 +3112,12 @@ struct SampleP {
   float* cand_v; int* cand_i; unsigned int* cand_n;
 };
 
+// Order-preserving key of a float.  -0.0 takes +0.0's key: the bound path compares floats (v >= thr), to which the two zeros
+// are equal, and TopKLogitsWarper (`scores < kth`) keeps both when they tie at the k-th value; a key of its own would put
+// -0.0 below a +0.0 threshold on the radix path alone.  No other float's key changes.
 __device__ __forceinline__ uint32_t sortable(float f) {
-  const uint32_t u = __float_as_uint(f);
+  uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
