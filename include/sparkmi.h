@@ -819,6 +819,51 @@ int smi_loud_rows(const float* in_dev, long long in_stride, const int32_t* n_hos
 int smi_gain_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
                   const double* stats_dev, float* out_dev, long long out_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Tempo: a pitch-preserving time-scale change of rows (WSOLA: overlap-add of frames whose places are found by a waveform
+ * similarity search), on the device.  Free functions like the two sections above: no handle, no state, asynchronous on the
+ * caller's stream, never synchronising, opt-in.  Every argument of every row is checked before anything reaches the device: a
+ * bad one returns SMI_EINVAL, names the argument in smi_last_error and launches nothing.  B <= 64, L <= 2^24.
+ *
+ * A row is scaled over a span x[0 .. L) = row[start .. end) of fp32 samples.  Everything outside the span reads as 0 and is
+ * never fetched from memory.  The tempo is the rational p / q (> 1: faster), 1 <= p, q <= 32767, 1/4 <= p / q <= 4.  The frame
+ * N is even, 16 <= N <= 2048, H = N / 2; the search radius is 0 <= D <= 1024.
+ *
+ * Quantised copy, for decisions only:  qx[i] = clamp(rint(fl64(x[i]) * 32767), -32767, 32767) -- the product is exact in
+ * float64, rint rounds half to even; a NaN sample gives 0, and so does every position outside the span.
+ * Lengths, host integer arithmetic (smi_tempo_layout):  M = ceil(L q / p) output samples in K = floor((M - 1) / H) + 1 frames
+ * (K = 0 when M = 0).  Frame k's nominal place is a_k = floor(k H p / q), in 64-bit integers.
+ * Frame places s_k.  s_0 = 0.  For k >= 1 the natural continuation is t_k = s_{k-1} + H, and s_k = a_k + delta where delta in
+ * [-D, D] minimises the exact distance
+ *     sum over i < N of (qx[t_k + i] - qx[a_k + delta + i])^2
+ * -- every term is below 2^32 and the sum below 2^43, so it is exact in 64-bit integers and its order is free.  Ties go to the
+ * smallest |a_k + delta - t_k|, then to the smaller delta.  Where |t_k - a_k| <= D this rule gives s_k = t_k without a search
+ * (the distance there is 0 and nothing is closer to t_k): the kernel takes that shortcut; it is not a second rule.
+ * Overlap-add.  w[i] = 0.5 - 0.5 cos(2 pi i / N), float64, is a table the caller passes (sparkmi/audio.py: tempo_window; the
+ * device designs no window).  For output sample m, k = m / H (integer division) and j = m - k H:
+ *     k = 0:   out[m] = x[m]
+ *     k >= 1:  out[m] = fl32( fl(fl64(x[s_k + j]) w[j]) + fl(fl64(x[s_{k-1} + j + H]) w[j + H]) )
+ * -- each product and the sum rounded on their own in float64 (no FMA), then one rounding to fp32.
+ * Consequences.  At p = q every s_k = k H and the output is the span bit for bit.  M and K depend on L, p, q and N alone.
+ *
+ * Two launches whatever B.  k_tempo_search, one block a row: the frames in order (t_k hangs on s_{k-1}); a searched frame's
+ * quantised target and candidate samples -- at most 2 N + 2 D int16 -- are staged in LDS, the candidates are spread over the
+ * block's threads, each sums its distance in a 64-bit integer, and the block reduces to the minimum under the tie rule.
+ * k_tempo_ola, grid (tiles of 1024 output samples, rows).  No atomics.  Guarantee: a row's places and samples depend, bit for
+ * bit, on its span and its own p, q, N, D and window alone -- not on B, the row's place, the strides, what lies outside the
+ * span or the grid. */
+/* M, the output length of a span of L samples (0 .. 2^24) at tempo p / q with frame N; K_out (may be null) receives the frame
+ * count.  -1 for a bad argument.  Pure host. */
+long long smi_tempo_layout(long long L, int p, int q, int N, long long* K_out);
+/* in_dev [B][in_stride] f32, row b valid for n_host[b]; 0 <= start_host[b] <= end_host[b] <= n_host[b] (both null: the whole
+ * row); p_host / q_host [B]: every row's own tempo; win_dev [N] float64; pos_dev [B][pos_stride] int32 receives s_k (relative
+ * to the span's start), then zeros to pos_stride (>= the most frames of a row, >= 1); out_dev [B][out_stride] f32 receives the
+ * row's M samples, then zeros to out_stride (>= the longest output, >= 1, <= 2^26), and must not overlap in_dev; m_host [B]
+ * (may be null) receives every M, filled before the launch. */
+int smi_tempo_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                   const int32_t* p_host, const int32_t* q_host, int N, int D, const double* win_dev, int32_t* pos_dev, long long pos_stride,
+                   float* out_dev, long long out_stride, int32_t* m_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

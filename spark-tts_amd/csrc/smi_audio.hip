@@ -20,6 +20,9 @@
 //                gates) and the gain to a target: the serial filter is cut into segments of LD_SEG samples, one lane each, that
 //                run from zero state; one wave per row carries the true states across; a second pass sums y^2.  No atomics.
 //   k_gain_rows                  rows times their gain, read from the device (smi_gain_rows).
+//   k_tempo_search, k_tempo_ola  pitch-preserving time-scale change of rows (smi_tempo_rows; WSOLA): one block per row walks the
+//                frames in order and, where a frame is searched, stages the quantised target and candidate samples in LDS as
+//                int16 and sums exact squared differences in 64-bit integers; the overlap-add is then parallel.  No atomics.
 #include <limits.h>
 
 #include <cmath>
@@ -46,6 +49,11 @@
 #define LD_PITCH (LD_SEG + 1)   // floats between two segments in LDS
 #define LD_GATE 256             // threads of k_loud_gate
 #define GN_TILE 1024            // samples a block of k_gain_rows
+#define TP_BLOCK 512            // threads of k_tempo_search: a candidate each, the usual 2 D + 1 = 481 in one round
+#define TP_TILE 1024            // output samples a block of k_tempo_ola
+#define TP_MAX_N 2048           // the frame
+#define TP_MAX_D 1024           // the search radius
+#define TP_MAX_OUT (1 << 26)    // 4 * RS_MAX_SAMPLES: the longest output row
 
 namespace {
 
@@ -691,6 +699,117 @@ __global__ __launch_bounds__(RS_BLOCK) void k_gain_rows(LdArgs a, const double* 
   }
 }
 
+// ---- time-scale change of rows (smi_tempo_rows)
+struct TpRow {
+  int32_t start, len, p, q, m, frames;   // the span x[start .. start + len); tempo p / q; M output samples in K frames
+};
+struct TpArgs {
+  TpRow r[RS_MAX_ROWS];
+};
+
+// sample i of the span, quantised for the search: clamp(rint(fl64(x) * 32767), +-32767); 0 outside the span and for a NaN.
+// Nothing outside the span is fetched.
+__device__ __forceinline__ int tp_quant(const float* __restrict__ x, long long i, int len) {
+  if (i < 0 || i >= len) return 0;
+  const double v = (double)x[i] * 32767.0;   // exact: 24 x 15 bits
+  if (!(v == v)) return 0;
+  return (int)fmin(fmax(rint(v), -32767.0), 32767.0);
+}
+
+// the smaller of two (distance, tie key) pairs: the key holds |a + delta - t| above delta + D, so it orders ties as the header does
+__device__ __forceinline__ void tp_min(unsigned long long& d, unsigned long long& key, unsigned long long d2, unsigned long long key2) {
+  if (d2 < d || (d2 == d && key2 < key)) { d = d2; key = key2; }
+}
+
+// One block per row; the frames in order, since t_k hangs on s_{k-1}.  A frame whose natural continuation lies within D of its
+// nominal place keeps it (what the search would return: distance 0, nothing closer to t_k).  Any other frame is searched: the
+// block stages qx[t .. t + N) and qx[a - D .. a + D + N) in LDS as int16, thread c < 2 D + 1 (then c + TP_BLOCK, ...) sums
+// (target - candidate)^2 over the N samples in a 64-bit integer -- each term below 2^32, the sum below 2^43: exact, whatever the
+// order -- and the block takes the minimum of (distance, |a + delta - t|, delta): a wave butterfly, then the waves' results from
+// LDS.  Lanes of a wave read the same target samples (a broadcast) and consecutive candidate samples.
+__global__ __launch_bounds__(TP_BLOCK) void k_tempo_search(TpArgs a, int N, int D, const float* __restrict__ in, long long in_stride,
+                                                           int32_t* __restrict__ pos, long long pos_stride) {
+  __shared__ __attribute__((aligned(16))) int16_t tq[TP_MAX_N];
+  __shared__ __attribute__((aligned(16))) int16_t cq[TP_MAX_N + 2 * TP_MAX_D];
+  __shared__ unsigned long long red[2][TP_BLOCK / 64];
+  const TpRow r = a.r[blockIdx.x];
+  const float* x = in + (size_t)blockIdx.x * in_stride + r.start;
+  int32_t* ps = pos + (size_t)blockIdx.x * pos_stride;
+  const int tid = threadIdx.x, H = N / 2, ncand = 2 * D + 1;
+  for (long long k = r.frames + tid; k < pos_stride; k += TP_BLOCK) ps[k] = 0;   // past the row's frames: zeros
+  long long s = 0;
+  for (int k = 0; k < r.frames; ++k) {
+    if (k) {
+      const long long ak = ((long long)k * H * r.p) / r.q;   // k H p < 2^26 * 2^15
+      const long long tk = s + H;
+      const long long off = tk - ak;
+      if (off >= -D && off <= D) s = tk;
+      else {
+        for (int i = tid; i < N; i += TP_BLOCK) tq[i] = (int16_t)tp_quant(x, tk + i, r.len);
+        for (int i = tid; i < N + 2 * D; i += TP_BLOCK) cq[i] = (int16_t)tp_quant(x, ak - D + i, r.len);
+        __syncthreads();
+        unsigned long long best = ~0ull, bkey = ~0ull;
+        for (int c = tid; c < ncand; c += TP_BLOCK) {
+          const int16_t* cw = cq + c;
+          unsigned long long acc = 0;
+          for (int i = 0; i < N; i += 2) {
+            const uint32_t tt = *(const uint32_t*)(tq + i);   // two target samples, the same in every lane
+            const uint32_t d0 = (uint32_t)((int)(int16_t)(tt & 0xFFFFu) - (int)cw[i]);
+            const uint32_t d1 = (uint32_t)(((int)tt >> 16) - (int)cw[i + 1]);
+            acc += (unsigned long long)(d0 * d0) + (unsigned long long)(d1 * d1);   // |d| <= 65534: d^2 < 2^32, as the unsigned product gives it
+          }
+          const long long dist_t = ak + (c - D) - tk;
+          tp_min(best, bkey, acc, ((unsigned long long)(dist_t < 0 ? -dist_t : dist_t) << 32) | (unsigned long long)c);
+        }
+        for (int o = 32; o; o >>= 1) {
+          const unsigned long long d2 = (unsigned long long)__shfl_xor((long long)best, o);
+          const unsigned long long k2 = (unsigned long long)__shfl_xor((long long)bkey, o);
+          tp_min(best, bkey, d2, k2);
+        }
+        if ((tid & 63) == 0) { red[0][tid >> 6] = best; red[1][tid >> 6] = bkey; }
+        __syncthreads();
+        best = red[0][0]; bkey = red[1][0];
+        for (int w = 1; w < TP_BLOCK / 64; ++w) tp_min(best, bkey, red[0][w], red[1][w]);
+        s = ak + ((long long)(bkey & 0xFFFFFFFFull) - D);
+        __syncthreads();   // (red, tq and cq are free for the next searched frame)
+      }
+    }
+    if (tid == 0) ps[k] = (int32_t)s;
+  }
+}
+
+// sample i of the span as float64; 0 outside the span, which is never fetched
+__device__ __forceinline__ double tp_sample(const float* __restrict__ x, long long i, int len) {
+  return i < 0 || i >= len ? 0.0 : (double)x[i];
+}
+
+// grid (tiles of TP_TILE output samples, rows): out[m] = fl32(fl64(x[s_k + j]) w[j] + fl64(x[s_{k-1} + j + H]) w[j + H]), each
+// product and the sum rounded on their own; frame 0 is the span's own first H samples; zeros from M to the stride
+__global__ __launch_bounds__(RS_BLOCK) void k_tempo_ola(TpArgs a, int N, const float* __restrict__ in, long long in_stride,
+                                                        const double* __restrict__ win, const int32_t* __restrict__ pos,
+                                                        long long pos_stride, float* __restrict__ out, long long out_stride) {
+  const TpRow r = a.r[blockIdx.y];
+  const float* x = in + (size_t)blockIdx.y * in_stride + r.start;
+  const int32_t* ps = pos + (size_t)blockIdx.y * pos_stride;
+  float* y = out + (size_t)blockIdx.y * out_stride;
+  const int H = N / 2;
+  const long long m0 = (long long)blockIdx.x * TP_TILE;
+  const long long end = min(out_stride, m0 + TP_TILE);
+  for (long long m = m0 + threadIdx.x; m < end; m += RS_BLOCK) {
+    float v = 0.f;
+    if (m < r.m) {
+      const int k = (int)(m / H), j = (int)(m - (long long)k * H);
+      if (k == 0) v = m < r.len ? x[m] : 0.f;
+      else {
+        const double u0 = tp_sample(x, (long long)ps[k] + j, r.len) * win[j];
+        const double u1 = tp_sample(x, (long long)ps[k - 1] + j + H, r.len) * win[j + H];
+        v = (float)(u0 + u1);
+      }
+    }
+    y[m] = v;
+  }
+}
+
 }  // namespace
 
 struct smi_rs {
@@ -1187,6 +1306,72 @@ int smi_gain_rows(const float* in_dev, long long in_stride, const int32_t* n_hos
   }
   const int tiles = (int)((out_stride + GN_TILE - 1) / GN_TILE);
   hipLaunchKernelGGL(k_gain_rows, dim3(tiles, B), dim3(RS_BLOCK), 0, (hipStream_t)stream, A, stats_dev, in_dev, in_stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// the lengths of a time-scaled span: M = ceil(L q / p) samples in K frames of N / 2; false for a bad argument
+static bool tp_layout(long long L, int p, int q, int N, long long& M, long long& K) {
+  if (L < 0 || L > RS_MAX_SAMPLES || p < 1 || p > 32767 || q < 1 || q > 32767 || p > 4 * q || q > 4 * p) return false;
+  if (N < 16 || N > TP_MAX_N || (N & 1)) return false;
+  M = (L * q + p - 1) / p;
+  K = M ? (M - 1) / (N / 2) + 1 : 0;
+  return true;
+}
+
+extern "C" {
+
+long long smi_tempo_layout(long long L, int p, int q, int N, long long* K_out) {
+  long long M = 0, K = 0;
+  if (!tp_layout(L, p, q, N, M, K)) return -1;
+  if (K_out) *K_out = K;
+  return M;
+}
+
+int smi_tempo_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                   const int32_t* p_host, const int32_t* q_host, int N, int D, const double* win_dev, int32_t* pos_dev, long long pos_stride,
+                   float* out_dev, long long out_stride, int32_t* m_host, void* stream) {
+  SMI_REQUIRE(N >= 16 && N <= TP_MAX_N && !(N & 1), "smi_tempo_rows: N=%d must be even in 16..%d", N, TP_MAX_N);
+  SMI_REQUIRE(D >= 0 && D <= TP_MAX_D, "smi_tempo_rows: D=%d outside 0..%d", D, TP_MAX_D);
+  SMI_REQUIRE(in_dev && n_host && p_host && q_host && win_dev && pos_dev && out_dev, "smi_tempo_rows: null argument");
+  LdArgs S;
+  int n_max = 0, len_max = 0;
+  const int rc = ld_rows_args("smi_tempo_rows", n_host, start_host, end_host, B, in_stride, S, n_max, len_max);
+  if (rc) return rc;
+  TpArgs A;
+  long long m_max = 0, k_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const int p = p_host[b], q = q_host[b];
+    SMI_REQUIRE(p >= 1 && p <= 32767, "smi_tempo_rows: p[%d]=%d outside 1..32767", b, p);
+    SMI_REQUIRE(q >= 1 && q <= 32767, "smi_tempo_rows: q[%d]=%d outside 1..32767", b, q);
+    SMI_REQUIRE(p <= 4 * q && q <= 4 * p, "smi_tempo_rows: p[%d]/q[%d] = %d/%d outside 1/4..4", b, b, p, q);
+    long long M = 0, K = 0;
+    SMI_REQUIRE(tp_layout(S.r[b].len, p, q, N, M, K), "smi_tempo_rows: row %d has no layout (smi_tempo_layout)", b);
+    TpRow& r = A.r[b];
+    r.start = S.r[b].start; r.len = S.r[b].len; r.p = p; r.q = q; r.m = (int32_t)M; r.frames = (int32_t)K;
+    if (M > m_max) m_max = M;
+    if (K > k_max) k_max = K;
+  }
+  SMI_REQUIRE(out_stride >= 1 && out_stride >= m_max && out_stride <= TP_MAX_OUT,
+              "smi_tempo_rows: out_stride=%lld outside max(1, the longest output row %lld)..%d", out_stride, m_max, TP_MAX_OUT);
+  SMI_REQUIRE(pos_stride >= 1 && pos_stride >= k_max && pos_stride <= TP_MAX_OUT,
+              "smi_tempo_rows: pos_stride=%lld outside max(1, the most frames of a row %lld)..%d", pos_stride, k_max, TP_MAX_OUT);
+  {
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + ((size_t)(B - 1) * in_stride + n_max) * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_tempo_rows: out_dev overlaps in_dev");
+  }
+  if (m_host)
+    for (int b = 0; b < B; ++b) m_host[b] = A.r[b].m;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_tempo_search, dim3(B), dim3(TP_BLOCK), 0, s, A, N, D, in_dev, in_stride, pos_dev, pos_stride);
+  SMI_LAUNCH_CHECK();
+  const int tiles = (int)((out_stride + TP_TILE - 1) / TP_TILE);
+  hipLaunchKernelGGL(k_tempo_ola, dim3(tiles, B), dim3(RS_BLOCK), 0, s, A, N, in_dev, in_stride, win_dev, pos_dev, pos_stride, out_dev, out_stride);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

@@ -15,6 +15,10 @@ the speech bounds of vocoded rows, and the trimmed rows as one waveform with pau
 ``DeviceAudio.loudness_rows`` / ``gain_rows`` (``smi_loud_rows``, ``smi_gain_rows``) level the output: the programme loudness of
 rows after ITU-R BS.1770 and the gain that brings each to a target under a peak ceiling, measured and applied on the device.
 ``k_weighting`` designs the weighting filter's coefficients for a sample rate with numpy alone.
+
+``DeviceAudio.tempo_rows`` (``smi_tempo_rows``) changes the speaking rate of rows at unchanged pitch: WSOLA whose similarity
+search is exact integer arithmetic, so the device is held to ``tests/tempo_ref.py`` bit for bit.  ``tempo_ratio``,
+``tempo_frame`` and ``tempo_window`` give its rational, its frame and radius for a sample rate, and its window.
 """
 from __future__ import annotations
 
@@ -109,6 +113,42 @@ def check_loudness(loudness, peak_ceiling, max_gain_db) -> None:
         raise ValueError(f"peak_ceiling must be > 0, not {peak_ceiling!r}")
     if max_gain_db < 0:
         raise ValueError(f"max_gain_db must be >= 0, not {max_gain_db!r}")
+
+
+TEMPO_MIN, TEMPO_MAX = 0.5, 2.0
+
+
+def tempo_ratio(tempo: float) -> Tuple[int, int]:
+    """(p, q) in lowest terms for a tempo in [0.5, 2.0] (> 1: faster), to a hundredth: ``round(tempo * 100) / 100``"""
+    if isinstance(tempo, bool) or not isinstance(tempo, (int, float, np.integer, np.floating)) or not math.isfinite(tempo):
+        raise ValueError(f"tempo must be a finite number, not {tempo!r}")
+    if not TEMPO_MIN <= tempo <= TEMPO_MAX:
+        raise ValueError(f"tempo must lie in [{TEMPO_MIN}, {TEMPO_MAX}], not {tempo!r}")
+    p = int(round(float(tempo) * 100))
+    g = math.gcd(p, 100)
+    return p // g, 100 // g
+
+
+def tempo_window(N: int) -> np.ndarray:
+    """float64 [N]: the periodic Hann window ``0.5 - 0.5 cos(2 pi i / N)`` that ``smi_tempo_rows`` takes as data; its two
+    halves sum to one, so frames half a window apart overlap-add to unit gain"""
+    N = int(N)
+    if N < 2 or N % 2:
+        raise ValueError(f"the frame must be even and positive, not {N}")
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(N, dtype=np.float64) / N)
+
+
+def tempo_frame(sr: int) -> Tuple[int, int]:
+    """(N, D) at ``sr`` Hz: a frame of 32 ms as two halves, ``2 * round(0.016 * sr)``, and a search radius of 15 ms"""
+    sr = int(sr)
+    if sr < 1:
+        raise ValueError(f"sample rate must be positive, not {sr}")
+    return 2 * int(round(0.016 * sr)), int(round(0.015 * sr))
+
+
+def tempo_len(L: int, p: int, q: int) -> int:
+    """ceil(L * q / p): the samples a span of ``L`` has at tempo p / q (``smi_tempo_layout``)"""
+    return -((-int(L) * int(q)) // int(p))
 
 
 class DeviceAudio:
@@ -333,6 +373,46 @@ class DeviceAudio:
                                                 C.c_void_p(stats.data_ptr()), C.c_void_p(out.data_ptr()), out.shape[1], self._stream()),
                         "smi_gain_rows")
         return out
+
+    def tempo_rows(self, x, n: Sequence[int], tempos: Sequence, spans: Optional[Sequence[Tuple[int, int]]] = None, out=None,
+                   sr: int = 16000, frame: Optional[Tuple[int, int]] = None):
+        """A pitch-preserving time-scale change of rows (WSOLA; include/sparkmi.h, smi_tempo_rows).  ``x``: [B][stride] float32
+        on the device, row b valid for ``n[b]``; ``tempos``: per row a number in [0.5, 2.0] (``tempo_ratio``; > 1: faster) or
+        a (p, q) pair; ``spans``: (start, end) per row, None: the whole rows -- nothing outside a span is read.  ``sr`` gives
+        the frame and the search radius (``tempo_frame``); ``frame`` = (N, D) replaces them.  ``out``: None: a new
+        [B][max(1, longest output)] tensor; or a contiguous [B][out_stride] float32 tensor on the device that does not overlap
+        ``x``.  Returns (y -- row b holds its ``m[b]`` samples, then zeros --, m, pos [B][frames] int32 on the device: every
+        frame's place in its span).  Two launches, nothing waits and nothing is copied back."""
+        import torch
+        B = self._rows(x, n, "tempo_rows")
+        st, en = self._spans(spans, B)
+        if len(tempos) != B:
+            raise ValueError("one tempo per row")
+        pq = [(int(t[0]), int(t[1])) if isinstance(t, (tuple, list)) else tempo_ratio(t) for t in tempos]
+        N, D = tempo_frame(sr) if frame is None else (int(frame[0]), int(frame[1]))
+        lens = [int(s[1]) - int(s[0]) for s in spans] if spans is not None else [int(v) for v in n]
+        frames = (C.c_longlong)()
+        m_max = k_max = 0
+        for (p, q), L in zip(pq, lens):   # (a bad row: the call below names it)
+            m = self._lib.smi_tempo_layout(max(0, L), p, q, N, C.byref(frames))
+            if m >= 0:
+                m_max, k_max = max(m_max, int(m)), max(k_max, int(frames.value))
+        wins = self.__dict__.setdefault("_tempo_windows", {})
+        if N not in wins and N >= 2 and N % 2 == 0:
+            wins[N] = torch.from_numpy(tempo_window(N)).to(self.device)
+        win = wins.get(N)
+        if out is None:
+            out = torch.empty((max(1, B), max(1, m_max)), dtype=torch.float32, device=self.device)
+        elif out.dim() != 2 or out.shape[0] != B or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("tempo_rows: out must be a contiguous [B][out_stride] float32 tensor on the device")
+        pos = torch.empty((max(1, B), max(1, k_max)), dtype=torch.int32, device=self.device)
+        i32 = lambda v: (C.c_int32 * B)(*[int(a) for a in v])   # noqa: E731
+        got = (C.c_int32 * max(1, B))()
+        self._lib.check(self._lib.smi_tempo_rows(C.c_void_p(x.data_ptr()), x.shape[1], i32(n), st, en, B, i32(a[0] for a in pq),
+                                                 i32(a[1] for a in pq), N, D, C.c_void_p(win.data_ptr() if win is not None else 0),
+                                                 C.c_void_p(pos.data_ptr()), pos.shape[1], C.c_void_p(out.data_ptr()), out.shape[1],
+                                                 got, self._stream()), "smi_tempo_rows")
+        return out, list(got)[:B], pos
 
 
 class StreamJoiner:

@@ -11,7 +11,8 @@ batching) and ``serve_stream`` (both at once: chunked audio for every live reque
 calls take ``joined=True`` for contiguous, playable pieces at any output rate (the chunks joined on the device);
 ``inference_long`` / ``inference_long_stream`` (text of any length: sentences as the rows of one in-flight session, their
 waveforms trimmed and joined on the device); ``loudness`` / ``peak_ceiling`` / ``max_gain_db`` on every call that returns whole
-utterances (the output at a programme loudness after BS.1770, measured and scaled on the device).
+utterances (the output at a programme loudness after BS.1770, measured and scaled on the device); ``tempo`` on the same calls
+(a pitch-preserving change of the speaking rate, 0.5 .. 2.0, on the device before the loudness stage).
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import PEAK_CEILING, check_loudness
+from .audio import PEAK_CEILING, check_loudness, tempo_len, tempo_ratio
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
 from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, NGRAM_KEY, PENALTY_KEYS, SAMPLING_KEYS, SEQ_KEYS, SparkLLM,
@@ -46,6 +47,8 @@ EOS_BIAS_KEY = "eos_bias"
 # request key: the programme loudness (LUFS) the request's waveform is brought to; it overrides the call's ``loudness``
 LOUDNESS_KEY = "loudness"
 LIMITED = (None, "max_gain", "ceiling")   # what bounded a row's gain (include/sparkmi.h, smi_loud_rows: limit 0 / 1 / 2)
+# request key: the request's own tempo (0.5 .. 2.0; > 1: faster); it overrides the call's ``tempo``
+TEMPO_KEY = "tempo"
 
 
 def _stream_pacing(max_batch: int, max_open=None, max_ahead=None, resume_ahead=None):
@@ -259,10 +262,11 @@ class SparkTTS:
                   min_new_tokens: int = 0, penalize_prompt: bool = True, return_log_probs: bool = False,
                   num_return_sequences: int = 1, allowed_token_ids: Optional[Sequence[int]] = None,
                   speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0, output_sample_rate: Optional[int] = None,
-                  loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0):
+                  loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
+                  tempo: Optional[float] = None):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate`` (or at ``output_sample_rate``,
         as in ``inference_batch``; ``loudness`` / ``peak_ceiling`` / ``max_gain_db``: the output's programme loudness, as
-        there).  The penalties
+        there; ``tempo``: the speaking rate, as there).  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
         penalty.  ``return_log_probs=True``: (waveform, info) with info = {``token_ids``: the generated ids,
@@ -290,7 +294,7 @@ class SparkTTS:
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                                     max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs,
                                     output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
-                                    max_gain_db=max_gain_db)[0]
+                                    max_gain_db=max_gain_db, tempo=tempo)[0]
 
     def _output_ratio(self, output_sample_rate: Optional[int]) -> Optional[Tuple[int, int]]:
         """(up, down) from the model's rate to ``output_sample_rate``; None when the vocoder's rows go out as they are"""
@@ -302,6 +306,12 @@ class SparkTTS:
             return None
         from .audio import ratio
         return ratio(self.sample_rate, int(output_sample_rate))
+
+    @staticmethod
+    def _no_stream_tempo(tempo, who: str) -> None:
+        if tempo is not None:
+            raise ValueError(f"{who}: tempo is not supported for chunked streams (a time-scale change across chunk edges needs "
+                             "carried state); use inference / inference_batch / serve / inference_long / inference_long_stream")
 
     @staticmethod
     def _no_stream_rate(output_sample_rate: Optional[int], who: str) -> None:
@@ -372,12 +382,38 @@ class SparkTTS:
         host = stats.cpu().tolist()
         return [None if t is None else dict(loudness=row[0], gain=row[2], limited=LIMITED[int(row[3])]) for t, row in zip(targets, host)]
 
+    @staticmethod
+    def _tempo_ratios(requests: Sequence[dict], tempo, first: int = 0) -> List[Optional[Tuple[int, int]]]:
+        """every request's tempo as (p, q) (its own ``tempo`` key, else the call's), all checked; None for a request without
+        one or at 1.0, which is left as vocoded.  ``first``: the index of ``requests[0]`` in the caller's list, for the message."""
+        if tempo is not None:
+            tempo_ratio(tempo)
+        out = []
+        for i, r in enumerate(requests):
+            t = r.get(TEMPO_KEY, tempo)
+            try:
+                pq = None if t is None else tempo_ratio(t)
+            except ValueError as e:
+                raise ValueError(f"request {first + i}: {e}") from None
+            out.append(None if pq == (1, 1) else pq)
+        return out
+
+    def _tempo_rows(self, wav, n: Sequence[int], ratios: Sequence[Optional[Tuple[int, int]]], spans=None):
+        """Rows (or their ``spans``) at their tempos, on the device (``audio.DeviceAudio.tempo_rows``: two launches for all rows,
+        nothing waits): (new rows, their lengths).  A row without a ratio goes through at 1/1, which copies it bit for bit.
+        Where no row has a ratio nothing is launched: (wav, n) as they came -- only without ``spans``."""
+        if spans is None and all(r is None for r in ratios):
+            return wav, list(n)
+        y, m, _ = self._device_audio().tempo_rows(wav.contiguous(), n, [r or (1, 1) for r in ratios], spans=spans, sr=self.sample_rate)
+        return y, m
+
     @torch.no_grad()
     def inference_batch(self, requests: Sequence[dict], temperature: float = 0.8, top_k: float = 50,
                         top_p: float = 0.95, *, do_sample: bool = True, max_new_tokens: int = 3000,
                         seed: Optional[int] = None, return_log_probs: bool = False, prompt_encode: str = "streams",
                         prompt_audio: str = "host", output_sample_rate: Optional[int] = None,
-                        loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0) -> List:
+                        loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
+                        tempo: Optional[float] = None) -> List:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
@@ -407,8 +443,14 @@ class SparkTTS:
         smi_loud_rows) on the device, after vocoding and before the resampling -- by a gain of at most ``max_gain_db`` that
         keeps the sample peak at or below ``peak_ceiling`` (a sample peak, not a true peak); a silent row is left as it is.
         All rows go through the same two device calls.  ``self.last_loudness`` then holds, per request (per take where it
-        has takes), None or {``loudness``: measured before the gain, ``gain``, ``limited``: None / "max_gain" / "ceiling"}."""
+        has takes), None or {``loudness``: measured before the gain, ``gain``, ``limited``: None / "max_gain" / "ceiling"}.
+        ``tempo`` (0.5 .. 2.0, to a hundredth; > 1: faster; None or 1.0: the rows as vocoded, no extra launch) or a request's own
+        ``tempo`` key, which overrides it: the speaking rate of the vocoded row is changed at unchanged pitch (WSOLA;
+        include/sparkmi.h, smi_tempo_rows) on the device, after vocoding and before the loudness stage, which measures the
+        final signal; a row of n samples then has ``audio.tempo_len(n, p, q)``.  It works for cloned voices, which the
+        ``speed`` label of voice creation does not reach, and it is exact where the label is a hint."""
         targets = self._loudness_targets(requests, loudness, peak_ceiling, max_gain_db)
+        ratios = self._tempo_ratios(requests, tempo)
         if prompt_encode not in ("streams", "rows"):
             raise ValueError(f"prompt_encode must be 'streams' or 'rows', not {prompt_encode!r}")
         if prompt_audio not in ("host", "device"):
@@ -501,6 +543,7 @@ class SparkTTS:
         n_wav = [n * hop for n in lens]
         wav = wav.squeeze(1)
         row_targets = [targets[b] for b in owner]
+        wav, n_wav = self._tempo_rows(wav, n_wav, [ratios[b] for b in owner])
         stats = None
         if any(t is not None for t in row_targets):
             wav = wav.contiguous()
@@ -531,7 +574,7 @@ class SparkTTS:
                          audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
                          audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
                          decode_stride: int = 10, output_sample_rate: Optional[int] = None,
-                         joined: bool = False) -> Iterator[np.ndarray]:
+                         joined: bool = False, tempo: Optional[float] = None) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
@@ -549,7 +592,10 @@ class SparkTTS:
         Refused (ValueError, before any device call) if the first chunk is shorter than two overlaps.
 
         There is no ``loudness`` here: the integrated loudness of BS.1770 is a property of the whole utterance, which a
-        chunk that must leave before the utterance ends cannot know (``inference`` / ``inference_long_stream`` take it)."""
+        chunk that must leave before the utterance ends cannot know (``inference`` / ``inference_long_stream`` take it).
+        Nor is there a ``tempo``: a time-scale change across chunk edges needs state carried from chunk to chunk, which is out
+        of scope; a given ``tempo`` is refused (ValueError).  ``inference`` / ``inference_long_stream`` take it."""
+        self._no_stream_tempo(tempo, "inference_stream")
         if not joined:
             self._no_stream_rate(output_sample_rate, "inference_stream")
         joiner = self._stream_joiner("inference_stream", output_sample_rate, 1, audio_chunk_duration, max_audio_chunk_duration,
@@ -646,7 +692,8 @@ class SparkTTS:
     @torch.no_grad()
     def serve(self, requests, temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *, do_sample: bool = True,
               max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False,
-              loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0):
+              loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
+              tempo: Optional[float] = None):
         """In-flight batching front end (the functional analogue of the reference's Triton deployment,
         runtime/triton_trtllm/run.sh:50-65): ``requests`` is an iterable of the dicts ``inference_batch`` takes;
         yields ``(index, waveform)`` as each utterance finishes.  Up to ``max_batch`` utterances are live; a new
@@ -660,10 +707,13 @@ class SparkTTS:
         takes have finished, each take a waveform or a (waveform, info) pair, vocoded together.
         ``loudness`` / ``peak_ceiling`` / ``max_gain_db`` and a request's own ``loudness`` key as in ``inference_batch``: each
         waveform is brought to its target on the device before its copy; ``self.last_loudness[index]`` holds what was measured
-        (a list for a request with takes) once the request has been yielded."""
+        (a list for a request with takes) once the request has been yielded.  ``tempo`` and a request's own ``tempo`` key as in
+        ``inference_batch``: the waveform's speaking rate is changed on the device, before the loudness stage."""
         forks: Dict[int, int] = {}   # request index -> takes, for the requests that carry num_return_sequences
         goals: Dict[int, Optional[float]] = {}   # request index -> loudness target
+        rates: Dict[int, Optional[Tuple[int, int]]] = {}   # request index -> tempo as (p, q)
         check_loudness(loudness, peak_ceiling, max_gain_db)
+        self._tempo_ratios([], tempo)
         self.last_loudness = {}
 
         def checked(reqs):   # each request's takes, checked before the request reaches the device
@@ -672,6 +722,7 @@ class SparkTTS:
                     forks[i] = _take_counts([r], self._max_batch)[0]
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 goals[i] = self._loudness_targets([r], loudness, peak_ceiling, max_gain_db)[0]
+                rates[i] = self._tempo_ratios([r], tempo, i)[0]
                 yield r
 
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
@@ -704,19 +755,19 @@ class SparkTTS:
                 rows.append(self._speech_row(i, toks, globals_[i]))
                 infos.append(None if lps is None else _lp_info(toks, lps[: len(toks)]))
             wav, lens = self._vocode_rows(rows)
-            wav = normalized(i, wav, lens, True)
+            wav, n = finished(i, wav, lens, True)
             wav = wav.cpu().numpy()
-            return [(wav[b, : lens[b] * hop].copy(), infos[b]) if infos[b] is not None else wav[b, : lens[b] * hop].copy()
-                    for b in range(len(rows))]
+            return [(wav[b, : n[b]].copy(), infos[b]) if infos[b] is not None else wav[b, : n[b]].copy() for b in range(len(rows))]
 
-        def normalized(i, wav, lens, takes):   # the vocoded rows of request i at its loudness target, still on the device
+        def finished(i, wav, lens, takes):   # the vocoded rows of request i at its tempo and loudness target, still on the device
+            wav, n = self._tempo_rows(wav, [f * hop for f in lens], [rates[i]] * len(lens))
             if goals[i] is None:
-                return wav
+                return wav, n
             wav = wav.contiguous()
-            stats = self._normalize_rows(wav, [f * hop for f in lens], [goals[i]] * len(lens), peak_ceiling, max_gain_db)
+            stats = self._normalize_rows(wav, n, [goals[i]] * len(lens), peak_ceiling, max_gain_db)
             got = self._loudness_info(stats, [goals[i]] * len(lens))
             self.last_loudness[i] = got if takes else got[0]
-            return wav
+            return wav, n
 
         for i, toks in self.model.serve(llm_requests(), max_live=self._max_batch, decode_stride=decode_stride,
                                         return_log_probs=return_log_probs):
@@ -728,7 +779,8 @@ class SparkTTS:
                 toks, lps = toks
             toks = self._cut_eos(toks)
             wav, lens = self._vocode_rows([self._speech_row(i, toks, globals_[i])])
-            w = normalized(i, wav, lens, False)[0, : lens[0] * hop].cpu().numpy().copy()
+            wav, n = finished(i, wav, lens, False)
+            w = wav[0, : n[0]].cpu().numpy().copy()
             if lps is None:
                 yield i, w
             else:
@@ -740,7 +792,8 @@ class SparkTTS:
                      audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
                      audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
                      max_open: Optional[int] = None, max_ahead: Optional[float] = None, resume_ahead: Optional[float] = None,
-                     clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None, joined: bool = False):
+                     clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None, joined: bool = False,
+                     tempo: Optional[float] = None):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -786,13 +839,15 @@ class SparkTTS:
         (ValueError, before any device call) if the first chunk is shorter than two overlaps.
 
         There is no ``loudness`` here, as in ``inference_stream``: integrated loudness needs the whole utterance (``serve``
-        takes it)."""
+        takes it).  Nor a ``tempo``, in the call or in a request: tempo across chunk edges needs carried state and is out of
+        scope; it is refused (ValueError), and ``serve`` takes it."""
+        self._no_stream_tempo(tempo, "serve_stream")
         if not joined:
             self._no_stream_rate(output_sample_rate, "serve_stream")
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
-                for k in (FORK_KEY,) + tuple(LOGPROB_KEYS):
+                for k in (FORK_KEY, TEMPO_KEY) + tuple(LOGPROB_KEYS):
                     if k in r:
                         raise ValueError(f"request {i}: {k} is not supported by serve_stream")
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
@@ -964,13 +1019,15 @@ class SparkTTS:
     # ------------------------------------------------------------------ long text: sentences as rows, trimmed and joined on the device
     def _long_pieces(self, text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
                      max_new_tokens, seed, prompt_tokens, keys: dict, max_width, min_width, pause, trim, trim_threshold, fade, eager: bool,
-                     info: dict, loudness=None, peak_ceiling=PEAK_CEILING, max_gain_db=20.0):
+                     info: dict, loudness=None, peak_ceiling=PEAK_CEILING, max_gain_db=20.0, tempo=None):
         """The engine of ``inference_long`` and ``inference_long_stream``: yields (first sentence, joined [total] float32 on the
         device, [(offset in it, gap, length) per sentence]) for runs of consecutive sentences in text order -- with ``eager``
         as soon as the next sentence due and those behind it are done, else in runs of ``max_batch`` once all are done.  Fills
-        ``info``.  With ``loudness``, every sentence's trimmed piece is brought to that programme loudness in place before the
-        assembly.  Everything is checked before anything reaches the device."""
+        ``info``.  With ``tempo``, every sentence's trimmed piece is time-scaled on its own into a row of its own; with
+        ``loudness``, every piece (scaled or not) is brought to that programme loudness in place before the assembly.
+        Everything is checked before anything reaches the device."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
+        rate = self._tempo_ratios([{}], tempo)[0]
         from .longform import control_prefix, control_prompt_ids, ready_run, sentence_seeds, split_text, trim_params
         sentences = split_text(text, max_width, min_width)
         for name, v in (("pause", pause), ("fade", fade), ("trim_threshold", trim_threshold)):
@@ -999,6 +1056,8 @@ class SparkTTS:
         info.update(sentences=sentences, token_ids=[None] * n_sent, bounds=[None] * n_sent, offsets=[None] * n_sent, truncated=[], silent=[])
         if loudness is not None:
             info.update(loudness=[None] * n_sent, gain=[None] * n_sent, limited=[None] * n_sent)
+        if rate is not None:
+            info.update(tempo_lengths=[None] * n_sent)
         audio = self._device_audio()
         tokens: Dict[int, List[int]] = {}
         state = {"due": 0, "total": 0, "spoken": False}
@@ -1024,6 +1083,12 @@ class SparkTTS:
             for a, b in bounds:
                 gaps.append(gap if b > a and state["spoken"] else 0)
                 state["spoken"] = state["spoken"] or b > a
+            cut = bounds              # of the untrimmed rows: what info["bounds"] reports
+            if rate is not None:      # each trimmed piece scaled on its own: row k of the new rows is the whole scaled piece
+                wav, n = self._tempo_rows(wav, n, [rate] * len(ks), spans=bounds)
+                bounds = [(0, v) for v in n]
+                for k, v in zip(ks, n):
+                    info["tempo_lengths"][k] = v
             offs, total = audio.concat_layout(bounds, gaps)
             stats = None
             if loudness is not None:   # each piece to the target on its own trimmed span, in place, before the assembly
@@ -1034,7 +1099,7 @@ class SparkTTS:
             if stats is not None:      # (one small copy, like the bounds', behind everything that was enqueued)
                 for k, d in zip(ks, self._loudness_info(stats, [loudness] * len(ks))):
                     info["loudness"][k], info["gain"][k], info["limited"][k] = d["loudness"], d["gain"], d["limited"]
-            for k, (a, b), o, g in zip(ks, bounds, offs, gaps):
+            for k, (a, b), o, g in zip(ks, cut, offs, gaps):
                 info["bounds"][k], info["offsets"][k] = (a, b), state["total"] + o
                 if b == a:
                     info["silent"].append(k)
@@ -1090,7 +1155,7 @@ class SparkTTS:
                        max_width: int = 300, min_width: int = 20, pause: float = 0.25, trim: bool = True,
                        trim_threshold: float = 0.01, fade: float = 0.005, output_sample_rate: Optional[int] = None,
                        return_info: bool = False, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
-                       max_gain_db: float = 20.0):
+                       max_gain_db: float = 20.0, tempo: Optional[float] = None):
         """A text of any length -> one float32 waveform: the text is cut into sentences (``longform.split_text``: ``max_width``,
         ``min_width``), the sentences are generated with the same voice as the requests of one in-flight session (up to
         ``max_batch`` live; ``max_new_tokens`` is per sentence), vocoded in ragged calls, cut at their speech bounds
@@ -1117,15 +1182,22 @@ class SparkTTS:
         include/sparkmi.h, smi_loud_rows / smi_gain_rows: trim, measure over the piece, scale in place, assemble) by a gain of at
         most ``max_gain_db`` that keeps its sample peak at or below ``peak_ceiling``; a silent sentence is untouched.  ``info``
         then also holds ``loudness`` (measured before the gain), ``gain`` and ``limited`` (None, "max_gain" or "ceiling") per
-        sentence."""
+        sentence.
+
+        ``tempo`` (0.5 .. 2.0; None or 1.0: no extra launch): every trimmed piece is time-scaled on its own at unchanged pitch
+        (include/sparkmi.h, smi_tempo_rows) after the trim and before the loudness stage and the assembly.  ``pause`` and
+        ``fade`` stay seconds of the joined waveform -- the silences are not scaled --, ``info["bounds"]`` stays in samples of
+        the untrimmed row, ``info["tempo_lengths"]`` holds every scaled piece's length and ``info["offsets"]`` places the scaled
+        pieces in the joined waveform."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
+        self._tempo_ratios([], tempo)
         out_ratio = self._output_ratio(output_sample_rate)
         keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
                                min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
         info: dict = {}
         parts = [out for _, out, _ in self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p,
                                                         do_sample, max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim,
-                                                        trim_threshold, fade, False, info, loudness, peak_ceiling, max_gain_db)
+                                                        trim_threshold, fade, False, info, loudness, peak_ceiling, max_gain_db, tempo)
                  if out is not None]
         if not parts:
             wav = np.zeros(0, dtype=np.float32)
@@ -1149,7 +1221,8 @@ class SparkTTS:
                               max_width: int = 300, min_width: int = 20, pause: float = 0.25, trim: bool = True,
                               trim_threshold: float = 0.01, fade: float = 0.005,
                               output_sample_rate: Optional[int] = None, loudness: Optional[float] = None,
-                              peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0) -> Iterator[np.ndarray]:
+                              peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
+                              tempo: Optional[float] = None) -> Iterator[np.ndarray]:
         """``inference_long`` piece by piece: yields contiguous float32 pieces in text order, sentence k's pause + trimmed and faded
         piece as soon as k and every sentence before it are done (an empty piece is not yielded).  At the model's rate the
         pieces' concatenation is ``inference_long``'s waveform bit for bit: a piece's bits are its own (include/sparkmi.h,
@@ -1157,14 +1230,16 @@ class SparkTTS:
         concatenation with the resampler's state kept across the pieces -- and the concatenation of what is yielded (the last
         piece is the resampler's flush) is bit for bit ``inference_long(..., output_sample_rate=...)``.  ``loudness`` /
         ``peak_ceiling`` / ``max_gain_db`` as in ``inference_long``: a sentence's loudness is measured over its own piece, so
-        the pieces stay bit for bit those of ``inference_long``."""
+        the pieces stay bit for bit those of ``inference_long``.  ``tempo`` as in ``inference_long``: a sentence's piece is
+        scaled whole and on its own before it leaves, so no state crosses the pieces and the same holds."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
+        rate = self._tempo_ratios([{}], tempo)[0] or (1, 1)
         out_ratio = self._output_ratio(output_sample_rate)
         keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
                                min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
         pieces = self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
                                    max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim, trim_threshold, fade, True, {},
-                                   loudness, peak_ceiling, max_gain_db)
+                                   loudness, peak_ceiling, max_gain_db, tempo)
         joiner = None
         for _, out, spans in pieces:
             if out is None:
@@ -1177,7 +1252,7 @@ class SparkTTS:
                 continue
             if joiner is None:   # (pieces of up to a pause and a whole vocoder row)
                 from .audio import StreamJoiner
-                key = (1, int(round(pause * self.sample_rate)) + self._max_frames * self.audio_tokenizer.model.hop, 0) + tuple(out_ratio)
+                key = (1, int(round(pause * self.sample_rate)) + tempo_len(self._max_frames * self.audio_tokenizer.model.hop, *rate), 0) + tuple(out_ratio)
                 if getattr(self, "_joiners", None) is None:
                     self._joiners = {}
                 if key not in self._joiners:
