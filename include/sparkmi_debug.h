@@ -73,9 +73,16 @@ int smi_llm_debug_read(smi_llm* h, int what, void* out_host, size_t cap, size_t*
  *     kernels up to and including `stage`: 0 QKV (+ bias, RoPE, K/V append: read q with smi_llm_debug_read(0), K/V with _get_kv),
  *     1 attention (buffer 1: the o_proj operand triples, head-interleaved k tiles), 2 o_proj + residual (buffer 4; one fused row:
  *     buffer 8), 3 gate_up + SwiGLU (buffer 2: act triples), 4 down_proj + residual (buffer 4).  smi_llm_debug_read's buffers
- *     0..4 and 6 then hold M rows.  Contiguous KV cache only.  Ends the current generation. */
+ *     0..4 and 6 then hold M rows.  Ends the current generation.
+ *   Paged KV cache (kv_page_tokens > 0): _set_kv / _get_kv give the slot pages for positions 0 .. pos0 + n - 1 and copy page by page
+ *     through the host's page table; _debug_layer / _debug_prefill_layer give every named slot pages up to its last row's position
+ *     (SMI_ENOMEM when the pool is short; pages stay with the slot until the next prefill or release).  The order of those calls
+ *     decides which pages a slot gets: tests/test_llm_paged_ops_gpu.py fills the slots a page at a time, round-robin.
+ *   smi_llm_debug_page_table: the pages `slot` holds, in position order, from the host's page table: *n = their count (0 on a
+ *     contiguous cache), the first min(*n, cap) of them in out. */
 int smi_llm_debug_set_kv(smi_llm* h, int layer, int slot, int pos0, int n, const float* k_host, const float* v_host);
 int smi_llm_debug_get_kv(smi_llm* h, int layer, int slot, int pos0, int n, float* k_host, float* v_host);
+int smi_llm_debug_page_table(smi_llm* h, int slot, int32_t* out, int cap, int32_t* n);
 int smi_llm_debug_layer(smi_llm* h, int layer, int M, const int32_t* rows_host, const float* hidden_host, int stage);
 /* Op-level tests of the PROMPT pass (tests/test_llm_prefill_ops_gpu.py): one decoder layer's kernels as a pass over more than 64
  * prompt rows launches them -- k_pgemm in its few-row (split-K o_proj / down_proj + k_resid_comb) and many-row shapes, k_attn_pf<f32>,
@@ -88,7 +95,7 @@ int smi_llm_debug_layer(smi_llm* h, int layer, int M, const int32_t* rows_host, 
  *     0 QKV (+ bias, RoPE, K/V append: smi_llm_debug_read(16), _get_kv), 1 attention (17), 2 o_proj + residual (20), 3 gate_up +
  *     SwiGLU (18), 4 down_proj + residual (20), 5 = stage 4, then layer + 1's QKV (16, _get_kv of layer + 1) -- the one reader of
  *     the RMSNorm partials down_proj leaves.  The last layer takes stage 0 only (a pass launches nothing after its K/V append): any
- *     other stage is SMI_EINVAL, as are a paged cache, M = 0 and a position outside the cache.  Ends the current generation.
+ *     other stage is SMI_EINVAL, as are M = 0 and a position outside the cache.  Ends the current generation.
  *   smi_llm_pf_tiles: host only, no GPU call -- the tiles the pass builds for k_attn_pf2 from M (slot, pos) rows: out[i] =
  *     (first row, rows, slot, first position) of tile i, *n = the number of tiles (at most cap are written). */
 enum { SMI_PF_GROUPED = 1, SMI_PF_PGEMM = 2 };

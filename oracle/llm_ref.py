@@ -154,7 +154,7 @@ def rope_angles(cfg, positions) -> np.ndarray:
 
 
 def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.ndarray], vcache: Dict[int, np.ndarray],
-                     own_kv: bool = True, qkv_only: bool = False) -> Dict[str, np.ndarray]:
+                     own_kv: bool = True, qkv_only: bool = False, mlp: bool = True) -> Dict[str, np.ndarray]:
     """One Qwen2 decoder layer (MQ Qwen2DecoderLayer) on M caller rows, every product and sum in float64.
 
     ``weights``: ``name -> array`` under HF names; ``rows``: (M, 2) (KV slot, position) pairs; ``x``: (M, hidden) residual rows
@@ -164,7 +164,7 @@ def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.nda
     e.g. as a bf16 cache stored them).  Returns what ``SparkLLM.debug_layer`` returns for stages 0-4, in its layouts:
     q (M, heads, hd), k / v (M, kv heads, hd) after bias and RoPE, attn (M, heads * hd), h_mid (M, hidden) after o_proj +
     residual, act (M, intermediate) = silu(gate) * up, h_out (M, hidden) after down_proj + residual.  ``qkv_only``: q, k, v alone
-    (the caches are not read)."""
+    (the caches are not read); ``mlp=False``: q .. h_mid (the MLP, which never sees the context, is left out)."""
     p = f"model.layers.{layer}."
     w = lambda n: np.asarray(weights[p + n], dtype=np.float64)  # noqa: E731
     nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
@@ -205,6 +205,8 @@ def layer_stages_f64(cfg, weights, layer: int, rows, x, kcache: Dict[int, np.nda
         pr /= pr.sum(-1, keepdims=True)
         attn[i] = np.einsum("ht,thd->hd", pr, Vr).reshape(-1)
     h_mid = x + attn @ w("self_attn.o_proj.weight").T
+    if not mlp:
+        return {"q": q, "k": k, "v": v, "attn": attn, "h_mid": h_mid}
     xn2 = rms(h_mid, w("post_attention_layernorm.weight"))
     g = xn2 @ w("mlp.gate_proj.weight").T
     act = g / (1.0 + np.exp(-g)) * (xn2 @ w("mlp.up_proj.weight").T)  # MQ:46-48 silu(gate) * up

@@ -2258,7 +2258,7 @@ struct AttnP {
   unsigned char* xs_out;  // o_proj operand: exact bf16 triples [q_dim/32][3][4][M][16 B]
   int M;
   int q_dim, n_kv, group, max_pos, n_heads;
-  KvMap km;            // paged KV cache (general kernel and k_attn_pf only; the slot_is_row kernels need contiguous slots)
+  KvMap km;            // paged KV cache (ptab null: contiguous slots); every form reads through it -- the slot_is_row kernels in their PG instantiations
   int slot_is_row;     // every row m lives in KV slot m (decode): addresses need no descriptor
   int work_blocks;     // = n_heads * M * nseg; later blocks are prefetch helpers
   PfDesc pf;
@@ -7168,10 +7168,35 @@ int smi_llm_debug_read(smi_llm* L, int what, void* out_host, size_t cap, size_t*
 
 // ---- op-level tests (sparkmi_debug.h): one layer's kernels, stage by stage, on caller-given rows -- through launch_one, i.e. the
 // launch builders, kernel choices and epilogue fusions of a real step
-static int debug_kv_check(const smi_llm* L, int layer, int slot, int pos0, int n) {
-  SMI_REQUIRE(L && !L->paged, "debug KV access needs a contiguous KV cache (kv_page_tokens = 0)");
+// (paged cache: the slot gets pages for positions 0 .. pos0 + n - 1 first, and everything issued so far is done on return)
+static int debug_kv_check(smi_llm* L, int layer, int slot, int pos0, int n) {
+  SMI_REQUIRE(L, "debug KV access: null handle");
   SMI_REQUIRE(layer >= 0 && layer < L->cfg.num_layers && slot >= 0 && slot < L->cfg.max_slots && pos0 >= 0 && n >= 0 &&
-              pos0 + n <= L->cfg.max_positions, "debug KV access: layer %d slot %d positions %d..%d out of range", layer, slot, pos0, pos0 + n);
+              n <= L->cfg.max_positions && pos0 <= L->cfg.max_positions - n,
+              "debug KV access: layer %d slot %d positions %d..%d out of range", layer, slot, pos0, pos0 + n);
+  const int tokens = pos0 + n;
+  SMI_TRY(pages_ensure(L, &slot, &tokens, 1, nullptr));
+  SMI_HIP(hipDeviceSynchronize());
+  return SMI_OK;
+}
+// kv_row on the host, through the host mirror of the page table: where position `pos` of (slot, kv head) lives, in rows of 64
+// elements, and how many of the positions pos .. pos + n - 1 follow it in memory (paged: to the end of pos's page)
+static size_t debug_kv_run(const smi_llm* L, int slot, int kh, int pos, int n, int* run) {
+  const size_t nkv = (size_t)L->cfg.num_kv_heads;
+  if (!L->paged) { *run = n; return ((size_t)slot * nkv + kh) * L->cfg.max_positions + pos; }
+  const int P = 1 << L->pshift, off = pos & (P - 1);
+  *run = n < P - off ? n : P - off;
+  const size_t pg = (size_t)L->hptab[(size_t)slot * L->ppslot + (pos >> L->pshift)];
+  return ((pg * nkv + kh) << L->pshift) + off;
+}
+
+// paged cache: every slot with need[slot] > 0 gets pages for its positions 0 .. need[slot] - 1 (all or nothing), table uploaded
+static int debug_pages(smi_llm* L, const std::vector<int>& need) {
+  std::vector<int> sl, tok;
+  for (int s = 0; s < (int)need.size(); ++s)
+    if (need[s] > 0) { sl.push_back(s); tok.push_back(need[s]); }
+  SMI_TRY(pages_ensure(L, sl.data(), tok.data(), (int)sl.size(), nullptr));
+  SMI_HIP(hipDeviceSynchronize());
   return SMI_OK;
 }
 
@@ -7180,7 +7205,6 @@ static int debug_kv_check(const smi_llm* L, int layer, int slot, int pos0, int n
 int smi_llm_debug_set_kv(smi_llm* L, int layer, int slot, int pos0, int n, const float* k_host, const float* v_host) {
   { const int rc = debug_kv_check(L, layer, slot, pos0, n); if (rc) return rc; }
   SMI_REQUIRE(k_host && v_host, "smi_llm_debug_set_kv: null argument");
-  SMI_HIP(hipDeviceSynchronize());
   const int nkv = L->cfg.num_kv_heads, f32 = L->cfg.kv_dtype;
   const size_t esz = f32 ? 4 : 2;
   std::vector<unsigned char> buf((size_t)n * kHeadDim * esz);
@@ -7197,8 +7221,10 @@ int smi_llm_debug_set_kv(smi_llm* L, int layer, int slot, int pos0, int n, const
           }
         }
       unsigned char* base = (unsigned char*)kv_layer(L, isv ? L->vcache : L->kcache, layer);
-      const size_t row0 = ((size_t)slot * nkv + kh) * L->cfg.max_positions + pos0;
-      SMI_HIP(hipMemcpy(base + row0 * kHeadDim * esz, buf.data(), buf.size(), hipMemcpyHostToDevice));
+      for (int t = 0, run; t < n; t += run) {   // one copy per run of rows that sit together (paged: per page)
+        const size_t row0 = debug_kv_run(L, slot, kh, pos0 + t, n - t, &run);
+        SMI_HIP(hipMemcpy(base + row0 * kHeadDim * esz, buf.data() + (size_t)t * kHeadDim * esz, (size_t)run * kHeadDim * esz, hipMemcpyHostToDevice));
+      }
     }
   return SMI_OK;
 }
@@ -7207,15 +7233,16 @@ int smi_llm_debug_set_kv(smi_llm* L, int layer, int slot, int pos0, int n, const
 int smi_llm_debug_get_kv(smi_llm* L, int layer, int slot, int pos0, int n, float* k_host, float* v_host) {
   { const int rc = debug_kv_check(L, layer, slot, pos0, n); if (rc) return rc; }
   SMI_REQUIRE(k_host && v_host, "smi_llm_debug_get_kv: null argument");
-  SMI_HIP(hipDeviceSynchronize());
   const int nkv = L->cfg.num_kv_heads, f32 = L->cfg.kv_dtype;
   const size_t esz = f32 ? 4 : 2;
   std::vector<unsigned char> buf((size_t)n * kHeadDim * esz);
   for (int isv = 0; isv < 2; ++isv)
     for (int kh = 0; kh < nkv; ++kh) {
       const unsigned char* base = (const unsigned char*)kv_layer(L, isv ? L->vcache : L->kcache, layer);
-      const size_t row0 = ((size_t)slot * nkv + kh) * L->cfg.max_positions + pos0;
-      SMI_HIP(hipMemcpy(buf.data(), base + row0 * kHeadDim * esz, buf.size(), hipMemcpyDeviceToHost));
+      for (int t = 0, run; t < n; t += run) {
+        const size_t row0 = debug_kv_run(L, slot, kh, pos0 + t, n - t, &run);
+        SMI_HIP(hipMemcpy(buf.data() + (size_t)t * kHeadDim * esz, base + row0 * kHeadDim * esz, (size_t)run * kHeadDim * esz, hipMemcpyDeviceToHost));
+      }
       for (int t = 0; t < n; ++t)
         for (int i = 0; i < kHeadDim; ++i) {
           const int d = isv ? i : (i >> 1) + 32 * (i & 1);
@@ -7228,6 +7255,16 @@ int smi_llm_debug_get_kv(smi_llm* L, int layer, int slot, int pos0, int n, float
   return SMI_OK;
 }
 
+// The pages `slot` holds, in position order, from the host mirror of the page table: *n = their count (0: contiguous cache, or a
+// slot without pages), the first min(*n, cap) in out.
+int smi_llm_debug_page_table(smi_llm* L, int slot, int32_t* out, int cap, int32_t* n) {
+  SMI_REQUIRE(L && n && cap >= 0 && (out || cap == 0), "smi_llm_debug_page_table: bad argument");
+  SMI_REQUIRE(slot >= 0 && slot < L->cfg.max_slots, "smi_llm_debug_page_table: slot %d", slot);
+  *n = L->paged ? L->slot_pages[slot] : 0;
+  for (int i = 0; i < *n && i < cap; ++i) out[i] = L->hptab[(size_t)slot * L->ppslot + i];
+  return SMI_OK;
+}
+
 // rows_host: M (slot, pos) pairs; hidden_host [M][hidden] fp32 = the residual rows entering `layer`.  Runs that layer's kernels up
 // to and including `stage` (0 QKV + bias + RoPE + KV append, 1 attention, 2 o_proj + residual, 3 gate_up + SwiGLU, 4 down_proj +
 // residual) for those rows through launch_one; results are then read with smi_llm_debug_read / smi_llm_debug_get_kv.  Ends the
@@ -7235,10 +7272,10 @@ int smi_llm_debug_get_kv(smi_llm* L, int layer, int slot, int pos0, int n, float
 int smi_llm_debug_layer(smi_llm* L, int layer, int M, const int32_t* rows_host, const float* hidden_host, int stage) {
   SMI_REQUIRE(L && rows_host && hidden_host && M >= 1 && M <= kMaxRows, "smi_llm_debug_layer: bad argument");
   SMI_REQUIRE(layer >= 0 && layer < L->cfg.num_layers && stage >= 0 && stage <= 4, "smi_llm_debug_layer: layer %d stage %d", layer, stage);
-  SMI_REQUIRE(!L->paged, "smi_llm_debug_layer needs a contiguous KV cache");
   SMI_HIP(hipDeviceSynchronize());
   graphs_flush(L);
   std::vector<RowDesc> rows(kMaxRows, RowDesc{0, 0, 0, 0});
+  std::vector<int> need(L->cfg.max_slots, 0);   // paged cache: positions each slot must have pages for
   int maxpos = 0, ident = 1;
   for (int m = 0; m < M; ++m) {
     const int sl = rows_host[2 * m], ps = rows_host[2 * m + 1];
@@ -7246,7 +7283,9 @@ int smi_llm_debug_layer(smi_llm* L, int layer, int M, const int32_t* rows_host, 
     rows[m] = RowDesc{sl, ps, 0, 0};
     maxpos = ps > maxpos ? ps : maxpos;
     ident &= sl == m;
+    need[sl] = ps + 1 > need[sl] ? ps + 1 : need[sl];
   }
+  SMI_TRY(debug_pages(L, need));
   SMI_HIP(hipMemcpy(L->rows, rows.data(), rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice));
   L->B = M; L->identity_slots = ident; L->session = 0; L->started = 0;
   L->attn_seg = segs_for(maxpos + 1);
@@ -7276,7 +7315,6 @@ int smi_llm_debug_prefill_layer(smi_llm* L, int layer, int stage, int n_seq, con
   SMI_REQUIRE(family == PF_GROUPED || family == PF_PGEMM, "smi_llm_debug_prefill_layer: family %d", family);
   SMI_REQUIRE(layer >= 0 && layer < L->cfg.num_layers && stage >= 0 && stage <= 5, "smi_llm_debug_prefill_layer: layer %d stage %d", layer, stage);
   SMI_REQUIRE(stage == 0 || layer < L->cfg.num_layers - 1, "smi_llm_debug_prefill_layer: the last layer of a prompt pass ends with its K/V append (stage 0 only)");
-  SMI_REQUIRE(!L->paged, "smi_llm_debug_prefill_layer needs a contiguous KV cache");
   SMI_REQUIRE(!L->exact, "smi_llm_debug_prefill_layer: the exact-weights mode has no prompt pass of its own (it runs chunks)");
   long long total = 0;
   int longest = 0;
@@ -7295,6 +7333,11 @@ int smi_llm_debug_prefill_layer(smi_llm* L, int layer, int stage, int n_seq, con
   L->B = 0; L->session = 0; L->started = 0; L->dbg_pf_rows = 0;
   L->attn_seg = segs_for(longest);
   int rc;
+  {
+    std::vector<int> need(L->cfg.max_slots, 0);
+    for (int b = 0; b < n_seq; ++b) need[seq_host[3 * b]] = seq_host[3 * b + 1] + seq_host[3 * b + 2];
+    if ((rc = debug_pages(L, need))) return rc;
+  }
   if ((rc = ensure_plan(L, (size_t)M))) return rc;
   if ((rc = ensure_big(L, M))) return rc;
   L->host_rows.clear();

@@ -286,6 +286,7 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_head": (_I, [_VP, _I, _P(HeadIO)]),
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
+    "smi_llm_debug_page_table": (_I, [_VP, _I, _P(C.c_int32), _I, _P(C.c_int32)]),
     "smi_llm_debug_layer": (_I, [_VP, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),
     "smi_llm_debug_prefill_layer": (_I, [_VP, _I, _I, _I, _P(C.c_int32), _P(C.c_float), _I]),
     "smi_llm_pf_tiles": (_I, [_P(C.c_int32), _I, _P(C.c_int32), _I, _P(C.c_int32)]),

@@ -952,6 +952,16 @@ class SparkLLM:
                         "smi_llm_debug_get_kv")
         return k, v
 
+    def debug_page_table(self, slot: int) -> np.ndarray:
+        """The pages ``slot`` holds, in position order (the host's page table; empty on a contiguous cache)."""
+        self._need_diag("debug_page_table")
+        n = C.c_int32(0)
+        ip = C.POINTER(C.c_int32)
+        self._lib.check(self._lib.smi_llm_debug_page_table(self._h, slot, None, 0, C.byref(n)), "smi_llm_debug_page_table")
+        out = np.zeros(n.value, dtype=np.int32)
+        self._lib.check(self._lib.smi_llm_debug_page_table(self._h, slot, out.ctypes.data_as(ip), out.size, C.byref(n)), "smi_llm_debug_page_table")
+        return out
+
     @staticmethod
     def _from_triples(raw: np.ndarray, K: int, M: int) -> np.ndarray:
         """[K / 32][3][4][M][8] bf16 (hi, mid, lo planes of an exact split) -> (M, K) fp32, k = 32 * tile + 8 * k8 + e."""
@@ -973,7 +983,8 @@ class SparkLLM:
         assert hidden.shape == (M, c.hidden_size)
         self._lib.check(self._lib.smi_llm_debug_layer(self._h, layer, M, rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                                       hidden.ctypes.data_as(C.POINTER(C.c_float)), stage), "smi_llm_debug_layer")
-        fused_one = stage == 2 and M == 1 and int(rows[0, 0]) == 0 and self.debug_fused_o()   # (fuse_o_now: the row sits in slot 0)
+        # (fuse_o_now: the row sits in slot 0 and its keys fit one attention segment, kAttnSeg = 1024)
+        fused_one = stage == 2 and M == 1 and int(rows[0, 0]) == 0 and int(rows[0, 1]) < 1024 and self.debug_fused_o()
         return self._stage_outputs(layer, stage, M, [(int(s), int(p), 1) for s, p in rows], (0, 1, 2, 8 if fused_one else 4))
 
     def _stage_outputs(self, layer: int, stage: int, M: int, runs, bufs) -> dict:

@@ -250,8 +250,10 @@ def test_refusals_leave_the_engine_usable(full_llm, engines):
     assert llm.debug_prefill_layer(nl - 1, ok, x, 0)["q"].shape == (65, cfg.num_attention_heads, 64)
     paged = _make(full_llm, "f32", kv_page_tokens=64, kv_pages=32)
     try:
+        # a paged cache is no refusal any more (tests/test_llm_paged_ops_gpu.py): the slot gets its pages and the bits are the same
+        assert np.array_equal(paged.debug_prefill_layer(0, ok, x, 2)["h"], want)
         with pytest.raises(SparkMIError):
-            paged.debug_prefill_layer(0, ok, x, 0)
+            paged.debug_prefill_layer(0, [(1, 0, 65), (8, 0, 65)], np.concatenate([x, x]), 0)   # slot beyond max_slots
         prompt = np.random.default_rng(10).integers(0, cfg.vocab_size, size=9).tolist()
         assert len(paged.generate_ids([prompt], 2)[0]) == 2                # the paged engine still generates
     finally:
