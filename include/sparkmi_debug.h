@@ -239,7 +239,7 @@ int smi_conv_form_get(int index, smi_conv_form* out);
  * ConvTranspose1d: S > 1, pad = (K - S) / 2, L_out = L * S.  L is the longest row's INPUT length and the row stride of X;
  * Y / Ys / R are [B][Cout][L_out].  gemv = 1: the per-utterance vector projection (k_gemv1; K = 1, L = 1, X [B][Cin],
  * Y [B][Cout], act none / ReLU (3) / sigmoid (4)); c1 = 1: the one-output-channel 7-tap conv (k_conv_c1) -- the two forms the
- * callers of make_conv_w select themselves.  plan_frames > 0: the plan is that of ONE row of plan_frames input positions in a
+ * callers of make_conv select themselves.  plan_frames > 0: the plan is that of ONE row of plan_frames input positions in a
  * call whose longest row has plan_ext_frames = L (PlanShape).  act: 0 none, 1 GELU, 2 tanh, 3 ReLU. */
 typedef struct smi_conv_case {
   int32_t Cout, Cin, K, dil, S, pad, istr, act;
@@ -258,7 +258,7 @@ typedef struct smi_conv_plan_info {
   int64_t lds_bytes;
   int64_t plan_blocks; /* blocks of the grid the plan was chosen for */
 } smi_conv_plan_info;
-/* what make_conv_w builds for the case: host only, no GPU call */
+/* what make_conv builds for the case: host only, no GPU call */
 int smi_conv_plan(const smi_conv_case* c, smi_conv_plan_info* out);
 /* device operands of smi_conv_run; null = absent.  R may alias Y.  bbias [B][Cout]; bias / gamma / beta / alpha [Cout] */
 typedef struct smi_conv_operands {
@@ -276,7 +276,7 @@ typedef struct smi_conv_operands {
   float out_scale;     /* 1 or 3 */
   int32_t reserved;
 } smi_conv_operands;
-/* Builds the launch with make_conv_w, applies the staging limits the vocoder and the encoder apply to their launch lists, runs
+/* Builds the launch with make_conv, applies the staging limits the vocoder and the encoder apply to their launch lists, runs
  * it, synchronises and reports the plan.  lens_host [B] valid INPUT lengths (null: all L); a strided conv's valid output
  * lengths are derived from them.  X must be readable for at least Cout floats (absent epilogue operands read it). */
 int smi_conv_run(const smi_conv_case* c, const smi_conv_operands* io, const int32_t* lens_host, smi_conv_plan_info* plan, void* stream);

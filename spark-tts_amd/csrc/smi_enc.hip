@@ -815,15 +815,20 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::map<
     P.push_back(L);
   };
   // Linear / Conv1d on [C][T] activations: input lengths of kind kin, output lengths of kind kout; row strides are the span's
-  // extents, the plan is the plan row's own output length.  Returns the launch for epilogue tweaks.
-  auto conv = [&](const std::string& name, const std::string& wname, const std::string& bname, int Cout, int Cin, int K, int dil, int pad,
-                  const float* X, int xstride, float* Y, const float* R, int ystride, int kin, int kout, int act, int istr) -> Launch& {
-    const PlanShape ps{0, 0, sp.plan.v[kout]};
-    P.push_back(make_conv_w(name, ent(h, wname), bname.empty() ? nullptr : ent(h, bname), Cout, Cin, K, dil, 1, pad, X, xstride, bs, Y,
-                            nullptr, nullptr, R, ystride, bs, len(kin), sp.B, E.v[kout], act, istr, kin == kout ? nullptr : len(kout),
-                            ent_is_bf(h, wname), &ps));
-    return P.back();
+  // extents, the plan is the plan row's own output length.  spec: the layer's ConvSpec, for a caller that names further epilogue
+  // operands; conv: the launch of that spec as it stands.
+  PlanShape kps[LK_COUNT];   // the plan row's length of every kind, as given
+  for (int k = 0; k < LK_COUNT; ++k) kps[k] = PlanShape{0, 0, sp.plan.v[k]};
+  auto spec = [&](const std::string& name, const std::string& wname, const std::string& bname, int Cout, int Cin, int K, int dil, int pad,
+                  const float* X, int xstride, float* Y, const float* R, int ystride, int kin, int kout, int act, int istr) {
+    ConvSpec s;
+    s.name = name; s.W = ent(h, wname); s.bias = bname.empty() ? nullptr : ent(h, bname); s.bf = ent_is_bf(h, wname);
+    s.Cout = Cout; s.Cin = Cin; s.K = K; s.dil = dil; s.pad = pad; s.istr = istr; s.act = act;
+    s.X = X; s.xstride = xstride; s.xb = bs; s.Y = Y; s.R = R; s.ystride = ystride; s.yb = bs;
+    s.lens = len(kin); s.olens = kin == kout ? nullptr : len(kout); s.B = sp.B; s.Lmax = E.v[kout]; s.ps = &kps[kout];
+    return s;
   };
+  auto conv = [&](auto&&... a) { P.push_back(make_conv(spec(a...))); };
   // attention of every row over its own kq queries and kk keys; the score rows in LDS are sized by the span's longest row
   auto mha = [&](const std::string& name, const float* Q, int qs, const float* K, int ks, const float* V, int vs, float* O, int os,
                  int heads, int kq, int kk) {
@@ -936,8 +941,9 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::map<
         const std::string b = p + ".convnext." + std::to_string(j);
         lnorm(b + ".dwconv+norm", b + ".norm", ent(h, b + ".dwconv.weight"), ent(h, b + ".dwconv.bias"), e2, e0, D, kT, 1e-6f, 0, 0);
         conv(b + ".pwconv1", b + ".pwconv1.weight", b + ".pwconv1.bias", EI, D, 1, 1, 0, e0, T, ew, nullptr, T, kT, kT, ACT_GELU, 1);
-        Launch& L = conv(b + ".pwconv2", b + ".pwconv2.weight", b + ".pwconv2.bias", D, EI, 1, 1, 0, ew, T, e2, e2, T, kT, kT, ACT_NONE, 1);
-        L.cp.gamma = ent(h, b + ".gamma");
+        ConvSpec s = spec(b + ".pwconv2", b + ".pwconv2.weight", b + ".pwconv2.bias", D, EI, 1, 1, 0, ew, T, e2, e2, T, kT, kT, ACT_NONE, 1);
+        s.gamma = ent(h, b + ".gamma");
+        P.push_back(make_conv(s));
       }
       lnorm(p + ".final_layer_norm", p + ".final_layer_norm", nullptr, nullptr, e2, e1, D, kT, 1e-6f, 0, triple_out);
       in = e1; cin = D;
@@ -980,26 +986,26 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::map<
     const int C = c.ecapa_channels, W = C / 8;
     const std::string se = "speaker_encoder.speaker_encoder";
     float *ea = B("ec_a"), *eb = B("ec_b"), *ec = B("ec_c"), *ecat = B("ec_cat"), *elat = B("ec_lat"), *evec = B("ec_vec");
-    auto crb = [&](const std::string& name, const std::string& p, int co, int ci, int k, int dil, int pad, const float* X, const float* X2,
-                   float* Y) {
-      Launch& L = conv(name, p + ".conv.weight", p + ".conv.bias", co, ci, k, dil, pad, X, Tm, Y, nullptr, Tm, LK_TM, LK_TM, ACT_RELU, 1);
-      L.cp.gamma = ent(h, "bnscale:" + p + ".bn"); L.cp.beta = ent(h, "bnshift:" + p + ".bn"); L.cp.X2 = X2;
+    // conv `pfx`(X + X2) -> ReLU -> BatchNorm `bn`
+    auto crb = [&](const std::string& name, const std::string& pfx, const std::string& bn, int co, int ci, int k, int dil, int pad, const float* X,
+                   const float* X2, float* Y) {
+      ConvSpec s = spec(name, pfx + ".weight", pfx + ".bias", co, ci, k, dil, pad, X, Tm, Y, nullptr, Tm, LK_TM, LK_TM, ACT_RELU, 1);
+      s.gamma = ent(h, "bnscale:" + bn); s.beta = ent(h, "bnshift:" + bn); s.X2 = X2;
+      P.push_back(make_conv(s));
     };
-    crb(se + ".layer1", se + ".layer1", C, c.num_mels, 5, 1, 2, mel, nullptr, ea);
+    crb(se + ".layer1", se + ".layer1.conv", se + ".layer1.bn", C, c.num_mels, 5, 1, 2, mel, nullptr, ea);
     const float* xin = ea;
     for (int li = 2; li <= 4; ++li) {
       const std::string b = se + ".layer" + std::to_string(li) + ".se_res2block";
       const int dil = li;
       float* y0 = eb;      // after the first 1x1
       float* y1 = ec;      // Res2 output (cat of the 8 branches)
-      crb(b + ".0", b + ".0", C, C, 1, 1, 0, xin, nullptr, y0);
+      crb(b + ".0", b + ".0.conv", b + ".0.bn", C, C, 1, 1, 0, xin, nullptr, y0);
       for (int j = 0; j < 7; ++j) {
         const std::string cj = b + ".1.convs." + std::to_string(j);
         // sp = conv(out_{j-1} + spx[j]) -> relu -> bn  (ecapa_tdnn.py:50-58); branch j reads slice j of y0, writes slice j of y1
-        Launch& L = conv(cj, cj + ".weight", cj + ".bias", W, W, 3, dil, dil, y0 + (size_t)j * W * Tm, Tm, y1 + (size_t)j * W * Tm, nullptr, Tm,
-                         LK_TM, LK_TM, ACT_RELU, 1);
-        L.cp.gamma = ent(h, "bnscale:" + b + ".1.bns." + std::to_string(j)); L.cp.beta = ent(h, "bnshift:" + b + ".1.bns." + std::to_string(j));
-        if (j >= 1) L.cp.X2 = y1 + (size_t)(j - 1) * W * Tm;
+        crb(cj, cj, b + ".1.bns." + std::to_string(j), W, W, 3, dil, dil, y0 + (size_t)j * W * Tm, j >= 1 ? y1 + (size_t)(j - 1) * W * Tm : nullptr,
+            y1 + (size_t)j * W * Tm);
       }
       {
         const float* src = y0 + (size_t)7 * W * Tm;
@@ -1008,20 +1014,19 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::map<
           hipLaunchKernelGGL(k_copy2d, g, bl, l, s, src, Tm, bs, dst, Tm, bs, W, Tmlen);
         });
       }
-      crb(b + ".2", b + ".2", C, C, 1, 1, 0, y1, nullptr, y0);
+      crb(b + ".2", b + ".2.conv", b + ".2.bn", C, C, 1, 1, 0, y1, nullptr, y0);
       float *mean = evec, *s1 = evec + C, *s2 = evec + C + 128;
       closure(b + ".3.mean", 1.0 * C * Tm, dim3((C + 3) / 4), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
         hipLaunchKernelGGL(k_rowmean, g, bl, l, s, y0, C, Tmlen, Tm, mean, bs);
       });
       // the two vector projections: one vector per row (k_gemv1: block y is the row)
-      const int* len1 = len(LK_ONE);
-      const PlanShape ps1{0, 0, 1};
-      P.push_back(make_conv_w(b + ".3.linear1", ent(h, b + ".3.linear1.weight"), ent(h, b + ".3.linear1.bias"), 128, C, 1, 1, 1, 0, mean, 1,
-                              bs, s1, nullptr, nullptr, nullptr, 1, bs, len1, sp.B, 1, ACT_RELU, 1, nullptr, false, &ps1));
-      P.back().gemv = true; P.back().grid = dim3(4, nB);
-      P.push_back(make_conv_w(b + ".3.linear2", ent(h, b + ".3.linear2.weight"), ent(h, b + ".3.linear2.bias"), C, 128, 1, 1, 1, 0, s1, 1,
-                              bs, s2, nullptr, nullptr, nullptr, 1, bs, len1, sp.B, 1, ACT_SIGMOID, 1, nullptr, false, &ps1));
-      P.back().gemv = true; P.back().grid = dim3((C + 31) / 32, nB);
+      auto gemv = [&](const std::string& l, int co, int ci, const float* X, float* Y, int act) {
+        ConvSpec s = spec(l, l + ".weight", l + ".bias", co, ci, 1, 1, 0, X, 1, Y, nullptr, 1, LK_ONE, LK_ONE, act, 1);
+        s.want = CONV_GEMV;
+        P.push_back(make_conv(s));
+      };
+      gemv(b + ".3.linear1", 128, C, mean, s1, ACT_RELU);
+      gemv(b + ".3.linear2", C, 128, s1, s2, ACT_SIGMOID);
       float* outl = ecat + (size_t)(li - 2) * C * Tm;
       const float* xi = xin;
       closure(b + ".3.scale+res", 2.0 * C * Tm, dim3((Tm + 255) / 256, C), 256, 0, [=](hipStream_t s, dim3 g, dim3 bl, size_t l) {
@@ -1076,11 +1081,8 @@ int enc_program(smi_enc* h, const EncSpan& sp, std::vector<Launch>& P, std::map<
   }
 
   for (const Launch& L : P) {
-    if (L.kind == 0) {
-      SMI_REQUIRE(L.cp.W, "smi_enc_forward: arena entry for %s not found", L.name.c_str());
-      SMI_REQUIRE(L.lds <= 64 * 1024, "smi_enc_forward: %s needs %zu bytes of LDS", L.name.c_str(), L.lds);
-      SMI_REQUIRE(L.cp.xw <= 192 && (L.chg == 1 || L.cp.xw <= 64), "smi_enc_forward: %s stages %d columns", L.name.c_str(), L.cp.xw);
-    }
+    int rc = L.kind == 0 ? check_conv(L, "smi_enc_forward") : SMI_OK;
+    if (rc) return rc;
     if (L.kind == 1) SMI_REQUIRE(L.lp.w && L.lp.bsh && L.cpt <= 32, "smi_enc_forward: LayerNorm %s: missing weights or too many channels", L.name.c_str());
   }
   return SMI_OK;
@@ -1354,7 +1356,7 @@ int dbg_launch(const smi_enc::Ws& W, const char* who, int index, char* name, int
   const Launch& L = W.prog[index];
   if (name && cap > 0) { strncpy(name, L.name.c_str(), (size_t)cap - 1); name[cap - 1] = 0; }
   info[0] = L.kind; info[1] = (int32_t)L.grid.x; info[2] = (int32_t)L.grid.y; info[3] = (int32_t)L.grid.z;
-  info[4] = L.kind == 0 ? 64 * L.nwv : L.blk;
+  info[4] = L.blk;
   info[5] = (int32_t)L.lds;
   info[6] = L.kind == 1 ? dwln_form(L.cpt) : 0;
   info[7] = 0;

@@ -123,33 +123,12 @@ inline int pad32(int c) { return (c + 31) / 32 * 32; }
 // out[q*S + r] += W[ci][co][j] * x[ci][(q*S + r + pad - j)/S] for j == (r + pad) mod S.
 ConvGeom conv_geom(int Cout, int Cin, int K, int dil, int pad, int S, bool bf = false);
 
-struct Launch {
-  int kind;          // 0 conv, 1 dwln, 2 codebook, 3 fsq, 4 zero-tail, 5 fused ResidualUnit, 9 closure (fn)
-  std::function<void(hipStream_t)> fn;
-  std::string name;
-  double flops;
-  ConvP cp; int qb; bool ks; int chg; int nwv = 4; bool gemv; bool bf = false; bool c1 = false; int c1_len = 0; dim3 grid; size_t lds;
-  int blk = 0;       // kind 9: threads per block of the closure's launch (with grid and lds: the record the diagnostics report)
-  int tph = 0;       // k_convbT: output phases per block of a transposed conv (0: k_convb, one phase per block)
-  long long plan_blocks = 0;   // blocks of the grid the plan was chosen for, where that is not the launch's own (PlanShape); 0: the launch's
-  ResP rp; int res_nwv = 0;   // kind 5: a fused ResidualUnit (k_resunit) with res_nwv waves per block
-  LnP lp; int cpt;
-  // small kernels keep their args here
-  const int64_t* sem; int semstride; const float* cb; int D, cbsize; float* Z; int zstride; long long zb;
-  FsqP fp; int B;
-  float* wav; int wstride, hop, tmaxhop;
-  const int* lens;
-};
-
-// blocks of the grid a launch's plan was made for: the small-grid kernel forms (WPF, WALL) are part of the plan
-inline long long plan_grid_blocks(const Launch& L) { return L.plan_blocks ? L.plan_blocks : (long long)L.grid.x * L.grid.y * L.grid.z; }
-
 // ------------------------------------------------------------------------------------------
 // The kernel form of a conv launch: which instantiation of k_conv / k_convb / k_convbT / k_conv_c1 / k_gemv1 runs it.
-// conv_form() is the ONE place where a launch's fields (and, in the diagnostics build, the SPARKMI_* A/B switches) become
-// template arguments; kConvForms is the ONE list of instantiations.  run_launch() looks the form up in the table, and
-// the diagnostics entry points (include/sparkmi_debug.h) enumerate the same table and report the same records, so the
-// list of forms a test covers and the launches cannot diverge.
+// kConvForms (smi_net.hip) is the ONE list of instantiations; make_conv() is the ONE place where a layer, a plan shape and, in
+// the diagnostics build, the SPARKMI_* A/B switches become an index into it.  run_launch() dispatches on that index, and the
+// diagnostics entry points (include/sparkmi_debug.h) enumerate the same table and copy the same record, so the list of forms a
+// test covers and the launches cannot diverge.
 // ------------------------------------------------------------------------------------------
 enum { CONV_K_CONV = 0, CONV_K_CONVB = 1, CONV_K_CONVBT = 2, CONV_K_C1 = 3, CONV_K_GEMV = 4 };
 struct ConvForm {
@@ -168,12 +147,39 @@ inline bool operator==(const ConvForm& a, const ConvForm& b) {
          a.wall == b.wall && a.tph == b.tph;
 }
 
-ConvForm conv_form(const Launch& L);
-
 // the table of instantiations the library carries (kConvForms, smi_net.hip), in the enumeration order of smi_conv_form_get
 int conv_form_count();
 const ConvForm& conv_form_at(int index);
 int conv_form_index(const ConvForm& f);   // -1: no such instantiation
+
+// What make_conv() chose for a conv launch from its PLAN shape.  plan_signature() compares the whole record, so a choice added
+// here separates rows without further ado; in return the record holds ints only, each a function of the layer and the plan
+// shape and never of the extent (the grid's x and z and plan_blocks stand in the Launch).
+struct ConvPlan {
+  int form;                     // index in kConvForms (-1: no instantiation; check_conv refuses the launch)
+  int qb, ks, chg, nwv, tph;    // the MFMA tile choices; a gemv / c1 launch keeps those of its layer (run boundaries depend on them)
+  int xw;                       // staged row width (= cp.xw)
+  int tiles_y;                  // grid.y of an MFMA form (0: gemv and c1 size their grids from the extent alone)
+  int small;                    // an MFMA form planned on at most 512 blocks (WPF and WALL depend on it)
+};
+
+struct Launch {
+  int kind;          // 0 conv, 1 dwln, 2 codebook, 3 fsq, 4 zero-tail, 5 fused ResidualUnit, 9 closure (fn)
+  std::function<void(hipStream_t)> fn;
+  std::string name;
+  double flops;
+  dim3 grid; size_t lds;
+  int blk = 0;       // kinds 0 and 9: threads per block (with grid and lds: what the launch runs with and the diagnostics report)
+  ConvP cp; ConvPlan plan;     // kind 0, as make_conv() left them
+  long long plan_blocks = 0;   // kind 0: blocks of the grid the plan was chosen for (with a PlanShape: not the launch's own grid)
+  ResP rp; int res_nwv = 0;   // kind 5: a fused ResidualUnit (k_resunit) with res_nwv waves per block
+  LnP lp; int cpt;
+  // small kernels keep their args here
+  const int64_t* sem; int semstride; const float* cb; int D, cbsize; float* Z; int zstride; long long zb;
+  FsqP fp; int B;
+  float* wav; int wstride, hop, tmaxhop;
+  const int* lens;
+};
 
 // the k_dwln instantiation (channels per thread) that covers a layer of ceil(C / 32) channels per thread
 inline int dwln_form(int cpt) { return cpt <= 2 ? 2 : (cpt <= 4 ? 4 : (cpt <= 12 ? 12 : (cpt <= 16 ? 16 : 32))); }
@@ -191,15 +197,28 @@ struct PlanShape {
   int len(int Lmax) const { return plan_len > 0 ? plan_len : (Lmax % ext_frames == 0 ? Lmax / ext_frames * frames : Lmax); }
 };
 
-// Build one conv launch.  X/Y strides are in floats; Lmax = padded INPUT length (time units).  The call shape (B, Lmax) plays two
-// roles: the PLAN shape picks tile width, channel split, wave count, chunk size and kernel form -- the summation order -- and the
-// EXTENT sizes the grid.  With `ps` the plan is that of ps's one row and only the extent comes from (B, Lmax): blocks beyond a
-// row's own length exit, so every row carries the bits of its plan shape.
-Launch make_conv_w(const std::string& name, const float* W, const float* bias,
-                   int Cout, int Cin, int K, int dil, int S, int pad, const float* X, int xstride, long long xb,
-                   float* Y, float* Ys, const float* alpha, const float* R, int ystride, long long yb,
-                   const int* lens, int B, int Lmax, int act, int istr = 1, const int* olens = nullptr, bool bf = false,
-                   const PlanShape* ps = nullptr);
+// One conv launch, field by field.  Strides are in floats; Lmax = padded OUTPUT positions per phase (the input length of a
+// stride-1 or transposed conv).  The call shape (B, Lmax) plays two roles: the PLAN shape picks tile width, channel split, wave
+// count, chunk size and kernel form -- the summation order -- and the EXTENT sizes the grid.  With `ps` the plan is that of ps's
+// one row and only the extent comes from (B, Lmax): blocks beyond a row's own length exit, so every row carries the bits of its
+// plan shape.
+enum { CONV_MFMA = 0, CONV_GEMV = 1, CONV_C1 = 2 };
+struct ConvSpec {
+  std::string name;
+  int Cout = 0, Cin = 0, K = 1, dil = 1, S = 1, pad = 0, istr = 1;   // S > 1: ConvTranspose1d; istr > 1: strided Conv1d
+  bool bf = false;        // the weights are two bf16 planes (PACK_CONV_B / PACK_CONVT_B): the layer runs on k_convb / k_convbT
+  const float* W = nullptr; const float* bias = nullptr;
+  const float* X = nullptr; const float* X2 = nullptr; int xstride = 0; long long xb = 0;
+  float* Y = nullptr; float* Ys = nullptr; const float* alpha = nullptr; const float* R = nullptr; int ystride = 0; long long yb = 0;
+  const int* lens = nullptr; const int* olens = nullptr; int B = 1, Lmax = 1, act = ACT_NONE;
+  const float* bbias = nullptr; const float* gamma = nullptr; const float* beta = nullptr; float out_scale = 1.0f;
+  int want = CONV_MFMA;   // CONV_GEMV: one vector per utterance (k_gemv1); CONV_C1: k_conv_c1 where the layer qualifies, else as CONV_MFMA
+  const PlanShape* ps = nullptr;
+};
+// The launch as it runs: form, grid, block, LDS, xw and plan_blocks are final; nobody assigns a field of it afterwards.
+Launch make_conv(const ConvSpec& s);
+// What a conv launch must satisfy before it runs: weights, a kernel form, the LDS limit, the staged width, k_convbT's epilogue.
+int check_conv(const Launch& L, const char* who);
 
 // Every choice a launch list makes from its plan shape, launch by launch: two rows may share a launch sequence when these agree.
 std::vector<long long> plan_signature(const std::vector<Launch>& P);

@@ -3,6 +3,7 @@
 // ResidualUnit, depthwise-conv + LayerNorm, the per-utterance GEMV, codebook / FSQ lookups, the table of their instantiations
 // and the builders that turn a layer into a launch.  The clients see smi_net.h; every launch of these kernels is in this file.
 #include "smi_net.h"
+#include <type_traits>
 
 namespace smi_net __attribute__((visibility("hidden"))) {
 namespace {
@@ -1176,60 +1177,17 @@ ConvGeom conv_geom(int Cout, int Cin, int K, int dil, int pad, int S, bool bf) {
   return g;
 }
 
-ConvForm conv_form(const Launch& L) {
-  ConvForm f{CONV_K_CONV, L.qb == 1 ? 1 : 2, 0, 1, 2, 4, 0, 0, 0};
-  if (L.gemv) return ConvForm{CONV_K_GEMV, 0, 0, 0, 0, 4, 0, 0, 0};
-  if (L.c1) return ConvForm{CONV_K_C1, 0, 0, 0, 0, 4, 0, 0, 7};   // one output channel, 7 taps: a thread per output sample (k_conv_c1)
-  if (L.bf && L.tph) return ConvForm{CONV_K_CONVBT, 1, 0, 2, 1, 4, 0, 0, L.tph == 4 ? 4 : 5};   // transposed conv, several output phases per block
-  if (L.bf) {            // bf16-split matrix pipe (k_convb): weights packed as two bf16 planes
-    f.kernel = CONV_K_CONVB;
-    const bool wide = L.cp.xw > 64;
-    if (L.chg == 4) {
-      // one tap, channels split over the waves, at most two blocks per CU: the chunk's weights are requested one chunk ahead (WPF)
-      const bool wpf = L.ks && L.cp.S == 1 && L.cp.ntaps[0] == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWPF");
-      f.chg = 4; f.nc = 1; f.ks = L.ks; f.wpf = wpf;
-    } else if (L.ks) {
-      // several taps on a grid of about a block per CU: all taps' weights of a chunk requested together (WALL)
-      int mt = 0;
-      for (int r = 0; r < L.cp.S; ++r) mt = L.cp.ntaps[r] > mt ? L.cp.ntaps[r] : mt;
-      // (measured at one / two utterances, 150 frames: 7-tap convs 71 -> 62 us at 456 blocks but 101 -> 115 at 912; the first transposed conv,
-      // 2 taps per phase, 85 -> 129 us: stride-1 layers with four taps or more on at most two blocks per CU)
-      const bool wall = L.chg == 2 && mt >= 4 && L.cp.S == 1 && plan_grid_blocks(L) <= 512 && !smi_env("SPARKMI_CB_NOWALL");
-      f.ks = 1; f.chg = 2; f.wall = wall; f.nc = (f.qb == 1 && !wide) ? 1 : 2;
-    } else if (L.chg == 2) {    // few taps per phase, rows wider than 64 columns (transposed convs): 64-channel chunks
-      f.chg = 2; f.nc = 2;
-    } else {
-      f.nc = (f.qb == 1 && !wide) ? 1 : 2;
-    }
-    return f;
-  }
-  if (L.chg == 4) {      // 1-tap layers: 128-channel chunks, narrow rows
-    f.chg = 4; f.nc = 1; f.ks = L.ks;
-    // measured (profiles/README.md): pays up to about two blocks per CU, costs beyond (fewer waves fit)
-    f.wpf = L.ks && plan_grid_blocks(L) <= 512;
-  } else if (L.nwv == 3) {      // three output tiles per block (never channel-split)
-    f.nwv = 3; f.nc = L.cp.xw > 128 ? 3 : 2;
-  } else if (L.cp.xw > 128) {   // strided convs: up to 192 staged columns
-    f.nc = 3; f.ks = L.ks;
-  } else {
-    f.ks = L.ks;
-  }
-  return f;
-}
-
 namespace {
+// every launcher takes grid, block and dynamic LDS from the record make_conv() left
 typedef void (*ConvLaunchFn)(const Launch&, hipStream_t);
 template <int QB, bool KS, int CHG, int NC, bool WPF, int NWV>
-void launch_k_conv(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_conv<QB, KS, CHG, NC, WPF, NWV>), L.grid, dim3(64 * NWV), L.lds, st, L.cp); }
+void launch_k_conv(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_conv<QB, KS, CHG, NC, WPF, NWV>), L.grid, dim3(L.blk), L.lds, st, L.cp); }
 template <int QB, bool KS, int CHG, int NC, bool WPF, bool WALL>
-void launch_k_convb(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_convb<QB, KS, CHG, NC, WPF, WALL>), L.grid, dim3(256), L.lds, st, L.cp); }
+void launch_k_convb(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_convb<QB, KS, CHG, NC, WPF, WALL>), L.grid, dim3(L.blk), L.lds, st, L.cp); }
 template <int PH>
-void launch_k_convbT(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_convbT<PH>), L.grid, dim3(256), L.lds, st, L.cp); }
-inline void launch_k_conv_c1(const Launch& L, hipStream_t st) {
-  hipLaunchKernelGGL((k_conv_c1<7>), dim3((L.c1_len + 255) / 256, L.grid.z), dim3(256), (size_t)L.cp.Cin * 7 * 4, st, L.cp);
-}
-inline void launch_k_gemv1(const Launch& L, hipStream_t st) { hipLaunchKernelGGL(k_gemv1, L.grid, dim3(256), 0, st, L.cp); }
-
+void launch_k_convbT(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_convbT<PH>), L.grid, dim3(L.blk), L.lds, st, L.cp); }
+inline void launch_k_conv_c1(const Launch& L, hipStream_t st) { hipLaunchKernelGGL((k_conv_c1<7>), L.grid, dim3(L.blk), L.lds, st, L.cp); }
+inline void launch_k_gemv1(const Launch& L, hipStream_t st) { hipLaunchKernelGGL(k_gemv1, L.grid, dim3(L.blk), L.lds, st, L.cp); }
 
 struct ConvFormEntry { ConvForm form; ConvLaunchFn launch; };
 #define SMI_F_CONV(QB_, KS_, CHG_, NC_, WPF_, NWV_) {{CONV_K_CONV, QB_, KS_, CHG_, NC_, NWV_, WPF_, 0, 0}, launch_k_conv<QB_, KS_, CHG_, NC_, WPF_, NWV_>}
@@ -1274,12 +1232,10 @@ int conv_form_index(const ConvForm& f) {
 
 int run_launch(const Launch& L, hipStream_t st) {
   switch (L.kind) {
-    case 0: {
-      const int fi = conv_form_index(conv_form(L));
-      SMI_REQUIRE(fi >= 0, "%s: no kernel instantiation for this launch plan", L.name.c_str());
-      kConvForms[fi].launch(L, st);
+    case 0:
+      SMI_REQUIRE(L.plan.form >= 0, "%s: no kernel instantiation for this launch plan", L.name.c_str());   // (a list that skipped check_conv)
+      kConvForms[L.plan.form].launch(L, st);
       break;
-    }
     case 1:
       switch (dwln_form(L.cpt)) {
         case 2: hipLaunchKernelGGL(k_dwln<2>, L.grid, dim3(256), 0, st, L.lp); break;
@@ -1310,107 +1266,151 @@ int run_launch(const Launch& L, hipStream_t st) {
   return SMI_OK;
 }
 
-Launch make_conv_w(const std::string& name, const float* W, const float* bias,
-                   int Cout, int Cin, int K, int dil, int S, int pad, const float* X, int xstride, long long xb,
-                   float* Y, float* Ys, const float* alpha, const float* R, int ystride, long long yb,
-                   const int* lens, int B, int Lmax, int act, int istr, const int* olens, bool bf, const PlanShape* ps) {
-  // Lmax = padded OUTPUT positions per phase (= input length for stride-1 convs and transposed convs)
-  // bf: the weights are packed as bf16 planes (PACK_CONV_B / PACK_CONVT_B) and the layer runs on k_convb
+namespace {
+bool env_is(const char* name, char v) { const char* e = smi_env(name); return e && e[0] == v; }
+
+// Where k_conv_c1 can stand in for the MFMA kernels: an exact 7-tap stride-1 conv to ONE channel with bias and activation only,
+// its weights within 48 KiB of LDS (SPARKMI_VOC_C1=0: never, A/B)
+bool c1_eligible(const ConvSpec& s) {
+  return !s.bf && s.Cout == 1 && s.S == 1 && s.istr == 1 && s.K == 7 && !s.X2 && !s.bbias && !s.gamma && !s.beta && !s.R && !s.Ys && s.Y &&
+         s.out_scale == 1.0f && s.Cin * 7 * 4 <= 48 * 1024 && !env_is("SPARKMI_VOC_C1", '0');
+}
+}  // namespace
+
+Launch make_conv(const ConvSpec& s) {
+  const int Cout = s.Cout, Cin = s.Cin, K = s.K, S = s.S, istr = s.istr;
+  const bool bf = s.bf;
   Launch L;
-  L.kind = 0; L.name = name; L.bf = bf;
-  ConvGeom g = conv_geom(Cout, Cin, K, dil, pad, S, bf);
+  L.kind = 0; L.name = s.name;
+  const ConvGeom g = conv_geom(Cout, Cin, K, s.dil, s.pad, S, bf);
   ConvP& p = L.cp;
   memset(&p, 0, sizeof(p));
-  p.X = X; p.W = W; p.bias = bias;
-  p.R = R; p.alpha = alpha; p.Y = Y; p.Ys = Ys; p.lens = lens;
-  p.Cin = Cin; p.CinP = pad8(Cin); p.Cout = Cout; p.S = S; p.act = act;
-  p.xstride = xstride; p.ystride = ystride; p.xb = xb; p.yb = yb;
-  p.out_scale = 1.0f;
-  { const char* e = smi_env("SPARKMI_SNAKE_SINF"); p.fast_sin = bf && !(e && e[0] == '1'); }   // SPARKMI_SNAKE_SINF=1: library sine everywhere (A/B)
-  p.istr = istr; p.olens = olens;
+  p.X = s.X; p.X2 = s.X2; p.W = s.W; p.bias = s.bias; p.bbias = s.bbias; p.gamma = s.gamma; p.beta = s.beta;
+  p.R = s.R; p.alpha = s.alpha; p.Y = s.Y; p.Ys = s.Ys; p.lens = s.lens; p.olens = s.olens;
+  p.Cin = Cin; p.CinP = pad8(Cin); p.Cout = Cout; p.S = S; p.act = s.act;
+  p.xstride = s.xstride; p.ystride = s.ystride; p.xb = s.xb; p.yb = s.yb;
+  p.out_scale = s.out_scale; p.istr = istr; p.halo_l = g.halo_l;
+  p.fast_sin = bf && !env_is("SPARKMI_SNAKE_SINF", '1');   // SPARKMI_SNAKE_SINF=1: library sine everywhere (A/B)
+  int maxtap = 0;
+  double taps = 0;
   for (int r = 0; r < S; ++r) {
     p.ntaps[r] = g.ntaps[r];
     p.wphase[r] = g.wphase[r];
     for (int i = 0; i < g.ntaps[r]; ++i) p.off[r][i] = g.off[r][i];
+    maxtap = g.ntaps[r] > maxtap ? g.ntaps[r] : maxtap;
+    taps += g.ntaps[r];
   }
+  L.flops = 2.0 * Cout * Cin * taps * s.Lmax * s.B;   // all phases together cover S*Lmax outputs
   const int cot = pad32(Cout) / 32;
-  const int eB = B, eL = Lmax;   // the extent; from here to the grid, (B, Lmax) is the plan shape
-  if (ps) { B = 1; Lmax = ps->len(Lmax); }
+  // ---- the plan: from here to the grid, (B, Lmax) is the plan shape; (s.B, s.Lmax) stays the extent
+  int B = s.B, Lmax = s.Lmax;
+  if (s.ps) { B = 1; Lmax = s.ps->len(Lmax); }
   // waves split the input channels when there are few time tiles and many channels
   // 64-column time tiles unless that leaves most CUs idle (short sequences): then 32-column tiles double the blocks
   const long long blocks64 = (long long)((Lmax + 63) / 64) * cot * B * S;
-  const int qb = (Lmax <= 32 || (blocks64 < 256 && smi_env("SPARKMI_QB2") == nullptr)) ? 1 : 2;
+  int qb = (Lmax <= 32 || (blocks64 < 256 && smi_env("SPARKMI_QB2") == nullptr)) ? 1 : 2;
   const int qt = qb * 32, nq = (Lmax + qt - 1) / qt;
   const long long blocks_cosplit = (long long)nq * ((cot + 3) / 4) * B * S;
   // (a partial last group of output tiles just idles its spare waves).  The choice depends on the call's shape
   // (B, longest row): a row is independent of its neighbours and padding bit for bit, and equal to fp32
   // re-association between calls of different shapes.
-  L.ks = blocks_cosplit < 512 && Cin >= 8;
-  L.qb = qb;
-  p.halo_l = g.halo_l;
-  p.xw = (qt - 1) * istr + 1 + g.halo_l + g.halo_r;
+  const bool ks = blocks_cosplit < 512 && Cin >= 8;
+  int xw = (qt - 1) * istr + 1 + g.halo_l + g.halo_r;
   // three-wave blocks where four would leave a wave (and so a SIMD of each CU) without an output tile; measured at
   // 150 frames: 75.0 -> 73.2 ms at B = 32, 21.0 -> 20.5 at B = 8, but 4.66 -> 4.72 at B = 1, hence the grid-size condition
-  L.nwv = (!bf && !L.ks && cot % 3 == 0 && cot % 4 != 0 && blocks_cosplit >= 2048) ? 3 : 4;
-  L.grid = dim3(nq, L.ks ? cot : (cot + L.nwv - 1) / L.nwv, B * S);
-  L.chg = (S == 1 && K == 1 && Cin >= 128 && L.ks) ? 4 : 1;   // K-split 1-tap layers stage 128 channels per chunk
-  if (bf && L.ks && L.chg == 1) L.chg = 2;                     // k_convb: a channel-split wave owns whole 16-channel steps
+  const int nwv = (!bf && !ks && cot % 3 == 0 && cot % 4 != 0 && blocks_cosplit >= 2048) ? 3 : 4;
+  dim3 pg(nq, ks ? cot : (cot + nwv - 1) / nwv, B * S);   // the plan's grid
+  int chg = (S == 1 && K == 1 && Cin >= 128 && ks) ? 4 : 1;   // K-split 1-tap layers stage 128 channels per chunk
+  if (bf && ks && chg == 1) chg = 2;                          // k_convb: a channel-split wave owns whole 16-channel steps
   // k_convb, one output tile per wave, few taps per phase (1x1 convs: 1; transposed convs: 2-3): a 32-channel chunk carries only
   // 6 * taps MFMAs per wave between its two barriers and its staging round trip.  128-channel chunks where the staged row is one
   // 64-column pass (1 tap), 64-channel chunks up to 128 columns (round 4; SPARKMI_CB_CHG=0: 32-channel chunks everywhere, A/B).
   // A 1-tap layer sums its channels in the same order whatever the chunk; a transposed conv's order goes from (32 channels, taps)
   // to (64 channels, taps) -- the choice depends on the layer's shape only, never on the batch.
-  if (bf && !L.ks && istr == 1 && Cin >= 128) {
-    int maxtap = 0;
-    for (int r = 0; r < S; ++r) maxtap = g.ntaps[r] > maxtap ? g.ntaps[r] : maxtap;
-    const char* e = smi_env("SPARKMI_CB_CHG");
-    if (maxtap <= 3 && !(e && e[0] == '0')) L.chg = p.xw <= 64 ? 4 : (p.xw <= 128 ? 2 : 1);
-  }
+  if (bf && !ks && istr == 1 && Cin >= 128 && maxtap <= 3 && !env_is("SPARKMI_CB_CHG", '0')) chg = xw <= 64 ? 4 : (xw <= 128 ? 2 : 1);
   // transposed convs with a grid that still fills the chip with PH phases per block: k_convbT (SPARKMI_CBT=0: off, A/B).  Its
-  // epilogue knows bias, the raw output and the Snake'd output only: check_launches() rejects a program that set anything else
-  // on such a launch after this function returned.
-  if (bf && !L.ks && S > 1 && istr == 1 && Cin >= 64 && olens == nullptr) {
+  // epilogue knows bias, the raw output and the Snake'd output only: a residual or an activation keeps the layer on k_convb, and
+  // check_conv() refuses a k_convbT launch that asks for any other operand.
+  int tph = 0;
+  if (bf && !ks && S > 1 && istr == 1 && Cin >= 64 && s.olens == nullptr && !env_is("SPARKMI_CBT", '0')) {
     const int ph = S % 4 == 0 ? 4 : (S == 5 ? 5 : 0);   // (S = 2: two phases x two column tiles measured level with k_convb -- it stays there)
-    const int qbt = 1;
-    const char* e = smi_env("SPARKMI_CBT");
-    if (ph && !(e && e[0] == '0')) {
-      const int qtt = qbt * 32, nqt = (Lmax + qtt - 1) / qtt;
-      const int xwt = qtt + g.halo_l + g.halo_r;
-      // (eight blocks per CU and more: at 900 blocks the stride-5 layer of an 8-row batch lost 0.40 -> 0.48 ms, at 3000+ every layer gained)
-      if ((long long)nqt * ((cot + 3) / 4) * B * (S / ph) >= 2048 && xwt <= 64 && !R && act == ACT_NONE) {
-        L.tph = ph; L.qb = qbt; L.chg = 2;
-        p.xw = xwt;
-        L.grid = dim3(nqt, (cot + 3) / 4, B * (S / ph));
-        L.lds = (size_t)2 * 8 * xwt * 16;
-      }
+    const int nqt = (Lmax + 31) / 32, xwt = 32 + g.halo_l + g.halo_r;   // one 32-column tile
+    // (eight blocks per CU and more: at 900 blocks the stride-5 layer of an 8-row batch lost 0.40 -> 0.48 ms, at 3000+ every layer gained)
+    if (ph && (long long)nqt * ((cot + 3) / 4) * B * (S / ph) >= 2048 && xwt <= 64 && !s.R && s.act == ACT_NONE) {
+      tph = ph; qb = 1; chg = 2; xw = xwt;
+      pg = dim3(nqt, (cot + 3) / 4, B * (S / ph));
     }
   }
-  if (ps) {   // the plan's grid is remembered, the launch covers the extent
-    L.plan_blocks = (long long)L.grid.x * L.grid.y * L.grid.z;
-    const int cols = 32 * L.qb;
-    L.grid.x = (eL + cols - 1) / cols;
-    L.grid.z *= eB;
-    B = eB; Lmax = eL;
+  p.xw = xw;
+  L.plan_blocks = (long long)pg.x * pg.y * pg.z;
+  const bool small = L.plan_blocks <= 512;   // about two blocks per CU: what the WPF / WALL forms are for
+  // ---- the kernel form of that plan
+  ConvForm f{CONV_K_CONV, qb, 0, 1, 2, 4, 0, 0, 0};
+  if (tph) {                    // transposed conv, several output phases per block
+    f = ConvForm{CONV_K_CONVBT, 1, 0, 2, 1, 4, 0, 0, tph};
+  } else if (bf) {              // bf16-split matrix pipe (k_convb): weights packed as two bf16 planes
+    f.kernel = CONV_K_CONVB;
+    f.nc = (qb == 1 && xw <= 64) ? 1 : 2;
+    if (chg == 4) {
+      // one tap, channels split over the waves, at most two blocks per CU: the chunk's weights are requested one chunk ahead (WPF)
+      f.chg = 4; f.nc = 1; f.ks = ks; f.wpf = ks && S == 1 && maxtap == 1 && small && !smi_env("SPARKMI_CB_NOWPF");
+    } else if (ks) {
+      // several taps on a grid of about a block per CU: all taps' weights of a chunk requested together (WALL)
+      // (measured at one / two utterances, 150 frames: 7-tap convs 71 -> 62 us at 456 blocks but 101 -> 115 at 912; the first transposed conv,
+      // 2 taps per phase, 85 -> 129 us: stride-1 layers with four taps or more on at most two blocks per CU)
+      f.ks = 1; f.chg = 2; f.wall = maxtap >= 4 && S == 1 && small && !smi_env("SPARKMI_CB_NOWALL");
+    } else if (chg == 2) {      // few taps per phase, rows wider than 64 columns (transposed convs): 64-channel chunks
+      f.chg = 2; f.nc = 2;
+    }
+  } else if (chg == 4) {        // 1-tap layers: 128-channel chunks, narrow rows
+    // WPF measured (profiles/README.md): pays up to about two blocks per CU, costs beyond (fewer waves fit)
+    f.chg = 4; f.nc = 1; f.ks = ks; f.wpf = ks && small;
+  } else {                      // three output tiles per block (never channel-split); strided convs: up to 192 staged columns
+    f.nwv = nwv; f.nc = xw > 128 ? 3 : 2; f.ks = ks;
   }
-  L.gemv = false;   // set by the caller for the per-utterance vector projections (use_gemv)
-  size_t lds = (size_t)8 * L.nwv * L.chg * p.xw * 4;
-  const size_t red = L.ks ? (size_t)4 * qb * 16 * 64 * 4 : 0;
-  L.lds = lds > red ? lds : red;
-  double taps = 0;
-  for (int r = 0; r < S; ++r) taps += g.ntaps[r];
-  L.flops = 2.0 * Cout * Cin * taps * Lmax * B;   // all phases together cover S*Lmax outputs
+  // ---- what runs: the MFMA form on the extent's grid, or the kernel the caller asked for
+  L.grid = s.ps ? dim3((s.Lmax + 32 * qb - 1) / (32 * qb), pg.y, pg.z * s.B) : pg;
+  L.blk = 64 * nwv;
+  const size_t stage = (size_t)8 * nwv * chg * xw * 4, red = ks ? (size_t)4 * qb * 16 * 64 * 4 : 0;
+  L.lds = stage > red ? stage : red;
+  bool mfma = true;
+  if (s.want == CONV_GEMV) {    // one block per 32 outputs and utterance; anything but an exact 1-tap layer on one position finds no form
+    mfma = false;
+    f = ConvForm{(!bf && K == 1 && S == 1 && istr == 1 && s.Lmax == 1) ? CONV_K_GEMV : -1, 0, 0, 0, 0, 4, 0, 0, 0};
+    L.grid = dim3(cot, s.B); L.blk = 256; L.lds = 0; L.plan_blocks = (long long)cot * B;
+  } else if (s.want == CONV_C1 && c1_eligible(s)) {   // a thread per output sample instead of a 32-row MFMA tile with one live row
+    mfma = false;
+    f = ConvForm{CONV_K_C1, 0, 0, 0, 0, 4, 0, 0, 7};
+    L.grid = dim3((s.Lmax + 255) / 256, s.B); L.blk = 256; L.lds = (size_t)Cin * 7 * 4;
+  }
+  L.plan = ConvPlan{conv_form_index(f), qb, ks, chg, nwv, tph, xw, mfma ? (int)pg.y : 0, mfma && small};
   return L;
 }
 
+int check_conv(const Launch& L, const char* who) {
+  const ConvP& p = L.cp;
+  const ConvPlan& q = L.plan;
+  const char* n = L.name.c_str();
+  SMI_REQUIRE(p.W, "%s: arena entry for %s not found", who, n);
+  SMI_REQUIRE(q.form >= 0, "%s: %s: no kernel instantiation for this launch plan", who, n);
+  SMI_REQUIRE(L.lds <= 64 * 1024, "%s: %s needs %zu bytes of LDS", who, n, L.lds);
+  // the staging limits: a strided layer (exact pipe) up to 192 columns in 32-channel chunks, else one 64-column pass; every other
+  // layer up to 128 columns, a 128-channel chunk one pass
+  if (p.istr > 1) SMI_REQUIRE(q.xw <= 192 && (q.chg == 1 || q.xw <= 64), "%s: %s stages %d columns", who, n, q.xw);
+  else SMI_REQUIRE(q.xw <= 128 && (q.chg != 4 || q.xw <= 64), "%s: %s stages %d columns", who, n, q.xw);
+  if (q.tph) SMI_REQUIRE(!p.bbias && !p.gamma && !p.beta && !p.R && !p.X2 && p.out_scale == 1.0f && p.act == ACT_NONE,
+                         "%s: %s: the multi-phase transposed conv has a bias / Snake epilogue only", who, n);
+  return SMI_OK;
+}
+
 std::vector<long long> plan_signature(const std::vector<Launch>& P) {
+  static_assert(sizeof(ConvPlan) % sizeof(int) == 0 && std::is_trivially_copyable<ConvPlan>::value, "the plan record is a row of ints");
   std::vector<long long> sig;
   for (const Launch& L : P) {
     sig.push_back(L.kind);
     if (L.kind == 0) {
-      const bool mfma = !L.gemv && !L.c1;   // (the vector projections and the one-channel conv size their grids from the extent alone)
-      for (long long v : {(long long)L.qb, (long long)L.ks, (long long)L.chg, (long long)L.nwv, (long long)L.tph, (long long)L.gemv, (long long)L.c1,
-                          (long long)L.bf, (long long)L.cp.xw, (long long)L.lds, (long long)(mfma ? L.grid.y : 0), (long long)(mfma && plan_grid_blocks(L) <= 512)})
-        sig.push_back(v);
+      const int* v = (const int*)&L.plan;   // the whole record: every choice made from the plan shape
+      sig.insert(sig.end(), v, v + sizeof(ConvPlan) / sizeof(int));
     } else if (L.kind == 5) {
       for (long long v : {(long long)L.res_nwv, (long long)L.rp.xw, (long long)L.lds}) sig.push_back(v);
     } else if (L.kind == 1) {

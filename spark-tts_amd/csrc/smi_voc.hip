@@ -178,18 +178,14 @@ struct WSrc {
 WSrc wsrc(const smi_voc* h) { return WSrc{&h->lay.e, h->arena}; }
 const float* ent(const smi_voc* h, const std::string& name) { return wsrc(h).get(name); }
 
-Launch make_conv(const WSrc& w, const std::string& name, const std::string& wname, const char* bname,
-                 int Cout, int Cin, int K, int dil, int S, int pad, const float* X, int xstride, long long xb,
-                 float* Y, float* Ys, const float* alpha, const float* R, int ystride, long long yb,
-                 const int* lens, int B, int Lmax, int act, const PlanShape* ps = nullptr) {
-  return make_conv_w(name, w.get(wname), bname ? w.get(bname) : nullptr, Cout, Cin, K, dil, S, pad, X, xstride, xb, Y, Ys,
-                     alpha, R, ystride, yb, lens, B, Lmax, act, 1, nullptr, w.is_bf(wname), ps);
-}
-Launch make_conv(const smi_voc* h, const std::string& name, const std::string& wname, const char* bname,
-                 int Cout, int Cin, int K, int dil, int S, int pad, const float* X, int xstride, long long xb,
-                 float* Y, float* Ys, const float* alpha, const float* R, int ystride, long long yb,
-                 const int* lens, int B, int Lmax, int act, const PlanShape* ps = nullptr) {
-  return make_conv(wsrc(h), name, wname, bname, Cout, Cin, K, dil, S, pad, X, xstride, xb, Y, Ys, alpha, R, ystride, yb, lens, B, Lmax, act, ps);
+// The spec of a layer on [C][L] activations: weights and bias by arena name, input and output with row stride L and batch stride
+// bs, B rows of at most L positions.  The caller names the layer's shape and its operands (and any stride that differs).
+ConvSpec layer(const WSrc& w, const std::string& name, const std::string& wname, const std::string& bname, int L, long long bs,
+               const int* lens, int B, const PlanShape* ps) {
+  ConvSpec s;
+  s.name = name; s.W = w.get(wname); s.bias = w.get(bname); s.bf = w.is_bf(wname);
+  s.xstride = s.ystride = L; s.xb = s.yb = bs; s.lens = lens; s.B = B; s.Lmax = L; s.ps = ps;
+  return s;
 }
 
 // ---- launch builders shared by smi_voc_forward and the one-block entry points (smi_voc_block_run): the same kernels,
@@ -204,18 +200,17 @@ float* add_res_unit(std::vector<Launch>& P, const WSrc& w, const std::string& u,
                     float* A, float* rawout, bool want_us, const float* next_alpha, int L, long long bs, const int* lens, int B,
                     const PlanShape* ps = nullptr) {
   float* US_out = want_us ? US : nullptr;
-  P.push_back(make_conv(w, u + ".conv7", u + ".1.weight", (u + ".1.bias").c_str(), C, C, 7, dil, 1, 3 * dil, US, L, bs,
-                        nullptr, A, w.get(u + ".2.alpha"), nullptr, L, bs, lens, B, L, ACT_NONE, ps));
-  P.push_back(make_conv(w, u + ".conv1+res", u + ".3.weight", (u + ".3.bias").c_str(), C, C, 1, 1, 1, 0, A, L, bs,
-                        rawout, US_out, next_alpha, U, L, bs, lens, B, L, ACT_NONE, ps));
+  ConvSpec s7 = layer(w, u + ".conv7", u + ".1.weight", u + ".1.bias", L, bs, lens, B, ps);
+  s7.Cout = s7.Cin = C; s7.K = 7; s7.dil = dil; s7.pad = 3 * dil; s7.X = US; s7.Ys = A; s7.alpha = w.get(u + ".2.alpha");
+  ConvSpec s1 = layer(w, u + ".conv1+res", u + ".3.weight", u + ".3.bias", L, bs, lens, B, ps);
+  s1.Cout = s1.Cin = C; s1.X = A; s1.Y = rawout; s1.Ys = US_out; s1.alpha = next_alpha; s1.R = U;
+  const Launch c7 = make_conv(s7), c1 = make_conv(s1);
   // C = 96 / 192 on the bf16-split pipe with one output tile per wave (not the channel-split mode of short sequences): the two
   // launches become one k_resunit (SPARKMI_RESFUSE=0: two launches, A/B).  The choice depends on the layer and on whether the
   // grid fills the chip, as every launch plan does -- never on a row's neighbours.
-  const Launch& c7 = P[P.size() - 2];
-  const Launch& c1 = P[P.size() - 1];
   const char* e = smi_env("SPARKMI_RESFUSE");
-  if ((C == 96 || C == 192) && c7.bf && c1.bf && !c7.ks && !c1.ks && c7.cp.W && c1.cp.W && c7.cp.bias && c1.cp.bias && c7.cp.alpha &&
-      c7.cp.xw <= 128 && !(e && e[0] == '0')) {
+  if ((C == 96 || C == 192) && s7.bf && s1.bf && !c7.plan.ks && !c1.plan.ks && s7.W && s1.W && s7.bias && s1.bias && s7.alpha &&
+      c7.plan.xw <= 128 && !(e && e[0] == '0')) {
     Launch F; F.kind = 5; F.name = u + ".conv7+conv1+res"; F.flops = c7.flops + c1.flops; F.res_nwv = C / 32;
     ResP& r = F.rp; memset(&r, 0, sizeof(r));
     r.Xs = US; r.U = U; r.W7 = c7.cp.W; r.b7 = c7.cp.bias; r.alpha2 = c7.cp.alpha; r.W1 = c1.cp.W; r.b1 = c1.cp.bias;
@@ -225,10 +220,11 @@ float* add_res_unit(std::vector<Launch>& P, const WSrc& w, const std::string& u,
     F.grid = dim3((L + 63) / 64, 1, B);
     const size_t stage = (size_t)2 * 6 * r.xw * 16, image = (size_t)2 * (C / 8) * 64 * 16;
     F.lds = stage > image ? stage : image;
-    P.pop_back(); P.pop_back();
     P.push_back(F);
     return F.rp.Ys;
   }
+  P.push_back(c7);
+  P.push_back(c1);
   return US_out;
 }
 
@@ -240,8 +236,10 @@ float* add_dec_block(std::vector<Launch>& P, const WSrc& w, const std::string& b
                    int Lin, long long bs_in, float* U, float* US, float* A, float* raw_final, const float* next_alpha, long long bs,
                    const int* lens_in, const int* lens_out, int B, const PlanShape* ps = nullptr) {
   const int Lout = Lin * s;
-  P.push_back(make_conv(w, b + ".convT", b + ".1.weight", (b + ".1.bias").c_str(), cout, cin, k, 1, s, (k - s) / 2, s_in, Lin, bs_in,
-                        U, US, w.get(b + ".2.block.0.alpha"), nullptr, Lout, bs, lens_in, B, Lin, ACT_NONE, ps));
+  ConvSpec t = layer(w, b + ".convT", b + ".1.weight", b + ".1.bias", Lin, bs_in, lens_in, B, ps);
+  t.Cout = cout; t.Cin = cin; t.K = k; t.S = s; t.pad = (k - s) / 2; t.X = s_in; t.Y = U; t.Ys = US; t.alpha = w.get(b + ".2.block.0.alpha");
+  t.ystride = Lout; t.yb = bs;
+  P.push_back(make_conv(t));
   for (int r = 0; r < 3; ++r) {
     const std::string u = b + "." + std::to_string(r + 2) + ".block";
     const int dil = r == 0 ? 1 : (r == 1 ? 3 : 9);
@@ -270,25 +268,20 @@ void add_lnorm(std::vector<Launch>& P, const WSrc& w, const std::string& name, c
 void add_convnext(std::vector<Launch>& P, const WSrc& w, const std::string& b, int D, int I, float* x, float* n, float* m,
                   const float* ada, int ada_stride, int T, long long bs, const int* lens, int B, const PlanShape* ps = nullptr) {
   add_lnorm(P, w, b + ".dwconv+norm", b + ".norm", ada, ada_stride, w.get(b + ".dwconv.weight"), w.get(b + ".dwconv.bias"), x, n, 0, D, T, bs, lens, B);
-  P.push_back(make_conv(w, b + ".pwconv1", b + ".pwconv1.weight", (b + ".pwconv1.bias").c_str(), I, D, 1, 1, 1, 0, n, T, bs, m,
-                        nullptr, nullptr, nullptr, T, bs, lens, B, T, ACT_GELU, ps));
-  P.push_back(make_conv(w, b + ".pwconv2", b + ".pwconv2.weight", (b + ".pwconv2.bias").c_str(), D, I, 1, 1, 1, 0, m, T, bs, x,
-                        nullptr, nullptr, x, T, bs, lens, B, T, ACT_NONE, ps));
-  P.back().cp.gamma = w.get(b + ".gamma");
+  ConvSpec p1 = layer(w, b + ".pwconv1", b + ".pwconv1.weight", b + ".pwconv1.bias", T, bs, lens, B, ps);
+  p1.Cout = I; p1.Cin = D; p1.X = n; p1.Y = m; p1.act = ACT_GELU;
+  P.push_back(make_conv(p1));
+  ConvSpec p2 = layer(w, b + ".pwconv2", b + ".pwconv2.weight", b + ".pwconv2.bias", T, bs, lens, B, ps);
+  p2.Cout = D; p2.Cin = I; p2.X = m; p2.Y = x; p2.R = x; p2.gamma = w.get(b + ".gamma");
+  P.push_back(make_conv(p2));
 }
 
-// what every conv launch must satisfy before it runs (the kernels' staging limits)
+// every conv launch of a list against check_conv (smi_net.h)
 int check_launches(const std::vector<Launch>& P, const char* who) {
-  for (const Launch& L : P) {
-    if (L.kind == 0) {
-      SMI_REQUIRE(L.cp.W, "%s: arena entry for %s not found", who, L.name.c_str());
-      SMI_REQUIRE(L.lds <= 64 * 1024, "%s: %s needs %zu bytes of LDS", who, L.name.c_str(), L.lds);
-      SMI_REQUIRE(L.cp.xw <= 128 && (L.chg != 4 || L.cp.xw <= 64), "%s: %s stages %d columns", who, L.name.c_str(), L.cp.xw);
-      if (L.tph) SMI_REQUIRE(!L.cp.bbias && !L.cp.gamma && !L.cp.beta && !L.cp.R && !L.cp.X2 && L.cp.out_scale == 1.0f && L.cp.act == ACT_NONE,
-                             "%s: %s: the multi-phase transposed conv has a bias / Snake epilogue only", who, L.name.c_str());
-    }
-  }
-  return SMI_OK;
+  int rc = SMI_OK;
+  for (size_t i = 0; i < P.size() && rc == SMI_OK; ++i)
+    if (P[i].kind == 0) rc = check_conv(P[i], who);
+  return rc;
 }
 
 // ---- one reference block as its own little arena (smi_voc_block_*: op-level tests on the reference's layer classes)
@@ -371,9 +364,9 @@ float* block_program(std::vector<Launch>& P, const smi_voc_block_cfg& c, const W
     return buf[0];
   }
   if (c.cond_dim > 0) {   // all scale / shift projections of the condition in one GEMV (vocos.py:105-108), as smi_voc_forward does
-    P.push_back(make_conv(w, "adaln_params", "cat:L.norm.scale.weight|L.norm.shift.weight", "cat:L.norm.scale.bias|L.norm.shift.bias",
-                          2 * c.C, c.cond_dim, 1, 1, 1, 0, cond_dev, 1, c.cond_dim, ada, nullptr, nullptr, nullptr, 1, 2 * c.C, len1, B, 1, ACT_NONE));
-    P.back().gemv = true; P.back().grid = dim3((2 * c.C + 31) / 32, B);
+    ConvSpec a = layer(w, "adaln_params", "cat:L.norm.scale.weight|L.norm.shift.weight", "cat:L.norm.scale.bias|L.norm.shift.bias", 1, 0, len1, B, nullptr);
+    a.Cout = 2 * c.C; a.Cin = c.cond_dim; a.X = cond_dev; a.xb = c.cond_dim; a.Y = ada; a.yb = 2 * c.C; a.want = CONV_GEMV;
+    P.push_back(make_conv(a));
   }
   add_convnext(P, w, "L", c.C, c.I, buf[0], buf[1], buf[2], c.cond_dim > 0 ? ada : nullptr, 2 * c.C, L, bs, lens_in, B);
   return buf[0];
@@ -505,11 +498,15 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
     for (int j = 0; j < 8; ++j) L.fp.levels[j] = j < c.fsq_dims ? c.fsq_levels[j] : 1;
     P.push_back(L);
   }
-  P.push_back(make_conv(h, "spk_project", "speaker_encoder.project.weight", "speaker_encoder.project.bias",
-                        c.spk_out_dim, latn, 1, 1, 1, 0, lat, 1, latn, dvec, nullptr, nullptr, nullptr, 1, c.spk_out_dim,
-                        len1, B, 1, ACT_NONE, ps));
-  auto use_gemv = [&](Launch& L) { L.gemv = true; L.grid = dim3((L.cp.Cout + 31) / 32, B); };
-  use_gemv(P.back());
+  const WSrc ws = wsrc(h);
+  // a per-utterance vector projection (k_gemv1): x [B][Cin] at batch stride xb -> y [B][Cout]
+  auto gemv = [&](const std::string& name, const std::string& wname, const std::string& bname, int Cout, int Cin, const float* X, long long xb,
+                  float* Y) {
+    ConvSpec s = layer(ws, name, wname, bname, 1, 0, len1, B, ps);
+    s.Cout = Cout; s.Cin = Cin; s.X = X; s.xb = xb; s.Y = Y; s.yb = Cout; s.want = CONV_GEMV;
+    P.push_back(make_conv(s));
+  };
+  gemv("spk_project", "speaker_encoder.project.weight", "speaker_encoder.project.bias", c.spk_out_dim, latn, lat, latn, dvec);
   // all AdaLayerNorm scale/shift projections of the condition in one GEMM (vocos.py:105-108)
   {
     std::string wn, bn;
@@ -517,10 +514,14 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
       if (e.name.rfind("cat:", 0) == 0 && e.kind == PACK_CONV) wn = e.name;
       if (e.name.rfind("cat:", 0) == 0 && e.kind == PACK_RAW) bn = e.name;
     }
-    P.push_back(make_conv(h, "adaln_params", wn, bn.c_str(), ada_stride, c.pre_cond_dim, 1, 1, 1, 0, dvec, 1, c.spk_out_dim,
-                          ada, nullptr, nullptr, nullptr, 1, ada_stride, len1, B, 1, ACT_NONE, ps));
-    use_gemv(P.back());
+    gemv("adaln_params", wn, bn, ada_stride, c.pre_cond_dim, dvec, c.spk_out_dim, ada);
   }
+  // a stride-1 layer on the call's [C][T] activations
+  auto conv = [&](const std::string& name, const std::string& pfx, int Cout, int Cin, int K, const float* X, float* Y) {
+    ConvSpec s = layer(ws, name, pfx + ".weight", pfx + ".bias", T, bs, len0, B, ps);
+    s.Cout = Cout; s.Cin = Cin; s.K = K; s.pad = K / 2; s.X = X; s.Y = Y;
+    return s;
+  };
   // --- semantic tokens -> codebook rows -> out_project (factorized_vector_quantize.py:154-167)
   float* zc = bufs[0];
   {
@@ -530,16 +531,18 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
     P.push_back(L);
   }
   float* zq = other({zc});
-  P.push_back(make_conv(h, "vq_out_project", "quantizer.out_project.weight", "quantizer.out_project.bias", c.vq_input_dim,
-                        c.codebook_dim, 1, 1, 1, 0, zc, T, bs, zq, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
-  if (h->debug) { Launch cp = P.back(); cp.cp.Y = h->dbg[0]; cp.name = "vq_out_project(dbg)"; P.push_back(cp); }
+  // a debug build runs the layer a second time into its stage buffer
+  auto push = [&](ConvSpec s, float* dbg) {
+    P.push_back(make_conv(s));
+    if (h->debug) { s.Y = dbg; s.name += "(dbg)"; P.push_back(make_conv(s)); }
+  };
+  push(conv("vq_out_project", "quantizer.out_project", c.vq_input_dim, c.codebook_dim, 1, zc, zq), h->dbg[0]);
   // --- prenet (feat_decoder.py:78-94)
   float* cur = other({zq});
-  P.push_back(make_conv(h, "prenet.linear_pre", "prenet.linear_pre.weight", "prenet.linear_pre.bias", D, c.pre_input_channels, 1,
-                        1, 1, 0, zq, T, bs, cur, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
-  P.back().cp.out_scale = c.pre_num_down > 0 ? 3.0f : 1.0f;   // first SamplingBlock(ratio 1): 3x
+  ConvSpec pre = conv("prenet.linear_pre", "prenet.linear_pre", D, c.pre_input_channels, 1, zq, cur);
+  pre.out_scale = c.pre_num_down > 0 ? 3.0f : 1.0f;   // first SamplingBlock(ratio 1): 3x
+  P.push_back(make_conv(pre));
   int ada_idx = 0;
-  const WSrc ws = wsrc(h);
   auto lnorm = [&](const std::string& name, const std::string& pfx, bool ada_norm, const float* X, float* Y, int triple) {
     const float* ap = ada_norm ? ada + (size_t)(ada_idx++) * 2 * D : nullptr;
     add_lnorm(P, ws, name, pfx, ap, ada_stride, nullptr, nullptr, X, Y, triple, D, T, bs, len0, B);
@@ -547,8 +550,7 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
   // embed conv7 -> norm -> nl x ConvNeXt -> final LN (vocos.py:324-335); consumes cur, leaves result in cur
   auto vocos = [&](const std::string& p, int nl, bool ada_norm, int triple_out) {
     float* n = other({cur});          // conv / norm output
-    P.push_back(make_conv(h, p + ".embed", p + ".embed.weight", (p + ".embed.bias").c_str(), D, D, 7, 1, 1, 3, cur, T, bs, n,
-                          nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
+    P.push_back(make_conv(conv(p + ".embed", p + ".embed", D, D, 7, cur, n)));
     float* x = other({n});            // residual stream (cur is dead once embed has run)
     lnorm(p + ".norm", p + ".norm", ada_norm, n, x, 0);
     float* m = other({x, n});         // MLP hidden
@@ -565,18 +567,17 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
   SMI_REQUIRE(!c.pre_tanh_final, "smi_voc: use_tanh_at_final is not supported");
   // prenet.linear, then + d_vector per utterance (bicodec.py:185-186)
   float* x0 = other({cur});
-  P.push_back(make_conv(h, "prenet.linear+d", "prenet.linear.weight", "prenet.linear.bias", c.pre_out_channels, D, 1, 1, 1, 0, cur, T,
-                        bs, x0, nullptr, nullptr, nullptr, T, bs, len0, B, T, ACT_NONE, ps));
-  P.back().cp.bbias = dvec;
-  if (h->debug) { Launch cp = P.back(); cp.cp.Y = h->dbg[1]; cp.name = "prenet.linear+d(dbg)"; P.push_back(cp); }
+  ConvSpec lin = conv("prenet.linear+d", "prenet.linear", c.pre_out_channels, D, 1, cur, x0);
+  lin.bbias = dvec;
+  push(lin, h->dbg[1]);
   // --- WaveGenerator (wave_generator.py:56-88)
   int ch = c.dec_channels;
   int Lcur = T;
   float* s_in = other({x0});   // snake'd input of the next ConvTranspose
   {
-    const std::string a0 = "decoder.model.1.block.0.alpha";
-    P.push_back(make_conv(h, "decoder.conv_in", "decoder.model.0.weight", "decoder.model.0.bias", ch, c.dec_in, 7, 1, 1, 3, x0, T, bs,
-                          h->debug ? h->dbg[2] : nullptr, s_in, ent(h, a0), nullptr, T, bs, len0, B, T, ACT_NONE, ps));
+    ConvSpec in = conv("decoder.conv_in", "decoder.model.0", ch, c.dec_in, 7, x0, h->debug ? (float*)h->dbg[2] : nullptr);
+    in.Ys = s_in; in.alpha = ent(h, "decoder.model.1.block.0.alpha");
+    P.push_back(make_conv(in));
   }
   for (int i = 0; i < c.dec_nblocks; ++i) {
     const int cin = ch >> i, cout = ch >> (i + 1), k = c.dec_ksizes[i], s = c.dec_rates[i];
@@ -597,18 +598,10 @@ int voc_program(smi_voc* h, std::vector<Launch>& P, const int64_t* sem_dev, int 
   const int hop = Lcur / T;
   {
     const std::string n = "decoder.model." + std::to_string(c.dec_nblocks + 2);
-    // final conv7 -> tanh, written straight into the caller's waveform buffer [B][wavstride]
-    P.push_back(make_conv(h, "decoder.conv_out+tanh", n + ".weight", (n + ".bias").c_str(), 1, clast, 7, 1, 1, 3, s_in, Lcur, bs,
-                          wav_dev, nullptr, nullptr, nullptr, Lcur, wavstride, lens_at(c.dec_nblocks), B, Lcur, ACT_TANH, ps));
-    {   // C -> 1: a thread per output sample instead of a 32-row MFMA tile with one live row (SPARKMI_VOC_C1=0: the MFMA kernel)
-      Launch& L = P.back();
-      const char* e = smi_env("SPARKMI_VOC_C1");
-      const ConvP& q = L.cp;
-      if (!(e && e[0] == '0') && !L.bf && q.Cout == 1 && q.S == 1 && q.istr == 1 && q.ntaps[0] == 7 && !q.X2 && !q.bbias && !q.gamma &&
-          !q.beta && !q.R && !q.Ys && q.Y && q.out_scale == 1.0f && q.Cin * 7 * 4 <= 48 * 1024) {
-        L.c1 = true; L.c1_len = Lcur;
-      }
-    }
+    // final conv7 -> tanh, written straight into the caller's waveform buffer [B][wavstride]; C -> 1: the one-channel kernel
+    ConvSpec o = layer(ws, "decoder.conv_out+tanh", n + ".weight", n + ".bias", Lcur, bs, lens_at(c.dec_nblocks), B, ps);
+    o.Cout = 1; o.Cin = clast; o.K = 7; o.pad = 3; o.X = s_in; o.Y = wav_dev; o.yb = wavstride; o.act = ACT_TANH; o.want = CONV_C1;
+    P.push_back(make_conv(o));
     Launch Z; Z.kind = 4; Z.name = "zero_tail"; Z.flops = 0; Z.wav = wav_dev; Z.wstride = (int)wavstride; Z.lens = len0; Z.hop = hop;
     Z.grid = dim3((unsigned)((wavstride + 255) / 256), B);
     P.push_back(Z);
@@ -817,7 +810,7 @@ int conv_case_lout(const smi_conv_case& c, int n) {   // output positions of a r
   return n;
 }
 
-// one conv launch for a case, through make_conv_w and the two caller overrides, with the checks the launch lists get
+// one conv launch for a case, through make_conv() and check_conv() as the launch lists' are
 int conv_case_launch(const smi_conv_case* cp, const smi_conv_operands& io, const int* lens, const int* olens, Launch& L, const char* who) {
   SMI_REQUIRE(cp, "%s: case is null", who);
   const smi_conv_case& c = *cp;
@@ -839,48 +832,32 @@ int conv_case_launch(const smi_conv_case* cp, const smi_conv_operands& io, const
   const int lout = conv_case_lout(c, c.L);
   SMI_REQUIRE(lout >= 1, "%s: L = %d gives no output", who, c.L);
   const PlanShape ps{c.plan_frames, c.plan_ext_frames};
-  const float* R = io.R ? io.R : (c.has_R ? io.X : nullptr);
-  const int Lmax = c.S > 1 ? c.L : lout;   // output positions per phase
-  if (c.gemv) {
-    SMI_REQUIRE(!c.bf && c.K == 1 && c.S == 1 && c.istr == 1 && c.L == 1 && !io.X2 && !io.bbias && !io.gamma && !io.beta && !io.R && !c.has_R && !io.Ys &&
+  SMI_REQUIRE(io.out_scale == 1.0f || io.out_scale == 3.0f, "%s: out_scale is 1 or 3", who);
+  SMI_REQUIRE(!(c.bf && io.X2), "%s: the bf16-split kernels stage X only (no second input)", who);
+  ConvSpec s;
+  s.name = "conv"; s.Cout = c.Cout; s.Cin = c.Cin; s.K = c.K; s.dil = c.dil; s.S = c.S; s.pad = c.pad; s.istr = c.istr; s.bf = c.bf != 0;
+  s.W = io.W; s.bias = io.bias; s.X = io.X; s.X2 = io.X2; s.xstride = c.L; s.xb = (long long)c.Cin * c.L;
+  s.Y = io.Y; s.Ys = io.Ys; s.alpha = io.alpha; s.R = io.R ? io.R : (c.has_R ? io.X : nullptr); s.ystride = lout; s.yb = (long long)c.Cout * lout;
+  s.lens = lens; s.olens = c.istr > 1 ? olens : nullptr; s.B = c.B; s.Lmax = c.S > 1 ? c.L : lout; s.act = c.act;   // Lmax: output positions per phase
+  s.bbias = io.bbias; s.gamma = io.gamma; s.beta = io.beta; s.out_scale = io.out_scale;
+  s.want = c.gemv ? CONV_GEMV : (c.c1 ? CONV_C1 : CONV_MFMA); s.ps = c.plan_frames ? &ps : nullptr;
+  if (c.gemv)
+    SMI_REQUIRE(!c.bf && c.K == 1 && c.S == 1 && c.istr == 1 && c.L == 1 && !io.X2 && !io.bbias && !io.gamma && !io.beta && !s.R && !io.Ys &&
                 io.out_scale == 1.0f && (c.act == ACT_NONE || c.act == ACT_RELU || c.act == ACT_SIGMOID),
                 "%s: the vector projection is an exact 1-tap layer on L = 1 with bias and ReLU / sigmoid only", who);
-    L = make_conv_w("conv", io.W, io.bias, c.Cout, c.Cin, 1, 1, 1, 0, io.X, 1, c.Cin, io.Y, nullptr, nullptr, nullptr, 1, c.Cout, lens, c.B, 1, c.act);
-    L.gemv = true; L.grid = dim3((c.Cout + 31) / 32, c.B);
-    return SMI_OK;
-  }
-  L = make_conv_w("conv", io.W, io.bias, c.Cout, c.Cin, c.K, c.dil, c.S, c.pad, io.X, c.L, (long long)c.Cin * c.L, io.Y, io.Ys, io.alpha, R,
-                  lout, (long long)c.Cout * lout, lens, c.B, Lmax, c.act, c.istr, c.istr > 1 ? olens : nullptr, c.bf != 0, c.plan_frames ? &ps : nullptr);
-  ConvP& q = L.cp;
-  q.X2 = io.X2; q.bbias = io.bbias; q.gamma = io.gamma; q.beta = io.beta; q.out_scale = io.out_scale;
-  SMI_REQUIRE(q.out_scale == 1.0f || q.out_scale == 3.0f, "%s: out_scale is 1 or 3", who);
-  SMI_REQUIRE(!(L.bf && q.X2), "%s: the bf16-split kernels stage X only (no second input)", who);
-  if (c.c1) {   // the vocoder's own conditions for the one-channel kernel (voc_program)
-    SMI_REQUIRE(!L.bf && q.Cout == 1 && q.S == 1 && q.istr == 1 && q.ntaps[0] == 7 && !q.X2 && !q.bbias && !q.gamma && !q.beta && !q.R && !q.Ys &&
-                q.out_scale == 1.0f && q.Cin * 7 * 4 <= 48 * 1024, "%s: k_conv_c1 is an exact 7-tap conv to one channel with bias and activation only", who);
-    L.c1 = true; L.c1_len = Lmax;
-    return SMI_OK;
-  }
-  SMI_REQUIRE(L.lds <= 64 * 1024, "%s: the launch needs %zu bytes of LDS", who, L.lds);
-  if (c.istr > 1) SMI_REQUIRE(q.xw <= 192 && (L.chg == 1 || q.xw <= 64), "%s: the launch stages %d columns", who, q.xw);   // the encoder's limit
-  else SMI_REQUIRE(q.xw <= 128 && (L.chg != 4 || q.xw <= 64), "%s: the launch stages %d columns", who, q.xw);             // check_launches
-  if (L.tph) SMI_REQUIRE(!q.bbias && !q.gamma && !q.beta && !q.R && !q.X2 && q.out_scale == 1.0f && q.act == ACT_NONE,
-                         "%s: the multi-phase transposed conv has a bias / Snake epilogue only", who);
-  return SMI_OK;
+  L = make_conv(s);
+  SMI_REQUIRE(!c.c1 || (L.plan.form >= 0 && conv_form_at(L.plan.form).kernel == CONV_K_C1),
+              "%s: k_conv_c1 is an exact 7-tap conv to one channel with bias and activation only", who);
+  return check_conv(L, who);
 }
 
-int conv_plan_info(const smi_conv_case& c, const Launch& L, smi_conv_plan_info* out, const char* who) {
-  const ConvForm f = conv_form(L);
-  const int fi = conv_form_index(f);
-  SMI_REQUIRE(fi >= 0, "%s: no kernel instantiation for this launch plan", who);
+void conv_plan_info(const smi_conv_case& c, const Launch& L, smi_conv_plan_info* out) {
   memset(out, 0, sizeof(*out));
-  out->form = form_record(f); out->form_index = fi; out->xw = L.cp.xw;
+  out->form = form_record(conv_form_at(L.plan.form)); out->form_index = L.plan.form; out->xw = L.plan.xw;
   out->grid[0] = (int)L.grid.x; out->grid[1] = (int)L.grid.y; out->grid[2] = (int)L.grid.z;
-  if (L.c1) { out->grid[0] = (L.c1_len + 255) / 256; out->grid[1] = (int)L.grid.z; out->grid[2] = 1; }
   out->lout = c.gemv ? 1 : conv_case_lout(c, c.L);
-  out->lds_bytes = L.c1 ? (long long)L.cp.Cin * 7 * 4 : (L.gemv ? 0 : (long long)L.lds);
-  out->plan_blocks = plan_grid_blocks(L);
-  return SMI_OK;
+  out->lds_bytes = (long long)L.lds;
+  out->plan_blocks = L.plan_blocks;
 }
 
 }  // namespace
@@ -905,7 +882,8 @@ int smi_conv_plan(const smi_conv_case* c, smi_conv_plan_info* out) {
   Launch L;
   int rc = conv_case_launch(c, io, nullptr, (const int*)(uintptr_t)768, L, "smi_conv_plan");
   if (rc) return rc;
-  return conv_plan_info(*c, L, out, "smi_conv_plan");
+  conv_plan_info(*c, L, out);
+  return SMI_OK;
 }
 
 int smi_conv_run(const smi_conv_case* c, const smi_conv_operands* io, const int32_t* lens_host, smi_conv_plan_info* plan, void* stream) {
@@ -927,7 +905,7 @@ int smi_conv_run(const smi_conv_case* c, const smi_conv_operands* io, const int3
   Launch L;
   rc = conv_case_launch(c, *io, lens, lens + B, L, "smi_conv_run");
   smi_conv_plan_info info;
-  if (rc == SMI_OK) rc = conv_plan_info(*c, L, &info, "smi_conv_run");
+  if (rc == SMI_OK) conv_plan_info(*c, L, &info);
   auto fail = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == SMI_OK) { smi_set_error("smi_conv_run: %s: %s", what, hipGetErrorString(e)); rc = SMI_EHIP; } };
   if (rc == SMI_OK) fail(hipMemcpyAsync(lens, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, st), "lens upload");
   if (rc == SMI_OK) rc = run_launch(L, st);
@@ -962,9 +940,7 @@ int smi_voc_block_plan(const smi_voc_block_cfg* cfg, int B, int L, smi_block_lau
     strncpy(o.name, P[i].name.c_str(), sizeof(o.name) - 1);
     o.kind = P[i].kind; o.form_index = -1;
     if (P[i].kind == 0) {
-      const ConvForm f = conv_form(P[i]);
-      o.form = form_record(f); o.form_index = conv_form_index(f);
-      SMI_REQUIRE(o.form_index >= 0, "smi_voc_block_plan: %s: no kernel instantiation for this launch plan", P[i].name.c_str());
+      o.form_index = P[i].plan.form; o.form = form_record(conv_form_at(o.form_index));
     } else if (P[i].kind == 1) {
       o.cpt = dwln_form(P[i].cpt);
     } else if (P[i].kind == 5) {

@@ -230,7 +230,7 @@ def plan_block(kind: int, B: int, L: int, *, C_: int, Cout: int = 0, K: int = 0,
 def run_conv(case: _lib.ConvCase, w: np.ndarray, x: torch.Tensor, *, bias=None, bbias=None, gamma=None, beta=None, R=None, alpha=None,
              x2=None, lens: Optional[Sequence[int]] = None, out_scale: float = 1.0, want_y: bool = True, want_ys: bool = False,
              r_aliases_y: bool = False, fill: float = 0.0):
-    """ONE conv layer on the HIP kernels (``smi_conv_run``, diagnostics build), built by ``make_conv_w`` -- the op-level seam for
+    """ONE conv layer on the HIP kernels (``smi_conv_run``, diagnostics build), built by ``make_conv`` -- the op-level seam for
     a single kernel form.  ``w``: Conv1d weights (Cout, Cin, K) or ConvTranspose1d weights (Cin, Cout, K), packed here with
     ``pack_conv`` / ``pack_conv_b``; ``x`` (B, Cin, L) on the GPU ((B, Cin) for gemv).  The outputs are pre-filled with ``fill``
     (``r_aliases_y``: Y starts as a copy of R and is the residual operand).  Returns (y, ys, plan)."""

@@ -1,8 +1,8 @@
 """The case table of tests/test_conv_forms_cpu.py and tests/test_conv_forms_gpu.py: one conv layer + call shape per kernel
-form the launch builder (make_conv_w / run_launch, csrc/smi_net.h) can pick, the block shapes that reach k_resunit, k_convbT
+form the launch builder (make_conv / run_launch, csrc/smi_net.h) can pick, the block shapes that reach k_resunit, k_convbT
 and the wide k_dwln forms, the float64 reference, and the derived acceptance bound.  DESIGN.md 4.0.1 has the derivations.
 
-Shapes are the smallest that meet each form's thresholds in make_conv_w:
+Shapes are the smallest that meet each form's thresholds in make_conv:
   qb = 1      L <= 32, or fewer than 256 blocks at 64-column tiles          qb = 2   otherwise
   ks          nq * ceil(cot / 4) * B * S < 512 and Cin >= 8   (cot = 32-row output tiles, nq = time tiles)
   3 waves     exact pipe, not ks, cot in {3, 6, 9, ..} not a multiple of 4, nq * ceil(cot / 4) * B * S >= 2048
@@ -76,17 +76,31 @@ CONV_CASES = {
     "bT4":            _c("k_convbT<4>", 40, 72, 8, S=4, bf=True, B=64, L=997),
     "bT4_s8":         _c("k_convbT<4>", 40, 72, 16, S=8, bf=True, B=64, L=485),
     "bT5":            _c("k_convbT<5>", 40, 72, 11, S=5, bf=True, B=64, L=997),
-    # ---- the two forms the callers of make_conv_w select
+    # ---- the two forms the callers of make_conv select
     "c1":             _c("k_conv_c1", 1, 22, 7, B=3, L=300, c1=True),
     "gemv":           _c("k_gemv1", 70, 100, 1, B=5, L=1, gemv=True),
 }
 
-# forms of the table that no argument tuple of make_conv_w reaches: form -> the builder condition that excludes it
+# forms of the table that no argument tuple of make_conv reaches: form -> the builder condition that excludes it
 UNREACHABLE = {
-    "k_conv<qb1,co,chg4,nc1>": "`L.chg = (S == 1 && K == 1 && Cin >= 128 && L.ks) ? 4 : 1`: the exact pipe stages 128-channel chunks only with L.ks "
-                               "(the other `L.chg = ... 4` needs `bf`)",
-    "k_conv<qb2,co,chg4,nc1>": "`L.chg = (S == 1 && K == 1 && Cin >= 128 && L.ks) ? 4 : 1`: the exact pipe stages 128-channel chunks only with L.ks "
-                               "(the other `L.chg = ... 4` needs `bf`)",
+    "k_conv<qb1,co,chg4,nc1>": "`chg = (S == 1 && K == 1 && Cin >= 128 && ks) ? 4 : 1`: the exact pipe stages 128-channel chunks only with ks "
+                               "(the other `chg = ... 4` needs `bf`)",
+    "k_conv<qb2,co,chg4,nc1>": "`chg = (S == 1 && K == 1 && Cin >= 128 && ks) ? 4 : 1`: the exact pipe stages 128-channel chunks only with ks "
+                               "(the other `chg = ... 4` needs `bf`)",
+}
+
+# What the builder must NOT run as asked: name -> (sparkmi.bicodec.conv_case arguments, None = smi_conv_plan refuses the case, or the
+# form it plans instead).  xw = (32 qb - 1) istr + 1 + (K - 1) dil as above.
+REFUSED = {
+    # a strided 1-tap layer at qb2 stages 127 columns in 128-channel chunks (chg 4 takes one 64-column pass)
+    "chg4_wide":    (dict(Cout=250, Cin=136, K=1, istr=2, B=4, L=999), None),
+    # istr 5, K 8 at qb2: 323 columns, over the 192 of the widest exact form
+    "strided_wide": (dict(Cout=40, Cin=12, K=8, istr=5, B=16, L=4043), None),
+    "c1_cout2":     (dict(Cout=2, Cin=22, K=7, B=3, L=300, c1=True), None),
+    "c1_residual":  (dict(Cout=1, Cin=22, K=7, B=3, L=300, c1=True, has_R=True), None),
+    "gemv_bf":      (dict(Cout=70, Cin=100, K=1, B=5, L=1, bf=True, gemv=True), None),
+    # the shape of case bT4 with a residual: k_convbT has a bias / Snake epilogue only, the layer stays on k_convb
+    "bT4_residual": (dict(Cout=40, Cin=72, K=8, S=4, bf=True, B=64, L=997, has_R=True), "k_convb<qb2,co,chg1,nc2>"),
 }
 
 # chunk of a form in input channels (k_conv: 8 rows x waves x chg; k_convb: 32 x chg)

@@ -1,4 +1,4 @@
-"""Which conv kernel form runs which case -- checked on the host.  The launch builder's choices (make_conv_w + the dispatch
+"""Which conv kernel form runs which case -- checked on the host.  The launch builder's choices (make_conv + the dispatch
 of run_launch, csrc/smi_net.h) are read through the diagnostics library's host-only plan entries; the case table of
 tests/conv_cases.py must reach every instantiated form, and its float64 reference with the derived bound must be able to
 tell a subtly wrong kernel from a right one.  tests/test_conv_forms_gpu.py runs the same cases on the kernels."""
@@ -46,6 +46,27 @@ def test_unreachable_forms_are_excluded_by_the_builder():
             for (Bn, L) in [(1, 20), (3, 45), (16, 2021), (512, 27), (2048, 27), (64, 4000)]:
                 f = B.plan_conv(B.conv_case(Cout, Cin, 1, B=Bn, L=L)).form
                 assert not (f.kernel == 0 and f.chg == 4 and not f.ks)
+
+
+def test_builder_refuses_what_no_kernel_runs():
+    """the REFUSED list: a staged row wider than the form's passes, k_conv_c1 / k_gemv1 asked for a layer they cannot run -- each
+    refused for that reason, before any launch; a residual keeps a k_convbT-shaped layer on k_convb.  The same layers without
+    the offending property plan."""
+    why = {"chg4_wide": "stages 127 columns", "strided_wide": "stages 323 columns", "c1_cout2": "k_conv_c1", "c1_residual": "k_conv_c1",
+           "gemv_bf": "vector projection"}
+    assert set(why) == {n for n, (_, want) in cc.REFUSED.items() if want is None}
+    for n, (kw, want) in cc.REFUSED.items():
+        if want is None:
+            with pytest.raises(Exception, match=why[n]):
+                B.plan_conv(B.conv_case(**kw))
+        else:
+            assert B.form_name(B.plan_conv(B.conv_case(**kw)).form.key()) == want, n
+    ok = {"chg4_wide": dict(L=499), "strided_wide": dict(L=138), "c1_cout2": dict(Cout=1), "c1_residual": dict(has_R=False),
+          "gemv_bf": dict(bf=False), "bT4_residual": dict(has_R=False)}
+    for n, fix in ok.items():
+        p = B.plan_conv(B.conv_case(**{**cc.REFUSED[n][0], **fix}))
+        assert p.form_index >= 0 and p.xw <= 64 * max(1, p.form.nc), n
+    assert B.form_name(B.plan_conv(B.conv_case(**{**cc.REFUSED["bT4_residual"][0], "has_R": False})).form.key()) == "k_convbT<4>"
 
 
 def test_case_mix_per_form(forms, plans):

@@ -142,7 +142,7 @@ def test_epilogue_against_float64(name, variant):
 
 @pytest.mark.parametrize("tph_case", ["bT4", "bT5"])
 def test_multi_phase_transposed_conv_epilogue(tph_case):
-    """k_convbT knows bias, the raw output and the Snake'd output; the run entry rejects everything else, as check_launches does"""
+    """k_convbT knows bias, the raw output and the Snake'd output; the run entry rejects everything else, as check_conv does"""
     from sparkmi import _lib
     from sparkmi.bicodec import conv_case, form_name, run_conv
     c = dict(cc.CONV_CASES[tph_case])
