@@ -864,6 +864,73 @@ int smi_tempo_rows(const float* in_dev, long long in_stride, const int32_t* n_ho
                    const int32_t* p_host, const int32_t* q_host, int N, int D, const double* win_dev, int32_t* pos_dev, long long pos_stride,
                    float* out_dev, long long out_stride, int32_t* m_host, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Tempo of joined streams: the arithmetic above with state carried from push to push, so that a stream whose input arrives in
+ * chunks (a joined stream of smi_join at 1/1) leaves in pieces before it has ended.  No sample is defined here: the
+ * concatenation of a stream's pieces is smi_tempo_rows of its whole input.  What is new is the state and the rule for when an
+ * output sample is final.
+ *
+ * When a frame is final.  A stream is an input sequence x with n samples so far; its total L is known only with the last push.
+ * H, a_k, t_k, s_k, M as above.  R_0 = H, and for k >= 1
+ *     R_k = max(a_k, a_{k-1} + H) + D + N.
+ * Frame k is final once n >= R_k: frame 0 copies x[0 .. H); for k >= 1 the target [t_k, t_k + N) ends at or before
+ * a_{k-1} + D + H + N because t_k = s_{k-1} + H <= a_{k-1} + D + H, every candidate ends at or before a_k + D + N, and the two
+ * overlap-add reads end before s_k + H <= a_k + D + H and s_{k-1} + N <= a_{k-1} + D + N -- all inside x[0 .. n), so nothing
+ * the frame reads can change and nothing of it is the zero the batch reads beyond L.  R_k does not fall as k grows, and s_k
+ * hangs on s_{k-1}, so final frames are emitted as a prefix.  A frame is emitted before the last push only when, in addition,
+ * (k + 1) H <= ceil(n q / p): then it is whole in the final M = ceil(L q / p) >= ceil(n q / p).  After a push that is not the
+ * last the stream has emitted E(n) = H F outputs, F the count of such frames; after the last push it has emitted M, the
+ * remaining frames computed as the batch computes them, with zeros read beyond L.  A push emits the difference, which may be 0.
+ * All of it is host integer arithmetic (smi_tempos_piece_len), never data.  A stream opened at p = q is a copy with no latency:
+ * there the batch output is the input, and a push emits its chunk.  Otherwise the first piece waits for N + D + up to H
+ * samples beyond the frame's nominal place.
+ *
+ * State.  On the host: n, F, p, q.  On the device, per stream: s_{F-1}, which is data-dependent and never copied back, and the
+ * input from h(F) = max(0, min(a_F, a_{F-1} + H) - D) (h(0) = 0) to n: the first sample frame F can still read -- its target
+ * starts at or after a_{F-1} - D + H, its candidates at a_F - D, its overlap-add reads at s_F >= a_F - D and s_{F-1} + H.
+ * h(F) does not fall as F grows.  The history n - h(F) is bounded: frame F was not emitted, so either n < R_F, and then
+ *     n - h(F) < |a_F - a_{F-1} - H| + 2 D + N <= 3 H + 2 D + N = 5 H + 2 D        (0 <= a_F - a_{F-1} <= 4 H),
+ * or (F + 1) H > ceil(n q / p), so n < (F + 1) H p / q, and then with a_k > k H p / q - 1
+ *     n - a_F + D < H p / q + 1 + D <= 4 H + 1 + D   and   n - a_{F-1} - H + D < 2 H p / q - H + 1 + D <= 7 H + 1 + D.
+ * The handle keeps max(7 H + D, 5 H + 2 D) samples per stream and set, which is enough for every p / q in 1/4 .. 4; a push
+ * makes at most 4 (max_chunk + that history) / H + 4 frames final.  Histories and places live in two sets that a stream uses in
+ * turn: a push reads one and writes the other, so one launch sequence serves a call whatever B.
+ *
+ * Two launches a call.  k_tempos_search, one block a row, walks the row's newly final frames in order over the virtual
+ * sequence of history followed by the new chunk, with the device functions k_tempo_search calls (distance, tie rule,
+ * shortcut), and writes s_k; k_tempos_ola, grid (tiles of 1024 samples of the pieces, rows), forms the samples with
+ * k_tempo_ola's expression and writes the next history.  No atomics.
+ *
+ * Guarantees: the concatenation of a stream's pieces is, bit for bit, smi_tempo_rows of its whole input at the same p, q, N, D
+ * and window, and the frame places are equal too -- whatever the granularity of the pushes, the stream's slot, its row in a
+ * call and the other rows.  A piece's length is pure host arithmetic; nothing synchronises and nothing is copied back.  A
+ * stream is refused (SMI_EINVAL) before n passes 2^28.  All pushes of a handle must go to one HIP stream (or be ordered by the
+ * caller). */
+typedef struct smi_tempos smi_tempos;
+/* max_streams (1..4096) slots; max_chunk (1..2^24) samples a push; N, D as for smi_tempo_rows; win_host [N] float64, the
+ * window.  Synchronous (one allocation, one small copy). */
+int smi_tempos_create(int max_streams, int max_chunk, int N, int D, const double* win_host, smi_tempos** out);
+int smi_tempos_destroy(smi_tempos* h);
+/* A new stream in slot `stream` at tempo p / q (ranges as for smi_tempo_rows): n and F are zero.  Host only.  A stream closes
+ * with its last push. */
+int smi_tempos_open(smi_tempos* h, int stream, int p, int q);
+/* One chunk per row: in_dev [B][stride] f32 (row b valid for len_host[b], which may be 0), of the open streams stream_host[b],
+ * each at most once in a call; last_host[b] = 1 on a stream's last push.  out_dev [B][out_stride] f32: row b receives its piece
+ * and zeros from there to out_stride (>= 1 and >= the longest piece); it must not overlap in_dev.  pos_dev (may be null)
+ * [B][pos_stride] int32 receives the places of the frames this push made final, in order, then zeros to pos_stride (>= 1 and
+ * >= the most frames of a piece).  n_out_host [B] (may be null) receives the pieces' lengths, filled before the launch.
+ * B <= 64.  Asynchronous on `stream`.  Every argument of every row is checked before anything changes or is launched: a bad one
+ * returns SMI_EINVAL and names the argument in smi_last_error. */
+int smi_tempos_push_rows(smi_tempos* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                         const int32_t* last_host, int B, int32_t* pos_dev, long long pos_stride, float* out_dev, long long out_stride,
+                         int32_t* n_out_host, void* stream);
+/* The piece length of one push, pure host arithmetic: a stream at p / q with frame N and radius D that holds n_before samples
+ * and has emitted frames_before frames takes len samples (last = 1: its last push); n_after / frames_after (may be null)
+ * receive the counters after it (at p = q the frames are the whole frames of n, which nothing depends on).  -1 for a bad
+ * argument. */
+long long smi_tempos_piece_len(int p, int q, int N, int D, long long n_before, long long frames_before, long long len, int last,
+                               long long* n_after, long long* frames_after);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,9 @@
 //   k_tempo_search, k_tempo_ola  pitch-preserving time-scale change of rows (smi_tempo_rows; WSOLA): one block per row walks the
 //                frames in order and, where a frame is searched, stages the quantised target and candidate samples in LDS as
 //                int16 and sums exact squared differences in 64-bit integers; the overlap-add is then parallel.  No atomics.
+//   k_tempos_search, k_tempos_ola  the same for joined streams (smi_tempos_*): the frames a push makes final, walked over the
+//                stream's history followed by its new chunk with the batch kernels' own device functions (tp_place, tp_ola);
+//                histories and last places live in two sets a stream uses in turn, as the joiner's state does.
 #include <limits.h>
 
 #include <cmath>
@@ -707,11 +710,25 @@ struct TpArgs {
   TpRow r[RS_MAX_ROWS];
 };
 
-// sample i of the span, quantised for the search: clamp(rint(fl64(x) * 32767), +-32767); 0 outside the span and for a NaN.
-// Nothing outside the span is fetched.
-__device__ __forceinline__ int tp_quant(const float* __restrict__ x, long long i, int len) {
-  if (i < 0 || i >= len) return 0;
-  const double v = (double)x[i] * 32767.0;   // exact: 24 x 15 bits
+// Where the tempo kernels read samples: get(i, v) fetches sample i into v where the sequence has one and returns false where it
+// has none (such a place reads as 0 and is never fetched).  TpSpan is a row's span (smi_tempo_rows); TsSeq is a stream's history
+// followed by its new chunk (smi_tempos_push_rows).
+struct TpSpan {
+  const float* __restrict__ x;
+  int len;
+  __device__ __forceinline__ bool get(long long i, float& v) const {
+    if (i < 0 || i >= len) return false;
+    v = x[i];
+    return true;
+  }
+};
+
+// sample i, quantised for the search: clamp(rint(fl64(x) * 32767), +-32767); 0 where there is no sample and for a NaN
+template <class Src>
+__device__ __forceinline__ int tp_quant(const Src& x, long long i) {
+  float f;
+  if (!x.get(i, f)) return 0;
+  const double v = (double)f * 32767.0;   // exact: 24 x 15 bits
   if (!(v == v)) return 0;
   return (int)fmin(fmax(rint(v), -32767.0), 32767.0);
 }
@@ -721,75 +738,91 @@ __device__ __forceinline__ void tp_min(unsigned long long& d, unsigned long long
   if (d2 < d || (d2 == d && key2 < key)) { d = d2; key = key2; }
 }
 
-// One block per row; the frames in order, since t_k hangs on s_{k-1}.  A frame whose natural continuation lies within D of its
-// nominal place keeps it (what the search would return: distance 0, nothing closer to t_k).  Any other frame is searched: the
-// block stages qx[t .. t + N) and qx[a - D .. a + D + N) in LDS as int16, thread c < 2 D + 1 (then c + TP_BLOCK, ...) sums
-// (target - candidate)^2 over the N samples in a 64-bit integer -- each term below 2^32, the sum below 2^43: exact, whatever the
-// order -- and the block takes the minimum of (distance, |a + delta - t|, delta): a wave butterfly, then the waves' results from
-// LDS.  Lanes of a wave read the same target samples (a broadcast) and consecutive candidate samples.
+// s_k of frame k >= 1 from s_{k-1}, by the whole block (TP_BLOCK threads, every one returns it).  A frame whose natural
+// continuation lies within D of its nominal place keeps it (what the search would return: distance 0, nothing closer to t_k).
+// Any other frame is searched: the block stages qx[t .. t + N) and qx[a - D .. a + D + N) in LDS as int16, thread c < 2 D + 1
+// (then c + TP_BLOCK, ...) sums (target - candidate)^2 over the N samples in a 64-bit integer -- each term below 2^32, the sum
+// below 2^43: exact, whatever the order -- and the block takes the minimum of (distance, |a + delta - t|, delta): a wave
+// butterfly, then the waves' results from LDS.  Lanes of a wave read the same target samples (a broadcast) and consecutive
+// candidate samples.  tq [TP_MAX_N], cq [TP_MAX_N + 2 TP_MAX_D] and red are the block's LDS, free again on return.
+template <class Src>
+__device__ __forceinline__ long long tp_place(const Src& x, long long k, long long s_prev, int N, int D, int p, int q, int16_t* tq,
+                                              int16_t* cq, unsigned long long (*red)[TP_BLOCK / 64]) {
+  const int tid = threadIdx.x, H = N / 2, ncand = 2 * D + 1;
+  const long long ak = (k * H * p) / q;   // k H p < 2^32 * 2^15
+  const long long tk = s_prev + H;
+  const long long off = tk - ak;
+  if (off >= -D && off <= D) return tk;
+  for (int i = tid; i < N; i += TP_BLOCK) tq[i] = (int16_t)tp_quant(x, tk + i);
+  for (int i = tid; i < N + 2 * D; i += TP_BLOCK) cq[i] = (int16_t)tp_quant(x, ak - D + i);
+  __syncthreads();
+  unsigned long long best = ~0ull, bkey = ~0ull;
+  for (int c = tid; c < ncand; c += TP_BLOCK) {
+    const int16_t* cw = cq + c;
+    unsigned long long acc = 0;
+    for (int i = 0; i < N; i += 2) {
+      const uint32_t tt = *(const uint32_t*)(tq + i);   // two target samples, the same in every lane
+      const uint32_t d0 = (uint32_t)((int)(int16_t)(tt & 0xFFFFu) - (int)cw[i]);
+      const uint32_t d1 = (uint32_t)(((int)tt >> 16) - (int)cw[i + 1]);
+      acc += (unsigned long long)(d0 * d0) + (unsigned long long)(d1 * d1);   // |d| <= 65534: d^2 < 2^32, as the unsigned product gives it
+    }
+    const long long dist_t = ak + (c - D) - tk;
+    tp_min(best, bkey, acc, ((unsigned long long)(dist_t < 0 ? -dist_t : dist_t) << 32) | (unsigned long long)c);
+  }
+  for (int o = 32; o; o >>= 1) {
+    const unsigned long long d2 = (unsigned long long)__shfl_xor((long long)best, o);
+    const unsigned long long k2 = (unsigned long long)__shfl_xor((long long)bkey, o);
+    tp_min(best, bkey, d2, k2);
+  }
+  if ((tid & 63) == 0) { red[0][tid >> 6] = best; red[1][tid >> 6] = bkey; }
+  __syncthreads();
+  best = red[0][0]; bkey = red[1][0];
+  for (int w = 1; w < TP_BLOCK / 64; ++w) tp_min(best, bkey, red[0][w], red[1][w]);
+  __syncthreads();   // (red, tq and cq are free for the next searched frame)
+  return ak + ((long long)(bkey & 0xFFFFFFFFull) - D);
+}
+
+// One block per row; the frames in order, since t_k hangs on s_{k-1} (tp_place).
 __global__ __launch_bounds__(TP_BLOCK) void k_tempo_search(TpArgs a, int N, int D, const float* __restrict__ in, long long in_stride,
                                                            int32_t* __restrict__ pos, long long pos_stride) {
   __shared__ __attribute__((aligned(16))) int16_t tq[TP_MAX_N];
   __shared__ __attribute__((aligned(16))) int16_t cq[TP_MAX_N + 2 * TP_MAX_D];
   __shared__ unsigned long long red[2][TP_BLOCK / 64];
   const TpRow r = a.r[blockIdx.x];
-  const float* x = in + (size_t)blockIdx.x * in_stride + r.start;
+  const TpSpan x = {in + (size_t)blockIdx.x * in_stride + r.start, r.len};
   int32_t* ps = pos + (size_t)blockIdx.x * pos_stride;
-  const int tid = threadIdx.x, H = N / 2, ncand = 2 * D + 1;
+  const int tid = threadIdx.x;
   for (long long k = r.frames + tid; k < pos_stride; k += TP_BLOCK) ps[k] = 0;   // past the row's frames: zeros
   long long s = 0;
   for (int k = 0; k < r.frames; ++k) {
-    if (k) {
-      const long long ak = ((long long)k * H * r.p) / r.q;   // k H p < 2^26 * 2^15
-      const long long tk = s + H;
-      const long long off = tk - ak;
-      if (off >= -D && off <= D) s = tk;
-      else {
-        for (int i = tid; i < N; i += TP_BLOCK) tq[i] = (int16_t)tp_quant(x, tk + i, r.len);
-        for (int i = tid; i < N + 2 * D; i += TP_BLOCK) cq[i] = (int16_t)tp_quant(x, ak - D + i, r.len);
-        __syncthreads();
-        unsigned long long best = ~0ull, bkey = ~0ull;
-        for (int c = tid; c < ncand; c += TP_BLOCK) {
-          const int16_t* cw = cq + c;
-          unsigned long long acc = 0;
-          for (int i = 0; i < N; i += 2) {
-            const uint32_t tt = *(const uint32_t*)(tq + i);   // two target samples, the same in every lane
-            const uint32_t d0 = (uint32_t)((int)(int16_t)(tt & 0xFFFFu) - (int)cw[i]);
-            const uint32_t d1 = (uint32_t)(((int)tt >> 16) - (int)cw[i + 1]);
-            acc += (unsigned long long)(d0 * d0) + (unsigned long long)(d1 * d1);   // |d| <= 65534: d^2 < 2^32, as the unsigned product gives it
-          }
-          const long long dist_t = ak + (c - D) - tk;
-          tp_min(best, bkey, acc, ((unsigned long long)(dist_t < 0 ? -dist_t : dist_t) << 32) | (unsigned long long)c);
-        }
-        for (int o = 32; o; o >>= 1) {
-          const unsigned long long d2 = (unsigned long long)__shfl_xor((long long)best, o);
-          const unsigned long long k2 = (unsigned long long)__shfl_xor((long long)bkey, o);
-          tp_min(best, bkey, d2, k2);
-        }
-        if ((tid & 63) == 0) { red[0][tid >> 6] = best; red[1][tid >> 6] = bkey; }
-        __syncthreads();
-        best = red[0][0]; bkey = red[1][0];
-        for (int w = 1; w < TP_BLOCK / 64; ++w) tp_min(best, bkey, red[0][w], red[1][w]);
-        s = ak + ((long long)(bkey & 0xFFFFFFFFull) - D);
-        __syncthreads();   // (red, tq and cq are free for the next searched frame)
-      }
-    }
+    if (k) s = tp_place(x, k, s, N, D, r.p, r.q, tq, cq, red);
     if (tid == 0) ps[k] = (int32_t)s;
   }
 }
 
-// sample i of the span as float64; 0 outside the span, which is never fetched
-__device__ __forceinline__ double tp_sample(const float* __restrict__ x, long long i, int len) {
-  return i < 0 || i >= len ? 0.0 : (double)x[i];
+// sample i as float64; 0 where there is none
+template <class Src>
+__device__ __forceinline__ double tp_sample(const Src& x, long long i) {
+  float f;
+  return x.get(i, f) ? (double)f : 0.0;
 }
 
-// grid (tiles of TP_TILE output samples, rows): out[m] = fl32(fl64(x[s_k + j]) w[j] + fl64(x[s_{k-1} + j + H]) w[j + H]), each
-// product and the sum rounded on their own; frame 0 is the span's own first H samples; zeros from M to the stride
+// output sample j of frame k >= 1, whose place is sk and whose predecessor's sk1:
+// fl32(fl64(x[s_k + j]) w[j] + fl64(x[s_{k-1} + j + H]) w[j + H]), each product and the sum rounded on their own
+template <class Src>
+__device__ __forceinline__ float tp_ola(const Src& x, int j, int H, long long sk, long long sk1, const double* __restrict__ win) {
+  const double u0 = tp_sample(x, sk + j) * win[j];
+  const double u1 = tp_sample(x, sk1 + j + H) * win[j + H];
+  return (float)(u0 + u1);
+}
+
+// grid (tiles of TP_TILE output samples, rows): tp_ola for every sample; frame 0 is the span's own first H samples; zeros from M
+// to the stride
 __global__ __launch_bounds__(RS_BLOCK) void k_tempo_ola(TpArgs a, int N, const float* __restrict__ in, long long in_stride,
                                                         const double* __restrict__ win, const int32_t* __restrict__ pos,
                                                         long long pos_stride, float* __restrict__ out, long long out_stride) {
   const TpRow r = a.r[blockIdx.y];
-  const float* x = in + (size_t)blockIdx.y * in_stride + r.start;
+  const TpSpan x = {in + (size_t)blockIdx.y * in_stride + r.start, r.len};
   const int32_t* ps = pos + (size_t)blockIdx.y * pos_stride;
   float* y = out + (size_t)blockIdx.y * out_stride;
   const int H = N / 2;
@@ -799,14 +832,115 @@ __global__ __launch_bounds__(RS_BLOCK) void k_tempo_ola(TpArgs a, int N, const f
     float v = 0.f;
     if (m < r.m) {
       const int k = (int)(m / H), j = (int)(m - (long long)k * H);
-      if (k == 0) v = m < r.len ? x[m] : 0.f;
-      else {
-        const double u0 = tp_sample(x, (long long)ps[k] + j, r.len) * win[j];
-        const double u1 = tp_sample(x, (long long)ps[k - 1] + j + H, r.len) * win[j + H];
-        v = (float)(u0 + u1);
-      }
+      if (k == 0) (void)x.get(m, v);
+      else v = tp_ola(x, j, H, ps[k], ps[k - 1], win);
     }
     y[m] = v;
+  }
+}
+
+// ---- time-scale change of joined streams (smi_tempos_*)
+struct TsRow {
+  int32_t slot, set;        // the stream's slot; the state set this push reads (it writes the other one)
+  int32_t len, p, q;        // chunk samples; tempo p / q (p == q: a copy)
+  int32_t n_old, n_new;     // input samples before / after this push
+  int32_t f_old, f_new;     // frames emitted before / after this push
+  int32_t m_new;            // outputs emitted after this push (before it: H f_old, or n_old at p == q)
+  int32_t h0_old, h0_new;   // first input sample the read set's history holds / the written set's will hold (-1: none is written)
+};
+struct TsArgs {
+  TsRow r[RS_MAX_ROWS];
+};
+struct TsState {
+  const double* win;        // [N]
+  float* hist;              // [2][max_streams][hcap]: hist[i] = x[h0 + i], i < n - h0
+  int32_t* spos;            // [2][max_streams]: s_{k-1} of the last emitted frame
+  int32_t* work;            // [RS_MAX_ROWS][fmax + 1]: s_{f_old - 1}, then the places of this push's frames
+  int32_t max_streams, hcap, fmax;
+};
+
+// a stream's input from h0_old to n_new: the history, then the chunk.  Nothing before h0_old is ever needed (the host's
+// arithmetic, smi_tempos_piece_len); it and everything from n_new on read as 0, as the batch reads what lies beyond L.
+struct TsSeq {
+  const float* __restrict__ hist;
+  const float* __restrict__ chunk;
+  int h0, n_old, n_new;
+  __device__ __forceinline__ bool get(long long i, float& v) const {
+    if (i < h0 || i >= n_new) return false;
+    v = i < n_old ? hist[i - h0] : chunk[i - n_old];
+    return true;
+  }
+};
+
+__device__ __forceinline__ TsSeq ts_seq(const TsRow& r, const TsState& s, const float* chunk) {
+  return {s.hist + ((size_t)r.set * s.max_streams + r.slot) * s.hcap, chunk, r.h0_old, r.n_old, r.n_new};
+}
+
+// One block per row walks the row's newly final frames in order with the batch kernel's tp_place, from the s_{k-1} the stream's
+// read set holds; the places go to the row's part of `work` (behind s_{f_old - 1}, for k_tempos_ola) and to pos (may be null),
+// and the last one into the set this launch does not read.
+__global__ __launch_bounds__(TP_BLOCK) void k_tempos_search(TsArgs a, TsState s, int N, int D, const float* __restrict__ in,
+                                                            long long in_stride, int32_t* __restrict__ pos, long long pos_stride) {
+  __shared__ __attribute__((aligned(16))) int16_t tq[TP_MAX_N];
+  __shared__ __attribute__((aligned(16))) int16_t cq[TP_MAX_N + 2 * TP_MAX_D];
+  __shared__ unsigned long long red[2][TP_BLOCK / 64];
+  const TsRow r = a.r[blockIdx.x];
+  const TsSeq x = ts_seq(r, s, in + (size_t)blockIdx.x * in_stride);
+  int32_t* wk = s.work + (size_t)blockIdx.x * (s.fmax + 1);
+  int32_t* ps = pos ? pos + (size_t)blockIdx.x * pos_stride : nullptr;
+  const int tid = threadIdx.x, nf = r.f_new - r.f_old;   // nf <= fmax: checked on the host
+  if (ps)
+    for (long long k = nf + tid; k < pos_stride; k += TP_BLOCK) ps[k] = 0;
+  long long sp = r.f_old ? s.spos[(size_t)r.set * s.max_streams + r.slot] : 0;
+  if (tid == 0) wk[0] = (int32_t)sp;
+  for (int i = 0; i < nf; ++i) {
+    const long long k = (long long)r.f_old + i;
+    if (k) sp = tp_place(x, k, sp, N, D, r.p, r.q, tq, cq, red);
+    if (tid == 0) {
+      wk[i + 1] = (int32_t)sp;
+      if (ps) ps[i] = (int32_t)sp;
+    }
+  }
+  if (tid == 0) s.spos[(size_t)(1 - r.set) * s.max_streams + r.slot] = (int32_t)sp;
+}
+
+// grid (tiles of TP_TILE samples of the pieces, rows): the batch kernel's tp_ola for every sample of the row's piece, zeros from
+// there to the stride; a stream at p == q copies its chunk.  Tile 0 of a row also writes the stream's next history into the set
+// this launch does not read.
+__global__ __launch_bounds__(RS_BLOCK) void k_tempos_ola(TsArgs a, TsState s, int N, const float* __restrict__ in, long long in_stride,
+                                                         float* __restrict__ out, long long out_stride) {
+  const TsRow r = a.r[blockIdx.y];
+  const float* c = in + (size_t)blockIdx.y * in_stride;
+  const TsSeq x = ts_seq(r, s, c);
+  const int32_t* wk = s.work + (size_t)blockIdx.y * (s.fmax + 1);
+  float* y = out + (size_t)blockIdx.y * out_stride;
+  const int H = N / 2, tid = threadIdx.x;
+  const bool copy = r.p == r.q;
+  if (blockIdx.x == 0 && r.h0_new >= 0) {
+    float* hist2 = s.hist + ((size_t)(1 - r.set) * s.max_streams + r.slot) * s.hcap;
+    const int nh = r.n_new - r.h0_new;   // <= hcap: checked on the host
+    for (int i = tid; i < nh; i += RS_BLOCK) {
+      float v = 0.f;
+      (void)x.get((long long)r.h0_new + i, v);
+      hist2[i] = v;
+    }
+  }
+  const long long m_old = copy ? (long long)r.n_old : (long long)H * r.f_old;
+  const long long i0 = (long long)blockIdx.x * TP_TILE;
+  const long long end = min(out_stride, i0 + TP_TILE);
+  for (long long i = i0 + tid; i < end; i += RS_BLOCK) {
+    const long long m = m_old + i;
+    float v = 0.f;
+    if (m < r.m_new) {
+      if (copy) v = c[i];   // m_new = n_new: i < len
+      else {
+        const long long k = m / H;
+        const int j = (int)(m - k * H), f = (int)(k - r.f_old);   // 0 <= f < f_new - f_old
+        if (k == 0) (void)x.get(m, v);
+        else v = tp_ola(x, j, H, wk[f + 1], wk[f], s.win);
+      }
+    }
+    y[i] = v;
   }
 }
 
@@ -1372,6 +1506,201 @@ int smi_tempo_rows(const float* in_dev, long long in_stride, const int32_t* n_ho
   SMI_LAUNCH_CHECK();
   const int tiles = (int)((out_stride + TP_TILE - 1) / TP_TILE);
   hipLaunchKernelGGL(k_tempo_ola, dim3(tiles, B), dim3(RS_BLOCK), 0, s, A, N, in_dev, in_stride, win_dev, pos_dev, pos_stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// ---- tempo of joined streams (smi_tempos_*): the host arithmetic of include/sparkmi.h's "when a frame is final"
+#define TS_MAX_N (1LL << 28)   // input samples of one stream: M <= 2^30 and every place stay inside int32
+
+static bool ts_args(int p, int q, int N, int D) {
+  return p >= 1 && p <= 32767 && q >= 1 && q <= 32767 && p <= 4 * q && q <= 4 * p && N >= 16 && N <= TP_MAX_N && !(N & 1) && D >= 0 &&
+         D <= TP_MAX_D;
+}
+
+static long long ts_nominal(long long k, int p, int q, int H) { return (k * H * p) / q; }
+
+// R_k: the input samples a stream must hold before frame k is final
+static long long ts_ready(long long k, int p, int q, int H, int D) {
+  if (k == 0) return H;
+  const long long a = ts_nominal(k, p, q, H), b = ts_nominal(k - 1, p, q, H) + H;
+  return (a > b ? a : b) + D + 2LL * H;
+}
+
+// the first input sample frame k can still read: where the history of a stream that has emitted k frames begins
+static long long ts_hist_start(long long k, int p, int q, int H, int D) {
+  if (k == 0) return 0;
+  const long long a = ts_nominal(k, p, q, H), b = ts_nominal(k - 1, p, q, H) + H;
+  const long long lo = (a < b ? a : b) - D;
+  return lo > 0 ? lo : 0;
+}
+
+// the samples of history a stream can hold between two pushes, whatever p / q in 1/4 .. 4 (include/sparkmi.h derives it)
+static int ts_hist_cap(int N, int D) {
+  const int H = N / 2, a = 7 * H + D, b = 5 * H + 2 * D;
+  return a > b ? a : b;
+}
+
+struct TsStream {
+  int open = 0, set = 0, p = 1, q = 1;
+  long long n = 0, f = 0;   // input samples so far, frames emitted
+};
+struct smi_tempos {
+  TsState s;
+  int max_chunk, N, D;
+  DevBuf<char> pool;
+  std::vector<TsStream> streams;
+};
+
+extern "C" {
+
+long long smi_tempos_piece_len(int p, int q, int N, int D, long long n_before, long long frames_before, long long len, int last,
+                               long long* n_after, long long* frames_after) {
+  if (!ts_args(p, q, N, D) || n_before < 0 || frames_before < 0 || len < 0 || n_before > TS_MAX_N || len > TS_MAX_N) return -1;
+  if (last != 0 && last != 1) return -1;
+  const int H = N / 2;
+  const long long n = n_before + len;
+  const long long M = (n * q + p - 1) / p;
+  long long f, piece;
+  if (p == q) {   // a copy: everything at once
+    f = last ? (M ? (M - 1) / H + 1 : 0) : n / H;
+    piece = len;
+  } else if (last) {
+    f = M ? (M - 1) / H + 1 : 0;
+    piece = M - frames_before * H;
+  } else {
+    f = frames_before;
+    while ((f + 1) * H <= M && n >= ts_ready(f, p, q, H, D)) ++f;
+    piece = (f - frames_before) * H;
+  }
+  if (piece < 0 || f < frames_before) return -1;
+  if (n_after) *n_after = n;
+  if (frames_after) *frames_after = f;
+  return piece;
+}
+
+int smi_tempos_create(int max_streams, int max_chunk, int N, int D, const double* win_host, smi_tempos** out) {
+  SMI_REQUIRE(out, "smi_tempos_create: null out");
+  *out = nullptr;
+  SMI_REQUIRE(max_streams >= 1 && max_streams <= JN_MAX_STREAMS, "smi_tempos_create: max_streams=%d outside 1..%d", max_streams, JN_MAX_STREAMS);
+  SMI_REQUIRE(max_chunk >= 1 && max_chunk <= RS_MAX_SAMPLES, "smi_tempos_create: max_chunk=%d outside 1..%d", max_chunk, RS_MAX_SAMPLES);
+  SMI_REQUIRE(N >= 16 && N <= TP_MAX_N && !(N & 1), "smi_tempos_create: N=%d must be even in 16..%d", N, TP_MAX_N);
+  SMI_REQUIRE(D >= 0 && D <= TP_MAX_D, "smi_tempos_create: D=%d outside 0..%d", D, TP_MAX_D);
+  SMI_REQUIRE(win_host, "smi_tempos_create: null win_host");
+  char arch[128];
+  const int rc = smi_device_check(arch, sizeof(arch));
+  if (rc) return rc;
+  smi_tempos* h = new smi_tempos();
+  h->max_chunk = max_chunk; h->N = N; h->D = D;
+  TsState& s = h->s;
+  s.max_streams = max_streams;
+  s.hcap = ts_hist_cap(N, D);
+  s.fmax = (int)(4LL * ((long long)max_chunk + s.hcap) / (N / 2) + 4);   // frames one push can emit
+  // one allocation: the window (float64), then the two history sets (fp32), the two sets of places and the frames' work (int32)
+  const size_t f64 = (size_t)N * sizeof(double);
+  const size_t n_hist = 2 * (size_t)max_streams * s.hcap, n_pos = 2 * (size_t)max_streams, n_work = (size_t)RS_MAX_ROWS * (s.fmax + 1);
+  const size_t bytes = f64 + n_hist * sizeof(float) + (n_pos + n_work) * sizeof(int32_t);
+  if (h->pool.alloc(bytes, "smi_tempos_create: stream state")) {
+    (void)hipGetLastError();
+    delete h;
+    return SMI_ENOMEM;
+  }
+  s.win = (const double*)h->pool.get();
+  s.hist = (float*)(h->pool + f64);
+  s.spos = (int32_t*)(s.hist + n_hist);
+  s.work = s.spos + n_pos;
+  hipError_t e = hipMemset(h->pool, 0, bytes);
+  if (e == hipSuccess) e = hipMemcpy(h->pool, win_host, f64, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    smi_set_error("smi_tempos_create: upload of the window: %s", hipGetErrorString(e));
+    delete h;
+    return SMI_EHIP;
+  }
+  h->streams.assign((size_t)max_streams, TsStream{});
+  *out = h;
+  return SMI_OK;
+}
+
+int smi_tempos_destroy(smi_tempos* h) {
+  delete h;
+  return SMI_OK;
+}
+
+int smi_tempos_open(smi_tempos* h, int stream, int p, int q) {
+  SMI_REQUIRE(h, "smi_tempos_open: null handle");
+  SMI_REQUIRE(stream >= 0 && stream < h->s.max_streams, "smi_tempos_open: stream=%d outside 0..%d", stream, h->s.max_streams - 1);
+  SMI_REQUIRE(p >= 1 && p <= 32767, "smi_tempos_open: p=%d outside 1..32767", p);
+  SMI_REQUIRE(q >= 1 && q <= 32767, "smi_tempos_open: q=%d outside 1..32767", q);
+  SMI_REQUIRE(p <= 4 * q && q <= 4 * p, "smi_tempos_open: p/q = %d/%d outside 1/4..4", p, q);
+  TsStream& st = h->streams[(size_t)stream];
+  st.open = 1; st.p = p; st.q = q; st.n = 0; st.f = 0;   // (st.set goes on alternating: a first push reads no state)
+  return SMI_OK;
+}
+
+int smi_tempos_push_rows(smi_tempos* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                         const int32_t* last_host, int B, int32_t* pos_dev, long long pos_stride, float* out_dev, long long out_stride,
+                         int32_t* n_out_host, void* stream) {
+  SMI_REQUIRE(h && in_dev && stream_host && len_host && last_host && out_dev, "smi_tempos_push_rows: null argument");
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "smi_tempos_push_rows: B=%d outside 1..%d", B, RS_MAX_ROWS);
+  SMI_REQUIRE(stride >= 1, "smi_tempos_push_rows: stride=%lld must be positive", stride);
+  const TsState& s = h->s;
+  const int H = h->N / 2;
+  TsArgs A;
+  long long n_new[RS_MAX_ROWS], f_new[RS_MAX_ROWS], piece[RS_MAX_ROWS], need = 1, need_pos = 1;
+  for (int b = 0; b < B; ++b) {
+    const int id = stream_host[b];
+    SMI_REQUIRE(id >= 0 && id < s.max_streams, "smi_tempos_push_rows: stream[%d]=%d outside 0..%d", b, id, s.max_streams - 1);
+    for (int c = 0; c < b; ++c)
+      SMI_REQUIRE(stream_host[c] != id, "smi_tempos_push_rows: stream[%d]=%d is row %d's stream too (one chunk of a stream a call)", b, id, c);
+    const TsStream& st = h->streams[(size_t)id];
+    SMI_REQUIRE(st.open, "smi_tempos_push_rows: stream[%d]=%d is not open (smi_tempos_open; a stream closes with its last chunk)", b, id);
+    const int len = len_host[b], last = last_host[b];
+    SMI_REQUIRE(last == 0 || last == 1, "smi_tempos_push_rows: last[%d]=%d is neither 0 nor 1", b, last);
+    SMI_REQUIRE(len >= 0 && len <= h->max_chunk && len <= stride, "smi_tempos_push_rows: len[%d]=%d outside 0..min(max_chunk=%d, stride=%lld)", b,
+                len, h->max_chunk, stride);
+    SMI_REQUIRE(st.n + len <= TS_MAX_N, "smi_tempos_push_rows: stream[%d]=%d would reach %lld samples: 2^28 is the limit of a stream", b, id,
+                st.n + len);
+    piece[b] = smi_tempos_piece_len(st.p, st.q, h->N, h->D, st.n, st.f, len, last, &n_new[b], &f_new[b]);
+    SMI_REQUIRE(piece[b] >= 0, "smi_tempos_push_rows: len[%d]=%d gives no valid piece", b, len);
+    const bool copy = st.p == st.q;
+    const long long h0_old = copy ? st.n : ts_hist_start(st.f, st.p, st.q, H, h->D);
+    const long long h0_new = last ? -1 : copy ? n_new[b] : ts_hist_start(f_new[b], st.p, st.q, H, h->D);
+    SMI_REQUIRE(f_new[b] - st.f <= s.fmax, "smi_tempos_push_rows: len[%d]=%d makes %lld frames final, the handle holds %d a push", b, len,
+                f_new[b] - st.f, s.fmax);
+    SMI_REQUIRE(last || (h0_new >= h0_old && n_new[b] - h0_new <= s.hcap),
+                "smi_tempos_push_rows: stream[%d]=%d needs %lld samples of history, the handle keeps %d", b, id, n_new[b] - h0_new, s.hcap);
+    TsRow& r = A.r[b];
+    r.slot = id; r.set = st.set; r.len = len; r.p = st.p; r.q = st.q;
+    r.n_old = (int32_t)st.n; r.n_new = (int32_t)n_new[b]; r.f_old = (int32_t)st.f; r.f_new = (int32_t)f_new[b];
+    r.m_new = (int32_t)((copy ? st.n : st.f * H) + piece[b]);
+    r.h0_old = (int32_t)h0_old; r.h0_new = (int32_t)h0_new;
+    if (piece[b] > need) need = piece[b];
+    if (f_new[b] - st.f > need_pos) need_pos = f_new[b] - st.f;
+  }
+  SMI_REQUIRE(out_stride >= need && out_stride <= TP_MAX_OUT, "smi_tempos_push_rows: out_stride=%lld outside %lld (the longest piece)..%d",
+              out_stride, need, TP_MAX_OUT);
+  SMI_REQUIRE(!pos_dev || (pos_stride >= need_pos && pos_stride <= TP_MAX_OUT),
+              "smi_tempos_push_rows: pos_stride=%lld outside %lld (the most frames of a piece)..%d", pos_stride, need_pos, TP_MAX_OUT);
+  {
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + (size_t)B * stride * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_tempos_push_rows: out_dev overlaps in_dev");
+  }
+  for (int b = 0; b < B; ++b) {
+    TsStream& st = h->streams[(size_t)stream_host[b]];
+    if (n_out_host) n_out_host[b] = (int32_t)piece[b];
+    st.n = n_new[b]; st.f = f_new[b]; st.set ^= 1;
+    if (last_host[b]) st.open = 0;
+  }
+  hipStream_t hs = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_tempos_search, dim3(B), dim3(TP_BLOCK), 0, hs, A, s, h->N, h->D, in_dev, stride, pos_dev, pos_stride);
+  SMI_LAUNCH_CHECK();
+  const int tiles = (int)((out_stride + TP_TILE - 1) / TP_TILE);
+  hipLaunchKernelGGL(k_tempos_ola, dim3(tiles, B), dim3(RS_BLOCK), 0, hs, A, s, h->N, in_dev, stride, out_dev, out_stride);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

@@ -19,6 +19,8 @@ rows after ITU-R BS.1770 and the gain that brings each to a target under a peak 
 ``DeviceAudio.tempo_rows`` (``smi_tempo_rows``) changes the speaking rate of rows at unchanged pitch: WSOLA whose similarity
 search is exact integer arithmetic, so the device is held to ``tests/tempo_ref.py`` bit for bit.  ``tempo_ratio``,
 ``tempo_frame`` and ``tempo_window`` give its rational, its frame and radius for a sample rate, and its window.
+``StreamTempo`` (``smi_tempos_*``) is its streaming form: the frame places and an input history are kept on the device per
+stream, and the pieces' concatenation is ``tempo_rows`` of the whole stream bit for bit, whatever the chunking.
 """
 from __future__ import annotations
 
@@ -538,6 +540,139 @@ class StreamJoiner:
         if not self._fake:
             assert got_all == want, (got_all, want)
         return out, want
+
+    def _stream(self) -> C.c_void_p:
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class StreamTempo:
+    """Owns one ``smi_tempos`` handle (include/sparkmi.h): the speaking rate of joined streams is changed at unchanged pitch while
+    they are still arriving -- WSOLA with the frame places and an input history kept on the device per stream, so that the
+    concatenation of a stream's pieces is, bit for bit, ``DeviceAudio.tempo_rows`` of its whole input, whatever the chunking.
+    Request keys map to the handle's stream slots as in ``StreamJoiner``: ``open(key, p, q)`` takes a free slot, ``push`` sends
+    one poll's chunks, and a key's slot is free again after its last push.  A key that ``push`` meets unopened is opened at
+    1/1, which copies its chunks with no latency.  ``frame`` = (N, D) (``tempo_frame``).  All pushes go to the current HIP
+    stream at the time of the call: keep them on one stream.  ``lib``: a stand-in library (tests watch the bookkeeping)."""
+
+    def __init__(self, max_streams: int, max_chunk: int, frame: Tuple[int, int], device="cuda:0", diag: bool = False, lib=None):
+        from .streaming import tempo_history
+        self._lib = lib if lib is not None else _lib.pick(diag)
+        self._fake = lib is not None
+        self.device = device
+        if not self._fake:
+            import torch
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise _lib.SparkMIError("StreamTempo runs on an MI355X only (device must be cuda:N); there is no CPU path")
+        self.max_streams, self.max_chunk = int(max_streams), int(max_chunk)
+        self.N, self.D = int(frame[0]), int(frame[1])
+        self.history = tempo_history(self.N, self.D)
+        win = np.ascontiguousarray(tempo_window(self.N), dtype=np.float64)
+        self._h = C.c_void_p()
+        self._lib.check(self._lib.smi_tempos_create(self.max_streams, self.max_chunk, self.N, self.D,
+                                                    win.ctypes.data_as(C.POINTER(C.c_double)), C.byref(self._h)), "smi_tempos_create")
+        self._free: List[int] = list(range(self.max_streams))   # (open() hands out the lowest free slot)
+        self._open: dict = {}       # key -> [slot, p, q, n, frames emitted]
+        self.calls = 0              # smi_tempos_push_rows calls so far: two launches each
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.smi_tempos_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """forget every open key (an abandoned stream's slots come back)"""
+        self._free = list(range(self.max_streams))
+        self._open = {}
+
+    def slot(self, key) -> Optional[int]:
+        return self._open[key][0] if key in self._open else None
+
+    def open(self, key, p: int = 1, q: int = 1) -> int:
+        if key in self._open:
+            raise ValueError(f"request {key}: already open")
+        if not self._free:
+            raise ValueError(f"StreamTempo: all {self.max_streams} stream slots are in use")
+        s = min(self._free)
+        self._lib.check(self._lib.smi_tempos_open(self._h, s, int(p), int(q)), "smi_tempos_open")
+        self._free.remove(s)
+        self._open[key] = [s, int(p), int(q), 0, 0]
+        return s
+
+    def piece_lengths(self, rows: Sequence[Tuple]) -> List[int]:
+        """the piece lengths ``push(x, rows)`` would return, without pushing (pure host arithmetic)"""
+        from .streaming import tempo_piece_len
+        state = {k: list(v) for k, v in self._open.items()}
+        out = []
+        for key, length, last in rows:
+            st = state.setdefault(key, [None, 1, 1, 0, 0])
+            piece, st[3], st[4] = tempo_piece_len(st[1], st[2], self.N, self.D, st[3], st[4], length, last)
+            out.append(piece)
+        return out
+
+    def push(self, x, rows: Sequence[Tuple], return_places: bool = False):
+        """``x``: [B][stride] float32 on the device, row b the new samples of request ``rows[b] = (key, length, last)``.
+        Returns (out [B][out_stride] float32 on the device -- row b holds its piece, then zeros --, the pieces' lengths); a
+        length may be 0.  ``return_places``: also (pos [B][frames] int32 on the device, the places of the frames each push made
+        final, and their counts).  A request that appears twice makes two device calls (``streaming.split_calls``), each two
+        launches; everything is enqueued on the current stream, nothing waits and nothing is copied back."""
+        from .streaming import split_calls, tempo_piece_len
+        B = len(rows)
+        if not B:
+            raise ValueError("push takes at least one row")
+        if not self._fake:
+            import torch
+            if x.dim() != 2 or x.shape[0] != B or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+                raise ValueError("push takes a contiguous [B][stride] float32 tensor on the device, one row per chunk")
+        for _, length, _ in rows:
+            if not 0 <= int(length) <= self.max_chunk:
+                raise ValueError(f"a chunk of {length} samples is outside 0..max_chunk={self.max_chunk}")
+        want = self.piece_lengths(rows)      # raises for a bad length before anything is opened or pushed
+        for key, _, _ in rows:
+            if key not in self._open:
+                self.open(key)
+        nf, state = [], {k: list(v) for k, v in self._open.items()}
+        for key, length, last in rows:       # the frames every push makes final, for the places
+            st = state[key]
+            f0 = st[4]
+            _, st[3], st[4] = tempo_piece_len(st[1], st[2], self.N, self.D, st[3], st[4], length, last)
+            nf.append(st[4] - f0)
+        stride, pstride = max(1, max(want)), max(1, max(nf))
+        in_stride = 1 if self._fake else int(x.shape[1])
+        out = pos = None
+        if not self._fake:
+            out = torch.empty((B, stride), dtype=torch.float32, device=self.device)
+            if return_places:
+                pos = torch.empty((B, pstride), dtype=torch.int32, device=self.device)
+        got_all: List[int] = []
+        for a, b in split_calls([r[0] for r in rows]):
+            n = b - a
+            i32 = lambda v: (C.c_int32 * n)(*[int(t) for t in v])   # noqa: E731
+            got = (C.c_int32 * n)()
+            src = C.c_void_p(0 if self._fake else x.data_ptr() + 4 * a * in_stride)
+            dst = C.c_void_p(0 if self._fake else out.data_ptr() + 4 * a * stride)
+            pdst = C.c_void_p(0 if pos is None else pos.data_ptr() + 4 * a * pstride)
+            self._lib.check(self._lib.smi_tempos_push_rows(self._h, src, in_stride, i32(self._open[r[0]][0] for r in rows[a:b]),
+                                                           i32(r[1] for r in rows[a:b]), i32(bool(r[2]) for r in rows[a:b]), n, pdst,
+                                                           pstride, dst, stride, got, None if self._fake else self._stream()),
+                            "smi_tempos_push_rows")
+            self.calls += 1
+            got_all += list(got)
+            for key, length, last in rows[a:b]:
+                st = self._open[key]
+                _, st[3], st[4] = tempo_piece_len(st[1], st[2], self.N, self.D, st[3], st[4], length, last)
+                if last:
+                    self._free.append(self._open.pop(key)[0])
+        if not self._fake:
+            assert got_all == want, (got_all, want)
+        return (out, want, pos, nf) if return_places else (out, want)
 
     def _stream(self) -> C.c_void_p:
         import torch

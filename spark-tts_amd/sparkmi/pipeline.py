@@ -12,7 +12,8 @@ calls take ``joined=True`` for contiguous, playable pieces at any output rate (t
 ``inference_long`` / ``inference_long_stream`` (text of any length: sentences as the rows of one in-flight session, their
 waveforms trimmed and joined on the device); ``loudness`` / ``peak_ceiling`` / ``max_gain_db`` on every call that returns whole
 utterances (the output at a programme loudness after BS.1770, measured and scaled on the device); ``tempo`` on the same calls
-(a pitch-preserving change of the speaking rate, 0.5 .. 2.0, on the device before the loudness stage).
+(a pitch-preserving change of the speaking rate, 0.5 .. 2.0, on the device before the loudness stage) and, with
+``joined=True``, on the two streaming calls (the same arithmetic with its state carried across the chunks on the device).
 """
 from __future__ import annotations
 
@@ -310,8 +311,66 @@ class SparkTTS:
     @staticmethod
     def _no_stream_tempo(tempo, who: str) -> None:
         if tempo is not None:
-            raise ValueError(f"{who}: tempo is not supported for chunked streams (a time-scale change across chunk edges needs "
-                             "carried state); use inference / inference_batch / serve / inference_long / inference_long_stream")
+            raise ValueError(f"{who}: tempo is not supported for overlapping chunks (a time-scale change across chunk edges needs "
+                             "carried state); pass joined=True for contiguous pieces at that tempo, or use inference / "
+                             "inference_batch / serve / inference_long / inference_long_stream")
+
+    def _stream_stages(self, who: str, output_sample_rate: Optional[int], max_streams: int, audio_chunk_duration: float,
+                       max_audio_chunk_duration: float, audio_chunk_size_scale_factor: float, audio_chunk_overlap_duration: float):
+        """The stages of a ``joined=True`` call with a tempo, in the batch path's order, their slots all free: (the crossfade -- a
+        ``StreamJoiner`` at 1/1 --, the ``StreamTempo``, and with ``output_sample_rate`` the resampler with state -- a second
+        ``StreamJoiner`` with overlap 0 at that ratio, which is plain concatenation plus the filter --, else None).  Everything is
+        checked before any device call."""
+        from .audio import StreamJoiner, StreamTempo, tempo_frame
+        out_ratio = self._output_ratio(output_sample_rate)
+        fade = self._stream_joiner(who, None, max_streams, audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor,
+                                   audio_chunk_overlap_duration)
+        frame = tempo_frame(self.sample_rate)
+        key = (int(max_streams), fade.max_chunk, frame)
+        if getattr(self, "_tempos", None) is None:
+            self._tempos = {}
+        if key not in self._tempos:
+            self._tempos[key] = StreamTempo(*key, device=self.device)
+        scale = self._tempos[key]
+        scale.reset()
+        rate = None
+        if out_ratio is not None:   # a push of the tempo stage emits at most 4 (history + chunk) + N samples (include/sparkmi.h)
+            key = (int(max_streams), 4 * (scale.history + scale.max_chunk) + scale.N, 0) + tuple(out_ratio)
+            if key not in self._joiners:
+                self._joiners[key] = StreamJoiner(*key, device=self.device)
+            rate = self._joiners[key]
+            rate.reset()
+        return fade, scale, rate
+
+    def _staged_push(self, stages, x, rows: Sequence[Tuple]):
+        """One poll's ready chunks ``rows[b] = (key, length, last)`` (``x`` [B][stride] on the device) through the stages of
+        ``_stream_stages``, all enqueued on the current stream: (rows on the device, {b: its row there}, the final pieces'
+        lengths, the pieces' lengths behind the tempo stage -- what a listener hears, at the model's rate).  A stage is skipped
+        for a push whose piece from the stage before is empty, unless it is the stream's last: its later pieces are empty."""
+        cur, lens = stages[0].push(x, rows)
+        lens = list(lens)
+        at = {b: b for b in range(len(rows))}
+        heard = lens
+        for stage in stages[1:]:
+            if stage is None:
+                continue
+            go = [b for b in sorted(at) if lens[b] > 0 or rows[b][2]]
+            for b in at:
+                if b not in go:
+                    lens[b] = 0
+            if not go:
+                at = {}
+            else:
+                src = [at[b] for b in go]
+                if src != list(range(cur.shape[0])):
+                    cur = cur[torch.tensor(src, device=self.device)].contiguous()
+                cur, got = stage.push(cur, [(rows[b][0], lens[b], rows[b][2]) for b in go])
+                at = {b: i for i, b in enumerate(go)}
+                for b, v in zip(go, got):
+                    lens[b] = v
+            if stage is stages[1]:
+                heard = list(lens)
+        return cur, at, lens, heard
 
     @staticmethod
     def _no_stream_rate(output_sample_rate: Optional[int], who: str) -> None:
@@ -593,13 +652,28 @@ class SparkTTS:
 
         There is no ``loudness`` here: the integrated loudness of BS.1770 is a property of the whole utterance, which a
         chunk that must leave before the utterance ends cannot know (``inference`` / ``inference_long_stream`` take it).
-        Nor is there a ``tempo``: a time-scale change across chunk edges needs state carried from chunk to chunk, which is out
-        of scope; a given ``tempo`` is refused (ValueError).  ``inference`` / ``inference_long_stream`` take it."""
-        self._no_stream_tempo(tempo, "inference_stream")
+
+        ``tempo`` (0.5 .. 2.0, to a hundredth; > 1: faster; None or 1.0: nothing new is built or launched) needs
+        ``joined=True``: the joined stream's speaking rate is changed at unchanged pitch while it is still arriving (WSOLA with
+        the frame places and an input history carried on the device; include/sparkmi.h, smi_tempos_*; ``audio.StreamTempo``).
+        The stages run in the batch path's order on the device -- crossfade, tempo, then with ``output_sample_rate`` the
+        resampler with state -- and only the final pieces are copied.  The pieces' concatenation is, bit for bit,
+        ``DeviceAudio.tempo_rows`` of the concatenated ``joined=True`` pieces without tempo (and ``resample_rows`` of that), so
+        it does not depend on the chunking; a piece holds back up to N + D + H samples of its input (63 ms at 16 kHz) for the
+        frames that are not final yet, and the last piece brings them.  With
+        ``joined=False`` a given ``tempo`` is refused (ValueError): overlapping chunks have no edges to carry state across."""
         if not joined:
+            self._no_stream_tempo(tempo, "inference_stream")
             self._no_stream_rate(output_sample_rate, "inference_stream")
-        joiner = self._stream_joiner("inference_stream", output_sample_rate, 1, audio_chunk_duration, max_audio_chunk_duration,
-                                     audio_chunk_size_scale_factor, audio_chunk_overlap_duration) if joined else None
+        rate = self._tempo_ratios([{}], tempo)[0]
+        sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
+        stages = None
+        if joined and rate is not None:
+            stages = self._stream_stages("inference_stream", output_sample_rate, 1, *sched_args)
+            joiner = stages[0]
+            stages[1].open(0, *rate)
+        else:
+            joiner = self._stream_joiner("inference_stream", output_sample_rate, 1, *sched_args) if joined else None
         if gender is not None:
             prompt, glob = self.process_prompt_control(gender, pitch, speed, text), None
         else:
@@ -626,6 +700,9 @@ class SparkTTS:
                 wav = voc.detokenize(torch.tensor([chunk], dtype=torch.long), glob.reshape(1, 1, -1), lengths=[len(chunk)]).reshape(1, -1)
             else:
                 wav = torch.zeros((1, 1), dtype=torch.float32, device=self.device)
+            if stages is not None:
+                out, at, lens, _ = self._staged_push(stages, wav, [(0, len(chunk) * hop, last)])
+                return out[at[0], : lens[0]].cpu().numpy().copy() if 0 in at else np.zeros(0, dtype=np.float32)
             out, lens = joiner.push(wav, [(0, len(chunk) * hop, last)])
             return out[0, : lens[0]].cpu().numpy().copy()
 
@@ -839,23 +916,41 @@ class SparkTTS:
         (ValueError, before any device call) if the first chunk is shorter than two overlaps.
 
         There is no ``loudness`` here, as in ``inference_stream``: integrated loudness needs the whole utterance (``serve``
-        takes it).  Nor a ``tempo``, in the call or in a request: tempo across chunk edges needs carried state and is out of
-        scope; it is refused (ValueError), and ``serve`` takes it."""
-        self._no_stream_tempo(tempo, "serve_stream")
+        takes it).
+
+        ``tempo`` and a request's own ``tempo`` key, which overrides it (0.5 .. 2.0; None or 1.0 everywhere: nothing new is
+        built or launched and every piece keeps its bits), need ``joined=True``; with ``joined=False`` either is refused
+        (ValueError).  Every request's joined stream then goes through a tempo stream of its own (include/sparkmi.h,
+        smi_tempos_*; ``audio.StreamTempo``) behind the crossfade and, with ``output_sample_rate``, through the resampler with
+        state behind that -- all on the vocoder's stream, two launches more per poll (four with a rate), the rows never
+        leaving the device.  A request without a tempo in such a call goes through a stream at 1/1, which copies with no
+        latency.  Per request the pieces' concatenation is, bit for bit, ``DeviceAudio.tempo_rows`` of its pieces without
+        tempo (then ``resample_rows`` of that), whoever else is live, with or without parking: the stages' state is keyed by
+        request like the joiner's, and a parked request's tempo stream stays open.  The ``Pacer`` then counts the seconds a
+        listener receives: the scaled piece's length at the model's rate.  Whether a call has the stages is settled when it
+        begins, from ``tempo`` and, where ``requests`` is a list, its requests; a request that brings a tempo of its own from
+        an iterator into a call without them is refused (ValueError): pass a list, or a ``tempo`` for the call."""
         if not joined:
+            self._no_stream_tempo(tempo, "serve_stream")
             self._no_stream_rate(output_sample_rate, "serve_stream")
+        call_rate = self._tempo_ratios([{}], tempo)[0]
+        rates: Dict[int, Tuple[int, int]] = {}   # request index -> its tempo as (p, q), (1, 1) without one
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
-                for k in (FORK_KEY, TEMPO_KEY) + tuple(LOGPROB_KEYS):
+                for k in (FORK_KEY,) + (() if joined else (TEMPO_KEY,)) + tuple(LOGPROB_KEYS):
                     if k in r:
-                        raise ValueError(f"request {i}: {k} is not supported by serve_stream")
+                        raise ValueError(f"request {i}: {k} is not supported by serve_stream" + (
+                            " with overlapping chunks; pass joined=True" if k == TEMPO_KEY else ""))
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
+                rates[i] = self._tempo_ratios([r], tempo, i)[0] or (1, 1)
                 yield r
 
+        staged = call_rate is not None
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
             for _ in checked(requests):
                 pass
+            staged = staged or any(v != (1, 1) for v in rates.values())
         decode_stride = int(decode_stride)
         if decode_stride < 1:
             raise ValueError("decode_stride must be >= 1")
@@ -875,14 +970,22 @@ class SparkTTS:
                         audio_chunk_duration=audio_chunk_duration, max_audio_chunk_duration=max_audio_chunk_duration,
                         audio_chunk_size_scale_factor=audio_chunk_size_scale_factor,
                         audio_chunk_overlap_duration=audio_chunk_overlap_duration)
-        joiner = self._stream_joiner("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), audio_chunk_duration,
-                                     max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration) if joined else None
+        sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
+        stages = None
+        if joined and staged:
+            stages = self._stream_stages("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args)
+            joiner = stages[0]
+        else:
+            joiner = self._stream_joiner("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args) if joined else None
         if getattr(self, "_voc_stream", None) is None:
             self._voc_stream = torch.cuda.Stream(device=self.device)
         vs = self._voc_stream
 
         def llm_requests():
             for i, r in enumerate(checked(requests)):
+                if stages is None and rates[i] != (1, 1):
+                    raise ValueError(f"request {i}: a tempo of its own from an iterator of requests, in a serve_stream call that began "
+                                     "without the tempo stages; pass the requests as a list, or a tempo for the call")
                 if r.get("gender") is not None:
                     prompt, g = self.process_prompt_control(r["gender"], r.get("pitch"), r.get("speed"), r["text"]), None
                 else:
@@ -914,20 +1017,27 @@ class SparkTTS:
                         at = iter(range(len(rows)))
                         idx = torch.tensor([next(at) if c[2] else len(rows) for c in chunks], device=self.device)
                         x = torch.cat([x, torch.zeros((1, x.shape[1]), dtype=torch.float32, device=self.device)])[idx].contiguous()
+                    if stages is not None:   # crossfade, tempo and the resampler, each with its state, one behind the other
+                        return chunks, (x,) + self._staged_push(stages, x, [(c[0], len(c[2]) * hop, c[3]) for c in chunks])
                     out, n_out = joiner.push(x, [(c[0], len(c[2]) * hop, c[3]) for c in chunks])
                 return chunks, (x, out, n_out)
             return chunks, wav
 
         def collect_joined(job):
-            chunks, (_, out, n_out) = job
+            chunks, (_, out, *rest) = job
+            at, n_out, heard = rest if stages is not None else ({b: b for b in range(len(chunks))}, rest[0], None)
             with torch.cuda.stream(vs):
                 out = out.cpu().numpy()
             for b, (key, index, sem, last) in enumerate(chunks):
                 if pacer.active:
-                    pacer.yielded(key, max(0, len(sem) - (overlap if index else 0)))
+                    frames = max(0, len(sem) - (overlap if index else 0))
+                    if heard is None:
+                        pacer.yielded(key, frames)
+                    else:                 # what the listener receives: the scaled piece at the model's rate
+                        pacer.yielded(key, frames, heard[b] / self.sample_rate)
                     if last:
                         pacer.close(key)
-                yield key, out[b, : n_out[b]].copy(), last
+                yield key, (out[at[b], : n_out[b]].copy() if b in at else np.zeros(0, dtype=np.float32)), last
 
         def collect(job):     # the host waits for the vocoder's stream only
             if joiner is not None:
@@ -980,6 +1090,8 @@ class SparkTTS:
                     for slot, r in zip(slots, batch):
                         live[slot] = [r[0], int(r[2]), 0]
                         mux.open(r[0], r[3])
+                        if stages is not None:   # (host only; a request without a tempo copies through at 1/1)
+                            stages[1].open(r[0], *rates[r[0]])
                 self.model.decode(decode_stride)   # enqueued: it runs while the host collects the previous poll's chunks
                 if job is not None:
                     yield from collect(job)

@@ -11,7 +11,9 @@ cross-fades consecutive chunks over the overlap (``runtime/triton_trtllm/client_
 ``SparkTTS.inference_stream`` (pipeline.py) drives the HIP LLM and vocoder with them.  ``StreamMux`` is the same logic for many
 requests at once -- the decoupled chunk loop answering every live request of an in-flight batch (run.sh:49-65) -- and
 ``SparkTTS.serve_stream`` drives it.  ``join_piece_len``, ``join_history`` and ``split_calls`` are the host arithmetic of the
-device-side stream joiner (``joined=True``; include/sparkmi.h, smi_join_*), which does on the device what ``crossfade`` does here.
+device-side stream joiner (``joined=True``; include/sparkmi.h, smi_join_*), which does on the device what ``crossfade`` does here;
+``tempo_piece_len``, ``tempo_ready``, ``tempo_history_start`` and ``tempo_history`` are that of the tempo stage behind it
+(smi_tempos_*): when a frame of a stream that is still arriving is final.
 """
 from __future__ import annotations
 
@@ -123,7 +125,66 @@ def split_calls(keys: Sequence[Hashable], max_rows: int = JOIN_MAX_ROWS) -> List
     return out
 
 
-def stream_chunks(token_iter: Iterator[Sequence[int]], scheduler: ChunkScheduler) -> Iterator[List[int]]:
+# ---- tempo of joined streams (include/sparkmi.h, smi_tempos_*): when a frame is final, as host arithmetic
+def _tempo_nominal(k: int, p: int, q: int, H: int) -> int:
+    return (k * H * p) // q
+
+
+def tempo_ready(k: int, p: int, q: int, N: int, D: int) -> int:
+    """R_k: the input samples a stream must hold before frame ``k`` is final -- H for frame 0, else
+    ``max(a_k, a_{k-1} + H) + D + N``"""
+    H = int(N) // 2
+    if k == 0:
+        return H
+    return max(_tempo_nominal(k, p, q, H), _tempo_nominal(k - 1, p, q, H) + H) + int(D) + int(N)
+
+
+def tempo_history_start(frames: int, p: int, q: int, N: int, D: int) -> int:
+    """the first input sample a stream that has emitted ``frames`` frames still needs: ``max(0, min(a_F, a_{F-1} + H) - D)``,
+    0 before the first frame, and everything is behind a stream at p = q"""
+    H = int(N) // 2
+    if frames == 0:
+        return 0
+    return max(0, min(_tempo_nominal(frames, p, q, H), _tempo_nominal(frames - 1, p, q, H) + H) - int(D))
+
+
+def tempo_history(N: int, D: int) -> int:
+    """input samples of history a tempo stream keeps, enough for every p / q in 1/4 .. 4: ``max(7 H + D, 5 H + 2 D)``"""
+    H = int(N) // 2
+    return max(7 * H + int(D), 5 * H + 2 * int(D))
+
+
+def tempo_piece_len(p: int, q: int, N: int, D: int, n_before: int, frames_before: int, length: int, last: bool) -> Tuple[int, int, int]:
+    """(piece length, n after, frames after) of one push -- the twin of ``smi_tempos_piece_len``: a stream at tempo p / q that
+    holds ``n_before`` input samples and has emitted ``frames_before`` frames of H = N / 2 outputs takes ``length`` more.  A
+    stream that goes on emits the longest prefix of frames k with ``n >= tempo_ready(k)`` and ``(k + 1) H <= ceil(n q / p)``; a
+    finished one has emitted ``ceil(n q / p)``; at p = q the piece is the chunk.  ValueError for a bad argument."""
+    p, q, N, D, n_before, frames_before, length = int(p), int(q), int(N), int(D), int(n_before), int(frames_before), int(length)
+    if not (1 <= p <= 32767 and 1 <= q <= 32767 and p <= 4 * q and q <= 4 * p):
+        raise ValueError(f"tempo p/q = {p}/{q} outside 1/4..4 with 1 <= p, q <= 32767")
+    if N < 16 or N > 2048 or N % 2 or not 0 <= D <= 1024:
+        raise ValueError(f"frame N={N} must be even in 16..2048 and the radius D={D} in 0..1024")
+    if n_before < 0 or frames_before < 0 or length < 0:
+        raise ValueError("negative counter or length")
+    H = N // 2
+    n = n_before + length
+    M = -((-n * q) // p)
+    whole = (M - 1) // H + 1 if M else 0
+    if p == q:
+        return length, n, (whole if last else n // H)
+    if last:
+        f, piece = whole, M - frames_before * H
+    else:
+        f = frames_before
+        while (f + 1) * H <= M and n >= tempo_ready(f, p, q, N, D):
+            f += 1
+        piece = (f - frames_before) * H
+    if piece < 0:
+        raise ValueError(f"{frames_before} frames cannot have left a stream of {n} samples")
+    return piece, n, f
+
+
+def stream_chunks(token_iter:Iterator[Sequence[int]], scheduler: ChunkScheduler) -> Iterator[List[int]]:
     """Token increments in, ready chunks out (the generator form of the reference loop)."""
     for inc in token_iter:
         if inc is None or len(inc) == 0:
@@ -311,12 +372,14 @@ class Pacer:
         self.parks = 0
         self.resumes = 0
 
-    def yielded(self, key: Hashable, frames: int) -> None:
-        """A chunk of ``frames`` new audio frames of request ``key`` has just been handed to its listener."""
+    def yielded(self, key: Hashable, frames: int, seconds: Optional[float] = None) -> None:
+        """A chunk of ``frames`` new audio frames of request ``key`` has just been handed to its listener.  ``seconds``: the
+        audio the listener actually received, where that is not ``frames / frame_rate`` (a piece at a tempo); it is counted in
+        place of the frames."""
         if key not in self._first:
             self._first[key] = self.clock()
             self._frames[key] = 0
-        self._frames[key] += int(frames)
+        self._frames[key] += int(frames) if seconds is None else float(seconds) * self.frame_rate
 
     def close(self, key: Hashable) -> None:
         self._first.pop(key, None)
