@@ -1029,9 +1029,10 @@ class SparkLLM:
 
     def debug_fused_o(self) -> bool:
         """One live row in slot 0 takes the fused attention + o_proj kernel (smi_llm.hip: fuse_o_now) unless SPARKMI_NO_FUSE_O=1 was set
-        when the engine was built or the head count has no fused instantiation."""
+        when the engine was built, the head count has no fused instantiation, or the engine is in the exact-weights mode (every
+        GEMM on k_gemm_x, the o_proj included: smi_llm_create leaves fuse_o off)."""
         import os
-        return os.environ.get("SPARKMI_NO_FUSE_O") is None and self.cfg.num_attention_heads in (4, 14)
+        return os.environ.get("SPARKMI_NO_FUSE_O") is None and self.cfg.num_attention_heads in (4, 14) and not self._cs.weights_exact
 
     def debug_sample(self, logits_row: Optional[np.ndarray], n_rows: int, seed: int, use_bound: bool = True) -> np.ndarray:
         """The device sampler alone on a caller's logits row (``smi_llm_debug_sample``): ``n_rows`` independent draws with

@@ -191,7 +191,8 @@ def head_model(W, gamma, x, eps=EPS, exact=False, corrupt=None):
     """The kernels' arithmetic in numpy float32: per wave (k tiles j = w, w + 4, ..) three accumulator chains over the hi, mid
     and lo terms, `(lo + mid) + hi`, the in-order add of the four waves, times r.  (A k tile's 32 products are summed by numpy's
     fp32 dot, not in the matrix unit's internal order: a faithful model of the roundings, not of the bits.)  exact: one chain
-    over k in the 4-wide steps of the fp32 matrix instruction.  ``corrupt``: one of CORRUPT_LOGITS."""
+    over k in the 4-wide steps of the fp32 matrix instruction, on the operand rebuilt as (hi + mid) + lo -- one line shared by every
+    epilogue of k_gemm_x ("drop_lo" there: g -> hi + mid).  ``corrupt``: one of CORRUPT_LOGITS."""
     W = np.asarray(W, np.float32)
     x = np.asarray(x, np.float32)
     gam = np.ones_like(gamma, dtype=np.float32) if corrupt == "no_gamma" else np.asarray(gamma, np.float32)
@@ -207,6 +208,9 @@ def head_model(W, gamma, x, eps=EPS, exact=False, corrupt=None):
     if corrupt == "drop_wave":
         skip = {j for j in range(KT) if j % NW == (KT - 1) % NW}
     if exact:
+        if corrupt == "drop_lo":               # the rebuilt operand x = (hi + mid) + lo without its lo term
+            hi, mid, _ = split3(g)
+            g = (hi + mid).astype(np.float32)
         acc = np.zeros((M, W.shape[0]), np.float32)
         for k0 in range(0, K, 4):
             if k0 // 32 in skip:

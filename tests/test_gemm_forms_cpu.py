@@ -101,3 +101,34 @@ def test_names_between_traced_row_counts(golden):
                 got = [f.kernel for f in _forms(shape, "bf16", M, layer)]
                 want = [f.kernel for f in _forms(shape, "bf16", below, layer)]
                 assert got == want, (shape, M, below, layer)
+
+
+def test_exact_weights_mode_picks_k_gemm_x_everywhere():
+    """exact = 1 (smi_llm_cfg.weights_exact): at every M in 1 .. 64, either cache type and the first / middle / last
+    layer all five GEMMs are k_gemm_x<PRO,EPI,kv> -- never a bf16 form -- on grid ((NT + 3) / 4, ceil(M / 16)) with 256 threads, one
+    launch and no dynamic LDS; the o_proj is there even at one row in slot 0 (the mode has no fused attention + o_proj).  The golden
+    trace has no exact case and stays as it is."""
+    PRO_PLAIN, PRO_NORM, EPI_RESID, EPI_SWIGLU, EPI_QKV, EPI_LM = 0, 1, 0, 1, 2, 3
+    for shape in ("tiny", "half"):
+        c = _shape(shape)
+        Q, KV = c.num_attention_heads * c.head_dim, c.num_key_value_heads * c.head_dim
+        nts = [(Q + 2 * KV) // 16, c.hidden_size // 16, 2 * c.intermediate_size // 16, c.hidden_size // 16, (c.vocab_size + 15) // 16]
+        for kv in ("bf16", "f32"):
+            kvf = int(kv == "f32")
+            names = [f"k_gemm_x<{PRO_NORM},{EPI_QKV},{kvf}>", f"k_gemm_x<{PRO_PLAIN},{EPI_RESID},0>", f"k_gemm_x<{PRO_NORM},{EPI_SWIGLU},0>",
+                     f"k_gemm_x<{PRO_PLAIN},{EPI_RESID},0>", f"k_gemm_x<{PRO_NORM},{EPI_LM},0>"]
+            for M in range(1, 65):
+                for layer in LAYERS:
+                    forms = _forms(shape, kv, M, layer, exact=1)
+                    for i, f in enumerate(forms):
+                        got = (f.kernel.decode(), f.grid[0], f.grid[1], f.block, f.launches, f.lds_bytes)
+                        want = (names[i], (nts[i] + 3) // 4, (M + 15) // 16, 256, 1, 0)
+                        assert got == want, (shape, kv, M, layer, i, got, want)
+                    assert [f.kernel for f in _forms(shape, kv, M, layer, exact=1, fused=1)] == [f.kernel for f in forms], "fused o_proj in the exact mode"
+        # the config's own field gives the same picks as the flag
+        cs = llm_cfg_struct(c, 64, 576, "bf16", False, weights_exact=True)
+        out = (_lib.GemmFormInfo * 5)()
+        d = _lib.diag()
+        d.check(d.smi_llm_gemm_forms(C.byref(cs), 1, _lib.SMI_LAYER_FIRST, C.byref(_lib.GemmFlags()), out), "smi_llm_gemm_forms")
+        assert [f.kernel for f in out] == [f.kernel for f in _forms(shape, "bf16", 1, _lib.SMI_LAYER_FIRST, exact=1)]
+        assert out[1].launches == 1 and _forms(shape, "bf16", 1, _lib.SMI_LAYER_FIRST)[1].launches == 0, "one row: only the bf16 path fuses the o_proj away"

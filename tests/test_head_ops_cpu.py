@@ -7,7 +7,7 @@
   * the launch forms the GPU cases name cover every form launch_one(KLM) has.
 
 Which inputs carry which corruption: the five logits corruptions run on the seeded rows of every shape; `drop_lo` on rows whose lo terms are all positive, at
-hidden 32 (from 128 on the whole lo chain is below the bound); `tie_high` on the planted pairs of every shape; `ignore_last_vtile` on the row whose maximum is planted alone in the last vocabulary tile;
+hidden 32 (from 128 on the whole lo chain is below the bound), for the bf16 kernels' lo chain and for the exact-weights kernel's rebuilt operand; `tie_high` on the planted pairs of every shape; `ignore_last_vtile` on the row whose maximum is planted alone in the last vocabulary tile;
 `tail_ids` on the row whose valid logits are all negative; `mask_after_best` on restricted rows with a global maximum planted
 one id past a range.
 """
@@ -145,3 +145,9 @@ def test_a_dropped_lo_chain_is_rejected_where_the_bound_can_see_it():
     assert ok, f"the fp32 model is at {ratio:.3f} of the bound on the lo inputs"
     ok, ratio = H.accept(H.head_model(W, gamma, x, corrupt="drop_lo"), ref, bnd)
     assert not ok and ratio > 1.5, f"a dropped lo chain passes the bound ({ratio:.3f})"
+    # the exact-weights kernel rebuilds x = (hi + mid) + lo in one line that all its epilogues share: the same inputs pin it
+    ok, ratio = H.accept(H.head_model(W, gamma, x, exact=True), ref, bnd)
+    assert ok, f"the exact-weights fp32 model is at {ratio:.3f} of the bound on the lo inputs"
+    ok, ratio = H.accept(H.head_model(W, gamma, x, exact=True, corrupt="drop_lo"), ref, bnd)
+    assert not ok and ratio > 1.5, f"an operand rebuilt without its lo term passes the bound ({ratio:.3f})"
+    assert H.expected_form(H.LO_HIDDEN, H.LO_VOCAB, 17, exact=True)[:2] == ("k_gemm_x<EPI_LM>", (H.lm_cap(H.LO_VOCAB), 2))

@@ -297,3 +297,20 @@ def test_rows_whose_lo_terms_add_up_stay_inside_the_bound(M):
     print(f"HEAD_RATIO {out['form']}/lo h{hidden}_v{vocab} rows={M} ratio={ratio:.4f}")
     assert ok, f"lo inputs {M} rows: logits at {ratio:.3f} of the bound"
     _check_partials(out, out["logits_lm"], vocab, f"lo inputs {M} rows")
+
+
+@pytest.mark.parametrize("M", [1, 17])
+def test_the_exact_kernels_rebuilt_operand_keeps_its_lo_term(M):
+    """The same inputs on an exact-weights engine: k_gemm_x rebuilds x = (hi + mid) + lo in one line that every epilogue shares; at
+    hidden 32 a lost lo term stands 2.3 bounds out (shown on the CPU), from K = 128 on it could not be told from rounding."""
+    hidden, vocab = H.LO_HIDDEN, H.LO_VOCAB
+    W, gamma, x = H.lo_inputs(hidden, vocab, 17)
+    ref, A, g, r = H.head_ref(W, gamma, x)
+    bnd = H.head_bound(ref, A, hidden)
+    llm, gamma0 = _engine("lo/exact", hidden, vocab, W, gamma, exact=True)
+    out = llm.debug_head(x[:M], reads=[1] * M)
+    _check_form(out, H.expected_form(hidden, vocab, M, exact=True), f"lo inputs, exact weights, {M} rows")
+    ok, ratio = H.accept(out["logits_lm"], ref[:M], bnd[:M])
+    print(f"HEAD_RATIO {out['form']}/lo h{hidden}_v{vocab} rows={M} ratio={ratio:.4f}")
+    assert ok, f"lo inputs, exact weights, {M} rows: logits at {ratio:.3f} of the bound"
+    _check_partials(out, out["logits_lm"], vocab, f"lo inputs, exact weights, {M} rows")
