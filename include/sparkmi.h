@@ -931,6 +931,90 @@ int smi_tempos_push_rows(smi_tempos* h, const float* in_dev, long long stride, c
 long long smi_tempos_piece_len(int p, int q, int N, int D, long long n_before, long long frames_before, long long len, int last,
                                long long* n_after, long long* frames_after);
 
+/* ------------------------------------------------------------------------------------------
+ * Loudness of joined streams: a running BS.1770 gain with state carried from push to push.  Integrated loudness is a property
+ * of the whole utterance, which a piece that has to leave early cannot know, so this is NOT smi_loud_rows run chunk by chunk;
+ * it has a definition of its own.  The gain follows the integrated loudness of what has arrived, moves at a bounded rate and
+ * stays under the peak ceiling, and everything is defined on the stream's absolute sample index, so that the chunking cannot
+ * change a bit.
+ *
+ * Measuring is the section "Output loudness" above, unchanged, on a stream x[0 .. n) whose total L is known only with the
+ * last push: the K-weighting from zero state at sample 0, segments of 128 samples counted from sample 0 with the carry
+ * s_{k+1} = T s_k + e_k, y^2 summed into hop parts and the parts into hops H_h in ascending order, and
+ * z_j = (((H_j + H_{j+1}) + H_{j+2}) + H_{j+3}) / fl64(block); hop = block / 4.  The kernels call smi_loud_rows' own device
+ * functions.  Consequence: after the last push the hop sums, the z_j and the gated loudness over all blocks are those of
+ * smi_loud_rows over the whole stream, bit for bit.
+ *
+ * Knots.  Knot j sits at sample j hop and is formed once blocks 0 .. j are whole, that is when n >= (j + 4) hop.  Every step is
+ * float64 and rounded on its own (no FMA); G_{j-1} is the knot before.
+ *   Running loudness.  I_j is the gated loudness over z_0 .. z_j: both gates as above (the relative threshold from the blocks
+ *     0 .. j that pass the absolute one) and the sums in the order given there: j' = t, t + 256, ..., then the fixed tree.
+ *   Target gain.  A_j = min(10^((target - I_j) / 20), 10^(max_gain_db / 20)) (flag 1 where the second binds).  If no block of
+ *     0 .. j passes the gates, A_j = G_{j-1}, and 1 at j = 0 (flag 8: hold).
+ *   Slew, for j > 0:  A_j is clamped to [fl(G_{j-1} s_dn), fl(G_{j-1} s_up)] (flag 4 where that moves it).  s_up =
+ *     10^(max_slew_db / 20) and s_dn = 1 / s_up are formed on the host at smi_louds_open.  Knot 0 is not clamped.
+ *   Peak.  P_j = max |x| over [(j - 1) hop, (j + 1) hop) intersected with [0, L): exact, a SAMPLE peak.  If fl(A_j P_j) > ceiling
+ *     then G_j = ceiling / P_j (flag 2), else G_j = A_j.  This step is the last, so the ceiling always wins; after a capped
+ *     knot the gain comes back at the slew rate.
+ * Samples.  For j hop <= i < (j + 1) hop:
+ *     g = G_j + fl(fl(G_{j+1} - G_j) * fl(fl64(i - j hop) / fl64(hop))),      out[i] = fl32(fl64(x[i]) * g).
+ * g lies between two knots that are both at most ceiling / (the peak of that hop), so |out| <= ceiling up to the roundings.
+ * End of the stream.  With K = floor((L - block) / hop), the last whole block: the stream has the knots 0 .. floor((L - 1) / hop)
+ * + 1.  Those behind K hold the target gain A_j = G_K (flag 8); the slew step (relative to G_{j-1}) and the peak step, over
+ * what exists of their hops, apply to them as to every knot.  1 <= L < block: smi_loud_rows' short-span rule (one block, the
+ * whole stream, the absolute gate alone) gives the one loudness and the one A = min(10^((target - I) / 20), 10^(max_gain_db /
+ * 20)) that all knots share (A = 1 and flag 8 where the gate fails); slew and peak steps as above.  L = 0: nothing.  A NaN
+ * target measures only: every G = 1, every flag 0, and the output is the input bit for bit.
+ *
+ * Emission (smi_louds_piece_len, host integer arithmetic).  Hop j needs G_{j+1}, so it leaves once n >= (j + 5) hop: after a
+ * push that is not the last a stream has emitted E(n) = hop * max(0, floor(n / hop) - 4) samples, after the last push L.  A
+ * push emits the difference, which may be 0.  The delay is below 5 hops of audio: 500 ms.
+ *
+ * State.  On the host: n (the knots made and the samples emitted follow from it) and the stream's parameters.  On the device,
+ * per stream and never copied back: the cascade's state at the last whole segment edge F = 128 floor(n / 128); the sum so far
+ * of the hop that is open at F and the three hop sums before it; G of the last knot, its I, the OR of the flags and the peak so
+ * far; every z_j so far (max_blocks bounds them: a push that would pass it is refused before anything changes); and the input
+ * from max(0, min(E(n), F) - 2) to n -- what is not emitted yet, the tail short of a whole segment, and the two samples that
+ * are the filter's input history at F -- at most max(5 hop, 128) + 2 samples.  Only whole segments change the carried state
+ * before the last push: the tail behind F is filtered too, so that the hops that close inside it are known, and filtered again
+ * from the same state by the push that completes its segment; a hop's sum is the same chain of additions either way, so the
+ * order of every sum is a function of the absolute index alone.  State lives in two sets that a stream uses in turn (a push
+ * reads one and writes the other), so one launch sequence serves a call whatever B; the z_j are written once each.
+ *
+ * Five launches a call, whatever B, no atomics: k_louds_seg, k_louds_carry, k_louds_energy -- smi_loud_rows' three filter
+ * launches over the virtual sequence of held input followed by the chunk, from the stream's state --; k_louds_knots, one block
+ * of 256 a row, which closes hops and blocks and walks the row's new knots in order; k_louds_apply, grid (tiles of 1024
+ * samples of the pieces, rows), which writes the pieces and the next held input.
+ *
+ * Guarantees: the concatenation of a stream's pieces, its knot gains and its flags are, bit for bit, those of the same stream
+ * pushed at once with last = 1 -- whatever the granularity of the pushes, empty ones included, the stream's slot, its row in
+ * a call, the other rows, the strides and what lies outside len.  A stream is refused before n passes 2^28.  All pushes of a
+ * handle must go to one HIP stream (or be ordered by the caller). */
+typedef struct smi_louds smi_louds;
+/* max_streams (1..4096) slots; max_chunk (1..2^24) samples a push; block: a multiple of 4; coef_host[10] as for smi_loud_rows;
+ * max_blocks (1..2^26): the blocks a stream may reach.  Synchronous (one allocation, one clear). */
+int smi_louds_create(int max_streams, int max_chunk, int block, const double* coef_host, int max_blocks, smi_louds** out);
+int smi_louds_destroy(smi_louds* h);
+/* A new stream in slot `stream`: n = 0.  target in LUFS (NaN: measure only), max_gain_db >= 0, ceiling > 0, max_slew_db >= 0
+ * (dB a hop).  Host only.  A stream closes with its last push. */
+int smi_louds_open(smi_louds* h, int stream, double target, double max_gain_db, double ceiling, double max_slew_db);
+/* One chunk per row: in_dev [B][stride] f32 (row b valid for len_host[b], which may be 0), of the open streams stream_host[b],
+ * each at most once in a call; last_host[b] = 1 on a stream's last push.  out_dev [B][out_stride] f32: row b receives its piece
+ * and zeros from there to out_stride (>= 1 and >= the longest piece); it must not overlap in_dev.  gain_dev (may be null)
+ * [B][gain_stride] float64 receives (G_j, flags) of the knots this push made final, in order, then zeros to gain_stride (>= 1
+ * and >= two values a knot of the row with the most; smi_louds_piece_len counts them).  stats_dev (may be null) [B][4] float64
+ * receives (I of the latest whole block -- after the last push the loudness of the whole stream --, the peak so far, the latest
+ * G, the OR of all flags so far).  n_out_host [B] (may be null) receives the pieces' lengths, filled before the launch.
+ * B <= 64.  Asynchronous on `stream`.  Every argument of every row is checked before anything changes or is launched: a bad one
+ * returns SMI_EINVAL and names the argument in smi_last_error. */
+int smi_louds_push_rows(smi_louds* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                        const int32_t* last_host, int B, double* gain_dev, long long gain_stride, float* out_dev, long long out_stride,
+                        int32_t* n_out_host, double* stats_dev, void* stream);
+/* The piece length of one push, pure host arithmetic: a stream that holds n_before samples takes len samples (last = 1: its
+ * last push); n_after / knots_after (may be null) receive the samples and the knots made after it (before it the stream had
+ * max(0, floor(n_before / hop) - 3) knots).  -1 for a bad argument. */
+long long smi_louds_piece_len(int block, long long n_before, long long len, int last, long long* n_after, long long* knots_after);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,11 @@
 //   k_tempos_search, k_tempos_ola  the same for joined streams (smi_tempos_*): the frames a push makes final, walked over the
 //                stream's history followed by its new chunk with the batch kernels' own device functions (tp_place, tp_ola);
 //                histories and last places live in two sets a stream uses in turn, as the joiner's state does.
+//   k_louds_seg, k_louds_carry, k_louds_energy, k_louds_knots, k_louds_apply   loudness of joined streams (smi_louds_*): the
+//                batch filter launches over a stream's held input followed by its new chunk, from the stream's carried state,
+//                with the batch kernels' own device functions (ld_step, the block sums); one block per row then closes hops and
+//                blocks and walks the row's new gain knots in order; the last launch writes the pieces and the next held input.
+//                Everything a push is follows from the stream's length before it (ls_plan, host and device).  No atomics.
 #include <limits.h>
 
 #include <cmath>
@@ -944,6 +949,370 @@ __global__ __launch_bounds__(RS_BLOCK) void k_tempos_ola(TsArgs a, TsState s, in
   }
 }
 
+// ---- loudness of joined streams (smi_louds_*)
+#define LS_STATE 12             // float64 of one stream's state in one set: s[4], open hop, three closed hops, G, I, flags, peak
+struct LsRow {
+  int32_t slot, set;        // the stream's slot; the state set this push reads (it writes the other one)
+  int32_t n_old, len;       // samples before this push; chunk samples, with bit 30 set on the stream's last push
+};
+struct LsArgs {
+  LsRow r[RS_MAX_ROWS];
+};
+struct LsParam {
+  double target, max_gain_db, ceiling, s_up, s_dn;
+};
+struct LsParams {
+  LsParam r[RS_MAX_ROWS];
+};
+struct LsState {
+  LdCoef c;
+  double* st;               // [2][max_streams][LS_STATE]
+  double* z;                // [max_streams][max_blocks]: the block mean squares so far (written once each: one set)
+  float* hist;              // [2][max_streams][hcap]: hist[i] = x[h0 + i], i < n - h0
+  double* work;             // [RS_MAX_ROWS][wrow]
+  long long wrow, w_s, w_parts, w_hops, w_gain;   // a row's scratch and where its parts lie (end states at 0)
+  int32_t max_streams, max_blocks, hcap, pps, block;
+};
+
+// everything a push is, from the stream's length before it, the chunk's length and `last`: the host's checks and the kernels
+// both call this, so they cannot disagree
+struct LsPlan {
+  int n_old, n_new, last;
+  int h0_old, h0_new;       // first sample the read set's history holds / the written set's will hold
+  int seg0, nwhole, nseg;   // first segment this push filters; the whole segments; those and the tail short of one
+  int e_old, e_new;         // samples emitted before / after
+  int k_old, k_new;         // knots made before / after
+  int z_old, z_new;         // whole blocks before / after
+};
+__host__ __device__ __forceinline__ int ls_emitted(int n, int hop) { return n / hop > 4 ? (n / hop - 4) * hop : 0; }
+__host__ __device__ __forceinline__ int ls_blocks(int n, int hop) { return n / hop > 3 ? n / hop - 3 : 0; }
+__host__ __device__ __forceinline__ int ls_hist_start(int n, int hop) {
+  const int e = ls_emitted(n, hop), f = n / LD_SEG * LD_SEG;
+  const int a = (e < f ? e : f) - 2;   // (the two samples before the first unfiltered segment are its input history)
+  return a > 0 ? a : 0;
+}
+__host__ __device__ __forceinline__ LsPlan ls_plan(int n_old, int len, int last, int hop) {
+  LsPlan p;
+  p.n_old = n_old; p.n_new = n_old + len; p.last = last;
+  p.h0_old = ls_hist_start(n_old, hop); p.h0_new = ls_hist_start(p.n_new, hop);
+  p.seg0 = n_old / LD_SEG;
+  p.nwhole = p.n_new / LD_SEG - p.seg0;
+  p.nseg = p.nwhole + (p.n_new % LD_SEG ? 1 : 0);
+  p.e_old = ls_emitted(n_old, hop); p.e_new = last ? p.n_new : ls_emitted(p.n_new, hop);
+  p.z_old = ls_blocks(n_old, hop); p.z_new = ls_blocks(p.n_new, hop);
+  p.k_old = p.z_old; p.k_new = last ? (p.n_new ? (p.n_new - 1) / hop + 2 : 0) : p.z_new;
+  return p;
+}
+__device__ __forceinline__ LsPlan ls_plan(const LsRow& r, int hop) { return ls_plan(r.n_old, r.len & 0x3FFFFFFF, (r.len >> 30) & 1, hop); }
+
+// a stream's input from h0_old to n_new: the history, then the chunk
+struct LsSeq {
+  const float* __restrict__ hist;
+  const float* __restrict__ chunk;
+  int h0, n_old;
+  __device__ __forceinline__ float at(int i) const { return i < n_old ? hist[i - h0] : chunk[i - n_old]; }
+};
+__device__ __forceinline__ LsSeq ls_seq(const LsRow& r, const LsPlan& p, const LsState& s, const float* chunk) {
+  return {s.hist + ((size_t)r.set * s.max_streams + r.slot) * s.hcap, chunk, p.h0_old, p.n_old};
+}
+
+// ld_stage over a stream: tile blockIdx.x of the segments this push filters, lane l on segment seg0 + 64 blockIdx.x + l
+__device__ __forceinline__ int ls_stage(const LsPlan& p, const LsSeq& x, float* lds, LdState& s) {
+  const int a0 = (p.seg0 + blockIdx.x * LD_LANES) * LD_SEG, tid = threadIdx.x;   // of the stream
+  const int cnt = min(LD_TILE, p.n_new - a0);
+  for (int i = tid; i < cnt; i += LD_LANES) lds[(i / LD_SEG) * LD_PITCH + (i % LD_SEG)] = x.at(a0 + i);
+  __syncthreads();
+  const int i0 = a0 + tid * LD_SEG;
+  s.x1 = i0 >= 1 && i0 < p.n_new ? (double)x.at(i0 - 1) : 0.0;
+  s.x2 = i0 >= 2 && i0 < p.n_new ? (double)x.at(i0 - 2) : 0.0;
+  return max(0, min(LD_SEG, p.n_new - i0));
+}
+
+// grid (tiles of LD_TILE samples of the push's segments, rows): k_loud_seg for every whole segment of the push
+__global__ __launch_bounds__(LD_LANES) void k_louds_seg(LsArgs a, LsState s, const float* __restrict__ in, long long in_stride) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const LsRow r = a.r[blockIdx.y];
+  const LsPlan p = ls_plan(r, s.block / 4);
+  if ((int)blockIdx.x * LD_LANES >= p.nwhole) return;
+  LdState t = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  ls_stage(p, ls_seq(r, p, s, in + (size_t)blockIdx.y * in_stride), rs_lds, t);
+  const int g = blockIdx.x * LD_LANES + threadIdx.x;
+  if (g >= p.nwhole) return;
+  const float* seg = rs_lds + threadIdx.x * LD_PITCH;
+  for (int i = 0; i < LD_SEG; ++i) ld_step(s.c, t, (double)seg[i]);
+  double* E = s.work + (size_t)blockIdx.y * s.wrow + 4 * (size_t)g;
+  E[0] = t.p1; E[1] = t.p2; E[2] = t.q1; E[3] = t.q2;
+}
+
+// one wave per row: k_loud_carry's recurrence from the stream's state; the state behind the last whole segment goes to the set
+// this launch does not read
+__global__ __launch_bounds__(64) void k_louds_carry(LsArgs a, LsState s) {
+  __shared__ double e[64][4];
+  const LsRow r = a.r[blockIdx.x];
+  const LsPlan p = ls_plan(r, s.block / 4);
+  const int lane = threadIdx.x, ns = p.nwhole + 1;
+  const double* E = s.work + (size_t)blockIdx.x * s.wrow;
+  double* S = s.work + (size_t)blockIdx.x * s.wrow + s.w_s;
+  const double* rd = s.st + ((size_t)r.set * s.max_streams + r.slot) * LS_STATE;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  if (p.seg0) { s0 = rd[0]; s1 = rd[1]; s2 = rd[2]; s3 = rd[3]; }
+  const LdCoef& c = s.c;
+  for (int k0 = 0; k0 < ns; k0 += 64) {
+    if (k0 + lane < p.nwhole)
+      for (int i = 0; i < 4; ++i) e[lane][i] = E[4 * (size_t)(k0 + lane) + i];
+    __syncthreads();
+    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+    const int cnt = min(64, ns - k0);
+    for (int t = 0; t < cnt; ++t) {
+      if (lane == t) { m0 = s0; m1 = s1; m2 = s2; m3 = s3; }
+      if (k0 + t < p.nwhole) {
+        const double n0 = (((c.T[0][0] * s0 + c.T[0][1] * s1) + c.T[0][2] * s2) + c.T[0][3] * s3) + e[t][0];
+        const double n1 = (((c.T[1][0] * s0 + c.T[1][1] * s1) + c.T[1][2] * s2) + c.T[1][3] * s3) + e[t][1];
+        const double n2 = (((c.T[2][0] * s0 + c.T[2][1] * s1) + c.T[2][2] * s2) + c.T[2][3] * s3) + e[t][2];
+        const double n3 = (((c.T[3][0] * s0 + c.T[3][1] * s1) + c.T[3][2] * s2) + c.T[3][3] * s3) + e[t][3];
+        s0 = n0; s1 = n1; s2 = n2; s3 = n3;
+      }
+    }
+    if (lane < cnt) {
+      double* d = S + 4 * (size_t)(k0 + lane);
+      d[0] = m0; d[1] = m1; d[2] = m2; d[3] = m3;
+    }
+    __syncthreads();
+  }
+  if (lane == 0) {   // (every lane holds the state behind the last whole segment)
+    double* wr = s.st + ((size_t)(1 - r.set) * s.max_streams + r.slot) * LS_STATE;
+    wr[0] = s0; wr[1] = s1; wr[2] = s2; wr[3] = s3;
+  }
+}
+
+// grid as k_louds_seg: k_loud_energy for every segment of the push, the tail short of one included (it is filtered again, from
+// the same state, by the push that completes it: the hops that close inside it have the sums they will have then)
+__global__ __launch_bounds__(LD_LANES) void k_louds_energy(LsArgs a, LsState s, const float* __restrict__ in, long long in_stride) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const LsRow r = a.r[blockIdx.y];
+  const int hop = s.block / 4;
+  const LsPlan p = ls_plan(r, hop);
+  if ((int)blockIdx.x * LD_LANES >= p.nseg) return;
+  LdState t = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int m = ls_stage(p, ls_seq(r, p, s, in + (size_t)blockIdx.y * in_stride), rs_lds, t);
+  if (m == 0) return;
+  const int g = blockIdx.x * LD_LANES + threadIdx.x;
+  double* row = s.work + (size_t)blockIdx.y * s.wrow;
+  const double* S = row + s.w_s + 4 * (size_t)g;
+  t.p1 = S[0]; t.p2 = S[1]; t.q1 = S[2]; t.q2 = S[3];
+  double* P = row + s.w_parts + (size_t)g * s.pps;
+  const float* seg = rs_lds + threadIdx.x * LD_PITCH;
+  int i = (p.seg0 + g) * LD_SEG;         // of the stream
+  int edge = (i / hop + 1) * hop;        // where the hop that holds sample i ends
+  int q = 0, held = 0;
+  double acc = 0.0;
+  for (int u = 0; u < m; ++u) {
+    const double o = ld_step(s.c, t, (double)seg[u]);
+    acc = acc + o * o;
+    held = 1;
+    if (++i == edge) {
+      P[q++] = acc;
+      acc = 0.0;
+      held = 0;
+      edge += hop;
+    }
+  }
+  if (held) P[q] = acc;
+}
+
+// the parts of hop h in the segments k0 .. k1 of this push, added in ascending order to t (ls_plan's seg0 is segment 0 of P)
+__device__ __forceinline__ double ls_hop_sum(double t, const double* P, int pps, int seg0, int hop, int h, int k0, int k1) {
+  for (int k = k0; k <= k1; ++k) t = t + P[(size_t)(k - seg0) * pps + (h - (k * LD_SEG) / hop)];
+  return t;
+}
+
+// The gated loudness over z[0 .. j] with k_loud_gate's sums: sum1 / cnt1 are this thread's running sums of the blocks
+// t, t + 256, ... <= j that pass the absolute gate.  Returns false where no block passes.
+__device__ __forceinline__ bool ls_gated(const double* z, int j, double abs_gate, double sum1, double cnt1, double* red, double& loud) {
+  const double S1 = ld_block_sum(sum1, red), C1 = ld_block_sum(cnt1, red);
+  loud = -INFINITY;
+  if (!(C1 > 0.0)) return false;
+  const double rel = 0.1 * (S1 / C1);
+  double sum = 0.0, cnt = 0.0;
+  for (int i = threadIdx.x; i <= j; i += LD_GATE) {
+    const double v = z[i];
+    if (v > abs_gate && v > rel) { sum = sum + v; cnt = cnt + 1.0; }
+  }
+  const double S2 = ld_block_sum(sum, red), C2 = ld_block_sum(cnt, red);
+  if (!(C2 > 0.0)) return false;
+  loud = -0.691 + 10.0 * log10(S2 / C2);
+  return true;
+}
+
+// max |x| over [lo, hi) of the stream, by the block
+__device__ __forceinline__ double ls_peak(const LsSeq& x, int lo, int hi, double* red) {
+  uint32_t pk = 0;
+  for (int i = lo + (int)threadIdx.x; i < hi; i += LD_GATE) pk = max(pk, __float_as_uint(x.at(i)) & 0x7FFFFFFFu);
+  return ld_block_max((double)__uint_as_float(pk), red);
+}
+
+// one knot: the target gain `A` (have: from a loudness; else a held gain), the slew step for j > 0, the peak step
+__device__ __forceinline__ double ls_knot(const LsParam& q, int j, double A, int flags, double g_prev, double gmax, bool clamp_max,
+                                          double pk, int& flags_out) {
+  if (!(q.target == q.target)) { flags_out = 0; return 1.0; }
+  if (clamp_max && A > gmax) { A = gmax; flags |= 1; }
+  if (j > 0) {
+    const double lo = g_prev * q.s_dn, hi = g_prev * q.s_up;
+    if (A < lo) { A = lo; flags |= 4; }
+    else if (A > hi) { A = hi; flags |= 4; }
+  }
+  double g = A;
+  if (A * pk > q.ceiling) { g = q.ceiling / pk; flags |= 2; }
+  flags_out = flags;
+  return g;
+}
+
+// One block per row: closes the hops and blocks the push completes, then walks the row's new knots in order (include/sparkmi.h).
+// Every thread carries the same scalars (the block-wide sums return one value to all); thread 0 writes.
+__global__ __launch_bounds__(LD_GATE) void k_louds_knots(LsArgs a, LsParams pr, LsState s, double abs_gate, const float* __restrict__ in,
+                                                         long long in_stride, double* __restrict__ gain, long long gain_stride,
+                                                         double* __restrict__ stats) {
+  __shared__ double red[LD_GATE];
+  const int b = blockIdx.x, tid = threadIdx.x, block = s.block, hop = block / 4;
+  const LsRow r = a.r[b];
+  const LsParam q = pr.r[b];
+  const LsPlan p = ls_plan(r, hop);
+  const LsSeq x = ls_seq(r, p, s, in + (size_t)b * in_stride);
+  const double* rd = s.st + ((size_t)r.set * s.max_streams + r.slot) * LS_STATE;
+  double* wr = s.st + ((size_t)(1 - r.set) * s.max_streams + r.slot) * LS_STATE;
+  double* row = s.work + (size_t)b * s.wrow;
+  const double* P = row + s.w_parts;
+  double* Hw = row + s.w_hops;       // Hw[3 + h - hF]: the sum of hop h; Hw[0 .. 3): the three hops before hF
+  double* gw = row + s.w_gain;       // gw[1 + j - k_old]: G_j; gw[0]: the last knot before this push
+  double* Z = s.z + (size_t)r.slot * s.max_blocks;
+  double* gr = gain ? gain + (size_t)b * gain_stride : nullptr;
+  const int nk = p.k_new - p.k_old;
+  if (gr)
+    for (long long i = 2LL * nk + tid; i < gain_stride; i += LD_GATE) gr[i] = 0.0;
+  // 1. hop sums, from the first hop that is open at the first segment this push filters
+  const int F_old = p.seg0 * LD_SEG, hF = F_old / hop;
+  const double open_old = F_old % hop ? rd[4] : 0.0;
+  const int nh_end = (p.n_new + hop - 1) / hop;
+  if (tid < 3) Hw[tid] = rd[5 + tid];
+  for (int h = hF + tid; h < nh_end; h += LD_GATE) {
+    const int lo = h * hop, hi = min(p.n_new, lo + hop) - 1;
+    Hw[3 + h - hF] = ls_hop_sum(h == hF ? open_old : 0.0, P, s.pps, p.seg0, hop, h, max(lo / LD_SEG, p.seg0), hi / LD_SEG);
+  }
+  __syncthreads();
+  // 2. the blocks this push completes
+  for (int j = p.z_old + tid; j < p.z_new; j += LD_GATE) {
+    const double* H = Hw + 3 + (j - hF);
+    Z[j] = (((H[0] + H[1]) + H[2]) + H[3]) / (double)block;
+  }
+  const double pk_chunk = ls_peak(x, p.n_old, p.n_new, red);   // (its barriers also publish Hw and Z to the block)
+  const double peak = p.n_old ? fmax(rd[11], pk_chunk) : pk_chunk;
+  // 3. the knots, in order
+  double g_prev = p.k_old ? rd[8] : 1.0, loud = p.n_old ? rd[9] : -INFINITY;
+  int flags_or = p.n_old ? (int)rd[10] : 0;
+  const double gmax = pow(10.0, q.max_gain_db / 20.0);
+  if (tid == 0) gw[0] = g_prev;
+  double sum1 = 0.0, cnt1 = 0.0;
+  for (int j = tid; j < p.k_old; j += LD_GATE) {
+    const double v = Z[j];
+    if (v > abs_gate) { sum1 = sum1 + v; cnt1 = cnt1 + 1.0; }
+  }
+  const int k_norm = min(p.k_new, p.z_new);
+  for (int j = p.k_old; j < k_norm; ++j) {
+    if (j % LD_GATE == tid) {
+      const double v = Z[j];
+      if (v > abs_gate) { sum1 = sum1 + v; cnt1 = cnt1 + 1.0; }
+    }
+    double I;
+    const bool have = ls_gated(Z, j, abs_gate, sum1, cnt1, red, I);
+    loud = I;
+    const double pk = ls_peak(x, max(0, (j - 1) * hop), min(p.n_new, (j + 1) * hop), red);
+    int fl;
+    const double A = have ? pow(10.0, (q.target - I) / 20.0) : g_prev;   // (g_prev is 1 at knot 0)
+    const double g = ls_knot(q, j, A, have ? 0 : 8, g_prev, gmax, have, pk, fl);
+    if (tid == 0) {
+      gw[1 + j - p.k_old] = g;
+      if (gr) { gr[2 * (j - p.k_old)] = g; gr[2 * (j - p.k_old) + 1] = (double)fl; }
+    }
+    g_prev = g;
+    flags_or |= fl;
+  }
+  if (p.k_new > k_norm) {   // the stream's end: the knots behind the last whole block hold one target gain
+    double A = g_prev;
+    int f0 = 8;
+    bool clamp = false;
+    if (p.z_new == 0) {     // shorter than a block: one block, the whole stream, the absolute gate alone
+      const int nh = (p.n_new + hop - 1) / hop;
+      double t = 0.0;
+      for (int h = 0; h < nh; ++h) t = t + Hw[3 + h - hF];
+      const double zz = t / (double)p.n_new;
+      A = 1.0;
+      loud = -INFINITY;
+      if (zz > abs_gate) {
+        loud = -0.691 + 10.0 * log10(zz);
+        A = pow(10.0, (q.target - loud) / 20.0);
+        f0 = 0;
+        clamp = true;
+      }
+    }
+    for (int j = max(p.k_old, k_norm); j < p.k_new; ++j) {
+      const double pk = ls_peak(x, max(0, (j - 1) * hop), min(p.n_new, (j + 1) * hop), red);
+      int fl;
+      const double g = ls_knot(q, j, A, f0, g_prev, gmax, clamp, pk, fl);
+      if (tid == 0) {
+        gw[1 + j - p.k_old] = g;
+        if (gr) { gr[2 * (j - p.k_old)] = g; gr[2 * (j - p.k_old) + 1] = (double)fl; }
+      }
+      g_prev = g;
+      flags_or |= fl;
+    }
+  }
+  if (tid) return;
+  // the next state: the hop that is open behind the last whole segment, and the three before it
+  const int F_new = (p.seg0 + p.nwhole) * LD_SEG, hN = F_new / hop;
+  double open_new = 0.0;
+  if (F_new % hop) {
+    const int lo = hN * hop;
+    open_new = ls_hop_sum(hN == hF ? open_old : 0.0, P, s.pps, p.seg0, hop, hN, max(lo / LD_SEG, p.seg0), p.seg0 + p.nwhole - 1);
+  }
+  const double h0 = Hw[hN - hF], h1 = Hw[hN - hF + 1], h2 = Hw[hN - hF + 2];
+  wr[4] = open_new; wr[5] = h0; wr[6] = h1; wr[7] = h2;
+  wr[8] = g_prev; wr[9] = loud; wr[10] = (double)flags_or; wr[11] = peak;
+  if (stats) {
+    double* st = stats + 4 * (size_t)b;
+    st[0] = loud; st[1] = peak; st[2] = g_prev; st[3] = (double)flags_or;
+  }
+}
+
+// grid (tiles of GN_TILE samples of the pieces, rows): every sample of the row's piece times the gain between its two knots,
+// zeros from there to the stride.  Tile 0 of a row also writes the stream's next history into the set this launch does not read.
+__global__ __launch_bounds__(RS_BLOCK) void k_louds_apply(LsArgs a, LsState s, const float* __restrict__ in, long long in_stride,
+                                                          float* __restrict__ out, long long out_stride) {
+  const LsRow r = a.r[blockIdx.y];
+  const int hop = s.block / 4, tid = threadIdx.x;
+  const LsPlan p = ls_plan(r, hop);
+  const LsSeq x = ls_seq(r, p, s, in + (size_t)blockIdx.y * in_stride);
+  const double* gw = s.work + (size_t)blockIdx.y * s.wrow + s.w_gain;
+  float* y = out + (size_t)blockIdx.y * out_stride;
+  if (blockIdx.x == 0 && !p.last) {
+    float* hist2 = s.hist + ((size_t)(1 - r.set) * s.max_streams + r.slot) * s.hcap;
+    for (int i = p.h0_new + tid; i < p.n_new; i += RS_BLOCK) hist2[i - p.h0_new] = x.at(i);   // n_new - h0_new <= hcap: the host's check
+  }
+  const long long i0 = (long long)blockIdx.x * GN_TILE;
+  const long long end = min(out_stride, i0 + GN_TILE);
+  const int piece = p.e_new - p.e_old;
+  for (long long i = i0 + tid; i < end; i += RS_BLOCK) {
+    float v = 0.f;
+    if (i < piece) {
+      const int m = p.e_old + (int)i, j = m / hop;
+      const double g0 = gw[1 + j - p.k_old], g1 = gw[2 + j - p.k_old];
+      const double fr = (double)(m - j * hop) / (double)hop;
+      const double d = (g1 - g0) * fr;
+      v = (float)((double)x.at(m) * (g0 + d));
+    }
+    y[i] = v;
+  }
+}
+
 }  // namespace
 
 struct smi_rs {
@@ -1701,6 +2070,187 @@ int smi_tempos_push_rows(smi_tempos* h, const float* in_dev, long long stride, c
   SMI_LAUNCH_CHECK();
   const int tiles = (int)((out_stride + TP_TILE - 1) / TP_TILE);
   hipLaunchKernelGGL(k_tempos_ola, dim3(tiles, B), dim3(RS_BLOCK), 0, hs, A, s, h->N, in_dev, stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// ---- loudness of joined streams (smi_louds_*): the host arithmetic of include/sparkmi.h's "Emission"
+#define LS_MAX_N (1LL << 28)   // input samples of one stream, as for smi_tempos
+
+struct LsStream {
+  int open = 0, set = 0;
+  long long n = 0;          // input samples so far: the knots made and the samples emitted follow from it (ls_plan)
+  LsParam q = {0.0, 0.0, 1.0, 1.0, 1.0};
+};
+struct smi_louds {
+  LsState s;
+  int max_chunk;
+  double abs_gate;
+  DevBuf<char> pool;
+  std::vector<LsStream> streams;
+};
+
+static bool ls_block_ok(int block) { return block >= 4 && block <= RS_MAX_SAMPLES && !(block & 3); }
+
+extern "C" {
+
+long long smi_louds_piece_len(int block, long long n_before, long long len, int last, long long* n_after, long long* knots_after) {
+  if (!ls_block_ok(block) || n_before < 0 || len < 0 || n_before > LS_MAX_N || len > LS_MAX_N || n_before + len > LS_MAX_N) return -1;
+  if (last != 0 && last != 1) return -1;
+  const LsPlan p = ls_plan((int)n_before, (int)len, last, block / 4);
+  if (n_after) *n_after = p.n_new;
+  if (knots_after) *knots_after = p.k_new;
+  return p.e_new - p.e_old;
+}
+
+int smi_louds_create(int max_streams, int max_chunk, int block, const double* coef_host, int max_blocks, smi_louds** out) {
+  SMI_REQUIRE(out, "smi_louds_create: null out");
+  *out = nullptr;
+  SMI_REQUIRE(max_streams >= 1 && max_streams <= JN_MAX_STREAMS, "smi_louds_create: max_streams=%d outside 1..%d", max_streams, JN_MAX_STREAMS);
+  SMI_REQUIRE(max_chunk >= 1 && max_chunk <= RS_MAX_SAMPLES, "smi_louds_create: max_chunk=%d outside 1..%d", max_chunk, RS_MAX_SAMPLES);
+  SMI_REQUIRE(ls_block_ok(block), "smi_louds_create: block=%d must be a multiple of 4 in 4..%d", block, RS_MAX_SAMPLES);
+  SMI_REQUIRE(max_blocks >= 1 && max_blocks <= (1 << 26), "smi_louds_create: max_blocks=%d outside 1..2^26", max_blocks);
+  SMI_REQUIRE(coef_host, "smi_louds_create: null coef_host");
+  for (int i = 0; i < 10; ++i)
+    SMI_REQUIRE(std::isfinite(coef_host[i]), "smi_louds_create: coef[%d]=%g is not finite", i, coef_host[i]);
+  char arch[128];
+  const int rc = smi_device_check(arch, sizeof(arch));
+  if (rc) return rc;
+  smi_louds* h = new smi_louds();
+  h->max_chunk = max_chunk;
+  h->abs_gate = pow(10.0, (-70.0 + 0.691) / 10.0);
+  LsState& s = h->s;
+  for (int st = 0; st < 2; ++st) {
+    for (int i = 0; i < 3; ++i) s.c.b[st][i] = coef_host[5 * st + i];
+    s.c.a1[st] = coef_host[5 * st + 3];
+    s.c.a2[st] = coef_host[5 * st + 4];
+  }
+  ld_transition(s.c);
+  const int hop = block / 4;
+  s.max_streams = max_streams; s.max_blocks = max_blocks; s.block = block;
+  s.hcap = (5 * hop > LD_SEG ? 5 * hop : LD_SEG) + 2;   // n - min(E(n), the last segment edge) + the two samples before it
+  s.pps = (LD_SEG - 1) / hop + 2;
+  // a row's scratch: a push filters the tail short of a segment it held and its chunk
+  const long long nseg = (long long)max_chunk / LD_SEG + 3, nhop = ((long long)max_chunk + LD_SEG) / hop + 8, nknot = (long long)max_chunk / hop + 10;
+  s.w_s = 4 * nseg;
+  s.w_parts = s.w_s + 4 * (nseg + 1);
+  s.w_hops = s.w_parts + nseg * s.pps;
+  s.w_gain = s.w_hops + nhop;
+  s.wrow = s.w_gain + nknot;
+  // one allocation: float64 first (states, blocks, scratch), then the two history sets (fp32)
+  const size_t n_st = 2 * (size_t)max_streams * LS_STATE, n_z = (size_t)max_streams * max_blocks, n_work = (size_t)RS_MAX_ROWS * s.wrow;
+  const size_t n_hist = 2 * (size_t)max_streams * s.hcap;
+  const size_t bytes = (n_st + n_z + n_work) * sizeof(double) + n_hist * sizeof(float);
+  if (h->pool.alloc(bytes, "smi_louds_create: stream state")) {
+    (void)hipGetLastError();
+    delete h;
+    return SMI_ENOMEM;
+  }
+  s.st = (double*)h->pool.get();
+  s.z = s.st + n_st;
+  s.work = s.z + n_z;
+  s.hist = (float*)(s.work + n_work);
+  const hipError_t e = hipMemset(h->pool, 0, bytes);
+  if (e != hipSuccess) {
+    smi_set_error("smi_louds_create: clearing the state: %s", hipGetErrorString(e));
+    delete h;
+    return SMI_EHIP;
+  }
+  h->streams.assign((size_t)max_streams, LsStream{});
+  *out = h;
+  return SMI_OK;
+}
+
+int smi_louds_destroy(smi_louds* h) {
+  delete h;
+  return SMI_OK;
+}
+
+int smi_louds_open(smi_louds* h, int stream, double target, double max_gain_db, double ceiling, double max_slew_db) {
+  SMI_REQUIRE(h, "smi_louds_open: null handle");
+  SMI_REQUIRE(stream >= 0 && stream < h->s.max_streams, "smi_louds_open: stream=%d outside 0..%d", stream, h->s.max_streams - 1);
+  SMI_REQUIRE(!std::isinf(target), "smi_louds_open: target=%g must be finite, or NaN to measure only", target);
+  SMI_REQUIRE(std::isfinite(max_gain_db) && max_gain_db >= 0.0, "smi_louds_open: max_gain_db=%g must be finite and >= 0", max_gain_db);
+  SMI_REQUIRE(std::isfinite(ceiling) && ceiling > 0.0, "smi_louds_open: ceiling=%g must be finite and > 0", ceiling);
+  SMI_REQUIRE(std::isfinite(max_slew_db) && max_slew_db >= 0.0 && max_slew_db <= 200.0, "smi_louds_open: max_slew_db=%g outside 0..200", max_slew_db);
+  LsStream& st = h->streams[(size_t)stream];
+  st.open = 1; st.n = 0;   // (st.set goes on alternating: a first push reads no state)
+  st.q.target = target; st.q.max_gain_db = max_gain_db; st.q.ceiling = ceiling;
+  st.q.s_up = pow(10.0, max_slew_db / 20.0);
+  st.q.s_dn = 1.0 / st.q.s_up;
+  return SMI_OK;
+}
+
+int smi_louds_push_rows(smi_louds* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                        const int32_t* last_host, int B, double* gain_dev, long long gain_stride, float* out_dev, long long out_stride,
+                        int32_t* n_out_host, double* stats_dev, void* stream) {
+  SMI_REQUIRE(h && in_dev && stream_host && len_host && last_host && out_dev, "smi_louds_push_rows: null argument");
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "smi_louds_push_rows: B=%d outside 1..%d", B, RS_MAX_ROWS);
+  SMI_REQUIRE(stride >= 1, "smi_louds_push_rows: stride=%lld must be positive", stride);
+  const LsState& s = h->s;
+  const int hop = s.block / 4;
+  LsArgs A;
+  LsParams Q;
+  LsPlan plan[RS_MAX_ROWS];
+  long long need = 1, need_gain = 1;
+  int nseg_max = 1;
+  for (int b = 0; b < B; ++b) {
+    const int id = stream_host[b];
+    SMI_REQUIRE(id >= 0 && id < s.max_streams, "smi_louds_push_rows: stream[%d]=%d outside 0..%d", b, id, s.max_streams - 1);
+    for (int c = 0; c < b; ++c)
+      SMI_REQUIRE(stream_host[c] != id, "smi_louds_push_rows: stream[%d]=%d is row %d's stream too (one chunk of a stream a call)", b, id, c);
+    const LsStream& st = h->streams[(size_t)id];
+    SMI_REQUIRE(st.open, "smi_louds_push_rows: stream[%d]=%d is not open (smi_louds_open; a stream closes with its last chunk)", b, id);
+    const int len = len_host[b], last = last_host[b];
+    SMI_REQUIRE(last == 0 || last == 1, "smi_louds_push_rows: last[%d]=%d is neither 0 nor 1", b, last);
+    SMI_REQUIRE(len >= 0 && len <= h->max_chunk && len <= stride, "smi_louds_push_rows: len[%d]=%d outside 0..min(max_chunk=%d, stride=%lld)", b,
+                len, h->max_chunk, stride);
+    SMI_REQUIRE(st.n + len <= LS_MAX_N, "smi_louds_push_rows: stream[%d]=%d would reach %lld samples: 2^28 is the limit of a stream", b, id,
+                st.n + len);
+    const LsPlan p = plan[b] = ls_plan((int)st.n, len, last, hop);
+    SMI_REQUIRE(p.z_new <= s.max_blocks, "smi_louds_push_rows: stream[%d]=%d would reach %d blocks, the handle holds max_blocks=%d", b, id,
+                p.z_new, s.max_blocks);
+    SMI_REQUIRE(p.h0_new >= p.h0_old && p.n_new - p.h0_new <= s.hcap, "smi_louds_push_rows: stream[%d]=%d needs %d samples of history, the handle keeps %d",
+                b, id, p.n_new - p.h0_new, s.hcap);
+    LsRow& r = A.r[b];
+    r.slot = id; r.set = st.set; r.n_old = (int32_t)st.n; r.len = len | (last << 30);
+    Q.r[b] = st.q;
+    if (p.e_new - p.e_old > need) need = p.e_new - p.e_old;
+    if (2LL * (p.k_new - p.k_old) > need_gain) need_gain = 2LL * (p.k_new - p.k_old);
+    if (p.nseg > nseg_max) nseg_max = p.nseg;
+  }
+  SMI_REQUIRE(out_stride >= need && out_stride <= TP_MAX_OUT, "smi_louds_push_rows: out_stride=%lld outside %lld (the longest piece)..%d",
+              out_stride, need, TP_MAX_OUT);
+  SMI_REQUIRE(!gain_dev || (gain_stride >= need_gain && gain_stride <= TP_MAX_OUT),
+              "smi_louds_push_rows: gain_stride=%lld outside %lld (two values a knot of the row with the most)..%d", gain_stride, need_gain, TP_MAX_OUT);
+  {
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + (size_t)B * stride * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_louds_push_rows: out_dev overlaps in_dev");
+  }
+  for (int b = 0; b < B; ++b) {
+    LsStream& st = h->streams[(size_t)stream_host[b]];
+    if (n_out_host) n_out_host[b] = plan[b].e_new - plan[b].e_old;
+    st.n = plan[b].n_new; st.set ^= 1;
+    if (last_host[b]) st.open = 0;
+  }
+  hipStream_t hs = (hipStream_t)stream;
+  const int tiles = (nseg_max + LD_LANES - 1) / LD_LANES;
+  const size_t lds = (size_t)LD_LANES * LD_PITCH * sizeof(float);
+  hipLaunchKernelGGL(k_louds_seg, dim3(tiles, B), dim3(LD_LANES), lds, hs, A, s, in_dev, stride);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_louds_carry, dim3(B), dim3(64), 0, hs, A, s);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_louds_energy, dim3(tiles, B), dim3(LD_LANES), lds, hs, A, s, in_dev, stride);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_louds_knots, dim3(B), dim3(LD_GATE), 0, hs, A, Q, s, h->abs_gate, in_dev, stride, gain_dev, gain_stride, stats_dev);
+  SMI_LAUNCH_CHECK();
+  const int gtiles = (int)((out_stride + GN_TILE - 1) / GN_TILE);
+  hipLaunchKernelGGL(k_louds_apply, dim3(gtiles, B), dim3(RS_BLOCK), 0, hs, A, s, in_dev, stride, out_dev, out_stride);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

@@ -269,6 +269,12 @@ SYMBOLS = {
                                   C.c_longlong, _P(C.c_int32), _VP]),
     "smi_tempos_piece_len": (C.c_longlong, [_I, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _I, _P(C.c_longlong),
                                             _P(C.c_longlong)]),
+    "smi_louds_create": (_I, [_I, _I, _I, _P(C.c_double), _I, _P(_VP)]),
+    "smi_louds_destroy": (_I, [_VP]),
+    "smi_louds_open": (_I, [_VP, _I, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "smi_louds_push_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, C.c_longlong, _VP,
+                                 C.c_longlong, _P(C.c_int32), _VP, _VP]),
+    "smi_louds_piece_len": (C.c_longlong, [_I, C.c_longlong, C.c_longlong, _I, _P(C.c_longlong), _P(C.c_longlong)]),
 }
 
 # include/sparkmi_debug.h: exported by libsparkmi_diag.so only

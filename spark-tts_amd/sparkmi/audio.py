@@ -21,6 +21,9 @@ search is exact integer arithmetic, so the device is held to ``tests/tempo_ref.p
 ``tempo_frame`` and ``tempo_window`` give its rational, its frame and radius for a sample rate, and its window.
 ``StreamTempo`` (``smi_tempos_*``) is its streaming form: the frame places and an input history are kept on the device per
 stream, and the pieces' concatenation is ``tempo_rows`` of the whole stream bit for bit, whatever the chunking.
+
+``StreamLoudness`` (``smi_louds_*``) levels joined streams while they arrive.  It is not ``loudness_rows`` chunk by chunk: the gain
+follows the running integrated loudness, knot by knot on the stream's absolute hops, at a bounded rate and under the ceiling.
 """
 from __future__ import annotations
 
@@ -673,6 +676,152 @@ class StreamTempo:
         if not self._fake:
             assert got_all == want, (got_all, want)
         return (out, want, pos, nf) if return_places else (out, want)
+
+    def _stream(self) -> C.c_void_p:
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class StreamLoudness:
+    """Owns one ``smi_louds`` handle (include/sparkmi.h): joined streams are brought to a programme-loudness target while they
+    are still arriving.  The gain follows the running BS.1770 loudness of what has arrived, knot by knot on the stream's absolute
+    hops, moves at most ``max_slew_db`` a hop and stays under the peak ceiling; the filter's state, the hop sums, the blocks so
+    far, the last knot and the input not yet emitted are kept on the device per stream, so that the concatenation of a stream's
+    pieces does not depend, by a bit, on how the stream was chunked.  A piece leaves at most five hops (500 ms) behind its
+    input.  Request keys map to the handle's stream slots as in ``StreamTempo``: ``open(key, target, ...)`` takes a free slot,
+    ``push`` sends one poll's chunks, and a key's slot is free again after its last push.  A key that ``push`` meets unopened
+    is opened without a target, which measures and copies.  ``max_seconds`` bounds a stream (its blocks are kept).  All pushes
+    go to the current HIP stream at the time of the call: keep them on one stream.  ``lib``: a stand-in library."""
+
+    def __init__(self, max_streams: int, max_chunk: int, sr: int = 16000, block: Optional[int] = None, coef: Optional[np.ndarray] = None,
+                 max_seconds: float = 600.0, max_blocks: Optional[int] = None, device="cuda:0", diag: bool = False, lib=None):
+        self._lib = lib if lib is not None else _lib.pick(diag)
+        self._fake = lib is not None
+        self.device = device
+        if not self._fake:
+            import torch
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise _lib.SparkMIError("StreamLoudness runs on an MI355X only (device must be cuda:N); there is no CPU path")
+        self.max_streams, self.max_chunk = int(max_streams), int(max_chunk)
+        self.block = loudness_block(sr) if block is None else int(block)
+        if self.block < 4 or self.block % 4:
+            raise ValueError(f"block={self.block} must be a positive multiple of 4")
+        self.hop = self.block // 4
+        self.max_blocks = int(max_blocks) if max_blocks is not None else max(1, int(math.ceil(max_seconds * sr / self.hop)))
+        coef = np.ascontiguousarray(k_weighting(sr) if coef is None else coef, dtype=np.float64)
+        if coef.shape != (10,):
+            raise ValueError("coef holds b0 b1 b2 a1 a2 of two stages: 10 values")
+        self._h = C.c_void_p()
+        self._lib.check(self._lib.smi_louds_create(self.max_streams, self.max_chunk, self.block, coef.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   self.max_blocks, C.byref(self._h)), "smi_louds_create")
+        self._free: List[int] = list(range(self.max_streams))   # (open() hands out the lowest free slot)
+        self._open: dict = {}       # key -> [slot, n]
+        self.calls = 0              # smi_louds_push_rows calls so far: five launches each
+        self.last_stats = None      # [B][4] float64 on the device: the stats of the last push's rows
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.smi_louds_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """forget every open key (an abandoned stream's slots come back)"""
+        self._free = list(range(self.max_streams))
+        self._open = {}
+
+    def slot(self, key) -> Optional[int]:
+        return self._open[key][0] if key in self._open else None
+
+    def open(self, key, target: Optional[float] = None, max_gain_db: float = 20.0, ceiling: float = PEAK_CEILING,
+             max_slew_db: float = 1.0) -> int:
+        if key in self._open:
+            raise ValueError(f"request {key}: already open")
+        if not self._free:
+            raise ValueError(f"StreamLoudness: all {self.max_streams} stream slots are in use")
+        s = min(self._free)
+        self._lib.check(self._lib.smi_louds_open(self._h, s, math.nan if target is None else float(target), float(max_gain_db),
+                                                 float(ceiling), float(max_slew_db)), "smi_louds_open")
+        self._free.remove(s)
+        self._open[key] = [s, 0]
+        return s
+
+    def _walk(self, rows: Sequence[Tuple]):
+        """(piece lengths, knots made) of ``push(x, rows)``, pure host arithmetic"""
+        from .streaming import loudness_knots, loudness_piece_len
+        state = {k: v[1] for k, v in self._open.items()}
+        pieces, knots = [], []
+        for key, length, last in rows:
+            n = state.get(key, 0)
+            piece, state[key], k = loudness_piece_len(self.block, n, length, last)
+            pieces.append(piece)
+            knots.append(k - loudness_knots(n, self.hop))
+        return pieces, knots
+
+    def piece_lengths(self, rows: Sequence[Tuple]) -> List[int]:
+        """the piece lengths ``push(x, rows)`` would return, without pushing (pure host arithmetic)"""
+        return self._walk(rows)[0]
+
+    def push(self, x, rows: Sequence[Tuple], return_gains: bool = False):
+        """``x``: [B][stride] float32 on the device, row b the new samples of request ``rows[b] = (key, length, last)``.
+        Returns (out [B][out_stride] float32 on the device -- row b holds its piece, then zeros --, the pieces' lengths); a
+        length may be 0.  ``return_gains``: also (gains [B][knots][2] float64 on the device -- (G_j, flags) of the knots each
+        push made final --, their counts, and stats [B][4] float64 on the device: the loudness of the latest whole block (after
+        a stream's last push: of the whole stream), the peak so far, the latest gain, the OR of the flags).  The stats are kept
+        in ``last_stats`` either way.  A request that appears twice makes two device calls (``streaming.split_calls``), each
+        five launches; everything is enqueued on the current stream, nothing waits and nothing is copied back."""
+        from .streaming import split_calls
+        B = len(rows)
+        if not B:
+            raise ValueError("push takes at least one row")
+        if not self._fake:
+            import torch
+            if x.dim() != 2 or x.shape[0] != B or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+                raise ValueError("push takes a contiguous [B][stride] float32 tensor on the device, one row per chunk")
+        for _, length, _ in rows:
+            if not 0 <= int(length) <= self.max_chunk:
+                raise ValueError(f"a chunk of {length} samples is outside 0..max_chunk={self.max_chunk}")
+        want, nk = self._walk(rows)          # raises for a bad length before anything is opened or pushed
+        for key, _, _ in rows:
+            if key not in self._open:
+                self.open(key)
+        stride, gstride = max(1, max(want)), max(1, max(nk))
+        in_stride = 1 if self._fake else int(x.shape[1])
+        out = gains = stats = None
+        if not self._fake:
+            out = torch.empty((B, stride), dtype=torch.float32, device=self.device)
+            stats = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+            if return_gains:
+                gains = torch.empty((B, gstride, 2), dtype=torch.float64, device=self.device)
+        got_all: List[int] = []
+        for a, b in split_calls([r[0] for r in rows]):
+            n = b - a
+            i32 = lambda v: (C.c_int32 * n)(*[int(t) for t in v])   # noqa: E731
+            got = (C.c_int32 * n)()
+            src = C.c_void_p(0 if self._fake else x.data_ptr() + 4 * a * in_stride)
+            dst = C.c_void_p(0 if self._fake else out.data_ptr() + 4 * a * stride)
+            gdst = C.c_void_p(0 if gains is None else gains.data_ptr() + 16 * a * gstride)
+            sdst = C.c_void_p(0 if stats is None else stats.data_ptr() + 32 * a)
+            self._lib.check(self._lib.smi_louds_push_rows(self._h, src, in_stride, i32(self._open[r[0]][0] for r in rows[a:b]),
+                                                          i32(r[1] for r in rows[a:b]), i32(bool(r[2]) for r in rows[a:b]), n, gdst,
+                                                          2 * gstride, dst, stride, got, sdst, None if self._fake else self._stream()),
+                            "smi_louds_push_rows")
+            self.calls += 1
+            got_all += list(got)
+            for key, length, last in rows[a:b]:
+                self._open[key][1] += int(length)
+                if last:
+                    self._free.append(self._open.pop(key)[0])
+        if not self._fake:
+            assert got_all == want, (got_all, want)
+        self.last_stats = stats
+        return (out, want, gains, nk, stats) if return_gains else (out, want)
 
     def _stream(self) -> C.c_void_p:
         import torch

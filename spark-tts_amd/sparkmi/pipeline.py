@@ -47,6 +47,14 @@ EOS_BIAS_KEY = "eos_bias"
 
 # request key: the programme loudness (LUFS) the request's waveform is brought to; it overrides the call's ``loudness``
 LOUDNESS_KEY = "loudness"
+
+
+class StreamLoudnessRefused(ValueError, TypeError):
+    """``loudness`` on a chunked stream with overlapping chunks.  A ValueError like the refusals of ``tempo`` and
+    ``output_sample_rate`` there; a TypeError too, because before the calls knew the keyword that is what passing it raised, and a
+    caller that catches that keeps working."""
+
+
 LIMITED = (None, "max_gain", "ceiling")   # what bounded a row's gain (include/sparkmi.h, smi_loud_rows: limit 0 / 1 / 2)
 # request key: the request's own tempo (0.5 .. 2.0; > 1: faster); it overrides the call's ``tempo``
 TEMPO_KEY = "tempo"
@@ -315,13 +323,34 @@ class SparkTTS:
                              "carried state); pass joined=True for contiguous pieces at that tempo, or use inference / "
                              "inference_batch / serve / inference_long / inference_long_stream")
 
+    @staticmethod
+    def _no_stream_loudness(loudness, who: str) -> None:
+        if loudness is not None:
+            raise StreamLoudnessRefused(f"{who}: loudness is not supported for overlapping chunks (the running gain is defined on "
+                                        "one contiguous stream and carries state across chunk edges); pass joined=True for "
+                                        "contiguous pieces at that loudness, or use inference / inference_batch / serve / "
+                                        "inference_long / inference_long_stream")
+
+    @staticmethod
+    def _check_slew(max_slew_db) -> None:
+        v = max_slew_db
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= v <= 200:
+            raise ValueError(f"max_slew_db must be a number in 0..200 (dB a hop of 100 ms), not {v!r}")
+
+    @staticmethod
+    def _stream_loudness_info(row: Sequence[float]) -> dict:
+        """a finished stream's entry: ``loudness`` (LUFS of the whole utterance before the gain, the batch measure), ``peak``,
+        ``gain`` (of the last knot) and ``flags`` (the OR over all knots: 1 max_gain, 2 ceiling, 4 slew, 8 hold)"""
+        return dict(loudness=float(row[0]), peak=float(row[1]), gain=float(row[2]), flags=int(row[3]))
+
     def _stream_stages(self, who: str, output_sample_rate: Optional[int], max_streams: int, audio_chunk_duration: float,
-                       max_audio_chunk_duration: float, audio_chunk_size_scale_factor: float, audio_chunk_overlap_duration: float):
-        """The stages of a ``joined=True`` call with a tempo, in the batch path's order, their slots all free: (the crossfade -- a
-        ``StreamJoiner`` at 1/1 --, the ``StreamTempo``, and with ``output_sample_rate`` the resampler with state -- a second
-        ``StreamJoiner`` with overlap 0 at that ratio, which is plain concatenation plus the filter --, else None).  Everything is
-        checked before any device call."""
-        from .audio import StreamJoiner, StreamTempo, tempo_frame
+                       max_audio_chunk_duration: float, audio_chunk_size_scale_factor: float, audio_chunk_overlap_duration: float,
+                       loudness: bool = False):
+        """The stages of a ``joined=True`` call with a tempo or a loudness, in the batch path's order, their slots all free: (the
+        crossfade -- a ``StreamJoiner`` at 1/1 --, the ``StreamTempo``, with ``loudness`` the ``StreamLoudness``, else None, and
+        with ``output_sample_rate`` the resampler with state -- a second ``StreamJoiner`` with overlap 0 at that ratio, which is
+        plain concatenation plus the filter --, else None).  Everything is checked before any device call."""
+        from .audio import StreamJoiner, StreamLoudness, StreamTempo, tempo_frame
         out_ratio = self._output_ratio(output_sample_rate)
         fade = self._stream_joiner(who, None, max_streams, audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor,
                                    audio_chunk_overlap_duration)
@@ -333,24 +362,36 @@ class SparkTTS:
             self._tempos[key] = StreamTempo(*key, device=self.device)
         scale = self._tempos[key]
         scale.reset()
+        longest = 4 * (scale.history + scale.max_chunk) + scale.N   # what a push of the tempo stage emits at most (include/sparkmi.h)
+        loud = None
+        if loudness:
+            key = (int(max_streams), longest)
+            if getattr(self, "_louds", None) is None:
+                self._louds = {}
+            if key not in self._louds:
+                self._louds[key] = StreamLoudness(*key, sr=self.sample_rate, max_seconds=3600.0, device=self.device)
+            loud = self._louds[key]
+            loud.reset()
+            longest += 5 * loud.hop   # a stream's last push brings what the stage held back
         rate = None
-        if out_ratio is not None:   # a push of the tempo stage emits at most 4 (history + chunk) + N samples (include/sparkmi.h)
-            key = (int(max_streams), 4 * (scale.history + scale.max_chunk) + scale.N, 0) + tuple(out_ratio)
+        if out_ratio is not None:
+            key = (int(max_streams), longest, 0) + tuple(out_ratio)
             if key not in self._joiners:
                 self._joiners[key] = StreamJoiner(*key, device=self.device)
             rate = self._joiners[key]
             rate.reset()
-        return fade, scale, rate
+        return fade, scale, loud, rate
 
     def _staged_push(self, stages, x, rows: Sequence[Tuple]):
         """One poll's ready chunks ``rows[b] = (key, length, last)`` (``x`` [B][stride] on the device) through the stages of
         ``_stream_stages``, all enqueued on the current stream: (rows on the device, {b: its row there}, the final pieces'
-        lengths, the pieces' lengths behind the tempo stage -- what a listener hears, at the model's rate).  A stage is skipped
-        for a push whose piece from the stage before is empty, unless it is the stream's last: its later pieces are empty."""
+        lengths, the pieces' lengths behind the tempo stage -- what a listener hears, at the model's rate --, and {b: the
+        loudness stage's stats row, on the device} for the rows that are their stream's last).  A stage is skipped for a push
+        whose piece from the stage before is empty, unless it is the stream's last: its later pieces are empty."""
         cur, lens = stages[0].push(x, rows)
         lens = list(lens)
         at = {b: b for b in range(len(rows))}
-        heard = lens
+        heard, final = lens, {}
         for stage in stages[1:]:
             if stage is None:
                 continue
@@ -370,7 +411,9 @@ class SparkTTS:
                     lens[b] = v
             if stage is stages[1]:
                 heard = list(lens)
-        return cur, at, lens, heard
+            elif stage is stages[2] and go:
+                final = {b: stage.last_stats[i] for i, b in enumerate(go) if rows[b][2]}
+        return cur, at, lens, heard, final
 
     @staticmethod
     def _no_stream_rate(output_sample_rate: Optional[int], who: str) -> None:
@@ -633,7 +676,9 @@ class SparkTTS:
                          audio_chunk_duration: float = 1.0, max_audio_chunk_duration: float = 30.0,
                          audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
                          decode_stride: int = 10, output_sample_rate: Optional[int] = None,
-                         joined: bool = False, tempo: Optional[float] = None) -> Iterator[np.ndarray]:
+                         joined: bool = False, tempo: Optional[float] = None, loudness: Optional[float] = None,
+                         peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
+                         max_slew_db: float = 1.0) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
@@ -650,8 +695,15 @@ class SparkTTS:
         waveform, the filter's state being kept across the chunk edges; a piece that would be empty is not yielded.
         Refused (ValueError, before any device call) if the first chunk is shorter than two overlaps.
 
-        There is no ``loudness`` here: the integrated loudness of BS.1770 is a property of the whole utterance, which a
-        chunk that must leave before the utterance ends cannot know (``inference`` / ``inference_long_stream`` take it).
+        ``loudness`` (LUFS; None: nothing new is built or launched) needs ``joined=True``.  The integrated loudness of BS.1770
+        is a property of the whole utterance, which a piece that must leave before the utterance ends cannot know, so this is
+        not the batch stage: the gain follows the running integrated loudness of what has arrived, knot by knot on the
+        stream's absolute hops of 100 ms, moves at most ``max_slew_db`` a hop, is at most ``max_gain_db`` and keeps every
+        sample under ``peak_ceiling`` (include/sparkmi.h, smi_louds_*; ``audio.StreamLoudness``).  The stage sits
+        behind the tempo stage and before the resampler with state, holds back up to five hops (500 ms) and keeps the total
+        length; the pieces do not depend, by a bit, on the chunking.  After the last piece ``self.last_loudness`` holds
+        {``loudness`` (of the whole utterance before the gain, equal to the batch measure), ``peak``, ``gain`` (the last
+        knot's), ``flags``}: one 32-byte copy.  With ``joined=False`` a given ``loudness`` is refused (ValueError).
 
         ``tempo`` (0.5 .. 2.0, to a hundredth; > 1: faster; None or 1.0: nothing new is built or launched) needs
         ``joined=True``: the joined stream's speaking rate is changed at unchanged pitch while it is still arriving (WSOLA with
@@ -664,14 +716,20 @@ class SparkTTS:
         ``joined=False`` a given ``tempo`` is refused (ValueError): overlapping chunks have no edges to carry state across."""
         if not joined:
             self._no_stream_tempo(tempo, "inference_stream")
+            self._no_stream_loudness(loudness, "inference_stream")
             self._no_stream_rate(output_sample_rate, "inference_stream")
         rate = self._tempo_ratios([{}], tempo)[0]
+        target = self._loudness_targets([{}], loudness, peak_ceiling, max_gain_db)[0]
+        self._check_slew(max_slew_db)
         sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
         stages = None
-        if joined and rate is not None:
-            stages = self._stream_stages("inference_stream", output_sample_rate, 1, *sched_args)
+        if joined and (rate is not None or target is not None):
+            stages = self._stream_stages("inference_stream", output_sample_rate, 1, *sched_args, loudness=target is not None)
             joiner = stages[0]
-            stages[1].open(0, *rate)
+            stages[1].open(0, *(rate or (1, 1)))
+            if stages[2] is not None:
+                stages[2].open(0, target, max_gain_db, peak_ceiling, max_slew_db)
+                self.last_loudness = None
         else:
             joiner = self._stream_joiner("inference_stream", output_sample_rate, 1, *sched_args) if joined else None
         if gender is not None:
@@ -701,8 +759,11 @@ class SparkTTS:
             else:
                 wav = torch.zeros((1, 1), dtype=torch.float32, device=self.device)
             if stages is not None:
-                out, at, lens, _ = self._staged_push(stages, wav, [(0, len(chunk) * hop, last)])
-                return out[at[0], : lens[0]].cpu().numpy().copy() if 0 in at else np.zeros(0, dtype=np.float32)
+                out, at, lens, _, final = self._staged_push(stages, wav, [(0, len(chunk) * hop, last)])
+                w = out[at[0], : lens[0]].cpu().numpy().copy() if 0 in at else np.zeros(0, dtype=np.float32)
+                if 0 in final:   # behind the last piece
+                    self.last_loudness = self._stream_loudness_info(final[0].cpu().tolist())
+                return w
             out, lens = joiner.push(wav, [(0, len(chunk) * hop, last)])
             return out[0, : lens[0]].cpu().numpy().copy()
 
@@ -870,7 +931,8 @@ class SparkTTS:
                      audio_chunk_size_scale_factor: float = 8.0, audio_chunk_overlap_duration: float = 0.1,
                      max_open: Optional[int] = None, max_ahead: Optional[float] = None, resume_ahead: Optional[float] = None,
                      clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None, joined: bool = False,
-                     tempo: Optional[float] = None):
+                     tempo: Optional[float] = None, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
+                     max_gain_db: float = 20.0, max_slew_db: float = 1.0):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -915,8 +977,14 @@ class SparkTTS:
         sizes and rate; its slots are all freed when a call begins, so nothing of a request outlives its call.)  Refused
         (ValueError, before any device call) if the first chunk is shorter than two overlaps.
 
-        There is no ``loudness`` here, as in ``inference_stream``: integrated loudness needs the whole utterance (``serve``
-        takes it).
+        ``loudness`` and a request's own ``loudness`` key, which overrides it (LUFS; None everywhere: nothing new is built or
+        launched and every piece keeps its bits), need ``joined=True``; with ``joined=False`` either is refused (ValueError).
+        Every request's stream then goes through a loudness stream of its own (``inference_stream`` describes the running
+        gain; include/sparkmi.h, smi_louds_*; ``audio.StreamLoudness``) behind the tempo stage and before the resampler with
+        state, five launches more per poll; a request without a target is measured and copied.  The stage holds back up to
+        500 ms of a request and keeps its total; the ``Pacer`` goes on counting the lengths behind the tempo stage.  After a
+        request's last piece ``self.last_loudness[index]`` holds its entry as in ``inference_stream`` (one 32-byte copy).
+        Whether a call has the stage is settled when it begins, as for ``tempo``.
 
         ``tempo`` and a request's own ``tempo`` key, which overrides it (0.5 .. 2.0; None or 1.0 everywhere: nothing new is
         built or launched and every piece keeps its bits), need ``joined=True``; with ``joined=False`` either is refused
@@ -932,25 +1000,34 @@ class SparkTTS:
         an iterator into a call without them is refused (ValueError): pass a list, or a ``tempo`` for the call."""
         if not joined:
             self._no_stream_tempo(tempo, "serve_stream")
+            self._no_stream_loudness(loudness, "serve_stream")
             self._no_stream_rate(output_sample_rate, "serve_stream")
         call_rate = self._tempo_ratios([{}], tempo)[0]
+        call_target = self._loudness_targets([{}], loudness, peak_ceiling, max_gain_db)[0]
+        self._check_slew(max_slew_db)
         rates: Dict[int, Tuple[int, int]] = {}   # request index -> its tempo as (p, q), (1, 1) without one
+        targets: Dict[int, Optional[float]] = {}   # request index -> its loudness target, None without one
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
-                for k in (FORK_KEY,) + (() if joined else (TEMPO_KEY,)) + tuple(LOGPROB_KEYS):
+                for k in (FORK_KEY,) + (() if joined else (TEMPO_KEY, LOUDNESS_KEY)) + tuple(LOGPROB_KEYS):
                     if k in r:
                         raise ValueError(f"request {i}: {k} is not supported by serve_stream" + (
-                            " with overlapping chunks; pass joined=True" if k == TEMPO_KEY else ""))
+                            " with overlapping chunks; pass joined=True" if k in (TEMPO_KEY, LOUDNESS_KEY) else ""))
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 rates[i] = self._tempo_ratios([r], tempo, i)[0] or (1, 1)
+                try:
+                    targets[i] = self._loudness_targets([r], loudness, peak_ceiling, max_gain_db)[0]
+                except ValueError as e:
+                    raise ValueError(str(e).replace("request 0:", f"request {i}:", 1)) from None
                 yield r
 
-        staged = call_rate is not None
+        staged, leveled = call_rate is not None, call_target is not None
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
             for _ in checked(requests):
                 pass
             staged = staged or any(v != (1, 1) for v in rates.values())
+            leveled = leveled or any(v is not None for v in targets.values())
         decode_stride = int(decode_stride)
         if decode_stride < 1:
             raise ValueError("decode_stride must be >= 1")
@@ -972,9 +1049,12 @@ class SparkTTS:
                         audio_chunk_overlap_duration=audio_chunk_overlap_duration)
         sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
         stages = None
-        if joined and staged:
-            stages = self._stream_stages("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args)
+        if joined and (staged or leveled):
+            stages = self._stream_stages("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args,
+                                         loudness=leveled)
             joiner = stages[0]
+            if leveled:
+                self.last_loudness = {}
         else:
             joiner = self._stream_joiner("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args) if joined else None
         if getattr(self, "_voc_stream", None) is None:
@@ -986,6 +1066,9 @@ class SparkTTS:
                 if stages is None and rates[i] != (1, 1):
                     raise ValueError(f"request {i}: a tempo of its own from an iterator of requests, in a serve_stream call that began "
                                      "without the tempo stages; pass the requests as a list, or a tempo for the call")
+                if (stages is None or stages[2] is None) and targets[i] is not None:
+                    raise ValueError(f"request {i}: a loudness of its own from an iterator of requests, in a serve_stream call that "
+                                     "began without the loudness stage; pass the requests as a list, or a loudness for the call")
                 if r.get("gender") is not None:
                     prompt, g = self.process_prompt_control(r["gender"], r.get("pitch"), r.get("speed"), r["text"]), None
                 else:
@@ -1025,9 +1108,11 @@ class SparkTTS:
 
         def collect_joined(job):
             chunks, (_, out, *rest) = job
-            at, n_out, heard = rest if stages is not None else ({b: b for b in range(len(chunks))}, rest[0], None)
+            at, n_out, heard, final = rest if stages is not None else ({b: b for b in range(len(chunks))}, rest[0], None, {})
             with torch.cuda.stream(vs):
                 out = out.cpu().numpy()
+                for b, row in final.items():   # behind a request's last piece
+                    self.last_loudness[chunks[b][0]] = self._stream_loudness_info(row.cpu().tolist())
             for b, (key, index, sem, last) in enumerate(chunks):
                 if pacer.active:
                     frames = max(0, len(sem) - (overlap if index else 0))
@@ -1092,6 +1177,8 @@ class SparkTTS:
                         mux.open(r[0], r[3])
                         if stages is not None:   # (host only; a request without a tempo copies through at 1/1)
                             stages[1].open(r[0], *rates[r[0]])
+                            if stages[2] is not None:   # (host only; a request without a target is measured and copied)
+                                stages[2].open(r[0], targets[r[0]], max_gain_db, peak_ceiling, max_slew_db)
                 self.model.decode(decode_stride)   # enqueued: it runs while the host collects the previous poll's chunks
                 if job is not None:
                     yield from collect(job)

@@ -184,6 +184,33 @@ def tempo_piece_len(p: int, q: int, N: int, D: int, n_before: int, frames_before
     return piece, n, f
 
 
+# ---- loudness of joined streams (include/sparkmi.h, smi_louds_*): what a push emits, as host arithmetic
+def loudness_knots(n: int, hop: int) -> int:
+    """knots a stream of ``n`` samples that goes on has made: knot j needs blocks 0 .. j whole, ``n >= (j + 4) hop``"""
+    return max(0, int(n) // int(hop) - 3)
+
+
+def loudness_emitted(n: int, hop: int) -> int:
+    """E(n): samples a stream that goes on has emitted: hop j needs knot j + 1, ``n >= (j + 5) hop``"""
+    return int(hop) * max(0, int(n) // int(hop) - 4)
+
+
+def loudness_piece_len(block: int, n_before: int, length: int, last: bool) -> Tuple[int, int, int]:
+    """(piece length, n after, knots made after) of one push -- the twin of ``smi_louds_piece_len``: a stream goes on with
+    ``loudness_emitted(n)`` samples out and ``loudness_knots(n)`` knots; a finished one has emitted all its L samples and has
+    the knots 0 .. floor((L - 1) / hop) + 1 (none at L = 0).  ValueError for a bad argument."""
+    block, n_before, length = int(block), int(n_before), int(length)
+    if block < 4 or block % 4:
+        raise ValueError(f"block={block} must be a positive multiple of 4")
+    if n_before < 0 or length < 0:
+        raise ValueError("negative counter or length")
+    hop = block // 4
+    n = n_before + length
+    if last:
+        return n - loudness_emitted(n_before, hop), n, ((n - 1) // hop + 2 if n else 0)
+    return loudness_emitted(n, hop) - loudness_emitted(n_before, hop), n, loudness_knots(n, hop)
+
+
 def stream_chunks(token_iter:Iterator[Sequence[int]], scheduler: ChunkScheduler) -> Iterator[List[int]]:
     """Token increments in, ready chunks out (the generator form of the reference loop)."""
     for inc in token_iter:
