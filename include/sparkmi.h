@@ -795,7 +795,8 @@ int smi_concat_rows(const float* in_dev, long long in_stride, const int32_t* n_h
  * t + 128, then t and t + 64, ...).  loudness = -0.691 + 10 log10(sum of the z passing both gates / their count).
  * Defined here where the standard is silent:  1 <= L < block: one block, the whole span, z = (the hop sums in ascending
  * order) / fl64(L), and the absolute gate alone;  no block passes, or L = 0: loudness = -inf, gain = 1, limit = 0.
- * Peak.  peak = max |x| over the span, exact.  It is a SAMPLE peak: the 4x oversampled true peak is not measured.
+ * Peak.  peak = max |x| over the span, exact.  It is a SAMPLE peak: the 4x oversampled true peak is not measured
+ * (not here: smi_limit_rows below measures it and holds the ceiling sample by sample).
  * Gain, float64, formed on the device:  g = 10^((target - loudness) / 20);  g = min(g, 10^(max_gain_db / 20)) (limit = 1 where
  * that binds);  if g * peak > ceiling then g = ceiling / peak (limit = 2).  A NaN target measures only: g = 1, limit = 0.
  * Apply (smi_gain_rows).  out[i] = fl32(fl64(x[i]) * g): one float64 product, one rounding, no FMA.
@@ -818,6 +819,64 @@ int smi_loud_rows(const float* in_dev, long long in_stride, const int32_t* n_hos
  * place); any other overlap is refused. */
 int smi_gain_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
                   const double* stats_dev, float* out_dev, long long out_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Output limiter: a look-ahead limiter with true-peak detection that keeps every sample of a row at or under a ceiling by
+ * reducing the gain around the overs only -- it starts ahead of them and recovers smoothly behind them --, on the device.  Free
+ * functions like the sections above: no handle, no state, asynchronous on the caller's stream, never synchronising, opt-in.
+ * Every argument of every row is checked before anything reaches the device: a bad one returns SMI_EINVAL, names the argument
+ * in smi_last_error and launches nothing.  B <= 64, n <= 2^24.  The limiter is feed-forward -- a sliding minimum followed by
+ * FIR smoothing --: no recursion, no carry, no order of segments, so a sample's bits follow from the definition alone.
+ *
+ * A row is limited over a span x[start .. end) of L samples, taken to be finite.  Samples outside the span are never read: they
+ * count as zero for the oversampler and as "no over" (r = 1) for the gain, and they are copied through unchanged, as
+ * smi_gain_rows copies them.  Everything is float64; fl() is one rounding: every product and every sum is rounded on its own
+ * (no FMA).  i and j index the span.
+ *
+ * 1 Envelope.  e[i] = max(|x[i]|, |u_1[i]|, .., |u_{P-1}[i]|), P = phases.  u_k[i], the interpolated value at time i + k / P, is
+ *     u_k[i] = sum over d = -10 .. 9, ascending from 0, of fl(h[P d + k + H] * fl64(x[i - d]))
+ *   -- every tap of phase k.  h = taps_host: 2 H + 1 float64 taps, H = 10 P, data the caller passes (sparkmi/audio.py:
+ *   resample_taps(P, 1), the resampler's own low-pass; the device designs no filter).  n_taps = 0: e[i] = |x[i]|, the
+ *   sample-peak mode.  Phase 0 is the sample itself, so the sample peak is always covered exactly.
+ * 2 Required gain.  v = fl(g * e[i]);  r[i] = ceiling / v (one correctly rounded division) where v > ceiling, else 1.  g is the
+ *   row's gain, read from device memory: gain_dev[b * gain_stride]; a null gain_dev: g = 1.  (The gain of smi_loud_rows' stats
+ *   is stats_dev + 2 with stride 4.)
+ * 3 Look-ahead minimum.  m[i] = min r[j] over i - R <= j <= i + A, r = 1 outside the span; A = lookahead, R = release, in
+ *   samples, 0 <= A <= 256, 0 <= R <= 2048.  m is defined outside the span as well.
+ * 4 Smoothing.  s'[i] = 1 - (the sum over k = -R .. A, ascending from 0, of fl(w[k + R] * fl(1 - m[i - k])));
+ *   s[i] = min(s'[i], r[i]).  w = win_host: A + R + 1 non-negative float64 weights, |sum of w (ascending) - 1| <= 1e-12, data
+ *   the caller passes (sparkmi/audio.py: limiter_window).  The sum is taken on the reduction 1 - m, so s is exactly 1 where no
+ *   over lies within A + R samples on either side.  Every m[i - k] of the sum has i inside its window, so s'[i] <= r[i] in exact
+ *   arithmetic; the min removes the last rounding.
+ * 5 Apply.  out[i] = fl32(fl(fl(fl64(x[i]) * g) * s[i])), then clamped to +-c32, the largest float32 <= ceiling.  Since
+ *   |fl64(x[i]) g s[i]| <= ceiling up to rounding, the clamp can only move a value by the final float32 rounding.
+ * 6 Stats, [4] float64 a row, all exact: fl(g * max e) -- the true peak going in (the sample peak with n_taps = 0) --; g;
+ *   min s; the count of samples with s < 1.  L = 0: (0, g, 1, 0).
+ *
+ * Guarantees.  A row's output and stats, bit for bit, depend on its span and the parameters alone -- not on B, the row's
+ * place, the strides, what lies outside the span or the grid.  |out[i]| <= ceiling for every sample of the span, exactly.  Where
+ * s[i] == 1, out[i] is smi_gain_rows' fl32(fl64(x[i]) g) bit for bit (but for a product in (c32, ceiling] that float32 rounds
+ * up past the ceiling, which the clamp brings to c32).  What the limiter does not promise: the true peak of the OUTPUT is
+ * held only as far as a gain that varies between samples allows (DESIGN.md 4.1.7 records the overshoot measured).
+ *
+ * Launches, whatever B, no atomics: k_limit_win, ceil((A + R + 1) / 384) launches of one block that carry the window to
+ * work_dev as kernel arguments (no copy is enqueued, nothing waits); k_limit_env, grid (tiles of 1024 samples of the span,
+ * rows) -- the tile and 10 samples on either side staged in LDS, r and the tile's max e to work_dev --; k_limit_apply, grid
+ * (tiles of 1024 samples up to out_stride, rows) -- r over the tile and A + R samples on either side staged in LDS, the minimum
+ * formed there in place by doubling, then the smoothing sums, the product, the clamp, and the tile's min s and count to
+ * work_dev --; k_limit_stats, one block a row.  r travels through work_dev, so out_dev == in_dev is allowed. */
+/* float64 elements of work_dev that smi_limit_rows needs for B rows of at most n_max samples; -1 for a bad argument.  Pure host. */
+long long smi_limit_work_len(long long n_max, int B);
+/* in_dev [B][in_stride] f32, row b valid for n_host[b]; 0 <= start_host[b] <= end_host[b] <= n_host[b] (both null: the whole
+ * row); gain_dev (may be null) and gain_stride >= 0 as in 2; ceiling > 0; taps_host [n_taps], n_taps = 0 or 20 phases + 1,
+ * 1 <= phases <= 8; win_host [lookahead + release + 1]; work_dev [work_len] float64 scratch (contents do not matter before,
+ * mean nothing after).  Row b of out_dev [B][out_stride] receives the row's n samples -- the span limited, the rest copied --
+ * and zeros from n to out_stride (>= the longest row); out_dev == in_dev with equal strides is allowed (in place), any other
+ * overlap is refused.  stats_dev [B][4] float64 as in 6; it must not overlap gain_dev. */
+int smi_limit_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                   const double* gain_dev, int gain_stride, double ceiling, const double* taps_host, int n_taps, int phases, int lookahead,
+                   int release, const double* win_host, double* work_dev, long long work_len, float* out_dev, long long out_stride,
+                   double* stats_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tempo: a pitch-preserving time-scale change of rows (WSOLA: overlap-add of frames whose places are found by a waveform

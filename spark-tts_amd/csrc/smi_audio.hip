@@ -20,6 +20,10 @@
 //                gates) and the gain to a target: the serial filter is cut into segments of LD_SEG samples, one lane each, that
 //                run from zero state; one wave per row carries the true states across; a second pass sums y^2.  No atomics.
 //   k_gain_rows                  rows times their gain, read from the device (smi_gain_rows).
+//   k_limit_win, k_limit_env, k_limit_apply, k_limit_stats   the look-ahead true-peak limiter of rows (smi_limit_rows), feed-forward
+//                and float64: the envelope of the 4x oversampled span and the required gain from a tile staged in LDS; then, per
+//                tile, the sliding minimum formed in LDS in place by doubling, the FIR smoothing of the reduction, the product and
+//                the clamp; the window arrives as kernel arguments, the tiles' extremes are reduced one block a row.  No atomics.
 //   k_tempo_search, k_tempo_ola  pitch-preserving time-scale change of rows (smi_tempo_rows; WSOLA): one block per row walks the
 //                frames in order and, where a frame is searched, stages the quantised target and candidate samples in LDS as
 //                int16 and sums exact squared differences in 64-bit integers; the overlap-add is then parallel.  No atomics.
@@ -57,7 +61,16 @@
 #define LD_PITCH (LD_SEG + 1)   // floats between two segments in LDS
 #define LD_GATE 256             // threads of k_loud_gate
 #define GN_TILE 1024            // samples a block of k_gain_rows
-#define TP_BLOCK 512            // threads of k_tempo_search: a candidate each, the usual 2 D + 1 = 481 in one round
+#define LM_TILE 1024            // samples a block of k_limit_env / k_limit_apply
+#define LM_HALO 10              // H / phases: the samples the interpolator reaches on either side
+#define LM_MAX_PHASES 8
+#define LM_MAX_TAPS (2 * LM_HALO * LM_MAX_PHASES + 1)
+#define LM_MAX_A 256            // the look-ahead
+#define LM_MAX_R 2048           // the release
+#define LM_WIN_PAD 2312         // float64 elements at the head of work_dev that hold the window (A + R + 1 <= 2305)
+#define LM_WIN_ARG 384          // weights one k_limit_win launch carries as kernel arguments
+#define LM_QPT ((LM_TILE + 2 * (LM_MAX_A + LM_MAX_R) + RS_BLOCK - 1) / RS_BLOCK)   // LDS entries a thread of k_limit_apply at most
+#define TP_BLOCK 512           // threads of k_tempo_search: a candidate each, the usual 2 D + 1 = 481 in one round
 #define TP_TILE 1024            // output samples a block of k_tempo_ola
 #define TP_MAX_N 2048           // the frame
 #define TP_MAX_D 1024           // the search radius
@@ -705,6 +718,200 @@ __global__ __launch_bounds__(RS_BLOCK) void k_gain_rows(LdArgs a, const double* 
     }
     y[i] = v;
   }
+}
+
+// ---- look-ahead true-peak limiter of rows (smi_limit_rows): feed-forward, float64, every product and sum rounded on its own
+struct LmTaps {
+  double h[LM_MAX_TAPS];   // the interpolator, h[0 .. 2H], H = LM_HALO * phases
+  int32_t n, phases;       // n = 0: the sample-peak mode
+};
+struct LmWin {
+  double w[LM_WIN_ARG];
+};
+struct LmLayout {          // float64 offsets into work_dev: the window, then a part per row (r, then three values a tile)
+  long long rows, row, emax, smin, cnt;
+};
+
+// the smoothing window travels as kernel arguments, LM_WIN_ARG weights a launch: nothing is copied and nothing waits
+__global__ __launch_bounds__(RS_BLOCK) void k_limit_win(LmWin w, int cnt, double* __restrict__ dst) {
+  for (int i = threadIdx.x; i < cnt; i += RS_BLOCK) dst[i] = w.w[i];
+}
+
+// block-wide max / min / sum over RS_BLOCK threads; max and min are exact in any order, the sum is one of small integers
+template <int OP>
+__device__ __forceinline__ double lm_block_red(double v, double* s) {
+  __syncthreads();
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = RS_BLOCK / 2; o; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const double p = s[threadIdx.x], q = s[threadIdx.x + o];
+      s[threadIdx.x] = OP == 0 ? fmax(p, q) : (OP == 1 ? fmin(p, q) : p + q);
+    }
+    __syncthreads();
+  }
+  return s[0];
+}
+
+// grid (tiles of LM_TILE samples of the span, rows).  The tile and LM_HALO samples on either side go to LDS with coalesced
+// reads (zeros outside the span, which is never read); a thread then takes every RS_BLOCK-th sample: the phases' sums in
+// ascending d, the envelope e, and the required gain r to the row's part of work.  The tile's max e goes beside it.
+__global__ __launch_bounds__(RS_BLOCK) void k_limit_env(LdArgs a, LmTaps tp, const double* __restrict__ gain, int gain_stride, double ceiling,
+                                                        const float* __restrict__ in, long long in_stride, double* __restrict__ work,
+                                                        LmLayout lay) {
+  __shared__ float xs[LM_TILE + 2 * LM_HALO];
+  __shared__ double red[RS_BLOCK];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const LdRow r = a.r[b];
+  const int t0 = blockIdx.x * LM_TILE;
+  if (t0 >= r.len) return;
+  const float* x = in + (size_t)b * in_stride + r.start;
+  for (int i = tid; i < LM_TILE + 2 * LM_HALO; i += RS_BLOCK) {
+    const int j = t0 - LM_HALO + i;
+    xs[i] = j >= 0 && j < r.len ? x[j] : 0.f;
+  }
+  __syncthreads();
+  const double g = gain ? gain[(size_t)b * gain_stride] : 1.0;
+  double* row = work + lay.rows + (size_t)b * lay.row;
+  const int cnt = min(LM_TILE, r.len - t0);
+  const int P = tp.phases, H = LM_HALO * P;
+  double emax = 0.0;
+  for (int i = tid; i < cnt; i += RS_BLOCK) {
+    const float* xc = xs + LM_HALO + i;
+    double e = fabs((double)xc[0]);
+    if (tp.n) {
+      for (int k = 1; k < P; ++k) {
+        double u = 0.0;
+        for (int d = -LM_HALO; d < LM_HALO; ++d) u = u + tp.h[P * d + k + H] * (double)xc[-d];   // (every tap of phase k)
+        e = fmax(e, fabs(u));
+      }
+    }
+    const double v = g * e;
+    row[t0 + i] = v > ceiling ? ceiling / v : 1.0;
+    emax = fmax(emax, e);
+  }
+  emax = lm_block_red<0>(emax, red);
+  if (!tid) row[lay.emax + blockIdx.x] = emax;
+}
+
+// grid (tiles of LM_TILE samples of the row up to out_stride, rows).  A tile that meets the span stages r over its samples and
+// A + R more on either side (1 outside the span) in LDS; the forward minimum over A + R + 1 entries is formed in place by
+// doubling -- every thread reads its entries of a round into registers before any is written --, so F[i] = min r[i .. i + A + R]
+// and m[j] = F[j - R]; the entries become the reductions 1 - m; a thread then sums its samples' windows in ascending k.  The
+// tile's min s and its count of s < 1 go to work.  in and out may be one buffer: a block reads the samples it writes, no others.
+__global__ __launch_bounds__(RS_BLOCK) void k_limit_apply(LdArgs a, int A, int R, const double* __restrict__ gain, int gain_stride, float c32,
+                                                          const double* __restrict__ win, const float* in, long long in_stride,
+                                                          const double* __restrict__ rq, double* __restrict__ tiles, LmLayout lay,
+                                                          float* out, long long out_stride) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  __shared__ double red[RS_BLOCK];
+  double* q = (double*)rs_lds;
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const LdRow r = a.r[b];
+  const float* x = in + (size_t)b * in_stride;
+  float* y = out + (size_t)b * out_stride;
+  const long long k0 = (long long)blockIdx.x * LM_TILE;
+  const bool hit = r.len > 0 && k0 < (long long)r.start + r.len && k0 + LM_TILE > r.start;
+  double s[LM_TILE / RS_BLOCK];
+#pragma unroll
+  for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) s[u] = 1.0;
+  if (hit) {
+    const int W = A + R, nq = LM_TILE + 2 * W;
+    const double* rr = rq + (size_t)b * lay.row;
+    const long long j0 = k0 - r.start - W;   // the span's index of q[0]
+    for (int i = tid; i < nq; i += RS_BLOCK) {
+      const long long j = j0 + i;
+      q[i] = j >= 0 && j < r.len ? rr[j] : 1.0;
+    }
+    __syncthreads();
+    double own[LM_TILE / RS_BLOCK];
+#pragma unroll
+    for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) own[u] = q[W + tid + u * RS_BLOCK];
+    int cur = 1;
+    while (cur < W + 1) {   // F over `cur` entries -> over min(2 cur, W + 1)
+      const int off = 2 * cur <= W + 1 ? cur : W + 1 - cur;
+      double t[LM_QPT];
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < LM_QPT; ++u) {
+        const int i = tid + u * RS_BLOCK;
+        t[u] = i < nq ? (i + off < nq ? fmin(q[i], q[i + off]) : q[i]) : 0.0;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < LM_QPT; ++u) {
+        const int i = tid + u * RS_BLOCK;
+        if (i < nq) q[i] = t[u];
+      }
+      cur += off;
+    }
+    __syncthreads();
+    for (int i = tid; i < nq; i += RS_BLOCK) q[i] = 1.0 - q[i];
+    __syncthreads();
+    double acc[LM_TILE / RS_BLOCK];
+#pragma unroll
+    for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) acc[u] = 0.0;
+    const double* qc = q + tid + A;   // m[j - k] of the tile's sample c lies at q[c + A - k]
+    for (int k = -R; k <= A; ++k) {
+      const double wk = win[k + R];
+#pragma unroll
+      for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) acc[u] = acc[u] + wk * qc[u * RS_BLOCK - k];
+    }
+#pragma unroll
+    for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) s[u] = fmin(1.0 - acc[u], own[u]);
+  }
+  const double g = gain ? gain[(size_t)b * gain_stride] : 1.0;
+  double smin = 1.0, cnt = 0.0;
+#pragma unroll
+  for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) {
+    const long long i = k0 + tid + u * RS_BLOCK;
+    if (i >= out_stride) continue;
+    float v = 0.f;
+    if (i < r.n) {
+      v = x[i];
+      if (i >= r.start && i < (long long)r.start + r.len) {
+        v = (float)(((double)v * g) * s[u]);
+        v = v > c32 ? c32 : (v < -c32 ? -c32 : v);
+        smin = fmin(smin, s[u]);
+        if (s[u] < 1.0) cnt = cnt + 1.0;
+      }
+    }
+    y[i] = v;
+  }
+  if (!hit) return;
+  smin = lm_block_red<1>(smin, red);
+  cnt = lm_block_red<2>(cnt, red);
+  if (!tid) {
+    double* row = tiles + (size_t)b * lay.row;
+    row[lay.smin + blockIdx.x] = smin;
+    row[lay.cnt + blockIdx.x] = cnt;
+  }
+}
+
+// one block per row: the tiles' values into the row's four stats.  max, min and a sum of whole numbers: exact in any order.
+__global__ __launch_bounds__(RS_BLOCK) void k_limit_stats(LdArgs a, const double* __restrict__ gain, int gain_stride,
+                                                          const double* __restrict__ work, LmLayout lay, double* __restrict__ stats) {
+  __shared__ double red[RS_BLOCK];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const LdRow r = a.r[b];
+  const double* row = work + lay.rows + (size_t)b * lay.row;
+  double emax = 0.0, smin = 1.0, cnt = 0.0;
+  if (r.len > 0) {
+    const int te = (r.len + LM_TILE - 1) / LM_TILE;
+    for (int t = tid; t < te; t += RS_BLOCK) emax = fmax(emax, row[lay.emax + t]);
+    const int t_lo = r.start / LM_TILE, t_hi = (r.start + r.len - 1) / LM_TILE;
+    for (int t = t_lo + tid; t <= t_hi; t += RS_BLOCK) {
+      smin = fmin(smin, row[lay.smin + t]);
+      cnt = cnt + row[lay.cnt + t];
+    }
+  }
+  emax = lm_block_red<0>(emax, red);
+  smin = lm_block_red<1>(smin, red);
+  cnt = lm_block_red<2>(cnt, red);
+  if (tid) return;
+  const double g = gain ? gain[(size_t)b * gain_stride] : 1.0;
+  double* st = stats + 4 * (size_t)b;
+  st[0] = g * emax; st[1] = g; st[2] = smin; st[3] = cnt;
 }
 
 // ---- time-scale change of rows (smi_tempo_rows)
@@ -1809,6 +2016,97 @@ int smi_gain_rows(const float* in_dev, long long in_stride, const int32_t* n_hos
   }
   const int tiles = (int)((out_stride + GN_TILE - 1) / GN_TILE);
   hipLaunchKernelGGL(k_gain_rows, dim3(tiles, B), dim3(RS_BLOCK), 0, (hipStream_t)stream, A, stats_dev, in_dev, in_stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// where the parts of the limiter's scratch lie: the window, then per row r [n_max] and three values a tile
+static LmLayout lm_layout(long long n_max) {
+  const long long tiles = n_max ? (n_max + LM_TILE - 1) / LM_TILE : 1;
+  LmLayout l;
+  l.rows = LM_WIN_PAD;
+  l.emax = (n_max + 7) / 8 * 8;
+  l.smin = l.emax + tiles;
+  l.cnt = l.smin + tiles;
+  l.row = (l.cnt + tiles + 7) / 8 * 8;
+  return l;
+}
+
+extern "C" {
+
+long long smi_limit_work_len(long long n_max, int B) {
+  if (n_max < 0 || n_max > RS_MAX_SAMPLES || B < 1 || B > RS_MAX_ROWS) return -1;
+  const LmLayout l = lm_layout(n_max);
+  return l.rows + l.row * B;
+}
+
+int smi_limit_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                   const double* gain_dev, int gain_stride, double ceiling, const double* taps_host, int n_taps, int phases, int lookahead,
+                   int release, const double* win_host, double* work_dev, long long work_len, float* out_dev, long long out_stride,
+                   double* stats_dev, void* stream) {
+  SMI_REQUIRE(in_dev && n_host && win_host && work_dev && out_dev && stats_dev, "smi_limit_rows: null argument");
+  SMI_REQUIRE(std::isfinite(ceiling) && ceiling > 0.0, "smi_limit_rows: ceiling=%g must be finite and > 0", ceiling);
+  SMI_REQUIRE(phases >= 1 && phases <= LM_MAX_PHASES, "smi_limit_rows: phases=%d outside 1..%d", phases, LM_MAX_PHASES);
+  SMI_REQUIRE(n_taps == 0 || n_taps == 2 * LM_HALO * phases + 1,
+              "smi_limit_rows: n_taps=%d is neither 0 (the sample peak) nor %d = 2 * 10 * phases + 1 for phases=%d", n_taps,
+              2 * LM_HALO * phases + 1, phases);
+  SMI_REQUIRE(n_taps == 0 || taps_host, "smi_limit_rows: null taps_host with n_taps=%d", n_taps);
+  for (int i = 0; i < n_taps; ++i) SMI_REQUIRE(std::isfinite(taps_host[i]), "smi_limit_rows: taps[%d]=%g is not finite", i, taps_host[i]);
+  SMI_REQUIRE(lookahead >= 0 && lookahead <= LM_MAX_A, "smi_limit_rows: lookahead=%d outside 0..%d", lookahead, LM_MAX_A);
+  SMI_REQUIRE(release >= 0 && release <= LM_MAX_R, "smi_limit_rows: release=%d outside 0..%d", release, LM_MAX_R);
+  const int nw = lookahead + release + 1;
+  double wsum = 0.0;
+  for (int i = 0; i < nw; ++i) {
+    SMI_REQUIRE(std::isfinite(win_host[i]) && win_host[i] >= 0.0, "smi_limit_rows: win[%d]=%g must be finite and >= 0", i, win_host[i]);
+    wsum = wsum + win_host[i];
+  }
+  SMI_REQUIRE(std::fabs(wsum - 1.0) <= 1e-12, "smi_limit_rows: win sums to 1%+.3g over its %d weights, not to 1 within 1e-12", wsum - 1.0, nw);
+  SMI_REQUIRE(gain_stride >= 0, "smi_limit_rows: gain_stride=%d is negative", gain_stride);
+  LdArgs A;
+  int n_max = 0, len_max = 0;
+  const int rc = ld_rows_args("smi_limit_rows", n_host, start_host, end_host, B, in_stride, A, n_max, len_max);
+  if (rc) return rc;
+  SMI_REQUIRE(out_stride >= 1 && out_stride >= n_max && out_stride <= RS_MAX_SAMPLES,
+              "smi_limit_rows: out_stride=%lld outside max(1, the longest row %d)..%d", out_stride, n_max, RS_MAX_SAMPLES);
+  if (!(out_dev == in_dev && out_stride == in_stride)) {   // in place, row on row, or apart
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + ((size_t)(B - 1) * in_stride + n_max) * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_limit_rows: out_dev overlaps in_dev (only out_dev == in_dev with equal strides is allowed)");
+  }
+  if (gain_dev) {
+    const double* g1 = gain_dev + (size_t)(B - 1) * gain_stride + 1;
+    SMI_REQUIRE(g1 <= stats_dev || stats_dev + 4 * (size_t)B <= gain_dev, "smi_limit_rows: stats_dev overlaps gain_dev");
+  }
+  const long long need = smi_limit_work_len(n_max, B);
+  SMI_REQUIRE(work_len >= need, "smi_limit_rows: work_len=%lld below %lld (smi_limit_work_len)", work_len, need);
+  const LmLayout lay = lm_layout(n_max);
+  LmTaps tp;
+  for (int i = 0; i < LM_MAX_TAPS; ++i) tp.h[i] = i < n_taps ? taps_host[i] : 0.0;
+  tp.n = n_taps; tp.phases = phases;
+  float c32 = (float)ceiling;   // the largest float32 <= ceiling
+  if ((double)c32 > ceiling) c32 = nextafterf(c32, 0.f);
+  hipStream_t s = (hipStream_t)stream;
+  for (int o = 0; o < nw; o += LM_WIN_ARG) {
+    LmWin w;
+    const int cnt = nw - o < LM_WIN_ARG ? nw - o : LM_WIN_ARG;
+    for (int i = 0; i < LM_WIN_ARG; ++i) w.w[i] = i < cnt ? win_host[o + i] : 0.0;
+    hipLaunchKernelGGL(k_limit_win, dim3(1), dim3(RS_BLOCK), 0, s, w, cnt, work_dev + o);
+    SMI_LAUNCH_CHECK();
+  }
+  const int etiles = len_max ? (len_max + LM_TILE - 1) / LM_TILE : 1;
+  hipLaunchKernelGGL(k_limit_env, dim3(etiles, B), dim3(RS_BLOCK), 0, s, A, tp, gain_dev, gain_stride, ceiling, in_dev, in_stride, work_dev, lay);
+  SMI_LAUNCH_CHECK();
+  const int tiles = (int)((out_stride + LM_TILE - 1) / LM_TILE);
+  const size_t lds = (size_t)(LM_TILE + 2 * (lookahead + release)) * sizeof(double);
+  hipLaunchKernelGGL(k_limit_apply, dim3(tiles, B), dim3(RS_BLOCK), lds, s, A, lookahead, release, gain_dev, gain_stride, c32,
+                     (const double*)work_dev, in_dev, in_stride, (const double*)(work_dev + lay.rows), work_dev + lay.rows, lay, out_dev,
+                     out_stride);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_limit_stats, dim3(B), dim3(RS_BLOCK), 0, s, A, gain_dev, gain_stride, (const double*)work_dev, lay, stats_dev);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

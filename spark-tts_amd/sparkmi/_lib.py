@@ -259,6 +259,9 @@ SYMBOLS = {
     "smi_loud_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_double), _I, _P(C.c_double),
                            C.c_double, C.c_double, _VP, C.c_longlong, _VP, _VP]),
     "smi_gain_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, _VP, C.c_longlong, _VP]),
+    "smi_limit_work_len": (C.c_longlong, [C.c_longlong, _I]),
+    "smi_limit_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, _I, C.c_double, _P(C.c_double), _I, _I,
+                            _I, _I, _P(C.c_double), _VP, C.c_longlong, _VP, C.c_longlong, _VP, _VP]),
     "smi_tempo_layout": (C.c_longlong, [C.c_longlong, _I, _I, _I, _P(C.c_longlong)]),
     "smi_tempo_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int32), _P(C.c_int32), _I, _I,
                             _VP, _VP, C.c_longlong, _VP, C.c_longlong, _P(C.c_int32), _VP]),

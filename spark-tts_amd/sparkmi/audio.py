@@ -16,6 +16,10 @@ the speech bounds of vocoded rows, and the trimmed rows as one waveform with pau
 rows after ITU-R BS.1770 and the gain that brings each to a target under a peak ceiling, measured and applied on the device.
 ``k_weighting`` designs the weighting filter's coefficients for a sample rate with numpy alone.
 
+``DeviceAudio.limit_rows`` (``smi_limit_rows``) is the look-ahead limiter behind them: peaks found on the 4x oversampled signal, a
+sliding minimum and an FIR window, feed-forward, so the device is held to ``tests/limit_ref.py`` bit for bit.  ``limiter_reach`` and
+``limiter_window`` give its look-ahead and release for a sample rate and its smoothing weights.
+
 ``DeviceAudio.tempo_rows`` (``smi_tempo_rows``) changes the speaking rate of rows at unchanged pitch: WSOLA whose similarity
 search is exact integer arithmetic, so the device is held to ``tests/tempo_ref.py`` bit for bit.  ``tempo_ratio``,
 ``tempo_frame`` and ``tempo_window`` give its rational, its frame and radius for a sample rate, and its window.
@@ -118,6 +122,46 @@ def check_loudness(loudness, peak_ceiling, max_gain_db) -> None:
         raise ValueError(f"peak_ceiling must be > 0, not {peak_ceiling!r}")
     if max_gain_db < 0:
         raise ValueError(f"max_gain_db must be >= 0, not {max_gain_db!r}")
+
+
+LIMITER_MODES = ("true", "sample")   # peak detection: on the 4x oversampled signal, or on the samples alone
+LIMITER_PHASES = 4
+LIMITER_MAX_LOOKAHEAD, LIMITER_MAX_RELEASE = 256, 2048   # samples (include/sparkmi.h, smi_limit_rows)
+
+
+def limiter_window(A: int, R: int) -> np.ndarray:
+    """float64 [A + R + 1], non-negative, unit sum: the smoothing weights ``smi_limit_rows`` takes as data -- a Hann shape over
+    A + R + 2 intervals with the end zeros dropped, ``0.5 - 0.5 cos(2 pi (j + 1) / (A + R + 2))``, normalised"""
+    A, R = int(A), int(R)
+    if not 0 <= A <= LIMITER_MAX_LOOKAHEAD or not 0 <= R <= LIMITER_MAX_RELEASE:
+        raise ValueError(f"lookahead must lie in 0..{LIMITER_MAX_LOOKAHEAD} and release in 0..{LIMITER_MAX_RELEASE} samples, not {A}, {R}")
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(1, A + R + 2, dtype=np.float64) / (A + R + 2))
+    return w / np.sum(w)
+
+
+def limiter_reach(sr: int, lookahead_ms: float = 2.5, release_ms: float = 25.0) -> Tuple[int, int]:
+    """(A, R) in samples at ``sr`` Hz, rounded: 40 and 400 at 16 kHz"""
+    sr = int(sr)
+    if sr < 1:
+        raise ValueError(f"sample rate must be positive, not {sr}")
+    for name, v in (("lookahead_ms", lookahead_ms), ("release_ms", release_ms)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be a finite number >= 0, not {v!r}")
+    A, R = int(round(lookahead_ms * sr / 1000.0)), int(round(release_ms * sr / 1000.0))
+    if A > LIMITER_MAX_LOOKAHEAD or R > LIMITER_MAX_RELEASE:
+        raise ValueError(f"at {sr} Hz lookahead_ms={lookahead_ms!r} and release_ms={release_ms!r} are {A} and {R} samples; the limiter "
+                         f"takes at most {LIMITER_MAX_LOOKAHEAD} and {LIMITER_MAX_RELEASE}")
+    return A, R
+
+
+def check_limiter(limiter, peak_ceiling=PEAK_CEILING, lookahead_ms: float = 2.5, release_ms: float = 25.0, sr: int = 16000):
+    """the limiter arguments of the ``SparkTTS`` calls, checked before anything reaches the device; returns (A, R) in samples"""
+    if limiter is not None and (not isinstance(limiter, str) or limiter not in LIMITER_MODES):
+        raise ValueError(f"limiter must be None, \"true\" or \"sample\", not {limiter!r}")
+    if isinstance(peak_ceiling, bool) or not isinstance(peak_ceiling, (int, float, np.integer, np.floating)) or not math.isfinite(peak_ceiling) \
+            or not peak_ceiling > 0:
+        raise ValueError(f"peak_ceiling must be a finite number > 0, not {peak_ceiling!r}")
+    return limiter_reach(sr, lookahead_ms, release_ms)
 
 
 TEMPO_MIN, TEMPO_MAX = 0.5, 2.0
@@ -378,6 +422,53 @@ class DeviceAudio:
                                                 C.c_void_p(stats.data_ptr()), C.c_void_p(out.data_ptr()), out.shape[1], self._stream()),
                         "smi_gain_rows")
         return out
+
+    def limit_rows(self, x, n: Sequence[int], gains=None, spans: Optional[Sequence[Tuple[int, int]]] = None, ceiling: float = PEAK_CEILING,
+                   mode: str = "true", lookahead: int = 40, release: int = 400, out=None):
+        """The look-ahead limiter (include/sparkmi.h, smi_limit_rows): row b's span times its gain and a smoothed reduction that
+        keeps every sample at or under ``ceiling``, the rest of the row copied, zeros from ``n[b]`` to the stride.  ``gains``:
+        None: 1; the [B][4] float64 stats of ``loudness_rows`` (their gain is applied here, so ``gain_rows`` is not needed); or
+        a [B] float64 tensor -- on the device, read there.  ``mode``: "true": peaks of the 4x oversampled signal
+        (``resample_taps(4, 1)``); "sample": of the samples alone.  ``lookahead`` / ``release``: samples (``limiter_reach``); the
+        window is ``limiter_window``.  ``out``: as in ``gain_rows`` (``x`` itself: in place).  Returns (out, stats [B][4]
+        float64 on the device: the true peak going in, the gain, the smallest factor, the samples reduced).  A launch or more for
+        the window, then three; nothing waits and nothing is copied.  The scratch is the object's own and only grows."""
+        import torch
+        B = self._rows(x, n, "limit_rows")
+        st, en = self._spans(spans, B)
+        if mode not in LIMITER_MODES:
+            raise ValueError(f"mode must be \"true\" or \"sample\", not {mode!r}")
+        A, R = int(lookahead), int(release)
+        gp, gs = C.c_void_p(0), 0
+        if gains is not None:
+            ok = gains.dtype == torch.float64 and gains.is_contiguous() and gains.is_cuda and gains.shape[0] >= B
+            if ok and gains.dim() == 2 and gains.shape[1] == 4:
+                gp, gs = C.c_void_p(gains.data_ptr() + 16), 4
+            elif ok and gains.dim() == 1:
+                gp, gs = C.c_void_p(gains.data_ptr()), 1
+            else:
+                raise ValueError("limit_rows: gains is None, the [B][4] float64 stats of loudness_rows or a [B] float64 tensor, on the device")
+        taps = np.ascontiguousarray(resample_taps(LIMITER_PHASES, 1), dtype=np.float64) if mode == "true" else None
+        wins = self.__dict__.setdefault("_limit_windows", {})
+        if (A, R) not in wins:
+            wins[(A, R)] = np.ascontiguousarray(limiter_window(A, R), dtype=np.float64)
+        win = wins[(A, R)]
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.dim() != 2 or out.shape[0] != B or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("limit_rows: out must be a contiguous [B][out_stride] float32 tensor on the device")
+        need = self._lib.smi_limit_work_len(max(0, max(int(v) for v in n)) if B else 0, max(1, min(B, MAX_ROWS)))
+        work = getattr(self, "_limit_work", None)
+        if work is None or work.numel() < need:
+            work = self._limit_work = torch.empty((max(1, int(need)),), dtype=torch.float64, device=self.device)
+        stats = torch.empty((max(1, B), 4), dtype=torch.float64, device=self.device)
+        self._lib.check(self._lib.smi_limit_rows(C.c_void_p(x.data_ptr()), x.shape[1], (C.c_int32 * B)(*[int(v) for v in n]), st, en, B, gp, gs,
+                                                 float(ceiling), None if taps is None else taps.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 0 if taps is None else taps.size, LIMITER_PHASES, A, R,
+                                                 win.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(work.data_ptr()), work.numel(),
+                                                 C.c_void_p(out.data_ptr()), out.shape[1], C.c_void_p(stats.data_ptr()), self._stream()),
+                        "smi_limit_rows")
+        return out, stats
 
     def tempo_rows(self, x, n: Sequence[int], tempos: Sequence, spans: Optional[Sequence[Tuple[int, int]]] = None, out=None,
                    sr: int = 16000, frame: Optional[Tuple[int, int]] = None):

@@ -13,7 +13,8 @@ calls take ``joined=True`` for contiguous, playable pieces at any output rate (t
 waveforms trimmed and joined on the device); ``loudness`` / ``peak_ceiling`` / ``max_gain_db`` on every call that returns whole
 utterances (the output at a programme loudness after BS.1770, measured and scaled on the device); ``tempo`` on the same calls
 (a pitch-preserving change of the speaking rate, 0.5 .. 2.0, on the device before the loudness stage) and, with
-``joined=True``, on the two streaming calls (the same arithmetic with its state carried across the chunks on the device).
+``joined=True``, on the two streaming calls (the same arithmetic with its state carried across the chunks on the device);
+``limiter`` on the calls that return whole utterances (a look-ahead true-peak limiter behind the loudness stage, on the device).
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import PEAK_CEILING, check_loudness, tempo_len, tempo_ratio
+from .audio import LIMITER_MODES, PEAK_CEILING, check_limiter, check_loudness, tempo_len, tempo_ratio
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
 from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, NGRAM_KEY, PENALTY_KEYS, SAMPLING_KEYS, SEQ_KEYS, SparkLLM,
@@ -56,6 +57,10 @@ class StreamLoudnessRefused(ValueError, TypeError):
 
 
 LIMITED = (None, "max_gain", "ceiling")   # what bounded a row's gain (include/sparkmi.h, smi_loud_rows: limit 0 / 1 / 2)
+# request key: the request's own limiter ("true", "sample" or None); it overrides the call's ``limiter``
+LIMITER_KEY = "limiter"
+# the ceiling the loudness stage is given where the limiter holds ``peak_ceiling`` behind it: large and finite, it cannot bind
+NO_CEILING = 1e30
 # request key: the request's own tempo (0.5 .. 2.0; > 1: faster); it overrides the call's ``tempo``
 TEMPO_KEY = "tempo"
 
@@ -272,10 +277,12 @@ class SparkTTS:
                   num_return_sequences: int = 1, allowed_token_ids: Optional[Sequence[int]] = None,
                   speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0, output_sample_rate: Optional[int] = None,
                   loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
-                  tempo: Optional[float] = None):
+                  tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
+                  limiter_release_ms: float = 25.0):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate`` (or at ``output_sample_rate``,
         as in ``inference_batch``; ``loudness`` / ``peak_ceiling`` / ``max_gain_db``: the output's programme loudness, as
-        there; ``tempo``: the speaking rate, as there).  The penalties
+        there; ``tempo``: the speaking rate, as there; ``limiter`` / ``limiter_lookahead_ms`` / ``limiter_release_ms``: the
+        look-ahead limiter, as there).  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
         penalty.  ``return_log_probs=True``: (waveform, info) with info = {``token_ids``: the generated ids,
@@ -303,7 +310,8 @@ class SparkTTS:
                                     temperature=temperature, top_k=top_k, top_p=top_p, do_sample=do_sample,
                                     max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs,
                                     output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
-                                    max_gain_db=max_gain_db, tempo=tempo)[0]
+                                    max_gain_db=max_gain_db, tempo=tempo, limiter=limiter,
+                                    limiter_lookahead_ms=limiter_lookahead_ms, limiter_release_ms=limiter_release_ms)[0]
 
     def _output_ratio(self, output_sample_rate: Optional[int]) -> Optional[Tuple[int, int]]:
         """(up, down) from the model's rate to ``output_sample_rate``; None when the vocoder's rows go out as they are"""
@@ -484,6 +492,86 @@ class SparkTTS:
         host = stats.cpu().tolist()
         return [None if t is None else dict(loudness=row[0], gain=row[2], limited=LIMITED[int(row[3])]) for t, row in zip(targets, host)]
 
+    def _limiter_modes(self, requests: Sequence[dict], limiter, peak_ceiling, lookahead_ms, release_ms, first: int = 0):
+        """(every request's limiter mode -- its own ``limiter`` key, else the call's; None: no limiter --, (A, R): the look-ahead
+        and the release in samples at the model's rate), all checked"""
+        reach = check_limiter(limiter, peak_ceiling, lookahead_ms, release_ms, self.sample_rate)
+        out = []
+        for i, r in enumerate(requests):
+            m = r.get(LIMITER_KEY, limiter)
+            try:
+                check_limiter(m, peak_ceiling, lookahead_ms, release_ms, self.sample_rate)
+            except ValueError as e:
+                raise ValueError(f"request {first + i}: {e}") from None
+            out.append(m)
+        return out, reach
+
+    @staticmethod
+    def _no_stream_limiter(limiter, who: str) -> None:
+        if limiter is not None:
+            raise ValueError(f"{who}: limiter is not supported on chunked streams (the look-ahead and the release reach across "
+                             "chunk edges, so a streaming limiter needs A + R samples of carried state); use inference / "
+                             "inference_batch / serve / inference_long / inference_long_stream")
+
+    def _level_rows(self, wav, n: Sequence[int], targets: Sequence[Optional[float]], modes: Sequence[Optional[str]], peak_ceiling: float,
+                    max_gain_db: float, reach: Tuple[int, int], spans=None):
+        """The loudness stage and the limiter for rows, in place and on the device: (the loudness stats [B][4] or None, the
+        limiter's stats [B][4] or None).  Without a limiter this is ``_normalize_rows``, launch for launch.  Rows with a
+        limiter are measured with a ceiling that cannot bind and go through ``audio.DeviceAudio.limit_rows``, which applies the
+        loudness gain itself and holds ``peak_ceiling``; ``gain_rows`` is not launched for them.  Rows of different modes in one
+        call go mode by mode, the other rows as empty spans, which every stage copies."""
+        if all(m is None for m in modes):
+            return self._normalize_rows(wav, n, targets, peak_ceiling, max_gain_db, spans=spans), None
+        audio = self._device_audio()
+        B = len(n)
+        full = [(0, int(v)) for v in n] if spans is None else [(int(a), int(b)) for a, b in spans]
+        stats = lstats = None
+        for mode in (None,) + LIMITER_MODES:
+            rows = [b for b in range(B) if modes[b] == mode]
+            if not rows:
+                continue
+            sp = spans if len(rows) == B else [full[b] if modes[b] == mode else (0, 0) for b in range(B)]
+            tg = [targets[b] if modes[b] == mode else None for b in range(B)]
+            st = None
+            if any(t is not None for t in tg):
+                st = audio.loudness_rows(wav, n, spans=sp, targets=tg, max_gain_db=max_gain_db,
+                                         ceiling=peak_ceiling if mode is None else NO_CEILING, sr=self.sample_rate)
+            if mode is None:
+                if st is not None:
+                    audio.gain_rows(wav, n, st, spans=sp, out=wav)
+                ls = None
+            else:
+                _, ls = audio.limit_rows(wav, n, gains=st, spans=sp, ceiling=peak_ceiling, mode=mode, lookahead=reach[0],
+                                         release=reach[1], out=wav)
+            if len(rows) == B:
+                stats, lstats = st, ls
+            else:   # (a few words per row, merged on the device so that one copy brings them all)
+                idx = torch.tensor(rows, dtype=torch.long, device=wav.device)
+                if st is not None:
+                    stats = torch.full((B, 4), math.nan, dtype=torch.float64, device=wav.device) if stats is None else stats
+                    stats[idx] = st[idx]
+                if ls is not None:
+                    lstats = torch.full((B, 4), math.nan, dtype=torch.float64, device=wav.device) if lstats is None else lstats
+                    lstats[idx] = ls[idx]
+        return stats, lstats
+
+    @staticmethod
+    def _level_info(stats, lstats, targets: Sequence[Optional[float]], modes: Sequence[Optional[str]]):
+        """one small copy behind everything enqueued: (``_loudness_info``'s entries, per row with a limiter {``true_peak``: of
+        the row times its gain, going in (the sample peak in "sample" mode), ``reduction_db``: -20 log10 of the smallest
+        factor, ``limited_samples``}, None for a row without one)"""
+        if lstats is None:
+            return SparkTTS._loudness_info(stats, targets), [None] * len(targets)
+        host = (lstats if stats is None else torch.cat([stats, lstats], dim=1)).cpu().tolist()
+        loud = [None if t is None or stats is None else dict(loudness=row[0], gain=row[2], limited=LIMITED[int(row[3])])
+                for t, row in zip(targets, host)]
+        lim = []
+        for m, row in zip(modes, host):
+            peak, _, smin, count = row[-4:]
+            lim.append(None if m is None else dict(true_peak=peak, reduction_db=0.0 if smin >= 1.0 else (
+                math.inf if smin <= 0.0 else -20.0 * math.log10(smin)), limited_samples=int(count)))
+        return loud, lim
+
     @staticmethod
     def _tempo_ratios(requests: Sequence[dict], tempo, first: int = 0) -> List[Optional[Tuple[int, int]]]:
         """every request's tempo as (p, q) (its own ``tempo`` key, else the call's), all checked; None for a request without
@@ -515,7 +603,8 @@ class SparkTTS:
                         seed: Optional[int] = None, return_log_probs: bool = False, prompt_encode: str = "streams",
                         prompt_audio: str = "host", output_sample_rate: Optional[int] = None,
                         loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
-                        tempo: Optional[float] = None) -> List:
+                        tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
+                        limiter_release_ms: float = 25.0) -> List:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
@@ -550,7 +639,16 @@ class SparkTTS:
         ``tempo`` key, which overrides it: the speaking rate of the vocoded row is changed at unchanged pitch (WSOLA;
         include/sparkmi.h, smi_tempo_rows) on the device, after vocoding and before the loudness stage, which measures the
         final signal; a row of n samples then has ``audio.tempo_len(n, p, q)``.  It works for cloned voices, which the
-        ``speed`` label of voice creation does not reach, and it is exact where the label is a hint."""
+        ``speed`` label of voice creation does not reach, and it is exact where the label is a hint.
+        ``limiter`` (None: nothing is launched and no bit changes; "true"; "sample") or a request's own ``limiter`` key, which
+        overrides it: a look-ahead limiter (include/sparkmi.h, smi_limit_rows) on the device, behind the
+        loudness stage and before the resampling, keeps every sample of the row at or under ``peak_ceiling`` by reducing the
+        gain around the overs only -- from ``limiter_lookahead_ms`` (2.5) before them to ``limiter_release_ms`` (25) behind --;
+        "true" finds the overs on the 4x oversampled signal, "sample" on the samples.  With ``loudness`` the row then reaches
+        its target (or ``max_gain_db``): the loudness stage measures with a ceiling that cannot bind, the limiter applies its
+        gain, and ``limited`` is None or "max_gain".  Without ``loudness`` the limiter alone bounds the vocoder's output.
+        ``self.last_limiter`` holds, per request (per take where it has takes), None or {``true_peak``: going in,
+        ``reduction_db``: the deepest reduction, ``limited_samples``}, from the one small copy that brings ``last_loudness``."""
         targets = self._loudness_targets(requests, loudness, peak_ceiling, max_gain_db)
         ratios = self._tempo_ratios(requests, tempo)
         if prompt_encode not in ("streams", "rows"):
@@ -563,6 +661,7 @@ class SparkTTS:
         if len(requests) > self._max_batch:
             raise ValueError(f"{len(requests)} requests > max_batch={self._max_batch}")
         n_takes = _take_counts(requests, self._max_batch)
+        modes, reach = self._limiter_modes(requests, limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         prompts, globals_ = [], []
         # voice-clone requests that come with prompt FILES: all their prompt encodes run together (parallel HIP streams, or one ragged call)
         need = [i for i, r in enumerate(requests)
@@ -646,25 +745,29 @@ class SparkTTS:
         wav = wav.squeeze(1)
         row_targets = [targets[b] for b in owner]
         wav, n_wav = self._tempo_rows(wav, n_wav, [ratios[b] for b in owner])
-        stats = None
-        if any(t is not None for t in row_targets):
+        row_modes = [modes[b] for b in owner]
+        stats = lstats = None
+        if any(t is not None for t in row_targets) or any(m is not None for m in row_modes):
             wav = wav.contiguous()
-            stats = self._normalize_rows(wav, n_wav, row_targets, peak_ceiling, max_gain_db)
+            stats, lstats = self._level_rows(wav, n_wav, row_targets, row_modes, peak_ceiling, max_gain_db, reach)
         if out_ratio is not None:   # rows at the caller's rate, still on the device
             wav, n_wav = self._device_audio().resample_rows(wav, n_wav, [out_ratio[0]] * len(lens), [out_ratio[1]] * len(lens))
         wav = wav.cpu().numpy()
-        loud = self._loudness_info(stats, row_targets)
+        loud, lim = self._level_info(stats, lstats, row_targets, row_modes)
         out = [wav[b, : n_wav[b]].copy() for b in range(len(sems))]
         out = [(w, infos[b]) if infos[b] is not None else w for b, w in enumerate(out)]
         if n_takes is None:
-            self.last_loudness = loud
+            self.last_loudness, self.last_limiter = loud, lim
             return out
         res: List = [[] for _ in requests]
         per: List = [[] for _ in requests]
+        perl: List = [[] for _ in requests]
         for i, b in enumerate(owner):
             res[b].append(out[i])
             per[b].append(loud[i])
+            perl[b].append(lim[i])
         self.last_loudness = [per[b] if FORK_KEY in r else per[b][0] for b, r in enumerate(requests)]
+        self.last_limiter = [perl[b] if FORK_KEY in r else perl[b][0] for b, r in enumerate(requests)]
         return [res[b] if FORK_KEY in r else res[b][0] for b, r in enumerate(requests)]
 
     @torch.no_grad()
@@ -678,7 +781,7 @@ class SparkTTS:
                          decode_stride: int = 10, output_sample_rate: Optional[int] = None,
                          joined: bool = False, tempo: Optional[float] = None, loudness: Optional[float] = None,
                          peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
-                         max_slew_db: float = 1.0) -> Iterator[np.ndarray]:
+                         max_slew_db: float = 1.0, limiter: Optional[str] = None) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
@@ -713,7 +816,10 @@ class SparkTTS:
         ``DeviceAudio.tempo_rows`` of the concatenated ``joined=True`` pieces without tempo (and ``resample_rows`` of that), so
         it does not depend on the chunking; a piece holds back up to N + D + H samples of its input (63 ms at 16 kHz) for the
         frames that are not final yet, and the last piece brings them.  With
-        ``joined=False`` a given ``tempo`` is refused (ValueError): overlapping chunks have no edges to carry state across."""
+        ``joined=False`` a given ``tempo`` is refused (ValueError): overlapping chunks have no edges to carry state across.
+
+        ``limiter`` is refused (ValueError), joined or not: the limiter of ``inference_batch`` has no streaming form yet."""
+        self._no_stream_limiter(limiter, "inference_stream")
         if not joined:
             self._no_stream_tempo(tempo, "inference_stream")
             self._no_stream_loudness(loudness, "inference_stream")
@@ -831,7 +937,8 @@ class SparkTTS:
     def serve(self, requests, temperature: float = 0.8, top_k: float = 50, top_p: float = 0.95, *, do_sample: bool = True,
               max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False,
               loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
-              tempo: Optional[float] = None):
+              tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
+              limiter_release_ms: float = 25.0):
         """In-flight batching front end (the functional analogue of the reference's Triton deployment,
         runtime/triton_trtllm/run.sh:50-65): ``requests`` is an iterable of the dicts ``inference_batch`` takes;
         yields ``(index, waveform)`` as each utterance finishes.  Up to ``max_batch`` utterances are live; a new
@@ -846,8 +953,13 @@ class SparkTTS:
         ``loudness`` / ``peak_ceiling`` / ``max_gain_db`` and a request's own ``loudness`` key as in ``inference_batch``: each
         waveform is brought to its target on the device before its copy; ``self.last_loudness[index]`` holds what was measured
         (a list for a request with takes) once the request has been yielded.  ``tempo`` and a request's own ``tempo`` key as in
-        ``inference_batch``: the waveform's speaking rate is changed on the device, before the loudness stage."""
+        ``inference_batch``: the waveform's speaking rate is changed on the device, before the loudness stage.  ``limiter`` /
+        ``limiter_lookahead_ms`` / ``limiter_release_ms`` and a request's own ``limiter`` key as in ``inference_batch``: the
+        look-ahead limiter behind the loudness stage; ``self.last_limiter[index]`` holds its entry (a list for a request with
+        takes) once the request has been yielded."""
         forks: Dict[int, int] = {}   # request index -> takes, for the requests that carry num_return_sequences
+        lims: Dict[int, Optional[str]] = {}   # request index -> limiter mode
+        self.last_limiter = {}
         goals: Dict[int, Optional[float]] = {}   # request index -> loudness target
         rates: Dict[int, Optional[Tuple[int, int]]] = {}   # request index -> tempo as (p, q)
         check_loudness(loudness, peak_ceiling, max_gain_db)
@@ -861,11 +973,13 @@ class SparkTTS:
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 goals[i] = self._loudness_targets([r], loudness, peak_ceiling, max_gain_db)[0]
                 rates[i] = self._tempo_ratios([r], tempo, i)[0]
+                lims[i] = self._limiter_modes([r], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms, i)[0][0]
                 yield r
 
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
             for _ in checked(requests):
                 pass
+        reach = self._limiter_modes([], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)[1]
         hop = self.audio_tokenizer.model.hop
         globals_: Dict[int, Optional[torch.Tensor]] = {}
         self.model.set_sampling(do_sample, temperature, int(top_k), float(top_p), seed)
@@ -899,12 +1013,15 @@ class SparkTTS:
 
         def finished(i, wav, lens, takes):   # the vocoded rows of request i at its tempo and loudness target, still on the device
             wav, n = self._tempo_rows(wav, [f * hop for f in lens], [rates[i]] * len(lens))
-            if goals[i] is None:
+            if goals[i] is None and lims[i] is None:
                 return wav, n
             wav = wav.contiguous()
-            stats = self._normalize_rows(wav, n, [goals[i]] * len(lens), peak_ceiling, max_gain_db)
-            got = self._loudness_info(stats, [goals[i]] * len(lens))
-            self.last_loudness[i] = got if takes else got[0]
+            stats, lstats = self._level_rows(wav, n, [goals[i]] * len(lens), [lims[i]] * len(lens), peak_ceiling, max_gain_db, reach)
+            got, lim = self._level_info(stats, lstats, [goals[i]] * len(lens), [lims[i]] * len(lens))
+            if goals[i] is not None:
+                self.last_loudness[i] = got if takes else got[0]
+            if lims[i] is not None:
+                self.last_limiter[i] = lim if takes else lim[0]
             return wav, n
 
         for i, toks in self.model.serve(llm_requests(), max_live=self._max_batch, decode_stride=decode_stride,
@@ -932,7 +1049,7 @@ class SparkTTS:
                      max_open: Optional[int] = None, max_ahead: Optional[float] = None, resume_ahead: Optional[float] = None,
                      clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None, joined: bool = False,
                      tempo: Optional[float] = None, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
-                     max_gain_db: float = 20.0, max_slew_db: float = 1.0):
+                     max_gain_db: float = 20.0, max_slew_db: float = 1.0, limiter: Optional[str] = None):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -997,7 +1114,11 @@ class SparkTTS:
         request like the joiner's, and a parked request's tempo stream stays open.  The ``Pacer`` then counts the seconds a
         listener receives: the scaled piece's length at the model's rate.  Whether a call has the stages is settled when it
         begins, from ``tempo`` and, where ``requests`` is a list, its requests; a request that brings a tempo of its own from
-        an iterator into a call without them is refused (ValueError): pass a list, or a ``tempo`` for the call."""
+        an iterator into a call without them is refused (ValueError): pass a list, or a ``tempo`` for the call.
+
+        ``limiter`` and a request's own ``limiter`` key are refused (ValueError), joined or not: the limiter of
+        ``inference_batch`` has no streaming form yet."""
+        self._no_stream_limiter(limiter, "serve_stream")
         if not joined:
             self._no_stream_tempo(tempo, "serve_stream")
             self._no_stream_loudness(loudness, "serve_stream")
@@ -1014,6 +1135,8 @@ class SparkTTS:
                     if k in r:
                         raise ValueError(f"request {i}: {k} is not supported by serve_stream" + (
                             " with overlapping chunks; pass joined=True" if k in (TEMPO_KEY, LOUDNESS_KEY) else ""))
+                if r.get(LIMITER_KEY) is not None:
+                    self._no_stream_limiter(r[LIMITER_KEY], f"request {i}: serve_stream")
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 rates[i] = self._tempo_ratios([r], tempo, i)[0] or (1, 1)
                 try:
@@ -1218,14 +1341,18 @@ class SparkTTS:
     # ------------------------------------------------------------------ long text: sentences as rows, trimmed and joined on the device
     def _long_pieces(self, text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
                      max_new_tokens, seed, prompt_tokens, keys: dict, max_width, min_width, pause, trim, trim_threshold, fade, eager: bool,
-                     info: dict, loudness=None, peak_ceiling=PEAK_CEILING, max_gain_db=20.0, tempo=None):
+                     info: dict, loudness=None, peak_ceiling=PEAK_CEILING, max_gain_db=20.0, tempo=None, limiter=None,
+                     limiter_lookahead_ms=2.5, limiter_release_ms=25.0):
         """The engine of ``inference_long`` and ``inference_long_stream``: yields (first sentence, joined [total] float32 on the
         device, [(offset in it, gap, length) per sentence]) for runs of consecutive sentences in text order -- with ``eager``
         as soon as the next sentence due and those behind it are done, else in runs of ``max_batch`` once all are done.  Fills
         ``info``.  With ``tempo``, every sentence's trimmed piece is time-scaled on its own into a row of its own; with
-        ``loudness``, every piece (scaled or not) is brought to that programme loudness in place before the assembly.
+        ``loudness``, every piece (scaled or not) is brought to that programme loudness in place before the assembly; with
+        ``limiter``, every piece goes through the look-ahead limiter on its own span there as well (``_level_rows``).
         Everything is checked before anything reaches the device."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
+        mode, reach = self._limiter_modes([{}], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
+        mode = mode[0]
         rate = self._tempo_ratios([{}], tempo)[0]
         from .longform import control_prefix, control_prompt_ids, ready_run, sentence_seeds, split_text, trim_params
         sentences = split_text(text, max_width, min_width)
@@ -1255,6 +1382,8 @@ class SparkTTS:
         info.update(sentences=sentences, token_ids=[None] * n_sent, bounds=[None] * n_sent, offsets=[None] * n_sent, truncated=[], silent=[])
         if loudness is not None:
             info.update(loudness=[None] * n_sent, gain=[None] * n_sent, limited=[None] * n_sent)
+        if mode is not None:
+            info.update(limiter=[None] * n_sent)
         if rate is not None:
             info.update(tempo_lengths=[None] * n_sent)
         audio = self._device_audio()
@@ -1289,15 +1418,20 @@ class SparkTTS:
                 for k, v in zip(ks, n):
                     info["tempo_lengths"][k] = v
             offs, total = audio.concat_layout(bounds, gaps)
-            stats = None
-            if loudness is not None:   # each piece to the target on its own trimmed span, in place, before the assembly
-                stats = self._normalize_rows(wav, n, [float(loudness)] * len(ks), peak_ceiling, max_gain_db, spans=bounds)
+            stats = lstats = None
+            goal = None if loudness is None else float(loudness)
+            if goal is not None or mode is not None:   # each piece on its own trimmed span, in place, before the assembly
+                stats, lstats = self._level_rows(wav, n, [goal] * len(ks), [mode] * len(ks), peak_ceiling, max_gain_db, reach, spans=bounds)
             out = None
             if total:
                 out, _ = audio.concat_rows(wav, bounds, gaps, fade_n, n=n)
-            if stats is not None:      # (one small copy, like the bounds', behind everything that was enqueued)
-                for k, d in zip(ks, self._loudness_info(stats, [loudness] * len(ks))):
-                    info["loudness"][k], info["gain"][k], info["limited"][k] = d["loudness"], d["gain"], d["limited"]
+            if stats is not None or lstats is not None:      # (one small copy, like the bounds', behind everything that was enqueued)
+                loud, lim = self._level_info(stats, lstats, [loudness] * len(ks), [mode] * len(ks))
+                for k, d, e in zip(ks, loud, lim):
+                    if d is not None:
+                        info["loudness"][k], info["gain"][k], info["limited"][k] = d["loudness"], d["gain"], d["limited"]
+                    if e is not None:
+                        info["limiter"][k] = e
             for k, (a, b), o, g in zip(ks, cut, offs, gaps):
                 info["bounds"][k], info["offsets"][k] = (a, b), state["total"] + o
                 if b == a:
@@ -1354,7 +1488,8 @@ class SparkTTS:
                        max_width: int = 300, min_width: int = 20, pause: float = 0.25, trim: bool = True,
                        trim_threshold: float = 0.01, fade: float = 0.005, output_sample_rate: Optional[int] = None,
                        return_info: bool = False, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
-                       max_gain_db: float = 20.0, tempo: Optional[float] = None):
+                       max_gain_db: float = 20.0, tempo: Optional[float] = None, limiter: Optional[str] = None,
+                       limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0):
         """A text of any length -> one float32 waveform: the text is cut into sentences (``longform.split_text``: ``max_width``,
         ``min_width``), the sentences are generated with the same voice as the requests of one in-flight session (up to
         ``max_batch`` live; ``max_new_tokens`` is per sentence), vocoded in ragged calls, cut at their speech bounds
@@ -1387,16 +1522,25 @@ class SparkTTS:
         (include/sparkmi.h, smi_tempo_rows) after the trim and before the loudness stage and the assembly.  ``pause`` and
         ``fade`` stay seconds of the joined waveform -- the silences are not scaled --, ``info["bounds"]`` stays in samples of
         the untrimmed row, ``info["tempo_lengths"]`` holds every scaled piece's length and ``info["offsets"]`` places the scaled
-        pieces in the joined waveform."""
+        pieces in the joined waveform.
+
+        ``limiter`` (None: no extra launch, no bit changes; "true"; "sample"), ``limiter_lookahead_ms``, ``limiter_release_ms``
+        as in ``inference_batch``: every piece goes through the look-ahead limiter (include/sparkmi.h, smi_limit_rows) on its
+        own trimmed span, behind the loudness stage and before the assembly, so one click no longer holds a whole sentence
+        under its target: with ``loudness`` a piece reaches the target (or ``max_gain_db``) and ``limited`` is None or
+        "max_gain".  Every sample of every piece is at or under ``peak_ceiling``; ``info["limiter"]`` holds {``true_peak``,
+        ``reduction_db``, ``limited_samples``} per sentence."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
         self._tempo_ratios([], tempo)
+        self._limiter_modes([], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         out_ratio = self._output_ratio(output_sample_rate)
         keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
                                min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
         info: dict = {}
         parts = [out for _, out, _ in self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p,
                                                         do_sample, max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim,
-                                                        trim_threshold, fade, False, info, loudness, peak_ceiling, max_gain_db, tempo)
+                                                        trim_threshold, fade, False, info, loudness, peak_ceiling, max_gain_db, tempo,
+                                                        limiter, limiter_lookahead_ms, limiter_release_ms)
                  if out is not None]
         if not parts:
             wav = np.zeros(0, dtype=np.float32)
@@ -1421,7 +1565,8 @@ class SparkTTS:
                               trim_threshold: float = 0.01, fade: float = 0.005,
                               output_sample_rate: Optional[int] = None, loudness: Optional[float] = None,
                               peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
-                              tempo: Optional[float] = None) -> Iterator[np.ndarray]:
+                              tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
+                              limiter_release_ms: float = 25.0) -> Iterator[np.ndarray]:
         """``inference_long`` piece by piece: yields contiguous float32 pieces in text order, sentence k's pause + trimmed and faded
         piece as soon as k and every sentence before it are done (an empty piece is not yielded).  At the model's rate the
         pieces' concatenation is ``inference_long``'s waveform bit for bit: a piece's bits are its own (include/sparkmi.h,
@@ -1430,15 +1575,18 @@ class SparkTTS:
         piece is the resampler's flush) is bit for bit ``inference_long(..., output_sample_rate=...)``.  ``loudness`` /
         ``peak_ceiling`` / ``max_gain_db`` as in ``inference_long``: a sentence's loudness is measured over its own piece, so
         the pieces stay bit for bit those of ``inference_long``.  ``tempo`` as in ``inference_long``: a sentence's piece is
-        scaled whole and on its own before it leaves, so no state crosses the pieces and the same holds."""
+        scaled whole and on its own before it leaves, so no state crosses the pieces and the same holds.  ``limiter`` /
+        ``limiter_lookahead_ms`` / ``limiter_release_ms`` as in ``inference_long``: a piece is limited whole and on its own
+        span -- this is the batch limiter, not a streaming one --, so the same holds again."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
+        self._limiter_modes([], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         rate = self._tempo_ratios([{}], tempo)[0] or (1, 1)
         out_ratio = self._output_ratio(output_sample_rate)
         keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
                                min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
         pieces = self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
                                    max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim, trim_threshold, fade, True, {},
-                                   loudness, peak_ceiling, max_gain_db, tempo)
+                                   loudness, peak_ceiling, max_gain_db, tempo, limiter, limiter_lookahead_ms, limiter_release_ms)
         joiner = None
         for _, out, spans in pieces:
             if out is None:
