@@ -1074,6 +1074,69 @@ int smi_louds_push_rows(smi_louds* h, const float* in_dev, long long stride, con
  * max(0, floor(n_before / hop) - 3) knots).  -1 for a bad argument. */
 long long smi_louds_piece_len(int block, long long n_before, long long len, int last, long long* n_after, long long* knots_after);
 
+/* ------------------------------------------------------------------------------------------
+ * Limiter of joined streams: the section "Output limiter" above with state carried from push to push, so that a stream whose
+ * input arrives in chunks leaves in pieces before it has ended.  No sample is defined here: the concatenation of a stream's
+ * pieces is smi_limit_rows of its whole input x[0 .. L) as one span, with a null gain_dev (g = 1) and the stream's mode,
+ * ceiling, A = lookahead, R = release, window and taps; after the last push the four stats are that call's stats.  All of it
+ * bit for bit.  The limiter is feed-forward, so what is new is only the rule for when a sample is final, and the state.
+ *
+ * When a sample is final.  W = A + R.  out[i] reads s[i] and x[i]; s[i] reads m[i - A .. i + R] and r[i]; m[j] reads
+ * r[j - R .. j + A]; r[j] reads e[j]; and e[j] reads x[j - 9 .. j + 10] (the taps d = -10 .. 9 of every phase; the sample-peak
+ * mode reads x[j] alone).  So out[i] reads x[i - W - 9 .. i + W + 10] and nothing else.  With n samples so far, every i with
+ * i + W + 10 <= n - 1 is final: nothing it reads lies at or beyond n, so nothing it reads can change, and none of it is the
+ * zero or the r = 1 that the batch form reads beyond L -- those can never stand in for input that is still to come.
+ *
+ * Emission (smi_limits_piece_len, host integer arithmetic).  After a push that is not the last a stream has emitted
+ * E(n) = max(0, n - (A + R + 10)) samples, after the last push L, the remaining samples formed as the batch forms them, with
+ * zeros and r = 1 read beyond L.  A push emits the difference, which may be 0.  One rule serves both modes (the sample-peak
+ * mode could leave 10 samples earlier; it does not), so a piece's length depends on n, A and R alone.  A piece leaves
+ * A + R + 10 samples behind its input -- 450 samples, 28 ms, at the default reach at 16 kHz -- and never waits for another chunk.
+ *
+ * State.  On the host: n and the stream's mode and ceiling.  On the device, per stream and never copied back: the input from
+ * max(0, E(n) - (A + R) - 9) to n -- the first sample that output E(n), the next to leave, reads -- which is at most
+ * 2 (A + R) + 19 samples (919 at the default reach, 4627 at the largest); and the running stats: max e, min s and the count of
+ * s < 1 over the samples emitted so far -- a max, a min and a sum of whole numbers, exact in any order.  r is not carried: a
+ * push computes it anew over [max(0, E(n_before) - (A + R)), E(n_after) + A + R) from the held input followed by the chunk, by
+ * the same expression, so it has the same bits.  State lives in two sets that a stream uses in turn (a push reads one and
+ * writes the other), so one launch sequence serves a call whatever B.
+ *
+ * Stats, [4] float64 a row: (max e, 1, min s, the count of s < 1) over the samples [0, E) the stream has emitted after this
+ * push: a function of n and the stream alone, not of how it was pushed.  Nothing emitted: (0, 1, 1, 0).
+ *
+ * Three launches a call, whatever B, no atomics; the window and the taps went to the device at smi_limits_create.  k_limits_env,
+ * grid (tiles of 1024 samples of the range of r above, rows): k_limit_env over the virtual sequence of held input followed by
+ * the chunk.  k_limits_apply, grid (tiles of 1024 samples of the pieces up to out_stride, rows): k_limit_apply's minimum by
+ * doubling, smoothing sums, product and clamp; tile 0 of a row also writes the next held input.  k_limits_stats, one block a
+ * row.  The three call the device functions that the batch kernels call.
+ *
+ * Guarantees: the concatenation of a stream's pieces and its final stats are, bit for bit, smi_limit_rows of the whole stream,
+ * and |out| <= ceiling exactly -- whatever the granularity of the pushes, empty ones included, the stream's slot, its row in a
+ * call, the other rows, the strides and what lies outside len.  A stream is refused before n passes 2^28.  All pushes of a
+ * handle must go to one HIP stream (or be ordered by the caller). */
+typedef struct smi_limits smi_limits;
+/* max_streams (1..4096) slots; max_chunk (1..2^24) samples a push; lookahead, release, win_host [lookahead + release + 1],
+ * taps_host [n_taps], n_taps (0: the handle serves the sample-peak mode only) and phases as for smi_limit_rows, with the same
+ * ranges and the same check of the window's sum.  Synchronous (one allocation, one clear, two small copies). */
+int smi_limits_create(int max_streams, int max_chunk, int lookahead, int release, const double* win_host, const double* taps_host, int n_taps,
+                      int phases, smi_limits** out);
+int smi_limits_destroy(smi_limits* h);
+/* A new stream in slot `stream`: n = 0.  true_peak = 1: peaks of the oversampled signal (the handle's taps); 0: the sample
+ * mode.  ceiling > 0.  Host only.  A stream closes with its last push. */
+int smi_limits_open(smi_limits* h, int stream, int true_peak, double ceiling);
+/* One chunk per row: in_dev [B][stride] f32 (row b valid for len_host[b], which may be 0), of the open streams stream_host[b],
+ * each at most once in a call; last_host[b] = 1 on a stream's last push.  out_dev [B][out_stride] f32: row b receives its piece
+ * and zeros from there to out_stride (>= 1 and >= the longest piece); it must not overlap in_dev.  stats_dev (may be null)
+ * [B][4] float64 as above.  n_out_host [B] (may be null) receives the pieces' lengths, filled before the launch.  B <= 64.
+ * Asynchronous on `stream`.  Every argument of every row is checked before anything changes or is launched: a bad one returns
+ * SMI_EINVAL and names the argument in smi_last_error. */
+int smi_limits_push_rows(smi_limits* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                         const int32_t* last_host, int B, float* out_dev, long long out_stride, int32_t* n_out_host, double* stats_dev,
+                         void* stream);
+/* The piece length of one push, pure host arithmetic: a stream with reach lookahead, release that holds n_before samples takes
+ * len samples (last = 1: its last push); n_after (may be null) receives the samples after it.  -1 for a bad argument. */
+long long smi_limits_piece_len(int lookahead, int release, long long n_before, long long len, int last, long long* n_after);
+
 #ifdef __cplusplus
 }
 #endif

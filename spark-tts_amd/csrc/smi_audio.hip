@@ -35,6 +35,11 @@
 //                with the batch kernels' own device functions (ld_step, the block sums); one block per row then closes hops and
 //                blocks and walks the row's new gain knots in order; the last launch writes the pieces and the next held input.
 //                Everything a push is follows from the stream's length before it (ls_plan, host and device).  No atomics.
+//   k_limits_env, k_limits_apply, k_limits_stats   the limiter of joined streams (smi_limits_*): the batch launches over a
+//                stream's held input followed by its new chunk, with the batch kernels' own device functions (lm_env, lm_req,
+//                lm_smooth, lm_out), for the samples that nothing still to come can change; the apply launch also writes the
+//                next held input, the stats launch carries max e, min s and the count.  r is computed anew, never carried.
+//                Everything a push is follows from the stream's length before it (lt_plan, host and device).  No atomics.
 #include <limits.h>
 
 #include <cmath>
@@ -753,6 +758,78 @@ __device__ __forceinline__ double lm_block_red(double v, double* s) {
   return s[0];
 }
 
+// The per-sample arithmetic of the limiter, shared by the batch kernels and the stream kernels (k_limits_*), so that the two
+// forms cannot differ in a bit.
+// e of the sample xc points at, in a staged tile with LM_HALO samples on either side: the phases' sums in ascending d.  h is
+// indexed like the taps (kernel arguments in the batch form, device memory in the stream form); tp false: the sample peak.
+template <class Taps>
+__device__ __forceinline__ double lm_env(const Taps& h, int P, bool tp, const float* xc) {
+  double e = fabs((double)xc[0]);
+  if (tp) {
+    const int H = LM_HALO * P;
+    for (int k = 1; k < P; ++k) {
+      double u = 0.0;
+      for (int d = -LM_HALO; d < LM_HALO; ++d) u = u + h[P * d + k + H] * (double)xc[-d];   // (every tap of phase k)
+      e = fmax(e, fabs(u));
+    }
+  }
+  return e;
+}
+// the required gain r of a sample with envelope e
+__device__ __forceinline__ double lm_req(double g, double e, double ceiling) {
+  const double v = g * e;
+  return v > ceiling ? ceiling / v : 1.0;
+}
+// q[0 .. LM_TILE + 2 W), W = A + R, holds r over a tile's samples and W more on either side (1 where there is none).  The
+// forward minimum over W + 1 entries is formed in place by doubling -- every thread reads its entries of a round into registers
+// before any is written --, so F[i] = min r[i .. i + W] and m[j] = F[j - R]; the entries become the reductions 1 - m; a thread
+// then sums its samples' windows in ascending k.  s[u] receives s of the tile's sample threadIdx.x + u RS_BLOCK.  Every thread
+// of the block calls this.
+__device__ __forceinline__ void lm_smooth(double* q, int A, int R, const double* __restrict__ win, double (&s)[LM_TILE / RS_BLOCK]) {
+  const int W = A + R, nq = LM_TILE + 2 * W, tid = threadIdx.x;
+  __syncthreads();
+  double own[LM_TILE / RS_BLOCK];
+#pragma unroll
+  for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) own[u] = q[W + tid + u * RS_BLOCK];
+  int cur = 1;
+  while (cur < W + 1) {   // F over `cur` entries -> over min(2 cur, W + 1)
+    const int off = 2 * cur <= W + 1 ? cur : W + 1 - cur;
+    double t[LM_QPT];
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < LM_QPT; ++u) {
+      const int i = tid + u * RS_BLOCK;
+      t[u] = i < nq ? (i + off < nq ? fmin(q[i], q[i + off]) : q[i]) : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < LM_QPT; ++u) {
+      const int i = tid + u * RS_BLOCK;
+      if (i < nq) q[i] = t[u];
+    }
+    cur += off;
+  }
+  __syncthreads();
+  for (int i = tid; i < nq; i += RS_BLOCK) q[i] = 1.0 - q[i];
+  __syncthreads();
+  double acc[LM_TILE / RS_BLOCK];
+#pragma unroll
+  for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) acc[u] = 0.0;
+  const double* qc = q + tid + A;   // m[j - k] of the tile's sample c lies at q[c + A - k]
+  for (int k = -R; k <= A; ++k) {
+    const double wk = win[k + R];
+#pragma unroll
+    for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) acc[u] = acc[u] + wk * qc[u * RS_BLOCK - k];
+  }
+#pragma unroll
+  for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) s[u] = fmin(1.0 - acc[u], own[u]);
+}
+// the product and the clamp
+__device__ __forceinline__ float lm_out(float x, double g, double s, float c32) {
+  const float v = (float)(((double)x * g) * s);
+  return v > c32 ? c32 : (v < -c32 ? -c32 : v);
+}
+
 // grid (tiles of LM_TILE samples of the span, rows).  The tile and LM_HALO samples on either side go to LDS with coalesced
 // reads (zeros outside the span, which is never read); a thread then takes every RS_BLOCK-th sample: the phases' sums in
 // ascending d, the envelope e, and the required gain r to the row's part of work.  The tile's max e goes beside it.
@@ -774,20 +851,10 @@ __global__ __launch_bounds__(RS_BLOCK) void k_limit_env(LdArgs a, LmTaps tp, con
   const double g = gain ? gain[(size_t)b * gain_stride] : 1.0;
   double* row = work + lay.rows + (size_t)b * lay.row;
   const int cnt = min(LM_TILE, r.len - t0);
-  const int P = tp.phases, H = LM_HALO * P;
   double emax = 0.0;
   for (int i = tid; i < cnt; i += RS_BLOCK) {
-    const float* xc = xs + LM_HALO + i;
-    double e = fabs((double)xc[0]);
-    if (tp.n) {
-      for (int k = 1; k < P; ++k) {
-        double u = 0.0;
-        for (int d = -LM_HALO; d < LM_HALO; ++d) u = u + tp.h[P * d + k + H] * (double)xc[-d];   // (every tap of phase k)
-        e = fmax(e, fabs(u));
-      }
-    }
-    const double v = g * e;
-    row[t0 + i] = v > ceiling ? ceiling / v : 1.0;
+    const double e = lm_env(tp.h, tp.phases, tp.n != 0, xs + LM_HALO + i);
+    row[t0 + i] = lm_req(g, e, ceiling);
     emax = fmax(emax, e);
   }
   emax = lm_block_red<0>(emax, red);
@@ -795,9 +862,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_limit_env(LdArgs a, LmTaps tp, con
 }
 
 // grid (tiles of LM_TILE samples of the row up to out_stride, rows).  A tile that meets the span stages r over its samples and
-// A + R more on either side (1 outside the span) in LDS; the forward minimum over A + R + 1 entries is formed in place by
-// doubling -- every thread reads its entries of a round into registers before any is written --, so F[i] = min r[i .. i + A + R]
-// and m[j] = F[j - R]; the entries become the reductions 1 - m; a thread then sums its samples' windows in ascending k.  The
+// A + R more on either side (1 outside the span) in LDS and smooths them there (lm_smooth).  The
 // tile's min s and its count of s < 1 go to work.  in and out may be one buffer: a block reads the samples it writes, no others.
 __global__ __launch_bounds__(RS_BLOCK) void k_limit_apply(LdArgs a, int A, int R, const double* __restrict__ gain, int gain_stride, float c32,
                                                           const double* __restrict__ win, const float* in, long long in_stride,
@@ -823,42 +888,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_limit_apply(LdArgs a, int A, int R
       const long long j = j0 + i;
       q[i] = j >= 0 && j < r.len ? rr[j] : 1.0;
     }
-    __syncthreads();
-    double own[LM_TILE / RS_BLOCK];
-#pragma unroll
-    for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) own[u] = q[W + tid + u * RS_BLOCK];
-    int cur = 1;
-    while (cur < W + 1) {   // F over `cur` entries -> over min(2 cur, W + 1)
-      const int off = 2 * cur <= W + 1 ? cur : W + 1 - cur;
-      double t[LM_QPT];
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < LM_QPT; ++u) {
-        const int i = tid + u * RS_BLOCK;
-        t[u] = i < nq ? (i + off < nq ? fmin(q[i], q[i + off]) : q[i]) : 0.0;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < LM_QPT; ++u) {
-        const int i = tid + u * RS_BLOCK;
-        if (i < nq) q[i] = t[u];
-      }
-      cur += off;
-    }
-    __syncthreads();
-    for (int i = tid; i < nq; i += RS_BLOCK) q[i] = 1.0 - q[i];
-    __syncthreads();
-    double acc[LM_TILE / RS_BLOCK];
-#pragma unroll
-    for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) acc[u] = 0.0;
-    const double* qc = q + tid + A;   // m[j - k] of the tile's sample c lies at q[c + A - k]
-    for (int k = -R; k <= A; ++k) {
-      const double wk = win[k + R];
-#pragma unroll
-      for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) acc[u] = acc[u] + wk * qc[u * RS_BLOCK - k];
-    }
-#pragma unroll
-    for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) s[u] = fmin(1.0 - acc[u], own[u]);
+    lm_smooth(q, A, R, win, s);
   }
   const double g = gain ? gain[(size_t)b * gain_stride] : 1.0;
   double smin = 1.0, cnt = 0.0;
@@ -870,8 +900,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_limit_apply(LdArgs a, int A, int R
     if (i < r.n) {
       v = x[i];
       if (i >= r.start && i < (long long)r.start + r.len) {
-        v = (float)(((double)v * g) * s[u]);
-        v = v > c32 ? c32 : (v < -c32 ? -c32 : v);
+        v = lm_out(v, g, s[u], c32);
         smin = fmin(smin, s[u]);
         if (s[u] < 1.0) cnt = cnt + 1.0;
       }
@@ -1517,6 +1546,176 @@ __global__ __launch_bounds__(RS_BLOCK) void k_louds_apply(LsArgs a, LsState s, c
       v = (float)((double)x.at(m) * (g0 + d));
     }
     y[i] = v;
+  }
+}
+
+// ---- limiter of joined streams (smi_limits_*)
+#define LT_STATE 4              // float64 of one stream's state in one set: max e, min s, the count of s < 1 (and one unused)
+struct LtRow {
+  int32_t slot, set;        // the stream's slot; the state set this push reads (it writes the other one)
+  int32_t n_old, len;       // samples before this push; chunk samples, with bit 30 set on the stream's last push
+  int32_t tp;               // 1: the true-peak mode; 0: the sample peak
+  float c32;                // the largest float32 <= ceiling
+  double ceiling;
+};
+struct LtArgs {
+  LtRow r[RS_MAX_ROWS];
+};
+struct LtState {
+  const double* win;        // [A + R + 1]
+  const double* taps;       // [LM_MAX_TAPS]
+  double* st;               // [2][max_streams][LT_STATE]
+  float* hist;              // [2][max_streams][hcap]: hist[i] = x[h0 + i], i < n - h0
+  double* work;             // [rows of a call][wrow]: r over [r_lo, r_hi), then three values a tile
+  long long wrow, w_emax, w_smin, w_cnt;
+  int32_t max_streams, hcap, A, R, phases;
+};
+
+// everything a push is, from the stream's length before it, the chunk's length and `last`: the host's checks and the kernels
+// both call this, so they cannot disagree.  W = A + R.
+struct LtPlan {
+  int n_old, n_new, last;
+  int e_old, e_new;         // samples emitted before / after
+  int h0_old, h0_new;       // first sample the read set's history holds / the written set's will hold
+  int r_lo, r_hi;           // the samples whose r this push computes: what the piece's sums can read, inside the stream
+};
+__host__ __device__ __forceinline__ int lt_emitted(int n, int W) { return n > W + LM_HALO ? n - (W + LM_HALO) : 0; }
+__host__ __device__ __forceinline__ int lt_hist_start(int n, int W) {
+  const int a = lt_emitted(n, W) - W - (LM_HALO - 1);
+  return a > 0 ? a : 0;
+}
+__host__ __device__ __forceinline__ LtPlan lt_plan(int n_old, int len, int last, int W) {
+  LtPlan p;
+  p.n_old = n_old; p.n_new = n_old + len; p.last = last;
+  p.e_old = lt_emitted(n_old, W); p.e_new = last ? p.n_new : lt_emitted(p.n_new, W);
+  p.h0_old = lt_hist_start(n_old, W); p.h0_new = lt_hist_start(p.n_new, W);
+  p.r_lo = p.e_old > W ? p.e_old - W : 0;
+  p.r_hi = p.e_new > p.e_old ? (p.e_new + W < p.n_new ? p.e_new + W : p.n_new) : p.r_lo;
+  return p;
+}
+__device__ __forceinline__ LtPlan lt_plan(const LtRow& r, int W) { return lt_plan(r.n_old, r.len & 0x3FFFFFFF, (r.len >> 30) & 1, W); }
+
+// a stream's input: the history from h0_old, then the chunk; zero before the stream, behind its end, and before h0_old (which
+// no sum of this push reads)
+struct LtSeq {
+  const float* __restrict__ hist;
+  const float* __restrict__ chunk;
+  int h0, n_old, n_new;
+  __device__ __forceinline__ float at(int i) const { return i < h0 || i >= n_new ? 0.f : (i < n_old ? hist[i - h0] : chunk[i - n_old]); }
+};
+__device__ __forceinline__ LtSeq lt_seq(const LtRow& r, const LtPlan& p, const LtState& s, const float* chunk) {
+  return {s.hist + ((size_t)r.set * s.max_streams + r.slot) * s.hcap, chunk, p.h0_old, p.n_old, p.n_new};
+}
+
+// grid (tiles of LM_TILE samples of [r_lo, r_hi), rows): k_limit_env over the virtual sequence of history followed by the chunk,
+// at g = 1; the tile's max e counts the samples this push emits alone
+__global__ __launch_bounds__(RS_BLOCK) void k_limits_env(LtArgs a, LtState s, const float* __restrict__ in, long long in_stride) {
+  __shared__ float xs[LM_TILE + 2 * LM_HALO];
+  __shared__ double red[RS_BLOCK];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const LtRow r = a.r[b];
+  const LtPlan p = lt_plan(r, s.A + s.R);
+  const int t0 = p.r_lo + blockIdx.x * LM_TILE;   // of the stream
+  if (t0 >= p.r_hi) return;
+  const LtSeq x = lt_seq(r, p, s, in + (size_t)b * in_stride);
+  for (int i = tid; i < LM_TILE + 2 * LM_HALO; i += RS_BLOCK) xs[i] = x.at(t0 - LM_HALO + i);
+  __syncthreads();
+  double* row = s.work + (size_t)b * s.wrow;
+  const int cnt = min(LM_TILE, p.r_hi - t0);
+  double emax = 0.0;
+  for (int i = tid; i < cnt; i += RS_BLOCK) {
+    const double e = lm_env(s.taps, s.phases, r.tp != 0, xs + LM_HALO + i);
+    row[t0 - p.r_lo + i] = lm_req(1.0, e, r.ceiling);
+    if (t0 + i >= p.e_old && t0 + i < p.e_new) emax = fmax(emax, e);
+  }
+  emax = lm_block_red<0>(emax, red);
+  if (!tid) row[s.w_emax + blockIdx.x] = emax;
+}
+
+// grid (tiles of LM_TILE samples of the pieces up to out_stride, rows): k_limit_apply over the piece -- r from the row's work,
+// 1 outside [r_lo, r_hi) --, zeros from the piece's end to the stride.  Tile 0 of a row also writes the stream's next history
+// into the set this launch does not read.
+__global__ __launch_bounds__(RS_BLOCK) void k_limits_apply(LtArgs a, LtState s, const float* __restrict__ in, long long in_stride,
+                                                           float* __restrict__ out, long long out_stride) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  __shared__ double red[RS_BLOCK];
+  double* q = (double*)rs_lds;
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const LtRow r = a.r[b];
+  const int W = s.A + s.R;
+  const LtPlan p = lt_plan(r, W);
+  const LtSeq x = lt_seq(r, p, s, in + (size_t)b * in_stride);
+  float* y = out + (size_t)b * out_stride;
+  double* row = s.work + (size_t)b * s.wrow;
+  if (blockIdx.x == 0 && !p.last) {
+    float* hist2 = s.hist + ((size_t)(1 - r.set) * s.max_streams + r.slot) * s.hcap;
+    for (int i = p.h0_new + tid; i < p.n_new; i += RS_BLOCK) hist2[i - p.h0_new] = x.at(i);   // n_new - h0_new <= hcap: the host's check
+  }
+  const long long k0 = (long long)blockIdx.x * LM_TILE;   // of the piece
+  const int piece = p.e_new - p.e_old;
+  const bool hit = k0 < piece;
+  double sv[LM_TILE / RS_BLOCK];
+#pragma unroll
+  for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) sv[u] = 1.0;
+  if (hit) {
+    const int nq = LM_TILE + 2 * W;
+    const int j0 = p.e_old + (int)k0 - W;   // the stream's index of q[0]
+    for (int i = tid; i < nq; i += RS_BLOCK) {
+      const int j = j0 + i;
+      q[i] = j >= p.r_lo && j < p.r_hi ? row[j - p.r_lo] : 1.0;
+    }
+    lm_smooth(q, s.A, s.R, s.win, sv);
+  }
+  double smin = 1.0, cnt = 0.0;
+#pragma unroll
+  for (int u = 0; u < LM_TILE / RS_BLOCK; ++u) {
+    const long long i = k0 + tid + u * RS_BLOCK;
+    if (i >= out_stride) continue;
+    float v = 0.f;
+    if (i < piece) {
+      v = lm_out(x.at(p.e_old + (int)i), 1.0, sv[u], r.c32);
+      smin = fmin(smin, sv[u]);
+      if (sv[u] < 1.0) cnt = cnt + 1.0;
+    }
+    y[i] = v;
+  }
+  if (!hit) return;
+  smin = lm_block_red<1>(smin, red);
+  cnt = lm_block_red<2>(cnt, red);
+  if (!tid) {
+    row[s.w_smin + blockIdx.x] = smin;
+    row[s.w_cnt + blockIdx.x] = cnt;
+  }
+}
+
+// one block per row: the tiles' values and the stream's stats so far into the set this launch does not read and, where asked
+// for, into the row's four stats.  max, min and a sum of whole numbers: exact in any order.
+__global__ __launch_bounds__(RS_BLOCK) void k_limits_stats(LtArgs a, LtState s, double* __restrict__ stats) {
+  __shared__ double red[RS_BLOCK];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const LtRow r = a.r[b];
+  const LtPlan p = lt_plan(r, s.A + s.R);
+  const double* row = s.work + (size_t)b * s.wrow;
+  double emax = 0.0, smin = 1.0, cnt = 0.0;
+  const int te = (p.r_hi - p.r_lo + LM_TILE - 1) / LM_TILE, ta = (p.e_new - p.e_old + LM_TILE - 1) / LM_TILE;
+  for (int t = tid; t < te; t += RS_BLOCK) emax = fmax(emax, row[s.w_emax + t]);
+  for (int t = tid; t < ta; t += RS_BLOCK) {
+    smin = fmin(smin, row[s.w_smin + t]);
+    cnt = cnt + row[s.w_cnt + t];
+  }
+  emax = lm_block_red<0>(emax, red);
+  smin = lm_block_red<1>(smin, red);
+  cnt = lm_block_red<2>(cnt, red);
+  if (tid) return;
+  if (p.n_old > 0) {   // (a first push reads no state)
+    const double* so = s.st + ((size_t)r.set * s.max_streams + r.slot) * LT_STATE;
+    emax = fmax(emax, so[0]); smin = fmin(smin, so[1]); cnt = cnt + so[2];
+  }
+  double* sn = s.st + ((size_t)(1 - r.set) * s.max_streams + r.slot) * LT_STATE;
+  sn[0] = emax; sn[1] = smin; sn[2] = cnt;
+  if (stats) {
+    double* st = stats + 4 * (size_t)b;
+    st[0] = emax; st[1] = 1.0; st[2] = smin; st[3] = cnt;
   }
 }
 
@@ -2549,6 +2748,182 @@ int smi_louds_push_rows(smi_louds* h, const float* in_dev, long long stride, con
   SMI_LAUNCH_CHECK();
   const int gtiles = (int)((out_stride + GN_TILE - 1) / GN_TILE);
   hipLaunchKernelGGL(k_louds_apply, dim3(gtiles, B), dim3(RS_BLOCK), 0, hs, A, s, in_dev, stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// ---- limiter of joined streams (smi_limits_*): the host arithmetic of include/sparkmi.h's "Emission"
+#define LT_MAX_N (1LL << 28)   // input samples of one stream, as for smi_tempos and smi_louds
+
+struct LtStream {
+  int open = 0, set = 0, tp = 0;
+  long long n = 0;          // input samples so far: the samples emitted and the history held follow from it (lt_plan)
+  double ceiling = 1.0;
+};
+struct smi_limits {
+  LtState s;
+  int max_chunk, n_taps, rows;
+  DevBuf<char> pool;
+  std::vector<LtStream> streams;
+};
+
+extern "C" {
+
+long long smi_limits_piece_len(int lookahead, int release, long long n_before, long long len, int last, long long* n_after) {
+  if (lookahead < 0 || lookahead > LM_MAX_A || release < 0 || release > LM_MAX_R) return -1;
+  if (n_before < 0 || len < 0 || n_before > LT_MAX_N || len > LT_MAX_N || n_before + len > LT_MAX_N) return -1;
+  if (last != 0 && last != 1) return -1;
+  const LtPlan p = lt_plan((int)n_before, (int)len, last, lookahead + release);
+  if (n_after) *n_after = p.n_new;
+  return p.e_new - p.e_old;
+}
+
+int smi_limits_create(int max_streams, int max_chunk, int lookahead, int release, const double* win_host, const double* taps_host, int n_taps,
+                      int phases, smi_limits** out) {
+  SMI_REQUIRE(out, "smi_limits_create: null out");
+  *out = nullptr;
+  SMI_REQUIRE(max_streams >= 1 && max_streams <= JN_MAX_STREAMS, "smi_limits_create: max_streams=%d outside 1..%d", max_streams, JN_MAX_STREAMS);
+  SMI_REQUIRE(max_chunk >= 1 && max_chunk <= RS_MAX_SAMPLES, "smi_limits_create: max_chunk=%d outside 1..%d", max_chunk, RS_MAX_SAMPLES);
+  SMI_REQUIRE(phases >= 1 && phases <= LM_MAX_PHASES, "smi_limits_create: phases=%d outside 1..%d", phases, LM_MAX_PHASES);
+  SMI_REQUIRE(n_taps == 0 || n_taps == 2 * LM_HALO * phases + 1,
+              "smi_limits_create: n_taps=%d is neither 0 (the sample peak alone) nor %d = 2 * 10 * phases + 1 for phases=%d", n_taps,
+              2 * LM_HALO * phases + 1, phases);
+  SMI_REQUIRE(n_taps == 0 || taps_host, "smi_limits_create: null taps_host with n_taps=%d", n_taps);
+  for (int i = 0; i < n_taps; ++i) SMI_REQUIRE(std::isfinite(taps_host[i]), "smi_limits_create: taps[%d]=%g is not finite", i, taps_host[i]);
+  SMI_REQUIRE(lookahead >= 0 && lookahead <= LM_MAX_A, "smi_limits_create: lookahead=%d outside 0..%d", lookahead, LM_MAX_A);
+  SMI_REQUIRE(release >= 0 && release <= LM_MAX_R, "smi_limits_create: release=%d outside 0..%d", release, LM_MAX_R);
+  SMI_REQUIRE(win_host, "smi_limits_create: null win_host");
+  const int W = lookahead + release, nw = W + 1;
+  double wsum = 0.0;
+  for (int i = 0; i < nw; ++i) {
+    SMI_REQUIRE(std::isfinite(win_host[i]) && win_host[i] >= 0.0, "smi_limits_create: win[%d]=%g must be finite and >= 0", i, win_host[i]);
+    wsum = wsum + win_host[i];
+  }
+  SMI_REQUIRE(std::fabs(wsum - 1.0) <= 1e-12, "smi_limits_create: win sums to 1%+.3g over its %d weights, not to 1 within 1e-12", wsum - 1.0, nw);
+  char arch[128];
+  const int rc = smi_device_check(arch, sizeof(arch));
+  if (rc) return rc;
+  smi_limits* h = new smi_limits();
+  h->max_chunk = max_chunk; h->n_taps = n_taps;
+  h->rows = max_streams < RS_MAX_ROWS ? max_streams : RS_MAX_ROWS;   // a call holds a stream once, so never more rows than slots
+  LtState& s = h->s;
+  s.max_streams = max_streams; s.A = lookahead; s.R = release; s.phases = phases;
+  s.hcap = 2 * W + 2 * LM_HALO - 1;   // n - max(0, E(n) - W - 9) with E(n) = n - (W + 10)
+  // a row's scratch: the longest piece is max_chunk + W + 10 samples (a last push onto W + 10 held ones) and reads r over W more on
+  // either side; then a max e a tile of those, and a min s and a count a tile of the piece
+  const long long rcap = ((long long)max_chunk + 3LL * W + LM_HALO + 7) / 8 * 8, tiles = rcap / LM_TILE + 1;
+  s.w_emax = rcap;
+  s.w_smin = s.w_emax + tiles;
+  s.w_cnt = s.w_smin + tiles;
+  s.wrow = (s.w_cnt + tiles + 7) / 8 * 8;
+  // one allocation: float64 first (window, taps, states, scratch), then the two history sets (fp32)
+  const size_t n_win = ((size_t)nw + 7) / 8 * 8, n_taps8 = ((size_t)LM_MAX_TAPS + 7) / 8 * 8, n_st = 2 * (size_t)max_streams * LT_STATE;
+  const size_t n_work = (size_t)h->rows * s.wrow, n_hist = 2 * (size_t)max_streams * s.hcap;
+  const size_t bytes = (n_win + n_taps8 + n_st + n_work) * sizeof(double) + n_hist * sizeof(float);
+  if (h->pool.alloc(bytes, "smi_limits_create: stream state")) {
+    (void)hipGetLastError();
+    delete h;
+    return SMI_ENOMEM;
+  }
+  double* base = (double*)h->pool.get();
+  s.win = base;
+  s.taps = base + n_win;
+  s.st = base + n_win + n_taps8;
+  s.work = s.st + n_st;
+  s.hist = (float*)(s.work + n_work);
+  hipError_t e = hipMemset(h->pool, 0, bytes);
+  if (e == hipSuccess) e = hipMemcpy(base, win_host, (size_t)nw * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && n_taps) e = hipMemcpy(base + n_win, taps_host, (size_t)n_taps * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    smi_set_error("smi_limits_create: upload of the window and the taps: %s", hipGetErrorString(e));
+    delete h;
+    return SMI_EHIP;
+  }
+  h->streams.assign((size_t)max_streams, LtStream{});
+  *out = h;
+  return SMI_OK;
+}
+
+int smi_limits_destroy(smi_limits* h) {
+  delete h;
+  return SMI_OK;
+}
+
+int smi_limits_open(smi_limits* h, int stream, int true_peak, double ceiling) {
+  SMI_REQUIRE(h, "smi_limits_open: null handle");
+  SMI_REQUIRE(stream >= 0 && stream < h->s.max_streams, "smi_limits_open: stream=%d outside 0..%d", stream, h->s.max_streams - 1);
+  SMI_REQUIRE(true_peak == 0 || true_peak == 1, "smi_limits_open: true_peak=%d is neither 0 nor 1", true_peak);
+  SMI_REQUIRE(!true_peak || h->n_taps, "smi_limits_open: true_peak=1 on a handle created with n_taps=0 (the sample peak alone)");
+  SMI_REQUIRE(std::isfinite(ceiling) && ceiling > 0.0, "smi_limits_open: ceiling=%g must be finite and > 0", ceiling);
+  LtStream& st = h->streams[(size_t)stream];
+  st.open = 1; st.n = 0; st.tp = true_peak; st.ceiling = ceiling;   // (st.set goes on alternating: a first push reads no state)
+  return SMI_OK;
+}
+
+int smi_limits_push_rows(smi_limits* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                         const int32_t* last_host, int B, float* out_dev, long long out_stride, int32_t* n_out_host, double* stats_dev,
+                         void* stream) {
+  SMI_REQUIRE(h && in_dev && stream_host && len_host && last_host && out_dev, "smi_limits_push_rows: null argument");
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "smi_limits_push_rows: B=%d outside 1..%d", B, RS_MAX_ROWS);
+  SMI_REQUIRE(stride >= 1, "smi_limits_push_rows: stride=%lld must be positive", stride);
+  const LtState& s = h->s;
+  const int W = s.A + s.R;
+  LtArgs A;
+  LtPlan plan[RS_MAX_ROWS];
+  long long need = 1;
+  int r_max = 1;
+  for (int b = 0; b < B; ++b) {
+    const int id = stream_host[b];
+    SMI_REQUIRE(id >= 0 && id < s.max_streams, "smi_limits_push_rows: stream[%d]=%d outside 0..%d", b, id, s.max_streams - 1);
+    for (int c = 0; c < b; ++c)
+      SMI_REQUIRE(stream_host[c] != id, "smi_limits_push_rows: stream[%d]=%d is row %d's stream too (one chunk of a stream a call)", b, id, c);
+    const LtStream& st = h->streams[(size_t)id];
+    SMI_REQUIRE(st.open, "smi_limits_push_rows: stream[%d]=%d is not open (smi_limits_open; a stream closes with its last chunk)", b, id);
+    const int len = len_host[b], last = last_host[b];
+    SMI_REQUIRE(last == 0 || last == 1, "smi_limits_push_rows: last[%d]=%d is neither 0 nor 1", b, last);
+    SMI_REQUIRE(len >= 0 && len <= h->max_chunk && len <= stride, "smi_limits_push_rows: len[%d]=%d outside 0..min(max_chunk=%d, stride=%lld)", b,
+                len, h->max_chunk, stride);
+    SMI_REQUIRE(st.n + len <= LT_MAX_N, "smi_limits_push_rows: stream[%d]=%d would reach %lld samples: 2^28 is the limit of a stream", b, id,
+                st.n + len);
+    const LtPlan p = plan[b] = lt_plan((int)st.n, len, last, W);
+    SMI_REQUIRE(last || (p.h0_new >= p.h0_old && p.n_new - p.h0_new <= s.hcap),
+                "smi_limits_push_rows: stream[%d]=%d needs %d samples of history, the handle keeps %d", b, id, p.n_new - p.h0_new, s.hcap);
+    SMI_REQUIRE(p.r_hi - p.r_lo <= s.w_emax, "smi_limits_push_rows: stream[%d]=%d needs %d values of scratch, the handle keeps %lld", b, id,
+                p.r_hi - p.r_lo, s.w_emax);
+    LtRow& r = A.r[b];
+    r.slot = id; r.set = st.set; r.n_old = (int32_t)st.n; r.len = len | (last << 30);
+    r.tp = st.tp; r.ceiling = st.ceiling;
+    r.c32 = (float)st.ceiling;   // the largest float32 <= ceiling
+    if ((double)r.c32 > st.ceiling) r.c32 = nextafterf(r.c32, 0.f);
+    if (p.e_new - p.e_old > need) need = p.e_new - p.e_old;
+    if (p.r_hi - p.r_lo > r_max) r_max = p.r_hi - p.r_lo;
+  }
+  SMI_REQUIRE(out_stride >= need && out_stride <= TP_MAX_OUT, "smi_limits_push_rows: out_stride=%lld outside %lld (the longest piece)..%d",
+              out_stride, need, TP_MAX_OUT);
+  {
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + (size_t)B * stride * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_limits_push_rows: out_dev overlaps in_dev");
+  }
+  for (int b = 0; b < B; ++b) {
+    LtStream& st = h->streams[(size_t)stream_host[b]];
+    if (n_out_host) n_out_host[b] = plan[b].e_new - plan[b].e_old;
+    st.n = plan[b].n_new; st.set ^= 1;
+    if (last_host[b]) st.open = 0;
+  }
+  hipStream_t hs = (hipStream_t)stream;
+  const int etiles = (r_max + LM_TILE - 1) / LM_TILE;
+  hipLaunchKernelGGL(k_limits_env, dim3(etiles, B), dim3(RS_BLOCK), 0, hs, A, s, in_dev, stride);
+  SMI_LAUNCH_CHECK();
+  const int tiles = (int)((out_stride + LM_TILE - 1) / LM_TILE);
+  const size_t lds = (size_t)(LM_TILE + 2 * W) * sizeof(double);
+  hipLaunchKernelGGL(k_limits_apply, dim3(tiles, B), dim3(RS_BLOCK), lds, hs, A, s, in_dev, stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_limits_stats, dim3(B), dim3(RS_BLOCK), 0, hs, A, s, stats_dev);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

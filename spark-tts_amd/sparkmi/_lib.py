@@ -278,6 +278,12 @@ SYMBOLS = {
     "smi_louds_push_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, C.c_longlong, _VP,
                                  C.c_longlong, _P(C.c_int32), _VP, _VP]),
     "smi_louds_piece_len": (C.c_longlong, [_I, C.c_longlong, C.c_longlong, _I, _P(C.c_longlong), _P(C.c_longlong)]),
+    "smi_limits_create": (_I, [_I, _I, _I, _I, _P(C.c_double), _P(C.c_double), _I, _I, _P(_VP)]),
+    "smi_limits_destroy": (_I, [_VP]),
+    "smi_limits_open": (_I, [_VP, _I, _I, C.c_double]),
+    "smi_limits_push_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, C.c_longlong,
+                                  _P(C.c_int32), _VP, _VP]),
+    "smi_limits_piece_len": (C.c_longlong, [_I, _I, C.c_longlong, C.c_longlong, _I, _P(C.c_longlong)]),
 }
 
 # include/sparkmi_debug.h: exported by libsparkmi_diag.so only

@@ -917,3 +917,136 @@ class StreamLoudness:
     def _stream(self) -> C.c_void_p:
         import torch
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class StreamLimiter:
+    """Owns one ``smi_limits`` handle (include/sparkmi.h): the look-ahead limiter of ``DeviceAudio.limit_rows`` for joined
+    streams that are still arriving.  The limiter is feed-forward, so nothing is defined anew: the concatenation of a stream's
+    pieces is ``limit_rows`` of its whole input at gain 1, bit for bit, however the stream was chunked; the input that a later
+    sample can still read (at most ``2 (A + R) + 19`` samples) and the running stats are kept on the device per stream.  A piece
+    leaves ``A + R + 10`` samples (28 ms at 16 kHz) behind its input, in both modes.  Request keys map to the handle's stream
+    slots as in ``StreamLoudness``: ``open(key, mode, ceiling)`` takes a free slot, ``push`` sends one poll's chunks, and a
+    key's slot is free again after its last push.  A key that ``push`` meets unopened is opened in the "true" mode at
+    ``PEAK_CEILING``.  All pushes go to the current HIP stream at the time of the call: keep them on one stream.  ``lib``: a
+    stand-in library."""
+
+    def __init__(self, max_streams: int, max_chunk: int, sr: int = 16000, lookahead_ms: float = 2.5, release_ms: float = 25.0,
+                 device="cuda:0", diag: bool = False, lib=None):
+        self._lib = lib if lib is not None else _lib.pick(diag)
+        self._fake = lib is not None
+        self.device = device
+        if not self._fake:
+            import torch
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise _lib.SparkMIError("StreamLimiter runs on an MI355X only (device must be cuda:N); there is no CPU path")
+        self.max_streams, self.max_chunk = int(max_streams), int(max_chunk)
+        self.lookahead, self.release = limiter_reach(sr, lookahead_ms, release_ms)
+        self.delay = self.lookahead + self.release + 10     # samples a piece leaves behind its input
+        win = np.ascontiguousarray(limiter_window(self.lookahead, self.release), dtype=np.float64)
+        taps = np.ascontiguousarray(resample_taps(LIMITER_PHASES, 1), dtype=np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))   # noqa: E731
+        self._h = C.c_void_p()
+        self._lib.check(self._lib.smi_limits_create(self.max_streams, self.max_chunk, self.lookahead, self.release, dp(win), dp(taps),
+                                                    taps.size, LIMITER_PHASES, C.byref(self._h)), "smi_limits_create")
+        self._free: List[int] = list(range(self.max_streams))   # (open() hands out the lowest free slot)
+        self._open: dict = {}       # key -> [slot, n]
+        self.calls = 0              # smi_limits_push_rows calls so far: three launches each
+        self.last_stats = None      # [B][4] float64 on the device: the stats of the last push's rows
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.smi_limits_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """forget every open key (an abandoned stream's slots come back)"""
+        self._free = list(range(self.max_streams))
+        self._open = {}
+
+    def slot(self, key) -> Optional[int]:
+        return self._open[key][0] if key in self._open else None
+
+    def open(self, key, mode: str = "true", ceiling: float = PEAK_CEILING) -> int:
+        if key in self._open:
+            raise ValueError(f"request {key}: already open")
+        if not isinstance(mode, str) or mode not in LIMITER_MODES:
+            raise ValueError(f"mode must be \"true\" or \"sample\", not {mode!r}")
+        if not self._free:
+            raise ValueError(f"StreamLimiter: all {self.max_streams} stream slots are in use")
+        s = min(self._free)
+        self._lib.check(self._lib.smi_limits_open(self._h, s, int(mode == "true"), float(ceiling)), "smi_limits_open")
+        self._free.remove(s)
+        self._open[key] = [s, 0]
+        return s
+
+    def piece_lengths(self, rows: Sequence[Tuple]) -> List[int]:
+        """the piece lengths ``push(x, rows)`` would return, without pushing (pure host arithmetic)"""
+        from .streaming import limiter_piece_len
+        state = {k: v[1] for k, v in self._open.items()}
+        pieces = []
+        for key, length, last in rows:
+            piece, state[key] = limiter_piece_len(self.lookahead, self.release, state.get(key, 0), length, last)
+            pieces.append(piece)
+        return pieces
+
+    def push(self, x, rows: Sequence[Tuple]):
+        """``x``: [B][stride] float32 on the device, row b the new samples of request ``rows[b] = (key, length, last)``.
+        Returns (out [B][out_stride] float32 on the device -- row b holds its piece, then zeros --, the pieces' lengths); a
+        length may be 0.  ``last_stats`` holds [B][4] float64 on the device: the peak going in, 1, the smallest factor and the
+        samples reduced, over what each row's stream has emitted so far (after its last push: over the whole stream).  A request
+        that appears twice makes two device calls (``streaming.split_calls``), each three launches; everything is enqueued on
+        the current stream, nothing waits and nothing is copied back."""
+        from .streaming import split_calls
+        B = len(rows)
+        if not B:
+            raise ValueError("push takes at least one row")
+        if not self._fake:
+            import torch
+            if x.dim() != 2 or x.shape[0] != B or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+                raise ValueError("push takes a contiguous [B][stride] float32 tensor on the device, one row per chunk")
+        for _, length, _ in rows:
+            if not 0 <= int(length) <= self.max_chunk:
+                raise ValueError(f"a chunk of {length} samples is outside 0..max_chunk={self.max_chunk}")
+        want = self.piece_lengths(rows)      # raises for a bad length before anything is opened or pushed
+        for key, _, _ in rows:
+            if key not in self._open:
+                self.open(key)
+        stride = max(1, max(want))
+        in_stride = 1 if self._fake else int(x.shape[1])
+        out = stats = None
+        if not self._fake:
+            out = torch.empty((B, stride), dtype=torch.float32, device=self.device)
+            stats = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        got_all: List[int] = []
+        for a, b in split_calls([r[0] for r in rows]):
+            n = b - a
+            i32 = lambda v: (C.c_int32 * n)(*[int(t) for t in v])   # noqa: E731
+            got = (C.c_int32 * n)()
+            src = C.c_void_p(0 if self._fake else x.data_ptr() + 4 * a * in_stride)
+            dst = C.c_void_p(0 if self._fake else out.data_ptr() + 4 * a * stride)
+            sdst = C.c_void_p(0 if stats is None else stats.data_ptr() + 32 * a)
+            self._lib.check(self._lib.smi_limits_push_rows(self._h, src, in_stride, i32(self._open[r[0]][0] for r in rows[a:b]),
+                                                           i32(r[1] for r in rows[a:b]), i32(bool(r[2]) for r in rows[a:b]), n, dst,
+                                                           stride, got, sdst, None if self._fake else self._stream()),
+                            "smi_limits_push_rows")
+            self.calls += 1
+            got_all += list(got)
+            for key, length, last in rows[a:b]:
+                self._open[key][1] += int(length)
+                if last:
+                    self._free.append(self._open.pop(key)[0])
+        if not self._fake:
+            assert got_all == want, (got_all, want)
+        self.last_stats = stats
+        return out, want
+
+    def _stream(self) -> C.c_void_p:
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

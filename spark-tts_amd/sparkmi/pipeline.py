@@ -14,7 +14,8 @@ waveforms trimmed and joined on the device); ``loudness`` / ``peak_ceiling`` / `
 utterances (the output at a programme loudness after BS.1770, measured and scaled on the device); ``tempo`` on the same calls
 (a pitch-preserving change of the speaking rate, 0.5 .. 2.0, on the device before the loudness stage) and, with
 ``joined=True``, on the two streaming calls (the same arithmetic with its state carried across the chunks on the device);
-``limiter`` on the calls that return whole utterances (a look-ahead true-peak limiter behind the loudness stage, on the device).
+``limiter`` on the calls that return whole utterances (a look-ahead true-peak limiter behind the loudness stage, on the device)
+and ``stream_limiter``, with ``joined=True``, on the two streaming calls (the same limiter with its input carried across the chunks).
 """
 from __future__ import annotations
 
@@ -61,6 +62,9 @@ LIMITED = (None, "max_gain", "ceiling")   # what bounded a row's gain (include/s
 LIMITER_KEY = "limiter"
 # the ceiling the loudness stage is given where the limiter holds ``peak_ceiling`` behind it: large and finite, it cannot bind
 NO_CEILING = 1e30
+# request key: the request's own streaming limiter ("true", "sample" or None) in ``serve_stream(joined=True)``; it overrides the
+# call's ``stream_limiter``
+STREAM_LIMITER_KEY = "stream_limiter"
 # request key: the request's own tempo (0.5 .. 2.0; > 1: faster); it overrides the call's ``tempo``
 TEMPO_KEY = "tempo"
 
@@ -353,12 +357,14 @@ class SparkTTS:
 
     def _stream_stages(self, who: str, output_sample_rate: Optional[int], max_streams: int, audio_chunk_duration: float,
                        max_audio_chunk_duration: float, audio_chunk_size_scale_factor: float, audio_chunk_overlap_duration: float,
-                       loudness: bool = False):
-        """The stages of a ``joined=True`` call with a tempo or a loudness, in the batch path's order, their slots all free: (the
-        crossfade -- a ``StreamJoiner`` at 1/1 --, the ``StreamTempo``, with ``loudness`` the ``StreamLoudness``, else None, and
-        with ``output_sample_rate`` the resampler with state -- a second ``StreamJoiner`` with overlap 0 at that ratio, which is
-        plain concatenation plus the filter --, else None).  Everything is checked before any device call."""
-        from .audio import StreamJoiner, StreamLoudness, StreamTempo, tempo_frame
+                       loudness: bool = False, limiter: Optional[Tuple[float, float]] = None):
+        """The stages of a ``joined=True`` call with a tempo, a loudness or a streaming limiter, in the batch path's order, their
+        slots all free: (the crossfade -- a ``StreamJoiner`` at 1/1 --, the ``StreamTempo``, with ``loudness`` the
+        ``StreamLoudness``, else None, with ``limiter`` = (lookahead_ms, release_ms) the ``StreamLimiter``, else None, and with
+        ``output_sample_rate`` the resampler with state -- a second ``StreamJoiner`` with overlap 0 at that ratio, which is
+        plain concatenation plus the filter --, else None).  Every stage's ``max_chunk`` is the longest piece the stage before it
+        can emit.  Everything is checked before any device call."""
+        from .audio import StreamJoiner, StreamLimiter, StreamLoudness, StreamTempo, tempo_frame
         out_ratio = self._output_ratio(output_sample_rate)
         fade = self._stream_joiner(who, None, max_streams, audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor,
                                    audio_chunk_overlap_duration)
@@ -381,6 +387,17 @@ class SparkTTS:
             loud = self._louds[key]
             loud.reset()
             longest += 5 * loud.hop   # a stream's last push brings what the stage held back
+        lim = None
+        if limiter is not None:
+            key = (int(max_streams), longest, float(limiter[0]), float(limiter[1]))
+            if getattr(self, "_limits", None) is None:
+                self._limits = {}
+            if key not in self._limits:
+                self._limits[key] = StreamLimiter(key[0], key[1], sr=self.sample_rate, lookahead_ms=key[2], release_ms=key[3],
+                                                  device=self.device)
+            lim = self._limits[key]
+            lim.reset()
+            longest += lim.delay      # A + R + 10: likewise
         rate = None
         if out_ratio is not None:
             key = (int(max_streams), longest, 0) + tuple(out_ratio)
@@ -388,18 +405,19 @@ class SparkTTS:
                 self._joiners[key] = StreamJoiner(*key, device=self.device)
             rate = self._joiners[key]
             rate.reset()
-        return fade, scale, loud, rate
+        return fade, scale, loud, lim, rate
 
     def _staged_push(self, stages, x, rows: Sequence[Tuple]):
         """One poll's ready chunks ``rows[b] = (key, length, last)`` (``x`` [B][stride] on the device) through the stages of
         ``_stream_stages``, all enqueued on the current stream: (rows on the device, {b: its row there}, the final pieces'
         lengths, the pieces' lengths behind the tempo stage -- what a listener hears, at the model's rate --, and {b: the
-        loudness stage's stats row, on the device} for the rows that are their stream's last).  A stage is skipped for a push
-        whose piece from the stage before is empty, unless it is the stream's last: its later pieces are empty."""
+        loudness stage's stats row, on the device} and {b: the limiter stage's} for the rows that are their stream's last).  A
+        stage is skipped for a push whose piece from the stage before is empty, unless it is the stream's last: its later
+        pieces are empty."""
         cur, lens = stages[0].push(x, rows)
         lens = list(lens)
         at = {b: b for b in range(len(rows))}
-        heard, final = lens, {}
+        heard, final, final_lim = lens, {}, {}
         for stage in stages[1:]:
             if stage is None:
                 continue
@@ -421,7 +439,17 @@ class SparkTTS:
                 heard = list(lens)
             elif stage is stages[2] and go:
                 final = {b: stage.last_stats[i] for i, b in enumerate(go) if rows[b][2]}
-        return cur, at, lens, heard, final
+            elif stage is stages[3] and go:
+                final_lim = {b: stage.last_stats[i] for i, b in enumerate(go) if rows[b][2]}
+        return cur, at, lens, heard, final, final_lim
+
+    @staticmethod
+    def _stream_limiter_info(row: Sequence[float]) -> dict:
+        """a finished stream's entry, as ``inference_batch``'s ``last_limiter``: ``true_peak`` (going in; the sample peak in the
+        "sample" mode), ``reduction_db`` (-20 log10 of the smallest factor) and ``limited_samples``"""
+        peak, _, smin, count = row
+        return dict(true_peak=peak, reduction_db=0.0 if smin >= 1.0 else (math.inf if smin <= 0.0 else -20.0 * math.log10(smin)),
+                    limited_samples=int(count))
 
     @staticmethod
     def _no_stream_rate(output_sample_rate: Optional[int], who: str) -> None:
@@ -510,8 +538,24 @@ class SparkTTS:
     def _no_stream_limiter(limiter, who: str) -> None:
         if limiter is not None:
             raise ValueError(f"{who}: limiter is not supported on chunked streams (the look-ahead and the release reach across "
-                             "chunk edges, so a streaming limiter needs A + R samples of carried state); use inference / "
-                             "inference_batch / serve / inference_long / inference_long_stream")
+                             "chunk edges): pass joined=True with stream_limiter= for the streaming form, whose pieces leave "
+                             "A + R + 10 samples late, or use inference / inference_batch / serve / inference_long / "
+                             "inference_long_stream")
+
+    @staticmethod
+    def _no_stream_limiter_form(stream_limiter, who: str) -> None:
+        if stream_limiter is not None:
+            raise ValueError(f"{who}: stream_limiter is not supported for overlapping chunks (the limiter works on one contiguous "
+                             "stream and carries its input across chunk edges); pass joined=True")
+
+    def _stream_limiter_mode(self, r: dict, stream_limiter, peak_ceiling, lookahead_ms, release_ms, who: str = ""):
+        """the streaming limiter's mode of one request -- its own ``stream_limiter`` key, else the call's; None: none --, checked"""
+        m = r.get(STREAM_LIMITER_KEY, stream_limiter)
+        try:
+            check_limiter(m, peak_ceiling, lookahead_ms, release_ms, self.sample_rate)
+        except ValueError as e:
+            raise ValueError(who + str(e).replace("limiter must", "stream_limiter must", 1)) from None
+        return m
 
     def _level_rows(self, wav, n: Sequence[int], targets: Sequence[Optional[float]], modes: Sequence[Optional[str]], peak_ceiling: float,
                     max_gain_db: float, reach: Tuple[int, int], spans=None):
@@ -781,7 +825,8 @@ class SparkTTS:
                          decode_stride: int = 10, output_sample_rate: Optional[int] = None,
                          joined: bool = False, tempo: Optional[float] = None, loudness: Optional[float] = None,
                          peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
-                         max_slew_db: float = 1.0, limiter: Optional[str] = None) -> Iterator[np.ndarray]:
+                         max_slew_db: float = 1.0, limiter: Optional[str] = None, stream_limiter: Optional[str] = None,
+                         limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
@@ -818,24 +863,43 @@ class SparkTTS:
         frames that are not final yet, and the last piece brings them.  With
         ``joined=False`` a given ``tempo`` is refused (ValueError): overlapping chunks have no edges to carry state across.
 
-        ``limiter`` is refused (ValueError), joined or not: the limiter of ``inference_batch`` has no streaming form yet."""
+        ``stream_limiter`` (None: nothing new is built or launched; "true": peaks of the 4x oversampled signal; "sample": of the
+        samples alone) needs ``joined=True``: the look-ahead limiter of ``inference_batch`` on the stream while it is still
+        arriving (include/sparkmi.h, smi_limits_*; ``audio.StreamLimiter``), behind the loudness stage and before
+        the resampler with state.  ``peak_ceiling``, ``limiter_lookahead_ms`` and ``limiter_release_ms`` mean what they mean
+        there.  The limiter is feed-forward, so the pieces' concatenation is, bit for bit, ``DeviceAudio.limit_rows`` of the
+        concatenated pieces of the same call without it, whatever the chunking; a piece leaves A + R + 10 samples (28 ms at
+        16 kHz) behind its input and the last piece brings them.  Its contract is its own: with ``loudness`` it works behind the
+        running gain of that stage, not behind one gain a row, and the loudness stage is then given no ceiling -- its gain
+        follows the target and the limiter holds ``peak_ceiling``.  After the last piece ``self.last_limiter`` holds
+        {``true_peak``, ``reduction_db``, ``limited_samples``} of the whole stream: one 32-byte copy.  With ``joined=False`` a
+        given ``stream_limiter`` is refused (ValueError).
+
+        ``limiter`` is refused (ValueError), joined or not: that keyword names the limiter of whole utterances, which
+        ``inference_batch`` has; the streaming form is asked for by ``stream_limiter``."""
         self._no_stream_limiter(limiter, "inference_stream")
         if not joined:
             self._no_stream_tempo(tempo, "inference_stream")
             self._no_stream_loudness(loudness, "inference_stream")
+            self._no_stream_limiter_form(stream_limiter, "inference_stream")
             self._no_stream_rate(output_sample_rate, "inference_stream")
         rate = self._tempo_ratios([{}], tempo)[0]
         target = self._loudness_targets([{}], loudness, peak_ceiling, max_gain_db)[0]
         self._check_slew(max_slew_db)
+        mode = self._stream_limiter_mode({}, stream_limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
         stages = None
-        if joined and (rate is not None or target is not None):
-            stages = self._stream_stages("inference_stream", output_sample_rate, 1, *sched_args, loudness=target is not None)
+        if joined and (rate is not None or target is not None or mode is not None):
+            stages = self._stream_stages("inference_stream", output_sample_rate, 1, *sched_args, loudness=target is not None,
+                                         limiter=None if mode is None else (limiter_lookahead_ms, limiter_release_ms))
             joiner = stages[0]
             stages[1].open(0, *(rate or (1, 1)))
-            if stages[2] is not None:
-                stages[2].open(0, target, max_gain_db, peak_ceiling, max_slew_db)
+            if stages[2] is not None:   # (with a limiter behind it the gain follows the target: the limiter holds the ceiling)
+                stages[2].open(0, target, max_gain_db, peak_ceiling if mode is None else NO_CEILING, max_slew_db)
                 self.last_loudness = None
+            if stages[3] is not None:
+                stages[3].open(0, mode, peak_ceiling)
+                self.last_limiter = None
         else:
             joiner = self._stream_joiner("inference_stream", output_sample_rate, 1, *sched_args) if joined else None
         if gender is not None:
@@ -865,10 +929,12 @@ class SparkTTS:
             else:
                 wav = torch.zeros((1, 1), dtype=torch.float32, device=self.device)
             if stages is not None:
-                out, at, lens, _, final = self._staged_push(stages, wav, [(0, len(chunk) * hop, last)])
+                out, at, lens, _, final, final_lim = self._staged_push(stages, wav, [(0, len(chunk) * hop, last)])
                 w = out[at[0], : lens[0]].cpu().numpy().copy() if 0 in at else np.zeros(0, dtype=np.float32)
                 if 0 in final:   # behind the last piece
                     self.last_loudness = self._stream_loudness_info(final[0].cpu().tolist())
+                if 0 in final_lim:
+                    self.last_limiter = self._stream_limiter_info(final_lim[0].cpu().tolist())
                 return w
             out, lens = joiner.push(wav, [(0, len(chunk) * hop, last)])
             return out[0, : lens[0]].cpu().numpy().copy()
@@ -1049,7 +1115,8 @@ class SparkTTS:
                      max_open: Optional[int] = None, max_ahead: Optional[float] = None, resume_ahead: Optional[float] = None,
                      clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None, joined: bool = False,
                      tempo: Optional[float] = None, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
-                     max_gain_db: float = 20.0, max_slew_db: float = 1.0, limiter: Optional[str] = None):
+                     max_gain_db: float = 20.0, max_slew_db: float = 1.0, limiter: Optional[str] = None,
+                     stream_limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -1116,13 +1183,29 @@ class SparkTTS:
         begins, from ``tempo`` and, where ``requests`` is a list, its requests; a request that brings a tempo of its own from
         an iterator into a call without them is refused (ValueError): pass a list, or a ``tempo`` for the call.
 
-        ``limiter`` and a request's own ``limiter`` key are refused (ValueError), joined or not: the limiter of
-        ``inference_batch`` has no streaming form yet."""
+        ``stream_limiter`` and a request's own ``stream_limiter`` key, which overrides it (None everywhere: nothing new is built
+        or launched and every piece keeps its bits), need ``joined=True``; with ``joined=False`` either is refused (ValueError).
+        Every request's stream then goes through a limiter stream of its own (``inference_stream`` describes it;
+        include/sparkmi.h, smi_limits_*; ``audio.StreamLimiter``) behind the loudness stage and before the resampler with state,
+        three launches more per poll, with max(``max_open``, ``max_batch``) slots, so a parked request keeps its slot.  A
+        request with a limiter has its loudness stream opened without a ceiling, as in ``inference_batch``.  A request without
+        one in a call that has the stage is copied through it: its stream is opened in the "sample" mode under a ceiling that
+        cannot bind, which gives every sample back bit for bit, A + R + 10 samples later.  The ``Pacer`` goes on counting the
+        lengths behind the tempo stage.  After a request's last piece ``self.last_limiter[index]`` holds its entry as in
+        ``inference_stream`` (one 32-byte copy; None for a request without a limiter).  Whether a call has the stage is settled
+        when it begins, as for ``tempo``; a request that brings a ``stream_limiter`` of its own from an iterator into a call
+        without it is refused (ValueError).
+
+        ``limiter`` and a request's own ``limiter`` key are refused (ValueError), joined or not: they name the limiter of whole
+        utterances; the streaming form is asked for by ``stream_limiter``."""
         self._no_stream_limiter(limiter, "serve_stream")
         if not joined:
             self._no_stream_tempo(tempo, "serve_stream")
             self._no_stream_loudness(loudness, "serve_stream")
+            self._no_stream_limiter_form(stream_limiter, "serve_stream")
             self._no_stream_rate(output_sample_rate, "serve_stream")
+        call_mode = self._stream_limiter_mode({}, stream_limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
+        modes: Dict[int, Optional[str]] = {}   # request index -> its streaming limiter's mode, None without one
         call_rate = self._tempo_ratios([{}], tempo)[0]
         call_target = self._loudness_targets([{}], loudness, peak_ceiling, max_gain_db)[0]
         self._check_slew(max_slew_db)
@@ -1131,10 +1214,10 @@ class SparkTTS:
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
-                for k in (FORK_KEY,) + (() if joined else (TEMPO_KEY, LOUDNESS_KEY)) + tuple(LOGPROB_KEYS):
+                for k in (FORK_KEY,) + (() if joined else (TEMPO_KEY, LOUDNESS_KEY, STREAM_LIMITER_KEY)) + tuple(LOGPROB_KEYS):
                     if k in r:
                         raise ValueError(f"request {i}: {k} is not supported by serve_stream" + (
-                            " with overlapping chunks; pass joined=True" if k in (TEMPO_KEY, LOUDNESS_KEY) else ""))
+                            " with overlapping chunks; pass joined=True" if k in (TEMPO_KEY, LOUDNESS_KEY, STREAM_LIMITER_KEY) else ""))
                 if r.get(LIMITER_KEY) is not None:
                     self._no_stream_limiter(r[LIMITER_KEY], f"request {i}: serve_stream")
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
@@ -1143,14 +1226,17 @@ class SparkTTS:
                     targets[i] = self._loudness_targets([r], loudness, peak_ceiling, max_gain_db)[0]
                 except ValueError as e:
                     raise ValueError(str(e).replace("request 0:", f"request {i}:", 1)) from None
+                modes[i] = self._stream_limiter_mode(r, stream_limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms,
+                                                     f"request {i}: ")
                 yield r
 
-        staged, leveled = call_rate is not None, call_target is not None
+        staged, leveled, limited = call_rate is not None, call_target is not None, call_mode is not None
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
             for _ in checked(requests):
                 pass
             staged = staged or any(v != (1, 1) for v in rates.values())
             leveled = leveled or any(v is not None for v in targets.values())
+            limited = limited or any(v is not None for v in modes.values())
         decode_stride = int(decode_stride)
         if decode_stride < 1:
             raise ValueError("decode_stride must be >= 1")
@@ -1172,12 +1258,14 @@ class SparkTTS:
                         audio_chunk_overlap_duration=audio_chunk_overlap_duration)
         sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
         stages = None
-        if joined and (staged or leveled):
+        if joined and (staged or leveled or limited):
             stages = self._stream_stages("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args,
-                                         loudness=leveled)
+                                         loudness=leveled, limiter=(limiter_lookahead_ms, limiter_release_ms) if limited else None)
             joiner = stages[0]
             if leveled:
                 self.last_loudness = {}
+            if limited:
+                self.last_limiter = {}
         else:
             joiner = self._stream_joiner("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args) if joined else None
         if getattr(self, "_voc_stream", None) is None:
@@ -1192,6 +1280,10 @@ class SparkTTS:
                 if (stages is None or stages[2] is None) and targets[i] is not None:
                     raise ValueError(f"request {i}: a loudness of its own from an iterator of requests, in a serve_stream call that "
                                      "began without the loudness stage; pass the requests as a list, or a loudness for the call")
+                if (stages is None or stages[3] is None) and modes[i] is not None:
+                    raise ValueError(f"request {i}: a stream_limiter of its own from an iterator of requests, in a serve_stream call "
+                                     "that began without the limiter stage; pass the requests as a list, or a stream_limiter for "
+                                     "the call")
                 if r.get("gender") is not None:
                     prompt, g = self.process_prompt_control(r["gender"], r.get("pitch"), r.get("speed"), r["text"]), None
                 else:
@@ -1231,11 +1323,14 @@ class SparkTTS:
 
         def collect_joined(job):
             chunks, (_, out, *rest) = job
-            at, n_out, heard, final = rest if stages is not None else ({b: b for b in range(len(chunks))}, rest[0], None, {})
+            at, n_out, heard, final, final_lim = rest if stages is not None else ({b: b for b in range(len(chunks))}, rest[0], None, {}, {})
             with torch.cuda.stream(vs):
                 out = out.cpu().numpy()
                 for b, row in final.items():   # behind a request's last piece
                     self.last_loudness[chunks[b][0]] = self._stream_loudness_info(row.cpu().tolist())
+                for b, row in final_lim.items():
+                    key = chunks[b][0]
+                    self.last_limiter[key] = None if modes[key] is None else self._stream_limiter_info(row.cpu().tolist())
             for b, (key, index, sem, last) in enumerate(chunks):
                 if pacer.active:
                     frames = max(0, len(sem) - (overlap if index else 0))
@@ -1301,7 +1396,13 @@ class SparkTTS:
                         if stages is not None:   # (host only; a request without a tempo copies through at 1/1)
                             stages[1].open(r[0], *rates[r[0]])
                             if stages[2] is not None:   # (host only; a request without a target is measured and copied)
-                                stages[2].open(r[0], targets[r[0]], max_gain_db, peak_ceiling, max_slew_db)
+                                stages[2].open(r[0], targets[r[0]], max_gain_db, peak_ceiling if modes[r[0]] is None else NO_CEILING,
+                                               max_slew_db)
+                            if stages[3] is not None:   # (host only; a request without a limiter is copied through, A + R + 10 late)
+                                if modes[r[0]] is None:
+                                    stages[3].open(r[0], "sample", NO_CEILING)
+                                else:
+                                    stages[3].open(r[0], modes[r[0]], peak_ceiling)
                 self.model.decode(decode_stride)   # enqueued: it runs while the host collects the previous poll's chunks
                 if job is not None:
                     yield from collect(job)

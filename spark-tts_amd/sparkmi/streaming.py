@@ -211,6 +211,27 @@ def loudness_piece_len(block: int, n_before: int, length: int, last: bool) -> Tu
     return loudness_emitted(n, hop) - loudness_emitted(n_before, hop), n, loudness_knots(n, hop)
 
 
+# ---- limiter of joined streams (include/sparkmi.h, smi_limits_*): what a push emits, as host arithmetic
+LIMITER_HALO = 10      # samples the true-peak interpolator reaches on either side
+
+
+def limiter_emitted(n: int, lookahead: int, release: int) -> int:
+    """E(n): samples a stream that goes on has emitted: sample i reads its input up to ``i + A + R + 10``, in both modes"""
+    return max(0, int(n) - (int(lookahead) + int(release) + LIMITER_HALO))
+
+
+def limiter_piece_len(lookahead: int, release: int, n_before: int, length: int, last: bool) -> Tuple[int, int]:
+    """(piece length, n after) of one push -- the twin of ``smi_limits_piece_len``: a stream goes on with ``limiter_emitted(n)``
+    samples out; a finished one has emitted all its L samples.  ValueError for a bad argument."""
+    A, R, n_before, length = int(lookahead), int(release), int(n_before), int(length)
+    if not 0 <= A <= 256 or not 0 <= R <= 2048:
+        raise ValueError(f"lookahead={A} outside 0..256 or release={R} outside 0..2048")
+    if n_before < 0 or length < 0:
+        raise ValueError("negative counter or length")
+    n = n_before + length
+    return (n if last else limiter_emitted(n, A, R)) - limiter_emitted(n_before, A, R), n
+
+
 def stream_chunks(token_iter:Iterator[Sequence[int]], scheduler: ChunkScheduler) -> Iterator[List[int]]:
     """Token increments in, ready chunks out (the generator form of the reference loop)."""
     for inc in token_iter:
