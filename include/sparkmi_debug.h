@@ -123,6 +123,7 @@ typedef struct smi_gemm_flags {
   int32_t pg_split_rows;   /* SPARKMI_PG_SPLIT_ROWS */
   int32_t lm_restricted;   /* every row constrained: the restricted lm_head */
   int32_t lm_blocks;       /* blocks of the persistent lm_head */
+  int32_t lm_screen;       /* one greedy row behind the int8 screen; -1 / 0: today's form */
 } smi_gemm_flags;
 typedef struct smi_gemm_form_info {
   char kernel[96];
@@ -188,7 +189,9 @@ int smi_llm_debug_ngram(smi_llm* h, const float* logits_host, int n_rows, const 
  *     its slot, so the step's feature mask has the sampling bit and the lm_head stores the logits rows in the handle's own
  *     buffer, as in a real step (no logits pointer is passed to launch_one).  With SMI_HEAD_FIN such a row's token is the
  *     sampler's: the arg-max, or ANY id that ties with it (TopKLogitsWarper keeps ties).
- *   flags: SMI_HEAD_FIN also runs launch_one(KFIN); SMI_HEAD_POISON fills the handle's logits buffer with quiet NaNs first.
+ *   flags: SMI_HEAD_FIN also runs launch_one(KFIN); SMI_HEAD_POISON fills the handle's logits buffer with quiet NaNs first;
+ *     SMI_HEAD_SCREEN asks for the screened lm_head at any vocabulary size: it runs where a step's would -- one
+ *     row that does not read its logits, no constraint, bf16 weights, at most 32 k tiles -- and `form` says whether it did.
  * Outputs, each nullable: logits_lm / logits_fin [M][vocab_size] = the handle's logits rows after KLM / after KFIN (whatever
  * the buffer holds where nothing was stored); pval / pidx [M][nblk] as the lm_head left them (pcap = entries each holds;
  * fewer than M * nblk: SMI_EINVAL); tokens [M] (SMI_HEAD_FIN).  nblk = the partial columns k_finalize reads (lm_blocks_for);
@@ -196,7 +199,7 @@ int smi_llm_debug_ngram(smi_llm* h, const float* logits_host, int n_rows, const 
  * launches of it the call made (a pass per 32 rows).  After SMI_HEAD_FIN smi_llm_debug_read's buffers 4, 3 and 6 hold the next
  * step's residual rows, first-norm operand triples and sums-of-squares partials of the M rows.  Synchronises; ends the
  * current generation. */
-enum { SMI_HEAD_FIN = 1, SMI_HEAD_POISON = 2 };
+enum { SMI_HEAD_FIN = 1, SMI_HEAD_POISON = 2, SMI_HEAD_SCREEN = 4 };
 typedef struct smi_head_io {
   const float* hidden;
   const smi_allow_params* allow;
@@ -212,6 +215,11 @@ typedef struct smi_head_io {
   char form[32];                            /* out */
 } smi_head_io;
 int smi_llm_debug_head(smi_llm* h, int M, smi_head_io* io);
+/* The screened lm_head's last candidate list and its selection log: tiles[0 .. min(*n_tiles, cap)) = the vocabulary
+ * tiles the last k_lm_select listed, ascending, *n_tiles their count; counts[0 .. min(*n_counts, ccap)) = the list lengths of the
+ * last selections, oldest first (at most 4096 are kept), *n_counts how many there are.  reset != 0 empties the log afterwards.
+ * Either array may be null with its cap 0.  Synchronises.  SMI_EINVAL on a handle without the int8 copy. */
+int smi_llm_debug_lm_screen(smi_llm* h, int32_t* tiles, int cap, int32_t* n_tiles, int32_t* counts, int ccap, int32_t* n_counts, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * Conv kernel forms (csrc/smi_net.h): which instantiation of k_conv / k_convb / k_convbT / k_conv_c1 / k_gemv1 the launch

@@ -1880,6 +1880,12 @@ __device__ __forceinline__ int lm_tile(const int* tlist, int idx) {
   idx = idx < c ? idx : c - 1;
   return tlist[1 + (idx > 0 ? idx : 0)];
 }
+// the screen's list (k_lm_select): entry idx of a list of c entries (c already clamped to NT), the tile index clamped as well
+__device__ __forceinline__ int lm_tile_scr(const int* tlist, int idx, int c, int NT) {
+  idx = idx < c ? idx : c - 1;
+  const int t = tlist[1 + (idx > 0 ? idx : 0)];
+  return t < 0 ? 0 : t < NT ? t : NT - 1;
+}
 // RT epilogue: the four logits of ids n .. n + 3 of the row in `slot`, outside its ranges -> -inf
 __device__ __forceinline__ void lm_mask4(const Ctl* ctl, int slot, int n, float4& s) {
   const AllowRec* a = &ctl->allow[slot];
@@ -1888,7 +1894,9 @@ __device__ __forceinline__ void lm_mask4(const Ctl* ctl, int slot, int n, float4
   if (!allow_has(a, n + 2)) s.z = -INFINITY;
   if (!allow_has(a, n + 3)) s.w = -INFINITY;
 }
-template <int HV, int RT = 0>
+// NM = 1 (with RT): the list is the int8 screen's (k_lm_select) -- the row is unconstrained, so the epilogue masks nothing, and the
+// list's count is clamped to NT.
+template <int HV, int RT = 0, int NM = 0>
 __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups_arg, int m0_launch) {
   constexpr int NTB = 2, NW = 4, U = 8, MT = 1;
   constexpr size_t kHalfBytes = (size_t)NW * NTB * MT * 1024 + 32 * 4 + NTB * 32 * 8;
@@ -1899,7 +1907,7 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups_arg, int m
   const int KT = p.KT, NT = p.NT;
   const int m0 = m0_launch + 16 * half;
   const int M = p.M - m0 < 16 ? (p.M - m0 > 0 ? p.M - m0 : 0) : 16;   // this wave group: rows m0 .. m0 + M - 1 (none: it only keeps the barriers)
-  const int ntl = RT ? p.tlist[0] : 0;                                // RT: vocabulary tiles in the list
+  const int ntl = !RT ? 0 : NM ? (p.tlist[0] < NT ? p.tlist[0] : NT) : p.tlist[0];   // RT: vocabulary tiles in the list
   const int ngroups = RT ? (ntl + NTB - 1) / NTB : ngroups_arg;
   float4* red = (float4*)smem;                                   // [NW][NTB][64]
   float* rarr = (float*)(smem + (size_t)NW * NTB * MT * 1024);
@@ -1925,7 +1933,7 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups_arg, int m
 #pragma unroll
       for (int nb = 0; nb < NTB; ++nb) {
         int nt = g * NTB + nb;
-        nt = RT ? lm_tile(p.tlist, nt) : (nt < NT ? nt : NT - 1);
+        nt = !RT ? (nt < NT ? nt : NT - 1) : NM ? lm_tile_scr(p.tlist, nt, ntl, NT) : lm_tile(p.tlist, nt);
         w[u][nb] = smi_ldw(&p.W[((size_t)nt * KT + j) * 64 + lane]);
       }
     }
@@ -1968,7 +1976,7 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups_arg, int m
     __syncthreads();
     if (wave < NTB) {
       const int nb = wave, nt = RT ? (g * NTB + nb < ntl ? p.tlist[1 + g * NTB + nb] : NT) : g * NTB + nb;
-      if (nt < NT) {
+      if (nt < NT && (!NM || nt >= 0)) {
         float4 s = red[(0 * NTB + nb) * 64 + lane];
 #pragma unroll
         for (int wv = 1; wv < NW; ++wv) {
@@ -1978,7 +1986,7 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups_arg, int m
         s.x *= rn; s.y *= rn; s.z *= rn; s.w *= rn;
         const int n = nt * 16 + 4 * (lane >> 4);
         const bool valid = em < M;
-        if (RT && valid) lm_mask4(p.ctl, p.rows[m0 + em].slot, n, s);
+        if (RT && !NM && valid) lm_mask4(p.ctl, p.rows[m0 + em].slot, n, s);
         if (valid && p.Y) {
           float* y = p.Y + (size_t)(m0 + em) * p.V + n;
           if (n + 0 < p.V) y[0] = s.x;
@@ -2021,6 +2029,230 @@ __global__ __launch_bounds__(256 * HV) void k_lm(GemmP p, int ngroups_arg, int m
   }
 }
 
+
+// ------------------------------------------------------------------------------------------
+// One-row greedy lm_head behind an int8 screen.  The step needs one number of the 297 MB matrix: the lowest id
+// of the maximum.  An int8 copy of the matrix (half the bytes; built once per handle by k_lm_pack8) proves for all but a few
+// 16-row vocabulary tiles that they cannot hold it; k_lm<1, RT, NM> then computes the listed tiles with the full kernel's chains
+// and order, so the partials that reach k_finalize hold the same maximum bits and the same lowest id.
+//   copy:    row v:  s_v = max_k |w_vk| / 127,  q_vk = rint(w_vk / s_v) (int8),  Q_v = sum_k |q_vk|;  tiles of 16 rows x 64 k
+//            (1 KiB, lane l holds row l & 15, k = 16 (l >> 4) .. + 15: the A operand of v_mfma_i32_16x16x64_i8), K zero-padded
+//   operand: x = a X1 + b X2 + r,  a = max|x| / 127,  b = a / 254,  X1, X2 int8,  |r_k| <= b / 2 (columns 0 and 1 of the B operand)
+//   screen:  S_v = s_v (a A1 + b A2),  A1 = sum q X1, A2 = sum q X2 exact in int32;
+//            |S_v - sum_k w_vk x_k| <= B_v = (s_v / 2) |x|_1 + (s_v Q_v) b / 2 + 2^-12 (s_v Q_v) max|x|   (the last term: fp32 rounding
+//            of S_v, of B_v and of k_lm's own sums)
+//   out:     per tile max (S_v + B_v) over its ids below V, per block max (S_v - B_v): a tile is a candidate when its upper bound
+//            reaches the largest lower bound (k_lm_select).  The RMSNorm factor is a positive common factor of the row and is left out.
+// A non-finite operand or max|x| = 0 marks every tile (upper bounds +inf, lower bounds -inf): the recompute then walks them all.
+// ------------------------------------------------------------------------------------------
+struct ScreenP {
+  const uint4* Q8;           // [NT][KT64][64] 16-byte lane pieces of the int8 copy
+  const float* s8;           // [NT * 16] s_v
+  const float* sq8;          // [NT * 16] s_v Q_v
+  const unsigned char* XS;   // the operand's triples (row 0 of M)
+  int M, NT, KT, KT64, V;
+  float* ub;                 // [NT] per-tile upper bounds
+  float* lb;                 // [nlb] per-block lower bounds
+  int nlb;
+  int* list;                 // {count, tiles ascending}
+  int* log;                  // diagnostics: {n, the counts of the last 4096 selections}, or null
+};
+constexpr int kScrKT = 16;   // k tiles of 64 a wave holds: K <= 1024 (the persistent lm_head's range)
+
+// The copy of one vocabulary tile per block (once per handle, outside any capture): thread (r = tid & 15, c = tid >> 4) walks
+// k = c, c + 16, .. of row r of the bf16 tile (lane piece ((k >> 3) & 3) * 16 + r of k tile k >> 5).
+__global__ __launch_bounds__(256) void k_lm_pack8(const uint16_t* W, int KT, int KT64, int V, unsigned char* Q8, float* s8, float* sq8) {
+  __shared__ float smx[4][16];
+  __shared__ int sqs[4][16];
+  const int nt = blockIdx.x, tid = threadIdx.x, r = tid & 15, c = tid >> 4, wave = tid >> 6, K = KT * 32;
+  const int row = nt * 16 + r;
+  auto elem = [&](int k) {
+    return smi_bf16_to_f32(W[(((size_t)nt * KT + (k >> 5)) * 64 + ((k >> 3) & 3) * 16 + r) * 8 + (k & 7)]);
+  };
+  float mx = 0.f;
+  for (int k = c; k < K; k += 16) mx = fmaxf(mx, fabsf(elem(k)));
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  if ((tid & 63) < 16) smx[wave][r] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(smx[0][r], smx[1][r]), fmaxf(smx[2][r], smx[3][r]));
+  if (row >= V) mx = 0.f;   // rows past the vocabulary never count
+  const float s = mx / 127.0f;
+  int qs = 0;
+  for (int k = c; k < K; k += 16) {
+    float q = s > 0.f ? rintf(elem(k) / s) : 0.f;
+    q = fminf(fmaxf(q, -127.f), 127.f);
+    const int qi = (int)q;
+    qs += qi < 0 ? -qi : qi;
+    Q8[((size_t)nt * KT64 + (k >> 6)) * 1024 + (((k & 63) >> 4) * 16 + r) * 16 + (k & 15)] = (unsigned char)(signed char)qi;
+  }
+  qs += __shfl_xor(qs, 16, 64);
+  qs += __shfl_xor(qs, 32, 64);
+  if ((tid & 63) < 16) sqs[wave][r] = qs;
+  __syncthreads();
+  if (tid < 16) {
+    const int Qv = sqs[0][r] + sqs[1][r] + sqs[2][r] + sqs[3][r];
+    s8[row] = s;
+    sq8[row] = s * (float)Qv;
+  }
+}
+
+// U = kScrKT: any K (loads and MFMAs of k tiles past KT64 are skipped, wave-uniform); otherwise KT64 == U exactly.
+template <int U>
+__global__ __launch_bounds__(256) void k_lm_screen(ScreenP p) {
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  constexpr bool ANY = U == kScrKT;
+  __shared__ float xf[kScrKT * 64];
+  __shared__ __attribute__((aligned(16))) signed char x1[kScrKT * 64];
+  __shared__ __attribute__((aligned(16))) signed char x2[kScrKT * 64];
+  __shared__ float rmx[4], rl1[4], rlo[4];
+  __shared__ int rbad[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int NT = p.NT, KT64 = p.KT64;
+  const int nw = (int)gridDim.x * 4, gw = (int)blockIdx.x * 4 + wave;
+  const int g4 = lane >> 4, c = lane & 15;
+  // the wave's first two tiles leave before anything else
+  uint4 wA[U], wB[U];
+  float4 sA, qA, sB, qB;
+  auto load = [&](uint4 (&w)[U], float4& s, float4& q, int t) {
+    t = t < NT ? t : NT - 1;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (!ANY || u < KT64) w[u] = smi_ldw(&p.Q8[((size_t)t * KT64 + u) * 64 + lane]);
+    s = *(const float4*)(p.s8 + (size_t)t * 16 + 4 * g4);
+    q = *(const float4*)(p.sq8 + (size_t)t * 16 + 4 * g4);
+  };
+  if (gw < NT) load(wA, sA, qA, gw);
+  if (gw + nw < NT) load(wB, sB, qB, gw + nw);
+  // ---- the operand: rebuilt from its triples (exact), max|x|, |x|_1, finite?
+  float mx = 0.f, l1 = 0.f;
+  int bad = 0;
+  for (int i = tid; i < kScrKT * 8; i += 256) {   // pieces of 8 k
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = 0.f;
+    if (i < p.KT * 4) {
+      const uint4 h = *(const uint4*)(p.XS + xs_off(i >> 2, 0, i & 3, 0, p.M));
+      const uint4 m = *(const uint4*)(p.XS + xs_off(i >> 2, 1, i & 3, 0, p.M));
+      const uint4 l = *(const uint4*)(p.XS + xs_off(i >> 2, 2, i & 3, 0, p.M));
+      const uint32_t hu[4] = {h.x, h.y, h.z, h.w}, mu[4] = {m.x, m.y, m.z, m.w}, lu[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[2 * e] = (__uint_as_float(hu[e] << 16) + __uint_as_float(mu[e] << 16)) + __uint_as_float(lu[e] << 16);
+        v[2 * e + 1] = (__uint_as_float(hu[e] & 0xffff0000u) + __uint_as_float(mu[e] & 0xffff0000u)) + __uint_as_float(lu[e] & 0xffff0000u);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float av = fabsf(v[e]);
+      bad |= !(av <= 3.4028234664e38f);   // NaN or inf
+      mx = fmaxf(mx, av);
+      l1 += av;
+      xf[i * 8 + e] = v[e];
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    l1 += __shfl_xor(l1, o, 64);
+    bad |= __shfl_xor(bad, o, 64);
+  }
+  if (lane == 0) { rmx[wave] = mx; rl1[wave] = l1; rbad[wave] = bad; }
+  __syncthreads();
+  mx = fmaxf(fmaxf(rmx[0], rmx[1]), fmaxf(rmx[2], rmx[3]));
+  l1 = (rl1[0] + rl1[1]) + (rl1[2] + rl1[3]);
+  const float a = mx / 127.0f, b = a / 254.0f;
+  const bool allc = (rbad[0] | rbad[1] | rbad[2] | rbad[3]) != 0 || !(b > 0.f);   // every tile a candidate (max|x| = 0, or so small that b underflows)
+  for (int k = tid; k < kScrKT * 64; k += 256) {
+    float X1 = 0.f, X2 = 0.f;
+    if (!allc) {
+      const float x = xf[k];
+      X1 = fminf(fmaxf(rintf(x / a), -127.f), 127.f);
+      X2 = fminf(fmaxf(rintf(fmaf(-a, X1, x) / b), -127.f), 127.f);
+    }
+    x1[k] = (signed char)(int)X1;
+    x2[k] = (signed char)(int)X2;
+  }
+  __syncthreads();
+  i32x4 bq[U];   // B operand: column 0 = X1, column 1 = X2, the rest zero; lane (c, g4) holds k = 16 g4 .. + 15 of each k tile
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const i32x4 z = {0, 0, 0, 0};
+    bq[u] = c == 0 ? *(const i32x4*)(x1 + u * 64 + 16 * g4) : c == 1 ? *(const i32x4*)(x2 + u * 64 + 16 * g4) : z;
+  }
+  const float hl1 = 0.5f * l1, hb = 0.5f * b, slack = mx * 0.000244140625f;   // 2^-12 max|x|
+  float lo_run = -INFINITY;
+  auto tile = [&](uint4 (&w)[U], float4& sv, float4& qv, int t) {
+    i32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (!ANY || u < KT64) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, w[u]), bq[u], acc, 0, 0, 0);
+    const float4 s4 = sv, q4 = qv;
+    const int tn = t + 2 * nw;
+    if (tn < NT) load(w, sv, qv, tn);   // the tile after next: in flight under the epilogue and the other buffer's MFMAs
+    // lanes c == 0 hold A1 of rows 4 g4 + r, lanes c == 1 A2
+    const float s[4] = {s4.x, s4.y, s4.z, s4.w}, q[4] = {q4.x, q4.y, q4.z, q4.w};
+    float up = -INFINITY, lo = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int a2 = __shfl_down(acc[r], 1, 64);
+      const float S = s[r] * (a * (float)acc[r] + b * (float)a2);
+      const float Bd = (s[r] * hl1 + q[r] * hb) + q[r] * slack;
+      if (c == 0 && t * 16 + 4 * g4 + r < p.V) { up = fmaxf(up, S + Bd); lo = fmaxf(lo, S - Bd); }
+    }
+    up = fmaxf(up, __shfl_xor(up, 16, 64));
+    up = fmaxf(up, __shfl_xor(up, 32, 64));
+    lo = fmaxf(lo, __shfl_xor(lo, 16, 64));
+    lo = fmaxf(lo, __shfl_xor(lo, 32, 64));
+    if (lane == 0) p.ub[t] = allc ? INFINITY : up;
+    lo_run = fmaxf(lo_run, lo);
+  };
+  for (int t = gw; t < NT; t += 2 * nw) {
+    tile(wA, sA, qA, t);
+    if (t + nw < NT) tile(wB, sB, qB, t + nw);
+  }
+  if (lane == 0) rlo[wave] = lo_run;
+  __syncthreads();
+  if (tid == 0 && (int)blockIdx.x < p.nlb) p.lb[blockIdx.x] = allc ? -INFINITY : fmaxf(fmaxf(rlo[0], rlo[1]), fmaxf(rlo[2], rlo[3]));
+}
+
+// One block: thr = the largest block lower bound; the tiles whose upper bound reaches it, ascending, as {count, tiles}.  A NaN
+// bound lists its tile.  Thread i owns the tiles i * per .. : counts, a block-wide exclusive scan, then the writes.
+__global__ __launch_bounds__(1024) void k_lm_select(ScreenP p) {
+  __shared__ float sthr[16];
+  __shared__ int scnt[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = p.NT;
+  float thr = -INFINITY;
+  for (int i = tid; i < p.nlb; i += 1024) thr = fmaxf(thr, p.lb[i]);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) thr = fmaxf(thr, __shfl_xor(thr, o, 64));
+  if (lane == 0) sthr[wave] = thr;
+  __syncthreads();
+  thr = sthr[0];
+#pragma unroll
+  for (int i = 1; i < 16; ++i) thr = fmaxf(thr, sthr[i]);
+  const int per = (NT + 1023) / 1024, t0 = tid * per, t1 = t0 + per < NT ? t0 + per : NT;
+  int n = 0;
+  for (int t = t0; t < t1; ++t) n += !(p.ub[t] < thr);
+  int inc = n;   // inclusive scan over the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  if (lane == 63) scnt[wave] = inc;
+  __syncthreads();
+  int base = 0, total = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { base += i < wave ? scnt[i] : 0; total += scnt[i]; }
+  int o = base + inc - n;
+  for (int t = t0; t < t1; ++t)
+    if (!(p.ub[t] < thr)) p.list[1 + o++] = t;
+  if (tid == 0) {
+    p.list[0] = total;
+    if (p.log) { const int i = p.log[0]; p.log[1 + (i & 4095)] = total; p.log[0] = i + 1; }
+  }
+}
 
 // lm_head for 17..32 rows per pass: ONE 4-wave group streams the weights once for both m-tiles.  Rows m0..m0+15 keep their
 // operand triples in registers exactly as in k_lm<1>; rows m0+16..m0+31 keep theirs in LDS (86 KB at K = 896: [k tile][3][4][16][16 B]),
@@ -3916,6 +4148,7 @@ struct Switches {
   int pg_forced;        // a SPARKMI_PGEMM_MIN_* is set: kernels picked per launch by the pass's row count, as in round 3
   int attn_pf2;         // bf16 KV: prefill attention on the matrix pipes
   int no_fuse_o;        // one-row decode with the separate o_proj kernel
+  int lm_screen;        // the one-row greedy lm_head's int8 screen: -1 by the size of the lm_head section, 0 / 1 forced (SPARKMI_LM_SCREEN)
 };
 
 }  // namespace
@@ -3979,6 +4212,11 @@ struct smi_llm {
   std::vector<int32_t> host_pctx;   // host staging of the rows an admission writes
   DevBuf<int> tlist;            // device: {count, vocabulary tiles ascending} -- the union of the constrained slots' tiles
   std::vector<int32_t> host_tlist;
+  // The one-row greedy lm_head's int8 screen: the copy of the lm_head section (tiles, s_v, s_v Q_v; built once by
+  // lm_screen_build), the per-tile upper / per-block lower bounds of a step, the candidate list {count, tiles} and, diagnostics,
+  // the counts of the last selections.  scr_on: steps that qualify take it (lm_screened); scr_force: smi_llm_debug_head asked.
+  DevBuf<unsigned char> scr_q8; DevBuf<float> scr_s8, scr_sq8, scr_ub, scr_lb; DevBuf<int> scr_list, scr_log;
+  int scr_ready, scr_on, scr_force, scr_blocks;
   DevBuf<float> lp;             // log-probabilities [max_steps][kMaxRows], beside hist (k_finalize)
   DevBuf<float> lp_part; DevBuf<float2> lp_rowc;   // k_logprob -> k_finalize: [kMaxRows][kLpBlocks] partial sums, [kMaxRows] (max, 1/T)
   DevBuf<uint16_t> phist;       // penalty histories [max_slots][vocab] (k_penalize, k_finalize)
@@ -4160,11 +4398,18 @@ bool lm_restricted(const smi_llm* L, unsigned feat) {
 bool logits_needed(const smi_llm* L, unsigned feat) {
   return (feat & (F_SAMPLE | F_PEN | F_LP | F_BIAS | F_NGRAM)) || ((feat & F_ALLOW) && !lm_restricted(L, feat));
 }
+// One live row whose logits no kernel reads (no sampling, penalty, log-probability, constraint, bias or n-gram row anywhere), bf16
+// weights, the persistent kernel's K range, and the copy built: the step's lm_head is screen + select + listed tiles.
+bool lm_screened(const smi_llm* L, unsigned feat) {
+  return (L->scr_on || L->scr_force) && L->scr_ready && L->B == 1 && L->KTh <= 32 && !L->exact &&
+         !(feat & (F_SAMPLE | F_PEN | F_LP | F_ALLOW | F_BIAS | F_NGRAM));
+}
 // the step-graph cache key: rows | segments << 8 | slots-are-rows << 24 | feature mask << 25 (kFeatBits = 7 bits: 25..31) |
-// restricted lm_head << 32 | steps per replay << 33
+// restricted lm_head << 32 | screened lm_head << 33 | steps per replay << 34
 uint64_t graph_key(const smi_llm* L, unsigned feat, int K) {
   return (uint64_t)L->B | ((uint64_t)L->attn_seg << 8) | ((uint64_t)(L->identity_slots ? 1 : 0) << 24) | ((uint64_t)feat << 25) |
-         ((uint64_t)(lm_restricted(L, feat) ? 1 : 0) << (25 + kFeatBits)) | ((uint64_t)K << (26 + kFeatBits));
+         ((uint64_t)(lm_restricted(L, feat) ? 1 : 0) << (25 + kFeatBits)) | ((uint64_t)(lm_screened(L, feat) ? 1 : 0) << (26 + kFeatBits)) |
+         ((uint64_t)K << (27 + kFeatBits));
 }
 void graphs_flush(smi_llm* L) {
   // an exec is never destroyed while a launch of it may still be running: the stream each exec last ran on drains first
@@ -4273,7 +4518,9 @@ enum { DN_DOWN1 = 1, DN_DOWNS, DN_DOWNC };
 // the persistent lm_head (KT <= 32):  id | k_lm32?, HV (k_lm) or UW (k_lm32), RT (the restricted form), the name smi_llm_debug_head reports
 #define SMI_LM_FORMS(X) \
   X(LM1, 0, 1, 0, "k_lm<1>") X(LM1_RT, 0, 1, 1, "k_lm<1,RT>") X(LM2, 0, 2, 0, "k_lm<2>") X(LM2_RT, 0, 2, 1, "k_lm<2,RT>") \
-  X(LM32_7, 1, 7, 0, "k_lm32<7>") X(LM32_7_RT, 1, 7, 1, "k_lm32<7,RT>") X(LM32_8, 1, 8, 0, "k_lm32<8>") X(LM32_8_RT, 1, 8, 1, "k_lm32<8,RT>")
+  X(LM32_7, 1, 7, 0, "k_lm32<7>") X(LM32_7_RT, 1, 7, 1, "k_lm32<7,RT>") X(LM32_8, 1, 8, 0, "k_lm32<8>") X(LM32_8_RT, 1, 8, 1, "k_lm32<8,RT>") \
+  /* RT = 2: one greedy row behind the int8 screen -- k_lm_screen, k_lm_select, then k_lm<1, RT, NM> on the screen's list */ \
+  X(LM1_SCR, 0, 1, 2, "k_lm_screen+k_lm<1,RT,NM>")
 // exact-weights mode (k_gemm_x: fp32 matrices, one exact fp32 FMA chain per output):  id | PRO, EPI
 #define SMI_X_FORMS(X) \
   X(X_QKV, PRO_NORM, EPI_QKV) X(X_RESID, PRO_PLAIN, EPI_RESID) X(X_GU, PRO_NORM, EPI_SWIGLU) X(X_LM, PRO_NORM, EPI_LM)
@@ -4318,6 +4565,7 @@ struct PickEnv {
   int pg_split_rows;
   int lm_restricted;   // the step's lm_head reads only the constrained rows' tiles
   int lm_blocks;       // blocks of the persistent lm_head
+  int lm_screen;       // one greedy row whose logits nobody reads: the int8 screen in front of the listed-tile lm_head
 };
 // One launch as a pick decided it.
 struct GemmPick {
@@ -4504,6 +4752,10 @@ GemmPick pick_lm(int KT, int NT, int M, const PickEnv& e) {
   const int rt = e.lm_restricted ? 1 : 0;
   const size_t lds = (size_t)4 * 2 * 1024 + 32 * 4 + 2 * 32 * 8;
   k.gx = lm_pass_blocks(e.lm_blocks, M); k.lm_groups = rt ? 0 : (NT + 1) / 2;
+  if (e.lm_screen && M == 1 && !rt) {   // the recompute keeps today's grid: k_finalize reads the same partial columns
+    k.form = GF_LM1_SCR; k.block = 256; k.lds = lds; k.launches = 3; k.lm_groups = 0;
+    return k;
+  }
   if (M <= 16) {
     k.form = GF_LM1 + rt; k.block = 256; k.lds = lds; k.launches = 1;
     return k;
@@ -4539,7 +4791,8 @@ void gemm_form_name(const GemmPick& k, char* out, size_t n) {
              k.nsplit > 1 ? "+k_resid_comb<1,1>" : "");
   } else if (f < GF_LM_END) {
     const LmShape& s = lm_shape(f);
-    snprintf(out, n, "%s<%d,%d>", s.k32 ? "k_lm32" : "k_lm", s.A, s.RT);
+    if (s.RT == 2) snprintf(out, n, "k_lm_screen+k_lm_select+k_lm<%d,1,1>", s.A);
+    else snprintf(out, n, "%s<%d,%d>", s.k32 ? "k_lm32" : "k_lm", s.A, s.RT);
   } else {
     const XShape& s = x_shape(f);
     snprintf(out, n, "k_gemm_x<%d,%d,%d>", s.PRO, s.EPI, k.kv_f32);
@@ -4924,16 +5177,40 @@ int launch_pgemm_form(const smi_llm* L, GemmP p, const GemmPick& k, hipStream_t 
   }
   return SMI_OK;
 }
-// the persistent lm_head: one launch up to 16 rows, else one pass per 32 rows
-template <int K32, int A, int RT>
-int launch_lm_form(const smi_llm*, const GemmP& p, const GemmPick& k, hipStream_t st) {
-  if constexpr (K32) static_cast<void>(LdsBig<k_lm32<A, RT>>::reg);   // 16 rows' operand triples in LDS: 86 KB at K = 896
-  for (int i = 0; i < k.launches; ++i) {
-    if constexpr (K32) hipLaunchKernelGGL((k_lm32<A, RT>), dim3(k.gx), dim3(256), k.lds, st, p, k.lm_groups, 32 * i);
-    else hipLaunchKernelGGL((k_lm<A, RT>), dim3(k.gx), dim3(256 * A), k.lds, st, p, k.lm_groups, 32 * i);
-    SMI_LAUNCH_CHECK();
-  }
+// One greedy row behind the int8 screen: screen, select, the listed tiles -- one chain on the step's stream.  The
+// recompute keeps the pick's grid (k_finalize reads the same partial columns); its groups come from the screen's list.
+int launch_lm_screened(const smi_llm* L, const GemmP& p, const GemmPick& k, hipStream_t st) {
+  SMI_REQUIRE(L->scr_ready && p.M == 1 && p.KT <= 2 * kScrKT && !p.Y, "launch_lm_screened: one greedy row whose logits nobody reads, K <= %d", 64 * kScrKT);
+  ScreenP s;
+  s.Q8 = (const uint4*)L->scr_q8.get(); s.s8 = L->scr_s8; s.sq8 = L->scr_sq8; s.XS = p.XS;
+  s.M = p.M; s.NT = p.NT; s.KT = p.KT; s.KT64 = (p.KT + 1) / 2; s.V = p.V;
+  s.ub = L->scr_ub; s.lb = L->scr_lb; s.nlb = L->scr_blocks; s.list = L->scr_list; s.log = L->scr_log;
+  if (s.KT64 == 14) hipLaunchKernelGGL((k_lm_screen<14>), dim3(s.nlb), dim3(256), 0, st, s);   // K = 896: every load and MFMA unconditional
+  else hipLaunchKernelGGL((k_lm_screen<kScrKT>), dim3(s.nlb), dim3(256), 0, st, s);
+  SMI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_lm_select, dim3(1), dim3(1024), 0, st, s);
+  SMI_LAUNCH_CHECK();
+  GemmP q = p;
+  q.tlist = L->scr_list;
+  hipLaunchKernelGGL((k_lm<1, 1, 1>), dim3(k.gx), dim3(256), k.lds, st, q, 0, 0);
+  SMI_LAUNCH_CHECK();
   return SMI_OK;
+}
+// the persistent lm_head: one launch up to 16 rows, else one pass per 32 rows; RT = 2: the screened one-row form
+template <int K32, int A, int RT>
+int launch_lm_form(const smi_llm* L, const GemmP& p, const GemmPick& k, hipStream_t st) {
+  if constexpr (RT == 2) {
+    static_assert(!K32 && A == 1, "the screened lm_head is the one-row kernel's");
+    return launch_lm_screened(L, p, k, st);
+  } else {
+    if constexpr (K32) static_cast<void>(LdsBig<k_lm32<A, RT>>::reg);   // 16 rows' operand triples in LDS: 86 KB at K = 896
+    for (int i = 0; i < k.launches; ++i) {
+      if constexpr (K32) hipLaunchKernelGGL((k_lm32<A, RT>), dim3(k.gx), dim3(256), k.lds, st, p, k.lm_groups, 32 * i);
+      else hipLaunchKernelGGL((k_lm<A, RT>), dim3(k.gx), dim3(256 * A), k.lds, st, p, k.lm_groups, 32 * i);
+      SMI_LAUNCH_CHECK();
+    }
+    return SMI_OK;
+  }
 }
 // exact-weights mode: p prepared as for k_gemm, W = fp32 [N][K]
 template <int PRO, int EPI>
@@ -5093,6 +5370,8 @@ int launch_one(smi_llm* L, int which, int layer, const RowDesc* rows, int M, flo
       // every row constrained: only the union's tiles (the groups come from p.tlist, the rows' own ranges through p.ctl)
       e.lm_restricted = L->KTh <= 32 && !logits && rows == L->rows && lm_restricted(L, step_feat(L));
       if (e.lm_restricted) { p.tlist = L->tlist; p.ctl = L->ctl; }
+      // one greedy row, nobody reads its logits: the int8 screen lists the tiles that can hold the maximum (same token, same maximum bits)
+      e.lm_screen = M == 1 && !logits && !p.Y && rows == L->rows && lm_screened(L, step_feat(L));
       SMI_REQUIRE(L->KTh <= 32 || (L->NTlm + 3) / 4 <= L->lm_cap, "lm_head partial buffer too small");
       return launch_form(L, p, pick_gemm(L, KLM, M, e), st);
     }
@@ -5441,7 +5720,38 @@ Switches read_switches() {
   }
   { const char* e = smi_env("SPARKMI_ATTN_PF2"); w.attn_pf2 = !(e && e[0] == '0'); }
   w.no_fuse_o = smi_env("SPARKMI_NO_FUSE_O") != nullptr;
+  // the int8 screen of the one-row greedy lm_head: on from kLmScreenMinBytes of lm_head section (the 0.5B shape); SPARKMI_LM_SCREEN=1
+  // forces it on at any size (the tests' tiny shapes), =0 off (A/B at the 0.5B shape)
+  { const char* e = smi_env("SPARKMI_LM_SCREEN"); w.lm_screen = e ? (e[0] != '0' ? 1 : 0) : -1; }
   return w;
+}
+
+// lm_head sections from this size take the int8 screen at one greedy row.  Fixed just under the 0.5B shape's 297.5 MB (166 000 x
+// 896 bf16), the one size it was measured at: the screen trades 149 MB of the stream for two more launches, which a small
+// vocabulary does not pay back.
+constexpr size_t kLmScreenMinBytes = (size_t)256 << 20;
+bool lm_screen_fits(const smi_llm* L) { return !L->exact && L->KTh <= 32; }
+// The int8 copy of the lm_head section and the screen's buffers: once per handle, outside any capture (smi_llm_create; the
+// diagnostics hook of a handle that was created without).  Synchronises.
+int lm_screen_build(smi_llm* L) {
+  if (L->scr_ready) return SMI_OK;
+  SMI_REQUIRE(lm_screen_fits(L), "lm_screen_build: bf16 weights and at most 32 k tiles");
+  const size_t NT = (size_t)L->NTlm, KT64 = (size_t)(L->KTh + 1) / 2;
+  L->scr_blocks = L->lm_blocks;
+  int rc;
+  if ((rc = L->scr_q8.alloc_zero(NT * KT64 * 1024, "lm_head int8 copy")) || (rc = L->scr_s8.alloc(NT * 16 * 4, "lm_head int8 scales")) ||
+      (rc = L->scr_sq8.alloc(NT * 16 * 4, "lm_head int8 row sums")) || (rc = L->scr_ub.alloc(NT * 4, "screen upper bounds")) ||
+      (rc = L->scr_lb.alloc((size_t)L->scr_blocks * 4, "screen lower bounds")) || (rc = L->scr_list.alloc_zero((NT + 1) * 4, "screen list")))
+    return rc;
+#ifdef SMI_DIAG
+  if ((rc = L->scr_log.alloc_zero((size_t)4097 * 4, "screen log"))) return rc;
+#endif
+  hipLaunchKernelGGL(k_lm_pack8, dim3((unsigned)NT), dim3(256), 0, 0, (const uint16_t*)sec(L, SMI_LLM_LM_HEAD, 0), L->KTh, (int)KT64, L->cfg.vocab_size,
+                     (unsigned char*)L->scr_q8, (float*)L->scr_s8, (float*)L->scr_sq8);
+  SMI_LAUNCH_CHECK();
+  SMI_HIP(hipDeviceSynchronize());
+  L->scr_ready = 1;
+  return SMI_OK;
 }
 
 }  // namespace
@@ -5561,6 +5871,9 @@ int smi_llm_create(const smi_llm_cfg* cfg, const void* arena_dev, size_t arena_b
   a(L->poll_host, (size_t)kMaxRows * (1 + (size_t)L->max_steps) * 8, "poll_host");
   // the large LDS window of every LdsBig kernel, once per device and outside any stream capture
   if (!rc) rc = lds_big_opt_in();
+  // the one-row greedy lm_head's int8 screen: the weights do not change, so the copy is built here, once, where steps will take it
+  L->scr_on = lm_screen_fits(L) && (L->sw.lm_screen == 1 || (L->sw.lm_screen < 0 && lay.bytes[SMI_LLM_LM_HEAD] >= kLmScreenMinBytes));
+  if (!rc && L->scr_on) rc = lm_screen_build(L);
   if (!rc && (hipEventCreate(&L->ev0) != hipSuccess || hipEventCreate(&L->ev1) != hipSuccess)) {
     smi_set_error("hipEventCreate failed");
     rc = SMI_EHIP;
@@ -7397,6 +7710,8 @@ int smi_llm_gemm_forms(const smi_llm_cfg* cfg, int M, int layer_pos, const smi_g
   e.pg_split_rows = f.pg_split_rows < 0 ? kPgSplitRows : f.pg_split_rows;
   e.lm_restricted = f.lm_restricted < 0 ? 0 : f.lm_restricted;
   e.lm_blocks = f.lm_blocks < 0 ? (lm_cap < 512 ? lm_cap : 512) : f.lm_blocks;
+  e.lm_screen = f.lm_screen < 0 ? 0 : f.lm_screen;
+  SMI_REQUIRE(!e.lm_screen || (KTh <= 32 && !e.exact && !e.lm_restricted && M == 1), "smi_llm_gemm_forms: the screened lm_head is one unconstrained row's on the persistent kernel");
   SMI_REQUIRE(!e.lm_restricted || (KTh <= 32 && !e.exact), "smi_llm_gemm_forms: the restricted lm_head is the persistent kernels'");
   GemmPick k[5];
   e.has_pf = e.pass == 0;                                   // QKV's helpers: this layer's gate_up slices
@@ -7702,7 +8017,13 @@ int smi_llm_debug_ngram(smi_llm* L, const float* logits_host, int n_rows, const 
 int smi_llm_debug_head(smi_llm* L, int M, smi_head_io* io) {
   SMI_REQUIRE(L && io && io->hidden, "smi_llm_debug_head: null argument");
   SMI_REQUIRE(M >= 1 && M <= L->cfg.max_slots && M <= kMaxRows, "smi_llm_debug_head: M=%d outside 1..max_slots", M);
-  SMI_REQUIRE((io->flags & ~(SMI_HEAD_FIN | SMI_HEAD_POISON)) == 0, "smi_llm_debug_head: flags=%d", io->flags);
+  SMI_REQUIRE((io->flags & ~(SMI_HEAD_FIN | SMI_HEAD_POISON | SMI_HEAD_SCREEN)) == 0, "smi_llm_debug_head: flags=%d", io->flags);
+  if ((io->flags & SMI_HEAD_SCREEN) && lm_screen_fits(L)) SMI_TRY(lm_screen_build(L));   // (outside any capture; nothing if it exists)
+  struct ScrForce {   // the request holds for this call's launches only
+    smi_llm* L;
+    ScrForce(smi_llm* L_, int on) : L(L_) { L->scr_force = on; }
+    ~ScrForce() { L->scr_force = 0; }
+  } scr_force(L, (io->flags & SMI_HEAD_SCREEN) ? 1 : 0);
   const int V = L->cfg.vocab_size, nblk = lm_blocks_for(L, M);
   SMI_REQUIRE((!io->pval && !io->pidx) || (size_t)io->pcap >= (size_t)M * nblk, "smi_llm_debug_head: pval / pidx hold %d entries, %d rows x %d columns needed",
               io->pcap, M, nblk);
@@ -7745,6 +8066,24 @@ int smi_llm_debug_head(smi_llm* L, int M, smi_head_io* io) {
     SMI_TRY(launch_one(L, KFIN, 0, L->rows, M, nullptr, 0));
     SMI_TRY(alone_fetch(L, M, io->logits_fin, io->tokens, nullptr));
   }
+  return SMI_OK;
+}
+
+// Diagnostics: the screened lm_head's last list and the lengths of the last selections (see sparkmi_debug.h).
+int smi_llm_debug_lm_screen(smi_llm* L, int32_t* tiles, int cap, int32_t* n_tiles, int32_t* counts, int ccap, int32_t* n_counts, int reset) {
+  SMI_REQUIRE(L && n_tiles && n_counts && cap >= 0 && ccap >= 0 && (tiles || cap == 0) && (counts || ccap == 0), "smi_llm_debug_lm_screen: bad argument");
+  SMI_REQUIRE(L->scr_ready && L->scr_log, "smi_llm_debug_lm_screen: this handle has no int8 copy of its lm_head");
+  SMI_HIP(hipDeviceSynchronize());
+  std::vector<int32_t> list((size_t)L->NTlm + 1), log(4097);
+  SMI_HIP(hipMemcpy(list.data(), L->scr_list, list.size() * 4, hipMemcpyDeviceToHost));
+  SMI_HIP(hipMemcpy(log.data(), L->scr_log, log.size() * 4, hipMemcpyDeviceToHost));
+  const int nt = list[0] < 0 ? 0 : list[0] < L->NTlm ? list[0] : L->NTlm;
+  *n_tiles = nt;
+  for (int i = 0; i < nt && i < cap; ++i) tiles[i] = list[1 + i];
+  const int total = log[0], kept = total < 4096 ? total : 4096;
+  *n_counts = kept;
+  for (int i = 0; i < kept && i < ccap; ++i) counts[i] = log[1 + ((total - kept + i) & 4095)];
+  if (reset) SMI_HIP(hipMemset(L->scr_log, 0, 4));
   return SMI_OK;
 }
 

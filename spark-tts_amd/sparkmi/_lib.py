@@ -137,7 +137,7 @@ class SeqParams(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
-SMI_HEAD_FIN, SMI_HEAD_POISON = 1, 2
+SMI_HEAD_FIN, SMI_HEAD_POISON, SMI_HEAD_SCREEN = 1, 2, 4
 
 
 class HeadIO(C.Structure):
@@ -151,7 +151,7 @@ class HeadIO(C.Structure):
 class GemmFlags(C.Structure):
     """smi_gemm_flags: the switches a GEMM pick reads (smi_llm_gemm_forms); -1 = what smi_llm_create leaves without a switch"""
     _fields_ = [(n, C.c_int32) for n in ("pass_", "fused", "stamps", "exact", "tune2", "prefetch_mask", "prefetch_rows", "kv_f32",
-                                         "pg_split_rows", "lm_restricted", "lm_blocks")]
+                                         "pg_split_rows", "lm_restricted", "lm_blocks", "lm_screen")]
 
     def __init__(self, **kw):
         super().__init__(**{n: kw.pop(n, -1) for n, _ in self._fields_})
@@ -306,6 +306,7 @@ DEBUG_SYMBOLS = {
     "smi_llm_debug_ngram": (_I, [_VP, _P(C.c_float), _I, _P(C.c_int32), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _I,
                                  _P(C.c_float), _P(C.c_int32)]),
     "smi_llm_debug_head": (_I, [_VP, _I, _P(HeadIO)]),
+    "smi_llm_debug_lm_screen": (_I, [_VP, _P(C.c_int32), _I, _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int32), _I]),
     "smi_llm_debug_set_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_get_kv": (_I, [_VP, _I, _I, _I, _I, _P(C.c_float), _P(C.c_float)]),
     "smi_llm_debug_page_table": (_I, [_VP, _I, _P(C.c_int32), _I, _P(C.c_int32)]),

@@ -1113,11 +1113,13 @@ class SparkLLM:
         return out, tok, fin
 
     def debug_head(self, hidden: np.ndarray, reads: Optional[Sequence[int]] = None, allow: Optional[Sequence[Optional[Sequence]]] = None,
-                   finalize: bool = True, poison: bool = False) -> dict:
+                   finalize: bool = True, poison: bool = False, screen: bool = False) -> dict:
         """The head of a decode step alone (``smi_llm_debug_head``): the final RMSNorm, the lm_head and -- ``finalize`` -- the
         token pick, on ``hidden`` (M, hidden) fp32 = the residual rows leaving the last layer, rows in slots 0 .. M - 1.
         ``reads[m]`` = 1: row m reads its logits (a neutral sampling record); ``allow[m]``: the row's (lo, hi) ranges or None
-        (no constraint); ``poison``: the logits buffer is filled with NaNs first.  Returns {"form", "grid", "block", "launches",
+        (no constraint); ``poison``: the logits buffer is filled with NaNs first; ``screen``: ask for the screened lm_head (the int8
+        screen, the selection, then the listed tiles only -- DESIGN 3.4.3) where a step could take it: "form" says whether it ran,
+        and ``debug_lm_screen`` returns the list it made.  Returns {"form", "grid", "block", "launches",
         "nblk", "logits_lm" (M, vocab), "pval" / "pidx" (M, nblk), and with ``finalize`` "logits_fin", "tokens", "h" (M, hidden),
         "g" (M, hidden: the next first-norm operand, re-summed from its triples), "ss" (M, hidden / 4)}."""
         self._need_diag("debug_head")
@@ -1139,7 +1141,7 @@ class SparkLLM:
                     recs[i].lo[j], recs[i].hi[j] = int(lo), int(hi)
                 recs[i].n_ranges = len(ranges or ())
             io.allow = recs
-        io.flags = (_lib.SMI_HEAD_FIN if finalize else 0) | (_lib.SMI_HEAD_POISON if poison else 0)
+        io.flags = (_lib.SMI_HEAD_FIN if finalize else 0) | (_lib.SMI_HEAD_POISON if poison else 0) | (_lib.SMI_HEAD_SCREEN if screen else 0)
         cap = ((c.vocab_size + 15) // 16 + 3) // 4   # lm_cap: the most partial columns a row has
         lg_lm = np.empty((M, c.vocab_size), np.float32)
         lg_fin = np.empty((M, c.vocab_size), np.float32)
@@ -1161,6 +1163,19 @@ class SparkLLM:
                        g=self._from_triples(self.debug_read(3, M * H * 6), H, M),
                        ss=self.debug_read(6, M * H).view(np.float32).reshape(M, H // 4).copy())
         return out
+
+    def debug_lm_screen(self, reset: bool = False):
+        """The screened lm_head's last candidate list and its selection log (``smi_llm_debug_lm_screen``): (the vocabulary tiles
+        the last selection listed, ascending; the list lengths of the last selections -- at most 4096 -- oldest first).
+        ``reset`` empties the log afterwards."""
+        self._need_diag("debug_lm_screen")
+        nt = (self.cfg.vocab_size + 15) // 16
+        tiles, counts = np.zeros(nt, np.int32), np.zeros(4096, np.int32)
+        n, nc = C.c_int32(0), C.c_int32(0)
+        ip = C.POINTER(C.c_int32)
+        self._lib.check(self._lib.smi_llm_debug_lm_screen(self._h, tiles.ctypes.data_as(ip), nt, C.byref(n), counts.ctypes.data_as(ip), 4096,
+                                                          C.byref(nc), 1 if reset else 0), "smi_llm_debug_lm_screen")
+        return tiles[: n.value].copy(), counts[: nc.value].copy()
 
     def debug_ngram(self, logits: np.ndarray, sizes: Sequence[int], contexts: Sequence[Sequence[int]], prompt_lens: Sequence[int]):
         """The n-gram ban, ``k_penalize`` and ``k_finalize`` alone (``smi_llm_debug_ngram``) on caller rows: ``logits`` [n][vocab]
