@@ -924,6 +924,53 @@ int smi_tempo_rows(const float* in_dev, long long in_stride, const int32_t* n_ho
                    float* out_dev, long long out_stride, int32_t* m_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pitch shift of rows: the frequency ratio of a row changed at an unchanged or separately chosen length, on the device.  It is
+ * the tempo section's stretch followed by the resampler section's polyphase sum and a cut, with the pitch and the tempo
+ * sharing ONE stretch pass.  Free functions like smi_tempo_rows: no handle, no state, asynchronous on the caller's stream, never
+ * synchronising, opt-in.  Every argument of every row is checked before anything is launched: a bad one returns SMI_EINVAL,
+ * names the argument in smi_last_error and leaves the output untouched.  B <= 64, L <= 2^24.
+ *
+ * For a span x[0 .. L) = row[start .. end), a tempo t = tp / tq (> 1: faster) and a pitch ratio r = rp / rq (> 1: higher),
+ * 1 <= tp, tq, rp, rq <= 32767 (host integer arithmetic, smi_pitch_layout):
+ * Stretch.   P / Q = (tp rq) / (tq rp) in lowest terms, within the tempo section's ranges (1 <= P, Q <= 32767,
+ *            1/4 <= P / Q <= 4).  z[0 .. M) is smi_tempo_rows' result on the span at tempo P / Q -- the same N, D and window,
+ *            the same integer search and tie rule, the same places s_k, K of them --, M = ceil(L Q / P).
+ * Resample.  up / down = rq / rp in lowest terms.  With taps h[0 .. 2H] (fp32, caller data; sparkmi/audio.py passes
+ *            resample_taps(up, down) rounded to fp32 once, H = 10 max(up, down)):
+ *                y[k] = sum_j z[j] h[H + k down - j up]
+ *            in smi_rs_resample_rows' order: j ascending from ceil((k down - H) / up), clamped at 0, to
+ *            floor((k down + H) / up), clamped at M - 1 -- the edges are zero-padded against z's own length M --, fp32, one
+ *            accumulator, the product and the sum rounded separately (no FMA).
+ * Length.    The row's output is y[0 .. n_out), n_out = ceil(L tq / tp): what smi_tempo_rows alone gives at tp / tq, and L
+ *            without a tempo.  ceil(M up / down) >= n_out (refused otherwise; for every hundredth r in [0.5, 2] and t in
+ *            [0.5, 2] the surplus is 0 to 2 samples); the surplus is cut.
+ * Consequences.  At rp = rq the row is smi_tempo_rows' row at tp / tq bit for bit, and at tp = tq too it is the span bit for
+ * bit.  P, Q, M, K, up, down and n_out depend on L, tp, tq, rp, rq and N alone.  The formants move with the pitch: this is the
+ * stretch-and-resample construction, not a pitch-synchronous one.
+ *
+ * Two launches whatever B, no atomics.  k_tempo_search as in the tempo section, with P / Q per row.  k_pitch_ola, grid (tiles of
+ * 1024 final output samples, rows): a block stages its row's taps in LDS, computes the stretched samples its tile's sums reach
+ * -- at most (1023 down + 2 H) / up + 3 of them, each by the tempo section's overlap-add from the places and the input --
+ * straight into LDS, and after one barrier forms its sums; z never exists in memory.  A row at rp = rq writes the overlap-add
+ * itself.  A row whose taps plus one tile's stretched window exceed 16384 floats of LDS is refused (the worst hundredth ratio,
+ * 199/100, needs 6059).  Guarantee: a row's places and samples depend, bit for bit, on its span and its own tp, tq, rp, rq, N,
+ * D, window and taps alone -- not on B, the row's place, the strides, what lies outside the span or the grid. */
+/* n_out of a span of L samples (0 .. 2^24); P_out, Q_out, M_out, K_out, up_out, down_out (each may be null) receive the rest of
+ * the plan.  -1 for a bad argument.  Pure host. */
+long long smi_pitch_layout(long long L, int tp, int tq, int rp, int rq, int N, int* P_out, int* Q_out, long long* M_out, long long* K_out,
+                           int* up_out, int* down_out);
+/* in_dev, in_stride, n_host, start_host, end_host, B, N, D, win_dev as in smi_tempo_rows; tp_host / tq_host / rp_host / rq_host
+ * [B]: every row's own tempo and pitch ratio; taps_dev [taps_len] f32: a pool of taps on the device, of which row b uses
+ * n_taps_host[b] (odd, >= 3) from tap_off_host[b] on -- n_taps_host[b] = 0, and only 0, for a row whose rp / rq is 1/1; pos_dev
+ * [B][pos_stride] int32 receives the stretch's s_k, then zeros to pos_stride (>= the most frames of a row, >= 1); out_dev
+ * [B][out_stride] f32 receives the row's n_out samples, then zeros to out_stride (>= the longest output, >= 1, <= 2^26), and
+ * must not overlap in_dev or taps_dev; m_host [B] (may be null) receives every n_out, filled before the launch. */
+int smi_pitch_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                   const int32_t* tp_host, const int32_t* tq_host, const int32_t* rp_host, const int32_t* rq_host, int N, int D,
+                   const double* win_dev, const float* taps_dev, long long taps_len, const int32_t* tap_off_host, const int32_t* n_taps_host,
+                   int32_t* pos_dev, long long pos_stride, float* out_dev, long long out_stride, int32_t* m_host, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tempo of joined streams: the arithmetic above with state carried from push to push, so that a stream whose input arrives in
  * chunks (a joined stream of smi_join at 1/1) leaves in pieces before it has ended.  No sample is defined here: the
  * concatenation of a stream's pieces is smi_tempo_rows of its whole input.  What is new is the state and the rule for when an

@@ -27,7 +27,10 @@
 //   k_tempo_search, k_tempo_ola  pitch-preserving time-scale change of rows (smi_tempo_rows; WSOLA): one block per row walks the
 //                frames in order and, where a frame is searched, stages the quantised target and candidate samples in LDS as
 //                int16 and sums exact squared differences in 64-bit integers; the overlap-add is then parallel.  No atomics.
-//   k_tempos_search, k_tempos_ola  the same for joined streams (smi_tempos_*): the frames a push makes final, walked over the
+//   k_pitch_ola                  the pitch shift of rows (smi_pitch_rows), behind k_tempo_search: a block computes the stretched
+//                samples of its tile's window with tp_ola straight into LDS and resamples them with rs_tile_sums; the stretched
+//                signal never reaches memory.  No atomics.
+//   k_tempos_search, k_tempos_ola  the time-scale change for joined streams (smi_tempos_*): the frames a push makes final, walked over the
 //                stream's history followed by its new chunk with the batch kernels' own device functions (tp_place, tp_ola);
 //                histories and last places live in two sets a stream uses in turn, as the joiner's state does.
 //   k_louds_seg, k_louds_carry, k_louds_energy, k_louds_knots, k_louds_apply   loudness of joined streams (smi_louds_*): the
@@ -1078,6 +1081,64 @@ __global__ __launch_bounds__(RS_BLOCK) void k_tempo_ola(TpArgs a, int N, const f
     }
     y[m] = v;
   }
+}
+
+// ---- pitch shift of rows (smi_pitch_rows): the stretch above at P / Q, resampled by up / down and cut to n_out
+struct PtRow {
+  int32_t n_out, up, down, half, tap_off;   // half = H >= 1: taps h[0 .. 2H]; up == down == 1: no pitch ratio (half and tap_off are then 0 and unused)
+};
+struct PtArgs {
+  PtRow r[RS_MAX_ROWS];
+};
+
+// sample m < M of the stretched span: k_tempo_ola's value
+template <class Src>
+__device__ __forceinline__ float pt_stretched(const Src& x, long long m, int H, const int32_t* __restrict__ ps, const double* __restrict__ win) {
+  const int k = (int)(m / H), j = (int)(m - (long long)k * H);
+  float v = 0.f;
+  if (k == 0) (void)x.get(m, v);
+  else v = tp_ola(x, j, H, ps[k], ps[k - 1], win);
+  return v;
+}
+
+// grid (tiles of RS_TILE final output samples, rows).  A block stages its row's taps, computes the stretched samples its tile's
+// sums reach -- at most rs_window() of them, each with tp_ola from the places and the input -- straight into LDS, and after one
+// barrier sums its outputs with k_rs_rows' loop (rs_tile_sums) against the stretched length M.  The stretched signal is never
+// written to memory.  A row without a pitch ratio writes the overlap-add itself, as k_tempo_ola does.  Zeros from n_out to the
+// stride.
+__global__ __launch_bounds__(RS_BLOCK) void k_pitch_ola(TpArgs a, PtArgs f, int N, const float* __restrict__ in, long long in_stride,
+                                                        const double* __restrict__ win, const float* __restrict__ taps,
+                                                        const int32_t* __restrict__ pos, long long pos_stride, float* __restrict__ out,
+                                                        long long out_stride) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const TpRow r = a.r[blockIdx.y];
+  const PtRow g = f.r[blockIdx.y];
+  const long long k0 = (long long)blockIdx.x * RS_TILE;
+  if (k0 >= out_stride) return;
+  const TpSpan x = {in + (size_t)blockIdx.y * in_stride + r.start, r.len};
+  const int32_t* ps = pos + (size_t)blockIdx.y * pos_stride;
+  float* y = out + (size_t)blockIdx.y * out_stride;
+  const int tid = threadIdx.x, H = N / 2;
+  if (k0 >= g.n_out) {   // padding past the row's length: zeros
+    for (int i = tid; i < RS_TILE && k0 + i < out_stride; i += RS_BLOCK) y[k0 + i] = 0.f;
+    return;
+  }
+  if (g.up == 1 && g.down == 1) {   // no pitch ratio: n_out == M, the stretched samples are the row
+    for (int i = tid; i < RS_TILE && k0 + i < out_stride; i += RS_BLOCK) y[k0 + i] = k0 + i < g.n_out ? pt_stretched(x, k0 + i, H, ps, win) : 0.f;
+    return;
+  }
+  const int ntaps = 2 * g.half + 1;
+  float* ht = rs_lds;
+  float* zw = rs_lds + ntaps;
+  const int klast = (int)min(k0 + RS_TILE, (long long)g.n_out) - 1;
+  const int j0 = rs_jlo((int)k0 * g.down, g.up, g.half);
+  const int j1 = min(rs_jhi(klast * g.down, g.up, g.half), r.m - 1);
+  const int nwin = j1 - j0 + 1;   // <= rs_window(): checked on the host
+  const float* h = taps + g.tap_off;
+  for (int i = tid; i < ntaps; i += RS_BLOCK) ht[i] = h[i];
+  for (int i = tid; i < nwin; i += RS_BLOCK) zw[i] = pt_stretched(x, (long long)j0 + i, H, ps, win);
+  __syncthreads();
+  rs_tile_sums(ht, zw, j0, r.m - 1, (int)k0, g.n_out, g.up, g.down, g.half, y + k0, (int)min((long long)RS_TILE, out_stride - k0));
 }
 
 // ---- time-scale change of joined streams (smi_tempos_*)
@@ -2372,6 +2433,125 @@ int smi_tempo_rows(const float* in_dev, long long in_stride, const int32_t* n_ho
   SMI_LAUNCH_CHECK();
   const int tiles = (int)((out_stride + TP_TILE - 1) / TP_TILE);
   hipLaunchKernelGGL(k_tempo_ola, dim3(tiles, B), dim3(RS_BLOCK), 0, s, A, N, in_dev, in_stride, win_dev, pos_dev, pos_stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// ---- pitch shift of rows (smi_pitch_*)
+struct PtPlan {
+  int P, Q, up, down;
+  long long M, K, n_out;
+};
+
+static long long pt_gcd(long long a, long long b) {
+  while (b) { const long long t = a % b; a = b; b = t; }
+  return a;
+}
+
+// the plan of a span of L samples at tempo tp / tq and pitch ratio rp / rq: the stretch P / Q = (tp rq) / (tq rp) in lowest
+// terms with its M and K, the resampling up / down = rq / rp in lowest terms, and n_out = ceil(L tq / tp); false for a bad argument
+static bool pt_plan(long long L, int tp, int tq, int rp, int rq, int N, PtPlan& pl) {
+  if (tp < 1 || tp > 32767 || tq < 1 || tq > 32767 || rp < 1 || rp > 32767 || rq < 1 || rq > 32767) return false;
+  const long long a = (long long)tp * rq, b = (long long)tq * rp, g = pt_gcd(a, b), gr = pt_gcd(rp, rq);
+  if (a / g > 32767 || b / g > 32767) return false;
+  pl.P = (int)(a / g); pl.Q = (int)(b / g);
+  pl.up = (int)(rq / gr); pl.down = (int)(rp / gr);
+  if (!tp_layout(L, pl.P, pl.Q, N, pl.M, pl.K)) return false;
+  pl.n_out = (L * tq + tp - 1) / tp;
+  return true;
+}
+
+extern "C" {
+
+long long smi_pitch_layout(long long L, int tp, int tq, int rp, int rq, int N, int* P_out, int* Q_out, long long* M_out, long long* K_out,
+                           int* up_out, int* down_out) {
+  PtPlan pl;
+  if (!pt_plan(L, tp, tq, rp, rq, N, pl)) return -1;
+  if (P_out) *P_out = pl.P;
+  if (Q_out) *Q_out = pl.Q;
+  if (M_out) *M_out = pl.M;
+  if (K_out) *K_out = pl.K;
+  if (up_out) *up_out = pl.up;
+  if (down_out) *down_out = pl.down;
+  return pl.n_out;
+}
+
+int smi_pitch_rows(const float* in_dev, long long in_stride, const int32_t* n_host, const int32_t* start_host, const int32_t* end_host, int B,
+                   const int32_t* tp_host, const int32_t* tq_host, const int32_t* rp_host, const int32_t* rq_host, int N, int D,
+                   const double* win_dev, const float* taps_dev, long long taps_len, const int32_t* tap_off_host, const int32_t* n_taps_host,
+                   int32_t* pos_dev, long long pos_stride, float* out_dev, long long out_stride, int32_t* m_host, void* stream) {
+  SMI_REQUIRE(N >= 16 && N <= TP_MAX_N && !(N & 1), "smi_pitch_rows: N=%d must be even in 16..%d", N, TP_MAX_N);
+  SMI_REQUIRE(D >= 0 && D <= TP_MAX_D, "smi_pitch_rows: D=%d outside 0..%d", D, TP_MAX_D);
+  SMI_REQUIRE(in_dev && n_host && tp_host && tq_host && rp_host && rq_host && win_dev && tap_off_host && n_taps_host && pos_dev && out_dev,
+              "smi_pitch_rows: null argument");
+  SMI_REQUIRE(taps_len >= 0 && (taps_dev || !taps_len), "smi_pitch_rows: taps_len=%lld needs a pool (taps_dev is null)", taps_len);
+  LdArgs S;
+  int n_max = 0, len_max = 0;
+  const int rc = ld_rows_args("smi_pitch_rows", n_host, start_host, end_host, B, in_stride, S, n_max, len_max);
+  if (rc) return rc;
+  TpArgs A;
+  PtArgs F;
+  long long m_max = 0, k_max = 0;
+  size_t lds = 0;
+  for (int b = 0; b < B; ++b) {
+    const int tp = tp_host[b], tq = tq_host[b], rp = rp_host[b], rq = rq_host[b];
+    SMI_REQUIRE(tp >= 1 && tp <= 32767, "smi_pitch_rows: tp[%d]=%d outside 1..32767", b, tp);
+    SMI_REQUIRE(tq >= 1 && tq <= 32767, "smi_pitch_rows: tq[%d]=%d outside 1..32767", b, tq);
+    SMI_REQUIRE(rp >= 1 && rp <= 32767, "smi_pitch_rows: rp[%d]=%d outside 1..32767", b, rp);
+    SMI_REQUIRE(rq >= 1 && rq <= 32767, "smi_pitch_rows: rq[%d]=%d outside 1..32767", b, rq);
+    PtPlan pl;
+    SMI_REQUIRE(pt_plan(S.r[b].len, tp, tq, rp, rq, N, pl),
+                "smi_pitch_rows: row %d has no layout (smi_pitch_layout): the stretch (tp[%d] rq[%d]) / (tq[%d] rp[%d]) = (%d * %d) / (%d * %d) "
+                "must lie in 1/4..4 with terms up to 32767", b, b, b, b, b, tp, rq, tq, rp);
+    TpRow& r = A.r[b];
+    r.start = S.r[b].start; r.len = S.r[b].len; r.p = pl.P; r.q = pl.Q; r.m = (int32_t)pl.M; r.frames = (int32_t)pl.K;
+    PtRow& g = F.r[b];
+    g.n_out = (int32_t)pl.n_out; g.up = pl.up; g.down = pl.down; g.half = 0; g.tap_off = 0;
+    const int nt = n_taps_host[b], off = tap_off_host[b];
+    if (pl.up == 1 && pl.down == 1) {
+      SMI_REQUIRE(nt == 0, "smi_pitch_rows: n_taps[%d]=%d must be 0 for a row whose pitch ratio is 1/1", b, nt);
+    } else {
+      SMI_REQUIRE(nt >= 3 && (nt & 1), "smi_pitch_rows: n_taps[%d]=%d must be odd and at least 3 (taps h[0 .. 2H], H >= 1) for a row at rp/rq = %d/%d",
+                  b, nt, rp, rq);
+      SMI_REQUIRE(off >= 0 && (long long)off + nt <= taps_len, "smi_pitch_rows: tap_off[%d]=%d with n_taps[%d]=%d leaves the pool of taps_len=%lld",
+                  b, off, b, nt, taps_len);
+      const long long fl = (long long)nt + rs_window(pl.up, pl.down, nt / 2);
+      SMI_REQUIRE(fl <= RS_LDS_FLOATS, "smi_pitch_rows: n_taps[%d]=%d with up/down = %d/%d needs %lld floats of LDS a tile, above %d", b, nt,
+                  pl.up, pl.down, fl, RS_LDS_FLOATS);
+      SMI_REQUIRE(pl.M * pl.up < (1LL << 31), "smi_pitch_rows: M * up = %lld of row %d reaches 2^31", pl.M * pl.up, b);
+      SMI_REQUIRE(pl.n_out * pl.down < (1LL << 31), "smi_pitch_rows: n_out * down = %lld of row %d reaches 2^31", pl.n_out * pl.down, b);
+      SMI_REQUIRE(rs_out_len(pl.M, pl.up, pl.down) >= pl.n_out, "smi_pitch_rows: row %d: the stretched span resamples to %lld samples, below n_out=%lld",
+                  b, rs_out_len(pl.M, pl.up, pl.down), pl.n_out);
+      g.half = nt / 2; g.tap_off = off;
+      if ((size_t)fl > lds) lds = (size_t)fl;
+    }
+    if (pl.n_out > m_max) m_max = pl.n_out;
+    if (pl.K > k_max) k_max = pl.K;
+  }
+  SMI_REQUIRE(out_stride >= 1 && out_stride >= m_max && out_stride <= TP_MAX_OUT,
+              "smi_pitch_rows: out_stride=%lld outside max(1, the longest output row %lld)..%d", out_stride, m_max, TP_MAX_OUT);
+  SMI_REQUIRE(pos_stride >= 1 && pos_stride >= k_max && pos_stride <= TP_MAX_OUT,
+              "smi_pitch_rows: pos_stride=%lld outside max(1, the most frames of a row %lld)..%d", pos_stride, k_max, TP_MAX_OUT);
+  {
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + ((size_t)(B - 1) * in_stride + n_max) * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_pitch_rows: out_dev overlaps in_dev");
+    const char* t0 = (const char*)taps_dev;
+    const char* t1 = t0 + (size_t)taps_len * sizeof(float);
+    SMI_REQUIRE(!taps_len || t1 <= o0 || o1 <= t0, "smi_pitch_rows: out_dev overlaps taps_dev");
+  }
+  if (m_host)
+    for (int b = 0; b < B; ++b) m_host[b] = F.r[b].n_out;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_tempo_search, dim3(B), dim3(TP_BLOCK), 0, s, A, N, D, in_dev, in_stride, pos_dev, pos_stride);
+  SMI_LAUNCH_CHECK();
+  const int tiles = (int)((out_stride + RS_TILE - 1) / RS_TILE);
+  hipLaunchKernelGGL(k_pitch_ola, dim3(tiles, B), dim3(RS_BLOCK), lds * sizeof(float), s, A, F, N, in_dev, in_stride, win_dev, taps_dev, pos_dev,
+                     pos_stride, out_dev, out_stride);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

@@ -265,6 +265,11 @@ SYMBOLS = {
     "smi_tempo_layout": (C.c_longlong, [C.c_longlong, _I, _I, _I, _P(C.c_longlong)]),
     "smi_tempo_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int32), _P(C.c_int32), _I, _I,
                             _VP, _VP, C.c_longlong, _VP, C.c_longlong, _P(C.c_int32), _VP]),
+    "smi_pitch_layout": (C.c_longlong, [C.c_longlong, _I, _I, _I, _I, _I, _P(_I), _P(_I), _P(C.c_longlong), _P(C.c_longlong), _P(_I),
+                                        _P(_I)]),
+    "smi_pitch_rows": (_I, [_VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                            _P(C.c_int32), _I, _I, _VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _VP, C.c_longlong, _VP, C.c_longlong,
+                            _P(C.c_int32), _VP]),
     "smi_tempos_create": (_I, [_I, _I, _I, _I, _P(C.c_double), _P(_VP)]),
     "smi_tempos_destroy": (_I, [_VP]),
     "smi_tempos_open": (_I, [_VP, _I, _I, _I]),

@@ -26,6 +26,10 @@ search is exact integer arithmetic, so the device is held to ``tests/tempo_ref.p
 ``StreamTempo`` (``smi_tempos_*``) is its streaming form: the frame places and an input history are kept on the device per
 stream, and the pieces' concatenation is ``tempo_rows`` of the whole stream bit for bit, whatever the chunking.
 
+``DeviceAudio.pitch_rows`` (``smi_pitch_rows``) moves the pitch of rows at an unchanged -- or, with a tempo, separately chosen --
+length: that stretch at (tp rq) / (tq rp), then the resampler's sum at rq / rp inside the same launch and a cut; the device is
+held to ``tests/pitch_ref.py`` bit for bit.  ``pitch_ratio`` gives the frequency ratio of a number of semitones.
+
 ``StreamLoudness`` (``smi_louds_*``) levels joined streams while they arrive.  It is not ``loudness_rows`` chunk by chunk: the gain
 follows the running integrated loudness, knot by knot on the stream's absolute hops, at a bounded rate and under the ceiling.
 """
@@ -174,6 +178,25 @@ def tempo_ratio(tempo: float) -> Tuple[int, int]:
     if not TEMPO_MIN <= tempo <= TEMPO_MAX:
         raise ValueError(f"tempo must lie in [{TEMPO_MIN}, {TEMPO_MAX}], not {tempo!r}")
     p = int(round(float(tempo) * 100))
+    g = math.gcd(p, 100)
+    return p // g, 100 // g
+
+
+PITCH_MIN, PITCH_MAX = -12.0, 12.0
+PITCH_TAP_CACHE = 32     # ratios whose fp32 taps ``DeviceAudio.pitch_rows`` keeps on the device at a time
+PITCH_TAP_SLOT = 4096    # floats a cached ratio may take: the longest filter of a hundredth ratio (199/100) has 3981 taps
+
+
+def pitch_ratio(semitones: float) -> Tuple[int, int]:
+    """(p, q) in lowest terms, the frequency ratio of a shift of ``semitones`` in [-12.0, 12.0] (> 0: higher) to a hundredth:
+    ``round(2 ** (semitones / 12) * 100) / 100``.  +2 -> 28/25, -2 -> 89/100, +7 -> 3/2, +12 -> 2/1.  The resolution is a
+    hundredth of the ratio: about 9 cents near 1.0 and about 17 cents at 0.5, so shifts of a few cents round to 1/1."""
+    if (isinstance(semitones, bool) or not isinstance(semitones, (int, float, np.integer, np.floating))
+            or not math.isfinite(semitones)):
+        raise ValueError(f"pitch_shift must be a finite number, not {semitones!r}")
+    if not PITCH_MIN <= semitones <= PITCH_MAX:
+        raise ValueError(f"pitch_shift must lie in [{PITCH_MIN}, {PITCH_MAX}] semitones, not {semitones!r}")
+    p = int(round(2.0 ** (float(semitones) / 12.0) * 100))
     g = math.gcd(p, 100)
     return p // g, 100 // g
 
@@ -508,6 +531,91 @@ class DeviceAudio:
                                                  i32(a[1] for a in pq), N, D, C.c_void_p(win.data_ptr() if win is not None else 0),
                                                  C.c_void_p(pos.data_ptr()), pos.shape[1], C.c_void_p(out.data_ptr()), out.shape[1],
                                                  got, self._stream()), "smi_tempo_rows")
+        return out, list(got)[:B], pos
+
+    def _pitch_taps(self, ratios: Sequence[Tuple[int, int]]):
+        """(pool tensor, {(up, down): (offset, count)}) with the fp32 taps of every (up, down) in ``ratios``: the object's own
+        small cache, apart from the resampler handle's registration pool, which a long-lived server with per-request pitches
+        must not fill.  The pool has ``PITCH_TAP_CACHE`` slots and is allocated once; a new ratio that finds no free slot takes
+        the slot of the ratio that has been unused the longest and is not of this call.  The copy into a slot is enqueued on
+        the stream the earlier launches that read the slot were enqueued on, so it runs behind them and nothing waits -- which
+        holds only while every ``pitch_rows`` call of one ``DeviceAudio`` is made on the same HIP stream: keep them on one
+        stream (as the ``Stream*`` classes ask), or give each stream a ``DeviceAudio`` of its own; a copy enqueued on another
+        stream could overwrite taps that a launch in flight still reads.  Only a call with more distinct ratios than the pool
+        has slots gets a larger pool."""
+        import torch
+        cache = self.__dict__.setdefault("_pitch_cache", {"pool": None, "where": {}})
+        keys = list(dict.fromkeys(ratios))
+        if cache["pool"] is None or len(keys) > cache["pool"].numel() // PITCH_TAP_SLOT:
+            slots = max(PITCH_TAP_CACHE, len(keys))
+            cache.update(pool=torch.empty((slots * PITCH_TAP_SLOT,), dtype=torch.float32, device=self.device), where={})
+        where = cache["where"]
+        slots = cache["pool"].numel() // PITCH_TAP_SLOT
+        for k in keys:
+            if k in where:
+                where[k] = where.pop(k)      # (used now: to the end of the order)
+                continue
+            if len(where) < slots:
+                off = len(where) * PITCH_TAP_SLOT
+            else:
+                off = where.pop(next(o for o in where if o not in keys))[0]
+            t = np.ascontiguousarray(resample_taps(*k).astype(np.float32))
+            cache["pool"][off: off + t.size].copy_(torch.from_numpy(t))
+            where[k] = (off, t.size)
+        return cache["pool"], where
+
+    def pitch_rows(self, x, n: Sequence[int], tempos: Sequence, pitches: Sequence, spans: Optional[Sequence[Tuple[int, int]]] = None,
+                   out=None, sr: int = 16000, frame: Optional[Tuple[int, int]] = None):
+        """A pitch shift of rows, with a tempo in the same pass (include/sparkmi.h, smi_pitch_rows): row b's span is stretched
+        once by WSOLA at tempo (tp rq) / (tq rp), resampled by rq / rp on the way out and cut to ``tempo_len(L, tp, tq)``
+        samples -- its own length where it has no tempo.  ``x``, ``n``, ``spans``, ``sr``, ``frame`` and ``out`` as in
+        ``tempo_rows``; ``tempos``: per row None (1/1), a number in [0.5, 2.0] (``tempo_ratio``) or a (p, q) pair; ``pitches``:
+        per row None (1/1), a number of semitones in [-12, 12] (``pitch_ratio``; > 0: higher) or the frequency ratio as a
+        (p, q) pair.  A row at pitch 1/1 is ``tempo_rows``' row bit for bit.  The formants move with the pitch.  Returns (y --
+        row b holds its ``m[b]`` samples, then zeros --, m, pos [B][frames] int32 on the device: the stretch's frame places).
+        Two launches, nothing waits and nothing is copied back; a ratio's taps are copied to the device on its first use, into
+        a cache of ``PITCH_TAP_CACHE`` slots that are taken over in turn: make all calls of one object on one HIP stream."""
+        import torch
+        B = self._rows(x, n, "pitch_rows")
+        st, en = self._spans(spans, B)
+        if len(tempos) != B or len(pitches) != B:
+            raise ValueError("one tempo and one pitch per row")
+        pair = lambda v, f: (1, 1) if v is None else (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else f(v)   # noqa: E731
+        tt = [pair(t, tempo_ratio) for t in tempos]
+        rr = [pair(r, pitch_ratio) for r in pitches]
+        N, D = tempo_frame(sr) if frame is None else (int(frame[0]), int(frame[1]))
+        lens = [int(s[1]) - int(s[0]) for s in spans] if spans is not None else [int(v) for v in n]
+        frames, up, down = C.c_longlong(), C.c_int(), C.c_int()
+        m_max = k_max = 0
+        updown: List[Optional[Tuple[int, int]]] = []
+        for (tp, tq), (rp, rq), L in zip(tt, rr, lens):   # (a bad row: the call below names it)
+            m = self._lib.smi_pitch_layout(max(0, L), tp, tq, rp, rq, N, None, None, None, C.byref(frames), C.byref(up), C.byref(down))
+            updown.append((up.value, down.value) if m >= 0 and (up.value, down.value) != (1, 1) else None)
+            if m >= 0:
+                m_max, k_max = max(m_max, int(m)), max(k_max, int(frames.value))
+            if updown[-1] is not None and 20 * max(updown[-1]) + 1 > PITCH_TAP_SLOT:
+                raise ValueError(f"pitch_rows: the pitch ratio {rp}/{rq} needs a filter of {20 * max(updown[-1]) + 1} taps, above the "
+                                 f"{PITCH_TAP_SLOT} a cached ratio may take (ratios of hundredths need at most 3981)")
+        pool, where = self._pitch_taps([k for k in updown if k is not None]) if any(k is not None for k in updown) else (None, {})
+        wins = self.__dict__.setdefault("_tempo_windows", {})
+        if N not in wins and N >= 2 and N % 2 == 0:
+            wins[N] = torch.from_numpy(tempo_window(N)).to(self.device)
+        win = wins.get(N)
+        if out is None:
+            out = torch.empty((max(1, B), max(1, m_max)), dtype=torch.float32, device=self.device)
+        elif out.dim() != 2 or out.shape[0] != B or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("pitch_rows: out must be a contiguous [B][out_stride] float32 tensor on the device")
+        pos = torch.empty((max(1, B), max(1, k_max)), dtype=torch.int32, device=self.device)
+        i32 = lambda v: (C.c_int32 * B)(*[int(a) for a in v])   # noqa: E731
+        got = (C.c_int32 * max(1, B))()
+        self._lib.check(self._lib.smi_pitch_rows(C.c_void_p(x.data_ptr()), x.shape[1], i32(n), st, en, B, i32(a[0] for a in tt),
+                                                 i32(a[1] for a in tt), i32(a[0] for a in rr), i32(a[1] for a in rr), N, D,
+                                                 C.c_void_p(win.data_ptr() if win is not None else 0),
+                                                 C.c_void_p(pool.data_ptr() if pool is not None else 0), 0 if pool is None else pool.numel(),
+                                                 i32(where[k][0] if k is not None else 0 for k in updown),
+                                                 i32(where[k][1] if k is not None else 0 for k in updown),
+                                                 C.c_void_p(pos.data_ptr()), pos.shape[1], C.c_void_p(out.data_ptr()), out.shape[1],
+                                                 got, self._stream()), "smi_pitch_rows")
         return out, list(got)[:B], pos
 
 

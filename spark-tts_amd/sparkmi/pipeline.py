@@ -15,7 +15,9 @@ utterances (the output at a programme loudness after BS.1770, measured and scale
 (a pitch-preserving change of the speaking rate, 0.5 .. 2.0, on the device before the loudness stage) and, with
 ``joined=True``, on the two streaming calls (the same arithmetic with its state carried across the chunks on the device);
 ``limiter`` on the calls that return whole utterances (a look-ahead true-peak limiter behind the loudness stage, on the device)
-and ``stream_limiter``, with ``joined=True``, on the two streaming calls (the same limiter with its input carried across the chunks).
+and ``stream_limiter``, with ``joined=True``, on the two streaming calls (the same limiter with its input carried across the chunks);
+``pitch_shift`` on the calls that return whole utterances (semitones for any voice, in the tempo stage's place: one stretch pass
+serves both, a resampler follows inside the same launch; the streaming calls refuse it).
 """
 from __future__ import annotations
 
@@ -27,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import LIMITER_MODES, PEAK_CEILING, check_limiter, check_loudness, tempo_len, tempo_ratio
+from .audio import LIMITER_MODES, PEAK_CEILING, check_limiter, check_loudness, pitch_ratio, tempo_len, tempo_ratio
 from .bicodec import BiCodecTokenizer
 from .config import LLMConfig, TopConfig
 from .llm import (ALLOW_KEY, FORK_KEY, LOGPROB_KEYS, NGRAM_KEY, PENALTY_KEYS, SAMPLING_KEYS, SEQ_KEYS, SparkLLM,
@@ -67,6 +69,9 @@ NO_CEILING = 1e30
 STREAM_LIMITER_KEY = "stream_limiter"
 # request key: the request's own tempo (0.5 .. 2.0; > 1: faster); it overrides the call's ``tempo``
 TEMPO_KEY = "tempo"
+# request key: the request's own pitch shift in semitones (-12.0 .. 12.0; > 0: higher); it overrides the call's ``pitch_shift``
+# (``pitch`` is taken: the label argument of voice creation)
+PITCH_SHIFT_KEY = "pitch_shift"
 
 
 def _stream_pacing(max_batch: int, max_open=None, max_ahead=None, resume_ahead=None):
@@ -282,11 +287,12 @@ class SparkTTS:
                   speech_tokens_only: bool = False, no_repeat_ngram_size: int = 0, output_sample_rate: Optional[int] = None,
                   loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
                   tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
-                  limiter_release_ms: float = 25.0):
+                  limiter_release_ms: float = 25.0, pitch_shift: Optional[float] = None):
         """Text (+ optional prompt audio / style labels) -> float32 waveform at ``sample_rate`` (or at ``output_sample_rate``,
         as in ``inference_batch``; ``loudness`` / ``peak_ceiling`` / ``max_gain_db``: the output's programme loudness, as
         there; ``tempo``: the speaking rate, as there; ``limiter`` / ``limiter_lookahead_ms`` / ``limiter_release_ms``: the
-        look-ahead limiter, as there).  The penalties
+        look-ahead limiter, as there; ``pitch_shift``: semitones on the output, as there -- not ``pitch``, the label of voice
+        creation).  The penalties
         (include/sparkmi.h, smi_llm_admit_penalized) apply before token selection; their defaults leave it unpenalised.
         For voice cloning ``penalize_prompt=False`` keeps the reference clip's semantic tokens out of the repetition
         penalty.  ``return_log_probs=True``: (waveform, info) with info = {``token_ids``: the generated ids,
@@ -315,7 +321,8 @@ class SparkTTS:
                                     max_new_tokens=max_new_tokens, seed=seed, return_log_probs=return_log_probs,
                                     output_sample_rate=output_sample_rate, loudness=loudness, peak_ceiling=peak_ceiling,
                                     max_gain_db=max_gain_db, tempo=tempo, limiter=limiter,
-                                    limiter_lookahead_ms=limiter_lookahead_ms, limiter_release_ms=limiter_release_ms)[0]
+                                    limiter_lookahead_ms=limiter_lookahead_ms, limiter_release_ms=limiter_release_ms,
+                                    pitch_shift=pitch_shift)[0]
 
     def _output_ratio(self, output_sample_rate: Optional[int]) -> Optional[Tuple[int, int]]:
         """(up, down) from the model's rate to ``output_sample_rate``; None when the vocoder's rows go out as they are"""
@@ -632,10 +639,41 @@ class SparkTTS:
             out.append(None if pq == (1, 1) else pq)
         return out
 
-    def _tempo_rows(self, wav, n: Sequence[int], ratios: Sequence[Optional[Tuple[int, int]]], spans=None):
+    @staticmethod
+    def _pitch_ratios(requests: Sequence[dict], pitch_shift, first: int = 0) -> List[Optional[Tuple[int, int]]]:
+        """every request's pitch shift as the frequency ratio (p, q) (its own ``pitch_shift`` key, else the call's), all checked;
+        None for a request without one or whose ratio comes out 1/1, which is left as it is.  ``first``: as in ``_tempo_ratios``."""
+        if pitch_shift is not None:
+            pitch_ratio(pitch_shift)
+        out = []
+        for i, r in enumerate(requests):
+            t = r.get(PITCH_SHIFT_KEY, pitch_shift)
+            try:
+                pq = None if t is None else pitch_ratio(t)
+            except ValueError as e:
+                raise ValueError(f"request {first + i}: {e}") from None
+            out.append(None if pq == (1, 1) else pq)
+        return out
+
+    @staticmethod
+    def _no_stream_pitch(pitch_shift, who: str) -> None:
+        if pitch_shift is not None:
+            raise ValueError(f"{who}: pitch_shift is not supported on chunked streams, joined or not (the stretch and the resampler "
+                             "behind it would need their state carried across chunk edges); the batch calls take it: inference / "
+                             "inference_batch / serve / inference_long / inference_long_stream")
+
+    def _tempo_rows(self, wav, n: Sequence[int], ratios: Sequence[Optional[Tuple[int, int]]], spans=None,
+                    pitches: Optional[Sequence[Optional[Tuple[int, int]]]] = None):
         """Rows (or their ``spans``) at their tempos, on the device (``audio.DeviceAudio.tempo_rows``: two launches for all rows,
         nothing waits): (new rows, their lengths).  A row without a ratio goes through at 1/1, which copies it bit for bit.
-        Where no row has a ratio nothing is launched: (wav, n) as they came -- only without ``spans``."""
+        Where no row has a ratio nothing is launched: (wav, n) as they came -- only without ``spans``.  Where any row has a
+        pitch ratio (``pitches``) the pitch stage replaces the tempo stage for all rows of the call
+        (``audio.DeviceAudio.pitch_rows``: two launches as well, the tempo and the pitch in one stretch pass; a row without a
+        pitch ratio comes out as ``tempo_rows`` gives it, bit for bit)."""
+        if pitches is not None and any(r is not None for r in pitches):
+            y, m, _ = self._device_audio().pitch_rows(wav.contiguous(), n, [r or (1, 1) for r in ratios], [r or (1, 1) for r in pitches],
+                                                      spans=spans, sr=self.sample_rate)
+            return y, m
         if spans is None and all(r is None for r in ratios):
             return wav, list(n)
         y, m, _ = self._device_audio().tempo_rows(wav.contiguous(), n, [r or (1, 1) for r in ratios], spans=spans, sr=self.sample_rate)
@@ -648,7 +686,7 @@ class SparkTTS:
                         prompt_audio: str = "host", output_sample_rate: Optional[int] = None,
                         loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
                         tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
-                        limiter_release_ms: float = 25.0) -> List:
+                        limiter_release_ms: float = 25.0, pitch_shift: Optional[float] = None) -> List:
         """Several independent utterances in one ragged batch (<= max_batch).  Greedy: each result equals the
         single-utterance call for that request -- exactly with an f32 KV cache; with the default bf16 cache up to near-tie
         arg-max flips between the prefill kernels the two call shapes select (include/sparkmi.h, smi_llm_session_begin).
@@ -692,9 +730,17 @@ class SparkTTS:
         its target (or ``max_gain_db``): the loudness stage measures with a ceiling that cannot bind, the limiter applies its
         gain, and ``limited`` is None or "max_gain".  Without ``loudness`` the limiter alone bounds the vocoder's output.
         ``self.last_limiter`` holds, per request (per take where it has takes), None or {``true_peak``: going in,
-        ``reduction_db``: the deepest reduction, ``limited_samples``}, from the one small copy that brings ``last_loudness``."""
+        ``reduction_db``: the deepest reduction, ``limited_samples``}, from the one small copy that brings ``last_loudness``.
+        ``pitch_shift`` (semitones, -12.0 .. 12.0; > 0: higher; None or a value whose ratio comes out 1/1: nothing new is
+        launched and no bit changes) or a request's own ``pitch_shift`` key, which overrides it: the vocoded row's pitch is moved
+        by the frequency ratio ``audio.pitch_ratio`` gives (2 ** (s / 12) to a hundredth: about 9 to 17 cents) at unchanged
+        length, on the device (include/sparkmi.h, smi_pitch_rows).  It works for cloned voices, which the
+        ``pitch`` label of voice creation does not reach.  Where a call has a pitched row the stage replaces the tempo stage:
+        one WSOLA stretch serves ``tempo`` and ``pitch_shift`` together, a polyphase resampler follows inside the same launch,
+        and the row has ``audio.tempo_len(n, p, q)`` samples as with ``tempo`` alone.  The formants move with the pitch."""
         targets = self._loudness_targets(requests, loudness, peak_ceiling, max_gain_db)
         ratios = self._tempo_ratios(requests, tempo)
+        shifts = self._pitch_ratios(requests, pitch_shift)
         if prompt_encode not in ("streams", "rows"):
             raise ValueError(f"prompt_encode must be 'streams' or 'rows', not {prompt_encode!r}")
         if prompt_audio not in ("host", "device"):
@@ -788,7 +834,7 @@ class SparkTTS:
         n_wav = [n * hop for n in lens]
         wav = wav.squeeze(1)
         row_targets = [targets[b] for b in owner]
-        wav, n_wav = self._tempo_rows(wav, n_wav, [ratios[b] for b in owner])
+        wav, n_wav = self._tempo_rows(wav, n_wav, [ratios[b] for b in owner], pitches=[shifts[b] for b in owner])
         row_modes = [modes[b] for b in owner]
         stats = lstats = None
         if any(t is not None for t in row_targets) or any(m is not None for m in row_modes):
@@ -826,7 +872,8 @@ class SparkTTS:
                          joined: bool = False, tempo: Optional[float] = None, loudness: Optional[float] = None,
                          peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
                          max_slew_db: float = 1.0, limiter: Optional[str] = None, stream_limiter: Optional[str] = None,
-                         limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0) -> Iterator[np.ndarray]:
+                         limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0,
+                         pitch_shift: Optional[float] = None) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
@@ -876,8 +923,10 @@ class SparkTTS:
         given ``stream_limiter`` is refused (ValueError).
 
         ``limiter`` is refused (ValueError), joined or not: that keyword names the limiter of whole utterances, which
-        ``inference_batch`` has; the streaming form is asked for by ``stream_limiter``."""
+        ``inference_batch`` has; the streaming form is asked for by ``stream_limiter``.  ``pitch_shift`` is refused (ValueError),
+        joined or not: the batch calls take it; its streaming form needs state that is not carried yet."""
         self._no_stream_limiter(limiter, "inference_stream")
+        self._no_stream_pitch(pitch_shift, "inference_stream")
         if not joined:
             self._no_stream_tempo(tempo, "inference_stream")
             self._no_stream_loudness(loudness, "inference_stream")
@@ -1004,7 +1053,7 @@ class SparkTTS:
               max_new_tokens: int = 3000, seed: Optional[int] = None, decode_stride: int = 8, return_log_probs: bool = False,
               loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
               tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
-              limiter_release_ms: float = 25.0):
+              limiter_release_ms: float = 25.0, pitch_shift: Optional[float] = None):
         """In-flight batching front end (the functional analogue of the reference's Triton deployment,
         runtime/triton_trtllm/run.sh:50-65): ``requests`` is an iterable of the dicts ``inference_batch`` takes;
         yields ``(index, waveform)`` as each utterance finishes.  Up to ``max_batch`` utterances are live; a new
@@ -1022,7 +1071,8 @@ class SparkTTS:
         ``inference_batch``: the waveform's speaking rate is changed on the device, before the loudness stage.  ``limiter`` /
         ``limiter_lookahead_ms`` / ``limiter_release_ms`` and a request's own ``limiter`` key as in ``inference_batch``: the
         look-ahead limiter behind the loudness stage; ``self.last_limiter[index]`` holds its entry (a list for a request with
-        takes) once the request has been yielded."""
+        takes) once the request has been yielded.  ``pitch_shift`` and a request's own ``pitch_shift`` key as in
+        ``inference_batch``: the waveform's pitch is moved on the device, in the tempo stage's place and pass."""
         forks: Dict[int, int] = {}   # request index -> takes, for the requests that carry num_return_sequences
         lims: Dict[int, Optional[str]] = {}   # request index -> limiter mode
         self.last_limiter = {}
@@ -1030,6 +1080,8 @@ class SparkTTS:
         rates: Dict[int, Optional[Tuple[int, int]]] = {}   # request index -> tempo as (p, q)
         check_loudness(loudness, peak_ceiling, max_gain_db)
         self._tempo_ratios([], tempo)
+        self._pitch_ratios([], pitch_shift)
+        shifts: Dict[int, Optional[Tuple[int, int]]] = {}   # request index -> pitch shift as a frequency ratio (p, q)
         self.last_loudness = {}
 
         def checked(reqs):   # each request's takes, checked before the request reaches the device
@@ -1039,6 +1091,7 @@ class SparkTTS:
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 goals[i] = self._loudness_targets([r], loudness, peak_ceiling, max_gain_db)[0]
                 rates[i] = self._tempo_ratios([r], tempo, i)[0]
+                shifts[i] = self._pitch_ratios([r], pitch_shift, i)[0]
                 lims[i] = self._limiter_modes([r], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms, i)[0][0]
                 yield r
 
@@ -1078,7 +1131,7 @@ class SparkTTS:
             return [(wav[b, : n[b]].copy(), infos[b]) if infos[b] is not None else wav[b, : n[b]].copy() for b in range(len(rows))]
 
         def finished(i, wav, lens, takes):   # the vocoded rows of request i at its tempo and loudness target, still on the device
-            wav, n = self._tempo_rows(wav, [f * hop for f in lens], [rates[i]] * len(lens))
+            wav, n = self._tempo_rows(wav, [f * hop for f in lens], [rates[i]] * len(lens), pitches=[shifts[i]] * len(lens))
             if goals[i] is None and lims[i] is None:
                 return wav, n
             wav = wav.contiguous()
@@ -1116,7 +1169,8 @@ class SparkTTS:
                      clock=None, pacer: Optional[Pacer] = None, output_sample_rate: Optional[int] = None, joined: bool = False,
                      tempo: Optional[float] = None, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
                      max_gain_db: float = 20.0, max_slew_db: float = 1.0, limiter: Optional[str] = None,
-                     stream_limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0):
+                     stream_limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0,
+                     pitch_shift: Optional[float] = None):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -1197,8 +1251,10 @@ class SparkTTS:
         without it is refused (ValueError).
 
         ``limiter`` and a request's own ``limiter`` key are refused (ValueError), joined or not: they name the limiter of whole
-        utterances; the streaming form is asked for by ``stream_limiter``."""
+        utterances; the streaming form is asked for by ``stream_limiter``.  ``pitch_shift`` and a request's own ``pitch_shift``
+        key are refused (ValueError), joined or not: the batch calls take it."""
         self._no_stream_limiter(limiter, "serve_stream")
+        self._no_stream_pitch(pitch_shift, "serve_stream")
         if not joined:
             self._no_stream_tempo(tempo, "serve_stream")
             self._no_stream_loudness(loudness, "serve_stream")
@@ -1220,6 +1276,8 @@ class SparkTTS:
                             " with overlapping chunks; pass joined=True" if k in (TEMPO_KEY, LOUDNESS_KEY, STREAM_LIMITER_KEY) else ""))
                 if r.get(LIMITER_KEY) is not None:
                     self._no_stream_limiter(r[LIMITER_KEY], f"request {i}: serve_stream")
+                if r.get(PITCH_SHIFT_KEY) is not None:
+                    self._no_stream_pitch(r[PITCH_SHIFT_KEY], f"request {i}: serve_stream")
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 rates[i] = self._tempo_ratios([r], tempo, i)[0] or (1, 1)
                 try:
@@ -1443,18 +1501,20 @@ class SparkTTS:
     def _long_pieces(self, text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
                      max_new_tokens, seed, prompt_tokens, keys: dict, max_width, min_width, pause, trim, trim_threshold, fade, eager: bool,
                      info: dict, loudness=None, peak_ceiling=PEAK_CEILING, max_gain_db=20.0, tempo=None, limiter=None,
-                     limiter_lookahead_ms=2.5, limiter_release_ms=25.0):
+                     limiter_lookahead_ms=2.5, limiter_release_ms=25.0, pitch_shift=None):
         """The engine of ``inference_long`` and ``inference_long_stream``: yields (first sentence, joined [total] float32 on the
         device, [(offset in it, gap, length) per sentence]) for runs of consecutive sentences in text order -- with ``eager``
         as soon as the next sentence due and those behind it are done, else in runs of ``max_batch`` once all are done.  Fills
         ``info``.  With ``tempo``, every sentence's trimmed piece is time-scaled on its own into a row of its own; with
         ``loudness``, every piece (scaled or not) is brought to that programme loudness in place before the assembly; with
         ``limiter``, every piece goes through the look-ahead limiter on its own span there as well (``_level_rows``).
+        With ``pitch_shift`` the pitch stage takes the tempo stage's place: every trimmed piece on its own, in one pass.
         Everything is checked before anything reaches the device."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
         mode, reach = self._limiter_modes([{}], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         mode = mode[0]
         rate = self._tempo_ratios([{}], tempo)[0]
+        shift = self._pitch_ratios([{}], pitch_shift)[0]
         from .longform import control_prefix, control_prompt_ids, ready_run, sentence_seeds, split_text, trim_params
         sentences = split_text(text, max_width, min_width)
         for name, v in (("pause", pause), ("fade", fade), ("trim_threshold", trim_threshold)):
@@ -1513,11 +1573,12 @@ class SparkTTS:
                 gaps.append(gap if b > a and state["spoken"] else 0)
                 state["spoken"] = state["spoken"] or b > a
             cut = bounds              # of the untrimmed rows: what info["bounds"] reports
-            if rate is not None:      # each trimmed piece scaled on its own: row k of the new rows is the whole scaled piece
-                wav, n = self._tempo_rows(wav, n, [rate] * len(ks), spans=bounds)
+            if rate is not None or shift is not None:   # each trimmed piece on its own: row k of the new rows is the whole piece
+                wav, n = self._tempo_rows(wav, n, [rate] * len(ks), spans=bounds, pitches=[shift] * len(ks))
                 bounds = [(0, v) for v in n]
                 for k, v in zip(ks, n):
-                    info["tempo_lengths"][k] = v
+                    if rate is not None:
+                        info["tempo_lengths"][k] = v
             offs, total = audio.concat_layout(bounds, gaps)
             stats = lstats = None
             goal = None if loudness is None else float(loudness)
@@ -1590,7 +1651,7 @@ class SparkTTS:
                        trim_threshold: float = 0.01, fade: float = 0.005, output_sample_rate: Optional[int] = None,
                        return_info: bool = False, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
                        max_gain_db: float = 20.0, tempo: Optional[float] = None, limiter: Optional[str] = None,
-                       limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0):
+                       limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0, pitch_shift: Optional[float] = None):
         """A text of any length -> one float32 waveform: the text is cut into sentences (``longform.split_text``: ``max_width``,
         ``min_width``), the sentences are generated with the same voice as the requests of one in-flight session (up to
         ``max_batch`` live; ``max_new_tokens`` is per sentence), vocoded in ragged calls, cut at their speech bounds
@@ -1630,9 +1691,14 @@ class SparkTTS:
         own trimmed span, behind the loudness stage and before the assembly, so one click no longer holds a whole sentence
         under its target: with ``loudness`` a piece reaches the target (or ``max_gain_db``) and ``limited`` is None or
         "max_gain".  Every sample of every piece is at or under ``peak_ceiling``; ``info["limiter"]`` holds {``true_peak``,
-        ``reduction_db``, ``limited_samples``} per sentence."""
+        ``reduction_db``, ``limited_samples``} per sentence.
+
+        ``pitch_shift`` (semitones, -12.0 .. 12.0; None or a ratio of 1/1: no extra launch) as in ``inference_batch``: every
+        trimmed piece's pitch is moved on its own (include/sparkmi.h, smi_pitch_rows), in the tempo stage's place and pass; a
+        piece keeps the length ``tempo`` alone gives it -- its own without one."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
         self._tempo_ratios([], tempo)
+        self._pitch_ratios([], pitch_shift)
         self._limiter_modes([], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         out_ratio = self._output_ratio(output_sample_rate)
         keys = self._long_keys(prompt_speech_path, gender, prompt_tokens, repetition_penalty, presence_penalty, frequency_penalty,
@@ -1641,7 +1707,7 @@ class SparkTTS:
         parts = [out for _, out, _ in self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p,
                                                         do_sample, max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim,
                                                         trim_threshold, fade, False, info, loudness, peak_ceiling, max_gain_db, tempo,
-                                                        limiter, limiter_lookahead_ms, limiter_release_ms)
+                                                        limiter, limiter_lookahead_ms, limiter_release_ms, pitch_shift)
                  if out is not None]
         if not parts:
             wav = np.zeros(0, dtype=np.float32)
@@ -1667,7 +1733,7 @@ class SparkTTS:
                               output_sample_rate: Optional[int] = None, loudness: Optional[float] = None,
                               peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
                               tempo: Optional[float] = None, limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5,
-                              limiter_release_ms: float = 25.0) -> Iterator[np.ndarray]:
+                              limiter_release_ms: float = 25.0, pitch_shift: Optional[float] = None) -> Iterator[np.ndarray]:
         """``inference_long`` piece by piece: yields contiguous float32 pieces in text order, sentence k's pause + trimmed and faded
         piece as soon as k and every sentence before it are done (an empty piece is not yielded).  At the model's rate the
         pieces' concatenation is ``inference_long``'s waveform bit for bit: a piece's bits are its own (include/sparkmi.h,
@@ -1678,8 +1744,10 @@ class SparkTTS:
         the pieces stay bit for bit those of ``inference_long``.  ``tempo`` as in ``inference_long``: a sentence's piece is
         scaled whole and on its own before it leaves, so no state crosses the pieces and the same holds.  ``limiter`` /
         ``limiter_lookahead_ms`` / ``limiter_release_ms`` as in ``inference_long``: a piece is limited whole and on its own
-        span -- this is the batch limiter, not a streaming one --, so the same holds again."""
+        span -- this is the batch limiter, not a streaming one --, so the same holds again.  ``pitch_shift`` as in
+        ``inference_long``: a piece is shifted whole and on its own, so the same holds once more."""
         check_loudness(loudness, peak_ceiling, max_gain_db)
+        self._pitch_ratios([], pitch_shift)
         self._limiter_modes([], limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         rate = self._tempo_ratios([{}], tempo)[0] or (1, 1)
         out_ratio = self._output_ratio(output_sample_rate)
@@ -1687,7 +1755,8 @@ class SparkTTS:
                                min_new_tokens, penalize_prompt, allowed_token_ids, speech_tokens_only, no_repeat_ngram_size)
         pieces = self._long_pieces(text, prompt_speech_path, prompt_text, gender, pitch, speed, temperature, top_k, top_p, do_sample,
                                    max_new_tokens, seed, prompt_tokens, keys, max_width, min_width, pause, trim, trim_threshold, fade, True, {},
-                                   loudness, peak_ceiling, max_gain_db, tempo, limiter, limiter_lookahead_ms, limiter_release_ms)
+                                   loudness, peak_ceiling, max_gain_db, tempo, limiter, limiter_lookahead_ms, limiter_release_ms,
+                                   pitch_shift)
         joiner = None
         for _, out, spans in pieces:
             if out is None:
