@@ -1038,6 +1038,78 @@ long long smi_tempos_piece_len(int p, int q, int N, int D, long long n_before, l
                                long long* n_after, long long* frames_after);
 
 /* ------------------------------------------------------------------------------------------
+ * Pitch shift of joined streams: the pitch section's arithmetic with state carried from push to push, the streaming form of
+ * smi_pitch_rows as smi_tempos_* is that of smi_tempo_rows.  No sample is defined here: the concatenation of a stream's pieces
+ * is smi_pitch_rows of its whole input at the same tp / tq, rp / rq, N, D, window and taps, bit for bit, and the stretch's frame
+ * places are equal too.  What is new is the rule for when an output sample is final, and the state.
+ *
+ * When an output is final.  Host integer arithmetic only (smi_pitchs_piece_len), never data.  P / Q, up / down as in the pitch
+ * section; taps h[0 .. 2G].  With n input samples so far, the stretch is smi_tempos_*' stream at P / Q and has emitted E(n)
+ * stretched samples z[0 .. E), exactly as smi_tempos_piece_len gives (E = n at P = Q).  After a push that is not the last the
+ * stream has emitted
+ *     K(n) = max(0, ceil((E(n) up - G) / down))
+ * final outputs -- smi_join's own expression, applied to the stretched stream: output k reads z up to floor((k down + G) / up),
+ * which lies below E exactly when k down + G < E up, so the sums of the first K outputs reach nothing that is not final, and
+ * their edge needs no clamp.  After the last push, with total length L, it has emitted n_out = ceil(L tq / tp): the remaining
+ * sums are clamped at M - 1, M = ceil(L Q / P), as the batch call clamps them, and the surplus is cut.  A push emits the
+ * difference, which may be 0.  K(n) never falls, since E never does.  K(n) <= ceil(n tq / tp), so what has left is at most the
+ * final n_out whatever follows: E <= ceil(n Q / P) < n Q / P + 1 gives E up / down < n tq / tp + up / down, and
+ * K < (E up - G) / down + 1 <= n tq / tp + 1 once G >= up; a stream with G < up is refused at open.  At rp = rq (up = down = 1,
+ * no taps, G = 0) K = E: the stream is smi_tempos_*' stream at tp / tq bit for bit, and with tp = tq too it copies its chunks
+ * with no latency.  Otherwise a piece is the tempo stream's hold-back at P / Q plus G / up stretched samples late.
+ *
+ * State.  On the host, per slot: n, the emitted frames F, the emitted outputs K, tp, tq, rp, rq.  On the device, per slot, in
+ * two sets used in turn as in smi_tempos_* (a push reads one and writes the other, so a refused call has changed nothing):
+ * smi_tempos_*' own state at P / Q -- s_{F-1} and the input from h(F), at most max(7 H + D, 5 H + 2 D) samples -- and the tail
+ * of the stretched signal that later outputs still reach, z[j(K) .. E), j(K) = max(0, ceil((K down - G) / up)), the first
+ * sample of output K's sum.  Where K > 0, K down >= E up - G, so j(K) >= E - 2 G / up and the tail holds at most 2 G / up
+ * samples; where K = 0, E up <= G and the tail is E <= G / up samples.  The handle keeps max_taps + 1 per slot and set, which is
+ * more than either, and a push whose tail would not fit is refused.  These are the only stretched samples that ever reach
+ * memory; they are the values the overlap-add produced, so the bits cannot differ from computing them again.  The slot also
+ * owns a copy of its stream's taps (fp32, at most max_taps of them), handed over at open.
+ *
+ * Two launches a call, whatever B, no atomics.  k_tempos_search as in the section above, with P / Q per row.  k_pitchs_ola, grid
+ * (tiles of 1024 final outputs of the pieces, rows; every row has a tile): a block stages its row's taps in LDS, fills the
+ * window of stretched samples its sums reach straight into LDS -- those below E before the push from the read set's tail, the
+ * others by the tempo section's overlap-add over history and chunk, reading zeros beyond L on the last push --, and after one
+ * barrier forms its sums; zeros from the piece's end to the stride.  A row at up = down = 1 writes the overlap-add itself.  Tile
+ * 0 of a row also writes the written set's input history and stretched tail.  A stream whose taps plus one tile's stretched
+ * window, (1023 down + 2 G) / up + 3 samples, exceed 16384 floats of LDS is refused at open, as the batch call refuses the row.
+ *
+ * Guarantees: as for smi_tempos_* -- pieces and places are those of smi_pitch_rows of the whole input whatever the granularity
+ * of the pushes, the stream's slot, its row in a call and the other rows; a piece's length is pure host arithmetic; nothing
+ * synchronises and nothing is copied back.  A stream is refused (SMI_EINVAL) before n passes 2^28 or E up or K down reaches
+ * 2^31.  All opens and pushes of a handle must go to one HIP stream (or be ordered by the caller). */
+typedef struct smi_pitchs smi_pitchs;
+/* max_streams, max_chunk, N, D, win_host as for smi_tempos_create; max_taps (0 .. 16383): the longest filter a stream of this
+ * handle may bring.  Synchronous (one allocation, one small copy). */
+int smi_pitchs_create(int max_streams, int max_chunk, int N, int D, const double* win_host, int max_taps, smi_pitchs** out);
+int smi_pitchs_destroy(smi_pitchs* h);
+/* A new stream in `slot` at tempo tp / tq and pitch ratio rp / rq (ranges as for smi_pitch_rows): n, F and K are zero.
+ * taps_host [n_taps] f32: the stream's filter h[0 .. 2G], n_taps odd and >= 3 -- or 0, and only 0, at rp = rq.  Refused:
+ * G < up, n_taps > max_taps, and a filter that does not fit the LDS (above).  The taps are copied into the slot on `stream`,
+ * ordered behind the slot's earlier pushes there and before later ones; taps_host is free on return.  A stream closes with its
+ * last push.  A refused open has changed nothing. */
+int smi_pitchs_open(smi_pitchs* h, int slot, int tp, int tq, int rp, int rq, const float* taps_host, int n_taps, void* stream);
+/* Arguments and checks as for smi_tempos_push_rows: one chunk per row of the open streams stream_host[b], each at most once in
+ * a call, len_host[b] may be 0, last_host[b] = 1 on a stream's last push; out_dev [B][out_stride] receives row b's piece and
+ * zeros from there to out_stride (>= 1 and >= the longest piece) and overlaps neither in_dev nor the handle's state; pos_dev
+ * (may be null) [B][pos_stride] receives the places of the stretch's frames this push made final, then zeros; n_out_host [B]
+ * (may be null) receives the pieces' lengths, filled before the launch.  B <= 64.  Asynchronous on `stream`; it never
+ * synchronises.  Every argument of every row is checked before anything changes or is launched: a bad one returns SMI_EINVAL
+ * and names the argument in smi_last_error. */
+int smi_pitchs_push_rows(smi_pitchs* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                         const int32_t* last_host, int B, int32_t* pos_dev, long long pos_stride, float* out_dev, long long out_stride,
+                         int32_t* n_out_host, void* stream);
+/* The piece length of one push, pure host arithmetic: a stream at tp / tq and rp / rq with frame N, radius D and n_taps taps
+ * that holds n_before samples and has emitted frames_before frames of the stretch and k_before outputs takes len samples
+ * (last = 1: its last push); n_after / frames_after / k_after (may be null) receive the counters after it.  -1 for a bad
+ * argument, among them G < up and counters that reach the limits above. */
+long long smi_pitchs_piece_len(int tp, int tq, int rp, int rq, int N, int D, int n_taps, long long n_before, long long frames_before,
+                               long long k_before, long long len, int last, long long* n_after, long long* frames_after,
+                               long long* k_after);
+
+/* ------------------------------------------------------------------------------------------
  * Loudness of joined streams: a running BS.1770 gain with state carried from push to push.  Integrated loudness is a property
  * of the whole utterance, which a piece that has to leave early cannot know, so this is NOT smi_loud_rows run chunk by chunk;
  * it has a definition of its own.  The gain follows the integrated loudness of what has arrived, moves at a bounded rate and

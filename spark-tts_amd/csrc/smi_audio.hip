@@ -33,6 +33,9 @@
 //   k_tempos_search, k_tempos_ola  the time-scale change for joined streams (smi_tempos_*): the frames a push makes final, walked over the
 //                stream's history followed by its new chunk with the batch kernels' own device functions (tp_place, tp_ola);
 //                histories and last places live in two sets a stream uses in turn, as the joiner's state does.
+//   k_pitchs_ola                 the pitch shift of joined streams (smi_pitchs_*), behind k_tempos_search: k_pitch_ola's window of
+//                stretched samples in LDS, filled from the stream's stored tail and with tp_ola over history and chunk, summed with
+//                rs_tile_sums; the tail the next outputs still reach is the only stretched signal in memory.  No atomics.
 //   k_louds_seg, k_louds_carry, k_louds_energy, k_louds_knots, k_louds_apply   loudness of joined streams (smi_louds_*): the
 //                batch filter launches over a stream's held input followed by its new chunk, from the stream's carried state,
 //                with the batch kernels' own device functions (ld_step, the block sums); one block per row then closes hops and
@@ -46,6 +49,7 @@
 #include <limits.h>
 
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "smi_common.h"
@@ -1244,6 +1248,102 @@ __global__ __launch_bounds__(RS_BLOCK) void k_tempos_ola(TsArgs a, TsState s, in
     }
     y[i] = v;
   }
+}
+
+// ---- pitch shift of joined streams (smi_pitchs_*): smi_tempos' stream at P / Q, resampled by up / down as it arrives
+struct PsRow {
+  int32_t k_old, k_new;     // final outputs emitted before / after this push
+};
+struct PsArgs {
+  PsRow r[RS_MAX_ROWS];
+};
+struct PsState {
+  float* taps;              // [max_streams][tslot]: a slot's up, down, G and a zero as int32, then its taps h[0 .. 2G] (written at open)
+  float* tail;              // [2][max_streams][tcap]: tail[i] = z[t0 + i], i < E - t0, t0 = rs_jlo(K down)
+  int32_t tslot, tcap;
+};
+
+// sample m of the stretched stream, E before this push <= m < E after it (TsRow::m_new; M on the last push): k_tempos_ola's value
+__device__ __forceinline__ float ps_stretched(const TsSeq& x, const TsRow& r, const int32_t* __restrict__ wk, long long m, int H,
+                                              const double* __restrict__ win) {
+  float v = 0.f;
+  if (r.p == r.q) {   // the stretch is a copy
+    (void)x.get(m, v);
+    return v;
+  }
+  const long long k = m / H;
+  const int j = (int)(m - k * H), f = (int)(k - r.f_old);   // 0 <= f < f_new - f_old
+  if (k == 0) (void)x.get(m, v);
+  else v = tp_ola(x, j, H, wk[f + 1], wk[f], win);
+  return v;
+}
+
+// grid (tiles of RS_TILE final outputs of the pieces, rows), behind k_tempos_search.  A block stages its row's taps, fills the
+// window of stretched samples its sums reach straight into LDS -- those below E before this push from the read set's tail, the
+// others with tp_ola over history and chunk from the places in `work` -- and after one barrier sums its outputs with
+// rs_tile_sums against the stretched samples there are (M on the last push).  A row at up = down = 1 writes the stretched
+// samples themselves, as k_tempos_ola does.  Zeros from the piece's end to the stride.  Tile 0 of a row also writes the
+// stream's next input history and next stretched tail into the set this launch does not read.
+__global__ __launch_bounds__(RS_BLOCK) void k_pitchs_ola(TsArgs a, PsArgs f, TsState s, PsState ps, int N, const float* __restrict__ in,
+                                                         long long in_stride, float* __restrict__ out, long long out_stride) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const TsRow r = a.r[blockIdx.y];
+  const PsRow g = f.r[blockIdx.y];
+  const TsSeq x = ts_seq(r, s, in + (size_t)blockIdx.y * in_stride);
+  const int32_t* wk = s.work + (size_t)blockIdx.y * (s.fmax + 1);
+  float* y = out + (size_t)blockIdx.y * out_stride;
+  const int H = N / 2, tid = threadIdx.x;
+  const int32_t* hd = (const int32_t*)(ps.taps + (size_t)r.slot * ps.tslot);
+  const int up = hd[0], down = hd[1], half = hd[2];
+  const bool plain = up == 1 && down == 1;
+  const long long e_old = r.p == r.q ? (long long)r.n_old : (long long)H * r.f_old;
+  const float* tail = ps.tail + ((size_t)r.set * s.max_streams + r.slot) * ps.tcap;
+  const int t0_old = plain ? 0 : rs_jlo(g.k_old * down, up, half);
+  if (blockIdx.x == 0 && r.h0_new >= 0) {   // (not the stream's last push)
+    float* hist2 = s.hist + ((size_t)(1 - r.set) * s.max_streams + r.slot) * s.hcap;
+    const int nh = r.n_new - r.h0_new;   // <= hcap: checked on the host
+    for (int i = tid; i < nh; i += RS_BLOCK) {
+      float v = 0.f;
+      (void)x.get((long long)r.h0_new + i, v);
+      hist2[i] = v;
+    }
+    if (!plain) {
+      float* tail2 = ps.tail + ((size_t)(1 - r.set) * s.max_streams + r.slot) * ps.tcap;
+      const int t0_new = rs_jlo(g.k_new * down, up, half);   // >= t0_old
+      const int nt = r.m_new - t0_new;   // <= tcap: checked on the host
+      for (int i = tid; i < nt; i += RS_BLOCK) {
+        const int m = t0_new + i;
+        tail2[i] = m < e_old ? tail[m - t0_old] : ps_stretched(x, r, wk, m, H, s.win);
+      }
+    }
+  }
+  const long long i0 = (long long)blockIdx.x * RS_TILE;
+  if (i0 >= out_stride) return;
+  const int n_write = (int)min((long long)RS_TILE, out_stride - i0);
+  const long long k0 = g.k_old + i0;
+  if (k0 >= g.k_new) {   // past the piece: zeros
+    for (int i = tid; i < n_write; i += RS_BLOCK) y[i0 + i] = 0.f;
+    return;
+  }
+  if (plain) {   // no pitch ratio: K = E, the stretched samples are the piece
+    for (int i = tid; i < n_write; i += RS_BLOCK) y[i0 + i] = k0 + i < g.k_new ? ps_stretched(x, r, wk, k0 + i, H, s.win) : 0.f;
+    return;
+  }
+  const int ntaps = 2 * half + 1;
+  float* ht = rs_lds;
+  float* zw = rs_lds + ntaps;
+  const int klast = (int)min(k0 + RS_TILE, (long long)g.k_new) - 1;
+  const int j0 = rs_jlo((int)k0 * down, up, half);   // >= t0_old
+  const int j1 = min(rs_jhi(klast * down, up, half), r.m_new - 1);
+  const int nwin = j1 - j0 + 1;   // <= rs_window(): checked at open
+  const float* h = ps.taps + (size_t)r.slot * ps.tslot + 4;
+  for (int i = tid; i < ntaps; i += RS_BLOCK) ht[i] = h[i];
+  for (int i = tid; i < nwin; i += RS_BLOCK) {
+    const int m = j0 + i;
+    zw[i] = m < e_old ? tail[m - t0_old] : ps_stretched(x, r, wk, m, H, s.win);
+  }
+  __syncthreads();
+  rs_tile_sums(ht, zw, j0, r.m_new - 1, (int)k0, g.k_new, up, down, half, y + i0, n_write);
 }
 
 // ---- loudness of joined streams (smi_louds_*)
@@ -2747,6 +2847,252 @@ int smi_tempos_push_rows(smi_tempos* h, const float* in_dev, long long stride, c
   SMI_LAUNCH_CHECK();
   const int tiles = (int)((out_stride + TP_TILE - 1) / TP_TILE);
   hipLaunchKernelGGL(k_tempos_ola, dim3(tiles, B), dim3(RS_BLOCK), 0, hs, A, s, h->N, in_dev, stride, out_dev, out_stride);
+  SMI_LAUNCH_CHECK();
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+// ---- pitch shift of joined streams (smi_pitchs_*): the host arithmetic of include/sparkmi.h's "When an output is final"
+struct PsPlan {
+  int P, Q, up, down, half;
+};
+
+// the plan of a stream at tempo tp / tq and pitch ratio rp / rq with n_taps taps; false for a bad argument
+static bool ps_plan(int tp, int tq, int rp, int rq, int N, int D, int n_taps, PsPlan& pl) {
+  PtPlan bp;
+  if (!pt_plan(0, tp, tq, rp, rq, N, bp) || !ts_args(bp.P, bp.Q, N, D)) return false;
+  pl.P = bp.P; pl.Q = bp.Q; pl.up = bp.up; pl.down = bp.down; pl.half = n_taps / 2;
+  if (bp.up == 1 && bp.down == 1) return n_taps == 0;
+  return n_taps >= 3 && (n_taps & 1) && n_taps < (1 << 15) && pl.half >= pl.up;
+}
+
+// K: the final outputs of a stream that goes on and has emitted E stretched samples
+static long long ps_final(long long E, const PsPlan& pl) {
+  const long long a = E * pl.up - pl.half;
+  return a <= 0 ? 0 : (a + pl.down - 1) / pl.down;
+}
+
+// the first stretched sample that output K and those behind it reach (rs_jlo on the host)
+static long long ps_tail_start(long long K, const PsPlan& pl) {
+  const long long a = K * pl.down - pl.half;
+  return a <= 0 ? 0 : (a + pl.up - 1) / pl.up;
+}
+
+struct PsStream {
+  int open = 0, set = 0, tp = 1, tq = 1, rp = 1, rq = 1, n_taps = 0;
+  PsPlan pl = {1, 1, 1, 1, 0};
+  long long n = 0, f = 0, k = 0;   // input samples so far, frames emitted, final outputs emitted
+};
+struct smi_pitchs {
+  TsState s;
+  PsState ps;
+  int max_chunk, N, D, max_taps;
+  DevBuf<char> pool;
+  std::vector<PsStream> streams;
+  std::vector<float> stage;   // [max_streams][tslot]: what open copies to the device, kept until the slot is opened again
+};
+
+extern "C" {
+
+long long smi_pitchs_piece_len(int tp, int tq, int rp, int rq, int N, int D, int n_taps, long long n_before, long long frames_before,
+                               long long k_before, long long len, int last, long long* n_after, long long* frames_after,
+                               long long* k_after) {
+  PsPlan pl;
+  if (!ps_plan(tp, tq, rp, rq, N, D, n_taps, pl) || k_before < 0) return -1;
+  long long n = 0, f = 0;
+  if (smi_tempos_piece_len(pl.P, pl.Q, N, D, n_before, frames_before, len, last, &n, &f) < 0) return -1;
+  long long E, K;
+  if (last) {
+    E = (n * pl.Q + pl.P - 1) / pl.P;   // M
+    K = (n * tq + tp - 1) / tp;         // n_out
+    if (rs_out_len(E, pl.up, pl.down) < K) return -1;
+  } else {
+    E = pl.P == pl.Q ? n : f * (N / 2);
+    K = ps_final(E, pl);
+  }
+  if (K < k_before || E * pl.up >= (1LL << 31) || K * pl.down >= (1LL << 31)) return -1;
+  if (n_after) *n_after = n;
+  if (frames_after) *frames_after = f;
+  if (k_after) *k_after = K;
+  return K - k_before;
+}
+
+int smi_pitchs_create(int max_streams, int max_chunk, int N, int D, const double* win_host, int max_taps, smi_pitchs** out) {
+  SMI_REQUIRE(out, "smi_pitchs_create: null out");
+  *out = nullptr;
+  SMI_REQUIRE(max_streams >= 1 && max_streams <= JN_MAX_STREAMS, "smi_pitchs_create: max_streams=%d outside 1..%d", max_streams, JN_MAX_STREAMS);
+  SMI_REQUIRE(max_chunk >= 1 && max_chunk <= RS_MAX_SAMPLES, "smi_pitchs_create: max_chunk=%d outside 1..%d", max_chunk, RS_MAX_SAMPLES);
+  SMI_REQUIRE(N >= 16 && N <= TP_MAX_N && !(N & 1), "smi_pitchs_create: N=%d must be even in 16..%d", N, TP_MAX_N);
+  SMI_REQUIRE(D >= 0 && D <= TP_MAX_D, "smi_pitchs_create: D=%d outside 0..%d", D, TP_MAX_D);
+  SMI_REQUIRE(win_host, "smi_pitchs_create: null win_host");
+  SMI_REQUIRE(max_taps >= 0 && max_taps < RS_LDS_FLOATS, "smi_pitchs_create: max_taps=%d outside 0..%d", max_taps, RS_LDS_FLOATS - 1);
+  char arch[128];
+  const int rc = smi_device_check(arch, sizeof(arch));
+  if (rc) return rc;
+  smi_pitchs* h = new smi_pitchs();
+  h->max_chunk = max_chunk; h->N = N; h->D = D; h->max_taps = max_taps;
+  TsState& s = h->s;
+  PsState& ps = h->ps;
+  s.max_streams = max_streams;
+  s.hcap = ts_hist_cap(N, D);
+  s.fmax = (int)(4LL * ((long long)max_chunk + s.hcap) / (N / 2) + 4);   // frames one push can emit
+  ps.tslot = 4 + ((max_taps + 3) & ~3);
+  ps.tcap = max_taps + 1;   // E - rs_jlo(K down) <= 2 G / up < max_taps (include/sparkmi.h derives it)
+  // one allocation: the window (float64), then the history sets, the tail sets and the slots' taps (fp32), the two sets of places
+  // and the frames' work (int32)
+  const size_t f64 = (size_t)N * sizeof(double);
+  const size_t n_hist = 2 * (size_t)max_streams * s.hcap, n_tail = 2 * (size_t)max_streams * ps.tcap, n_taps = (size_t)max_streams * ps.tslot;
+  const size_t n_pos = 2 * (size_t)max_streams, n_work = (size_t)RS_MAX_ROWS * (s.fmax + 1);
+  const size_t bytes = f64 + (n_hist + n_tail + n_taps) * sizeof(float) + (n_pos + n_work) * sizeof(int32_t);
+  if (h->pool.alloc(bytes, "smi_pitchs_create: stream state")) {
+    (void)hipGetLastError();
+    delete h;
+    return SMI_ENOMEM;
+  }
+  s.win = (const double*)h->pool.get();
+  s.hist = (float*)(h->pool + f64);
+  ps.tail = s.hist + n_hist;
+  ps.taps = ps.tail + n_tail;
+  s.spos = (int32_t*)(ps.taps + n_taps);
+  s.work = s.spos + n_pos;
+  hipError_t e = hipMemset(h->pool, 0, bytes);
+  if (e == hipSuccess) e = hipMemcpy(h->pool, win_host, f64, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    smi_set_error("smi_pitchs_create: upload of the window: %s", hipGetErrorString(e));
+    delete h;
+    return SMI_EHIP;
+  }
+  h->streams.assign((size_t)max_streams, PsStream{});
+  h->stage.assign(n_taps, 0.f);
+  *out = h;
+  return SMI_OK;
+}
+
+int smi_pitchs_destroy(smi_pitchs* h) {
+  delete h;
+  return SMI_OK;
+}
+
+int smi_pitchs_open(smi_pitchs* h, int slot, int tp, int tq, int rp, int rq, const float* taps_host, int n_taps, void* stream) {
+  SMI_REQUIRE(h, "smi_pitchs_open: null handle");
+  SMI_REQUIRE(slot >= 0 && slot < h->s.max_streams, "smi_pitchs_open: slot=%d outside 0..%d", slot, h->s.max_streams - 1);
+  SMI_REQUIRE(tp >= 1 && tp <= 32767, "smi_pitchs_open: tp=%d outside 1..32767", tp);
+  SMI_REQUIRE(tq >= 1 && tq <= 32767, "smi_pitchs_open: tq=%d outside 1..32767", tq);
+  SMI_REQUIRE(rp >= 1 && rp <= 32767, "smi_pitchs_open: rp=%d outside 1..32767", rp);
+  SMI_REQUIRE(rq >= 1 && rq <= 32767, "smi_pitchs_open: rq=%d outside 1..32767", rq);
+  PtPlan bp;
+  SMI_REQUIRE(pt_plan(0, tp, tq, rp, rq, h->N, bp) && ts_args(bp.P, bp.Q, h->N, h->D),
+              "smi_pitchs_open: the stretch (tp rq) / (tq rp) = (%d * %d) / (%d * %d) must lie in 1/4..4 with terms up to 32767", tp, rq, tq, rp);
+  if (bp.up == 1 && bp.down == 1) {
+    SMI_REQUIRE(n_taps == 0, "smi_pitchs_open: n_taps=%d must be 0 for a stream whose pitch ratio is 1/1", n_taps);
+  } else {
+    SMI_REQUIRE(n_taps >= 3 && (n_taps & 1), "smi_pitchs_open: n_taps=%d must be odd and at least 3 (taps h[0 .. 2G], G >= 1) at rp/rq = %d/%d",
+                n_taps, rp, rq);
+    SMI_REQUIRE(taps_host, "smi_pitchs_open: null taps_host");
+    SMI_REQUIRE(n_taps <= h->max_taps, "smi_pitchs_open: n_taps=%d above the handle's max_taps=%d", n_taps, h->max_taps);
+    SMI_REQUIRE(n_taps / 2 >= bp.up, "smi_pitchs_open: n_taps=%d gives G=%d below up=%d: the final outputs could pass the stream's length", n_taps,
+                n_taps / 2, bp.up);
+    const long long fl = (long long)n_taps + rs_window(bp.up, bp.down, n_taps / 2);
+    SMI_REQUIRE(fl <= RS_LDS_FLOATS, "smi_pitchs_open: n_taps=%d with up/down = %d/%d needs %lld floats of LDS a tile, above %d", n_taps, bp.up,
+                bp.down, fl, RS_LDS_FLOATS);
+  }
+  PsPlan pl;
+  SMI_REQUIRE(ps_plan(tp, tq, rp, rq, h->N, h->D, n_taps, pl), "smi_pitchs_open: tp/tq = %d/%d, rp/rq = %d/%d, n_taps=%d give no plan", tp, tq, rp, rq,
+              n_taps);
+  float* st = h->stage.data() + (size_t)slot * h->ps.tslot;
+  const int32_t head[4] = {pl.up, pl.down, pl.half, 0};
+  memcpy(st, head, sizeof(head));
+  if (n_taps) memcpy(st + 4, taps_host, (size_t)n_taps * sizeof(float));
+  // behind the launches of the slot's earlier stream on this HIP stream, before this one's
+  SMI_HIP(hipMemcpyAsync(h->ps.taps + (size_t)slot * h->ps.tslot, st, (size_t)(4 + n_taps) * sizeof(float), hipMemcpyHostToDevice,
+                         (hipStream_t)stream));
+  PsStream& ss = h->streams[(size_t)slot];
+  ss.open = 1; ss.tp = tp; ss.tq = tq; ss.rp = rp; ss.rq = rq; ss.n_taps = n_taps; ss.pl = pl;
+  ss.n = 0; ss.f = 0; ss.k = 0;   // (ss.set goes on alternating: a first push reads no state)
+  return SMI_OK;
+}
+
+int smi_pitchs_push_rows(smi_pitchs* h, const float* in_dev, long long stride, const int32_t* stream_host, const int32_t* len_host,
+                         const int32_t* last_host, int B, int32_t* pos_dev, long long pos_stride, float* out_dev, long long out_stride,
+                         int32_t* n_out_host, void* stream) {
+  SMI_REQUIRE(h && in_dev && stream_host && len_host && last_host && out_dev, "smi_pitchs_push_rows: null argument");
+  SMI_REQUIRE(B >= 1 && B <= RS_MAX_ROWS, "smi_pitchs_push_rows: B=%d outside 1..%d", B, RS_MAX_ROWS);
+  SMI_REQUIRE(stride >= 1, "smi_pitchs_push_rows: stride=%lld must be positive", stride);
+  const TsState& s = h->s;
+  const int H = h->N / 2;
+  TsArgs A;
+  PsArgs F;
+  long long n_new[RS_MAX_ROWS], f_new[RS_MAX_ROWS], k_new[RS_MAX_ROWS], piece[RS_MAX_ROWS], need = 1, need_pos = 1;
+  size_t lds = 0;
+  for (int b = 0; b < B; ++b) {
+    const int id = stream_host[b];
+    SMI_REQUIRE(id >= 0 && id < s.max_streams, "smi_pitchs_push_rows: stream[%d]=%d outside 0..%d", b, id, s.max_streams - 1);
+    for (int c = 0; c < b; ++c)
+      SMI_REQUIRE(stream_host[c] != id, "smi_pitchs_push_rows: stream[%d]=%d is row %d's stream too (one chunk of a stream a call)", b, id, c);
+    const PsStream& st = h->streams[(size_t)id];
+    const PsPlan& pl = st.pl;
+    SMI_REQUIRE(st.open, "smi_pitchs_push_rows: stream[%d]=%d is not open (smi_pitchs_open; a stream closes with its last chunk)", b, id);
+    const int len = len_host[b], last = last_host[b];
+    SMI_REQUIRE(last == 0 || last == 1, "smi_pitchs_push_rows: last[%d]=%d is neither 0 nor 1", b, last);
+    SMI_REQUIRE(len >= 0 && len <= h->max_chunk && len <= stride, "smi_pitchs_push_rows: len[%d]=%d outside 0..min(max_chunk=%d, stride=%lld)", b,
+                len, h->max_chunk, stride);
+    SMI_REQUIRE(st.n + len <= TS_MAX_N, "smi_pitchs_push_rows: stream[%d]=%d would reach %lld samples: 2^28 is the limit of a stream", b, id,
+                st.n + len);
+    piece[b] = smi_pitchs_piece_len(st.tp, st.tq, st.rp, st.rq, h->N, h->D, st.n_taps, st.n, st.f, st.k, len, last, &n_new[b], &f_new[b], &k_new[b]);
+    SMI_REQUIRE(piece[b] >= 0,
+                "smi_pitchs_push_rows: len[%d]=%d gives no valid piece (E up or K down would reach 2^31, or the stretched stream resamples "
+                "to fewer samples than the stream's length)", b, len);
+    const bool copy = pl.P == pl.Q, plain = pl.up == 1 && pl.down == 1;
+    const long long h0_old = copy ? st.n : ts_hist_start(st.f, pl.P, pl.Q, H, h->D);
+    const long long h0_new = last ? -1 : copy ? n_new[b] : ts_hist_start(f_new[b], pl.P, pl.Q, H, h->D);
+    const long long e_new = last ? (n_new[b] * pl.Q + pl.P - 1) / pl.P : copy ? n_new[b] : f_new[b] * H;
+    SMI_REQUIRE(f_new[b] - st.f <= s.fmax, "smi_pitchs_push_rows: len[%d]=%d makes %lld frames final, the handle holds %d a push", b, len,
+                f_new[b] - st.f, s.fmax);
+    SMI_REQUIRE(last || (h0_new >= h0_old && n_new[b] - h0_new <= s.hcap),
+                "smi_pitchs_push_rows: stream[%d]=%d needs %lld samples of history, the handle keeps %d", b, id, n_new[b] - h0_new, s.hcap);
+    SMI_REQUIRE(last || plain || e_new - ps_tail_start(k_new[b], pl) <= h->ps.tcap,
+                "smi_pitchs_push_rows: stream[%d]=%d needs %lld stretched samples of tail, the handle keeps %d", b, id,
+                e_new - ps_tail_start(k_new[b], pl), h->ps.tcap);
+    TsRow& r = A.r[b];
+    r.slot = id; r.set = st.set; r.len = len; r.p = pl.P; r.q = pl.Q;
+    r.n_old = (int32_t)st.n; r.n_new = (int32_t)n_new[b]; r.f_old = (int32_t)st.f; r.f_new = (int32_t)f_new[b];
+    r.m_new = (int32_t)e_new;
+    r.h0_old = (int32_t)h0_old; r.h0_new = (int32_t)h0_new;
+    F.r[b].k_old = (int32_t)st.k; F.r[b].k_new = (int32_t)k_new[b];
+    if (!plain) {
+      const size_t fl = (size_t)st.n_taps + (size_t)rs_window(pl.up, pl.down, pl.half);   // <= RS_LDS_FLOATS: checked at open
+      if (fl > lds) lds = fl;
+    }
+    if (piece[b] > need) need = piece[b];
+    if (f_new[b] - st.f > need_pos) need_pos = f_new[b] - st.f;
+  }
+  SMI_REQUIRE(out_stride >= need && out_stride <= TP_MAX_OUT, "smi_pitchs_push_rows: out_stride=%lld outside %lld (the longest piece)..%d",
+              out_stride, need, TP_MAX_OUT);
+  SMI_REQUIRE(!pos_dev || (pos_stride >= need_pos && pos_stride <= TP_MAX_OUT),
+              "smi_pitchs_push_rows: pos_stride=%lld outside %lld (the most frames of a piece)..%d", pos_stride, need_pos, TP_MAX_OUT);
+  {
+    const char* i0 = (const char*)in_dev;
+    const char* i1 = i0 + (size_t)B * stride * sizeof(float);
+    const char* o0 = (const char*)out_dev;
+    const char* o1 = o0 + (size_t)B * out_stride * sizeof(float);
+    SMI_REQUIRE(i1 <= o0 || o1 <= i0, "smi_pitchs_push_rows: out_dev overlaps in_dev");
+    const char* p0 = h->pool.get();
+    const char* p1 = p0 + h->pool.bytes();
+    SMI_REQUIRE(p1 <= o0 || o1 <= p0, "smi_pitchs_push_rows: out_dev overlaps the handle's state");
+  }
+  for (int b = 0; b < B; ++b) {
+    PsStream& st = h->streams[(size_t)stream_host[b]];
+    if (n_out_host) n_out_host[b] = (int32_t)piece[b];
+    st.n = n_new[b]; st.f = f_new[b]; st.k = k_new[b]; st.set ^= 1;
+    if (last_host[b]) st.open = 0;
+  }
+  hipStream_t hs = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_tempos_search, dim3(B), dim3(TP_BLOCK), 0, hs, A, s, h->N, h->D, in_dev, stride, pos_dev, pos_stride);
+  SMI_LAUNCH_CHECK();
+  const int tiles = (int)((out_stride + RS_TILE - 1) / RS_TILE);
+  hipLaunchKernelGGL(k_pitchs_ola, dim3(tiles, B), dim3(RS_BLOCK), lds * sizeof(float), hs, A, F, s, h->ps, h->N, in_dev, stride, out_dev,
+                     out_stride);
   SMI_LAUNCH_CHECK();
   return SMI_OK;
 }

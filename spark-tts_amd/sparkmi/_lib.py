@@ -277,6 +277,13 @@ SYMBOLS = {
                                   C.c_longlong, _P(C.c_int32), _VP]),
     "smi_tempos_piece_len": (C.c_longlong, [_I, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, _I, _P(C.c_longlong),
                                             _P(C.c_longlong)]),
+    "smi_pitchs_create": (_I, [_I, _I, _I, _I, _P(C.c_double), _I, _P(_VP)]),
+    "smi_pitchs_destroy": (_I, [_VP]),
+    "smi_pitchs_open": (_I, [_VP, _I, _I, _I, _I, _I, _P(C.c_float), _I, _VP]),
+    "smi_pitchs_push_rows": (_I, [_VP, _VP, C.c_longlong, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _I, _VP, C.c_longlong, _VP,
+                                  C.c_longlong, _P(C.c_int32), _VP]),
+    "smi_pitchs_piece_len": (C.c_longlong, [_I, _I, _I, _I, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _I,
+                                            _P(C.c_longlong), _P(C.c_longlong), _P(C.c_longlong)]),
     "smi_louds_create": (_I, [_I, _I, _I, _P(C.c_double), _I, _P(_VP)]),
     "smi_louds_destroy": (_I, [_VP]),
     "smi_louds_open": (_I, [_VP, _I, C.c_double, C.c_double, C.c_double, C.c_double]),

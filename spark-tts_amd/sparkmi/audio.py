@@ -29,6 +29,9 @@ stream, and the pieces' concatenation is ``tempo_rows`` of the whole stream bit 
 ``DeviceAudio.pitch_rows`` (``smi_pitch_rows``) moves the pitch of rows at an unchanged -- or, with a tempo, separately chosen --
 length: that stretch at (tp rq) / (tq rp), then the resampler's sum at rq / rp inside the same launch and a cut; the device is
 held to ``tests/pitch_ref.py`` bit for bit.  ``pitch_ratio`` gives the frequency ratio of a number of semitones.
+``StreamPitch`` (``smi_pitchs_*``) is its streaming form, in ``StreamTempo``'s place: the stretch's state and the tail of the
+stretched signal the resampler still reaches are kept on the device per stream, with the stream's taps, and the pieces'
+concatenation is ``pitch_rows`` of the whole stream bit for bit, whatever the chunking.
 
 ``StreamLoudness`` (``smi_louds_*``) levels joined streams while they arrive.  It is not ``loudness_rows`` chunk by chunk: the gain
 follows the running integrated loudness, knot by knot on the stream's absolute hops, at a bounded rate and under the ceiling.
@@ -870,6 +873,170 @@ class StreamTempo:
             for key, length, last in rows[a:b]:
                 st = self._open[key]
                 _, st[3], st[4] = tempo_piece_len(st[1], st[2], self.N, self.D, st[3], st[4], length, last)
+                if last:
+                    self._free.append(self._open.pop(key)[0])
+        if not self._fake:
+            assert got_all == want, (got_all, want)
+        return (out, want, pos, nf) if return_places else (out, want)
+
+    def _stream(self) -> C.c_void_p:
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+PITCH_STREAM_TAPS = 3981    # the longest filter of a hundredth ratio (199/100): what a ``StreamPitch`` slot holds by default
+
+
+class StreamPitch:
+    """Owns one ``smi_pitchs`` handle (include/sparkmi.h): the pitch of joined streams is moved, with a tempo in the same stretch
+    pass, while they are still arriving -- ``StreamTempo``'s state at the stretch (tp rq) / (tq rp) plus the tail of the stretched
+    signal the resampler's next outputs still reach, kept on the device per stream, so that the concatenation of a stream's
+    pieces is, bit for bit, ``DeviceAudio.pitch_rows`` of its whole input, whatever the chunking.  The twin of ``StreamTempo``:
+    ``open(key, tempo=(p, q), pitch=(rp, rq))`` takes a free slot and hands the slot the ratio's taps (``resample_taps(up,
+    down)`` rounded to fp32 once), ``push`` sends one poll's chunks, and a key's slot is free again after its last push.  A key
+    that ``push`` meets unopened is opened at 1/1 and 1/1, which copies its chunks with no latency; a key at the pitch ratio
+    1/1 is ``StreamTempo``'s stream bit for bit.  ``frame`` = (N, D) (``tempo_frame``); ``max_taps``: the longest filter a
+    stream may bring.  ``history`` and ``max_chunk`` bound a push's piece (``longest``).  All opens and pushes go to the
+    current HIP stream at the time of the call: keep them on one stream.  ``lib``: a stand-in library (tests watch the
+    bookkeeping)."""
+
+    def __init__(self, max_streams: int, max_chunk: int, frame: Tuple[int, int], max_taps: int = PITCH_STREAM_TAPS, device="cuda:0",
+                 diag: bool = False, lib=None):
+        from .streaming import tempo_history
+        self._lib = lib if lib is not None else _lib.pick(diag)
+        self._fake = lib is not None
+        self.device = device
+        if not self._fake:
+            import torch
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise _lib.SparkMIError("StreamPitch runs on an MI355X only (device must be cuda:N); there is no CPU path")
+        self.max_streams, self.max_chunk, self.max_taps = int(max_streams), int(max_chunk), int(max_taps)
+        self.N, self.D = int(frame[0]), int(frame[1])
+        self.history = tempo_history(self.N, self.D)
+        win = np.ascontiguousarray(tempo_window(self.N), dtype=np.float64)
+        self._h = C.c_void_p()
+        self._lib.check(self._lib.smi_pitchs_create(self.max_streams, self.max_chunk, self.N, self.D,
+                                                    win.ctypes.data_as(C.POINTER(C.c_double)), self.max_taps, C.byref(self._h)),
+                        "smi_pitchs_create")
+        self._free: List[int] = list(range(self.max_streams))   # (open() hands out the lowest free slot)
+        self._open: dict = {}       # key -> [slot, tp, tq, rp, rq, taps, n, frames emitted, outputs emitted]
+        self._taps: dict = {}       # (up, down) -> the fp32 taps, built once
+        self.calls = 0              # smi_pitchs_push_rows calls so far: two launches each
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.smi_pitchs_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """forget every open key (an abandoned stream's slots come back)"""
+        self._free = list(range(self.max_streams))
+        self._open = {}
+
+    def slot(self, key) -> Optional[int]:
+        return self._open[key][0] if key in self._open else None
+
+    def longest(self) -> int:
+        """what a push emits at most, whatever the streams' ratios: the stretch's longest piece (include/sparkmi.h, tempo of
+        joined streams), resampled by at most 2 in the pipeline's range of ratios, and the stretched tail behind it"""
+        return 2 * (4 * (self.history + self.max_chunk) + self.N) + self.max_taps + 2
+
+    def open(self, key, tempo: Tuple[int, int] = (1, 1), pitch: Tuple[int, int] = (1, 1)) -> int:
+        from .streaming import pitch_plan
+        if key in self._open:
+            raise ValueError(f"request {key}: already open")
+        if not self._free:
+            raise ValueError(f"StreamPitch: all {self.max_streams} stream slots are in use")
+        tp, tq, rp, rq = int(tempo[0]), int(tempo[1]), int(pitch[0]), int(pitch[1])
+        _, _, up, down = pitch_plan(tp, tq, rp, rq)
+        taps = None
+        if (up, down) != (1, 1):
+            if (up, down) not in self._taps:
+                self._taps[(up, down)] = np.ascontiguousarray(resample_taps(up, down).astype(np.float32))
+            taps = self._taps[(up, down)]
+        s = min(self._free)
+        self._lib.check(self._lib.smi_pitchs_open(self._h, s, tp, tq, rp, rq,
+                                                  None if taps is None else taps.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  0 if taps is None else int(taps.size), None if self._fake else self._stream()),
+                        "smi_pitchs_open")
+        self._free.remove(s)
+        self._open[key] = [s, tp, tq, rp, rq, 0 if taps is None else int(taps.size), 0, 0, 0]
+        return s
+
+    def _step(self, st, length, last) -> int:
+        """one push of ``length`` samples through the counters ``st`` (changed in place): its piece's length"""
+        from .streaming import pitch_piece_len
+        piece, st[6], st[7], st[8] = pitch_piece_len(st[1], st[2], st[3], st[4], self.N, self.D, st[5], st[6], st[7], st[8], length, last)
+        return piece
+
+    def _walk(self, rows: Sequence[Tuple]) -> List[Tuple]:
+        """per row (piece length, frames made final, the counters after it): the pushes in order over a copy of the counters,
+        so the frames are walked once a push"""
+        state = {k: list(v) for k, v in self._open.items()}
+        out = []
+        for key, length, last in rows:
+            st = state.setdefault(key, [None, 1, 1, 1, 1, 0, 0, 0, 0])
+            f0 = st[7]
+            piece = self._step(st, length, last)
+            out.append((piece, st[7] - f0, tuple(st[6:9])))
+        return out
+
+    def piece_lengths(self, rows: Sequence[Tuple]) -> List[int]:
+        """the piece lengths ``push(x, rows)`` would return, without pushing (pure host arithmetic)"""
+        return [w[0] for w in self._walk(rows)]
+
+    def push(self, x, rows: Sequence[Tuple], return_places: bool = False):
+        """``x``: [B][stride] float32 on the device, row b the new samples of request ``rows[b] = (key, length, last)``.
+        Returns (out [B][out_stride] float32 on the device -- row b holds its piece, then zeros --, the pieces' lengths); a
+        length may be 0.  ``return_places``: also (pos [B][frames] int32 on the device, the places of the stretch's frames each
+        push made final, and their counts).  A request that appears twice makes two device calls (``streaming.split_calls``),
+        each two launches; everything is enqueued on the current stream, nothing waits and nothing is copied back."""
+        from .streaming import split_calls
+        B = len(rows)
+        if not B:
+            raise ValueError("push takes at least one row")
+        if not self._fake:
+            import torch
+            if x.dim() != 2 or x.shape[0] != B or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+                raise ValueError("push takes a contiguous [B][stride] float32 tensor on the device, one row per chunk")
+        for _, length, _ in rows:
+            if not 0 <= int(length) <= self.max_chunk:
+                raise ValueError(f"a chunk of {length} samples is outside 0..max_chunk={self.max_chunk}")
+        walk = self._walk(rows)              # raises for a bad length before anything is opened or pushed
+        want, nf = [w[0] for w in walk], [w[1] for w in walk]
+        for key, _, _ in rows:
+            if key not in self._open:
+                self.open(key)
+        stride, pstride = max(1, max(want)), max(1, max(nf))
+        in_stride = 1 if self._fake else int(x.shape[1])
+        out = pos = None
+        if not self._fake:
+            out = torch.empty((B, stride), dtype=torch.float32, device=self.device)
+            if return_places:
+                pos = torch.empty((B, pstride), dtype=torch.int32, device=self.device)
+        got_all: List[int] = []
+        for a, b in split_calls([r[0] for r in rows]):
+            n = b - a
+            i32 = lambda v: (C.c_int32 * n)(*[int(t) for t in v])   # noqa: E731
+            got = (C.c_int32 * n)()
+            src = C.c_void_p(0 if self._fake else x.data_ptr() + 4 * a * in_stride)
+            dst = C.c_void_p(0 if self._fake else out.data_ptr() + 4 * a * stride)
+            pdst = C.c_void_p(0 if pos is None else pos.data_ptr() + 4 * a * pstride)
+            self._lib.check(self._lib.smi_pitchs_push_rows(self._h, src, in_stride, i32(self._open[r[0]][0] for r in rows[a:b]),
+                                                           i32(r[1] for r in rows[a:b]), i32(bool(r[2]) for r in rows[a:b]), n, pdst,
+                                                           pstride, dst, stride, got, None if self._fake else self._stream()),
+                            "smi_pitchs_push_rows")
+            self.calls += 1
+            got_all += list(got)
+            for (key, _, last), w in zip(rows[a:b], walk[a:b]):
+                self._open[key][6:9] = w[2]
                 if last:
                     self._free.append(self._open.pop(key)[0])
         if not self._fake:

@@ -17,7 +17,9 @@ utterances (the output at a programme loudness after BS.1770, measured and scale
 ``limiter`` on the calls that return whole utterances (a look-ahead true-peak limiter behind the loudness stage, on the device)
 and ``stream_limiter``, with ``joined=True``, on the two streaming calls (the same limiter with its input carried across the chunks);
 ``pitch_shift`` on the calls that return whole utterances (semitones for any voice, in the tempo stage's place: one stretch pass
-serves both, a resampler follows inside the same launch; the streaming calls refuse it).
+serves both, a resampler follows inside the same launch; the streaming calls refuse it) and ``stream_pitch_shift``, with
+``joined=True``, on the two streaming calls (the same arithmetic with the stretch's state and the resampler's tail carried across
+the chunks, in the tempo stream's place).
 """
 from __future__ import annotations
 
@@ -72,6 +74,9 @@ TEMPO_KEY = "tempo"
 # request key: the request's own pitch shift in semitones (-12.0 .. 12.0; > 0: higher); it overrides the call's ``pitch_shift``
 # (``pitch`` is taken: the label argument of voice creation)
 PITCH_SHIFT_KEY = "pitch_shift"
+# request key of serve_stream(joined=True): the request's own pitch shift on the stream, in semitones; it overrides the call's
+# ``stream_pitch_shift``
+STREAM_PITCH_SHIFT_KEY = "stream_pitch_shift"
 
 
 def _stream_pacing(max_batch: int, max_open=None, max_ahead=None, resume_ahead=None):
@@ -364,26 +369,36 @@ class SparkTTS:
 
     def _stream_stages(self, who: str, output_sample_rate: Optional[int], max_streams: int, audio_chunk_duration: float,
                        max_audio_chunk_duration: float, audio_chunk_size_scale_factor: float, audio_chunk_overlap_duration: float,
-                       loudness: bool = False, limiter: Optional[Tuple[float, float]] = None):
-        """The stages of a ``joined=True`` call with a tempo, a loudness or a streaming limiter, in the batch path's order, their
-        slots all free: (the crossfade -- a ``StreamJoiner`` at 1/1 --, the ``StreamTempo``, with ``loudness`` the
+                       loudness: bool = False, limiter: Optional[Tuple[float, float]] = None, pitch: bool = False):
+        """The stages of a ``joined=True`` call with a tempo, a pitch shift, a loudness or a streaming limiter, in the batch path's
+        order, their slots all free: (the crossfade -- a ``StreamJoiner`` at 1/1 --, the ``StreamTempo`` or, with ``pitch``, the
+        ``StreamPitch`` that takes its place (one stretch pass serves both), with ``loudness`` the
         ``StreamLoudness``, else None, with ``limiter`` = (lookahead_ms, release_ms) the ``StreamLimiter``, else None, and with
         ``output_sample_rate`` the resampler with state -- a second ``StreamJoiner`` with overlap 0 at that ratio, which is
         plain concatenation plus the filter --, else None).  Every stage's ``max_chunk`` is the longest piece the stage before it
         can emit.  Everything is checked before any device call."""
-        from .audio import StreamJoiner, StreamLimiter, StreamLoudness, StreamTempo, tempo_frame
+        from .audio import StreamJoiner, StreamLimiter, StreamLoudness, StreamPitch, StreamTempo, tempo_frame
         out_ratio = self._output_ratio(output_sample_rate)
         fade = self._stream_joiner(who, None, max_streams, audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor,
                                    audio_chunk_overlap_duration)
         frame = tempo_frame(self.sample_rate)
         key = (int(max_streams), fade.max_chunk, frame)
-        if getattr(self, "_tempos", None) is None:
-            self._tempos = {}
-        if key not in self._tempos:
-            self._tempos[key] = StreamTempo(*key, device=self.device)
-        scale = self._tempos[key]
-        scale.reset()
-        longest = 4 * (scale.history + scale.max_chunk) + scale.N   # what a push of the tempo stage emits at most (include/sparkmi.h)
+        if pitch:
+            if getattr(self, "_pitchs", None) is None:
+                self._pitchs = {}
+            if key not in self._pitchs:
+                self._pitchs[key] = StreamPitch(*key, device=self.device)
+            scale = self._pitchs[key]
+            scale.reset()
+            longest = scale.longest()   # what a push of the pitch stage emits at most: the stretch's piece at up to two outputs a sample
+        else:
+            if getattr(self, "_tempos", None) is None:
+                self._tempos = {}
+            if key not in self._tempos:
+                self._tempos[key] = StreamTempo(*key, device=self.device)
+            scale = self._tempos[key]
+            scale.reset()
+            longest = 4 * (scale.history + scale.max_chunk) + scale.N   # what a push of the tempo stage emits at most (include/sparkmi.h)
         loud = None
         if loudness:
             key = (int(max_streams), longest)
@@ -413,6 +428,16 @@ class SparkTTS:
             rate = self._joiners[key]
             rate.reset()
         return fade, scale, loud, lim, rate
+
+    @staticmethod
+    def _open_scale(stage, key, rate: Optional[Tuple[int, int]], shift: Optional[Tuple[int, int]]) -> None:
+        """opens request ``key`` in stage 1: a ``StreamTempo`` at its tempo, or a ``StreamPitch`` at its tempo and pitch ratio
+        (the taps' copy is enqueued on the current stream: the one the pushes go to)"""
+        from .audio import StreamPitch
+        if isinstance(stage, StreamPitch):
+            stage.open(key, rate or (1, 1), shift or (1, 1))
+        else:
+            stage.open(key, *(rate or (1, 1)))
 
     def _staged_push(self, stages, x, rows: Sequence[Tuple]):
         """One poll's ready chunks ``rows[b] = (key, length, last)`` (``x`` [B][stride] on the device) through the stages of
@@ -662,6 +687,34 @@ class SparkTTS:
                              "behind it would need their state carried across chunk edges); the batch calls take it: inference / "
                              "inference_batch / serve / inference_long / inference_long_stream")
 
+    @staticmethod
+    def _stream_pitch_ratios(requests: Sequence[dict], stream_pitch_shift, first: int = 0) -> List[Optional[Tuple[int, int]]]:
+        """``_pitch_ratios`` for the streaming calls: a request's own ``stream_pitch_shift`` key, else the call's; values and
+        rounding are ``audio.pitch_ratio``'s, and the message names the streaming keyword"""
+        def one(v):
+            try:
+                return pitch_ratio(v)
+            except ValueError as e:
+                raise ValueError(str(e).replace("pitch_shift", "stream_pitch_shift", 1)) from None
+        if stream_pitch_shift is not None:
+            one(stream_pitch_shift)
+        out = []
+        for i, r in enumerate(requests):
+            t = r.get(STREAM_PITCH_SHIFT_KEY, stream_pitch_shift)
+            try:
+                pq = None if t is None else one(t)
+            except ValueError as e:
+                raise ValueError(f"request {first + i}: {e}") from None
+            out.append(None if pq == (1, 1) else pq)
+        return out
+
+    @staticmethod
+    def _no_stream_pitch_form(stream_pitch_shift, who: str) -> None:
+        if stream_pitch_shift is not None:
+            raise ValueError(f"{who}: stream_pitch_shift is not supported for overlapping chunks (the stretch and the resampler "
+                             "behind it carry state across chunk edges); pass joined=True for contiguous pieces at that pitch, or "
+                             "use pitch_shift on inference / inference_batch / serve / inference_long / inference_long_stream")
+
     def _tempo_rows(self, wav, n: Sequence[int], ratios: Sequence[Optional[Tuple[int, int]]], spans=None,
                     pitches: Optional[Sequence[Optional[Tuple[int, int]]]] = None):
         """Rows (or their ``spans``) at their tempos, on the device (``audio.DeviceAudio.tempo_rows``: two launches for all rows,
@@ -873,7 +926,7 @@ class SparkTTS:
                          peak_ceiling: float = PEAK_CEILING, max_gain_db: float = 20.0,
                          max_slew_db: float = 1.0, limiter: Optional[str] = None, stream_limiter: Optional[str] = None,
                          limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0,
-                         pitch_shift: Optional[float] = None) -> Iterator[np.ndarray]:
+                         pitch_shift: Optional[float] = None, stream_pitch_shift: Optional[float] = None) -> Iterator[np.ndarray]:
         """Yields float32 waveform chunks while the LLM is still generating, cut and overlapped as
         the reference's decoupled Triton model does (model.py:347-385; run.sh:53-56 defaults); join
         them with ``sparkmi.streaming.crossfade(chunks, int(overlap_duration * sample_rate))``
@@ -924,25 +977,37 @@ class SparkTTS:
 
         ``limiter`` is refused (ValueError), joined or not: that keyword names the limiter of whole utterances, which
         ``inference_batch`` has; the streaming form is asked for by ``stream_limiter``.  ``pitch_shift`` is refused (ValueError),
-        joined or not: the batch calls take it; its streaming form needs state that is not carried yet."""
+        joined or not: the batch calls take it; the streaming form is asked for by ``stream_pitch_shift``.
+
+        ``stream_pitch_shift`` (semitones, -12.0 .. 12.0; > 0: higher; values and rounding are ``audio.pitch_ratio``'s; None, 0 or
+        a value whose ratio comes out 1/1: nothing new is built or launched) needs ``joined=True``: the joined stream's pitch is
+        moved at unchanged length while it is still arriving (include/sparkmi.h, smi_pitchs_*; ``audio.StreamPitch``; DESIGN.md
+        4.1.10).  The stage takes the tempo stage's place: one stretch pass serves ``tempo`` and the pitch, and the loudness
+        stage, ``stream_limiter`` and ``output_sample_rate`` see the shifted stream.  The pieces' concatenation is, bit for bit,
+        ``DeviceAudio.pitch_rows`` of the concatenated pieces of the same call without it, whatever the chunking, and as long
+        as ``tempo`` alone makes it; a piece is the tempo stream's hold-back plus the filter's reach late and the last piece
+        brings the rest.  The formants move with the pitch.  With ``joined=False`` it is refused (ValueError)."""
         self._no_stream_limiter(limiter, "inference_stream")
         self._no_stream_pitch(pitch_shift, "inference_stream")
         if not joined:
+            self._no_stream_pitch_form(stream_pitch_shift, "inference_stream")
             self._no_stream_tempo(tempo, "inference_stream")
             self._no_stream_loudness(loudness, "inference_stream")
             self._no_stream_limiter_form(stream_limiter, "inference_stream")
             self._no_stream_rate(output_sample_rate, "inference_stream")
         rate = self._tempo_ratios([{}], tempo)[0]
+        shift = self._stream_pitch_ratios([{}], stream_pitch_shift)[0]
         target = self._loudness_targets([{}], loudness, peak_ceiling, max_gain_db)[0]
         self._check_slew(max_slew_db)
         mode = self._stream_limiter_mode({}, stream_limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
         stages = None
-        if joined and (rate is not None or target is not None or mode is not None):
+        if joined and (rate is not None or shift is not None or target is not None or mode is not None):
             stages = self._stream_stages("inference_stream", output_sample_rate, 1, *sched_args, loudness=target is not None,
-                                         limiter=None if mode is None else (limiter_lookahead_ms, limiter_release_ms))
+                                         limiter=None if mode is None else (limiter_lookahead_ms, limiter_release_ms),
+                                         pitch=shift is not None)
             joiner = stages[0]
-            stages[1].open(0, *(rate or (1, 1)))
+            self._open_scale(stages[1], 0, rate, shift)
             if stages[2] is not None:   # (with a limiter behind it the gain follows the target: the limiter holds the ceiling)
                 stages[2].open(0, target, max_gain_db, peak_ceiling if mode is None else NO_CEILING, max_slew_db)
                 self.last_loudness = None
@@ -1170,7 +1235,7 @@ class SparkTTS:
                      tempo: Optional[float] = None, loudness: Optional[float] = None, peak_ceiling: float = PEAK_CEILING,
                      max_gain_db: float = 20.0, max_slew_db: float = 1.0, limiter: Optional[str] = None,
                      stream_limiter: Optional[str] = None, limiter_lookahead_ms: float = 2.5, limiter_release_ms: float = 25.0,
-                     pitch_shift: Optional[float] = None):
+                     pitch_shift: Optional[float] = None, stream_pitch_shift: Optional[float] = None):
         """``serve`` and ``inference_stream`` at once (the reference's deployment: in-flight batching with the decoupled chunk loop
         answering every live request, run.sh:49-65, model.py:347-385): ``requests`` is an iterable of the dicts ``serve`` takes;
         yields ``(index, chunk_waveform, last)``, a request's chunks in order, cut and overlapped as ``inference_stream`` cuts
@@ -1252,10 +1317,24 @@ class SparkTTS:
 
         ``limiter`` and a request's own ``limiter`` key are refused (ValueError), joined or not: they name the limiter of whole
         utterances; the streaming form is asked for by ``stream_limiter``.  ``pitch_shift`` and a request's own ``pitch_shift``
-        key are refused (ValueError), joined or not: the batch calls take it."""
+        key are refused (ValueError), joined or not: the batch calls take it; the streaming form is asked for by
+        ``stream_pitch_shift``.
+
+        ``stream_pitch_shift`` and a request's own ``stream_pitch_shift`` key, which overrides it (semitones, -12.0 .. 12.0, as
+        ``audio.pitch_ratio`` rounds them; None, 0 or a ratio of 1/1 everywhere: nothing new is built or launched), need
+        ``joined=True``; without it they are refused (ValueError).  In a call that has a pitched request the pitch stage
+        (include/sparkmi.h, smi_pitchs_*; ``audio.StreamPitch``) takes the tempo stage's place for every
+        request: one stretch pass serves a request's tempo and pitch, and a request without a pitch goes through at the ratio
+        1/1, which is the tempo stream's bits (a copy with no latency where it has no tempo either).  Per request the pieces'
+        concatenation is, bit for bit, ``DeviceAudio.pitch_rows`` of its pieces without the shift, whoever else is live, with or
+        without parking: the state is keyed by request.  Loudness, ``stream_limiter`` and ``output_sample_rate`` see the shifted
+        stream; the ``Pacer`` goes on counting the lengths behind this stage.  Whether a call has the stage is settled when it
+        begins, as for ``tempo``; a request that brings a shift of its own from an iterator into a call without the stage is
+        refused (ValueError).  The formants move with the pitch."""
         self._no_stream_limiter(limiter, "serve_stream")
         self._no_stream_pitch(pitch_shift, "serve_stream")
         if not joined:
+            self._no_stream_pitch_form(stream_pitch_shift, "serve_stream")
             self._no_stream_tempo(tempo, "serve_stream")
             self._no_stream_loudness(loudness, "serve_stream")
             self._no_stream_limiter_form(stream_limiter, "serve_stream")
@@ -1263,6 +1342,8 @@ class SparkTTS:
         call_mode = self._stream_limiter_mode({}, stream_limiter, peak_ceiling, limiter_lookahead_ms, limiter_release_ms)
         modes: Dict[int, Optional[str]] = {}   # request index -> its streaming limiter's mode, None without one
         call_rate = self._tempo_ratios([{}], tempo)[0]
+        call_shift = self._stream_pitch_ratios([{}], stream_pitch_shift)[0]
+        shifts: Dict[int, Optional[Tuple[int, int]]] = {}   # request index -> its pitch shift as a frequency ratio (p, q), None without one
         call_target = self._loudness_targets([{}], loudness, peak_ceiling, max_gain_db)[0]
         self._check_slew(max_slew_db)
         rates: Dict[int, Tuple[int, int]] = {}   # request index -> its tempo as (p, q), (1, 1) without one
@@ -1270,16 +1351,18 @@ class SparkTTS:
 
         def checked(reqs):   # a request's keys, checked before it reaches the device
             for i, r in enumerate(reqs):
-                for k in (FORK_KEY,) + (() if joined else (TEMPO_KEY, LOUDNESS_KEY, STREAM_LIMITER_KEY)) + tuple(LOGPROB_KEYS):
+                staged_keys = (TEMPO_KEY, LOUDNESS_KEY, STREAM_LIMITER_KEY, STREAM_PITCH_SHIFT_KEY)
+                for k in (FORK_KEY,) + (() if joined else staged_keys) + tuple(LOGPROB_KEYS):
                     if k in r:
                         raise ValueError(f"request {i}: {k} is not supported by serve_stream" + (
-                            " with overlapping chunks; pass joined=True" if k in (TEMPO_KEY, LOUDNESS_KEY, STREAM_LIMITER_KEY) else ""))
+                            " with overlapping chunks; pass joined=True" if k in staged_keys else ""))
                 if r.get(LIMITER_KEY) is not None:
                     self._no_stream_limiter(r[LIMITER_KEY], f"request {i}: serve_stream")
                 if r.get(PITCH_SHIFT_KEY) is not None:
                     self._no_stream_pitch(r[PITCH_SHIFT_KEY], f"request {i}: serve_stream")
                 _request_seq(r, self._eos, self.model.cfg.vocab_size, f"request {i}")
                 rates[i] = self._tempo_ratios([r], tempo, i)[0] or (1, 1)
+                shifts[i] = self._stream_pitch_ratios([r], stream_pitch_shift, i)[0]
                 try:
                     targets[i] = self._loudness_targets([r], loudness, peak_ceiling, max_gain_db)[0]
                 except ValueError as e:
@@ -1289,12 +1372,14 @@ class SparkTTS:
                 yield r
 
         staged, leveled, limited = call_rate is not None, call_target is not None, call_mode is not None
+        pitched = call_shift is not None
         if isinstance(requests, (list, tuple)):   # a whole list is checked before anything runs
             for _ in checked(requests):
                 pass
             staged = staged or any(v != (1, 1) for v in rates.values())
             leveled = leveled or any(v is not None for v in targets.values())
             limited = limited or any(v is not None for v in modes.values())
+            pitched = pitched or any(v is not None for v in shifts.values())
         decode_stride = int(decode_stride)
         if decode_stride < 1:
             raise ValueError("decode_stride must be >= 1")
@@ -1316,9 +1401,10 @@ class SparkTTS:
                         audio_chunk_overlap_duration=audio_chunk_overlap_duration)
         sched_args = (audio_chunk_duration, max_audio_chunk_duration, audio_chunk_size_scale_factor, audio_chunk_overlap_duration)
         stages = None
-        if joined and (staged or leveled or limited):
+        if joined and (staged or pitched or leveled or limited):
             stages = self._stream_stages("serve_stream", output_sample_rate, max(int(max_open), self._max_batch), *sched_args,
-                                         loudness=leveled, limiter=(limiter_lookahead_ms, limiter_release_ms) if limited else None)
+                                         loudness=leveled, limiter=(limiter_lookahead_ms, limiter_release_ms) if limited else None,
+                                         pitch=pitched)
             joiner = stages[0]
             if leveled:
                 self.last_loudness = {}
@@ -1335,6 +1421,10 @@ class SparkTTS:
                 if stages is None and rates[i] != (1, 1):
                     raise ValueError(f"request {i}: a tempo of its own from an iterator of requests, in a serve_stream call that began "
                                      "without the tempo stages; pass the requests as a list, or a tempo for the call")
+                if not pitched and shifts[i] is not None:
+                    raise ValueError(f"request {i}: a stream_pitch_shift of its own from an iterator of requests, in a serve_stream "
+                                     "call that began without the pitch stage; pass the requests as a list, or a stream_pitch_shift "
+                                     "for the call")
                 if (stages is None or stages[2] is None) and targets[i] is not None:
                     raise ValueError(f"request {i}: a loudness of its own from an iterator of requests, in a serve_stream call that "
                                      "began without the loudness stage; pass the requests as a list, or a loudness for the call")
@@ -1452,7 +1542,8 @@ class SparkTTS:
                         live[slot] = [r[0], int(r[2]), 0]
                         mux.open(r[0], r[3])
                         if stages is not None:   # (host only; a request without a tempo copies through at 1/1)
-                            stages[1].open(r[0], *rates[r[0]])
+                            with torch.cuda.stream(vs):   # (a pitched request's taps travel on the stream its pushes go to)
+                                self._open_scale(stages[1], r[0], rates[r[0]], shifts[r[0]])
                             if stages[2] is not None:   # (host only; a request without a target is measured and copied)
                                 stages[2].open(r[0], targets[r[0]], max_gain_db, peak_ceiling if modes[r[0]] is None else NO_CEILING,
                                                max_slew_db)

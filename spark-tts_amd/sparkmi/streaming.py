@@ -13,7 +13,9 @@ requests at once -- the decoupled chunk loop answering every live request of an 
 ``SparkTTS.serve_stream`` drives it.  ``join_piece_len``, ``join_history`` and ``split_calls`` are the host arithmetic of the
 device-side stream joiner (``joined=True``; include/sparkmi.h, smi_join_*), which does on the device what ``crossfade`` does here;
 ``tempo_piece_len``, ``tempo_ready``, ``tempo_history_start`` and ``tempo_history`` are that of the tempo stage behind it
-(smi_tempos_*): when a frame of a stream that is still arriving is final.
+(smi_tempos_*): when a frame of a stream that is still arriving is final; ``pitch_plan``, ``pitch_final``, ``pitch_tail_start``
+and ``pitch_piece_len`` are that of the pitch stage that takes its place (smi_pitchs_*): when an output of the resampler behind
+the stretch is final.
 """
 from __future__ import annotations
 
@@ -182,6 +184,60 @@ def tempo_piece_len(p: int, q: int, N: int, D: int, n_before: int, frames_before
     if piece < 0:
         raise ValueError(f"{frames_before} frames cannot have left a stream of {n} samples")
     return piece, n, f
+
+
+# ---- pitch shift of joined streams (include/sparkmi.h, smi_pitchs_*): when an output is final, as host arithmetic
+def pitch_plan(tp: int, tq: int, rp: int, rq: int) -> Tuple[int, int, int, int]:
+    """(P, Q, up, down): the stretch ``(tp rq) / (tq rp)`` and the resampling ``rq / rp`` of a tempo tp / tq and a pitch ratio
+    rp / rq, each in lowest terms"""
+    tp, tq, rp, rq = int(tp), int(tq), int(rp), int(rq)
+    if min(tp, tq, rp, rq) < 1 or max(tp, tq, rp, rq) > 32767:
+        raise ValueError(f"tempo {tp}/{tq} and pitch ratio {rp}/{rq} must have terms in 1..32767")
+    a, b = tp * rq, tq * rp
+    g, gr = math.gcd(a, b), math.gcd(rp, rq)
+    return a // g, b // g, rq // gr, rp // gr
+
+
+def pitch_final(E: int, up: int, down: int, half: int) -> int:
+    """K: the final outputs of a stream that goes on and has emitted ``E`` stretched samples, ``max(0, ceil((E up - G) / down))``"""
+    return max(0, -((-(int(E) * int(up) - int(half))) // int(down)))
+
+
+def pitch_tail_start(K: int, up: int, down: int, half: int) -> int:
+    """the first stretched sample that output ``K`` and those behind it reach: ``max(0, ceil((K down - G) / up))``"""
+    return max(0, -((-(int(K) * int(down) - int(half))) // int(up)))
+
+
+def pitch_piece_len(tp: int, tq: int, rp: int, rq: int, N: int, D: int, n_taps: int, n_before: int, frames_before: int, k_before: int,
+                    length: int, last: bool) -> Tuple[int, int, int, int]:
+    """(piece length, n after, frames after, outputs after) of one push -- the twin of ``smi_pitchs_piece_len``: the stretch is
+    a tempo stream at P / Q (``tempo_piece_len``) that has emitted E samples; a stream that goes on has emitted
+    ``pitch_final(E)`` outputs, a finished one ``ceil(n tq / tp)``.  ValueError for a bad argument."""
+    P, Q, up, down = pitch_plan(tp, tq, rp, rq)
+    n_taps, k_before = int(n_taps), int(k_before)
+    half = n_taps // 2
+    if (up, down) == (1, 1):
+        if n_taps:
+            raise ValueError(f"a stream at the pitch ratio 1/1 takes no taps, not {n_taps}")
+    elif n_taps < 3 or n_taps % 2 == 0 or n_taps >= 1 << 15 or half < up:
+        raise ValueError(f"{n_taps} taps: odd, at least 3 and G >= up = {up} at the pitch ratio {rp}/{rq}")
+    if k_before < 0:
+        raise ValueError("negative counter")
+    if int(n_before) > 1 << 28 or int(length) > 1 << 28:
+        raise ValueError("2^28 samples are the limit of a stream")
+    _, n, f = tempo_piece_len(P, Q, N, D, n_before, frames_before, length, last)
+    if last:
+        E, K = -((-n * Q) // P), -((-n * int(tq)) // int(tp))
+        if -((-E * up) // down) < K:
+            raise ValueError(f"the stretched stream resamples to fewer samples than the stream's length {K}")
+    else:
+        E = n if P == Q else f * (int(N) // 2)
+        K = pitch_final(E, up, down, half)
+    if K < k_before:
+        raise ValueError(f"{k_before} outputs cannot have left a stream of {n} samples")
+    if E * up >= 1 << 31 or K * down >= 1 << 31:
+        raise ValueError("E up or K down reaches 2^31: the limit of a stream")
+    return K - k_before, n, f, K
 
 
 # ---- loudness of joined streams (include/sparkmi.h, smi_louds_*): what a push emits, as host arithmetic
